@@ -11,11 +11,17 @@ independent, so N GPUs filter N x 64 pairs (weak scaling) with no collective on 
 carries a few scalar all-reduces (max time, checksum, check flags) and, with --distribution scatter, the
 batch scatter / gather around the timed region plus an extra pipelined scatter -> filter -> gather leg.
 
-Prints ONE JSON line on rank 0 (see the driver contract in the task statement):
+Prints ONE JSON line on rank 0:
   value     = whole-job filtered Mpixels/s (full-frame W*H per pair), max-over-ranks time
+  ms_per_step = milliseconds of one timed step (max over ranks)
   roofline  = dominant kernel (the Thomas-solve pass) priced in ALGORITHMIC bytes:
               (4+8R)*P bytes per launch / mean launch duration from HIP events on the launch stream
-  cpu_baseline = the CPU oracle (a port of the reference path) timed on this box's host cores
+  cpu_baseline = the CPU oracle (a port of the reference path) timed on the host cores (--full only)
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything else the benchmark
+measures or checks: the oracle check of the first and last pair, the CPU baseline, the extra legs (matchers -> filter,
+natural-image guide, down-scaled path, generic FGS, config-5 stream) and at N > 1 the RCCL data-path legs.
+--dump-outputs DIR writes what the last timed step computed (see dump_outputs()).
 
 Launching.  Under torch.distributed.run (RANK / WORLD_SIZE in the environment) this process IS a worker.
 A plain `python bench.py --gpus N` with N > 1 becomes a launcher instead: it starts N fresh worker
@@ -37,6 +43,9 @@ if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6300 GB/s is the measured copy ceiling
+# --dump-outputs: elements per dumped array.  Two float32 arrays plus a float64 index of the sample: 32 MB at most.
+DUMP_CAP = 1 << 21
+DUMP_SEED = 20241016
 
 
 def parse_args(argv=None):
@@ -75,7 +84,16 @@ def parse_args(argv=None):
     ap.add_argument("--launch-timeout", type=float, default=900.0,
                     help="self-launch: seconds before workers are stopped (below the driver's own limit, so that a hung "
                          "rendezvous is diagnosed here)")
-    return ap.parse_args(argv)
+    ap.add_argument("--full", action="store_true",
+                    help="also run the oracle check, the CPU baseline and every extra leg (off: the timed steps only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the filtered disparity and confidence maps of the last timed step (rank 0's pairs) as "
+                         "float32 .npy files under DIR; a batch above %d elements per array is sampled at fixed, "
+                         "seeded positions" % DUMP_CAP)
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ---------------------------------------------------------------------------------------------
@@ -283,6 +301,34 @@ def check_pairs(f, out, view, dl, dr, roi, radius, solver, which, threads):
     return ok, res
 
 
+def dump_outputs(d, out, f):
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files under `d`:
+    filtered_disparity.npy (the int16 maps, exact in float32) and confidence.npy (the LRC confidence maps; absent in a
+    dry run).  Up to DUMP_CAP elements per array the whole (pairs, H, W) batch is written; above it the same
+    DUMP_SEED-drawn sorted flat positions of both arrays, listed in sample_index.npy (float64, exact)."""
+    import numpy as np
+    import torch
+
+    os.makedirs(d, exist_ok=True)
+    n, H, W = out.shape
+    idx = None
+    if n * H * W > DUMP_CAP:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, n * H * W, DUMP_CAP))
+        np.save(os.path.join(d, "sample_index.npy"), idx.astype(np.float64))
+
+    def pick(t, offset):                                     # t: one array of `offset`-th pair (or the batch at 0)
+        if idx is None:
+            return t.cpu().numpy().astype(np.float32)
+        lo, hi = np.searchsorted(idx, [offset, offset + t.numel()])
+        sel = torch.from_numpy(idx[lo:hi] - offset).to(t.device)
+        return t.reshape(-1)[sel].cpu().numpy().astype(np.float32)
+
+    np.save(os.path.join(d, "filtered_disparity.npy"), pick(out, 0))
+    if f is not None:
+        conf = [pick(f.getConfidenceMap(k), k * H * W) for k in range(n)]
+        np.save(os.path.join(d, "confidence.npy"), np.stack(conf) if idx is None else np.concatenate(conf))
+
+
 def worker(args):
     # Libraries under us write to stdout (gloo's connection banner, RCCL with NCCL_DEBUG set): the one JSON line
     # goes to a private copy of the original stdout and everything else any library prints lands on stderr.
@@ -397,7 +443,7 @@ def worker(args):
 
     # ---- correctness of what is being timed: first and last pair of EVERY rank against the CPU oracle ----
     checked = None
-    if not args.no_check and not dry:
+    if args.full and not args.no_check and not dry:
         import oracle
         if rank == 0:
             oracle.build()            # one rank compiles the checker if its .so is stale; the others wait
@@ -435,10 +481,12 @@ def worker(args):
     prof = f.readProfile() if f is not None else {}
     if f is not None:
         f.enableProfiling(False)
+    if args.dump_outputs and rank == 0:                      # before any later call on f replaces its confidence maps
+        dump_outputs(args.dump_outputs, out, f)
 
     # ---- gather the filtered maps (outside the timed region), then the pipelined serving-shaped leg ----
     gather_ms, pipelined = None, None
-    if world > 1 and args.distribution == "scatter" and not dry:
+    if args.full and world > 1 and args.distribution == "scatter" and not dry:
         sync(); dist.barrier()
         t1 = time.perf_counter()
         full_out = parallel.gather_batch(out, n_total)
@@ -511,7 +559,7 @@ def worker(args):
 
     if dry and world > 1 and os.environ.get("ADF_BENCH_TEST_HANG_RANK") == str(rank):   # test hook: a transfer that never ends
         time.sleep(3600)
-    if world > 1 and args.distribution == "local" and args.rccl_legs == "auto":
+    if args.full and world > 1 and args.distribution == "local" and args.rccl_legs == "auto":
         legs = None
         try:
             if dry:
@@ -537,7 +585,7 @@ def worker(args):
         if line is not None:
             line["rccl_legs"] = legs
 
-    if rank == 0 and args.cpu_seconds > 0 and not dry:
+    if args.full and rank == 0 and args.cpu_seconds > 0 and not dry:
         try:
             ncpu = min(pairs, 2)
             cpu = cpu_baseline(view[:ncpu].cpu().numpy(), dl[:ncpu].cpu().numpy(), dr[:ncpu].cpu().numpy(), roi, radius,
@@ -553,7 +601,7 @@ def worker(args):
     if world > 1:
         dist.barrier()                                       # the other ranks wait here while rank 0 times the CPU port
 
-    if rank == 0 and world == 1 and args.matcher_pairs > 0 and not dry:
+    if args.full and rank == 0 and world == 1 and args.matcher_pairs > 0 and not dry:
         nd = max(16, (cfg["roi"][0] + 15) // 16 * 16)       # the config's ROI x is its numDisparities
         pipeline = {}
         for m, blk in (("bm", 15), ("sgbm", 3), ("bm_half", 7)):
@@ -564,14 +612,14 @@ def worker(args):
                 pipeline[m] = {"error": str(e)}
         line["views_to_filtered"] = pipeline
 
-    if rank == 0 and world == 1 and not dry and args.natural_pairs > 0:
+    if args.full and rank == 0 and world == 1 and not dry and args.natural_pairs > 0:
         try:
             line["natural_guide"] = natural_guide_leg(adf, torch, dev, dl, dr, roi, radius, ch, min(args.natural_pairs, pairs),
                                                       args.solver, not args.no_check)
         except Exception as e:                               # the extra leg must never cost the bench line
             line["natural_guide"] = {"error": str(e)}
 
-    if rank == 0 and world == 1 and not dry and args.next_rows > 0:
+    if args.full and rank == 0 and world == 1 and not dry and args.next_rows > 0:
         try:
             line["next_rows"] = next_rows_leg(adf, torch, dev, synthetic, cfg, W, H, ch, base_seed, min(args.next_rows, pairs),
                                               radius, not args.no_check)
@@ -931,7 +979,7 @@ def build_line(args, dry, world, backend, n_total, pairs, W, H, ch, roi, roi_kin
         "metric": "filtered Mpixels/s (+ achieved HBM GB/s) on 4K disparity, 1/2/4/8 GPUs vs CPU ref",
         "value": round(mpx, 2), "unit": "Mpixels/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
         "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": args.full,
         "config": {"workload": "BASELINE config %d: %d pairs/GPU of %dx%d, ROI %s (%s), depth-discontinuity radius %d, 8UC%d "
                                "guide, lambda 8000 sigma 1.5, 3 FGS iterations, LRC confidence on"
                                % (args.config, pairs, W, H, list(roi), roi_kind, radius, ch),

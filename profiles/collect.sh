@@ -9,7 +9,7 @@ tag=gpurun_out/${round}_${solver}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 rm -rf ${tag}_stats ${tag}_pmc_fetch ${tag}_pmc_write
 # 1. the bench line itself (with the CPU baseline leg)
-python3 bench.py --solver $solver --steps 10 --warmup 3 > ${tag}_bench_n1.json 2> ${tag}_bench_n1.err
+python3 bench.py --full --solver $solver --steps 10 --warmup 3 > ${tag}_bench_n1.json 2> ${tag}_bench_n1.err
 # 2. per-kernel durations of the same command (shorter run, no CPU leg)
 rocprofv3 --kernel-trace --stats -d ${tag}_stats -o stats --output-format csv -- python3 bench.py --solver $solver --steps 5 --warmup 2 --cpu-seconds 0 --no-check --matcher-pairs 0 --natural-pairs 0 --next-rows 0 > ${tag}_stats.log 2>&1
 # 3. HBM traffic: FETCH_SIZE and WRITE_SIZE in separate passes (8 pairs, one step, kernel trace only)

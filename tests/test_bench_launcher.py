@@ -19,7 +19,7 @@ def _clean_env():
 
 
 def test_self_launch_two_ranks_one_line():
-    p = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dry-run", "--steps", "3", "--warmup", "1", "--pairs", "2"],
+    p = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dry-run", "--full", "--steps", "3", "--warmup", "1", "--pairs", "2"],
                        cwd=ROOT, env=_clean_env(), capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -47,7 +47,7 @@ def test_self_launch_two_ranks_one_line():
 
 
 def test_rccl_legs_can_be_switched_off():
-    p = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dry-run", "--steps", "1", "--warmup", "0", "--rccl-legs", "off"],
+    p = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dry-run", "--full", "--steps", "1", "--warmup", "0", "--rccl-legs", "off"],
                        cwd=ROOT, env=_clean_env(), capture_output=True, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads(p.stdout.strip())
@@ -84,7 +84,7 @@ def test_worker_failure_propagates():
 def test_self_launch_eight_ranks_rehearsal():
     """BASELINE config 4's world size (8 ranks, one node) on gloo: eight workers, one line, eight identities, the
     data-path legs (7-peer point-to-point groups, 4 pipelined sub-batches) run and verify themselves."""
-    p = subprocess.run([sys.executable, BENCH, "--gpus", "8", "--dry-run", "--steps", "2", "--warmup", "1", "--pairs", "5"],
+    p = subprocess.run([sys.executable, BENCH, "--gpus", "8", "--dry-run", "--full", "--steps", "2", "--warmup", "1", "--pairs", "5"],
                        cwd=ROOT, env=_clean_env(), capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [ln for ln in p.stdout.splitlines() if ln.strip()]
@@ -120,7 +120,7 @@ def test_hung_extra_leg_prints_the_line_and_fails():
     and the job exits non-zero."""
     env = _clean_env()
     env.update(ADF_BENCH_TEST_HANG_RANK="1", ADF_BENCH_WATCHDOG_S="6")
-    p = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dry-run", "--steps", "1", "--warmup", "0", "--pairs", "2",
+    p = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dry-run", "--full", "--steps", "1", "--warmup", "0", "--pairs", "2",
                         "--launch-timeout", "120"],
                        cwd=ROOT, env=env, capture_output=True, text=True, timeout=600)
     assert p.returncode == 5, (p.returncode, p.stderr[-2000:])
@@ -128,3 +128,28 @@ def test_hung_extra_leg_prints_the_line_and_fails():
     assert len(lines) == 1, p.stdout
     d = json.loads(lines[0])
     assert d["extra_legs_hung"] is True and d["n_gpus"] == 2 and "watchdog" in d["rccl_legs"]
+
+
+def test_plain_run_times_the_steps_only_and_dumps_outputs(tmp_path):
+    """Without --full the line carries the timed steps only (no extra legs at N > 1); --dump-outputs writes rank 0's
+    last-step maps as float32, the same on every run with the same arguments."""
+    p = subprocess.run([sys.executable, BENCH, "--gpus", "2", "--dry-run", "--steps", "3", "--warmup", "1", "--pairs", "2"],
+                       cwd=ROOT, env=_clean_env(), capture_output=True, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-3000:]
+    d = json.loads(p.stdout.strip())
+    assert d["full"] is False and d["steps"] == 3 and d["ms_per_step"] > 0 and d["rccl_legs"] is None
+    assert d["cpu_baseline"] is None and d["checked"] is None and "extra_legs_hung" not in d
+    import numpy as np
+    dumps = []
+    for k in range(2):
+        out = tmp_path / str(k)
+        p = subprocess.run([sys.executable, BENCH, "--dry-run", "--steps", "2", "--warmup", "0", "--pairs", "3",
+                            "--dump-outputs", str(out)], cwd=ROOT, env=_clean_env(), capture_output=True, text=True, timeout=300)
+        assert p.returncode == 0, p.stderr[-3000:]
+        assert json.loads(p.stdout.strip())["steps"] == 2
+        dumps.append(np.load(out / "filtered_disparity.npy"))
+    assert dumps[0].dtype == np.float32 and dumps[0].shape == (3, 4, 4) and (dumps[0] == 1).all()
+    assert np.array_equal(dumps[0], dumps[1])
+    p = subprocess.run([sys.executable, BENCH, "--dry-run", "--steps", "0"], cwd=ROOT, env=_clean_env(),
+                       capture_output=True, text=True, timeout=300)
+    assert p.returncode != 0 and "--steps" in p.stderr
