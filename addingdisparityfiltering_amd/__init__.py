@@ -27,9 +27,11 @@ from .ximgproc import (  # noqa: F401
     createFastGlobalSmootherFilter,
     createRightMatcher,
     fastGlobalSmootherFilter,
+    filterSpeckles,
     releaseCachedMemory,
     getDisparityVis,
     readGT,
+    speckleWorkspaceBytes,
 )
 
 __version__ = "0.1.0"

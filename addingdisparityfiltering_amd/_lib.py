@@ -102,6 +102,9 @@ SYMBOLS = [
     ("adf_sgbm_get_disp12_max_diff", _i, [_vp, C.POINTER(_i)]),
     ("adf_sgbm_compute_device", _i, [_vp, _i, _vp, _pd, _pd, _vp, _pd, _pd, _i, _i, _i, _vp, _pd, _pd, _vp]),
     ("adf_sgbm_compute_host", _i, [_vp, _i, _vp, _pd, _pd, _vp, _pd, _pd, _i, _i, _i, _vp, _pd, _pd]),
+    ("adf_filter_speckles_workspace_bytes", _sz, [_i, _i, _i]),
+    ("adf_filter_speckles_device", _i, [_i, _vp, _pd, _pd, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
+    ("adf_filter_speckles_host", _i, [_i, _vp, _pd, _pd, _i, _i, _i, _i, _i]),
 ]
 
 _lib = None

@@ -16,6 +16,7 @@ SOURCES = {
     "resize_kernels.hip": [],
     "bm_matcher.hip": [],
     "sgbm_matcher.hip": [],
+    "speckle_kernels.hip": [],
 }
 HEADERS = ["adf_internal.h", "fgs_wave_common.h"]
 OUT = os.path.join(_HERE, "libadf_wls.so")

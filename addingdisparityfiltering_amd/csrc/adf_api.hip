@@ -1368,6 +1368,20 @@ hipError_t device_malloc(void** p, size_t bytes)
     if (e != hipSuccess) *p = nullptr;
     return e;
 }
+
+void* cache_take(int device, size_t need, hipStream_t st, size_t* bytes) { return BlockCache::get().take(device, need, st, bytes); }
+
+void cache_give(int device, void* p, size_t bytes, hipStream_t st)
+{
+    hipEvent_t ev = nullptr;
+    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess || hipEventRecord(ev, st) != hipSuccess) {
+        (void)hipGetLastError();                                     // no event: hand the block back idle
+        if (ev) hipEventDestroy(ev);
+        ev = nullptr;
+        hipStreamSynchronize(st);
+    }
+    BlockCache::get().give(device, p, bytes, ev);
+}
 } // namespace adf
 
 extern "C" void adf_release_cached_memory(void)

@@ -11,6 +11,7 @@ edge_filter.hpp (EF.hpp), over the C-ABI in include/adf_wls.h:
     DisparityWLSFilter.get*/set*                    DF.hpp:90-122
     createFastGlobalSmootherFilter(...)             EF.hpp:393
     fastGlobalSmootherFilter(...)                   EF.hpp:413
+    filterSpeckles(img, newVal, maxSpeckleSize, maxDiff, buf)   calib3d (outside the reference tree)
 
 Images are numpy arrays (host path: copied to the GPU and back) or torch CUDA
 tensors (device path: zero-copy, asynchronous on torch's current stream).  A
@@ -353,7 +354,8 @@ class StereoBM(StereoMatcher):
         if self.disp12MaxDiff >= 0 and self.disp12MaxDiff < 1000000:
             raise AdfError(_lib.ADF_EBADARG, "disp12MaxDiff (left-right check inside the matcher) is not implemented")
         if self.speckleWindowSize > 0:
-            raise AdfError(_lib.ADF_EBADARG, "speckle filtering is not implemented")
+            raise AdfError(_lib.ADF_EBADARG, "speckle filtering is not implemented inside compute(); "
+                                             "use filterSpeckles on the result")
         batched = len(left.shape) == 3
         L = _Image(left, np.uint8, "left", batched)
         R = _Image(right, np.uint8, "right", batched)
@@ -478,7 +480,8 @@ class StereoSGBM(StereoMatcher):
         if self.mode not in (StereoSGBM.MODE_SGBM, StereoSGBM.MODE_HH, StereoSGBM.MODE_SGBM_3WAY):
             raise AdfError(_lib.ADF_EBADARG, "mode must be StereoSGBM.MODE_SGBM, MODE_HH or MODE_SGBM_3WAY")
         if self.speckleWindowSize > 0:
-            raise AdfError(_lib.ADF_EBADARG, "speckle filtering is not implemented")
+            raise AdfError(_lib.ADF_EBADARG, "speckle filtering is not implemented inside compute(); "
+                                             "use filterSpeckles on the result")
         nd = len(left.shape)
         color = nd in (3, 4) and left.shape[-1] == 3      # (H,W,3) / (N,H,W,3); a batch of 3-pixel-wide gray images is not a case
         batched = nd == (4 if color else 3)
@@ -510,6 +513,64 @@ class StereoSGBM(StereoMatcher):
         else:
             _lib.check(lib.adf_sgbm_compute_host(*args))
         return disparity
+
+
+_INT32_MAX = 2 ** 31 - 1
+
+
+def _round_half_even(v, what):
+    """cvRound of a double argument (round half to even), as an int32 for the C-ABI."""
+    v = float(v)
+    if not math.isfinite(v):
+        raise AdfError(_lib.ADF_EBADARG, "%s must be finite" % what)
+    return int(round(v))
+
+
+def filterSpeckles(img, newVal, maxSpeckleSize, maxDiff, buf=None):
+    """cv::filterSpeckles (calib3d; in-tree call site modules/stereo/src/stereo_binary_sgbm.cpp:716-718): 4-connected
+    components of pixels != newVal whose neighbours differ by at most maxDiff; every component of at most
+    maxSpeckleSize pixels is set to newVal.  `img` is a CV_16SC1 map (H,W) or a batch (N,H,W), modified IN PLACE:
+    a torch CUDA tensor runs on the device, asynchronously on torch's current stream; a numpy array takes the host
+    entry point.  newVal and maxDiff are rounded half-to-even like cv's doubles (cvRound).  `buf` (device path only):
+    a CUDA tensor of at least speckleWorkspaceBytes(...) bytes used as the workspace -- the call then allocates
+    nothing and may be captured into a CUDA graph; None = the library's cached scratch.  Returns (img, buf) like
+    cv2.filterSpeckles.  Parity with calib3d is unpinned (include/adf_wls.h)."""
+    if img is None:
+        raise AdfError(_lib.ADF_EBADARG, "img is empty")
+    dt = img.dtype if _is_torch(img) else np.asarray(img).dtype
+    if dt == np.uint8 or (torch is not None and dt == torch.uint8):
+        raise AdfError(_lib.ADF_EBADARG, "filterSpeckles supports CV_16SC1 only (CV_8UC1 is not supported)")
+    nd = len(img.shape)
+    if nd not in (2, 3):
+        raise AdfError(_lib.ADF_EBADARG, "img must be (H,W) or a batch (N,H,W)")
+    im = _Image(img, np.int16, "img", nd == 3)
+    nv = _round_half_even(newVal, "newVal")
+    if not -32768 <= nv <= 32767:
+        raise AdfError(_lib.ADF_EBADARG, "newVal %r is outside the CV_16S range" % (newVal,))
+    md = max(-_INT32_MAX, min(_INT32_MAX, _round_half_even(maxDiff, "maxDiff")))   # (|diff| <= 65535 either way)
+    ms = max(-_INT32_MAX, min(_INT32_MAX, int(maxSpeckleSize)))                     # (W*H < 2^31 either way)
+    lib = _lib.lib()
+    args = [im.n, C.c_void_p(im.ptr), im.stride, im.pair_stride, im.w, im.h, nv, ms, md]
+    if not im.device:
+        _lib.check(lib.adf_filter_speckles_host(*args))
+        return img, buf
+    ws, ws_bytes = None, 0
+    if buf is not None:
+        if not (_is_torch(buf) and buf.is_cuda and buf.is_contiguous()):
+            raise AdfError(_lib.ADF_EBADARG, "buf must be a contiguous CUDA tensor (or None)")
+        if buf.device != img.device:
+            raise AdfError(_lib.ADF_EBADARG, "buf lives on %s, img on %s" % (buf.device, img.device))
+        ws, ws_bytes = C.c_void_p(buf.data_ptr()), buf.numel() * buf.element_size()
+        if ws_bytes < speckleWorkspaceBytes(im.n, im.h, im.w):
+            raise AdfError(_lib.ADF_ESIZE, "buf holds %d bytes; %d needed" % (ws_bytes, speckleWorkspaceBytes(im.n, im.h, im.w)))
+    with torch.cuda.device(img.device):
+        _lib.check(lib.adf_filter_speckles_device(*args, ws, ws_bytes, _stream_of(im)))
+    return img, buf
+
+
+def speckleWorkspaceBytes(n, H, W):
+    """Bytes of device workspace filterSpeckles needs for n maps of H x W (8 per pixel)."""
+    return int(_lib.lib().adf_filter_speckles_workspace_bytes(int(n), int(W), int(H)))
 
 
 def createDisparityWLSFilter(matcher_left):

@@ -336,9 +336,9 @@ int adf_bm_compute_host(adf_bm_t* h, int n_pairs,
  * CV_16SC1 with 4 fractional bits, invalid pixels (minDisparity-1)*16, matchable columns
  * [max(minDisparity+numDisparities,0), W+min(minDisparity,0)).  The class itself lives in OpenCV's calib3d (outside
  * the reference tree: parity unpinned); results are bit-exact against oracle/adf_oracle_sgbm.c and anchored on the
- * reference's own semi-global test (modules/stereo/test/test_block_matching.cpp:157-238).  Not implemented, and not
- * reachable from the filter (its factories switch it off): the speckle filter.  Limits: numDisparities <= 512,
- * blockSize odd <= 11. */
+ * reference's own semi-global test (modules/stereo/test/test_block_matching.cpp:157-238).  The matchers' own speckle
+ * filter (speckleWindowSize > 0) is not run by compute(), and the filter's factories switch it off anyway; the same
+ * step exists as the separate call adf_filter_speckles_* below.  Limits: numDisparities <= 512, blockSize odd <= 11. */
 #define ADF_SGBM_MODE_SGBM 0
 #define ADF_SGBM_MODE_HH 1
 #define ADF_SGBM_MODE_3WAY 2 /* StereoSGBM::MODE_SGBM_3WAY */
@@ -370,6 +370,34 @@ int adf_sgbm_compute_host(adf_sgbm_t* h, int n_pairs,
                           const uint8_t* right, ptrdiff_t right_stride, ptrdiff_t right_pair_stride,
                           int channels, int W, int H,
                           int16_t* disparity, ptrdiff_t disp_stride, ptrdiff_t disp_pair_stride);
+
+/* ---------------- speckle filter (cv::filterSpeckles) ----------------
+ * cv::filterSpeckles(img, newVal, maxSpeckleSize, maxDiff, buf) of OpenCV's calib3d, the step a StereoBM / StereoSGBM
+ * pipeline runs on the matcher's output; the in-tree call site is modules/stereo/src/stereo_binary_sgbm.cpp:716-718:
+ * filterSpeckles(disp, (minDisparity-1)*16, speckleWindowSize, 16*speckleRange, buffer).  Semantics:
+ *   - pixels equal to new_val belong to no component;
+ *   - 4-neighbours p, q are in one component when both differ from new_val and |d(p) - d(q)| <= max_diff (int32);
+ *   - every component of AT MOST max_speckle_size pixels is set to new_val; every other pixel keeps its value;
+ *   - max_speckle_size <= 0 changes nothing; a negative max_diff makes every pixel its own component.
+ * The result does not depend on how components are labelled: bit-exact against a sequential restatement and
+ * identical from run to run.  calib3d is outside the reference tree, so parity with it is UNPINNED; what OpenCV does
+ * when built with IPP is not known here.  cv's newVal and maxDiff are doubles: the C++ and Python layers round them
+ * half-to-even (cvRound) before they reach these ints.
+ * CV_16SC1 maps only (what both matchers produce; CV_8UC1 is not supported), n_maps equally sized maps `map_stride`
+ * bytes apart, modified IN PLACE.  new_val must lie in [-32768, 32767] (ADF_EBADARG); W*H must be below 2^31
+ * (int32 labels, ADF_ESIZE).
+ * workspace (cv's buf): device memory of at least adf_filter_speckles_workspace_bytes(n_maps, W, H) bytes (int32
+ * label + int32 count per pixel, 8 B/px), 4-byte aligned; with it the call allocates nothing and never synchronises,
+ * so it may be captured into a hipGraph.  NULL = scratch from the library's cache of device blocks, ordered on
+ * `stream` behind its previous user (no host synchronisation; the first call of a size allocates it; not capturable).
+ * _device: device pointers, asynchronous on `stream`, on the current HIP device.  _host: host pointers, copies,
+ * runs and synchronises. */
+size_t adf_filter_speckles_workspace_bytes(int n_maps, int W, int H);
+int adf_filter_speckles_device(int n_maps, int16_t* img, ptrdiff_t stride, ptrdiff_t map_stride, int W, int H,
+                               int new_val, int max_speckle_size, int max_diff,
+                               void* workspace, size_t workspace_bytes, void* stream);
+int adf_filter_speckles_host(int n_maps, int16_t* img, ptrdiff_t stride, ptrdiff_t map_stride, int W, int H,
+                             int new_val, int max_speckle_size, int max_diff);
 
 #ifdef __cplusplus
 }

@@ -86,6 +86,23 @@ inline ptrdiff_t mat_step(const Mat& m) { return (ptrdiff_t)m.step; }
 inline void mat_create(Mat& m, int rows, int cols, int depth, int cn) { m.create(rows, cols, depth, cn); }
 #endif
 
+// cv::filterSpeckles(img, newVal, maxSpeckleSize, maxDiff) of calib3d (outside the reference tree; parity unpinned, see
+// adf_filter_speckles_* in adf_wls.h) on a CV_16SC1 host Mat, in place, through the library's host entry.  newVal and
+// maxDiff are rounded half-to-even (cvRound) before they reach the C-ABI; CV_8UC1 is not supported.
+inline void filterSpeckles(Mat& img, double newVal, int maxSpeckleSize, double maxDiff)
+{
+    if (img.empty() || mat_depth(img) != D16S || mat_channels(img) != 1)
+        throw Exception(ADF_EBADARG, "filterSpeckles: img must be a non-empty CV_16SC1 image (CV_8UC1 is not supported)");
+    if (!(newVal >= -32768.5 && newVal <= 32767.5))                           // (NaN fails too)
+        throw Exception(ADF_EBADARG, "filterSpeckles: newVal is outside the CV_16S range");
+    const double nv = std::nearbyint(newVal);                                 // default rounding mode: half to even
+    if (nv < -32768.0 || nv > 32767.0) throw Exception(ADF_EBADARG, "filterSpeckles: newVal is outside the CV_16S range");
+    if (std::isnan(maxDiff)) throw Exception(ADF_EBADARG, "filterSpeckles: maxDiff is NaN");
+    const double md = std::fmin(std::fmax(std::nearbyint(maxDiff), -2147483647.0), 2147483647.0);
+    check(adf_filter_speckles_host(1, reinterpret_cast<int16_t*>(img.data), mat_step(img), 0, img.cols, img.rows,
+                                   (int)nv, maxSpeckleSize, (int)md));
+}
+
 namespace ximgproc {
 
 // DF.hpp:52-76
