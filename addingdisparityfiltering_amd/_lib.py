@@ -77,6 +77,7 @@ SYMBOLS = [
     ("adf_release_cached_memory", None, []),
     ("adf_weight_table_host", _i, [C.c_float, _vp, _i]),
     ("adf_fgs_get_device", _i, [_vp, C.POINTER(_i)]),
+    ("adf_fgs_get_solver", _i, [_vp, C.POINTER(_i)]),
     ("adf_fgs_filter_host", _i, [_vp, _vp, _pd, _vp, _pd, _i, _i]),
     ("adf_fgs_filter_device", _i, [_vp, _vp, _pd, _vp, _pd, _i, _i, _vp]),
     ("adf_compute_mse_host", _i, [_vp, _pd, _vp, _pd, _i, _i, C.POINTER(Rect), C.POINTER(_d)]),

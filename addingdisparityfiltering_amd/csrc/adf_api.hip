@@ -1391,6 +1391,7 @@ extern "C" void adf_release_cached_memory(void)
 }
 
 extern "C" int adf_fgs_get_device(const adf_fgs_t* f, int* device) { NEED_HANDLE(f); if (device) *device = f->device; return ADF_OK; }
+extern "C" int adf_fgs_get_solver(const adf_fgs_t* f, int* solver) { NEED_HANDLE(f); if (solver) *solver = f->solver; return ADF_OK; }
 
 extern "C" void adf_fgs_destroy(adf_fgs_t* f)
 {

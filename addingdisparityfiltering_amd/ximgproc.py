@@ -669,6 +669,12 @@ class FastGlobalSmootherFilter:
             except Exception:
                 pass
 
+    def getSolver(self):
+        """The solver this filter runs: SOLVER_WAVE only if it was asked for and the guide fits it (library extension)."""
+        v = C.c_int(-1)
+        _lib.check(_lib.lib().adf_fgs_get_solver(self._h, C.byref(v)))
+        return v.value
+
     def filter(self, src, dst=None):
         """EF.hpp:370, FGS.cpp:182-233.  A torch CUDA tensor is filtered where it is (asynchronously on
         torch's current stream) and a CUDA tensor is returned; anything else takes the host path."""

@@ -239,6 +239,9 @@ void adf_release_cached_memory(void);
 #define ADF_WEIGHT_TABLE_LEVELS (3 * 256 * 256)
 int adf_weight_table_host(float sigma_color, float* table, int levels);
 int adf_fgs_get_device(const adf_fgs_t* h, int* device);
+/* Solver the handle actually runs: the one asked for at creation, except that ADF_SOLVER_WAVE covers guides up to
+ * 8192 x 4352 (and at least 2 x 2) -- a larger or degenerate guide runs ADF_SOLVER_EXACT. */
+int adf_fgs_get_solver(const adf_fgs_t* h, int* solver);
 
 /* FastGlobalSmootherFilter::filter(src, dst) (EF.hpp:370, FGS.cpp:182-233).
  * src/dst: HOST pointers, same size as the guide, depth ADF_8U / ADF_16S / ADF_32F,

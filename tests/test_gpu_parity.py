@@ -222,6 +222,25 @@ def test_generic_fgs_api(adf, oracle, dt, cn, gch):
     assert got.dtype == src.dtype and np.array_equal(got, exp)
 
 
+@pytest.mark.parametrize("dt", [np.uint8, np.int16, np.float32], ids=["u8", "i16", "f32"])
+@pytest.mark.parametrize("cn", [1, 2, 3, 4])
+@pytest.mark.parametrize("h,w", [(3, 4097), (3, 8192), (2177, 40), (4352, 50)])
+def test_generic_fgs_exact_at_wave_bucket_limits(adf, oracle, h, w, dt, cn):
+    """The exact solver's generic path (transposed layout) at the shapes where the wave solver changes buckets -- the
+    two-wavefront rows and the half-strip columns -- and at the largest it takes: bit for bit the scalar order."""
+    rng = np.random.default_rng(h * 7 + w + cn)
+    guide = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
+    shape = (h, w) if cn == 1 else (h, w, cn)
+    if dt == np.float32: src = rng.normal(0, 1000, shape).astype(np.float32)
+    elif dt == np.int16: src = rng.integers(-32767, 32767, shape).astype(np.int16)
+    else: src = rng.integers(0, 256, shape).astype(np.uint8)
+    exp = oracle.fgs_filter(guide, src, 8000.0, 1.5, threads=8)
+    f = adf.createFastGlobalSmootherFilter(guide, 8000.0, 1.5, solver=adf.SOLVER_EXACT)
+    assert f.getSolver() == adf.SOLVER_EXACT
+    got = f.filter(src)
+    assert got.dtype == src.dtype and np.array_equal(got, exp), int((got != exp).sum())
+
+
 @pytest.mark.parametrize("dt,cn", [(np.uint8, 3), (np.int16, 1), (np.float32, 2)])
 def test_generic_fgs_device_pointers(adf, oracle, dt, cn):
     """adf_fgs_filter_device: the same filter on images that already live in HBM (torch CUDA tensors are
