@@ -75,7 +75,7 @@ static Geom make_geom(int W, int H, int rx, int ry, int rw, int rh)
     g.W = W; g.H = H; g.rx = rx; g.ry = ry; g.rw = rw; g.rh = rh;
     g.pw = round_up(rw, 64);
     g.ph = round_up(rh, 64);
-    size_t a = (size_t)round_up(rh, ADF_TILE_ROWS) * g.pw, b = (size_t)rw * g.ph;   // (the wave solver's pair plane holds rows in tiles)
+    size_t a = (size_t)round_up(rh, TILE_ROWS) * g.pw, b = (size_t)rw * g.ph;   // (the wave solver's pair plane holds rows in tiles)
     g.plane = ((a > b ? a : b) + 63) / 64 * 64;
     g.frame = (size_t)W * H;
     // confidence plane: ROI column 0 16-byte aligned, >= 3 zero floats behind a row, pitch a multiple of 4 (adf_internal.h)
@@ -501,11 +501,10 @@ struct adf_wls {
     bool scaled_fuse = true; // ADF_SCALED_FUSE=0: the down-scaled path through the two resize kernels (A/B measurements)
     bool conf_band = true;   // ADF_CONF_BAND=0: the two-kernel confidence stage (A/B measurements)
     bool merge_small = true; // ADF_MERGE_SMALL=0: never the merged preparation launch (A/B measurements)
-    size_t conf_lds_floor = 0; // ADF_CONF_LDS_FLOOR_KB: see ConfBandArgs::lds_floor (A/B measurements)
     // HIP maps the streams of ONE priority level onto a small pool of hardware queues (4 by default) and two streams that
     // share a queue run one after the other: a side stream of the caller's priority lost the overlap for about one caller
     // stream in four (tools/batch_cpp.cpp: 13.5-13.6 ms per 64 x 4K call instead of 12.8-13.2).  Each priority level has a pool
-    // of its own, so the side stream is created on a level the caller's stream is NOT on.  ADF_SIDE_PRIORITY overrides (A/B).
+    // of its own, so the side stream is created on a level the caller's stream is NOT on.
     static bool null_caller_of(hipStream_t s) { return s == nullptr || s == hipStreamLegacy || s == hipStreamPerThread; }
     int ensure_side(hipStream_t caller)
     {
@@ -516,12 +515,7 @@ struct adf_wls {
         prio = (cp != greatest) ? greatest : (greatest < least ? greatest + 1 : greatest);   // the highest level, or the one below it
         // (the NULL stream is the exception: beside a side stream of another level its calls took 13.9-14.0 ms, with one of
         // its own level 12.8-13.0 -- torch's default stream is the NULL stream)
-        const bool null_caller = null_caller_of(caller);
-        const char* e = getenv("ADF_SIDE_PRIORITY");
-        if (e) prio = atoi(e);
-        if (prio < greatest) prio = greatest;
-        if (prio > least) prio = least;
-        if (null_caller && !e) HIP_TRY(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));   // the default level, as rounds 1-3 did
+        if (null_caller_of(caller)) HIP_TRY(hipStreamCreateWithFlags(&side, hipStreamNonBlocking));   // the default level, as rounds 1-3 did
         else HIP_TRY(hipStreamCreateWithPriority(&side, hipStreamNonBlocking, prio));
         HIP_TRY(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
         HIP_TRY(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
@@ -552,7 +546,6 @@ extern "C" int adf_wls_create(adf_wls_t** out, int use_confidence, int l, int r,
     if (const char* e = getenv("ADF_SCALED_FUSE")) h->scaled_fuse = atoi(e) != 0;  // measurement knob
     if (const char* e = getenv("ADF_LO_HALF")) h->scaled_half = atoi(e) != 0;
     if (const char* e = getenv("ADF_MERGE_SMALL")) h->merge_small = atoi(e) != 0;   // measurement knob
-    if (const char* e = getenv("ADF_CONF_LDS_FLOOR_KB")) h->conf_lds_floor = (size_t)atoi(e) * 1024;
     *out = h;
     return ADF_OK;
 }
@@ -851,7 +844,7 @@ static int wls_filter_impl(adf_wls_t* h, int n_pairs,
                     HIP_TRY(launch_prep_small(ba, wa, oa, n, st));         // FGS.cpp:163-172 + DF.cpp:197-210 + :284
                 } else if (band) {
                     // both views, LRC and x255 in one band sweep: the right view's map lives in LDS only
-                    ConfBandArgs ba{dL, sL, psL, dRp, sR, psR, confp, g, rrx, thresh, h->disc_radius, h->roll_off, 0, fork_weights ? h->conf_lds_floor : 0};
+                    ConfBandArgs ba{dL, sL, psL, dRp, sR, psR, confp, g, rrx, thresh, h->disc_radius, h->roll_off, 0};
                     ProfScope ps(prof, K_LRC, 8.0 * P, 8.0 * P, st);     // dL 2 + dR 2 read, conf 4 written
                     HIP_TRY(launch_conf_band(ba, n, st));                  // DF.cpp:197-210
                 } else {

@@ -40,9 +40,7 @@ enum Orient { ORIENT_N = 0, ORIENT_T = 1, ORIENT_PAIR = 2, ORIENT_STRIP = 3 };
 #define ADF_STRIP 16
 // Rows per tile of the pair plane: [rh/TR][pw/16][TR rows][U0 x16 | U1 x16] -- a strip visit of the column pass is
 // TR*128 contiguous bytes, a row of the row pass is 128-byte pieces at a TR*128-byte stride (power of two).
-#ifndef ADF_TILE_ROWS
-#define ADF_TILE_ROWS 2
-#endif
+constexpr int TILE_ROWS = 2;
 
 // What the last sweep of a solve writes (fused epilogues).
 enum Epilogue {
@@ -83,9 +81,6 @@ struct ConfBandArgs {
     Geom g; int rrx; int thresh;
     int radius; float roll_off;
     int rows_per_band;
-    // dynamic LDS to ask for at least: above 80 KiB only ONE band workgroup fits a CU, which leaves wave slots for the
-    // weight kernel that runs beside this one on the side stream (0 = just what the kernel needs)
-    size_t lds_floor;
 };
 
 // Non-ROI pixels: filtered map = fill (DF.cpp:284), confidence = 0 (DF.cpp:187-190); either may be null.
@@ -224,7 +219,7 @@ int max_disc_radius();
 // float index of U0(i, j) inside an ORIENT_PAIR plane of pitch pw (U1 is ADF_STRIP floats further)
 __device__ __forceinline__ size_t pair_index(int i, int j, int pw)
 {
-    constexpr int TR = ADF_TILE_ROWS;
+    constexpr int TR = TILE_ROWS;
     return (size_t)(i / TR) * (size_t)(2 * TR * pw) + (size_t)((j >> 4) * (32 * TR) + (i % TR) * 32 + (j & 15));
 }
 // float index of C(i, j) inside an ORIENT_STRIP plane of rh rows

@@ -118,13 +118,9 @@ __global__ void __launch_bounds__(NT) discontinuity_kernel(DiscArgs a)
 // The launchers use 128 rows per block for big batches (halo rows and the LUT / prefetch ramp are
 // amortised) and fewer when the whole launch would otherwise be too few blocks to fill 256 CUs
 // (single-image latency).
-#ifndef ADF_CONF_GROUP
-#define ADF_CONF_GROUP 8 // rows per prefetch / gather group of the column-walking kernels (measured: 8 beats 16 and 32:
-                         // fewer registers -> more resident waves matters more than prefetch depth)
-#endif
-#ifndef ADF_LRC_GROUP
-#define ADF_LRC_GROUP 4  // same for the fused left-view kernel (it also carries the gathered dR / cR per row)
-#endif
+constexpr int CONF_GROUP = 8; // rows per prefetch / gather group of the column-walking kernels (measured: 8 beats 16 and 32:
+                              // fewer registers -> more resident waves matters more than prefetch depth)
+constexpr int LRC_GROUP = 4;  // same for the fused left-view kernel (it also carries the gathered dR / cR per row)
 #define DC_ROWS ((rows_total + (int)gridDim.y - 1) / (int)gridDim.y)
 
 inline int row_blocks(int rows, int blocks_xz)
@@ -185,7 +181,7 @@ __global__ void __launch_bounds__(NT) discontinuity_col_kernel(DiscArgs a)
 
     // rows are consumed in groups of U (a multiple of the window height K, so that ring slots stay
     // compile-time) and the next group's U loads are in flight while the current group is reduced
-    constexpr int U = K * ((ADF_CONF_GROUP + K - 1) / K);
+    constexpr int U = K * ((CONF_GROUP + K - 1) / K);
     WinSum ring[K], S;
     S.clear();
     int nxt[U];
@@ -237,7 +233,7 @@ __global__ void __launch_bounds__(NT) conf_left_kernel(ConfLeftArgs a)
 {
     constexpr int K = 2 * RT + 1;
     constexpr int OUTW = NT - 2 * RT;
-    constexpr int U = K * ((ADF_LRC_GROUP + K - 1) / K);
+    constexpr int U = K * ((LRC_GROUP + K - 1) / K);
     constexpr int CR = RT > 0 ? RT : 1;
     __shared__ int2 rowbuf[2][NT];
     const Geom& g = a.g;
@@ -994,10 +990,9 @@ hipError_t launch_conf_band(const ConfBandArgs& a0, int n_pairs, hipStream_t st)
         // alternating runs each; radius 3 12.78-13.22 against 13.18-13.33; StereoBM factory's geometry (radius 5)
         // 13.04-13.17 against 13.46-13.63, and 13.59-13.64 with the ring in registers; radius 4 13.02-13.17 against 13.54.
         // Radius 6..8 (108..128 registers) keep the quarter free: radius 6 13.65-13.78 against 13.92)
-        static const int quarters_env = [] { const char* e = getenv("ADF_CONF_BAND_QUARTERS"); return e ? atoi(e) : 0; }();   // A/B knob
         // (narrow ROIs, whose small band workgroups share a CU, keep the quarter free at every radius: 256 frames of
         // 1242x375 per call 2.95-2.97 against 3.06 ms)
-        const int quarters = quarters_env >= 1 && quarters_env <= 4 ? quarters_env : (a.radius <= 5 && per_cu == 1 ? 4 : 3);
+        const int quarters = a.radius <= 5 && per_cu == 1 ? 4 : 3;
         bands_total = cus * quarters / 4 * per_cu;
     }
     int bands = (bands_total + n_pairs - 1) / n_pairs;
@@ -1008,8 +1003,7 @@ hipError_t launch_conf_band(const ConfBandArgs& a0, int n_pairs, hipStream_t st)
     if (rpb > a.g.rh) rpb = a.g.rh;
     a.rows_per_band = rpb;
     const dim3 grid((a.g.rh + rpb - 1) / rpb, n_pairs), block(64 * waves);
-    size_t lds = conf_band_lds(a.g.rw, a.radius);
-    if (a.lds_floor > lds) lds = a.lds_floor;         // (occupancy control: see ConfBandArgs::lds_floor)
+    const size_t lds = conf_band_lds(a.g.rw, a.radius);
     const bool rl = conf_band_rlds(a.g.rw, a.radius);
     hipError_t le = hipErrorInvalidValue;
 #define ADF_CB(RR, RL) le = launch_conf_band_variant<RR, RL>(a, grid, block, lds, st)

@@ -69,35 +69,15 @@ __device__ __forceinline__ void launder(float (&v)[M])
     for (int i = 0; i < M; i++) asm volatile("" : "+v"(v[i]));
 }
 
-// Reciprocal used inside the sweeps.  v_rcp_f32 is accurate to 1 ulp; one Newton step makes it
-// (nearly) correctly rounded at the price of two more dependent FMAs on the serial chain.
-template <bool REFINE>
-__device__ __forceinline__ float rcp_sel(float x) { return REFINE ? rcp_nr(x) : __builtin_amdgcn_rcpf(x); }
-
-// Quotient x / den from a reciprocal r of den.  x * r carries the reciprocal's rounding AND the product's;
-// one residual step (two FMAs) makes the quotient correctly rounded in all but rare cases, i.e. as good as
-// the IEEE division of the scalar order.  Measured against the float64 banded solve on the badly
-// conditioned draws of tests/test_gpu_fuzz.py (mean |error| of the float planes, in LSB of the output):
-// scalar order 0.060; wave solver 0.073 with plain products, 0.059 with the residual step in the boundary
-// sweeps (bit 0; the other two phases do not matter), at +2.3 % of a BASELINE step (the fused first row
-// pass +11 %).  It changes nothing in how often the two float32 evaluations round differently, which is
-// what the parity tests measure, so the build default is 0; -DADF_WAVE_DIVFIX=1 buys the accuracy.
-#ifndef ADF_WAVE_DIVFIX
-#define ADF_WAVE_DIVFIX 0   // bit 0: boundary sweeps, bit 1: interior solve, bit 2: reduced system
-#endif
-template <int WHERE>
-__device__ __forceinline__ float qdiv(float x, float den, float r)
-{
-    const float q = x * r;
-    return (ADF_WAVE_DIVFIX & WHERE) ? __builtin_fmaf(__builtin_fmaf(-den, q, x), r, q) : q;
-}
-
-#ifndef ADF_WAVE_REFINE_BOUNDARY
-#define ADF_WAVE_REFINE_BOUNDARY 1
-#endif
-#ifndef ADF_WAVE_REFINE_SOLVE
-#define ADF_WAVE_REFINE_SOLVE 1
-#endif
+// Quotients x / den are formed as x * r from r = rcp_nr(den): v_rcp_f32 is accurate to 1 ulp, and one Newton step
+// makes it (nearly) correctly rounded at the price of two more dependent FMAs on the serial chain.  x * r carries the
+// reciprocal's rounding AND the product's.  A residual step (two FMAs) would make the quotient correctly rounded in all
+// but rare cases, i.e. as good as the IEEE division of the scalar order.  Measured against the float64 banded solve on
+// the badly conditioned draws of tests/test_gpu_fuzz.py (mean |error| of the float planes, in LSB of the output):
+// scalar order 0.060; wave solver 0.073 with plain products, 0.059 with the residual step in the boundary sweeps (the
+// other two phases do not matter), at +2.3 % of a BASELINE step (the fused first row pass +11 %).  It changes nothing in
+// how often the two float32 evaluations round differently, which is what the parity tests measure, so the plain
+// product stays (the residual-step variant was removed; it is in the history at a483289).
 
 // Phase 1 for NC independent chunks (columns): boundary coefficients with O(1) state.  The
 // left->right (LU) and right->left (UL) sweeps are independent serial chains; they advance together,
@@ -107,15 +87,6 @@ template <int M, int R, int NC>
 __device__ __forceinline__ void chunk_boundary(const float (&c)[NC][M], const float (&f0)[NC][M], const float (&f1)[NC][M],
                                                const float (&a_s)[NC], Boundary<R> (&o)[NC])
 {
-    constexpr bool NRB = ADF_WAVE_REFINE_BOUNDARY != 0;
-#ifdef ADF_WAVE_DEBUG_SKIP_COMPUTE  // timing experiment only: keep the data flow, drop the sweeps
-#pragma unroll
-    for (int e = 0; e < NC; e++) {
-        o[e].GE0 = f0[e][0]; o[e].GE1 = f1[e][0]; o[e].PE = c[e][0]; o[e].QE = c[e][M - 1];
-        o[e].GS0 = f0[e][M - 1]; o[e].GS1 = f1[e][M - 1]; o[e].PS = a_s[e]; o[e].QS = c[e][1];
-    }
-    return;
-#endif
     // left -> right: x_i + D_i x_{i+1} = g_i - p_i xL;   right -> left: x_i + E_i x_{i-1} = h_i - q_i xR
     float D[NC], g0[NC], g1[NC], p[NC];
     float r[NC], dr[NC], h0[NC], h1[NC], q[NC];
@@ -123,13 +94,13 @@ __device__ __forceinline__ void chunk_boundary(const float (&c)[NC][M], const fl
     for (int e = 0; e < NC; e++) {
         const float a = a_s[e];
         const float dl = (1.0f - a) - c[e][0];
-        const float rl = rcp_sel<NRB>(dl);
-        D[e] = qdiv<1>(c[e][0], dl, rl); g0[e] = qdiv<1>(f0[e][0], dl, rl); g1[e] = (R > 1) ? qdiv<1>(f1[e][0], dl, rl) : 0.0f; p[e] = qdiv<1>(a, dl, rl);
+        const float rl = rcp_nr(dl);
+        D[e] = c[e][0] * rl; g0[e] = f0[e][0] * rl; g1[e] = (R > 1) ? f1[e][0] * rl : 0.0f; p[e] = a * rl;
         const float ci = c[e][M - 2];
         const float ar = (M - 2 == 0) ? a_s[e] : c[e][(M - 3 > 0) ? M - 3 : 0];
         dr[e] = (1.0f - ar) - ci;
-        r[e] = rcp_sel<NRB>(dr[e]);
-        h0[e] = qdiv<1>(f0[e][M - 2], dr[e], r[e]); h1[e] = (R > 1) ? qdiv<1>(f1[e][M - 2], dr[e], r[e]) : 0.0f; q[e] = qdiv<1>(ci, dr[e], r[e]);
+        r[e] = rcp_nr(dr[e]);
+        h0[e] = f0[e][M - 2] * r[e]; h1[e] = (R > 1) ? f1[e][M - 2] * r[e] : 0.0f; q[e] = ci * r[e];
     }
 #pragma unroll
     for (int t = 1; t <= M - 2; t++) {
@@ -140,11 +111,11 @@ __device__ __forceinline__ void chunk_boundary(const float (&c)[NC][M], const fl
                 const float a = c[e][i - 1];
                 const float b = (1.0f - a) - c[e][i];
                 const float dl = __builtin_fmaf(-a, D[e], b);
-                const float rl = rcp_sel<NRB>(dl);
-                D[e] = qdiv<1>(c[e][i], dl, rl);
-                g0[e] = qdiv<1>(__builtin_fmaf(-a, g0[e], f0[e][i]), dl, rl);
-                if (R > 1) g1[e] = qdiv<1>(__builtin_fmaf(-a, g1[e], f1[e][i]), dl, rl);
-                p[e] = qdiv<1>(-a * p[e], dl, rl);
+                const float rl = rcp_nr(dl);
+                D[e] = c[e][i] * rl;
+                g0[e] = __builtin_fmaf(-a, g0[e], f0[e][i]) * rl;
+                if (R > 1) g1[e] = __builtin_fmaf(-a, g1[e], f1[e][i]) * rl;
+                p[e] = -a * p[e] * rl;
                 asm volatile("" : "+v"(p[e])); // p feeds nothing until the end: keep its chain in step
             }
             {
@@ -155,10 +126,10 @@ __device__ __forceinline__ void chunk_boundary(const float (&c)[NC][M], const fl
                 asm volatile("" : "+v"(ci), "+v"(a));
                 const float b = (1.0f - a) - ci;
                 dr[e] = __builtin_fmaf(-ci * ci, r[e], b);
-                r[e] = rcp_sel<NRB>(dr[e]);
-                h0[e] = qdiv<1>(__builtin_fmaf(-ci, h0[e], f0[e][j]), dr[e], r[e]);
-                if (R > 1) h1[e] = qdiv<1>(__builtin_fmaf(-ci, h1[e], f1[e][j]), dr[e], r[e]);
-                q[e] = qdiv<1>(-ci * q[e], dr[e], r[e]);
+                r[e] = rcp_nr(dr[e]);
+                h0[e] = __builtin_fmaf(-ci, h0[e], f0[e][j]) * r[e];
+                if (R > 1) h1[e] = __builtin_fmaf(-ci, h1[e], f1[e][j]) * r[e];
+                q[e] = -ci * q[e] * r[e];
                 asm volatile("" : "+v"(q[e]));
             }
         }
@@ -167,7 +138,7 @@ __device__ __forceinline__ void chunk_boundary(const float (&c)[NC][M], const fl
 #pragma unroll
     for (int e = 0; e < NC; e++) {
         o[e].GE0 = g0[e]; o[e].GE1 = g1[e]; o[e].PE = p[e]; o[e].QE = D[e];
-        o[e].GS0 = h0[e]; o[e].GS1 = h1[e]; o[e].PS = qdiv<1>(a_s[e], dr[e], r[e]); o[e].QS = q[e];
+        o[e].GS0 = h0[e]; o[e].GS1 = h1[e]; o[e].PS = a_s[e] * r[e]; o[e].QS = q[e];
     }
 }
 
@@ -177,17 +148,6 @@ __device__ __forceinline__ void chunk_solve(float (&c)[NC][M], float (&f0)[NC][M
                                             const float (&a_s)[NC], const float (&xL0)[NC], const float (&xL1)[NC],
                                             const float (&xR0)[NC], const float (&xR1)[NC])
 {
-    constexpr bool NRS = ADF_WAVE_REFINE_SOLVE != 0;
-#ifdef ADF_WAVE_DEBUG_SKIP_COMPUTE
-#pragma unroll
-    for (int e = 0; e < NC; e++)
-#pragma unroll
-        for (int i = 0; i < M; i++) {
-            f0[e][i] = __builtin_fmaf(c[e][i], xR0[e] + xL0[e], f0[e][i]);
-            f1[e][i] = __builtin_fmaf(c[e][i], xR1[e] + xL1[e], f1[e][i]);
-        }
-    return;
-#endif
 #pragma unroll
     for (int e = 0; e < NC; e++) launder<M>(c[e]);
     float corig[NC], D[NC], g0[NC], g1[NC];
@@ -196,10 +156,10 @@ __device__ __forceinline__ void chunk_solve(float (&c)[NC][M], float (&f0)[NC][M
         const float a = a_s[e];
         corig[e] = c[e][0];
         const float dn = (1.0f - a) - corig[e];
-        const float r = rcp_sel<NRS>(dn);
-        D[e] = qdiv<2>(corig[e], dn, r);
-        g0[e] = qdiv<2>(__builtin_fmaf(-a, xL0[e], f0[e][0]), dn, r);
-        g1[e] = (R > 1) ? qdiv<2>(__builtin_fmaf(-a, xL1[e], f1[e][0]), dn, r) : 0.0f;
+        const float r = rcp_nr(dn);
+        D[e] = corig[e] * r;
+        g0[e] = __builtin_fmaf(-a, xL0[e], f0[e][0]) * r;
+        g1[e] = (R > 1) ? __builtin_fmaf(-a, xL1[e], f1[e][0]) * r : 0.0f;
         c[e][0] = D[e]; f0[e][0] = g0[e]; if (R > 1) f1[e][0] = g1[e];
     }
 #pragma unroll
@@ -210,10 +170,10 @@ __device__ __forceinline__ void chunk_solve(float (&c)[NC][M], float (&f0)[NC][M
             corig[e] = c[e][i];
             const float b = (1.0f - a) - corig[e];
             const float dn = __builtin_fmaf(-a, D[e], b);
-            const float r = rcp_sel<NRS>(dn);
-            D[e] = qdiv<2>(corig[e], dn, r);
-            g0[e] = qdiv<2>(__builtin_fmaf(-a, g0[e], f0[e][i]), dn, r);
-            if (R > 1) g1[e] = qdiv<2>(__builtin_fmaf(-a, g1[e], f1[e][i]), dn, r);
+            const float r = rcp_nr(dn);
+            D[e] = corig[e] * r;
+            g0[e] = __builtin_fmaf(-a, g0[e], f0[e][i]) * r;
+            if (R > 1) g1[e] = __builtin_fmaf(-a, g1[e], f1[e][i]) * r;
             c[e][i] = D[e]; f0[e][i] = g0[e]; if (R > 1) f1[e][i] = g1[e];
         }
         ADF_STEP_FENCE();
@@ -248,18 +208,10 @@ typedef float v2f __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ v2f vfma(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ v2f vsplat(float x) { return (v2f){x, x}; }
-template <bool REFINE>
-__device__ __forceinline__ v2f vrcp_sel(v2f x)
+__device__ __forceinline__ v2f vrcp_nr(v2f x)
 {
     const v2f r = {__builtin_amdgcn_rcpf(x.x), __builtin_amdgcn_rcpf(x.y)};
-    return REFINE ? vfma(vfma(-x, r, vsplat(1.0f)), r, r) : r;
-}
-
-template <int WHERE>
-__device__ __forceinline__ v2f vqdiv(v2f x, v2f den, v2f r)
-{
-    const v2f q = x * r;
-    return (ADF_WAVE_DIVFIX & WHERE) ? vfma(vfma(-den, q, x), r, q) : q;
+    return vfma(vfma(-x, r, vsplat(1.0f)), r, r);
 }
 
 template <int R>
@@ -268,19 +220,18 @@ struct Boundary2 { v2f GS0, GS1, PS, QS, GE0, GE1, PE, QE; };
 template <int M, int R>
 __device__ __forceinline__ void chunk_boundary2(const v2f (&c)[M], const v2f (&f0)[M], const v2f (&f1)[M], v2f a_s, Boundary2<R>& o)
 {
-    constexpr bool NRB = ADF_WAVE_REFINE_BOUNDARY != 0;
     const v2f one = vsplat(1.0f), zero = vsplat(0.0f);
     // left -> right: x_i + D_i x_{i+1} = g_i - p_i xL;   right -> left: x_i + E_i x_{i-1} = h_i - q_i xR
     v2f D, g0, g1, p, r, dr, h0, h1, q;
     {
         const v2f dl = (one - a_s) - c[0];
-        const v2f rl = vrcp_sel<NRB>(dl);
-        D = vqdiv<1>(c[0], dl, rl); g0 = vqdiv<1>(f0[0], dl, rl); g1 = (R > 1) ? vqdiv<1>(f1[0], dl, rl) : zero; p = vqdiv<1>(a_s, dl, rl);
+        const v2f rl = vrcp_nr(dl);
+        D = c[0] * rl; g0 = f0[0] * rl; g1 = (R > 1) ? f1[0] * rl : zero; p = a_s * rl;
         const v2f ci = c[M - 2];
         const v2f ar = (M - 2 == 0) ? a_s : c[(M - 3 > 0) ? M - 3 : 0];
         dr = (one - ar) - ci;
-        r = vrcp_sel<NRB>(dr);
-        h0 = vqdiv<1>(f0[M - 2], dr, r); h1 = (R > 1) ? vqdiv<1>(f1[M - 2], dr, r) : zero; q = vqdiv<1>(ci, dr, r);
+        r = vrcp_nr(dr);
+        h0 = f0[M - 2] * r; h1 = (R > 1) ? f1[M - 2] * r : zero; q = ci * r;
     }
 #pragma unroll
     for (int t = 1; t <= M - 2; t++) {
@@ -289,11 +240,11 @@ __device__ __forceinline__ void chunk_boundary2(const v2f (&c)[M], const v2f (&f
             const v2f a = c[i - 1];
             const v2f b = (one - a) - c[i];
             const v2f dl = vfma(-a, D, b);
-            const v2f rl = vrcp_sel<NRB>(dl);
-            D = vqdiv<1>(c[i], dl, rl);
-            g0 = vqdiv<1>(vfma(-a, g0, f0[i]), dl, rl);
-            if (R > 1) g1 = vqdiv<1>(vfma(-a, g1, f1[i]), dl, rl);
-            p = vqdiv<1>(-a * p, dl, rl);
+            const v2f rl = vrcp_nr(dl);
+            D = c[i] * rl;
+            g0 = vfma(-a, g0, f0[i]) * rl;
+            if (R > 1) g1 = vfma(-a, g1, f1[i]) * rl;
+            p = -a * p * rl;
             // pin every chain to its step: pure arithmetic is not ordered against the fence below by
             // instruction selection, and a chain that drifts out of the loop drags one reciprocal per
             // step along with it (the right-hand-side chains feed nothing until the end)
@@ -308,36 +259,32 @@ __device__ __forceinline__ void chunk_boundary2(const v2f (&c)[M], const v2f (&f
             asm volatile("" : "+v"(ci), "+v"(a));
             const v2f b = (one - a) - ci;
             dr = vfma(-ci * ci, r, b);
-            r = vrcp_sel<NRB>(dr);
-            h0 = vqdiv<1>(vfma(-ci, h0, f0[j]), dr, r);
-            if (R > 1) h1 = vqdiv<1>(vfma(-ci, h1, f1[j]), dr, r);
-            q = vqdiv<1>(-ci * q, dr, r);
+            r = vrcp_nr(dr);
+            h0 = vfma(-ci, h0, f0[j]) * r;
+            if (R > 1) h1 = vfma(-ci, h1, f1[j]) * r;
+            q = -ci * q * r;
             if (R > 1) asm volatile("" : "+v"(h0), "+v"(h1), "+v"(q));
             else asm volatile("" : "+v"(h0), "+v"(q));
         }
         ADF_STEP_FENCE();
     }
     o.GE0 = g0; o.GE1 = g1; o.PE = p; o.QE = D;
-    o.GS0 = h0; o.GS1 = h1; o.PS = vqdiv<1>(a_s, dr, r); o.QS = q;
+    o.GS0 = h0; o.GS1 = h1; o.PS = a_s * r; o.QS = q;
 }
 
-// `emit(i, x0, x1)` is called the moment row i of the chunk is final -- the separator row first, then up the chunk as the
-// back-substitution forms them -- so that a caller can issue the row's store under the remaining arithmetic instead of
-// after it (round 4).
-template <int M, int R, typename Emit>
-__device__ __forceinline__ void chunk_solve2(v2f (&c)[M], v2f (&f0)[M], v2f (&f1)[M], v2f a_s, v2f xL0, v2f xL1, v2f xR0, v2f xR1, Emit&& emit)
+template <int M, int R>
+__device__ __forceinline__ void chunk_solve2(v2f (&c)[M], v2f (&f0)[M], v2f (&f1)[M], v2f a_s, v2f xL0, v2f xL1, v2f xR0, v2f xR1)
 {
-    constexpr bool NRS = ADF_WAVE_REFINE_SOLVE != 0;
     const v2f one = vsplat(1.0f), zero = vsplat(0.0f);
 #pragma unroll
     for (int i = 0; i < M; i++) asm volatile("" : "+v"(c[i]));
     v2f corig = c[0], D, g0, g1;
     {
         const v2f dn = (one - a_s) - corig;
-        const v2f r = vrcp_sel<NRS>(dn);
-        D = vqdiv<2>(corig, dn, r);
-        g0 = vqdiv<2>(vfma(-a_s, xL0, f0[0]), dn, r);
-        g1 = (R > 1) ? vqdiv<2>(vfma(-a_s, xL1, f1[0]), dn, r) : zero;
+        const v2f r = vrcp_nr(dn);
+        D = corig * r;
+        g0 = vfma(-a_s, xL0, f0[0]) * r;
+        g1 = (R > 1) ? vfma(-a_s, xL1, f1[0]) * r : zero;
         c[0] = D; f0[0] = g0; if (R > 1) f1[0] = g1;
     }
 #pragma unroll
@@ -346,10 +293,10 @@ __device__ __forceinline__ void chunk_solve2(v2f (&c)[M], v2f (&f0)[M], v2f (&f1
         corig = c[i];
         const v2f b = (one - a) - corig;
         const v2f dn = vfma(-a, D, b);
-        const v2f r = vrcp_sel<NRS>(dn);
-        D = vqdiv<2>(corig, dn, r);
-        g0 = vqdiv<2>(vfma(-a, g0, f0[i]), dn, r);
-        if (R > 1) g1 = vqdiv<2>(vfma(-a, g1, f1[i]), dn, r);
+        const v2f r = vrcp_nr(dn);
+        D = corig * r;
+        g0 = vfma(-a, g0, f0[i]) * r;
+        if (R > 1) g1 = vfma(-a, g1, f1[i]) * r;
         c[i] = D; f0[i] = g0; if (R > 1) f1[i] = g1;
         if (R > 1) asm volatile("" : "+v"(D), "+v"(g0), "+v"(g1));
         else asm volatile("" : "+v"(D), "+v"(g0));
@@ -357,7 +304,6 @@ __device__ __forceinline__ void chunk_solve2(v2f (&c)[M], v2f (&f0)[M], v2f (&f1
     }
     v2f x0 = xR0, x1 = xR1;
     f0[M - 1] = x0; if (R > 1) f1[M - 1] = x1;
-    emit(M - 1, x0, x1);
 #pragma unroll
     for (int i = M - 2; i >= 0; i--) {
         x0 = vfma(-c[i], x0, f0[i]);
@@ -365,14 +311,8 @@ __device__ __forceinline__ void chunk_solve2(v2f (&c)[M], v2f (&f0)[M], v2f (&f1
         if (R > 1) { x1 = vfma(-c[i], x1, f1[i]); f1[i] = x1; }
         if (R > 1) asm volatile("" : "+v"(x0), "+v"(x1));
         else asm volatile("" : "+v"(x0));
-        emit(i, x0, x1);
         ADF_STEP_FENCE();
     }
-}
-template <int M, int R>
-__device__ __forceinline__ void chunk_solve2(v2f (&c)[M], v2f (&f0)[M], v2f (&f1)[M], v2f a_s, v2f xL0, v2f xL1, v2f xR0, v2f xR1)
-{
-    chunk_solve2<M, R>(c, f0, f1, a_s, xL0, xL1, xR0, xR1, [](int, v2f, v2f) {});
 }
 
 template <int M, int R>
@@ -416,7 +356,7 @@ __device__ __forceinline__ void pcr64(int lane, float al, float be, float ga, fl
         float fp1 = (R > 1) ? __shfl_down(p1, d) : 0.0f;
         if (lane < d) { am = 0.0f; bm = 1.0f; gm = 0.0f; fm0 = 0.0f; fm1 = 0.0f; }
         if (lane + d > 63) { ap = 0.0f; bp = 1.0f; gp = 0.0f; fp0 = 0.0f; fp1 = 0.0f; }
-        const float k1 = qdiv<4>(al, bm, rcp_nr(bm)), k2 = qdiv<4>(ga, bp, rcp_nr(bp));
+        const float k1 = al * rcp_nr(bm), k2 = ga * rcp_nr(bp);
         be = __builtin_fmaf(-ap, k2, __builtin_fmaf(-gm, k1, be));
         p0 = __builtin_fmaf(-fp0, k2, __builtin_fmaf(-fm0, k1, p0));
         if (R > 1) p1 = __builtin_fmaf(-fp1, k2, __builtin_fmaf(-fm1, k1, p1));
@@ -424,8 +364,8 @@ __device__ __forceinline__ void pcr64(int lane, float al, float be, float ga, fl
         ga = -gp * k2;
     }
     const float rb = rcp_nr(be);
-    x0 = qdiv<4>(p0, be, rb);
-    x1 = (R > 1) ? qdiv<4>(p1, be, rb) : 0.0f;
+    x0 = p0 * rb;
+    x1 = (R > 1) ? p1 * rb : 0.0f;
 }
 
 
@@ -443,8 +383,8 @@ __device__ __forceinline__ void reduced128(int lane, const float* al, const floa
     const float al_o = al[o * stride], be_o = be[o * stride], ga_o = ga[o * stride], p0_o = p0[o * stride];
     const float al_m = al[m * stride], be_m = be[m * stride], ga_m = ga[m * stride], p0_m = p0[m * stride];
     const float p1_e = (R > 1) ? p1[e * stride] : 0.0f, p1_o = (R > 1) ? p1[o * stride] : 0.0f, p1_m = (R > 1) ? p1[m * stride] : 0.0f;
-    const float k1 = lane > 0 ? qdiv<4>(al_e, be_m, rcp_nr(be_m)) : 0.0f;     // (row 0 has no predecessor: its alpha is 0)
-    const float k2 = qdiv<4>(ga_e, be_o, rcp_nr(be_o));
+    const float k1 = lane > 0 ? al_e * rcp_nr(be_m) : 0.0f;     // (row 0 has no predecessor: its alpha is 0)
+    const float k2 = ga_e * rcp_nr(be_o);
     const float AL = -al_m * k1, GA = -ga_o * k2;
     const float BE = __builtin_fmaf(-al_o, k2, __builtin_fmaf(-ga_m, k1, be_e));
     const float P0 = __builtin_fmaf(-p0_o, k2, __builtin_fmaf(-p0_m, k1, p0_e));
@@ -453,10 +393,10 @@ __device__ __forceinline__ void reduced128(int lane, const float* al, const floa
     pcr64<R>(lane, AL, BE, GA, P0, P1, xe0, xe1);
     const float xn0 = __shfl_down(xe0, 1), xn1 = (R > 1) ? __shfl_down(xe1, 1) : 0.0f;   // (lane 63: row 127's gamma is 0)
     const float rb = rcp_nr(be_o);
-    const float xo0 = qdiv<4>(__builtin_fmaf(-ga_o, xn0, __builtin_fmaf(-al_o, xe0, p0_o)), be_o, rb);
+    const float xo0 = __builtin_fmaf(-ga_o, xn0, __builtin_fmaf(-al_o, xe0, p0_o)) * rb;
     x0[e * stride] = xe0; x0[o * stride] = xo0;
     if (R > 1) {
-        const float xo1 = qdiv<4>(__builtin_fmaf(-ga_o, xn1, __builtin_fmaf(-al_o, xe1, p1_o)), be_o, rb);
+        const float xo1 = __builtin_fmaf(-ga_o, xn1, __builtin_fmaf(-al_o, xe1, p1_o)) * rb;
         x1[e * stride] = xe1; x1[o * stride] = xo1;
     }
 }

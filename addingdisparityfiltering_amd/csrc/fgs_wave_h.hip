@@ -3,24 +3,12 @@
 
 #include <algorithm>
 
-// A/B knobs of the low-resolution fused prologue (tools/ab_lo.sh)
-#ifndef ADF_LO_UMASK
-#define ADF_LO_UMASK 1      // end-of-row masks only in the float4 group that can reach the row's end (wave-uniform branch)
-#endif
-#ifndef ADF_LO_NEEDMASK
-#define ADF_LO_NEEDMASK 1   // zero-window masks only where a half's staged span leaves the window (wave-uniform branch)
-#endif
-#ifndef ADF_LO_TAPS_EARLY
-#define ADF_LO_TAPS_EARLY 2 // tap table entries requested: 0 = per half, when it has been staged; 1 = per half, before; 2 = all, with the row's first loads
-#endif
-#ifndef ADF_H_TWO_WAVE_MAX
-#define ADF_H_TWO_WAVE_MAX 60   // longest chunk whose two-right-hand-side kernel fits two waves per SIMD
-#endif
-
 namespace adf {
 
 namespace {
 using namespace wave;
+
+constexpr int H_TWO_WAVE_MAX = 60;   // longest chunk whose two-right-hand-side kernel fits two waves per SIMD
 
 // ---------------------------------------------------------------------------------------------
 // Horizontal pass: one wavefront per row, in place.
@@ -75,7 +63,7 @@ __host__ __device__ constexpr int lo_row_cap(int m) { return (((m * 64) / 3) & ~
 __host__ __device__ constexpr int lo_stage_vec4(int m) { return 12 * lo_row_cap(m) > 256 * m ? (12 * lo_row_cap(m) + 15) / 16 : m * 16; }
 
 template <int M, int R, int FUSED, int NW = 1>
-__global__ void __launch_bounds__(64 * NW, (M > (NW == 2 ? 40 : ADF_H_TWO_WAVE_MAX) && R > 1) ? 1 : 2) wave_hpass_kernel(WavePassArgs a)
+__global__ void __launch_bounds__(64 * NW, (M > (NW == 2 ? 40 : H_TWO_WAVE_MAX) && R > 1) ? 1 : 2) wave_hpass_kernel(WavePassArgs a)
 {
     static_assert(M % 4 == 0 && M >= 4, "chunk length must be a multiple of 4");
     static_assert(NW == 1 || NW == 2, "one or two wavefronts per row");
@@ -93,7 +81,7 @@ __global__ void __launch_bounds__(64 * NW, (M > (NW == 2 ? 40 : ADF_H_TWO_WAVE_M
     // ([U0 x16 | U1 x16] per strip, see fgs_wave_common.h): a row is 2*pitch contiguous floats
     constexpr bool PAIR = R > 1;
     // (rows come in tiles of TR: float4 #q of pair row r lives at (r/TR)*(TR*nvecU) + (q/8)*8*TR + (r%TR)*8 + q%8)
-    constexpr int TR = ADF_TILE_ROWS;
+    constexpr int TR = TILE_ROWS;
     const size_t offU = PAIR ? (size_t)blockIdx.y * 2 * a.plane + (size_t)(blockIdx.x / TR) * (size_t)(2 * TR * a.pitch) + (size_t)(blockIdx.x % TR) * 32 : off;
 #define ADF_PIDX(q) (PAIR ? ((((q) >> 3) * (8 * TR)) + ((q) & 7)) : (q))
     const int nvecU = PAIR ? 2 * nvec : nvec;
@@ -173,11 +161,12 @@ __global__ void __launch_bounds__(64 * NW, (M > (NW == 2 ? 40 : ADF_H_TWO_WAVE_M
                 ss[hh] = __builtin_amdgcn_readfirstlane(s_first);
                 ns[hh] = __builtin_amdgcn_readfirstlane(s_last + 2 - s_first);      // 0 for an empty half
             }
-            // does a staged element of the half lie outside the confidence map's window (wave-uniform)?
+            // does a staged element of the half lie outside the confidence map's window (wave-uniform)?  Zero-window
+            // masks are applied only where a half's staged span leaves the window.
             bool need_mask[2];
 #pragma unroll
             for (int hh = 0; hh < 2; hh++)
-                need_mask[hh] = a.lo_zero_outside && (!ADF_LO_NEEDMASK || yr[0] < a.lo_vy0 || yr[1] >= a.lo_vy1 || ss[hh] < a.lo_vx0 || min(ss[hh] + ns[hh], sw) > a.lo_vx1);
+                need_mask[hh] = a.lo_zero_outside && (yr[0] < a.lo_vy0 || yr[1] >= a.lo_vy1 || ss[hh] < a.lo_vx0 || min(ss[hh] + ns[hh], sw) > a.lo_vx1);
             // Per half: fetch the two source rows (coalesced: lane i takes source elements ss + 4i .. of the confidence
             // rows, ss + 8i .. of the disparity rows; a vector that would cross the row's end is fetched element by
             // element, clamped, which also fills the slots behind the row with the edge element), stage them, tap them.
@@ -259,7 +248,8 @@ __global__ void __launch_bounds__(64 * NW, (M > (NW == 2 ? 40 : ADF_H_TWO_WAVE_M
             typedef short s4a4 __attribute__((ext_vector_type(4), aligned(4)));
             typedef float v2f __attribute__((ext_vector_type(2)));
             const v2f bb0 = {b0, b0}, bb1 = {b1, b1};
-            // the columns' taps (one float per column, the same for every row of the call: L2 hits)
+            // the columns' taps (one float per column, the same for every row of the call: L2 hits), all of them
+            // requested with the row's first loads
             v4f tp[MQ];
             auto load_taps = [&](int hh) {
 #pragma unroll
@@ -270,23 +260,15 @@ __global__ void __launch_bounds__(64 * NW, (M > (NW == 2 ? 40 : ADF_H_TWO_WAVE_M
                 }
             };
             fetch(0, rc[0], rd[0]);
-#if ADF_LO_TAPS_EARLY == 2
             load_taps(0); load_taps(1);
-#endif
 #pragma unroll
             for (int hh = 0; hh < 2; hh++) {
-#if ADF_LO_TAPS_EARLY == 1
-                load_taps(hh);
-#endif
                 put(hh, rc[hh], rd[hh]);
                 __syncthreads();
                 if (hh == 0) {
                     asm volatile("" ::: "memory");               // (the next half's loads: not before this half is staged)
                     fetch(1, rc[1], rd[1]);
                 }
-#if ADF_LO_TAPS_EARLY == 0
-                load_taps(hh);
-#endif
 #pragma unroll
                 for (int k = (hh ? KH : 0); k < (hh ? MQ : KH); k++) {
                     // (opaque: nothing here depends on a load, and the compiler would otherwise form every group's
@@ -340,7 +322,7 @@ __global__ void __launch_bounds__(64 * NW, (M > (NW == 2 ? 40 : ADF_H_TWO_WAVE_M
                         dv[c] = post_scaled ? q2 : q1;
                     }
                     // columns behind the row's end (the last, partial float4 and the lanes past it) are zero
-                    if (!ADF_LO_UMASK || 4 * (v0 + 64 * k + 64) > a.len) {       // (wave-uniform: only the group that holds the row's end, and those past it)
+                    if (4 * (v0 + 64 * k + 64) > a.len) {       // (wave-uniform: only the group that holds the row's end, and those past it)
                         const int left = a.len - 4 * idx;
 #pragma unroll
                         for (int c = 0; c < 4; c++) { const bool on = c < left; cv[c] = on ? cv[c] : 0.0f; dv[c] = on ? dv[c] : 0.0f; }

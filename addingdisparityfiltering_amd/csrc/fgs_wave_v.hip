@@ -4,32 +4,6 @@
 // chunk length a 2160-row column needs and turns into scratch spills.
 #include "fgs_wave_common.h"
 
-#ifdef ADF_V_PHASE_TIMING
-// Measurement builds only (build.build_variant("vphase", ["ADF_V_PHASE_TIMING"]), tools/vphase.py): per-workgroup
-// phase time stamps of the plain column pass on the 100 MHz clock, plus the CU the workgroup ran on.
-__device__ unsigned long long adf_vphase[1 << 20];  // [wg][0..6 stamps, 7 = XCC_ID << 32 | HW_ID]
-__device__ unsigned long long adf_vwave[1 << 21];   // [wg][wave][start, end]
-extern "C" int adf_debug_read_vphase(unsigned long long* dst, int n)
-{
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(adf_vphase), sizeof(unsigned long long) * (size_t)n);
-}
-extern "C" int adf_debug_read_vwave(unsigned long long* dst, int n)
-{
-    return (int)hipMemcpyFromSymbol(dst, HIP_SYMBOL(adf_vwave), sizeof(unsigned long long) * (size_t)n);
-}
-#ifndef ADF_V_PHASE_EPI
-#define ADF_V_PHASE_EPI EPI_PLANES   // which pass is stamped (1 = the last pass with the fused epilogue)
-#endif
-#define ADF_WG_ID ((size_t)(((size_t)blockIdx.y * gridDim.x + blockIdx.x) % (1u << 17)))
-#define ADF_STAMP(k) do { if (EPI == ADF_V_PHASE_EPI && threadIdx.x == 0) adf_vphase[ADF_WG_ID * 8 + (k)] = wall_clock64(); } while (0)
-#define ADF_WSTAMP(k) do { if (EPI == ADF_V_PHASE_EPI && (threadIdx.x & 63) == 0) adf_vwave[(ADF_WG_ID * 8 + (threadIdx.x >> 6)) * 2 + (k)] = wall_clock64(); } while (0)
-#define ADF_DRAIN() asm volatile("s_waitcnt vmcnt(0)" ::: "memory")
-#else
-#define ADF_STAMP(k) do { } while (0)
-#define ADF_WSTAMP(k) do { } while (0)
-#define ADF_DRAIN() do { } while (0)
-#endif
-
 namespace adf {
 
 namespace {
@@ -46,100 +20,6 @@ constexpr int VC = 16;   // columns per strip (the layouts' strip: fgs_wave_comm
 // CU's register file per workgroup -- with a 128-row reduced system per column (fgs_wave_common.h, reduced128).  Half
 // strips read 32-byte pieces (a quarter less bandwidth on a full chip, tools/micro/vpattern.hip), still well ahead of
 // the exact solver such ROIs fell back to.  Everything below is written for VCW columns x NCH chunks.
-
-// ---------------------------------------------------------------------------------------------
-// Whole-line loads by LDS-DMA (round 3; NOT the default: -DADF_V_GLDS=1 selects it).  Moving the pass's bytes alone
-// (tools/micro/vpattern.hip) this shape is 15 % faster than the register loads below, but in the pass every wave meets
-// the others at the barrier before the reduced system, so the strip is not done before its slowest wave's loads are:
-// A/B on the 64 x 4K step 4.25-4.29 ms (DMA) against 4.19-4.21 ms (register loads) for the two plain passes, and
-// the short columns of 1242 x 375 frames lose 8 % to the ring's LDS (profiles/r03_ab_glds.txt, EXPERIMENTS.md section 9).
-// A thread owns (chunk, column pair), so loading straight into its registers
-// makes every wave instruction fetch 8 rows x 64 bytes at 8 bytes per lane ("fragment-shaped"): measured on the pass's
-// own layout (tools/micro/vpattern.hip, profiles/r03_vpattern.txt) that moves the pass's bytes at 4.5 TB/s, while
-// global_load_lds_dwordx4 instructions that fetch 8 WHOLE 128-byte lines each (16 bytes per lane, half as many
-// instructions, no register destination) into a small per-wave LDS ring, followed by 8-byte LDS reads into the same
-// registers, move them at 5.3 TB/s.  Items of a wave's load sequence, for its 8 chunks at once:
-//   line item i    row r0+i of the pair plane: [U0 x16 | U1 x16] = one line per chunk, lane (chunk j, piece p)
-//   weight item k  rows r0+2k, r0+2k+1 of the strip-major weights: 2 x 64 bytes per chunk, lane (j, row parity, piece)
-// in the order L0 L1 W0 L2 L3 W1 ..., 3M/2 items, VRING slots of 1 KiB in flight per wave.  The DMA is issued by
-// inline asm (M0 = LDS destination), so its waits are counted here by hand: item K is complete once at most
-// (items issued after K) operations are outstanding -- anything else the compiler has in flight is older or younger
-// than all of them and only makes the wait stronger.
-// ---------------------------------------------------------------------------------------------
-#ifndef ADF_V_STORE_IN_SOLVE
-#define ADF_V_STORE_IN_SOLVE 0   // bit 0: plane passes, bit 1: the last pass -- a row's store is issued inside the back-substitution (round-4 experiment)
-#endif
-#ifndef ADF_V_GLDS
-#define ADF_V_GLDS 0   // 1: LDS-DMA whole-line loads (round-3 experiment, kept for A/B: the pass gains nothing, see below)
-#endif
-// (short columns leave room for two workgroups per CU: their rings stay small enough not to take that away)
-template <int M> struct VRing { static constexpr int ITEMS = 3 * M / 2, WANT = M >= 18 ? 12 : 4, SLOTS = ITEMS < WANT ? ITEMS : WANT; };
-
-template <int N> __device__ __forceinline__ void v_wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
-__device__ __forceinline__ void v_wait_lds() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-__device__ __forceinline__ void v_glds16(const void* gsrc, unsigned lds_dst)
-{
-    unsigned keep;
-    asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
-                 : "=&s"(keep) : "v"(gsrc), "s"(lds_dst) : "memory");
-}
-
-struct VLoadCtx {
-    const char* bC; const char* b0;
-    unsigned lo, line_safe;        // byte offset of the NEXT line item's line / of row 0 of this strip (piece offset included)
-    unsigned wo, w_safe;           // byte offset of the NEXT weight item's row / of row 0 (row parity and piece included)
-    unsigned tile_b, r0, h, q;     // q = row parity this lane fetches in a weight item
-    unsigned ring;                 // LDS byte address of the wave's ring (SGPR)
-    unsigned rd;                   // this thread's read position inside a slot, as an offset into the dynamic LDS array
-};
-
-// items are issued in order, so the source offsets simply walk down the rows (rows live in tiles of TR rows:
-// consecutive rows are 128 bytes apart inside a tile and a tile apart, minus the rows already walked, at its end)
-template <int M, int K>
-__device__ __forceinline__ void v_issue(VLoadCtx& x)
-{
-    constexpr unsigned TR = ADF_TILE_ROWS;
-    if constexpr (K < VRing<M>::ITEMS) {
-        const unsigned slot = x.ring + (unsigned)(K % VRing<M>::SLOTS) * 1024u;
-        if constexpr (K % 3 == 2) {
-            const unsigned row = x.r0 + 2u * (K / 3) + x.q;
-            v_glds16(x.bC + (row < x.h ? x.wo : x.w_safe), slot);
-            x.wo += 128u;
-        } else {
-            constexpr unsigned i = K - K / 3;
-            v_glds16(x.b0 + (x.r0 + i < x.h ? x.lo : x.line_safe), slot);
-            x.lo += (((x.r0 + i + 1u) & (TR - 1u)) == 0u) ? x.tile_b - (TR - 1u) * 128u : 128u;
-        }
-    }
-}
-
-template <int M, int K>
-__device__ __forceinline__ void v_load_items(VLoadCtx& x, const char* lds, v2f (&c)[M], v2f (&f0)[M], v2f (&f1)[M])
-{
-    if constexpr (K < VRing<M>::ITEMS) {
-        constexpr int S = VRing<M>::SLOTS, T = VRing<M>::ITEMS;
-        v_wait_vm<(K + S - 1 < T ? S - 1 : T - 1 - K)>();
-        const char* s = lds + x.rd + (K % S) * 1024;      // (an index into the __shared__ array: ds_read with an immediate offset)
-        if constexpr (K % 3 == 2) {
-            c[2 * (K / 3)] = *reinterpret_cast<const v2f*>(s);
-            c[2 * (K / 3) + 1] = *reinterpret_cast<const v2f*>(s + 64);
-        } else {
-            f0[K - K / 3] = *reinterpret_cast<const v2f*>(s);
-            f1[K - K / 3] = *reinterpret_cast<const v2f*>(s + 64);
-        }
-        if constexpr (K + S < T) {
-            v_wait_lds();                                   // the slot has been read: it may be filled again
-            v_issue<M, K + S>(x);
-        }
-        v_load_items<M, K + 1>(x, lds, c, f0, f1);
-    }
-}
-
-template <int M, int K>
-__device__ __forceinline__ void v_prime(VLoadCtx& x)
-{
-    if constexpr (K < VRing<M>::SLOTS) { v_issue<M, K>(x); v_prime<M, K + 1>(x); }
-}
 
 // saturate_cast<short> of both columns of a thread, packed (low half = first column).  cvRound semantics as sat16() in
 // adf_internal.h: round half to even; NaN and anything outside the int range become INT_MIN and hence -32768; the clamp
@@ -159,7 +39,7 @@ __device__ __forceinline__ unsigned epi_pack16(v2f u0, v2f u1)
     v2f x = u0;
     if (EPI == EPI_WLS_CONF) {
         const v2f sc = vsplat(0x1p64f);
-        x = u0 * (vrcp_sel<true>(vfma(u1, sc, vsplat(ADF_EPS * 0x1p64f))) * sc);
+        x = u0 * (vrcp_nr(vfma(u1, sc, vsplat(ADF_EPS * 0x1p64f))) * sc);
     }
     const bool o0 = !(__builtin_fabsf(x.x) < 2147483648.0f), o1 = !(__builtin_fabsf(x.y) < 2147483648.0f);
     const int i0 = (int)(o0 ? -32768.0f : __builtin_rintf(x.x)), i1 = (int)(o1 ? -32768.0f : __builtin_rintf(x.y));
@@ -167,9 +47,7 @@ __device__ __forceinline__ unsigned epi_pack16(v2f u0, v2f u1)
     return __builtin_bit_cast(unsigned, (s2)__builtin_amdgcn_cvt_pk_i16(i0, i1));
 }
 
-// FS (round-4 experiment, ADF_V_STORE_IN_SOLVE): the rows are stored from inside the back-substitution; for the last pass
-// the launcher picks it when the packed 4-byte output stores apply (conditions uniform over the launch, checked on the host)
-template <int M, int R, int EPI, int VCW = VC, int NCH = 64, bool FS = false>
+template <int M, int R, int EPI, int VCW = VC, int NCH = 64>
 __global__ void __launch_bounds__(VT) wave_vpass_kernel(WavePassArgs a)
 {
     static_assert((VCW == 16 && NCH == 64) || (VCW == 8 && NCH == 128), "whole strips of 64 chunks or half strips of 128");
@@ -178,26 +56,8 @@ __global__ void __launch_bounds__(VT) wave_vpass_kernel(WavePassArgs a)
     __shared__ float nb[4][NCH][VCW];   // next-chunk exchange: GS0, GS1, PS, QS
     __shared__ float red[5][VCW][NCH];  // separator rows by (column, chunk)
     __shared__ float xs[2][VCW][NCH];   // separator solutions
-    extern __shared__ __align__(16) char vring[];   // R == 2: 8 waves x VRing<M>::SLOTS KiB (LDS-DMA landing zone)
     const int tid = threadIdx.x;
     const int xp = tid & (XPN - 1), cidx = tid / XPN;
-#ifdef ADF_V_STAGGER
-    // Experiment (tools/vstagger.sh): every workgroup of a pass runs the same program for the same time, so the CUs
-    // stay in step -- all loading, then all computing.  Delay the first round's workgroups by a fraction of the
-    // period so that later rounds inherit the offset.
-    {
-        const unsigned lin = blockIdx.y * gridDim.x + blockIdx.x;
-        if (lin < 256u) {
-            const unsigned g = (lin / 8u) % ADF_V_STAGGER;           // (blocks b, b+8, .. share an XCD)
-            for (unsigned k = 0; k < g * ADF_V_STAGGER_UNIT; k++) __builtin_amdgcn_s_sleep(127);
-        }
-    }
-#endif
-    ADF_STAMP(0); ADF_WSTAMP(0);
-#ifdef ADF_V_PHASE_TIMING
-    if (EPI == ADF_V_PHASE_EPI && threadIdx.x == 0)   // hwreg(HW_REG_XCC_ID) and hwreg(HW_REG_HW_ID), 32 bits each
-        adf_vphase[ADF_WG_ID * 8 + 7] = ((unsigned long long)__builtin_amdgcn_s_getreg(63508) << 32) | (unsigned)__builtin_amdgcn_s_getreg(63492);
-#endif
     // A strip row is a 64-byte half of a 128-byte line of a single right-hand-side plane (R == 1) and a
     // 32-byte quarter of a line of the int16 output; the rest of the line belongs to the neighbouring
     // strips (the pair plane of R == 2 and the weights are laid out so that this does not happen).  Blocks b,
@@ -234,7 +94,7 @@ __global__ void __launch_bounds__(VT) wave_vpass_kernel(WavePassArgs a)
     const unsigned pitch_b = (unsigned)a.pitch * (R > 1 ? 8u : 4u);
     // pair plane: [row tile][strip][row in tile][32 floats]; consecutive rows are 128 bytes apart inside a tile and a
     // tile apart (minus the rows already walked) at a tile boundary -- which rows those are depends on the chunk's start
-    constexpr unsigned TR = ADF_TILE_ROWS;
+    constexpr unsigned TR = TILE_ROWS;
     const unsigned tile_b = 2u * TR * (unsigned)a.pitch * 4u;            // bytes from a tile to the next one
 #define ADF_VSTEP(i) ((R > 1) ? (((((unsigned)r0 + (unsigned)(i) + 1u) & (TR - 1u)) == 0u) ? tile_b - (TR - 1u) * 128u : 128u) : pitch_b)
     const unsigned voff0 = (R > 1) ? (((unsigned)r0 / TR) * (2u * TR * (unsigned)a.pitch) + (unsigned)strip * (32u * TR) + ((unsigned)r0 % TR) * 32u + c16) * 4u
@@ -250,37 +110,12 @@ __global__ void __launch_bounds__(VT) wave_vpass_kernel(WavePassArgs a)
     const unsigned csafe = ((unsigned)strip * (unsigned)h * VC + c16) * 4u;
     v2f a_s = vsplat(0.0f);
     if (cidx > 0 && r0 - 1 < h) a_s = *reinterpret_cast<const v2f*>(bC + (coff0 - pitch_c)) * vsplat(a.lambda);
-    if constexpr (R > 1 && ADF_V_GLDS && VCW == VC) {
-        // Rows past the end of the column are fetched from row 0 of the same strip (always inside the planes) and NOT
-        // masked: Cvert is 0 in the last row (FGS.cpp:658-660), so whatever finite, diagonally dominant system those
-        // rows form is decoupled from the real one by exact zeros (0 * finite), and the stores below skip them.
-        VLoadCtx x;
-        x.bC = bC; x.b0 = b0;
-        const unsigned piece = 16u * (unsigned)xp;
-        x.line_safe = (unsigned)strip * (32u * TR) * 4u + piece;
-        // (an opaque copy of the chunk's first row: the row tests of the load phase must not be shared with the store
-        // phase's, or one register per row stays alive across the whole solve)
-        unsigned r0l = (unsigned)r0;
-        asm volatile("" : "+v"(r0l));
-        x.lo = ((r0l / TR) * (2u * TR * (unsigned)a.pitch) + (unsigned)strip * (32u * TR) + (r0l % TR) * 32u) * 4u + piece;
-        x.q = (unsigned)xp >> 2;
-        x.w_safe = ((unsigned)strip * (unsigned)h) * (VC * 4u) + 16u * ((unsigned)xp & 3u);
-        x.wo = ((unsigned)strip * (unsigned)h + r0l + x.q) * (VC * 4u) + 16u * ((unsigned)xp & 3u);
-        x.tile_b = tile_b; x.r0 = r0l; x.h = (unsigned)h;
-        char* ringp = vring + (tid >> 6) * (VRing<M>::SLOTS * 1024);
-        x.ring = __builtin_amdgcn_readfirstlane((unsigned)(size_t)ringp);
-        x.rd = (unsigned)((tid >> 6) * (VRing<M>::SLOTS * 1024) + ((tid >> 3) & 7) * 128 + xp * 8);
-        v_prime<M, 0>(x);
-        v_load_items<M, 0>(x, vring, c, f0, f1);
-        const v2f lam = vsplat(a.lambda);
-#pragma unroll
-        for (int i = 0; i < M; i++) c[i] *= lam;
-    } else {
-        // Rows past the end of the column are loaded from row 0 of the same column (always inside the
-        // planes, no load under a divergent branch) and NOT masked: Cvert is 0 in the last row
-        // (FGS.cpp:658-660), so whatever finite, diagonally dominant system those rows form is decoupled
-        // from the real one by exact zeros (0 * finite), and the stores below skip them.  Untouched
-        // loaded pairs stay where the load put them -- a select here would copy every pair.
+    // Rows past the end of the column are loaded from row 0 of the same column (always inside the
+    // planes, no load under a divergent branch) and NOT masked: Cvert is 0 in the last row
+    // (FGS.cpp:658-660), so whatever finite, diagonally dominant system those rows form is decoupled
+    // from the real one by exact zeros (0 * finite), and the stores below skip them.  Untouched
+    // loaded pairs stay where the load put them -- a select here would copy every pair.
+    {
         unsigned voff = voff0, coff = coff0;
         const v2f lam = vsplat(a.lambda);
 #pragma unroll
@@ -297,10 +132,8 @@ __global__ void __launch_bounds__(VT) wave_vpass_kernel(WavePassArgs a)
         for (int i = 0; i < M; i++) c[i] *= lam;
     }
 
-    ADF_DRAIN(); ADF_STAMP(1);
     Boundary2<R> bd;
     chunk_boundary2<M, R>(c, f0, f1, a_s, bd);
-    ADF_STAMP(2);
     *reinterpret_cast<v2f*>(&nb[0][cidx][2 * xp]) = bd.GS0;
     *reinterpret_cast<v2f*>(&nb[1][cidx][2 * xp]) = bd.GS1;
     *reinterpret_cast<v2f*>(&nb[2][cidx][2 * xp]) = bd.PS;
@@ -342,46 +175,7 @@ __global__ void __launch_bounds__(VT) wave_vpass_kernel(WavePassArgs a)
             xL0 = (v2f){xs[0][cc][cidx - 1], xs[0][cc + 1][cidx - 1]};
             xL1 = (v2f){xs[1][cc][cidx - 1], xs[1][cc + 1][cidx - 1]};
         }
-        ADF_STAMP(3);
-        // Round 4: a row is final the moment the back-substitution forms it; its store is issued
-        // there, under the remaining arithmetic, instead of in a loop of its own behind the solve.  The offsets walk
-        // UP the rows from the chunk's last one.
-        if constexpr (FS && EPI == EPI_PLANES) {
-            unsigned r0s = (unsigned)r0;
-            asm volatile("" : "+v"(r0s));        // (recomputed here: no load address stays alive across the sweeps)
-            const unsigned rl = r0s + (unsigned)(M - 1);
-            unsigned vo = (R > 1) ? ((rl / TR) * (2u * TR * (unsigned)a.pitch) + (unsigned)strip * (32u * TR) + (rl % TR) * 32u + c16) * 4u
-                                  : (rl * (unsigned)a.pitch + (unsigned)col) * 4u;
-            const int hv = h - (int)r0s;         // rows of this chunk inside the column
-            chunk_solve2<M, R>(c, f0, f1, a_s, xL0, xL1, xR0, xR1, [&](int i, v2f x0, v2f x1) {
-                if (i < hv) {
-                    *reinterpret_cast<v2f*>(b0 + vo) = x0;
-                    if (R > 1) *reinterpret_cast<v2f*>(b1 + vo) = x1;
-                }
-                if (i > 0) vo -= ADF_VSTEP(i - 1);
-            });
-            ADF_STAMP(4); ADF_STAMP(5); ADF_DRAIN(); ADF_STAMP(6); ADF_WSTAMP(1);
-            return;
-        } else if constexpr (FS) {
-            static_assert(!FS || EPI == EPI_PLANES || (R > 1 && EPI == EPI_WLS_CONF), "fused stores: plane passes and the disparity filter's last pass");
-            int r0e = r0, cole = col;
-            asm volatile("" : "+v"(r0e), "+v"(cole));
-            // (a wave-uniform base in scalar registers + one 32-bit offset per thread that walks up the rows)
-            char* obase = reinterpret_cast<char*>(a.out) + (ptrdiff_t)blockIdx.y * a.out_pair_stride + (ptrdiff_t)a.out_y0 * a.out_stride +
-                          (ptrdiff_t)a.out_x0 * 2;
-            const unsigned os = (unsigned)a.out_stride;
-            unsigned oo = (unsigned)(r0e + (M - 1)) * os + (unsigned)cole * 2u;
-            const int hv = (cole < a.nscan ? h : 0) - r0e;
-            chunk_solve2<M, R>(c, f0, f1, a_s, xL0, xL1, xR0, xR1, [&](int i, v2f x0, v2f x1) {
-                const unsigned v = epi_pack16<EPI>(x0, x1);
-                if (i < hv) *reinterpret_cast<unsigned*>(obase + oo) = v;
-                oo -= os;
-            });
-            ADF_STAMP(4); ADF_STAMP(5); ADF_DRAIN(); ADF_STAMP(6); ADF_WSTAMP(1);
-            return;
-        }
         chunk_solve2<M, R>(c, f0, f1, a_s, xL0, xL1, xR0, xR1);
-        ADF_STAMP(4);
     }
 
     unsigned voff = voff0;
@@ -484,39 +278,14 @@ __global__ void __launch_bounds__(VT) wave_vpass_kernel(WavePassArgs a)
         }
         }
     }
-    ADF_STAMP(5); ADF_DRAIN(); ADF_STAMP(6); ADF_WSTAMP(1);
-}
-
-// Dynamic LDS of a two-right-hand-side instantiation: the wave rings of the LDS-DMA loads (A/B build -DADF_V_GLDS=1 only).
-// Beyond 48 KiB the function needs its limit raised, per function AND device.  No "already done" memo: one keyed on the
-// function's TYPE -- identical for every instantiation -- would skip the attribute for all kernels but the first
-// (ADVICE r3); the call is cheap next to a pass and only this experimental build makes it.
-template <typename K>
-hipError_t v_allow_lds(K kernel, size_t bytes)
-{
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
 }
 
 template <int M, int VCW = VC, int NCH = 64>
 hipError_t launch_v(const WavePassArgs& a, int n_rhs, int epi, int n_pairs, hipStream_t st)
 {
     dim3 grid(a.pitch / VCW, n_pairs), block(VT);
-    const size_t ring = (size_t)(VT / 64) * VRing<M>::SLOTS * 1024;
-#define ADF_LVF(RR, EE, FF)                                                                                   \
-    do {                                                                                                      \
-        const size_t lds = ((RR) > 1 && ADF_V_GLDS && VCW == VC) ? ring : 0;                                  \
-        if (lds > 16 * 1024) {                                                                                \
-            hipError_t e = v_allow_lds(wave_vpass_kernel<M, RR, EE, VCW, NCH, FF>, lds);                      \
-            if (e != hipSuccess) return e;                                                                    \
-        }                                                                                                     \
-        hipLaunchKernelGGL((wave_vpass_kernel<M, RR, EE, VCW, NCH, FF>), grid, block, lds, st, a);            \
-    } while (0)
-#define ADF_LV(RR, EE) ADF_LVF(RR, EE, false)
-    // (the packed 4-byte stores of the last pass: single-channel output, even ROI width, everything 4-byte aligned)
-    const bool packed_out = a.out_cn == 1 && (a.nscan & 1) == 0 && ((a.out_x0 * 2) & 3) == 0 &&
-                            ((reinterpret_cast<uintptr_t>(a.out) | (uintptr_t)a.out_stride | (uintptr_t)a.out_pair_stride) & 3u) == 0;
-    if (n_rhs == 2 && epi == EPI_PLANES) ADF_LVF(2, EPI_PLANES, (ADF_V_STORE_IN_SOLVE & 1) != 0);
-    else if (n_rhs == 2 && epi == EPI_WLS_CONF && (ADF_V_STORE_IN_SOLVE & 2) && packed_out) ADF_LVF(2, EPI_WLS_CONF, (ADF_V_STORE_IN_SOLVE & 2) != 0);
+#define ADF_LV(RR, EE) hipLaunchKernelGGL((wave_vpass_kernel<M, RR, EE, VCW, NCH>), grid, block, 0, st, a)
+    if (n_rhs == 2 && epi == EPI_PLANES) ADF_LV(2, EPI_PLANES);
     else if (n_rhs == 2 && epi == EPI_WLS_CONF) ADF_LV(2, EPI_WLS_CONF);
     else if (n_rhs == 1 && epi == EPI_PLANES) ADF_LV(1, EPI_PLANES);
     else if (n_rhs == 1 && epi == EPI_I16) ADF_LV(1, EPI_I16);
@@ -527,7 +296,6 @@ hipError_t launch_v(const WavePassArgs& a, int n_rhs, int epi, int n_pairs, hipS
     else if (n_rhs == 2 && epi == EPI_U8) ADF_LV(2, EPI_U8);
     else return hipErrorInvalidValue;
 #undef ADF_LV
-#undef ADF_LVF
     return hipGetLastError();
 }
 

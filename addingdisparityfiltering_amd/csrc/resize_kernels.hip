@@ -31,13 +31,7 @@ namespace {
 // Source elements outside [vx0, vx1) x [vy0, vy1) read as zero when `zero_outside` is set: the low-resolution
 // confidence map is only written inside its ROI by the band kernel (DF.cpp:187-190: zero elsewhere), which saves the
 // separate fill launch.
-#ifndef ADF_RESIZE_RR
-#define ADF_RESIZE_RR 4
-#endif
-#ifndef ADF_RESIZE_TY
-#define ADF_RESIZE_TY 4
-#endif
-constexpr int RC = 4, RR = ADF_RESIZE_RR, TY = ADF_RESIZE_TY;
+constexpr int RC = 4, RR = 4, TY = 4;
 static_assert(RC == 4, "the vector stores below write four columns");
 
 //   VEC (scale_x <= 0.6 as well, i.e. the maps at most 0.6 of the view's width): the RC destination columns of a thread

@@ -1,6 +1,6 @@
 #!/bin/bash
 # A/B of library variants on the bench configurations (round 3).  usage: bash tools/ab_bench.sh variant [variant ...]
-# ("default" = libadf_wls.so, anything else = libadf_wls_<name>.so built with build.build_variant)
+# ("default" = libadf_wls.so, anything else = libadf_wls_<name>.so: another build of the library, e.g. of an older commit)
 cd "$GRAFT_REPO_ROOT"
 show='import sys,json; d=json.loads(sys.stdin.read()); print("   ", d["value"], d["ms_per_step"], {k:v["ms_per_step"] for k,v in d["kernels"].items()})'
 for v in "$@"; do
