@@ -356,94 +356,64 @@ struct FinalOut {
     int epilogue; void* out; ptrdiff_t stride, pair_stride; int x0, y0, cn, c;
 };
 
-static int run_passes_exact(const Geom& g, const SolvePlanes& p, int n_rhs, float lambda, float atten,
-                            int num_iter, const FinalOut& fo, int n_pairs, hipStream_t st, Profiler* prof = nullptr)
-{
-    float lam = lambda;
-    const double px = (double)g.rw * g.rh * n_pairs;
-    const double alg = (4.0 + 8.0 * n_rhs) * px;      // read weight + R rhs, write R rhs
-    const double moved = (12.0 + 16.0 * n_rhs) * px;  // exact solver: D and the eliminated rhs round-trip
-    for (int it = 0; it < num_iter; it++) {
-        PassArgs h{};
-        h.C = p.CH; h.U0 = p.A0; h.U1 = p.A1; h.D = p.D; h.F0 = p.F0; h.F1 = p.F1;
-        h.O0 = p.B0; h.O1 = p.B1;
-        h.nscan = g.rh; h.len = g.rw; h.pitch_in = g.ph; h.pitch_out = g.pw;
-        h.plane = g.plane; h.lambda = lam;
-        {
-            ProfScope ps(prof, K_PASS_H, alg, moved, st);
-            HIP_TRY(launch_exact_pass(h, n_rhs, EPI_PLANES, n_pairs, st)); // FGS.cpp:209
-        }
+// output bytes per pixel of a fused epilogue
+static double epilogue_bytes(int epilogue) { return epilogue == EPI_F32 ? 4.0 : epilogue == EPI_U8 ? 1.0 : 2.0; }
 
-        const bool last = (it == num_iter - 1);
-        PassArgs v{};
-        v.C = p.CV; v.U0 = p.B0; v.U1 = p.B1; v.D = p.D; v.F0 = p.F0; v.F1 = p.F1;
-        v.O0 = p.A0; v.O1 = p.A1;
-        v.nscan = g.rw; v.len = g.rh; v.pitch_in = g.pw; v.pitch_out = g.ph;
-        v.plane = g.plane; v.lambda = lam;
-        if (last) {
-            v.out = fo.out; v.out_stride = fo.stride; v.out_pair_stride = fo.pair_stride;
-            v.out_x0 = fo.x0; v.out_y0 = fo.y0; v.out_cn = fo.cn; v.out_c = fo.c;
-        }
-        {
-            // the fused epilogue writes 2 (int16) instead of 4R bytes per pixel
-            const double out_b = last ? (fo.epilogue == EPI_F32 ? 4.0 : fo.epilogue == EPI_U8 ? 1.0 : 2.0) * px : 4.0 * n_rhs * px;
-            ProfScope ps(prof, last ? K_PASS_V_LAST : K_PASS_V, (4.0 + 4.0 * n_rhs) * px + out_b,
-                         (12.0 + 12.0 * n_rhs) * px + out_b, st);
-            HIP_TRY(launch_exact_pass(v, n_rhs, last ? fo.epilogue : EPI_PLANES, n_pairs, st)); // FGS.cpp:210
-        }
-        lam *= atten;                                                      // FGS.cpp:211 (float)
-    }
-    return ADF_OK;
+template <class Args>
+static void set_final_out(Args& a, const FinalOut& fo)
+{
+    a.out = fo.out; a.out_stride = fo.stride; a.out_pair_stride = fo.pair_stride;
+    a.out_x0 = fo.x0; a.out_y0 = fo.y0; a.out_cn = fo.cn; a.out_c = fo.c;
 }
 
-// Same six passes with the on-chip partitioned solver: row-major planes, in place, algorithmic traffic.
-static int run_passes_wave(const Geom& g, const SolvePlanes& p, int n_rhs, float lambda, float atten,
-                           int num_iter, const FinalOut& fo, int n_pairs, hipStream_t st, Profiler* prof = nullptr,
-                           const WavePassArgs* fuse_first = nullptr)
+// The passes on either solver.  exact: the planes ping-pong between A and B, the horizontal pass reads the row index
+// fastest; wave: the on-chip partitioned solver, row-major planes solved in place.  `fuse` (wave only): the inputs the
+// first row pass forms its right-hand sides from.
+static int run_passes(bool wave, const Geom& g, const SolvePlanes& p, int n_rhs, float lambda, float atten, int num_iter,
+                      const FinalOut& fo, int n_pairs, hipStream_t st, Profiler* prof = nullptr,
+                      const FusedInputs* fuse = nullptr)
 {
-    float lam = lambda;
     const double px = (double)g.rw * g.rh * n_pairs;
-    const double alg = (4.0 + 8.0 * n_rhs) * px;
-    for (int it = 0; it < num_iter; it++) {
-        WavePassArgs h{};
-        h.C = p.CH; h.U0 = p.A0; h.U1 = p.A1;
-        h.nscan = g.rh; h.len = g.rw; h.pitch = g.pw; h.plane = g.plane; h.lambda = lam;
-        const bool fused = (it == 0 && fuse_first);
-        if (fused) {   // U1 = conf, U0 = conf*float(dL) formed in the pass (DF.cpp:288-290)
-            h.conf_in = fuse_first->conf_in; h.conf_frame = fuse_first->conf_frame; h.conf_pitch = fuse_first->conf_pitch;
-            h.conf_x0 = fuse_first->conf_x0; h.conf_y0 = fuse_first->conf_y0;
-            h.dl_in = fuse_first->dl_in; h.dl_stride = fuse_first->dl_stride; h.dl_pair_stride = fuse_first->dl_pair_stride;
-            h.dl_x0 = fuse_first->dl_x0; h.dl_y0 = fuse_first->dl_y0;
-            // ... or interpolated from the low-resolution maps in the pass (down-scaled path, DF.cpp:272-274)
-            h.lo_conf = fuse_first->lo_conf; h.lo_conf_stride = fuse_first->lo_conf_stride; h.lo_conf_pair = fuse_first->lo_conf_pair;
-            h.lo_dl = fuse_first->lo_dl; h.lo_dl_stride = fuse_first->lo_dl_stride; h.lo_dl_pair = fuse_first->lo_dl_pair;
-            h.lo_w = fuse_first->lo_w; h.lo_h = fuse_first->lo_h; h.hi_x0 = fuse_first->hi_x0; h.hi_y0 = fuse_first->hi_y0;
-            h.lo_scale_x = fuse_first->lo_scale_x; h.lo_scale_y = fuse_first->lo_scale_y; h.lo_post_scale = fuse_first->lo_post_scale;
-            h.lo_zero_outside = fuse_first->lo_zero_outside; h.lo_vx0 = fuse_first->lo_vx0; h.lo_vy0 = fuse_first->lo_vy0;
-            h.lo_vx1 = fuse_first->lo_vx1; h.lo_vy1 = fuse_first->lo_vy1; h.lo_taps = fuse_first->lo_taps; h.lo_half = fuse_first->lo_half;
+    float lam = lambda;
+    for (int it = 0; it < num_iter; it++, lam *= atten) {                      // FGS.cpp:211 (float)
+        const bool fused = it == 0 && fuse, last = it == num_iter - 1;
+        const int epi = last ? fo.epilogue : EPI_PLANES;
+        // algorithmic bytes: the row pass reads the weight + R right-hand sides and writes R -- fused, C + conf
+        // + dL read (low-resolution maps: their bytes per view pixel, each row counted once), U0/U1 written; the column
+        // pass writes the fused epilogue's output instead of 4R bytes per pixel on the last iteration
+        const double lo_b = (fused && fuse->lo_conf) ? 6.0 * fuse->lo_scale_x * fuse->lo_scale_y : 6.0;
+        const double hb = fused ? (4.0 + lo_b + 8.0) * px : (4.0 + 8.0 * n_rhs) * px;
+        const double out_b = (last ? epilogue_bytes(fo.epilogue) : 4.0 * n_rhs) * px;
+        const double vb = (4.0 + 4.0 * n_rhs) * px + out_b;
+        if (wave) {
+            WavePassArgs h{}, v{};
+            h.C = p.CH; h.U0 = p.A0; h.U1 = p.A1;
+            h.nscan = g.rh; h.len = g.rw; h.pitch = g.pw; h.plane = g.plane; h.lambda = lam;
+            if (fused) h.fuse = *fuse;
+            v.C = p.CV; v.U0 = p.A0; v.U1 = p.A1;
+            v.nscan = g.rw; v.len = g.rh; v.pitch = g.pw; v.plane = g.plane; v.lambda = lam;
+            if (last) set_final_out(v, fo);
+            {
+                ProfScope ps(prof, fused ? K_PASS_H_FIRST : K_PASS_H, hb, hb, st);
+                HIP_TRY(launch_wave_hpass(h, n_rhs, n_pairs, st));             // FGS.cpp:209
+            }
+            ProfScope ps(prof, last ? K_PASS_V_LAST : K_PASS_V, vb, vb, st);
+            HIP_TRY(launch_wave_vpass(v, n_rhs, epi, n_pairs, st));           // FGS.cpp:210
+        } else {
+            // moved bytes: the exact solver's D and eliminated right-hand sides round-trip through memory
+            PassArgs h{}, v{};
+            h.C = p.CH; h.U0 = p.A0; h.U1 = p.A1; h.D = p.D; h.F0 = p.F0; h.F1 = p.F1; h.O0 = p.B0; h.O1 = p.B1;
+            h.nscan = g.rh; h.len = g.rw; h.pitch_in = g.ph; h.pitch_out = g.pw; h.plane = g.plane; h.lambda = lam;
+            v.C = p.CV; v.U0 = p.B0; v.U1 = p.B1; v.D = p.D; v.F0 = p.F0; v.F1 = p.F1; v.O0 = p.A0; v.O1 = p.A1;
+            v.nscan = g.rw; v.len = g.rh; v.pitch_in = g.pw; v.pitch_out = g.ph; v.plane = g.plane; v.lambda = lam;
+            if (last) set_final_out(v, fo);
+            {
+                ProfScope ps(prof, K_PASS_H, hb, (12.0 + 16.0 * n_rhs) * px, st);
+                HIP_TRY(launch_exact_pass(h, n_rhs, EPI_PLANES, n_pairs, st)); // FGS.cpp:209
+            }
+            ProfScope ps(prof, last ? K_PASS_V_LAST : K_PASS_V, vb, (12.0 + 12.0 * n_rhs) * px + out_b, st);
+            HIP_TRY(launch_exact_pass(v, n_rhs, epi, n_pairs, st));           // FGS.cpp:210
         }
-        {
-            // C + conf + dL read, U0/U1 written (low-resolution maps: their bytes per view pixel, each row counted once)
-            const double lo_b = (fused && fuse_first->lo_conf) ? 6.0 * fuse_first->lo_scale_x * fuse_first->lo_scale_y : 6.0;
-            const double b = fused ? (4.0 + lo_b + 8.0) * px : alg;
-            ProfScope ps(prof, fused ? K_PASS_H_FIRST : K_PASS_H, b, b, st);
-            HIP_TRY(launch_wave_hpass(h, n_rhs, n_pairs, st));             // FGS.cpp:209
-        }
-        const bool last = (it == num_iter - 1);
-        WavePassArgs v{};
-        v.C = p.CV; v.U0 = p.A0; v.U1 = p.A1;
-        v.nscan = g.rw; v.len = g.rh; v.pitch = g.pw; v.plane = g.plane; v.lambda = lam;
-        if (last) {
-            v.out = fo.out; v.out_stride = fo.stride; v.out_pair_stride = fo.pair_stride;
-            v.out_x0 = fo.x0; v.out_y0 = fo.y0; v.out_cn = fo.cn; v.out_c = fo.c;
-        }
-        {
-            const double out_b = last ? (fo.epilogue == EPI_F32 ? 4.0 : fo.epilogue == EPI_U8 ? 1.0 : 2.0) * px : 4.0 * n_rhs * px;
-            const double bytes = (4.0 + 4.0 * n_rhs) * px + out_b;
-            ProfScope ps(prof, last ? K_PASS_V_LAST : K_PASS_V, bytes, bytes, st);
-            HIP_TRY(launch_wave_vpass(v, n_rhs, last ? fo.epilogue : EPI_PLANES, n_pairs, st)); // FGS.cpp:210
-        }
-        lam *= atten;                                                      // FGS.cpp:211 (float)
     }
     return ADF_OK;
 }
@@ -456,6 +426,15 @@ static bool wave_fits(const Geom& g)
 // ----------------------------------------------------------------------------------------------
 // DisparityWLSFilter
 // ----------------------------------------------------------------------------------------------
+// The down-scaled path's low-resolution confidence maps and what cv::resize of them into the handle's view-sized planes
+// needs (DF.cpp:274).
+struct ConfResize {
+    float* clo; int dW, dH; adf_rect rlo; // the maps (W = dW pitch, one per pair) and their ROI
+    Geom ghi;                             // the view's geometry
+    bool band_map;                        // the band kernel made them: zero outside the ROI (DF.cpp:187-190)
+    int n_pairs;
+};
+
 struct adf_wls {
     int device = 0;
     // DF.cpp:142-159
@@ -493,10 +472,7 @@ struct adf_wls {
     bool overlap = true;
     // Down-scaled call whose first row pass interpolated the maps itself: the view-sized confidence map of
     // getConfidenceMap() (DF.cpp:274) has not been materialised; adf_wls_get_confidence_* runs the float resize then.
-    struct LazyConf {
-        bool pending = false;
-        const float* clo = nullptr; int dW = 0, dH = 0; adf_rect rlo{0, 0, 0, 0}; Geom ghi{}; bool band_map = false; int n_pairs = 0;
-    } lazy_conf;
+    struct LazyConf { bool pending = false; ConfResize resize{}; } lazy_conf;
     bool scaled_half = true; // ADF_LO_HALF=0: never the half-width form of the fused low-resolution prologue (A/B, tests)
     bool scaled_fuse = true; // ADF_SCALED_FUSE=0: the down-scaled path through the two resize kernels (A/B measurements)
     bool conf_band = true;   // ADF_CONF_BAND=0: the two-kernel confidence stage (A/B measurements)
@@ -630,25 +606,237 @@ static size_t wls_pair_ws_bytes(const Geom& g, bool conf, bool wave, bool disc_m
     return planes * g.plane * sizeof(float) + (conf && disc_maps ? 2 * g.frame * sizeof(float) : 0);
 }
 
-// What the down-scaled path queues where a same-size call runs its confidence kernels: the low-resolution confidence
-// map and the two resizes, for ALL pairs of the call, on the caller's stream -- i.e. beside the weight kernel, which
-// wls_filter_impl has forked to the side stream by then.
-struct ScaledStage;
-static int run_scaled_stage(const ScaledStage& s, hipStream_t st, Profiler* prof, int part);
-// fills `fuse` with the low-resolution form of the fused first row pass for the chunk starting at pair `first`, when the
-// stage asked for it; false = the resize kernels run
-static bool scaled_fuse_lo(const ScaledStage& s, int first, const Geom& g, WavePassArgs& fuse);
-static void scaled_note_lazy_conf(const ScaledStage& s);
-static int scaled_resize_conf_now(const ScaledStage& s, hipStream_t st, Profiler* prof);
+// DF.cpp:228-233: the caller's ROI, or what the handle's offsets leave of a w x hgt map
+static int resolve_roi(const adf_wls* h, const adf_rect* roi_in, int w, int hgt, adf_rect& roi)
+{
+    if (roi_in && roi_in->width * roi_in->height != 0) roi = *roi_in;
+    else roi = adf_rect{h->left_offset, h->top_offset, w - h->left_offset - h->right_offset, hgt - h->top_offset - h->bottom_offset};
+    if (roi.width <= 0 || roi.height <= 0 || roi.x < 0 || roi.y < 0 || roi.x + roi.width > w || roi.y + roi.height > hgt)
+        return fail(ADF_ESIZE, "ROI (%d,%d,%d,%d) does not fit a %dx%d map", roi.x, roi.y, roi.width, roi.height, w, hgt);
+    return ADF_OK;
+}
 
-// conf_given: the down-scaled path (DF.cpp:274): the confidence kernels are skipped and dispR is not used; `scaled`
-// (may be null) fills h->conf with the view-sized confidence planes of all pairs and produces dispL itself.
+// DF.cpp:262-264: the right map of a confidence-mode call on maps w wide
+static int check_right_map(const int16_t* dispR, ptrdiff_t sR, int w)
+{
+    if (!dispR) return fail(ADF_EBADARG, "disparity_map_right is required with use_confidence");
+    if (sR < (ptrdiff_t)w * 2) return fail(ADF_ESIZE, "right disparity stride smaller than a row");
+    return ADF_OK;
+}
+
+static int check_radius(const adf_wls* h)
+{
+    if (h->disc_radius < 0 || h->disc_radius > max_disc_radius())
+        return fail(ADF_EBADARG, "depth discontinuity radius %d outside [0,%d]", h->disc_radius, max_disc_radius());
+    return ADF_OK;
+}
+
+// Stand-in for a device block that is not allocated yet, in alignment checks: hipMalloc returns 256-byte aligned memory.
+static float* const UNALLOCATED = reinterpret_cast<float*>(uintptr_t(256));
+
+// The wave solver's fit checks take a pass's arguments: those of a first row pass of `len` columns fed from `f`.
+static WavePassArgs first_pass_probe(const FusedInputs& f, int len)
+{
+    WavePassArgs a{};
+    a.fuse = f; a.len = len;
+    return a;
+}
+
+// Fused first row pass at view resolution: U1 = conf, U0 = conf*float(dL) read from the confidence planes and the left
+// disparity maps of the pairs from `conf` / `dl` on (DF.cpp:288-290).
+static FusedInputs view_fuse(const float* conf, const int16_t* dl, ptrdiff_t sL, ptrdiff_t psL, const Geom& g)
+{
+    FusedInputs f{};
+    f.conf_in = conf; f.conf_frame = g.cframe; f.conf_pitch = g.cpitch; f.conf_x0 = g.cx0 + g.rx; f.conf_y0 = g.ry;
+    f.dl_in = dl; f.dl_stride = sL; f.dl_pair_stride = psL; f.dl_x0 = g.rx; f.dl_y0 = g.ry;
+    return f;
+}
+
+// The down-scaled path's own work (DF.cpp:239-247, 268-277) for ALL pairs of a call.  adf_wls_filter_scaled_device
+// decides and allocates it; wls_filter_impl queues it on the caller's stream where a same-size call runs its confidence
+// kernels -- beside the weight kernel, which it has forked to the side stream by then and which needs the view only.
+// Measured at 64 x 4K views / 1080p maps: everything after the fork 13.8-14.1 / 13.8-14.0 ms per call (radius 2 / 5; the
+// band kernel crawls beside the weight kernel's small workgroups, 0.44 -> 0.9-1.7 ms, but the resizes then run alone),
+// the low-resolution confidence map before the fork 14.20 / 14.51 (two memory-bound kernels side by side gain nothing),
+// no overlap at all 14.49 / 14.69.
+struct ScaledStage {
+    const int16_t* dispL; ptrdiff_t sL, psL;   // the caller's low-resolution maps
+    const int16_t* dispR; ptrdiff_t sR, psR;
+    float resize_factor, x_ratio;              // DF.cpp:225, 241
+    char* dhi; size_t dhi_bytes;               // the resized left maps (not with fuse_lo)
+    float *cl, *cr;                            // low-resolution discontinuity maps
+    ConfResize lo;                             // low-resolution confidence maps, both geometries, pair count
+    bool fuse_lo;                              // the first row pass interpolates the low-resolution maps itself ...
+    float* taps;                               // ... with this scratch for the columns' source coordinates
+};
+
+// Fused first row pass in its low-resolution form, for the pairs from `first` on (DF.cpp:272-274 then 288-290).
+static FusedInputs lo_fuse(const adf_wls* h, const ScaledStage& s, int first, const Geom& g)
+{
+    const ConfResize& c = s.lo;
+    const size_t lo = (size_t)c.dW * c.dH;
+    FusedInputs f{};
+    f.lo_conf = c.clo + (size_t)first * lo; f.lo_conf_stride = c.dW; f.lo_conf_pair = (ptrdiff_t)lo;
+    f.lo_dl = (const int16_t*)((const char*)s.dispL + (ptrdiff_t)first * s.psL); f.lo_dl_stride = s.sL; f.lo_dl_pair = s.psL;
+    f.lo_w = c.dW; f.lo_h = c.dH; f.hi_x0 = g.rx; f.hi_y0 = g.ry;
+    f.lo_scale_x = (double)c.dW / c.ghi.W; f.lo_scale_y = (double)c.dH / c.ghi.H; f.lo_post_scale = s.x_ratio;
+    if (c.band_map) {
+        f.lo_zero_outside = 1; f.lo_vx0 = c.rlo.x; f.lo_vy0 = c.rlo.y; f.lo_vx1 = c.rlo.x + c.rlo.width; f.lo_vy1 = c.rlo.y + c.rlo.height;
+    }
+    f.lo_taps = s.taps; f.lo_half = h->scaled_half ? 1 : 0;
+    return f;
+}
+
+// cv::resize of the low-resolution confidence maps into the handle's view-sized planes (DF.cpp:274)
+static int resize_conf_planes(adf_wls_t* h, const ConfResize& c, hipStream_t st, Profiler* prof)
+{
+    const size_t lo = (size_t)c.dW * c.dH;
+    const Geom& ghi = c.ghi;
+    const double Fhi = (double)ghi.W * ghi.H * c.n_pairs;
+    ResizeArgs rc32{c.clo, (ptrdiff_t)c.dW * 4, (ptrdiff_t)(lo * 4), c.dW, c.dH, (float*)h->conf.p + ghi.cx0, (ptrdiff_t)ghi.cpitch * 4,
+                    (ptrdiff_t)(ghi.cframe * 4), ghi.W, ghi.H, (double)c.dW / ghi.W, (double)c.dH / ghi.H, 1.0f, 0};
+    if (c.band_map) { rc32.zero_outside = 1; rc32.vx0 = c.rlo.x; rc32.vy0 = c.rlo.y; rc32.vx1 = c.rlo.x + c.rlo.width; rc32.vy1 = c.rlo.y + c.rlo.height; }
+    ProfScope ps(prof, K_RESIZE, 4.0 * Fhi + 4.0 * (double)lo * c.n_pairs, 4.0 * Fhi + 4.0 * (double)lo * c.n_pairs, st);
+    HIP_TRY(launch_resize_linear(rc32, c.n_pairs, st));
+    return ADF_OK;
+}
+
+// The low-resolution confidence maps of all pairs (DF.cpp:197-210 at the maps' resolution, DF.cpp:318, 359).
+static int scaled_conf_map(adf_wls_t* h, const ScaledStage& s, hipStream_t st, Profiler* prof)
+{
+    const ConfResize& c = s.lo;
+    const Geom glo = plain_conf_layout(make_geom(c.dW, c.dH, c.rlo.x, c.rlo.y, c.rlo.width, c.rlo.height));
+    const size_t lo = (size_t)c.dW * c.dH;
+    const double Plo = (double)c.rlo.width * c.rlo.height * c.n_pairs;
+    const int rrx = c.dW - (c.rlo.x + c.rlo.width);                       // DF.cpp:202
+    const float roll_off = h->roll_off / (s.resize_factor * s.resize_factor);   // DF.cpp:359
+    const int thresh_lo = (int)(s.resize_factor * h->lrc_thresh);       // DF.cpp:318
+    if (c.band_map) {
+        // the one-sweep kernel at the maps' resolution: ROI pixels from the band kernel, zeros outside (DF.cpp:187-190)
+        ConfBandArgs ba{s.dispL, s.sL, s.psL, s.dispR, s.sR, s.psR, c.clo, glo, rrx, thresh_lo, h->disc_radius, roll_off, 0};
+        ProfScope ps(prof, K_LRC, 8.0 * Plo, 8.0 * Plo, st);
+        HIP_TRY(launch_conf_band(ba, c.n_pairs, st));                    // DF.cpp:197-210
+        return ADF_OK;
+    }
+    DiscArgs da{{s.dispL, s.dispR}, {s.sL, s.sR}, {s.psL, s.psR}, {c.rlo.x, rrx}, c.rlo.y, c.rlo.width, c.rlo.height,
+                h->disc_radius, roll_off, {s.cl, s.cr}, c.dW, lo, -1};
+    {
+        ProfScope ps(prof, K_DISC, 4.0 * Plo, 12.0 * Plo, st);
+        HIP_TRY(launch_discontinuity(da, c.n_pairs, st));                // DF.cpp:204
+    }
+    LrcArgs la{s.dispL, s.sL, s.psL, s.dispR, s.sR, s.psR, s.cl, s.cr, c.clo, nullptr, 0, 0, 0, nullptr, nullptr, glo, rrx, thresh_lo, ORIENT_N};
+    ProfScope ps(prof, K_LRC, 4.0 * (double)lo * c.n_pairs, 4.0 * (double)lo * c.n_pairs + 12.0 * Plo, st);
+    HIP_TRY(launch_lrc_prologue(la, c.n_pairs, st));                     // DF.cpp:208-209
+    return ADF_OK;
+}
+
+// The resizes to the view: the confidence maps (DF.cpp:274) and the left disparity maps (DF.cpp:243-244, 272-273).
+static int scaled_resize(adf_wls_t* h, const ScaledStage& s, hipStream_t st, Profiler* prof)
+{
+    const ConfResize& c = s.lo;
+    int rc = h->use_confidence ? resize_conf_planes(h, c, st, prof) : ADF_OK;
+    if (rc) return rc;
+    const int W = c.ghi.W, H = c.ghi.H;
+    const size_t lo = (size_t)c.dW * c.dH;
+    const double Fhi = (double)W * H * c.n_pairs;
+    ResizeArgs r16{s.dispL, s.sL, s.psL, c.dW, c.dH, s.dhi, (ptrdiff_t)W * 2, (ptrdiff_t)s.dhi_bytes, W, H, (double)c.dW / W, (double)c.dH / H, s.x_ratio, 1};
+    ProfScope ps(prof, K_RESIZE, 2.0 * Fhi + 2.0 * (double)lo * c.n_pairs, 2.0 * Fhi + 2.0 * (double)lo * c.n_pairs, st);
+    HIP_TRY(launch_resize_linear(r16, c.n_pairs, st));
+    return ADF_OK;
+}
+
+// How a WLS filter call makes the two right-hand sides conf*disp and conf (DF.cpp:286-290), or float(disp) without
+// confidence (DF.cpp:257).
+enum ConfStage {
+    CONF_NONE,        // no confidence: the plain prologue
+    CONF_SCALED,      // down-scaled: low-resolution confidence map, both resizes, then the prologue or the fused first pass
+    CONF_SCALED_LO,   // down-scaled: low-resolution confidence map; the first row pass interpolates it and the disparity map
+    CONF_MERGED,      // weights + one-sweep confidence map + fill outside the ROI in one launch (small calls)
+    CONF_BAND,        // both views' maps, LRC and x255 in one band sweep: the right view's map lives in LDS only
+    CONF_LEFT,        // the right view's map, then the left one + LRC + x255 in one sweep (cL never hits memory)
+    CONF_TWO_KERNEL,  // both views' maps, then LRC + x255 + the right-hand sides (and the fill outside the ROI)
+};
+
+// What one chunk of pairs queues.
+struct ChunkPlan {
+    ConfStage stage;
+    bool fork_weights;     // the weight kernel runs on the side stream, beside the confidence kernels
+    bool outside_on_side;  // ... behind the fill outside the ROI
+};
+
+// What a WLS filter call queues, decided before its chunk loop.
+struct WlsPlan {
+    bool wave;                // the wave solver (else the exact one)
+    bool fused_first;         // the first row pass forms its right-hand sides itself (no prologue planes)
+    bool band;                // the one-sweep confidence kernel: no full-frame discontinuity maps in the workspace
+    size_t per_pair; int chunk;
+    // chunks of `chunk` pairs, and a shorter last one: the merged launch is for small calls, so it depends on the
+    // chunk's pair count
+    ChunkPlan full, tail;
+    int path;                 // ADF_PATH_* bits
+};
+
+static ChunkPlan plan_chunk(const adf_wls* h, ConfStage stage, bool wave)
+{
+    // confidence mode: the weights depend on the guide only and the confidence kernels on the disparity maps only -- one
+    // is bound by memory latency, the others lean on the vector ALUs -- so the weight kernel is forked onto the side
+    // stream and joined before the first solve pass (not beside the merged launch, which computes it)
+    const bool fork = stage != CONF_NONE && stage != CONF_MERGED && h->overlap;
+    // the fill of everything outside the ROI (DF.cpp:284, :187-190) touches no pixel any other kernel of the call
+    // touches: on the wave path it rides the side stream too instead of sitting between the confidence kernel and the
+    // first solve pass (one dependent launch less on the critical path of a single-pair call) -- and it goes FIRST
+    // there: alone it takes 0.08 ms of a 64 x 4K step on the StereoBM factory's ROI, but queued behind the weight kernel
+    // it starts when the confidence kernel's workgroups hold nearly every register of every CU and crawls through 0.8 ms
+    // as the call's tail (round 3).  The two-kernel stage fills in its LRC kernel.
+    return ChunkPlan{stage, fork, fork && wave && stage != CONF_TWO_KERNEL};
+}
+
+static WlsPlan plan_wls(const adf_wls* h, const Geom& g, int n_pairs, const int16_t* dispL, ptrdiff_t sL, ptrdiff_t psL,
+                        ptrdiff_t sG, int gch, const ScaledStage* scaled)
+{
+    WlsPlan p{};
+    const bool conf = h->use_confidence;
+    // sizes outside the register-resident kernels' range fall back to the exact solver
+    p.wave = h->solver == ADF_SOLVER_WAVE && wave_fits(g);
+    ConfStage stage = !conf ? CONF_NONE
+                    : scaled ? (scaled->fuse_lo ? CONF_SCALED_LO : CONF_SCALED)
+                    : (p.wave && h->disc_radius <= conf_left_max_radius()) ? CONF_LEFT : CONF_TWO_KERNEL;
+    // The view-resolution form of the fused first pass has alignment conditions that depend only on the geometry, the
+    // strides and the pointers known here, not on the chunk.
+    const float* planes = h->conf.p ? (const float*)h->conf.p : UNALLOCATED;
+    p.fused_first = stage == CONF_SCALED_LO ||
+                    ((stage == CONF_SCALED || stage == CONF_LEFT) && p.wave &&
+                     wave_hpass_can_fuse(first_pass_probe(view_fuse(planes, dispL, sL, psL, g), g.rw)));
+    // the band kernel writes no right-hand sides: it needs the fused first pass
+    p.band = stage == CONF_LEFT && p.fused_first && h->conf_band && conf_band_fits(g, h->disc_radius);
+    if (p.band) stage = CONF_BAND;
+    p.per_pair = wls_pair_ws_bytes(g, conf, p.wave, !p.band);
+    p.chunk = (int)(h->ws_limit / p.per_pair);
+    if (p.chunk < 1) p.chunk = 1;
+    if (p.chunk > n_pairs) p.chunk = n_pairs;
+    auto chunk_of = [&](int n) {
+        const bool merged = p.band && h->merge_small && prep_small_fits(g, h->disc_radius, gch, n) && prep_small_guide_fits(g, sG, gch);
+        return plan_chunk(h, merged ? CONF_MERGED : stage, p.wave);
+    };
+    p.full = chunk_of(p.chunk);
+    p.tail = chunk_of(n_pairs % p.chunk ? n_pairs % p.chunk : p.chunk);
+    p.path = ((p.band || (scaled && scaled->lo.band_map)) ? ADF_PATH_CONF_BAND : 0) |
+             (p.fused_first ? ADF_PATH_FUSED_FIRST_PASS : 0) |
+             ((p.full.stage == CONF_MERGED || p.tail.stage == CONF_MERGED) ? ADF_PATH_MERGED_PREP : 0);
+    if (stage == CONF_SCALED_LO)
+        p.path |= ADF_PATH_SCALED_FUSED |
+                  (wave_hpass_lo_half(first_pass_probe(lo_fuse(h, *scaled, 0, g), g.rw)) ? ADF_PATH_SCALED_HALF : 0);
+    return p;
+}
+
+// scaled: the down-scaled path (DF.cpp:274): its stage replaces the confidence kernels, dispR is not used, and dispL is
+// the stage's resized map (with fuse_lo only a stand-in that is never dereferenced).
 static int wls_filter_impl(adf_wls_t* h, int n_pairs,
                            const int16_t* dispL, ptrdiff_t sL, ptrdiff_t psL,
                            const uint8_t* view, ptrdiff_t sG, ptrdiff_t psG, int gch, int W, int H,
                            int16_t* out, ptrdiff_t sO, ptrdiff_t psO,
                            const int16_t* dispR, ptrdiff_t sR, ptrdiff_t psR,
-                           const adf_rect* roi_in, bool conf_given, hipStream_t st, const ScaledStage* scaled = nullptr)
+                           const adf_rect* roi_in, hipStream_t st, const ScaledStage* scaled = nullptr)
 {
     NEED_HANDLE(h);
     // DF.cpp:221-222
@@ -658,22 +846,13 @@ static int wls_filter_impl(adf_wls_t* h, int n_pairs,
     if (n_pairs < 1) return fail(ADF_EBADARG, "n_pairs must be >= 1");
     if (sL < (ptrdiff_t)W * 2 || sO < (ptrdiff_t)W * 2 || sG < (ptrdiff_t)W * gch)
         return fail(ADF_ESIZE, "row stride smaller than a row");
-    if (h->use_confidence && !conf_given) { // DF.cpp:262-264
-        if (!dispR) return fail(ADF_EBADARG, "disparity_map_right is required with use_confidence");
-        if (sR < (ptrdiff_t)W * 2) return fail(ADF_ESIZE, "right disparity stride smaller than a row");
-    }
+    const bool conf = h->use_confidence;
+    int rc;
+    if (conf && !scaled && (rc = check_right_map(dispR, sR, W))) return rc;
     if (h->lambda < 0 || h->sigma_color < 0) return fail(ADF_EBADARG, "lambda and sigma_color must be >= 0 (FGS.cpp:143)");
-    // DF.cpp:228-233
     adf_rect roi;
-    if (roi_in && roi_in->width * roi_in->height != 0) roi = *roi_in;
-    else roi = adf_rect{h->left_offset, h->top_offset, W - h->left_offset - h->right_offset,
-                        H - h->top_offset - h->bottom_offset};
-    if (roi.width <= 0 || roi.height <= 0 || roi.x < 0 || roi.y < 0 || roi.x + roi.width > W ||
-        roi.y + roi.height > H)
-        return fail(ADF_ESIZE, "ROI (%d,%d,%d,%d) does not fit a %dx%d map", roi.x, roi.y, roi.width,
-                    roi.height, W, H);
-    if (h->use_confidence && (h->disc_radius < 0 || h->disc_radius > max_disc_radius()))
-        return fail(ADF_EBADARG, "depth discontinuity radius %d outside [0,%d]", h->disc_radius, max_disc_radius());
+    if ((rc = resolve_roi(h, roi_in, W, H, roi))) return rc;
+    if (conf && (rc = check_radius(h))) return rc;
 
     DeviceScope ds(h->device);
     const Geom g = make_geom(W, H, roi.x, roi.y, roi.width, roi.height);
@@ -681,33 +860,14 @@ static int wls_filter_impl(adf_wls_t* h, int n_pairs,
     h->roi = roi; h->last_W = W; h->last_H = H; h->last_pairs = n_pairs;
     h->last_cpitch = g.cpitch; h->last_cx0 = g.cx0; h->last_path = 0;
 
-    int rc = h->lut.ensure((float)h->sigma_color, st);
-    if (rc) return rc;
-    const bool conf = h->use_confidence;
-    // sizes outside the register-resident kernels' range fall back to the exact solver
-    const bool wave = h->solver == ADF_SOLVER_WAVE && wave_fits(g);
+    if ((rc = h->lut.ensure((float)h->sigma_color, st))) return rc;
+    const WlsPlan plan = plan_wls(h, g, n_pairs, dispL, sL, psL, sG, gch, scaled);
+    const bool wave = plan.wave;
     h->last_solver = wave ? ADF_SOLVER_WAVE : ADF_SOLVER_EXACT;
-    // does the one-sweep confidence kernel run (both views' maps stay on chip)?  It needs the fused first row pass,
-    // whose alignment conditions depend only on the geometry, the strides and the pointers known here.
-    bool band = false;
-    if (conf && !conf_given && wave && h->conf_band && conf_band_fits(g, h->disc_radius)) {
-        WavePassArgs probe{};
-        probe.conf_in = (const float*)h->conf.p; probe.conf_frame = g.cframe; probe.conf_pitch = g.cpitch; probe.conf_x0 = g.cx0 + roi.x; probe.conf_y0 = roi.y;
-        probe.dl_in = dispL; probe.dl_stride = sL; probe.dl_pair_stride = psL; probe.dl_x0 = roi.x; probe.dl_y0 = roi.y;
-        probe.len = g.rw;
-        // (h->conf.p may still be null or about to be re-allocated: hipMalloc returns 256-byte aligned memory either way)
-        if (!probe.conf_in) probe.conf_in = reinterpret_cast<const float*>(uintptr_t(256));
-        band = wave_hpass_can_fuse(probe);
-    }
-    const size_t per_pair = wls_pair_ws_bytes(g, conf, wave, !band);
-    int chunk = (int)(h->ws_limit / per_pair);
-    if (chunk < 1) chunk = 1;
-    if (chunk > n_pairs) chunk = n_pairs;
-    if ((rc = h->ws.reserve(per_pair * (size_t)chunk, st))) return rc;
-    if (conf && !conf_given && (rc = ensure_conf_planes(h, g, n_pairs, st))) return rc;
-
+    if ((rc = h->ws.reserve(plan.per_pair * (size_t)plan.chunk, st))) return rc;
+    if (conf && !scaled && (rc = ensure_conf_planes(h, g, n_pairs, st))) return rc;
     {
-        const long long sig[8] = {W, H, roi.x, roi.y, roi.width, roi.height, (long long)band * 4 + (long long)wave * 2 + conf, chunk};
+        const long long sig[8] = {W, H, roi.x, roi.y, roi.width, roi.height, (long long)plan.band * 4 + (long long)wave * 2 + conf, plan.chunk};
         if (memcmp(sig, h->ws_sig, sizeof(sig)) != 0) {
             HIP_TRY(hipMemsetAsync(h->ws.p, 0, h->ws.bytes, st));
             memcpy(h->ws_sig, sig, sizeof(sig));
@@ -715,7 +875,7 @@ static int wls_filter_impl(adf_wls_t* h, int n_pairs,
     }
     // carve the workspace
     float* base = (float*)h->ws.p;
-    auto take = [&](size_t elems) { float* p = base; base += elems * (size_t)chunk; return p; };
+    auto take = [&](size_t elems) { float* p = base; base += elems * (size_t)plan.chunk; return p; };
     SolvePlanes p{};
     p.CH = take(g.plane); p.CV = take(g.plane); p.A0 = take(g.plane);
     if (!wave) { p.D = take(g.plane); p.F0 = take(g.plane); p.B0 = take(g.plane); }
@@ -723,7 +883,7 @@ static int wls_filter_impl(adf_wls_t* h, int n_pairs,
     if (conf) {
         p.A1 = take(g.plane);                     // wave: directly behind A0 (the pair plane spans both)
         if (!wave) { p.F1 = take(g.plane); p.B1 = take(g.plane); }
-        if (!band) { cL = take(g.frame); cR = take(g.frame); }
+        if (!plan.band) { cL = take(g.frame); cR = take(g.frame); }
     }
     // exact: the horizontal pass wants the row index fastest (T); wave: row-major (N), except that two
     // right-hand sides share one interleaved pair plane (A0 and A1 are adjacent: 2*plane floats per
@@ -731,168 +891,119 @@ static int wls_filter_impl(adf_wls_t* h, int n_pairs,
     const int orient_h = wave ? ORIENT_N : ORIENT_T;
     const int orient_u2 = wave ? ORIENT_PAIR : ORIENT_T;     // the two right-hand sides of a confidence-mode call
     const int orient_cv = wave ? ORIENT_STRIP : ORIENT_N;
+    const int16_t fill = (int16_t)(16 * (h->min_disp - 1));            // DF.cpp:254,284
+    const int rrx = W - (roi.x + roi.width);                           // DF.cpp:202
+    const int thresh = (int)(1.0f * h->lrc_thresh);                    // DF.cpp:318 (resize_factor 1)
+    Profiler* prof = &h->prof;
+    h->last_path = plan.path;
 
-    for (int first = 0; first < n_pairs; first += chunk) {
-        const int n = (n_pairs - first < chunk) ? n_pairs - first : chunk;
+    for (int first = 0; first < n_pairs; first += plan.chunk) {
+        const int n = (n_pairs - first < plan.chunk) ? n_pairs - first : plan.chunk;
+        const ChunkPlan& cp = n == plan.chunk ? plan.full : plan.tail;
         const int16_t* dL = (const int16_t*)((const char*)dispL + (ptrdiff_t)first * psL);
+        const int16_t* dR = dispR ? (const int16_t*)((const char*)dispR + (ptrdiff_t)first * psR) : nullptr;
         const uint8_t* gv = view + (ptrdiff_t)first * psG;
         int16_t* o = (int16_t*)((char*)out + (ptrdiff_t)first * psO);
-
+        float* confp = conf ? (float*)h->conf.p + (size_t)first * g.cframe : nullptr;
         const double F = (double)g.frame * n, P = (double)g.rw * g.rh * n;
-        Profiler* prof = &h->prof;
-        const int16_t fill = (int16_t)(16 * (h->min_disp - 1));            // DF.cpp:254,284
-        if (!conf) {                                                       // with confidence the LRC kernel fills
-            OutsideArgs oa{o, sO, psO, fill, nullptr, g};
-            ProfScope ps(prof, K_FILL, 2.0 * (F - P), 2.0 * (F - P), st);
-            HIP_TRY(launch_outside(oa, n, st));
-            if (scaled && first == 0 && (rc = run_scaled_stage(*scaled, st, prof, 1))) return rc;
-        }
+        // the output outside the ROI (DF.cpp:284), and the confidence plane there where this call's own kernels make it
+        OutsideArgs oa{o, sO, psO, fill, scaled ? nullptr : confp, g};
+        const double ob = (oa.conf ? 6.0 : 2.0) * (F - P);
+        auto fill_outside = [&](hipStream_t s) { ProfScope ps(prof, K_FILL, ob, ob, s); return launch_outside(oa, n, s); };
         WeightArgs wa{gv, sG, psG, gch, h->lut.cur, p.CH, p.CV, orient_h, orient_cv, g,
                       wave ? nullptr : p.B0};   // exact: B0 is free until the first pass writes its output there
-        // confidence mode: the weights depend on the guide only and the confidence kernels on the disparity
-        // maps only -- one is bound by memory latency, the others lean on the vector ALUs -- so the weight
-        // kernel is forked onto the side stream and joined before the first solve pass
-        // one small frame per call: weights, confidence map and fill in ONE launch on the caller's stream (no fork)
-        const bool merged = band && h->merge_small && prep_small_fits(g, h->disc_radius, gch, n) && prep_small_guide_fits(g, sG, gch);
-        const bool fork_weights = conf && h->overlap && !merged;
+        ConfBandArgs ba{dL, sL, psL, dR, sR, psR, confp, g, rrx, thresh, h->disc_radius, h->roll_off, 0};
+        DiscArgs da{{dL, dR}, {sL, sR}, {psL, psR}, {roi.x, rrx}, roi.y, roi.width, roi.height, h->disc_radius, h->roll_off,
+                    {cL, cR}, W, g.frame, cp.stage == CONF_LEFT ? 1 : -1};
+        const FusedInputs fuse = cp.stage == CONF_SCALED_LO ? lo_fuse(h, *scaled, first, g) : view_fuse(confp, dL, sL, psL, g);
+
         hipStream_t wst = st;
-        if (fork_weights) {
+        if (cp.fork_weights) {
             if ((rc = h->ensure_side(st))) return rc;
             HIP_TRY(hipEventRecord(h->ev_fork, st));
             HIP_TRY(hipStreamWaitEvent(h->side, h->ev_fork, 0));
             wst = h->side;
         }
-        // the fill of everything outside the ROI (DF.cpp:284, :187-190) touches no pixel any other kernel of the call
-        // touches: on the wave path it rides the side stream too instead of sitting between the confidence kernel and
-        // the first solve pass (one dependent launch less on the critical path of a single-pair call) -- and it goes
-        // FIRST there: alone it takes 0.08 ms of a 64 x 4K step on the StereoBM factory's ROI, but queued behind the
-        // weight kernel it starts when the confidence kernel's workgroups hold nearly every register of every CU and
-        // crawls through 0.8 ms as the call's tail (round 3)
-        // (down-scaled path: the resized confidence map covers the whole frame, only the output is filled)
-        const bool outside_on_side = fork_weights && wave && (conf_given || h->disc_radius <= conf_left_max_radius());
-        if (outside_on_side) {
-            OutsideArgs oa{o, sO, psO, fill, conf_given ? nullptr : (float*)h->conf.p + (size_t)first * g.cframe, g};
-            const double ob = (conf_given ? 2.0 : 6.0) * (F - P);
-            ProfScope ps(prof, K_FILL, ob, ob, wst);
-            HIP_TRY(launch_outside(oa, n, wst));
-        }
-        if (!merged) {
+        if (cp.stage == CONF_NONE || cp.outside_on_side) HIP_TRY(fill_outside(wst));
+        if (cp.stage == CONF_NONE && scaled && first == 0 && (rc = scaled_resize(h, *scaled, st, prof))) return rc;
+        if (cp.stage != CONF_MERGED) {
             ProfScope ps(prof, K_WEIGHTS, (gch + 8.0) * P, (gch + 8.0) * P, wst);
             HIP_TRY(launch_weights(wa, n, wst));                           // FGS.cpp:163-172
         }
-        if (fork_weights) HIP_TRY(hipEventRecord(h->ev_join, h->side));
+        if (cp.fork_weights) HIP_TRY(hipEventRecord(h->ev_join, h->side));
 
-        if (conf) {
-            const int16_t* dRp = (const int16_t*)((const char*)dispR + (ptrdiff_t)first * psR);
-            const int rrx = W - (roi.x + roi.width);                       // DF.cpp:202
-            float* confp = (float*)h->conf.p + (size_t)first * g.cframe;
-            const int thresh = (int)(1.0f * h->lrc_thresh);                // DF.cpp:318 (resize_factor 1)
-            DiscArgs da{};
-            da.disp[0] = dL; da.stride[0] = sL; da.pair_stride[0] = psL; da.rx[0] = roi.x; da.dst[0] = cL;
-            da.disp[1] = dRp; da.stride[1] = sR; da.pair_stride[1] = psR; da.rx[1] = rrx; da.dst[1] = cR;
-            da.ry = roi.y; da.rw = roi.width; da.rh = roi.height; da.radius = h->disc_radius;
-            da.roll_off = h->roll_off; da.W = W; da.frame = g.frame; da.only_view = -1;
-            WavePassArgs fuse{};                                            // inputs of a fused first pass
-            if (conf_given) {
-                // confidence resized to the view (DF.cpp:274): only the prologue remains (DF.cpp:286-290)
-                if (!outside_on_side) {
-                    OutsideArgs oa{o, sO, psO, fill, nullptr, g};
-                    ProfScope ps(prof, K_FILL, 2.0 * (F - P), 2.0 * (F - P), st);
-                    HIP_TRY(launch_outside(oa, n, st));                    // DF.cpp:284
-                }
-                const bool lo_fused = scaled && wave && scaled_fuse_lo(*scaled, first, g, fuse);
-                if (scaled && first == 0 && ((rc = run_scaled_stage(*scaled, st, prof, 0)) || (!lo_fused && (rc = run_scaled_stage(*scaled, st, prof, 1))))) return rc;
-                if (lo_fused) {
-                    // the first row pass taps the low-resolution maps itself: no resize launch, no view-sized planes
-                    h->last_path |= ADF_PATH_SCALED_FUSED;
-                    if (wave_hpass_lo_half(fuse)) h->last_path |= ADF_PATH_SCALED_HALF;
-                    if (first == 0) {
-                        if (stream_is_capturing(st)) {
-                            // a call captured into a graph is replayed without this host code: the view-sized confidence
-                            // maps are made inside the call (the graph), so getConfidenceMap() stays current after replays
-                            if ((rc = scaled_resize_conf_now(*scaled, st, prof))) return rc;
-                        } else scaled_note_lazy_conf(*scaled);
-                    }
-                } else {
-                fuse.conf_in = confp; fuse.conf_frame = g.cframe; fuse.conf_pitch = g.cpitch; fuse.conf_x0 = g.cx0 + roi.x; fuse.conf_y0 = roi.y;
-                fuse.dl_in = dL; fuse.dl_stride = sL; fuse.dl_pair_stride = psL; fuse.dl_x0 = roi.x; fuse.dl_y0 = roi.y;
-                fuse.len = g.rw;
-                }
-                if (!lo_fused && !(wave && wave_hpass_can_fuse(fuse))) {
-                    fuse = WavePassArgs{};
-                    PlainPrologueArgs pa{dL, sL, psL, ADF_16S, 1, 0, p.A0, g, orient_u2, confp, p.A1};
-                    ProfScope ps(prof, K_PROLOGUE, 14.0 * P, 14.0 * P, st);
-                    HIP_TRY(launch_plain_prologue(pa, n, st));
-                }
-            } else if (wave && h->disc_radius <= conf_left_max_radius()) {
-                // wave path: right map, then left map + LRC + x255 in one sweep (cL never hits memory);
-                // the first horizontal pass forms conf*disp itself when alignment allows
-                da.only_view = 1;
-                fuse.conf_in = confp; fuse.conf_frame = g.cframe; fuse.conf_pitch = g.cpitch; fuse.conf_x0 = g.cx0 + roi.x; fuse.conf_y0 = roi.y;
-                fuse.dl_in = dL; fuse.dl_stride = sL; fuse.dl_pair_stride = psL; fuse.dl_x0 = roi.x; fuse.dl_y0 = roi.y;
-                fuse.len = g.rw;
-                const bool fused_h = wave_hpass_can_fuse(fuse);
-                if (!fused_h) fuse = WavePassArgs{};
-                if (band && !fused_h) return fail(ADF_EHIP, "internal: confidence kernel selection and first-pass fusion disagree");
-                if (band) h->last_path |= ADF_PATH_CONF_BAND;
-                if (merged) {
-                    h->last_path |= ADF_PATH_MERGED_PREP;
-                    ConfBandArgs ba{dL, sL, psL, dRp, sR, psR, confp, g, rrx, thresh, h->disc_radius, h->roll_off, 0};
-                    OutsideArgs oa{o, sO, psO, fill, confp, g};
-                    const double b = (8.0 + gch + 8.0) * P + 6.0 * (F - P);
-                    ProfScope ps(prof, K_LRC, b, b, st);
-                    HIP_TRY(launch_prep_small(ba, wa, oa, n, st));         // FGS.cpp:163-172 + DF.cpp:197-210 + :284
-                } else if (band) {
-                    // both views, LRC and x255 in one band sweep: the right view's map lives in LDS only
-                    ConfBandArgs ba{dL, sL, psL, dRp, sR, psR, confp, g, rrx, thresh, h->disc_radius, h->roll_off, 0};
-                    ProfScope ps(prof, K_LRC, 8.0 * P, 8.0 * P, st);     // dL 2 + dR 2 read, conf 4 written
-                    HIP_TRY(launch_conf_band(ba, n, st));                  // DF.cpp:197-210
-                } else {
-                    {
-                        ProfScope ps(prof, K_DISC, 2.0 * P, 6.0 * P, st);
-                        HIP_TRY(launch_discontinuity(da, n, st));          // DF.cpp:204 (right view)
-                    }
-                    ConfLeftArgs ca{dL, sL, psL, dRp, sR, psR, cR, confp, fused_h ? nullptr : p.A0, fused_h ? nullptr : p.A1,
-                                    g, rrx, thresh, h->disc_radius, h->roll_off};
-                    // alg: conf (4P); moved: dL 2 + dR 2 + cR 4 reads, conf 4 (+8 when U0/U1 are materialised)
-                    const double wu = fused_h ? 0.0 : 8.0;
-                    ProfScope ps(prof, K_LRC, (4.0 + wu) * P, (12.0 + wu) * P, st);
-                    HIP_TRY(launch_conf_left(ca, n, st));                  // DF.cpp:204-209 (+288-290)
-                }
-                if (!outside_on_side && !merged) {
-                    OutsideArgs oa{o, sO, psO, fill, confp, g};
-                    ProfScope ps(prof, K_FILL, 6.0 * (F - P), 6.0 * (F - P), st);
-                    HIP_TRY(launch_outside(oa, n, st));                    // DF.cpp:284, :187-190
-                }
-            } else {
-                {   // reads the int16 ROIs, writes the float maps (the maps themselves are not algorithmic I/O)
-                    ProfScope ps(prof, K_DISC, 4.0 * P, 12.0 * P, st);
-                    HIP_TRY(launch_discontinuity(da, n, st));              // DF.cpp:204
-                }
-                LrcArgs la{dL, sL, psL, dRp, sR, psR, cL, cR, confp, o, sO, psO, fill, p.A0, p.A1, g, rrx, thresh, orient_u2};
-                {   // alg: confidence map out (4F) + the two rhs planes (8P); moved adds dL,dR,cL,cR reads
-                    ProfScope ps(prof, K_LRC, 4.0 * F + 8.0 * P + 2.0 * (F - P), 4.0 * F + 20.0 * P + 2.0 * (F - P), st);
-                    HIP_TRY(launch_lrc_prologue(la, n, st));               // DF.cpp:208-209,288-290
-                }
-            }
-            if (fork_weights) HIP_TRY(hipStreamWaitEvent(st, h->ev_join, 0));
-            if (wave && (fuse.conf_in || fuse.lo_conf)) h->last_path |= ADF_PATH_FUSED_FIRST_PASS;
-            FinalOut fo{EPI_WLS_CONF, o, sO, psO, roi.x, roi.y, 1, 0};
-            rc = wave ? run_passes_wave(g, p, 2, (float)h->lambda, (float)h->atten, h->num_iter, fo, n, st, prof,
-                                        (fuse.conf_in || fuse.lo_conf) ? &fuse : nullptr)
-                      : run_passes_exact(g, p, 2, (float)h->lambda, (float)h->atten, h->num_iter, fo, n, st, prof);
-            if (rc) return rc;                                             // DF.cpp:292-296
-        } else {
+        switch (cp.stage) {
+        case CONF_NONE: {
             PlainPrologueArgs pa{dL, sL, psL, ADF_16S, 1, 0, p.A0, g, orient_h};
-            {
-                ProfScope ps(prof, K_PROLOGUE, 6.0 * P, 6.0 * P, st);
-                HIP_TRY(launch_plain_prologue(pa, n, st));                 // FGS.cpp:203-205
-            }
-            FinalOut fo{EPI_I16, o, sO, psO, roi.x, roi.y, 1, 0};
-            rc = wave ? run_passes_wave(g, p, 1, (float)h->lambda, (float)h->atten, h->num_iter, fo, n, st, prof)
-                      : run_passes_exact(g, p, 1, (float)h->lambda, (float)h->atten, h->num_iter, fo, n, st, prof);
-            if (rc) return rc;                                             // DF.cpp:257-258
+            ProfScope ps(prof, K_PROLOGUE, 6.0 * P, 6.0 * P, st);
+            HIP_TRY(launch_plain_prologue(pa, n, st));                     // FGS.cpp:203-205
+            break;
         }
+        case CONF_SCALED: {   // confidence resized to the view (DF.cpp:274): only the prologue remains (DF.cpp:286-290)
+            if (!cp.outside_on_side) HIP_TRY(fill_outside(st));
+            if (first == 0 && ((rc = scaled_conf_map(h, *scaled, st, prof)) || (rc = scaled_resize(h, *scaled, st, prof)))) return rc;
+            if (plan.fused_first) break;
+            PlainPrologueArgs pa{dL, sL, psL, ADF_16S, 1, 0, p.A0, g, orient_u2, confp, p.A1};
+            ProfScope ps(prof, K_PROLOGUE, 14.0 * P, 14.0 * P, st);
+            HIP_TRY(launch_plain_prologue(pa, n, st));
+            break;
+        }
+        case CONF_SCALED_LO:  // the first row pass taps the low-resolution maps itself: no resize launch, no view-sized planes
+            if (!cp.outside_on_side) HIP_TRY(fill_outside(st));
+            if (first != 0) break;
+            if ((rc = scaled_conf_map(h, *scaled, st, prof))) return rc;
+            // a call captured into a graph is replayed without this host code: the view-sized confidence maps are made
+            // inside the call (the graph), so getConfidenceMap() stays current after replays; otherwise on demand
+            if (!stream_is_capturing(st)) h->lazy_conf = adf_wls::LazyConf{true, scaled->lo};
+            else if ((rc = resize_conf_planes(h, scaled->lo, st, prof))) return rc;
+            break;
+        case CONF_MERGED: {
+            const double b = (8.0 + gch + 8.0) * P + 6.0 * (F - P);
+            ProfScope ps(prof, K_LRC, b, b, st);
+            HIP_TRY(launch_prep_small(ba, wa, oa, n, st));                 // FGS.cpp:163-172 + DF.cpp:197-210 + :284
+            break;
+        }
+        case CONF_BAND: {
+            {
+                ProfScope ps(prof, K_LRC, 8.0 * P, 8.0 * P, st);         // dL 2 + dR 2 read, conf 4 written
+                HIP_TRY(launch_conf_band(ba, n, st));                      // DF.cpp:197-210
+            }
+            if (!cp.outside_on_side) HIP_TRY(fill_outside(st));            // DF.cpp:284, :187-190
+            break;
+        }
+        case CONF_LEFT: {
+            {
+                ProfScope ps(prof, K_DISC, 2.0 * P, 6.0 * P, st);
+                HIP_TRY(launch_discontinuity(da, n, st));                  // DF.cpp:204 (right view)
+            }
+            const bool fused = plan.fused_first;
+            ConfLeftArgs ca{dL, sL, psL, dR, sR, psR, cR, confp, fused ? nullptr : p.A0, fused ? nullptr : p.A1,
+                            g, rrx, thresh, h->disc_radius, h->roll_off};
+            {   // alg: conf (4P); moved: dL 2 + dR 2 + cR 4 reads, conf 4 (+8 when U0/U1 are materialised)
+                const double wu = fused ? 0.0 : 8.0;
+                ProfScope ps(prof, K_LRC, (4.0 + wu) * P, (12.0 + wu) * P, st);
+                HIP_TRY(launch_conf_left(ca, n, st));                      // DF.cpp:204-209 (+288-290)
+            }
+            if (!cp.outside_on_side) HIP_TRY(fill_outside(st));            // DF.cpp:284, :187-190
+            break;
+        }
+        case CONF_TWO_KERNEL: {
+            {   // reads the int16 ROIs, writes the float maps (the maps themselves are not algorithmic I/O)
+                ProfScope ps(prof, K_DISC, 4.0 * P, 12.0 * P, st);
+                HIP_TRY(launch_discontinuity(da, n, st));                  // DF.cpp:204
+            }
+            LrcArgs la{dL, sL, psL, dR, sR, psR, cL, cR, confp, o, sO, psO, fill, p.A0, p.A1, g, rrx, thresh, orient_u2};
+            // alg: confidence map out (4F) + the two rhs planes (8P); moved adds dL,dR,cL,cR reads
+            ProfScope ps(prof, K_LRC, 4.0 * F + 8.0 * P + 2.0 * (F - P), 4.0 * F + 20.0 * P + 2.0 * (F - P), st);
+            HIP_TRY(launch_lrc_prologue(la, n, st));                       // DF.cpp:208-209,288-290
+            break;
+        }
+        }
+        if (cp.fork_weights) HIP_TRY(hipStreamWaitEvent(st, h->ev_join, 0));
+        FinalOut fo{conf ? EPI_WLS_CONF : EPI_I16, o, sO, psO, roi.x, roi.y, 1, 0};
+        rc = run_passes(wave, g, p, conf ? 2 : 1, (float)h->lambda, (float)h->atten, h->num_iter, fo, n, st, prof,
+                        plan.fused_first ? &fuse : nullptr);
+        if (rc) return rc;                                                 // DF.cpp:257-258, 292-296
     }
     return ADF_OK;
 }
@@ -905,126 +1016,7 @@ extern "C" int adf_wls_filter_device(adf_wls_t* h, int n_pairs,
                                      const adf_rect* roi_in, void* stream)
 {
     return wls_filter_impl(h, n_pairs, dispL, sL, psL, view, sG, psG, gch, W, H, out, sO, psO, dispR, sR, psR, roi_in,
-                           false, (hipStream_t)stream);
-}
-
-struct ScaledStage {
-    adf_wls_t* h; int n_pairs;
-    const int16_t* dispL; ptrdiff_t sL, psL;
-    const int16_t* dispR; ptrdiff_t sR, psR;
-    int dW, dH, W, H;
-    adf_rect rlo; Geom ghi;
-    float resize_factor, x_ratio;
-    char* dhi; size_t dhi_bytes;
-    float *cl, *cr, *clo;
-    bool conf;
-    bool fuse_lo;   // the first row pass interpolates (decided by adf_wls_filter_scaled_device: dhi is not allocated then)
-    float* taps;    // ... with this scratch for the columns' source coordinates
-};
-
-static bool scaled_band_map(const ScaledStage& s)
-{
-    return s.conf && s.h->conf_band &&
-           conf_band_fits(plain_conf_layout(make_geom(s.dW, s.dH, s.rlo.x, s.rlo.y, s.rlo.width, s.rlo.height)), s.h->disc_radius);
-}
-
-static void scaled_lo_args(const ScaledStage& s, int first, const Geom& g, WavePassArgs& f)
-{
-    const size_t lo = (size_t)s.dW * s.dH;
-    f = WavePassArgs{};
-    f.lo_conf = s.clo + (size_t)first * lo; f.lo_conf_stride = s.dW; f.lo_conf_pair = (ptrdiff_t)lo;
-    f.lo_dl = (const int16_t*)((const char*)s.dispL + (ptrdiff_t)first * s.psL); f.lo_dl_stride = s.sL; f.lo_dl_pair = s.psL;
-    f.lo_w = s.dW; f.lo_h = s.dH; f.hi_x0 = g.rx; f.hi_y0 = g.ry;
-    f.lo_scale_x = (double)s.dW / s.W; f.lo_scale_y = (double)s.dH / s.H; f.lo_post_scale = s.x_ratio;
-    if (scaled_band_map(s)) {
-        f.lo_zero_outside = 1; f.lo_vx0 = s.rlo.x; f.lo_vy0 = s.rlo.y; f.lo_vx1 = s.rlo.x + s.rlo.width; f.lo_vy1 = s.rlo.y + s.rlo.height;
-    }
-    f.len = g.rw; f.lo_taps = s.taps; f.lo_half = s.h->scaled_half ? 1 : 0;
-}
-
-static bool scaled_fuse_lo(const ScaledStage& s, int first, const Geom& g, WavePassArgs& fuse)
-{
-    if (!s.fuse_lo) return false;
-    scaled_lo_args(s, first, g, fuse);
-    return true;     // (adf_wls_filter_scaled_device has checked wave_hpass_can_fuse_lo on the same arguments)
-}
-
-static void scaled_note_lazy_conf(const ScaledStage& s)
-{
-    adf_wls::LazyConf& z = s.h->lazy_conf;
-    z.pending = true; z.clo = s.clo; z.dW = s.dW; z.dH = s.dH; z.rlo = s.rlo; z.ghi = s.ghi; z.band_map = scaled_band_map(s); z.n_pairs = s.n_pairs;
-}
-
-// cv::resize of the low-resolution confidence maps into the handle's view-sized planes (DF.cpp:274)
-static int resize_conf_planes(adf_wls_t* h, const float* clo, int dW, int dH, const adf_rect& rlo, const Geom& ghi, bool band_map,
-                              int n_pairs, hipStream_t st, Profiler* prof)
-{
-    const size_t lo = (size_t)dW * dH;
-    const double Fhi = (double)ghi.W * ghi.H * n_pairs;
-    ResizeArgs rc32{clo, (ptrdiff_t)dW * 4, (ptrdiff_t)(lo * 4), dW, dH, (float*)h->conf.p + ghi.cx0, (ptrdiff_t)ghi.cpitch * 4,
-                    (ptrdiff_t)(ghi.cframe * 4), ghi.W, ghi.H, (double)dW / ghi.W, (double)dH / ghi.H, 1.0f, 0};
-    if (band_map) { rc32.zero_outside = 1; rc32.vx0 = rlo.x; rc32.vy0 = rlo.y; rc32.vx1 = rlo.x + rlo.width; rc32.vy1 = rlo.y + rlo.height; }
-    ProfScope ps(prof, K_RESIZE, 4.0 * Fhi + 4.0 * (double)lo * n_pairs, 4.0 * Fhi + 4.0 * (double)lo * n_pairs, st);
-    HIP_TRY(launch_resize_linear(rc32, n_pairs, st));
-    return ADF_OK;
-}
-
-static int scaled_resize_conf_now(const ScaledStage& s, hipStream_t st, Profiler* prof)
-{
-    return resize_conf_planes(s.h, s.clo, s.dW, s.dH, s.rlo, s.ghi, scaled_band_map(s), s.n_pairs, st, prof);
-}
-
-// part 0: the low-resolution confidence map; part 1: the two resizes.  Both are queued beside the weight kernel (after
-// its fork).  Measured at 64 x 4K views / 1080p maps: everything after the fork 13.8-14.1 / 13.8-14.0 ms per call (radius 2 / 5;
-// the band kernel crawls beside the weight kernel's small workgroups, 0.44 -> 0.9-1.7 ms, but the resizes then run
-// alone), part 0 before the fork 14.20 / 14.51 (two memory-bound kernels side by side gain nothing), no overlap at all
-// 14.49 / 14.69.
-static int run_scaled_stage(const ScaledStage& s, hipStream_t st, Profiler* prof, int part)
-{
-    adf_wls_t* h = s.h;
-    const int n_pairs = s.n_pairs, dW = s.dW, dH = s.dH, W = s.W, H = s.H;
-    const size_t lo = (size_t)dW * dH;
-    const adf_rect& rlo = s.rlo;
-    const double Plo = (double)rlo.width * rlo.height * n_pairs, Fhi = (double)W * H * n_pairs;
-    const bool band_map = s.conf && h->conf_band && conf_band_fits(plain_conf_layout(make_geom(dW, dH, rlo.x, rlo.y, rlo.width, rlo.height)), h->disc_radius);
-    if (s.conf && part == 0) {
-        const Geom glo = plain_conf_layout(make_geom(dW, dH, rlo.x, rlo.y, rlo.width, rlo.height));
-        const int rrx = dW - (rlo.x + rlo.width);                          // DF.cpp:202
-        DiscArgs da{};
-        da.disp[0] = s.dispL; da.stride[0] = s.sL; da.pair_stride[0] = s.psL; da.rx[0] = rlo.x; da.dst[0] = s.cl;
-        da.disp[1] = s.dispR; da.stride[1] = s.sR; da.pair_stride[1] = s.psR; da.rx[1] = rrx; da.dst[1] = s.cr;
-        da.ry = rlo.y; da.rw = rlo.width; da.rh = rlo.height; da.radius = h->disc_radius;
-        da.roll_off = h->roll_off / (s.resize_factor * s.resize_factor);    // DF.cpp:359
-        da.W = dW; da.frame = lo; da.only_view = -1;
-        const int thresh_lo = (int)(s.resize_factor * h->lrc_thresh);       // DF.cpp:318
-        if (band_map) {
-            // the one-sweep kernel at the maps' resolution: ROI pixels from the band kernel, zeros outside (DF.cpp:187-190)
-            ConfBandArgs ba{s.dispL, s.sL, s.psL, s.dispR, s.sR, s.psR, s.clo, glo, rrx, thresh_lo, h->disc_radius, da.roll_off, 0};
-            h->last_path |= ADF_PATH_CONF_BAND;
-            {
-                ProfScope ps(prof, K_LRC, 8.0 * Plo, 8.0 * Plo, st);
-                HIP_TRY(launch_conf_band(ba, n_pairs, st));                // DF.cpp:197-210
-            }
-            // (zeros outside the ROI: the resize's window)
-        } else {
-            {
-                ProfScope ps(prof, K_DISC, 4.0 * Plo, 12.0 * Plo, st);
-                HIP_TRY(launch_discontinuity(da, n_pairs, st));            // DF.cpp:204
-            }
-            LrcArgs la{s.dispL, s.sL, s.psL, s.dispR, s.sR, s.psR, s.cl, s.cr, s.clo, nullptr, 0, 0, 0, nullptr, nullptr, glo, rrx, thresh_lo, ORIENT_N};
-            ProfScope ps(prof, K_LRC, 4.0 * (double)lo * n_pairs, 4.0 * (double)lo * n_pairs + 12.0 * Plo, st);
-            HIP_TRY(launch_lrc_prologue(la, n_pairs, st));                 // DF.cpp:208-209
-        }
-    }
-    if (part == 0) return ADF_OK;
-    if (s.conf) {
-        int rc = resize_conf_planes(h, s.clo, dW, dH, rlo, s.ghi, band_map, n_pairs, st, prof);   // DF.cpp:274
-        if (rc) return rc;
-    }
-    ResizeArgs r16{s.dispL, s.sL, s.psL, dW, dH, s.dhi, (ptrdiff_t)W * 2, (ptrdiff_t)s.dhi_bytes, W, H, (double)dW / W, (double)dH / H, s.x_ratio, 1};
-    ProfScope ps(prof, K_RESIZE, 2.0 * Fhi + 2.0 * (double)lo * n_pairs, 2.0 * Fhi + 2.0 * (double)lo * n_pairs, st);
-    HIP_TRY(launch_resize_linear(r16, n_pairs, st));                       // DF.cpp:243-244, 272-273
-    return ADF_OK;
+                           (hipStream_t)stream);
 }
 
 // Down-scaled disparity path (DF.cpp:224-227, 239-247, 268-277): disparity maps of dW x dH, view and
@@ -1039,22 +1031,15 @@ extern "C" int adf_wls_filter_scaled_device(adf_wls_t* h, int n_pairs,
     NEED_HANDLE(h);
     hipStream_t st = (hipStream_t)stream;
     if (dW == W && dH == H)                                                // DF.cpp:224-227: same size, resize_factor 1
-        return wls_filter_impl(h, n_pairs, dispL, sL, psL, view, sG, psG, gch, W, H, out, sO, psO, dispR, sR, psR, roi_in, false, st);
+        return wls_filter_impl(h, n_pairs, dispL, sL, psL, view, sG, psG, gch, W, H, out, sO, psO, dispR, sR, psR, roi_in, st);
     if (!dispL || dW <= 0 || dH <= 0 || W <= 0 || H <= 0) return fail(ADF_EBADARG, "disparity_map_left is empty");
     if (n_pairs < 1) return fail(ADF_EBADARG, "n_pairs must be >= 1");
     if (sL < (ptrdiff_t)dW * 2) return fail(ADF_ESIZE, "row stride smaller than a row");
     const bool conf = h->use_confidence;
-    if (conf) {
-        if (!dispR) return fail(ADF_EBADARG, "disparity_map_right is required with use_confidence");
-        if (sR < (ptrdiff_t)dW * 2) return fail(ADF_ESIZE, "right disparity stride smaller than a row");
-        if (h->disc_radius < 0 || h->disc_radius > max_disc_radius())
-            return fail(ADF_EBADARG, "depth discontinuity radius %d outside [0,%d]", h->disc_radius, max_disc_radius());
-    }
-    adf_rect rlo;                                                          // DF.cpp:228-233, disparity-map coordinates
-    if (roi_in && roi_in->width * roi_in->height != 0) rlo = *roi_in;
-    else rlo = adf_rect{h->left_offset, h->top_offset, dW - h->left_offset - h->right_offset, dH - h->top_offset - h->bottom_offset};
-    if (rlo.width <= 0 || rlo.height <= 0 || rlo.x < 0 || rlo.y < 0 || rlo.x + rlo.width > dW || rlo.y + rlo.height > dH)
-        return fail(ADF_ESIZE, "ROI (%d,%d,%d,%d) does not fit a %dx%d map", rlo.x, rlo.y, rlo.width, rlo.height, dW, dH);
+    int rc;
+    if (conf && ((rc = check_right_map(dispR, sR, dW)) || (rc = check_radius(h)))) return rc;
+    adf_rect rlo;                                                          // disparity-map coordinates
+    if ((rc = resolve_roi(h, roi_in, dW, dH, rlo))) return rc;
     const float resize_factor = dW / (float)W;                             // DF.cpp:225
     const float x_ratio = W / (float)dW, y_ratio = H / (float)dH;          // DF.cpp:241-242,270-271
     adf_rect rhi{(int)(rlo.x * x_ratio), (int)(rlo.y * y_ratio), (int)(rlo.width * x_ratio), (int)(rlo.height * y_ratio)};
@@ -1065,38 +1050,29 @@ extern "C" int adf_wls_filter_scaled_device(adf_wls_t* h, int n_pairs,
     h->lazy_conf.pending = false;    // (the previous call's low-resolution maps are about to be overwritten or freed)
     const size_t lo = (size_t)dW * dH, hi = (size_t)W * H;
     const Geom ghi = make_geom(W, H, rhi.x, rhi.y, rhi.width, rhi.height);   // the geometry wls_filter_impl will derive
+    ScaledStage s{dispL, sL, psL, dispR, sR, psR, resize_factor, x_ratio, nullptr, 0, nullptr, nullptr,
+                  ConfResize{UNALLOCATED, dW, dH, rlo, ghi, false, n_pairs}, false, nullptr};
+    s.lo.band_map = conf && h->conf_band &&
+                    conf_band_fits(plain_conf_layout(make_geom(dW, dH, rlo.x, rlo.y, rlo.width, rlo.height)), h->disc_radius);
     // Can the first row pass interpolate the maps itself (fgs_wave_h.hip, FUSE_LO)?  Confidence mode on the wave solver,
     // scale factors within the staging buffer's reach.  Then neither the resized disparity map nor -- until
     // getConfidenceMap() asks for it -- the resized confidence map is ever written.
-    bool fuse_lo = false;
-    if (conf && h->scaled_fuse && h->solver == ADF_SOLVER_WAVE && wave_fits(ghi)) {
-        ScaledStage probe{h, n_pairs, dispL, sL, psL, dispR, sR, psR, dW, dH, W, H, rlo, ghi, resize_factor, x_ratio,
-                          nullptr, 0, nullptr, nullptr, reinterpret_cast<float*>(uintptr_t(256)), conf, true, nullptr};
-        WavePassArgs f;
-        scaled_lo_args(probe, 0, ghi, f);
-        fuse_lo = wave_hpass_can_fuse_lo(f);
-    }
+    s.fuse_lo = conf && h->scaled_fuse && h->solver == ADF_SOLVER_WAVE && wave_fits(ghi) &&
+                wave_hpass_can_fuse_lo(first_pass_probe(lo_fuse(h, s, 0, ghi), ghi.rw));
     // scratch: resized disparity (int16, view size; not with fuse_lo) + low-resolution cL, cR, conf (float)
-    const size_t dhi_bytes = fuse_lo ? 0 : (hi * 2 + 255) / 256 * 256;
-    const size_t maps_bytes = ((size_t)n_pairs * (dhi_bytes + (conf ? 3 * lo * sizeof(float) : 0)) + 255) / 256 * 256;
-    const size_t need = maps_bytes + (fuse_lo ? 2 * ((size_t)rhi.width + 4) * sizeof(float) : 0);   // + the columns' taps
-    int rc = h->scaled.reserve(need, st);
-    if (rc) return rc;
-    char* dhi = (char*)h->scaled.p;
-    float* cl = (float*)(dhi + (size_t)n_pairs * dhi_bytes);
-    float* cr = cl + (size_t)n_pairs * lo;
-    float* clo = cr + (size_t)n_pairs * lo;
-    float* taps = fuse_lo ? (float*)((char*)h->scaled.p + maps_bytes) : nullptr;
+    s.dhi_bytes = s.fuse_lo ? 0 : (hi * 2 + 255) / 256 * 256;
+    const size_t maps_bytes = ((size_t)n_pairs * (s.dhi_bytes + (conf ? 3 * lo * sizeof(float) : 0)) + 255) / 256 * 256;
+    const size_t need = maps_bytes + (s.fuse_lo ? 2 * ((size_t)rhi.width + 4) * sizeof(float) : 0);   // + the columns' taps
+    if ((rc = h->scaled.reserve(need, st))) return rc;
+    s.dhi = (char*)h->scaled.p;
+    s.cl = (float*)(s.dhi + (size_t)n_pairs * s.dhi_bytes);
+    s.cr = s.cl + (size_t)n_pairs * lo;
+    s.lo.clo = s.cr + (size_t)n_pairs * lo;
+    s.taps = s.fuse_lo ? (float*)((char*)h->scaled.p + maps_bytes) : nullptr;
     if (conf && (rc = ensure_conf_planes(h, ghi, n_pairs, st))) return rc;
-    ScaledStage stage{h, n_pairs, dispL, sL, psL, dispR, sR, psR, dW, dH, W, H, rlo, ghi, resize_factor, x_ratio,
-                      dhi, dhi_bytes, cl, cr, clo, conf, fuse_lo, taps};
-    // (without confidence the stage is the disparity resize alone; either way wls_filter_impl queues it after it has
-    // forked the weight kernel, which needs the view only)
     // (fuse_lo: wls_filter_impl never dereferences its dispL -- the caller's low-resolution map stands in, with its own strides)
-    rc = fuse_lo ? wls_filter_impl(h, n_pairs, dispL, (ptrdiff_t)W * 2, 0, view, sG, psG, gch, W, H,
-                                   out, sO, psO, nullptr, 0, 0, &rhi, conf, st, &stage)
-                 : wls_filter_impl(h, n_pairs, (const int16_t*)dhi, (ptrdiff_t)W * 2, (ptrdiff_t)dhi_bytes, view, sG, psG, gch, W, H,
-                                   out, sO, psO, nullptr, 0, 0, &rhi, conf, st, &stage);
+    rc = wls_filter_impl(h, n_pairs, s.fuse_lo ? dispL : (const int16_t*)s.dhi, (ptrdiff_t)W * 2, (ptrdiff_t)s.dhi_bytes,
+                         view, sG, psG, gch, W, H, out, sO, psO, nullptr, 0, 0, &rhi, st, &s);
     h->roi = rlo;                                                          // getROI(): valid_disp_ROI (DF.cpp:139)
     return rc;
 }
@@ -1197,8 +1173,7 @@ static int conf_copy(adf_wls_t* h, int pair, float* dst, ptrdiff_t stride, hipMe
     if (h->lazy_conf.pending) {
         // a down-scaled call whose first row pass interpolated the maps itself: resize the low-resolution confidence
         // maps of the call now (DF.cpp:274; all pairs, one launch, outside the filter call), once
-        const adf_wls::LazyConf& z = h->lazy_conf;
-        int rc = resize_conf_planes(h, z.clo, z.dW, z.dH, z.rlo, z.ghi, z.band_map, z.n_pairs, st, nullptr);
+        int rc = resize_conf_planes(h, h->lazy_conf.resize, st, nullptr);
         if (rc) return rc;
         h->lazy_conf.pending = false;
     }
@@ -1428,8 +1403,7 @@ static int fgs_filter_run(adf_fgs* f, int depth, int channels, const void* src, 
         // the epilogue of channel c overwrites only channel c of the image, which later
         // channels never read (they read their own channel), so filtering in place is safe
         FinalOut fo{epi, dst, dstride, 0, 0, 0, channels, c};
-        int rc = wave ? run_passes_wave(g, p, nr, f->lambda, f->atten, f->num_iter, fo, 1, st)
-                      : run_passes_exact(g, p, 1, f->lambda, f->atten, f->num_iter, fo, 1, st);
+        int rc = run_passes(wave, g, p, nr, f->lambda, f->atten, f->num_iter, fo, 1, st);
         if (rc) return rc;
         c += nr;
     }

@@ -147,11 +147,8 @@ struct PassArgs {
     float lambda;
 };
 
-// One pass of the on-chip partitioned solver (fgs_wave.hip).  Planes are row-major [rh][pitch] and
-// are solved IN PLACE; horizontal: nscan = rows, len = row length; vertical: nscan = columns,
-// len = column length.  The last vertical pass may fuse an epilogue and write `out` instead.
-struct WavePassArgs {
-    const float* C; float* U0; float* U1;
+// Inputs of a fused first horizontal pass of the wave solver (WavePassArgs::fuse; all zero = not fused).
+struct FusedInputs {
     // fused prologue of the first horizontal pass (DF.cpp:288-290): when conf_in is set the right-hand
     // sides are read as U1 = conf, U0 = conf * float(dL) from the confidence plane and the disparity map
     const float* conf_in; size_t conf_frame; int conf_pitch, conf_x0, conf_y0;
@@ -169,12 +166,23 @@ struct WavePassArgs {
     int lo_zero_outside, lo_vx0, lo_vy0, lo_vx1, lo_vy1;
     int lo_half;      // 0: never the half-width form of the low-resolution prologue (ADF_LO_HALF=0: A/B and test knob)
     float* lo_taps;   // scratch, 4*ceil(len/4) floats, 16-byte aligned: the launcher fills it with the columns' taps (s0 + fx)
+};
+
+// One pass of the on-chip partitioned solver (fgs_wave.hip).  Planes are row-major [rh][pitch] and
+// are solved IN PLACE; horizontal: nscan = rows, len = row length; vertical: nscan = columns,
+// len = column length.  The last vertical pass may fuse an epilogue and write `out` instead.
+struct WavePassArgs {
+    const float* C; float* U0; float* U1;
+    FusedInputs fuse;
     void* out; ptrdiff_t out_stride, out_pair_stride;
     int out_x0, out_y0, out_cn, out_c;
     int nscan, len, pitch;
     size_t plane;
     float lambda;
 };
+// the kernels' argument layout (grouping the fused inputs moved no member)
+static_assert(sizeof(WavePassArgs) == 280 && offsetof(WavePassArgs, out) == 208 && offsetof(WavePassArgs, nscan) == 248 &&
+              offsetof(WavePassArgs, plane) == 264 && offsetof(WavePassArgs, lambda) == 272, "WavePassArgs layout");
 
 // Records the calling thread's last error message (adf_last_error) and returns `code`.
 int set_error(int code, const char* msg);

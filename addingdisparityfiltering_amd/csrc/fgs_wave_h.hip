@@ -99,10 +99,10 @@ __global__ void __launch_bounds__(64 * NW, (M > (NW == 2 ? 40 : H_TWO_WAVE_MAX) 
         // fused inputs (the launcher guarantees a 16-byte aligned conf row start and len >= 4)
         const float4* sF = nullptr; const char* sD = nullptr;
         if (FUSED == FUSE_VIEW) {
-            sF = reinterpret_cast<const float4*>(a.conf_in + (size_t)blockIdx.y * a.conf_frame +
-                                                 (size_t)(a.conf_y0 + blockIdx.x) * a.conf_pitch + a.conf_x0);
-            sD = reinterpret_cast<const char*>(a.dl_in) + (ptrdiff_t)blockIdx.y * a.dl_pair_stride +
-                 (ptrdiff_t)(a.dl_y0 + blockIdx.x) * a.dl_stride + (ptrdiff_t)a.dl_x0 * 2;
+            sF = reinterpret_cast<const float4*>(a.fuse.conf_in + (size_t)blockIdx.y * a.fuse.conf_frame +
+                                                 (size_t)(a.fuse.conf_y0 + blockIdx.x) * a.fuse.conf_pitch + a.fuse.conf_x0);
+            sD = reinterpret_cast<const char*>(a.fuse.dl_in) + (ptrdiff_t)blockIdx.y * a.fuse.dl_pair_stride +
+                 (ptrdiff_t)(a.fuse.dl_y0 + blockIdx.x) * a.fuse.dl_stride + (ptrdiff_t)a.fuse.dl_x0 * 2;
         }
         // fused: the row is ceil(len/4) vectors; conf (the library's own plane, Geom::cx0 / cpitch) is always 16-byte
         // aligned, dL is the caller's and only 2-byte aligned for an odd ROI x (8-byte loads at any even address).
@@ -127,7 +127,7 @@ __global__ void __launch_bounds__(64 * NW, (M > (NW == 2 ? 40 : H_TWO_WAVE_MAX) 
             constexpr int CROW = lo_row_cap(M);
             constexpr int TC4 = (CROW / 4 + 63) / 64, TD8 = (CROW / 8 + 63) / 64;
             static_assert(12 * CROW <= 16 * lo_stage_vec4(M) && CROW % 8 == 0, "two confidence rows and two disparity rows fit the staging buffer");
-            const int sw = a.lo_w, sh = a.lo_h;
+            const int sw = a.fuse.lo_w, sh = a.fuse.lo_h;
             // the C row first: its loads are in flight while the low-resolution rows are fetched and staged
 #pragma unroll
             for (int k = 0; k < MQ; k++) {
@@ -138,17 +138,17 @@ __global__ void __launch_bounds__(64 * NW, (M > (NW == 2 ? 40 : H_TWO_WAVE_MAX) 
             // rows (wave-uniform)
             int sy; float fy;
             {
-                const int dy = a.hi_y0 + (int)blockIdx.x;
-                fy = (float)(((double)dy + 0.5) * a.lo_scale_y - 0.5);
+                const int dy = a.fuse.hi_y0 + (int)blockIdx.x;
+                fy = (float)(((double)dy + 0.5) * a.fuse.lo_scale_y - 0.5);
                 sy = (int)floorf(fy);
                 fy -= (float)sy;                                 // (rows clamp with their weights kept, like the resize kernel)
             }
             const float b0 = 1.0f - fy, b1 = fy;
-            const bool post_scaled = a.lo_post_scale != 1.0f;
+            const bool post_scaled = a.fuse.lo_post_scale != 1.0f;
             int yr[2] = {min(max(sy, 0), sh - 1), min(max(sy + 1, 0), sh - 1)};
             yr[0] = __builtin_amdgcn_readfirstlane(yr[0]); yr[1] = __builtin_amdgcn_readfirstlane(yr[1]);
-            const float* cbase = a.lo_conf + (ptrdiff_t)blockIdx.y * a.lo_conf_pair;
-            const char* dbase = reinterpret_cast<const char*>(a.lo_dl) + (ptrdiff_t)blockIdx.y * a.lo_dl_pair;
+            const float* cbase = a.fuse.lo_conf + (ptrdiff_t)blockIdx.y * a.fuse.lo_conf_pair;
+            const char* dbase = reinterpret_cast<const char*>(a.fuse.lo_dl) + (ptrdiff_t)blockIdx.y * a.fuse.lo_dl_pair;
             // columns of the two halves (wave-uniform): first source element and number of staged slots (the slot behind
             // the last tap included: past the row's end it repeats the edge element, which carries weight 0)
             int ss[2], ns[2];
@@ -157,7 +157,7 @@ __global__ void __launch_bounds__(64 * NW, (M > (NW == 2 ? 40 : H_TWO_WAVE_MAX) 
                 const int cfirst = 64 * M * wv + 256 * (hh ? KH : 0);
                 const int clast = min(64 * M * wv + 256 * (hh ? MQ : KH), a.len) - 1;
                 int s_first = 0, s_last = -2; float f_;
-                if (clast >= cfirst) { lin_tap(a.hi_x0 + cfirst, a.lo_scale_x, sw, s_first, f_); lin_tap(a.hi_x0 + clast, a.lo_scale_x, sw, s_last, f_); }
+                if (clast >= cfirst) { lin_tap(a.fuse.hi_x0 + cfirst, a.fuse.lo_scale_x, sw, s_first, f_); lin_tap(a.fuse.hi_x0 + clast, a.fuse.lo_scale_x, sw, s_last, f_); }
                 ss[hh] = __builtin_amdgcn_readfirstlane(s_first);
                 ns[hh] = __builtin_amdgcn_readfirstlane(s_last + 2 - s_first);      // 0 for an empty half
             }
@@ -166,7 +166,7 @@ __global__ void __launch_bounds__(64 * NW, (M > (NW == 2 ? 40 : H_TWO_WAVE_MAX) 
             bool need_mask[2];
 #pragma unroll
             for (int hh = 0; hh < 2; hh++)
-                need_mask[hh] = a.lo_zero_outside && (yr[0] < a.lo_vy0 || yr[1] >= a.lo_vy1 || ss[hh] < a.lo_vx0 || min(ss[hh] + ns[hh], sw) > a.lo_vx1);
+                need_mask[hh] = a.fuse.lo_zero_outside && (yr[0] < a.fuse.lo_vy0 || yr[1] >= a.fuse.lo_vy1 || ss[hh] < a.fuse.lo_vx0 || min(ss[hh] + ns[hh], sw) > a.fuse.lo_vx1);
             // Per half: fetch the two source rows (coalesced: lane i takes source elements ss + 4i .. of the confidence
             // rows, ss + 8i .. of the disparity rows; a vector that would cross the row's end is fetched element by
             // element, clamped, which also fills the slots behind the row with the edge element), stage them, tap them.
@@ -176,8 +176,8 @@ __global__ void __launch_bounds__(64 * NW, (M > (NW == 2 ? 40 : H_TWO_WAVE_MAX) 
             auto fetch = [&](int hh, v4f (&qc)[2][TC4], s8u (&qd)[2][TD8]) {
 #pragma unroll
                 for (int r = 0; r < 2; r++) {
-                    const float* crow = cbase + (ptrdiff_t)yr[r] * a.lo_conf_stride;
-                    const int16_t* drow = reinterpret_cast<const int16_t*>(dbase + (ptrdiff_t)yr[r] * a.lo_dl_stride);
+                    const float* crow = cbase + (ptrdiff_t)yr[r] * a.fuse.lo_conf_stride;
+                    const int16_t* drow = reinterpret_cast<const int16_t*>(dbase + (ptrdiff_t)yr[r] * a.fuse.lo_dl_stride);
 #pragma unroll
                     for (int t = 0; t < TC4; t++) {
                         const int e = ss[hh] + 4 * (64 * t + lane);
@@ -214,8 +214,8 @@ __global__ void __launch_bounds__(64 * NW, (M > (NW == 2 ? 40 : H_TWO_WAVE_MAX) 
             typedef short s8a __attribute__((ext_vector_type(8)));
             s8a* Ls8 = reinterpret_cast<s8a*>(stage) + CROW / 2;
             auto put = [&](int hh, const v4f (&qc)[2][TC4], const s8u (&qd)[2][TD8]) {
-                const bool rin0 = !a.lo_zero_outside || (yr[0] >= a.lo_vy0 && yr[0] < a.lo_vy1);
-                const bool rin1 = !a.lo_zero_outside || (yr[1] >= a.lo_vy0 && yr[1] < a.lo_vy1);
+                const bool rin0 = !a.fuse.lo_zero_outside || (yr[0] >= a.fuse.lo_vy0 && yr[0] < a.fuse.lo_vy1);
+                const bool rin1 = !a.fuse.lo_zero_outside || (yr[1] >= a.fuse.lo_vy0 && yr[1] < a.fuse.lo_vy1);
 #pragma unroll
                 for (int t = 0; t < TC4; t++) {
                     const int i4 = 64 * t + lane, e = ss[hh] + 4 * i4;
@@ -224,7 +224,7 @@ __global__ void __launch_bounds__(64 * NW, (M > (NW == 2 ? 40 : H_TWO_WAVE_MAX) 
 #pragma unroll
                         for (int c = 0; c < 4; c++) {
                             const int ec = min(e + c, sw - 1);
-                            const bool cin = ec >= a.lo_vx0 && ec < a.lo_vx1;
+                            const bool cin = ec >= a.fuse.lo_vx0 && ec < a.fuse.lo_vx1;
                             if (!(rin0 && cin)) q0[c] = 0.0f;
                             if (!(rin1 && cin)) q1[c] = 0.0f;
                         }
@@ -256,7 +256,7 @@ __global__ void __launch_bounds__(64 * NW, (M > (NW == 2 ? 40 : H_TWO_WAVE_MAX) 
                 for (int k = (hh ? KH : 0); k < (hh ? MQ : KH); k++) {
                     const int idx = v0 + 64 * k + lane;
                     tp[k] = v4f{0.f, 0.f, 0.f, 0.f};
-                    if (idx < nfused) tp[k] = reinterpret_cast<const v4f*>(a.lo_taps)[idx];
+                    if (idx < nfused) tp[k] = reinterpret_cast<const v4f*>(a.fuse.lo_taps)[idx];
                 }
             };
             fetch(0, rc[0], rd[0]);
@@ -317,7 +317,7 @@ __global__ void __launch_bounds__(64 * NW, (M > (NW == 2 ? 40 : H_TWO_WAVE_MAX) 
                         // size ratio), so sat16's guard for NaN / out-of-int-range cannot fire -- and a branch per column
                         // would let the compiler sink every column's arithmetic behind the last one's (registers)
                         const float q1 = fminf(fmaxf(rintf(v[1]), -32768.0f), 32767.0f);
-                        const float q2 = fminf(fmaxf(rintf(q1 * a.lo_post_scale), -32768.0f), 32767.0f);
+                        const float q2 = fminf(fmaxf(rintf(q1 * a.fuse.lo_post_scale), -32768.0f), 32767.0f);
                         cv[c] = v[0];
                         dv[c] = post_scaled ? q2 : q1;
                     }
@@ -512,16 +512,16 @@ template <int M, int NW = 1>
 hipError_t launch_h(const WavePassArgs& a, int n_rhs, int n_pairs, hipStream_t st)
 {
     dim3 grid(a.nscan, n_pairs), block(64 * NW);
-    if (a.lo_conf) {
-        if (n_rhs != 2 || !a.lo_taps) return hipErrorInvalidValue;
+    if (a.fuse.lo_conf) {
+        if (n_rhs != 2 || !a.fuse.lo_taps) return hipErrorInvalidValue;
         const int n = ((a.len + 3) / 4) * 4;
-        hipLaunchKernelGGL(lo_tap_table_kernel, dim3((n + 255) / 256), dim3(256), 0, st, a.lo_taps, n, a.len, a.hi_x0, a.lo_scale_x, a.lo_w);
+        hipLaunchKernelGGL(lo_tap_table_kernel, dim3((n + 255) / 256), dim3(256), 0, st, a.fuse.lo_taps, n, a.len, a.fuse.hi_x0, a.fuse.lo_scale_x, a.fuse.lo_w);
         // maps of exactly half the view's width, ROI on an even column >= 2: the form with shared source elements
         if (wave_hpass_lo_half(a))
             hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_LO_HALF, NW>), grid, block, 0, st, a);
         else
             hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_LO, NW>), grid, block, 0, st, a);
-    } else if (a.conf_in) {
+    } else if (a.fuse.conf_in) {
         if (n_rhs != 2) return hipErrorInvalidValue;
         hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_VIEW, NW>), grid, block, 0, st, a);
     } else if (n_rhs == 2) hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_NONE, NW>), grid, block, 0, st, a);
@@ -551,16 +551,16 @@ int wave_max_row_len() { return 128 * 64; }
 // the prologue kernels instead.
 bool wave_hpass_can_fuse(const WavePassArgs& a)
 {
-    if (!a.conf_in || !a.dl_in) return false;
-    if (a.len < 4 || a.conf_pitch % 4 != 0 || a.conf_x0 % 4 != 0 || a.conf_frame % 4 != 0) return false;
-    if ((reinterpret_cast<uintptr_t>(a.conf_in) & 15u) != 0) return false;
-    if (a.dl_stride % 2 != 0 || a.dl_pair_stride % 2 != 0 || (reinterpret_cast<uintptr_t>(a.dl_in) & 1u) != 0) return false;
+    if (!a.fuse.conf_in || !a.fuse.dl_in) return false;
+    if (a.len < 4 || a.fuse.conf_pitch % 4 != 0 || a.fuse.conf_x0 % 4 != 0 || a.fuse.conf_frame % 4 != 0) return false;
+    if ((reinterpret_cast<uintptr_t>(a.fuse.conf_in) & 15u) != 0) return false;
+    if (a.fuse.dl_stride % 2 != 0 || a.fuse.dl_pair_stride % 2 != 0 || (reinterpret_cast<uintptr_t>(a.fuse.dl_in) & 1u) != 0) return false;
     return true;
 }
 
 bool wave_hpass_lo_half(const WavePassArgs& a)
 {
-    if (!(a.lo_conf && a.lo_half && a.lo_scale_x == 0.5 && (a.hi_x0 & 1) == 0 && a.hi_x0 >= 2)) return false;
+    if (!(a.fuse.lo_conf && a.fuse.lo_half && a.fuse.lo_scale_x == 0.5 && (a.fuse.hi_x0 & 1) == 0 && a.fuse.hi_x0 >= 2)) return false;
     int m, nw;
     pick_row_bucket(a.len, m, nw);
     return !(m == 60 && nw == 1);     // (that bucket's half-width form needs five registers more than a lane has: the general form)
@@ -571,10 +571,10 @@ bool wave_hpass_lo_half(const WavePassArgs& a)
 // must keep rows 4-byte / 2-byte aligned.  The same tap function runs here and in the kernel.
 bool wave_hpass_can_fuse_lo(const WavePassArgs& a)
 {
-    if (!a.lo_conf || !a.lo_dl || a.lo_w < 2 || a.lo_w > 65535 || a.lo_h < 1 || a.len < 2 || a.len > wave_max_row_len()) return false;
-    if ((reinterpret_cast<uintptr_t>(a.lo_conf) & 3u) != 0 || (reinterpret_cast<uintptr_t>(a.lo_dl) & 1u) != 0) return false;
-    if (a.lo_dl_stride % 2 != 0 || a.lo_dl_pair % 2 != 0) return false;
-    if (!(a.lo_scale_x > 0.0 && a.lo_scale_y > 0.0) || a.hi_x0 < 0 || a.hi_y0 < 0) return false;
+    if (!a.fuse.lo_conf || !a.fuse.lo_dl || a.fuse.lo_w < 2 || a.fuse.lo_w > 65535 || a.fuse.lo_h < 1 || a.len < 2 || a.len > wave_max_row_len()) return false;
+    if ((reinterpret_cast<uintptr_t>(a.fuse.lo_conf) & 3u) != 0 || (reinterpret_cast<uintptr_t>(a.fuse.lo_dl) & 1u) != 0) return false;
+    if (a.fuse.lo_dl_stride % 2 != 0 || a.fuse.lo_dl_pair % 2 != 0) return false;
+    if (!(a.fuse.lo_scale_x > 0.0 && a.fuse.lo_scale_y > 0.0) || a.fuse.hi_x0 < 0 || a.fuse.hi_y0 < 0) return false;
     int m, nw;
     pick_row_bucket(a.len, m, nw);
     const int mq = m / 4, kh = (mq + 1) / 2, cap = lo_row_cap(m);
@@ -584,8 +584,8 @@ bool wave_hpass_can_fuse_lo(const WavePassArgs& a)
             const int clast = std::min(64 * m * wv + 256 * (hh ? mq : kh), a.len) - 1;
             if (clast < cfirst) continue;
             int s_first, s_last; float f_;
-            lin_tap(a.hi_x0 + cfirst, a.lo_scale_x, a.lo_w, s_first, f_);
-            lin_tap(a.hi_x0 + clast, a.lo_scale_x, a.lo_w, s_last, f_);
+            lin_tap(a.fuse.hi_x0 + cfirst, a.fuse.lo_scale_x, a.fuse.lo_w, s_first, f_);
+            lin_tap(a.fuse.hi_x0 + clast, a.fuse.lo_scale_x, a.fuse.lo_w, s_last, f_);
             if (s_last + 2 - s_first > cap) return false;
         }
     return true;
@@ -594,8 +594,8 @@ bool wave_hpass_can_fuse_lo(const WavePassArgs& a)
 hipError_t launch_wave_hpass(const WavePassArgs& a, int n_rhs, int n_pairs, hipStream_t st)
 {
     if (a.len < 2 || a.len > wave_max_row_len() || a.pitch % 64 != 0 || a.pitch < a.len) return hipErrorInvalidValue;
-    if (a.lo_conf && !wave_hpass_can_fuse_lo(a)) return hipErrorInvalidValue;
-    if (!a.lo_conf && a.conf_in && !wave_hpass_can_fuse(a)) return hipErrorInvalidValue;
+    if (a.fuse.lo_conf && !wave_hpass_can_fuse_lo(a)) return hipErrorInvalidValue;
+    if (!a.fuse.lo_conf && a.fuse.conf_in && !wave_hpass_can_fuse(a)) return hipErrorInvalidValue;
     int m, nw;
     pick_row_bucket(a.len, m, nw);
     if (nw == 2) {           // wider than 4096 columns: two wavefronts per row

@@ -1,6 +1,6 @@
 """The wave solver (ADF_SOLVER_WAVE) bucket by bucket against a float64 solve of the same systems.
 
-Window: the generic Fast Global Smoother on float32 sources runs the same run_passes_wave as the WLS filter, with no
+Window: the generic Fast Global Smoother on float32 sources runs the same run_passes as the WLS filter, with no
 normalisation and no rounding, so solver errors show.  Every chunk-length bucket of the row pass (pick_row_bucket) and
 of the column pass (launch_wave_vpass) runs at its shortest and longest length (tests/wave_f64_cases.py), with one
 (R1), two (R2: the pair plane), three (R2+R1: pair and leftover) and four (R2x2) channels.
