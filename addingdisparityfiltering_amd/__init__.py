@@ -6,9 +6,11 @@ filter construction does, and fails loudly if libadf_wls.so has not been built.
 """
 from .ximgproc import (  # noqa: F401
     AdfError,
+    COLOR_BGR2GRAY,
     DisparityFilter,
     DisparityWLSFilter,
     FastGlobalSmootherFilter,
+    INTER_LINEAR,
     PATH_CONF_BAND,
     PATH_FUSED_FIRST_PASS,
     PATH_MERGED_PREP,
@@ -26,11 +28,15 @@ from .ximgproc import (  # noqa: F401
     createDisparityWLSFilterGeneric,
     createFastGlobalSmootherFilter,
     createRightMatcher,
+    cvtColor,
     fastGlobalSmootherFilter,
     filterSpeckles,
     releaseCachedMemory,
     getDisparityVis,
+    halfSize,
+    matcherViews,
     readGT,
+    resize,
     speckleWorkspaceBytes,
 )
 

@@ -106,6 +106,9 @@ SYMBOLS = [
     ("adf_filter_speckles_workspace_bytes", _sz, [_i, _i, _i]),
     ("adf_filter_speckles_device", _i, [_i, _vp, _pd, _pd, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     ("adf_filter_speckles_host", _i, [_i, _vp, _pd, _pd, _i, _i, _i, _i, _i]),
+    ("adf_half_size", _i, [_i, C.POINTER(_i)]),
+    ("adf_prepare_views_device", _i, [_i, _vp, _pd, _pd, _i, _i, _i, _vp, _pd, _pd, _i, _i, _i, _vp]),
+    ("adf_prepare_views_host", _i, [_i, _vp, _pd, _pd, _i, _i, _i, _vp, _pd, _pd, _i, _i, _i]),
 ]
 
 _lib = None

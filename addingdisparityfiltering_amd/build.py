@@ -18,6 +18,7 @@ SOURCES = {
     "bm_matcher.hip": [],
     "sgbm_matcher.hip": [],
     "speckle_kernels.hip": [],
+    "view_prep_kernels.hip": [],
 }
 OUT = os.path.join(_HERE, "libadf_wls.so")
 # -ffp-contract=off: the exact solver and the confidence map reproduce the reference's separate

@@ -12,6 +12,7 @@ edge_filter.hpp (EF.hpp), over the C-ABI in include/adf_wls.h:
     createFastGlobalSmootherFilter(...)             EF.hpp:393
     fastGlobalSmootherFilter(...)                   EF.hpp:413
     filterSpeckles(img, newVal, maxSpeckleSize, maxDiff, buf)   calib3d (outside the reference tree)
+    resize(src, dsize, fx, fy) at half size, cvtColor(src, COLOR_BGR2GRAY)   imgproc (outside the reference tree)
 
 Images are numpy arrays (host path: copied to the GPU and back) or torch CUDA
 tensors (device path: zero-copy, asynchronous on torch's current stream).  A
@@ -571,6 +572,111 @@ def filterSpeckles(img, newVal, maxSpeckleSize, maxDiff, buf=None):
 def speckleWorkspaceBytes(n, H, W):
     """Bytes of device workspace filterSpeckles needs for n maps of H x W (8 per pixel)."""
     return int(_lib.lib().adf_filter_speckles_workspace_bytes(int(n), int(W), int(H)))
+
+
+# ---------------------------------------------------------------------------------------------
+# The matcher's views: the two imgproc calls of the sample's default pipeline (samples/disparity_filtering.cpp:130-141)
+# on the device (csrc/view_prep_kernels.hip; arithmetic and the unpinned odd-size tail: include/adf_wls.h).
+# ---------------------------------------------------------------------------------------------
+COLOR_BGR2GRAY = 6      # cv::COLOR_BGR2GRAY
+INTER_LINEAR = 1        # cv::INTER_LINEAR
+
+
+def halfSize(n):
+    """cvRound(n * 0.5), half to even (adf_half_size): the size cv::resize(.., 0.5, 0.5) gives an axis of n pixels."""
+    v = C.c_int()
+    _lib.check(_lib.lib().adf_half_size(int(n), C.byref(v)))
+    return v.value
+
+
+def _view_image(src, what):
+    """(_Image, batched, colour) of an 8-bit view (H,W), (H,W,3), (N,H,W) or (N,H,W,3); a three-dimensional shape that
+    ends in 3 is one colour image, so a batch of 3-pixel-wide gray images is passed as (N,H,W,1)."""
+    if src is None:
+        raise AdfError(_lib.ADF_EBADARG, "%s is empty" % what)
+    nd = len(src.shape)
+    if nd not in (2, 3, 4):
+        raise AdfError(_lib.ADF_EBADARG, "%s must be (H,W[,3]) or a batch (N,H,W[,3])" % what)
+    if nd == 4 and src.shape[-1] not in (1, 3):
+        raise AdfError(_lib.ADF_EBADARG, "%s has %d channels; CV_8UC1 and CV_8UC3 are supported" % (what, src.shape[-1]))
+    color = src.shape[-1] == 3 and nd in (3, 4)
+    batched = nd == 4 or (nd == 3 and not color)
+    if nd == 4 and not color:
+        src = src[..., 0]                                        # (the stride of a one-element axis means nothing)
+    im = _Image(src, np.uint8, what, batched, allow_channels=(3,) if color else (1,))
+    im.unit_axis = nd == 4 and not color
+    return im, batched, color
+
+
+def _prepare_views(im, batched, half, dst_channels, dst, what):
+    w, h = (halfSize(im.w), halfSize(im.h)) if half else (im.w, im.h)
+    if w < 1 or h < 1:
+        raise AdfError(_lib.ADF_EBADARG, "%s: the half-size image of %d x %d is empty" % (what, im.w, im.h))
+    unit = im.unit_axis and dst_channels == 1                    # (N,H,W,1) in, (N,h,w,1) out
+    shape = ((im.n,) if batched else ()) + (h, w) + ((3,) if dst_channels == 3 else (1,) if unit else ())
+    if dst is None:
+        dst = torch.empty(shape, dtype=torch.uint8, device=im.keep.device) if im.device else np.empty(shape, np.uint8)
+    if tuple(dst.shape) != shape:
+        raise AdfError(_lib.ADF_ESIZE, "%s: dst must have shape %s" % (what, shape))
+    D = _Image(dst[..., 0] if unit else dst, np.uint8, "dst", batched, allow_channels=(dst_channels,))
+    if (D.n, D.h, D.w) != (im.n, h, w) or D.device != im.device:
+        raise AdfError(_lib.ADF_ESIZE, "%s: dst must have shape %s on the side (host or device) of src" % (what, shape))
+    args = [im.n, C.c_void_p(im.ptr), im.stride, im.pair_stride, im.w, im.h, im.c,
+            C.c_void_p(D.ptr), D.stride, D.pair_stride, w, h, dst_channels]
+    if not im.device:
+        _lib.check(_lib.lib().adf_prepare_views_host(*args))
+        return dst
+    if dst.device != im.keep.device:
+        raise AdfError(_lib.ADF_EBADARG, "dst lives on %s, src on %s" % (dst.device, im.keep.device))
+    with torch.cuda.device(im.keep.device):
+        _lib.check(_lib.lib().adf_prepare_views_device(*args, _stream_of(im)))
+    return dst
+
+
+def resize(src, dsize=None, fx=0, fy=0, interpolation=INTER_LINEAR, dst=None):
+    """cv::resize(src, dst, dsize, fx, fy, INTER_LINEAR) for the one scale the sample uses (SAMPLE:137-138):
+    fx == fy == 0.5, or the `dsize` (width, height) that scale gives, (halfSize(W), halfSize(H)).  The 2x2 mean
+    (a + b + c + d + 2) >> 2 per channel, bit-exact; odd sizes: include/adf_wls.h (parity unpinned).  `src` is a CV_8UC1 /
+    CV_8UC3 image (H,W[,3]) or a batch (N,H,W[,3]) -- a batch of 3-pixel-wide gray images goes as (N,H,W,1) -- ; a torch
+    CUDA tensor is resized on the device, asynchronously on torch's current stream (row strides of a sliced view are
+    honoured), a numpy array takes the host entry point.  `dst`: an output of the right shape to write into (with it the
+    device call allocates nothing and may be captured into a CUDA graph)."""
+    if interpolation != INTER_LINEAR:
+        raise AdfError(_lib.ADF_EBADARG, "resize supports INTER_LINEAR at a scale of exactly 0.5 only")
+    im, batched, color = _view_image(src, "src")
+    if dsize is not None and tuple(dsize) != (0, 0):
+        if tuple(int(v) for v in dsize) != (halfSize(im.w), halfSize(im.h)):
+            raise AdfError(_lib.ADF_EBADARG, "resize supports half size only: dsize must be (%d, %d) for a %d x %d image"
+                           % (halfSize(im.w), halfSize(im.h), im.w, im.h))
+    elif not (fx == 0.5 and fy == 0.5):
+        raise AdfError(_lib.ADF_EBADARG, "resize supports fx == fy == 0.5 only (got fx=%r, fy=%r)" % (fx, fy))
+    return _prepare_views(im, batched, True, im.c, dst, "resize")
+
+
+def cvtColor(src, code, dst=None):
+    """cv::cvtColor(src, dst, COLOR_BGR2GRAY) (SAMPLE:155-156): (B*1868 + G*9617 + R*4899 + 8192) >> 14, bit-exact.
+    `src` is a CV_8UC3 image (H,W,3) or a batch (N,H,W,3), numpy (host entry) or torch CUDA (device, current stream)."""
+    if code != COLOR_BGR2GRAY:
+        raise AdfError(_lib.ADF_EBADARG, "cvtColor supports COLOR_BGR2GRAY only (got code %r)" % (code,))
+    im, batched, color = _view_image(src, "src")
+    if not color:
+        raise AdfError(_lib.ADF_EBADARG, "cvtColor(COLOR_BGR2GRAY) needs a 3-channel image")
+    return _prepare_views(im, batched, False, 1, dst, "cvtColor")
+
+
+def matcherViews(view, scale=0.5, gray=True, dst=None):
+    """Extension: what the sample feeds its matcher, from a full-size view, in ONE launch -- resize(view, 0.5, 0.5) then
+    cvtColor(BGR2GRAY) without the half-size colour image ever being written (identical, bit for bit, to the two calls).
+    scale 0.5 or 1.0; gray=False keeps the channels (StereoSGBM takes colour views: that is resize()).  `view` may
+    hold all left and all right views of a batch in one tensor."""
+    if scale not in (0.5, 1.0, 1):
+        raise AdfError(_lib.ADF_EBADARG, "matcherViews supports scale 0.5 and 1.0 only (got %r)" % (scale,))
+    im, batched, color = _view_image(view, "view")
+    half = scale == 0.5
+    to_gray = bool(gray) and color
+    if not half and not to_gray:
+        raise AdfError(_lib.ADF_EBADARG, "matcherViews: scale 1.0 without a colour conversion leaves nothing to do")
+    return _prepare_views(im, batched, half, 1 if to_gray else im.c, dst, "matcherViews")
 
 
 def createDisparityWLSFilter(matcher_left):

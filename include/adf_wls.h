@@ -402,6 +402,44 @@ int adf_filter_speckles_device(int n_maps, int16_t* img, ptrdiff_t stride, ptrdi
 int adf_filter_speckles_host(int n_maps, int16_t* img, ptrdiff_t stride, ptrdiff_t map_stride, int W, int H,
                              int new_val, int max_speckle_size, int max_diff);
 
+/* ---------------- the matcher's views (cv::resize to half size, cv::cvtColor BGR2GRAY) ----------------
+ * The two imgproc calls the sample's default pipeline makes before matching (samples/disparity_filtering.cpp:130-141):
+ *     resize(left, left_for_matcher, Size(), 0.5, 0.5);              both views, colour
+ *     cvtColor(left_for_matcher, left_for_matcher, COLOR_BGR2GRAY);  StereoBM only
+ * on n_images equally sized 8-bit images, rows `stride` bytes apart, images `image_stride` bytes apart (all left views
+ * then all right views, or interleaved pairs: both are a batch of images).  Four cases:
+ *     src_channels 3 -> dst_channels 3, half size     resize(.., 0.5, 0.5) on CV_8UC3
+ *     src_channels 1 -> dst_channels 1, half size     the same on CV_8UC1
+ *     src_channels 3 -> dst_channels 1, same size     cvtColor(COLOR_BGR2GRAY)
+ *     src_channels 3 -> dst_channels 1, half size     both in one sweep (the half-size colour image is never written)
+ * (dst_W, dst_H) must be (W, H) or (adf_half_size(W), adf_half_size(H)).  Every other scale, 1 -> 3 channels, 4 channels
+ * and a same-size call that would change nothing are ADF_EBADARG; general INTER_LINEAR is not built.
+ * Arithmetic, all integer, so every case is bit-exact and the fused case equals the two-step case:
+ *   - half size: the destination is cvRound(W * 0.5) x cvRound(H * 0.5), half to even (1242 x 375 -> 621 x 188); cv::resize
+ *     with INTER_LINEAR at a scale of exactly 2 in both directions is the 2x2 mean, (a + b + c + d + 2) >> 2 per channel;
+ *   - where the last destination column or row has a single source column / row (W or H = 3 mod 4), the sample is the
+ *     mean over the source pixels that exist, cvRound((float)sum / count), half to even;
+ *   - gray: (B * 1868 + G * 9617 + R * 4899 + 8192) >> 14 on the 8-bit channels (in the fused case: the rounded ones),
+ *     channel order B, G, R.
+ * imgproc is outside the reference tree.  The even-size case is what the replay of the tutorial's pair against its
+ * published result images rests on; for odd sizes (the single-column / single-row tail) parity with OpenCV is UNPINNED:
+ * the rule above is this library's definition.
+ * src and dst must not overlap.  Destination images of a batch must not overlap each other (they follow one another,
+ * or interleave row by row).  Images whose source base and strides are 16-byte aligned and whose destination base and
+ * strides are 16-byte aligned (8 is enough at half size) take the vector path; anything else is computed byte by byte
+ * (same results, slower).
+ * _device: device pointers on the current HIP device, asynchronous on `stream`; no allocation, no synchronisation, so
+ * the call may be captured into a hipGraph.  _host: host pointers; copies, runs and synchronises. */
+int adf_half_size(int n, int* half); /* cvRound(n * 0.5), half to even: every layer computes dsize with it */
+int adf_prepare_views_device(int n_images, const uint8_t* src, ptrdiff_t src_stride, ptrdiff_t src_image_stride,
+                             int W, int H, int src_channels,
+                             uint8_t* dst, ptrdiff_t dst_stride, ptrdiff_t dst_image_stride,
+                             int dst_W, int dst_H, int dst_channels, void* stream);
+int adf_prepare_views_host(int n_images, const uint8_t* src, ptrdiff_t src_stride, ptrdiff_t src_image_stride,
+                           int W, int H, int src_channels,
+                           uint8_t* dst, ptrdiff_t dst_stride, ptrdiff_t dst_image_stride,
+                           int dst_W, int dst_H, int dst_channels);
+
 #ifdef __cplusplus
 }
 #endif

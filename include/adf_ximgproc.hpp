@@ -103,6 +103,57 @@ inline void filterSpeckles(Mat& img, double newVal, int maxSpeckleSize, double m
                                    (int)nv, maxSpeckleSize, (int)md));
 }
 
+// The two imgproc calls in front of the matcher in the sample's default pipeline (samples/disparity_filtering.cpp:130-141;
+// adf_prepare_views_* in adf_wls.h) on host Mats, through the library's host entry.  Same limits as the C-ABI:
+//   resize    CV_8UC1 / CV_8UC3, INTER_LINEAR, fx == fy == 0.5 or the dsize that scale gives (halfSize of both axes):
+//             the 2x2 mean (a + b + c + d + 2) >> 2; odd sizes: adf_wls.h (parity unpinned)
+//   cvtColor  COLOR_BGR2GRAY on CV_8UC3: (B * 1868 + G * 9617 + R * 4899 + 8192) >> 14
+// src and dst may be the same Mat, as in the sample.
+// dsize is cv::Size with OpenCV (a template parameter, so that this header asks nothing of opencv2/core.hpp that the
+// rest of it does not use) and the stand-in below without.
+#ifndef ADF_HAVE_OPENCV
+struct Size {
+    int width = 0, height = 0;
+    Size() {}
+    Size(int w, int h) : width(w), height(h) {}
+};
+#endif
+enum { INTER_LINEAR = 1, COLOR_BGR2GRAY = 6 }; // cv's values
+
+inline int halfSize(int n) { int h = 0; check(adf_half_size(n, &h)); return h; } // cvRound(n * 0.5)
+
+template <class SizeT>
+inline void resize(const Mat& src, Mat& dst, SizeT dsize, double fx = 0, double fy = 0, int interpolation = INTER_LINEAR)
+{
+    if (src.empty() || mat_depth(src) != D8U || (mat_channels(src) != 1 && mat_channels(src) != 3))
+        throw Exception(ADF_EBADARG, "resize: src must be a non-empty CV_8UC1 or CV_8UC3 image");
+    if (interpolation != INTER_LINEAR) throw Exception(ADF_EBADARG, "resize: INTER_LINEAR at a scale of exactly 0.5 only");
+    const int w = halfSize(src.cols), h = halfSize(src.rows);
+    if (dsize.width != 0 || dsize.height != 0) {
+        if (dsize.width != w || dsize.height != h) throw Exception(ADF_EBADARG, "resize: half size only (dsize must be halfSize of both axes)");
+    } else if (!(fx == 0.5 && fy == 0.5)) {
+        throw Exception(ADF_EBADARG, "resize: fx == fy == 0.5 only");
+    }
+    if (w < 1 || h < 1) throw Exception(ADF_EBADARG, "resize: the half-size image is empty");
+    Mat out;
+    mat_create(out, h, w, D8U, mat_channels(src));
+    check(adf_prepare_views_host(1, src.data, mat_step(src), 0, src.cols, src.rows, mat_channels(src),
+                                 out.data, mat_step(out), 0, w, h, mat_channels(src)));
+    dst = out;
+}
+
+inline void cvtColor(const Mat& src, Mat& dst, int code, int dstCn = 0)
+{
+    if (code != COLOR_BGR2GRAY || (dstCn != 0 && dstCn != 1)) throw Exception(ADF_EBADARG, "cvtColor: COLOR_BGR2GRAY only");
+    if (src.empty() || mat_depth(src) != D8U || mat_channels(src) != 3)
+        throw Exception(ADF_EBADARG, "cvtColor: src must be a non-empty CV_8UC3 image");
+    Mat out;
+    mat_create(out, src.rows, src.cols, D8U, 1);
+    check(adf_prepare_views_host(1, src.data, mat_step(src), 0, src.cols, src.rows, 3, out.data, mat_step(out), 0,
+                                 src.cols, src.rows, 1));
+    dst = out;
+}
+
 namespace ximgproc {
 
 // DF.hpp:52-76
