@@ -8,6 +8,7 @@ CSRC = os.path.join(_HERE, "csrc")
 # source -> extra flags
 SOURCES = {
     "adf_api.hip": [],
+    "adf_host.hip": [],
     "conf_kernels.hip": [],
     "weights_kernels.hip": [],
     "fgs_exact.hip": [],

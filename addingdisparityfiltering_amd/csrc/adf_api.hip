@@ -3,66 +3,17 @@
 // Orchestrates DisparityWLSFilterImpl::filter (DF.cpp:219-298) and
 // FastGlobalSmootherFilterImpl::{init,filter} (FGS.cpp:141-233) as a fixed sequence of HIP kernel
 // launches on the caller's stream.  No host<->device synchronisation happens on the device-pointer
-// path after the workspace exists, so a caller may capture it into a hipGraph.
-#include "adf_internal.h"
-#include "../../include/adf_wls.h"
+// path after the workspace exists, so a caller may capture it into a hipGraph.  Errors, device memory, the weight
+// tables and the host entry points' copies come from the shared host toolkit (adf_host.h).
+#include "adf_host.h"
 
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <memory>
-#include <mutex>
 #include <new>
-#include <thread>
-#include <vector>
 
 using namespace adf;
-
-// ----------------------------------------------------------------------------------------------
-// error plumbing
-// ----------------------------------------------------------------------------------------------
-static thread_local char g_err[512] = "";
-
-static int fail(int code, const char* fmt, ...)
-{
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(g_err, sizeof(g_err), fmt, ap);
-    va_end(ap);
-    return code;
-}
-
-// error reporting for the other translation units (declared in adf_internal.h)
-namespace adf {
-int set_error(int code, const char* msg) { return fail(code, "%s", msg); }
-}
-
-#define HIP_TRY(expr)                                                                         \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail(e_ == hipErrorOutOfMemory ? ADF_ENOMEM : ADF_EHIP, "%s failed: %s",   \
-                        #expr, hipGetErrorString(e_));                                        \
-    } while (0)
-
-extern "C" int adf_version(void) { return ADF_VERSION; }
-extern "C" const char* adf_last_error(void) { return g_err; }
-extern "C" int adf_device_count(void)
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
-
-extern "C" int adf_device_pci_bus_id(int device, char* buf, int len)
-{
-    if (!buf || len < 16) return fail(ADF_EBADARG, "adf_device_pci_bus_id: buffer of at least 16 bytes required");
-    buf[0] = 0;
-    HIP_TRY(hipDeviceGetPCIBusId(buf, len, device));
-    return ADF_OK;
-}
 
 // ----------------------------------------------------------------------------------------------
 // shared pieces
@@ -87,225 +38,6 @@ static Geom make_geom(int W, int H, int rx, int ry, int rw, int rh)
 
 // Confidence plane as a plain W-pitch frame (the low-resolution scratch map of the down-scaled path).
 static Geom plain_conf_layout(Geom g) { g.cx0 = 0; g.cpitch = g.W; g.cframe = g.frame; return g; }
-
-// RAII: run on the handle's device, restore the caller's on exit.
-struct DeviceScope {
-    int prev = -1; bool switched = false;
-    explicit DeviceScope(int dev)
-    {
-        if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceScope() { if (switched) hipSetDevice(prev); }
-};
-
-static bool stream_is_capturing(hipStream_t st)
-{
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return cs != hipStreamCaptureStatusNone;
-}
-
-// Growable device buffer (never shrinks; freed with the handle).
-struct DevBuf {
-    void* p = nullptr; size_t bytes = 0;
-    int reserve(size_t need, hipStream_t st)
-    {
-        if (need <= bytes) return ADF_OK;
-        if (p) { HIP_TRY(hipStreamSynchronize(st)); HIP_TRY(hipFree(p)); p = nullptr; bytes = 0; }
-        need = (need + 255) / 256 * 256;
-        HIP_TRY(adf::device_malloc(&p, need));
-        bytes = need;
-        // deterministic padding lanes: the sweeps read (and discard) pitch padding
-        HIP_TRY(hipMemsetAsync(p, 0, need, st));
-        return ADF_OK;
-    }
-    void release() { if (p) hipFree(p); p = nullptr; bytes = 0; }
-};
-
-// Weight LUTs (FGS.cpp:150-154, 663-675), built on the host with libm, one immutable device table per sigma seen
-// (up to LUT_CACHE of them per handle).  Round 3: a table is never rewritten, so coming back to a sigma used before --
-// the common way callers vary it -- is a pointer switch with no device work and no synchronisation (capturable into a
-// hipGraph), and a NEW sigma no longer drains the stream: its table goes into a fresh buffer no kernel in flight can be
-// reading.  Only that first upload is a synchronous copy; a caller that captures filter calls must have used every
-// sigma it switches between once before the capture (include/adf_wls.h).
-//
-// Tables are shared by every handle of the process on the same device (LutStore): the one-shot function
-// fastGlobalSmootherFilter (EF.hpp:413) and the reference's own perf test (perf_fgs_filter.cpp:70-76) create a filter
-// per call, and 3*256*256 libm calls cost ~1 ms on one core -- ten times the 720p filter call itself.  A table seen
-// before is a look-up; a new one is built by a few threads (each entry is the same scalar libm expression as before:
-// same bits).
-struct LutTable {
-    int device = 0; float sigma = 0; float* dev = nullptr;
-    LutTable() = default;
-    LutTable(const LutTable&) = delete;
-    LutTable& operator=(const LutTable&) = delete;
-    ~LutTable() { if (dev) { DeviceScope ds(device); hipFree(dev); } }
-};
-
-struct LutStore {
-    static constexpr size_t CAP = 16;
-    std::mutex m;
-    std::vector<std::shared_ptr<LutTable>> tables;               // most recently used last
-    static LutStore& get() { static LutStore* s = new LutStore; return *s; }   // (never destroyed: no HIP calls at exit)
-    std::shared_ptr<LutTable> find(int device, float sigma)
-    {
-        std::lock_guard<std::mutex> lk(m);
-        for (size_t k = 0; k < tables.size(); k++)
-            if (tables[k]->device == device && tables[k]->sigma == sigma) {
-                auto t = tables[k];
-                tables.erase(tables.begin() + (ptrdiff_t)k); tables.push_back(t);
-                return t;
-            }
-        return nullptr;
-    }
-    void add(const std::shared_ptr<LutTable>& t)
-    {
-        std::lock_guard<std::mutex> lk(m);
-        // (a table dropped here lives on while a handle still refers to it; with no handle left nothing can be reading it)
-        if (tables.size() >= CAP) tables.erase(tables.begin());
-        tables.push_back(t);
-    }
-    void clear() { std::lock_guard<std::mutex> lk(m); tables.clear(); }
-};
-
-static void lut_build_host(float s, float* host)
-{
-    auto span = [&](int a, int b) { for (int i = a; i < b; i++) host[i] = -expf(-sqrtf((float)i) / s); };
-    // Where the argument is at or below -110 the float exponential is +0 -- exp(-110) = 1.7e-48 lies 400 times below half
-    // the smallest denormal, so every libm returns zero there, and the entry is -0.0f.  With the filter's usual sigma
-    // (1..2) that is nine tenths of the table: those entries are stored, not computed.  The argument falls
-    // monotonically with i (sqrtf and the division are monotone), so the first such index bounds the computed part.
-    int n = ADF_LUT_LEVELS;
-    if (s > 0.0f) {
-        const double lim = 110.0 * (double)s;
-        if (lim * lim * 1.001 + 2.0 < (double)ADF_LUT_LEVELS) {
-            int i0 = (int)(lim * lim * 1.001) + 2;
-            while (i0 < ADF_LUT_LEVELS && !(-sqrtf((float)i0) / s <= -110.0f)) i0++;   // (a check, not a search: the margin covers it)
-            n = i0;
-        }
-    }
-    for (int i = n; i < ADF_LUT_LEVELS; i++) host[i] = -0.0f;
-    unsigned hw = std::thread::hardware_concurrency();
-    int nt = (int)(hw >= 16 ? 8 : hw >= 4 ? hw / 2 : 1);
-    if (n < 32768) nt = 1;                                        // a thread costs more to start than such a share to compute
-    if (nt <= 1) { span(0, n); return; }
-    std::vector<std::thread> th;
-    const int per = (n + nt - 1) / nt;
-    bool ok = true;
-    int done = std::min(per, n);                                  // the caller's own share is [0, per)
-    for (int t = 1; t < nt && ok; t++) {
-        const int a = t * per, b = std::min(n, a + per);
-        if (a >= b) break;
-        try { th.emplace_back(span, a, b); done = b; } catch (...) { ok = false; }
-    }
-    span(0, std::min(per, n));
-    for (auto& t : th) t.join();
-    if (done < n) span(done, n);                                  // threads that could not be started
-}
-
-struct Lut {
-    static constexpr int LUT_CACHE = 8;
-    struct Entry { std::shared_ptr<LutTable> t; unsigned long long used; };
-    std::vector<Entry> tables;
-    const float* cur = nullptr;
-    unsigned long long tick = 0;
-    size_t bytes() const { return tables.size() * sizeof(float) * ADF_LUT_LEVELS; }
-    int ensure(float s, hipStream_t st)
-    {
-        for (auto& e : tables)
-            if (e.t->sigma == s) { e.used = ++tick; cur = e.t->dev; return ADF_OK; }
-        if ((int)tables.size() >= LUT_CACHE) {                 // drop the least recently used table: kernels of
-            size_t lru = 0;                                    // earlier calls on `st` may still read it
-            for (size_t k = 1; k < tables.size(); k++) if (tables[k].used < tables[lru].used) lru = k;
-            HIP_TRY(hipStreamSynchronize(st));
-            tables.erase(tables.begin() + (ptrdiff_t)lru);
-        }
-        int device = 0;
-        HIP_TRY(hipGetDevice(&device));
-        std::shared_ptr<LutTable> t = LutStore::get().find(device, s);
-        if (!t) {
-            std::vector<float> host(ADF_LUT_LEVELS);
-            lut_build_host(s, host.data());
-            float* d = nullptr;
-            HIP_TRY(hipMalloc(&d, sizeof(float) * ADF_LUT_LEVELS));
-            hipError_t e = hipMemcpy(d, host.data(), sizeof(float) * ADF_LUT_LEVELS, hipMemcpyHostToDevice);
-            if (e != hipSuccess) { hipFree(d); return fail(ADF_EHIP, "LUT upload failed: %s", hipGetErrorString(e)); }
-            t = std::make_shared<LutTable>();
-            t->device = device; t->sigma = s; t->dev = d;
-            LutStore::get().add(t);
-        }
-        tables.push_back(Entry{t, ++tick});
-        cur = t->dev;
-        return ADF_OK;
-    }
-    // (the caller has made sure no kernel still reads the tables: handle destruction synchronises first)
-    void release() { tables.clear(); cur = nullptr; }
-};
-
-// Device blocks of short-lived handles (adf_fgs: the planes and the staged image of ONE image), kept for the next
-// handle instead of going back to the driver: hipMalloc + hipFree of a 4K handle's 300 MB cost more than its filter
-// call, and hipFree waits for the whole device.  A block comes back with the event behind its last user; whoever takes
-// it makes its own stream wait for that event first, so nobody synchronises the host.
-struct BlockCache {
-    struct Ent { int device; void* p; size_t bytes; hipEvent_t ready; };
-    static constexpr size_t CAP_BYTES = (size_t)3 << 30;
-    static constexpr size_t CAP_ENTRIES = 8;
-    std::mutex m;
-    std::vector<Ent> ents;                                         // oldest first
-    size_t total = 0;
-    static BlockCache& get() { static BlockCache* c = new BlockCache; return *c; }
-    static void drop(const Ent& e)
-    {
-        DeviceScope ds(e.device);
-        if (e.ready) { hipEventSynchronize(e.ready); hipEventDestroy(e.ready); }
-        hipFree(e.p);
-    }
-    // a cached block of at least `need` bytes (and not wastefully larger), ordered into `st`; null if there is none
-    void* take(int device, size_t need, hipStream_t st, size_t* bytes)
-    {
-        Ent hit{};
-        {
-            std::lock_guard<std::mutex> lk(m);
-            size_t best = ents.size();
-            for (size_t k = 0; k < ents.size(); k++)
-                if (ents[k].device == device && ents[k].bytes >= need && ents[k].bytes <= need + need / 4 + ((size_t)1 << 20) &&
-                    (best == ents.size() || ents[k].bytes < ents[best].bytes))
-                    best = k;
-            if (best == ents.size()) return nullptr;
-            hit = ents[best];
-            ents.erase(ents.begin() + (ptrdiff_t)best);
-            total -= hit.bytes;
-        }
-        if (hit.ready) {
-            const hipError_t e = hipStreamWaitEvent(st, hit.ready, 0);
-            if (e != hipSuccess) hipEventSynchronize(hit.ready);
-            hipEventDestroy(hit.ready);
-        }
-        *bytes = hit.bytes;
-        return hit.p;
-    }
-    void give(int device, void* p, size_t bytes, hipEvent_t ready)
-    {
-        std::vector<Ent> out;
-        {
-            std::lock_guard<std::mutex> lk(m);
-            ents.push_back(Ent{device, p, bytes, ready});
-            total += bytes;
-            while (!ents.empty() && (total > CAP_BYTES || ents.size() > CAP_ENTRIES)) {
-                out.push_back(ents.front());
-                total -= ents.front().bytes;
-                ents.erase(ents.begin());
-            }
-        }
-        for (auto& e : out) drop(e);
-    }
-    void clear()
-    {
-        std::vector<Ent> out;
-        { std::lock_guard<std::mutex> lk(m); out.swap(ents); total = 0; }
-        for (auto& e : out) drop(e);
-    }
-};
 
 // Per-launch HIP-event timing (adf_wls_profile_*).  Events are pooled and reused.
 enum KClass { K_FILL = 0, K_WEIGHTS, K_DISC, K_LRC, K_PROLOGUE, K_PASS_H_FIRST, K_PASS_H, K_PASS_V, K_PASS_V_LAST, K_RESIZE, K_COUNT };
@@ -538,7 +270,6 @@ extern "C" void adf_wls_destroy(adf_wls_t* h)
     delete h;
 }
 
-#define NEED_HANDLE(h) do { if (!(h)) return fail(ADF_EBADARG, "%s: handle is NULL", __func__); } while (0)
 
 extern "C" int adf_wls_set_lambda(adf_wls_t* h, double v) { NEED_HANDLE(h); h->lambda = v; return ADF_OK; }
 extern "C" int adf_wls_get_lambda(const adf_wls_t* h, double* v) { NEED_HANDLE(h); if (v) *v = h->lambda; return ADF_OK; }
@@ -588,7 +319,7 @@ extern "C" int adf_wls_sync(adf_wls_t* h, void* stream)
 // never is, so the buffer is cleared whenever the layout it was last used with changes.
 static int ensure_conf_planes(adf_wls* h, const Geom& g, int n_pairs, hipStream_t st)
 {
-    int rc = h->conf.reserve(g.cframe * sizeof(float) * (size_t)n_pairs, st);
+    int rc = h->conf.reserve(g.cframe * sizeof(float) * (size_t)n_pairs, st, FILL_ZERO);
     if (rc) return rc;
     const long long sig[4] = {g.W, g.H, g.cx0, n_pairs};
     if (memcmp(sig, h->conf_sig, sizeof(sig)) != 0) {
@@ -864,7 +595,7 @@ static int wls_filter_impl(adf_wls_t* h, int n_pairs,
     const WlsPlan plan = plan_wls(h, g, n_pairs, dispL, sL, psL, sG, gch, scaled);
     const bool wave = plan.wave;
     h->last_solver = wave ? ADF_SOLVER_WAVE : ADF_SOLVER_EXACT;
-    if ((rc = h->ws.reserve(plan.per_pair * (size_t)plan.chunk, st))) return rc;
+    if ((rc = h->ws.reserve(plan.per_pair * (size_t)plan.chunk, st, FILL_ZERO))) return rc;
     if (conf && !scaled && (rc = ensure_conf_planes(h, g, n_pairs, st))) return rc;
     {
         const long long sig[8] = {W, H, roi.x, roi.y, roi.width, roi.height, (long long)plan.band * 4 + (long long)wave * 2 + conf, plan.chunk};
@@ -1063,7 +794,7 @@ extern "C" int adf_wls_filter_scaled_device(adf_wls_t* h, int n_pairs,
     s.dhi_bytes = s.fuse_lo ? 0 : (hi * 2 + 255) / 256 * 256;
     const size_t maps_bytes = ((size_t)n_pairs * (s.dhi_bytes + (conf ? 3 * lo * sizeof(float) : 0)) + 255) / 256 * 256;
     const size_t need = maps_bytes + (s.fuse_lo ? 2 * ((size_t)rhi.width + 4) * sizeof(float) : 0);   // + the columns' taps
-    if ((rc = h->scaled.reserve(need, st))) return rc;
+    if ((rc = h->scaled.reserve(need, st, FILL_ZERO))) return rc;
     s.dhi = (char*)h->scaled.p;
     s.cl = (float*)(s.dhi + (size_t)n_pairs * s.dhi_bytes);
     s.cr = s.cl + (size_t)n_pairs * lo;
@@ -1095,29 +826,21 @@ extern "C" int adf_wls_filter_scaled_host(adf_wls_t* h, int n_pairs,
     const size_t dbytes = (size_t)dW * dH * 2, obytes = (size_t)W * H * 2, gbytes = (size_t)W * H * gch;
     const size_t dpad = (dbytes + 255) / 256 * 256, opad = (obytes + 255) / 256 * 256, gpad = (gbytes + 255) / 256 * 256;
     const size_t need = (size_t)n_pairs * (2 * dpad + opad + gpad);
-    int rc = h->stage.reserve(need, st);
+    int rc = h->stage.reserve(need, st, FILL_ZERO);
     if (rc) return rc;
     char* dLd = (char*)h->stage.p;
     char* dRd = dLd + (size_t)n_pairs * dpad;
     char* od = dRd + (size_t)n_pairs * dpad;
     char* gd = od + (size_t)n_pairs * opad;
-    for (int k = 0; k < n_pairs; k++) {
-        HIP_TRY(hipMemcpy2DAsync(dLd + k * dpad, (size_t)dW * 2, (const char*)dispL + (ptrdiff_t)k * psL, sL,
-                                 (size_t)dW * 2, dH, hipMemcpyHostToDevice, st));
-        if (dispR)
-            HIP_TRY(hipMemcpy2DAsync(dRd + k * dpad, (size_t)dW * 2, (const char*)dispR + (ptrdiff_t)k * psR, sR,
-                                     (size_t)dW * 2, dH, hipMemcpyHostToDevice, st));
-        HIP_TRY(hipMemcpy2DAsync(gd + k * gpad, (size_t)W * gch, view + (ptrdiff_t)k * psG, sG,
-                                 (size_t)W * gch, H, hipMemcpyHostToDevice, st));
-    }
+    if ((rc = copy_images(dLd, (size_t)dW * 2, dpad, dispL, sL, psL, (size_t)dW * 2, dH, n_pairs, hipMemcpyHostToDevice, st))) return rc;
+    if (dispR && (rc = copy_images(dRd, (size_t)dW * 2, dpad, dispR, sR, psR, (size_t)dW * 2, dH, n_pairs, hipMemcpyHostToDevice, st))) return rc;
+    if ((rc = copy_images(gd, (size_t)W * gch, gpad, view, sG, psG, (size_t)W * gch, H, n_pairs, hipMemcpyHostToDevice, st))) return rc;
     rc = adf_wls_filter_scaled_device(h, n_pairs, (const int16_t*)dLd, (ptrdiff_t)dW * 2, (ptrdiff_t)dpad, dW, dH,
                                       (const uint8_t*)gd, (ptrdiff_t)W * gch, (ptrdiff_t)gpad, gch, W, H,
                                       (int16_t*)od, (ptrdiff_t)W * 2, (ptrdiff_t)opad,
                                       dispR ? (const int16_t*)dRd : nullptr, (ptrdiff_t)dW * 2, (ptrdiff_t)dpad, roi, st);
     if (rc) return rc;
-    for (int k = 0; k < n_pairs; k++)
-        HIP_TRY(hipMemcpy2DAsync((char*)out + (ptrdiff_t)k * psO, sO, od + k * opad, (size_t)W * 2,
-                                 (size_t)W * 2, H, hipMemcpyDeviceToHost, st));
+    if ((rc = copy_images(out, sO, psO, od, (size_t)W * 2, opad, (size_t)W * 2, H, n_pairs, hipMemcpyDeviceToHost, st))) return rc;
     HIP_TRY(hipStreamSynchronize(st));
     return ADF_OK;
 }
@@ -1266,9 +989,9 @@ static int fgs_create_impl(adf_fgs_t** out, const uint8_t* guide, ptrdiff_t gstr
     const size_t planes_bytes = (6 * f->g.plane * sizeof(float) + 255) / 256 * 256;
     const size_t io_bytes = ((gbytes > (size_t)w * hgt * 16 ? gbytes : (size_t)w * hgt * 16) + 255) / 256 * 256;
     hipError_t e = hipSuccess;
-    f->block = BlockCache::get().take(f->device, planes_bytes + io_bytes, st, &f->block_bytes);
+    f->block = cache_take(f->device, planes_bytes + io_bytes, st, &f->block_bytes);
     if (!f->block) {
-        e = adf::device_malloc(&f->block, planes_bytes + io_bytes);  // (clears the cache and retries when the driver refuses)
+        e = device_malloc(&f->block, planes_bytes + io_bytes);  // (clears the cache and retries when the driver refuses)
         if (e != hipSuccess) {
             f->block = nullptr; adf_fgs_destroy(f);
             return fail(e == hipErrorOutOfMemory ? ADF_ENOMEM : ADF_EHIP, "adf_fgs_create: %s", hipGetErrorString(e));
@@ -1316,48 +1039,6 @@ extern "C" int adf_fgs_create_device(adf_fgs_t** out, const uint8_t* guide, ptrd
                            (hipStream_t)stream);
 }
 
-extern "C" int adf_weight_table_host(float sigma_color, float* table, int levels)
-{
-    if (!table || levels != ADF_LUT_LEVELS) return fail(ADF_EBADARG, "table must hold %d floats", ADF_LUT_LEVELS);
-    if (!(sigma_color >= 0.0f)) return fail(ADF_EBADARG, "sigma_color must be >= 0 (FGS.cpp:143)");
-    lut_build_host(sigma_color, table);
-    return ADF_OK;
-}
-
-namespace adf {
-hipError_t device_malloc(void** p, size_t bytes)
-{
-    hipError_t e = hipMalloc(p, bytes);
-    if (e == hipErrorOutOfMemory) {
-        (void)hipGetLastError();
-        BlockCache::get().clear();                                   // the cache may be what fills the memory
-        e = hipMalloc(p, bytes);
-    }
-    if (e != hipSuccess) *p = nullptr;
-    return e;
-}
-
-void* cache_take(int device, size_t need, hipStream_t st, size_t* bytes) { return BlockCache::get().take(device, need, st, bytes); }
-
-void cache_give(int device, void* p, size_t bytes, hipStream_t st)
-{
-    hipEvent_t ev = nullptr;
-    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess || hipEventRecord(ev, st) != hipSuccess) {
-        (void)hipGetLastError();                                     // no event: hand the block back idle
-        if (ev) hipEventDestroy(ev);
-        ev = nullptr;
-        hipStreamSynchronize(st);
-    }
-    BlockCache::get().give(device, p, bytes, ev);
-}
-} // namespace adf
-
-extern "C" void adf_release_cached_memory(void)
-{
-    BlockCache::get().clear();
-    LutStore::get().clear();
-}
-
 extern "C" int adf_fgs_get_device(const adf_fgs_t* f, int* device) { NEED_HANDLE(f); if (device) *device = f->device; return ADF_OK; }
 extern "C" int adf_fgs_get_solver(const adf_fgs_t* f, int* solver) { NEED_HANDLE(f); if (solver) *solver = f->solver; return ADF_OK; }
 
@@ -1367,7 +1048,7 @@ extern "C" void adf_fgs_destroy(adf_fgs_t* f)
     DeviceScope ds(f->device);
     if (f->block) {
         if (f->busy && !f->in_capture) {
-            BlockCache::get().give(f->device, f->block, f->block_bytes, f->busy);    // (the event goes with the block)
+            cache_give_event(f->device, f->block, f->block_bytes, f->busy);    // (the event goes with the block)
             f->busy = nullptr;
         } else {
             hipDeviceSynchronize();

@@ -1,0 +1,90 @@
+// adf_host.h -- the host toolkit every C-ABI source shares (adf_host.hip): error returns, the device scope, device
+// memory (growable buffers, the process-wide block cache, scratch taken from it), the weight tables and the image
+// copies of the host-pointer entry points.  Host code only; what kernels and host code share is adf_internal.h.
+#pragma once
+
+#include "adf_internal.h"
+#include "../../include/adf_wls.h"
+
+#include <memory>
+#include <vector>
+
+namespace adf {
+
+// Records the calling thread's last error message (adf_last_error), printf-style, and returns `code`.
+int fail(int code, const char* fmt, ...);
+
+#define HIP_TRY(expr)                                                                              \
+    do {                                                                                           \
+        hipError_t e_ = (expr);                                                                    \
+        if (e_ != hipSuccess)                                                                      \
+            return adf::fail(e_ == hipErrorOutOfMemory ? ADF_ENOMEM : ADF_EHIP, "%s failed: %s",   \
+                             #expr, hipGetErrorString(e_));                                        \
+    } while (0)
+#define NEED_HANDLE(h) do { if (!(h)) return adf::fail(ADF_EBADARG, "%s: handle is NULL", __func__); } while (0)
+
+// RAII: run on the handle's device, restore the caller's on exit.
+struct DeviceScope {
+    int prev = -1; bool switched = false;
+    explicit DeviceScope(int dev)
+    {
+        if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = hipSetDevice(dev) == hipSuccess;
+    }
+    ~DeviceScope() { if (switched) hipSetDevice(prev); }
+};
+
+bool stream_is_capturing(hipStream_t st);
+
+// Growable device buffer (never shrinks; freed with the handle).  Growing drains `st` before the old block is freed.
+// FILL_ZERO clears a newly allocated block on `st` (the filters: the sweeps read, and discard, pitch padding);
+// FILL_NONE leaves it as the driver gave it (the matchers' workspaces: gigabytes that are written before they are read).
+enum Fill { FILL_NONE, FILL_ZERO };
+struct DevBuf {
+    void* p = nullptr; size_t bytes = 0;
+    int reserve(size_t need, hipStream_t st, Fill fill);
+    void release() { if (p) hipFree(p); p = nullptr; bytes = 0; }
+};
+
+// hipMalloc that, when the driver refuses, first hands the library's own cache of device blocks (below, up to 3 GB)
+// back to the driver and tries once more: no call may fail for want of memory the library itself is sitting on.
+hipError_t device_malloc(void** p, size_t bytes);
+// The process-wide cache of device blocks (adf_host.hip: BlockCache).  take: a cached block of at least `need` bytes
+// on `device`, ordered into `st` behind its last user, or null.  give: after queueing the work that uses the block --
+// `ready` (may be null: idle), or an event recorded on `st`, goes with it, so nobody synchronises the host.
+void* cache_take(int device, size_t need, hipStream_t st, size_t* bytes);
+void cache_give(int device, void* p, size_t bytes, hipStream_t st);
+void cache_give_event(int device, void* p, size_t bytes, hipEvent_t ready);
+
+// Library scratch of one call on the current device: a block of the cache, else a fresh allocation, ordered into `st`;
+// it goes back to the cache behind `st` when the scope ends -- on an error return too.
+struct Scratch {
+    int device = 0; void* p = nullptr; size_t bytes = 0; hipStream_t st = nullptr;
+    Scratch() = default;
+    Scratch(const Scratch&) = delete;
+    Scratch& operator=(const Scratch&) = delete;
+    int take(size_t need, hipStream_t stream);
+    ~Scratch() { if (p) cache_give(device, p, bytes, st); }
+};
+
+// The weight tables of one handle (FGS.cpp:150-154, 663-675): up to LUT_CACHE sigmas, each an immutable device table
+// shared with every handle of the process on the same device (adf_host.hip: LutStore).
+struct LutTable;
+struct Lut {
+    static constexpr int LUT_CACHE = 8;
+    struct Entry { std::shared_ptr<LutTable> t; unsigned long long used; };
+    std::vector<Entry> tables;
+    const float* cur = nullptr;
+    unsigned long long tick = 0;
+    size_t bytes() const { return tables.size() * sizeof(float) * ADF_LUT_LEVELS; }
+    int ensure(float s, hipStream_t st);
+    // (the caller has made sure no kernel still reads the tables: handle destruction synchronises first)
+    void release() { tables.clear(); cur = nullptr; }
+};
+
+// The host-pointer entry points' copies: `n` images of `rows` rows of `row_bytes`, image k at `k * image_stride` bytes
+// with rows `pitch` bytes apart on either side, asynchronously on `st` (a host destination is complete once `st` has
+// been synchronised).  The layout of a staging block stays with the caller.
+int copy_images(void* dst, size_t dst_pitch, ptrdiff_t dst_image_stride, const void* src, size_t src_pitch,
+                ptrdiff_t src_image_stride, size_t row_bytes, size_t rows, int n, hipMemcpyKind kind, hipStream_t st);
+
+} // namespace adf

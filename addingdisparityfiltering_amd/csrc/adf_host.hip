@@ -1,0 +1,297 @@
+// adf_host.hip -- the host toolkit of adf_host.h: no kernel lives here.
+#include "adf_host.h"
+
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <mutex>
+#include <thread>
+
+using namespace adf;
+
+// ----------------------------------------------------------------------------------------------
+// error plumbing
+// ----------------------------------------------------------------------------------------------
+static thread_local char g_err[512] = "";
+
+int adf::fail(int code, const char* fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(g_err, sizeof(g_err), fmt, ap);
+    va_end(ap);
+    return code;
+}
+
+extern "C" int adf_version(void) { return ADF_VERSION; }
+extern "C" const char* adf_last_error(void) { return g_err; }
+extern "C" int adf_device_count(void)
+{
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
+    return n;
+}
+
+extern "C" int adf_device_pci_bus_id(int device, char* buf, int len)
+{
+    if (!buf || len < 16) return fail(ADF_EBADARG, "adf_device_pci_bus_id: buffer of at least 16 bytes required");
+    buf[0] = 0;
+    HIP_TRY(hipDeviceGetPCIBusId(buf, len, device));
+    return ADF_OK;
+}
+
+bool adf::stream_is_capturing(hipStream_t st)
+{
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); return false; }
+    return cs != hipStreamCaptureStatusNone;
+}
+
+int adf::DevBuf::reserve(size_t need, hipStream_t st, Fill fill)
+{
+    if (need <= bytes) return ADF_OK;
+    if (p) { HIP_TRY(hipStreamSynchronize(st)); HIP_TRY(hipFree(p)); p = nullptr; bytes = 0; }
+    need = (need + 255) / 256 * 256;
+    HIP_TRY(device_malloc(&p, need));
+    bytes = need;
+    if (fill == FILL_ZERO) HIP_TRY(hipMemsetAsync(p, 0, need, st));
+    return ADF_OK;
+}
+
+// Weight LUTs (FGS.cpp:150-154, 663-675), built on the host with libm, one immutable device table per sigma seen
+// (up to LUT_CACHE of them per handle).  Round 3: a table is never rewritten, so coming back to a sigma used before --
+// the common way callers vary it -- is a pointer switch with no device work and no synchronisation (capturable into a
+// hipGraph), and a NEW sigma no longer drains the stream: its table goes into a fresh buffer no kernel in flight can be
+// reading.  Only that first upload is a synchronous copy; a caller that captures filter calls must have used every
+// sigma it switches between once before the capture (include/adf_wls.h).
+//
+// Tables are shared by every handle of the process on the same device (LutStore): the one-shot function
+// fastGlobalSmootherFilter (EF.hpp:413) and the reference's own perf test (perf_fgs_filter.cpp:70-76) create a filter
+// per call, and 3*256*256 libm calls cost ~1 ms on one core -- ten times the 720p filter call itself.  A table seen
+// before is a look-up; a new one is built by a few threads (each entry is the same scalar libm expression as before:
+// same bits).
+struct adf::LutTable {
+    int device = 0; float sigma = 0; float* dev = nullptr;
+    LutTable() = default;
+    LutTable(const LutTable&) = delete;
+    LutTable& operator=(const LutTable&) = delete;
+    ~LutTable() { if (dev) { DeviceScope ds(device); hipFree(dev); } }
+};
+
+struct LutStore {
+    static constexpr size_t CAP = 16;
+    std::mutex m;
+    std::vector<std::shared_ptr<LutTable>> tables;               // most recently used last
+    static LutStore& get() { static LutStore* s = new LutStore; return *s; }   // (never destroyed: no HIP calls at exit)
+    std::shared_ptr<LutTable> find(int device, float sigma)
+    {
+        std::lock_guard<std::mutex> lk(m);
+        for (size_t k = 0; k < tables.size(); k++)
+            if (tables[k]->device == device && tables[k]->sigma == sigma) {
+                auto t = tables[k];
+                tables.erase(tables.begin() + (ptrdiff_t)k); tables.push_back(t);
+                return t;
+            }
+        return nullptr;
+    }
+    void add(const std::shared_ptr<LutTable>& t)
+    {
+        std::lock_guard<std::mutex> lk(m);
+        // (a table dropped here lives on while a handle still refers to it; with no handle left nothing can be reading it)
+        if (tables.size() >= CAP) tables.erase(tables.begin());
+        tables.push_back(t);
+    }
+    void clear() { std::lock_guard<std::mutex> lk(m); tables.clear(); }
+};
+
+static void lut_build_host(float s, float* host)
+{
+    auto span = [&](int a, int b) { for (int i = a; i < b; i++) host[i] = -expf(-sqrtf((float)i) / s); };
+    // Where the argument is at or below -110 the float exponential is +0 -- exp(-110) = 1.7e-48 lies 400 times below half
+    // the smallest denormal, so every libm returns zero there, and the entry is -0.0f.  With the filter's usual sigma
+    // (1..2) that is nine tenths of the table: those entries are stored, not computed.  The argument falls
+    // monotonically with i (sqrtf and the division are monotone), so the first such index bounds the computed part.
+    int n = ADF_LUT_LEVELS;
+    if (s > 0.0f) {
+        const double lim = 110.0 * (double)s;
+        if (lim * lim * 1.001 + 2.0 < (double)ADF_LUT_LEVELS) {
+            int i0 = (int)(lim * lim * 1.001) + 2;
+            while (i0 < ADF_LUT_LEVELS && !(-sqrtf((float)i0) / s <= -110.0f)) i0++;   // (a check, not a search: the margin covers it)
+            n = i0;
+        }
+    }
+    for (int i = n; i < ADF_LUT_LEVELS; i++) host[i] = -0.0f;
+    unsigned hw = std::thread::hardware_concurrency();
+    int nt = (int)(hw >= 16 ? 8 : hw >= 4 ? hw / 2 : 1);
+    if (n < 32768) nt = 1;                                        // a thread costs more to start than such a share to compute
+    if (nt <= 1) { span(0, n); return; }
+    std::vector<std::thread> th;
+    const int per = (n + nt - 1) / nt;
+    bool ok = true;
+    int done = std::min(per, n);                                  // the caller's own share is [0, per)
+    for (int t = 1; t < nt && ok; t++) {
+        const int a = t * per, b = std::min(n, a + per);
+        if (a >= b) break;
+        try { th.emplace_back(span, a, b); done = b; } catch (...) { ok = false; }
+    }
+    span(0, std::min(per, n));
+    for (auto& t : th) t.join();
+    if (done < n) span(done, n);                                  // threads that could not be started
+}
+
+int adf::Lut::ensure(float s, hipStream_t st)
+{
+    for (auto& e : tables)
+        if (e.t->sigma == s) { e.used = ++tick; cur = e.t->dev; return ADF_OK; }
+    if ((int)tables.size() >= LUT_CACHE) {                 // drop the least recently used table: kernels of
+        size_t lru = 0;                                    // earlier calls on `st` may still read it
+        for (size_t k = 1; k < tables.size(); k++) if (tables[k].used < tables[lru].used) lru = k;
+        HIP_TRY(hipStreamSynchronize(st));
+        tables.erase(tables.begin() + (ptrdiff_t)lru);
+    }
+    int device = 0;
+    HIP_TRY(hipGetDevice(&device));
+    std::shared_ptr<LutTable> t = LutStore::get().find(device, s);
+    if (!t) {
+        std::vector<float> host(ADF_LUT_LEVELS);
+        lut_build_host(s, host.data());
+        float* d = nullptr;
+        HIP_TRY(hipMalloc(&d, sizeof(float) * ADF_LUT_LEVELS));
+        hipError_t e = hipMemcpy(d, host.data(), sizeof(float) * ADF_LUT_LEVELS, hipMemcpyHostToDevice);
+        if (e != hipSuccess) { hipFree(d); return fail(ADF_EHIP, "LUT upload failed: %s", hipGetErrorString(e)); }
+        t = std::make_shared<LutTable>();
+        t->device = device; t->sigma = s; t->dev = d;
+        LutStore::get().add(t);
+    }
+    tables.push_back(Entry{t, ++tick});
+    cur = t->dev;
+    return ADF_OK;
+}
+
+// Device blocks of short-lived handles (adf_fgs: the planes and the staged image of ONE image), kept for the next
+// handle instead of going back to the driver: hipMalloc + hipFree of a 4K handle's 300 MB cost more than its filter
+// call, and hipFree waits for the whole device.  A block comes back with the event behind its last user; whoever takes
+// it makes its own stream wait for that event first, so nobody synchronises the host.
+struct BlockCache {
+    struct Ent { int device; void* p; size_t bytes; hipEvent_t ready; };
+    static constexpr size_t CAP_BYTES = (size_t)3 << 30;
+    static constexpr size_t CAP_ENTRIES = 8;
+    std::mutex m;
+    std::vector<Ent> ents;                                         // oldest first
+    size_t total = 0;
+    static BlockCache& get() { static BlockCache* c = new BlockCache; return *c; }
+    static void drop(const Ent& e)
+    {
+        DeviceScope ds(e.device);
+        if (e.ready) { hipEventSynchronize(e.ready); hipEventDestroy(e.ready); }
+        hipFree(e.p);
+    }
+    // a cached block of at least `need` bytes (and not wastefully larger), ordered into `st`; null if there is none
+    void* take(int device, size_t need, hipStream_t st, size_t* bytes)
+    {
+        Ent hit{};
+        {
+            std::lock_guard<std::mutex> lk(m);
+            size_t best = ents.size();
+            for (size_t k = 0; k < ents.size(); k++)
+                if (ents[k].device == device && ents[k].bytes >= need && ents[k].bytes <= need + need / 4 + ((size_t)1 << 20) &&
+                    (best == ents.size() || ents[k].bytes < ents[best].bytes))
+                    best = k;
+            if (best == ents.size()) return nullptr;
+            hit = ents[best];
+            ents.erase(ents.begin() + (ptrdiff_t)best);
+            total -= hit.bytes;
+        }
+        if (hit.ready) {
+            const hipError_t e = hipStreamWaitEvent(st, hit.ready, 0);
+            if (e != hipSuccess) hipEventSynchronize(hit.ready);
+            hipEventDestroy(hit.ready);
+        }
+        *bytes = hit.bytes;
+        return hit.p;
+    }
+    void give(int device, void* p, size_t bytes, hipEvent_t ready)
+    {
+        std::vector<Ent> out;
+        {
+            std::lock_guard<std::mutex> lk(m);
+            ents.push_back(Ent{device, p, bytes, ready});
+            total += bytes;
+            while (!ents.empty() && (total > CAP_BYTES || ents.size() > CAP_ENTRIES)) {
+                out.push_back(ents.front());
+                total -= ents.front().bytes;
+                ents.erase(ents.begin());
+            }
+        }
+        for (auto& e : out) drop(e);
+    }
+    void clear()
+    {
+        std::vector<Ent> out;
+        { std::lock_guard<std::mutex> lk(m); out.swap(ents); total = 0; }
+        for (auto& e : out) drop(e);
+    }
+};
+
+extern "C" int adf_weight_table_host(float sigma_color, float* table, int levels)
+{
+    if (!table || levels != ADF_LUT_LEVELS) return fail(ADF_EBADARG, "table must hold %d floats", ADF_LUT_LEVELS);
+    if (!(sigma_color >= 0.0f)) return fail(ADF_EBADARG, "sigma_color must be >= 0 (FGS.cpp:143)");
+    lut_build_host(sigma_color, table);
+    return ADF_OK;
+}
+
+namespace adf {
+hipError_t device_malloc(void** p, size_t bytes)
+{
+    hipError_t e = hipMalloc(p, bytes);
+    if (e == hipErrorOutOfMemory) {
+        (void)hipGetLastError();
+        BlockCache::get().clear();                                   // the cache may be what fills the memory
+        e = hipMalloc(p, bytes);
+    }
+    if (e != hipSuccess) *p = nullptr;
+    return e;
+}
+
+void* cache_take(int device, size_t need, hipStream_t st, size_t* bytes) { return BlockCache::get().take(device, need, st, bytes); }
+
+void cache_give(int device, void* p, size_t bytes, hipStream_t st)
+{
+    hipEvent_t ev = nullptr;
+    if (hipEventCreateWithFlags(&ev, hipEventDisableTiming) != hipSuccess || hipEventRecord(ev, st) != hipSuccess) {
+        (void)hipGetLastError();                                     // no event: hand the block back idle
+        if (ev) hipEventDestroy(ev);
+        ev = nullptr;
+        hipStreamSynchronize(st);
+    }
+    BlockCache::get().give(device, p, bytes, ev);
+}
+
+void cache_give_event(int device, void* p, size_t bytes, hipEvent_t ready) { BlockCache::get().give(device, p, bytes, ready); }
+
+int Scratch::take(size_t need, hipStream_t stream)
+{
+    if (hipGetDevice(&device) != hipSuccess) return fail(ADF_ENODEV, "no HIP device");
+    st = stream;
+    if ((p = cache_take(device, need, st, &bytes))) return ADF_OK;
+    HIP_TRY(device_malloc(&p, need));
+    bytes = need;
+    return ADF_OK;
+}
+
+int copy_images(void* dst, size_t dst_pitch, ptrdiff_t dst_image_stride, const void* src, size_t src_pitch,
+                ptrdiff_t src_image_stride, size_t row_bytes, size_t rows, int n, hipMemcpyKind kind, hipStream_t st)
+{
+    for (int k = 0; k < n; k++)
+        HIP_TRY(hipMemcpy2DAsync((char*)dst + k * dst_image_stride, dst_pitch, (const char*)src + k * src_image_stride, src_pitch,
+                                 row_bytes, rows, kind, st));
+    return ADF_OK;
+}
+} // namespace adf
+
+extern "C" void adf_release_cached_memory(void)
+{
+    BlockCache::get().clear();
+    LutStore::get().clear();
+}

@@ -1,4 +1,4 @@
-// adf_internal.h -- shared declarations between the HIP kernels and the C-ABI host code.
+// adf_internal.h -- shared declarations between the HIP kernels and the C-ABI host code (whose own toolkit is adf_host.h).
 // Not installed; the public boundary is include/adf_wls.h.
 #pragma once
 
@@ -183,18 +183,6 @@ struct WavePassArgs {
 // the kernels' argument layout (grouping the fused inputs moved no member)
 static_assert(sizeof(WavePassArgs) == 280 && offsetof(WavePassArgs, out) == 208 && offsetof(WavePassArgs, nscan) == 248 &&
               offsetof(WavePassArgs, plane) == 264 && offsetof(WavePassArgs, lambda) == 272, "WavePassArgs layout");
-
-// Records the calling thread's last error message (adf_last_error) and returns `code`.
-int set_error(int code, const char* msg);
-// hipMalloc that, when the driver refuses, first hands the library's own cache of destroyed filters' device blocks
-// (up to 3 GB, adf_api.hip: BlockCache) back to the driver and tries once more: no call may fail for want of memory
-// the library itself is sitting on.
-hipError_t device_malloc(void** p, size_t bytes);
-// Library-supplied scratch from the same cache (adf_api.hip: BlockCache): a cached block of at least `need` bytes on
-// `device`, ordered into `st` behind its last user, or null (then device_malloc one); give it back after queueing the
-// work that uses it -- the event recorded on `st` goes with the block, so nobody synchronises the host.
-void* cache_take(int device, size_t need, hipStream_t st, size_t* bytes);
-void cache_give(int device, void* p, size_t bytes, hipStream_t st);
 
 // Launchers (defined in the .hip files).  All are asynchronous on `st`.
 hipError_t launch_discontinuity(const DiscArgs& a, int n_pairs, hipStream_t st);

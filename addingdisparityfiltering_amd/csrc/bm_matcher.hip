@@ -26,10 +26,11 @@
 // is decided once at the end.  Nothing but the int16 result is written.
 // The kernel is bound by integer VALU issue (about 11 instructions per pixel and disparity; EXPERIMENTS.md section 10), not
 // by HBM: the views are read through L1/L2 once per disparity, HBM sees them once.
-#include "adf_internal.h"
-#include "../../include/adf_wls.h"
+#include "adf_host.h"
 
 #include <new>
+
+using namespace adf;
 
 namespace {
 
@@ -393,37 +394,18 @@ struct adf_bm {
     int device = 0;
     int min_disp = 0, num_disp = 0, block = 21;
     int cap = 31, texthr = 10, uniq = 15;       // cv::StereoBM's defaults
-    void* views = nullptr; size_t views_bytes = 0;   // prefiltered left + right views of the batch
-    void* stage = nullptr; size_t stage_bytes = 0;   // host-pointer entry: device copies of the I/O
+    DevBuf views;   // prefiltered left + right views of the batch
+    DevBuf stage;   // host-pointer entry: device copies of the I/O
 };
-
-namespace {
-int bm_fail(int code, const char* msg) { return adf::set_error(code, msg); }
-int reserve(void** p, size_t* have, size_t need, hipStream_t st)
-{
-    if (need <= *have) return ADF_OK;
-    if (*p) { if (hipStreamSynchronize(st) != hipSuccess) return bm_fail(ADF_EHIP, "hipStreamSynchronize failed"); hipFree(*p); *p = nullptr; *have = 0; }
-    need = (need + 255) / 256 * 256;
-    hipError_t e = adf::device_malloc(p, need);   // (gives the filter cache's blocks back first if it must)
-    if (e != hipSuccess) { *p = nullptr; return bm_fail(e == hipErrorOutOfMemory ? ADF_ENOMEM : ADF_EHIP, "hipMalloc failed for the matcher workspace"); }
-    *have = need;
-    return ADF_OK;
-}
-struct DevScope {
-    int prev = -1; bool sw = false;
-    explicit DevScope(int d) { if (hipGetDevice(&prev) == hipSuccess && prev != d) sw = hipSetDevice(d) == hipSuccess; }
-    ~DevScope() { if (sw) hipSetDevice(prev); }
-};
-} // namespace
 
 extern "C" int adf_bm_create(adf_bm_t** out, int num_disparities, int block_size)
 {
-    if (!out) return bm_fail(ADF_EBADARG, "out is NULL");
+    if (!out) return fail(ADF_EBADARG, "out is NULL");
     *out = nullptr;
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return bm_fail(ADF_ENODEV, "no HIP device");
+    if (hipGetDevice(&dev) != hipSuccess) return fail(ADF_ENODEV, "no HIP device");
     adf_bm* h = new (std::nothrow) adf_bm;
-    if (!h) return bm_fail(ADF_ENOMEM, "out of host memory");
+    if (!h) return fail(ADF_ENOMEM, "out of host memory");
     h->device = dev; h->num_disp = num_disparities; h->block = block_size;
     *out = h;
     return ADF_OK;
@@ -432,16 +414,16 @@ extern "C" int adf_bm_create(adf_bm_t** out, int num_disparities, int block_size
 extern "C" void adf_bm_destroy(adf_bm_t* h)
 {
     if (!h) return;
-    DevScope ds(h->device);
-    if (h->views) hipFree(h->views);
-    if (h->stage) hipFree(h->stage);
+    DeviceScope ds(h->device);
+    h->views.release();
+    h->stage.release();
     delete h;
 }
 
 extern "C" int adf_bm_set_params(adf_bm_t* h, int min_disparity, int num_disparities, int block_size,
                                  int prefilter_cap, int texture_threshold, int uniqueness_ratio)
 {
-    if (!h) return bm_fail(ADF_EBADARG, "handle is NULL");
+    if (!h) return fail(ADF_EBADARG, "handle is NULL");
     h->min_disp = min_disparity; h->num_disp = num_disparities; h->block = block_size;
     h->cap = prefilter_cap; h->texthr = texture_threshold; h->uniq = uniqueness_ratio;
     return ADF_OK;
@@ -449,7 +431,7 @@ extern "C" int adf_bm_set_params(adf_bm_t* h, int min_disparity, int num_dispari
 
 extern "C" int adf_bm_get_device(const adf_bm_t* h, int* device)
 {
-    if (!h) return bm_fail(ADF_EBADARG, "handle is NULL");
+    if (!h) return fail(ADF_EBADARG, "handle is NULL");
     if (device) *device = h->device;
     return ADF_OK;
 }
@@ -457,7 +439,7 @@ extern "C" int adf_bm_get_device(const adf_bm_t* h, int* device)
 extern "C" int adf_bm_get_params(const adf_bm_t* h, int* min_disparity, int* num_disparities, int* block_size,
                                  int* prefilter_cap, int* texture_threshold, int* uniqueness_ratio)
 {
-    if (!h) return bm_fail(ADF_EBADARG, "handle is NULL");
+    if (!h) return fail(ADF_EBADARG, "handle is NULL");
     if (min_disparity) *min_disparity = h->min_disp;
     if (num_disparities) *num_disparities = h->num_disp;
     if (block_size) *block_size = h->block;
@@ -470,18 +452,18 @@ extern "C" int adf_bm_get_params(const adf_bm_t* h, int* min_disparity, int* num
 static int bm_check(const adf_bm* h, int n, const void* l, const void* r, const void* d, int W, int H,
                     ptrdiff_t ls, ptrdiff_t rs, ptrdiff_t dstr)
 {
-    if (!h) return bm_fail(ADF_EBADARG, "handle is NULL");
-    if (n <= 0 || !l || !r || !d) return bm_fail(ADF_EBADARG, "views and disparity must be non-NULL, n_pairs positive");
-    if (W <= 0 || H <= 0 || ls < W || rs < W || dstr < (ptrdiff_t)W * 2) return bm_fail(ADF_ESIZE, "bad size or stride");
-    if ((dstr & 1) || (reinterpret_cast<uintptr_t>(d) & 1)) return bm_fail(ADF_ESIZE, "disparity rows must be 2-byte aligned");
+    if (!h) return fail(ADF_EBADARG, "handle is NULL");
+    if (n <= 0 || !l || !r || !d) return fail(ADF_EBADARG, "views and disparity must be non-NULL, n_pairs positive");
+    if (W <= 0 || H <= 0 || ls < W || rs < W || dstr < (ptrdiff_t)W * 2) return fail(ADF_ESIZE, "bad size or stride");
+    if ((dstr & 1) || (reinterpret_cast<uintptr_t>(d) & 1)) return fail(ADF_ESIZE, "disparity rows must be 2-byte aligned");
     // the checks cv::StereoBM::compute makes on its parameters; the window is limited to 21 so that a
     // window sum fits 16 bits
-    if (h->num_disp <= 0 || h->num_disp % 16) return bm_fail(ADF_EBADARG, "numDisparities must be positive and divisible by 16");
-    if (h->block < 5 || h->block > 21 || h->block % 2 == 0) return bm_fail(ADF_EBADARG, "blockSize must be odd and within 5..21");
-    if (h->block >= (W < H ? W : H)) return bm_fail(ADF_EBADARG, "blockSize must be smaller than the image");
-    if (h->cap < 1 || h->cap > 63) return bm_fail(ADF_EBADARG, "preFilterCap must be within 1..63");
-    if (h->texthr < 0 || h->uniq < 0) return bm_fail(ADF_EBADARG, "textureThreshold and uniquenessRatio must be non-negative");
-    if (h->min_disp < -32768 || h->min_disp + h->num_disp > 2047) return bm_fail(ADF_EBADARG, "disparity range does not fit CV_16S with 4 fractional bits");
+    if (h->num_disp <= 0 || h->num_disp % 16) return fail(ADF_EBADARG, "numDisparities must be positive and divisible by 16");
+    if (h->block < 5 || h->block > 21 || h->block % 2 == 0) return fail(ADF_EBADARG, "blockSize must be odd and within 5..21");
+    if (h->block >= (W < H ? W : H)) return fail(ADF_EBADARG, "blockSize must be smaller than the image");
+    if (h->cap < 1 || h->cap > 63) return fail(ADF_EBADARG, "preFilterCap must be within 1..63");
+    if (h->texthr < 0 || h->uniq < 0) return fail(ADF_EBADARG, "textureThreshold and uniquenessRatio must be non-negative");
+    if (h->min_disp < -32768 || h->min_disp + h->num_disp > 2047) return fail(ADF_EBADARG, "disparity range does not fit CV_16S with 4 fractional bits");
     return ADF_OK;
 }
 
@@ -497,22 +479,22 @@ static int bm_compute_impl(adf_bm_t* h, int n_pairs,
 {
     int rc = bm_check(h, n_pairs, left, right, disp_left, W, H, left_stride, right_stride, dl_stride);
     if (rc) return rc;
-    if (n_pairs > 1 && (dl_pair_stride & 1)) return bm_fail(ADF_ESIZE, "disparity maps must be 2-byte aligned");
+    if (n_pairs > 1 && (dl_pair_stride & 1)) return fail(ADF_ESIZE, "disparity maps must be 2-byte aligned");
     const int nviews = disp_right ? 2 : 1;
     if (disp_right) {
         if (dr_stride < (ptrdiff_t)W * 2 || (dr_stride & 1) || (reinterpret_cast<uintptr_t>(disp_right) & 1) ||
             (n_pairs > 1 && (dr_pair_stride & 1)))
-            return bm_fail(ADF_ESIZE, "bad stride or alignment of the right disparity map");
+            return fail(ADF_ESIZE, "bad stride or alignment of the right disparity map");
         if (h->min_disp + h->num_disp - 1 > 32767 || -(h->min_disp + h->num_disp) + 1 < -32768)
-            return bm_fail(ADF_EBADARG, "disparity range of the right-view matcher does not fit");
+            return fail(ADF_EBADARG, "disparity range of the right-view matcher does not fit");
     }
-    DevScope ds(h->device);
+    DeviceScope ds(h->device);
     const int HG = (H + 3) / 4, HGP = HG + 2 * PG;
     const int Wp = (W + XPAD + 3) / 4 * 4;                     // padded row: lanes past the image read (and discard) it
     const size_t view = (size_t)HGP * Wp;                      // dwords per prefiltered view
-    rc = reserve(&h->views, &h->views_bytes, 2 * view * (size_t)n_pairs * sizeof(uint32_t), st);
+    rc = h->views.reserve(2 * view * (size_t)n_pairs * sizeof(uint32_t), st, FILL_NONE);
     if (rc) return rc;
-    uint32_t* Lt = (uint32_t*)h->views;
+    uint32_t* Lt = (uint32_t*)h->views.p;
     uint32_t* Rt = Lt + view * (size_t)n_pairs;
 
     PrefilterArgs p;
@@ -545,10 +527,10 @@ static int bm_compute_impl(adf_bm_t* h, int n_pairs,
     if (a.v[0].xe > a.v[0].xs || (nviews == 2 && a.v[1].xe > a.v[1].xs)) {
         hipError_t e = h->uniq > 0 ? launch_match<true>(a, w2, dim3(256), n_pairs, st)
                                    : launch_match<false>(a, w2, dim3(256), n_pairs, st);
-        if (e != hipSuccess) return bm_fail(ADF_EHIP, hipGetErrorString(e));
+        if (e != hipSuccess) return fail(ADF_EHIP, "%s", hipGetErrorString(e));
     }
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return bm_fail(ADF_EHIP, hipGetErrorString(e));
+    if (e != hipSuccess) return fail(ADF_EHIP, "%s", hipGetErrorString(e));
     return ADF_OK;
 }
 
@@ -571,7 +553,7 @@ extern "C" int adf_bm_compute_both_device(adf_bm_t* h, int n_pairs,
                                           int16_t* disp_right, ptrdiff_t disp_right_stride, ptrdiff_t disp_right_pair_stride,
                                           void* stream)
 {
-    if (!disp_right) return bm_fail(ADF_EBADARG, "disp_right is NULL");
+    if (!disp_right) return fail(ADF_EBADARG, "disp_right is NULL");
     return bm_compute_impl(h, n_pairs, left, left_stride, left_pair_stride, right, right_stride, right_pair_stride, W, H,
                            disp_left, disp_left_stride, disp_left_pair_stride,
                            disp_right, disp_right_stride, disp_right_pair_stride, (hipStream_t)stream);
@@ -585,24 +567,19 @@ extern "C" int adf_bm_compute_host(adf_bm_t* h, int n_pairs,
 {
     int rc = bm_check(h, n_pairs, left, right, disparity, W, H, left_stride, right_stride, disp_stride);
     if (rc) return rc;
-    DevScope ds(h->device);
+    DeviceScope ds(h->device);
     const size_t vbytes = (size_t)W * H, dbytes = (size_t)W * H * 2;
-    rc = reserve(&h->stage, &h->stage_bytes, (2 * vbytes + dbytes) * (size_t)n_pairs, nullptr);
+    rc = h->stage.reserve((2 * vbytes + dbytes) * (size_t)n_pairs, nullptr, FILL_NONE);
     if (rc) return rc;
-    uint8_t* dl = (uint8_t*)h->stage;
+    uint8_t* dl = (uint8_t*)h->stage.p;
     uint8_t* dr = dl + vbytes * n_pairs;
     int16_t* dd = (int16_t*)(dr + vbytes * n_pairs);
-    for (int i = 0; i < n_pairs; i++) {
-        if (hipMemcpy2D(dl + vbytes * i, W, left + (ptrdiff_t)i * left_pair_stride, left_stride, W, H, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy2D(dr + vbytes * i, W, right + (ptrdiff_t)i * right_pair_stride, right_stride, W, H, hipMemcpyHostToDevice) != hipSuccess)
-            return bm_fail(ADF_EHIP, "copying the views to the device failed");
-    }
+    if ((rc = copy_images(dl, W, vbytes, left, left_stride, left_pair_stride, W, H, n_pairs, hipMemcpyHostToDevice, nullptr))) return rc;
+    if ((rc = copy_images(dr, W, vbytes, right, right_stride, right_pair_stride, W, H, n_pairs, hipMemcpyHostToDevice, nullptr))) return rc;
     rc = adf_bm_compute_device(h, n_pairs, dl, W, (ptrdiff_t)vbytes, dr, W, (ptrdiff_t)vbytes, W, H, dd, (ptrdiff_t)W * 2, (ptrdiff_t)dbytes, nullptr);
     if (rc) return rc;
-    if (hipStreamSynchronize(nullptr) != hipSuccess) return bm_fail(ADF_EHIP, "the matcher kernels failed");
-    for (int i = 0; i < n_pairs; i++)
-        if (hipMemcpy2D(reinterpret_cast<char*>(disparity) + (ptrdiff_t)i * disp_pair_stride, disp_stride, dd + (size_t)W * H * i, (size_t)W * 2,
-                        (size_t)W * 2, H, hipMemcpyDeviceToHost) != hipSuccess)
-            return bm_fail(ADF_EHIP, "copying the disparity map back failed");
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    if ((rc = copy_images(disparity, disp_stride, disp_pair_stride, dd, (size_t)W * 2, dbytes, (size_t)W * 2, H, n_pairs, hipMemcpyDeviceToHost, nullptr))) return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
     return ADF_OK;
 }

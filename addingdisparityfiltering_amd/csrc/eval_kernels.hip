@@ -2,10 +2,11 @@
 // pipeline whose maps live in HBM can score them without a round trip:
 //   computeMSE (DF.cpp:497-517), computeBadPixelPercent (:519-539), getDisparityVis (:541-556).
 // The reductions are exact 64-bit integer sums (order-independent, bit-reproducible).
-#include "adf_internal.h"
-#include "../../include/adf_wls.h"
+#include "adf_host.h"
 
 #include <cstdio>
+
+using namespace adf;
 
 namespace {
 
@@ -58,24 +59,23 @@ __global__ void __launch_bounds__(256) vis_kernel(const int16_t* src, ptrdiff_t 
 int run_eval(const int16_t* gt, ptrdiff_t sg, const int16_t* src, ptrdiff_t ss, int W, int H, const adf_rect* roi,
              int thresh, bool device, hipStream_t st, unsigned long long out[3])
 {
-    if (!gt || !src || W <= 0 || H <= 0) return adf::set_error(ADF_EBADARG, "GT / src must be non-empty CV_16SC1 maps"); // DF.cpp:499-501
+    if (!gt || !src || W <= 0 || H <= 0) return fail(ADF_EBADARG, "GT / src must be non-empty CV_16SC1 maps"); // DF.cpp:499-501
     adf_rect r = roi && roi->width * roi->height != 0 ? *roi : adf_rect{0, 0, W, H};
     if (r.x < 0 || r.y < 0 || r.width <= 0 || r.height <= 0 || r.x + r.width > W || r.y + r.height > H)
-        return adf::set_error(ADF_ESIZE, "ROI does not fit the maps");
+        return fail(ADF_ESIZE, "ROI does not fit the maps");
     const int16_t *dg = gt, *ds = src;
     ptrdiff_t dsg = sg, dss = ss;
     void* tmp = nullptr;
     if (!device) {
         const size_t rowb = (size_t)W * 2;
-        if (hipMalloc(&tmp, 2 * rowb * H + 64) != hipSuccess) return adf::set_error(ADF_ENOMEM, "hipMalloc failed");
-        if (hipMemcpy2DAsync(tmp, rowb, gt, sg, rowb, H, hipMemcpyHostToDevice, st) != hipSuccess ||
-            hipMemcpy2DAsync((char*)tmp + rowb * H, rowb, src, ss, rowb, H, hipMemcpyHostToDevice, st) != hipSuccess) {
-            hipFree(tmp); return adf::set_error(ADF_EHIP, "host to device copy failed");
-        }
+        if (hipMalloc(&tmp, 2 * rowb * H + 64) != hipSuccess) return fail(ADF_ENOMEM, "hipMalloc failed");
+        int rc = copy_images(tmp, rowb, 0, gt, sg, 0, rowb, H, 1, hipMemcpyHostToDevice, st);
+        if (rc == ADF_OK) rc = copy_images((char*)tmp + rowb * H, rowb, 0, src, ss, 0, rowb, H, 1, hipMemcpyHostToDevice, st);
+        if (rc) { hipFree(tmp); return rc; }
         dg = (const int16_t*)tmp; ds = (const int16_t*)((char*)tmp + rowb * H); dsg = dss = (ptrdiff_t)rowb;
     }
     unsigned long long* acc = nullptr;
-    if (hipMalloc((void**)&acc, 3 * sizeof(unsigned long long)) != hipSuccess) { if (tmp) hipFree(tmp); return ADF_ENOMEM; }
+    if (hipMalloc((void**)&acc, 3 * sizeof(unsigned long long)) != hipSuccess) { if (tmp) hipFree(tmp); return fail(ADF_ENOMEM, "hipMalloc failed"); }
     hipMemsetAsync(acc, 0, 3 * sizeof(unsigned long long), st);
     EvalArgs a{dg, dsg, ds, dss, r.x, r.y, r.width, r.height, thresh, acc};
     dim3 grid((r.width + 255) / 256 > 64 ? 64 : (r.width + 255) / 256, r.height > 256 ? 256 : r.height);
@@ -84,7 +84,7 @@ int run_eval(const int16_t* gt, ptrdiff_t sg, const int16_t* src, ptrdiff_t ss, 
     if (e == hipSuccess) e = hipStreamSynchronize(st);
     hipFree(acc);
     if (tmp) hipFree(tmp);
-    return e == hipSuccess ? ADF_OK : adf::set_error(ADF_EHIP, hipGetErrorString(e));
+    return e == hipSuccess ? ADF_OK : fail(ADF_EHIP, "%s", hipGetErrorString(e));
 }
 
 } // namespace
@@ -124,22 +124,24 @@ extern "C" int adf_compute_bad_pixel_percent_host(const int16_t* gt, ptrdiff_t s
 extern "C" int adf_get_disparity_vis_device(const int16_t* src, ptrdiff_t ss, uint8_t* dst, ptrdiff_t sd, int W, int H,
                                             double scale, void* stream)
 {
-    if (!src || !dst || W <= 0 || H <= 0) return ADF_EBADARG;        // DF.cpp:543
+    if (!src || !dst || W <= 0 || H <= 0) return fail(ADF_EBADARG, "src / dst must be non-empty maps");   // DF.cpp:543
     hipLaunchKernelGGL(vis_kernel, dim3((W + 255) / 256, H), dim3(256), 0, (hipStream_t)stream, src, ss, dst, sd, W, H, scale);
-    return hipGetLastError() == hipSuccess ? ADF_OK : ADF_EHIP;
+    HIP_TRY(hipGetLastError());
+    return ADF_OK;
 }
 extern "C" int adf_get_disparity_vis_host(const int16_t* src, ptrdiff_t ss, uint8_t* dst, ptrdiff_t sd, int W, int H, double scale)
 {
-    if (!src || !dst || W <= 0 || H <= 0) return ADF_EBADARG;
+    if (!src || !dst || W <= 0 || H <= 0) return fail(ADF_EBADARG, "src / dst must be non-empty maps");
     void* tmp = nullptr;
     const size_t sb = (size_t)W * 2, db = (size_t)W;
-    if (hipMalloc(&tmp, (sb + db) * H + 64) != hipSuccess) return ADF_ENOMEM;
-    hipError_t e = hipMemcpy2D(tmp, sb, src, ss, sb, H, hipMemcpyHostToDevice);
+    if (hipMalloc(&tmp, (sb + db) * H + 64) != hipSuccess) return fail(ADF_ENOMEM, "hipMalloc failed");
+    int rc = copy_images(tmp, sb, 0, src, ss, 0, sb, H, 1, hipMemcpyHostToDevice, nullptr);
     uint8_t* dd = (uint8_t*)tmp + sb * H;
-    if (e == hipSuccess) {
+    if (rc == ADF_OK) {
         hipLaunchKernelGGL(vis_kernel, dim3((W + 255) / 256, H), dim3(256), 0, nullptr, (const int16_t*)tmp, (ptrdiff_t)sb, dd, (ptrdiff_t)db, W, H, scale);
-        e = hipMemcpy2D(dst, sd, dd, db, db, H, hipMemcpyDeviceToHost);
+        rc = copy_images(dst, sd, 0, dd, db, 0, db, H, 1, hipMemcpyDeviceToHost, nullptr);
     }
+    if (rc == ADF_OK && hipStreamSynchronize(nullptr) != hipSuccess) rc = fail(ADF_EHIP, "the visualisation kernel or its copies failed");
     hipFree(tmp);
-    return e == hipSuccess ? ADF_OK : ADF_EHIP;
+    return rc;
 }

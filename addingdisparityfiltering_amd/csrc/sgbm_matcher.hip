@@ -22,12 +22,13 @@
 //                         winner and fits the sub-pixel parabola (stereo_binary_sgbm.cpp:286-301, 419-446, 519-596)
 //   sgbm_fill_kernel / sgbm_median_kernel   invalid value everywhere first; 3x3 median of the CV_16S map last
 // HBM: C, S and L2 volumes of H x width1 x D int16 each (4K, 256 disparities: 4 GB each, per image in flight).
-#include "adf_internal.h"
-#include "../../include/adf_wls.h"
+#include "adf_host.h"
 
 #include <algorithm>
 #include <cstdlib>
 #include <new>
+
+using namespace adf;
 
 namespace {
 
@@ -521,25 +522,6 @@ __global__ void __launch_bounds__(256) sgbm_median_kernel(MedianArgs a)
     a.dst[(ptrdiff_t)blockIdx.z * a.dpair + (ptrdiff_t)y * a.dstride + x] = (int16_t)v[4];
 }
 
-int sg_fail(int code, const char* msg) { return adf::set_error(code, msg); }
-
-struct DevScope {
-    int prev = -1; bool sw = false;
-    explicit DevScope(int d) { if (hipGetDevice(&prev) == hipSuccess && prev != d) sw = hipSetDevice(d) == hipSuccess; }
-    ~DevScope() { if (sw) hipSetDevice(prev); }
-};
-
-int sg_reserve(void** p, size_t* have, size_t need, hipStream_t st)
-{
-    if (need <= *have) return ADF_OK;
-    if (*p) { if (hipStreamSynchronize(st) != hipSuccess) return sg_fail(ADF_EHIP, "hipStreamSynchronize failed"); hipFree(*p); *p = nullptr; *have = 0; }
-    need = (need + 255) / 256 * 256;
-    hipError_t e = adf::device_malloc(p, need);   // (gives the filter cache's blocks back first if it must)
-    if (e != hipSuccess) { *p = nullptr; return sg_fail(e == hipErrorOutOfMemory ? ADF_ENOMEM : ADF_EHIP, "hipMalloc failed for the matcher workspace"); }
-    *have = need;
-    return ADF_OK;
-}
-
 template <int CN>
 hipError_t launch_cost(const CostArgs& a, int bs, int n_images, hipStream_t st)
 {
@@ -597,19 +579,19 @@ struct adf_sgbm {
     int min_disp = 0, num_disp = 16, block = 3;
     int P1 = 0, P2 = 0, cap = 0, uniq = 0, mode = ADF_SGBM_MODE_SGBM;    // cv::StereoSGBM::create's defaults
     int disp12 = 0;                                                        // ... incl. disp12MaxDiff = 0, which the algorithm reads as 1 (check ON)
-    void* ws = nullptr; size_t ws_bytes = 0;
-    void* stage = nullptr; size_t stage_bytes = 0;
+    DevBuf ws;      // the volumes of the images in flight
+    DevBuf stage;   // host-pointer entry: device copies of the I/O
     size_t ws_limit = (size_t)64 << 30;
 };
 
 extern "C" int adf_sgbm_create(adf_sgbm_t** out, int min_disparity, int num_disparities, int block_size)
 {
-    if (!out) return sg_fail(ADF_EBADARG, "out is NULL");
+    if (!out) return fail(ADF_EBADARG, "out is NULL");
     *out = nullptr;
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return sg_fail(ADF_ENODEV, "no HIP device");
+    if (hipGetDevice(&dev) != hipSuccess) return fail(ADF_ENODEV, "no HIP device");
     adf_sgbm* h = new (std::nothrow) adf_sgbm;
-    if (!h) return sg_fail(ADF_ENOMEM, "out of host memory");
+    if (!h) return fail(ADF_ENOMEM, "out of host memory");
     h->device = dev; h->min_disp = min_disparity; h->num_disp = num_disparities; h->block = block_size;
     if (const char* e = getenv("ADF_WS_LIMIT_GB")) {
         const double gb = atof(e);
@@ -622,16 +604,16 @@ extern "C" int adf_sgbm_create(adf_sgbm_t** out, int min_disparity, int num_disp
 extern "C" void adf_sgbm_destroy(adf_sgbm_t* h)
 {
     if (!h) return;
-    DevScope ds(h->device);
-    if (h->ws) hipFree(h->ws);
-    if (h->stage) hipFree(h->stage);
+    DeviceScope ds(h->device);
+    h->ws.release();
+    h->stage.release();
     delete h;
 }
 
 extern "C" int adf_sgbm_set_params(adf_sgbm_t* h, int min_disparity, int num_disparities, int block_size, int P1, int P2,
                                    int prefilter_cap, int uniqueness_ratio, int mode)
 {
-    if (!h) return sg_fail(ADF_EBADARG, "handle is NULL");
+    if (!h) return fail(ADF_EBADARG, "handle is NULL");
     h->min_disp = min_disparity; h->num_disp = num_disparities; h->block = block_size;
     h->P1 = P1; h->P2 = P2; h->cap = prefilter_cap; h->uniq = uniqueness_ratio; h->mode = mode;
     return ADF_OK;
@@ -640,7 +622,7 @@ extern "C" int adf_sgbm_set_params(adf_sgbm_t* h, int min_disparity, int num_dis
 extern "C" int adf_sgbm_get_params(const adf_sgbm_t* h, int* min_disparity, int* num_disparities, int* block_size, int* P1, int* P2,
                                    int* prefilter_cap, int* uniqueness_ratio, int* mode)
 {
-    if (!h) return sg_fail(ADF_EBADARG, "handle is NULL");
+    if (!h) return fail(ADF_EBADARG, "handle is NULL");
     if (min_disparity) *min_disparity = h->min_disp;
     if (num_disparities) *num_disparities = h->num_disp;
     if (block_size) *block_size = h->block;
@@ -654,21 +636,21 @@ extern "C" int adf_sgbm_get_params(const adf_sgbm_t* h, int* min_disparity, int*
 
 extern "C" int adf_sgbm_set_disp12_max_diff(adf_sgbm_t* h, int v)
 {
-    if (!h) return sg_fail(ADF_EBADARG, "handle is NULL");
+    if (!h) return fail(ADF_EBADARG, "handle is NULL");
     h->disp12 = v;
     return ADF_OK;
 }
 
 extern "C" int adf_sgbm_get_disp12_max_diff(const adf_sgbm_t* h, int* v)
 {
-    if (!h) return sg_fail(ADF_EBADARG, "handle is NULL");
+    if (!h) return fail(ADF_EBADARG, "handle is NULL");
     if (v) *v = h->disp12;
     return ADF_OK;
 }
 
 extern "C" int adf_sgbm_get_device(const adf_sgbm_t* h, int* device)
 {
-    if (!h) return sg_fail(ADF_EBADARG, "handle is NULL");
+    if (!h) return fail(ADF_EBADARG, "handle is NULL");
     if (device) *device = h->device;
     return ADF_OK;
 }
@@ -676,21 +658,21 @@ extern "C" int adf_sgbm_get_device(const adf_sgbm_t* h, int* device)
 static int sgbm_check(const adf_sgbm* h, int n, const void* l, const void* r, const void* d, int cn, int W, int H,
                       ptrdiff_t ls, ptrdiff_t rs, ptrdiff_t dstr)
 {
-    if (!h) return sg_fail(ADF_EBADARG, "handle is NULL");
-    if (n <= 0 || !l || !r || !d) return sg_fail(ADF_EBADARG, "views and disparity must be non-NULL, n_pairs positive");
-    if (cn != 1 && cn != 3) return sg_fail(ADF_EBADARG, "views must be CV_8UC1 or CV_8UC3");
-    if (W <= 0 || H <= 0 || ls < (ptrdiff_t)W * cn || rs < (ptrdiff_t)W * cn || dstr < (ptrdiff_t)W * 2) return sg_fail(ADF_ESIZE, "bad size or stride");
-    if ((dstr & 1) || (reinterpret_cast<uintptr_t>(d) & 1)) return sg_fail(ADF_ESIZE, "disparity rows must be 2-byte aligned");
+    if (!h) return fail(ADF_EBADARG, "handle is NULL");
+    if (n <= 0 || !l || !r || !d) return fail(ADF_EBADARG, "views and disparity must be non-NULL, n_pairs positive");
+    if (cn != 1 && cn != 3) return fail(ADF_EBADARG, "views must be CV_8UC1 or CV_8UC3");
+    if (W <= 0 || H <= 0 || ls < (ptrdiff_t)W * cn || rs < (ptrdiff_t)W * cn || dstr < (ptrdiff_t)W * 2) return fail(ADF_ESIZE, "bad size or stride");
+    if ((dstr & 1) || (reinterpret_cast<uintptr_t>(d) & 1)) return fail(ADF_ESIZE, "disparity rows must be 2-byte aligned");
     if (h->mode != ADF_SGBM_MODE_3WAY && h->mode != ADF_SGBM_MODE_SGBM && h->mode != ADF_SGBM_MODE_HH)
-        return sg_fail(ADF_EBADARG, "mode must be StereoSGBM::MODE_SGBM, MODE_HH or MODE_SGBM_3WAY");
-    if (h->num_disp <= 0 || h->num_disp % 16) return sg_fail(ADF_EBADARG, "numDisparities must be positive and divisible by 16");
-    if (h->num_disp > 512) return sg_fail(ADF_EBADARG, "numDisparities above 512 is not supported");
+        return fail(ADF_EBADARG, "mode must be StereoSGBM::MODE_SGBM, MODE_HH or MODE_SGBM_3WAY");
+    if (h->num_disp <= 0 || h->num_disp % 16) return fail(ADF_EBADARG, "numDisparities must be positive and divisible by 16");
+    if (h->num_disp > 512) return fail(ADF_EBADARG, "numDisparities above 512 is not supported");
     const int bs = h->block > 0 ? h->block : 5;
-    if (bs % 2 == 0 || bs > 11) return sg_fail(ADF_EBADARG, "blockSize must be odd and at most 11");
-    if (h->min_disp < -2047 || h->min_disp + h->num_disp > 2047) return sg_fail(ADF_EBADARG, "disparity range does not fit CV_16S with 4 fractional bits");
-    if (h->P1 < 0 || h->P2 < 0 || h->P1 > 8000 || h->P2 > 16000) return sg_fail(ADF_EBADARG, "P1 / P2 out of range");
+    if (bs % 2 == 0 || bs > 11) return fail(ADF_EBADARG, "blockSize must be odd and at most 11");
+    if (h->min_disp < -2047 || h->min_disp + h->num_disp > 2047) return fail(ADF_EBADARG, "disparity range does not fit CV_16S with 4 fractional bits");
+    if (h->P1 < 0 || h->P2 < 0 || h->P1 > 8000 || h->P2 > 16000) return fail(ADF_EBADARG, "P1 / P2 out of range");
     if (h->disp12 < 100000 && (size_t)(W + 2 * (size_t)W) * 8 > 150 * 1024)
-        return sg_fail(ADF_ESIZE, "the matcher's own left-right check (disp12MaxDiff) supports images up to 6400 columns");
+        return fail(ADF_ESIZE, "the matcher's own left-right check (disp12MaxDiff) supports images up to 6400 columns");
     return ADF_OK;
 }
 
@@ -703,9 +685,9 @@ extern "C" int adf_sgbm_compute_device(adf_sgbm_t* h, int n_pairs,
 {
     int rc = sgbm_check(h, n_pairs, left, right, disparity, channels, W, H, left_stride, right_stride, disp_stride);
     if (rc) return rc;
-    if (n_pairs > 1 && (disp_pair_stride & 1)) return sg_fail(ADF_ESIZE, "disparity maps must be 2-byte aligned");
+    if (n_pairs > 1 && (disp_pair_stride & 1)) return fail(ADF_ESIZE, "disparity maps must be 2-byte aligned");
     hipStream_t st = (hipStream_t)stream;
-    DevScope ds(h->device);
+    DeviceScope ds(h->device);
     const int cn = channels, D = h->num_disp, minD = h->min_disp, maxD = minD + D;
     const int bs = h->block > 0 ? h->block : 5;
     const int P1 = h->P1 > 0 ? h->P1 : 2, P2 = std::max(h->P2 > 0 ? h->P2 : 5, P1 + 1);
@@ -726,9 +708,9 @@ extern "C" int adf_sgbm_compute_device(adf_sgbm_t* h, int n_pairs,
     int chunk = (int)(h->ws_limit / per_img);
     if (chunk < 1) chunk = 1;
     if (chunk > n_pairs) chunk = n_pairs;
-    rc = sg_reserve(&h->ws, &h->ws_bytes, per_img * (size_t)chunk, st);
+    rc = h->ws.reserve(per_img * (size_t)chunk, st, FILL_NONE);
     if (rc) return rc;
-    char* wsb = (char*)h->ws;
+    char* wsb = (char*)h->ws.p;
     uint32_t* rec1 = (uint32_t*)wsb;
     uint32_t* rec2 = (uint32_t*)(wsb + rec_bytes * chunk);
     int16_t* Cv = (int16_t*)(wsb + 2 * rec_bytes * chunk);
@@ -753,19 +735,19 @@ extern "C" int adf_sgbm_compute_device(adf_sgbm_t* h, int n_pairs,
             int rpb = 128;
             while (rpb > 16 && (size_t)((H + rpb - 1) / rpb) * ((w1 + 61) / 62) * ((D + 63) / 64) * n < 2048) rpb >>= 1;
             ca.rows_per_band = rpb;
-            if ((size_t)((H + rpb - 1) / rpb) * n > 65535) return sg_fail(ADF_ESIZE, "too many images per call for the cost kernel's grid");
+            if ((size_t)((H + rpb - 1) / rpb) * n > 65535) return fail(ADF_ESIZE, "too many images per call for the cost kernel's grid");
             hipError_t e = cn == 1 ? launch_cost<1>(ca, bs, n, st) : launch_cost<3>(ca, bs, n, st);
-            if (e != hipSuccess) return sg_fail(ADF_EHIP, hipGetErrorString(e));
+            if (e != hipSuccess) return fail(ADF_EHIP, "%s", hipGetErrorString(e));
             PathArgs pa{Cv, Sv, Lv, volp, W, H, D, minD, minX1, w1, P1, P2, ur, raw, (ptrdiff_t)W, (ptrdiff_t)raw_el, 0, 0, h->disp12};
             e = D <= 64 ? launch_paths<1>(pa, h->mode, n, st) : D <= 128 ? launch_paths<2>(pa, h->mode, n, st)
               : D <= 256 ? launch_paths<4>(pa, h->mode, n, st) : launch_paths<8>(pa, h->mode, n, st);
-            if (e != hipSuccess) return sg_fail(ADF_EHIP, hipGetErrorString(e));
+            if (e != hipSuccess) return fail(ADF_EHIP, "%s", hipGetErrorString(e));
         }
         MedianArgs ma{raw, (ptrdiff_t)W, (ptrdiff_t)raw_el, out, disp_stride / 2, disp_pair_stride / 2, W, H};
         hipLaunchKernelGGL(sgbm_median_kernel, dim3((W + 255) / 256, H, n), dim3(256), 0, st, ma);
     }
     hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return sg_fail(ADF_EHIP, hipGetErrorString(e));
+    if (e != hipSuccess) return fail(ADF_EHIP, "%s", hipGetErrorString(e));
     return ADF_OK;
 }
 
@@ -777,24 +759,20 @@ extern "C" int adf_sgbm_compute_host(adf_sgbm_t* h, int n_pairs,
 {
     int rc = sgbm_check(h, n_pairs, left, right, disparity, channels, W, H, left_stride, right_stride, disp_stride);
     if (rc) return rc;
-    DevScope ds(h->device);
+    DeviceScope ds(h->device);
     const size_t vrow = (size_t)W * channels, vbytes = vrow * H, dbytes = (size_t)W * H * 2;
-    rc = sg_reserve(&h->stage, &h->stage_bytes, (2 * vbytes + dbytes) * (size_t)n_pairs + 512, nullptr);
+    rc = h->stage.reserve((2 * vbytes + dbytes) * (size_t)n_pairs + 512, nullptr, FILL_NONE);
     if (rc) return rc;
-    uint8_t* dl = (uint8_t*)h->stage;
+    uint8_t* dl = (uint8_t*)h->stage.p;
     uint8_t* dr = dl + vbytes * n_pairs;
     int16_t* dd = (int16_t*)(((uintptr_t)(dr + vbytes * n_pairs) + 255) & ~(uintptr_t)255);
-    for (int i = 0; i < n_pairs; i++) {
-        if (hipMemcpy2D(dl + vbytes * i, vrow, left + (ptrdiff_t)i * left_pair_stride, left_stride, vrow, H, hipMemcpyHostToDevice) != hipSuccess ||
-            hipMemcpy2D(dr + vbytes * i, vrow, right + (ptrdiff_t)i * right_pair_stride, right_stride, vrow, H, hipMemcpyHostToDevice) != hipSuccess)
-            return sg_fail(ADF_EHIP, "copying the views to the device failed");
-    }
+    if ((rc = copy_images(dl, vrow, vbytes, left, left_stride, left_pair_stride, vrow, H, n_pairs, hipMemcpyHostToDevice, nullptr))) return rc;
+    if ((rc = copy_images(dr, vrow, vbytes, right, right_stride, right_pair_stride, vrow, H, n_pairs, hipMemcpyHostToDevice, nullptr))) return rc;
     rc = adf_sgbm_compute_device(h, n_pairs, dl, (ptrdiff_t)vrow, (ptrdiff_t)vbytes, dr, (ptrdiff_t)vrow, (ptrdiff_t)vbytes, channels, W, H,
                                  dd, (ptrdiff_t)W * 2, (ptrdiff_t)dbytes, nullptr);
     if (rc) return rc;
-    for (int i = 0; i < n_pairs; i++)
-        if (hipMemcpy2D((char*)disparity + (ptrdiff_t)i * disp_pair_stride, disp_stride, (char*)dd + dbytes * i, (size_t)W * 2,
-                        (size_t)W * 2, H, hipMemcpyDeviceToHost) != hipSuccess)
-            return sg_fail(ADF_EHIP, "copying the disparity map back failed");
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    if ((rc = copy_images(disparity, disp_stride, disp_pair_stride, dd, (size_t)W * 2, dbytes, (size_t)W * 2, H, n_pairs, hipMemcpyDeviceToHost, nullptr))) return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
     return ADF_OK;
 }

@@ -23,8 +23,9 @@
 // are smaller).  So every find loop strictly decreases its index and ends within index + 1 steps, and every union
 // loop strictly decreases a + b per retry (a failed CAS returns the smaller label a was linked to meanwhile) and ends
 // within a + b + 1 retries.  Labels are map-linear int32 indices: W * H < 2^31 is required.
-#include "adf_internal.h"
-#include "../../include/adf_wls.h"
+#include "adf_host.h"
+
+using namespace adf;
 
 namespace {
 
@@ -206,19 +207,17 @@ __global__ void __launch_bounds__(256) speckle_apply_kernel(SpeckleArgs a)
     if (a.sizes[(size_t)blockIdx.y * a.plane + r] <= a.max_size) row[x] = (int16_t)a.new_val;
 }
 
-int sp_fail(int code, const char* msg) { return adf::set_error(code, msg); }
-
 int speckle_check(int n, const int16_t* img, ptrdiff_t stride, ptrdiff_t map_stride, int W, int H, int new_val)
 {
-    if (!img || n < 1 || W < 1 || H < 1) return sp_fail(ADF_EBADARG, "filterSpeckles: the image is empty");
-    if (new_val < -32768 || new_val > 32767) return sp_fail(ADF_EBADARG, "filterSpeckles: newVal is outside the CV_16S range");
-    if ((int64_t)W * H >= ((int64_t)1 << 31)) return sp_fail(ADF_ESIZE, "filterSpeckles: W*H must be below 2^31 (int32 labels)");
-    if ((uint64_t)n * (uint64_t)W * (uint64_t)H > ((uint64_t)1 << 40)) return sp_fail(ADF_ESIZE, "filterSpeckles: batch too large");
+    if (!img || n < 1 || W < 1 || H < 1) return fail(ADF_EBADARG, "filterSpeckles: the image is empty");
+    if (new_val < -32768 || new_val > 32767) return fail(ADF_EBADARG, "filterSpeckles: newVal is outside the CV_16S range");
+    if ((int64_t)W * H >= ((int64_t)1 << 31)) return fail(ADF_ESIZE, "filterSpeckles: W*H must be below 2^31 (int32 labels)");
+    if ((uint64_t)n * (uint64_t)W * (uint64_t)H > ((uint64_t)1 << 40)) return fail(ADF_ESIZE, "filterSpeckles: batch too large");
     if (((uintptr_t)img & 1) || (stride & 1) || (map_stride & 1))
-        return sp_fail(ADF_EBADARG, "filterSpeckles: CV_16S image and strides must be 2-byte aligned");
-    if (stride < (ptrdiff_t)W * 2) return sp_fail(ADF_ESIZE, "filterSpeckles: row stride smaller than a row");
+        return fail(ADF_EBADARG, "filterSpeckles: CV_16S image and strides must be 2-byte aligned");
+    if (stride < (ptrdiff_t)W * 2) return fail(ADF_ESIZE, "filterSpeckles: row stride smaller than a row");
     if (n > 1 && map_stride < stride * (H - 1) + (ptrdiff_t)W * 2)
-        return sp_fail(ADF_ESIZE, "filterSpeckles: maps of the batch overlap (map stride smaller than a map)");
+        return fail(ADF_ESIZE, "filterSpeckles: maps of the batch overlap (map stride smaller than a map)");
     return ADF_OK;
 }
 
@@ -244,16 +243,9 @@ int speckle_run(int n, int16_t* img, ptrdiff_t stride, ptrdiff_t map_stride, int
         hipLaunchKernelGGL(speckle_count_kernel, dim3(pix_blocks, nm), dim3(256), 0, st, a);
         hipLaunchKernelGGL(speckle_apply_kernel, dim3(pix_blocks, nm), dim3(256), 0, st, a);
         const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return sp_fail(ADF_EHIP, hipGetErrorString(e));
+        if (e != hipSuccess) return fail(ADF_EHIP, "%s", hipGetErrorString(e));
     }
     return ADF_OK;
-}
-
-bool capturing(hipStream_t st)
-{
-    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-    if (hipStreamIsCapturing(st, &cs) != hipSuccess) { (void)hipGetLastError(); return false; }
-    return cs != hipStreamCaptureStatusNone;
 }
 
 } // namespace
@@ -273,24 +265,15 @@ extern "C" int adf_filter_speckles_device(int n_maps, int16_t* img, ptrdiff_t st
     const size_t need = adf_filter_speckles_workspace_bytes(n_maps, W, H);
     hipStream_t st = (hipStream_t)stream;
     if (workspace) {
-        if (workspace_bytes < need) return sp_fail(ADF_ESIZE, "filterSpeckles: workspace smaller than adf_filter_speckles_workspace_bytes");
-        if ((uintptr_t)workspace & 3) return sp_fail(ADF_EBADARG, "filterSpeckles: workspace must be 4-byte aligned");
+        if (workspace_bytes < need) return fail(ADF_ESIZE, "filterSpeckles: workspace smaller than adf_filter_speckles_workspace_bytes");
+        if ((uintptr_t)workspace & 3) return fail(ADF_EBADARG, "filterSpeckles: workspace must be 4-byte aligned");
         return speckle_run(n_maps, img, stride, map_stride, W, H, new_val, max_speckle_size, max_diff, workspace, st);
     }
     // library scratch: a block of the process-wide cache, ordered behind its last user's event (no host wait)
-    if (capturing(st)) return sp_fail(ADF_EBADARG, "filterSpeckles: a call captured into a graph needs a caller workspace");
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return sp_fail(ADF_ENODEV, "filterSpeckles: no HIP device");
-    size_t have = 0;
-    void* blk = adf::cache_take(dev, need, st, &have);
-    if (!blk) {
-        const hipError_t e = adf::device_malloc(&blk, need);
-        if (e != hipSuccess) return sp_fail(e == hipErrorOutOfMemory ? ADF_ENOMEM : ADF_EHIP, "filterSpeckles: workspace allocation failed");
-        have = need;
-    }
-    rc = speckle_run(n_maps, img, stride, map_stride, W, H, new_val, max_speckle_size, max_diff, blk, st);
-    adf::cache_give(dev, blk, have, st);
-    return rc;
+    if (stream_is_capturing(st)) return fail(ADF_EBADARG, "filterSpeckles: a call captured into a graph needs a caller workspace");
+    Scratch blk;
+    if ((rc = blk.take(need, st))) return rc;
+    return speckle_run(n_maps, img, stride, map_stride, W, H, new_val, max_speckle_size, max_diff, blk.p, st);
 }
 
 extern "C" int adf_filter_speckles_host(int n_maps, int16_t* img, ptrdiff_t stride, ptrdiff_t map_stride, int W, int H,
@@ -298,31 +281,17 @@ extern "C" int adf_filter_speckles_host(int n_maps, int16_t* img, ptrdiff_t stri
 {
     int rc = speckle_check(n_maps, img, stride, map_stride, W, H, new_val);
     if (rc) return rc;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return sp_fail(ADF_ENODEV, "filterSpeckles: no HIP device");
     // one block: the maps, dense, then the workspace
     const size_t row = (size_t)W * 2, map = (size_t)H * row, maps = (map * n_maps + 255) / 256 * 256;
-    const size_t need = maps + adf_filter_speckles_workspace_bytes(n_maps, W, H);
-    size_t have = 0;
-    void* blk = adf::cache_take(dev, need, nullptr, &have);
-    if (!blk) {
-        const hipError_t e = adf::device_malloc(&blk, need);
-        if (e != hipSuccess) return sp_fail(e == hipErrorOutOfMemory ? ADF_ENOMEM : ADF_EHIP, "filterSpeckles: allocation failed");
-        have = need;
-    }
-    char* d = static_cast<char*>(blk);
-    for (int i = 0; i < n_maps && rc == ADF_OK; i++)
-        if (hipMemcpy2D(d + map * i, row, reinterpret_cast<const char*>(img) + (ptrdiff_t)i * map_stride, stride, row, H,
-                        hipMemcpyHostToDevice) != hipSuccess)
-            rc = sp_fail(ADF_EHIP, "filterSpeckles: copying the maps to the device failed");
-    if (rc == ADF_OK)
-        rc = speckle_run(n_maps, reinterpret_cast<int16_t*>(d), (ptrdiff_t)row, (ptrdiff_t)map, W, H, new_val,
-                         max_speckle_size, max_diff, d + maps, nullptr);
-    if (rc == ADF_OK && hipStreamSynchronize(nullptr) != hipSuccess) rc = sp_fail(ADF_EHIP, "filterSpeckles: the kernels failed");
-    for (int i = 0; i < n_maps && rc == ADF_OK; i++)
-        if (hipMemcpy2D(reinterpret_cast<char*>(img) + (ptrdiff_t)i * map_stride, stride, d + map * i, row, row, H,
-                        hipMemcpyDeviceToHost) != hipSuccess)
-            rc = sp_fail(ADF_EHIP, "filterSpeckles: copying the maps back failed");
-    adf::cache_give(dev, blk, have, nullptr);
-    return rc;
+    Scratch blk;
+    if ((rc = blk.take(maps + adf_filter_speckles_workspace_bytes(n_maps, W, H), nullptr))) return rc;
+    char* d = static_cast<char*>(blk.p);
+    if ((rc = copy_images(d, row, map, img, stride, map_stride, row, H, n_maps, hipMemcpyHostToDevice, nullptr))) return rc;
+    rc = speckle_run(n_maps, reinterpret_cast<int16_t*>(d), (ptrdiff_t)row, (ptrdiff_t)map, W, H, new_val,
+                     max_speckle_size, max_diff, d + maps, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    if ((rc = copy_images(img, stride, map_stride, d, row, map, row, H, n_maps, hipMemcpyDeviceToHost, nullptr))) return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return ADF_OK;
 }

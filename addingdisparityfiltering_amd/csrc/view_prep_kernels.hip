@@ -23,8 +23,9 @@
 // with dwordx4 loads, works in registers, and stores 8, 16 or 24 bytes.  That needs 16-byte aligned source rows and 8-
 // or 16-byte aligned destination rows (the launcher checks base pointers and strides on the host); images that are not,
 // the last partial run of a row and partial cells take the byte path of the same kernel, one byte per access.
-#include "adf_internal.h"
-#include "../../include/adf_wls.h"
+#include "adf_host.h"
+
+using namespace adf;
 
 namespace {
 
@@ -161,8 +162,6 @@ __global__ void __launch_bounds__(NT) view_prep_kernel(ViewPrepArgs a)
     }
 }
 
-int vp_fail(int code, const char* msg) { return adf::set_error(code, msg); }
-
 const char* const SUPPORTED =
     "prepare_views supports CV_8UC3 -> CV_8UC3 and CV_8UC1 -> CV_8UC1 at half size, CV_8UC3 -> CV_8UC1 at full or half "
     "size (half size = adf_half_size of the width and of the height)";
@@ -173,24 +172,24 @@ int half_of(int n) { return (n >> 1) + (n & (n >> 1) & 1); }     // cvRound(n * 
 int view_prep_check(int n, const uint8_t* src, ptrdiff_t sstride, ptrdiff_t simage, int W, int H, int sc,
                     const uint8_t* dst, ptrdiff_t dstride, ptrdiff_t dimage, int dW, int dH, int dc, bool* half)
 {
-    if (n < 1) return vp_fail(ADF_EBADARG, "prepare_views: n_images must be at least 1");
-    if (!src || !dst) return vp_fail(ADF_EBADARG, "prepare_views: src and dst must not be null");
-    if (W < 1 || H < 1 || dW < 1 || dH < 1) return vp_fail(ADF_EBADARG, "prepare_views: the source or the destination image is empty");
-    if (!((sc == 3 && (dc == 3 || dc == 1)) || (sc == 1 && dc == 1))) return vp_fail(ADF_EBADARG, SUPPORTED);
+    if (n < 1) return fail(ADF_EBADARG, "prepare_views: n_images must be at least 1");
+    if (!src || !dst) return fail(ADF_EBADARG, "prepare_views: src and dst must not be null");
+    if (W < 1 || H < 1 || dW < 1 || dH < 1) return fail(ADF_EBADARG, "prepare_views: the source or the destination image is empty");
+    if (!((sc == 3 && (dc == 3 || dc == 1)) || (sc == 1 && dc == 1))) return fail(ADF_EBADARG, "%s", SUPPORTED);
     if (dW == W && dH == H) *half = false;
     else if (dW == half_of(W) && dH == half_of(H)) *half = true;
-    else return vp_fail(ADF_EBADARG, SUPPORTED);
-    if (!*half && sc == dc) return vp_fail(ADF_EBADARG, SUPPORTED);            // nothing to do is not a case either
-    if (W > MAX_DIM || H > MAX_DIM) return vp_fail(ADF_ESIZE, "prepare_views: W and H must not exceed 2^24");
+    else return fail(ADF_EBADARG, "%s", SUPPORTED);
+    if (!*half && sc == dc) return fail(ADF_EBADARG, "%s", SUPPORTED);            // nothing to do is not a case either
+    if (W > MAX_DIM || H > MAX_DIM) return fail(ADF_ESIZE, "prepare_views: W and H must not exceed 2^24");
     if (sstride < (ptrdiff_t)W * sc || dstride < (ptrdiff_t)dW * dc)
-        return vp_fail(ADF_EBADARG, "prepare_views: row stride smaller than a row");
+        return fail(ADF_EBADARG, "prepare_views: row stride smaller than a row");
     if (n > 1) {
-        if (simage < 0) return vp_fail(ADF_EBADARG, "prepare_views: negative image stride");
+        if (simage < 0) return fail(ADF_EBADARG, "prepare_views: negative image stride");
         // destination images either follow one another or interleave row by row
         const ptrdiff_t drow = (ptrdiff_t)dW * dc;
         const bool stacked = dimage >= dstride * (dH - 1) + drow;
         const bool interleaved = dimage >= drow && dimage * (n - 1) + drow <= dstride;
-        if (!stacked && !interleaved) return vp_fail(ADF_EBADARG, "prepare_views: destination images overlap");
+        if (!stacked && !interleaved) return fail(ADF_EBADARG, "prepare_views: destination images overlap");
     }
     return ADF_OK;
 }
@@ -200,7 +199,7 @@ int view_prep_launch(int n, ViewPrepArgs a, hipStream_t st)
 {
     using S = Shape<CH_IN, CH_OUT, HALF>;
     a.runs = (a.dW + S::RUN - 1) / S::RUN;
-    if ((int64_t)a.runs * a.dH >= ((int64_t)1 << 31)) return vp_fail(ADF_ESIZE, "prepare_views: image too large");
+    if ((int64_t)a.runs * a.dH >= ((int64_t)1 << 31)) return fail(ADF_ESIZE, "prepare_views: image too large");
     a.total = a.runs * a.dH;
     const uintptr_t smis = (uintptr_t)a.src | (uintptr_t)a.sstride | (n > 1 ? (uintptr_t)a.simage : 0);
     const uintptr_t dmis = (uintptr_t)a.dst | (uintptr_t)a.dstride | (n > 1 ? (uintptr_t)a.dimage : 0);
@@ -213,7 +212,7 @@ int view_prep_launch(int n, ViewPrepArgs a, hipStream_t st)
         a.dst = dst + (ptrdiff_t)m0 * a.dimage;
         hipLaunchKernelGGL((view_prep_kernel<CH_IN, CH_OUT, HALF>), dim3((unsigned)((a.total + NT - 1) / NT), nm), dim3(NT), 0, st, a);
         const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return vp_fail(ADF_EHIP, hipGetErrorString(e));
+        if (e != hipSuccess) return fail(ADF_EHIP, "%s", hipGetErrorString(e));
     }
     return ADF_OK;
 }
@@ -235,7 +234,7 @@ int view_prep_run(int n, const uint8_t* src, ptrdiff_t sstride, ptrdiff_t simage
 
 extern "C" int adf_half_size(int n, int* half)
 {
-    if (n < 0 || !half) return vp_fail(ADF_EBADARG, "adf_half_size: n must not be negative and half must not be null");
+    if (n < 0 || !half) return fail(ADF_EBADARG, "adf_half_size: n must not be negative and half must not be null");
     *half = half_of(n);
     return ADF_OK;
 }
@@ -262,33 +261,20 @@ extern "C" int adf_prepare_views_host(int n_images, const uint8_t* src, ptrdiff_
     int rc = view_prep_check(n_images, src, src_stride, src_image_stride, W, H, src_channels,
                              dst, dst_stride, dst_image_stride, dst_W, dst_H, dst_channels, &half);
     if (rc) return rc;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return vp_fail(ADF_ENODEV, "prepare_views: no HIP device");
     // one block: the source images, then the destination images, rows and images padded to 16 bytes (the vector path)
     const size_t srow = (size_t)W * src_channels, drow = (size_t)dst_W * dst_channels;
     const size_t sp = (srow + 15) / 16 * 16, dp = (drow + 15) / 16 * 16;
     const size_t simg = sp * H, dimg = dp * dst_H, need = (simg + dimg) * (size_t)n_images;
-    size_t have = 0;
-    void* blk = adf::cache_take(dev, need, nullptr, &have);
-    if (!blk) {
-        const hipError_t e = adf::device_malloc(&blk, need);
-        if (e != hipSuccess) return vp_fail(e == hipErrorOutOfMemory ? ADF_ENOMEM : ADF_EHIP, "prepare_views: allocation failed");
-        have = need;
-    }
-    uint8_t* ds = static_cast<uint8_t*>(blk);
+    Scratch blk;
+    if ((rc = blk.take(need, nullptr))) return rc;
+    uint8_t* ds = static_cast<uint8_t*>(blk.p);
     uint8_t* dd = ds + simg * n_images;
-    for (int i = 0; i < n_images && rc == ADF_OK; i++)
-        if (hipMemcpy2D(ds + simg * i, sp, src + (ptrdiff_t)i * src_image_stride, src_stride, srow, H,
-                        hipMemcpyHostToDevice) != hipSuccess)
-            rc = vp_fail(ADF_EHIP, "prepare_views: copying the images to the device failed");
-    if (rc == ADF_OK)
-        rc = view_prep_run(n_images, ds, (ptrdiff_t)sp, (ptrdiff_t)simg, W, H, src_channels,
-                           dd, (ptrdiff_t)dp, (ptrdiff_t)dimg, dst_W, dst_H, dst_channels, half, nullptr);
-    if (rc == ADF_OK && hipStreamSynchronize(nullptr) != hipSuccess) rc = vp_fail(ADF_EHIP, "prepare_views: the kernel failed");
-    for (int i = 0; i < n_images && rc == ADF_OK; i++)
-        if (hipMemcpy2D(dst + (ptrdiff_t)i * dst_image_stride, dst_stride, dd + dimg * i, dp, drow, dst_H,
-                        hipMemcpyDeviceToHost) != hipSuccess)
-            rc = vp_fail(ADF_EHIP, "prepare_views: copying the images back failed");
-    adf::cache_give(dev, blk, have, nullptr);
-    return rc;
+    if ((rc = copy_images(ds, sp, simg, src, src_stride, src_image_stride, srow, H, n_images, hipMemcpyHostToDevice, nullptr))) return rc;
+    rc = view_prep_run(n_images, ds, (ptrdiff_t)sp, (ptrdiff_t)simg, W, H, src_channels,
+                       dd, (ptrdiff_t)dp, (ptrdiff_t)dimg, dst_W, dst_H, dst_channels, half, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    if ((rc = copy_images(dst, dst_stride, dst_image_stride, dd, dp, dimg, drow, dst_H, n_images, hipMemcpyDeviceToHost, nullptr))) return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return ADF_OK;
 }

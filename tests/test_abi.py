@@ -103,7 +103,7 @@ def test_synthetic_example_shape_and_determinism():
 
 def test_weight_table_equals_the_oracles_for_a_sweep_of_sigmas():
     """The library builds the table by threads and stores the tail where the exponential has underflowed instead of
-    computing it (adf_api.hip: lut_build_host): every entry must still carry the bits libm gives the oracle."""
+    computing it (adf_host.hip: lut_build_host): every entry must still carry the bits libm gives the oracle."""
     import ctypes as C
 
     import numpy as np

@@ -1,5 +1,5 @@
 """Filters made and destroyed per call (EF.hpp:413 fastGlobalSmootherFilter; perf_fgs_filter.cpp:70-76): the library hands a
-destroyed filter's device block to the next one behind an event and shares weight tables by sigma (adf_api.hip:
+destroyed filter's device block to the next one behind an event and shares weight tables by sigma (adf_host.hip:
 BlockCache, LutStore).  Results must not depend on any of that."""
 import numpy as np
 import pytest
