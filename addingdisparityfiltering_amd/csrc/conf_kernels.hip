@@ -16,6 +16,7 @@
 #include "adf_internal.h"
 #include <mutex>
 #include <cstdlib>
+#include <type_traits>
 #include "prep_bodies.h"
 
 #pragma clang fp contract(off)
@@ -30,6 +31,19 @@ constexpr int TX = 64; // tile width  (one wavefront wide: 128-byte int16 rows, 
 constexpr int TY = 32; // tile height
 constexpr int NT = 256;
 constexpr int MAX_RADIUS = 40;
+
+// One value of a discontinuity map (DF.cpp:369-370) from a window's exact sum s1 and square sum; scale = 1 / window
+// area.  sum2() returns the square sum as a double, formed from each kernel's own representation; it is a callable so
+// that it is formed where the formula uses it ("Confidence kernels").
+template <class Sum2>
+__device__ __forceinline__ float disc_value(int s1, Sum2 sum2, double scale, float roll_off)
+{
+    const float mean = (float)((double)s1 * scale);
+    const float sq = (float)(sum2() * scale);
+    const float variance = sq - mean * mean;          // DF.cpp:369
+    const float v = 1.0f - roll_off * variance;       // DF.cpp:370
+    return v < 0.0f ? 0.0f : v;
+}
 
 // ---------------------------------------------------------------------------------------
 // Depth-discontinuity maps.  One block = one TX x TY tile of ROI outputs of one view of one pair
@@ -95,11 +109,7 @@ __global__ void __launch_bounds__(NT) discontinuity_kernel(DiscArgs a)
             }
             const int gy = y0 + ys + i;
             if (gy < a.rh && gx < a.rw) {
-                const float mean = (float)((double)s1 * scale);
-                const float sq = (float)((double)s2 * scale);
-                const float variance = sq - mean * mean;       // DF.cpp:369
-                const float v = 1.0f - a.roll_off * variance;  // DF.cpp:370
-                dst[(size_t)(a.ry + gy) * a.W + rx + gx] = v < 0.0f ? 0.0f : v;
+                dst[(size_t)(a.ry + gy) * a.W + rx + gx] = disc_value(s1, [=] { return (double)s2; }, scale, a.roll_off);
             }
         }
     }
@@ -211,11 +221,7 @@ __global__ void __launch_bounds__(NT) discontinuity_col_kernel(DiscArgs a)
                 S.add(hsum);
                 if (n >= 2 * RT && writer) {                     // window rows n-2RT..n are complete
                     const int oy = y_out0 + n - 2 * RT;
-                    const float mean = (float)((double)S.s1 * scale);
-                    const float sq = (float)(S.sum2() * scale);
-                    const float variance = sq - mean * mean;      // DF.cpp:369
-                    const float v = 1.0f - a.roll_off * variance; // DF.cpp:370
-                    ADF_ST(&dst[(size_t)oy * a.W], v < 0.0f ? 0.0f : v);
+                    ADF_ST(&dst[(size_t)oy * a.W], disc_value(S.s1, [&] { return S.sum2(); }, scale, a.roll_off));
                 }
             }
         }
@@ -316,11 +322,7 @@ __global__ void __launch_bounds__(NT) conf_left_kernel(ConfLeftArgs a)
                 if (n >= 2 * RT && writer) {                     // window centred on input row n-RT is complete
                     const int oy = y_out0 + n - 2 * RT;
                     const int i_abs = g.ry + oy;
-                    const float mean = (float)((double)S.s1 * scale);
-                    const float sq = (float)(S.sum2() * scale);
-                    const float variance = sq - mean * mean;      // DF.cpp:369
-                    float c = 1.0f - a.roll_off * variance;       // DF.cpp:370
-                    c = c < 0.0f ? 0.0f : c;
+                    float c = disc_value(S.s1, [&] { return S.sum2(); }, scale, a.roll_off);
                     // centre row's own disparity and its gathers: this group's slot s-RT, or carried over
                     const int d = (s >= RT) ? cur[(s >= RT) ? s - RT : 0] : cd[(s < RT) ? s : 0];
                     const int dr = (s >= RT) ? gd[(s >= RT) ? s - RT : 0] : cdr[(s < RT) ? s : 0];
@@ -367,7 +369,10 @@ __global__ void __launch_bounds__(NT) conf_left_kernel(ConfLeftArgs a)
 constexpr int CB_COLS = 4;
 #define CB_HALO(RT) (((RT) + CB_COLS - 1) / CB_COLS)                 // halo lanes on each side of a wave
 #define CB_WOUT(RT) ((64 - 2 * CB_HALO(RT)) * CB_COLS)               // output columns per wave: 248 (radius <= 4), 240 (5..8)
-#define CB_RLDS(RT) ((RT) >= 4)                                     // right view's row ring in LDS by default (conf_band_body)
+// The right view's K raw rows of the band kernel (conf_band_body): registers at radius 1..3, LDS at 4..6 (K + 1 rows
+// of any width the kernel covers fit), LDS where the ROI's width lets them fit at 7..8.
+enum BandRing { RING_REGS, RING_LDS, RING_LDS_BY_WIDTH };
+constexpr BandRing band_ring(int rt) { return rt < 4 ? RING_REGS : rt <= 6 ? RING_LDS : RING_LDS_BY_WIDTH; }
 constexpr int CB_MAX_WAVES = 16;
 constexpr int CB_MAX_BAND_ROWS = 2048;                             // output rows of a band (ColSum::lo must not wrap)
 constexpr int CB_MAX_RADIUS = 2 * CB_COLS;
@@ -391,16 +396,6 @@ struct ColSum {
         hi += diff >> 16;
     }
 };
-
-__device__ __forceinline__ float disc_value(int s1, unsigned lo, int hi, double scale, float roll_off)
-{
-    const float mean = (float)((double)s1 * scale);
-    // (65536 * hi + lo is an integer below 2^53: the fused form is exact, like the product and the sum it replaces)
-    const float sq = (float)(__builtin_fma((double)hi, 65536.0, (double)lo) * scale);
-    const float variance = sq - mean * mean;          // DF.cpp:369
-    const float v = 1.0f - roll_off * variance;       // DF.cpp:370
-    return v < 0.0f ? 0.0f : v;
-}
 
 // The four map values of a lane's columns from its column sums.  Horizontal window of output column q (0..3): virtual
 // columns q-RT .. q+RT relative to the lane's first column, i.e. the lane's own columns max(0,q-RT) .. min(3,q+RT) --
@@ -443,13 +438,14 @@ __device__ __forceinline__ void band_row_values(const ColSum (&V)[CB_COLS], doub
         int h1 = p1[b] - p1[a], hh = ph[b] - ph[a];
         unsigned hl = pl[b] - pl[a];
         band_neighbours<RT, CB_HALO(RT)>(p1, pl, ph, q, h1, hl, hh);
-        out[q] = disc_value(h1, hl, hh, scale, roll_off);
+        // (65536 * hh + hl is an integer below 2^53: the fused form is exact, like the product and the sum it replaces)
+        out[q] = disc_value(h1, [=] { return __builtin_fma((double)hh, 65536.0, (double)hl); }, scale, roll_off);
     }
 }
 
 // (band `band` of image `pz`; smem = the workgroup's dynamic LDS.  Waves past the ROI's width own no columns and only
 // keep the barriers company: the merged preparation kernel launches at least four waves per block.)
-template <int RT, bool RLDS = CB_RLDS(RT)>
+template <int RT, bool RLDS = band_ring(RT) != RING_REGS>
 __device__ __forceinline__ void conf_band_body(const ConfBandArgs& a, const int band, const size_t pz, unsigned char* smem)
 {
     constexpr int K = 2 * RT + 1;
@@ -607,7 +603,7 @@ __device__ __forceinline__ void conf_band_body(const ConfBandArgs& a, const int 
 #undef CB_ELEM
 }
 
-template <int RT, bool RLDS = CB_RLDS(RT)>
+template <int RT, bool RLDS = band_ring(RT) != RING_REGS>
 __global__ void __launch_bounds__(64 * CB_MAX_WAVES) conf_band_kernel(ConfBandArgs a)
 {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -862,6 +858,30 @@ inline size_t disc_lds_bytes(int r)
     return IH * TX * 8 + IH * TX * 4 + ((IH * IWP * 2 + 15) & ~(size_t)15);
 }
 
+// f(std::integral_constant<int, R>), a kernel, for the R in [LO, HI] that equals radius; nullptr if there is none.
+template <int LO, int HI, class F>
+inline auto dispatch_radius(int radius, F&& f) -> decltype(f(std::integral_constant<int, LO>{}))
+{
+    if (radius == LO) return f(std::integral_constant<int, LO>{});
+    if constexpr (LO < HI) return dispatch_radius<LO + 1, HI>(radius, f);
+    else return nullptr;
+}
+
+// Dynamic LDS beyond `threshold` has to be allowed per function AND device (a process may hold handles on several):
+// set whenever needed, never cached process-wide.
+template <class Kernel>
+inline hipError_t ensure_dynamic_lds(Kernel kernel, size_t bytes, size_t threshold)
+{
+    if (bytes <= threshold) return hipSuccess;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
+
+inline dim3 col_grid(int rw, int rh, int radius, int nz)   // column-walking kernels: strips of NT - 2*radius output columns
+{
+    const int gx = (rw + (NT - 2 * radius) - 1) / (NT - 2 * radius);
+    return dim3(gx, row_blocks(rh, gx * nz), nz);
+}
+
 } // namespace
 
 int max_disc_radius() { return MAX_RADIUS; }
@@ -870,28 +890,17 @@ hipError_t launch_discontinuity(const DiscArgs& a, int n_pairs, hipStream_t st)
 {
     if (a.rw <= 0 || a.rh <= 0 || n_pairs <= 0) return hipSuccess;
     if (a.radius < 0 || a.radius > MAX_RADIUS) return hipErrorInvalidValue;
+    const int nz = (a.only_view >= 0 ? 1 : 2) * n_pairs;
     if (a.radius <= 8) {
-        dim3 grid(1, 1, (a.only_view >= 0 ? 1 : 2) * n_pairs);
-#define ADF_DC(RR)                                                                             \
-    case RR:                                                                                   \
-        grid.x = (a.rw + (NT - 2 * RR) - 1) / (NT - 2 * RR);                                   \
-        grid.y = row_blocks(a.rh, grid.x * grid.z);                                            \
-        hipLaunchKernelGGL(discontinuity_col_kernel<RR>, grid, dim3(NT), 0, st, a);            \
-        break;
-        switch (a.radius) {
-            ADF_DC(0) ADF_DC(1) ADF_DC(2) ADF_DC(3) ADF_DC(4) ADF_DC(5) ADF_DC(6) ADF_DC(7) ADF_DC(8)
-        }
-#undef ADF_DC
+        const auto k = dispatch_radius<0, 8>(a.radius, [](auto R) { return &discontinuity_col_kernel<decltype(R)::value>; });
+        hipLaunchKernelGGL(k, col_grid(a.rw, a.rh, a.radius, nz), dim3(NT), 0, st, a);
         return hipGetLastError();
     }
     static_assert(TX == 64 && TY == 32 && NT == 256, "discontinuity_kernel assumes a 64x32 tile and 256 threads");
     const size_t lds = disc_lds_bytes(a.radius);
-    if (lds > 48 * 1024) {      // per function AND device: set whenever needed, never cached process-wide
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(discontinuity_kernel),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
-    }
-    dim3 grid((a.rw + TX - 1) / TX, (a.rh + TY - 1) / TY, (a.only_view >= 0 ? 1 : 2) * n_pairs);
+    hipError_t e = ensure_dynamic_lds(discontinuity_kernel, lds, 48 * 1024);
+    if (e != hipSuccess) return e;
+    dim3 grid((a.rw + TX - 1) / TX, (a.rh + TY - 1) / TY, nz);
     hipLaunchKernelGGL(discontinuity_kernel, grid, dim3(NT), lds, st, a);
     return hipGetLastError();
 }
@@ -899,64 +908,80 @@ hipError_t launch_discontinuity(const DiscArgs& a, int n_pairs, hipStream_t st)
 int conf_left_max_radius() { return 8; }
 
 constexpr size_t CB_LDS_LIMIT = 150 * 1024;
-static inline size_t conf_band_lds_rows(int rw, size_t ring_rows) { const size_t rwp = (size_t)((rw + 3) & ~3); return 2 * rwp * 4 + ring_rows * rwp * 2; }
-// does the band kernel keep the right view's whole row ring in LDS for this width?
-static inline bool conf_band_rlds(int rw, int radius) { return CB_RLDS(radius) && conf_band_lds_rows(rw, 2 * (size_t)radius + 2) <= CB_LDS_LIMIT; }
-static inline size_t conf_band_lds(int rw, int radius)
+
+// What a band workgroup of an ROI looks like: one wave per CB_WOUT columns, the right map's two rows and the ring of
+// raw right rows in LDS -- all K + 1 of them where band_ring() says so and they fit, else the centre row + slack.
+struct BandShape { int waves; size_t lds; bool rlds; };
+static BandShape conf_band_shape(const Geom& g, int radius)
 {
-    return conf_band_lds_rows(rw, conf_band_rlds(rw, radius) ? 2 * (size_t)radius + 2 : (size_t)radius + 2);   // rows of raw right disparities
+    const size_t rwp = (size_t)((g.rw + 3) & ~3);
+    const auto lds = [&](size_t ring_rows) { return 2 * rwp * 4 + ring_rows * rwp * 2; };
+    const size_t K = 2 * (size_t)radius + 1;
+    const bool rlds = band_ring(radius) != RING_REGS && lds(K + 1) <= CB_LDS_LIMIT;
+    return BandShape{(g.rw + CB_WOUT(radius) - 1) / CB_WOUT(radius), lds(rlds ? K + 1 : (size_t)radius + 2), rlds};
 }
 
 bool conf_band_fits(const Geom& g, int radius)
 {
     return radius >= 1 && radius <= CB_MAX_RADIUS && g.rw >= 8 && g.rw > radius && g.rw <= CB_MAX_WAVES * CB_WOUT(radius) &&
-           g.rh > radius && conf_band_lds(g.rw, radius) <= CB_LDS_LIMIT;
+           g.rh > radius && conf_band_shape(g, radius).lds <= CB_LDS_LIMIT;
+}
+
+// The band kernel's instantiation for a radius and ring choice (nullptr: no such radius).
+typedef void (*BandKernel)(ConfBandArgs);
+static BandKernel conf_band_variant(int radius, bool rlds)
+{
+    return dispatch_radius<1, CB_MAX_RADIUS>(radius, [&](auto R) -> BandKernel {
+        constexpr int RR = decltype(R)::value;
+        if constexpr (band_ring(RR) == RING_LDS_BY_WIDTH) return rlds ? conf_band_kernel<RR, true> : conf_band_kernel<RR, false>;
+        else return conf_band_kernel<RR>;
+    });
 }
 
 // Band workgroups of this shape a CU holds at once (occupancy query, remembered per radius for the last shape asked).
-static int conf_band_resident(int radius, bool rlds, int threads, size_t lds, int dev)
+static int conf_band_resident(int radius, const BandShape& sh, int dev)
 {
-    struct Memo { int dev, threads; size_t lds; bool rlds; int value; };
+    struct Memo { int dev; BandShape sh; int value; };
     static Memo memo[CB_MAX_RADIUS + 1] = {};
     static std::mutex mu;
     {
         std::lock_guard<std::mutex> lk(mu);
         const Memo& m = memo[radius];
-        if (m.value > 0 && m.dev == dev && m.threads == threads && m.lds == lds && m.rlds == rlds) return m.value;
+        if (m.value > 0 && m.dev == dev && m.sh.waves == sh.waves && m.sh.lds == sh.lds && m.sh.rlds == sh.rlds) return m.value;
     }
     int v = 0;
-    hipError_t e = hipErrorInvalidValue;
-    // (radius 1..3 have no LDS-ring variant, 4..6 always use it, 7..8 by the ROI's width)
-#define ADF_CBQ(RR) case RR: e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, conf_band_kernel<RR>, threads, lds); break;
-#define ADF_CBQ2(RR) case RR: e = rlds ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, conf_band_kernel<RR, true>, threads, lds) \
-                                       : hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, conf_band_kernel<RR, false>, threads, lds); break;
-    switch (radius) { ADF_CBQ(1) ADF_CBQ(2) ADF_CBQ(3) ADF_CBQ(4) ADF_CBQ(5) ADF_CBQ(6) ADF_CBQ2(7) ADF_CBQ2(8) }
-#undef ADF_CBQ
-#undef ADF_CBQ2
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&v, conf_band_variant(radius, sh.rlds), 64 * sh.waves, sh.lds);
     if (e != hipSuccess || v < 1) { (void)hipGetLastError(); v = 1; }
     std::lock_guard<std::mutex> lk(mu);
-    memo[radius] = Memo{dev, threads, lds, rlds, v};
+    memo[radius] = Memo{dev, sh, v};
     return v;
 }
 
-template <int RR, bool RL>
-static hipError_t launch_conf_band_variant(const ConfBandArgs& a, dim3 grid, dim3 block, size_t lds, hipStream_t st)
+// CUs of a device, read once per device (racing writers store the same value); 256 if it cannot be asked
+static int cu_count(int dev)
 {
-    // (the attribute belongs to the function ON THE CURRENT DEVICE and a process may hold handles on several: no cache)
-    if (lds > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(conf_band_kernel<RR, RL>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return e;
+    static int cache[64] = {0};
+    int cus = 0;
+    if (dev >= 0 && dev < 64) cus = __atomic_load_n(&cache[dev], __ATOMIC_RELAXED);
+    if (cus <= 0) {
+        if (dev < 0 || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
+        if (dev >= 0 && dev < 64) __atomic_store_n(&cache[dev], cus, __ATOMIC_RELAXED);
     }
-    hipLaunchKernelGGL((conf_band_kernel<RR, RL>), grid, block, lds, st, a);
-    return hipSuccess;
+    return cus;
 }
 
-hipError_t launch_conf_band(const ConfBandArgs& a0, int n_pairs, hipStream_t st)
+// rows of a band asked to be `want` rows tall: at least the halo's 2 * radius (and 4), at most CB_MAX_BAND_ROWS and rh
+static int conf_band_clamp_rows(int want, int rh, int radius)
 {
-    if (!conf_band_fits(a0.g, a0.radius)) return hipErrorInvalidValue;
-    ConfBandArgs a = a0;
-    const int waves = (a.g.rw + CB_WOUT(a.radius) - 1) / CB_WOUT(a.radius);
+    const int min_rpb = 2 * radius > 4 ? 2 * radius : 4;
+    int rpb = want < min_rpb ? min_rpb : want;
+    if (rpb > CB_MAX_BAND_ROWS) rpb = CB_MAX_BAND_ROWS;
+    return rpb > rh ? rh : rpb;
+}
+
+// How tall the bands of a launch are: the policy, and what it was measured against.
+static int conf_band_rows_per_band(const Geom& g, int radius, const BandShape& sh, int n_pairs)
+{
     // bands: at most ONE workgroup per CU, on three quarters of the CUs (round 3; it was two rounds of the chip).  A band workgroup is 15 waves with 57 KB of
     // LDS: it only starts on a CU that has all of that free at once, and the weight kernel that runs beside this one on
     // the side stream refills every slot a finished band leaves with its own small workgroups -- the second round's
@@ -968,22 +993,16 @@ hipError_t launch_conf_band(const ConfBandArgs& a0, int n_pairs, hipStream_t st)
     static const int bands_env = [] { const char* e = getenv("ADF_CONF_BANDS_TOTAL"); return e ? atoi(e) : 0; }();   // A/B knob
     int bands_total = bands_env;
     if (bands_total <= 0) {
-        static int cu_count[64] = {0};                        // per device, read once (racing writers store the same value)
-        int dev = 0, cus = 0;
+        int dev = 0;
         if (hipGetDevice(&dev) != hipSuccess) dev = -1;
-        if (dev >= 0 && dev < 64) cus = __atomic_load_n(&cu_count[dev], __ATOMIC_RELAXED);
-        if (cus <= 0) {
-            if (dev < 0 || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-            if (dev >= 0 && dev < 64) __atomic_store_n(&cu_count[dev], cus, __ATOMIC_RELAXED);
-        }
+        const int cus = cu_count(dev);
         // a quarter of the CUs left to the weight kernel (and the fill) alone: radius 2 -- both finish together, 1.82 / 1.92 ms
         // instead of 1.35 / 2.0 with a band on every CU, the step 13.12-13.18 -> 13.04-13.09 ms; radius 3 -- 13.55-13.78 ->
         // 13.09-13.13 ms; radius 5 on the StereoBM factory's ROI -- 13.87-14.16 -> 13.69-13.96 (the band kernels of radius 4..8
         // fill a SIMD's registers with four waves: nothing runs BESIDE them, but the fill no longer crawls behind them)
         // (narrow ROIs make small band workgroups, several of which share a CU: ask the runtime how many -- 256 frames of
         // 1242x375 per call lost 6 % with one tall band per frame)
-        int per_cu = conf_band_resident(a.radius, conf_band_rlds(a.g.rw, a.radius), 64 * waves, conf_band_lds(a.g.rw, a.radius), dev);
-        if (per_cu < 1) per_cu = 1;
+        const int per_cu = conf_band_resident(radius, sh, dev);   // (at least 1)
         // (after the slide's instruction diet the kernels whose registers leave room for a wave of the weight kernel beside
         // the band's four on a SIMD -- at most 104 per lane: radius 1..3, and 4..5 since their right-view ring moved to
         // LDS -- do better with a band on EVERY CU: radius 2 12.81-13.24 against 13.05-13.20 ms per 64 x 4K step, four
@@ -992,33 +1011,25 @@ hipError_t launch_conf_band(const ConfBandArgs& a0, int n_pairs, hipStream_t st)
         // Radius 6..8 (108..128 registers) keep the quarter free: radius 6 13.65-13.78 against 13.92)
         // (narrow ROIs, whose small band workgroups share a CU, keep the quarter free at every radius: 256 frames of
         // 1242x375 per call 2.95-2.97 against 3.06 ms)
-        const int quarters = a.radius <= 5 && per_cu == 1 ? 4 : 3;
+        const int quarters = radius <= 5 && per_cu == 1 ? 4 : 3;
         bands_total = cus * quarters / 4 * per_cu;
     }
-    int bands = (bands_total + n_pairs - 1) / n_pairs;
-    int rpb = (a.g.rh + bands - 1) / bands;
-    const int min_rpb = 2 * a.radius > 4 ? 2 * a.radius : 4;     // (at least as many output rows as halo rows)
-    if (rpb < min_rpb) rpb = min_rpb;
-    if (rpb > CB_MAX_BAND_ROWS) rpb = CB_MAX_BAND_ROWS;
-    if (rpb > a.g.rh) rpb = a.g.rh;
-    a.rows_per_band = rpb;
-    const dim3 grid((a.g.rh + rpb - 1) / rpb, n_pairs), block(64 * waves);
-    const size_t lds = conf_band_lds(a.g.rw, a.radius);
-    const bool rl = conf_band_rlds(a.g.rw, a.radius);
-    hipError_t le = hipErrorInvalidValue;
-#define ADF_CB(RR, RL) le = launch_conf_band_variant<RR, RL>(a, grid, block, lds, st)
-    switch (a.radius) {
-    case 1: ADF_CB(1, false); break;
-    case 2: ADF_CB(2, false); break;
-    case 3: ADF_CB(3, false); break;
-    case 4: ADF_CB(4, true); break;
-    case 5: ADF_CB(5, true); break;
-    case 6: ADF_CB(6, true); break;
-    case 7: if (rl) ADF_CB(7, true); else ADF_CB(7, false); break;
-    case 8: if (rl) ADF_CB(8, true); else ADF_CB(8, false); break;
-    }
-    if (le != hipSuccess) return le;
-#undef ADF_CB
+    const int bands = (bands_total + n_pairs - 1) / n_pairs;
+    return conf_band_clamp_rows((g.rh + bands - 1) / bands, g.rh, radius);
+}
+
+hipError_t launch_conf_band(const ConfBandArgs& a0, int n_pairs, hipStream_t st)
+{
+    if (!conf_band_fits(a0.g, a0.radius)) return hipErrorInvalidValue;
+    ConfBandArgs a = a0;
+    const BandShape sh = conf_band_shape(a.g, a.radius);
+    a.rows_per_band = conf_band_rows_per_band(a.g, a.radius, sh, n_pairs);
+    const dim3 grid((a.g.rh + a.rows_per_band - 1) / a.rows_per_band, n_pairs), block(64 * sh.waves);
+    const BandKernel k = conf_band_variant(a.radius, sh.rlds);
+    if (!k) return hipErrorInvalidValue;
+    hipError_t e = ensure_dynamic_lds(k, sh.lds, 48 * 1024);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k, grid, block, sh.lds, st, a);
     return hipGetLastError();
 }
 
@@ -1043,17 +1054,15 @@ hipError_t launch_prep_small(const ConfBandArgs& c0, const WeightArgs& w, const 
     PrepArgs a{};
     a.c = c0; a.w = w; a.o = o;
     const Geom& g = c0.g;
-    int waves = (g.rw + CB_WOUT(c0.radius) - 1) / CB_WOUT(c0.radius);
+    const BandShape sh = conf_band_shape(g, c0.radius);
+    int waves = sh.waves;
     if (waves < prep::WS_NT / 64) waves = prep::WS_NT / 64;
     if (waves < NT / 64) waves = NT / 64;                  // (the fill role works in blocks of NT threads)
     // short bands and few rows per weight block: every role is walked row by row, a barrier per row
     // (as short as the halo allows while that still leaves no more than about one band per CU, and about two weight
     // blocks per CU: beyond that the roles only queue behind each other)
-    int rpb = 2 * c0.radius > 4 ? 2 * c0.radius : 4;
     const int rows_all = g.rh * n_pairs;
-    if (rpb < (rows_all + 255) / 256) rpb = (rows_all + 255) / 256;
-    if (rpb > CB_MAX_BAND_ROWS) rpb = CB_MAX_BAND_ROWS;
-    if (rpb > g.rh) rpb = g.rh;
+    const int rpb = conf_band_clamp_rows((rows_all + 255) / 256, g.rh, c0.radius);
     a.c.rows_per_band = rpb;
     a.nC = (g.rh + rpb - 1) / rpb;
     a.nWx = (g.rw + prep::WS_BCOLS - 1) / prep::WS_BCOLS;
@@ -1068,37 +1077,24 @@ hipError_t launch_prep_small(const ConfBandArgs& c0, const WeightArgs& w, const 
     const size_t npix = (size_t)(g.H - g.rh) * g.W;
     const int nOB = (int)((npix + (size_t)NT * OUT_ROWS - 1) / ((size_t)NT * OUT_ROWS));
     const dim3 grid(a.nC + a.nW + a.nOA + nOB, n_pairs), block(64 * waves);
-    const size_t lds = conf_band_lds(g.rw, c0.radius);
-    if (lds + sizeof(prep::WsShared<3>) > 150 * 1024) return hipErrorInvalidValue;
-#define ADF_PS(CC, RR)                                                                                     \
-    case RR:                                                                                               \
-        if (lds > 32 * 1024) {                                                                             \
-            hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(prep_small_kernel<CC, RR>),   \
-                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);      \
-            if (e != hipSuccess) return e;                                                                 \
-        }                                                                                                  \
-        hipLaunchKernelGGL((prep_small_kernel<CC, RR>), grid, block, lds, st, a);                          \
-        break;
-    if (w.ch == 1) { switch (c0.radius) { ADF_PS(1, 1) ADF_PS(1, 2) ADF_PS(1, 3) ADF_PS(1, 4) ADF_PS(1, 5) } }
-    else { switch (c0.radius) { ADF_PS(3, 1) ADF_PS(3, 2) ADF_PS(3, 3) ADF_PS(3, 4) ADF_PS(3, 5) } }
-#undef ADF_PS
+    if (sh.lds + sizeof(prep::WsShared<3>) > 150 * 1024) return hipErrorInvalidValue;
+    const auto k = dispatch_radius<1, 5>(c0.radius, [&](auto R) {
+        return w.ch == 1 ? &prep_small_kernel<1, decltype(R)::value> : &prep_small_kernel<3, decltype(R)::value>;
+    });
+    if (!k) return hipErrorInvalidValue;
+    hipError_t e = ensure_dynamic_lds(k, sh.lds, 32 * 1024);   // (lower than elsewhere: the kernel's static WsShared counts too)
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(k, grid, block, sh.lds, st, a);
     return hipGetLastError();
 }
 
 hipError_t launch_conf_left(const ConfLeftArgs& a, int n_pairs, hipStream_t st)
 {
     if (a.radius < 0 || a.radius > 8) return hipErrorInvalidValue;
-    const bool wu = a.U0 != nullptr;
-    dim3 grid(1, 1, n_pairs);
-#define ADF_CL(RR)                                                                             \
-    case RR:                                                                                   \
-        grid.x = (a.g.rw + (NT - 2 * RR) - 1) / (NT - 2 * RR);                                 \
-        grid.y = row_blocks(a.g.rh, grid.x * grid.z);                                          \
-        if (wu) hipLaunchKernelGGL((conf_left_kernel<RR, true>), grid, dim3(NT), 0, st, a);    \
-        else hipLaunchKernelGGL((conf_left_kernel<RR, false>), grid, dim3(NT), 0, st, a);      \
-        break;
-    switch (a.radius) { ADF_CL(0) ADF_CL(1) ADF_CL(2) ADF_CL(3) ADF_CL(4) ADF_CL(5) ADF_CL(6) ADF_CL(7) ADF_CL(8) }
-#undef ADF_CL
+    const auto k = dispatch_radius<0, 8>(a.radius, [&](auto R) {   // with or without the right-hand sides (WRITE_U)
+        return a.U0 ? &conf_left_kernel<decltype(R)::value, true> : &conf_left_kernel<decltype(R)::value, false>;
+    });
+    hipLaunchKernelGGL(k, col_grid(a.g.rw, a.g.rh, a.radius, n_pairs), dim3(NT), 0, st, a);
     return hipGetLastError();
 }
 
