@@ -95,12 +95,15 @@ class _Image:
             raise AdfError(_lib.ADF_ESIZE, "%s rows must be dense (channel-interleaved, unit pixel stride)" % what)
 
 
-def _out_like(img, batched, dtype_np):
-    shape = (img.n, img.h, img.w) if batched else (img.h, img.w)
+def _empty(img, shape, dtype_np):
+    """An uninitialised array where `img` lives: a tensor on its device, or a numpy array."""
     if img.device:
-        tdt = {np.int16: torch.int16, np.float32: torch.float32}[dtype_np]
-        return torch.empty(shape, dtype=tdt, device=img.keep.device)
+        return torch.empty(shape, dtype=_TORCH_DTYPE[dtype_np], device=img.keep.device)
     return np.empty(shape, dtype_np)
+
+
+def _out_like(img, batched, dtype_np):
+    return _empty(img, (img.n, img.h, img.w) if batched else (img.h, img.w), dtype_np)
 
 
 def _stream_of(img):
@@ -112,17 +115,46 @@ def _stream_of(img):
     return None
 
 
-def _handle_device(getter, handle):
-    dev = C.c_int(-1)
-    _lib.check(getter(handle, C.byref(dev)))
-    return dev.value
+def _read(fn, ctype, *args):
+    """What a C getter writes through its last argument (an int* or a double*)."""
+    v = ctype()
+    _lib.check(fn(*args, C.byref(v)))
+    return v.value
 
 
-def _check_device(getter, handle, imgs, what, dev=None):
-    """A handle's workspace lives on the device that was current when it was created (include/adf_wls.h):
+_entries = {}   # base name -> (host function, device function), resolved on first use
+
+
+def _call(name, img, args):
+    """THE host/device fork: `name`_device(*args, stream) for an image held by a CUDA tensor (torch's current stream on
+    its device), `name`_host(*args) otherwise.  Pointers go as plain integers (None = null): the prototypes in _lib.py
+    say void*, so no ctypes object is built per argument."""
+    pair = _entries.get(name)
+    if pair is None:
+        pair = _entries[name] = (getattr(_lib.lib(), name + "_host"), getattr(_lib.lib(), name + "_device"))
+    if img.device:
+        _lib.check(pair[1](*args, _stream_of(img)))
+    else:
+        _lib.check(pair[0](*args))
+
+
+class _Handle:
+    """Owns `_h`, the library's handle of a filter or a matcher: a subclass names its destroy function, and the handle
+    goes with the object."""
+    _h, _destroy = None, None
+
+    def __del__(self):
+        h, self._h = self._h, None
+        if h:
+            try:
+                getattr(_lib.lib(), self._destroy)(h)
+            except Exception:
+                pass
+
+
+def _check_device(dev, imgs, what):
+    """A handle's workspace lives on the device that was current when it was created (include/adf_wls.h), `dev`:
     tensors of another GPU would pair it with foreign pointers and a foreign stream."""
-    if dev is None:
-        dev = _handle_device(getter, handle)
     for im in imgs:
         if im is not None and im.device and im.keep.device.index != dev:
             raise AdfError(_lib.ADF_EBADARG, "%s lives on cuda:%d; tensors on cuda:%s cannot be passed to it "
@@ -137,8 +169,9 @@ class DisparityFilter:
         raise NotImplementedError
 
 
-class DisparityWLSFilter(DisparityFilter):
+class DisparityWLSFilter(_Handle, DisparityFilter):
     """Disparity map filter based on the Weighted Least Squares filter (DF.hpp:82-122)."""
+    _destroy = "adf_wls_destroy"
 
     def __init__(self, use_confidence, left_offset=0, right_offset=0, top_offset=0, bottom_offset=0,
                  min_disp=0):
@@ -147,47 +180,29 @@ class DisparityWLSFilter(DisparityFilter):
                                              right_offset, top_offset, bottom_offset, min_disp))
         self._use_confidence = bool(use_confidence)
         self._last = None  # (batched, device, example image) of the last filter call
-        self._dev = _handle_device(_lib.lib().adf_wls_get_device, self._h)   # fixed at creation
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            try:
-                _lib.lib().adf_wls_destroy(h)
-            except Exception:
-                pass
+        self._dev = _read(_lib.lib().adf_wls_get_device, C.c_int, self._h)   # fixed at creation
 
     # ---- parameters (DF.hpp:90-122) ----
-    def _getd(self, fn):
-        v = C.c_double()
-        _lib.check(fn(self._h, C.byref(v)))
-        return v.value
-
-    def _geti(self, fn):
-        v = C.c_int()
-        _lib.check(fn(self._h, C.byref(v)))
-        return v.value
-
     def getLambda(self):
-        return self._getd(_lib.lib().adf_wls_get_lambda)
+        return _read(_lib.lib().adf_wls_get_lambda, C.c_double, self._h)
 
     def setLambda(self, _lambda):
         _lib.check(_lib.lib().adf_wls_set_lambda(self._h, float(_lambda)))
 
     def getSigmaColor(self):
-        return self._getd(_lib.lib().adf_wls_get_sigma_color)
+        return _read(_lib.lib().adf_wls_get_sigma_color, C.c_double, self._h)
 
     def setSigmaColor(self, _sigma_color):
         _lib.check(_lib.lib().adf_wls_set_sigma_color(self._h, float(_sigma_color)))
 
     def getLRCthresh(self):
-        return self._geti(_lib.lib().adf_wls_get_lrc_thresh)
+        return _read(_lib.lib().adf_wls_get_lrc_thresh, C.c_int, self._h)
 
     def setLRCthresh(self, _LRC_thresh):
         _lib.check(_lib.lib().adf_wls_set_lrc_thresh(self._h, int(_LRC_thresh)))
 
     def getDepthDiscontinuityRadius(self):
-        return self._geti(_lib.lib().adf_wls_get_depth_discontinuity_radius)
+        return _read(_lib.lib().adf_wls_get_depth_discontinuity_radius, C.c_int, self._h)
 
     def setDepthDiscontinuityRadius(self, _disc_radius):
         _lib.check(_lib.lib().adf_wls_set_depth_discontinuity_radius(self._h, int(_disc_radius)))
@@ -200,14 +215,14 @@ class DisparityWLSFilter(DisparityFilter):
         _lib.check(_lib.lib().adf_wls_set_solver(self._h, int(solver)))
 
     def getSolver(self):
-        return self._geti(_lib.lib().adf_wls_get_solver)
+        return _read(_lib.lib().adf_wls_get_solver, C.c_int, self._h)
 
     def getLastSolver(self):
-        return self._geti(_lib.lib().adf_wls_get_last_solver)
+        return _read(_lib.lib().adf_wls_get_last_solver, C.c_int, self._h)
 
     def getLastPath(self):
         """PATH_* bits of the last filter call: which kernels its confidence stage took (introspection only)."""
-        return self._geti(_lib.lib().adf_wls_get_last_path)
+        return _read(_lib.lib().adf_wls_get_last_path, C.c_int, self._h)
 
     def enableProfiling(self, on=True):
         """Bracket every kernel launch with HIP events on the caller's stream (measurement hook)."""
@@ -253,15 +268,15 @@ class DisparityWLSFilter(DisparityFilter):
         if (out.n, out.h, out.w) != (gv.n, gv.h, gv.w) or out.device != dl.device:               # DF.cpp:252,282
             raise AdfError(_lib.ADF_ESIZE, "filtered_disparity_map has the wrong size or placement")
         if dl.device:
-            _check_device(None, self._h, (dl, gv, dr, out), "this DisparityWLSFilter", self._dev)
+            _check_device(self._dev, (dl, gv, dr, out), "this DisparityWLSFilter")
         roi = _as_rect(ROI)
-        # (pointers go as plain integers: the prototypes in _lib.py say void*)
         args = (self._h, dl.n,
                 dl.ptr, dl.stride, dl.pair_stride, dl.w, dl.h,
                 gv.ptr, gv.stride, gv.pair_stride, gv.c, gv.w, gv.h,
                 out.ptr, out.stride, out.pair_stride,
                 dr.ptr if dr else None, dr.stride if dr else 0, dr.pair_stride if dr else 0,
                 C.byref(roi) if roi is not None else None)
+        # (the one fork written out instead of going through _call: this call's host time is counted in microseconds)
         if dl.device:
             _lib.check(_lib.lib().adf_wls_filter_scaled_device(*args, _stream_of(dl)))
         else:
@@ -277,13 +292,8 @@ class DisparityWLSFilter(DisparityFilter):
         pairs = range(ex.n) if pair is None else [pair]
         outs = []
         for k in pairs:
-            if device:
-                o = torch.empty((ex.h, ex.w), dtype=torch.float32, device=ex.keep.device)
-                _lib.check(_lib.lib().adf_wls_get_confidence_device(self._h, k, C.c_void_p(o.data_ptr()),
-                                                                    ex.w * 4, _stream_of(ex)))
-            else:
-                o = np.empty((ex.h, ex.w), np.float32)
-                _lib.check(_lib.lib().adf_wls_get_confidence_host(self._h, k, C.c_void_p(o.ctypes.data), ex.w * 4))
+            o = _empty(ex, (ex.h, ex.w), np.float32)
+            _call("adf_wls_get_confidence", ex, (self._h, k, o.data_ptr() if device else o.ctypes.data, ex.w * 4))
             outs.append(o)
         if pair is not None or not batched:
             return outs[0]
@@ -305,85 +315,106 @@ class DisparityWLSFilter(DisparityFilter):
 # at the calib3d boundary, bit-exact against oracle/adf_oracle_bm.c); StereoSGBM.compute() is the semi-global matcher in
 # the sample's mode (csrc/sgbm_matcher.hip, bit-exact against oracle/adf_oracle_sgbm.c).
 # ---------------------------------------------------------------------------------------------
-class StereoMatcher:
+def _accessors(*names):
+    """Class decorator: cv::StereoMatcher's getX() / setX(v) pair for every attribute x in `names`."""
+    def pair(name):
+        return (lambda self: getattr(self, name)), (lambda self, v: setattr(self, name, v))
+
+    def add(cls):
+        for name in names:
+            for prefix, fn in zip(("get", "set"), pair(name)):
+                fn.__name__ = prefix + name[0].upper() + name[1:]
+                setattr(cls, fn.__name__, fn)
+        return cls
+    return add
+
+
+@_accessors("minDisparity", "numDisparities", "blockSize", "disp12MaxDiff", "speckleWindowSize", "uniquenessRatio")
+class StereoMatcher(_Handle):
+    """The parameters every matcher has, and the part of compute() both have in common.  A subclass names its C entry
+    point (`_entry`) and the channels a view may have (`_channels`), and supplies `_refuse()` (its own settings it cannot
+    run), `_prepare(imgs)` (make the handle if absent, check the device, push the parameters) and `_args(L, R, D)`."""
+    _channels = (1,)
+
     def __init__(self, minDisparity=0, numDisparities=16, blockSize=3):
         self.minDisparity, self.numDisparities, self.blockSize = minDisparity, numDisparities, blockSize
         self.disp12MaxDiff, self.speckleWindowSize, self.uniquenessRatio = -1, 0, 10
 
-    def getMinDisparity(self): return self.minDisparity
-    def setMinDisparity(self, v): self.minDisparity = v
-    def getNumDisparities(self): return self.numDisparities
-    def setNumDisparities(self, v): self.numDisparities = v
-    def getBlockSize(self): return self.blockSize
-    def setBlockSize(self, v): self.blockSize = v
-    def getDisp12MaxDiff(self): return self.disp12MaxDiff
-    def setDisp12MaxDiff(self, v): self.disp12MaxDiff = v
-    def getSpeckleWindowSize(self): return self.speckleWindowSize
-    def setSpeckleWindowSize(self, v): self.speckleWindowSize = v
-    def getUniquenessRatio(self): return self.uniquenessRatio
-    def setUniquenessRatio(self, v): self.uniquenessRatio = v
+    def _views(self, left, right, device_only=None):
+        """(L, R, batched): both views described and equal in size; `device_only`: the refusal of host arrays."""
+        nd = len(left.shape)
+        color = 3 in self._channels and nd in (3, 4) and left.shape[-1] == 3   # (H,W,3) / (N,H,W,3); a batch of 3-pixel-wide gray images is not a case
+        batched = nd == (4 if color else 3)
+        L = _Image(left, np.uint8, "left", batched, self._channels)
+        R = _Image(right, np.uint8, "right", batched, self._channels)
+        if device_only and not (L.device and R.device):
+            raise AdfError(_lib.ADF_EBADARG, device_only)
+        if (L.n, L.h, L.w, L.c) != (R.n, R.h, R.w, R.c):
+            raise AdfError(_lib.ADF_ESIZE, "All the images must have the same size")
+        return L, R, batched
+
+    @staticmethod
+    def _outputs(maps, names, L, batched, mismatch):
+        """(maps, their descriptors): the caller's maps, new ones where None, of the views' size and on their side."""
+        maps = [_out_like(L, batched, np.int16) if m is None else m for m in maps]
+        descs = [_Image(m, np.int16, what, batched) for m, what in zip(maps, names)]
+        for D in descs:
+            if (D.n, D.h, D.w) != (L.n, L.h, L.w) or D.device != L.device:
+                raise AdfError(_lib.ADF_ESIZE, mismatch)
+        return maps, descs
+
+    def compute(self, left, right, disparity=None):
+        """StereoMatcher::compute: 8-bit views (H,W) or a batch (N,H,W) -> CV_16SC1 disparity*16, rejected pixels
+        (minDisparity-1)*16.  torch CUDA tensors are matched where they are, asynchronously on torch's current stream;
+        numpy arrays take the host entry point.  The speckle filter is not built into either matcher: the filter
+        factory switches it off (DF.cpp:390)."""
+        self._refuse()
+        if self.speckleWindowSize > 0:
+            raise AdfError(_lib.ADF_EBADARG, "speckle filtering is not implemented inside compute(); "
+                                             "use filterSpeckles on the result")
+        L, R, batched = self._views(left, right)
+        if L.device != R.device:
+            raise AdfError(_lib.ADF_EBADARG, "left and right must live on the same side (host or device)")
+        (disparity,), (D,) = self._outputs((disparity,), ("disparity",), L, batched, "disparity must match the views")
+        self._prepare((L, R, D))
+        _call(self._entry, L, self._args(L, R, D))
+        return disparity
 
 
+@_accessors("textureThreshold", "preFilterCap")
 class StereoBM(StereoMatcher):
+    """cv::StereoBM's accessors plus compute() on the device (csrc/bm_matcher.hip): CV_8UC1 views.  The left-right check
+    and the speckle filter of cv::StereoBM are not implemented: the filter factory switches both off (DF.cpp:389-390)."""
+    _destroy, _entry = "adf_bm_destroy", "adf_bm_compute"
+
     def __init__(self, numDisparities=0, blockSize=21):
         super().__init__(0, numDisparities if numDisparities > 0 else 64, blockSize)   # cv::StereoBM: 0 -> 64
         self.textureThreshold, self.uniquenessRatio, self.preFilterCap = 10, 15, 31
-        self._h = None
 
     @staticmethod
     def create(numDisparities=0, blockSize=21):
         return StereoBM(numDisparities, blockSize)
 
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            try:
-                _lib.lib().adf_bm_destroy(h)
-            except Exception:
-                pass
+    def _left_right_check_on(self):
+        return 0 <= self.disp12MaxDiff < 1000000
 
-    def getTextureThreshold(self): return self.textureThreshold
-    def setTextureThreshold(self, v): self.textureThreshold = v
-    def getPreFilterCap(self): return self.preFilterCap
-    def setPreFilterCap(self, v): self.preFilterCap = v
-
-    def compute(self, left, right, disparity=None):
-        """StereoMatcher::compute: CV_8UC1 views (H,W) or a batch (N,H,W) -> CV_16SC1 disparity*16, rejected
-        pixels (minDisparity-1)*16.  torch CUDA tensors are matched where they are, asynchronously on torch's
-        current stream; numpy arrays take the host entry point.  The left-right check and the speckle filter
-        of cv::StereoBM are not implemented: the filter factory switches both off (DF.cpp:389-390)."""
-        if self.disp12MaxDiff >= 0 and self.disp12MaxDiff < 1000000:
+    def _refuse(self):
+        if self._left_right_check_on():
             raise AdfError(_lib.ADF_EBADARG, "disp12MaxDiff (left-right check inside the matcher) is not implemented")
-        if self.speckleWindowSize > 0:
-            raise AdfError(_lib.ADF_EBADARG, "speckle filtering is not implemented inside compute(); "
-                                             "use filterSpeckles on the result")
-        batched = len(left.shape) == 3
-        L = _Image(left, np.uint8, "left", batched)
-        R = _Image(right, np.uint8, "right", batched)
-        if (L.n, L.h, L.w) != (R.n, R.h, R.w):
-            raise AdfError(_lib.ADF_ESIZE, "All the images must have the same size")
-        if L.device != R.device:
-            raise AdfError(_lib.ADF_EBADARG, "left and right must live on the same side (host or device)")
-        if disparity is None:
-            disparity = _out_like(L, batched, np.int16)
-        D = _Image(disparity, np.int16, "disparity", batched)
-        if (D.n, D.h, D.w) != (L.n, L.h, L.w) or D.device != L.device:
-            raise AdfError(_lib.ADF_ESIZE, "disparity must match the views")
+
+    def _prepare(self, imgs):
         lib = _lib.lib()
         if self._h is None:
             h = C.c_void_p()
             _lib.check(lib.adf_bm_create(C.byref(h), int(self.numDisparities), int(self.blockSize)))
             self._h = h
-        _check_device(lib.adf_bm_get_device, self._h, [L, R, D], "this StereoBM")
+        _check_device(_read(lib.adf_bm_get_device, C.c_int, self._h), imgs, "this StereoBM")
         _lib.check(lib.adf_bm_set_params(self._h, int(self.minDisparity), int(self.numDisparities), int(self.blockSize),
                                          int(self.preFilterCap), int(self.textureThreshold), int(self.uniquenessRatio)))
-        args = [self._h, L.n, C.c_void_p(L.ptr), L.stride, L.pair_stride, C.c_void_p(R.ptr), R.stride, R.pair_stride,
-                L.w, L.h, C.c_void_p(D.ptr), D.stride, D.pair_stride]
-        if L.device:
-            _lib.check(lib.adf_bm_compute_device(*args, _stream_of(L)))
-        else:
-            _lib.check(lib.adf_bm_compute_host(*args))
-        return disparity
+
+    def _args(self, L, R, D):
+        return (self._h, L.n, L.ptr, L.stride, L.pair_stride, R.ptr, R.stride, R.pair_stride, L.w, L.h,
+                D.ptr, D.stride, D.pair_stride)
 
     def computeBoth(self, left, right, disparity_left=None, disparity_right=None):
         """Extension: this matcher's map AND the map of createRightMatcher(self) (DF.cpp:417-431) from one launch --
@@ -393,24 +424,11 @@ class StereoBM(StereoMatcher):
         The reference's right matcher keeps cv::StereoBM's default preFilterCap of 31 (DF.cpp:421-431 copy every
         parameter BUT the cap), so one shared prefilter is only the same computation when this matcher's cap is 31
         too; with any other cap the two maps are produced by the two separate computes (same results, two launches)."""
-        batched = len(left.shape) == 3
-        L = _Image(left, np.uint8, "left", batched)
-        R = _Image(right, np.uint8, "right", batched)
-        if not (L.device and R.device):
-            raise AdfError(_lib.ADF_EBADARG, "computeBoth takes device tensors; use two compute() calls on the host")
-        if (L.n, L.h, L.w) != (R.n, R.h, R.w):
-            raise AdfError(_lib.ADF_ESIZE, "All the images must have the same size")
-        if (self.disp12MaxDiff >= 0 and self.disp12MaxDiff < 1000000) or self.speckleWindowSize > 0:
+        L, R, batched = self._views(left, right, "computeBoth takes device tensors; use two compute() calls on the host")
+        if self._left_right_check_on() or self.speckleWindowSize > 0:
             raise AdfError(_lib.ADF_EBADARG, "the matcher's own left-right check and speckle filter are not implemented")
-        if disparity_left is None:
-            disparity_left = _out_like(L, batched, np.int16)
-        if disparity_right is None:
-            disparity_right = _out_like(L, batched, np.int16)
-        DL = _Image(disparity_left, np.int16, "disparity_left", batched)
-        DR = _Image(disparity_right, np.int16, "disparity_right", batched)
-        for D in (DL, DR):
-            if (D.n, D.h, D.w) != (L.n, L.h, L.w) or not D.device:
-                raise AdfError(_lib.ADF_ESIZE, "disparity maps must match the views")
+        (disparity_left, disparity_right), (DL, DR) = self._outputs(
+            (disparity_left, disparity_right), ("disparity_left", "disparity_right"), L, batched, "disparity maps must match the views")
         if self.preFilterCap != 31:
             if getattr(self, "_right", None) is None:
                 self._right = StereoBM(1, 5)
@@ -421,32 +439,26 @@ class StereoBM(StereoMatcher):
             self.compute(left, right, disparity_left)
             self._right.compute(right, left, disparity_right)
             return disparity_left, disparity_right
-        lib = _lib.lib()
-        if self._h is None:
-            h = C.c_void_p()
-            _lib.check(lib.adf_bm_create(C.byref(h), int(self.numDisparities), int(self.blockSize)))
-            self._h = h
-        _check_device(lib.adf_bm_get_device, self._h, [L, R, DL, DR], "this StereoBM")
-        _lib.check(lib.adf_bm_set_params(self._h, int(self.minDisparity), int(self.numDisparities), int(self.blockSize),
-                                         int(self.preFilterCap), int(self.textureThreshold), int(self.uniquenessRatio)))
-        _lib.check(lib.adf_bm_compute_both_device(
-            self._h, L.n, C.c_void_p(L.ptr), L.stride, L.pair_stride, C.c_void_p(R.ptr), R.stride, R.pair_stride, L.w, L.h,
-            C.c_void_p(DL.ptr), DL.stride, DL.pair_stride, C.c_void_p(DR.ptr), DR.stride, DR.pair_stride, _stream_of(L)))
+        self._prepare((L, R, DL, DR))
+        _lib.check(_lib.lib().adf_bm_compute_both_device(*self._args(L, R, DL), DR.ptr, DR.stride, DR.pair_stride, _stream_of(L)))
         return disparity_left, disparity_right
 
 
+@_accessors("P1", "P2", "mode", "preFilterCap")
 class StereoSGBM(StereoMatcher):
     """cv::StereoSGBM's accessors plus compute() on the device (csrc/sgbm_matcher.hip): the published semi-global
     algorithm with three paths (MODE_SGBM_3WAY, the mode the reference's sample selects:
     samples/disparity_filtering.cpp:166-176), five (MODE_SGBM) or eight (MODE_HH), bit-exact against
-    oracle/adf_oracle_sgbm.c; parity unpinned at calib3d."""
+    oracle/adf_oracle_sgbm.c; parity unpinned at calib3d.  compute() takes CV_8UC1 / CV_8UC3 views (H,W[,3]) or a batch
+    (N,H,W[,3]) and runs the matcher's own left-right check (disp12MaxDiff; create's default 0 reads as 1, the filter
+    factory switches it off with 1000000, DF.cpp:389); the speckle filter is not built (DF.cpp:390 sets it to 0)."""
     MODE_SGBM, MODE_HH, MODE_SGBM_3WAY = 0, 1, 2
+    _destroy, _entry, _channels = "adf_sgbm_destroy", "adf_sgbm_compute", (1, 3)
 
     def __init__(self, minDisparity=0, numDisparities=16, blockSize=3, P1=0, P2=0, mode=0, preFilterCap=0):
         super().__init__(minDisparity, numDisparities, blockSize)
         self.P1, self.P2, self.mode, self.preFilterCap = P1, P2, mode, preFilterCap
         self.disp12MaxDiff, self.uniquenessRatio = 0, 0     # cv::StereoSGBM::create's defaults (the filter factory raises disp12MaxDiff to 1000000)
-        self._h = None
 
     @staticmethod
     def create(minDisparity=0, numDisparities=16, blockSize=3, P1=0, P2=0, disp12MaxDiff=0, preFilterCap=0,
@@ -455,65 +467,25 @@ class StereoSGBM(StereoMatcher):
         m.disp12MaxDiff, m.uniquenessRatio, m.speckleWindowSize = disp12MaxDiff, uniquenessRatio, speckleWindowSize
         return m
 
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            try:
-                _lib.lib().adf_sgbm_destroy(h)
-            except Exception:
-                pass
-
-    def getP1(self): return self.P1
-    def setP1(self, v): self.P1 = v
-    def getP2(self): return self.P2
-    def setP2(self, v): self.P2 = v
-    def getMode(self): return self.mode
-    def setMode(self, v): self.mode = v
-    def getPreFilterCap(self): return self.preFilterCap
-    def setPreFilterCap(self, v): self.preFilterCap = v
-
-    def compute(self, left, right, disparity=None):
-        """StereoMatcher::compute: CV_8UC1 / CV_8UC3 views (H,W[,3]) or a batch (N,H,W[,3]) -> CV_16SC1 disparity*16,
-        invalid pixels (minDisparity-1)*16.  torch CUDA tensors are matched where they are, asynchronously on torch's
-        current stream; numpy arrays take the host entry point.  MODE_SGBM_3WAY (3 paths, the sample's), MODE_SGBM (5)
-        and MODE_HH (8), the matcher's own left-right check (disp12MaxDiff; create's default 0 reads as 1, the filter
-        factory switches it off with 1000000, DF.cpp:389); the speckle filter is not built (DF.cpp:390 sets it to 0)."""
+    def _refuse(self):
         if self.mode not in (StereoSGBM.MODE_SGBM, StereoSGBM.MODE_HH, StereoSGBM.MODE_SGBM_3WAY):
             raise AdfError(_lib.ADF_EBADARG, "mode must be StereoSGBM.MODE_SGBM, MODE_HH or MODE_SGBM_3WAY")
-        if self.speckleWindowSize > 0:
-            raise AdfError(_lib.ADF_EBADARG, "speckle filtering is not implemented inside compute(); "
-                                             "use filterSpeckles on the result")
-        nd = len(left.shape)
-        color = nd in (3, 4) and left.shape[-1] == 3      # (H,W,3) / (N,H,W,3); a batch of 3-pixel-wide gray images is not a case
-        batched = nd == (4 if color else 3)
-        L = _Image(left, np.uint8, "left", batched, allow_channels=(1, 3))
-        R = _Image(right, np.uint8, "right", batched, allow_channels=(1, 3))
-        if (L.n, L.h, L.w, L.c) != (R.n, R.h, R.w, R.c):
-            raise AdfError(_lib.ADF_ESIZE, "All the images must have the same size")
-        if L.device != R.device:
-            raise AdfError(_lib.ADF_EBADARG, "left and right must live on the same side (host or device)")
-        if disparity is None:
-            disparity = _out_like(L, batched, np.int16)
-        D = _Image(disparity, np.int16, "disparity", batched)
-        if (D.n, D.h, D.w) != (L.n, L.h, L.w) or D.device != L.device:
-            raise AdfError(_lib.ADF_ESIZE, "disparity must match the views")
+
+    def _prepare(self, imgs):
         lib = _lib.lib()
         if self._h is None:
             h = C.c_void_p()
             _lib.check(lib.adf_sgbm_create(C.byref(h), int(self.minDisparity), int(self.numDisparities), int(self.blockSize)))
             self._h = h
-        _check_device(lib.adf_sgbm_get_device, self._h, [L, R, D], "this StereoSGBM")
+        _check_device(_read(lib.adf_sgbm_get_device, C.c_int, self._h), imgs, "this StereoSGBM")
         _lib.check(lib.adf_sgbm_set_params(self._h, int(self.minDisparity), int(self.numDisparities), int(self.blockSize),
                                            int(self.P1), int(self.P2), int(self.preFilterCap), int(self.uniquenessRatio),
                                            int(self.mode)))
         _lib.check(lib.adf_sgbm_set_disp12_max_diff(self._h, int(self.disp12MaxDiff)))
-        args = [self._h, L.n, C.c_void_p(L.ptr), L.stride, L.pair_stride, C.c_void_p(R.ptr), R.stride, R.pair_stride,
-                L.c, L.w, L.h, C.c_void_p(D.ptr), D.stride, D.pair_stride]
-        if L.device:
-            _lib.check(lib.adf_sgbm_compute_device(*args, _stream_of(L)))
-        else:
-            _lib.check(lib.adf_sgbm_compute_host(*args))
-        return disparity
+
+    def _args(self, L, R, D):
+        return (self._h, L.n, L.ptr, L.stride, L.pair_stride, R.ptr, R.stride, R.pair_stride, L.c, L.w, L.h,
+                D.ptr, D.stride, D.pair_stride)
 
 
 _INT32_MAX = 2 ** 31 - 1
@@ -550,10 +522,9 @@ def filterSpeckles(img, newVal, maxSpeckleSize, maxDiff, buf=None):
         raise AdfError(_lib.ADF_EBADARG, "newVal %r is outside the CV_16S range" % (newVal,))
     md = max(-_INT32_MAX, min(_INT32_MAX, _round_half_even(maxDiff, "maxDiff")))   # (|diff| <= 65535 either way)
     ms = max(-_INT32_MAX, min(_INT32_MAX, int(maxSpeckleSize)))                     # (W*H < 2^31 either way)
-    lib = _lib.lib()
-    args = [im.n, C.c_void_p(im.ptr), im.stride, im.pair_stride, im.w, im.h, nv, ms, md]
+    args = (im.n, im.ptr, im.stride, im.pair_stride, im.w, im.h, nv, ms, md)
     if not im.device:
-        _lib.check(lib.adf_filter_speckles_host(*args))
+        _call("adf_filter_speckles", im, args)
         return img, buf
     ws, ws_bytes = None, 0
     if buf is not None:
@@ -561,11 +532,11 @@ def filterSpeckles(img, newVal, maxSpeckleSize, maxDiff, buf=None):
             raise AdfError(_lib.ADF_EBADARG, "buf must be a contiguous CUDA tensor (or None)")
         if buf.device != img.device:
             raise AdfError(_lib.ADF_EBADARG, "buf lives on %s, img on %s" % (buf.device, img.device))
-        ws, ws_bytes = C.c_void_p(buf.data_ptr()), buf.numel() * buf.element_size()
+        ws, ws_bytes = buf.data_ptr(), buf.numel() * buf.element_size()
         if ws_bytes < speckleWorkspaceBytes(im.n, im.h, im.w):
             raise AdfError(_lib.ADF_ESIZE, "buf holds %d bytes; %d needed" % (ws_bytes, speckleWorkspaceBytes(im.n, im.h, im.w)))
     with torch.cuda.device(img.device):
-        _lib.check(lib.adf_filter_speckles_device(*args, ws, ws_bytes, _stream_of(im)))
+        _call("adf_filter_speckles", im, args + (ws, ws_bytes))
     return img, buf
 
 
@@ -584,9 +555,7 @@ INTER_LINEAR = 1        # cv::INTER_LINEAR
 
 def halfSize(n):
     """cvRound(n * 0.5), half to even (adf_half_size): the size cv::resize(.., 0.5, 0.5) gives an axis of n pixels."""
-    v = C.c_int()
-    _lib.check(_lib.lib().adf_half_size(int(n), C.byref(v)))
-    return v.value
+    return _read(_lib.lib().adf_half_size, C.c_int, int(n))
 
 
 def _view_image(src, what):
@@ -615,21 +584,20 @@ def _prepare_views(im, batched, half, dst_channels, dst, what):
     unit = im.unit_axis and dst_channels == 1                    # (N,H,W,1) in, (N,h,w,1) out
     shape = ((im.n,) if batched else ()) + (h, w) + ((3,) if dst_channels == 3 else (1,) if unit else ())
     if dst is None:
-        dst = torch.empty(shape, dtype=torch.uint8, device=im.keep.device) if im.device else np.empty(shape, np.uint8)
+        dst = _empty(im, shape, np.uint8)
     if tuple(dst.shape) != shape:
         raise AdfError(_lib.ADF_ESIZE, "%s: dst must have shape %s" % (what, shape))
     D = _Image(dst[..., 0] if unit else dst, np.uint8, "dst", batched, allow_channels=(dst_channels,))
     if (D.n, D.h, D.w) != (im.n, h, w) or D.device != im.device:
         raise AdfError(_lib.ADF_ESIZE, "%s: dst must have shape %s on the side (host or device) of src" % (what, shape))
-    args = [im.n, C.c_void_p(im.ptr), im.stride, im.pair_stride, im.w, im.h, im.c,
-            C.c_void_p(D.ptr), D.stride, D.pair_stride, w, h, dst_channels]
+    args = (im.n, im.ptr, im.stride, im.pair_stride, im.w, im.h, im.c, D.ptr, D.stride, D.pair_stride, w, h, dst_channels)
     if not im.device:
-        _lib.check(_lib.lib().adf_prepare_views_host(*args))
+        _call("adf_prepare_views", im, args)
         return dst
     if dst.device != im.keep.device:
         raise AdfError(_lib.ADF_EBADARG, "dst lives on %s, src on %s" % (dst.device, im.keep.device))
     with torch.cuda.device(im.keep.device):
-        _lib.check(_lib.lib().adf_prepare_views_device(*args, _stream_of(im)))
+        _call("adf_prepare_views", im, args)
     return dst
 
 
@@ -736,101 +704,79 @@ def createDisparityWLSFilterGeneric(use_confidence):
 # ---------------------------------------------------------------------------------------------
 # Fast Global Smoother (EF.hpp:361-413)
 # ---------------------------------------------------------------------------------------------
-class FastGlobalSmootherFilter:
+_DEPTH = {np.uint8: _lib.DEPTH_8U, np.int16: _lib.DEPTH_16S, np.float32: _lib.DEPTH_32F}
+_NUMPY_DTYPE = {**{t: n for n, t in _TORCH_DTYPE.items()}, **{np.dtype(n): n for n in _ITEMSIZE}}
+
+
+class _Dense:
+    """An array the smoother makes dense itself, as _call, _check_device and _stream_of see an image: `device`, `keep`
+    and `ptr`, plus `dtype`, the numpy type of its elements (None: none the library takes).  A CUDA tensor stays where it
+    is, anything else becomes a numpy array; a strided one is copied.  Rows are then shape[1] * channels elements apart
+    whatever stride a one-element axis reports, so the pitch comes from the shape and no stride is read."""
+
+    def __init__(self, a):
+        self.device = _is_torch(a) and a.is_cuda
+        self.keep = a = a.contiguous() if self.device else np.ascontiguousarray(a)
+        self.ptr = a.data_ptr() if self.device else a.ctypes.data
+        self.dtype = _NUMPY_DTYPE.get(a.dtype)
+
+
+class FastGlobalSmootherFilter(_Handle):
+    _destroy = "adf_fgs_destroy"
+
     def __init__(self, guide, lambda_, sigma_color, lambda_attenuation=0.25, num_iter=3, solver=SOLVER_WAVE):
         self._h = C.c_void_p()
-        if _is_torch(guide) and guide.is_cuda:
+        device = _is_torch(guide) and guide.is_cuda
+        if guide is None or (guide.numel() if device else getattr(guide, "size", 0)) == 0:
+            raise AdfError(_lib.ADF_EBADARG, "guide is empty")  # FGS.cpp:143
+        im = _Dense(guide)
+        g = im.keep
+        if im.dtype is not np.uint8 or len(g.shape) not in (2, 3) or (len(g.shape) == 3 and g.shape[2] not in (1, 3)):
+            raise AdfError(_lib.ADF_EBADARG, "guide must be CV_8UC1 or CV_8UC3")  # FGS.cpp:144
+        ch = 1 if len(g.shape) == 2 else g.shape[2]
+        self._shape = tuple(g.shape[:2])
+        args = (C.byref(self._h), im.ptr, g.shape[1] * ch, ch, g.shape[1], g.shape[0], float(lambda_), float(sigma_color),
+                float(lambda_attenuation), int(num_iter), int(solver))
+        if device:
             # the guide already lives in HBM (a device pipeline, e.g. sparse_match_interpolators.cpp:202-203):
             # adf_fgs_create_device, asynchronous on torch's current stream, nothing crosses PCIe
-            if guide.numel() == 0:
-                raise AdfError(_lib.ADF_EBADARG, "guide is empty")  # FGS.cpp:143
-            if guide.dtype != torch.uint8 or guide.dim() not in (2, 3) or (guide.dim() == 3 and guide.shape[2] not in (1, 3)):
-                raise AdfError(_lib.ADF_EBADARG, "guide must be CV_8UC1 or CV_8UC3")  # FGS.cpp:144
-            gt = guide.contiguous()
-            ch = 1 if gt.dim() == 2 else gt.shape[2]
-            self._shape = tuple(gt.shape[:2])
-            with torch.cuda.device(gt.device):
-                st = C.c_void_p(torch.cuda.current_stream(gt.device).cuda_stream)
-                _lib.check(_lib.lib().adf_fgs_create_device(C.byref(self._h), C.c_void_p(gt.data_ptr()), gt.shape[1] * ch,
-                                                            ch, gt.shape[1], gt.shape[0], float(lambda_), float(sigma_color),
-                                                            float(lambda_attenuation), int(num_iter), int(solver), st))
-            self._guide_keep = gt      # the copy into the handle is queued on the stream: keep the source alive
-            return
-        if guide is None or getattr(guide, "size", 0) == 0:
-            raise AdfError(_lib.ADF_EBADARG, "guide is empty")  # FGS.cpp:143
-        g = np.ascontiguousarray(guide)
-        if g.dtype != np.uint8 or g.ndim not in (2, 3) or (g.ndim == 3 and g.shape[2] not in (1, 3)):
-            raise AdfError(_lib.ADF_EBADARG, "guide must be CV_8UC1 or CV_8UC3")  # FGS.cpp:144
-        ch = 1 if g.ndim == 2 else g.shape[2]
-        self._shape = g.shape[:2]
-        _lib.check(_lib.lib().adf_fgs_create(C.byref(self._h), C.c_void_p(g.ctypes.data), g.shape[1] * ch, ch,
-                                             g.shape[1], g.shape[0], float(lambda_), float(sigma_color),
-                                             float(lambda_attenuation), int(num_iter), int(solver)))
-
-    def __del__(self):
-        h, self._h = getattr(self, "_h", None), None
-        if h:
-            try:
-                _lib.lib().adf_fgs_destroy(h)
-            except Exception:
-                pass
+            with torch.cuda.device(g.device):
+                _lib.check(_lib.lib().adf_fgs_create_device(*args, _stream_of(im)))
+            self._guide_keep = g       # the copy into the handle is queued on the stream: keep the source alive
+        else:
+            _lib.check(_lib.lib().adf_fgs_create(*args))
 
     def getSolver(self):
         """The solver this filter runs: SOLVER_WAVE only if it was asked for and the guide fits it (library extension)."""
-        v = C.c_int(-1)
-        _lib.check(_lib.lib().adf_fgs_get_solver(self._h, C.byref(v)))
-        return v.value
+        return _read(_lib.lib().adf_fgs_get_solver, C.c_int, self._h)
 
     def filter(self, src, dst=None):
         """EF.hpp:370, FGS.cpp:182-233.  A torch CUDA tensor is filtered where it is (asynchronously on
         torch's current stream) and a CUDA tensor is returned; anything else takes the host path."""
-        if _is_torch(src) and src.is_cuda:
-            return self._filter_device(src, dst)
-        s = np.ascontiguousarray(src)
-        depth = {np.dtype(np.uint8): _lib.DEPTH_8U, np.dtype(np.int16): _lib.DEPTH_16S,
-                 np.dtype(np.float32): _lib.DEPTH_32F}.get(s.dtype)
-        if depth is None or s.ndim not in (2, 3):
+        S = _Dense(src)
+        s, dtype, device = S.keep, S.dtype, S.device
+        if dtype not in _DEPTH or len(s.shape) not in (2, 3):
             raise AdfError(_lib.ADF_EBADARG, "src depth must be CV_8U, CV_16S or CV_32F")  # FGS.cpp:184
-        cn = 1 if s.ndim == 2 else s.shape[2]
+        cn = 1 if len(s.shape) == 2 else s.shape[2]
         if cn > 4:
             raise AdfError(_lib.ADF_EBADARG, "src must have at most 4 channels")
-        if s.shape[:2] != self._shape:
+        if tuple(s.shape[:2]) != self._shape:
             raise AdfError(_lib.ADF_ESIZE,
                            "Size of the filtered image must be equal to the size of the guide image")  # FGS.cpp:187
         if dst is None:
-            dst = np.empty_like(s)
-        elif not (isinstance(dst, np.ndarray) and dst.flags["C_CONTIGUOUS"] and dst.shape == s.shape and dst.dtype == s.dtype):
+            dst = torch.empty_like(s) if device else np.empty_like(s)
+        else:
             # the library writes h rows of w*cn elements at a dense stride: anything else would be overrun
-            raise AdfError(_lib.ADF_ESIZE, "dst must be a C-contiguous ndarray with src's shape and dtype")
-        rowb = s.shape[1] * cn * s.itemsize
-        _lib.check(_lib.lib().adf_fgs_filter_host(self._h, C.c_void_p(s.ctypes.data), rowb,
-                                                  C.c_void_p(dst.ctypes.data), rowb, depth, cn))
-        return dst
-
-
-    def _filter_device(self, src, dst):
-        depth = {torch.uint8: _lib.DEPTH_8U, torch.int16: _lib.DEPTH_16S, torch.float32: _lib.DEPTH_32F}.get(src.dtype)
-        if depth is None or src.dim() not in (2, 3):
-            raise AdfError(_lib.ADF_EBADARG, "src depth must be CV_8U, CV_16S or CV_32F")  # FGS.cpp:184
-        s = src.contiguous()
-        cn = 1 if s.dim() == 2 else s.shape[2]
-        if cn > 4:
-            raise AdfError(_lib.ADF_EBADARG, "src must have at most 4 channels")
-        if tuple(s.shape[:2]) != tuple(self._shape):
-            raise AdfError(_lib.ADF_ESIZE,
-                           "Size of the filtered image must be equal to the size of the guide image")  # FGS.cpp:187
-        if dst is None:
-            dst = torch.empty_like(s)
-        elif not (_is_torch(dst) and dst.is_cuda and dst.is_contiguous() and dst.shape == s.shape and dst.dtype == s.dtype):
-            raise AdfError(_lib.ADF_EBADARG, "dst must be a contiguous CUDA tensor shaped like src")
-        rowb = s.shape[1] * cn * s.element_size()
-        dev = C.c_int(-1)
-        _lib.check(_lib.lib().adf_fgs_get_device(self._h, C.byref(dev)))
-        if s.device.index != dev.value or dst.device.index != dev.value:
-            raise AdfError(_lib.ADF_EBADARG, "this FastGlobalSmootherFilter lives on cuda:%d" % dev.value)
-        st = C.c_void_p(torch.cuda.current_stream(s.device).cuda_stream)
-        _lib.check(_lib.lib().adf_fgs_filter_device(self._h, C.c_void_p(s.data_ptr()), rowb,
-                                                    C.c_void_p(dst.data_ptr()), rowb, depth, cn, st))
+            dense = (_is_torch(dst) and dst.is_cuda and dst.is_contiguous()) if device else \
+                    (isinstance(dst, np.ndarray) and dst.flags["C_CONTIGUOUS"])
+            if not (dense and dst.shape == s.shape and dst.dtype == s.dtype):
+                if device:
+                    raise AdfError(_lib.ADF_EBADARG, "dst must be a contiguous CUDA tensor shaped like src")
+                raise AdfError(_lib.ADF_ESIZE, "dst must be a C-contiguous ndarray with src's shape and dtype")
+        D, rowb = _Dense(dst), s.shape[1] * cn * _ITEMSIZE[dtype]
+        if device:
+            _check_device(_read(_lib.lib().adf_fgs_get_device, C.c_int, self._h), (S, D), "this FastGlobalSmootherFilter")
+        _call("adf_fgs_filter", S, (self._h, S.ptr, rowb, D.ptr, rowb, _DEPTH[dtype], cn))
         return dst
 
 
@@ -868,7 +814,7 @@ def readGT(src_path):
         im.load()
     except Exception:
         return 1, np.zeros((0, 0), np.int16)
-    if im.mode in ("RGB", "RGBA") and im.mode == "RGB":
+    if im.mode == "RGB":
         a = np.asarray(im, np.int32)                       # PIL is RGB; the reference indexes BGR val[2]=R, val[1]=G
         return 0, (64 * a[:, :, 0] + a[:, :, 1] // 4).astype(np.int16)
     if im.mode == "L":
@@ -877,53 +823,36 @@ def readGT(src_path):
     return 1, np.zeros((im.size[1], im.size[0]), np.int16)
 
 
-def _eval_pair(GT, src, ROI):
+def _evaluate(name, GT, src, ROI, *thresh):
+    """One of the two error measures: `name`_host / _device(GT, src, size, ROI, [thresh,] &result)."""
     g = _Image(GT, np.int16, "GT", False)
     s = _Image(src, np.int16, "src", False)
     if (g.h, g.w) != (s.h, s.w):
         raise AdfError(_lib.ADF_ESIZE, "GT and src differ in size")   # DF.cpp:501
     if g.device != s.device:
         raise AdfError(_lib.ADF_EBADARG, "GT and src must both be numpy arrays or both be CUDA tensors")
-    return g, s, _as_rect(ROI)
+    roi, out = _as_rect(ROI), C.c_double()
+    _call(name, g, (g.ptr, g.stride, s.ptr, s.stride, g.w, g.h, C.byref(roi) if roi is not None else None, *[int(t) for t in thresh], C.byref(out)))
+    return out.value
 
 
 def computeMSE(GT, src, ROI=None):
     """DF.hpp:176, DF.cpp:497-517."""
-    g, s, roi = _eval_pair(GT, src, ROI)
-    out = C.c_double()
-    args = [C.c_void_p(g.ptr), g.stride, C.c_void_p(s.ptr), s.stride, g.w, g.h,
-            C.byref(roi) if roi is not None else None, C.byref(out)]
-    if g.device:
-        _lib.check(_lib.lib().adf_compute_mse_device(*args, _stream_of(g)))
-    else:
-        _lib.check(_lib.lib().adf_compute_mse_host(*args))
-    return out.value
+    return _evaluate("adf_compute_mse", GT, src, ROI)
 
 
 def computeBadPixelPercent(GT, src, ROI=None, thresh=24):
     """DF.hpp:190, DF.cpp:519-539."""
-    g, s, roi = _eval_pair(GT, src, ROI)
-    out = C.c_double()
-    args = [C.c_void_p(g.ptr), g.stride, C.c_void_p(s.ptr), s.stride, g.w, g.h,
-            C.byref(roi) if roi is not None else None, int(thresh), C.byref(out)]
-    if g.device:
-        _lib.check(_lib.lib().adf_compute_bad_pixel_percent_device(*args, _stream_of(g)))
-    else:
-        _lib.check(_lib.lib().adf_compute_bad_pixel_percent_host(*args))
-    return out.value
+    return _evaluate("adf_compute_bad_pixel_percent", GT, src, ROI, thresh)
 
 
 def getDisparityVis(src, dst=None, scale=1.0):
     """DF.hpp:202, DF.cpp:541-556."""
     s = _Image(src, np.int16, "src", False)
     if dst is None:
-        dst = torch.empty((s.h, s.w), dtype=torch.uint8, device=s.keep.device) if s.device else np.empty((s.h, s.w), np.uint8)
+        dst = _empty(s, (s.h, s.w), np.uint8)
     d = _Image(dst, np.uint8, "dst", False)
     if (d.h, d.w) != (s.h, s.w) or d.device != s.device:
         raise AdfError(_lib.ADF_ESIZE, "dst has the wrong size or placement")
-    args = [C.c_void_p(s.ptr), s.stride, C.c_void_p(d.ptr), d.stride, s.w, s.h, float(scale)]
-    if s.device:
-        _lib.check(_lib.lib().adf_get_disparity_vis_device(*args, _stream_of(s)))
-    else:
-        _lib.check(_lib.lib().adf_get_disparity_vis_host(*args))
+    _call("adf_get_disparity_vis", s, (s.ptr, s.stride, d.ptr, d.stride, s.w, s.h, float(scale)))
     return dst
