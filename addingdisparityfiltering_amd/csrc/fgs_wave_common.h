@@ -39,21 +39,48 @@
 #pragma once
 #include "adf_internal.h"
 
+#include <type_traits>
+
 namespace adf {
 namespace wave {
 
+// ---------------------------------------------------------------------------------------------
+// Element type T of the chunk templates: float in the row pass (a lane owns one chunk), v2f in the column pass (a
+// thread owns the same rows of two adjacent columns).  On 2-vectors the sweeps compile to the packed fp32 instructions
+// (v_pk_fma_f32, v_pk_mul_f32, v_pk_add_f32: two lanes of work per issue slot), and the register pair an 8-byte load
+// fills is the pair the arithmetic and the 8-byte store use; v_rcp_f32 has no packed form and is issued per element.
+// ---------------------------------------------------------------------------------------------
+typedef float v2f __attribute__((ext_vector_type(2)));
+
+__device__ __forceinline__ v2f vfma(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
+__device__ __forceinline__ v2f vsplat(float x) { return (v2f){x, x}; }
+__device__ __forceinline__ v2f vrcp_nr(v2f x)
+{
+    const v2f r = {__builtin_amdgcn_rcpf(x.x), __builtin_amdgcn_rcpf(x.y)};
+    return vfma(vfma(-x, r, vsplat(1.0f)), r, r);
+}
 __device__ __forceinline__ float rcp_nr(float x)
 {
     float r = __builtin_amdgcn_rcpf(x);
     return __builtin_fmaf(__builtin_fmaf(-x, r, 1.0f), r, r);
+}
+__device__ __forceinline__ v2f rcp_nr(v2f x) { return vrcp_nr(x); }
+// fma on either element type: the builtin itself (v_fma_f32 / v_pk_fma_f32).  A macro, not a function: behind a
+// wrapper the row pass's sweeps come out in another instruction order (several kernels, other register counts).
+#define ADF_FMA(a, b, c) __builtin_elementwise_fma(a, b, c)
+template <class T>
+__device__ __forceinline__ T splat(float x)
+{
+    if constexpr (std::is_same_v<T, v2f>) return vsplat(x);
+    else return x;
 }
 
 // ---------------------------------------------------------------------------------------------
 // Chunk kernels shared by both passes.  c[] is already multiplied by lambda; element M-1 is the
 // separator, elements 0..M-2 the interior; a_s is c of the element before the chunk (0 for chunk 0).
 // ---------------------------------------------------------------------------------------------
-template <int R>
-struct Boundary { float GS0, GS1, PS, QS, GE0, GE1, PE, QE; };
+template <class T, int R>
+struct Boundary { T GS0, GS1, PS, QS, GE0, GE1, PE, QE; };
 
 // The sweeps below are serial recurrences; hipcc's scheduler, left alone, hoists every
 // chain-independent temporary (b_i = 1 - a_i - c_i, c_i^2, negations) of a fully unrolled sweep to the
@@ -62,12 +89,26 @@ struct Boundary { float GS0, GS1, PS, QS, GE0, GE1, PE, QE; };
 // within their own step), and an empty asm on c[] keeps temporaries from being shared between sweeps.
 #define ADF_STEP_FENCE() __builtin_amdgcn_sched_barrier(0)
 
-template <int M>
-__device__ __forceinline__ void launder(float (&v)[M])
+template <int M, class T>
+__device__ __forceinline__ void launder(T (&v)[M])
 {
 #pragma unroll
     for (int i = 0; i < M; i++) asm volatile("" : "+v"(v[i]));
 }
+
+// Which chains an empty asm pins to their step -- the one difference between the two passes' sweeps, kept as each
+// pass was tuned.  The column pass (v2f) pins all of them:
+// pin every chain to its step: pure arithmetic is not ordered against the fence below by
+// instruction selection, and a chain that drifts out of the loop drags one reciprocal per
+// step along with it (the right-hand-side chains feed nothing until the end)
+// The row pass (float) pins only p and q of the boundary sweeps (they feed nothing until the end: keep their chains
+// in step); its M = 60 bucket is within five registers of spilling (wave_hpass_lo_half), so its schedule is left alone.
+template <class T>
+constexpr bool pin_rhs_chains = std::is_same_v<T, v2f>;
+// Likewise how a sweep receives its scalar operands (a_s, xL, xR): by reference in the row pass, by value in the
+// column pass, as the two passes' former copies did -- the generated code of either pass changes with it.
+template <class T>
+using In = std::conditional_t<std::is_same_v<T, v2f>, T, const T&>;
 
 // Quotients x / den are formed as x * r from r = rcp_nr(den): v_rcp_f32 is accurate to 1 ulp, and one Newton step
 // makes it (nearly) correctly rounded at the price of two more dependent FMAs on the serial chain.  x * r carries the
@@ -79,191 +120,55 @@ __device__ __forceinline__ void launder(float (&v)[M])
 // how often the two float32 evaluations round differently, which is what the parity tests measure, so the plain
 // product stays (the residual-step variant was removed; it is in the history at a483289).
 
-// Phase 1 for NC independent chunks (columns): boundary coefficients with O(1) state.  The
-// left->right (LU) and right->left (UL) sweeps are independent serial chains; they advance together,
-// one element each per step, so that every step carries 2*NC independent chains (the passes are bound
-// by VALU dependency stalls, not by issue slots).
-template <int M, int R, int NC>
-__device__ __forceinline__ void chunk_boundary(const float (&c)[NC][M], const float (&f0)[NC][M], const float (&f1)[NC][M],
-                                               const float (&a_s)[NC], Boundary<R> (&o)[NC])
+// Phase 1: boundary coefficients with O(1) state.  The left->right (LU) and right->left (UL) sweeps are independent
+// serial chains; they advance together, one element each per step, so that every step carries two independent chains
+// (the passes are bound by VALU dependency stalls, not by issue slots).
+template <int M, int R, class T>
+__device__ __forceinline__ void chunk_boundary(const T (&c)[M], const T (&f0)[M], const T (&f1)[M], In<T> a_s, Boundary<T, R>& o)
 {
+    const T one = splat<T>(1.0f), zero = splat<T>(0.0f);
     // left -> right: x_i + D_i x_{i+1} = g_i - p_i xL;   right -> left: x_i + E_i x_{i-1} = h_i - q_i xR
-    float D[NC], g0[NC], g1[NC], p[NC];
-    float r[NC], dr[NC], h0[NC], h1[NC], q[NC];
-#pragma unroll
-    for (int e = 0; e < NC; e++) {
-        const float a = a_s[e];
-        const float dl = (1.0f - a) - c[e][0];
-        const float rl = rcp_nr(dl);
-        D[e] = c[e][0] * rl; g0[e] = f0[e][0] * rl; g1[e] = (R > 1) ? f1[e][0] * rl : 0.0f; p[e] = a * rl;
-        const float ci = c[e][M - 2];
-        const float ar = (M - 2 == 0) ? a_s[e] : c[e][(M - 3 > 0) ? M - 3 : 0];
-        dr[e] = (1.0f - ar) - ci;
-        r[e] = rcp_nr(dr[e]);
-        h0[e] = f0[e][M - 2] * r[e]; h1[e] = (R > 1) ? f1[e][M - 2] * r[e] : 0.0f; q[e] = ci * r[e];
-    }
-#pragma unroll
-    for (int t = 1; t <= M - 2; t++) {
-        const int i = t, j = M - 2 - t; // LU element, UL element
-#pragma unroll
-        for (int e = 0; e < NC; e++) {
-            {
-                const float a = c[e][i - 1];
-                const float b = (1.0f - a) - c[e][i];
-                const float dl = __builtin_fmaf(-a, D[e], b);
-                const float rl = rcp_nr(dl);
-                D[e] = c[e][i] * rl;
-                g0[e] = __builtin_fmaf(-a, g0[e], f0[e][i]) * rl;
-                if (R > 1) g1[e] = __builtin_fmaf(-a, g1[e], f1[e][i]) * rl;
-                p[e] = -a * p[e] * rl;
-                asm volatile("" : "+v"(p[e])); // p feeds nothing until the end: keep its chain in step
-            }
-            {
-                // opaque copies: without them the compiler shares b_j = 1 - a_j - c_j between the two
-                // sweeps and keeps it alive from one sweep's visit of j to the other's
-                float ci = c[e][j];
-                float a = (j == 0) ? a_s[e] : c[e][(j > 0) ? j - 1 : 0];
-                asm volatile("" : "+v"(ci), "+v"(a));
-                const float b = (1.0f - a) - ci;
-                dr[e] = __builtin_fmaf(-ci * ci, r[e], b);
-                r[e] = rcp_nr(dr[e]);
-                h0[e] = __builtin_fmaf(-ci, h0[e], f0[e][j]) * r[e];
-                if (R > 1) h1[e] = __builtin_fmaf(-ci, h1[e], f1[e][j]) * r[e];
-                q[e] = -ci * q[e] * r[e];
-                asm volatile("" : "+v"(q[e]));
-            }
-        }
-        ADF_STEP_FENCE();
-    }
-#pragma unroll
-    for (int e = 0; e < NC; e++) {
-        o[e].GE0 = g0[e]; o[e].GE1 = g1[e]; o[e].PE = p[e]; o[e].QE = D[e];
-        o[e].GS0 = h0[e]; o[e].GS1 = h1[e]; o[e].PS = a_s[e] * r[e]; o[e].QS = q[e];
-    }
-}
-
-// Phase 2: interior Thomas solve with both neighbours known; solutions overwrite f0 / f1.
-template <int M, int R, int NC>
-__device__ __forceinline__ void chunk_solve(float (&c)[NC][M], float (&f0)[NC][M], float (&f1)[NC][M],
-                                            const float (&a_s)[NC], const float (&xL0)[NC], const float (&xL1)[NC],
-                                            const float (&xR0)[NC], const float (&xR1)[NC])
-{
-#pragma unroll
-    for (int e = 0; e < NC; e++) launder<M>(c[e]);
-    float corig[NC], D[NC], g0[NC], g1[NC];
-#pragma unroll
-    for (int e = 0; e < NC; e++) {
-        const float a = a_s[e];
-        corig[e] = c[e][0];
-        const float dn = (1.0f - a) - corig[e];
-        const float r = rcp_nr(dn);
-        D[e] = corig[e] * r;
-        g0[e] = __builtin_fmaf(-a, xL0[e], f0[e][0]) * r;
-        g1[e] = (R > 1) ? __builtin_fmaf(-a, xL1[e], f1[e][0]) * r : 0.0f;
-        c[e][0] = D[e]; f0[e][0] = g0[e]; if (R > 1) f1[e][0] = g1[e];
-    }
-#pragma unroll
-    for (int i = 1; i <= M - 2; i++) {
-#pragma unroll
-        for (int e = 0; e < NC; e++) {
-            const float a = corig[e];
-            corig[e] = c[e][i];
-            const float b = (1.0f - a) - corig[e];
-            const float dn = __builtin_fmaf(-a, D[e], b);
-            const float r = rcp_nr(dn);
-            D[e] = corig[e] * r;
-            g0[e] = __builtin_fmaf(-a, g0[e], f0[e][i]) * r;
-            if (R > 1) g1[e] = __builtin_fmaf(-a, g1[e], f1[e][i]) * r;
-            c[e][i] = D[e]; f0[e][i] = g0[e]; if (R > 1) f1[e][i] = g1[e];
-        }
-        ADF_STEP_FENCE();
-    }
-    float x0[NC], x1[NC];
-#pragma unroll
-    for (int e = 0; e < NC; e++) {
-        x0[e] = xR0[e]; x1[e] = xR1[e];
-        f0[e][M - 1] = x0[e]; if (R > 1) f1[e][M - 1] = x1[e];
-    }
-#pragma unroll
-    for (int i = M - 2; i >= 0; i--) {
-#pragma unroll
-        for (int e = 0; e < NC; e++) {
-            x0[e] = __builtin_fmaf(-c[e][i], x0[e], f0[e][i]);
-            f0[e][i] = x0[e];
-            if (R > 1) { x1[e] = __builtin_fmaf(-c[e][i], x1[e], f1[e][i]); f1[e][i] = x1[e]; }
-        }
-        ADF_STEP_FENCE();
-    }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Two-column versions for the vertical pass.  A thread owns the same rows of two adjacent columns;
-// written on 2-vectors the sweeps compile to the packed fp32 instructions (v_pk_fma_f32, v_pk_mul_f32,
-// v_pk_add_f32: two lanes of work per issue slot), and the register pair an 8-byte load fills is the
-// pair the arithmetic and the 8-byte store use -- no moves between "two scalars" and "a pair".  The
-// operations and their order are exactly those of the scalar templates above (v_rcp_f32 has no packed
-// form and is issued per element), so results are bit-identical to them.
-// ---------------------------------------------------------------------------------------------
-typedef float v2f __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ v2f vfma(v2f a, v2f b, v2f c) { return __builtin_elementwise_fma(a, b, c); }
-__device__ __forceinline__ v2f vsplat(float x) { return (v2f){x, x}; }
-__device__ __forceinline__ v2f vrcp_nr(v2f x)
-{
-    const v2f r = {__builtin_amdgcn_rcpf(x.x), __builtin_amdgcn_rcpf(x.y)};
-    return vfma(vfma(-x, r, vsplat(1.0f)), r, r);
-}
-
-template <int R>
-struct Boundary2 { v2f GS0, GS1, PS, QS, GE0, GE1, PE, QE; };
-
-template <int M, int R>
-__device__ __forceinline__ void chunk_boundary2(const v2f (&c)[M], const v2f (&f0)[M], const v2f (&f1)[M], v2f a_s, Boundary2<R>& o)
-{
-    const v2f one = vsplat(1.0f), zero = vsplat(0.0f);
-    // left -> right: x_i + D_i x_{i+1} = g_i - p_i xL;   right -> left: x_i + E_i x_{i-1} = h_i - q_i xR
-    v2f D, g0, g1, p, r, dr, h0, h1, q;
+    T D, g0, g1, p, r, dr, h0, h1, q;
     {
-        const v2f dl = (one - a_s) - c[0];
-        const v2f rl = vrcp_nr(dl);
+        const T dl = (one - a_s) - c[0];
+        const T rl = rcp_nr(dl);
         D = c[0] * rl; g0 = f0[0] * rl; g1 = (R > 1) ? f1[0] * rl : zero; p = a_s * rl;
-        const v2f ci = c[M - 2];
-        const v2f ar = (M - 2 == 0) ? a_s : c[(M - 3 > 0) ? M - 3 : 0];
+        const T ci = c[M - 2];
+        const T ar = (M - 2 == 0) ? a_s : c[(M - 3 > 0) ? M - 3 : 0];
         dr = (one - ar) - ci;
-        r = vrcp_nr(dr);
+        r = rcp_nr(dr);
         h0 = f0[M - 2] * r; h1 = (R > 1) ? f1[M - 2] * r : zero; q = ci * r;
     }
 #pragma unroll
     for (int t = 1; t <= M - 2; t++) {
         const int i = t, j = M - 2 - t; // LU element, UL element
         {
-            const v2f a = c[i - 1];
-            const v2f b = (one - a) - c[i];
-            const v2f dl = vfma(-a, D, b);
-            const v2f rl = vrcp_nr(dl);
+            const T a = c[i - 1];
+            const T b = (one - a) - c[i];
+            const T dl = ADF_FMA(-a, D, b);
+            const T rl = rcp_nr(dl);
             D = c[i] * rl;
-            g0 = vfma(-a, g0, f0[i]) * rl;
-            if (R > 1) g1 = vfma(-a, g1, f1[i]) * rl;
+            g0 = ADF_FMA(-a, g0, f0[i]) * rl;
+            if (R > 1) g1 = ADF_FMA(-a, g1, f1[i]) * rl;
             p = -a * p * rl;
-            // pin every chain to its step: pure arithmetic is not ordered against the fence below by
-            // instruction selection, and a chain that drifts out of the loop drags one reciprocal per
-            // step along with it (the right-hand-side chains feed nothing until the end)
-            if (R > 1) asm volatile("" : "+v"(g0), "+v"(g1), "+v"(p));
+            if constexpr (!pin_rhs_chains<T>) asm volatile("" : "+v"(p));
+            else if (R > 1) asm volatile("" : "+v"(g0), "+v"(g1), "+v"(p));
             else asm volatile("" : "+v"(g0), "+v"(p));
         }
         {
             // opaque copies: without them the compiler shares b_j = 1 - a_j - c_j between the two
             // sweeps and keeps it alive from one sweep's visit of j to the other's
-            v2f ci = c[j];
-            v2f a = (j == 0) ? a_s : c[(j > 0) ? j - 1 : 0];
+            T ci = c[j];
+            T a = (j == 0) ? a_s : c[(j > 0) ? j - 1 : 0];
             asm volatile("" : "+v"(ci), "+v"(a));
-            const v2f b = (one - a) - ci;
-            dr = vfma(-ci * ci, r, b);
-            r = vrcp_nr(dr);
-            h0 = vfma(-ci, h0, f0[j]) * r;
-            if (R > 1) h1 = vfma(-ci, h1, f1[j]) * r;
+            const T b = (one - a) - ci;
+            dr = ADF_FMA(-ci * ci, r, b);
+            r = rcp_nr(dr);
+            h0 = ADF_FMA(-ci, h0, f0[j]) * r;
+            if (R > 1) h1 = ADF_FMA(-ci, h1, f1[j]) * r;
             q = -ci * q * r;
-            if (R > 1) asm volatile("" : "+v"(h0), "+v"(h1), "+v"(q));
+            if constexpr (!pin_rhs_chains<T>) asm volatile("" : "+v"(q));
+            else if (R > 1) asm volatile("" : "+v"(h0), "+v"(h1), "+v"(q));
             else asm volatile("" : "+v"(h0), "+v"(q));
         }
         ADF_STEP_FENCE();
@@ -272,78 +177,69 @@ __device__ __forceinline__ void chunk_boundary2(const v2f (&c)[M], const v2f (&f
     o.GS0 = h0; o.GS1 = h1; o.PS = a_s * r; o.QS = q;
 }
 
-template <int M, int R>
-__device__ __forceinline__ void chunk_solve2(v2f (&c)[M], v2f (&f0)[M], v2f (&f1)[M], v2f a_s, v2f xL0, v2f xL1, v2f xR0, v2f xR1)
+// Phase 2: interior Thomas solve with both neighbours known; solutions overwrite f0 / f1.
+template <int M, int R, class T>
+__device__ __forceinline__ void chunk_solve(T (&c)[M], T (&f0)[M], T (&f1)[M], In<T> a_s, In<T> xL0, In<T> xL1, In<T> xR0, In<T> xR1)
 {
-    const v2f one = vsplat(1.0f), zero = vsplat(0.0f);
-#pragma unroll
-    for (int i = 0; i < M; i++) asm volatile("" : "+v"(c[i]));
-    v2f corig = c[0], D, g0, g1;
+    const T one = splat<T>(1.0f), zero = splat<T>(0.0f);
+    launder(c);
+    T corig = c[0], D, g0, g1;
     {
-        const v2f dn = (one - a_s) - corig;
-        const v2f r = vrcp_nr(dn);
+        const T dn = (one - a_s) - corig;
+        const T r = rcp_nr(dn);
         D = corig * r;
-        g0 = vfma(-a_s, xL0, f0[0]) * r;
-        g1 = (R > 1) ? vfma(-a_s, xL1, f1[0]) * r : zero;
+        g0 = ADF_FMA(-a_s, xL0, f0[0]) * r;
+        g1 = (R > 1) ? ADF_FMA(-a_s, xL1, f1[0]) * r : zero;
         c[0] = D; f0[0] = g0; if (R > 1) f1[0] = g1;
     }
 #pragma unroll
     for (int i = 1; i <= M - 2; i++) {
-        const v2f a = corig;
+        const T a = corig;
         corig = c[i];
-        const v2f b = (one - a) - corig;
-        const v2f dn = vfma(-a, D, b);
-        const v2f r = vrcp_nr(dn);
+        const T b = (one - a) - corig;
+        const T dn = ADF_FMA(-a, D, b);
+        const T r = rcp_nr(dn);
         D = corig * r;
-        g0 = vfma(-a, g0, f0[i]) * r;
-        if (R > 1) g1 = vfma(-a, g1, f1[i]) * r;
+        g0 = ADF_FMA(-a, g0, f0[i]) * r;
+        if (R > 1) g1 = ADF_FMA(-a, g1, f1[i]) * r;
         c[i] = D; f0[i] = g0; if (R > 1) f1[i] = g1;
-        if (R > 1) asm volatile("" : "+v"(D), "+v"(g0), "+v"(g1));
-        else asm volatile("" : "+v"(D), "+v"(g0));
+        if constexpr (pin_rhs_chains<T>) {
+            if (R > 1) asm volatile("" : "+v"(D), "+v"(g0), "+v"(g1));
+            else asm volatile("" : "+v"(D), "+v"(g0));
+        }
         ADF_STEP_FENCE();
     }
-    v2f x0 = xR0, x1 = xR1;
+    T x0 = xR0, x1 = xR1;
     f0[M - 1] = x0; if (R > 1) f1[M - 1] = x1;
 #pragma unroll
     for (int i = M - 2; i >= 0; i--) {
-        x0 = vfma(-c[i], x0, f0[i]);
+        x0 = ADF_FMA(-c[i], x0, f0[i]);
         f0[i] = x0;
-        if (R > 1) { x1 = vfma(-c[i], x1, f1[i]); f1[i] = x1; }
-        if (R > 1) asm volatile("" : "+v"(x0), "+v"(x1));
-        else asm volatile("" : "+v"(x0));
+        if (R > 1) { x1 = ADF_FMA(-c[i], x1, f1[i]); f1[i] = x1; }
+        if constexpr (pin_rhs_chains<T>) {
+            if (R > 1) asm volatile("" : "+v"(x0), "+v"(x1));
+            else asm volatile("" : "+v"(x0));
+        }
         ADF_STEP_FENCE();
     }
-}
-
-template <int M, int R>
-__device__ __forceinline__ void separator_row2(const v2f (&c)[M], const v2f (&f0)[M], const v2f (&f1)[M], const Boundary2<R>& o,
-                                               v2f nGS0, v2f nGS1, v2f nPS, v2f nQS, v2f& al, v2f& be, v2f& ga, v2f& p0, v2f& p1)
-{
-    const v2f ae = c[M - 2], ce = c[M - 1];
-    const v2f bb = (vsplat(1.0f) - ae) - ce;
-    al = -ae * o.PE;
-    be = vfma(-ce, nPS, vfma(-ae, o.QE, bb));
-    ga = -ce * nQS;
-    p0 = vfma(-ce, nGS0, vfma(-ae, o.GE0, f0[M - 1]));
-    p1 = (R > 1) ? vfma(-ce, nGS1, vfma(-ae, o.GE1, f1[M - 1])) : vsplat(0.0f);
 }
 
 // Separator equation of a chunk: alpha*x_prev + beta*x + gamma*x_next = phi.
 // nGS*/nPS/nQS are the NEXT chunk's left-end coefficients (zero for the last chunk).
-template <int M, int R>
-__device__ __forceinline__ void separator_row(const float (&c)[M], const float (&f0)[M], const float (&f1)[M],
-                                              const Boundary<R>& o, float nGS0, float nGS1, float nPS, float nQS,
-                                              float& al, float& be, float& ga, float& p0, float& p1)
+template <int M, int R, class T>
+__device__ __forceinline__ void separator_row(const T (&c)[M], const T (&f0)[M], const T (&f1)[M], const Boundary<T, R>& o,
+                                              T nGS0, T nGS1, T nPS, T nQS, T& al, T& be, T& ga, T& p0, T& p1)
 {
-    const float ae = c[M - 2], ce = c[M - 1];
-    const float bb = (1.0f - ae) - ce;
+    const T ae = c[M - 2], ce = c[M - 1];
+    const T bb = (splat<T>(1.0f) - ae) - ce;
     al = -ae * o.PE;
-    be = __builtin_fmaf(-ce, nPS, __builtin_fmaf(-ae, o.QE, bb));
+    be = ADF_FMA(-ce, nPS, ADF_FMA(-ae, o.QE, bb));
     ga = -ce * nQS;
-    p0 = __builtin_fmaf(-ce, nGS0, __builtin_fmaf(-ae, o.GE0, f0[M - 1]));
-    p1 = (R > 1) ? __builtin_fmaf(-ce, nGS1, __builtin_fmaf(-ae, o.GE1, f1[M - 1])) : 0.0f;
+    p0 = ADF_FMA(-ce, nGS0, ADF_FMA(-ae, o.GE0, f0[M - 1]));
+    p1 = (R > 1) ? ADF_FMA(-ce, nGS1, ADF_FMA(-ae, o.GE1, f1[M - 1])) : splat<T>(0.0f);
 }
 
+// pcr64 and reduced128 are scalar in both passes: they run one separator row per lane.
 // Parallel cyclic reduction of a 64-row tridiagonal system held one row per lane.
 template <int R>
 __device__ __forceinline__ void pcr64(int lane, float al, float be, float ga, float p0, float p1, float& x0, float& x1)
@@ -401,6 +297,28 @@ __device__ __forceinline__ void reduced128(int lane, const float* al, const floa
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// Host side: each pass keeps ONE constexpr list of its buckets, shortest first; the launcher's choice and its
+// dispatch to the kernel instantiations both come from that list.
+// ---------------------------------------------------------------------------------------------
+struct Bucket { int m, chunks; };   // chunk length M, chunks per scanline: holds scanlines of up to m * chunks elements
+
+template <int N>
+constexpr int bucket_index(const Bucket (&b)[N], int len)   // the first bucket that holds len (the last one if none does)
+{
+    int i = 0;
+    while (i < N - 1 && len > b[i].m * b[i].chunks) i++;
+    return i;
+}
+
+// f(std::integral_constant<int, i>{}) for a run-time i in [0, N)
+template <int N, int I = 0, class F>
+inline hipError_t dispatch_index(int i, F&& f)
+{
+    if (i == I) return f(std::integral_constant<int, I>{});
+    if constexpr (I + 1 < N) return dispatch_index<N, I + 1>(i, f);
+    else return hipErrorInvalidValue;
+}
 
 } // namespace wave
 } // namespace adf

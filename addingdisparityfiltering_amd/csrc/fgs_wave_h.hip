@@ -86,7 +86,7 @@ __global__ void __launch_bounds__(64 * NW, (M > (NW == 2 ? 40 : H_TWO_WAVE_MAX) 
 #define ADF_PIDX(q) (PAIR ? ((((q) >> 3) * (8 * TR)) + ((q) & 7)) : (q))
     const int nvecU = PAIR ? 2 * nvec : nvec;
     constexpr int MQ = M / 4;
-    float c[1][M], f0[1][M], f1[1][M];
+    float c[M], f0[M], f1[M];
 
     // All of the row's coalesced loads (16 B per lane, 1 KiB per instruction) are issued before the
     // first use so that a row pays one memory latency, not one per plane; each plane is then turned
@@ -409,62 +409,62 @@ __global__ void __launch_bounds__(64 * NW, (M > (NW == 2 ? 40 : H_TWO_WAVE_MAX) 
                 const int j = (lane & 31) * M + 4 * k;                                    \
                 const int sidx = ((j >> 4) << 3) + ((j & 15) >> 2);                       \
                 const float4 v = stage[sidx], w = stage[sidx + 4];                        \
-                f0[0][4 * k + 0] = v.x; f0[0][4 * k + 1] = v.y; f0[0][4 * k + 2] = v.z; f0[0][4 * k + 3] = v.w; \
-                f1[0][4 * k + 0] = w.x; f1[0][4 * k + 1] = w.y; f1[0][4 * k + 2] = w.z; f1[0][4 * k + 3] = w.w; \
+                f0[4 * k + 0] = v.x; f0[4 * k + 1] = v.y; f0[4 * k + 2] = v.z; f0[4 * k + 3] = v.w; \
+                f1[4 * k + 0] = w.x; f1[4 * k + 1] = w.y; f1[4 * k + 2] = w.z; f1[4 * k + 3] = w.w; \
             }                                                                             \
         }                                                                                 \
         __syncthreads();                                                                  \
     }
-    ADF_TRANSPOSE_IN(tC, c[0], a.lambda)
+    ADF_TRANSPOSE_IN(tC, c, a.lambda)
     if (PAIR && FUSED == FUSE_NONE) {
         ADF_PAIR_IN(t0, 0)
         ADF_PAIR_IN(t1, 1)
     } else {
-        ADF_TRANSPOSE_IN(t0, f0[0], 1.0f)
-        if (R > 1) ADF_TRANSPOSE_IN(t1, f1[0], 1.0f)
+        ADF_TRANSPOSE_IN(t0, f0, 1.0f)
+        if (R > 1) ADF_TRANSPOSE_IN(t1, f1, 1.0f)
         else {
 #pragma unroll
-            for (int i = 0; i < M; i++) f1[0][i] = 0.0f;
+            for (int i = 0; i < M; i++) f1[i] = 0.0f;
         }
     }
 #undef ADF_PAIR_IN
 #undef ADF_TRANSPOSE_IN
 
-    float a_s[1] = {__shfl_up(c[0][M - 1], 1)};
-    if (lane == 0) a_s[0] = 0.0f;
+    float a_s = __shfl_up(c[M - 1], 1);
+    if (lane == 0) a_s = 0.0f;
     if constexpr (NW == 2) {                                     // chunk 64 follows chunk 63
-        if (wv == 0 && lane == 63) xch[0] = c[0][M - 1];
+        if (wv == 0 && lane == 63) xch[0] = c[M - 1];
         __syncthreads();
-        if (wv == 1 && lane == 0) a_s[0] = xch[0];
+        if (wv == 1 && lane == 0) a_s = xch[0];
     }
 
-    Boundary<R> bd[1];
-    chunk_boundary<M, R, 1>(c, f0, f1, a_s, bd);
-    float nGS0 = __shfl_down(bd[0].GS0, 1), nGS1 = (R > 1) ? __shfl_down(bd[0].GS1, 1) : 0.0f;
-    float nPS = __shfl_down(bd[0].PS, 1), nQS = __shfl_down(bd[0].QS, 1);
+    Boundary<float, R> bd;
+    chunk_boundary<M, R>(c, f0, f1, a_s, bd);
+    float nGS0 = __shfl_down(bd.GS0, 1), nGS1 = (R > 1) ? __shfl_down(bd.GS1, 1) : 0.0f;
+    float nPS = __shfl_down(bd.PS, 1), nQS = __shfl_down(bd.QS, 1);
     if (lane == 63) { nGS0 = 0.0f; nGS1 = 0.0f; nPS = 0.0f; nQS = 0.0f; }
     if constexpr (NW == 2) {                                     // chunk 63's next chunk is wave 1's first
-        if (wv == 1 && lane == 0) { xch[1] = bd[0].GS0; xch[2] = (R > 1) ? bd[0].GS1 : 0.0f; xch[3] = bd[0].PS; xch[4] = bd[0].QS; }
+        if (wv == 1 && lane == 0) { xch[1] = bd.GS0; xch[2] = (R > 1) ? bd.GS1 : 0.0f; xch[3] = bd.PS; xch[4] = bd.QS; }
         __syncthreads();
         if (wv == 0 && lane == 63) { nGS0 = xch[1]; nGS1 = xch[2]; nPS = xch[3]; nQS = xch[4]; }
     }
-    float al, be, ga, p0, p1, xs0[1], xs1[1];
-    separator_row<M, R>(c[0], f0[0], f1[0], bd[0], nGS0, nGS1, nPS, nQS, al, be, ga, p0, p1);
-    float xL0[1], xL1[1];
+    float al, be, ga, p0, p1, xs0, xs1;
+    separator_row<M, R>(c, f0, f1, bd, nGS0, nGS1, nPS, nQS, al, be, ga, p0, p1);
+    float xL0, xL1;
     if constexpr (NW == 2) {
         const int g = 64 * wv + lane;                            // chunk of this lane
         red[0][g] = al; red[1][g] = be; red[2][g] = ga; red[3][g] = p0; red[4][g] = p1;
         __syncthreads();
         if (wv == 0) reduced128<R>(lane, red[0], red[1], red[2], red[3], red[4], 1, xsol[0], xsol[1]);
         __syncthreads();
-        xs0[0] = xsol[0][g]; xs1[0] = (R > 1) ? xsol[1][g] : 0.0f;
-        xL0[0] = g > 0 ? xsol[0][g - 1] : 0.0f; xL1[0] = (R > 1 && g > 0) ? xsol[1][g - 1] : 0.0f;
+        xs0 = xsol[0][g]; xs1 = (R > 1) ? xsol[1][g] : 0.0f;
+        xL0 = g > 0 ? xsol[0][g - 1] : 0.0f; xL1 = (R > 1 && g > 0) ? xsol[1][g - 1] : 0.0f;
     } else {
-        pcr64<R>(lane, al, be, ga, p0, p1, xs0[0], xs1[0]);
-        xL0[0] = __shfl_up(xs0[0], 1); xL1[0] = (R > 1) ? __shfl_up(xs1[0], 1) : 0.0f;
-        if (lane == 0) { xL0[0] = 0.0f; xL1[0] = 0.0f; }
+        pcr64<R>(lane, al, be, ga, p0, p1, xs0, xs1);
+        xL0 = __shfl_up(xs0, 1); xL1 = (R > 1) ? __shfl_up(xs1, 1) : 0.0f;
+        if (lane == 0) { xL0 = 0.0f; xL1 = 0.0f; }
     }
-    chunk_solve<M, R, 1>(c, f0, f1, a_s, xL0, xL1, xs0, xs1);
+    chunk_solve<M, R>(c, f0, f1, a_s, xL0, xL1, xs0, xs1);
 
     typedef float v4f __attribute__((ext_vector_type(4)));
     // The pass works in place: the store addresses ARE the load addresses, and the compiler would keep
@@ -475,7 +475,7 @@ __global__ void __launch_bounds__(64 * NW, (M > (NW == 2 ? 40 : H_TWO_WAVE_MAX) 
     if (!PAIR) {
 #pragma unroll
         for (int k = 0; k < MQ; k++)
-            stage[lane * MQ + k] = make_float4(f0[0][4 * k], f0[0][4 * k + 1], f0[0][4 * k + 2], f0[0][4 * k + 3]);
+            stage[lane * MQ + k] = make_float4(f0[4 * k], f0[4 * k + 1], f0[4 * k + 2], f0[4 * k + 3]);
         __syncthreads();
         v4f* d4 = reinterpret_cast<v4f*>(a.U0 + off);
 #pragma unroll
@@ -493,8 +493,8 @@ __global__ void __launch_bounds__(64 * NW, (M > (NW == 2 ? 40 : H_TWO_WAVE_MAX) 
                 for (int k = 0; k < MQ; k++) {
                     const int j = (lane & 31) * M + 4 * k;
                     const int sidx = ((j >> 4) << 3) + ((j & 15) >> 2);
-                    stage[sidx] = make_float4(f0[0][4 * k], f0[0][4 * k + 1], f0[0][4 * k + 2], f0[0][4 * k + 3]);
-                    stage[sidx + 4] = make_float4(f1[0][4 * k], f1[0][4 * k + 1], f1[0][4 * k + 2], f1[0][4 * k + 3]);
+                    stage[sidx] = make_float4(f0[4 * k], f0[4 * k + 1], f0[4 * k + 2], f0[4 * k + 3]);
+                    stage[sidx + 4] = make_float4(f1[4 * k], f1[4 * k + 1], f1[4 * k + 2], f1[4 * k + 3]);
                 }
             }
             __syncthreads();
@@ -529,21 +529,22 @@ hipError_t launch_h(const WavePassArgs& a, int n_rhs, int n_pairs, hipStream_t s
     return hipGetLastError();
 }
 
+// The row buckets: one wavefront per row of 64 chunks up to 4096 columns, two wavefronts (128 chunks) above.
+// (60 x 64 = 3840 columns: a full 4K row; 60 x 128 = 7680: a full 8K row)
+constexpr Bucket ROW_BUCKETS[] = {{4, 64}, {8, 64}, {16, 64}, {20, 64}, {28, 64}, {40, 64}, {56, 64}, {60, 64}, {64, 64},
+                                  {40, 128}, {48, 128}, {56, 128}, {60, 128}, {64, 128}};
+constexpr int N_ROW_BUCKETS = sizeof(ROW_BUCKETS) / sizeof(ROW_BUCKETS[0]);
+
 // chunk length / wavefronts per row the launcher picks for a row of `len` elements
 void pick_row_bucket(int len, int& m, int& nw)
 {
-    if (len > 64 * 64) {
-        const int q = (len + 127) / 128;
-        nw = 2; m = q <= 40 ? 40 : q <= 48 ? 48 : q <= 56 ? 56 : q <= 60 ? 60 : 64;
-        return;
-    }
-    const int q = (len + 63) / 64;
-    nw = 1; m = q <= 4 ? 4 : q <= 8 ? 8 : q <= 16 ? 16 : q <= 20 ? 20 : q <= 28 ? 28 : q <= 40 ? 40 : q <= 56 ? 56 : q <= 60 ? 60 : 64;
+    const Bucket& b = ROW_BUCKETS[bucket_index(ROW_BUCKETS, len)];
+    m = b.m; nw = b.chunks / 64;
 }
 
 } // namespace
 
-int wave_max_row_len() { return 128 * 64; }
+int wave_max_row_len() { return ROW_BUCKETS[N_ROW_BUCKETS - 1].m * ROW_BUCKETS[N_ROW_BUCKETS - 1].chunks; }
 
 // The fused first pass reads conf as float4s -- the confidence plane is the library's own and laid out so that the ROI
 // row starts 16-byte aligned whatever the ROI is (Geom::cx0 / cpitch) -- and dL, the caller's map, in 8-byte pieces at
@@ -596,28 +597,10 @@ hipError_t launch_wave_hpass(const WavePassArgs& a, int n_rhs, int n_pairs, hipS
     if (a.len < 2 || a.len > wave_max_row_len() || a.pitch % 64 != 0 || a.pitch < a.len) return hipErrorInvalidValue;
     if (a.fuse.lo_conf && !wave_hpass_can_fuse_lo(a)) return hipErrorInvalidValue;
     if (!a.fuse.lo_conf && a.fuse.conf_in && !wave_hpass_can_fuse(a)) return hipErrorInvalidValue;
-    int m, nw;
-    pick_row_bucket(a.len, m, nw);
-    if (nw == 2) {           // wider than 4096 columns: two wavefronts per row
-        switch (m) {
-        case 40: return launch_h<40, 2>(a, n_rhs, n_pairs, st);
-        case 48: return launch_h<48, 2>(a, n_rhs, n_pairs, st);
-        case 56: return launch_h<56, 2>(a, n_rhs, n_pairs, st);
-        case 60: return launch_h<60, 2>(a, n_rhs, n_pairs, st);   // 7680 columns: a full 8K row
-        default: return launch_h<64, 2>(a, n_rhs, n_pairs, st);
-        }
-    }
-    switch (m) {
-    case 4: return launch_h<4>(a, n_rhs, n_pairs, st);
-    case 8: return launch_h<8>(a, n_rhs, n_pairs, st);
-    case 16: return launch_h<16>(a, n_rhs, n_pairs, st);
-    case 20: return launch_h<20>(a, n_rhs, n_pairs, st);
-    case 28: return launch_h<28>(a, n_rhs, n_pairs, st);
-    case 40: return launch_h<40>(a, n_rhs, n_pairs, st);
-    case 56: return launch_h<56>(a, n_rhs, n_pairs, st);
-    case 60: return launch_h<60>(a, n_rhs, n_pairs, st);       // 3840 columns: a full 4K row
-    default: return launch_h<64>(a, n_rhs, n_pairs, st);
-    }
+    return dispatch_index<N_ROW_BUCKETS>(bucket_index(ROW_BUCKETS, a.len), [&](auto I) {
+        constexpr Bucket b = ROW_BUCKETS[decltype(I)::value];
+        return launch_h<b.m, b.chunks / 64>(a, n_rhs, n_pairs, st);
+    });
 }
 
 } // namespace adf

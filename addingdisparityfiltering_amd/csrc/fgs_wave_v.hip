@@ -102,8 +102,8 @@ __global__ void __launch_bounds__(VT) wave_vpass_kernel(WavePassArgs a)
     const unsigned pitch_c = 4u * VC;
     const unsigned coff0 = (((unsigned)strip * (unsigned)h + (unsigned)r0) * VC + c16) * 4u;
 
-    // both columns of a row in one register pair, from the 8-byte load to the 8-byte store (see the
-    // two-column templates in fgs_wave_common.h)
+    // both columns of a row in one register pair, from the 8-byte load to the 8-byte store (the chunk
+    // templates of fgs_wave_common.h on v2f)
     v2f c[M], f0[M], f1[M];
     // row 0 of the column: always inside the planes
     const unsigned safe = (R > 1) ? ((unsigned)strip * (32u * TR) + c16) * 4u : (unsigned)col * 4u;
@@ -132,8 +132,8 @@ __global__ void __launch_bounds__(VT) wave_vpass_kernel(WavePassArgs a)
         for (int i = 0; i < M; i++) c[i] *= lam;
     }
 
-    Boundary2<R> bd;
-    chunk_boundary2<M, R>(c, f0, f1, a_s, bd);
+    Boundary<v2f, R> bd;
+    chunk_boundary<M, R>(c, f0, f1, a_s, bd);
     *reinterpret_cast<v2f*>(&nb[0][cidx][2 * xp]) = bd.GS0;
     *reinterpret_cast<v2f*>(&nb[1][cidx][2 * xp]) = bd.GS1;
     *reinterpret_cast<v2f*>(&nb[2][cidx][2 * xp]) = bd.PS;
@@ -146,7 +146,7 @@ __global__ void __launch_bounds__(VT) wave_vpass_kernel(WavePassArgs a)
             nPS = *reinterpret_cast<const v2f*>(&nb[2][cidx + 1][2 * xp]); nQS = *reinterpret_cast<const v2f*>(&nb[3][cidx + 1][2 * xp]);
         }
         v2f al, be, ga, p0, p1;
-        separator_row2<M, R>(c, f0, f1, bd, nGS0, nGS1, nPS, nQS, al, be, ga, p0, p1);
+        separator_row<M, R>(c, f0, f1, bd, nGS0, nGS1, nPS, nQS, al, be, ga, p0, p1);
         red[0][2 * xp][cidx] = al.x; red[1][2 * xp][cidx] = be.x; red[2][2 * xp][cidx] = ga.x;
         red[3][2 * xp][cidx] = p0.x; red[4][2 * xp][cidx] = p1.x;
         red[0][2 * xp + 1][cidx] = al.y; red[1][2 * xp + 1][cidx] = be.y; red[2][2 * xp + 1][cidx] = ga.y;
@@ -175,7 +175,7 @@ __global__ void __launch_bounds__(VT) wave_vpass_kernel(WavePassArgs a)
             xL0 = (v2f){xs[0][cc][cidx - 1], xs[0][cc + 1][cidx - 1]};
             xL1 = (v2f){xs[1][cc][cidx - 1], xs[1][cc + 1][cidx - 1]};
         }
-        chunk_solve2<M, R>(c, f0, f1, a_s, xL0, xL1, xR0, xR1);
+        chunk_solve<M, R>(c, f0, f1, a_s, xL0, xL1, xR0, xR1);
     }
 
     unsigned voff = voff0;
@@ -284,42 +284,34 @@ template <int M, int VCW = VC, int NCH = 64>
 hipError_t launch_v(const WavePassArgs& a, int n_rhs, int epi, int n_pairs, hipStream_t st)
 {
     dim3 grid(a.pitch / VCW, n_pairs), block(VT);
-#define ADF_LV(RR, EE) hipLaunchKernelGGL((wave_vpass_kernel<M, RR, EE, VCW, NCH>), grid, block, 0, st, a)
-    if (n_rhs == 2 && epi == EPI_PLANES) ADF_LV(2, EPI_PLANES);
-    else if (n_rhs == 2 && epi == EPI_WLS_CONF) ADF_LV(2, EPI_WLS_CONF);
-    else if (n_rhs == 1 && epi == EPI_PLANES) ADF_LV(1, EPI_PLANES);
-    else if (n_rhs == 1 && epi == EPI_I16) ADF_LV(1, EPI_I16);
-    else if (n_rhs == 1 && epi == EPI_F32) ADF_LV(1, EPI_F32);
-    else if (n_rhs == 1 && epi == EPI_U8) ADF_LV(1, EPI_U8);
-    else if (n_rhs == 2 && epi == EPI_I16) ADF_LV(2, EPI_I16);   // channel pairs of a generic FGS source
-    else if (n_rhs == 2 && epi == EPI_F32) ADF_LV(2, EPI_F32);
-    else if (n_rhs == 2 && epi == EPI_U8) ADF_LV(2, EPI_U8);
-    else return hipErrorInvalidValue;
-#undef ADF_LV
-    return hipGetLastError();
+    constexpr int N_EPI = EPI_U8 + 1;
+    if (n_rhs < 1 || n_rhs > 2 || epi < 0 || epi >= N_EPI) return hipErrorInvalidValue;
+    return dispatch_index<2 * N_EPI>((n_rhs - 1) * N_EPI + epi, [&](auto K) {
+        constexpr int R = decltype(K)::value / N_EPI + 1, EPI = decltype(K)::value % N_EPI;
+        // (two right-hand sides with a generic epilogue: channel pairs of a generic FGS source)
+        if constexpr (R == 1 && EPI == EPI_WLS_CONF) return hipErrorInvalidValue;   // the ratio needs both right-hand sides
+        else {
+            hipLaunchKernelGGL((wave_vpass_kernel<M, R, EPI, VCW, NCH>), grid, block, 0, st, a);
+            return hipGetLastError();
+        }
+    });
 }
+
+// The column buckets: full strips of 64 chunks up to 2176 rows, half strips of 128 chunks above.
+constexpr Bucket COL_BUCKETS[] = {{2, 64}, {4, 64}, {8, 64}, {12, 64}, {18, 64}, {26, 64}, {34, 64}, {20, 128}, {26, 128}, {34, 128}};
+constexpr int N_COL_BUCKETS = sizeof(COL_BUCKETS) / sizeof(COL_BUCKETS[0]);
 
 } // namespace
 
-int wave_max_col_len() { return 128 * 34; }
+int wave_max_col_len() { return COL_BUCKETS[N_COL_BUCKETS - 1].m * COL_BUCKETS[N_COL_BUCKETS - 1].chunks; }
 
 hipError_t launch_wave_vpass(const WavePassArgs& a, int n_rhs, int epilogue, int n_pairs, hipStream_t st)
 {
     if (a.len < 2 || a.len > wave_max_col_len() || a.pitch % 64 != 0 || a.pitch < a.nscan) return hipErrorInvalidValue;
-    if (a.len > 64 * 34) {   // taller than 2176 rows: half strips of 128 chunks
-        const int m = (a.len + 127) / 128;
-        if (m <= 20) return launch_v<20, VC / 2, 128>(a, n_rhs, epilogue, n_pairs, st);
-        if (m <= 26) return launch_v<26, VC / 2, 128>(a, n_rhs, epilogue, n_pairs, st);
-        return launch_v<34, VC / 2, 128>(a, n_rhs, epilogue, n_pairs, st);
-    }
-    const int m = (a.len + 63) / 64;
-    if (m <= 2) return launch_v<2>(a, n_rhs, epilogue, n_pairs, st);
-    if (m <= 4) return launch_v<4>(a, n_rhs, epilogue, n_pairs, st);
-    if (m <= 8) return launch_v<8>(a, n_rhs, epilogue, n_pairs, st);
-    if (m <= 12) return launch_v<12>(a, n_rhs, epilogue, n_pairs, st);
-    if (m <= 18) return launch_v<18>(a, n_rhs, epilogue, n_pairs, st);
-    if (m <= 26) return launch_v<26>(a, n_rhs, epilogue, n_pairs, st);
-    return launch_v<34>(a, n_rhs, epilogue, n_pairs, st);
+    return dispatch_index<N_COL_BUCKETS>(bucket_index(COL_BUCKETS, a.len), [&](auto I) {
+        constexpr Bucket b = COL_BUCKETS[decltype(I)::value];
+        return launch_v<b.m, b.chunks == 64 ? VC : VC / 2, b.chunks>(a, n_rhs, epilogue, n_pairs, st);
+    });
 }
 
 } // namespace adf

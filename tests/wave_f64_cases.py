@@ -27,11 +27,11 @@ FLOOR = 1e-6
 VARIED_FACTOR = 8.0
 FLAT_FACTOR = 96.0
 
-# Mirrors pick_row_bucket (csrc/fgs_wave_h.hip): one wavefront per row of 64 chunks of M elements up to 4096 columns,
+# Mirrors ROW_BUCKETS (csrc/fgs_wave_h.hip): one wavefront per row of 64 chunks of M elements up to 4096 columns,
 # two wavefronts (128 chunks) above.  (M, chunks); a bucket takes the lengths (previous bucket's chunks*M, chunks*M].
 ROW_BUCKETS = [(4, 64), (8, 64), (16, 64), (20, 64), (28, 64), (40, 64), (56, 64), (60, 64), (64, 64),
                (40, 128), (48, 128), (56, 128), (60, 128), (64, 128)]
-# Mirrors launch_wave_vpass (csrc/fgs_wave_v.hip): full strips of 64 chunks up to 2176 rows, half strips of 128 chunks
+# Mirrors COL_BUCKETS (csrc/fgs_wave_v.hip): full strips of 64 chunks up to 2176 rows, half strips of 128 chunks
 # above.  (M, chunks per column).
 COL_BUCKETS = [(2, 64), (4, 64), (8, 64), (12, 64), (18, 64), (26, 64), (34, 64), (20, 128), (26, 128), (34, 128)]
 COL_WIDTHS = (40, 50)      # partial 16-column strips, and a pitch padded to 64
