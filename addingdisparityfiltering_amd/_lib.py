@@ -63,6 +63,10 @@ SYMBOLS = [
     ("adf_wls_filter_host", _i, _FILTER_DEV[:-1]),
     ("adf_wls_filter_scaled_device", _i, _FILTER_SCALED_DEV),
     ("adf_wls_filter_scaled_host", _i, _FILTER_SCALED_DEV[:-1]),
+    ("adf_wls_filter_f32_device", _i, _FILTER_DEV),
+    ("adf_wls_filter_f32_host", _i, _FILTER_DEV[:-1]),
+    ("adf_wls_filter_scaled_f32_device", _i, _FILTER_SCALED_DEV),
+    ("adf_wls_filter_scaled_f32_host", _i, _FILTER_SCALED_DEV[:-1]),
     ("adf_wls_get_confidence_device", _i, [_vp, _i, _vp, _pd, _vp]),
     ("adf_wls_get_confidence_host", _i, [_vp, _i, _vp, _pd]),
     ("adf_wls_get_device", _i, [_vp, C.POINTER(_i)]),

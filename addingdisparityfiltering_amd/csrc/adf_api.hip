@@ -89,7 +89,10 @@ struct FinalOut {
 };
 
 // output bytes per pixel of a fused epilogue
-static double epilogue_bytes(int epilogue) { return epilogue == EPI_F32 ? 4.0 : epilogue == EPI_U8 ? 1.0 : 2.0; }
+static double epilogue_bytes(int epilogue)
+{
+    return (epilogue == EPI_F32 || epilogue == EPI_WLS_CONF_F32) ? 4.0 : epilogue == EPI_U8 ? 1.0 : 2.0;
+}
 
 template <class Args>
 static void set_final_out(Args& a, const FinalOut& fo)
@@ -455,7 +458,7 @@ static int scaled_conf_map(adf_wls_t* h, const ScaledStage& s, hipStream_t st, P
         ProfScope ps(prof, K_DISC, 4.0 * Plo, 12.0 * Plo, st);
         HIP_TRY(launch_discontinuity(da, c.n_pairs, st));                // DF.cpp:204
     }
-    LrcArgs la{s.dispL, s.sL, s.psL, s.dispR, s.sR, s.psR, s.cl, s.cr, c.clo, nullptr, 0, 0, 0, nullptr, nullptr, glo, rrx, thresh_lo, ORIENT_N};
+    LrcArgs la{s.dispL, s.sL, s.psL, s.dispR, s.sR, s.psR, s.cl, s.cr, c.clo, nullptr, 0, 0, 0, 0, nullptr, nullptr, glo, rrx, thresh_lo, ORIENT_N};
     ProfScope ps(prof, K_LRC, 4.0 * (double)lo * c.n_pairs, 4.0 * (double)lo * c.n_pairs + 12.0 * Plo, st);
     HIP_TRY(launch_lrc_prologue(la, c.n_pairs, st));                     // DF.cpp:208-209
     return ADF_OK;
@@ -560,12 +563,19 @@ static WlsPlan plan_wls(const adf_wls* h, const Geom& g, int n_pairs, const int1
     return p;
 }
 
+// The filtered map of a call: CV_16SC1 (adf_wls_filter_*) or, with f32, CV_32FC1 holding the float the int16 epilogue
+// rounds (adf_wls_filter_f32_*).  Only the last column pass and the fill outside the ROI know the difference.
+struct OutMap {
+    void* p; ptrdiff_t stride, pair_stride; bool f32;
+    size_t esz() const { return f32 ? sizeof(float) : sizeof(int16_t); }
+};
+
 // scaled: the down-scaled path (DF.cpp:274): its stage replaces the confidence kernels, dispR is not used, and dispL is
 // the stage's resized map (with fuse_lo only a stand-in that is never dereferenced).
 static int wls_filter_impl(adf_wls_t* h, int n_pairs,
                            const int16_t* dispL, ptrdiff_t sL, ptrdiff_t psL,
                            const uint8_t* view, ptrdiff_t sG, ptrdiff_t psG, int gch, int W, int H,
-                           int16_t* out, ptrdiff_t sO, ptrdiff_t psO,
+                           const OutMap& om,
                            const int16_t* dispR, ptrdiff_t sR, ptrdiff_t psR,
                            const adf_rect* roi_in, hipStream_t st, const ScaledStage* scaled = nullptr)
 {
@@ -573,10 +583,15 @@ static int wls_filter_impl(adf_wls_t* h, int n_pairs,
     // DF.cpp:221-222
     if (!dispL || W <= 0 || H <= 0) return fail(ADF_EBADARG, "disparity_map_left is empty");
     if (!view || (gch != 1 && gch != 3)) return fail(ADF_EBADARG, "left_view must be CV_8UC1 or CV_8UC3");
+    void* const out = om.p;
+    const ptrdiff_t sO = om.stride, psO = om.pair_stride;
+    const double ob_px = (double)om.esz();                                 // output bytes per pixel
     if (!out) return fail(ADF_EBADARG, "filtered_disparity_map is NULL");
     if (n_pairs < 1) return fail(ADF_EBADARG, "n_pairs must be >= 1");
-    if (sL < (ptrdiff_t)W * 2 || sO < (ptrdiff_t)W * 2 || sG < (ptrdiff_t)W * gch)
+    if (sL < (ptrdiff_t)W * 2 || sO < (ptrdiff_t)(W * om.esz()) || sG < (ptrdiff_t)W * gch)
         return fail(ADF_ESIZE, "row stride smaller than a row");
+    if (om.f32 && ((reinterpret_cast<uintptr_t>(out) | (uintptr_t)sO | (uintptr_t)psO) & 3u))
+        return fail(ADF_EBADARG, "a float filtered_disparity_map needs a 4-byte aligned base and strides");
     const bool conf = h->use_confidence;
     int rc;
     if (conf && !scaled && (rc = check_right_map(dispR, sR, W))) return rc;
@@ -634,12 +649,12 @@ static int wls_filter_impl(adf_wls_t* h, int n_pairs,
         const int16_t* dL = (const int16_t*)((const char*)dispL + (ptrdiff_t)first * psL);
         const int16_t* dR = dispR ? (const int16_t*)((const char*)dispR + (ptrdiff_t)first * psR) : nullptr;
         const uint8_t* gv = view + (ptrdiff_t)first * psG;
-        int16_t* o = (int16_t*)((char*)out + (ptrdiff_t)first * psO);
+        void* o = (char*)out + (ptrdiff_t)first * psO;
         float* confp = conf ? (float*)h->conf.p + (size_t)first * g.cframe : nullptr;
         const double F = (double)g.frame * n, P = (double)g.rw * g.rh * n;
         // the output outside the ROI (DF.cpp:284), and the confidence plane there where this call's own kernels make it
-        OutsideArgs oa{o, sO, psO, fill, scaled ? nullptr : confp, g};
-        const double ob = (oa.conf ? 6.0 : 2.0) * (F - P);
+        OutsideArgs oa{o, sO, psO, fill, om.f32 ? 1 : 0, scaled ? nullptr : confp, g};
+        const double ob = ((oa.conf ? 4.0 : 0.0) + ob_px) * (F - P);
         auto fill_outside = [&](hipStream_t s) { ProfScope ps(prof, K_FILL, ob, ob, s); return launch_outside(oa, n, s); };
         WeightArgs wa{gv, sG, psG, gch, h->lut.cur, p.CH, p.CV, orient_h, orient_cv, g,
                       wave ? nullptr : p.B0};   // exact: B0 is free until the first pass writes its output there
@@ -689,7 +704,7 @@ static int wls_filter_impl(adf_wls_t* h, int n_pairs,
             else if ((rc = resize_conf_planes(h, scaled->lo, st, prof))) return rc;
             break;
         case CONF_MERGED: {
-            const double b = (8.0 + gch + 8.0) * P + 6.0 * (F - P);
+            const double b = (8.0 + gch + 8.0) * P + (4.0 + ob_px) * (F - P);
             ProfScope ps(prof, K_LRC, b, b, st);
             HIP_TRY(launch_prep_small(ba, wa, oa, n, st));                 // FGS.cpp:163-172 + DF.cpp:197-210 + :284
             break;
@@ -723,15 +738,16 @@ static int wls_filter_impl(adf_wls_t* h, int n_pairs,
                 ProfScope ps(prof, K_DISC, 4.0 * P, 12.0 * P, st);
                 HIP_TRY(launch_discontinuity(da, n, st));                  // DF.cpp:204
             }
-            LrcArgs la{dL, sL, psL, dR, sR, psR, cL, cR, confp, o, sO, psO, fill, p.A0, p.A1, g, rrx, thresh, orient_u2};
+            LrcArgs la{dL, sL, psL, dR, sR, psR, cL, cR, confp, o, sO, psO, fill, om.f32 ? 1 : 0, p.A0, p.A1, g, rrx, thresh, orient_u2};
             // alg: confidence map out (4F) + the two rhs planes (8P); moved adds dL,dR,cL,cR reads
-            ProfScope ps(prof, K_LRC, 4.0 * F + 8.0 * P + 2.0 * (F - P), 4.0 * F + 20.0 * P + 2.0 * (F - P), st);
+            ProfScope ps(prof, K_LRC, 4.0 * F + 8.0 * P + ob_px * (F - P), 4.0 * F + 20.0 * P + ob_px * (F - P), st);
             HIP_TRY(launch_lrc_prologue(la, n, st));                       // DF.cpp:208-209,288-290
             break;
         }
         }
         if (cp.fork_weights) HIP_TRY(hipStreamWaitEvent(st, h->ev_join, 0));
-        FinalOut fo{conf ? EPI_WLS_CONF : EPI_I16, o, sO, psO, roi.x, roi.y, 1, 0};
+        const int epi = conf ? (om.f32 ? EPI_WLS_CONF_F32 : EPI_WLS_CONF) : (om.f32 ? EPI_F32 : EPI_I16);
+        FinalOut fo{epi, o, sO, psO, roi.x, roi.y, 1, 0};
         rc = run_passes(wave, g, p, conf ? 2 : 1, (float)h->lambda, (float)h->atten, h->num_iter, fo, n, st, prof,
                         plan.fused_first ? &fuse : nullptr);
         if (rc) return rc;                                                 // DF.cpp:257-258, 292-296
@@ -739,30 +755,18 @@ static int wls_filter_impl(adf_wls_t* h, int n_pairs,
     return ADF_OK;
 }
 
-extern "C" int adf_wls_filter_device(adf_wls_t* h, int n_pairs,
-                                     const int16_t* dispL, ptrdiff_t sL, ptrdiff_t psL,
-                                     const uint8_t* view, ptrdiff_t sG, ptrdiff_t psG, int gch, int W, int H,
-                                     int16_t* out, ptrdiff_t sO, ptrdiff_t psO,
-                                     const int16_t* dispR, ptrdiff_t sR, ptrdiff_t psR,
-                                     const adf_rect* roi_in, void* stream)
-{
-    return wls_filter_impl(h, n_pairs, dispL, sL, psL, view, sG, psG, gch, W, H, out, sO, psO, dispR, sR, psR, roi_in,
-                           (hipStream_t)stream);
-}
-
 // Down-scaled disparity path (DF.cpp:224-227, 239-247, 268-277): disparity maps of dW x dH, view and
 // output of W x H.  ROI is in disparity-map coordinates, like the reference's.
-extern "C" int adf_wls_filter_scaled_device(adf_wls_t* h, int n_pairs,
-                                            const int16_t* dispL, ptrdiff_t sL, ptrdiff_t psL, int dW, int dH,
-                                            const uint8_t* view, ptrdiff_t sG, ptrdiff_t psG, int gch, int W, int H,
-                                            int16_t* out, ptrdiff_t sO, ptrdiff_t psO,
-                                            const int16_t* dispR, ptrdiff_t sR, ptrdiff_t psR,
-                                            const adf_rect* roi_in, void* stream)
+static int wls_filter_scaled_device(adf_wls_t* h, int n_pairs,
+                                    const int16_t* dispL, ptrdiff_t sL, ptrdiff_t psL, int dW, int dH,
+                                    const uint8_t* view, ptrdiff_t sG, ptrdiff_t psG, int gch, int W, int H,
+                                    const OutMap& om,
+                                    const int16_t* dispR, ptrdiff_t sR, ptrdiff_t psR,
+                                    const adf_rect* roi_in, hipStream_t st)
 {
     NEED_HANDLE(h);
-    hipStream_t st = (hipStream_t)stream;
     if (dW == W && dH == H)                                                // DF.cpp:224-227: same size, resize_factor 1
-        return wls_filter_impl(h, n_pairs, dispL, sL, psL, view, sG, psG, gch, W, H, out, sO, psO, dispR, sR, psR, roi_in, st);
+        return wls_filter_impl(h, n_pairs, dispL, sL, psL, view, sG, psG, gch, W, H, om, dispR, sR, psR, roi_in, st);
     if (!dispL || dW <= 0 || dH <= 0 || W <= 0 || H <= 0) return fail(ADF_EBADARG, "disparity_map_left is empty");
     if (n_pairs < 1) return fail(ADF_EBADARG, "n_pairs must be >= 1");
     if (sL < (ptrdiff_t)dW * 2) return fail(ADF_ESIZE, "row stride smaller than a row");
@@ -803,27 +807,28 @@ extern "C" int adf_wls_filter_scaled_device(adf_wls_t* h, int n_pairs,
     if (conf && (rc = ensure_conf_planes(h, ghi, n_pairs, st))) return rc;
     // (fuse_lo: wls_filter_impl never dereferences its dispL -- the caller's low-resolution map stands in, with its own strides)
     rc = wls_filter_impl(h, n_pairs, s.fuse_lo ? dispL : (const int16_t*)s.dhi, (ptrdiff_t)W * 2, (ptrdiff_t)s.dhi_bytes,
-                         view, sG, psG, gch, W, H, out, sO, psO, nullptr, 0, 0, &rhi, st, &s);
+                         view, sG, psG, gch, W, H, om, nullptr, 0, 0, &rhi, st, &s);
     h->roi = rlo;                                                          // getROI(): valid_disp_ROI (DF.cpp:139)
     return rc;
 }
 
-extern "C" int adf_wls_filter_scaled_host(adf_wls_t* h, int n_pairs,
-                                          const int16_t* dispL, ptrdiff_t sL, ptrdiff_t psL, int dW, int dH,
-                                          const uint8_t* view, ptrdiff_t sG, ptrdiff_t psG, int gch, int W, int H,
-                                          int16_t* out, ptrdiff_t sO, ptrdiff_t psO,
-                                          const int16_t* dispR, ptrdiff_t sR, ptrdiff_t psR,
-                                          const adf_rect* roi)
+static int wls_filter_scaled_host(adf_wls_t* h, int n_pairs,
+                                  const int16_t* dispL, ptrdiff_t sL, ptrdiff_t psL, int dW, int dH,
+                                  const uint8_t* view, ptrdiff_t sG, ptrdiff_t psG, int gch, int W, int H,
+                                  const OutMap& om,
+                                  const int16_t* dispR, ptrdiff_t sR, ptrdiff_t psR,
+                                  const adf_rect* roi)
 {
     NEED_HANDLE(h);
-    if (!dispL || !view || !out || W <= 0 || H <= 0 || dW <= 0 || dH <= 0 || n_pairs < 1)
+    if (!dispL || !view || !om.p || W <= 0 || H <= 0 || dW <= 0 || dH <= 0 || n_pairs < 1)
         return fail(ADF_EBADARG, "adf_wls_filter_host: empty input");
     if (gch != 1 && gch != 3) return fail(ADF_EBADARG, "left_view must be CV_8UC1 or CV_8UC3");
     if (h->use_confidence && !dispR) return fail(ADF_EBADARG, "disparity_map_right is required with use_confidence");
     DeviceScope ds(h->device);
     hipStream_t st = nullptr;
     // dense device copies: [dispL | dispR | out | view] per batch
-    const size_t dbytes = (size_t)dW * dH * 2, obytes = (size_t)W * H * 2, gbytes = (size_t)W * H * gch;
+    const size_t orow = (size_t)W * om.esz();
+    const size_t dbytes = (size_t)dW * dH * 2, obytes = orow * H, gbytes = (size_t)W * H * gch;
     const size_t dpad = (dbytes + 255) / 256 * 256, opad = (obytes + 255) / 256 * 256, gpad = (gbytes + 255) / 256 * 256;
     const size_t need = (size_t)n_pairs * (2 * dpad + opad + gpad);
     int rc = h->stage.reserve(need, st, FILL_ZERO);
@@ -835,26 +840,53 @@ extern "C" int adf_wls_filter_scaled_host(adf_wls_t* h, int n_pairs,
     if ((rc = copy_images(dLd, (size_t)dW * 2, dpad, dispL, sL, psL, (size_t)dW * 2, dH, n_pairs, hipMemcpyHostToDevice, st))) return rc;
     if (dispR && (rc = copy_images(dRd, (size_t)dW * 2, dpad, dispR, sR, psR, (size_t)dW * 2, dH, n_pairs, hipMemcpyHostToDevice, st))) return rc;
     if ((rc = copy_images(gd, (size_t)W * gch, gpad, view, sG, psG, (size_t)W * gch, H, n_pairs, hipMemcpyHostToDevice, st))) return rc;
-    rc = adf_wls_filter_scaled_device(h, n_pairs, (const int16_t*)dLd, (ptrdiff_t)dW * 2, (ptrdiff_t)dpad, dW, dH,
-                                      (const uint8_t*)gd, (ptrdiff_t)W * gch, (ptrdiff_t)gpad, gch, W, H,
-                                      (int16_t*)od, (ptrdiff_t)W * 2, (ptrdiff_t)opad,
-                                      dispR ? (const int16_t*)dRd : nullptr, (ptrdiff_t)dW * 2, (ptrdiff_t)dpad, roi, st);
+    rc = wls_filter_scaled_device(h, n_pairs, (const int16_t*)dLd, (ptrdiff_t)dW * 2, (ptrdiff_t)dpad, dW, dH,
+                                  (const uint8_t*)gd, (ptrdiff_t)W * gch, (ptrdiff_t)gpad, gch, W, H,
+                                  OutMap{od, (ptrdiff_t)orow, (ptrdiff_t)opad, om.f32},
+                                  dispR ? (const int16_t*)dRd : nullptr, (ptrdiff_t)dW * 2, (ptrdiff_t)dpad, roi, st);
     if (rc) return rc;
-    if ((rc = copy_images(out, sO, psO, od, (size_t)W * 2, opad, (size_t)W * 2, H, n_pairs, hipMemcpyDeviceToHost, st))) return rc;
+    if ((rc = copy_images(om.p, om.stride, om.pair_stride, od, orow, opad, orow, H, n_pairs, hipMemcpyDeviceToHost, st))) return rc;
     HIP_TRY(hipStreamSynchronize(st));
     return ADF_OK;
 }
 
-extern "C" int adf_wls_filter_host(adf_wls_t* h, int n_pairs,
-                                   const int16_t* dispL, ptrdiff_t sL, ptrdiff_t psL,
-                                   const uint8_t* view, ptrdiff_t sG, ptrdiff_t psG, int gch, int W, int H,
-                                   int16_t* out, ptrdiff_t sO, ptrdiff_t psO,
-                                   const int16_t* dispR, ptrdiff_t sR, ptrdiff_t psR,
-                                   const adf_rect* roi)
-{
-    return adf_wls_filter_scaled_host(h, n_pairs, dispL, sL, psL, W, H, view, sG, psG, gch, W, H, out, sO, psO,
-                                      dispR, sR, psR, roi);
-}
+// The eight entry points: {same size, scaled} x {device, host} x {CV_16SC1, CV_32FC1 output}.
+#define ADF_WLS_SAME_ARGS const int16_t* dispL, ptrdiff_t sL, ptrdiff_t psL, \
+                          const uint8_t* view, ptrdiff_t sG, ptrdiff_t psG, int gch, int W, int H
+#define ADF_WLS_SCALED_ARGS const int16_t* dispL, ptrdiff_t sL, ptrdiff_t psL, int dW, int dH, \
+                            const uint8_t* view, ptrdiff_t sG, ptrdiff_t psG, int gch, int W, int H
+#define ADF_WLS_RIGHT_ARGS const int16_t* dispR, ptrdiff_t sR, ptrdiff_t psR, const adf_rect* roi
+#define ADF_WLS_ENTRIES(SUFFIX, T, F32)                                                                                       \
+    extern "C" int adf_wls_filter##SUFFIX##_device(adf_wls_t* h, int n_pairs, ADF_WLS_SAME_ARGS, T* out, ptrdiff_t sO,        \
+                                                   ptrdiff_t psO, ADF_WLS_RIGHT_ARGS, void* stream)                           \
+    {                                                                                                                         \
+        return wls_filter_impl(h, n_pairs, dispL, sL, psL, view, sG, psG, gch, W, H, OutMap{out, sO, psO, F32}, dispR, sR,    \
+                               psR, roi, (hipStream_t)stream);                                                                \
+    }                                                                                                                         \
+    extern "C" int adf_wls_filter_scaled##SUFFIX##_device(adf_wls_t* h, int n_pairs, ADF_WLS_SCALED_ARGS, T* out,             \
+                                                          ptrdiff_t sO, ptrdiff_t psO, ADF_WLS_RIGHT_ARGS, void* stream)      \
+    {                                                                                                                         \
+        return wls_filter_scaled_device(h, n_pairs, dispL, sL, psL, dW, dH, view, sG, psG, gch, W, H,                         \
+                                        OutMap{out, sO, psO, F32}, dispR, sR, psR, roi, (hipStream_t)stream);                 \
+    }                                                                                                                         \
+    extern "C" int adf_wls_filter_scaled##SUFFIX##_host(adf_wls_t* h, int n_pairs, ADF_WLS_SCALED_ARGS, T* out, ptrdiff_t sO, \
+                                                        ptrdiff_t psO, ADF_WLS_RIGHT_ARGS)                                    \
+    {                                                                                                                         \
+        return wls_filter_scaled_host(h, n_pairs, dispL, sL, psL, dW, dH, view, sG, psG, gch, W, H,                           \
+                                      OutMap{out, sO, psO, F32}, dispR, sR, psR, roi);                                        \
+    }                                                                                                                         \
+    extern "C" int adf_wls_filter##SUFFIX##_host(adf_wls_t* h, int n_pairs, ADF_WLS_SAME_ARGS, T* out, ptrdiff_t sO,          \
+                                                 ptrdiff_t psO, ADF_WLS_RIGHT_ARGS)                                           \
+    {                                                                                                                         \
+        return wls_filter_scaled_host(h, n_pairs, dispL, sL, psL, W, H, view, sG, psG, gch, W, H, OutMap{out, sO, psO, F32},  \
+                                      dispR, sR, psR, roi);                                                                   \
+    }
+ADF_WLS_ENTRIES(, int16_t, false)
+ADF_WLS_ENTRIES(_f32, float, true)
+#undef ADF_WLS_ENTRIES
+#undef ADF_WLS_SAME_ARGS
+#undef ADF_WLS_SCALED_ARGS
+#undef ADF_WLS_RIGHT_ARGS
 
 extern "C" int adf_wls_profile_enable(adf_wls_t* h, int on)
 {

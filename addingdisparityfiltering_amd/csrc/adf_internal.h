@@ -48,8 +48,10 @@ enum Epilogue {
     EPI_WLS_CONF = 1, // int16 = sat(u0 * (1/(u1+EPS)))   DF.cpp:295-296
     EPI_I16 = 2,      // int16 = sat(u0)                  FGS.cpp:216 (no-confidence path, DF.cpp:257-258)
     EPI_F32 = 3,      // float natural layout             FGS.cpp:218
-    EPI_U8 = 4        // uint8 = sat(u0)                  FGS.cpp:216
+    EPI_U8 = 4,       // uint8 = sat(u0)                  FGS.cpp:216
+    EPI_WLS_CONF_F32 = 5 // float = the value EPI_WLS_CONF rounds, single channel (adf_wls_filter_f32_*)
 };
+constexpr int N_EPILOGUES = EPI_WLS_CONF_F32 + 1;
 
 // Both views of a pair in one launch: index 0 = left, 1 = right (mirrored ROI x, DF.cpp:202-203).
 struct DiscArgs {
@@ -83,9 +85,10 @@ struct ConfBandArgs {
     int rows_per_band;
 };
 
-// Non-ROI pixels: filtered map = fill (DF.cpp:284), confidence = 0 (DF.cpp:187-190); either may be null.
+// Non-ROI pixels: filtered map = fill (DF.cpp:284), confidence = 0 (DF.cpp:187-190); either may be null.  The map is
+// CV_16SC1, or CV_32FC1 holding float(fill) when out_f32 is set (adf_wls_filter_f32_*).
 struct OutsideArgs {
-    int16_t* out; ptrdiff_t stride, pair_stride; int16_t fill;
+    void* out; ptrdiff_t stride, pair_stride; int16_t fill; int out_f32;
     float* conf;
     Geom g;
 };
@@ -95,7 +98,7 @@ struct LrcArgs {
     const int16_t* dR; ptrdiff_t sR, psR;
     const float* cL; const float* cR; // full-frame discontinuity maps
     float* conf;                      // confidence plane (x255; Geom::cpitch layout), zero outside ROI
-    int16_t* out; ptrdiff_t sO, psO; int16_t fill; // filtered map: `fill` outside the ROI (DF.cpp:284); may be null
+    void* out; ptrdiff_t sO, psO; int16_t fill; int out_f32; // filtered map (int16, or float when out_f32): `fill` outside the ROI (DF.cpp:284); may be null
     float* U0; float* U1;             // ROI planes: conf*disp, conf
     Geom g; int rrx;                  // right ROI x (DF.cpp:202)
     int thresh; int orient;           // orientation of U0/U1
@@ -223,6 +226,16 @@ __device__ __forceinline__ size_t strip_index(int i, int j, int rh)
 {
     return ((size_t)(j >> 4) * (size_t)rh + (size_t)i) * ADF_STRIP + (size_t)(j & 15);
 }
+// One pixel of a filtered map outside the ROI: `fill` as int16, or as the float of the same value (uniform branch).
+__device__ __forceinline__ void store_fill(void* map, ptrdiff_t row_offset_bytes, int j, int16_t fill, int f32)
+{
+    char* row = reinterpret_cast<char*>(map) + row_offset_bytes;
+    if (f32) reinterpret_cast<float*>(row)[j] = (float)fill;
+    else reinterpret_cast<int16_t*>(row)[j] = fill;
+}
+// The float epilogues' form of a value the int16 epilogues saturate to -32768 for being NaN, infinite or outside the
+// int range (sat16 below): -32768.0f, so that sat16(float map) == int16 map and the float map holds no NaN or inf.
+__device__ __forceinline__ float wls_f32_value(float x) { return !(__builtin_fabsf(x) < 2147483648.0f) ? -32768.0f : x; }
 // saturate_cast<short>(float): cvRound (round-half-even; NaN / out-of-int-range -> INT_MIN) + clamp.
 __device__ __forceinline__ int16_t sat16(float v)
 {

@@ -628,7 +628,7 @@ __device__ __forceinline__ void outside_body(const OutsideArgs& a, const int nAx
         const int j = t < g.rx ? t : t + g.rw;
         const int i0 = g.ry + by * OUT_ROWS, i1 = min(i0 + OUT_ROWS, g.ry + g.rh);
         for (int i = i0; i < i1; i++) {
-            if (out) reinterpret_cast<int16_t*>(out + (ptrdiff_t)i * a.stride)[j] = a.fill;
+            if (out) store_fill(out, (ptrdiff_t)i * a.stride, j, a.fill, a.out_f32);
             if (conf) conf[(size_t)i * g.cpitch + j] = 0.0f;
         }
     } else {
@@ -640,7 +640,7 @@ __device__ __forceinline__ void outside_body(const OutsideArgs& a, const int nAx
             int i = (int)(p / (size_t)g.W);
             const int j = (int)(p - (size_t)i * g.W);
             if (i >= g.ry) i += g.rh;                        // rows below the ROI
-            if (out) reinterpret_cast<int16_t*>(out + (ptrdiff_t)i * a.stride)[j] = a.fill;
+            if (out) store_fill(out, (ptrdiff_t)i * a.stride, j, a.fill, a.out_f32);
             if (conf) conf[(size_t)i * g.cpitch + j] = 0.0f;
         }
     }
@@ -751,8 +751,7 @@ __global__ void __launch_bounds__(NT) lrc_prologue_kernel(LrcArgs a)
         if (in_frame) {
             conf[(size_t)i * g.cpitch + j] = c;
             if (a.out && !in_roi)                                          // DF.cpp:284
-                reinterpret_cast<int16_t*>(reinterpret_cast<char*>(a.out) + (ptrdiff_t)pz * a.psO +
-                                           (ptrdiff_t)i * a.sO)[j] = a.fill;
+                store_fill(a.out, (ptrdiff_t)pz * a.psO + (ptrdiff_t)i * a.sO, j, a.fill, a.out_f32);
         }
         if (!U0) continue;
         if (a.orient != ORIENT_T) {

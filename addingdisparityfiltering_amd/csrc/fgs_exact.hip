@@ -210,6 +210,9 @@ __global__ void __launch_bounds__(64) exact_pass_kernel(PassArgs a)
                         if (EPI == EPI_WLS_CONF) {
                             const float rcp = 1.0f / (u1_[j] + ADF_EPS);     // DF.cpp:295
                             reinterpret_cast<int16_t*>(row)[e] = sat16(u0_[j] * rcp); // DF.cpp:296
+                        } else if (EPI == EPI_WLS_CONF_F32) {   // the float the branch above rounds
+                            const float rcp = 1.0f / (u1_[j] + ADF_EPS);     // DF.cpp:295
+                            reinterpret_cast<float*>(row)[e] = wls_f32_value(u0_[j] * rcp);
                         } else if (EPI == EPI_I16)
                             reinterpret_cast<int16_t*>(row)[e] = sat16(u0_[j]);
                         else if (EPI == EPI_U8)
@@ -235,6 +238,7 @@ hipError_t launch_exact_pass(const PassArgs& a, int n_rhs, int epilogue, int n_p
 #define ADF_LAUNCH(RR, EE) hipLaunchKernelGGL((exact_pass_kernel<RR, EE>), grid, block, 0, st, a)
     if (n_rhs == 2 && epilogue == EPI_PLANES) ADF_LAUNCH(2, EPI_PLANES);
     else if (n_rhs == 2 && epilogue == EPI_WLS_CONF) ADF_LAUNCH(2, EPI_WLS_CONF);
+    else if (n_rhs == 2 && epilogue == EPI_WLS_CONF_F32) ADF_LAUNCH(2, EPI_WLS_CONF_F32);
     else if (n_rhs == 1 && epilogue == EPI_PLANES) ADF_LAUNCH(1, EPI_PLANES);
     else if (n_rhs == 1 && epilogue == EPI_I16) ADF_LAUNCH(1, EPI_I16);
     else if (n_rhs == 1 && epilogue == EPI_F32) ADF_LAUNCH(1, EPI_F32);

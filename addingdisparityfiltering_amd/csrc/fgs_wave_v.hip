@@ -33,18 +33,36 @@ constexpr int VC = 16;   // columns per strip (the layouts' strip: fgs_wave_comm
 //  * u1 == 0 exactly: 1 / 1e-43 overflows to +inf -- here 2^64 * rcp(2^64 * 1e-43) does -- and 0 * inf, x * inf and NaN
 //    all leave the int range -> -32768, as in the reference (tests: zero-confidence edge case).
 // (u1 * 2^64 + EPS * 2^64 in one FMA: it differs from (u1 + EPS) * 2^64 only below the last bit of a denormal sum.)
+// epi_value is the float both forms of an epilogue start from: epi_pack16 rounds it, epi_f32 stores it.
+template <int EPI>
+__device__ __forceinline__ v2f epi_value(v2f u0, v2f u1)
+{
+    if (EPI == EPI_WLS_CONF || EPI == EPI_WLS_CONF_F32) {
+        const v2f sc = vsplat(0x1p64f);
+        return u0 * (vrcp_nr(vfma(u1, sc, vsplat(ADF_EPS * 0x1p64f))) * sc);
+    }
+    return u0;
+}
+
 template <int EPI>
 __device__ __forceinline__ unsigned epi_pack16(v2f u0, v2f u1)
 {
-    v2f x = u0;
-    if (EPI == EPI_WLS_CONF) {
-        const v2f sc = vsplat(0x1p64f);
-        x = u0 * (vrcp_nr(vfma(u1, sc, vsplat(ADF_EPS * 0x1p64f))) * sc);
-    }
+    const v2f x = epi_value<EPI>(u0, u1);
     const bool o0 = !(__builtin_fabsf(x.x) < 2147483648.0f), o1 = !(__builtin_fabsf(x.y) < 2147483648.0f);
     const int i0 = (int)(o0 ? -32768.0f : __builtin_rintf(x.x)), i1 = (int)(o1 ? -32768.0f : __builtin_rintf(x.y));
     typedef short s2 __attribute__((ext_vector_type(2)));
     return __builtin_bit_cast(unsigned, (s2)__builtin_amdgcn_cvt_pk_i16(i0, i1));
+}
+
+// Both columns of a thread as the float map holds them.  EPI_WLS_CONF_F32: the ratio, with -32768.0f wherever
+// epi_pack16 saturates to -32768 for a value that is NaN, infinite or outside the int range (u1 == 0 above), so the
+// map holds no NaN or inf and saturate_cast<short> of it is the int16 map bit for bit.  EPI_F32: u0 as it is.
+template <int EPI>
+__device__ __forceinline__ v2f epi_f32(v2f u0, v2f u1)
+{
+    const v2f x = epi_value<EPI>(u0, u1);
+    if (EPI == EPI_WLS_CONF_F32) return (v2f){wls_f32_value(x.x), wls_f32_value(x.y)};
+    return x;
 }
 
 template <int M, int R, int EPI, int VCW = VC, int NCH = 64>
@@ -196,7 +214,7 @@ __global__ void __launch_bounds__(VT) wave_vpass_kernel(WavePassArgs a)
         asm volatile("" : "+v"(r0e), "+v"(cole));
         char* ob = reinterpret_cast<char*>(a.out) + (ptrdiff_t)blockIdx.y * a.out_pair_stride +
                    (ptrdiff_t)(a.out_y0 + r0e) * a.out_stride;
-        const int esz = (EPI == EPI_F32) ? 4 : (EPI == EPI_U8) ? 1 : 2;
+        const int esz = (EPI == EPI_F32 || EPI == EPI_WLS_CONF_F32) ? 4 : (EPI == EPI_U8) ? 1 : 2;
         unsigned ooff = (unsigned)((a.out_x0 + cole) * a.out_cn + a.out_c) * (unsigned)esz;
         // Single-channel int16 output with an even number of columns (every call of the disparity filter on an even-width
         // ROI): both columns of the thread go out as one packed dword -- or, when the ROI starts on an odd column (the
@@ -248,7 +266,37 @@ __global__ void __launch_bounds__(VT) wave_vpass_kernel(WavePassArgs a)
                     ADF_STEP_FENCE();
                 }
             }
-        } else {
+        } else if ((EPI == EPI_WLS_CONF_F32 || (EPI == EPI_F32 && R == 1)) && a.out_cn == 1) {
+            // Single-channel float output (adf_wls_filter_f32_*, a one-channel generic smoother): both columns of the
+            // thread go out as one float2 -- the eight column pairs of a strip row are one contiguous 64-byte piece --
+            // or, when the map's base, strides or ROI x do not keep a pair 8-byte aligned, as two dwords.  The thread
+            // that holds the last column of an odd-width ROI stores its first column only; as in the packed int16 path
+            // there is no branch but the row mask, and every condition is uniform over the launch.
+            const bool al8 = ((reinterpret_cast<uintptr_t>(a.out) | (uintptr_t)a.out_stride | (uintptr_t)a.out_pair_stride) & 7u) == 0 &&
+                             (a.out_x0 & 1) == 0;
+            const int hv2 = (cole + 1 < a.nscan ? h : 0) - r0e;   // rows of a thread with two columns inside the ROI
+            const int hv1 = (cole + 1 == a.nscan ? h : 0) - r0e;  // ... with only its first column inside
+            char* dst = ob + ooff;
+            if (al8) {
+#pragma unroll
+                for (int i = 0; i < M; i++) {
+                    const v2f v = epi_f32<EPI>(f0[i], f1[i]);
+                    if (i < hv2) *reinterpret_cast<v2f*>(dst) = v;
+                    if (i < hv1) reinterpret_cast<float*>(dst)[0] = v.x;
+                    dst += a.out_stride;
+                    ADF_STEP_FENCE();
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < M; i++) {
+                    const v2f v = epi_f32<EPI>(f0[i], f1[i]);
+                    if (i < hv2) { reinterpret_cast<float*>(dst)[0] = v.x; reinterpret_cast<float*>(dst)[1] = v.y; }
+                    if (i < hv1) reinterpret_cast<float*>(dst)[0] = v.x;
+                    dst += a.out_stride;
+                    ADF_STEP_FENCE();
+                }
+            }
+        } else if (EPI != EPI_WLS_CONF_F32) {   // (the ratio as a float is single-channel only: launch_wave_vpass)
 #pragma unroll
         for (int i = 0; i < M; i++) {
             if (r0 + i < h) {
@@ -284,12 +332,12 @@ template <int M, int VCW = VC, int NCH = 64>
 hipError_t launch_v(const WavePassArgs& a, int n_rhs, int epi, int n_pairs, hipStream_t st)
 {
     dim3 grid(a.pitch / VCW, n_pairs), block(VT);
-    constexpr int N_EPI = EPI_U8 + 1;
+    constexpr int N_EPI = N_EPILOGUES;
     if (n_rhs < 1 || n_rhs > 2 || epi < 0 || epi >= N_EPI) return hipErrorInvalidValue;
     return dispatch_index<2 * N_EPI>((n_rhs - 1) * N_EPI + epi, [&](auto K) {
         constexpr int R = decltype(K)::value / N_EPI + 1, EPI = decltype(K)::value % N_EPI;
         // (two right-hand sides with a generic epilogue: channel pairs of a generic FGS source)
-        if constexpr (R == 1 && EPI == EPI_WLS_CONF) return hipErrorInvalidValue;   // the ratio needs both right-hand sides
+        if constexpr (R == 1 && (EPI == EPI_WLS_CONF || EPI == EPI_WLS_CONF_F32)) return hipErrorInvalidValue;   // the ratio needs both right-hand sides
         else {
             hipLaunchKernelGGL((wave_vpass_kernel<M, R, EPI, VCW, NCH>), grid, block, 0, st, a);
             return hipGetLastError();
@@ -308,6 +356,7 @@ int wave_max_col_len() { return COL_BUCKETS[N_COL_BUCKETS - 1].m * COL_BUCKETS[N
 hipError_t launch_wave_vpass(const WavePassArgs& a, int n_rhs, int epilogue, int n_pairs, hipStream_t st)
 {
     if (a.len < 2 || a.len > wave_max_col_len() || a.pitch % 64 != 0 || a.pitch < a.nscan) return hipErrorInvalidValue;
+    if (epilogue == EPI_WLS_CONF_F32 && a.out_cn != 1) return hipErrorInvalidValue;
     return dispatch_index<N_COL_BUCKETS>(bucket_index(COL_BUCKETS, a.len), [&](auto I) {
         constexpr Bucket b = COL_BUCKETS[decltype(I)::value];
         return launch_v<b.m, b.chunks == 64 ? VC : VC / 2, b.chunks>(a, n_rhs, epilogue, n_pairs, st);

@@ -243,6 +243,19 @@ class DisparityWLSFilter(_Handle, DisparityFilter):
     # ---- DisparityFilter::filter (DF.hpp:75) ----
     def filter(self, disparity_map_left, left_view, filtered_disparity_map=None,
                disparity_map_right=None, ROI=None, right_view=None):
+        return self._filter("adf_wls_filter_scaled", np.int16, disparity_map_left, left_view, filtered_disparity_map,
+                            disparity_map_right, ROI)
+
+    def filterFloat(self, disparity_map_left, left_view, filtered_disparity_map=None,
+                    disparity_map_right=None, ROI=None):
+        """Extension (adf_wls_filter*_f32_*, include/adf_wls.h): filter() with a float32 filtered map that keeps what the
+        rounding to 1/16 pixel throws away.  Same inputs and rules; the map is in the int16 map's units (disparity * 16),
+        -16.0 outside the ROI, never NaN or inf, and rounding it (half to even, saturated to int16) gives filter()'s map
+        bit for bit."""
+        return self._filter("adf_wls_filter_scaled_f32", np.float32, disparity_map_left, left_view, filtered_disparity_map,
+                            disparity_map_right, ROI)
+
+    def _filter(self, entry, out_dtype, disparity_map_left, left_view, filtered_disparity_map, disparity_map_right, ROI):
         if disparity_map_left is None:
             raise AdfError(_lib.ADF_EBADARG, "disparity_map_left is empty")
         if left_view is None:
@@ -263,8 +276,8 @@ class DisparityWLSFilter(_Handle, DisparityFilter):
         if gv.device != dl.device or (dr is not None and dr.device != dl.device):
             raise AdfError(_lib.ADF_EBADARG, "inputs must all be numpy arrays or all be CUDA tensors")
         if filtered_disparity_map is None:
-            filtered_disparity_map = _out_like(gv, batched, np.int16)
-        out = _Image(filtered_disparity_map, np.int16, "filtered_disparity_map", batched)
+            filtered_disparity_map = _out_like(gv, batched, out_dtype)
+        out = _Image(filtered_disparity_map, out_dtype, "filtered_disparity_map", batched)
         if (out.n, out.h, out.w) != (gv.n, gv.h, gv.w) or out.device != dl.device:               # DF.cpp:252,282
             raise AdfError(_lib.ADF_ESIZE, "filtered_disparity_map has the wrong size or placement")
         if dl.device:
@@ -278,9 +291,9 @@ class DisparityWLSFilter(_Handle, DisparityFilter):
                 C.byref(roi) if roi is not None else None)
         # (the one fork written out instead of going through _call: this call's host time is counted in microseconds)
         if dl.device:
-            _lib.check(_lib.lib().adf_wls_filter_scaled_device(*args, _stream_of(dl)))
+            _lib.check(getattr(_lib.lib(), entry + "_device")(*args, _stream_of(dl)))
         else:
-            _lib.check(_lib.lib().adf_wls_filter_scaled_host(*args))
+            _lib.check(getattr(_lib.lib(), entry + "_host")(*args))
         self._last = (batched, dl.device, gv)
         return filtered_disparity_map
 

@@ -175,6 +175,57 @@ int adf_wls_filter_scaled_host(adf_wls_t* h, int n_pairs,
                                const int16_t* disp_right, ptrdiff_t disp_right_stride, ptrdiff_t disp_right_pair_stride,
                                const adf_rect* roi);
 
+/* Extension (no counterpart in the reference, which ends in disp_mul_conf.convertTo(dst, CV_16S), DF.cpp:296): the same
+ * four calls with a CV_32FC1 filtered map that keeps what the rounding to 1/16 pixel throws away -- for callers that go
+ * on to depth (f*B/d) or point clouds, where the 1/16-pixel staircase is the dominant error on small disparities.  Every
+ * argument means what it means above; `out` is float*, W x H, strides in bytes.
+ *   - Units: those of the int16 map, disparity * 16.  The value stored is exactly the float the int16 epilogue rounds:
+ *     u0 * (1 / (u1 + EPS)) of the two filtered planes in confidence mode (DF.cpp:295; EPS = 1e-43f, DF.cpp:47), u0
+ *     without confidence (DF.cpp:257-258).
+ *   - Outside the ROI every pixel is -16.0f: the int16 map's fill, 16 * (min_disp - 1) with min_disp ignored
+ *     (DF.cpp:146,149,254,284).
+ *   - Where the int16 map saturates to -32768 because the value is not finite or |x| >= 2^31 (u1 == 0 exactly: a ROI
+ *     without a single confident pixel gives 0 * inf), the float map holds -32768.0f.  It never holds NaN or inf.
+ *     Finite values beyond the int16 range are stored as they are.
+ *   - Rounding relation: for the same handle, inputs, parameters and solver, saturate_cast<short>(out_f32) -- cvRound,
+ *     half to even, clamped to [-32768, 32767] -- equals the map adf_wls_filter* writes, bit for bit, inside and
+ *     outside the ROI.
+ *   - adf_wls_get_confidence_*, adf_wls_get_roi, adf_wls_get_last_solver, adf_wls_get_last_path, profiling (the float
+ *     map counts 4 bytes per pixel), stream capture, the fallback to ADF_SOLVER_EXACT beyond 8192 x 4352 and the chunked
+ *     workspace behave as for the int16 call.
+ *   - Alignment: `out`, out_stride and out_pair_stride must be multiples of 4 bytes (ADF_EBADARG otherwise).  A base or
+ *     strides that are not multiples of 8, or an odd ROI x, give the same bits through a slower store path. */
+int adf_wls_filter_f32_device(adf_wls_t* h, int n_pairs,
+                              const int16_t* disp_left, ptrdiff_t disp_left_stride, ptrdiff_t disp_left_pair_stride,
+                              const uint8_t* left_view, ptrdiff_t view_stride, ptrdiff_t view_pair_stride,
+                              int view_channels, int W, int H,
+                              float* out, ptrdiff_t out_stride, ptrdiff_t out_pair_stride,
+                              const int16_t* disp_right, ptrdiff_t disp_right_stride, ptrdiff_t disp_right_pair_stride,
+                              const adf_rect* roi, void* stream);
+int adf_wls_filter_f32_host(adf_wls_t* h, int n_pairs,
+                            const int16_t* disp_left, ptrdiff_t disp_left_stride, ptrdiff_t disp_left_pair_stride,
+                            const uint8_t* left_view, ptrdiff_t view_stride, ptrdiff_t view_pair_stride,
+                            int view_channels, int W, int H,
+                            float* out, ptrdiff_t out_stride, ptrdiff_t out_pair_stride,
+                            const int16_t* disp_right, ptrdiff_t disp_right_stride, ptrdiff_t disp_right_pair_stride,
+                            const adf_rect* roi);
+int adf_wls_filter_scaled_f32_device(adf_wls_t* h, int n_pairs,
+                                     const int16_t* disp_left, ptrdiff_t disp_left_stride, ptrdiff_t disp_left_pair_stride,
+                                     int disp_W, int disp_H,
+                                     const uint8_t* left_view, ptrdiff_t view_stride, ptrdiff_t view_pair_stride,
+                                     int view_channels, int W, int H,
+                                     float* out, ptrdiff_t out_stride, ptrdiff_t out_pair_stride,
+                                     const int16_t* disp_right, ptrdiff_t disp_right_stride, ptrdiff_t disp_right_pair_stride,
+                                     const adf_rect* roi, void* stream);
+int adf_wls_filter_scaled_f32_host(adf_wls_t* h, int n_pairs,
+                                   const int16_t* disp_left, ptrdiff_t disp_left_stride, ptrdiff_t disp_left_pair_stride,
+                                   int disp_W, int disp_H,
+                                   const uint8_t* left_view, ptrdiff_t view_stride, ptrdiff_t view_pair_stride,
+                                   int view_channels, int W, int H,
+                                   float* out, ptrdiff_t out_stride, ptrdiff_t out_pair_stride,
+                                   const int16_t* disp_right, ptrdiff_t disp_right_stride, ptrdiff_t disp_right_pair_stride,
+                                   const adf_rect* roi);
+
 /* getConfidenceMap() (DF.hpp:117, DF.cpp:138): CV_32FC1, W x H, values in [0,255],
  * zero outside the ROI, of pair `pair` of the last filter call.  Valid until the
  * next filter call on the handle. */

@@ -179,6 +179,12 @@ public:
     virtual Rect getROI() = 0;
     // extension: ADF_SOLVER_EXACT (bit-exact scalar order) or ADF_SOLVER_WAVE (on-chip, <= 1 LSB)
     virtual void setSolver(int solver) = 0;
+    // extension (adf_wls_filter*_f32_* in adf_wls.h): filter() with a CV_32FC1 filtered map, view-sized, that keeps what
+    // the rounding to 1/16 pixel throws away -- the int16 map's units (disparity * 16), -16.0f outside the ROI, never
+    // NaN or inf, and saturate_cast<short> of it is filter()'s map bit for bit.  Same rules as filter(), the
+    // lower-resolution maps included.
+    virtual void filterToFloat(const Mat& disparity_map_left, const Mat& left_view, Mat& filtered_disparity_map,
+                               const Mat& disparity_map_right = Mat(), Rect ROI = Rect()) = 0;
 };
 
 class DisparityWLSFilterImpl : public DisparityWLSFilter {
@@ -196,6 +202,16 @@ public:
 
     void filter(const Mat& dl, const Mat& view, Mat& out, const Mat& dr, Rect ROI, const Mat&) override
     {
+        run(dl, view, out, dr, ROI, false);
+    }
+    void filterToFloat(const Mat& dl, const Mat& view, Mat& out, const Mat& dr, Rect ROI) override
+    {
+        run(dl, view, out, dr, ROI, true);
+    }
+private:
+    // filter() and filterToFloat(): one set of checks, the output's depth and the entry point differ
+    void run(const Mat& dl, const Mat& view, Mat& out, const Mat& dr, Rect ROI, bool f32)
+    {
         if (dl.empty() || mat_depth(dl) != D16S || mat_channels(dl) != 1)       // DF.cpp:221
             throw Exception(ADF_EBADARG, "disparity_map_left must be a non-empty CV_16SC1 image");
         if (view.empty() || mat_depth(view) != D8U || (mat_channels(view) != 1 && mat_channels(view) != 3)) // :222
@@ -207,16 +223,24 @@ public:
             if (dr.rows != dl.rows || dr.cols != dl.cols)
                 throw Exception(ADF_ESIZE, "left and right disparity maps differ in size");
         }
-        mat_create(out, view.rows, view.cols, D16S, 1);                        // DF.cpp:252,282 (view-sized)
+        mat_create(out, view.rows, view.cols, f32 ? D32F : D16S, 1);           // DF.cpp:252,282 (view-sized)
         adf_rect roi{ROI.x, ROI.y, ROI.width, ROI.height};
+        const int16_t* l = reinterpret_cast<const int16_t*>(dl.data);
+        const int16_t* r = have_r ? reinterpret_cast<const int16_t*>(dr.data) : nullptr;
+        const ptrdiff_t rs = have_r ? mat_step(dr) : 0;
+        const adf_rect* rp = ROI.area() != 0 ? &roi : nullptr;
         // a lower-resolution disparity map is resized to the view inside the call (DF.cpp:239-247,268-277)
-        check(adf_wls_filter_scaled_host(h_, 1, reinterpret_cast<const int16_t*>(dl.data), mat_step(dl), 0, dl.cols, dl.rows,
-                                  view.data, mat_step(view), 0, mat_channels(view), view.cols, view.rows,
-                                  reinterpret_cast<int16_t*>(out.data), mat_step(out), 0,
-                                  have_r ? reinterpret_cast<const int16_t*>(dr.data) : nullptr, have_r ? mat_step(dr) : 0, 0,
-                                  ROI.area() != 0 ? &roi : nullptr));
+        if (f32)
+            check(adf_wls_filter_scaled_f32_host(h_, 1, l, mat_step(dl), 0, dl.cols, dl.rows, view.data, mat_step(view), 0,
+                                                 mat_channels(view), view.cols, view.rows,
+                                                 reinterpret_cast<float*>(out.data), mat_step(out), 0, r, rs, 0, rp));
+        else
+            check(adf_wls_filter_scaled_host(h_, 1, l, mat_step(dl), 0, dl.cols, dl.rows, view.data, mat_step(view), 0,
+                                             mat_channels(view), view.cols, view.rows,
+                                             reinterpret_cast<int16_t*>(out.data), mat_step(out), 0, r, rs, 0, rp));
         last_rows_ = view.rows; last_cols_ = view.cols;
     }
+public:
     double getLambda() override { double v; check(adf_wls_get_lambda(h_, &v)); return v; }
     void setLambda(double v) override { check(adf_wls_set_lambda(h_, v)); }
     double getSigmaColor() override { double v; check(adf_wls_get_sigma_color(h_, &v)); return v; }
