@@ -65,6 +65,65 @@ __device__ __forceinline__ v2f epi_f32(v2f u0, v2f u1)
     return x;
 }
 
+// ---- the single-channel store forms of the fused epilogues ----
+// Both columns of a thread in the map's own type: a packed dword with 2-byte halves (int16 maps) or a v2f with 4-byte
+// halves (float maps).
+template <int EPI, bool F32>
+__device__ __forceinline__ auto epi_out(v2f u0, v2f u1)
+{
+    if constexpr (F32) return epi_f32<EPI>(u0, u1);
+    else return epi_pack16<EPI>(u0, u1);
+}
+__device__ __forceinline__ void put_first(char* dst, unsigned v) { reinterpret_cast<uint16_t*>(dst)[0] = (uint16_t)v; }
+__device__ __forceinline__ void put_first(char* dst, v2f v) { reinterpret_cast<float*>(dst)[0] = v.x; }
+__device__ __forceinline__ void put_second(char* dst, unsigned v) { reinterpret_cast<uint16_t*>(dst)[1] = (uint16_t)(v >> 16); }
+__device__ __forceinline__ void put_second(char* dst, v2f v) { reinterpret_cast<float*>(dst)[1] = v.y; }
+__device__ __forceinline__ void put_both(char* dst, unsigned v) { *reinterpret_cast<unsigned*>(dst) = v; }
+__device__ __forceinline__ void put_both(char* dst, v2f v) { *reinterpret_cast<v2f*>(dst) = v; }
+
+// Can a column pair of a single-channel map of `esz`-byte elements go out as ONE store of 2 * esz bytes: do the map's
+// base, its strides and the ROI's first column keep every pair that much aligned?  (uniform over the launch)
+__device__ __forceinline__ bool out_pairs_aligned(const WavePassArgs& a, unsigned esz)
+{
+    const unsigned m = 2u * esz - 1u;
+    return ((reinterpret_cast<uintptr_t>(a.out) | (uintptr_t)a.out_stride | (uintptr_t)a.out_pair_stride) & m) == 0 &&
+           (((unsigned)a.out_x0 * esz) & m) == 0;
+}
+
+// The thread's M rows of a single-channel map, from dst down: row i < hv2 stores both columns -- as one store when
+// `aligned`, as two halves otherwise -- and, in the form with LAST_ODD, row i < hv1 its first column only (the thread
+// that holds the last column of an odd-width ROI).  No branch but the row masks; every other condition is uniform
+// over the launch.  Without LAST_ODD neither the hv1 compare nor its store is compiled: that is the form of every
+// disparity-filter call on an even-width ROI.
+template <int EPI, bool F32, bool LAST_ODD, int M>
+__device__ __forceinline__ void store_rows(const v2f (&f0)[M], const v2f (&f1)[M], char* dst, ptrdiff_t stride, bool aligned, int hv2, int hv1)
+{
+#pragma unroll
+    for (int i = 0; i < M; i++) {
+        const auto v = epi_out<EPI, F32>(f0[i], f1[i]);
+        if (i < hv2) {
+            if (aligned) put_both(dst, v);
+            else { put_first(dst, v); put_second(dst, v); }
+        }
+        if constexpr (LAST_ODD) {
+            if (i < hv1) put_first(dst, v);
+        }
+        dst += stride;
+        ADF_STEP_FENCE();
+    }
+}
+
+// Bytes from row r0 + i of a column to row r0 + i + 1 in the plane of the right-hand sides.  Pair plane (R == 2):
+// [row tile][strip][row in tile][32 floats]; consecutive rows are 128 bytes apart inside a tile and a tile apart
+// (minus the rows already walked) at a tile boundary -- which rows those are depends on the chunk's start.
+template <int R>
+__device__ __forceinline__ unsigned vstep(int r0, int i, int pitch)
+{
+    constexpr unsigned TR = TILE_ROWS;
+    if (R > 1) return ((((unsigned)r0 + (unsigned)i + 1u) & (TR - 1u)) == 0u) ? 2u * TR * (unsigned)pitch * 4u - (TR - 1u) * 128u : 128u;
+    return (unsigned)pitch * 4u;
+}
+
 template <int M, int R, int EPI, int VCW = VC, int NCH = 64>
 __global__ void __launch_bounds__(VT) wave_vpass_kernel(WavePassArgs a)
 {
@@ -109,12 +168,7 @@ __global__ void __launch_bounds__(VT) wave_vpass_kernel(WavePassArgs a)
     const char* bC = reinterpret_cast<const char*>(a.C + pb);
     char* b0 = reinterpret_cast<char*>(a.U0 + (R > 1 ? 2 * pb : pb));
     char* b1 = (R > 1) ? b0 + 4 * VC : nullptr;
-    const unsigned pitch_b = (unsigned)a.pitch * (R > 1 ? 8u : 4u);
-    // pair plane: [row tile][strip][row in tile][32 floats]; consecutive rows are 128 bytes apart inside a tile and a
-    // tile apart (minus the rows already walked) at a tile boundary -- which rows those are depends on the chunk's start
     constexpr unsigned TR = TILE_ROWS;
-    const unsigned tile_b = 2u * TR * (unsigned)a.pitch * 4u;            // bytes from a tile to the next one
-#define ADF_VSTEP(i) ((R > 1) ? (((((unsigned)r0 + (unsigned)(i) + 1u) & (TR - 1u)) == 0u) ? tile_b - (TR - 1u) * 128u : 128u) : pitch_b)
     const unsigned voff0 = (R > 1) ? (((unsigned)r0 / TR) * (2u * TR * (unsigned)a.pitch) + (unsigned)strip * (32u * TR) + ((unsigned)r0 % TR) * 32u + c16) * 4u
                                    : ((unsigned)r0 * (unsigned)a.pitch + (unsigned)col) * 4u;
     const unsigned pitch_c = 4u * VC;
@@ -143,7 +197,7 @@ __global__ void __launch_bounds__(VT) wave_vpass_kernel(WavePassArgs a)
             c[i] = *reinterpret_cast<const v2f*>(bC + (ok ? coff : csafe));
             f0[i] = *reinterpret_cast<const v2f*>(b0 + vo);
             f1[i] = (R > 1) ? *reinterpret_cast<const v2f*>(b1 + vo) : vsplat(0.0f);
-            voff += ADF_VSTEP(i); coff += pitch_c;
+            voff += vstep<R>(r0, i, a.pitch); coff += pitch_c;
             ADF_STEP_FENCE();   // one row's addresses at a time: hoisting all of them costs 2 registers per row
         }
 #pragma unroll
@@ -205,7 +259,7 @@ __global__ void __launch_bounds__(VT) wave_vpass_kernel(WavePassArgs a)
                 *reinterpret_cast<v2f*>(b0 + voff) = f0[i];
                 if (R > 1) *reinterpret_cast<v2f*>(b1 + voff) = f1[i];
             }
-            voff += ADF_VSTEP(i);
+            voff += vstep<R>(r0, i, a.pitch);
         }
     } else {
         // (opaque copies made AFTER the solve: nothing of the epilogue's addressing may be formed while the strip
@@ -224,78 +278,20 @@ __global__ void __launch_bounds__(VT) wave_vpass_kernel(WavePassArgs a)
         // Round 4: an ODD number of columns takes the same path -- the one thread per strip row that holds the ROI's last
         // column stores its low half only (2 bytes), everything else is unchanged.
         const bool fast16 = (EPI == EPI_WLS_CONF || EPI == EPI_I16) && a.out_cn == 1;
-        if (fast16 && (a.nscan & 1)) {
-            const bool al4 = ((reinterpret_cast<uintptr_t>(a.out) | (uintptr_t)a.out_stride | (uintptr_t)a.out_pair_stride) & 3u) == 0 &&
-                             ((a.out_x0 * 2) & 3) == 0;
+        // Single-channel float output (adf_wls_filter_f32_*, a one-channel generic smoother): the same, as one float2
+        // -- the eight column pairs of a strip row are one contiguous 64-byte piece -- or as two dwords.
+        const bool fast32 = (EPI == EPI_WLS_CONF_F32 || (EPI == EPI_F32 && R == 1)) && a.out_cn == 1;
+        if (fast16 || fast32) {
             const int hv2 = (cole + 1 < a.nscan ? h : 0) - r0e;   // rows of a thread with two columns inside the ROI
             const int hv1 = (cole + 1 == a.nscan ? h : 0) - r0e;  // ... with only its first column inside
             char* dst = ob + ooff;
-#pragma unroll
-            for (int i = 0; i < M; i++) {
-                const unsigned v = epi_pack16<EPI>(f0[i], f1[i]);
-                if (i < hv2) {
-                    if (al4) *reinterpret_cast<unsigned*>(dst) = v;
-                    else { reinterpret_cast<uint16_t*>(dst)[0] = (uint16_t)v; reinterpret_cast<uint16_t*>(dst)[1] = (uint16_t)(v >> 16); }
-                }
-                if (i < hv1) reinterpret_cast<uint16_t*>(dst)[0] = (uint16_t)v;
-                dst += a.out_stride;
-                ADF_STEP_FENCE();
-            }
-        } else if (fast16) {
-            const bool al4 = ((reinterpret_cast<uintptr_t>(a.out) | (uintptr_t)a.out_stride | (uintptr_t)a.out_pair_stride) & 3u) == 0 &&
-                             ((a.out_x0 * 2) & 3) == 0;
-            const int hv = (cole < a.nscan ? h : 0) - r0e;        // rows of this thread to store (threads on pitch padding: none)
-            char* dst = ob + ooff;
-            if (al4) {
-#pragma unroll
-                for (int i = 0; i < M; i++) {
-                    const unsigned v = epi_pack16<EPI>(f0[i], f1[i]);
-                    if (i < hv) *reinterpret_cast<unsigned*>(dst) = v;
-                    dst += a.out_stride;
-                    ADF_STEP_FENCE();
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < M; i++) {
-                    const unsigned v = epi_pack16<EPI>(f0[i], f1[i]);
-                    if (i < hv) {
-                        reinterpret_cast<uint16_t*>(dst)[0] = (uint16_t)v;
-                        reinterpret_cast<uint16_t*>(dst)[1] = (uint16_t)(v >> 16);
-                    }
-                    dst += a.out_stride;
-                    ADF_STEP_FENCE();
-                }
-            }
-        } else if ((EPI == EPI_WLS_CONF_F32 || (EPI == EPI_F32 && R == 1)) && a.out_cn == 1) {
-            // Single-channel float output (adf_wls_filter_f32_*, a one-channel generic smoother): both columns of the
-            // thread go out as one float2 -- the eight column pairs of a strip row are one contiguous 64-byte piece --
-            // or, when the map's base, strides or ROI x do not keep a pair 8-byte aligned, as two dwords.  The thread
-            // that holds the last column of an odd-width ROI stores its first column only; as in the packed int16 path
-            // there is no branch but the row mask, and every condition is uniform over the launch.
-            const bool al8 = ((reinterpret_cast<uintptr_t>(a.out) | (uintptr_t)a.out_stride | (uintptr_t)a.out_pair_stride) & 7u) == 0 &&
-                             (a.out_x0 & 1) == 0;
-            const int hv2 = (cole + 1 < a.nscan ? h : 0) - r0e;   // rows of a thread with two columns inside the ROI
-            const int hv1 = (cole + 1 == a.nscan ? h : 0) - r0e;  // ... with only its first column inside
-            char* dst = ob + ooff;
-            if (al8) {
-#pragma unroll
-                for (int i = 0; i < M; i++) {
-                    const v2f v = epi_f32<EPI>(f0[i], f1[i]);
-                    if (i < hv2) *reinterpret_cast<v2f*>(dst) = v;
-                    if (i < hv1) reinterpret_cast<float*>(dst)[0] = v.x;
-                    dst += a.out_stride;
-                    ADF_STEP_FENCE();
-                }
-            } else {
-#pragma unroll
-                for (int i = 0; i < M; i++) {
-                    const v2f v = epi_f32<EPI>(f0[i], f1[i]);
-                    if (i < hv2) { reinterpret_cast<float*>(dst)[0] = v.x; reinterpret_cast<float*>(dst)[1] = v.y; }
-                    if (i < hv1) reinterpret_cast<float*>(dst)[0] = v.x;
-                    dst += a.out_stride;
-                    ADF_STEP_FENCE();
-                }
-            }
+            if (fast16 && (a.nscan & 1)) store_rows<EPI, false, true>(f0, f1, dst, a.out_stride, out_pairs_aligned(a, 2), hv2, hv1);
+            else if (fast16) {
+                const int hv = (cole < a.nscan ? h : 0) - r0e;    // rows of this thread to store (threads on pitch padding: none)
+                if (out_pairs_aligned(a, 2)) store_rows<EPI, false, false>(f0, f1, dst, a.out_stride, true, hv, 0);
+                else store_rows<EPI, false, false>(f0, f1, dst, a.out_stride, false, hv, 0);
+            } else if (out_pairs_aligned(a, 4)) store_rows<EPI, true, true>(f0, f1, dst, a.out_stride, true, hv2, hv1);
+            else store_rows<EPI, true, true>(f0, f1, dst, a.out_stride, false, hv2, hv1);
         } else if (EPI != EPI_WLS_CONF_F32) {   // (the ratio as a float is single-channel only: launch_wave_vpass)
 #pragma unroll
         for (int i = 0; i < M; i++) {
