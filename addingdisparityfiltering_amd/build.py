@@ -10,6 +10,7 @@ SOURCES = {
     "adf_api.hip": [],
     "adf_host.hip": [],
     "conf_kernels.hip": [],
+    "rhs_prologue.hip": [],
     "weights_kernels.hip": [],
     "fgs_exact.hip": [],
     "fgs_wave_h.hip": [],

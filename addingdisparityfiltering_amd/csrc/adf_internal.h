@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include "../../include/adf_wls.h" /* the public enums (adf_depth) are the kernels' codes too */
 
 #define ADF_LUT_LEVELS (3 * 256 * 256) /* FGS.cpp:150 */
 #define ADF_EPS 1e-43f                 /* DF.cpp:47  */
@@ -213,6 +214,13 @@ int wave_max_col_len();
 // largest depth-discontinuity radius the tile kernel supports (LDS bound)
 int max_disc_radius();
 
+// The block of the tile kernels of conf_kernels.hip and rhs_prologue.hip (`using namespace tile`): NT threads, TX x TY pixels.
+namespace tile {
+constexpr int TX = 64; // tile width  (one wavefront wide: 128-byte int16 rows, 256-byte float rows)
+constexpr int TY = 32; // tile height
+constexpr int NT = 256;
+}
+
 // Device-side helpers shared by kernels.
 #if defined(__HIPCC__)
 // float index of U0(i, j) inside an ORIENT_PAIR plane of pitch pw (U1 is ADF_STRIP floats further)
@@ -226,6 +234,40 @@ __device__ __forceinline__ size_t strip_index(int i, int j, int rh)
 {
     return ((size_t)(j >> 4) * (size_t)rh + (size_t)i) * ADF_STRIP + (size_t)(j & 15);
 }
+// The two right-hand sides of image pz.  ORIENT_PAIR: the one plane of 2*plane floats per image, U1 ADF_STRIP floats
+// behind U0 (the U1 argument is unused); ORIENT_N / ORIENT_T: a plane each, U1 null where there is one right-hand side.
+struct RhsPlanes { float* U0; float* U1; };
+__device__ __forceinline__ RhsPlanes rhs_planes(float* U0, float* U1, int orient, size_t pz, size_t plane)
+{
+    const bool pair = orient == ORIENT_PAIR;
+    float* u0 = U0 + pz * (pair ? 2 : 1) * plane;
+    return RhsPlanes{u0, pair ? u0 + ADF_STRIP : U1 ? U1 + pz * plane : nullptr};
+}
+// float index of ROI pixel (i, j) inside a right-hand side plane (ORIENT_N, ORIENT_T or ORIENT_PAIR)
+__device__ __forceinline__ size_t rhs_index(int orient, int i, int j, const Geom& g)
+{
+    return orient == ORIENT_PAIR ? pair_index(i, j, g.pw) : orient == ORIENT_T ? (size_t)j * g.ph + i : (size_t)i * g.pw + j;
+}
+// ORIENT_T from a kernel whose threads walk along image rows: thread (tx, ty) stages its pixels (tx, ty + 4*kk) in LDS
+// (odd pitch); after the last one the whole block calls store() with the ROI coordinates (j0, i0) of the tile's first
+// pixel -- negative where the tile starts outside the ROI -- and writes them out with the row index fastest.
+struct RhsTile {
+    float t0[tile::TX * (tile::TY + 1)], t1[tile::TX * (tile::TY + 1)];
+    __device__ __forceinline__ void stage(int tx, int y, float v0, float v1) { t0[tx * (tile::TY + 1) + y] = v0; t1[tx * (tile::TY + 1) + y] = v1; }
+    __device__ __forceinline__ void store(float* U0, float* U1, const Geom& g, int j0, int i0) const
+    {
+        __syncthreads();
+#pragma unroll
+        for (int m = 0; m < tile::TX / 8; m++) {
+            const int cidx = threadIdx.x / tile::TY + 8 * m, ridx = threadIdx.x % tile::TY, j = j0 + cidx, i = i0 + ridx;
+            if ((unsigned)j < (unsigned)g.rw && (unsigned)i < (unsigned)g.rh) {   // (a negative j or i is outside too)
+                const size_t o = rhs_index(ORIENT_T, i, j, g);
+                U0[o] = t0[cidx * (tile::TY + 1) + ridx];
+                if (U1) U1[o] = t1[cidx * (tile::TY + 1) + ridx];
+            }
+        }
+    }
+};
 // One pixel of a filtered map outside the ROI: `fill` as int16, or as the float of the same value (uniform branch).
 __device__ __forceinline__ void store_fill(void* map, ptrdiff_t row_offset_bytes, int j, int16_t fill, int f32)
 {

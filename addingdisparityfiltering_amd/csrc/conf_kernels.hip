@@ -1,13 +1,9 @@
-// conf_kernels.hip -- confidence-map half of DisparityWLSFilter::filter for gfx950.
+// conf_kernels.hip -- confidence-map half of DisparityWLSFilter::filter for gfx950: the discontinuity, left-sweep and
+// band kernels, the fill outside the ROI and the merged preparation launch.  (The two-kernel stage's second kernel,
+// lrc_prologue_kernel, is in rhs_prologue.hip.)
 //
 //   discontinuity_kernel : DF.cpp:161-194 (box mean / mean of squares on the ROI copy,
 //                          BORDER_REFLECT_101) + DF.cpp:343-373 (variance -> roll-off map)
-//   lrc_prologue_kernel  : DF.cpp:306-341 (discontinuity-aware left-right check), DF.cpp:209
-//                          (x255) and DF.cpp:288-290 (conf*float(disp)), fused; writes the
-//                          two right-hand sides of the solve in the orientation the first
-//                          pass wants
-//   plain_prologue_kernel: source channel -> float right-hand side: the no-confidence path's
-//                          float(disp) (DF.cpp:250,257) and FGS.cpp:191-205 (split + convertTo)
 //   outside_kernel       : out = 16*(min_disp-1) = -16 and confidence 0 outside the ROI
 //                          (DF.cpp:149,254,284; :187-190)
 //
@@ -25,11 +21,9 @@ namespace adf {
 
 namespace {
 
+using namespace tile;
 // streaming outputs are written once and read by a later kernel after gigabytes of other traffic
 #define ADF_ST(p, v) __builtin_nontemporal_store((v), (p))
-constexpr int TX = 64; // tile width  (one wavefront wide: 128-byte int16 rows, 256-byte float rows)
-constexpr int TY = 32; // tile height
-constexpr int NT = 256;
 constexpr int MAX_RADIUS = 40;
 
 // One value of a discontinuity map (DF.cpp:369-370) from a window's exact sum s1 and square sum; scale = 1 / window
@@ -335,9 +329,10 @@ __global__ void __launch_bounds__(NT) conf_left_kernel(ConfLeftArgs a)
                     c = 255.0f * c;                               // DF.cpp:209
                     ADF_ST(&conf[(size_t)i_abs * g.cpitch + j_abs], c);
                     if (WRITE_U) {
-                        const size_t o = pz * 2 * g.plane + pair_index(oy, gx_out, g.pw);   // ORIENT_PAIR
-                        a.U0[o] = c * (float)d;                   // DF.cpp:289-290
-                        a.U0[o + ADF_STRIP] = c;
+                        const RhsPlanes u = rhs_planes(a.U0, a.U1, ORIENT_PAIR, pz, g.plane);
+                        const size_t o = rhs_index(ORIENT_PAIR, oy, gx_out, g);
+                        u.U0[o] = c * (float)d;                   // DF.cpp:289-290
+                        u.U1[o] = c;
                     }
                 }
             }
@@ -651,6 +646,16 @@ __global__ void __launch_bounds__(NT) outside_kernel(OutsideArgs a, int nAx, int
     outside_body(a, nAx, nA, blockIdx.x, blockIdx.z);
 }
 
+// The blocks outside_body decodes: nA of part A, nAx (at least 1) across, then nB of part B; in_range: a grid's x holds them.
+struct OutsideGrid { int nAx, nA; size_t nB; bool in_range; };
+inline OutsideGrid outside_grid(const Geom& g)
+{
+    const int side = g.W - g.rw;
+    const int nAx = (side + NT - 1) / NT, nA = side > 0 ? nAx * ((g.rh + OUT_ROWS - 1) / OUT_ROWS) : 0;
+    const size_t nB = ((size_t)(g.H - g.rh) * g.W + (size_t)NT * OUT_ROWS - 1) / ((size_t)NT * OUT_ROWS);
+    return OutsideGrid{nAx > 0 ? nAx : 1, nA, nB, nA + nB <= 0x7fffffffu};
+}
+
 // ---------------------------------------------------------------------------------------
 // Everything a confidence-mode call prepares before its first solve pass, in ONE launch (round 3): blocks
 // [0, nC) are bands of the one-sweep confidence kernel (the longest role first), [nC, nC + nW) blocks of the streaming
@@ -679,175 +684,6 @@ __global__ void __launch_bounds__(64 * CB_MAX_WAVES) prep_small_kernel(PrepArgs 
         prep::weights_stream_body<CH>(a.w, k % a.nWx, k / a.nWx, a.nWy, pz, ws, threadIdx.x < prep::WS_NT);
     } else {
         if (threadIdx.x < NT) outside_body(a.o, a.nOAx, a.nOA, b - (unsigned)(a.nC + a.nW), pz);
-    }
-}
-
-// ---------------------------------------------------------------------------------------
-// LRC + x255 + prologue.  Grid covers the full frame so the confidence plane is written
-// exactly once everywhere (zero outside the ROI, DF.cpp:187-190,209).
-// ---------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(NT) lrc_prologue_kernel(LrcArgs a)
-{
-    __shared__ float t0[TX * (TY + 1)];
-    __shared__ float t1[TX * (TY + 1)];
-    const Geom& g = a.g;
-    const int tid = threadIdx.x, tx = tid % TX, ty = tid / TX;
-    const int x0 = blockIdx.x * TX, y0 = blockIdx.y * TY;
-    const size_t pz = blockIdx.z;
-    const char* pL = reinterpret_cast<const char*>(a.dL) + (ptrdiff_t)pz * a.psL;
-    const char* pR = reinterpret_cast<const char*>(a.dR) + (ptrdiff_t)pz * a.psR;
-    const float* cL = a.cL + pz * g.frame;
-    const float* cR = a.cR + pz * g.frame;
-    float* conf = a.conf + pz * g.cframe + g.cx0;
-    const bool pair = a.orient == ORIENT_PAIR;
-    float* U0 = a.U0 ? a.U0 + pz * (pair ? 2 : 1) * g.plane : nullptr;   // null: confidence only (down-scaled path)
-    float* U1 = a.U0 ? (pair ? U0 + ADF_STRIP : a.U1 + pz * g.plane) : nullptr;
-    const int j = x0 + tx;
-    const int right_end = a.rrx + g.rw;
-
-    // Three phases over the thread's TY/4 pixels -- own values, the gathers they address, then arithmetic and
-    // stores -- so that no loaded value is first used inside the storing loop (stores count in vmcnt on this
-    // target: a wait for a load there would also wait for every store issued before it).
-    constexpr int NK = TY / 4;
-    int dv[NK], drv[NK]; float cv[NK], bv[NK]; bool roi_k[NK], hit[NK];
-#pragma unroll
-    for (int kk = 0; kk < NK; kk++) {
-        const int i = y0 + ty + 4 * kk;
-        roi_k[kk] = i < g.H && j < g.W && j >= g.rx && j < g.rx + g.rw && i >= g.ry && i < g.ry + g.rh;
-        dv[kk] = 0; cv[kk] = 0.0f;
-        if (roi_k[kk]) {
-            dv[kk] = reinterpret_cast<const int16_t*>(pL + (ptrdiff_t)i * a.sL)[j];
-            cv[kk] = cL[(size_t)i * g.W + j];
-        }
-    }
-#pragma unroll
-    for (int kk = 0; kk < NK; kk++) {
-        const int i = y0 + ty + 4 * kk;
-        const int ridx = j - (dv[kk] >> 4);                             // DF.cpp:331
-        hit[kk] = roi_k[kk] && ridx >= a.rrx && ridx < right_end;
-        drv[kk] = 0; bv[kk] = 0.0f;
-        if (hit[kk]) {
-            drv[kk] = reinterpret_cast<const int16_t*>(pR + (ptrdiff_t)i * a.sR)[ridx];
-            bv[kk] = cR[(size_t)i * g.W + ridx];
-        }
-    }
-#pragma unroll
-    for (int kk = 0; kk < NK; kk++) asm volatile("" : "+v"(drv[kk]), "+v"(bv[kk]));   // the one wait for the gathers
-#pragma unroll
-    for (int kk = 0; kk < NK; kk++) {
-        const int i = y0 + ty + 4 * kk;
-        const bool in_frame = i < g.H && j < g.W;
-        const bool in_roi = roi_k[kk];
-        const int d = dv[kk];
-        float c = cv[kk], u0 = 0.0f;
-        if (in_roi) {
-            if (hit[kk]) {
-                if (abs(d + drv[kk]) < a.thresh) c = bv[kk] < c ? bv[kk] : c;   // DF.cpp:334-335 (std::min)
-                else c = 0.0f;                                                  // DF.cpp:337
-            }
-            c = 255.0f * c;                                             // DF.cpp:209
-            u0 = c * (float)d;                                          // DF.cpp:289-290
-        }
-        if (in_frame) {
-            conf[(size_t)i * g.cpitch + j] = c;
-            if (a.out && !in_roi)                                          // DF.cpp:284
-                store_fill(a.out, (ptrdiff_t)pz * a.psO + (ptrdiff_t)i * a.sO, j, a.fill, a.out_f32);
-        }
-        if (!U0) continue;
-        if (a.orient != ORIENT_T) {
-            if (in_roi) {
-                const size_t o = pair ? pair_index(i - g.ry, j - g.rx, g.pw) : (size_t)(i - g.ry) * g.pw + (j - g.rx);
-                U0[o] = u0; U1[o] = c;
-            }
-        } else {
-            t0[tx * (TY + 1) + ty + 4 * kk] = u0;
-            t1[tx * (TY + 1) + ty + 4 * kk] = c;
-        }
-    }
-    if (U0 && a.orient == ORIENT_T) {
-        __syncthreads();
-#pragma unroll
-        for (int m = 0; m < TX / 8; m++) {
-            const int cidx = tid / TY + 8 * m, ridx = tid % TY;
-            const int jj = x0 + cidx, ii = y0 + ridx;
-            if (jj >= g.rx && jj < g.rx + g.rw && ii >= g.ry && ii < g.ry + g.rh && ii < g.H && jj < g.W) {
-                size_t o = (size_t)(jj - g.rx) * g.ph + (ii - g.ry);
-                U0[o] = t0[cidx * (TY + 1) + ridx];
-                U1[o] = t1[cidx * (TY + 1) + ridx];
-            }
-        }
-    }
-}
-
-__global__ void __launch_bounds__(NT) plain_prologue_kernel(PlainPrologueArgs a)
-{
-    __shared__ float t0[TX * (TY + 1)];
-    __shared__ float t1[TX * (TY + 1)];
-    const Geom& g = a.g;
-    const int tid = threadIdx.x, tx = tid % TX, ty = tid / TX;
-    const int x0 = blockIdx.x * TX, y0 = blockIdx.y * TY; // ROI coordinates
-    const size_t pz = blockIdx.z;
-    const char* pL = reinterpret_cast<const char*>(a.src) + (ptrdiff_t)pz * a.pair_stride;
-    const float* cf = a.conf ? a.conf + pz * g.cframe + g.cx0 : nullptr;
-    const bool pair = a.orient == ORIENT_PAIR;          // only with confidence weighting (two right-hand sides)
-    float* U0 = a.U0 + pz * (pair ? 2 : 1) * g.plane;
-    const bool two = a.conf != nullptr || a.pair2;      // two right-hand sides
-    float* U1 = two ? (pair ? U0 + ADF_STRIP : a.U1 + pz * g.plane) : nullptr;
-    const int j = x0 + tx;
-    // loads of all TY/4 pixels first, stores afterwards (see lrc_prologue_kernel)
-    constexpr int NK = TY / 4;
-    float v0[NK], v1[NK];
-#pragma unroll
-    for (int kk = 0; kk < NK; kk++) {
-        const int i = y0 + ty + 4 * kk;
-        const bool ok = i < g.rh && j < g.rw;
-        float u0 = 0.0f, u1 = 0.0f;
-        if (ok) {
-            const char* row = pL + (ptrdiff_t)(g.ry + i) * a.stride;
-            const size_t e = (size_t)(g.rx + j) * a.cn + a.c;
-            if (a.depth == 3) u0 = (float)reinterpret_cast<const int16_t*>(row)[e];      // CV_16S
-            else if (a.depth == 0) u0 = (float)reinterpret_cast<const uint8_t*>(row)[e]; // CV_8U
-            else u0 = reinterpret_cast<const float*>(row)[e];                            // CV_32F
-            if (a.pair2) {                                                               // second channel, FGS.cpp:200-205
-                const size_t e2 = (size_t)(g.rx + j) * a.cn + a.c2;
-                if (a.depth == 3) u1 = (float)reinterpret_cast<const int16_t*>(row)[e2];
-                else if (a.depth == 0) u1 = (float)reinterpret_cast<const uint8_t*>(row)[e2];
-                else u1 = reinterpret_cast<const float*>(row)[e2];
-            }
-            if (cf) {                                                                    // DF.cpp:286-290
-                u1 = cf[(size_t)(g.ry + i) * g.cpitch + g.rx + j];
-                u0 = u1 * u0;
-            }
-        }
-        v0[kk] = u0; v1[kk] = u1;
-    }
-#pragma unroll
-    for (int kk = 0; kk < NK; kk++) asm volatile("" : "+v"(v0[kk]), "+v"(v1[kk]));   // the one wait
-#pragma unroll
-    for (int kk = 0; kk < NK; kk++) {
-        const int i = y0 + ty + 4 * kk;
-        const bool ok = i < g.rh && j < g.rw;
-        if (a.orient != ORIENT_T) {
-            if (ok) {
-                const size_t o = pair ? pair_index(i, j, g.pw) : (size_t)i * g.pw + j;
-                U0[o] = v0[kk]; if (two) U1[o] = v1[kk];
-            }
-        } else {
-            t0[tx * (TY + 1) + ty + 4 * kk] = v0[kk];
-            t1[tx * (TY + 1) + ty + 4 * kk] = v1[kk];
-        }
-    }
-    if (a.orient == ORIENT_T) {
-        __syncthreads();
-#pragma unroll
-        for (int m = 0; m < TX / 8; m++) {
-            const int cidx = tid / TY + 8 * m, ridx = tid % TY;
-            const int jj = x0 + cidx, ii = y0 + ridx;
-            if (jj < g.rw && ii < g.rh) {
-                U0[(size_t)jj * g.ph + ii] = t0[cidx * (TY + 1) + ridx];
-                if (two) U1[(size_t)jj * g.ph + ii] = t1[cidx * (TY + 1) + ridx];
-            }
-        }
     }
 }
 
@@ -1069,13 +905,10 @@ hipError_t launch_prep_small(const ConfBandArgs& c0, const WeightArgs& w, const 
     if (wrows < 4) wrows = 4;
     a.nWy = (g.rh + wrows - 1) / wrows;
     a.nW = a.nWx * a.nWy;
-    const int side = g.W - g.rw;
-    a.nOAx = (side + NT - 1) / NT;
-    a.nOA = side > 0 ? a.nOAx * ((g.rh + OUT_ROWS - 1) / OUT_ROWS) : 0;
-    if (a.nOAx < 1) a.nOAx = 1;
-    const size_t npix = (size_t)(g.H - g.rh) * g.W;
-    const int nOB = (int)((npix + (size_t)NT * OUT_ROWS - 1) / ((size_t)NT * OUT_ROWS));
-    const dim3 grid(a.nC + a.nW + a.nOA + nOB, n_pairs), block(64 * waves);
+    const OutsideGrid og = outside_grid(g);
+    if (!og.in_range) return hipErrorInvalidValue;
+    a.nOAx = og.nAx; a.nOA = og.nA;
+    const dim3 grid(a.nC + a.nW + og.nA + (int)og.nB, n_pairs), block(64 * waves);
     if (sh.lds + sizeof(prep::WsShared<3>) > 150 * 1024) return hipErrorInvalidValue;
     const auto k = dispatch_radius<1, 5>(c0.radius, [&](auto R) {
         return w.ch == 1 ? &prep_small_kernel<1, decltype(R)::value> : &prep_small_kernel<3, decltype(R)::value>;
@@ -1099,27 +932,10 @@ hipError_t launch_conf_left(const ConfLeftArgs& a, int n_pairs, hipStream_t st)
 
 hipError_t launch_outside(const OutsideArgs& a, int n_pairs, hipStream_t st)
 {
-    const int side = a.g.W - a.g.rw;
-    const int nAx = (side + NT - 1) / NT, nA = side > 0 ? nAx * ((a.g.rh + OUT_ROWS - 1) / OUT_ROWS) : 0;
-    const size_t npix = (size_t)(a.g.H - a.g.rh) * a.g.W;
-    const size_t nB = (npix + (size_t)NT * OUT_ROWS - 1) / ((size_t)NT * OUT_ROWS);
-    if (nA + nB == 0) return hipSuccess;
-    if (nA + nB > 0x7fffffffu) return hipErrorInvalidValue;
-    hipLaunchKernelGGL(outside_kernel, dim3((unsigned)(nA + nB), 1, n_pairs), dim3(NT), 0, st, a, nAx > 0 ? nAx : 1, nA);
-    return hipGetLastError();
-}
-
-hipError_t launch_lrc_prologue(const LrcArgs& a, int n_pairs, hipStream_t st)
-{
-    dim3 grid((a.g.W + TX - 1) / TX, (a.g.H + TY - 1) / TY, n_pairs);
-    hipLaunchKernelGGL(lrc_prologue_kernel, grid, dim3(NT), 0, st, a);
-    return hipGetLastError();
-}
-
-hipError_t launch_plain_prologue(const PlainPrologueArgs& a, int n_pairs, hipStream_t st)
-{
-    dim3 grid((a.g.rw + TX - 1) / TX, (a.g.rh + TY - 1) / TY, n_pairs);
-    hipLaunchKernelGGL(plain_prologue_kernel, grid, dim3(NT), 0, st, a);
+    const OutsideGrid og = outside_grid(a.g);
+    if (og.nA + og.nB == 0) return hipSuccess;
+    if (!og.in_range) return hipErrorInvalidValue;
+    hipLaunchKernelGGL(outside_kernel, dim3((unsigned)(og.nA + og.nB), 1, n_pairs), dim3(NT), 0, st, a, og.nAx, og.nA);
     return hipGetLastError();
 }
 

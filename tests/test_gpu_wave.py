@@ -155,8 +155,9 @@ def test_batch_equals_singles_and_full_width(adf, oracle):
 
 
 # every chunk-length bucket of the row pass (fgs_wave_h.hip: 4..64 elements per lane), at a width that fills
-# it and at one just past the previous bucket, with an ROI the fused first pass accepts (x, width multiples
-# of 4) and one it must refuse (odd x / width: the pair plane is then written by the confidence kernel)
+# it and at one just past the previous bucket, with an aligned ROI (x, width multiples of 4) and an unaligned
+# one (odd x / width; the fused first pass takes both: wave_hpass_can_fuse refuses only rows under 4 pixels, and
+# tests/test_gpu_rhs_prologue.py covers the confidence kernel writing the pair plane)
 # (round 3: beyond 4096 columns two wavefronts share a row -- 128 chunks of 40..64 elements, a 128-row reduced system)
 @pytest.mark.parametrize("width", [256, 260, 512, 1024, 1100, 1280, 1792, 2500, 2560, 3584, 3700, 3840, 3844, 4096,
                                    4100, 5120, 5124, 6144, 7168, 7680, 7700, 8192])
