@@ -16,12 +16,16 @@ from .ximgproc import (  # noqa: F401
     PATH_MERGED_PREP,
     PATH_SCALED_FUSED,
     PATH_SCALED_HALF,
+    SGBM_COST_BT,
+    SGBM_COST_CENSUS_DENSE,
+    SGBM_COST_CENSUS_SPARSE,
     SOLVER_EXACT,
     SOLVER_WAVE,
     StereoBM,
     StereoMatcher,
     StereoSGBM,
     UNKNOWN_DISPARITY,
+    censusTransform,
     computeBadPixelPercent,
     computeMSE,
     createDisparityWLSFilter,

@@ -14,6 +14,7 @@ ADF_OK, ADF_EBADARG, ADF_ESIZE, ADF_EHIP, ADF_ENOMEM, ADF_ENODEV = range(6)
 SOLVER_EXACT, SOLVER_WAVE = 0, 1
 PATH_CONF_BAND, PATH_FUSED_FIRST_PASS, PATH_MERGED_PREP, PATH_SCALED_FUSED, PATH_SCALED_HALF = 1, 2, 4, 8, 16    # adf_wls_get_last_path bits (include/adf_wls.h)
 DEPTH_8U, DEPTH_16S, DEPTH_32F = 0, 3, 5
+SGBM_COST_BT, SGBM_COST_CENSUS_DENSE, SGBM_COST_CENSUS_SPARSE = 0, 1, 2    # adf_sgbm_set_cost (include/adf_wls.h)
 
 
 class AdfError(RuntimeError):
@@ -105,8 +106,12 @@ SYMBOLS = [
     ("adf_sgbm_get_params", _i, [_vp] + [C.POINTER(_i)] * 8),
     ("adf_sgbm_set_disp12_max_diff", _i, [_vp, _i]),
     ("adf_sgbm_get_disp12_max_diff", _i, [_vp, C.POINTER(_i)]),
+    ("adf_sgbm_set_cost", _i, [_vp, _i, _i]),
+    ("adf_sgbm_get_cost", _i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
     ("adf_sgbm_compute_device", _i, [_vp, _i, _vp, _pd, _pd, _vp, _pd, _pd, _i, _i, _i, _vp, _pd, _pd, _vp]),
     ("adf_sgbm_compute_host", _i, [_vp, _i, _vp, _pd, _pd, _vp, _pd, _pd, _i, _i, _i, _vp, _pd, _pd]),
+    ("adf_census_transform_device", _i, [_i, _vp, _pd, _pd, _i, _i, _i, _i, _vp, _pd, _pd, _vp]),
+    ("adf_census_transform_host", _i, [_i, _vp, _pd, _pd, _i, _i, _i, _i, _vp, _pd, _pd]),
     ("adf_filter_speckles_workspace_bytes", _sz, [_i, _i, _i]),
     ("adf_filter_speckles_device", _i, [_i, _vp, _pd, _pd, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     ("adf_filter_speckles_host", _i, [_i, _vp, _pd, _pd, _i, _i, _i, _i, _i]),

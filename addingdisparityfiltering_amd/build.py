@@ -19,6 +19,7 @@ SOURCES = {
     "resize_kernels.hip": [],
     "bm_matcher.hip": [],
     "sgbm_matcher.hip": [],
+    "census_kernels.hip": [],
     "speckle_kernels.hip": [],
     "view_prep_kernels.hip": [],
 }

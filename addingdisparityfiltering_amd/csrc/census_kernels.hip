@@ -1,0 +1,161 @@
+// census_kernels.hip -- the census transform on the device: the descriptor the semi-global matcher's Hamming cost
+// compares (sgbm_matcher.hip, ADF_SGBM_COST_CENSUS_*), and adf_census_transform_* of include/adf_wls.h.
+//
+// The reference's own semi-global matcher, cv::stereo::StereoBinarySGBM, matches on census descriptors
+// (modules/stereo/src/stereo_binary_sgbm.cpp, include/opencv2/stereo/descriptor.hpp, src/descriptor.cpp).  What is built
+// here is the published transform (Zabih & Woodfill 1994) with the bit rule of descriptor.hpp:182-194 (a bit is 1 when
+// the neighbour is larger than the centre, the first comparison ends up most significant) and the two sampling grids
+// of descriptor.cpp:65-74 (every offset / every second offset).  It is THIS LIBRARY'S definition, not a bit-level copy
+// of the in-tree code, which is no usable oracle: its row ranges read one row past Range::end (descriptor.hpp:219), it
+// compares a row OFFSET with a row INDEX to skip the centre (`ii != i`, descriptor.hpp:234), and it leaves the border
+// pixels unwritten (descriptor.hpp:222).  Here neighbour coordinates are clamped to the image (replicated edge), so every
+// pixel has a descriptor, and the offset (0, 0) is skipped where the grid passes through it.
+//
+// Bit order: rows top to bottom, left to right within a row; the first comparison is bit nbits-1, the upper 64 - nbits
+// bits are zero.  One uint64 per pixel.
+#include "census.h"
+
+#include <algorithm>
+
+using namespace adf;
+
+namespace {
+
+struct CensusArgs {
+    const uint8_t* src; ptrdiff_t sstride, simage;
+    uint64_t* dst; ptrdiff_t dstride, dimage;       // bytes
+    int W, H;
+};
+
+constexpr int CT_W = 64, CT_H = 16;                 // pixels of a workgroup: a wave per row, four rows per sweep
+
+// One workgroup: the 64 x 16 tile plus its K/2 halo on every side in LDS (coordinates clamped while it is loaded, so
+// an image smaller than the window is all replicated edge), then one pixel per lane and sweep: K*K - 1 (dense) or
+// fewer (sparse) byte compares against the centre, fully unrolled, and one 8-byte store per lane.
+template <bool SPARSE, int K>
+__global__ void __launch_bounds__(256) census_kernel(CensusArgs a)
+{
+    constexpr int N2 = K / 2, STEP = SPARSE ? 2 : 1;
+    constexpr int PER_AXIS = 2 * N2 / STEP + 1, NBITS = PER_AXIS * PER_AXIS - (N2 % STEP == 0 ? 1 : 0);
+    constexpr int LW = CT_W + 2 * N2, LH = CT_H + 2 * N2;
+    __shared__ uint8_t tile[LH][LW];
+    const int x0 = blockIdx.x * CT_W, y0 = blockIdx.y * CT_H;
+    const uint8_t* src = a.src + (ptrdiff_t)blockIdx.z * a.simage;
+    for (int i = threadIdx.x; i < LH * LW; i += 256) {
+        const int r = i / LW, c = i - r * LW;
+        const int y = min(max(y0 - N2 + r, 0), a.H - 1), x = min(max(x0 - N2 + c, 0), a.W - 1);
+        tile[r][c] = src[(ptrdiff_t)y * a.sstride + x];
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int x = x0 + lane;
+    if (x >= a.W) return;
+    for (int r = wv; r < CT_H; r += 4) {
+        const int y = y0 + r;
+        if (y >= a.H) break;
+        const uint32_t centre = tile[r + N2][lane + N2];
+        uint32_t hi = 0, lo = 0;
+        int bit = NBITS - 1;                                   // (a compile-time constant at every use: both loops unroll)
+#pragma unroll
+        for (int dy = -N2; dy <= N2; dy += STEP)
+#pragma unroll
+            for (int dx = -N2; dx <= N2; dx += STEP) {
+                if (dy == 0 && dx == 0) continue;
+                const uint32_t b = tile[r + N2 + dy][lane + N2 + dx] > centre ? 1u : 0u;
+                if (bit >= 32) hi |= b << (bit - 32);
+                else lo |= b << bit;
+                bit--;
+            }
+        uint64_t* row = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(a.dst) + (ptrdiff_t)blockIdx.z * a.dimage + (ptrdiff_t)y * a.dstride);
+        row[x] = ((uint64_t)hi << 32) | lo;
+    }
+}
+
+template <bool SPARSE, int K>
+void census_launch(const CensusArgs& a, int n, hipStream_t st)
+{
+    hipLaunchKernelGGL((census_kernel<SPARSE, K>), dim3((a.W + CT_W - 1) / CT_W, (a.H + CT_H - 1) / CT_H, n), dim3(256), 0, st, a);
+}
+
+int census_args_check(int n, const void* src, ptrdiff_t sstride, ptrdiff_t simage, int W, int H, int type, int k,
+                      const void* dst, ptrdiff_t dstride, ptrdiff_t dimage)
+{
+    if (n <= 0 || !src || !dst) return fail(ADF_EBADARG, "censusTransform: images must be non-NULL, n_images positive");
+    if (int rc = census_check(type, k)) return rc;
+    if (W <= 0 || H <= 0 || sstride < (ptrdiff_t)W || dstride < (ptrdiff_t)W * 8) return fail(ADF_ESIZE, "censusTransform: bad size or stride");
+    if (n > 1 && (simage < 0 || dimage < 0)) return fail(ADF_ESIZE, "censusTransform: image strides must not be negative");
+    if ((reinterpret_cast<uintptr_t>(dst) & 7) || (dstride & 7) || (n > 1 && (dimage & 7)))
+        return fail(ADF_EBADARG, "censusTransform: dst and its strides must be 8-byte aligned (one uint64 per pixel)");
+    return ADF_OK;
+}
+
+} // namespace
+
+int adf::census_check(int census_type, int k)
+{
+    if (census_type != ADF_SGBM_COST_CENSUS_DENSE && census_type != ADF_SGBM_COST_CENSUS_SPARSE)
+        return fail(ADF_EBADARG, "census type %d is not ADF_SGBM_COST_CENSUS_DENSE or ADF_SGBM_COST_CENSUS_SPARSE", census_type);
+    if (census_bits(census_type, k) == 0)
+        return fail(ADF_EBADARG, "census size %d is not supported: odd, 3..7 for the dense and 5..11 for the sparse descriptor "
+                                 "(at most 48 bits)", k);
+    return ADF_OK;
+}
+
+int adf::census_run(int n, const uint8_t* src, ptrdiff_t sstride, ptrdiff_t simage, int W, int H, int census_type, int k,
+                    uint64_t* dst, ptrdiff_t dstride, ptrdiff_t dimage, hipStream_t st)
+{
+    constexpr int MAX_GRID_Z = 65535;
+    const bool sparse = census_type == ADF_SGBM_COST_CENSUS_SPARSE;
+    for (int m0 = 0; m0 < n; m0 += MAX_GRID_Z) {
+        const int nm = std::min(n - m0, MAX_GRID_Z);
+        const CensusArgs a{src + (ptrdiff_t)m0 * simage, sstride, n > 1 ? simage : 0,
+                           reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(dst) + (ptrdiff_t)m0 * dimage), dstride, n > 1 ? dimage : 0, W, H};
+        switch (sparse ? -k : k) {
+        case 3: census_launch<false, 3>(a, nm, st); break;
+        case 5: census_launch<false, 5>(a, nm, st); break;
+        case 7: census_launch<false, 7>(a, nm, st); break;
+        case -5: census_launch<true, 5>(a, nm, st); break;
+        case -7: census_launch<true, 7>(a, nm, st); break;
+        case -9: census_launch<true, 9>(a, nm, st); break;
+        case -11: census_launch<true, 11>(a, nm, st); break;
+        default: return fail(ADF_EBADARG, "census size %d is not supported", k);
+        }
+        const hipError_t e = hipGetLastError();
+        if (e != hipSuccess) return fail(ADF_EHIP, "%s", hipGetErrorString(e));
+    }
+    return ADF_OK;
+}
+
+// ----------------------------------------------------------------------------------------------
+// C-ABI (include/adf_wls.h, "census transform")
+// ----------------------------------------------------------------------------------------------
+extern "C" int adf_census_transform_device(int n_images, const uint8_t* src, ptrdiff_t src_stride, ptrdiff_t src_image_stride,
+                                           int W, int H, int census_type, int census_size,
+                                           uint64_t* dst, ptrdiff_t dst_stride, ptrdiff_t dst_image_stride, void* stream)
+{
+    const int rc = census_args_check(n_images, src, src_stride, src_image_stride, W, H, census_type, census_size, dst, dst_stride, dst_image_stride);
+    if (rc) return rc;
+    return census_run(n_images, src, src_stride, src_image_stride, W, H, census_type, census_size, dst, dst_stride, dst_image_stride,
+                      (hipStream_t)stream);
+}
+
+extern "C" int adf_census_transform_host(int n_images, const uint8_t* src, ptrdiff_t src_stride, ptrdiff_t src_image_stride,
+                                         int W, int H, int census_type, int census_size,
+                                         uint64_t* dst, ptrdiff_t dst_stride, ptrdiff_t dst_image_stride)
+{
+    int rc = census_args_check(n_images, src, src_stride, src_image_stride, W, H, census_type, census_size, dst, dst_stride, dst_image_stride);
+    if (rc) return rc;
+    // one block: the descriptor planes (8-byte aligned at its start), then the source images
+    const size_t srow = (size_t)W, drow = (size_t)W * 8, simg = srow * H, dimg = drow * H;
+    Scratch blk;
+    if ((rc = blk.take((simg + dimg) * (size_t)n_images, nullptr))) return rc;
+    uint64_t* dd = static_cast<uint64_t*>(blk.p);
+    uint8_t* ds = static_cast<uint8_t*>(blk.p) + dimg * n_images;
+    if ((rc = copy_images(ds, srow, simg, src, src_stride, src_image_stride, srow, H, n_images, hipMemcpyHostToDevice, nullptr))) return rc;
+    rc = census_run(n_images, ds, (ptrdiff_t)srow, (ptrdiff_t)simg, W, H, census_type, census_size, dd, (ptrdiff_t)drow, (ptrdiff_t)dimg, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    if ((rc = copy_images(dst, dst_stride, dst_image_stride, dd, drow, dimg, drow, H, n_images, hipMemcpyDeviceToHost, nullptr))) return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return ADF_OK;
+}

@@ -21,8 +21,11 @@
 //                         butterfly + 4 readlanes.  TOP writes the volume S, LEFT adds to it, RIGHT adds, picks the
 //                         winner and fits the sub-pixel parabola (stereo_binary_sgbm.cpp:286-301, 419-446, 519-596)
 //   sgbm_fill_kernel / sgbm_median_kernel   invalid value everywhere first; 3x3 median of the CV_16S map last
+// ADF_SGBM_COST_CENSUS_* (adf_sgbm_set_cost) swaps the first two for the census transform (census_kernels.hip) and a
+// Hamming pixel cost -- what the reference's own matcher, cv::stereo::StereoBinarySGBM, matches on -- through the same
+// cost kernel (the pixel cost is its template policy); everything from the volume C on is the same code.
 // HBM: C, S and L2 volumes of H x width1 x D int16 each (4K, 256 disparities: 4 GB each, per image in flight).
-#include "adf_host.h"
+#include "census.h"
 
 #include <algorithm>
 #include <cstdlib>
@@ -85,7 +88,7 @@ __global__ void __launch_bounds__(256) sgbm_signals_kernel(SignalArgs a)
 // block costs
 // ---------------------------------------------------------------------------------------------------------------
 struct CostArgs {
-    const uint32_t* rec1; const uint32_t* rec2; size_t rec_pair;
+    const uint32_t* rec1; const uint32_t* rec2; size_t rec_pair;     // what the pixel cost reads, per image; dwords per image
     int16_t* C; size_t vol;              // int16 elements per image volume = H * w1 * D
     int W, H, D, minD, minX1, w1, rows_per_band;
 };
@@ -106,13 +109,49 @@ __device__ __forceinline__ us2 bt_pair(const Rec& u, const Rec& v)
     return m >> sh;
 }
 
+// The pixel cost is a policy of the cost kernel: DWORDS per pixel of the planes it reads, MAX_PIXEL (the largest cost of
+// one pixel: whether two disparities fit a register), Own (a lane's image-1 pixel, loaded once per row) and
+// cost(own, q) against the image-2 pixel at q.
+template <int CN>
+struct BtCost {                                               // the signal records of sgbm_signals_kernel
+    static constexpr int DWORDS = CN * 3, MAX_PIXEL = CN * 189;   // (derivative distance <= 2 * 63, intensity distance <= 255 / 4)
+    struct Own { Rec u[CN]; };
+    static __device__ __forceinline__ Own own(const uint32_t* p)
+    {
+        Own o;
+#pragma unroll
+        for (int c = 0; c < CN; c++) o.u[c] = Rec{p[c * 3], p[c * 3 + 1], p[c * 3 + 2]};
+        return o;
+    }
+    static __device__ __forceinline__ uint32_t cost(const Own& o, const uint32_t* q)
+    {
+        us2 acc = {0, 0};
+#pragma unroll
+        for (int c = 0; c < CN; c++) {
+            const Rec v = {q[c * 3], q[c * 3 + 1], q[c * 3 + 2]};
+            acc += bt_pair(o.u[c], v);
+        }
+        return (uint32_t)acc.x + (uint32_t)acc.y;
+    }
+};
+
+struct CensusCost {                                           // the descriptor planes of census_kernel: one 8-byte load, one xor, two bit counts
+    static constexpr int DWORDS = 2, MAX_PIXEL = 48;          // (census_bits() is at most 48)
+    struct Own { uint64_t c; };
+    static __device__ __forceinline__ Own own(const uint32_t* p) { return Own{*reinterpret_cast<const uint64_t*>(p)}; }
+    static __device__ __forceinline__ uint32_t cost(const Own& o, const uint32_t* q)
+    {
+        return (uint32_t)__builtin_popcountll(o.c ^ *reinterpret_cast<const uint64_t*>(q));
+    }
+};
+
 // Lanes run along x: lane = one matchable column (the first and last BS/2 lanes of a wave are halo and repeat the edge
 // column at the borders of the matchable area = the clamped window), wave = DD consecutive disparities of 64 - 2*(BS/2)
 // output columns, workgroup = 4 waves = 4*DD disparities of the same columns (their int16 results are one contiguous
 // piece per column).  Per row and disparity a lane evaluates ONE pixel cost (its own column of image 1 against column
 // x - d of image 2: consecutive lanes read consecutive records) and receives its neighbours' through whole-wave DPP
 // shifts; the vertical window is a running sum over a register ring with static slots (the row loop is unrolled by BS).
-template <int BS, int CN, int DD>
+template <int BS, class COST, int DD>
 __global__ void __launch_bounds__(256) sgbm_cost_kernel(CostArgs a)
 {
     constexpr int R = BS / 2, OUTW = 64 - 2 * R;
@@ -134,11 +173,11 @@ __global__ void __launch_bounds__(256) sgbm_cost_kernel(CostArgs a)
     int16_t* C = a.C + (size_t)img * a.vol;
     const int dl = wave_active ? d0 : dbase;                  // idle waves walk along (they share the barriers and the stores)
     // Round 4: TWO disparities share a register from the pixel cost on (low / high half) wherever the block sum fits 16
-    // bits -- a pixel cost is at most 189 per channel (derivative distance <= 2 * 63, intensity distance <= 255 / 4) --
+    // bits -- a Birchfield-Tomasi pixel cost is at most 189 per channel, a Hamming one at most 48 --
     // so the window shifts, the running sums and the clamp run once per pair: about a third fewer vector instructions
     // in a kernel that is bound by issuing them.  (Sums of halves never carry: every intermediate stays below 2^16, and
     // the ring entry is subtracted from the running sum BEFORE the new one is added.)
-    constexpr bool PACK = BS * BS * CN * 189 < 65536;
+    constexpr bool PACK = BS * BS * COST::MAX_PIXEL < 65536;
     int ring[PACK ? 1 : BS][PACK ? 1 : DD], csum[PACK ? 1 : DD];
     uint32_t ring2[PACK ? BS : 1][PACK ? DD / 2 : 1], csum2[PACK ? DD / 2 : 1];
     if constexpr (PACK) {
@@ -166,22 +205,12 @@ __global__ void __launch_bounds__(256) sgbm_cost_kernel(CostArgs a)
             const int n = n0 + s;
             if (n < nsteps) {                                    // block-uniform
                 const int yy = min(max(y0 - R + n, 0), a.H - 1);
-                const uint32_t* pu = rec1 + ((size_t)yy * a.W + X) * (CN * 3);
-                const uint32_t* pv = rec2 + ((size_t)yy * a.W + (X - (dl + a.minD))) * (CN * 3);
-                Rec u[CN];
-#pragma unroll
-                for (int c = 0; c < CN; c++) u[c] = Rec{pu[c * 3], pu[c * 3 + 1], pu[c * 3 + 2]};
+                const uint32_t* pv = rec2 + ((size_t)yy * a.W + (X - (dl + a.minD))) * COST::DWORDS;
+                const typename COST::Own u = COST::own(rec1 + ((size_t)yy * a.W + X) * COST::DWORDS);
                 short res[PACK ? 1 : DD];
                 uint32_t res2[PACK ? DD / 2 : 1];
                 auto pixel_cost = [&](int dd) -> uint32_t {
-                    us2 acc = {0, 0};
-#pragma unroll
-                    for (int c = 0; c < CN; c++) {
-                        const uint32_t* q = pv - dd * (CN * 3) + c * 3;           // column X - (d0 + dd + minD)
-                        const Rec v = {q[0], q[1], q[2]};
-                        acc += bt_pair(u[c], v);
-                    }
-                    return (uint32_t)acc.x + (uint32_t)acc.y;
+                    return COST::cost(u, pv - dd * COST::DWORDS);                 // column X - (d0 + dd + minD)
                 };
                 if constexpr (PACK) {
 #pragma unroll
@@ -522,7 +551,7 @@ __global__ void __launch_bounds__(256) sgbm_median_kernel(MedianArgs a)
     a.dst[(ptrdiff_t)blockIdx.z * a.dpair + (ptrdiff_t)y * a.dstride + x] = (int16_t)v[4];
 }
 
-template <int CN>
+template <class COST>
 hipError_t launch_cost(const CostArgs& a, int bs, int n_images, hipStream_t st)
 {
     // DD disparities per wave: 16 while the register ring (BS x DD) stays small, 8 for the tall windows
@@ -531,12 +560,12 @@ hipError_t launch_cost(const CostArgs& a, int bs, int n_images, hipStream_t st)
     const int nbands = (a.H + a.rows_per_band - 1) / a.rows_per_band;
     const dim3 grid((a.w1 + outw - 1) / outw, (a.D + 4 * dd - 1) / (4 * dd), nbands * n_images), block(256);
     switch (bs) {
-    case 1: hipLaunchKernelGGL((sgbm_cost_kernel<1, CN, 16>), grid, block, 0, st, a); break;
-    case 3: hipLaunchKernelGGL((sgbm_cost_kernel<3, CN, 16>), grid, block, 0, st, a); break;
-    case 5: hipLaunchKernelGGL((sgbm_cost_kernel<5, CN, 16>), grid, block, 0, st, a); break;
-    case 7: hipLaunchKernelGGL((sgbm_cost_kernel<7, CN, 8>), grid, block, 0, st, a); break;
-    case 9: hipLaunchKernelGGL((sgbm_cost_kernel<9, CN, 8>), grid, block, 0, st, a); break;
-    case 11: hipLaunchKernelGGL((sgbm_cost_kernel<11, CN, 8>), grid, block, 0, st, a); break;
+    case 1: hipLaunchKernelGGL((sgbm_cost_kernel<1, COST, 16>), grid, block, 0, st, a); break;
+    case 3: hipLaunchKernelGGL((sgbm_cost_kernel<3, COST, 16>), grid, block, 0, st, a); break;
+    case 5: hipLaunchKernelGGL((sgbm_cost_kernel<5, COST, 16>), grid, block, 0, st, a); break;
+    case 7: hipLaunchKernelGGL((sgbm_cost_kernel<7, COST, 8>), grid, block, 0, st, a); break;
+    case 9: hipLaunchKernelGGL((sgbm_cost_kernel<9, COST, 8>), grid, block, 0, st, a); break;
+    case 11: hipLaunchKernelGGL((sgbm_cost_kernel<11, COST, 8>), grid, block, 0, st, a); break;
     default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
@@ -579,6 +608,7 @@ struct adf_sgbm {
     int min_disp = 0, num_disp = 16, block = 3;
     int P1 = 0, P2 = 0, cap = 0, uniq = 0, mode = ADF_SGBM_MODE_SGBM;    // cv::StereoSGBM::create's defaults
     int disp12 = 0;                                                        // ... incl. disp12MaxDiff = 0, which the algorithm reads as 1 (check ON)
+    int cost = ADF_SGBM_COST_BT, census_size = 7;                          // adf_sgbm_set_cost (census_size: read by the census costs only)
     DevBuf ws;      // the volumes of the images in flight
     DevBuf stage;   // host-pointer entry: device copies of the I/O
     size_t ws_limit = (size_t)64 << 30;
@@ -648,6 +678,25 @@ extern "C" int adf_sgbm_get_disp12_max_diff(const adf_sgbm_t* h, int* v)
     return ADF_OK;
 }
 
+extern "C" int adf_sgbm_set_cost(adf_sgbm_t* h, int cost_type, int census_size)
+{
+    if (!h) return fail(ADF_EBADARG, "handle is NULL");
+    if (cost_type != ADF_SGBM_COST_BT) {
+        if (int rc = census_check(cost_type, census_size)) return rc;
+        h->census_size = census_size;
+    }
+    h->cost = cost_type;
+    return ADF_OK;
+}
+
+extern "C" int adf_sgbm_get_cost(const adf_sgbm_t* h, int* cost_type, int* census_size)
+{
+    if (!h) return fail(ADF_EBADARG, "handle is NULL");
+    if (cost_type) *cost_type = h->cost;
+    if (census_size) *census_size = h->census_size;
+    return ADF_OK;
+}
+
 extern "C" int adf_sgbm_get_device(const adf_sgbm_t* h, int* device)
 {
     if (!h) return fail(ADF_EBADARG, "handle is NULL");
@@ -661,6 +710,7 @@ static int sgbm_check(const adf_sgbm* h, int n, const void* l, const void* r, co
     if (!h) return fail(ADF_EBADARG, "handle is NULL");
     if (n <= 0 || !l || !r || !d) return fail(ADF_EBADARG, "views and disparity must be non-NULL, n_pairs positive");
     if (cn != 1 && cn != 3) return fail(ADF_EBADARG, "views must be CV_8UC1 or CV_8UC3");
+    if (h->cost != ADF_SGBM_COST_BT && cn != 1) return fail(ADF_EBADARG, "a census cost takes CV_8UC1 views (descriptor.cpp:58)");
     if (W <= 0 || H <= 0 || ls < (ptrdiff_t)W * cn || rs < (ptrdiff_t)W * cn || dstr < (ptrdiff_t)W * 2) return fail(ADF_ESIZE, "bad size or stride");
     if ((dstr & 1) || (reinterpret_cast<uintptr_t>(d) & 1)) return fail(ADF_ESIZE, "disparity rows must be 2-byte aligned");
     if (h->mode != ADF_SGBM_MODE_3WAY && h->mode != ADF_SGBM_MODE_SGBM && h->mode != ADF_SGBM_MODE_HH)
@@ -696,9 +746,11 @@ extern "C" int adf_sgbm_compute_device(adf_sgbm_t* h, int n_pairs,
     const int minX1 = std::max(maxD, 0), w1 = (W + std::min(minD, 0)) - minX1;
     const int16_t invalid = (int16_t)((minD - 1) * SG_DISP_SCALE);
 
-    // workspace per image in flight: two signal planes, the C and S volumes, the raw map (every part 256-byte aligned)
+    // workspace per image in flight: two signal planes (12 * cn bytes per pixel) or, with a census cost, two descriptor
+    // planes (8), the C and S volumes, the raw map (every part 256-byte aligned)
+    const bool census = h->cost != ADF_SGBM_COST_BT;
     auto up256 = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t rec_bytes = up256((size_t)W * H * cn * 3 * 4);
+    const size_t rec_bytes = up256((size_t)W * H * (census ? 8 : cn * 3 * 4));
     const size_t rec_pair = rec_bytes / 4;                                            // dwords
     const size_t vol_bytes = up256(w1 > 0 ? (size_t)H * w1 * D * 2 : 0);
     const size_t volp = vol_bytes / 2;                                                // int16 elements
@@ -726,17 +778,23 @@ extern "C" int adf_sgbm_compute_device(adf_sgbm_t* h, int n_pairs,
         FillArgs fa{raw, W, (ptrdiff_t)raw_el, W, H, invalid};
         hipLaunchKernelGGL(sgbm_fill_kernel, dim3((W + 255) / 256, H, n), dim3(256), 0, st, fa);
         if (w1 > 0) {
-            SignalArgs sa{L, left_stride, left_pair_stride, cn, W, H, ftzero, rec1, rec_pair};
-            hipLaunchKernelGGL(sgbm_signals_kernel, dim3((W + 255) / 256, H, n), dim3(256), 0, st, sa);
-            sa.img = R; sa.stride = right_stride; sa.pair_stride = right_pair_stride; sa.rec = rec2;
-            hipLaunchKernelGGL(sgbm_signals_kernel, dim3((W + 255) / 256, H, n), dim3(256), 0, st, sa);
+            if (census) {                                      // preFilterCap plays no part in this cost
+                if ((rc = census_run(n, L, left_stride, left_pair_stride, W, H, h->cost, h->census_size, (uint64_t*)rec1, (ptrdiff_t)W * 8, (ptrdiff_t)rec_bytes, st))) return rc;
+                if ((rc = census_run(n, R, right_stride, right_pair_stride, W, H, h->cost, h->census_size, (uint64_t*)rec2, (ptrdiff_t)W * 8, (ptrdiff_t)rec_bytes, st))) return rc;
+            } else {
+                SignalArgs sa{L, left_stride, left_pair_stride, cn, W, H, ftzero, rec1, rec_pair};
+                hipLaunchKernelGGL(sgbm_signals_kernel, dim3((W + 255) / 256, H, n), dim3(256), 0, st, sa);
+                sa.img = R; sa.stride = right_stride; sa.pair_stride = right_pair_stride; sa.rec = rec2;
+                hipLaunchKernelGGL(sgbm_signals_kernel, dim3((W + 255) / 256, H, n), dim3(256), 0, st, sa);
+            }
             CostArgs ca{rec1, rec2, rec_pair, Cv, volp, W, H, D, minD, minX1, w1, 0};
             // bands: the bs-1 warm-up rows are paid per band; enough workgroups to fill the chip when the image is small
             int rpb = 128;
             while (rpb > 16 && (size_t)((H + rpb - 1) / rpb) * ((w1 + 61) / 62) * ((D + 63) / 64) * n < 2048) rpb >>= 1;
             ca.rows_per_band = rpb;
             if ((size_t)((H + rpb - 1) / rpb) * n > 65535) return fail(ADF_ESIZE, "too many images per call for the cost kernel's grid");
-            hipError_t e = cn == 1 ? launch_cost<1>(ca, bs, n, st) : launch_cost<3>(ca, bs, n, st);
+            hipError_t e = census ? launch_cost<CensusCost>(ca, bs, n, st)
+                         : cn == 1 ? launch_cost<BtCost<1>>(ca, bs, n, st) : launch_cost<BtCost<3>>(ca, bs, n, st);
             if (e != hipSuccess) return fail(ADF_EHIP, "%s", hipGetErrorString(e));
             PathArgs pa{Cv, Sv, Lv, volp, W, H, D, minD, minX1, w1, P1, P2, ur, raw, (ptrdiff_t)W, (ptrdiff_t)raw_el, 0, 0, h->disp12};
             e = D <= 64 ? launch_paths<1>(pa, h->mode, n, st) : D <= 128 ? launch_paths<2>(pa, h->mode, n, st)

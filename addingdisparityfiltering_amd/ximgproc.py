@@ -12,6 +12,7 @@ edge_filter.hpp (EF.hpp), over the C-ABI in include/adf_wls.h:
     createFastGlobalSmootherFilter(...)             EF.hpp:393
     fastGlobalSmootherFilter(...)                   EF.hpp:413
     filterSpeckles(img, newVal, maxSpeckleSize, maxDiff, buf)   calib3d (outside the reference tree)
+    censusTransform(image, kernelSize, type)        modules/stereo descriptor.hpp:428 / descriptor.cpp:77-98
     resize(src, dsize, fx, fy) at half size, cvtColor(src, COLOR_BGR2GRAY)   imgproc (outside the reference tree)
 
 Images are numpy arrays (host path: copied to the GPU and back) or torch CUDA
@@ -25,6 +26,7 @@ import math
 import numpy as np
 
 from . import _lib
+from ._lib import SGBM_COST_BT, SGBM_COST_CENSUS_DENSE, SGBM_COST_CENSUS_SPARSE  # noqa: F401  (re-exported)
 from ._lib import AdfError, PATH_CONF_BAND, PATH_FUSED_FIRST_PASS, PATH_MERGED_PREP, PATH_SCALED_FUSED, PATH_SCALED_HALF, Rect, SOLVER_EXACT, SOLVER_WAVE  # noqa: F401  (re-exported)
 
 try:  # torch is optional plumbing: device memory and streams only
@@ -46,8 +48,9 @@ def _as_rect(roi):
     return Rect(int(x), int(y), int(w), int(h))
 
 
-_ITEMSIZE = {np.int16: 2, np.uint8: 1, np.float32: 4}
-_TORCH_DTYPE = {np.int16: torch.int16, np.uint8: torch.uint8, np.float32: torch.float32} if torch is not None else {}
+_ITEMSIZE = {np.int16: 2, np.uint8: 1, np.float32: 4, np.uint64: 8}
+# (torch has no unsigned 64-bit type that every build can index: a descriptor plane is an int64 tensor carrying the bit pattern)
+_TORCH_DTYPE = {np.int16: torch.int16, np.uint8: torch.uint8, np.float32: torch.float32, np.uint64: torch.int64} if torch is not None else {}
 _raw_stream = getattr(getattr(torch, "_C", None), "_cuda_getCurrentRawStream", None) if torch is not None else None
 
 
@@ -457,14 +460,19 @@ class StereoBM(StereoMatcher):
         return disparity_left, disparity_right
 
 
-@_accessors("P1", "P2", "mode", "preFilterCap")
+@_accessors("P1", "P2", "mode", "preFilterCap", "costType", "censusSize")
 class StereoSGBM(StereoMatcher):
     """cv::StereoSGBM's accessors plus compute() on the device (csrc/sgbm_matcher.hip): the published semi-global
     algorithm with three paths (MODE_SGBM_3WAY, the mode the reference's sample selects:
     samples/disparity_filtering.cpp:166-176), five (MODE_SGBM) or eight (MODE_HH), bit-exact against
     oracle/adf_oracle_sgbm.c; parity unpinned at calib3d.  compute() takes CV_8UC1 / CV_8UC3 views (H,W[,3]) or a batch
     (N,H,W[,3]) and runs the matcher's own left-right check (disp12MaxDiff; create's default 0 reads as 1, the filter
-    factory switches it off with 1000000, DF.cpp:389); the speckle filter is not built (DF.cpp:390 sets it to 0)."""
+    factory switches it off with 1000000, DF.cpp:389); the speckle filter is not built (DF.cpp:390 sets it to 0).
+
+    Extension: setCostType(SGBM_COST_CENSUS_DENSE / _SPARSE) + setCensusSize(k) match on census descriptors with a Hamming
+    distance, the cost of the reference's own cv::stereo::StereoBinarySGBM (its setBinaryKernelType / kernelSize;
+    include/adf_wls.h: adf_sgbm_set_cost).  CV_8UC1 views only; preFilterCap is ignored; bit-exact against the direct
+    statement tests/census_ref.py.  The library checks the pair (type, size) when compute() pushes it."""
     MODE_SGBM, MODE_HH, MODE_SGBM_3WAY = 0, 1, 2
     _destroy, _entry, _channels = "adf_sgbm_destroy", "adf_sgbm_compute", (1, 3)
 
@@ -472,6 +480,7 @@ class StereoSGBM(StereoMatcher):
         super().__init__(minDisparity, numDisparities, blockSize)
         self.P1, self.P2, self.mode, self.preFilterCap = P1, P2, mode, preFilterCap
         self.disp12MaxDiff, self.uniquenessRatio = 0, 0     # cv::StereoSGBM::create's defaults (the filter factory raises disp12MaxDiff to 1000000)
+        self.costType, self.censusSize = SGBM_COST_BT, 7    # a new adf_sgbm handle's
 
     @staticmethod
     def create(minDisparity=0, numDisparities=16, blockSize=3, P1=0, P2=0, disp12MaxDiff=0, preFilterCap=0,
@@ -495,6 +504,7 @@ class StereoSGBM(StereoMatcher):
                                            int(self.P1), int(self.P2), int(self.preFilterCap), int(self.uniquenessRatio),
                                            int(self.mode)))
         _lib.check(lib.adf_sgbm_set_disp12_max_diff(self._h, int(self.disp12MaxDiff)))
+        _lib.check(lib.adf_sgbm_set_cost(self._h, int(self.costType), int(self.censusSize)))
 
     def _args(self, L, R, D):
         return (self._h, L.n, L.ptr, L.stride, L.pair_stride, R.ptr, R.stride, R.pair_stride, L.c, L.w, L.h,
@@ -551,6 +561,35 @@ def filterSpeckles(img, newVal, maxSpeckleSize, maxDiff, buf=None):
     with torch.cuda.device(img.device):
         _call("adf_filter_speckles", im, args + (ws, ws_bytes))
     return img, buf
+
+
+def censusTransform(image, kernelSize, type, dst=None):
+    """cv::stereo::censusTransform(image, kernelSize, dist, type) (descriptor.hpp:428, descriptor.cpp:77-98): the census
+    descriptor of every pixel of a CV_8UC1 image (H,W) or a batch (N,H,W), `type` SGBM_COST_CENSUS_DENSE (kernelSize 3, 5,
+    7: 8 / 24 / 48 bits) or SGBM_COST_CENSUS_SPARSE (5, 7, 9, 11: 8 / 16 / 24 / 36 bits); the definition (replicated
+    edge, bit order) is the library's own: include/adf_wls.h.  A numpy image gives an np.uint64 array through the host
+    entry; a torch CUDA tensor gives an int64 tensor carrying the same bit pattern, on the device and asynchronously on
+    torch's current stream.  `dst`: an output of that type and shape to write into."""
+    if image is None:
+        raise AdfError(_lib.ADF_EBADARG, "image is empty")
+    nd = len(image.shape)
+    if nd not in (2, 3):
+        raise AdfError(_lib.ADF_EBADARG, "image must be (H,W) or a batch (N,H,W) of CV_8UC1 images")
+    im = _Image(image, np.uint8, "image", nd == 3)
+    if dst is None:
+        dst = _out_like(im, nd == 3, np.uint64)
+    D = _Image(dst, np.uint64, "dst", nd == 3)
+    if (D.n, D.h, D.w) != (im.n, im.h, im.w) or D.device != im.device:
+        raise AdfError(_lib.ADF_ESIZE, "dst must have the image's shape on its side (host or device)")
+    args = (im.n, im.ptr, im.stride, im.pair_stride, im.w, im.h, int(type), int(kernelSize), D.ptr, D.stride, D.pair_stride)
+    if not im.device:
+        _call("adf_census_transform", im, args)
+        return dst
+    if dst.device != im.keep.device:
+        raise AdfError(_lib.ADF_EBADARG, "dst lives on %s, image on %s" % (dst.device, im.keep.device))
+    with torch.cuda.device(im.keep.device):
+        _call("adf_census_transform", im, args)
+    return dst
 
 
 def speckleWorkspaceBytes(n, H, W):
@@ -661,7 +700,8 @@ def matcherViews(view, scale=0.5, gray=True, dst=None):
 
 
 def createDisparityWLSFilter(matcher_left):
-    """DF.hpp:131, DF.cpp:386-414: set the filter up from the matcher (and mutate the matcher)."""
+    """DF.hpp:131, DF.cpp:386-414: set the filter up from the matcher (and mutate the matcher).  A StereoSGBM's cost type
+    and census size are not among the mutated parameters: createRightMatcher(matcher_left) carries them to the right view."""
     matcher_left.setDisp12MaxDiff(1000000)
     matcher_left.setSpeckleWindowSize(0)
     min_disp = matcher_left.getMinDisparity()
@@ -703,6 +743,8 @@ def createRightMatcher(matcher_left):
         right.setP2(matcher_left.getP2())
         right.setMode(matcher_left.getMode())
         right.setPreFilterCap(matcher_left.getPreFilterCap())
+        right.setCostType(matcher_left.getCostType())         # (a different cost on the right view would wreck the LRC confidence)
+        right.setCensusSize(matcher_left.getCensusSize())
         right.setDisp12MaxDiff(1000000)
         right.setSpeckleWindowSize(0)
         return right

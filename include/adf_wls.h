@@ -411,6 +411,25 @@ int adf_sgbm_set_disp12_max_diff(adf_sgbm_t* h, int disp12_max_diff);
 int adf_sgbm_get_disp12_max_diff(const adf_sgbm_t* h, int* disp12_max_diff);
 int adf_sgbm_get_params(const adf_sgbm_t* h, int* min_disparity, int* num_disparities, int* block_size, int* P1, int* P2,
                         int* prefilter_cap, int* uniqueness_ratio, int* mode);
+/* The matching cost.  The reference's own semi-global matcher, cv::stereo::StereoBinarySGBM, matches on census
+ * descriptors with a Hamming distance (modules/stereo/src/stereo_binary_sgbm.cpp; setBinaryKernelType, stereo.hpp:227-228;
+ * descriptor.cpp:54-75), and its test is this library's anchor (test_block_matching.cpp:157-238).  With a census cost
+ *   pixel cost  = popcount(census(left)(y, x) ^ census(right)(y, x - d)), the descriptors of adf_census_transform_*
+ *                 below at (cost_type, census_size);
+ *   block cost  = the sum of pixel costs over the blockSize x blockSize window, window coordinates clamped to the rows
+ *                 [0, H) and to the matchable columns -- the rule of the Birchfield-Tomasi path, at most 11*11*48;
+ * and everything from the cost volume on (paths, winner, uniqueness, sub-pixel fit, left-right check, median) is the
+ * same code.  preFilterCap is ignored; views must be CV_8UC1 (descriptor.cpp:58), 3 channels are ADF_EBADARG at compute
+ * time.  Path costs are bounded by the block cost, so P1 / P2 want the scale of blockSize^2 * bits, not of
+ * Birchfield-Tomasi costs.  The definition is this library's own (see adf_census_transform_*): bit-exact against the
+ * direct statement tests/census_ref.py, NOT against the in-tree code.
+ * census_size is validated here (ADF_EBADARG; the handle keeps its cost) and ignored, and left as it was, with ADF_SGBM_COST_BT.
+ * A handle may change cost between calls. */
+#define ADF_SGBM_COST_BT 0            /* cv::StereoSGBM's Birchfield-Tomasi block cost (default) */
+#define ADF_SGBM_COST_CENSUS_DENSE 1  /* cv::stereo CV_DENSE_CENSUS (descriptor.hpp:58, descriptor.cpp:65-69), census_size 3, 5, 7 */
+#define ADF_SGBM_COST_CENSUS_SPARSE 2 /* cv::stereo CV_SPARSE_CENSUS (descriptor.cpp:70-74), census_size 5, 7, 9, 11 */
+int adf_sgbm_set_cost(adf_sgbm_t* h, int cost_type, int census_size);
+int adf_sgbm_get_cost(const adf_sgbm_t* h, int* cost_type, int* census_size); /* a new handle: ADF_SGBM_COST_BT, 7 */
 /* StereoMatcher::compute(left, right, disparity) on n_pairs equally sized CV_8UC1 / CV_8UC3 pairs (`channels`);
  * disparity: CV_16SC1, W x H (strides in bytes).  Asynchronous on `stream`. */
 int adf_sgbm_compute_device(adf_sgbm_t* h, int n_pairs,
@@ -424,6 +443,33 @@ int adf_sgbm_compute_host(adf_sgbm_t* h, int n_pairs,
                           const uint8_t* right, ptrdiff_t right_stride, ptrdiff_t right_pair_stride,
                           int channels, int W, int H,
                           int16_t* disparity, ptrdiff_t disp_stride, ptrdiff_t disp_pair_stride);
+
+/* ---------------- census transform (cv::stereo::censusTransform) ----------------
+ * cv::stereo::censusTransform(image, kernelSize, dist, type) (descriptor.hpp:428, descriptor.cpp:77-98) on n_images
+ * equally sized CV_8UC1 images, rows `src_stride` and images `src_image_stride` bytes apart: the published transform
+ * (Zabih & Woodfill 1994), one uint64 descriptor per pixel, rows `dst_stride` and images `dst_image_stride` bytes apart.
+ * census_type is ADF_SGBM_COST_CENSUS_DENSE or _SPARSE, census_size the odd window size k, n2 = k / 2:
+ *   - dense (descriptor.cpp:65-69): offsets -n2 .. n2 in both directions, k in {3, 5, 7}: 8 / 24 / 48 bits;
+ *   - sparse (every second pixel, descriptor.cpp:70-74): offsets -n2, -n2 + 2, ... <= n2, k in {5, 7, 9, 11}:
+ *     8 / 16 / 24 / 36 bits;
+ *   - the offset (0, 0) is skipped where it occurs; a bit is 1 when neighbour > centre (descriptor.hpp:182-194);
+ *   - neighbour coordinates are clamped to the image (replicated edge): every pixel has a descriptor, also in an image
+ *     smaller than the window;
+ *   - bit order: rows top to bottom, left to right within a row; the first comparison is the most significant of the
+ *     bits used, the upper bits are zero.
+ * This is the library's OWN definition, not bit parity with the in-tree code, which is no usable bit-level oracle: its
+ * row ranges read one row past Range::end (descriptor.hpp:219), it compares a row offset with a row index where it
+ * means to skip the centre (`ii != i`, descriptor.hpp:234), and it leaves the border pixels unwritten (:222); it keeps
+ * 32 bits (dense up to 5 only, descriptor.cpp:83).  Every other (type, size) is ADF_EBADARG; dst and its strides must
+ * be 8-byte aligned (ADF_EBADARG).  src and dst must not overlap.
+ * _device: device pointers on the current HIP device, asynchronous on `stream`; no allocation, no synchronisation, so
+ * the call may be captured into a hipGraph.  _host: host pointers; copies, runs and synchronises. */
+int adf_census_transform_device(int n_images, const uint8_t* src, ptrdiff_t src_stride, ptrdiff_t src_image_stride,
+                                int W, int H, int census_type, int census_size,
+                                uint64_t* dst, ptrdiff_t dst_stride, ptrdiff_t dst_image_stride, void* stream);
+int adf_census_transform_host(int n_images, const uint8_t* src, ptrdiff_t src_stride, ptrdiff_t src_image_stride,
+                              int W, int H, int census_type, int census_size,
+                              uint64_t* dst, ptrdiff_t dst_stride, ptrdiff_t dst_image_stride);
 
 /* ---------------- speckle filter (cv::filterSpeckles) ----------------
  * cv::filterSpeckles(img, newVal, maxSpeckleSize, maxDiff, buf) of OpenCV's calib3d, the step a StereoBM / StereoSGBM

@@ -45,7 +45,7 @@ inline void check(int rc) { if (rc != ADF_OK) throw Exception(rc, adf_last_error
 using Mat = cv::Mat;
 using Rect = cv::Rect;
 template <class T> using Ptr = cv::Ptr<T>;
-enum { D8U = CV_8U, D16S = CV_16S, D32F = CV_32F };
+enum { D8U = CV_8U, D16S = CV_16S, D32S = 4 /* CV_32S */, D32F = CV_32F };
 inline int mat_depth(const Mat& m) { return m.depth(); }
 inline int mat_channels(const Mat& m) { return m.channels(); }
 inline ptrdiff_t mat_step(const Mat& m) { return (ptrdiff_t)m.step; }
@@ -57,7 +57,7 @@ struct Rect {
     Rect(int x_, int y_, int w_, int h_) : x(x_), y(y_), width(w_), height(h_) {}
     int area() const { return width * height; }
 };
-enum { D8U = 0, D16S = 3, D32F = 5 }; // cv depth codes
+enum { D8U = 0, D16S = 3, D32S = 4, D32F = 5 }; // cv depth codes
 // Minimal dense image: shared buffer, header copies share data (like cv::Mat).
 struct Mat {
     int rows = 0, cols = 0, depth_ = D8U, cn = 1;
@@ -101,6 +101,23 @@ inline void filterSpeckles(Mat& img, double newVal, int maxSpeckleSize, double m
     const double md = std::fmin(std::fmax(std::nearbyint(maxDiff), -2147483647.0), 2147483647.0);
     check(adf_filter_speckles_host(1, reinterpret_cast<int16_t*>(img.data), mat_step(img), 0, img.cols, img.rows,
                                    (int)nv, maxSpeckleSize, (int)md));
+}
+
+// cv::stereo::censusTransform(image, kernelSize, dist, type) (modules/stereo descriptor.hpp:428, descriptor.cpp:77-98) on a
+// CV_8UC1 host Mat, through the library's host entry: the census descriptor of every pixel, type
+// ADF_SGBM_COST_CENSUS_DENSE (kernelSize 3, 5, 7) or ADF_SGBM_COST_CENSUS_SPARSE (5, 7, 9, 11); definition, bit order
+// and why it is not bit parity with the in-tree code: adf_census_transform_* in adf_wls.h.  A descriptor has up to 48
+// bits, and cv::Mat has no 64-bit integer depth, so dist is CV_32SC2: one uint64 per pixel in the machine's byte order
+// (channel 0 the low half), read with dist.ptr<uint64_t>(y)[x].
+inline void censusTransform(const Mat& image, int kernelSize, Mat& dist, int type)
+{
+    if (image.empty() || mat_depth(image) != D8U || mat_channels(image) != 1)                 // descriptor.cpp:81
+        throw Exception(ADF_EBADARG, "censusTransform: image must be a non-empty CV_8UC1 image");
+    Mat out;
+    mat_create(out, image.rows, image.cols, D32S, 2);
+    check(adf_census_transform_host(1, image.data, mat_step(image), 0, image.cols, image.rows, type, kernelSize,
+                                    reinterpret_cast<uint64_t*>(out.data), mat_step(out), 0));
+    dist = out;
 }
 
 // The two imgproc calls in front of the matcher in the sample's default pipeline (samples/disparity_filtering.cpp:130-141;
@@ -325,6 +342,8 @@ inline cv::Ptr<cv::StereoMatcher> createRightMatcher(cv::Ptr<cv::StereoMatcher> 
         right_sgbm->setP2(sgbm->getP2());
         right_sgbm->setMode(sgbm->getMode());
         right_sgbm->setPreFilterCap(sgbm->getPreFilterCap());
+        // (cv::StereoSGBM has one matching cost: the census costs exist on adf::ximgproc::StereoSGBM below, whose
+        // createRightMatcher carries them over)
         right_sgbm->setDisp12MaxDiff(1000000);
         right_sgbm->setSpeckleWindowSize(0);
         return right_sgbm;
@@ -412,6 +431,7 @@ class StereoSGBM {
     adf_sgbm_t* h_ = nullptr;
     int min_disp_, num_disp_, block_, P1_ = 0, P2_ = 0, cap_ = 0, uniq_ = 0, mode_ = MODE_SGBM;    // cv::StereoSGBM::create's defaults
     int disp12_ = 0, speckle_window_ = 0;
+    int cost_ = ADF_SGBM_COST_BT, census_size_ = 7;                                                  // a new adf_sgbm handle's
 public:
     enum { MODE_SGBM = ADF_SGBM_MODE_SGBM, MODE_HH = ADF_SGBM_MODE_HH, MODE_SGBM_3WAY = ADF_SGBM_MODE_3WAY };
     StereoSGBM(int minDisparity, int numDisparities, int blockSize) : min_disp_(minDisparity), num_disp_(numDisparities), block_(blockSize)
@@ -435,6 +455,10 @@ public:
     int getMode() const { return mode_; }                    void setMode(int v) { mode_ = v; }
     int getDisp12MaxDiff() const { return disp12_; }         void setDisp12MaxDiff(int v) { disp12_ = v; }
     int getSpeckleWindowSize() const { return speckle_window_; } void setSpeckleWindowSize(int v) { speckle_window_ = v; }
+    // extension (adf_sgbm_set_cost in adf_wls.h): ADF_SGBM_COST_BT, or a census descriptor + Hamming distance, the cost of
+    // cv::stereo::StereoBinarySGBM (its setBinaryKernelType / kernelSize); the pair is checked when compute() pushes it
+    int getCostType() const { return cost_; }                void setCostType(int v) { cost_ = v; }
+    int getCensusSize() const { return census_size_; }       void setCensusSize(int v) { census_size_ = v; }
     // StereoMatcher::compute: CV_8UC1 / CV_8UC3 views -> CV_16SC1 disparity * 16, invalid pixels (minDisparity - 1) * 16
     void compute(const Mat& left, const Mat& right, Mat& disparity)
     {
@@ -447,6 +471,7 @@ public:
             throw Exception(ADF_EBADARG, "the matcher's speckle filter is not implemented");
         check(adf_sgbm_set_params(h_, min_disp_, num_disp_, block_, P1_, P2_, cap_, uniq_, mode_));
         check(adf_sgbm_set_disp12_max_diff(h_, disp12_));
+        check(adf_sgbm_set_cost(h_, cost_, census_size_));
         Mat out;
         mat_create(out, left.rows, left.cols, D16S, 1);
         check(adf_sgbm_compute_host(h_, 1, left.data, mat_step(left), 0, right.data, mat_step(right), 0, mat_channels(left),
@@ -475,6 +500,8 @@ inline Ptr<StereoSGBM> createRightMatcher(const Ptr<StereoSGBM>& matcher_left)
     right_sgbm->setP2(matcher_left->getP2());
     right_sgbm->setMode(matcher_left->getMode());
     right_sgbm->setPreFilterCap(matcher_left->getPreFilterCap());
+    right_sgbm->setCostType(matcher_left->getCostType());       // (a different cost on the right view would wreck the LRC confidence)
+    right_sgbm->setCensusSize(matcher_left->getCensusSize());
     right_sgbm->setDisp12MaxDiff(1000000);
     right_sgbm->setSpeckleWindowSize(0);
     return right_sgbm;
