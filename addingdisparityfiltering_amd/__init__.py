@@ -14,6 +14,7 @@ from .ximgproc import (  # noqa: F401
     PATH_CONF_BAND,
     PATH_FUSED_FIRST_PASS,
     PATH_MERGED_PREP,
+    PATH_ROW_WEIGHTS_GUIDE,
     PATH_SCALED_FUSED,
     PATH_SCALED_HALF,
     SGBM_COST_BT,

@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("ADF_WLS_LIB") or os.path.join(_HERE, "libadf_wls.so")
 ADF_OK, ADF_EBADARG, ADF_ESIZE, ADF_EHIP, ADF_ENOMEM, ADF_ENODEV = range(6)
 SOLVER_EXACT, SOLVER_WAVE = 0, 1
 PATH_CONF_BAND, PATH_FUSED_FIRST_PASS, PATH_MERGED_PREP, PATH_SCALED_FUSED, PATH_SCALED_HALF = 1, 2, 4, 8, 16    # adf_wls_get_last_path bits (include/adf_wls.h)
+PATH_ROW_WEIGHTS_GUIDE = 32    # adf_wls_get_last_solver_path bit
 DEPTH_8U, DEPTH_16S, DEPTH_32F = 0, 3, 5
 SGBM_COST_BT, SGBM_COST_CENSUS_DENSE, SGBM_COST_CENSUS_SPARSE = 0, 1, 2    # adf_sgbm_set_cost (include/adf_wls.h)
 
@@ -60,6 +61,7 @@ SYMBOLS = [
     ("adf_wls_get_solver", _i, [_vp, C.POINTER(_i)]),
     ("adf_wls_get_last_solver", _i, [_vp, C.POINTER(_i)]),
     ("adf_wls_get_last_path", _i, [_vp, C.POINTER(_i)]),
+    ("adf_wls_get_last_solver_path", _i, [_vp, C.POINTER(_i)]),
     ("adf_wls_filter_device", _i, _FILTER_DEV),
     ("adf_wls_filter_host", _i, _FILTER_DEV[:-1]),
     ("adf_wls_filter_scaled_device", _i, _FILTER_SCALED_DEV),

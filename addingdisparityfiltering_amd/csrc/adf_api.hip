@@ -106,18 +106,20 @@ static void set_final_out(Args& a, const FinalOut& fo)
 // first row pass forms its right-hand sides from.
 static int run_passes(bool wave, const Geom& g, const SolvePlanes& p, int n_rhs, float lambda, float atten, int num_iter,
                       const FinalOut& fo, int n_pairs, hipStream_t st, Profiler* prof = nullptr,
-                      const FusedInputs* fuse = nullptr)
+                      const FusedInputs* fuse = nullptr, const GuideWeights* gw = nullptr)
 {
     const double px = (double)g.rw * g.rh * n_pairs;
     float lam = lambda;
     for (int it = 0; it < num_iter; it++, lam *= atten) {                      // FGS.cpp:211 (float)
         const bool fused = it == 0 && fuse, last = it == num_iter - 1;
         const int epi = last ? fo.epilogue : EPI_PLANES;
-        // algorithmic bytes: the row pass reads the weight + R right-hand sides and writes R -- fused, C + conf
-        // + dL read (low-resolution maps: their bytes per view pixel, each row counted once), U0/U1 written; the column
-        // pass writes the fused epilogue's output instead of 4R bytes per pixel on the last iteration
+        // algorithmic bytes: the row pass reads the weight (the Chor plane, or `gw`: the guide row itself)
+        // + R right-hand sides and writes R -- fused, C + conf + dL read (low-resolution maps: their bytes per view pixel,
+        // each row counted once), U0/U1 written; the column pass writes the fused epilogue's output instead of 4R bytes
+        // per pixel on the last iteration
         const double lo_b = (fused && fuse->lo_conf) ? 6.0 * fuse->lo_scale_x * fuse->lo_scale_y : 6.0;
-        const double hb = fused ? (4.0 + lo_b + 8.0) * px : (4.0 + 8.0 * n_rhs) * px;
+        const double wb = gw ? (double)gw->ch : 4.0;
+        const double hb = fused ? (wb + lo_b + 8.0) * px : (wb + 8.0 * n_rhs) * px;
         const double out_b = (last ? epilogue_bytes(fo.epilogue) : 4.0 * n_rhs) * px;
         const double vb = (4.0 + 4.0 * n_rhs) * px + out_b;
         if (wave) {
@@ -125,6 +127,7 @@ static int run_passes(bool wave, const Geom& g, const SolvePlanes& p, int n_rhs,
             h.C = p.CH; h.U0 = p.A0; h.U1 = p.A1;
             h.nscan = g.rh; h.len = g.rw; h.pitch = g.pw; h.plane = g.plane; h.lambda = lam;
             if (fused) h.fuse = *fuse;
+            if (gw) h.gw = *gw;
             v.C = p.CV; v.U0 = p.A0; v.U1 = p.A1;
             v.nscan = g.rw; v.len = g.rh; v.pitch = g.pw; v.plane = g.plane; v.lambda = lam;
             if (last) set_final_out(v, fo);
@@ -189,6 +192,7 @@ struct adf_wls {
     int last_cpitch = 0, last_cx0 = 0;       // layout of the confidence planes of the last call (Geom::cpitch, cx0)
     long long conf_sig[4] = {0, 0, 0, 0};    // (W, H, cx0, pairs) the confidence planes were last zeroed for
     int last_path = 0;                       // ADF_PATH_* bits of the last call (adf_wls_get_last_path)
+    int last_solver_path = 0;                // ... of its solve passes (adf_wls_get_last_solver_path)
     // device memory
     Lut lut;
     DevBuf ws;    // per-chunk workspace
@@ -212,6 +216,7 @@ struct adf_wls {
     bool scaled_fuse = true; // ADF_SCALED_FUSE=0: the down-scaled path through the two resize kernels (A/B measurements)
     bool conf_band = true;   // ADF_CONF_BAND=0: the two-kernel confidence stage (A/B measurements)
     bool merge_small = true; // ADF_MERGE_SMALL=0: never the merged preparation launch (A/B measurements)
+    bool row_weights_guide = true; // ADF_ROW_WEIGHTS_GUIDE=0: the row passes always read the Chor plane (A/B measurements, tests)
     // HIP maps the streams of ONE priority level onto a small pool of hardware queues (4 by default) and two streams that
     // share a queue run one after the other: a side stream of the caller's priority lost the overlap for about one caller
     // stream in four (tools/batch_cpp.cpp: 13.5-13.6 ms per 64 x 4K call instead of 12.8-13.2).  Each priority level has a pool
@@ -255,6 +260,7 @@ extern "C" int adf_wls_create(adf_wls_t** out, int use_confidence, int l, int r,
     if (const char* e = getenv("ADF_NO_OVERLAP")) h->overlap = atoi(e) == 0;   // measurement knob
     if (const char* e = getenv("ADF_CONF_BAND")) h->conf_band = atoi(e) != 0;    // measurement knob
     if (const char* e = getenv("ADF_SCALED_FUSE")) h->scaled_fuse = atoi(e) != 0;  // measurement knob
+    if (const char* e = getenv("ADF_ROW_WEIGHTS_GUIDE")) h->row_weights_guide = atoi(e) != 0;   // measurement knob
     if (const char* e = getenv("ADF_LO_HALF")) h->scaled_half = atoi(e) != 0;
     if (const char* e = getenv("ADF_MERGE_SMALL")) h->merge_small = atoi(e) != 0;   // measurement knob
     *out = h;
@@ -301,6 +307,7 @@ extern "C" int adf_wls_set_solver(adf_wls_t* h, int solver)
 extern "C" int adf_wls_get_solver(const adf_wls_t* h, int* v) { NEED_HANDLE(h); if (v) *v = h->solver; return ADF_OK; }
 extern "C" int adf_wls_get_last_solver(const adf_wls_t* h, int* v) { NEED_HANDLE(h); if (v) *v = h->last_solver; return ADF_OK; }
 extern "C" int adf_wls_get_last_path(const adf_wls_t* h, int* v) { NEED_HANDLE(h); if (v) *v = h->last_path; return ADF_OK; }
+extern "C" int adf_wls_get_last_solver_path(const adf_wls_t* h, int* v) { NEED_HANDLE(h); if (v) *v = h->last_solver_path; return ADF_OK; }
 
 extern "C" int adf_wls_get_device(const adf_wls_t* h, int* device) { NEED_HANDLE(h); if (device) *device = h->device; return ADF_OK; }
 extern "C" int adf_wls_get_roi(const adf_wls_t* h, adf_rect* roi) { NEED_HANDLE(h); if (roi) *roi = h->roi; return ADF_OK; }
@@ -496,6 +503,7 @@ struct ChunkPlan {
     ConfStage stage;
     bool fork_weights;     // the weight kernel runs on the side stream, beside the confidence kernels
     bool outside_on_side;  // ... behind the fill outside the ROI
+    bool guide_rows;       // the row passes form their weights from the guide: the weight kernel writes Cvert only
 };
 
 // What a WLS filter call queues, decided before its chunk loop.
@@ -507,10 +515,11 @@ struct WlsPlan {
     // chunks of `chunk` pairs, and a shorter last one: the merged launch is for small calls, so it depends on the
     // chunk's pair count
     ChunkPlan full, tail;
-    int path;                 // ADF_PATH_* bits
+    int path;                 // ADF_PATH_* bits of the preparation stage
+    int solver_path;          // ... of the solve passes
 };
 
-static ChunkPlan plan_chunk(const adf_wls* h, ConfStage stage, bool wave)
+static ChunkPlan plan_chunk(const adf_wls* h, ConfStage stage, bool wave, bool guide_rows)
 {
     // confidence mode: the weights depend on the guide only and the confidence kernels on the disparity maps only -- one
     // is bound by memory latency, the others lean on the vector ALUs -- so the weight kernel is forked onto the side
@@ -522,11 +531,18 @@ static ChunkPlan plan_chunk(const adf_wls* h, ConfStage stage, bool wave)
     // there: alone it takes 0.08 ms of a 64 x 4K step on the StereoBM factory's ROI, but queued behind the weight kernel
     // it starts when the confidence kernel's workgroups hold nearly every register of every CU and crawls through 0.8 ms
     // as the call's tail (round 3).  The two-kernel stage fills in its LRC kernel.
-    return ChunkPlan{stage, fork, fork && wave && stage != CONF_TWO_KERNEL};
+    // (the merged launch for small calls writes both weight planes: those are bound by latency, not bytes)
+    return ChunkPlan{stage, fork, fork && wave && stage != CONF_TWO_KERNEL, guide_rows && stage != CONF_MERGED};
+}
+
+// The row passes' weights straight from the guide of the pairs from `guide` on (fgs_wave_h.hip, WS_GUIDE*).
+static GuideWeights guide_weights(const adf_wls* h, const uint8_t* guide, ptrdiff_t sG, ptrdiff_t psG, int gch, const Geom& g)
+{
+    return GuideWeights{guide, sG, psG, gch, g.rx, g.ry, h->lut.cur};
 }
 
 static WlsPlan plan_wls(const adf_wls* h, const Geom& g, int n_pairs, const int16_t* dispL, ptrdiff_t sL, ptrdiff_t psL,
-                        ptrdiff_t sG, int gch, const ScaledStage* scaled)
+                        const uint8_t* view, ptrdiff_t sG, ptrdiff_t psG, int gch, const ScaledStage* scaled)
 {
     WlsPlan p{};
     const bool conf = h->use_confidence;
@@ -548,15 +564,27 @@ static WlsPlan plan_wls(const adf_wls* h, const Geom& g, int n_pairs, const int1
     p.chunk = (int)(h->ws_limit / p.per_pair);
     if (p.chunk < 1) p.chunk = 1;
     if (p.chunk > n_pairs) p.chunk = n_pairs;
+    // The guide is new on every call, so the Chor plane of a full-resolution call on the wave solver is written once and
+    // read num_iter times for nothing the guide row does not say in fewer bytes: the row passes take the guide instead
+    // where their bucket has that form and the streaming weight kernel (the one with a Cvert-only form) runs.
+    bool guide_rows = false;
+    if (p.wave && !scaled && h->row_weights_guide) {
+        WavePassArgs probe{};
+        probe.len = g.rw; probe.gw = guide_weights(h, view, sG, psG, gch, g);
+        WeightArgs wprobe{};
+        wprobe.stride = sG; wprobe.ch = gch; wprobe.chor_orient = ORIENT_N; wprobe.g = g;
+        guide_rows = wave_hpass_guide_fits(probe) && weights_stream_fits(wprobe);
+    }
     auto chunk_of = [&](int n) {
         const bool merged = p.band && h->merge_small && prep_small_fits(g, h->disc_radius, gch, n) && prep_small_guide_fits(g, sG, gch);
-        return plan_chunk(h, merged ? CONF_MERGED : stage, p.wave);
+        return plan_chunk(h, merged ? CONF_MERGED : stage, p.wave, guide_rows);
     };
     p.full = chunk_of(p.chunk);
     p.tail = chunk_of(n_pairs % p.chunk ? n_pairs % p.chunk : p.chunk);
     p.path = ((p.band || (scaled && scaled->lo.band_map)) ? ADF_PATH_CONF_BAND : 0) |
              (p.fused_first ? ADF_PATH_FUSED_FIRST_PASS : 0) |
              ((p.full.stage == CONF_MERGED || p.tail.stage == CONF_MERGED) ? ADF_PATH_MERGED_PREP : 0);
+    p.solver_path = (p.full.guide_rows || p.tail.guide_rows) ? ADF_PATH_ROW_WEIGHTS_GUIDE : 0;
     if (stage == CONF_SCALED_LO)
         p.path |= ADF_PATH_SCALED_FUSED |
                   (wave_hpass_lo_half(first_pass_probe(lo_fuse(h, *scaled, 0, g), g.rw)) ? ADF_PATH_SCALED_HALF : 0);
@@ -604,10 +632,10 @@ static int wls_filter_impl(adf_wls_t* h, int n_pairs,
     const Geom g = make_geom(W, H, roi.x, roi.y, roi.width, roi.height);
     h->lazy_conf.pending = false;
     h->roi = roi; h->last_W = W; h->last_H = H; h->last_pairs = n_pairs;
-    h->last_cpitch = g.cpitch; h->last_cx0 = g.cx0; h->last_path = 0;
+    h->last_cpitch = g.cpitch; h->last_cx0 = g.cx0; h->last_path = 0; h->last_solver_path = 0;
 
     if ((rc = h->lut.ensure((float)h->sigma_color, st))) return rc;
-    const WlsPlan plan = plan_wls(h, g, n_pairs, dispL, sL, psL, sG, gch, scaled);
+    const WlsPlan plan = plan_wls(h, g, n_pairs, dispL, sL, psL, view, sG, psG, gch, scaled);
     const bool wave = plan.wave;
     h->last_solver = wave ? ADF_SOLVER_WAVE : ADF_SOLVER_EXACT;
     if ((rc = h->ws.reserve(plan.per_pair * (size_t)plan.chunk, st, FILL_ZERO))) return rc;
@@ -641,7 +669,7 @@ static int wls_filter_impl(adf_wls_t* h, int n_pairs,
     const int rrx = W - (roi.x + roi.width);                           // DF.cpp:202
     const int thresh = (int)(1.0f * h->lrc_thresh);                    // DF.cpp:318 (resize_factor 1)
     Profiler* prof = &h->prof;
-    h->last_path = plan.path;
+    h->last_path = plan.path; h->last_solver_path = plan.solver_path;
 
     for (int first = 0; first < n_pairs; first += plan.chunk) {
         const int n = (n_pairs - first < plan.chunk) ? n_pairs - first : plan.chunk;
@@ -656,8 +684,10 @@ static int wls_filter_impl(adf_wls_t* h, int n_pairs,
         OutsideArgs oa{o, sO, psO, fill, om.f32 ? 1 : 0, scaled ? nullptr : confp, g};
         const double ob = ((oa.conf ? 4.0 : 0.0) + ob_px) * (F - P);
         auto fill_outside = [&](hipStream_t s) { ProfScope ps(prof, K_FILL, ob, ob, s); return launch_outside(oa, n, s); };
-        WeightArgs wa{gv, sG, psG, gch, h->lut.cur, p.CH, p.CV, orient_h, orient_cv, g,
+        // (guide_rows: no Chor -- the plane stays carved and untouched)
+        WeightArgs wa{gv, sG, psG, gch, h->lut.cur, cp.guide_rows ? nullptr : p.CH, p.CV, orient_h, orient_cv, g,
                       wave ? nullptr : p.B0};   // exact: B0 is free until the first pass writes its output there
+        const GuideWeights gw = guide_weights(h, gv, sG, psG, gch, g);
         ConfBandArgs ba{dL, sL, psL, dR, sR, psR, confp, g, rrx, thresh, h->disc_radius, h->roll_off, 0};
         DiscArgs da{{dL, dR}, {sL, sR}, {psL, psR}, {roi.x, rrx}, roi.y, roi.width, roi.height, h->disc_radius, h->roll_off,
                     {cL, cR}, W, g.frame, cp.stage == CONF_LEFT ? 1 : -1};
@@ -673,7 +703,8 @@ static int wls_filter_impl(adf_wls_t* h, int n_pairs,
         if (cp.stage == CONF_NONE || cp.outside_on_side) HIP_TRY(fill_outside(wst));
         if (cp.stage == CONF_NONE && scaled && first == 0 && (rc = scaled_resize(h, *scaled, st, prof))) return rc;
         if (cp.stage != CONF_MERGED) {
-            ProfScope ps(prof, K_WEIGHTS, (gch + 8.0) * P, (gch + 8.0) * P, wst);
+            const double wb = (gch + (cp.guide_rows ? 4.0 : 8.0)) * P;
+            ProfScope ps(prof, K_WEIGHTS, wb, wb, wst);
             HIP_TRY(launch_weights(wa, n, wst));                           // FGS.cpp:163-172
         }
         if (cp.fork_weights) HIP_TRY(hipEventRecord(h->ev_join, h->side));
@@ -749,7 +780,7 @@ static int wls_filter_impl(adf_wls_t* h, int n_pairs,
         const int epi = conf ? (om.f32 ? EPI_WLS_CONF_F32 : EPI_WLS_CONF) : (om.f32 ? EPI_F32 : EPI_I16);
         FinalOut fo{epi, o, sO, psO, roi.x, roi.y, 1, 0};
         rc = run_passes(wave, g, p, conf ? 2 : 1, (float)h->lambda, (float)h->atten, h->num_iter, fo, n, st, prof,
-                        plan.fused_first ? &fuse : nullptr);
+                        plan.fused_first ? &fuse : nullptr, cp.guide_rows ? &gw : nullptr);
         if (rc) return rc;                                                 // DF.cpp:257-258, 292-296
     }
     return ADF_OK;

@@ -172,6 +172,15 @@ struct FusedInputs {
     float* lo_taps;   // scratch, 4*ceil(len/4) floats, 16-byte aligned: the launcher fills it with the columns' taps (s0 + fx)
 };
 
+// Where a row pass of the wave solver takes its edge weights from when it forms them itself instead of reading the Chor
+// plane (WavePassArgs::gw; guide null = the plane): the guide row of the pass's own row, Chor[y][x] = lut[|g(y,x) -
+// g(y,x+1)|^2] (FGS.cpp:607-614).  ROI column j / row i of the pass is guide pixel (x0 + j, y0 + i).
+struct GuideWeights {
+    const uint8_t* guide; ptrdiff_t stride, pair_stride;   // bytes
+    int ch, x0, y0;                                        // channels (1 or 3), ROI origin
+    const float* lut;                                      // the full weight table (ADF_LUT_LEVELS entries)
+};
+
 // One pass of the on-chip partitioned solver (fgs_wave.hip).  Planes are row-major [rh][pitch] and
 // are solved IN PLACE; horizontal: nscan = rows, len = row length; vertical: nscan = columns,
 // len = column length.  The last vertical pass may fuse an epilogue and write `out` instead.
@@ -183,10 +192,12 @@ struct WavePassArgs {
     int nscan, len, pitch;
     size_t plane;
     float lambda;
+    GuideWeights gw;   // row passes only
 };
-// the kernels' argument layout (grouping the fused inputs moved no member)
-static_assert(sizeof(WavePassArgs) == 280 && offsetof(WavePassArgs, out) == 208 && offsetof(WavePassArgs, nscan) == 248 &&
-              offsetof(WavePassArgs, plane) == 264 && offsetof(WavePassArgs, lambda) == 272, "WavePassArgs layout");
+// the kernels' argument layout (the guide of the row passes' weights is appended: no other member moved)
+static_assert(sizeof(WavePassArgs) == 328 && offsetof(WavePassArgs, out) == 208 && offsetof(WavePassArgs, nscan) == 248 &&
+              offsetof(WavePassArgs, plane) == 264 && offsetof(WavePassArgs, lambda) == 272 && offsetof(WavePassArgs, gw) == 280 &&
+              sizeof(GuideWeights) == 48, "WavePassArgs layout");
 
 // Launchers (defined in the .hip files).  All are asynchronous on `st`.
 hipError_t launch_discontinuity(const DiscArgs& a, int n_pairs, hipStream_t st);
@@ -201,7 +212,8 @@ bool prep_small_fits(const Geom& g, int radius, int channels, int n_pairs);
 hipError_t launch_prep_small(const ConfBandArgs& c, const WeightArgs& w, const OutsideArgs& o, int n_pairs, hipStream_t st);
 int conf_left_max_radius();
 hipError_t launch_plain_prologue(const PlainPrologueArgs& a, int n_pairs, hipStream_t st);
-hipError_t launch_weights(const WeightArgs& a, int n_pairs, hipStream_t st);
+hipError_t launch_weights(const WeightArgs& a, int n_pairs, hipStream_t st);   // a.chor null: Cvert only (streaming kernel)
+bool weights_stream_fits(const WeightArgs& a);                                  // ... which takes these arguments?
 hipError_t launch_resize_linear(const ResizeArgs& a, int n_pairs, hipStream_t st);
 hipError_t launch_exact_pass(const PassArgs& a, int n_rhs, int epilogue, int n_pairs, hipStream_t st);
 hipError_t launch_wave_hpass(const WavePassArgs& a, int n_rhs, int n_pairs, hipStream_t st);
@@ -210,6 +222,7 @@ int wave_max_row_len();
 bool wave_hpass_can_fuse(const WavePassArgs& a);
 bool wave_hpass_can_fuse_lo(const WavePassArgs& a);   // the low-resolution form: scale / span limits of the LDS staging
 bool wave_hpass_lo_half(const WavePassArgs& a);      // ... in its half-width form (fgs_wave_h.hip, FUSE_LO_HALF)?
+bool wave_hpass_guide_fits(const WavePassArgs& a);   // can the row pass form its weights from a.gw (a.len, a.gw, a.fuse)?
 int wave_max_col_len();
 // largest depth-discontinuity radius the tile kernel supports (LDS bound)
 int max_disc_radius();

@@ -1,5 +1,6 @@
 // fgs_wave_h.hip -- horizontal pass of the on-chip partitioned solver (see fgs_wave_common.h).
 #include "fgs_wave_common.h"
+#include "prep_bodies.h"
 
 #include <algorithm>
 
@@ -26,6 +27,12 @@ constexpr int H_TWO_WAVE_MAX = 60;   // longest chunk whose two-right-hand-side 
 //  FUSE_LO_HALF  FUSE_LO for maps of exactly half the view's width on a ROI that starts on an even column >= 2
 //                (lo_interp4).  Same operands, same arithmetic: bit-identical to FUSE_LO (tests).
 constexpr int FUSE_NONE = 0, FUSE_VIEW = 1, FUSE_LO = 2, FUSE_LO_HALF = 3;
+// Where the row's weights come from (WS):
+//  WS_PLANE            the Chor plane the weight kernel wrote (load_c, transpose_in).
+//  WS_GUIDE1 / _GUIDE3 the guide row itself, one or three channels (guide_fetch, guide_weights): Chor is a pure function
+//                      of it, 1 or 3 bytes per pixel to read where the plane costs 4 to write and 4 in every row pass.
+//                      One-wave rows, FUSE_NONE and FUSE_VIEW.  Same table entry, same multiply: bit-identical c[].
+constexpr int WS_PLANE = 0, WS_GUIDE1 = 1, WS_GUIDE3 = 3;   // (a guide form's value is its channel count)
 
 typedef float v4f __attribute__((ext_vector_type(4)));
 
@@ -97,7 +104,7 @@ __device__ __forceinline__ float4 load_c(const WavePassArgs& a, const RowPos& p,
 
 // FUSE_NONE.  One right-hand side: t0 = U0, t1 = 0.  Two: t0 / t1 hold the first / second half of this wave's part
 // of the interleaved pair row (2 * M * 64 floats) instead of U0 / U1.
-template <int M, int R>
+template <int M, int R, bool WITH_C>
 __device__ __forceinline__ void load_planes(const WavePassArgs& a, const RowPos& p, float4 (&tC)[M / 4], float4 (&t0)[M / 4], float4 (&t1)[M / 4])
 {
     constexpr bool PAIR = R > 1;
@@ -107,7 +114,7 @@ __device__ __forceinline__ void load_planes(const WavePassArgs& a, const RowPos&
 #pragma unroll
     for (int k = 0; k < MQ; k++) {
         const int uidx = u0 + 64 * k + p.lane;
-        tC[k] = load_c(a, p, k);
+        if constexpr (WITH_C) tC[k] = load_c(a, p, k);
         t0[k] = make_float4(0.f, 0.f, 0.f, 0.f); t1[k] = t0[k];
         if (uidx < p.nvecU) t0[k] = load_nt(s0 + rhs_vec<PAIR>(uidx));
         if (PAIR && uidx + 64 * MQ < p.nvecU) t1[k] = load_nt(s0 + rhs_vec<PAIR>(uidx + 64 * MQ));
@@ -125,7 +132,7 @@ __device__ __forceinline__ int fused_vecs(int len) { return (len >> 2) + ((len &
 // ends with the row (never past the caller's buffer) and shifted into place afterwards, its conf elements
 // past the row are cleared -- both in the second loop, behind one wave-uniform branch, so that no loaded
 // value is touched while loads are still being issued.
-template <int M>
+template <int M, bool WITH_C>
 __device__ __forceinline__ void load_fused_view(const WavePassArgs& a, const RowPos& p, float4 (&tC)[M / 4], float4 (&t0)[M / 4], float4 (&t1)[M / 4])
 {
     constexpr int MQ = M / 4;
@@ -141,7 +148,7 @@ __device__ __forceinline__ void load_fused_view(const WavePassArgs& a, const Row
 #pragma unroll
     for (int k = 0; k < MQ; k++) {
         const int idx = p.v0 + 64 * k + p.lane;
-        tC[k] = load_c(a, p, k);
+        if constexpr (WITH_C) tC[k] = load_c(a, p, k);
         t0[k] = make_float4(0.f, 0.f, 0.f, 0.f); t1[k] = t0[k];
         draw[k] = make_short4(0, 0, 0, 0);
         // loads only: the products conf*float(dL) wait for the second loop, or every iteration would
@@ -475,6 +482,149 @@ __device__ __forceinline__ void load_fused_lo(const WavePassArgs& a, const RowPo
     }
 }
 
+// ---- weights from the guide row (WS_GUIDE1 / WS_GUIDE3) ----
+// c[i] of lane l is lambda * lut[|g(l*M + i) - g(l*M + i + 1)|^2] (FGS.cpp:607-612), 0 in the ROI's last column
+// (FGS.cpp:614) and behind it.  The wave's span of the guide row -- 64*M + 1 pixels -- is fetched as coalesced 16-byte
+// vectors from the 16-byte boundary at or below its first byte, with the row's other loads; the raw bytes go through the
+// wave's staging buffer, from which every lane reads the bytes of its own chunk and of the pixel behind it (a chunk is
+// CH*M bytes and M a multiple of 4: lane offsets are dword-aligned up to the wave-uniform misalignment of the row).
+// The indices come from the packed-byte helpers of prep_bodies.h, the weights from the first GW_HEAD table entries held
+// in LDS; indices beyond it take one gather each from the full table (L2-resident), issued only in rows that have any.
+constexpr int GW_HEAD = 1024;   // 4 KiB beside the staging buffer: eight one-wave workgroups of the M = 56 / 60 buckets still fit a CU's LDS
+
+template <int M, int CH>
+struct GuideShape {
+    static constexpr int NV = (CH * (64 * M + 1) + 15 + 1023) / 1024;   // 16-byte vectors per lane, at any misalignment 0..15
+    static constexpr int ND = (CH * (M + 1) + 3 + 3) / 4;               // dwords a lane reads back, at any byte offset 0..3
+    static constexpr int NH = GW_HEAD / 256;                            // float4s per lane of the table head
+    static_assert(NV * 1024 <= 256 * M, "the guide vectors fit the wave's staging buffer");
+    static_assert(4 * (3 + 63 * (CH * M / 4) + ND) <= 256 * M, "the last lane reads inside the staging buffer");
+};
+template <int M, int CH>
+struct GuideRaw { prep::ws_v4u g[GuideShape<M, CH>::NV]; prep::ws_v4f h[GuideShape<M, CH>::NH]; unsigned mis; };
+template <int M>
+struct GuideRaw<M, WS_PLANE> {};
+
+// The loads: the guide row through a range-checked window on exactly the bytes the weights need -- pixels 0 .. len-1 of
+// the ROI row, rounded out to whole dwords -- so that vectors reaching past them (the row's tail, the end of the
+// caller's buffer in the last row of the last image) read zeros there instead of touching memory; and the table head.
+template <int M, int CH>
+__device__ __forceinline__ void guide_fetch(const WavePassArgs& a, int lane, GuideRaw<M, CH>& q)
+{
+    const uintptr_t row = reinterpret_cast<uintptr_t>(a.gw.guide) + (uintptr_t)((ptrdiff_t)blockIdx.y * a.gw.pair_stride +
+                          (ptrdiff_t)(a.gw.y0 + (int)blockIdx.x) * a.gw.stride + (ptrdiff_t)a.gw.x0 * CH);
+    q.mis = (unsigned)__builtin_amdgcn_readfirstlane((int)(row & 15u));
+    const __amdgpu_buffer_rsrc_t win = prep::ws_window(reinterpret_cast<const void*>(row - q.mis), (q.mis + (unsigned)a.len * CH + 3u) & ~3u);
+#pragma unroll
+    for (int k = 0; k < GuideShape<M, CH>::NV; k++)
+        q.g[k] = __builtin_amdgcn_raw_buffer_load_b128(win, (unsigned)(64 * k + lane) * 16u, 0, 2 /* nt: used once */);
+#pragma unroll
+    for (int k = 0; k < GuideShape<M, CH>::NH; k++)
+        q.h[k] = reinterpret_cast<const prep::ws_v4f*>(a.gw.lut)[64 * k + lane];
+}
+
+// head look-up, ROI mask and lambda of a lane's M elements: c[i] holds a table index, or (FAR) a weight already fetched
+// from the full table -- weights are -exp(..) <= -0, so the sign bit tells them from an index
+template <int M, bool FAR>
+__device__ __forceinline__ void guide_finish(const float* head, int lim, float lambda, float (&c)[M])
+{
+#pragma unroll
+    for (int i = 0; i < M; i++) {
+        const unsigned u = __float_as_uint(c[i]);
+        float w = head[min(u, (unsigned)(GW_HEAD - 1))];
+        if (FAR) {
+            // (opaque: the read stays unconditional -- left alone, the compiler puts it behind a branch per element and
+            // selects between an LDS and a scratch address)
+            asm volatile("" : "+v"(w));
+            w = (int)u < 0 ? c[i] : w;
+        }
+        c[i] = (i < lim ? w : 0.0f) * lambda;                      // one multiply, as transpose_in
+    }
+}
+
+template <int M, int CH>
+__device__ __forceinline__ void guide_weights(const WavePassArgs& a, float4* stage, float* head, int lane, const GuideRaw<M, CH>& q, float (&c)[M])
+{
+    typedef GuideShape<M, CH> S;
+#pragma unroll
+    for (int k = 0; k < S::NH; k++) reinterpret_cast<prep::ws_v4f*>(head)[64 * k + lane] = q.h[k];
+#pragma unroll
+    for (int k = 0; k < S::NV; k++) reinterpret_cast<prep::ws_v4u*>(stage)[64 * k + lane] = q.g[k];
+    __syncthreads();
+    // The window ends with the ROI row, so the pixel behind it reads as zeros and the last column's index -- whose weight
+    // is masked below -- would nearly always lie beyond the head and send the whole row to the full table for nothing:
+    // the last pixel is repeated behind the row instead (index 0).
+    if (lane == 0) {
+        unsigned char* B = reinterpret_cast<unsigned char*>(stage) + q.mis + (unsigned)(a.len - 1) * CH;
+#pragma unroll
+        for (int ci = 0; ci < CH; ci++) B[CH + ci] = B[ci];
+    }
+    __syncthreads();
+    const unsigned* L = reinterpret_cast<const unsigned*>(stage) + (q.mis >> 2) + lane * (CH * M / 4);
+    const unsigned mb = q.mis & 3u;
+    unsigned d[S::ND];
+#pragma unroll
+    for (int j = 0; j < S::ND; j++) d[j] = L[j];
+    // dword #j of the lane's bytes, counted from its first pixel
+    auto e = [&](int j) -> unsigned { return __builtin_amdgcn_alignbyte(j + 1 < S::ND ? d[j + 1 < S::ND ? j + 1 : 0] : 0u, d[j], mb); };
+    int far = 0;                                                   // the lane's largest index
+    if constexpr (CH == 3) {
+        unsigned p[5], pa[5];
+        p[4] = e(0) & 0x00ffffffu; pa[4] = prep::ws_norm2(p[4]);
+#pragma unroll
+        for (int g = 0; g < M / 4; g++) {
+            prep::ws_unpack3(e(3 * g), e(3 * g + 1), e(3 * g + 2), p);
+            pa[0] = pa[4];
+            p[4] = e(3 * g + 3) & 0x00ffffffu;                     // the next group's first pixel
+#pragma unroll
+            for (int k = 1; k <= 4; k++) pa[k] = prep::ws_norm2(p[k]);
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int idx = prep::ws_dist2(p[k], pa[k], p[k + 1], pa[k + 1]);
+                far = max(far, idx);
+                c[4 * g + k] = __int_as_float(idx);
+            }
+        }
+    } else {
+#pragma unroll
+        for (int g = 0; g < M / 4; g++) {
+            const unsigned eg = e(g), nb = e(g + 1) & 0xffu;
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                const int v = (int)((eg >> (8 * k)) & 0xffu);
+                const int r = k < 3 ? (int)((eg >> (8 * k + 8)) & 0xffu) : (int)nb;
+                const int idx = prep::ws_dist2_c1(v, r);
+                far = max(far, idx);
+                c[4 * g + k] = __int_as_float(idx);
+            }
+        }
+    }
+    const int lim = a.len - 1 - lane * M;                          // elements i < lim have their right neighbour inside the ROI
+    if (__builtin_amdgcn_ballot_w64(far >= GW_HEAD) != 0) {        // wave-uniform: some index of the row lies beyond the head
+        // One gather per element through a range-checked window, at an offset no window reaches for the lanes whose
+        // index the head holds (they fetch nothing and get +0, which no weight is), sixteen in flight at a time.
+        const __amdgpu_buffer_rsrc_t lutwin = prep::ws_window(a.gw.lut, sizeof(float) * ADF_LUT_LEVELS);
+        constexpr int G = 16;
+#pragma unroll
+        for (int i0 = 0; i0 < M; i0 += G) {
+            unsigned w[G];
+#pragma unroll
+            for (int k = 0; k < G; k++)
+                if (i0 + k < M) {
+                    const int idx = __float_as_int(c[i0 + k]);
+                    w[k] = __builtin_amdgcn_raw_buffer_load_b32(lutwin, idx >= GW_HEAD ? (unsigned)idx * 4u : prep::WS_DROP, 0, 0);
+                }
+#pragma unroll
+            for (int k = 0; k < G; k++)
+                if (i0 + k < M) c[i0 + k] = w[k] != 0u ? __uint_as_float(w[k]) : c[i0 + k];
+        }
+        guide_finish<M, true>(head, lim, a.lambda, c);
+    } else {
+        guide_finish<M, false>(head, lim, a.lambda, c);
+    }
+    __syncthreads();
+}
+
 // ---- transpose in: "float4 #(64k + lane)" -> "chunk of lane", through the wave's staging buffer ----
 template <int M>
 __device__ __forceinline__ void transpose_in(float4* stage, int lane, const float4 (&t)[M / 4], float (&dst)[M], float scale)
@@ -564,13 +714,16 @@ __device__ __forceinline__ void store_pair(const WavePassArgs& a, const RowPos& 
 // solves (fgs_wave_common.h, reduced128).
 // (the longest chunk with two right-hand sides does not fit two waves per SIMD without spilling: the
 // pair staging keeps both right-hand sides and two of the three load batches alive at once)
-template <int M, int R, int FUSED, int NW = 1>
+template <int M, int R, int FUSED, int NW = 1, int WS = WS_PLANE>
 __global__ void __launch_bounds__(64 * NW, (M > (NW == 2 ? 40 : H_TWO_WAVE_MAX) && R > 1) ? 1 : 2) wave_hpass_kernel(WavePassArgs a)
 {
     static_assert(M % 4 == 0 && M >= 4, "chunk length must be a multiple of 4");
     static_assert(NW == 1 || NW == 2, "one or two wavefronts per row");
     constexpr bool LO = FUSED == FUSE_LO || FUSED == FUSE_LO_HALF;
     constexpr bool PAIR = R > 1;
+    constexpr bool GUIDE = WS != WS_PLANE;
+    static_assert(!GUIDE || (NW == 1 && !LO), "the guide forms: one-wave rows whose prologue leaves the staging buffer alone");
+    __shared__ __attribute__((aligned(16))) float lut_head[GUIDE ? GW_HEAD : 1];
     __shared__ float4 stage_all[NW][LO ? lo_stage_vec4(M) : M * 16];
     __shared__ float xch[NW == 2 ? 5 : 1];              // c in front of chunk 64; GS0, GS1, PS, QS of chunk 64
     __shared__ float red[NW == 2 ? 5 : 1][NW == 2 ? 128 : 1];   // separator rows
@@ -580,12 +733,15 @@ __global__ void __launch_bounds__(64 * NW, (M > (NW == 2 ? 40 : H_TWO_WAVE_MAX) 
     float4* stage = stage_all[wv];
 
     float4 tC[M / 4], t0[M / 4], t1[M / 4];
+    GuideRaw<M, WS> tG;
+    if constexpr (GUIDE) guide_fetch<M, WS>(a, lane, tG);
     if constexpr (LO) load_fused_lo<M, FUSED == FUSE_LO_HALF>(a, p, stage, tC, t0, t1);
-    else if constexpr (FUSED == FUSE_VIEW) load_fused_view<M>(a, p, tC, t0, t1);
-    else load_planes<M, R>(a, p, tC, t0, t1);
+    else if constexpr (FUSED == FUSE_VIEW) load_fused_view<M, !GUIDE>(a, p, tC, t0, t1);
+    else load_planes<M, R, !GUIDE>(a, p, tC, t0, t1);
 
     float c[M], f0[M], f1[M];
-    transpose_in<M>(stage, lane, tC, c, a.lambda);
+    if constexpr (GUIDE) guide_weights<M, WS>(a, stage, lut_head, lane, tG, c);
+    else transpose_in<M>(stage, lane, tC, c, a.lambda);
     if constexpr (PAIR && FUSED == FUSE_NONE) {
         pair_in<M>(stage, lane, t0, 0, f0, f1);
         pair_in<M>(stage, lane, t1, 1, f0, f1);
@@ -647,10 +803,32 @@ __global__ void __launch_bounds__(64 * NW, (M > (NW == 2 ? 40 : H_TWO_WAVE_MAX) 
 // single-occupancy kernels, whose half-width form needs five registers more than a lane has (it takes the general form).
 constexpr bool lo_half_bucket(int m, int nw) { return !(m == 60 && nw == 1); }
 
+// the guide forms of a bucket: every one-wave bucket has them
+constexpr bool guide_bucket(int nw) { return nw == 1; }
+
+// the plain and the fused-view pass with their weights from the guide (a.gw)
+template <int M, int WS>
+hipError_t launch_h_guide(const WavePassArgs& a, int n_rhs, dim3 grid, hipStream_t st)
+{
+    if (a.fuse.conf_in) {
+        if (n_rhs != 2) return hipErrorInvalidValue;
+        hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_VIEW, 1, WS>), grid, dim3(64), 0, st, a);
+    } else if (n_rhs == 2) hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_NONE, 1, WS>), grid, dim3(64), 0, st, a);
+    else hipLaunchKernelGGL((wave_hpass_kernel<M, 1, FUSE_NONE, 1, WS>), grid, dim3(64), 0, st, a);
+    return hipGetLastError();
+}
+
 template <int M, int NW = 1>
 hipError_t launch_h(const WavePassArgs& a, int n_rhs, int n_pairs, hipStream_t st)
 {
     dim3 grid(a.nscan, n_pairs), block(64 * NW);
+    if (a.gw.guide) {
+        if constexpr (guide_bucket(NW)) {
+            if (a.gw.ch == 1) return launch_h_guide<M, WS_GUIDE1>(a, n_rhs, grid, st);
+            if (a.gw.ch == 3) return launch_h_guide<M, WS_GUIDE3>(a, n_rhs, grid, st);
+        }
+        return hipErrorInvalidValue;
+    }
     if (a.fuse.lo_conf) {
         if (n_rhs != 2 || !a.fuse.lo_taps) return hipErrorInvalidValue;
         const int n = ((a.len + 3) / 4) * 4;
@@ -700,6 +878,18 @@ bool wave_hpass_can_fuse(const WavePassArgs& a)
     return true;
 }
 
+// The guide forms exist for one-wave rows whose right-hand sides come from the planes or the view-resolution fused
+// prologue; the guide needs no alignment (the kernel aligns its window itself), the table a 16-byte aligned base.
+bool wave_hpass_guide_fits(const WavePassArgs& a)
+{
+    if (!a.gw.guide || !a.gw.lut || (a.gw.ch != 1 && a.gw.ch != 3) || a.fuse.lo_conf) return false;
+    if ((reinterpret_cast<uintptr_t>(a.gw.lut) & 15u) != 0 || a.gw.x0 < 0 || a.gw.y0 < 0) return false;
+    if (a.len < 2 || a.len > wave_max_row_len()) return false;
+    int m, nw;
+    pick_row_bucket(a.len, m, nw);
+    return guide_bucket(nw);
+}
+
 bool wave_hpass_lo_half(const WavePassArgs& a)
 {
     if (!(a.fuse.lo_conf && a.fuse.lo_half && a.fuse.lo_scale_x == 0.5 && (a.fuse.hi_x0 & 1) == 0 && a.fuse.hi_x0 >= 2)) return false;
@@ -738,6 +928,7 @@ hipError_t launch_wave_hpass(const WavePassArgs& a, int n_rhs, int n_pairs, hipS
     if (a.len < 2 || a.len > wave_max_row_len() || a.pitch % 64 != 0 || a.pitch < a.len) return hipErrorInvalidValue;
     if (a.fuse.lo_conf && !wave_hpass_can_fuse_lo(a)) return hipErrorInvalidValue;
     if (!a.fuse.lo_conf && a.fuse.conf_in && !wave_hpass_can_fuse(a)) return hipErrorInvalidValue;
+    if (a.gw.guide && !wave_hpass_guide_fits(a)) return hipErrorInvalidValue;
     return dispatch_index<N_ROW_BUCKETS>(bucket_index(ROW_BUCKETS, a.len), [&](auto I) {
         constexpr Bucket b = ROW_BUCKETS[decltype(I)::value];
         return launch_h<b.m, b.chunks / 64>(a, n_rhs, n_pairs, st);

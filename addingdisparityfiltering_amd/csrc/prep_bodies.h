@@ -70,39 +70,57 @@ __device__ __forceinline__ WsGuide ws_guide(uintptr_t base0, ptrdiff_t stride_by
 }
 
 // the lane's window of a row: `wo` = byte offset (from the descriptor's base) of the aligned dword holding the lane's first pixel
-template <int CH>
+// (HOR = false: no horizontal differences are wanted, so the pixel to the right of the lane's four is not fetched)
+template <int CH, bool HOR>
 __device__ __forceinline__ WsWin<CH> ws_load(const WsGuide& gd, unsigned wo)
 {
     WsWin<CH> w;
     if constexpr (CH == 3) {
         w.a = __builtin_amdgcn_raw_buffer_load_b128(gd.rsrc, wo, 0, 0);
-        w.b = __builtin_amdgcn_raw_buffer_load_b32(gd.rsrc, wo + 16u, 0, 0);
+        w.b = HOR ? __builtin_amdgcn_raw_buffer_load_b32(gd.rsrc, wo + 16u, 0, 0) : 0u;
     } else {
         w.a = __builtin_amdgcn_raw_buffer_load_b64(gd.rsrc, wo, 0, 0);
     }
     return w;
 }
 
-// Table indices of a lane's four pixels in one row: hidx[k] = |pixel k - pixel k+1|^2 (FGS.cpp:607-612), vidx[k] =
+// Squared colour distances on packed bytes, shared by the weight kernels and the wave solver's row pass (fgs_wave_h.hip),
+// which forms its weights from the guide row itself.  Three-channel pixels are held as [c0 c1 c2 0]:
+//   sum_c (a_c - b_c)^2 = a.a + b.b - 2 a.b        (v_dot4_u32_u8)
+// four packed pixels (twelve bytes, three dwords starting on a pixel) as [c0 c1 c2 0] each
+__device__ __forceinline__ void ws_unpack3(unsigned e0, unsigned e1, unsigned e2, unsigned* p)
+{
+    p[0] = e0 & 0x00ffffffu;
+    p[1] = __builtin_amdgcn_perm(e1, e0, 0x0c050403u);
+    p[2] = __builtin_amdgcn_perm(e2, e1, 0x0c040302u);
+    p[3] = e2 >> 8;
+}
+__device__ __forceinline__ unsigned ws_norm2(unsigned p) { return __builtin_amdgcn_udot4(p, p, 0u, false); }
+// the table index of two pixels p, q and their a.a
+__device__ __forceinline__ int ws_dist2(unsigned p, unsigned pa, unsigned q, unsigned qa)
+{
+    return (int)(pa + qa) - 2 * (int)__builtin_amdgcn_udot4(p, q, 0u, false);
+}
+// ... of two one-channel pixels
+__device__ __forceinline__ int ws_dist2_c1(int v, int r) { return (v - r) * (v - r); }
+
+// Table indices of a lane's four pixels in one row: hidx[k] = |pixel k - pixel k+1|^2 (FGS.cpp:607-612; HOR only), vidx[k] =
 // |previous row's pixel k - pixel k|^2 (FGS.cpp:640-653); m = bytes the window starts before the first pixel.
-template <int CH>
+template <int CH, bool HOR>
 __device__ __forceinline__ void ws_indices(const WsWin<CH>& w, unsigned m, WsPrev<CH>& pv, int (&hidx)[WS_COLS], int (&vidx)[WS_COLS])
 {
     if constexpr (CH == 3) {
         const unsigned e0 = __builtin_amdgcn_alignbyte(w.a.y, w.a.x, m), e1 = __builtin_amdgcn_alignbyte(w.a.z, w.a.y, m);
         const unsigned e2 = __builtin_amdgcn_alignbyte(w.a.w, w.a.z, m), e3 = __builtin_amdgcn_alignbyte(w.b, w.a.w, m);
         unsigned p[WS_COLS + 1], pa[WS_COLS + 1];              // pixels as [c0 c1 c2 0], and a.a
-        p[0] = e0 & 0x00ffffffu;
-        p[1] = __builtin_amdgcn_perm(e1, e0, 0x0c050403u);
-        p[2] = __builtin_amdgcn_perm(e2, e1, 0x0c040302u);
-        p[3] = e2 >> 8;
+        ws_unpack3(e0, e1, e2, p);
         p[4] = e3 & 0x00ffffffu;
 #pragma unroll
-        for (int k = 0; k <= WS_COLS; k++) pa[k] = __builtin_amdgcn_udot4(p[k], p[k], 0u, false);
+        for (int k = 0; k <= WS_COLS; k++) pa[k] = ws_norm2(p[k]);
 #pragma unroll
         for (int k = 0; k < WS_COLS; k++) {
-            hidx[k] = (int)(pa[k] + pa[k + 1]) - 2 * (int)__builtin_amdgcn_udot4(p[k], p[k + 1], 0u, false);
-            vidx[k] = (int)(pa[k] + pv.qa[k]) - 2 * (int)__builtin_amdgcn_udot4(p[k], pv.q[k], 0u, false);
+            hidx[k] = HOR ? ws_dist2(p[k], pa[k], p[k + 1], pa[k + 1]) : 0;
+            vidx[k] = ws_dist2(p[k], pa[k], pv.q[k], pv.qa[k]);
             pv.q[k] = p[k]; pv.qa[k] = pa[k];
         }
     } else {
@@ -113,8 +131,8 @@ __device__ __forceinline__ void ws_indices(const WsWin<CH>& w, unsigned m, WsPre
             const int v = (int)((e >> (8 * k)) & 0xffu);
             const int r = k < WS_COLS - 1 ? (int)((e >> (8 * k + 8)) & 0xffu) : (int)nb;
             const int u = (int)((pv.q[0] >> (8 * k)) & 0xffu);
-            hidx[k] = (v - r) * (v - r);
-            vidx[k] = (u - v) * (u - v);
+            hidx[k] = HOR ? ws_dist2_c1(v, r) : 0;
+            vidx[k] = ws_dist2_c1(u, v);
         }
         pv.q[0] = e;
     }
@@ -142,26 +160,29 @@ constexpr unsigned WS_DROP = 0x80000000u;      // a byte offset no window reache
 // is the selector.  Round 3: the table indices of NATURAL images exceed the head in 1.5-4 % of the pixels
 // (tools/real_guide_time.py); the version before this one fetched those one lane at a time with dependent scalar loads
 // inside a branch and took 3.5x as long on the KITTI fixture as on the benchmark's synthetic scene.
+// HOR = false: the vertical weights only.
 struct WsPending { float wl[2 * WS_COLS]; unsigned g[2 * WS_COLS]; };
+template <bool HOR>
 __device__ __forceinline__ void ws_lookup_issue(const float* lut_head, const __amdgpu_buffer_rsrc_t& lutwin, const int (&hidx)[WS_COLS],
                                                 const int (&vidx)[WS_COLS], WsPending& p)
 {
 #pragma unroll
     for (int k = 0; k < WS_COLS; k++) {
-        p.wl[k] = lut_head[min(hidx[k], WS_LUT_HEAD - 1)];
+        p.wl[k] = HOR ? lut_head[min(hidx[k], WS_LUT_HEAD - 1)] : 0.0f;
         p.wl[WS_COLS + k] = lut_head[min(vidx[k], WS_LUT_HEAD - 1)];
     }
 #pragma unroll
     for (int k = 0; k < WS_COLS; k++) {
-        p.g[k] = __builtin_amdgcn_raw_buffer_load_b32(lutwin, hidx[k] >= WS_LUT_HEAD ? (unsigned)hidx[k] * 4u : WS_DROP, 0, 0);
+        p.g[k] = HOR ? __builtin_amdgcn_raw_buffer_load_b32(lutwin, hidx[k] >= WS_LUT_HEAD ? (unsigned)hidx[k] * 4u : WS_DROP, 0, 0) : 0u;
         p.g[WS_COLS + k] = __builtin_amdgcn_raw_buffer_load_b32(lutwin, vidx[k] >= WS_LUT_HEAD ? (unsigned)vidx[k] * 4u : WS_DROP, 0, 0);
     }
 }
+template <bool HOR>
 __device__ __forceinline__ void ws_lookup_finish(const WsPending& p, float (&wh)[WS_COLS], float (&wv)[WS_COLS])
 {
 #pragma unroll
     for (int k = 0; k < WS_COLS; k++) {
-        wh[k] = p.g[k] != 0u ? __uint_as_float(p.g[k]) : p.wl[k];
+        wh[k] = !HOR ? 0.0f : p.g[k] != 0u ? __uint_as_float(p.g[k]) : p.wl[k];
         wv[k] = p.g[WS_COLS + k] != 0u ? __uint_as_float(p.g[WS_COLS + k]) : p.wl[WS_COLS + k];
     }
 }
@@ -173,7 +194,7 @@ struct WsOut {
     __device__ __forceinline__ void init(const WeightArgs& a, size_t pz, int j0, int y_first)
     {
         const Geom& g = a.g;
-        chor = ws_window(a.chor + pz * g.plane, g.plane * sizeof(float));
+        chor = ws_window(a.chor ? a.chor + pz * g.plane : a.chor, a.chor ? g.plane * sizeof(float) : 0);   // (no Chor: an empty window)
         cvert = ws_window(a.cvert + pz * g.plane, g.plane * sizeof(float));
         strip = a.cvert_orient == ORIENT_STRIP;
 #pragma unroll
@@ -210,7 +231,9 @@ struct WsOut {
 // Block (bx, by) of nby row blocks, image pz.  `active`: the thread is one of the WS_NT that do the work -- a launch
 // with wider blocks (the merged preparation kernel below conf_band_kernel) parks its other waves here: they take part
 // in the one barrier (behind the table load) and leave.
-template <int CH>
+// HOR = false (WeightArgs::chor is null: the wave solver's row passes take their weights from the guide themselves):
+// Cvert only -- no horizontal differences, look-ups or stores.
+template <int CH, bool HOR = true>
 __device__ __forceinline__ void weights_stream_body(const WeightArgs& a, int bx, int by, int nby, size_t pz, WsShared<CH>& sh, bool active)
 {
     static_assert(CH == 1 || CH == 3, "guides have one or three channels");
@@ -239,7 +262,7 @@ __device__ __forceinline__ void weights_stream_body(const WeightArgs& a, int bx,
     const unsigned lane_off = (unsigned)(tid * WS_COLS * CH);
     // row n of the block = ROI row min(y0+n, rh-1): byte offset of the block's first pixel (its low two bits: the misalignment)
     auto row_off = [&](int n) -> unsigned { return col_off + (unsigned)(min(y0 + n, g.rh - 1) - y0) * gd.stride; };
-    auto load = [&](int n) -> WsWin<CH> { return ws_load<CH>(gd, (row_off(n) & ~3u) + lane_off); };
+    auto load = [&](int n) -> WsWin<CH> { return ws_load<CH, HOR>(gd, (row_off(n) & ~3u) + lane_off); };
 
     WsOut out;
     out.init(a, pz, j0, y0);
@@ -257,8 +280,8 @@ __device__ __forceinline__ void weights_stream_body(const WeightArgs& a, int bx,
     WsPending pend;
     {
         int hidx[WS_COLS], vidx[WS_COLS];
-        ws_indices<CH>(nxt[0], row_off(0) & 3u, pv, hidx, vidx);
-        ws_lookup_issue(lut_head, lutwin, hidx, vidx, pend);
+        ws_indices<CH, HOR>(nxt[0], row_off(0) & 3u, pv, hidx, vidx);
+        ws_lookup_issue<HOR>(lut_head, lutwin, hidx, vidx, pend);
     }
     for (int n0 = 0; n0 < nrows; n0 += WS_U) {
 #pragma unroll
@@ -274,12 +297,12 @@ __device__ __forceinline__ void weights_stream_body(const WeightArgs& a, int bx,
             WsPending ahead;
             {
                 int hidx[WS_COLS], vidx[WS_COLS];
-                ws_indices<CH>(s + 1 < WS_U ? cur[s + 1 < WS_U ? s + 1 : 0] : nxt[0], row_off(min(n + 1, nrows - 1)) & 3u, pv, hidx, vidx);
-                ws_lookup_issue(lut_head, lutwin, hidx, vidx, ahead);
+                ws_indices<CH, HOR>(s + 1 < WS_U ? cur[s + 1 < WS_U ? s + 1 : 0] : nxt[0], row_off(min(n + 1, nrows - 1)) & 3u, pv, hidx, vidx);
+                ws_lookup_issue<HOR>(lut_head, lutwin, hidx, vidx, ahead);
             }
             float wh[WS_COLS], wv[WS_COLS];
-            ws_lookup_finish(pend, wh, wv);
-            out.store_h(n, wh, n < nrows - 1);                                         // Chor of ROI row y0+n, FGS.cpp:607-614
+            ws_lookup_finish<HOR>(pend, wh, wv);
+            if constexpr (HOR) out.store_h(n, wh, n < nrows - 1);                                         // Chor of ROI row y0+n, FGS.cpp:607-614
             out.store_v(n - 1, wv, y0 + n - 1 == g.rh - 1, n >= 1 && n < nrows);       // Cvert of the previous row, FGS.cpp:635-660
             pend = ahead;
         }

@@ -121,11 +121,12 @@ __global__ void __launch_bounds__(NT) weights_kernel(WeightArgs a)
 
 // Row-major outputs (wave solver): the column-walking streaming kernel; its body is shared with the merged preparation
 // kernel of conf_kernels.hip (prep_bodies.h).
-template <int CH>
+// HOR = false: Cvert only (a.chor is null; the row passes read the guide themselves).
+template <int CH, bool HOR>
 __global__ void __launch_bounds__(prep::WS_NT) weights_stream_kernel(WeightArgs a)
 {
     __shared__ prep::WsShared<CH> sh;
-    prep::weights_stream_body<CH>(a, blockIdx.x, blockIdx.y, gridDim.y, blockIdx.z, sh, true);
+    prep::weights_stream_body<CH, HOR>(a, blockIdx.x, blockIdx.y, gridDim.y, blockIdx.z, sh, true);
 }
 
 // Row-major [rh][pw] -> transposed [rw][ph] through a 64 x 64 LDS tile, 16-byte accesses on both sides
@@ -157,8 +158,17 @@ __global__ void __launch_bounds__(256) transpose_n_to_t_kernel(const float* __re
 
 } // namespace
 
+// row-major Chor: the streaming kernel -- unless a block's slice of the guide cannot be put behind one 32-bit buffer
+// descriptor (row strides of a gigabyte: the generic tile kernel takes those)
+bool weights_stream_fits(const WeightArgs& a)
+{
+    static const bool force_generic = [] { const char* e = getenv("ADF_WEIGHTS_GENERIC"); return e && atoi(e) != 0; }();   // test hook
+    return !force_generic && a.chor_orient == ORIENT_N && a.stride > 0 && a.stride < ((ptrdiff_t)1 << 29) && (size_t)a.g.W * a.ch < ((size_t)1 << 29);
+}
+
 hipError_t launch_weights(const WeightArgs& a, int n_pairs, hipStream_t st)
 {
+    const bool hor = a.chor != nullptr;   // no Chor plane: only the streaming kernel has that form
     if (a.chor_orient == ORIENT_T && a.cvert_orient == ORIENT_N && a.scratch) {
         // exact solver: the streaming kernel (one pass over the guide at streaming speed) + one tiled
         // transpose of Chor beat the generic tile kernel's scattered look-ups by 3x
@@ -171,10 +181,7 @@ hipError_t launch_weights(const WeightArgs& a, int n_pairs, hipStream_t st)
         return hipGetLastError();
     }
     if (a.cvert_orient != ORIENT_N && !(a.cvert_orient == ORIENT_STRIP && a.chor_orient == ORIENT_N)) return hipErrorInvalidValue;
-    // row-major Chor: the streaming kernel -- unless a block's slice of the guide cannot be put behind one 32-bit buffer
-    // descriptor (row strides of a gigabyte: the generic tile kernel below takes those)
-    static const bool force_generic = [] { const char* e = getenv("ADF_WEIGHTS_GENERIC"); return e && atoi(e) != 0; }();   // test hook
-    if (!force_generic && a.chor_orient == ORIENT_N && a.stride > 0 && a.stride < ((ptrdiff_t)1 << 29) && (size_t)a.g.W * a.ch < ((size_t)1 << 29)) {
+    if (weights_stream_fits(a)) {
         dim3 sgrid((a.g.rw + prep::WS_BCOLS - 1) / prep::WS_BCOLS, 1, n_pairs);
         {
             // rows per block: tall blocks amortise the table load and the extra row; enough blocks for the chip; and few
@@ -185,11 +192,14 @@ hipError_t launch_weights(const WeightArgs& a, int n_pairs, hipStream_t st)
             while (rpb > 1 && (size_t)(rpb + 1) * (size_t)a.stride >= ((size_t)1 << 30)) rpb >>= 1;
             sgrid.y = (a.g.rh + rpb - 1) / rpb;
         }
-        if (a.ch == 1) hipLaunchKernelGGL(weights_stream_kernel<1>, sgrid, dim3(prep::WS_NT), 0, st, a);
-        else if (a.ch == 3) hipLaunchKernelGGL(weights_stream_kernel<3>, sgrid, dim3(prep::WS_NT), 0, st, a);
+        if (a.ch == 1 && hor) hipLaunchKernelGGL((weights_stream_kernel<1, true>), sgrid, dim3(prep::WS_NT), 0, st, a);
+        else if (a.ch == 1) hipLaunchKernelGGL((weights_stream_kernel<1, false>), sgrid, dim3(prep::WS_NT), 0, st, a);
+        else if (a.ch == 3 && hor) hipLaunchKernelGGL((weights_stream_kernel<3, true>), sgrid, dim3(prep::WS_NT), 0, st, a);
+        else if (a.ch == 3) hipLaunchKernelGGL((weights_stream_kernel<3, false>), sgrid, dim3(prep::WS_NT), 0, st, a);
         else return hipErrorInvalidValue;
         return hipGetLastError();
     }
+    if (!hor) return hipErrorInvalidValue;
     dim3 grid((a.g.rw + TX - 1) / TX, (a.g.rh + TY - 1) / TY, n_pairs);
     if (a.ch == 1) hipLaunchKernelGGL(weights_kernel<1>, grid, dim3(NT), 0, st, a);
     else if (a.ch == 3) hipLaunchKernelGGL(weights_kernel<3>, grid, dim3(NT), 0, st, a);

@@ -27,7 +27,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import SGBM_COST_BT, SGBM_COST_CENSUS_DENSE, SGBM_COST_CENSUS_SPARSE  # noqa: F401  (re-exported)
-from ._lib import AdfError, PATH_CONF_BAND, PATH_FUSED_FIRST_PASS, PATH_MERGED_PREP, PATH_SCALED_FUSED, PATH_SCALED_HALF, Rect, SOLVER_EXACT, SOLVER_WAVE  # noqa: F401  (re-exported)
+from ._lib import AdfError, PATH_CONF_BAND, PATH_FUSED_FIRST_PASS, PATH_MERGED_PREP, PATH_ROW_WEIGHTS_GUIDE, PATH_SCALED_FUSED, PATH_SCALED_HALF, Rect, SOLVER_EXACT, SOLVER_WAVE  # noqa: F401  (re-exported)
 
 try:  # torch is optional plumbing: device memory and streams only
     import torch
@@ -226,6 +226,10 @@ class DisparityWLSFilter(_Handle, DisparityFilter):
     def getLastPath(self):
         """PATH_* bits of the last filter call: which kernels its confidence stage took (introspection only)."""
         return _read(_lib.lib().adf_wls_get_last_path, C.c_int, self._h)
+
+    def getLastSolverPath(self):
+        """... and which its solve passes took (PATH_ROW_WEIGHTS_GUIDE): a word of its own."""
+        return _read(_lib.lib().adf_wls_get_last_solver_path, C.c_int, self._h)
 
     def enableProfiling(self, on=True):
         """Bracket every kernel launch with HIP events on the caller's stream (measurement hook)."""

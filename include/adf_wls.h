@@ -128,6 +128,11 @@ int adf_wls_get_last_solver(const adf_wls_t* h, int* solver);
 #define ADF_PATH_SCALED_HALF 16      /* ... in its form for maps of exactly half the view's width on a ROI starting on an even
                                         column >= 2 (the sample's default): four output columns share four source elements */
 int adf_wls_get_last_path(const adf_wls_t* h, int* path_flags);
+/* ... and which the solve passes took -- a word of its own: callers compare the word above as a whole. */
+#define ADF_PATH_ROW_WEIGHTS_GUIDE 32 /* wave solver, full-resolution call: the row passes formed their edge weights from the
+                                        guide rows themselves (FGS.cpp:607-614 inside the pass); the weight kernel wrote the
+                                        vertical weights only and the horizontal plane was neither written nor read */
+int adf_wls_get_last_solver_path(const adf_wls_t* h, int* path_flags);
 
 /* DisparityFilter::filter (DF.hpp:75, DF.cpp:219-298) on a batch of n_pairs
  * independent, equally sized stereo pairs laid out `*_pair_stride` bytes apart
