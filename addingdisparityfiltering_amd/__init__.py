@@ -7,6 +7,7 @@ filter construction does, and fails loudly if libadf_wls.so has not been built.
 from .ximgproc import (  # noqa: F401
     AdfError,
     COLOR_BGR2GRAY,
+    CV_32F,
     DisparityFilter,
     DisparityWLSFilter,
     FastGlobalSmootherFilter,
@@ -40,7 +41,11 @@ from .ximgproc import (  # noqa: F401
     getDisparityVis,
     halfSize,
     matcherViews,
+    pointCloud,
+    pointCloudWorkspaceBytes,
     readGT,
+    reprojectImageTo3D,
+    reprojectWorkspaceBytes,
     resize,
     speckleWorkspaceBytes,
 )

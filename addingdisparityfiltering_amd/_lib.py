@@ -16,6 +16,7 @@ PATH_CONF_BAND, PATH_FUSED_FIRST_PASS, PATH_MERGED_PREP, PATH_SCALED_FUSED, PATH
 PATH_ROW_WEIGHTS_GUIDE = 32    # adf_wls_get_last_solver_path bit
 DEPTH_8U, DEPTH_16S, DEPTH_32F = 0, 3, 5
 SGBM_COST_BT, SGBM_COST_CENSUS_DENSE, SGBM_COST_CENSUS_SPARSE = 0, 1, 2    # adf_sgbm_set_cost (include/adf_wls.h)
+MISSING_NONE, MISSING_MIN, MISSING_VALUE = 0, 1, 2    # adf_reproject_params.missing_mode (include/adf_wls.h)
 
 
 class AdfError(RuntimeError):
@@ -35,10 +36,18 @@ class Rect(C.Structure):
     _fields_ = [("x", C.c_int), ("y", C.c_int), ("width", C.c_int), ("height", C.c_int)]
 
 
+class ReprojectParams(C.Structure):
+    """adf_reproject_params: Q row-major, disp_scale, missing_mode, missing_value."""
+    _fields_ = [("Q", C.c_double * 16), ("disp_scale", C.c_double), ("missing_mode", C.c_int), ("missing_value", C.c_double)]
+
+
 # every symbol include/adf_wls.h declares: (name, restype, argtypes)
 _vp, _i, _d, _pd, _sz = C.c_void_p, C.c_int, C.c_double, C.c_ssize_t, C.c_size_t
 _FILTER_DEV = [_vp, _i, _vp, _pd, _pd, _vp, _pd, _pd, _i, _i, _i, _vp, _pd, _pd, _vp, _pd, _pd,
                C.POINTER(Rect), _vp]
+_REPROJECT_DEV = [_i, _vp, _i, _pd, _pd, _i, _i, C.POINTER(ReprojectParams), _vp, _pd, _pd, _i, _vp, _sz, _vp]
+_POINT_CLOUD_DEV = [_i, _vp, _i, _pd, _pd, _i, _i, C.POINTER(ReprojectParams), C.POINTER(Rect), _d, _d, _vp, _pd, _pd, _i,
+                    _vp, _pd, _vp, _pd, _vp, _pd, _i, _vp, _vp, _sz, _vp]
 _FILTER_SCALED_DEV = [_vp, _i, _vp, _pd, _pd, _i, _i, _vp, _pd, _pd, _i, _i, _i, _vp, _pd, _pd, _vp, _pd, _pd,
                       C.POINTER(Rect), _vp]
 SYMBOLS = [
@@ -120,6 +129,12 @@ SYMBOLS = [
     ("adf_half_size", _i, [_i, C.POINTER(_i)]),
     ("adf_prepare_views_device", _i, [_i, _vp, _pd, _pd, _i, _i, _i, _vp, _pd, _pd, _i, _i, _i, _vp]),
     ("adf_prepare_views_host", _i, [_i, _vp, _pd, _pd, _i, _i, _i, _vp, _pd, _pd, _i, _i, _i]),
+    ("adf_reproject_workspace_bytes", _sz, [_i]),
+    ("adf_reproject_to_3d_device", _i, _REPROJECT_DEV),
+    ("adf_reproject_to_3d_host", _i, _REPROJECT_DEV[:-3]),
+    ("adf_point_cloud_workspace_bytes", _sz, [_i, _i, _i]),
+    ("adf_point_cloud_device", _i, _POINT_CLOUD_DEV),
+    ("adf_point_cloud_host", _i, _POINT_CLOUD_DEV[:-3]),
 ]
 
 _lib = None

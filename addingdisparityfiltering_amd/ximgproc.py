@@ -14,6 +14,7 @@ edge_filter.hpp (EF.hpp), over the C-ABI in include/adf_wls.h:
     filterSpeckles(img, newVal, maxSpeckleSize, maxDiff, buf)   calib3d (outside the reference tree)
     censusTransform(image, kernelSize, type)        modules/stereo descriptor.hpp:428 / descriptor.cpp:77-98
     resize(src, dsize, fx, fy) at half size, cvtColor(src, COLOR_BGR2GRAY)   imgproc (outside the reference tree)
+    reprojectImageTo3D(disparity, Q, handleMissingValues, ddepth), pointCloud(...)   calib3d (outside the reference tree)
 
 Images are numpy arrays (host path: copied to the GPU and back) or torch CUDA
 tensors (device path: zero-copy, asynchronous on torch's current stream).  A
@@ -701,6 +702,182 @@ def matcherViews(view, scale=0.5, gray=True, dst=None):
     if not half and not to_gray:
         raise AdfError(_lib.ADF_EBADARG, "matcherViews: scale 1.0 without a colour conversion leaves nothing to do")
     return _prepare_views(im, batched, half, 1 if to_gray else im.c, dst, "matcherViews")
+
+
+# ---------------------------------------------------------------------------------------------
+# Reprojection to 3-D (cv::reprojectImageTo3D of calib3d, outside the reference tree) and the point list, on the device
+# (csrc/reproject_kernels.hip; definition, missing values and the unpinned parity: include/adf_wls.h).
+# ---------------------------------------------------------------------------------------------
+CV_32F = 5              # cv's depth code, the one `ddepth` reprojectImageTo3D builds
+_RP, _PC = "reprojectImageTo3D", "pointCloud"
+
+
+def _reproject_source(who, disparity):
+    """(_Image, batched, depth code) of a CV_16SC1 / CV_32FC1 map (H,W) or batch (N,H,W)."""
+    if disparity is None:
+        raise AdfError(_lib.ADF_EBADARG, "%s: the disparity map is empty" % who)
+    dt = _NUMPY_DTYPE.get(disparity.dtype if _is_torch(disparity) else np.asarray(disparity).dtype)
+    if dt not in (np.int16, np.float32):
+        raise AdfError(_lib.ADF_EBADARG, "%s: disparity must be CV_16SC1 or CV_32FC1" % who)
+    nd = len(disparity.shape)
+    if nd not in (2, 3):
+        raise AdfError(_lib.ADF_EBADARG, "%s: disparity must be (H,W) or a batch (N,H,W)" % who)
+    im = _Image(disparity, dt, "disparity", nd == 3)
+    if im.w * im.h >= 2 ** 31:
+        raise AdfError(_lib.ADF_ESIZE, "%s: W*H must be below 2^31" % who)
+    return im, nd == 3, _DEPTH[dt]
+
+
+def _reproject_params(who, Q, dispScale, handleMissingValues, missingValue):
+    """adf_reproject_params from cv's arguments: missingValue (when given) selects ADF_MISSING_VALUE, else
+    handleMissingValues selects ADF_MISSING_MIN."""
+    if _is_torch(Q):
+        Q = Q.detach().cpu().numpy()
+    try:
+        q = np.asarray(Q, dtype=np.float64)
+    except (TypeError, ValueError):
+        q = np.zeros(0)
+    if q.shape != (4, 4):
+        raise AdfError(_lib.ADF_EBADARG, "%s: Q must be a 4x4 matrix" % who)
+    prm = _lib.ReprojectParams()
+    prm.Q[:] = [float(v) for v in q.ravel()]
+    prm.disp_scale = float(dispScale)
+    if not math.isfinite(prm.disp_scale):
+        raise AdfError(_lib.ADF_EBADARG, "%s: disp_scale must be finite" % who)
+    prm.missing_mode, prm.missing_value = _lib.MISSING_MIN if handleMissingValues else _lib.MISSING_NONE, 0.0
+    if missingValue is not None:
+        prm.missing_mode, prm.missing_value = _lib.MISSING_VALUE, float(missingValue)
+        if not math.isfinite(prm.missing_value):
+            raise AdfError(_lib.ADF_EBADARG, "%s: missing_value must be finite" % who)
+    return prm
+
+
+def reprojectWorkspaceBytes(n):
+    """Bytes of device workspace reprojectImageTo3D needs for n maps (4 per map; read with handleMissingValues only)."""
+    return int(_lib.lib().adf_reproject_workspace_bytes(int(n)))
+
+
+def pointCloudWorkspaceBytes(n, H, W):
+    """Bytes of device workspace the point list of n maps of H x W needs (adf_point_cloud_workspace_bytes)."""
+    return int(_lib.lib().adf_point_cloud_workspace_bytes(int(n), int(W), int(H)))
+
+
+def reprojectImageTo3D(disparity, Q, handleMissingValues=False, ddepth=-1, dst=None, dispScale=1.0, missingValue=None,
+                       zOnly=False, buf=None):
+    """cv::reprojectImageTo3D(disparity, _3dImage, Q, handleMissingValues, ddepth) (calib3d): the CV_32FC3 image of
+    (X, Y, Z) = Q * (x, y, d, 1) / W for a CV_16SC1 / CV_32FC1 map (H,W) or a batch (N,H,W) -> (H,W,3) / (N,H,W,3), every
+    step one binary64 operation in the order include/adf_wls.h states (bit-exact against tests/reproject_ref.py; parity
+    with calib3d is unpinned).  A numpy map takes the host entry; a torch CUDA tensor runs on the device, asynchronously
+    on torch's current stream (row strides of a sliced view are honoured).  `Q`: any 4x4 array-like.  `ddepth`: -1 or
+    CV_32F.  handleMissingValues: pixels at the map's minimum get Z = 10000 (each map of a batch has its own minimum).
+    Extensions: `dispScale` multiplies the raw value first (1/16 turns the filters' fixed-point units into pixels; cv
+    itself never divides), `missingValue` names the missing value instead of reducing for the minimum (-16 for filterFloat
+    output), `zOnly` gives the Z plane (H,W) alone, `dst` an output to write into, `buf` (device path with
+    handleMissingValues) a CUDA tensor of at least reprojectWorkspaceBytes(N) bytes: with it, or without
+    handleMissingValues, the call allocates nothing and may be captured into a CUDA graph."""
+    if ddepth not in (-1, CV_32F):
+        raise AdfError(_lib.ADF_EBADARG, "%s: ddepth must be -1 or CV_32F (CV_16SC3 and CV_32SC3 are not built)" % _RP)
+    im, batched, depth = _reproject_source(_RP, disparity)
+    prm = _reproject_params(_RP, Q, dispScale, handleMissingValues, missingValue)
+    ch = 1 if zOnly else 3
+    shape = ((im.n,) if batched else ()) + (im.h, im.w) + (() if zOnly else (3,))
+    if dst is None:
+        dst = _empty(im, shape, np.float32)
+    if tuple(dst.shape) != shape:
+        raise AdfError(_lib.ADF_ESIZE, "%s: dst must have shape %s" % (_RP, shape))
+    D = _Image(dst, np.float32, "dst", batched, allow_channels=(ch,))
+    if D.device != im.device:
+        raise AdfError(_lib.ADF_ESIZE, "%s: dst must have shape %s on the side (host or device) of disparity" % (_RP, shape))
+    args = (im.n, im.ptr, depth, im.stride, im.pair_stride, im.w, im.h, C.byref(prm), D.ptr, D.stride, D.pair_stride, ch)
+    if not im.device:
+        _call("adf_reproject_to_3d", im, args)
+        return dst
+    if dst.device != im.keep.device:
+        raise AdfError(_lib.ADF_EBADARG, "dst lives on %s, disparity on %s" % (dst.device, im.keep.device))
+    ws, ws_bytes = None, 0
+    if buf is not None:
+        if not (_is_torch(buf) and buf.is_cuda and buf.is_contiguous()):
+            raise AdfError(_lib.ADF_EBADARG, "buf must be a contiguous CUDA tensor (or None)")
+        if buf.device != im.keep.device:
+            raise AdfError(_lib.ADF_EBADARG, "buf lives on %s, disparity on %s" % (buf.device, im.keep.device))
+        ws, ws_bytes = buf.data_ptr(), buf.numel() * buf.element_size()
+        if prm.missing_mode == _lib.MISSING_MIN and ws_bytes < reprojectWorkspaceBytes(im.n):
+            raise AdfError(_lib.ADF_ESIZE, "buf holds %d bytes; %d needed" % (ws_bytes, reprojectWorkspaceBytes(im.n)))
+    with torch.cuda.device(im.keep.device):
+        _call("adf_reproject_to_3d", im, args + (ws, ws_bytes))
+    return dst
+
+
+def pointCloud(disparity, Q, view=None, ROI=None, zRange=None, handleMissingValues=False, missingValue=None, dispScale=1.0,
+               capacity=None, withIndex=False):
+    """Extension: the compact list of the valid points of a map, without the (H,W,3) image ever being written.  A pixel
+    is valid when it lies inside `ROI` ((x, y, w, h); None = the whole map), is not missing (handleMissingValues /
+    missingValue as in reprojectImageTo3D), its X, Y, Z are finite and zRange[0] <= Z <= zRange[1] (`zRange` None = no
+    range).  Returns (points, colours, index, count): points (count,3) float32 in raster order with the bits
+    reprojectImageTo3D gives, colours (count,C) uint8 from `view` ((H,W) or (H,W,C), C 1 or 3; None without a view), index
+    (count,) int32 = y*W + x with withIndex (else None), count = the number of valid pixels.  `capacity` bounds the entries
+    written (default: the ROI's area); count is the full number even then, and the outputs are trimmed to
+    min(count, capacity).  THE TRIM COSTS ONE HOST READ OF THE COUNT: on the device path the call synchronises torch's
+    current stream once (callers that must not wait use adf_point_cloud_device).  A batch (N,H,W) gives four lists."""
+    im, batched, depth = _reproject_source(_PC, disparity)
+    prm = _reproject_params(_PC, Q, dispScale, handleMissingValues, missingValue)
+    roi = _as_rect(ROI) or Rect(0, 0, im.w, im.h)
+    if roi.x < 0 or roi.y < 0 or roi.width < 1 or roi.height < 1 or roi.x > im.w - roi.width or roi.y > im.h - roi.height:
+        raise AdfError(_lib.ADF_ESIZE, "%s: ROI does not fit the map" % _PC)
+    z_min, z_max = (-math.inf, math.inf) if zRange is None else (float(zRange[0]), float(zRange[1]))
+    if math.isnan(z_min) or math.isnan(z_max):
+        raise AdfError(_lib.ADF_EBADARG, "%s: z_min and z_max must not be NaN" % _PC)
+    area = roi.width * roi.height
+    if capacity is None:
+        capacity = area
+    capacity = int(capacity)
+    if capacity < 0:
+        raise AdfError(_lib.ADF_EBADARG, "%s: capacity must not be negative" % _PC)
+    capacity = min(capacity, _INT32_MAX)
+    V, vch = None, 0
+    if view is not None:
+        nd = len(disparity.shape)
+        extra = len(view.shape) - nd
+        if extra not in (0, 1) or tuple(view.shape[:nd]) != tuple(disparity.shape):
+            raise AdfError(_lib.ADF_ESIZE, "%s: view must have the disparity map's size" % _PC)
+        vch = view.shape[-1] if extra else 1
+        if vch not in (1, 3):
+            raise AdfError(_lib.ADF_EBADARG, "%s: view_channels must be 1 or 3" % _PC)
+        V = _Image(view[..., 0] if extra and vch == 1 else view, np.uint8, "view", batched, allow_channels=(vch,))
+        if V.device != im.device:
+            raise AdfError(_lib.ADF_EBADARG, "inputs must all be numpy arrays or all be CUDA tensors")
+    rows = max(1, min(capacity, area))                           # (an empty tensor has no pointer to pass)
+    if im.device:
+        dev = im.keep.device
+        if V is not None and V.keep.device != dev:
+            raise AdfError(_lib.ADF_EBADARG, "view lives on %s, disparity on %s" % (V.keep.device, dev))
+        points = torch.empty((im.n, rows, 3), dtype=torch.float32, device=dev)
+        colours = torch.empty((im.n, rows, vch), dtype=torch.uint8, device=dev) if V is not None else None
+        index = torch.empty((im.n, rows), dtype=torch.int32, device=dev) if withIndex else None
+        counts = torch.empty((im.n,), dtype=torch.int32, device=dev)
+        ptr = lambda t: None if t is None else t.data_ptr()
+    else:
+        points = np.empty((im.n, rows, 3), np.float32)
+        colours = np.empty((im.n, rows, vch), np.uint8) if V is not None else None
+        index = np.empty((im.n, rows), np.int32) if withIndex else None
+        counts = np.zeros((im.n,), np.uint32)
+        ptr = lambda a: None if a is None else a.ctypes.data
+    args = (im.n, im.ptr, depth, im.stride, im.pair_stride, im.w, im.h, C.byref(prm), C.byref(roi), z_min, z_max,
+            None if V is None else V.ptr, 0 if V is None else V.stride, 0 if V is None else V.pair_stride, vch,
+            ptr(points), rows * 12, ptr(colours), rows * vch, ptr(index), rows * 4, capacity, ptr(counts))
+    if im.device:
+        with torch.cuda.device(im.keep.device):
+            _call("adf_point_cloud", im, args + (None, 0))
+        got = [int(c) for c in counts.cpu().tolist()]            # the one host read (synchronises the current stream)
+    else:
+        _call("adf_point_cloud", im, args)
+        got = [int(c) for c in counts]
+    keep = [min(c, capacity) for c in got]
+    cut = lambda a: [None] * im.n if a is None else [a[k, :keep[k]] for k in range(im.n)]
+    P, Cl, I = cut(points), cut(colours), cut(index)
+    if batched:
+        return P, Cl, I, got
+    return P[0], Cl[0], I[0], got[0]
 
 
 def createDisparityWLSFilter(matcher_left):

@@ -542,6 +542,82 @@ int adf_prepare_views_host(int n_images, const uint8_t* src, ptrdiff_t src_strid
                            uint8_t* dst, ptrdiff_t dst_stride, ptrdiff_t dst_image_stride,
                            int dst_W, int dst_H, int dst_channels);
 
+/* ---------------- reprojection to 3-D (cv::reprojectImageTo3D) and the point list ----------------
+ * cv::reprojectImageTo3D(disparity, _3dImage, Q, handleMissingValues, ddepth) of OpenCV's calib3d, the call a stereo
+ * pipeline makes after filtering: from a disparity map and the 4x4 matrix Q of stereoRectify to an XYZ image, and --
+ * an extension -- to a compact list of the valid points.  n_maps equally sized maps `map_stride` bytes apart, CV_16SC1
+ * (ADF_16S) or CV_32FC1 (ADF_32F); CV_8U / CV_32S maps are not supported.
+ *
+ * Reprojection.  Map pixel (x, y) with raw source value s, Q row-major doubles:
+ *     d   = (double)s * disp_scale                 (disp_scale = 1.0 is cv's behaviour: no division by 16 for CV_16S)
+ *     r_i = ((Q[i][0]*x + Q[i][1]*y) + Q[i][3]) + Q[i][2]*d          i = 0..3
+ *     iw  = 1.0 / r_3
+ *     X = r_0*iw, Y = r_1*iw, Z = r_2*iw           stored as (float)X, (float)Y, (float)Z (round to nearest)
+ *   - every product, sum and the division is ONE IEEE binary64 operation, in exactly this order; no fused multiply-add;
+ *   - nothing is sanitised: r_3 == 0 gives +-inf or NaN as the arithmetic gives them, as in cv.  The sign and payload of
+ *     a NaN are not part of the contract.
+ * calib3d is outside the reference tree, so parity with it is UNPINNED: this is the library's own definition, bit-exact
+ * against the direct NumPy statement tests/reproject_ref.py.  One known difference: cv accumulates Q[i][0] column by
+ * column in double (x additions) instead of multiplying by x, which differs in the last bits of a double before the
+ * rounding to float.
+ *
+ * Missing values (missing_mode):
+ *     ADF_MISSING_NONE  0  no pixel is missing
+ *     ADF_MISSING_MIN   1  cv's handleMissingValues = true: m = the minimum raw source value of THAT map -- each map of a
+ *                          batch has its own, taken over the whole map (not a ROI), NaN in a float map ignored (a map of
+ *                          NaN only has m = NaN: nothing is missing)
+ *     ADF_MISSING_VALUE 2  extension: m = missing_value, no reduction launch.  Suits this library's own fills: -16 outside
+ *                          the filter's ROI, (minDisparity - 1) * 16 from the matchers
+ *   missing(s) <=> fabs((double)s - m) <= FLT_EPSILON, tested on RAW values (before disp_scale).  A missing pixel gets
+ *   Z = 10000.0f (cv's bigZ); its X and Y stay as computed.
+ *
+ * Outputs.  out_channels = 3: CV_32FC3, interleaved XYZ.  out_channels = 1 (extension): the Z plane only, a CV_32FC1 depth
+ * map.  cv's ddepth CV_16SC3 / CV_32SC3 are not built.  `out`, out_stride and out_map_stride must be multiples of 4 bytes;
+ * a source whose base and strides are multiples of 8 (CV_16S) or 16 bytes (CV_32F) is read with one load per four pixels,
+ * an output whose base and strides are multiples of 16 bytes is written with 16-byte stores; anything else gives the same
+ * bits element by element (slower).
+ *
+ * Point list.  valid(p) <=> p lies inside `roi` (NULL = whole map) and not missing(s) and Xf, Yf, Zf are all finite and
+ * z_min <= Zf <= z_max (doubles; -infinity / +infinity switch the range off; NaN is refused).  Per map, the k-th valid
+ * pixel in raster order (y major, x minor) gives points[k] = (Xf, Yf, Zf) -- the bits of the reprojection above --,
+ * optionally colours[k] = the `view` pixel (view_channels = 1 or 3 bytes, as the view has) and index[k] = y*W + x
+ * (int32).  counts[map] = the number of valid pixels, even when it exceeds `capacity`; entries k >= capacity are not
+ * written and nothing beyond min(count, capacity) is touched.  Lists of map k start k * *_map_stride BYTES after the first.
+ * The result is identical from run to run.  `points` and points_map_stride (and index) must be multiples of 4 bytes.
+ *
+ * W*H must be below 2^31 (ADF_ESIZE), for the image too.
+ *
+ * Conventions (as adf_filter_speckles_* and adf_census_transform_*): calls run on the current HIP device; `prm` is a HOST
+ * pointer in both forms -- Q travels in the kernel arguments, there is no upload.  Workspace: adf_reproject_workspace_bytes
+ * (4 bytes per map, read and written with ADF_MISSING_MIN only; the other modes use none and ignore the argument) /
+ * adf_point_cloud_workspace_bytes (the minimum slots and one uint32 per tile of 1024 pixels), 4-byte aligned device
+ * memory.  With a caller workspace the _device calls allocate nothing, never synchronise and may be captured into a
+ * hipGraph; with workspace = NULL they take scratch from the library's cache of device blocks (not capturable).  In the
+ * _device form `counts` is a device pointer too.  _host: host pointers (counts on the host); copies, runs, synchronises. */
+#define ADF_MISSING_NONE 0
+#define ADF_MISSING_MIN 1
+#define ADF_MISSING_VALUE 2
+typedef struct adf_reproject_params { double Q[16]; double disp_scale; int missing_mode; double missing_value; } adf_reproject_params;
+size_t adf_reproject_workspace_bytes(int n_maps);
+int adf_reproject_to_3d_device(int n_maps, const void* disp, int depth, ptrdiff_t stride, ptrdiff_t map_stride,
+                               int W, int H, const adf_reproject_params* prm, float* out, ptrdiff_t out_stride,
+                               ptrdiff_t out_map_stride, int out_channels, void* workspace, size_t workspace_bytes, void* stream);
+int adf_reproject_to_3d_host(int n_maps, const void* disp, int depth, ptrdiff_t stride, ptrdiff_t map_stride,
+                             int W, int H, const adf_reproject_params* prm, float* out, ptrdiff_t out_stride,
+                             ptrdiff_t out_map_stride, int out_channels);
+size_t adf_point_cloud_workspace_bytes(int n_maps, int W, int H);
+int adf_point_cloud_device(int n_maps, const void* disp, int depth, ptrdiff_t stride, ptrdiff_t map_stride, int W, int H,
+                           const adf_reproject_params* prm, const adf_rect* roi, double z_min, double z_max,
+                           const uint8_t* view, ptrdiff_t view_stride, ptrdiff_t view_map_stride, int view_channels,
+                           float* points, ptrdiff_t points_map_stride, uint8_t* colours, ptrdiff_t colours_map_stride,
+                           int32_t* index, ptrdiff_t index_map_stride, int capacity, uint32_t* counts,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int adf_point_cloud_host(int n_maps, const void* disp, int depth, ptrdiff_t stride, ptrdiff_t map_stride, int W, int H,
+                         const adf_reproject_params* prm, const adf_rect* roi, double z_min, double z_max,
+                         const uint8_t* view, ptrdiff_t view_stride, ptrdiff_t view_map_stride, int view_channels,
+                         float* points, ptrdiff_t points_map_stride, uint8_t* colours, ptrdiff_t colours_map_stride,
+                         int32_t* index, ptrdiff_t index_map_stride, int capacity, uint32_t* counts);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,6 +14,7 @@
 
 #include "adf_wls.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstring>
 #include <memory>
@@ -45,7 +46,7 @@ inline void check(int rc) { if (rc != ADF_OK) throw Exception(rc, adf_last_error
 using Mat = cv::Mat;
 using Rect = cv::Rect;
 template <class T> using Ptr = cv::Ptr<T>;
-enum { D8U = CV_8U, D16S = CV_16S, D32S = 4 /* CV_32S */, D32F = CV_32F };
+enum { D8U = CV_8U, D16S = CV_16S, D32S = 4 /* CV_32S */, D32F = CV_32F, D64F = 6 /* CV_64F */ };
 inline int mat_depth(const Mat& m) { return m.depth(); }
 inline int mat_channels(const Mat& m) { return m.channels(); }
 inline ptrdiff_t mat_step(const Mat& m) { return (ptrdiff_t)m.step; }
@@ -57,7 +58,7 @@ struct Rect {
     Rect(int x_, int y_, int w_, int h_) : x(x_), y(y_), width(w_), height(h_) {}
     int area() const { return width * height; }
 };
-enum { D8U = 0, D16S = 3, D32S = 4, D32F = 5 }; // cv depth codes
+enum { D8U = 0, D16S = 3, D32S = 4, D32F = 5, D64F = 6 }; // cv depth codes
 // Minimal dense image: shared buffer, header copies share data (like cv::Mat).
 struct Mat {
     int rows = 0, cols = 0, depth_ = D8U, cn = 1;
@@ -66,7 +67,7 @@ struct Mat {
     std::shared_ptr<std::vector<unsigned char>> buf;
     Mat() {}
     Mat(int r, int c, int depth, int channels = 1) { create(r, c, depth, channels); }
-    static size_t esz(int depth) { return depth == D8U ? 1 : depth == D16S ? 2 : 4; }
+    static size_t esz(int depth) { return depth == D8U ? 1 : depth == D16S ? 2 : depth == D64F ? 8 : 4; }
     void create(int r, int c, int depth, int channels = 1)
     {
         if (r == rows && c == cols && depth == depth_ && channels == cn && data) return;
@@ -169,6 +170,84 @@ inline void cvtColor(const Mat& src, Mat& dst, int code, int dstCn = 0)
     check(adf_prepare_views_host(1, src.data, mat_step(src), 0, src.cols, src.rows, 3, out.data, mat_step(out), 0,
                                  src.cols, src.rows, 1));
     dst = out;
+}
+
+// cv::reprojectImageTo3D(disparity, _3dImage, Q, handleMissingValues, ddepth) of calib3d (outside the reference tree;
+// parity unpinned) and the point list, on host Mats through the library's host entries: definition, missing values and
+// what "valid" means are adf_reproject_* / adf_point_cloud_* in adf_wls.h.  disparity: CV_16SC1 or CV_32FC1; Q: 4x4, CV_32F
+// or CV_64F; ddepth: -1 or CV_32F.  Extensions after cv's arguments: dispScale multiplies the raw value first (1/16 for the
+// filters' fixed-point units), missingValue names the missing value instead of the map's minimum (-16 for filterToFloat
+// output), zOnly gives the CV_32FC1 Z plane alone.
+inline adf_reproject_params reproject_params(const char* who, const Mat& Q, bool handleMissingValues, double dispScale,
+                                             const double* missingValue)
+{
+    if (Q.empty() || Q.rows != 4 || Q.cols != 4 || mat_channels(Q) != 1 || (mat_depth(Q) != D32F && mat_depth(Q) != D64F))
+        throw Exception(ADF_EBADARG, std::string(who) + ": Q must be a 4x4 CV_32F or CV_64F matrix");
+    adf_reproject_params p;
+    for (int r = 0; r < 4; r++) {
+        const unsigned char* row = Q.data + (size_t)mat_step(Q) * r;
+        for (int c = 0; c < 4; c++)
+            p.Q[4 * r + c] = mat_depth(Q) == D64F ? reinterpret_cast<const double*>(row)[c] : (double)reinterpret_cast<const float*>(row)[c];
+    }
+    p.disp_scale = dispScale;
+    p.missing_mode = missingValue ? ADF_MISSING_VALUE : handleMissingValues ? ADF_MISSING_MIN : ADF_MISSING_NONE;
+    p.missing_value = missingValue ? *missingValue : 0.0;
+    return p;
+}
+
+inline int reproject_depth(const char* who, const Mat& disparity)
+{
+    if (disparity.empty() || mat_channels(disparity) != 1 || (mat_depth(disparity) != D16S && mat_depth(disparity) != D32F))
+        throw Exception(ADF_EBADARG, std::string(who) + ": disparity must be a non-empty CV_16SC1 or CV_32FC1 image");
+    return mat_depth(disparity) == D16S ? ADF_16S : ADF_32F;
+}
+
+inline void reprojectImageTo3D(const Mat& disparity, Mat& _3dImage, const Mat& Q, bool handleMissingValues = false, int ddepth = -1,
+                               double dispScale = 1.0, const double* missingValue = nullptr, bool zOnly = false)
+{
+    const int depth = reproject_depth("reprojectImageTo3D", disparity);
+    if (ddepth != -1 && ddepth != D32F)
+        throw Exception(ADF_EBADARG, "reprojectImageTo3D: ddepth must be -1 or CV_32F (CV_16SC3 and CV_32SC3 are not built)");
+    const adf_reproject_params p = reproject_params("reprojectImageTo3D", Q, handleMissingValues, dispScale, missingValue);
+    Mat out;
+    mat_create(out, disparity.rows, disparity.cols, D32F, zOnly ? 1 : 3);
+    check(adf_reproject_to_3d_host(1, disparity.data, depth, mat_step(disparity), 0, disparity.cols, disparity.rows, &p,
+                                   reinterpret_cast<float*>(out.data), mat_step(out), 0, zOnly ? 1 : 3));
+    _3dImage = out;
+}
+
+// The valid points of the map in raster order, three floats each, into `points`; optionally their `view` pixels
+// (CV_8UC1 / CV_8UC3, the map's size) into `colours` and y * cols + x into `index`.  ROI with zero area = the whole map;
+// zMin / zMax = -+infinity switch the range off.  Returns the number of points.
+inline size_t pointCloud(const Mat& disparity, const Mat& Q, std::vector<float>& points, std::vector<uint8_t>* colours = nullptr,
+                         const Mat& view = Mat(), Rect ROI = Rect(), double zMin = -HUGE_VAL, double zMax = HUGE_VAL,
+                         bool handleMissingValues = false, double dispScale = 1.0, const double* missingValue = nullptr,
+                         std::vector<int32_t>* index = nullptr)
+{
+    const int depth = reproject_depth("pointCloud", disparity);
+    const adf_reproject_params p = reproject_params("pointCloud", Q, handleMissingValues, dispScale, missingValue);
+    int vch = 0;
+    if (colours) {
+        if (view.empty() || mat_depth(view) != D8U || view.rows != disparity.rows || view.cols != disparity.cols)
+            throw Exception(ADF_ESIZE, "pointCloud: colours need a CV_8U view of the disparity map's size");
+        vch = mat_channels(view);
+    }
+    adf_rect roi{ROI.x, ROI.y, ROI.width, ROI.height};
+    const bool whole = ROI.area() == 0;
+    const size_t area = whole ? (size_t)disparity.rows * (size_t)disparity.cols : (size_t)ROI.width * (size_t)ROI.height;
+    if (area > 2147483647u) throw Exception(ADF_ESIZE, "pointCloud: W*H must be below 2^31");
+    points.resize(std::max<size_t>(area, 1) * 3);
+    if (colours) colours->resize(std::max<size_t>(area, 1) * (size_t)std::max(vch, 1));
+    if (index) index->resize(std::max<size_t>(area, 1));
+    uint32_t count = 0;
+    check(adf_point_cloud_host(1, disparity.data, depth, mat_step(disparity), 0, disparity.cols, disparity.rows, &p,
+                               whole ? nullptr : &roi, zMin, zMax, colours ? view.data : nullptr, colours ? mat_step(view) : 0, 0, vch,
+                               points.data(), 0, colours ? colours->data() : nullptr, 0, index ? index->data() : nullptr, 0,
+                               (int)area, &count));
+    points.resize((size_t)count * 3);
+    if (colours) colours->resize((size_t)count * (size_t)vch);
+    if (index) index->resize(count);
+    return count;
 }
 
 namespace ximgproc {
