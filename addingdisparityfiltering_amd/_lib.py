@@ -16,6 +16,7 @@ PATH_CONF_BAND, PATH_FUSED_FIRST_PASS, PATH_MERGED_PREP, PATH_SCALED_FUSED, PATH
 PATH_ROW_WEIGHTS_GUIDE = 32    # adf_wls_get_last_solver_path bit
 DEPTH_8U, DEPTH_16S, DEPTH_32F = 0, 3, 5
 SGBM_COST_BT, SGBM_COST_CENSUS_DENSE, SGBM_COST_CENSUS_SPARSE = 0, 1, 2    # adf_sgbm_set_cost (include/adf_wls.h)
+BM_COST_SAD, BM_COST_CENSUS_DENSE, BM_COST_CENSUS_SPARSE = 0, 1, 2    # adf_bm_set_cost (the census values equal SGBM_COST_CENSUS_*)
 MISSING_NONE, MISSING_MIN, MISSING_VALUE = 0, 1, 2    # adf_reproject_params.missing_mode (include/adf_wls.h)
 
 
@@ -107,6 +108,8 @@ SYMBOLS = [
     ("adf_bm_set_params", _i, [_vp, _i, _i, _i, _i, _i, _i]),
     ("adf_bm_get_device", _i, [_vp, C.POINTER(_i)]),
     ("adf_bm_get_params", _i, [_vp] + [C.POINTER(_i)] * 6),
+    ("adf_bm_set_cost", _i, [_vp, _i, _i]),
+    ("adf_bm_get_cost", _i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
     ("adf_bm_compute_device", _i, [_vp, _i, _vp, _pd, _pd, _vp, _pd, _pd, _i, _i, _vp, _pd, _pd, _vp]),
     ("adf_bm_compute_both_device", _i, [_vp, _i, _vp, _pd, _pd, _vp, _pd, _pd, _i, _i, _vp, _pd, _pd, _vp, _pd, _pd, _vp]),
     ("adf_bm_compute_host", _i, [_vp, _i, _vp, _pd, _pd, _vp, _pd, _pd, _i, _i, _vp, _pd, _pd]),

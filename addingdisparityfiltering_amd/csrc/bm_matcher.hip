@@ -26,7 +26,14 @@
 // is decided once at the end.  Nothing but the int16 result is written.
 // The kernel is bound by integer VALU issue (about 11 instructions per pixel and disparity; EXPERIMENTS.md section 10), not
 // by HBM: the views are read through L1/L2 once per disparity, HBM sees them once.
-#include "adf_host.h"
+//
+// Census cost (adf_bm_set_cost).  The pixel cost is a policy of the match kernel.  With
+// ADF_BM_COST_CENSUS_* the prefiltered views are replaced by the census descriptors of the raw views, split into
+// P = ceil(bits / 8) byte planes in the same row-group interleaved layout (plane p holds bits 8p .. 8p+7, no +1 bias),
+// and the vertical sum of four rows of a column is popcount((L ^ R) & window_mask), added up over the groups and over
+// the planes.  A one-plane descriptor keeps its left columns in registers as SAD does; wider ones reload them per plane
+// (an L1/L2 hit).  Prefix, scan, LDS exchange, winner tracking and epilogue do not know which cost they serve.
+#include "census.h"
 
 #include <new>
 
@@ -66,9 +73,69 @@ __global__ void __launch_bounds__(256) bm_prefilter_kernel(PrefilterArgs a)
     a.dst[(size_t)blockIdx.z * a.dst_pair + (size_t)gp * a.Wp + x] = out;
 }
 
+struct CensusPackArgs {
+    const uint8_t* src[2]; ptrdiff_t stride[2], pair_stride[2];   // left, right
+    uint32_t* dst; size_t dst_view, dst_pair, dst_plane;          // dwords between the two views, the pairs, the planes
+    int W, Wp, H, HGP;
+};
+
+// The census descriptors of both views (blockIdx.z = 2 * pair + view) as byte planes in the matcher's layout, straight
+// from the raw views: the 64 x 16 tile of four row groups plus its halo goes through LDS with clamped coordinates, as in
+// census_kernel (census_kernels.hip), whose comparison loop this repeats -- the bits are adf_census_transform's -- and a
+// lane forms the descriptors of the four rows of its group and stores one dword per plane.  Going through
+// adf::census_run instead would write 8 bytes per pixel and read them back to keep 1..6.  The
+// padding groups hold the descriptors of the edge-replicated image; no window of a matched row reaches them.
+template <bool SPARSE, int K>
+__global__ void __launch_bounds__(256) bm_census_pack_kernel(CensusPackArgs a)
+{
+    constexpr int N2 = K / 2, STEP = SPARSE ? 2 : 1;
+    constexpr int PER_AXIS = 2 * N2 / STEP + 1, NBITS = PER_AXIS * PER_AXIS - (N2 % STEP == 0 ? 1 : 0);
+    constexpr int NP = (NBITS + 7) / 8;
+    constexpr int LW = 64 + 2 * N2, LH = 16 + 2 * N2;
+    __shared__ uint8_t tile[LH][LW];
+    const int view = blockIdx.z & 1;
+    const unsigned pz = blockIdx.z >> 1;
+    const int x0 = blockIdx.x * 64, gp0 = blockIdx.y * 4, y0 = 4 * (gp0 - PG);
+    const uint8_t* src = a.src[view] + (ptrdiff_t)pz * a.pair_stride[view];
+    for (int i = threadIdx.x; i < LH * LW; i += 256) {
+        const int r = i / LW, c = i - r * LW;
+        const int y = min(max(y0 - N2 + r, 0), a.H - 1), x = min(max(x0 - N2 + c, 0), a.W - 1);
+        tile[r][c] = src[(ptrdiff_t)y * a.stride[view] + x];
+    }
+    __syncthreads();
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int x = x0 + lane, gp = gp0 + wv;
+    if (x >= a.W || gp >= a.HGP) return;
+    uint32_t out[NP];
+#pragma unroll
+    for (int p = 0; p < NP; p++) out[p] = 0;
+#pragma unroll
+    for (int b = 0; b < 4; b++) {
+        const int r = 4 * wv + b;
+        const uint32_t centre = tile[r + N2][lane + N2];
+        uint32_t hi = 0, lo = 0;
+        int bit = NBITS - 1;                                   // (a compile-time constant at every use: both loops unroll)
+#pragma unroll
+        for (int dy = -N2; dy <= N2; dy += STEP)
+#pragma unroll
+            for (int dx = -N2; dx <= N2; dx += STEP) {
+                if (dy == 0 && dx == 0) continue;
+                const uint32_t v = tile[r + N2 + dy][lane + N2 + dx] > centre ? 1u : 0u;
+                if (bit >= 32) hi |= v << (bit - 32);
+                else lo |= v << bit;
+                bit--;
+            }
+#pragma unroll
+        for (int p = 0; p < NP; p++) out[p] |= (((p < 4 ? lo >> (8 * p) : hi >> (8 * (p - 4)))) & 0xFFu) << (8 * b);
+    }
+    uint32_t* dst = a.dst + (size_t)view * a.dst_view + (size_t)pz * a.dst_pair + (size_t)gp * a.Wp + x;
+#pragma unroll
+    for (int p = 0; p < NP; p++) dst[(size_t)p * a.dst_plane] = out[p];
+}
+
 // One view's search: its prefiltered "left" (reference) and "right" (searched) images, output and disparity range.
 struct ViewArgs {
-    const uint32_t* Lt; const uint32_t* Rt;                  // prefiltered views, t_pair dwords per image
+    const uint32_t* Lt; const uint32_t* Rt;                  // prefiltered views (census: descriptor planes), t_pair dwords per image
     int16_t* disp; ptrdiff_t dstride, dpair;                 // bytes
     int mindisp;
     int xs, xe;            // matched columns [xs, xe)
@@ -83,6 +150,25 @@ struct MatchArgs {
     size_t t_pair;
     int W, Wp, H, HG;                                        // Wp: dwords per prefiltered row (W + XPAD, multiple of 4)
     int ndisp, cap;
+    int planes; size_t plane;                                // census: byte planes of a descriptor, dwords per plane
+};
+
+// The pixel cost of the match kernel: what one dword of four rows of the reference column (L) and of the searched
+// column (R) adds to a vertical window sum -- all four rows (`full`) or the rows under a byte mask (`part`).
+struct CostSad {
+    static constexpr bool CENSUS = false, MULTI = false;
+    static __device__ __forceinline__ uint32_t full(uint32_t R, uint32_t L, uint32_t acc) { return __builtin_amdgcn_sad_u8(R, L, acc); }
+    // rows with a zero reference byte are skipped (the prefiltered views are stored +1)
+    static __device__ __forceinline__ uint32_t part(uint32_t R, uint32_t L, uint32_t m, uint32_t acc) { return __builtin_amdgcn_msad_u8(R, L & m, acc); }
+};
+// Hamming distance of four 8-bit descriptor slices: one v_xor (fused with the mask), one v_bcnt_u32_b32 that accumulates.
+// MULTI: a descriptor of several byte planes, their number read at run time; a one-plane descriptor (dense 3, sparse 5)
+// has its own instantiation, because the plane loop costs it a third of its time.
+template <bool MULTI_>
+struct CostCensus {
+    static constexpr bool CENSUS = true, MULTI = MULTI_;
+    static __device__ __forceinline__ uint32_t full(uint32_t R, uint32_t L, uint32_t acc) { return (uint32_t)__builtin_popcount(R ^ L) + acc; }
+    static __device__ __forceinline__ uint32_t part(uint32_t R, uint32_t L, uint32_t m, uint32_t acc) { return (uint32_t)__builtin_popcount((R ^ L) & m) + acc; }
 };
 
 // rows of group gi (relative to the output group) that lie in the window of output row r
@@ -120,15 +206,17 @@ __device__ __forceinline__ uint32_t wave_scan(uint32_t v)
 
 // adjacent columns per lane: four on the filter's path; two with the uniqueness test, whose four extra state
 // registers per pixel would otherwise push the kernel past 256 registers (measured per 4K pair: 3.3 ms with four
-// columns, 1.98 ms with two)
-constexpr int cpl_of(bool uniq) { return uniq ? 2 : 4; }
+// columns, 1.98 ms with two); two also with a census cost of several planes at window half-sizes 9 and 10, whose
+// accumulators across the planes are live through the vertical sums: with four columns those two instantiations need
+// 298 registers
+constexpr int cpl_of(bool uniq, bool multi, int w2) { return (uniq || (multi && w2 >= 9)) ? 2 : 4; }
 constexpr int XPAD = 64 * 4 + 4;       // columns of padding right of a prefiltered row (lanes past the image read it)
 constexpr int floordiv(int a, int b) { return (a >= 0) ? a / b : -((-a + b - 1) / b); }
 
-template <int W2, bool UNIQ>
+template <int W2, bool UNIQ, class COST>
 __global__ void __launch_bounds__(256) bm_match_kernel(MatchArgs a)
 {
-    constexpr int CPL = cpl_of(UNIQ);
+    constexpr int CPL = cpl_of(UNIQ, COST::MULTI, W2);
     constexpr int TILE = 64 * CPL;          // columns per wave, window halo included
     constexpr int TOUT = TILE - 2 * W2;
     constexpr int GB = (W2 + 3) / 4;        // groups above the output group that the windows reach
@@ -163,12 +251,12 @@ __global__ void __launch_bounds__(256) bm_match_kernel(MatchArgs a)
 #pragma unroll
     for (int gi = 0; gi < NG; gi++) load4(Lt + (size_t)gi * Wp, cl, Ld[gi]);
 
-    // four vertical window sums (one per output row of the group) of |L - R| down column j of this lane
+    // four vertical window sums (one per output row of the group) of the pixel cost down column j of this lane
     auto vertical = [&](const uint32_t (&Rd)[NG][CPL], int j, uint32_t (&V)[4]) {
         uint32_t F = 0;
 #pragma unroll
         for (int gi = 0; gi < NG; gi++)
-            if (group_common(W2, GB, gi)) F = __builtin_amdgcn_sad_u8(Rd[gi][j], Ld[gi][j], F);
+            if (group_common(W2, GB, gi)) F = COST::full(Rd[gi][j], Ld[gi][j], F);
 #pragma unroll
         for (int r = 0; r < 4; r++) {
             uint32_t acc = F;
@@ -176,8 +264,8 @@ __global__ void __launch_bounds__(256) bm_match_kernel(MatchArgs a)
             for (int gi = 0; gi < NG; gi++) {
                 const uint32_t m = window_mask(W2, GB, gi, r);
                 if (group_common(W2, GB, gi) || m == 0) continue;
-                if (m == 0xFFFFFFFFu) acc = __builtin_amdgcn_sad_u8(Rd[gi][j], Ld[gi][j], acc);
-                else acc = __builtin_amdgcn_msad_u8(Rd[gi][j], Ld[gi][j] & m, acc);   // rows with a zero reference byte are skipped
+                if (m == 0xFFFFFFFFu) acc = COST::full(Rd[gi][j], Ld[gi][j], acc);
+                else acc = COST::part(Rd[gi][j], Ld[gi][j], m, acc);
             }
             V[r] = acc;
         }
@@ -222,13 +310,14 @@ __global__ void __launch_bounds__(256) bm_match_kernel(MatchArgs a)
         }
     };
 
-    // texture of the window: sum of |L - cap| (only needed with a texture threshold)
+    // texture of the window: sum of |L - cap| (only needed with a texture threshold; a census cost has no prefiltered
+    // image whose texture could be summed, and the host passes it a threshold of 0)
     uint32_t tex[4][CPL];
 #pragma unroll
     for (int r = 0; r < 4; r++)
 #pragma unroll
         for (int j = 0; j < CPL; j++) tex[r][j] = INF;
-    if (texthr > 0) {
+    if (!COST::CENSUS && texthr > 0) {
         uint32_t Rd[NG][CPL], V[CPL][4];
         const uint32_t ft = (uint32_t)(a.cap + 1) * 0x01010101u;
 #pragma unroll
@@ -288,34 +377,47 @@ __global__ void __launch_bounds__(256) bm_match_kernel(MatchArgs a)
 
     const int xbase = c - mindisp;                           // R column of disparity index 0; xbase - k >= 0 for matched columns
     auto rcol = [&](int k) -> unsigned { return (unsigned)min(max(xbase - k, 0), Wp - CPL); };
+    // The columns of disparities k, k+1 of plane p (SAD: the one prefiltered image); a descriptor of several planes also
+    // reloads the lane's own columns of that plane -- an L1/L2 hit -- since all planes of L do not fit the registers.
+    const int planes = COST::MULTI ? a.planes : 1;
     uint32_t R0[NG][CPL], R1[NG][CPL];
-    {
-        const unsigned x0 = rcol(0), x1 = rcol(1);
+    auto fetch = [&](int k, int p) {
+        const size_t po = COST::MULTI ? (size_t)p * a.plane : 0;
+        const unsigned x0 = rcol(k), x1 = rcol(k + 1);
 #pragma unroll
-        for (int gi = 0; gi < NG; gi++) { load4(Rt + (size_t)gi * (unsigned)Wp, x0, R0[gi]); load4(Rt + (size_t)gi * (unsigned)Wp, x1, R1[gi]); }
-    }
-    for (int k = 0; k < a.ndisp; k += 2) {
-        uint32_t P[4][CPL];
+        for (int gi = 0; gi < NG; gi++) { load4(Rt + po + (size_t)gi * (unsigned)Wp, x0, R0[gi]); load4(Rt + po + (size_t)gi * (unsigned)Wp, x1, R1[gi]); }
+        if (planes > 1) {
+#pragma unroll
+            for (int gi = 0; gi < NG; gi++) load4(Lt + po + (size_t)gi * (unsigned)Wp, cl, Ld[gi]);
+        }
+    };
+    fetch(0, 0);
+    // One loop over (pair of disparities, plane): a plane adds its vertical sums to P, the last plane of a pair reduces it.
+    uint32_t P[4][CPL];
+#pragma unroll
+    for (int r = 0; r < 4; r++)
+#pragma unroll
+        for (int j = 0; j < CPL; j++) P[r][j] = 0;
+    for (int k = 0, p = 0; k < a.ndisp;) {
 #pragma unroll
         for (int j = 0; j < CPL; j++) {
             uint32_t V0[4], V1[4];
             vertical(R0, j, V0);
             vertical(R1, j, V1);
 #pragma unroll
-            for (int r = 0; r < 4; r++) P[r][j] = V0[r] + (V1[r] << 16);   // exact: both halves stay below 2^16
+            for (int r = 0; r < 4; r++) P[r][j] += V0[r] + (V1[r] << 16);   // exact: both halves stay below 2^16
         }
-        // the next two disparities' columns are fetched while this pair is reduced (the last fetch is unused)
-        {
-            const unsigned x0 = rcol(k + 2), x1 = rcol(k + 3);
-#pragma unroll
-            for (int gi = 0; gi < NG; gi++) { load4(Rt + (size_t)gi * (unsigned)Wp, x0, R0[gi]); load4(Rt + (size_t)gi * (unsigned)Wp, x1, R1[gi]); }
-        }
+        // the next plane's, or the next two disparities', columns are fetched while this pair is reduced (the last fetch is unused)
+        const bool last = p + 1 == planes;
+        fetch(last ? k + 2 : k, last ? 0 : p + 1);
+        if (!last) { p++; continue; }
 #pragma unroll
         for (int r = 0; r < 4; r++) {
             horizontal(P[r], r);
 #pragma unroll
-            for (int j = 0; j < CPL; j++) track_pair(r, j, (uint32_t)k, P[r][j]);
+            for (int j = 0; j < CPL; j++) { track_pair(r, j, (uint32_t)k, P[r][j]); P[r][j] = 0; }
         }
+        k += 2; p = 0;
     }
 
     const int16_t filtered = (int16_t)((mindisp - 1) * 16);
@@ -368,15 +470,15 @@ __global__ void __launch_bounds__(256) bm_border_kernel(MatchArgs a)
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) row[i < nleft ? i : xr + (i - nleft)] = filtered;
 }
 
-template <bool UNIQ>
+template <bool UNIQ, class COST>
 hipError_t launch_match(const MatchArgs& a, int w2, dim3 block, int n, hipStream_t st)
 {
-    const int tout = 64 * cpl_of(UNIQ) - 2 * w2;
+    const int tout = 64 * cpl_of(UNIQ, COST::MULTI, w2) - 2 * w2;
     int cols = a.v[0].xe - a.v[0].xs;
     if (a.nviews == 2 && a.v[1].xe - a.v[1].xs > cols) cols = a.v[1].xe - a.v[1].xs;
     dim3 grid((cols + tout - 1) / tout, (a.HG + 3) / 4, n * a.nviews);
     switch (w2) {
-#define ADF_BM_CASE(K) case K: hipLaunchKernelGGL((bm_match_kernel<K, UNIQ>), grid, block, 0, st, a); break;
+#define ADF_BM_CASE(K) case K: hipLaunchKernelGGL((bm_match_kernel<K, UNIQ, COST>), grid, block, 0, st, a); break;
     ADF_BM_CASE(2) ADF_BM_CASE(3) ADF_BM_CASE(4) ADF_BM_CASE(5) ADF_BM_CASE(6)
     ADF_BM_CASE(7) ADF_BM_CASE(8) ADF_BM_CASE(9) ADF_BM_CASE(10)
 #undef ADF_BM_CASE
@@ -394,7 +496,8 @@ struct adf_bm {
     int device = 0;
     int min_disp = 0, num_disp = 0, block = 21;
     int cap = 31, texthr = 10, uniq = 15;       // cv::StereoBM's defaults
-    DevBuf views;   // prefiltered left + right views of the batch
+    int cost = ADF_BM_COST_SAD, census_size = 7;   // adf_bm_set_cost (census_size: read by the census costs only)
+    DevBuf views;   // prefiltered left + right views of the batch, or their census descriptor planes
     DevBuf stage;   // host-pointer entry: device copies of the I/O
 };
 
@@ -426,6 +529,25 @@ extern "C" int adf_bm_set_params(adf_bm_t* h, int min_disparity, int num_dispari
     if (!h) return fail(ADF_EBADARG, "handle is NULL");
     h->min_disp = min_disparity; h->num_disp = num_disparities; h->block = block_size;
     h->cap = prefilter_cap; h->texthr = texture_threshold; h->uniq = uniqueness_ratio;
+    return ADF_OK;
+}
+
+extern "C" int adf_bm_set_cost(adf_bm_t* h, int cost_type, int census_size)
+{
+    if (!h) return fail(ADF_EBADARG, "handle is NULL");
+    if (cost_type != ADF_BM_COST_SAD) {
+        if (int rc = census_check(cost_type, census_size)) return rc;
+        h->census_size = census_size;
+    }
+    h->cost = cost_type;
+    return ADF_OK;
+}
+
+extern "C" int adf_bm_get_cost(const adf_bm_t* h, int* cost_type, int* census_size)
+{
+    if (!h) return fail(ADF_EBADARG, "handle is NULL");
+    if (cost_type) *cost_type = h->cost;
+    if (census_size) *census_size = h->census_size;
     return ADF_OK;
 }
 
@@ -467,7 +589,14 @@ static int bm_check(const adf_bm* h, int n, const void* l, const void* r, const 
     return ADF_OK;
 }
 
-// Shared body: prefilter both images once, then one launch for the left view alone (disp_right == NULL) or for
+template <bool SPARSE, int K>
+static void census_pack_launch(const CensusPackArgs& p, int n_pairs, hipStream_t st)
+{
+    hipLaunchKernelGGL((bm_census_pack_kernel<SPARSE, K>), dim3((p.W + 63) / 64, (p.HGP + 3) / 4, 2 * n_pairs), dim3(256), 0, st, p);
+}
+
+// Shared body: prefilter both images once (census: form their descriptor planes), then one launch for the left view
+// alone (disp_right == NULL) or for
 // both views.
 static int bm_compute_impl(adf_bm_t* h, int n_pairs,
                            const uint8_t* left, ptrdiff_t left_stride, ptrdiff_t left_pair_stride,
@@ -491,19 +620,40 @@ static int bm_compute_impl(adf_bm_t* h, int n_pairs,
     DeviceScope ds(h->device);
     const int HG = (H + 3) / 4, HGP = HG + 2 * PG;
     const int Wp = (W + XPAD + 3) / 4 * 4;                     // padded row: lanes past the image read (and discard) it
-    const size_t view = (size_t)HGP * Wp;                      // dwords per prefiltered view
-    rc = h->views.reserve(2 * view * (size_t)n_pairs * sizeof(uint32_t), st, FILL_NONE);
+    const size_t view = (size_t)HGP * Wp;                      // dwords per prefiltered view / per descriptor plane
+    const bool census = h->cost != ADF_BM_COST_SAD;
+    const int planes = census ? (census_bits(h->cost, h->census_size) + 7) / 8 : 1;
+    const size_t image = view * (size_t)planes;                // dwords per image: sized from the handle's cost of THIS call
+    rc = h->views.reserve(2 * image * (size_t)n_pairs * sizeof(uint32_t), st, FILL_NONE);
     if (rc) return rc;
     uint32_t* Lt = (uint32_t*)h->views.p;
-    uint32_t* Rt = Lt + view * (size_t)n_pairs;
+    uint32_t* Rt = Lt + image * (size_t)n_pairs;
 
-    PrefilterArgs p;
-    p.W = W; p.Wp = Wp; p.H = H; p.HGP = HGP; p.cap = h->cap; p.dst_pair = view;
-    dim3 pgrid((W + 255) / 256, HGP, n_pairs);
-    p.src = left; p.stride = left_stride; p.pair_stride = left_pair_stride; p.dst = Lt;
-    hipLaunchKernelGGL(bm_prefilter_kernel, pgrid, dim3(256), 0, st, p);
-    p.src = right; p.stride = right_stride; p.pair_stride = right_pair_stride; p.dst = Rt;
-    hipLaunchKernelGGL(bm_prefilter_kernel, pgrid, dim3(256), 0, st, p);
+    if (census) {
+        CensusPackArgs p;
+        p.src[0] = left; p.stride[0] = left_stride; p.pair_stride[0] = left_pair_stride;
+        p.src[1] = right; p.stride[1] = right_stride; p.pair_stride[1] = right_pair_stride;
+        p.dst = Lt; p.dst_view = image * (size_t)n_pairs; p.dst_pair = image; p.dst_plane = view;
+        p.W = W; p.Wp = Wp; p.H = H; p.HGP = HGP;
+        switch (h->cost == ADF_BM_COST_CENSUS_SPARSE ? -h->census_size : h->census_size) {
+        case 3: census_pack_launch<false, 3>(p, n_pairs, st); break;
+        case 5: census_pack_launch<false, 5>(p, n_pairs, st); break;
+        case 7: census_pack_launch<false, 7>(p, n_pairs, st); break;
+        case -5: census_pack_launch<true, 5>(p, n_pairs, st); break;
+        case -7: census_pack_launch<true, 7>(p, n_pairs, st); break;
+        case -9: census_pack_launch<true, 9>(p, n_pairs, st); break;
+        case -11: census_pack_launch<true, 11>(p, n_pairs, st); break;
+        default: return fail(ADF_EBADARG, "census size %d is not supported", h->census_size);
+        }
+    } else {
+        PrefilterArgs p;
+        p.W = W; p.Wp = Wp; p.H = H; p.HGP = HGP; p.cap = h->cap; p.dst_pair = view;
+        dim3 pgrid((W + 255) / 256, HGP, n_pairs);
+        p.src = left; p.stride = left_stride; p.pair_stride = left_pair_stride; p.dst = Lt;
+        hipLaunchKernelGGL(bm_prefilter_kernel, pgrid, dim3(256), 0, st, p);
+        p.src = right; p.stride = right_stride; p.pair_stride = right_pair_stride; p.dst = Rt;
+        hipLaunchKernelGGL(bm_prefilter_kernel, pgrid, dim3(256), 0, st, p);
+    }
 
     const int w2 = h->block / 2;
     auto view_args = [&](const uint32_t* ref, const uint32_t* srch, int16_t* d, ptrdiff_t ds_, ptrdiff_t dp, int md, int texthr, int uniq) {
@@ -517,16 +667,21 @@ static int bm_compute_impl(adf_bm_t* h, int n_pairs,
         return v;
     };
     MatchArgs a;
-    a.nviews = nviews; a.t_pair = view;
+    a.nviews = nviews; a.t_pair = image; a.planes = planes; a.plane = view;
     a.W = W; a.Wp = Wp; a.H = H; a.HG = HG; a.ndisp = h->num_disp; a.cap = h->cap;
-    a.v[0] = view_args(Lt, Rt, disp_left, dl_stride, dl_pair_stride, h->min_disp, h->texthr, h->uniq);
+    // (a census cost has no prefiltered image to sum a texture of: textureThreshold is validated and not used)
+    a.v[0] = view_args(Lt, Rt, disp_left, dl_stride, dl_pair_stride, h->min_disp, census ? 0 : h->texthr, h->uniq);
     // the right-view matcher of createRightMatcher (disparity_filters.cpp:421-431): views swapped,
     // minDisparity = -(min_disp + num_disp) + 1, texture and uniqueness tests off
     a.v[1] = disp_right ? view_args(Rt, Lt, disp_right, dr_stride, dr_pair_stride, -(h->min_disp + h->num_disp) + 1, 0, 0) : a.v[0];
     hipLaunchKernelGGL(bm_border_kernel, dim3(4, H, n_pairs * nviews), dim3(256), 0, st, a);
     if (a.v[0].xe > a.v[0].xs || (nviews == 2 && a.v[1].xe > a.v[1].xs)) {
-        hipError_t e = h->uniq > 0 ? launch_match<true>(a, w2, dim3(256), n_pairs, st)
-                                   : launch_match<false>(a, w2, dim3(256), n_pairs, st);
+        hipError_t e = planes > 1 ? (h->uniq > 0 ? launch_match<true, CostCensus<true>>(a, w2, dim3(256), n_pairs, st)
+                                                 : launch_match<false, CostCensus<true>>(a, w2, dim3(256), n_pairs, st))
+                     : census ? (h->uniq > 0 ? launch_match<true, CostCensus<false>>(a, w2, dim3(256), n_pairs, st)
+                                             : launch_match<false, CostCensus<false>>(a, w2, dim3(256), n_pairs, st))
+                              : (h->uniq > 0 ? launch_match<true, CostSad>(a, w2, dim3(256), n_pairs, st)
+                                             : launch_match<false, CostSad>(a, w2, dim3(256), n_pairs, st));
         if (e != hipSuccess) return fail(ADF_EHIP, "%s", hipGetErrorString(e));
     }
     hipError_t e = hipGetLastError();

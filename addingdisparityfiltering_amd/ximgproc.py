@@ -13,6 +13,7 @@ edge_filter.hpp (EF.hpp), over the C-ABI in include/adf_wls.h:
     fastGlobalSmootherFilter(...)                   EF.hpp:413
     filterSpeckles(img, newVal, maxSpeckleSize, maxDiff, buf)   calib3d (outside the reference tree)
     censusTransform(image, kernelSize, type)        modules/stereo descriptor.hpp:428 / descriptor.cpp:77-98
+    StereoBM.setCostType(BM_COST_CENSUS_*) / setCensusSize(k)   the cost of modules/stereo stereo_binary_bm.cpp:367-408 (extension)
     resize(src, dsize, fx, fy) at half size, cvtColor(src, COLOR_BGR2GRAY)   imgproc (outside the reference tree)
     reprojectImageTo3D(disparity, Q, handleMissingValues, ddepth), pointCloud(...)   calib3d (outside the reference tree)
 
@@ -28,6 +29,7 @@ import numpy as np
 
 from . import _lib
 from ._lib import SGBM_COST_BT, SGBM_COST_CENSUS_DENSE, SGBM_COST_CENSUS_SPARSE  # noqa: F401  (re-exported)
+from ._lib import BM_COST_SAD, BM_COST_CENSUS_DENSE, BM_COST_CENSUS_SPARSE  # noqa: F401  (re-exported)
 from ._lib import AdfError, PATH_CONF_BAND, PATH_FUSED_FIRST_PASS, PATH_MERGED_PREP, PATH_ROW_WEIGHTS_GUIDE, PATH_SCALED_FUSED, PATH_SCALED_HALF, Rect, SOLVER_EXACT, SOLVER_WAVE  # noqa: F401  (re-exported)
 
 try:  # torch is optional plumbing: device memory and streams only
@@ -402,15 +404,23 @@ class StereoMatcher(_Handle):
         return disparity
 
 
-@_accessors("textureThreshold", "preFilterCap")
+@_accessors("textureThreshold", "preFilterCap", "costType", "censusSize")
 class StereoBM(StereoMatcher):
     """cv::StereoBM's accessors plus compute() on the device (csrc/bm_matcher.hip): CV_8UC1 views.  The left-right check
-    and the speckle filter of cv::StereoBM are not implemented: the filter factory switches both off (DF.cpp:389-390)."""
+    and the speckle filter of cv::StereoBM are not implemented: the filter factory switches both off (DF.cpp:389-390).
+
+    Extension: setCostType(BM_COST_CENSUS_DENSE / _SPARSE) + setCensusSize(k) match census descriptors with a Hamming
+    distance, the cost of the reference's own cv::stereo::StereoBinaryBM (include/adf_wls.h: adf_bm_set_cost), which
+    ignores gain and exposure differences between the cameras.  preFilterCap and textureThreshold are validated as
+    with SAD and NOT USED with a census cost: there is no prefiltered image whose texture could be summed.  Bit-exact
+    against the direct statement tests/bm_census_ref.py.  The library checks the pair (type, size) when compute()
+    pushes it."""
     _destroy, _entry = "adf_bm_destroy", "adf_bm_compute"
 
     def __init__(self, numDisparities=0, blockSize=21):
         super().__init__(0, numDisparities if numDisparities > 0 else 64, blockSize)   # cv::StereoBM: 0 -> 64
         self.textureThreshold, self.uniquenessRatio, self.preFilterCap = 10, 15, 31
+        self.costType, self.censusSize = BM_COST_SAD, 7     # a new adf_bm handle's
 
     @staticmethod
     def create(numDisparities=0, blockSize=21):
@@ -432,6 +442,7 @@ class StereoBM(StereoMatcher):
         _check_device(_read(lib.adf_bm_get_device, C.c_int, self._h), imgs, "this StereoBM")
         _lib.check(lib.adf_bm_set_params(self._h, int(self.minDisparity), int(self.numDisparities), int(self.blockSize),
                                          int(self.preFilterCap), int(self.textureThreshold), int(self.uniquenessRatio)))
+        _lib.check(lib.adf_bm_set_cost(self._h, int(self.costType), int(self.censusSize)))
 
     def _args(self, L, R, D):
         return (self._h, L.n, L.ptr, L.stride, L.pair_stride, R.ptr, R.stride, R.pair_stride, L.w, L.h,
@@ -444,18 +455,20 @@ class StereoBM(StereoMatcher):
 
         The reference's right matcher keeps cv::StereoBM's default preFilterCap of 31 (DF.cpp:421-431 copy every
         parameter BUT the cap), so one shared prefilter is only the same computation when this matcher's cap is 31
-        too; with any other cap the two maps are produced by the two separate computes (same results, two launches)."""
+        too; with any other cap the two maps are produced by the two separate computes (same results, two launches).
+        With a census cost there is no prefilter: the views share their descriptor planes whatever the cap is, and the
+        single launch is always taken."""
         L, R, batched = self._views(left, right, "computeBoth takes device tensors; use two compute() calls on the host")
         if self._left_right_check_on() or self.speckleWindowSize > 0:
             raise AdfError(_lib.ADF_EBADARG, "the matcher's own left-right check and speckle filter are not implemented")
         (disparity_left, disparity_right), (DL, DR) = self._outputs(
             (disparity_left, disparity_right), ("disparity_left", "disparity_right"), L, batched, "disparity maps must match the views")
-        if self.preFilterCap != 31:
+        if self.preFilterCap != 31 and self.costType == BM_COST_SAD:
             if getattr(self, "_right", None) is None:
                 self._right = StereoBM(1, 5)
             rm = createRightMatcher(self)
             for k in ("minDisparity", "numDisparities", "blockSize", "textureThreshold", "uniquenessRatio",
-                      "preFilterCap", "disp12MaxDiff", "speckleWindowSize"):
+                      "preFilterCap", "disp12MaxDiff", "speckleWindowSize", "costType", "censusSize"):
                 setattr(self._right, k, getattr(rm, k))
             self.compute(left, right, disparity_left)
             self._right.compute(right, left, disparity_right)
@@ -881,7 +894,7 @@ def pointCloud(disparity, Q, view=None, ROI=None, zRange=None, handleMissingValu
 
 
 def createDisparityWLSFilter(matcher_left):
-    """DF.hpp:131, DF.cpp:386-414: set the filter up from the matcher (and mutate the matcher).  A StereoSGBM's cost type
+    """DF.hpp:131, DF.cpp:386-414: set the filter up from the matcher (and mutate the matcher).  A matcher's cost type
     and census size are not among the mutated parameters: createRightMatcher(matcher_left) carries them to the right view."""
     matcher_left.setDisp12MaxDiff(1000000)
     matcher_left.setSpeckleWindowSize(0)
@@ -914,6 +927,8 @@ def createRightMatcher(matcher_left):
         right.setMinDisparity(-(min_disp + num_disp) + 1)
         right.setTextureThreshold(0)
         right.setUniquenessRatio(0)
+        right.setCostType(matcher_left.getCostType())         # (a different cost on the right view would wreck the LRC confidence)
+        right.setCensusSize(matcher_left.getCensusSize())
         right.setDisp12MaxDiff(1000000)
         right.setSpeckleWindowSize(0)
         return right

@@ -359,6 +359,29 @@ int adf_bm_set_params(adf_bm_t* h, int min_disparity, int num_disparities, int b
 int adf_bm_get_device(const adf_bm_t* h, int* device);
 int adf_bm_get_params(const adf_bm_t* h, int* min_disparity, int* num_disparities, int* block_size,
                       int* prefilter_cap, int* texture_threshold, int* uniqueness_ratio);
+/* The matching cost.  The reference's own block matcher, cv::stereo::StereoBinaryBM, matches census descriptors with a
+ * Hamming distance (modules/stereo/src/stereo_binary_bm.cpp:367-408; setBinaryKernelType, kernelSize).  With a census cost
+ *   cL, cR      = adf_census_transform_* (below) of the left and the right CV_8UC1 view at (cost_type, census_size):
+ *                 dense 3 / 5 / 7, sparse 5 / 7 / 9 / 11; neighbour coordinates clamped, so every pixel has a descriptor;
+ *   pixel cost  = popcount(cL(y, x) ^ cR(y, x - d));
+ *   block cost  = S[k][x], the sum of the pixel cost over the full blockSize x blockSize window, d = minDisparity + k
+ *                 (at most 21 * 21 * 48 = 21168);
+ * and everything else is the SAD matcher's: the valid rectangle x in [max(maxD,0) + w/2, W + min(minD,0) - w/2),
+ * y in [w/2, H - w/2), (minDisparity-1)*16 outside it, ties to the largest disparity (with a Hamming cost ties are the
+ * rule: a flat image ties everywhere), the uniqueness test, the sub-pixel formula and the +15 >> 4 rounding.
+ * preFilterCap and textureThreshold are validated as with SAD and NOT USED with a census cost: there is no prefiltered
+ * image, hence no texture that could be summed (the filter factory sets textureThreshold to 0 anyway,
+ * disparity_filters.cpp:399-400).  The definition is this library's own -- bit-exact against the direct statement
+ * tests/bm_census_ref.py, NOT against the in-tree StereoBinaryBM, whose descriptors are no usable bit-level oracle (see
+ * adf_census_transform_*) and whose median filters and 8-bit output are not built.
+ * ADF_BM_COST_CENSUS_* equal ADF_SGBM_COST_CENSUS_*, which are accepted too.  An unknown (cost_type, census_size) pair is
+ * ADF_EBADARG and the handle keeps its cost; census_size is ignored, and left as it was, with ADF_BM_COST_SAD.  A handle
+ * may change cost between calls; adf_bm_compute_both_device shares the descriptor planes between the two views. */
+#define ADF_BM_COST_SAD 0            /* cv::StereoBM's SAD on the x-Sobel prefiltered views (default) */
+#define ADF_BM_COST_CENSUS_DENSE 1   /* cv::stereo CV_DENSE_CENSUS, census_size 3, 5, 7 */
+#define ADF_BM_COST_CENSUS_SPARSE 2  /* cv::stereo CV_SPARSE_CENSUS, census_size 5, 7, 9, 11 */
+int adf_bm_set_cost(adf_bm_t* h, int cost_type, int census_size);
+int adf_bm_get_cost(const adf_bm_t* h, int* cost_type, int* census_size); /* a new handle: ADF_BM_COST_SAD, 7 */
 /* StereoMatcher::compute(left, right, disparity) on a batch of n_pairs equally sized CV_8UC1 pairs laid out
  * `*_pair_stride` bytes apart; disparity: CV_16SC1, W x H (strides in bytes).  Asynchronous on `stream`. */
 int adf_bm_compute_device(adf_bm_t* h, int n_pairs,

@@ -412,6 +412,8 @@ inline cv::Ptr<cv::StereoMatcher> createRightMatcher(cv::Ptr<cv::StereoMatcher> 
         right_bm->setUniquenessRatio(0);
         right_bm->setDisp12MaxDiff(1000000);
         right_bm->setSpeckleWindowSize(0);
+        // (cv::StereoBM has one matching cost: the census costs exist on adf::ximgproc::StereoBM below, whose
+        // createRightMatcher carries them over)
         return right_bm;
     }
     if (cv::Ptr<cv::StereoSGBM> sgbm = matcher_left.dynamicCast<cv::StereoSGBM>()) {
@@ -441,6 +443,7 @@ class StereoBM {
     adf_bm_t* h_ = nullptr;
     int min_disp_ = 0, num_disp_, block_, cap_ = 31, texture_ = 10, uniq_ = 15;   // cv::StereoBM's defaults
     int disp12_ = -1, speckle_window_ = 0;
+    int cost_ = ADF_BM_COST_SAD, census_size_ = 7;                                // a new adf_bm handle's
 public:
     StereoBM(int numDisparities, int blockSize) : num_disp_(numDisparities > 0 ? numDisparities : 64), block_(blockSize)
     {
@@ -458,6 +461,11 @@ public:
     int getUniquenessRatio() const { return uniq_; }         void setUniquenessRatio(int v) { uniq_ = v; }
     int getDisp12MaxDiff() const { return disp12_; }         void setDisp12MaxDiff(int v) { disp12_ = v; }
     int getSpeckleWindowSize() const { return speckle_window_; } void setSpeckleWindowSize(int v) { speckle_window_ = v; }
+    // extension (adf_bm_set_cost in adf_wls.h): ADF_BM_COST_SAD, or a census descriptor + Hamming distance, the cost of
+    // the reference's own cv::stereo::StereoBinaryBM; preFilterCap and textureThreshold are validated and not used with
+    // it (there is no prefiltered image).  The library checks the pair (type, size) when compute() pushes it.
+    int getCostType() const { return cost_; }                void setCostType(int v) { cost_ = v; }
+    int getCensusSize() const { return census_size_; }       void setCensusSize(int v) { census_size_ = v; }
     // StereoMatcher::compute: CV_8UC1 views -> CV_16SC1 disparity * 16, rejected pixels (minDisparity - 1) * 16
     void compute(const Mat& left, const Mat& right, Mat& disparity)
     {
@@ -469,6 +477,7 @@ public:
         if ((disp12_ >= 0 && disp12_ < 1000000) || speckle_window_ > 0)          // the filter factory switches both off (DF.cpp:389-390)
             throw Exception(ADF_EBADARG, "the matcher's own left-right check and speckle filter are not implemented");
         check(adf_bm_set_params(h_, min_disp_, num_disp_, block_, cap_, texture_, uniq_));
+        check(adf_bm_set_cost(h_, cost_, census_size_));
         Mat out;
         mat_create(out, left.rows, left.cols, D16S, 1);
         check(adf_bm_compute_host(h_, 1, left.data, mat_step(left), 0, right.data, mat_step(right), 0, left.cols, left.rows,
@@ -499,6 +508,8 @@ inline Ptr<StereoBM> createRightMatcher(const Ptr<StereoBM>& matcher_left)
     right_bm->setDisp12MaxDiff(1000000);
     right_bm->setSpeckleWindowSize(0);
     // (the reference's BM branch does not copy preFilterCap: the right matcher keeps cv::StereoBM's default 31)
+    right_bm->setCostType(matcher_left->getCostType());         // (a different cost on the right view would wreck the LRC confidence)
+    right_bm->setCensusSize(matcher_left->getCensusSize());
     return right_bm;
 }
 
