@@ -28,7 +28,7 @@
 // by HBM: the views are read through L1/L2 once per disparity, HBM sees them once.
 //
 // Census cost (adf_bm_set_cost).  The pixel cost is a policy of the match kernel.  With
-// ADF_BM_COST_CENSUS_* the prefiltered views are replaced by the census descriptors of the raw views, split into
+// ADF_BM_COST_CENSUS_* the prefiltered views are replaced by the census descriptors (census.h) of the raw views, split into
 // P = ceil(bits / 8) byte planes in the same row-group interleaved layout (plane p holds bits 8p .. 8p+7, no +1 bias),
 // and the vertical sum of four rows of a column is popcount((L ^ R) & window_mask), added up over the groups and over
 // the planes.  A one-plane descriptor keeps its left columns in registers as SAD does; wider ones reload them per plane
@@ -80,57 +80,37 @@ struct CensusPackArgs {
 };
 
 // The census descriptors of both views (blockIdx.z = 2 * pair + view) as byte planes in the matcher's layout, straight
-// from the raw views: the 64 x 16 tile of four row groups plus its halo goes through LDS with clamped coordinates, as in
-// census_kernel (census_kernels.hip), whose comparison loop this repeats -- the bits are adf_census_transform's -- and a
-// lane forms the descriptors of the four rows of its group and stores one dword per plane.  Going through
-// adf::census_run instead would write 8 bytes per pixel and read them back to keep 1..6.  The
-// padding groups hold the descriptors of the edge-replicated image; no window of a matched row reaches them.
-template <bool SPARSE, int K>
-__global__ void __launch_bounds__(256) bm_census_pack_kernel(CensusPackArgs a)
+// from the raw views.  The descriptor lives in census.h: its shape S, the tile (four row groups) plus halo through LDS with
+// clamped coordinates and the comparison loop are the ones census_kernel runs, so the bits are adf_census_transform's.  This
+// kernel's own: a wave takes a row group, a lane forms the descriptors of its four rows and stores one dword per byte plane.
+// Going through adf::census_run instead would write 8 bytes per pixel and read them back to keep 1..6.
+// The padding groups hold the descriptors of the edge-replicated image; no window of a matched row reaches them.
+template <class S>
+__global__ void __launch_bounds__(CENSUS_THREADS) bm_census_pack_kernel(CensusPackArgs a)
 {
-    constexpr int N2 = K / 2, STEP = SPARSE ? 2 : 1;
-    constexpr int PER_AXIS = 2 * N2 / STEP + 1, NBITS = PER_AXIS * PER_AXIS - (N2 % STEP == 0 ? 1 : 0);
-    constexpr int NP = (NBITS + 7) / 8;
-    constexpr int LW = 64 + 2 * N2, LH = 16 + 2 * N2;
-    __shared__ uint8_t tile[LH][LW];
+    constexpr int GROUPS = CENSUS_TILE_H / 4;                  // row groups of a tile: one per wave
+    static_assert(GROUPS * 64 == CENSUS_THREADS);
+    __shared__ uint8_t tile[S::LH][S::LW];
     const int view = blockIdx.z & 1;
     const unsigned pz = blockIdx.z >> 1;
-    const int x0 = blockIdx.x * 64, gp0 = blockIdx.y * 4, y0 = 4 * (gp0 - PG);
-    const uint8_t* src = a.src[view] + (ptrdiff_t)pz * a.pair_stride[view];
-    for (int i = threadIdx.x; i < LH * LW; i += 256) {
-        const int r = i / LW, c = i - r * LW;
-        const int y = min(max(y0 - N2 + r, 0), a.H - 1), x = min(max(x0 - N2 + c, 0), a.W - 1);
-        tile[r][c] = src[(ptrdiff_t)y * a.stride[view] + x];
-    }
-    __syncthreads();
+    const int x0 = blockIdx.x * CENSUS_TILE_W, gp0 = blockIdx.y * GROUPS, y0 = 4 * (gp0 - PG);
+    census_tile_load<S>(tile, a.src[view] + (ptrdiff_t)pz * a.pair_stride[view], a.stride[view], x0, y0, a.W, a.H);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int x = x0 + lane, gp = gp0 + wv;
     if (x >= a.W || gp >= a.HGP) return;
-    uint32_t out[NP];
+    uint32_t out[S::PLANES];
 #pragma unroll
-    for (int p = 0; p < NP; p++) out[p] = 0;
+    for (int p = 0; p < S::PLANES; p++) out[p] = 0;
 #pragma unroll
     for (int b = 0; b < 4; b++) {
-        const int r = 4 * wv + b;
-        const uint32_t centre = tile[r + N2][lane + N2];
-        uint32_t hi = 0, lo = 0;
-        int bit = NBITS - 1;                                   // (a compile-time constant at every use: both loops unroll)
+        uint32_t hi, lo;
+        census_compare<S>(tile, 4 * wv + b, lane, hi, lo);
 #pragma unroll
-        for (int dy = -N2; dy <= N2; dy += STEP)
-#pragma unroll
-            for (int dx = -N2; dx <= N2; dx += STEP) {
-                if (dy == 0 && dx == 0) continue;
-                const uint32_t v = tile[r + N2 + dy][lane + N2 + dx] > centre ? 1u : 0u;
-                if (bit >= 32) hi |= v << (bit - 32);
-                else lo |= v << bit;
-                bit--;
-            }
-#pragma unroll
-        for (int p = 0; p < NP; p++) out[p] |= (((p < 4 ? lo >> (8 * p) : hi >> (8 * (p - 4)))) & 0xFFu) << (8 * b);
+        for (int p = 0; p < S::PLANES; p++) out[p] |= (((p < 4 ? lo >> (8 * p) : hi >> (8 * (p - 4)))) & 0xFFu) << (8 * b);
     }
     uint32_t* dst = a.dst + (size_t)view * a.dst_view + (size_t)pz * a.dst_pair + (size_t)gp * a.Wp + x;
 #pragma unroll
-    for (int p = 0; p < NP; p++) dst[(size_t)p * a.dst_plane] = out[p];
+    for (int p = 0; p < S::PLANES; p++) dst[(size_t)p * a.dst_plane] = out[p];
 }
 
 // One view's search: its prefiltered "left" (reference) and "right" (searched) images, output and disparity range.
@@ -487,6 +467,15 @@ hipError_t launch_match(const MatchArgs& a, int w2, dim3 block, int n, hipStream
     return hipGetLastError();
 }
 
+// The kernel of a call: the cost policy first (SAD; census with its one plane resident or with the plane loop), then UNIQ.
+hipError_t launch_match_for(const MatchArgs& a, bool census, bool uniq, int w2, int n, hipStream_t st)
+{
+    auto with = [&](auto cost) {
+        return uniq ? launch_match<true, decltype(cost)>(a, w2, dim3(256), n, st) : launch_match<false, decltype(cost)>(a, w2, dim3(256), n, st);
+    };
+    return !census ? with(CostSad{}) : a.planes > 1 ? with(CostCensus<true>{}) : with(CostCensus<false>{});
+}
+
 } // namespace
 
 // ----------------------------------------------------------------------------------------------
@@ -535,12 +524,7 @@ extern "C" int adf_bm_set_params(adf_bm_t* h, int min_disparity, int num_dispari
 extern "C" int adf_bm_set_cost(adf_bm_t* h, int cost_type, int census_size)
 {
     if (!h) return fail(ADF_EBADARG, "handle is NULL");
-    if (cost_type != ADF_BM_COST_SAD) {
-        if (int rc = census_check(cost_type, census_size)) return rc;
-        h->census_size = census_size;
-    }
-    h->cost = cost_type;
-    return ADF_OK;
+    return census_cost_set(h->cost, h->census_size, ADF_BM_COST_SAD, cost_type, census_size);
 }
 
 extern "C" int adf_bm_get_cost(const adf_bm_t* h, int* cost_type, int* census_size)
@@ -589,15 +573,8 @@ static int bm_check(const adf_bm* h, int n, const void* l, const void* r, const 
     return ADF_OK;
 }
 
-template <bool SPARSE, int K>
-static void census_pack_launch(const CensusPackArgs& p, int n_pairs, hipStream_t st)
-{
-    hipLaunchKernelGGL((bm_census_pack_kernel<SPARSE, K>), dim3((p.W + 63) / 64, (p.HGP + 3) / 4, 2 * n_pairs), dim3(256), 0, st, p);
-}
-
 // Shared body: prefilter both images once (census: form their descriptor planes), then one launch for the left view
-// alone (disp_right == NULL) or for
-// both views.
+// alone (disp_right == NULL) or for both views.
 static int bm_compute_impl(adf_bm_t* h, int n_pairs,
                            const uint8_t* left, ptrdiff_t left_stride, ptrdiff_t left_pair_stride,
                            const uint8_t* right, ptrdiff_t right_stride, ptrdiff_t right_pair_stride,
@@ -622,7 +599,7 @@ static int bm_compute_impl(adf_bm_t* h, int n_pairs,
     const int Wp = (W + XPAD + 3) / 4 * 4;                     // padded row: lanes past the image read (and discard) it
     const size_t view = (size_t)HGP * Wp;                      // dwords per prefiltered view / per descriptor plane
     const bool census = h->cost != ADF_BM_COST_SAD;
-    const int planes = census ? (census_bits(h->cost, h->census_size) + 7) / 8 : 1;
+    const int planes = census ? census_planes(h->cost, h->census_size) : 1;
     const size_t image = view * (size_t)planes;                // dwords per image: sized from the handle's cost of THIS call
     rc = h->views.reserve(2 * image * (size_t)n_pairs * sizeof(uint32_t), st, FILL_NONE);
     if (rc) return rc;
@@ -635,16 +612,9 @@ static int bm_compute_impl(adf_bm_t* h, int n_pairs,
         p.src[1] = right; p.stride[1] = right_stride; p.pair_stride[1] = right_pair_stride;
         p.dst = Lt; p.dst_view = image * (size_t)n_pairs; p.dst_pair = image; p.dst_plane = view;
         p.W = W; p.Wp = Wp; p.H = H; p.HGP = HGP;
-        switch (h->cost == ADF_BM_COST_CENSUS_SPARSE ? -h->census_size : h->census_size) {
-        case 3: census_pack_launch<false, 3>(p, n_pairs, st); break;
-        case 5: census_pack_launch<false, 5>(p, n_pairs, st); break;
-        case 7: census_pack_launch<false, 7>(p, n_pairs, st); break;
-        case -5: census_pack_launch<true, 5>(p, n_pairs, st); break;
-        case -7: census_pack_launch<true, 7>(p, n_pairs, st); break;
-        case -9: census_pack_launch<true, 9>(p, n_pairs, st); break;
-        case -11: census_pack_launch<true, 11>(p, n_pairs, st); break;
-        default: return fail(ADF_EBADARG, "census size %d is not supported", h->census_size);
-        }
+        const dim3 grid((W + CENSUS_TILE_W - 1) / CENSUS_TILE_W, (HGP * 4 + CENSUS_TILE_H - 1) / CENSUS_TILE_H, 2 * n_pairs);
+        const bool known = census_dispatch(h->cost, h->census_size, [&](auto s) { hipLaunchKernelGGL((bm_census_pack_kernel<decltype(s)>), grid, dim3(CENSUS_THREADS), 0, st, p); });
+        if (!known) return fail(ADF_EBADARG, "census size %d is not supported", h->census_size);
     } else {
         PrefilterArgs p;
         p.W = W; p.Wp = Wp; p.H = H; p.HGP = HGP; p.cap = h->cap; p.dst_pair = view;
@@ -676,12 +646,7 @@ static int bm_compute_impl(adf_bm_t* h, int n_pairs,
     a.v[1] = disp_right ? view_args(Rt, Lt, disp_right, dr_stride, dr_pair_stride, -(h->min_disp + h->num_disp) + 1, 0, 0) : a.v[0];
     hipLaunchKernelGGL(bm_border_kernel, dim3(4, H, n_pairs * nviews), dim3(256), 0, st, a);
     if (a.v[0].xe > a.v[0].xs || (nviews == 2 && a.v[1].xe > a.v[1].xs)) {
-        hipError_t e = planes > 1 ? (h->uniq > 0 ? launch_match<true, CostCensus<true>>(a, w2, dim3(256), n_pairs, st)
-                                                 : launch_match<false, CostCensus<true>>(a, w2, dim3(256), n_pairs, st))
-                     : census ? (h->uniq > 0 ? launch_match<true, CostCensus<false>>(a, w2, dim3(256), n_pairs, st)
-                                             : launch_match<false, CostCensus<false>>(a, w2, dim3(256), n_pairs, st))
-                              : (h->uniq > 0 ? launch_match<true, CostSad>(a, w2, dim3(256), n_pairs, st)
-                                             : launch_match<false, CostSad>(a, w2, dim3(256), n_pairs, st));
+        hipError_t e = launch_match_for(a, census, h->uniq > 0, w2, n_pairs, st);
         if (e != hipSuccess) return fail(ADF_EHIP, "%s", hipGetErrorString(e));
     }
     hipError_t e = hipGetLastError();

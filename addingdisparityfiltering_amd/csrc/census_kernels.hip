@@ -1,5 +1,6 @@
 // census_kernels.hip -- the census transform on the device: the descriptor the semi-global matcher's Hamming cost
-// compares (sgbm_matcher.hip, ADF_SGBM_COST_CENSUS_*), and adf_census_transform_* of include/adf_wls.h.
+// compares (sgbm_matcher.hip, ADF_SGBM_COST_CENSUS_*), and adf_census_transform_* of include/adf_wls.h.  The descriptor -- the
+// pairs that exist, their bits, the tile load, the comparison loop -- is stated in census.h; the kernel here sweeps rows and stores.
 //
 // The reference's own semi-global matcher, cv::stereo::StereoBinarySGBM, matches on census descriptors
 // (modules/stereo/src/stereo_binary_sgbm.cpp, include/opencv2/stereo/descriptor.hpp, src/descriptor.cpp).  What is built
@@ -27,54 +28,25 @@ struct CensusArgs {
     int W, H;
 };
 
-constexpr int CT_W = 64, CT_H = 16;                 // pixels of a workgroup: a wave per row, four rows per sweep
-
-// One workgroup: the 64 x 16 tile plus its K/2 halo on every side in LDS (coordinates clamped while it is loaded, so
-// an image smaller than the window is all replicated edge), then one pixel per lane and sweep: K*K - 1 (dense) or
-// fewer (sparse) byte compares against the centre, fully unrolled, and one 8-byte store per lane.
-template <bool SPARSE, int K>
-__global__ void __launch_bounds__(256) census_kernel(CensusArgs a)
+// One workgroup: the 64 x 16 tile plus its K/2 halo on every side in LDS (census_tile_load), then one pixel per lane and
+// sweep: the descriptor's compares (census_compare) and one 8-byte store per lane.
+template <class S>
+__global__ void __launch_bounds__(CENSUS_THREADS) census_kernel(CensusArgs a)
 {
-    constexpr int N2 = K / 2, STEP = SPARSE ? 2 : 1;
-    constexpr int PER_AXIS = 2 * N2 / STEP + 1, NBITS = PER_AXIS * PER_AXIS - (N2 % STEP == 0 ? 1 : 0);
-    constexpr int LW = CT_W + 2 * N2, LH = CT_H + 2 * N2;
-    __shared__ uint8_t tile[LH][LW];
-    const int x0 = blockIdx.x * CT_W, y0 = blockIdx.y * CT_H;
-    const uint8_t* src = a.src + (ptrdiff_t)blockIdx.z * a.simage;
-    for (int i = threadIdx.x; i < LH * LW; i += 256) {
-        const int r = i / LW, c = i - r * LW;
-        const int y = min(max(y0 - N2 + r, 0), a.H - 1), x = min(max(x0 - N2 + c, 0), a.W - 1);
-        tile[r][c] = src[(ptrdiff_t)y * a.sstride + x];
-    }
-    __syncthreads();
+    __shared__ uint8_t tile[S::LH][S::LW];
+    const int x0 = blockIdx.x * CENSUS_TILE_W, y0 = blockIdx.y * CENSUS_TILE_H;
+    census_tile_load<S>(tile, a.src + (ptrdiff_t)blockIdx.z * a.simage, a.sstride, x0, y0, a.W, a.H);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int x = x0 + lane;
     if (x >= a.W) return;
-    for (int r = wv; r < CT_H; r += 4) {
+    for (int r = wv; r < CENSUS_TILE_H; r += CENSUS_THREADS / 64) {
         const int y = y0 + r;
         if (y >= a.H) break;
-        const uint32_t centre = tile[r + N2][lane + N2];
-        uint32_t hi = 0, lo = 0;
-        int bit = NBITS - 1;                                   // (a compile-time constant at every use: both loops unroll)
-#pragma unroll
-        for (int dy = -N2; dy <= N2; dy += STEP)
-#pragma unroll
-            for (int dx = -N2; dx <= N2; dx += STEP) {
-                if (dy == 0 && dx == 0) continue;
-                const uint32_t b = tile[r + N2 + dy][lane + N2 + dx] > centre ? 1u : 0u;
-                if (bit >= 32) hi |= b << (bit - 32);
-                else lo |= b << bit;
-                bit--;
-            }
+        uint32_t hi, lo;
+        census_compare<S>(tile, r, lane, hi, lo);
         uint64_t* row = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(a.dst) + (ptrdiff_t)blockIdx.z * a.dimage + (ptrdiff_t)y * a.dstride);
         row[x] = ((uint64_t)hi << 32) | lo;
     }
-}
-
-template <bool SPARSE, int K>
-void census_launch(const CensusArgs& a, int n, hipStream_t st)
-{
-    hipLaunchKernelGGL((census_kernel<SPARSE, K>), dim3((a.W + CT_W - 1) / CT_W, (a.H + CT_H - 1) / CT_H, n), dim3(256), 0, st, a);
 }
 
 int census_args_check(int n, const void* src, ptrdiff_t sstride, ptrdiff_t simage, int W, int H, int type, int k,
@@ -105,21 +77,13 @@ int adf::census_run(int n, const uint8_t* src, ptrdiff_t sstride, ptrdiff_t sima
                     uint64_t* dst, ptrdiff_t dstride, ptrdiff_t dimage, hipStream_t st)
 {
     constexpr int MAX_GRID_Z = 65535;
-    const bool sparse = census_type == ADF_SGBM_COST_CENSUS_SPARSE;
     for (int m0 = 0; m0 < n; m0 += MAX_GRID_Z) {
         const int nm = std::min(n - m0, MAX_GRID_Z);
         const CensusArgs a{src + (ptrdiff_t)m0 * simage, sstride, n > 1 ? simage : 0,
                            reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(dst) + (ptrdiff_t)m0 * dimage), dstride, n > 1 ? dimage : 0, W, H};
-        switch (sparse ? -k : k) {
-        case 3: census_launch<false, 3>(a, nm, st); break;
-        case 5: census_launch<false, 5>(a, nm, st); break;
-        case 7: census_launch<false, 7>(a, nm, st); break;
-        case -5: census_launch<true, 5>(a, nm, st); break;
-        case -7: census_launch<true, 7>(a, nm, st); break;
-        case -9: census_launch<true, 9>(a, nm, st); break;
-        case -11: census_launch<true, 11>(a, nm, st); break;
-        default: return fail(ADF_EBADARG, "census size %d is not supported", k);
-        }
+        const dim3 grid((W + CENSUS_TILE_W - 1) / CENSUS_TILE_W, (H + CENSUS_TILE_H - 1) / CENSUS_TILE_H, nm);
+        const bool known = census_dispatch(census_type, k, [&](auto s) { hipLaunchKernelGGL((census_kernel<decltype(s)>), grid, dim3(CENSUS_THREADS), 0, st, a); });
+        if (!known) return fail(ADF_EBADARG, "census size %d is not supported", k);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess) return fail(ADF_EHIP, "%s", hipGetErrorString(e));
     }

@@ -23,7 +23,7 @@
 //   sgbm_fill_kernel / sgbm_median_kernel   invalid value everywhere first; 3x3 median of the CV_16S map last
 // ADF_SGBM_COST_CENSUS_* (adf_sgbm_set_cost) swaps the first two for the census transform (census_kernels.hip) and a
 // Hamming pixel cost -- what the reference's own matcher, cv::stereo::StereoBinarySGBM, matches on -- through the same
-// cost kernel (the pixel cost is its template policy); everything from the volume C on is the same code.
+// cost kernel (the pixel cost is its template policy, its bound census.h's); everything from the volume C on is the same code.
 // HBM: C, S and L2 volumes of H x width1 x D int16 each (4K, 256 disparities: 4 GB each, per image in flight).
 #include "census.h"
 
@@ -136,7 +136,7 @@ struct BtCost {                                               // the signal reco
 };
 
 struct CensusCost {                                           // the descriptor planes of census_kernel: one 8-byte load, one xor, two bit counts
-    static constexpr int DWORDS = 2, MAX_PIXEL = 48;          // (census_bits() is at most 48)
+    static constexpr int DWORDS = 2, MAX_PIXEL = CENSUS_MAX_BITS;   // (census.h pins every descriptor to at most that many bits)
     struct Own { uint64_t c; };
     static __device__ __forceinline__ Own own(const uint32_t* p) { return Own{*reinterpret_cast<const uint64_t*>(p)}; }
     static __device__ __forceinline__ uint32_t cost(const Own& o, const uint32_t* q)
@@ -681,12 +681,7 @@ extern "C" int adf_sgbm_get_disp12_max_diff(const adf_sgbm_t* h, int* v)
 extern "C" int adf_sgbm_set_cost(adf_sgbm_t* h, int cost_type, int census_size)
 {
     if (!h) return fail(ADF_EBADARG, "handle is NULL");
-    if (cost_type != ADF_SGBM_COST_BT) {
-        if (int rc = census_check(cost_type, census_size)) return rc;
-        h->census_size = census_size;
-    }
-    h->cost = cost_type;
-    return ADF_OK;
+    return census_cost_set(h->cost, h->census_size, ADF_SGBM_COST_BT, cost_type, census_size);
 }
 
 extern "C" int adf_sgbm_get_cost(const adf_sgbm_t* h, int* cost_type, int* census_size)

@@ -67,6 +67,19 @@ def test_every_descriptor_bit_exact(adf, ctype, k):
     assert (inner != -16).all() and (np.abs(inner - 5 * 16) <= 8).mean() > 0.5      # the pair really matches: most pixels find the shift
 
 
+@pytest.mark.parametrize("ctype,k", PAIRS)
+def test_image_narrower_than_a_tile_with_more_padding_than_image_rows(adf, ctype, k):
+    """The shared tile load under the pack kernel's coordinates: 40 columns are less than one 64-column tile (every
+    tile row ends in clamped columns), and 9 rows are three row groups between six padding groups (most of the tile's
+    rows lie above or below the image and are clamped)."""
+    key = (365, 9, 40, 3)
+    got = _bm(adf, 16, 5, ctype=ctype, k=k).compute(*_views(*key))
+    exp = _expected(key, 16, 5, ctype=ctype, k=k)
+    assert np.array_equal(got, exp)
+    inner = exp[2:-2, 17:-2].astype(np.int64)
+    assert (inner != -16).all() and (np.abs(inner - 3 * 16) <= 8).mean() >= 0.5      # not vacuous: the pair matches at its shift
+
+
 @pytest.mark.parametrize("ctype,k", [(DENSE, 3), (DENSE, 7)])                      # 1 and 6 planes
 @pytest.mark.parametrize("H,W,bs", [(21, 330, 5), (22, 330, 21), (70, 150, 9)])
 def test_tile_and_row_group_boundaries(adf, H, W, bs, ctype, k):
