@@ -42,6 +42,12 @@ class ReprojectParams(C.Structure):
     _fields_ = [("Q", C.c_double * 16), ("disp_scale", C.c_double), ("missing_mode", C.c_int), ("missing_value", C.c_double)]
 
 
+class RectifyParams(C.Structure):
+    """adf_rectify_params: fx, fy, cx, cy, dist (k1 k2 p1 p2 k3 k4 k5 k6), ir = inverse(P[:, :3] * R) row-major."""
+    _fields_ = [("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double),
+                ("dist", C.c_double * 8), ("ir", C.c_double * 9)]
+
+
 # every symbol include/adf_wls.h declares: (name, restype, argtypes)
 _vp, _i, _d, _pd, _sz = C.c_void_p, C.c_int, C.c_double, C.c_ssize_t, C.c_size_t
 _FILTER_DEV = [_vp, _i, _vp, _pd, _pd, _vp, _pd, _pd, _i, _i, _i, _vp, _pd, _pd, _vp, _pd, _pd,
@@ -49,6 +55,9 @@ _FILTER_DEV = [_vp, _i, _vp, _pd, _pd, _vp, _pd, _pd, _i, _i, _i, _vp, _pd, _pd,
 _REPROJECT_DEV = [_i, _vp, _i, _pd, _pd, _i, _i, C.POINTER(ReprojectParams), _vp, _pd, _pd, _i, _vp, _sz, _vp]
 _POINT_CLOUD_DEV = [_i, _vp, _i, _pd, _pd, _i, _i, C.POINTER(ReprojectParams), C.POINTER(Rect), _d, _d, _vp, _pd, _pd, _i,
                     _vp, _pd, _vp, _pd, _vp, _pd, _i, _vp, _vp, _sz, _vp]
+_RECTIFY_MAP_DEV = [C.POINTER(RectifyParams), _i, _i, _vp, _pd, _vp, _pd, _vp]
+_REMAP_DEV = [_i, _vp, _pd, _pd, _i, _i, _i, _vp, _pd, _vp, _pd, _vp, _pd, _pd, _i, _i, _i, _i, _vp, _vp]
+_RECTIFY_VIEWS_DEV = [_i, _vp, _pd, _pd, _i, _i, _i, C.POINTER(RectifyParams), _vp, _pd, _pd, _i, _i, _i, _i, _vp, _vp]
 _FILTER_SCALED_DEV = [_vp, _i, _vp, _pd, _pd, _i, _i, _vp, _pd, _pd, _i, _i, _i, _vp, _pd, _pd, _vp, _pd, _pd,
                       C.POINTER(Rect), _vp]
 SYMBOLS = [
@@ -138,6 +147,13 @@ SYMBOLS = [
     ("adf_point_cloud_workspace_bytes", _sz, [_i, _i, _i]),
     ("adf_point_cloud_device", _i, _POINT_CLOUD_DEV),
     ("adf_point_cloud_host", _i, _POINT_CLOUD_DEV[:-3]),
+    ("adf_rectify_params_init", _i, [_vp, _vp, _i, _vp, _vp, _i, C.POINTER(RectifyParams)]),
+    ("adf_init_undistort_rectify_map_device", _i, _RECTIFY_MAP_DEV),
+    ("adf_init_undistort_rectify_map_host", _i, _RECTIFY_MAP_DEV[:-1]),
+    ("adf_remap_device", _i, _REMAP_DEV),
+    ("adf_remap_host", _i, _REMAP_DEV[:-1]),
+    ("adf_rectify_views_device", _i, _RECTIFY_VIEWS_DEV),
+    ("adf_rectify_views_host", _i, _RECTIFY_VIEWS_DEV[:-1]),
 ]
 
 _lib = None

@@ -23,6 +23,7 @@ SOURCES = {
     "speckle_kernels.hip": [],
     "view_prep_kernels.hip": [],
     "reproject_kernels.hip": [],
+    "rectify_kernels.hip": [],
 }
 OUT = os.path.join(_HERE, "libadf_wls.so")
 # -ffp-contract=off: the exact solver and the confidence map reproduce the reference's separate

@@ -16,6 +16,7 @@ edge_filter.hpp (EF.hpp), over the C-ABI in include/adf_wls.h:
     StereoBM.setCostType(BM_COST_CENSUS_*) / setCensusSize(k)   the cost of modules/stereo stereo_binary_bm.cpp:367-408 (extension)
     resize(src, dsize, fx, fy) at half size, cvtColor(src, COLOR_BGR2GRAY)   imgproc (outside the reference tree)
     reprojectImageTo3D(disparity, Q, handleMissingValues, ddepth), pointCloud(...)   calib3d (outside the reference tree)
+    initUndistortRectifyMap(K, dist, R, P, size), remap(src, map1, map2), rectifyViews(...)   calib3d / imgproc (outside the reference tree)
 
 Images are numpy arrays (host path: copied to the GPU and back) or torch CUDA
 tensors (device path: zero-copy, asynchronous on torch's current stream).  A
@@ -891,6 +892,156 @@ def pointCloud(disparity, Q, view=None, ROI=None, zRange=None, handleMissingValu
     if batched:
         return P, Cl, I, got
     return P[0], Cl[0], I[0], got[0]
+
+
+# ---------------------------------------------------------------------------------------------
+# Rectification (cv::initUndistortRectifyMap of calib3d, cv::remap of imgproc, outside the reference tree) on the device
+# (csrc/rectify_kernels.hip; definition, limits and the unpinned parity: include/adf_wls.h, "rectification").
+# ---------------------------------------------------------------------------------------------
+CV_32FC1 = 5            # cv's type code of the one map form that is built
+BORDER_CONSTANT = 0     # cv::BORDER_CONSTANT
+_IM, _RM, _RV = "initUndistortRectifyMap", "remap", "rectifyViews"
+
+
+def _matrix(who, name, m, shapes):
+    """A host float64 matrix of one of `shapes` from any array-like (a tensor is read back)."""
+    if _is_torch(m):
+        m = m.detach().cpu().numpy()
+    try:
+        a = np.ascontiguousarray(m, dtype=np.float64)
+    except (TypeError, ValueError):
+        a = np.zeros(0)
+    if a.shape not in shapes:
+        raise AdfError(_lib.ADF_EBADARG, "%s: %s must be a %s matrix" % (who, name, " or ".join("%dx%d" % s for s in shapes)))
+    return a
+
+
+def rectifyParams(cameraMatrix, distCoeffs=None, R=None, newCameraMatrix=None, who="rectifyParams"):
+    """adf_rectify_params from cv's arguments, through adf_rectify_params_init (the one inverse every layer shares).
+    distCoeffs: None or 0, 4, 5 or 8 numbers in cv's order; R: None (identity) or 3x3; newCameraMatrix: 3x3 or 3x4 (P1 / P2
+    of stereoRectify), None = cameraMatrix."""
+    K = _matrix(who, "cameraMatrix", cameraMatrix, ((3, 3),))
+    P = K if newCameraMatrix is None else _matrix(who, "newCameraMatrix", newCameraMatrix, ((3, 3), (3, 4)))
+    Rm = None if R is None else _matrix(who, "R", R, ((3, 3),))
+    if _is_torch(distCoeffs):
+        distCoeffs = distCoeffs.detach().cpu().numpy()
+    d = np.zeros(0) if distCoeffs is None else np.ascontiguousarray(distCoeffs, dtype=np.float64).ravel()
+    prm = _lib.RectifyParams()
+    _lib.check(_lib.lib().adf_rectify_params_init(K.ctypes.data, d.ctypes.data if d.size else None, int(d.size),
+                                                  None if Rm is None else Rm.ctypes.data, P.ctypes.data, P.shape[1], C.byref(prm)))
+    return prm
+
+
+def _border(who, borderValue, ch):
+    """The three bytes of border_value from a scalar or a 3-tuple (cv::Scalar: a scalar sets the first channel only in
+    cv; here a scalar means every channel, which is what a gray fill wants)."""
+    try:
+        vals = [float(v) for v in borderValue] if hasattr(borderValue, "__len__") else [float(borderValue)] * 3
+    except (TypeError, ValueError):
+        vals = []
+    if len(vals) == 1:
+        vals = vals * 3
+    if len(vals) not in (3, 4) or any(not (0 <= v <= 255) or v != int(v) for v in vals[:3]):
+        raise AdfError(_lib.ADF_EBADARG, "%s: borderValue must be an integer in [0, 255] or three of them" % who)
+    return (C.c_uint8 * 3)(*[int(v) for v in vals[:3]])
+
+
+def _on_device(im, fn):
+    if not im.device:
+        return fn()
+    with torch.cuda.device(im.keep.device):
+        return fn()
+
+
+def initUndistortRectifyMap(cameraMatrix, distCoeffs, R, newCameraMatrix, size, m1type=CV_32FC1, device=None):
+    """cv::initUndistortRectifyMap(cameraMatrix, distCoeffs, R, newCameraMatrix, size, CV_32FC1) -> (map1, map2): the two
+    float planes (H,W) of source coordinates for `size` = (width, height), every step one binary64 operation in the order
+    include/adf_wls.h states (bit-exact against tests/rectify_ref.py; parity with calib3d is unpinned).  Only m1type
+    CV_32FC1 is built (no CV_16SC2 pair, no convertMaps).  `device`: None gives numpy arrays through the host entry; a
+    torch device (or "cuda") gives CUDA tensors computed on it, asynchronously on torch's current stream."""
+    if m1type != CV_32FC1:
+        raise AdfError(_lib.ADF_EBADARG, "%s: m1type must be CV_32FC1 (the CV_16SC2 pair is not built)" % _IM)
+    prm = rectifyParams(cameraMatrix, distCoeffs, R, newCameraMatrix, _IM)
+    try:
+        W, H = int(size[0]), int(size[1])
+    except (TypeError, ValueError, IndexError):
+        raise AdfError(_lib.ADF_EBADARG, "%s: size must be (width, height)" % _IM)
+    if W < 1 or H < 1:
+        raise AdfError(_lib.ADF_EBADARG, "%s: the size is empty" % _IM)
+    if W * H >= 2 ** 31:
+        raise AdfError(_lib.ADF_ESIZE, "%s: W*H must be below 2^31" % _IM)
+    if device is None:
+        m1, m2 = np.empty((H, W), np.float32), np.empty((H, W), np.float32)
+    else:
+        if torch is None:
+            raise AdfError(_lib.ADF_EBADARG, "%s: device maps need torch" % _IM)
+        m1 = torch.empty((H, W), dtype=torch.float32, device=device)
+        m2 = torch.empty_like(m1)
+        if not m1.is_cuda:
+            raise AdfError(_lib.ADF_EBADARG, "%s: device must be a CUDA device (None gives numpy arrays)" % _IM)
+    X, Y = _Image(m1, np.float32, "map1", False), _Image(m2, np.float32, "map2", False)
+    _on_device(X, lambda: _call("adf_init_undistort_rectify_map", X, (C.byref(prm), W, H, X.ptr, X.stride, Y.ptr, Y.stride)))
+    return m1, m2
+
+
+def _sample(who, src, maps, prm, W, H, borderValue, dst):
+    """The common part of remap and rectifyViews: `maps` = (X, Y) _Images or None, `prm` = RectifyParams or None."""
+    im, batched, color = _view_image(src, "src")
+    if im.w > 32767 or im.h > 32767:
+        raise AdfError(_lib.ADF_ESIZE, "%s: srcW and srcH must not exceed 32767" % who)
+    if W * H >= 2 ** 31:
+        raise AdfError(_lib.ADF_ESIZE, "%s: W*H must be below 2^31" % who)
+    border = _border(who, borderValue, im.c)
+    shape = ((im.n,) if batched else ()) + (H, W) + ((3,) if color else (1,) if im.unit_axis else ())
+    if dst is None:
+        dst = _empty(im, shape, np.uint8)
+    if tuple(dst.shape) != shape:
+        raise AdfError(_lib.ADF_ESIZE, "%s: dst must have shape %s" % (who, shape))
+    D = _Image(dst[..., 0] if im.unit_axis else dst, np.uint8, "dst", batched, allow_channels=(im.c,))
+    if D.device != im.device or (im.device and dst.device != im.keep.device):
+        raise AdfError(_lib.ADF_ESIZE, "%s: dst must have shape %s where src lives (host, or the same device)" % (who, shape))
+    head = (im.n, im.ptr, im.stride, im.pair_stride, im.w, im.h, im.c)
+    tail = (D.ptr, D.stride, D.pair_stride, W, H, INTER_LINEAR, BORDER_CONSTANT, border)
+    if maps is not None:
+        X, Y = maps
+        for m in maps:
+            if m.device != im.device or (im.device and m.keep.device != im.keep.device):
+                raise AdfError(_lib.ADF_EBADARG, "%s: the maps must live where src lives (host, or the same device)" % who)
+        _on_device(im, lambda: _call("adf_remap", im, head + (X.ptr, X.stride, Y.ptr, Y.stride) + tail))
+    else:
+        _on_device(im, lambda: _call("adf_rectify_views", im, head + (C.byref(prm),) + tail))
+    return dst
+
+
+def remap(src, map1, map2, interpolation=INTER_LINEAR, borderMode=BORDER_CONSTANT, borderValue=0, dst=None):
+    """cv::remap(src, dst, map1, map2, INTER_LINEAR, BORDER_CONSTANT, borderValue) with a CV_32FC1 map pair (H,W): bilinear
+    with 5 fractional bits, the integer form include/adf_wls.h states (bit-exact against tests/rectify_ref.py).  `src` is a
+    CV_8UC1 / CV_8UC3 image (h,w[,3]) of any size up to 32767 x 32767 or a batch (N,h,w[,3]); one map pair serves the whole
+    batch.  numpy arrays take the host entry, torch CUDA tensors run on the device on torch's current stream (with `dst`
+    given nothing is allocated: capturable).  Other interpolations and border modes are refused.  `borderValue`: an integer
+    for every channel, or three."""
+    if interpolation != INTER_LINEAR or borderMode != BORDER_CONSTANT:
+        raise AdfError(_lib.ADF_EBADARG, "%s: INTER_LINEAR with BORDER_CONSTANT only" % _RM)
+    if map1 is None or map2 is None or len(map1.shape) != 2 or tuple(map1.shape) != tuple(map2.shape):
+        raise AdfError(_lib.ADF_EBADARG, "%s: map1 and map2 must be two CV_32FC1 planes (H,W) of one size" % _RM)
+    X, Y = _Image(map1, np.float32, "map1", False), _Image(map2, np.float32, "map2", False)
+    return _sample(_RM, src, (X, Y), None, X.w, X.h, borderValue, dst)
+
+
+def rectifyViews(src, cameraMatrix, distCoeffs, R, newCameraMatrix, size=None, borderValue=0, dst=None):
+    """Extension: remap(src, *initUndistortRectifyMap(cameraMatrix, distCoeffs, R, newCameraMatrix, size)) in ONE launch,
+    bit for bit, without the maps ever being written: the per-frame call (one read of the source, one write of the
+    destination).  `size` = (width, height) of the rectified view, None = the source's.  `src` may hold every view of one
+    camera in a batch; the two cameras of a rig have different parameters and take two calls."""
+    im, _, _ = _view_image(src, "src")
+    try:
+        W, H = (im.w, im.h) if size is None else (int(size[0]), int(size[1]))
+    except (TypeError, ValueError, IndexError):
+        raise AdfError(_lib.ADF_EBADARG, "%s: size must be (width, height)" % _RV)
+    if W < 1 or H < 1:
+        raise AdfError(_lib.ADF_EBADARG, "%s: the size is empty" % _RV)
+    prm = rectifyParams(cameraMatrix, distCoeffs, R, newCameraMatrix, _RV)
+    return _sample(_RV, src, None, prm, W, H, borderValue, dst)
 
 
 def createDisparityWLSFilter(matcher_left):

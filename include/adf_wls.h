@@ -641,6 +641,96 @@ int adf_point_cloud_host(int n_maps, const void* disp, int depth, ptrdiff_t stri
                          float* points, ptrdiff_t points_map_stride, uint8_t* colours, ptrdiff_t colours_map_stride,
                          int32_t* index, ptrdiff_t index_map_stride, int capacity, uint32_t* counts);
 
+/* ---------------- rectification (cv::initUndistortRectifyMap, cv::remap) ----------------
+ * The two calls a stereo pipeline makes in front of everything above: cv::initUndistortRectifyMap(K, dist, R, P, size,
+ * CV_32FC1, map1, map2) once per camera and cv::remap(src, dst, map1, map2, INTER_LINEAR, BORDER_CONSTANT, borderValue) per
+ * frame, with K, dist of the calibration and R1/P1 (R2/P2) of the caller's stereoRectify -- the same stereoRectify whose Q
+ * adf_reproject_* takes.  adf_rectify_views_* (extension) is both in one launch: the maps never exist in memory.
+ * calib3d and imgproc are outside the reference tree, so parity with OpenCV is UNPINNED: what follows is the library's own
+ * definition, bit-exact against the direct NumPy statement tests/rectify_ref.py.
+ *
+ * Parameters (host only).  adf_rectify_params_init(K, dist, n_dist, R, P, p_cols, out): K, dist, R, P are cv's cameraMatrix,
+ * distCoeffs, R and newCameraMatrix, row-major doubles.
+ *   - fx, fy, cx, cy = K[0], K[4], K[2], K[5]; the skew K[1] is ignored, as in cv;
+ *   - dist in cv's order k1 k2 p1 p2 k3 k4 k5 k6; n_dist 0, 4, 5 or 8 (missing entries are 0; dist may be NULL with 0).  n_dist
+ *     12 or 14 (thin prism, tilt) and every other count are ADF_EBADARG: those models are not built;
+ *   - R: 9 doubles, NULL = identity; P: 3 x p_cols with p_cols 3 or 4 (ADF_EBADARG otherwise), only P[:, :3] is read;
+ *   - ir = the inverse of A = P[:, :3] * R (A = P[:, :3] itself when R is NULL), in binary64, in this order:
+ *         A[i][j] = (P[i][0]*R[0][j] + P[i][1]*R[1][j]) + P[i][2]*R[2][j]
+ *         the signed cofactors, two products and one difference each:
+ *           c00 = a11*a22 - a12*a21   c01 = a12*a20 - a10*a22   c02 = a10*a21 - a11*a20
+ *           c10 = a02*a21 - a01*a22   c11 = a00*a22 - a02*a20   c12 = a01*a20 - a00*a21
+ *           c20 = a01*a12 - a02*a11   c21 = a02*a10 - a00*a12   c22 = a00*a11 - a01*a10
+ *         the determinant by the first row: det = (a00*c00 + a01*c01) + a02*c02
+ *         one division per entry: ir[3*i + j] = c_ji / det      (the adjugate is the transposed cofactor matrix)
+ *     det == 0 or a non-finite det is ADF_EBADARG.  Every layer (Python, C++) calls this function: one inverse.
+ *
+ * Maps.  adf_init_undistort_rectify_map_* writes two CV_32FC1 planes of W x H; for destination pixel (u, v), with
+ * k1..k6, p1, p2 from dist, every operator below ONE IEEE binary64 operation in exactly this order, no fused multiply-add:
+ *     X = (ir0*u + ir1*v) + ir2      Y = (ir3*u + ir4*v) + ir5      D = (ir6*u + ir7*v) + ir8
+ *     w = 1.0 / D        x = X*w        y = Y*w
+ *     x2 = x*x    y2 = y*y    r2 = x2 + y2    xy2 = (2.0*x)*y
+ *     kr = (1.0 + ((k3*r2 + k2)*r2 + k1)*r2) / (1.0 + ((k6*r2 + k5)*r2 + k4)*r2)
+ *     xd = (x*kr + p1*xy2) + p2*(r2 + 2.0*x2)
+ *     yd = (y*kr + p1*(r2 + 2.0*y2)) + p2*xy2
+ *     mapx = (float)(fx*xd + cx)     mapy = (float)(fy*yd + cy)         (round to nearest)
+ *   Nothing is sanitised: D == 0 gives inf or NaN as the arithmetic gives them; the sign and payload of a NaN are not part
+ *   of the contract.  Known differences from cv: cv accumulates ir0, ir3, ir6 along u (u additions) instead of multiplying by
+ *   u, and cv's SIMD builds fuse multiply-adds; both differ in the last bits of a double before the rounding to float.
+ *   Only the CV_32FC1 pair is built: cv's CV_16SC2 + CV_16UC1 fixed-point pair and convertMaps are not.  The maps and their
+ *   strides must be multiples of 4 bytes (ADF_EBADARG); multiples of 16 are written with 16-byte stores.  W*H < 2^31.
+ *
+ * Sampling.  adf_remap_*: n_images equally sized 8-bit images of 1 or 3 channels (srcW x srcH, rows src_stride bytes
+ * apart, images src_image_stride bytes apart) through ONE map pair of W x H into n_images destinations of W x H.  Only
+ * ADF_INTER_LINEAR with ADF_BORDER_CONSTANT is accepted; everything else is ADF_EBADARG.  border_value: 3 bytes (a 1-channel
+ * image reads the first; NULL = 0).  Per destination pixel, float and integer arithmetic, 5 fractional bits as cv's
+ * INTER_TAB_SIZE = 32:
+ *     tx = mapx*32.0f   ty = mapy*32.0f
+ *     ok = tx >= -1048576.0f && tx <= 1048575.0f && ty >= -1048576.0f && ty <= 1048575.0f       (false for NaN)
+ *     not ok: every channel = border_value[c]
+ *     sx = (int)rintf(tx) (half to even)   ix = sx >> 5   ax = sx & 31          (the same for y)
+ *     tap(i, j) = 0 <= i < srcW && 0 <= j < srcH ? src[j][i][c] : border_value[c]
+ *     out = (tap(ix,iy)*(32-ax)*(32-ay) + tap(ix+1,iy)*ax*(32-ay) + tap(ix,iy+1)*(32-ax)*ay + tap(ix+1,iy+1)*ax*ay + 512) >> 10
+ *   This equals cv's 15-bit table form (its weights are these times 32, its rounding +16384 >> 15).  A tap outside the source
+ *   is never loaded.  Limits: srcW, srcH <= 32767 and W*H < 2^31 (ADF_ESIZE).  src and dst must not overlap; destination
+ *   images of a batch must not overlap each other (they follow one another, or interleave row by row).  A destination whose
+ *   base and strides are multiples of 4 bytes is written with whole 4- / 12-byte stores, maps whose bases and strides are
+ *   multiples of 16 are read with 16-byte loads; anything else gives the same bits byte by byte (slower).
+ *
+ * adf_rectify_views_* takes the arguments of adf_remap_* with the parameters in place of the maps, evaluates the
+ * coordinates and samples in one launch, and gives the bits of the two-step form: it is the per-frame call, its bytes one
+ * read of the source plus one write of the destination.
+ *
+ * Conventions (as adf_reproject_* and adf_prepare_views_*): _device runs on the current HIP device, asynchronously on
+ * `stream`, allocates nothing and never synchronises, so it may be captured into a hipGraph; `prm` and border_value are HOST
+ * pointers in both forms -- they travel in the kernel arguments, there is no upload.  _host: host pointers; copies, runs and
+ * synchronises. */
+#define ADF_INTER_LINEAR 1    /* cv::INTER_LINEAR */
+#define ADF_BORDER_CONSTANT 0 /* cv::BORDER_CONSTANT */
+typedef struct adf_rectify_params { double fx, fy, cx, cy; double dist[8]; double ir[9]; } adf_rectify_params;
+int adf_rectify_params_init(const double K[9], const double* dist, int n_dist, const double* R /* 9, NULL = I */,
+                            const double* P /* 9 or 12 */, int p_cols /* 3 or 4 */, adf_rectify_params* out);
+int adf_init_undistort_rectify_map_device(const adf_rectify_params* prm, int W, int H, float* mapx, ptrdiff_t mapx_stride,
+                                          float* mapy, ptrdiff_t mapy_stride, void* stream);
+int adf_init_undistort_rectify_map_host(const adf_rectify_params* prm, int W, int H, float* mapx, ptrdiff_t mapx_stride,
+                                        float* mapy, ptrdiff_t mapy_stride);
+int adf_remap_device(int n_images, const uint8_t* src, ptrdiff_t src_stride, ptrdiff_t src_image_stride, int srcW, int srcH,
+                     int channels, const float* mapx, ptrdiff_t mapx_stride, const float* mapy, ptrdiff_t mapy_stride,
+                     uint8_t* dst, ptrdiff_t dst_stride, ptrdiff_t dst_image_stride, int W, int H, int interpolation,
+                     int border_mode, const uint8_t* border_value /* 3 */, void* stream);
+int adf_remap_host(int n_images, const uint8_t* src, ptrdiff_t src_stride, ptrdiff_t src_image_stride, int srcW, int srcH,
+                   int channels, const float* mapx, ptrdiff_t mapx_stride, const float* mapy, ptrdiff_t mapy_stride,
+                   uint8_t* dst, ptrdiff_t dst_stride, ptrdiff_t dst_image_stride, int W, int H, int interpolation,
+                   int border_mode, const uint8_t* border_value /* 3 */);
+int adf_rectify_views_device(int n_images, const uint8_t* src, ptrdiff_t src_stride, ptrdiff_t src_image_stride, int srcW,
+                             int srcH, int channels, const adf_rectify_params* prm, uint8_t* dst, ptrdiff_t dst_stride,
+                             ptrdiff_t dst_image_stride, int W, int H, int interpolation, int border_mode,
+                             const uint8_t* border_value /* 3 */, void* stream);
+int adf_rectify_views_host(int n_images, const uint8_t* src, ptrdiff_t src_stride, ptrdiff_t src_image_stride, int srcW,
+                           int srcH, int channels, const adf_rectify_params* prm, uint8_t* dst, ptrdiff_t dst_stride,
+                           ptrdiff_t dst_image_stride, int W, int H, int interpolation, int border_mode,
+                           const uint8_t* border_value /* 3 */);
+
 #ifdef __cplusplus
 }
 #endif

@@ -250,6 +250,135 @@ inline size_t pointCloud(const Mat& disparity, const Mat& Q, std::vector<float>&
     return count;
 }
 
+// cv::initUndistortRectifyMap(cameraMatrix, distCoeffs, R, newCameraMatrix, size, m1type, map1, map2) of calib3d and
+// cv::remap(src, dst, map1, map2, interpolation, borderMode, borderValue) of imgproc (outside the reference tree; parity
+// unpinned) on host Mats through the library's host entries, and rectifyViews, both in one launch without the maps:
+// definition and limits are adf_rectify_params_init / adf_init_undistort_rectify_map_* / adf_remap_* /
+// adf_rectify_views_* in adf_wls.h.  cameraMatrix, R, newCameraMatrix: CV_64F, 3x3 (newCameraMatrix also 3x4: P1 / P2 of
+// stereoRectify); R and newCameraMatrix may be empty (identity / cameraMatrix).  distCoeffs: empty or a CV_64F vector of 4, 5
+// or 8.  m1type: CV_32FC1 only.  Images: CV_8UC1 / CV_8UC3; INTER_LINEAR with BORDER_CONSTANT only.  borderValue is
+// templated like dsize above (cv::Scalar, or the stand-in below): its first three entries are the channels' fill.
+#ifndef ADF_HAVE_OPENCV
+struct Scalar {
+    double val[4] = {0, 0, 0, 0};
+    Scalar() {}
+    Scalar(double v0, double v1 = 0, double v2 = 0, double v3 = 0) { val[0] = v0; val[1] = v1; val[2] = v2; val[3] = v3; }
+    double operator[](int i) const { return val[i]; }
+};
+#endif
+enum { BORDER_CONSTANT = 0, M32FC1 = 5 /* CV_32FC1 */ }; // cv's values
+
+inline const double* rectify_matrix(const char* who, const char* name, const Mat& m, bool may_be_empty, bool or_3x4, double* copy)
+{
+    if (m.empty() && may_be_empty) return nullptr;
+    if (m.empty() || mat_depth(m) != D64F || mat_channels(m) != 1 || m.rows != 3 || !(m.cols == 3 || (or_3x4 && m.cols == 4)))
+        throw Exception(ADF_EBADARG, std::string(who) + ": " + name + " must be a CV_64F 3x3" + (or_3x4 ? " or 3x4" : "") + " matrix");
+    for (int r = 0; r < 3; r++) std::memcpy(copy + r * m.cols, m.data + (size_t)mat_step(m) * r, sizeof(double) * m.cols);
+    return copy;
+}
+
+inline adf_rectify_params rectify_params(const char* who, const Mat& cameraMatrix, const Mat& distCoeffs, const Mat& R, const Mat& newCameraMatrix)
+{
+    double K[9], Rm[9], P[12], dist[14];
+    rectify_matrix(who, "cameraMatrix", cameraMatrix, false, false, K);
+    const double* r = rectify_matrix(who, "R", R, true, false, Rm);
+    const double* p = rectify_matrix(who, "newCameraMatrix", newCameraMatrix, true, true, P);
+    int n_dist = 0;
+    if (!distCoeffs.empty()) {
+        if (mat_depth(distCoeffs) != D64F || mat_channels(distCoeffs) != 1 || (distCoeffs.rows != 1 && distCoeffs.cols != 1) ||
+            distCoeffs.rows * distCoeffs.cols > 14)
+            throw Exception(ADF_EBADARG, std::string(who) + ": distCoeffs must be a CV_64F vector of 4, 5 or 8 coefficients");
+        n_dist = distCoeffs.rows * distCoeffs.cols;
+        for (int i = 0; i < n_dist; i++)
+            dist[i] = distCoeffs.rows == 1 ? reinterpret_cast<const double*>(distCoeffs.data)[i]
+                                           : *reinterpret_cast<const double*>(distCoeffs.data + (size_t)mat_step(distCoeffs) * i);
+    }
+    adf_rectify_params prm;
+    check(adf_rectify_params_init(K, dist, n_dist, r, p ? p : K, p ? newCameraMatrix.cols : 3, &prm));
+    return prm;
+}
+
+template <class SizeT>
+inline void initUndistortRectifyMap(const Mat& cameraMatrix, const Mat& distCoeffs, const Mat& R, const Mat& newCameraMatrix,
+                                    SizeT size, int m1type, Mat& map1, Mat& map2)
+{
+    if (m1type != M32FC1) throw Exception(ADF_EBADARG, "initUndistortRectifyMap: m1type must be CV_32FC1 (the CV_16SC2 pair is not built)");
+    if (size.width < 1 || size.height < 1) throw Exception(ADF_EBADARG, "initUndistortRectifyMap: the size is empty");
+    const adf_rectify_params prm = rectify_params("initUndistortRectifyMap", cameraMatrix, distCoeffs, R, newCameraMatrix);
+    Mat mx, my;
+    mat_create(mx, size.height, size.width, D32F, 1);
+    mat_create(my, size.height, size.width, D32F, 1);
+    check(adf_init_undistort_rectify_map_host(&prm, size.width, size.height, reinterpret_cast<float*>(mx.data), mat_step(mx),
+                                              reinterpret_cast<float*>(my.data), mat_step(my)));
+    map1 = mx;
+    map2 = my;
+}
+
+template <class ScalarT> inline void border_bytes(const char* who, const ScalarT& v, uint8_t* b)
+{
+    for (int c = 0; c < 3; c++) {
+        const double d = v[c];
+        if (!(d >= 0.0 && d <= 255.0) || d != std::floor(d)) throw Exception(ADF_EBADARG, std::string(who) + ": borderValue must hold integers in [0, 255]");
+        b[c] = (uint8_t)d;
+    }
+}
+
+inline void rectify_source(const char* who, const Mat& src)
+{
+    if (src.empty() || mat_depth(src) != D8U || (mat_channels(src) != 1 && mat_channels(src) != 3))
+        throw Exception(ADF_EBADARG, std::string(who) + ": src must be a non-empty CV_8UC1 or CV_8UC3 image");
+}
+
+template <class ScalarT>
+inline void remap(const Mat& src, Mat& dst, const Mat& map1, const Mat& map2, int interpolation, int borderMode, const ScalarT& borderValue)
+{
+    rectify_source("remap", src);
+    if (map1.empty() || map2.empty() || mat_depth(map1) != D32F || mat_depth(map2) != D32F || mat_channels(map1) != 1 ||
+        mat_channels(map2) != 1 || map1.rows != map2.rows || map1.cols != map2.cols)
+        throw Exception(ADF_EBADARG, "remap: map1 and map2 must be two CV_32FC1 planes of one size");
+    uint8_t b[3];
+    border_bytes("remap", borderValue, b);
+    Mat out;
+    mat_create(out, map1.rows, map1.cols, D8U, mat_channels(src));
+    check(adf_remap_host(1, src.data, mat_step(src), 0, src.cols, src.rows, mat_channels(src), reinterpret_cast<const float*>(map1.data),
+                         mat_step(map1), reinterpret_cast<const float*>(map2.data), mat_step(map2), out.data, mat_step(out), 0,
+                         map1.cols, map1.rows, interpolation, borderMode, b));
+    dst = out;
+}
+
+inline void remap(const Mat& src, Mat& dst, const Mat& map1, const Mat& map2, int interpolation = INTER_LINEAR, int borderMode = BORDER_CONSTANT)
+{
+    const double zero[3] = {0, 0, 0};
+    remap(src, dst, map1, map2, interpolation, borderMode, zero);
+}
+
+// Extension: remap(src, dst, <the maps of initUndistortRectifyMap(...)>) in one launch, bit for bit, without the maps.
+// size with zero area = the source's size.
+template <class SizeT, class ScalarT>
+inline void rectifyViews(const Mat& src, Mat& dst, const Mat& cameraMatrix, const Mat& distCoeffs, const Mat& R, const Mat& newCameraMatrix,
+                         SizeT size, const ScalarT& borderValue)
+{
+    rectify_source("rectifyViews", src);
+    const int W = size.width == 0 && size.height == 0 ? src.cols : size.width, H = size.width == 0 && size.height == 0 ? src.rows : size.height;
+    if (W < 1 || H < 1) throw Exception(ADF_EBADARG, "rectifyViews: the size is empty");
+    const adf_rectify_params prm = rectify_params("rectifyViews", cameraMatrix, distCoeffs, R, newCameraMatrix);
+    uint8_t b[3];
+    border_bytes("rectifyViews", borderValue, b);
+    Mat out;
+    mat_create(out, H, W, D8U, mat_channels(src));
+    check(adf_rectify_views_host(1, src.data, mat_step(src), 0, src.cols, src.rows, mat_channels(src), &prm, out.data, mat_step(out), 0,
+                                 W, H, ADF_INTER_LINEAR, ADF_BORDER_CONSTANT, b));
+    dst = out;
+}
+
+template <class SizeT>
+inline void rectifyViews(const Mat& src, Mat& dst, const Mat& cameraMatrix, const Mat& distCoeffs, const Mat& R, const Mat& newCameraMatrix,
+                         SizeT size)
+{
+    const double zero[3] = {0, 0, 0};
+    rectifyViews(src, dst, cameraMatrix, distCoeffs, R, newCameraMatrix, size, zero);
+}
+
 namespace ximgproc {
 
 // DF.hpp:52-76
