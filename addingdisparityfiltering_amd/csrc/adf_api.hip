@@ -826,8 +826,8 @@ static int wls_filter_scaled_device(adf_wls_t* h, int n_pairs,
     s.fuse_lo = conf && h->scaled_fuse && h->solver == ADF_SOLVER_WAVE && wave_fits(ghi) &&
                 wave_hpass_can_fuse_lo(first_pass_probe(lo_fuse(h, s, 0, ghi), ghi.rw));
     // scratch: resized disparity (int16, view size; not with fuse_lo) + low-resolution cL, cR, conf (float)
-    s.dhi_bytes = s.fuse_lo ? 0 : (hi * 2 + 255) / 256 * 256;
-    const size_t maps_bytes = ((size_t)n_pairs * (s.dhi_bytes + (conf ? 3 * lo * sizeof(float) : 0)) + 255) / 256 * 256;
+    s.dhi_bytes = s.fuse_lo ? 0 : pad_to(hi * 2, 256);
+    const size_t maps_bytes = pad_to((size_t)n_pairs * (s.dhi_bytes + (conf ? 3 * lo * sizeof(float) : 0)), 256);
     const size_t need = maps_bytes + (s.fuse_lo ? 2 * ((size_t)rhi.width + 4) * sizeof(float) : 0);   // + the columns' taps
     if ((rc = h->scaled.reserve(need, st, FILL_ZERO))) return rc;
     s.dhi = (char*)h->scaled.p;
@@ -860,7 +860,7 @@ static int wls_filter_scaled_host(adf_wls_t* h, int n_pairs,
     // dense device copies: [dispL | dispR | out | view] per batch
     const size_t orow = (size_t)W * om.esz();
     const size_t dbytes = (size_t)dW * dH * 2, obytes = orow * H, gbytes = (size_t)W * H * gch;
-    const size_t dpad = (dbytes + 255) / 256 * 256, opad = (obytes + 255) / 256 * 256, gpad = (gbytes + 255) / 256 * 256;
+    const size_t dpad = pad_to(dbytes, 256), opad = pad_to(obytes, 256), gpad = pad_to(gbytes, 256);
     const size_t need = (size_t)n_pairs * (2 * dpad + opad + gpad);
     int rc = h->stage.reserve(need, st, FILL_ZERO);
     if (rc) return rc;

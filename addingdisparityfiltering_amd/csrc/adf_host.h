@@ -1,11 +1,14 @@
 // adf_host.h -- the host toolkit every C-ABI source shares (adf_host.hip): error returns, the device scope, device
-// memory (growable buffers, the process-wide block cache, scratch taken from it), the weight tables and the image
-// copies of the host-pointer entry points.  Host code only; what kernels and host code share is adf_internal.h.
+// memory (growable buffers, the process-wide block cache, scratch taken from it), the weight tables, the image copies
+// of the host-pointer entry points, and what the stateless operators' launches share: the launch check, rounding up,
+// THE batch loop over the grid limit, the rule for destination images that must not overlap, and the choice between a
+// caller's workspace and library scratch.  Host code only; what kernels and host code share is adf_internal.h.
 #pragma once
 
 #include "adf_internal.h"
 #include "../../include/adf_wls.h"
 
+#include <algorithm>
 #include <memory>
 #include <vector>
 
@@ -34,6 +37,24 @@ struct DeviceScope {
 };
 
 bool stream_is_capturing(hipStream_t st);
+
+#define ADF_LOCAL __attribute__((visibility("hidden")))   // shared by the library's sources, not a dynamic symbol
+ADF_LOCAL int launched();                      // after a call's launches: ADF_OK, or ADF_EHIP with the runtime's message
+constexpr size_t pad_to(size_t v, size_t a) { return (v + a - 1) / a * a; }   // v rounded up to a multiple of a
+
+// THE loop over a batch that one grid dimension cannot hold: f(m0, nm) launches images [m0, m0 + nm), nm <= per_launch,
+// re-pointing whatever it addresses per image by m0; the first non-zero return ends the loop and is returned.
+constexpr int GRID_LIMIT = 65535;              // what a grid holds along y or z: the images of one launch
+template <class F> int for_batches(int n, int per_launch, F&& f)
+{
+    for (int m0 = 0, nm; m0 < n; m0 += nm)
+        if (int rc = f(m0, nm = std::min(n - m0, per_launch))) return rc;
+    return ADF_OK;
+}
+
+// n images of `rows` rows of `row_bytes` (rows `stride`, images `image_stride` bytes apart) stay clear of one another:
+// they follow one another or, where the operator allows it, interleave row by row.
+ADF_LOCAL bool images_disjoint(int n, ptrdiff_t row_bytes, int rows, ptrdiff_t stride, ptrdiff_t image_stride, bool may_interleave);
 
 // Growable device buffer (never shrinks; freed with the handle).  Growing drains `st` before the old block is freed.
 // FILL_ZERO clears a newly allocated block on `st` (the filters: the sweeps read, and discard, pitch padding);
@@ -65,6 +86,11 @@ struct Scratch {
     int take(size_t need, hipStream_t stream);
     ~Scratch() { if (p) cache_give(device, p, bytes, st); }
 };
+
+// *ws = the caller's workspace of a `who` call when there is one (refused when smaller than `need`, the result of
+// `size_fn`, or not 4-byte aligned), else library scratch in `blk` ordered into `st` (refused inside a stream capture).
+ADF_LOCAL int workspace_or_scratch(const char* who, const char* size_fn, void* workspace, size_t workspace_bytes, size_t need,
+                                   hipStream_t st, Scratch& blk, void** ws);
 
 // The weight tables of one handle (FGS.cpp:150-154, 663-675): up to LUT_CACHE sigmas, each an immutable device table
 // shared with every handle of the process on the same device (adf_host.hip: LutStore).

@@ -47,11 +47,23 @@ bool adf::stream_is_capturing(hipStream_t st)
     return cs != hipStreamCaptureStatusNone;
 }
 
+int adf::launched()
+{
+    const hipError_t e = hipGetLastError();
+    return e != hipSuccess ? fail(ADF_EHIP, "%s", hipGetErrorString(e)) : ADF_OK;
+}
+
+bool adf::images_disjoint(int n, ptrdiff_t row_bytes, int rows, ptrdiff_t stride, ptrdiff_t image_stride, bool may_interleave)
+{
+    if (n < 2 || image_stride >= stride * (rows - 1) + row_bytes) return true;          // one image, or one after another
+    return may_interleave && image_stride >= row_bytes && image_stride * (n - 1) + row_bytes <= stride;
+}
+
 int adf::DevBuf::reserve(size_t need, hipStream_t st, Fill fill)
 {
     if (need <= bytes) return ADF_OK;
     if (p) { HIP_TRY(hipStreamSynchronize(st)); HIP_TRY(hipFree(p)); p = nullptr; bytes = 0; }
-    need = (need + 255) / 256 * 256;
+    need = pad_to(need, 256);
     HIP_TRY(device_malloc(&p, need));
     bytes = need;
     if (fill == FILL_ZERO) HIP_TRY(hipMemsetAsync(p, 0, need, st));
@@ -278,6 +290,21 @@ int Scratch::take(size_t need, hipStream_t stream)
     HIP_TRY(device_malloc(&p, need));
     bytes = need;
     return ADF_OK;
+}
+
+int workspace_or_scratch(const char* who, const char* size_fn, void* workspace, size_t workspace_bytes, size_t need,
+                         hipStream_t st, Scratch& blk, void** ws)
+{
+    *ws = workspace;
+    if (workspace) {
+        if (workspace_bytes < need) return fail(ADF_ESIZE, "%s: workspace smaller than %s", who, size_fn);
+        return (uintptr_t)workspace & 3 ? fail(ADF_EBADARG, "%s: workspace must be 4-byte aligned", who) : ADF_OK;
+    }
+    // library scratch: a block of the process-wide cache, ordered behind its last user's event (no host wait)
+    if (stream_is_capturing(st)) return fail(ADF_EBADARG, "%s: a call captured into a graph needs a caller workspace", who);
+    const int rc = blk.take(need, st);
+    *ws = blk.p;
+    return rc;
 }
 
 int copy_images(void* dst, size_t dst_pitch, ptrdiff_t dst_image_stride, const void* src, size_t src_pitch,

@@ -649,9 +649,7 @@ static int bm_compute_impl(adf_bm_t* h, int n_pairs,
         hipError_t e = launch_match_for(a, census, h->uniq > 0, w2, n_pairs, st);
         if (e != hipSuccess) return fail(ADF_EHIP, "%s", hipGetErrorString(e));
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(ADF_EHIP, "%s", hipGetErrorString(e));
-    return ADF_OK;
+    return launched();
 }
 
 extern "C" int adf_bm_compute_device(adf_bm_t* h, int n_pairs,

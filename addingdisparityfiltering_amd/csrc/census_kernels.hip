@@ -16,8 +16,6 @@
 // bits are zero.  One uint64 per pixel.
 #include "census.h"
 
-#include <algorithm>
-
 using namespace adf;
 
 namespace {
@@ -76,18 +74,13 @@ int adf::census_check(int census_type, int k)
 int adf::census_run(int n, const uint8_t* src, ptrdiff_t sstride, ptrdiff_t simage, int W, int H, int census_type, int k,
                     uint64_t* dst, ptrdiff_t dstride, ptrdiff_t dimage, hipStream_t st)
 {
-    constexpr int MAX_GRID_Z = 65535;
-    for (int m0 = 0; m0 < n; m0 += MAX_GRID_Z) {
-        const int nm = std::min(n - m0, MAX_GRID_Z);
+    return for_batches(n, GRID_LIMIT, [&](int m0, int nm) {
         const CensusArgs a{src + (ptrdiff_t)m0 * simage, sstride, n > 1 ? simage : 0,
                            reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(dst) + (ptrdiff_t)m0 * dimage), dstride, n > 1 ? dimage : 0, W, H};
         const dim3 grid((W + CENSUS_TILE_W - 1) / CENSUS_TILE_W, (H + CENSUS_TILE_H - 1) / CENSUS_TILE_H, nm);
         const bool known = census_dispatch(census_type, k, [&](auto s) { hipLaunchKernelGGL((census_kernel<decltype(s)>), grid, dim3(CENSUS_THREADS), 0, st, a); });
-        if (!known) return fail(ADF_EBADARG, "census size %d is not supported", k);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(ADF_EHIP, "%s", hipGetErrorString(e));
-    }
-    return ADF_OK;
+        return known ? launched() : fail(ADF_EBADARG, "census size %d is not supported", k);
+    });
 }
 
 // ----------------------------------------------------------------------------------------------

@@ -50,7 +50,6 @@ namespace {
 constexpr int NT = 256;
 constexpr int PX = 4;                  // destination pixels per thread
 constexpr int IMAGES = 4;              // images of a batch that share one evaluation of the coordinates
-constexpr int MAX_GRID_Y = 65535;
 constexpr int MAX_SRC_DIM = 32767;     // ix + 1 and iy + 1 stay inside the 16 bits sx >> 5 leaves
 
 // THE coordinate arithmetic (include/adf_wls.h); ry = {ir1*v, ir4*v, ir7*v} of the pixel's row
@@ -282,121 +281,123 @@ template <int CH, bool FUSED> __global__ void __launch_bounds__(NT) sample_kerne
 // host side
 // ---------------------------------------------------------------------------------------------------------
 const char* const IM = "initUndistortRectifyMap";
+const char* const RM = "remap";
+const char* const RV = "rectifyViews";
 
-int launched(void)
+struct MapCall {                       // one adf_init_undistort_rectify_map_* call as its C entry point received it
+    const adf_rectify_params* prm; int W, H;
+    float* mapx; ptrdiff_t xstride; float* mapy; ptrdiff_t ystride;
+};
+
+// base and strides of both map planes are multiples of `align`
+bool maps_aligned(const float* mapx, ptrdiff_t xstride, const float* mapy, ptrdiff_t ystride, int align)
 {
-    const hipError_t e = hipGetLastError();
-    return e != hipSuccess ? fail(ADF_EHIP, "%s", hipGetErrorString(e)) : ADF_OK;
+    return (((uintptr_t)mapx | (uintptr_t)xstride | (uintptr_t)mapy | (uintptr_t)ystride) & (uintptr_t)(align - 1)) == 0;
 }
 
-size_t round16(size_t v) { return (v + 15) / 16 * 16; }
-
-int map_check(const adf_rectify_params* prm, int W, int H, const float* mapx, ptrdiff_t xstride, const float* mapy, ptrdiff_t ystride)
+int map_check(const MapCall& c)
 {
-    if (!prm) return fail(ADF_EBADARG, "%s: prm must not be null", IM);
-    if (W < 1 || H < 1) return fail(ADF_EBADARG, "%s: the size is empty", IM);
-    if (!mapx || !mapy) return fail(ADF_EBADARG, "%s: mapx and mapy must not be null", IM);
-    if ((int64_t)W * H >= ((int64_t)1 << 31)) return fail(ADF_ESIZE, "%s: W*H must be below 2^31", IM);
-    if (((uintptr_t)mapx | (uintptr_t)xstride | (uintptr_t)mapy | (uintptr_t)ystride) & 3)
+    if (!c.prm) return fail(ADF_EBADARG, "%s: prm must not be null", IM);
+    if (c.W < 1 || c.H < 1) return fail(ADF_EBADARG, "%s: the size is empty", IM);
+    if (!c.mapx || !c.mapy) return fail(ADF_EBADARG, "%s: mapx and mapy must not be null", IM);
+    if ((int64_t)c.W * c.H >= ((int64_t)1 << 31)) return fail(ADF_ESIZE, "%s: W*H must be below 2^31", IM);
+    if (!maps_aligned(c.mapx, c.xstride, c.mapy, c.ystride, 4))
         return fail(ADF_EBADARG, "%s: the maps and their strides must be 4-byte aligned", IM);
-    if (xstride < (ptrdiff_t)W * 4 || ystride < (ptrdiff_t)W * 4) return fail(ADF_ESIZE, "%s: row stride smaller than a row", IM);
+    if (c.xstride < (ptrdiff_t)c.W * 4 || c.ystride < (ptrdiff_t)c.W * 4) return fail(ADF_ESIZE, "%s: row stride smaller than a row", IM);
     return ADF_OK;
 }
 
-int map_launch(const adf_rectify_params* prm, int W, int H, float* mapx, ptrdiff_t xstride, float* mapy, ptrdiff_t ystride, hipStream_t st)
+int map_launch(const MapCall& c, hipStream_t st)
 {
     MapArgs a;
-    a.mapx = reinterpret_cast<char*>(mapx); a.xstride = xstride;
-    a.mapy = reinterpret_cast<char*>(mapy); a.ystride = ystride;
-    a.W = W; a.H = H;
-    a.groups = (W + PX - 1) / PX;
-    a.total = (int)((int64_t)a.groups * H);                          // (W * H < 2^31)
-    a.vec = (((uintptr_t)mapx | (uintptr_t)xstride | (uintptr_t)mapy | (uintptr_t)ystride) & 15) == 0;
-    a.p = *prm;
+    a.mapx = reinterpret_cast<char*>(c.mapx); a.xstride = c.xstride;
+    a.mapy = reinterpret_cast<char*>(c.mapy); a.ystride = c.ystride;
+    a.W = c.W; a.H = c.H;
+    a.groups = (c.W + PX - 1) / PX;
+    a.total = (int)((int64_t)a.groups * c.H);                        // (W * H < 2^31)
+    a.vec = maps_aligned(c.mapx, c.xstride, c.mapy, c.ystride, 16);
+    a.p = *c.prm;
     hipLaunchKernelGGL(rectify_map_kernel, dim3((unsigned)(((int64_t)a.total + NT - 1) / NT)), dim3(NT), 0, st, a);
     return launched();
 }
 
-// Everything about a sampling call that can be refused without a device (`who`: remap or rectifyViews).
-int sample_check(const char* who, int n, const uint8_t* src, ptrdiff_t sstride, ptrdiff_t simage, int srcW, int srcH, int ch,
-                 const uint8_t* dst, ptrdiff_t dstride, ptrdiff_t dimage, int W, int H, int interpolation, int border_mode)
+// One sampling call as its C entry point received it.  remap has the maps and no prm, rectifyViews prm and no maps.
+struct SampleCall {
+    const char* who; int n;
+    const uint8_t* src; ptrdiff_t sstride, simage; int srcW, srcH, ch;
+    const float* mapx; ptrdiff_t xstride; const float* mapy; ptrdiff_t ystride; const adf_rectify_params* prm;
+    uint8_t* dst; ptrdiff_t dstride, dimage; int W, H, interpolation, border_mode; const uint8_t* border;
+};
+
+// Everything about a sampling call that can be refused without a device, but for its maps or its prm.
+int sample_check(const SampleCall& c)
 {
-    if (n < 1) return fail(ADF_EBADARG, "%s: n_images must be at least 1", who);
-    if (!src || !dst) return fail(ADF_EBADARG, "%s: src and dst must not be null", who);
-    if (srcW < 1 || srcH < 1 || W < 1 || H < 1) return fail(ADF_EBADARG, "%s: the source or the destination image is empty", who);
-    if (ch != 1 && ch != 3) return fail(ADF_EBADARG, "%s: images must be CV_8UC1 or CV_8UC3", who);
-    if (interpolation != ADF_INTER_LINEAR || border_mode != ADF_BORDER_CONSTANT)
-        return fail(ADF_EBADARG, "%s: INTER_LINEAR with BORDER_CONSTANT only", who);
-    if (srcW > MAX_SRC_DIM || srcH > MAX_SRC_DIM) return fail(ADF_ESIZE, "%s: srcW and srcH must not exceed 32767", who);
-    if ((int64_t)W * H >= ((int64_t)1 << 31)) return fail(ADF_ESIZE, "%s: W*H must be below 2^31", who);
-    if (sstride < (ptrdiff_t)srcW * ch || dstride < (ptrdiff_t)W * ch) return fail(ADF_ESIZE, "%s: row stride smaller than a row", who);
-    if (n > 1) {
-        if (simage < 0) return fail(ADF_EBADARG, "%s: negative image stride", who);
-        // destination images either follow one another or interleave row by row
-        const ptrdiff_t drow = (ptrdiff_t)W * ch;
-        const bool stacked = dimage >= dstride * (H - 1) + drow;
-        const bool interleaved = dimage >= drow && dimage * (n - 1) + drow <= dstride;
-        if (!stacked && !interleaved) return fail(ADF_EBADARG, "%s: destination images overlap", who);
-    }
+    if (c.n < 1) return fail(ADF_EBADARG, "%s: n_images must be at least 1", c.who);
+    if (!c.src || !c.dst) return fail(ADF_EBADARG, "%s: src and dst must not be null", c.who);
+    if (c.srcW < 1 || c.srcH < 1 || c.W < 1 || c.H < 1) return fail(ADF_EBADARG, "%s: the source or the destination image is empty", c.who);
+    if (c.ch != 1 && c.ch != 3) return fail(ADF_EBADARG, "%s: images must be CV_8UC1 or CV_8UC3", c.who);
+    if (c.interpolation != ADF_INTER_LINEAR || c.border_mode != ADF_BORDER_CONSTANT)
+        return fail(ADF_EBADARG, "%s: INTER_LINEAR with BORDER_CONSTANT only", c.who);
+    if (c.srcW > MAX_SRC_DIM || c.srcH > MAX_SRC_DIM) return fail(ADF_ESIZE, "%s: srcW and srcH must not exceed 32767", c.who);
+    if ((int64_t)c.W * c.H >= ((int64_t)1 << 31)) return fail(ADF_ESIZE, "%s: W*H must be below 2^31", c.who);
+    if (c.sstride < (ptrdiff_t)c.srcW * c.ch || c.dstride < (ptrdiff_t)c.W * c.ch) return fail(ADF_ESIZE, "%s: row stride smaller than a row", c.who);
+    if (c.n > 1 && c.simage < 0) return fail(ADF_EBADARG, "%s: negative image stride", c.who);
+    if (!images_disjoint(c.n, (ptrdiff_t)c.W * c.ch, c.H, c.dstride, c.dimage, true))
+        return fail(ADF_EBADARG, "%s: destination images overlap", c.who);
     return ADF_OK;
 }
 
-int maps_check(const float* mapx, ptrdiff_t xstride, const float* mapy, ptrdiff_t ystride, int W)
+int remap_check(const SampleCall& c)
 {
-    if (!mapx || !mapy) return fail(ADF_EBADARG, "remap: mapx and mapy must not be null");
-    if (((uintptr_t)mapx | (uintptr_t)xstride | (uintptr_t)mapy | (uintptr_t)ystride) & 3)
+    if (const int rc = sample_check(c)) return rc;
+    if (!c.mapx || !c.mapy) return fail(ADF_EBADARG, "remap: mapx and mapy must not be null");
+    if (!maps_aligned(c.mapx, c.xstride, c.mapy, c.ystride, 4))
         return fail(ADF_EBADARG, "remap: the maps and their strides must be 4-byte aligned");
-    if (xstride < (ptrdiff_t)W * 4 || ystride < (ptrdiff_t)W * 4) return fail(ADF_ESIZE, "remap: map row stride smaller than a row");
+    if (c.xstride < (ptrdiff_t)c.W * 4 || c.ystride < (ptrdiff_t)c.W * 4) return fail(ADF_ESIZE, "remap: map row stride smaller than a row");
     return ADF_OK;
 }
 
-// maps != null: remap; prm != null: rectifyViews
-int sample_launch(int n, const uint8_t* src, ptrdiff_t sstride, ptrdiff_t simage, int srcW, int srcH, int ch,
-                  const float* mapx, ptrdiff_t xstride, const float* mapy, ptrdiff_t ystride, const adf_rectify_params* prm,
-                  uint8_t* dst, ptrdiff_t dstride, ptrdiff_t dimage, int W, int H, const uint8_t* border, hipStream_t st)
+int rectify_views_check(const SampleCall& c)
+{
+    if (const int rc = sample_check(c)) return rc;
+    return c.prm ? ADF_OK : fail(ADF_EBADARG, "%s: prm must not be null", RV);
+}
+
+int sample_launch(const SampleCall& c, hipStream_t st)
 {
     SampleArgs a = {};
-    a.sstride = sstride; a.simage = n > 1 ? simage : 0;
-    a.srcW = srcW; a.srcH = srcH;
-    a.mapx = reinterpret_cast<const char*>(mapx); a.xstride = xstride;
-    a.mapy = reinterpret_cast<const char*>(mapy); a.ystride = ystride;
-    a.dstride = dstride; a.dimage = n > 1 ? dimage : 0;
-    a.W = W; a.H = H;
-    a.groups = (W + PX - 1) / PX;
-    a.total = (int)((int64_t)a.groups * H);                          // (W * H < 2^31)
-    a.vec_map = (((uintptr_t)mapx | (uintptr_t)xstride | (uintptr_t)mapy | (uintptr_t)ystride) & 15) == 0;
-    a.vec_dst = (((uintptr_t)dst | (uintptr_t)dstride | (uintptr_t)a.dimage) & 3) == 0;
-    for (int c = 0; c < 3; c++) a.border[c] = border ? border[c < ch ? c : 0] : 0;
-    if (prm) a.p = *prm;
+    a.sstride = c.sstride; a.simage = c.n > 1 ? c.simage : 0;
+    a.srcW = c.srcW; a.srcH = c.srcH;
+    a.mapx = reinterpret_cast<const char*>(c.mapx); a.xstride = c.xstride;
+    a.mapy = reinterpret_cast<const char*>(c.mapy); a.ystride = c.ystride;
+    a.dstride = c.dstride; a.dimage = c.n > 1 ? c.dimage : 0;
+    a.W = c.W; a.H = c.H;
+    a.groups = (c.W + PX - 1) / PX;
+    a.total = (int)((int64_t)a.groups * c.H);                        // (W * H < 2^31)
+    a.vec_map = maps_aligned(c.mapx, c.xstride, c.mapy, c.ystride, 16);
+    a.vec_dst = (((uintptr_t)c.dst | (uintptr_t)a.dstride | (uintptr_t)a.dimage) & 3) == 0;
+    for (int k = 0; k < 3; k++) a.border[k] = c.border ? c.border[k < c.ch ? k : 0] : 0;
+    if (c.prm) a.p = *c.prm;
     const unsigned blocks = (unsigned)(((int64_t)a.total + NT - 1) / NT);
-    constexpr int PER_LAUNCH = MAX_GRID_Y * IMAGES;
-    for (int m0 = 0; m0 < n; m0 += PER_LAUNCH) {
-        a.n = n - m0 < PER_LAUNCH ? n - m0 : PER_LAUNCH;
-        a.src = src + (ptrdiff_t)m0 * a.simage;
-        a.dst = dst + (ptrdiff_t)m0 * a.dimage;
-        const dim3 grid(blocks, (unsigned)((a.n + IMAGES - 1) / IMAGES));
-        if (prm) {
-            if (ch == 3) hipLaunchKernelGGL((sample_kernel<3, true>), grid, dim3(NT), 0, st, a);
-            else hipLaunchKernelGGL((sample_kernel<1, true>), grid, dim3(NT), 0, st, a);
-        } else {
-            if (ch == 3) hipLaunchKernelGGL((sample_kernel<3, false>), grid, dim3(NT), 0, st, a);
-            else hipLaunchKernelGGL((sample_kernel<1, false>), grid, dim3(NT), 0, st, a);
-        }
-        const int rc = launched();
-        if (rc) return rc;
-    }
-    return ADF_OK;
+    const auto kernel = c.prm ? (c.ch == 3 ? sample_kernel<3, true> : sample_kernel<1, true>)
+                              : (c.ch == 3 ? sample_kernel<3, false> : sample_kernel<1, false>);
+    return for_batches(c.n, GRID_LIMIT * IMAGES, [&](int m0, int nm) {
+        a.n = nm;
+        a.src = c.src + (ptrdiff_t)m0 * a.simage;
+        a.dst = c.dst + (ptrdiff_t)m0 * a.dimage;
+        hipLaunchKernelGGL(kernel, dim3(blocks, (unsigned)((nm + IMAGES - 1) / IMAGES)), dim3(NT), 0, st, a);
+        return launched();
+    });
 }
 
 // The _host form of both sampling calls: one block holds the source images, the maps (remap) and the destination
 // images, rows padded to 16 bytes.
-int sample_host(int n, const uint8_t* src, ptrdiff_t sstride, ptrdiff_t simage, int srcW, int srcH, int ch,
-                const float* mapx, ptrdiff_t xstride, const float* mapy, ptrdiff_t ystride, const adf_rectify_params* prm,
-                uint8_t* dst, ptrdiff_t dstride, ptrdiff_t dimage, int W, int H, const uint8_t* border)
+int sample_host(const SampleCall& c)
 {
-    const size_t srow = (size_t)srcW * ch, drow = (size_t)W * ch, mrow = (size_t)W * 4;
-    const size_t sp = round16(srow), dp = round16(drow), mp = round16(mrow);
-    const size_t simg = sp * srcH, dimg = dp * H, mplane = mapx ? mp * H : 0;
+    const int n = c.n;
+    const size_t srow = (size_t)c.srcW * c.ch, drow = (size_t)c.W * c.ch, mrow = (size_t)c.W * 4;
+    const size_t sp = pad_to(srow, 16), dp = pad_to(drow, 16), mp = pad_to(mrow, 16);
+    const size_t simg = sp * c.srcH, dimg = dp * c.H, mplane = c.mapx ? mp * c.H : 0;
     Scratch blk;
     int rc;
     if ((rc = blk.take((simg + dimg) * (size_t)n + 2 * mplane, nullptr))) return rc;
@@ -404,22 +405,21 @@ int sample_host(int n, const uint8_t* src, ptrdiff_t sstride, ptrdiff_t simage, 
     uint8_t* dd = ds + simg * n;
     float* dx = reinterpret_cast<float*>(dd + dimg * n);
     float* dy = reinterpret_cast<float*>(reinterpret_cast<char*>(dx) + mplane);
-    if ((rc = copy_images(ds, sp, simg, src, sstride, simage, srow, srcH, n, hipMemcpyHostToDevice, nullptr))) return rc;
-    if (mapx) {
-        if ((rc = copy_images(dx, mp, 0, mapx, xstride, 0, mrow, H, 1, hipMemcpyHostToDevice, nullptr))) return rc;
-        if ((rc = copy_images(dy, mp, 0, mapy, ystride, 0, mrow, H, 1, hipMemcpyHostToDevice, nullptr))) return rc;
+    SampleCall d = c;                                                // the same call on the staged copies
+    d.src = ds; d.sstride = (ptrdiff_t)sp; d.simage = (ptrdiff_t)simg;
+    d.dst = dd; d.dstride = (ptrdiff_t)dp; d.dimage = (ptrdiff_t)dimg;
+    if ((rc = copy_images(ds, sp, simg, c.src, c.sstride, c.simage, srow, c.srcH, n, hipMemcpyHostToDevice, nullptr))) return rc;
+    if (c.mapx) {
+        d.mapx = dx; d.mapy = dy; d.xstride = d.ystride = (ptrdiff_t)mp;
+        if ((rc = copy_images(dx, mp, 0, c.mapx, c.xstride, 0, mrow, c.H, 1, hipMemcpyHostToDevice, nullptr))) return rc;
+        if ((rc = copy_images(dy, mp, 0, c.mapy, c.ystride, 0, mrow, c.H, 1, hipMemcpyHostToDevice, nullptr))) return rc;
     }
-    rc = sample_launch(n, ds, (ptrdiff_t)sp, (ptrdiff_t)simg, srcW, srcH, ch, mapx ? dx : nullptr, (ptrdiff_t)mp, mapx ? dy : nullptr,
-                       (ptrdiff_t)mp, prm, dd, (ptrdiff_t)dp, (ptrdiff_t)dimg, W, H, border, nullptr);
-    if (rc) return rc;
+    if ((rc = sample_launch(d, nullptr))) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
-    if ((rc = copy_images(dst, dstride, dimage, dd, dp, dimg, drow, H, n, hipMemcpyDeviceToHost, nullptr))) return rc;
+    if ((rc = copy_images(c.dst, c.dstride, c.dimage, dd, dp, dimg, drow, c.H, n, hipMemcpyDeviceToHost, nullptr))) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
     return ADF_OK;
 }
-
-const char* const RM = "remap";
-const char* const RV = "rectifyViews";
 
 } // namespace
 
@@ -457,25 +457,27 @@ extern "C" int adf_rectify_params_init(const double K[9], const double* dist, in
 extern "C" int adf_init_undistort_rectify_map_device(const adf_rectify_params* prm, int W, int H, float* mapx, ptrdiff_t mapx_stride,
                                                      float* mapy, ptrdiff_t mapy_stride, void* stream)
 {
-    const int rc = map_check(prm, W, H, mapx, mapx_stride, mapy, mapy_stride);
-    if (rc) return rc;
-    return map_launch(prm, W, H, mapx, mapx_stride, mapy, mapy_stride, (hipStream_t)stream);
+    const MapCall c{prm, W, H, mapx, mapx_stride, mapy, mapy_stride};
+    const int rc = map_check(c);
+    return rc ? rc : map_launch(c, (hipStream_t)stream);
 }
 
 extern "C" int adf_init_undistort_rectify_map_host(const adf_rectify_params* prm, int W, int H, float* mapx, ptrdiff_t mapx_stride,
                                                    float* mapy, ptrdiff_t mapy_stride)
 {
-    int rc = map_check(prm, W, H, mapx, mapx_stride, mapy, mapy_stride);
+    const MapCall c{prm, W, H, mapx, mapx_stride, mapy, mapy_stride};
+    int rc = map_check(c);
     if (rc) return rc;
-    const size_t mrow = (size_t)W * 4, mp = round16(mrow), plane = mp * H;
+    const size_t mrow = (size_t)W * 4, mp = pad_to(mrow, 16), plane = mp * H;
     Scratch blk;
     if ((rc = blk.take(2 * plane, nullptr))) return rc;
-    float* dx = static_cast<float*>(blk.p);
-    float* dy = reinterpret_cast<float*>(static_cast<char*>(blk.p) + plane);
-    if ((rc = map_launch(prm, W, H, dx, (ptrdiff_t)mp, dy, (ptrdiff_t)mp, nullptr))) return rc;
+    MapCall d = c;                                                   // the same call into the staged planes
+    d.mapx = static_cast<float*>(blk.p); d.mapy = reinterpret_cast<float*>(static_cast<char*>(blk.p) + plane);
+    d.xstride = d.ystride = (ptrdiff_t)mp;
+    if ((rc = map_launch(d, nullptr))) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
-    if ((rc = copy_images(mapx, mapx_stride, 0, dx, mp, 0, mrow, H, 1, hipMemcpyDeviceToHost, nullptr))) return rc;
-    if ((rc = copy_images(mapy, mapy_stride, 0, dy, mp, 0, mrow, H, 1, hipMemcpyDeviceToHost, nullptr))) return rc;
+    if ((rc = copy_images(mapx, mapx_stride, 0, d.mapx, mp, 0, mrow, H, 1, hipMemcpyDeviceToHost, nullptr))) return rc;
+    if ((rc = copy_images(mapy, mapy_stride, 0, d.mapy, mp, 0, mrow, H, 1, hipMemcpyDeviceToHost, nullptr))) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
     return ADF_OK;
 }
@@ -485,11 +487,10 @@ extern "C" int adf_remap_device(int n_images, const uint8_t* src, ptrdiff_t src_
                                 uint8_t* dst, ptrdiff_t dst_stride, ptrdiff_t dst_image_stride, int W, int H, int interpolation,
                                 int border_mode, const uint8_t* border_value, void* stream)
 {
-    int rc = sample_check(RM, n_images, src, src_stride, src_image_stride, srcW, srcH, channels, dst, dst_stride, dst_image_stride,
-                          W, H, interpolation, border_mode);
-    if (rc || (rc = maps_check(mapx, mapx_stride, mapy, mapy_stride, W))) return rc;
-    return sample_launch(n_images, src, src_stride, src_image_stride, srcW, srcH, channels, mapx, mapx_stride, mapy, mapy_stride,
-                         nullptr, dst, dst_stride, dst_image_stride, W, H, border_value, (hipStream_t)stream);
+    const SampleCall c{RM, n_images, src, src_stride, src_image_stride, srcW, srcH, channels, mapx, mapx_stride, mapy, mapy_stride,
+                       nullptr, dst, dst_stride, dst_image_stride, W, H, interpolation, border_mode, border_value};
+    const int rc = remap_check(c);
+    return rc ? rc : sample_launch(c, (hipStream_t)stream);
 }
 
 extern "C" int adf_remap_host(int n_images, const uint8_t* src, ptrdiff_t src_stride, ptrdiff_t src_image_stride, int srcW, int srcH,
@@ -497,11 +498,10 @@ extern "C" int adf_remap_host(int n_images, const uint8_t* src, ptrdiff_t src_st
                               uint8_t* dst, ptrdiff_t dst_stride, ptrdiff_t dst_image_stride, int W, int H, int interpolation,
                               int border_mode, const uint8_t* border_value)
 {
-    int rc = sample_check(RM, n_images, src, src_stride, src_image_stride, srcW, srcH, channels, dst, dst_stride, dst_image_stride,
-                          W, H, interpolation, border_mode);
-    if (rc || (rc = maps_check(mapx, mapx_stride, mapy, mapy_stride, W))) return rc;
-    return sample_host(n_images, src, src_stride, src_image_stride, srcW, srcH, channels, mapx, mapx_stride, mapy, mapy_stride,
-                       nullptr, dst, dst_stride, dst_image_stride, W, H, border_value);
+    const SampleCall c{RM, n_images, src, src_stride, src_image_stride, srcW, srcH, channels, mapx, mapx_stride, mapy, mapy_stride,
+                       nullptr, dst, dst_stride, dst_image_stride, W, H, interpolation, border_mode, border_value};
+    const int rc = remap_check(c);
+    return rc ? rc : sample_host(c);
 }
 
 extern "C" int adf_rectify_views_device(int n_images, const uint8_t* src, ptrdiff_t src_stride, ptrdiff_t src_image_stride, int srcW,
@@ -509,12 +509,10 @@ extern "C" int adf_rectify_views_device(int n_images, const uint8_t* src, ptrdif
                                         ptrdiff_t dst_image_stride, int W, int H, int interpolation, int border_mode,
                                         const uint8_t* border_value, void* stream)
 {
-    const int rc = sample_check(RV, n_images, src, src_stride, src_image_stride, srcW, srcH, channels, dst, dst_stride,
-                                dst_image_stride, W, H, interpolation, border_mode);
-    if (rc) return rc;
-    if (!prm) return fail(ADF_EBADARG, "%s: prm must not be null", RV);
-    return sample_launch(n_images, src, src_stride, src_image_stride, srcW, srcH, channels, nullptr, 0, nullptr, 0, prm,
-                         dst, dst_stride, dst_image_stride, W, H, border_value, (hipStream_t)stream);
+    const SampleCall c{RV, n_images, src, src_stride, src_image_stride, srcW, srcH, channels, nullptr, 0, nullptr, 0,
+                       prm, dst, dst_stride, dst_image_stride, W, H, interpolation, border_mode, border_value};
+    const int rc = rectify_views_check(c);
+    return rc ? rc : sample_launch(c, (hipStream_t)stream);
 }
 
 extern "C" int adf_rectify_views_host(int n_images, const uint8_t* src, ptrdiff_t src_stride, ptrdiff_t src_image_stride, int srcW,
@@ -522,10 +520,8 @@ extern "C" int adf_rectify_views_host(int n_images, const uint8_t* src, ptrdiff_
                                       ptrdiff_t dst_image_stride, int W, int H, int interpolation, int border_mode,
                                       const uint8_t* border_value)
 {
-    const int rc = sample_check(RV, n_images, src, src_stride, src_image_stride, srcW, srcH, channels, dst, dst_stride,
-                                dst_image_stride, W, H, interpolation, border_mode);
-    if (rc) return rc;
-    if (!prm) return fail(ADF_EBADARG, "%s: prm must not be null", RV);
-    return sample_host(n_images, src, src_stride, src_image_stride, srcW, srcH, channels, nullptr, 0, nullptr, 0, prm,
-                       dst, dst_stride, dst_image_stride, W, H, border_value);
+    const SampleCall c{RV, n_images, src, src_stride, src_image_stride, srcW, srcH, channels, nullptr, 0, nullptr, 0,
+                       prm, dst, dst_stride, dst_image_stride, W, H, interpolation, border_mode, border_value};
+    const int rc = rectify_views_check(c);
+    return rc ? rc : sample_host(c);
 }

@@ -43,7 +43,6 @@ constexpr int PX = 4;                  // pixels per thread of the streaming ker
 constexpr int MIN_GROUPS = 32;         // groups of PX pixels per thread of the minimum kernel: 32768 pixels per workgroup
 constexpr int TILE = 1024;             // pixels per tile of the point list: TILE / NT rounds of one pixel per lane
 constexpr int ROUNDS = TILE / NT, SEGS = ROUNDS * (NT / 64);
-constexpr int MAX_GRID_Y = 65535;      // maps per launch (grid y)
 constexpr uint32_t KEY_NONE = 0xffffffffu;
 
 struct Geometry {                      // what every kernel needs to turn (x, y, s) into a point
@@ -369,74 +368,88 @@ template <class SRC> __global__ void __launch_bounds__(NT) cloud_write_kernel(Cl
 // ---------------------------------------------------------------------------------------------------------
 int esz_of(int depth) { return depth == ADF_16S ? 2 : 4; }
 
-// Everything about the source maps and the parameters that can be refused without a device.
-int source_check(const char* who, int n, const void* disp, int depth, ptrdiff_t stride, ptrdiff_t map_stride, int W, int H,
-                 const adf_reproject_params* prm)
-{
-    if (!disp || n < 1 || W < 1 || H < 1) return fail(ADF_EBADARG, "%s: the disparity map is empty", who);
-    if (!prm) return fail(ADF_EBADARG, "%s: prm must not be null", who);
-    if (depth != ADF_16S && depth != ADF_32F) return fail(ADF_EBADARG, "%s: disparity must be CV_16SC1 or CV_32FC1", who);
-    if (prm->missing_mode < ADF_MISSING_NONE || prm->missing_mode > ADF_MISSING_VALUE)
-        return fail(ADF_EBADARG, "%s: missing_mode must be ADF_MISSING_NONE, ADF_MISSING_MIN or ADF_MISSING_VALUE", who);
-    if (!std::isfinite(prm->disp_scale)) return fail(ADF_EBADARG, "%s: disp_scale must be finite", who);
-    if (prm->missing_mode == ADF_MISSING_VALUE && !std::isfinite(prm->missing_value))
-        return fail(ADF_EBADARG, "%s: missing_value must be finite", who);
-    if ((int64_t)W * H >= ((int64_t)1 << 31)) return fail(ADF_ESIZE, "%s: W*H must be below 2^31", who);
-    const int esz = esz_of(depth);
-    if (((uintptr_t)disp | (uintptr_t)stride | (n > 1 ? (uintptr_t)map_stride : 0)) & (uintptr_t)(esz - 1))
-        return fail(ADF_EBADARG, "%s: the disparity map and its strides must be aligned to its element size", who);
-    if (stride < (ptrdiff_t)W * esz) return fail(ADF_ESIZE, "%s: row stride smaller than a row", who);
-    return ADF_OK;
-}
-
 const char* const RP = "reprojectImageTo3D";
 const char* const PC = "pointCloud";
 
-int image_check(int n, const void* disp, int depth, ptrdiff_t stride, ptrdiff_t map_stride, int W, int H,
-                const adf_reproject_params* prm, const float* out, ptrdiff_t ostride, ptrdiff_t omap, int ch)
+struct SourceMaps {                    // the arguments both calls begin with
+    int n; const void* disp; int depth; ptrdiff_t stride, map_stride; int W, H;
+    const adf_reproject_params* prm;
+};
+
+struct ImageCall {                     // one adf_reproject_to_3d_* call as its C entry point received it
+    SourceMaps s;
+    float* out; ptrdiff_t ostride, omap; int ch;
+};
+
+struct CloudCall {                     // one adf_point_cloud_* call as its C entry point received it
+    SourceMaps s;
+    const adf_rect* roi_arg; double z_min, z_max;
+    const uint8_t* view; ptrdiff_t vstride, vmap; int vch;
+    float* points; ptrdiff_t pmap; uint8_t* colours; ptrdiff_t cmap; int32_t* index; ptrdiff_t imap;
+    int capacity; uint32_t* counts;
+    adf_rect roi; int tiles;           // what cloud_check derives: the ROI in force and its tiles
+};
+
+// bits of a base pointer and its strides (the map stride counts only in a batch) that break an alignment of `align`
+uintptr_t misaligned(int n, const void* p, ptrdiff_t stride, ptrdiff_t map_stride, int align)
 {
-    const int rc = source_check(RP, n, disp, depth, stride, map_stride, W, H, prm);
-    if (rc) return rc;
-    if (!out) return fail(ADF_EBADARG, "%s: out must not be null", RP);
-    if (ch != 1 && ch != 3) return fail(ADF_EBADARG, "%s: out_channels must be 3 (XYZ) or 1 (Z only)", RP);
-    if (((uintptr_t)out | (uintptr_t)ostride | (n > 1 ? (uintptr_t)omap : 0)) & 3)
-        return fail(ADF_EBADARG, "%s: out and its strides must be 4-byte aligned", RP);
-    if (ostride < (ptrdiff_t)W * ch * 4) return fail(ADF_ESIZE, "%s: output row stride smaller than a row", RP);
-    if (n > 1 && omap < ostride * (H - 1) + (ptrdiff_t)W * ch * 4)
+    return ((uintptr_t)p | (uintptr_t)stride | (n > 1 ? (uintptr_t)map_stride : 0)) & (uintptr_t)(align - 1);
+}
+
+// Everything about the source maps and the parameters that can be refused without a device.
+int source_check(const char* who, const SourceMaps& s)
+{
+    if (!s.disp || s.n < 1 || s.W < 1 || s.H < 1) return fail(ADF_EBADARG, "%s: the disparity map is empty", who);
+    if (!s.prm) return fail(ADF_EBADARG, "%s: prm must not be null", who);
+    if (s.depth != ADF_16S && s.depth != ADF_32F) return fail(ADF_EBADARG, "%s: disparity must be CV_16SC1 or CV_32FC1", who);
+    if (s.prm->missing_mode < ADF_MISSING_NONE || s.prm->missing_mode > ADF_MISSING_VALUE)
+        return fail(ADF_EBADARG, "%s: missing_mode must be ADF_MISSING_NONE, ADF_MISSING_MIN or ADF_MISSING_VALUE", who);
+    if (!std::isfinite(s.prm->disp_scale)) return fail(ADF_EBADARG, "%s: disp_scale must be finite", who);
+    if (s.prm->missing_mode == ADF_MISSING_VALUE && !std::isfinite(s.prm->missing_value))
+        return fail(ADF_EBADARG, "%s: missing_value must be finite", who);
+    if ((int64_t)s.W * s.H >= ((int64_t)1 << 31)) return fail(ADF_ESIZE, "%s: W*H must be below 2^31", who);
+    if (misaligned(s.n, s.disp, s.stride, s.map_stride, esz_of(s.depth)))
+        return fail(ADF_EBADARG, "%s: the disparity map and its strides must be aligned to its element size", who);
+    if (s.stride < (ptrdiff_t)s.W * esz_of(s.depth)) return fail(ADF_ESIZE, "%s: row stride smaller than a row", who);
+    return ADF_OK;
+}
+
+int image_check(const ImageCall& c)
+{
+    if (const int rc = source_check(RP, c.s)) return rc;
+    if (!c.out) return fail(ADF_EBADARG, "%s: out must not be null", RP);
+    if (c.ch != 1 && c.ch != 3) return fail(ADF_EBADARG, "%s: out_channels must be 3 (XYZ) or 1 (Z only)", RP);
+    if (misaligned(c.s.n, c.out, c.ostride, c.omap, 4)) return fail(ADF_EBADARG, "%s: out and its strides must be 4-byte aligned", RP);
+    if (c.ostride < (ptrdiff_t)c.s.W * c.ch * 4) return fail(ADF_ESIZE, "%s: output row stride smaller than a row", RP);
+    if (!images_disjoint(c.s.n, (ptrdiff_t)c.s.W * c.ch * 4, c.s.H, c.ostride, c.omap, false))
         return fail(ADF_ESIZE, "%s: output maps of the batch overlap (map stride smaller than a map)", RP);
     return ADF_OK;
 }
 
-void set_geometry(Geometry& g, const adf_reproject_params* prm, const uint32_t* min_key)
+void set_geometry(Geometry& g, const adf_reproject_params* prm)
 {
     for (int i = 0; i < 16; i++) g.Q[i] = prm->Q[i];
     g.scale = prm->disp_scale;
     g.missing = prm->missing_value;
     g.mode = prm->missing_mode;
-    g.min_key = min_key;
+    g.min_key = nullptr;
 }
 
-int launched(void)
-{
-    const hipError_t e = hipGetLastError();
-    return e != hipSuccess ? fail(ADF_EHIP, "%s", hipGetErrorString(e)) : ADF_OK;
-}
-
-// The source side of ImageArgs (smap: 0 for a single map): groups of PX pixels, and whether base and strides allow the
-// 8- / 16-byte loads of PX values.
-ImageArgs source_args(const void* disp, ptrdiff_t stride, ptrdiff_t smap, int W, int H, int esz)
+// The source side of ImageArgs for the maps from `disp` on (smap: 0 for a single map): groups of PX pixels, and whether
+// base and strides allow the 8- / 16-byte loads of PX values.
+ImageArgs source_args(const SourceMaps& s, const char* disp, ptrdiff_t smap)
 {
     ImageArgs a = {};
-    a.src = static_cast<const char*>(disp); a.sstride = stride; a.smap = smap;
-    a.W = W; a.H = H;
-    a.groups = (W + PX - 1) / PX;
-    a.total = (int)((int64_t)a.groups * H);                          // (W * H < 2^31)
-    a.vec_src = (((uintptr_t)disp | (uintptr_t)stride | (uintptr_t)smap) & (uintptr_t)(esz * PX - 1)) == 0;
+    a.src = disp; a.sstride = s.stride; a.smap = smap;
+    a.W = s.W; a.H = s.H;
+    a.groups = (s.W + PX - 1) / PX;
+    a.total = (int)((int64_t)a.groups * s.H);                        // (W * H < 2^31)
+    a.vec_src = (((uintptr_t)disp | (uintptr_t)s.stride | (uintptr_t)smap) & (uintptr_t)(esz_of(s.depth) * PX - 1)) == 0;
     return a;
 }
 
-// the minimum of maps [m0, m0 + nm) into slots[0 .. nm) (ADF_MISSING_MIN)
-template <class SRC> int min_run(ImageArgs a, unsigned nm, uint32_t* slots, hipStream_t st)
+// the minimum of the nm maps of `a` into slots[0 .. nm) (ADF_MISSING_MIN)
+template <class SRC> int min_run(const ImageArgs& a, unsigned nm, uint32_t* slots, hipStream_t st)
 {
     HIP_TRY(hipMemsetAsync(slots, 0xff, (size_t)nm * sizeof(uint32_t), st));
     const unsigned blocks = (unsigned)(((int64_t)a.total + NT * MIN_GROUPS - 1) / (NT * MIN_GROUPS));
@@ -444,131 +457,102 @@ template <class SRC> int min_run(ImageArgs a, unsigned nm, uint32_t* slots, hipS
     return launched();
 }
 
-template <class SRC>
-int image_run(int n, ImageArgs a, int ch, uint32_t* slots, hipStream_t st)
+// ws: the minimum slots (adf_reproject_workspace_bytes; read with ADF_MISSING_MIN only)
+template <class SRC> int image_launch(const ImageCall& c, void* ws, hipStream_t st)
 {
-    const char* src = a.src;
-    char* out = a.out;
-    for (int m0 = 0; m0 < n; m0 += MAX_GRID_Y) {
-        const unsigned nm = (unsigned)(n - m0 < MAX_GRID_Y ? n - m0 : MAX_GRID_Y);
+    const SourceMaps& s = c.s;
+    const char* src = static_cast<const char*>(s.disp);
+    char* out = reinterpret_cast<char*>(c.out);
+    ImageArgs a = source_args(s, src, s.n > 1 ? s.map_stride : 0);
+    a.ostride = c.ostride; a.omap = s.n > 1 ? c.omap : 0;
+    a.vec_dst = (((uintptr_t)out | (uintptr_t)a.ostride | (uintptr_t)a.omap) & 15) == 0;
+    set_geometry(a.g, s.prm);
+    return for_batches(s.n, GRID_LIMIT, [&](int m0, unsigned nm) {
         a.src = src + (ptrdiff_t)m0 * a.smap;
         a.out = out + (ptrdiff_t)m0 * a.omap;
-        int rc;
         if (a.g.mode == ADF_MISSING_MIN) {
-            a.g.min_key = slots + m0;
-            if ((rc = min_run<SRC>(a, nm, slots + m0, st))) return rc;
+            a.g.min_key = static_cast<uint32_t*>(ws) + m0;
+            if (const int rc = min_run<SRC>(a, nm, static_cast<uint32_t*>(ws) + m0, st)) return rc;
         }
-        const dim3 grid((unsigned)((a.total + NT - 1) / NT), nm);
-        if (ch == 3) hipLaunchKernelGGL((reproject_kernel<SRC, 3>), grid, dim3(NT), 0, st, a);
-        else hipLaunchKernelGGL((reproject_kernel<SRC, 1>), grid, dim3(NT), 0, st, a);
-        if ((rc = launched())) return rc;
-    }
-    return ADF_OK;
+        const auto kernel = c.ch == 3 ? reproject_kernel<SRC, 3> : reproject_kernel<SRC, 1>;
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((a.total + NT - 1) / NT), nm), dim3(NT), 0, st, a);
+        return launched();
+    });
 }
 
-int image_launch(int n, const void* disp, int depth, ptrdiff_t stride, ptrdiff_t map_stride, int W, int H,
-                 const adf_reproject_params* prm, float* out, ptrdiff_t ostride, ptrdiff_t omap, int ch, void* ws, hipStream_t st)
+int image_launch(const ImageCall& c, void* ws, hipStream_t st)
 {
-    ImageArgs a = source_args(disp, stride, n > 1 ? map_stride : 0, W, H, esz_of(depth));
-    a.out = reinterpret_cast<char*>(out); a.ostride = ostride; a.omap = n > 1 ? omap : 0;
-    a.vec_dst = (((uintptr_t)out | (uintptr_t)ostride | (n > 1 ? (uintptr_t)omap : 0)) & 15) == 0;
-    set_geometry(a.g, prm, nullptr);
-    return depth == ADF_16S ? image_run<int16_t>(n, a, ch, static_cast<uint32_t*>(ws), st)
-                            : image_run<float>(n, a, ch, static_cast<uint32_t*>(ws), st);
+    return c.s.depth == ADF_16S ? image_launch<int16_t>(c, ws, st) : image_launch<float>(c, ws, st);
 }
 
-struct CloudCall {                     // what cloud_check derives from the arguments of adf_point_cloud_*
-    adf_rect roi;
-    int tiles;
-};
-
-int cloud_check(int n, const void* disp, int depth, ptrdiff_t stride, ptrdiff_t map_stride, int W, int H,
-                const adf_reproject_params* prm, const adf_rect* roi, double z_min, double z_max,
-                const uint8_t* view, ptrdiff_t vstride, int vch, const float* points, ptrdiff_t pmap,
-                const uint8_t* colours, ptrdiff_t cmap, const int32_t* index, ptrdiff_t imap, int capacity,
-                const uint32_t* counts, CloudCall* c)
+// Sets c.roi and c.tiles.
+int cloud_check(CloudCall& c)
 {
-    const int rc = source_check(PC, n, disp, depth, stride, map_stride, W, H, prm);
-    if (rc) return rc;
-    if (!points || !counts) return fail(ADF_EBADARG, "%s: points and counts must not be null", PC);
-    if (colours && !view) return fail(ADF_EBADARG, "%s: colours need a view", PC);
-    if (view && vch != 1 && vch != 3) return fail(ADF_EBADARG, "%s: view_channels must be 1 or 3", PC);
-    if (view && vstride < (ptrdiff_t)W * vch) return fail(ADF_ESIZE, "%s: view row stride smaller than a row", PC);
-    if (capacity < 0) return fail(ADF_EBADARG, "%s: capacity must not be negative", PC);
-    if (z_min != z_min || z_max != z_max) return fail(ADF_EBADARG, "%s: z_min and z_max must not be NaN", PC);
-    if (((uintptr_t)points | (n > 1 ? (uintptr_t)pmap : 0)) & 3)
-        return fail(ADF_EBADARG, "%s: points and its map stride must be 4-byte aligned", PC);
-    if (index && (((uintptr_t)index | (n > 1 ? (uintptr_t)imap : 0)) & 3))
+    const SourceMaps& s = c.s;
+    if (const int rc = source_check(PC, s)) return rc;
+    if (!c.points || !c.counts) return fail(ADF_EBADARG, "%s: points and counts must not be null", PC);
+    if (c.colours && !c.view) return fail(ADF_EBADARG, "%s: colours need a view", PC);
+    if (c.view && c.vch != 1 && c.vch != 3) return fail(ADF_EBADARG, "%s: view_channels must be 1 or 3", PC);
+    if (c.view && c.vstride < (ptrdiff_t)s.W * c.vch) return fail(ADF_ESIZE, "%s: view row stride smaller than a row", PC);
+    if (c.capacity < 0) return fail(ADF_EBADARG, "%s: capacity must not be negative", PC);
+    if (c.z_min != c.z_min || c.z_max != c.z_max) return fail(ADF_EBADARG, "%s: z_min and z_max must not be NaN", PC);
+    if (misaligned(s.n, c.points, 0, c.pmap, 4)) return fail(ADF_EBADARG, "%s: points and its map stride must be 4-byte aligned", PC);
+    if (c.index && misaligned(s.n, c.index, 0, c.imap, 4))
         return fail(ADF_EBADARG, "%s: index and its map stride must be 4-byte aligned", PC);
-    c->roi = roi ? *roi : adf_rect{0, 0, W, H};
-    const adf_rect& r = c->roi;
-    if (r.x < 0 || r.y < 0 || r.width < 1 || r.height < 1 || r.x > W - r.width || r.y > H - r.height)
+    c.roi = c.roi_arg ? *c.roi_arg : adf_rect{0, 0, s.W, s.H};
+    const adf_rect& r = c.roi;
+    if (r.x < 0 || r.y < 0 || r.width < 1 || r.height < 1 || r.x > s.W - r.width || r.y > s.H - r.height)
         return fail(ADF_ESIZE, "%s: ROI does not fit the map", PC);
-    const int64_t npx = (int64_t)r.width * r.height, fit = capacity < npx ? capacity : npx;   // entries a map can write
-    if (n > 1 && (pmap < fit * 12 || (colours && cmap < fit * vch) || (index && imap < fit * 4)))
+    const int64_t npx = (int64_t)r.width * r.height, fit = c.capacity < npx ? c.capacity : npx;   // entries a map can write
+    if (s.n > 1 && (c.pmap < fit * 12 || (c.colours && c.cmap < fit * c.vch) || (c.index && c.imap < fit * 4)))
         return fail(ADF_ESIZE, "%s: lists of the batch overlap (map stride smaller than a list)", PC);
-    c->tiles = (int)((npx + TILE - 1) / TILE);
+    c.tiles = (int)((npx + TILE - 1) / TILE);
     return ADF_OK;
 }
 
-size_t min_slots_bytes(int n) { return ((size_t)n * sizeof(uint32_t) + 15) / 16 * 16; }
+size_t min_slots_bytes(int n) { return pad_to((size_t)n * sizeof(uint32_t), 16); }
 
-template <class SRC> int cloud_run(int n, CloudArgs a, int H, uint32_t* slots, hipStream_t st)
+// ws: adf_point_cloud_workspace_bytes of device memory, the minimum slots and then the tile counts
+template <class SRC> int cloud_launch(const CloudCall& c, void* ws, hipStream_t st)
 {
-    const char* src = a.src;
-    const uint8_t* view = a.view;
-    char* points = reinterpret_cast<char*>(a.points);
-    uint8_t* colours = a.colours;
-    char* index = reinterpret_cast<char*>(a.index);
-    uint32_t* counts = a.counts;
-    uint32_t* tile_counts = a.tile_counts;
-    for (int m0 = 0; m0 < n; m0 += MAX_GRID_Y) {
-        const unsigned nm = (unsigned)(n - m0 < MAX_GRID_Y ? n - m0 : MAX_GRID_Y);
-        a.src = src + (ptrdiff_t)m0 * a.smap;
-        a.view = view ? view + (ptrdiff_t)m0 * a.vmap : nullptr;
-        a.points = reinterpret_cast<float*>(points + (ptrdiff_t)m0 * a.pmap);
-        a.colours = colours ? colours + (ptrdiff_t)m0 * a.cmap : nullptr;
-        a.index = index ? reinterpret_cast<int32_t*>(index + (ptrdiff_t)m0 * a.imap) : nullptr;
-        a.counts = counts + m0;
+    const SourceMaps& s = c.s;
+    const int n = s.n;
+    CloudArgs a;
+    a.sstride = s.stride; a.smap = n > 1 ? s.map_stride : 0;
+    a.W = s.W; a.roi = c.roi; a.npx = c.roi.width * c.roi.height; a.tiles = c.tiles;
+    a.z_min = c.z_min; a.z_max = c.z_max;
+    a.vstride = c.vstride; a.vmap = n > 1 ? c.vmap : 0; a.vch = c.view ? c.vch : 0;
+    a.pmap = n > 1 ? c.pmap : 0; a.cmap = n > 1 ? c.cmap : 0; a.imap = n > 1 ? c.imap : 0;
+    a.capacity = c.capacity;
+    set_geometry(a.g, s.prm);
+    uint32_t* slots = static_cast<uint32_t*>(ws);
+    uint32_t* tile_counts = reinterpret_cast<uint32_t*>(static_cast<char*>(ws) + min_slots_bytes(n));
+    return for_batches(n, GRID_LIMIT, [&](int m0, unsigned nm) {
+        a.src = static_cast<const char*>(s.disp) + (ptrdiff_t)m0 * a.smap;
+        a.view = c.view ? c.view + (ptrdiff_t)m0 * a.vmap : nullptr;
+        a.points = reinterpret_cast<float*>(reinterpret_cast<char*>(c.points) + (ptrdiff_t)m0 * a.pmap);
+        a.colours = c.colours ? c.colours + (ptrdiff_t)m0 * a.cmap : nullptr;
+        a.index = c.index ? reinterpret_cast<int32_t*>(reinterpret_cast<char*>(c.index) + (ptrdiff_t)m0 * a.imap) : nullptr;
+        a.counts = c.counts + m0;
         a.tile_counts = tile_counts + (size_t)m0 * a.tiles;
         int rc;
         if (a.g.mode == ADF_MISSING_MIN) {                           // over the whole map, not the ROI
             a.g.min_key = slots + m0;
-            if ((rc = min_run<SRC>(source_args(a.src, a.sstride, a.smap, a.W, H, (int)sizeof(SRC)), nm, slots + m0, st))) return rc;
+            if ((rc = min_run<SRC>(source_args(s, a.src, a.smap), nm, slots + m0, st))) return rc;
         }
         hipLaunchKernelGGL((cloud_count_kernel<SRC>), dim3((unsigned)a.tiles, nm), dim3(NT), 0, st, a);
         if ((rc = launched())) return rc;
         hipLaunchKernelGGL(cloud_scan_kernel, dim3(nm), dim3(NT), 0, st, a);
         if ((rc = launched())) return rc;
         hipLaunchKernelGGL((cloud_write_kernel<SRC>), dim3((unsigned)a.tiles, nm), dim3(NT), 0, st, a);
-        if ((rc = launched())) return rc;
-    }
-    return ADF_OK;
+        return launched();
+    });
 }
 
-int cloud_launch(int n, const void* disp, int depth, ptrdiff_t stride, ptrdiff_t map_stride, int W, int H,
-                 const adf_reproject_params* prm, const CloudCall& c, double z_min, double z_max,
-                 const uint8_t* view, ptrdiff_t vstride, ptrdiff_t vmap, int vch, float* points, ptrdiff_t pmap,
-                 uint8_t* colours, ptrdiff_t cmap, int32_t* index, ptrdiff_t imap, int capacity, uint32_t* counts,
-                 void* ws, hipStream_t st)
+int cloud_launch(const CloudCall& c, void* ws, hipStream_t st)
 {
-    CloudArgs a;
-    a.src = static_cast<const char*>(disp); a.sstride = stride; a.smap = n > 1 ? map_stride : 0;
-    a.W = W; a.roi = c.roi; a.npx = c.roi.width * c.roi.height; a.tiles = c.tiles;
-    a.z_min = z_min; a.z_max = z_max;
-    a.view = view; a.vstride = vstride; a.vmap = n > 1 ? vmap : 0; a.vch = view ? vch : 0;
-    a.points = points; a.pmap = n > 1 ? pmap : 0;
-    a.colours = colours; a.cmap = n > 1 ? cmap : 0;
-    a.index = index; a.imap = n > 1 ? imap : 0;
-    a.capacity = capacity;
-    a.counts = counts;
-    uint32_t* slots = static_cast<uint32_t*>(ws);
-    a.tile_counts = reinterpret_cast<uint32_t*>(static_cast<char*>(ws) + min_slots_bytes(n));
-    set_geometry(a.g, prm, nullptr);
-    return depth == ADF_16S ? cloud_run<int16_t>(n, a, H, slots, st) : cloud_run<float>(n, a, H, slots, st);
+    return c.s.depth == ADF_16S ? cloud_launch<int16_t>(c, ws, st) : cloud_launch<float>(c, ws, st);
 }
-
-size_t round16(size_t v) { return (v + 15) / 16 * 16; }
 
 } // namespace
 
@@ -582,40 +566,36 @@ extern "C" int adf_reproject_to_3d_device(int n_maps, const void* disp, int dept
                                           ptrdiff_t out_map_stride, int out_channels, void* workspace, size_t workspace_bytes,
                                           void* stream)
 {
-    int rc = image_check(n_maps, disp, depth, stride, map_stride, W, H, prm, out, out_stride, out_map_stride, out_channels);
+    const ImageCall c{{n_maps, disp, depth, stride, map_stride, W, H, prm}, out, out_stride, out_map_stride, out_channels};
+    int rc = image_check(c);
     if (rc) return rc;
     hipStream_t st = (hipStream_t)stream;
-    if (prm->missing_mode != ADF_MISSING_MIN)                        // nothing to reduce: no workspace is used
-        return image_launch(n_maps, disp, depth, stride, map_stride, W, H, prm, out, out_stride, out_map_stride, out_channels, nullptr, st);
-    const size_t need = adf_reproject_workspace_bytes(n_maps);
-    if (workspace) {
-        if (workspace_bytes < need) return fail(ADF_ESIZE, "%s: workspace smaller than adf_reproject_workspace_bytes", RP);
-        if ((uintptr_t)workspace & 3) return fail(ADF_EBADARG, "%s: workspace must be 4-byte aligned", RP);
-        return image_launch(n_maps, disp, depth, stride, map_stride, W, H, prm, out, out_stride, out_map_stride, out_channels, workspace, st);
-    }
-    if (stream_is_capturing(st)) return fail(ADF_EBADARG, "%s: a call captured into a graph needs a caller workspace", RP);
+    if (prm->missing_mode != ADF_MISSING_MIN) return image_launch(c, nullptr, st);   // nothing to reduce: no workspace is used
     Scratch blk;
-    if ((rc = blk.take(need, st))) return rc;
-    return image_launch(n_maps, disp, depth, stride, map_stride, W, H, prm, out, out_stride, out_map_stride, out_channels, blk.p, st);
+    void* ws;
+    rc = workspace_or_scratch(RP, "adf_reproject_workspace_bytes", workspace, workspace_bytes, adf_reproject_workspace_bytes(n_maps), st, blk, &ws);
+    return rc ? rc : image_launch(c, ws, st);
 }
 
 extern "C" int adf_reproject_to_3d_host(int n_maps, const void* disp, int depth, ptrdiff_t stride, ptrdiff_t map_stride,
                                         int W, int H, const adf_reproject_params* prm, float* out, ptrdiff_t out_stride,
                                         ptrdiff_t out_map_stride, int out_channels)
 {
-    int rc = image_check(n_maps, disp, depth, stride, map_stride, W, H, prm, out, out_stride, out_map_stride, out_channels);
+    const ImageCall c{{n_maps, disp, depth, stride, map_stride, W, H, prm}, out, out_stride, out_map_stride, out_channels};
+    int rc = image_check(c);
     if (rc) return rc;
     // one block: the maps, the images (rows padded to 16 bytes: the vector path), the minimum slots
     const size_t srow = (size_t)W * esz_of(depth), orow = (size_t)W * out_channels * 4;
-    const size_t sp = round16(srow), op = round16(orow), smap = sp * H, omap = op * H;
+    const size_t sp = pad_to(srow, 16), op = pad_to(orow, 16), smap = sp * H, omap = op * H;
     Scratch blk;
-    if ((rc = blk.take((smap + omap) * n_maps + round16(adf_reproject_workspace_bytes(n_maps)), nullptr))) return rc;
+    if ((rc = blk.take((smap + omap) * n_maps + pad_to(adf_reproject_workspace_bytes(n_maps), 16), nullptr))) return rc;
     char* ds = static_cast<char*>(blk.p);
     char* dout = ds + smap * n_maps;
+    ImageCall d = c;                                                 // the same call on the staged copies
+    d.s.disp = ds; d.s.stride = (ptrdiff_t)sp; d.s.map_stride = (ptrdiff_t)smap;
+    d.out = reinterpret_cast<float*>(dout); d.ostride = (ptrdiff_t)op; d.omap = (ptrdiff_t)omap;
     if ((rc = copy_images(ds, sp, smap, disp, stride, map_stride, srow, H, n_maps, hipMemcpyHostToDevice, nullptr))) return rc;
-    rc = image_launch(n_maps, ds, depth, (ptrdiff_t)sp, (ptrdiff_t)smap, W, H, prm, reinterpret_cast<float*>(dout), (ptrdiff_t)op,
-                      (ptrdiff_t)omap, out_channels, dout + omap * n_maps, nullptr);
-    if (rc) return rc;
+    if ((rc = image_launch(d, dout + omap * n_maps, nullptr))) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
     if ((rc = copy_images(out, out_stride, out_map_stride, dout, op, omap, orow, H, n_maps, hipMemcpyDeviceToHost, nullptr))) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
@@ -636,26 +616,16 @@ extern "C" int adf_point_cloud_device(int n_maps, const void* disp, int depth, p
                                       int32_t* index, ptrdiff_t index_map_stride, int capacity, uint32_t* counts,
                                       void* workspace, size_t workspace_bytes, void* stream)
 {
-    CloudCall c;
-    int rc = cloud_check(n_maps, disp, depth, stride, map_stride, W, H, prm, roi, z_min, z_max, view, view_stride, view_channels,
-                         points, points_map_stride, colours, colours_map_stride, index, index_map_stride, capacity, counts, &c);
+    CloudCall c{{n_maps, disp, depth, stride, map_stride, W, H, prm}, roi, z_min, z_max, view, view_stride, view_map_stride, view_channels,
+                points, points_map_stride, colours, colours_map_stride, index, index_map_stride, capacity, counts, {}, 0};
+    int rc = cloud_check(c);
     if (rc) return rc;
     if ((uintptr_t)counts & 3) return fail(ADF_EBADARG, "%s: counts must be 4-byte aligned", PC);
-    hipStream_t st = (hipStream_t)stream;
-    const size_t need = adf_point_cloud_workspace_bytes(n_maps, W, H);
-    void* ws = workspace;
     Scratch blk;
-    if (workspace) {
-        if (workspace_bytes < need) return fail(ADF_ESIZE, "%s: workspace smaller than adf_point_cloud_workspace_bytes", PC);
-        if ((uintptr_t)workspace & 3) return fail(ADF_EBADARG, "%s: workspace must be 4-byte aligned", PC);
-    } else {
-        if (stream_is_capturing(st)) return fail(ADF_EBADARG, "%s: a call captured into a graph needs a caller workspace", PC);
-        if ((rc = blk.take(need, st))) return rc;
-        ws = blk.p;
-    }
-    return cloud_launch(n_maps, disp, depth, stride, map_stride, W, H, prm, c, z_min, z_max, view, view_stride, view_map_stride,
-                        view_channels, points, points_map_stride, colours, colours_map_stride, index, index_map_stride,
-                        capacity, counts, ws, st);
+    void* ws;
+    rc = workspace_or_scratch(PC, "adf_point_cloud_workspace_bytes", workspace, workspace_bytes,
+                              adf_point_cloud_workspace_bytes(n_maps, W, H), (hipStream_t)stream, blk, &ws);
+    return rc ? rc : cloud_launch(c, ws, (hipStream_t)stream);
 }
 
 extern "C" int adf_point_cloud_host(int n_maps, const void* disp, int depth, ptrdiff_t stride, ptrdiff_t map_stride, int W, int H,
@@ -664,17 +634,17 @@ extern "C" int adf_point_cloud_host(int n_maps, const void* disp, int depth, ptr
                                     float* points, ptrdiff_t points_map_stride, uint8_t* colours, ptrdiff_t colours_map_stride,
                                     int32_t* index, ptrdiff_t index_map_stride, int capacity, uint32_t* counts)
 {
-    CloudCall c;
-    int rc = cloud_check(n_maps, disp, depth, stride, map_stride, W, H, prm, roi, z_min, z_max, view, view_stride, view_channels,
-                         points, points_map_stride, colours, colours_map_stride, index, index_map_stride, capacity, counts, &c);
+    CloudCall c{{n_maps, disp, depth, stride, map_stride, W, H, prm}, roi, z_min, z_max, view, view_stride, view_map_stride, view_channels,
+                points, points_map_stride, colours, colours_map_stride, index, index_map_stride, capacity, counts, {}, 0};
+    int rc = cloud_check(c);
     if (rc) return rc;
     if (!colours) view = nullptr;                                    // (nothing else reads it)
     // one block: the maps, the views, then per map the three lists sized for what can be written, the counts, the workspace
     const size_t npx = (size_t)c.roi.width * c.roi.height, fit = (size_t)capacity < npx ? (size_t)capacity : npx;
-    const size_t srow = (size_t)W * esz_of(depth), sp = round16(srow), smap = sp * H;
-    const size_t vrow = view ? (size_t)W * view_channels : 0, vp = round16(vrow), vmap = vp * H;
-    const size_t pmap = round16(fit * 12), cmap = colours ? round16(fit * view_channels) : 0, imap = index ? round16(fit * 4) : 0;
-    const size_t cnt = round16((size_t)n_maps * sizeof(uint32_t));
+    const size_t srow = (size_t)W * esz_of(depth), sp = pad_to(srow, 16), smap = sp * H;
+    const size_t vrow = view ? (size_t)W * view_channels : 0, vp = pad_to(vrow, 16), vmap = vp * H;
+    const size_t pmap = pad_to(fit * 12, 16), cmap = colours ? pad_to(fit * view_channels, 16) : 0, imap = index ? pad_to(fit * 4, 16) : 0;
+    const size_t cnt = pad_to((size_t)n_maps * sizeof(uint32_t), 16);
     Scratch blk;
     if ((rc = blk.take((smap + vmap + pmap + cmap + imap) * n_maps + cnt + adf_point_cloud_workspace_bytes(n_maps, W, H), nullptr)))
         return rc;
@@ -684,15 +654,17 @@ extern "C" int adf_point_cloud_host(int n_maps, const void* disp, int depth, ptr
     char* dc = dp + pmap * n_maps;
     char* di = dc + cmap * n_maps;
     char* dn = di + imap * n_maps;
+    CloudCall d = c;                                                 // the same call on the staged copies
+    d.s.disp = ds; d.s.stride = (ptrdiff_t)sp; d.s.map_stride = (ptrdiff_t)smap;
+    d.view = view ? reinterpret_cast<const uint8_t*>(dv) : nullptr; d.vstride = (ptrdiff_t)vp; d.vmap = (ptrdiff_t)vmap;
+    d.points = reinterpret_cast<float*>(dp); d.pmap = (ptrdiff_t)pmap;
+    d.colours = colours ? reinterpret_cast<uint8_t*>(dc) : nullptr; d.cmap = (ptrdiff_t)cmap;
+    d.index = index ? reinterpret_cast<int32_t*>(di) : nullptr; d.imap = (ptrdiff_t)imap;
+    d.counts = reinterpret_cast<uint32_t*>(dn);
     if ((rc = copy_images(ds, sp, smap, disp, stride, map_stride, srow, H, n_maps, hipMemcpyHostToDevice, nullptr))) return rc;
     if (view && (rc = copy_images(dv, vp, vmap, view, view_stride, view_map_stride, vrow, H, n_maps, hipMemcpyHostToDevice, nullptr)))
         return rc;
-    rc = cloud_launch(n_maps, ds, depth, (ptrdiff_t)sp, (ptrdiff_t)smap, W, H, prm, c, z_min, z_max,
-                      view ? reinterpret_cast<const uint8_t*>(dv) : nullptr, (ptrdiff_t)vp, (ptrdiff_t)vmap, view_channels,
-                      reinterpret_cast<float*>(dp), (ptrdiff_t)pmap, colours ? reinterpret_cast<uint8_t*>(dc) : nullptr, (ptrdiff_t)cmap,
-                      index ? reinterpret_cast<int32_t*>(di) : nullptr, (ptrdiff_t)imap, capacity, reinterpret_cast<uint32_t*>(dn),
-                      dn + cnt, nullptr);
-    if (rc) return rc;
+    if ((rc = cloud_launch(d, dn + cnt, nullptr))) return rc;
     HIP_TRY(hipMemcpyAsync(counts, dn, (size_t)n_maps * sizeof(uint32_t), hipMemcpyDeviceToHost, nullptr));
     HIP_TRY(hipStreamSynchronize(nullptr));
     for (int k = 0; k < n_maps; k++) {                               // only what was written comes back

@@ -744,12 +744,11 @@ extern "C" int adf_sgbm_compute_device(adf_sgbm_t* h, int n_pairs,
     // workspace per image in flight: two signal planes (12 * cn bytes per pixel) or, with a census cost, two descriptor
     // planes (8), the C and S volumes, the raw map (every part 256-byte aligned)
     const bool census = h->cost != ADF_SGBM_COST_BT;
-    auto up256 = [](size_t b) { return (b + 255) / 256 * 256; };
-    const size_t rec_bytes = up256((size_t)W * H * (census ? 8 : cn * 3 * 4));
+    const size_t rec_bytes = pad_to((size_t)W * H * (census ? 8 : cn * 3 * 4), 256);
     const size_t rec_pair = rec_bytes / 4;                                            // dwords
-    const size_t vol_bytes = up256(w1 > 0 ? (size_t)H * w1 * D * 2 : 0);
+    const size_t vol_bytes = pad_to(w1 > 0 ? (size_t)H * w1 * D * 2 : 0, 256);
     const size_t volp = vol_bytes / 2;                                                // int16 elements
-    const size_t raw_bytes = up256((size_t)W * H * 2);
+    const size_t raw_bytes = pad_to((size_t)W * H * 2, 256);
     const size_t raw_el = raw_bytes / 2;
     const size_t per_img = 2 * rec_bytes + 3 * vol_bytes + raw_bytes;     // C, S and the last accumulating path's own volume
     int chunk = (int)(h->ws_limit / per_img);
@@ -799,9 +798,7 @@ extern "C" int adf_sgbm_compute_device(adf_sgbm_t* h, int n_pairs,
         MedianArgs ma{raw, (ptrdiff_t)W, (ptrdiff_t)raw_el, out, disp_stride / 2, disp_pair_stride / 2, W, H};
         hipLaunchKernelGGL(sgbm_median_kernel, dim3((W + 255) / 256, H, n), dim3(256), 0, st, ma);
     }
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(ADF_EHIP, "%s", hipGetErrorString(e));
-    return ADF_OK;
+    return launched();
 }
 
 extern "C" int adf_sgbm_compute_host(adf_sgbm_t* h, int n_pairs,
@@ -818,7 +815,7 @@ extern "C" int adf_sgbm_compute_host(adf_sgbm_t* h, int n_pairs,
     if (rc) return rc;
     uint8_t* dl = (uint8_t*)h->stage.p;
     uint8_t* dr = dl + vbytes * n_pairs;
-    int16_t* dd = (int16_t*)(((uintptr_t)(dr + vbytes * n_pairs) + 255) & ~(uintptr_t)255);
+    int16_t* dd = (int16_t*)pad_to((uintptr_t)(dr + vbytes * n_pairs), 256);
     if ((rc = copy_images(dl, vrow, vbytes, left, left_stride, left_pair_stride, vrow, H, n_pairs, hipMemcpyHostToDevice, nullptr))) return rc;
     if ((rc = copy_images(dr, vrow, vbytes, right, right_stride, right_pair_stride, vrow, H, n_pairs, hipMemcpyHostToDevice, nullptr))) return rc;
     rc = adf_sgbm_compute_device(h, n_pairs, dl, (ptrdiff_t)vrow, (ptrdiff_t)vbytes, dr, (ptrdiff_t)vrow, (ptrdiff_t)vbytes, channels, W, H,

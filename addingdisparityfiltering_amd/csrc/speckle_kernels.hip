@@ -30,7 +30,6 @@ using namespace adf;
 namespace {
 
 constexpr int TW = 64, TH = 32, TN = TW * TH, NT = 256, PPT = TN / NT;
-constexpr int MAX_GRID_Y = 65535;      // maps per launch (grid y)
 
 struct SpeckleArgs {
     int16_t* img; ptrdiff_t stride, map_stride;   // bytes
@@ -207,45 +206,47 @@ __global__ void __launch_bounds__(256) speckle_apply_kernel(SpeckleArgs a)
     if (a.sizes[(size_t)blockIdx.y * a.plane + r] <= a.max_size) row[x] = (int16_t)a.new_val;
 }
 
-int speckle_check(int n, const int16_t* img, ptrdiff_t stride, ptrdiff_t map_stride, int W, int H, int new_val)
+struct SpeckleCall {                   // one call as its C entry point received it
+    int n; int16_t* img; ptrdiff_t stride, map_stride; int W, H;
+    int new_val, max_size, max_diff;
+};
+
+int speckle_check(const SpeckleCall& c)
 {
-    if (!img || n < 1 || W < 1 || H < 1) return fail(ADF_EBADARG, "filterSpeckles: the image is empty");
-    if (new_val < -32768 || new_val > 32767) return fail(ADF_EBADARG, "filterSpeckles: newVal is outside the CV_16S range");
-    if ((int64_t)W * H >= ((int64_t)1 << 31)) return fail(ADF_ESIZE, "filterSpeckles: W*H must be below 2^31 (int32 labels)");
-    if ((uint64_t)n * (uint64_t)W * (uint64_t)H > ((uint64_t)1 << 40)) return fail(ADF_ESIZE, "filterSpeckles: batch too large");
-    if (((uintptr_t)img & 1) || (stride & 1) || (map_stride & 1))
+    if (!c.img || c.n < 1 || c.W < 1 || c.H < 1) return fail(ADF_EBADARG, "filterSpeckles: the image is empty");
+    if (c.new_val < -32768 || c.new_val > 32767) return fail(ADF_EBADARG, "filterSpeckles: newVal is outside the CV_16S range");
+    if ((int64_t)c.W * c.H >= ((int64_t)1 << 31)) return fail(ADF_ESIZE, "filterSpeckles: W*H must be below 2^31 (int32 labels)");
+    if ((uint64_t)c.n * (uint64_t)c.W * (uint64_t)c.H > ((uint64_t)1 << 40)) return fail(ADF_ESIZE, "filterSpeckles: batch too large");
+    if (((uintptr_t)c.img & 1) || (c.stride & 1) || (c.map_stride & 1))
         return fail(ADF_EBADARG, "filterSpeckles: CV_16S image and strides must be 2-byte aligned");
-    if (stride < (ptrdiff_t)W * 2) return fail(ADF_ESIZE, "filterSpeckles: row stride smaller than a row");
-    if (n > 1 && map_stride < stride * (H - 1) + (ptrdiff_t)W * 2)
+    if (c.stride < (ptrdiff_t)c.W * 2) return fail(ADF_ESIZE, "filterSpeckles: row stride smaller than a row");
+    if (!images_disjoint(c.n, (ptrdiff_t)c.W * 2, c.H, c.stride, c.map_stride, false))
         return fail(ADF_ESIZE, "filterSpeckles: maps of the batch overlap (map stride smaller than a map)");
     return ADF_OK;
 }
 
-int speckle_run(int n, int16_t* img, ptrdiff_t stride, ptrdiff_t map_stride, int W, int H, int new_val, int max_size,
-                int max_diff, void* ws, hipStream_t st)
+// ws: adf_filter_speckles_workspace_bytes of device memory, the labels of every map and then their sizes
+int speckle_run(const SpeckleCall& c, void* ws, hipStream_t st)
 {
-    const size_t plane = (size_t)W * H;
+    const size_t plane = (size_t)c.W * c.H;
     SpeckleArgs a;
-    a.stride = stride; a.map_stride = map_stride;
-    a.W = W; a.H = H; a.tiles_x = (W + TW - 1) / TW; a.tiles_y = (H + TH - 1) / TH;
-    a.new_val = new_val; a.max_size = max_size; a.max_diff = max_diff;
+    a.stride = c.stride; a.map_stride = c.map_stride;
+    a.W = c.W; a.H = c.H; a.tiles_x = (c.W + TW - 1) / TW; a.tiles_y = (c.H + TH - 1) / TH;
+    a.new_val = c.new_val; a.max_size = c.max_size; a.max_diff = c.max_diff;
     a.plane = (int)plane;
-    const int n_vert = (a.tiles_x - 1) * H, n_edges = n_vert + (a.tiles_y - 1) * W;
+    const int n_vert = (a.tiles_x - 1) * c.H, n_edges = n_vert + (a.tiles_y - 1) * c.W;
     const unsigned pix_blocks = (unsigned)((plane + 255) / 256);
-    for (int m0 = 0; m0 < n; m0 += MAX_GRID_Y) {
-        const unsigned nm = (unsigned)(n - m0 < MAX_GRID_Y ? n - m0 : MAX_GRID_Y);
-        a.img = reinterpret_cast<int16_t*>(reinterpret_cast<char*>(img) + (ptrdiff_t)m0 * map_stride);
+    return for_batches(c.n, GRID_LIMIT, [&](int m0, unsigned nm) {
+        a.img = reinterpret_cast<int16_t*>(reinterpret_cast<char*>(c.img) + (ptrdiff_t)m0 * c.map_stride);
         a.labels = static_cast<int*>(ws) + plane * m0;
-        a.sizes = static_cast<int*>(ws) + plane * n + plane * m0;
+        a.sizes = static_cast<int*>(ws) + plane * c.n + plane * m0;
         hipLaunchKernelGGL(speckle_tile_kernel, dim3((unsigned)(a.tiles_x * a.tiles_y), nm), dim3(NT), 0, st, a);
         if (n_edges > 0)
             hipLaunchKernelGGL(speckle_merge_kernel, dim3((unsigned)((n_edges + 255) / 256), nm), dim3(256), 0, st, a, n_vert, n_edges);
         hipLaunchKernelGGL(speckle_count_kernel, dim3(pix_blocks, nm), dim3(256), 0, st, a);
         hipLaunchKernelGGL(speckle_apply_kernel, dim3(pix_blocks, nm), dim3(256), 0, st, a);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(ADF_EHIP, "%s", hipGetErrorString(e));
-    }
-    return ADF_OK;
+        return launched();
+    });
 }
 
 } // namespace
@@ -260,38 +261,33 @@ extern "C" int adf_filter_speckles_device(int n_maps, int16_t* img, ptrdiff_t st
                                           int new_val, int max_speckle_size, int max_diff,
                                           void* workspace, size_t workspace_bytes, void* stream)
 {
-    int rc = speckle_check(n_maps, img, stride, map_stride, W, H, new_val);
+    const SpeckleCall c{n_maps, img, stride, map_stride, W, H, new_val, max_speckle_size, max_diff};
+    int rc = speckle_check(c);
     if (rc) return rc;
-    const size_t need = adf_filter_speckles_workspace_bytes(n_maps, W, H);
-    hipStream_t st = (hipStream_t)stream;
-    if (workspace) {
-        if (workspace_bytes < need) return fail(ADF_ESIZE, "filterSpeckles: workspace smaller than adf_filter_speckles_workspace_bytes");
-        if ((uintptr_t)workspace & 3) return fail(ADF_EBADARG, "filterSpeckles: workspace must be 4-byte aligned");
-        return speckle_run(n_maps, img, stride, map_stride, W, H, new_val, max_speckle_size, max_diff, workspace, st);
-    }
-    // library scratch: a block of the process-wide cache, ordered behind its last user's event (no host wait)
-    if (stream_is_capturing(st)) return fail(ADF_EBADARG, "filterSpeckles: a call captured into a graph needs a caller workspace");
     Scratch blk;
-    if ((rc = blk.take(need, st))) return rc;
-    return speckle_run(n_maps, img, stride, map_stride, W, H, new_val, max_speckle_size, max_diff, blk.p, st);
+    void* ws;
+    rc = workspace_or_scratch("filterSpeckles", "adf_filter_speckles_workspace_bytes", workspace, workspace_bytes,
+                              adf_filter_speckles_workspace_bytes(n_maps, W, H), (hipStream_t)stream, blk, &ws);
+    return rc ? rc : speckle_run(c, ws, (hipStream_t)stream);
 }
 
 extern "C" int adf_filter_speckles_host(int n_maps, int16_t* img, ptrdiff_t stride, ptrdiff_t map_stride, int W, int H,
                                         int new_val, int max_speckle_size, int max_diff)
 {
-    int rc = speckle_check(n_maps, img, stride, map_stride, W, H, new_val);
+    const SpeckleCall c{n_maps, img, stride, map_stride, W, H, new_val, max_speckle_size, max_diff};
+    int rc = speckle_check(c);
     if (rc) return rc;
     // one block: the maps, dense, then the workspace
-    const size_t row = (size_t)W * 2, map = (size_t)H * row, maps = (map * n_maps + 255) / 256 * 256;
+    const size_t row = (size_t)W * 2, map = (size_t)H * row, maps = pad_to(map * n_maps, 256);
     Scratch blk;
     if ((rc = blk.take(maps + adf_filter_speckles_workspace_bytes(n_maps, W, H), nullptr))) return rc;
-    char* d = static_cast<char*>(blk.p);
-    if ((rc = copy_images(d, row, map, img, stride, map_stride, row, H, n_maps, hipMemcpyHostToDevice, nullptr))) return rc;
-    rc = speckle_run(n_maps, reinterpret_cast<int16_t*>(d), (ptrdiff_t)row, (ptrdiff_t)map, W, H, new_val,
-                     max_speckle_size, max_diff, d + maps, nullptr);
-    if (rc) return rc;
+    char* dm = static_cast<char*>(blk.p);
+    SpeckleCall d = c;                                               // the same call on the staged maps
+    d.img = reinterpret_cast<int16_t*>(dm); d.stride = (ptrdiff_t)row; d.map_stride = (ptrdiff_t)map;
+    if ((rc = copy_images(dm, row, map, img, stride, map_stride, row, H, n_maps, hipMemcpyHostToDevice, nullptr))) return rc;
+    if ((rc = speckle_run(d, dm + maps, nullptr))) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
-    if ((rc = copy_images(img, stride, map_stride, d, row, map, row, H, n_maps, hipMemcpyDeviceToHost, nullptr))) return rc;
+    if ((rc = copy_images(img, stride, map_stride, dm, row, map, row, H, n_maps, hipMemcpyDeviceToHost, nullptr))) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
     return ADF_OK;
 }

@@ -30,7 +30,6 @@ using namespace adf;
 namespace {
 
 constexpr int NT = 256;
-constexpr int MAX_GRID_Y = 65535;      // images per launch (grid y)
 constexpr int MAX_DIM = 1 << 24;       // W, H limit: byte offsets inside a row and run counts stay far inside int32
 
 struct ViewPrepArgs {
@@ -168,66 +167,60 @@ const char* const SUPPORTED =
 
 int half_of(int n) { return (n >> 1) + (n & (n >> 1) & 1); }     // cvRound(n * 0.5), half to even, n >= 0
 
-// Everything that can be refused without a device.  *half: the call shrinks.
-int view_prep_check(int n, const uint8_t* src, ptrdiff_t sstride, ptrdiff_t simage, int W, int H, int sc,
-                    const uint8_t* dst, ptrdiff_t dstride, ptrdiff_t dimage, int dW, int dH, int dc, bool* half)
+// One call as its C entry point received it; `half` (the call shrinks) is view_prep_check's.
+struct ViewPrepCall {
+    int n; const uint8_t* src; ptrdiff_t sstride, simage; int W, H, sc;
+    uint8_t* dst; ptrdiff_t dstride, dimage; int dW, dH, dc;
+    bool half;
+};
+
+// Everything that can be refused without a device.
+int view_prep_check(ViewPrepCall& c)
 {
-    if (n < 1) return fail(ADF_EBADARG, "prepare_views: n_images must be at least 1");
-    if (!src || !dst) return fail(ADF_EBADARG, "prepare_views: src and dst must not be null");
-    if (W < 1 || H < 1 || dW < 1 || dH < 1) return fail(ADF_EBADARG, "prepare_views: the source or the destination image is empty");
-    if (!((sc == 3 && (dc == 3 || dc == 1)) || (sc == 1 && dc == 1))) return fail(ADF_EBADARG, "%s", SUPPORTED);
-    if (dW == W && dH == H) *half = false;
-    else if (dW == half_of(W) && dH == half_of(H)) *half = true;
+    if (c.n < 1) return fail(ADF_EBADARG, "prepare_views: n_images must be at least 1");
+    if (!c.src || !c.dst) return fail(ADF_EBADARG, "prepare_views: src and dst must not be null");
+    if (c.W < 1 || c.H < 1 || c.dW < 1 || c.dH < 1) return fail(ADF_EBADARG, "prepare_views: the source or the destination image is empty");
+    if (!((c.sc == 3 && (c.dc == 3 || c.dc == 1)) || (c.sc == 1 && c.dc == 1))) return fail(ADF_EBADARG, "%s", SUPPORTED);
+    if (c.dW == c.W && c.dH == c.H) c.half = false;
+    else if (c.dW == half_of(c.W) && c.dH == half_of(c.H)) c.half = true;
     else return fail(ADF_EBADARG, "%s", SUPPORTED);
-    if (!*half && sc == dc) return fail(ADF_EBADARG, "%s", SUPPORTED);            // nothing to do is not a case either
-    if (W > MAX_DIM || H > MAX_DIM) return fail(ADF_ESIZE, "prepare_views: W and H must not exceed 2^24");
-    if (sstride < (ptrdiff_t)W * sc || dstride < (ptrdiff_t)dW * dc)
+    if (!c.half && c.sc == c.dc) return fail(ADF_EBADARG, "%s", SUPPORTED);       // nothing to do is not a case either
+    if (c.W > MAX_DIM || c.H > MAX_DIM) return fail(ADF_ESIZE, "prepare_views: W and H must not exceed 2^24");
+    if (c.sstride < (ptrdiff_t)c.W * c.sc || c.dstride < (ptrdiff_t)c.dW * c.dc)
         return fail(ADF_EBADARG, "prepare_views: row stride smaller than a row");
-    if (n > 1) {
-        if (simage < 0) return fail(ADF_EBADARG, "prepare_views: negative image stride");
-        // destination images either follow one another or interleave row by row
-        const ptrdiff_t drow = (ptrdiff_t)dW * dc;
-        const bool stacked = dimage >= dstride * (dH - 1) + drow;
-        const bool interleaved = dimage >= drow && dimage * (n - 1) + drow <= dstride;
-        if (!stacked && !interleaved) return fail(ADF_EBADARG, "prepare_views: destination images overlap");
-    }
+    if (c.n > 1 && c.simage < 0) return fail(ADF_EBADARG, "prepare_views: negative image stride");
+    if (!images_disjoint(c.n, (ptrdiff_t)c.dW * c.dc, c.dH, c.dstride, c.dimage, true))
+        return fail(ADF_EBADARG, "prepare_views: destination images overlap");
     return ADF_OK;
 }
 
 template <int CH_IN, int CH_OUT, bool HALF>
-int view_prep_launch(int n, ViewPrepArgs a, hipStream_t st)
+int view_prep_launch(const ViewPrepCall& c, hipStream_t st)
 {
     using S = Shape<CH_IN, CH_OUT, HALF>;
+    ViewPrepArgs a;
+    a.sstride = c.sstride; a.simage = c.n > 1 ? c.simage : 0;
+    a.dstride = c.dstride; a.dimage = c.n > 1 ? c.dimage : 0;
+    a.W = c.W; a.H = c.H; a.dW = c.dW; a.dH = c.dH;
     a.runs = (a.dW + S::RUN - 1) / S::RUN;
     if ((int64_t)a.runs * a.dH >= ((int64_t)1 << 31)) return fail(ADF_ESIZE, "prepare_views: image too large");
     a.total = a.runs * a.dH;
-    const uintptr_t smis = (uintptr_t)a.src | (uintptr_t)a.sstride | (n > 1 ? (uintptr_t)a.simage : 0);
-    const uintptr_t dmis = (uintptr_t)a.dst | (uintptr_t)a.dstride | (n > 1 ? (uintptr_t)a.dimage : 0);
+    const uintptr_t smis = (uintptr_t)c.src | (uintptr_t)a.sstride | (uintptr_t)a.simage;
+    const uintptr_t dmis = (uintptr_t)c.dst | (uintptr_t)a.dstride | (uintptr_t)a.dimage;
     a.vec = (smis & 15) == 0 && (dmis & (S::DST_ALIGN - 1)) == 0;
-    const uint8_t* src = a.src;
-    uint8_t* dst = a.dst;
-    for (int m0 = 0; m0 < n; m0 += MAX_GRID_Y) {
-        const unsigned nm = (unsigned)(n - m0 < MAX_GRID_Y ? n - m0 : MAX_GRID_Y);
-        a.src = src + (ptrdiff_t)m0 * a.simage;
-        a.dst = dst + (ptrdiff_t)m0 * a.dimage;
+    return for_batches(c.n, GRID_LIMIT, [&](int m0, unsigned nm) {
+        a.src = c.src + (ptrdiff_t)m0 * a.simage;
+        a.dst = c.dst + (ptrdiff_t)m0 * a.dimage;
         hipLaunchKernelGGL((view_prep_kernel<CH_IN, CH_OUT, HALF>), dim3((unsigned)((a.total + NT - 1) / NT), nm), dim3(NT), 0, st, a);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess) return fail(ADF_EHIP, "%s", hipGetErrorString(e));
-    }
-    return ADF_OK;
+        return launched();
+    });
 }
 
-int view_prep_run(int n, const uint8_t* src, ptrdiff_t sstride, ptrdiff_t simage, int W, int H, int sc,
-                  uint8_t* dst, ptrdiff_t dstride, ptrdiff_t dimage, int dW, int dH, int dc, bool half, hipStream_t st)
+int view_prep_run(const ViewPrepCall& c, hipStream_t st)
 {
-    ViewPrepArgs a;
-    a.src = src; a.sstride = sstride; a.simage = n > 1 ? simage : 0;
-    a.dst = dst; a.dstride = dstride; a.dimage = n > 1 ? dimage : 0;
-    a.W = W; a.H = H; a.dW = dW; a.dH = dH;
-    a.runs = a.total = a.vec = 0;
-    if (sc == 3 && dc == 3) return view_prep_launch<3, 3, true>(n, a, st);
-    if (sc == 1) return view_prep_launch<1, 1, true>(n, a, st);
-    return half ? view_prep_launch<3, 1, true>(n, a, st) : view_prep_launch<3, 1, false>(n, a, st);
+    if (c.sc == 3 && c.dc == 3) return view_prep_launch<3, 3, true>(c, st);
+    if (c.sc == 1) return view_prep_launch<1, 1, true>(c, st);
+    return c.half ? view_prep_launch<3, 1, true>(c, st) : view_prep_launch<3, 1, false>(c, st);
 }
 
 } // namespace
@@ -244,12 +237,10 @@ extern "C" int adf_prepare_views_device(int n_images, const uint8_t* src, ptrdif
                                         uint8_t* dst, ptrdiff_t dst_stride, ptrdiff_t dst_image_stride,
                                         int dst_W, int dst_H, int dst_channels, void* stream)
 {
-    bool half = false;
-    const int rc = view_prep_check(n_images, src, src_stride, src_image_stride, W, H, src_channels,
-                                   dst, dst_stride, dst_image_stride, dst_W, dst_H, dst_channels, &half);
-    if (rc) return rc;
-    return view_prep_run(n_images, src, src_stride, src_image_stride, W, H, src_channels,
-                         dst, dst_stride, dst_image_stride, dst_W, dst_H, dst_channels, half, (hipStream_t)stream);
+    ViewPrepCall c{n_images, src, src_stride, src_image_stride, W, H, src_channels,
+                   dst, dst_stride, dst_image_stride, dst_W, dst_H, dst_channels, false};
+    const int rc = view_prep_check(c);
+    return rc ? rc : view_prep_run(c, (hipStream_t)stream);
 }
 
 extern "C" int adf_prepare_views_host(int n_images, const uint8_t* src, ptrdiff_t src_stride, ptrdiff_t src_image_stride,
@@ -257,22 +248,23 @@ extern "C" int adf_prepare_views_host(int n_images, const uint8_t* src, ptrdiff_
                                       uint8_t* dst, ptrdiff_t dst_stride, ptrdiff_t dst_image_stride,
                                       int dst_W, int dst_H, int dst_channels)
 {
-    bool half = false;
-    int rc = view_prep_check(n_images, src, src_stride, src_image_stride, W, H, src_channels,
-                             dst, dst_stride, dst_image_stride, dst_W, dst_H, dst_channels, &half);
+    ViewPrepCall c{n_images, src, src_stride, src_image_stride, W, H, src_channels,
+                   dst, dst_stride, dst_image_stride, dst_W, dst_H, dst_channels, false};
+    int rc = view_prep_check(c);
     if (rc) return rc;
     // one block: the source images, then the destination images, rows and images padded to 16 bytes (the vector path)
     const size_t srow = (size_t)W * src_channels, drow = (size_t)dst_W * dst_channels;
-    const size_t sp = (srow + 15) / 16 * 16, dp = (drow + 15) / 16 * 16;
+    const size_t sp = pad_to(srow, 16), dp = pad_to(drow, 16);
     const size_t simg = sp * H, dimg = dp * dst_H, need = (simg + dimg) * (size_t)n_images;
     Scratch blk;
     if ((rc = blk.take(need, nullptr))) return rc;
     uint8_t* ds = static_cast<uint8_t*>(blk.p);
     uint8_t* dd = ds + simg * n_images;
+    ViewPrepCall d = c;                                              // the same call on the staged copies
+    d.src = ds; d.sstride = (ptrdiff_t)sp; d.simage = (ptrdiff_t)simg;
+    d.dst = dd; d.dstride = (ptrdiff_t)dp; d.dimage = (ptrdiff_t)dimg;
     if ((rc = copy_images(ds, sp, simg, src, src_stride, src_image_stride, srow, H, n_images, hipMemcpyHostToDevice, nullptr))) return rc;
-    rc = view_prep_run(n_images, ds, (ptrdiff_t)sp, (ptrdiff_t)simg, W, H, src_channels,
-                       dd, (ptrdiff_t)dp, (ptrdiff_t)dimg, dst_W, dst_H, dst_channels, half, nullptr);
-    if (rc) return rc;
+    if ((rc = view_prep_run(d, nullptr))) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
     if ((rc = copy_images(dst, dst_stride, dst_image_stride, dd, dp, dimg, drow, dst_H, n_images, hipMemcpyDeviceToHost, nullptr))) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
