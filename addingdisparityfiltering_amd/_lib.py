@@ -17,6 +17,9 @@ PATH_ROW_WEIGHTS_GUIDE = 32    # adf_wls_get_last_solver_path bit
 DEPTH_8U, DEPTH_16S, DEPTH_32F = 0, 3, 5
 SGBM_COST_BT, SGBM_COST_CENSUS_DENSE, SGBM_COST_CENSUS_SPARSE = 0, 1, 2    # adf_sgbm_set_cost (include/adf_wls.h)
 BM_COST_SAD, BM_COST_CENSUS_DENSE, BM_COST_CENSUS_SPARSE = 0, 1, 2    # adf_bm_set_cost (the census values equal SGBM_COST_CENSUS_*)
+# modified census (window mean) on the dense / the sparse grid, centre-symmetric census; 3 and 7 stay unassigned (include/adf_wls.h)
+SGBM_COST_MCT_DENSE, SGBM_COST_MCT_SPARSE, SGBM_COST_CENSUS_CS = 4, 5, 6
+BM_COST_MCT_DENSE, BM_COST_MCT_SPARSE, BM_COST_CENSUS_CS = 4, 5, 6
 MISSING_NONE, MISSING_MIN, MISSING_VALUE = 0, 1, 2    # adf_reproject_params.missing_mode (include/adf_wls.h)
 
 

@@ -28,7 +28,7 @@
 // by HBM: the views are read through L1/L2 once per disparity, HBM sees them once.
 //
 // Census cost (adf_bm_set_cost).  The pixel cost is a policy of the match kernel.  With
-// ADF_BM_COST_CENSUS_* the prefiltered views are replaced by the census descriptors (census.h) of the raw views, split into
+// ADF_BM_COST_CENSUS_* / _MCT_* the prefiltered views are replaced by the census descriptors (census.h) of the raw views, split into
 // P = ceil(bits / 8) byte planes in the same row-group interleaved layout (plane p holds bits 8p .. 8p+7, no +1 bias),
 // and the vertical sum of four rows of a column is popcount((L ^ R) & window_mask), added up over the groups and over
 // the planes.  A one-plane descriptor keeps its left columns in registers as SAD does; wider ones reload them per plane
@@ -91,10 +91,11 @@ __global__ void __launch_bounds__(CENSUS_THREADS) bm_census_pack_kernel(CensusPa
     constexpr int GROUPS = CENSUS_TILE_H / 4;                  // row groups of a tile: one per wave
     static_assert(GROUPS * 64 == CENSUS_THREADS);
     __shared__ uint8_t tile[S::LH][S::LW];
+    __shared__ uint16_t sums[S::SH][S::SW];                    // the mean rule's column sums; not referenced by the other rules
     const int view = blockIdx.z & 1;
     const unsigned pz = blockIdx.z >> 1;
     const int x0 = blockIdx.x * CENSUS_TILE_W, gp0 = blockIdx.y * GROUPS, y0 = 4 * (gp0 - PG);
-    census_tile_load<S>(tile, a.src[view] + (ptrdiff_t)pz * a.pair_stride[view], a.stride[view], x0, y0, a.W, a.H);
+    census_tile_load<S>(tile, sums, a.src[view] + (ptrdiff_t)pz * a.pair_stride[view], a.stride[view], x0, y0, a.W, a.H);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int x = x0 + lane, gp = gp0 + wv;
     if (x >= a.W || gp >= a.HGP) return;
@@ -104,7 +105,7 @@ __global__ void __launch_bounds__(CENSUS_THREADS) bm_census_pack_kernel(CensusPa
 #pragma unroll
     for (int b = 0; b < 4; b++) {
         uint32_t hi, lo;
-        census_compare<S>(tile, 4 * wv + b, lane, hi, lo);
+        census_compare<S>(tile, sums, 4 * wv + b, lane, hi, lo);
 #pragma unroll
         for (int p = 0; p < S::PLANES; p++) out[p] |= (((p < 4 ? lo >> (8 * p) : hi >> (8 * (p - 4)))) & 0xFFu) << (8 * b);
     }

@@ -12,6 +12,10 @@
 // pixels unwritten (descriptor.hpp:222).  Here neighbour coordinates are clamped to the image (replicated edge), so every
 // pixel has a descriptor, and the offset (0, 0) is skipped where the grid passes through it.
 //
+// Two more comparison rules run through the same kernel (census.h, CensusRule): the modified census
+// transform (Froeba & Ernst 2004; ADF_SGBM_COST_MCT_*: neighbours against the window mean) and the centre-symmetric census
+// (Spangenberg et al. 2013; ADF_SGBM_COST_CENSUS_CS: neighbours against their mirror image, half the bits).
+//
 // Bit order: rows top to bottom, left to right within a row; the first comparison is bit nbits-1, the upper 64 - nbits
 // bits are zero.  One uint64 per pixel.
 #include "census.h"
@@ -26,14 +30,16 @@ struct CensusArgs {
     int W, H;
 };
 
-// One workgroup: the 64 x 16 tile plus its K/2 halo on every side in LDS (census_tile_load), then one pixel per lane and
-// sweep: the descriptor's compares (census_compare) and one 8-byte store per lane.
+// One workgroup: the 64 x 16 tile plus its K/2 halo on every side in LDS (census_tile_load; with the window-mean rule
+// also the tile's column sums), then one pixel per lane and sweep: the descriptor's compares (census_compare) and one
+// 8-byte store per lane.
 template <class S>
 __global__ void __launch_bounds__(CENSUS_THREADS) census_kernel(CensusArgs a)
 {
     __shared__ uint8_t tile[S::LH][S::LW];
+    __shared__ uint16_t sums[S::SH][S::SW];                    // the mean rule's column sums; not referenced by the other rules
     const int x0 = blockIdx.x * CENSUS_TILE_W, y0 = blockIdx.y * CENSUS_TILE_H;
-    census_tile_load<S>(tile, a.src + (ptrdiff_t)blockIdx.z * a.simage, a.sstride, x0, y0, a.W, a.H);
+    census_tile_load<S>(tile, sums, a.src + (ptrdiff_t)blockIdx.z * a.simage, a.sstride, x0, y0, a.W, a.H);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int x = x0 + lane;
     if (x >= a.W) return;
@@ -41,7 +47,7 @@ __global__ void __launch_bounds__(CENSUS_THREADS) census_kernel(CensusArgs a)
         const int y = y0 + r;
         if (y >= a.H) break;
         uint32_t hi, lo;
-        census_compare<S>(tile, r, lane, hi, lo);
+        census_compare<S>(tile, sums, r, lane, hi, lo);
         uint64_t* row = reinterpret_cast<uint64_t*>(reinterpret_cast<char*>(a.dst) + (ptrdiff_t)blockIdx.z * a.dimage + (ptrdiff_t)y * a.dstride);
         row[x] = ((uint64_t)hi << 32) | lo;
     }
@@ -63,11 +69,12 @@ int census_args_check(int n, const void* src, ptrdiff_t sstride, ptrdiff_t simag
 
 int adf::census_check(int census_type, int k)
 {
-    if (census_type != ADF_SGBM_COST_CENSUS_DENSE && census_type != ADF_SGBM_COST_CENSUS_SPARSE)
-        return fail(ADF_EBADARG, "census type %d is not ADF_SGBM_COST_CENSUS_DENSE or ADF_SGBM_COST_CENSUS_SPARSE", census_type);
+    if (census_type < ADF_SGBM_COST_CENSUS_DENSE || census_type > ADF_SGBM_COST_CENSUS_CS || census_type == 3)
+        return fail(ADF_EBADARG, "census type %d is not ADF_SGBM_COST_CENSUS_DENSE (1), ADF_SGBM_COST_CENSUS_SPARSE (2), ADF_SGBM_COST_MCT_DENSE (4), "
+                                 "ADF_SGBM_COST_MCT_SPARSE (5) or ADF_SGBM_COST_CENSUS_CS (6)", census_type);
     if (census_bits(census_type, k) == 0)
-        return fail(ADF_EBADARG, "census size %d is not supported: odd, 3..7 for the dense and 5..11 for the sparse descriptor "
-                                 "(at most 48 bits)", k);
+        return fail(ADF_EBADARG, "census size %d is not supported: odd, 3..7 for the dense, 5..11 for the sparse (census and modified census) "
+                                 "and 3..9 for the centre-symmetric descriptor (at most 48 bits)", k);
     return ADF_OK;
 }
 

@@ -31,6 +31,8 @@ import numpy as np
 from . import _lib
 from ._lib import SGBM_COST_BT, SGBM_COST_CENSUS_DENSE, SGBM_COST_CENSUS_SPARSE  # noqa: F401  (re-exported)
 from ._lib import BM_COST_SAD, BM_COST_CENSUS_DENSE, BM_COST_CENSUS_SPARSE  # noqa: F401  (re-exported)
+from ._lib import SGBM_COST_MCT_DENSE, SGBM_COST_MCT_SPARSE, SGBM_COST_CENSUS_CS  # noqa: F401  (re-exported)
+from ._lib import BM_COST_MCT_DENSE, BM_COST_MCT_SPARSE, BM_COST_CENSUS_CS  # noqa: F401  (re-exported)
 from ._lib import AdfError, PATH_CONF_BAND, PATH_FUSED_FIRST_PASS, PATH_MERGED_PREP, PATH_ROW_WEIGHTS_GUIDE, PATH_SCALED_FUSED, PATH_SCALED_HALF, Rect, SOLVER_EXACT, SOLVER_WAVE  # noqa: F401  (re-exported)
 
 try:  # torch is optional plumbing: device memory and streams only
@@ -415,7 +417,10 @@ class StereoBM(StereoMatcher):
     ignores gain and exposure differences between the cameras.  preFilterCap and textureThreshold are validated as
     with SAD and NOT USED with a census cost: there is no prefiltered image whose texture could be summed.  Bit-exact
     against the direct statement tests/bm_census_ref.py.  The library checks the pair (type, size) when compute()
-    pushes it."""
+    pushes it.  Descriptors: BM_COST_CENSUS_DENSE (k 3, 5, 7), BM_COST_CENSUS_SPARSE (5, 7, 9, 11), the modified census
+    BM_COST_MCT_DENSE (3, 5, 7) / BM_COST_MCT_SPARSE (5, 7, 9, 11: neighbours against the window mean) and the
+    centre-symmetric BM_COST_CENSUS_CS (3, 5, 7, 9: 4 / 12 / 24 / 40 bits, neighbours against their mirror image); see
+    censusTransform.  The matcher's time follows the descriptor's byte planes, ceil(bits / 8)."""
     _destroy, _entry = "adf_bm_destroy", "adf_bm_compute"
 
     def __init__(self, numDisparities=0, blockSize=21):
@@ -491,7 +496,10 @@ class StereoSGBM(StereoMatcher):
     Extension: setCostType(SGBM_COST_CENSUS_DENSE / _SPARSE) + setCensusSize(k) match on census descriptors with a Hamming
     distance, the cost of the reference's own cv::stereo::StereoBinarySGBM (its setBinaryKernelType / kernelSize;
     include/adf_wls.h: adf_sgbm_set_cost).  CV_8UC1 views only; preFilterCap is ignored; bit-exact against the direct
-    statement tests/census_ref.py.  The library checks the pair (type, size) when compute() pushes it."""
+    statement tests/census_ref.py.  The library checks the pair (type, size) when compute() pushes it.  Descriptors:
+    SGBM_COST_CENSUS_DENSE (k 3, 5, 7), SGBM_COST_CENSUS_SPARSE (5, 7, 9, 11), the modified census SGBM_COST_MCT_DENSE
+    (3, 5, 7) / SGBM_COST_MCT_SPARSE (5, 7, 9, 11: neighbours against the window mean) and the centre-symmetric
+    SGBM_COST_CENSUS_CS (3, 5, 7, 9: neighbours against their mirror image); see censusTransform."""
     MODE_SGBM, MODE_HH, MODE_SGBM_3WAY = 0, 1, 2
     _destroy, _entry, _channels = "adf_sgbm_destroy", "adf_sgbm_compute", (1, 3)
 
@@ -585,7 +593,11 @@ def filterSpeckles(img, newVal, maxSpeckleSize, maxDiff, buf=None):
 def censusTransform(image, kernelSize, type, dst=None):
     """cv::stereo::censusTransform(image, kernelSize, dist, type) (descriptor.hpp:428, descriptor.cpp:77-98): the census
     descriptor of every pixel of a CV_8UC1 image (H,W) or a batch (N,H,W), `type` SGBM_COST_CENSUS_DENSE (kernelSize 3, 5,
-    7: 8 / 24 / 48 bits) or SGBM_COST_CENSUS_SPARSE (5, 7, 9, 11: 8 / 16 / 24 / 36 bits); the definition (replicated
+    7: 8 / 24 / 48 bits) or SGBM_COST_CENSUS_SPARSE (5, 7, 9, 11: 8 / 16 / 24 / 36 bits); SGBM_COST_MCT_DENSE /
+    SGBM_COST_MCT_SPARSE, the modified census transform (same grids, sizes and bit counts; a bit is
+    k*k*neighbour > sum of the whole clamped k x k window, centre included); or SGBM_COST_CENSUS_CS, the centre-symmetric
+    census (3, 5, 7, 9: 4 / 12 / 24 / 40 bits; the offsets before (0, 0) in raster order, a bit is neighbour > its
+    mirror image through the centre).  The BM_COST_* twins have the same values.  The definition (replicated
     edge, bit order) is the library's own: include/adf_wls.h.  A numpy image gives an np.uint64 array through the host
     entry; a torch CUDA tensor gives an int64 tensor carrying the same bit pattern, on the device and asynchronously on
     torch's current stream.  `dst`: an output of that type and shape to write into."""

@@ -362,7 +362,10 @@ int adf_bm_get_params(const adf_bm_t* h, int* min_disparity, int* num_disparitie
 /* The matching cost.  The reference's own block matcher, cv::stereo::StereoBinaryBM, matches census descriptors with a
  * Hamming distance (modules/stereo/src/stereo_binary_bm.cpp:367-408; setBinaryKernelType, kernelSize).  With a census cost
  *   cL, cR      = adf_census_transform_* (below) of the left and the right CV_8UC1 view at (cost_type, census_size):
- *                 dense 3 / 5 / 7, sparse 5 / 7 / 9 / 11; neighbour coordinates clamped, so every pixel has a descriptor;
+ *                 dense 3 / 5 / 7, sparse 5 / 7 / 9 / 11, modified census (ADF_BM_COST_MCT_DENSE 3 / 5 / 7, _MCT_SPARSE
+ *                 5 / 7 / 9 / 11: k * k * neighbour > window sum), centre-symmetric (ADF_BM_COST_CENSUS_CS 3 / 5 / 7 / 9:
+ *                 neighbour > mirrored neighbour, 4 / 12 / 24 / 40 bits); neighbour coordinates clamped, so every
+ *                 pixel has a descriptor; the matcher's time follows the byte planes, ceil(bits / 8);
  *   pixel cost  = popcount(cL(y, x) ^ cR(y, x - d));
  *   block cost  = S[k][x], the sum of the pixel cost over the full blockSize x blockSize window, d = minDisparity + k
  *                 (at most 21 * 21 * 48 = 21168);
@@ -374,12 +377,16 @@ int adf_bm_get_params(const adf_bm_t* h, int* min_disparity, int* num_disparitie
  * disparity_filters.cpp:399-400).  The definition is this library's own -- bit-exact against the direct statement
  * tests/bm_census_ref.py, NOT against the in-tree StereoBinaryBM, whose descriptors are no usable bit-level oracle (see
  * adf_census_transform_*) and whose median filters and 8-bit output are not built.
- * ADF_BM_COST_CENSUS_* equal ADF_SGBM_COST_CENSUS_*, which are accepted too.  An unknown (cost_type, census_size) pair is
+ * ADF_BM_COST_CENSUS_* / _MCT_* equal ADF_SGBM_COST_CENSUS_* / _MCT_*, which are accepted too.  An unknown (cost_type, census_size) pair is
  * ADF_EBADARG and the handle keeps its cost; census_size is ignored, and left as it was, with ADF_BM_COST_SAD.  A handle
  * may change cost between calls; adf_bm_compute_both_device shares the descriptor planes between the two views. */
 #define ADF_BM_COST_SAD 0            /* cv::StereoBM's SAD on the x-Sobel prefiltered views (default) */
 #define ADF_BM_COST_CENSUS_DENSE 1   /* cv::stereo CV_DENSE_CENSUS, census_size 3, 5, 7 */
 #define ADF_BM_COST_CENSUS_SPARSE 2  /* cv::stereo CV_SPARSE_CENSUS, census_size 5, 7, 9, 11 */
+/* (3 and 7 stay unassigned, as with ADF_SGBM_COST_*: callers rely on their being refused) */
+#define ADF_BM_COST_MCT_DENSE 4      /* modified census (window mean), dense grid, census_size 3, 5, 7 */
+#define ADF_BM_COST_MCT_SPARSE 5     /* modified census (window mean), sparse grid, census_size 5, 7, 9, 11 */
+#define ADF_BM_COST_CENSUS_CS 6      /* cv::stereo CV_CS_CENSUS, centre-symmetric, census_size 3, 5, 7, 9 */
 int adf_bm_set_cost(adf_bm_t* h, int cost_type, int census_size);
 int adf_bm_get_cost(const adf_bm_t* h, int* cost_type, int* census_size); /* a new handle: ADF_BM_COST_SAD, 7 */
 /* StereoMatcher::compute(left, right, disparity) on a batch of n_pairs equally sized CV_8UC1 pairs laid out
@@ -443,7 +450,9 @@ int adf_sgbm_get_params(const adf_sgbm_t* h, int* min_disparity, int* num_dispar
  * descriptors with a Hamming distance (modules/stereo/src/stereo_binary_sgbm.cpp; setBinaryKernelType, stereo.hpp:227-228;
  * descriptor.cpp:54-75), and its test is this library's anchor (test_block_matching.cpp:157-238).  With a census cost
  *   pixel cost  = popcount(census(left)(y, x) ^ census(right)(y, x - d)), the descriptors of adf_census_transform_*
- *                 below at (cost_type, census_size);
+ *                 below at (cost_type, census_size): census dense 3 / 5 / 7 and sparse 5 / 7 / 9 / 11, modified census
+ *                 (ADF_SGBM_COST_MCT_DENSE 3 / 5 / 7, _MCT_SPARSE 5 / 7 / 9 / 11), centre-symmetric census
+ *                 (ADF_SGBM_COST_CENSUS_CS 3 / 5 / 7 / 9);
  *   block cost  = the sum of pixel costs over the blockSize x blockSize window, window coordinates clamped to the rows
  *                 [0, H) and to the matchable columns -- the rule of the Birchfield-Tomasi path, at most 11*11*48;
  * and everything from the cost volume on (paths, winner, uniqueness, sub-pixel fit, left-right check, median) is the
@@ -456,6 +465,13 @@ int adf_sgbm_get_params(const adf_sgbm_t* h, int* min_disparity, int* num_dispar
 #define ADF_SGBM_COST_BT 0            /* cv::StereoSGBM's Birchfield-Tomasi block cost (default) */
 #define ADF_SGBM_COST_CENSUS_DENSE 1  /* cv::stereo CV_DENSE_CENSUS (descriptor.hpp:58, descriptor.cpp:65-69), census_size 3, 5, 7 */
 #define ADF_SGBM_COST_CENSUS_SPARSE 2 /* cv::stereo CV_SPARSE_CENSUS (descriptor.cpp:70-74), census_size 5, 7, 9, 11 */
+/* 3 and 7 stay unassigned: callers (and this library's tests) rely on (3, 5) and (7, 5) being refused as unknown types, so
+ * the newer descriptors start at 4. */
+#define ADF_SGBM_COST_MCT_DENSE 4     /* modified census transform (Froeba & Ernst 2004; cv::stereo CV_MODIFIED_CENSUS_TRANSFORM's
+                                         rule): neighbours against the window mean, dense grid, census_size 3, 5, 7 */
+#define ADF_SGBM_COST_MCT_SPARSE 5    /* the same rule on the sparse grid, census_size 5, 7, 9, 11 */
+#define ADF_SGBM_COST_CENSUS_CS 6     /* centre-symmetric census (Spangenberg et al. 2013; cv::stereo CV_CS_CENSUS,
+                                         descriptor.hpp:59): neighbours against their mirror image, census_size 3, 5, 7, 9 */
 int adf_sgbm_set_cost(adf_sgbm_t* h, int cost_type, int census_size);
 int adf_sgbm_get_cost(const adf_sgbm_t* h, int* cost_type, int* census_size); /* a new handle: ADF_SGBM_COST_BT, 7 */
 /* StereoMatcher::compute(left, right, disparity) on n_pairs equally sized CV_8UC1 / CV_8UC3 pairs (`channels`);
@@ -476,7 +492,8 @@ int adf_sgbm_compute_host(adf_sgbm_t* h, int n_pairs,
  * cv::stereo::censusTransform(image, kernelSize, dist, type) (descriptor.hpp:428, descriptor.cpp:77-98) on n_images
  * equally sized CV_8UC1 images, rows `src_stride` and images `src_image_stride` bytes apart: the published transform
  * (Zabih & Woodfill 1994), one uint64 descriptor per pixel, rows `dst_stride` and images `dst_image_stride` bytes apart.
- * census_type is ADF_SGBM_COST_CENSUS_DENSE or _SPARSE, census_size the odd window size k, n2 = k / 2:
+ * census_type is one of ADF_SGBM_COST_CENSUS_DENSE, _CENSUS_SPARSE, _MCT_DENSE, _MCT_SPARSE, _CENSUS_CS (or its
+ * ADF_BM_COST_* twin), census_size the odd window size k, n2 = k / 2:
  *   - dense (descriptor.cpp:65-69): offsets -n2 .. n2 in both directions, k in {3, 5, 7}: 8 / 24 / 48 bits;
  *   - sparse (every second pixel, descriptor.cpp:70-74): offsets -n2, -n2 + 2, ... <= n2, k in {5, 7, 9, 11}:
  *     8 / 16 / 24 / 36 bits;
@@ -485,6 +502,18 @@ int adf_sgbm_compute_host(adf_sgbm_t* h, int n_pairs,
  *     smaller than the window;
  *   - bit order: rows top to bottom, left to right within a row; the first comparison is the most significant of the
  *     bits used, the upper bits are zero.
+ * Two more comparison rules run on the same clamped window, in the same raster order, with the same bit order and the
+ * same strict `>` (stated directly in tests/census_variants_ref.py; the device is bit-exact against it):
+ *   - ADF_SGBM_COST_MCT_DENSE, k in {3, 5, 7}, and ADF_SGBM_COST_MCT_SPARSE, k in {5, 7, 9, 11}: the modified census
+ *     transform (Froeba & Ernst 2004; the rule of cv::stereo's CV_MODIFIED_CENSUS_TRANSFORM).  The offsets, hence the bit
+ *     counts (8 / 24 / 48; 8 / 16 / 24 / 36), are the dense / sparse ones above, (0, 0) skipped.  S is the sum of all
+ *     k * k pixels of the clamped k x k window around the pixel, centre included (the sparse grids use the full window
+ *     too); a bit is 1 when k * k * p(y+dy, x+dx) > S: integers, no division, no rounding rule, at most 121 * 255.
+ *   - ADF_SGBM_COST_CENSUS_CS, k in {3, 5, 7, 9}: the centre-symmetric census (Spangenberg et al. 2013; cv::stereo's
+ *     CV_CS_CENSUS).  The offsets are the first half of the window in raster order: every dx in [-n2, n2] for dy in
+ *     [-n2, -1], then dx in [-n2, -1] for dy = 0; a bit is 1 when p(y+dy, x+dx) > p(y-dy, x-dx), both coordinates
+ *     clamped: 4 / 12 / 24 / 40 bits.  k = 11 would take 60 bits and is refused (at most 48).
+ *   Not built: cv::stereo's CV_MODIFIED_CS_CENSUS, CV_MEAN_VARIATION and CV_STAR_KERNEL, and the modified census's threshold.
  * This is the library's OWN definition, not bit parity with the in-tree code, which is no usable bit-level oracle: its
  * row ranges read one row past Range::end (descriptor.hpp:219), it compares a row offset with a row index where it
  * means to skip the centre (`ii != i`, descriptor.hpp:234), and it leaves the border pixels unwritten (:222); it keeps

@@ -106,7 +106,9 @@ inline void filterSpeckles(Mat& img, double newVal, int maxSpeckleSize, double m
 
 // cv::stereo::censusTransform(image, kernelSize, dist, type) (modules/stereo descriptor.hpp:428, descriptor.cpp:77-98) on a
 // CV_8UC1 host Mat, through the library's host entry: the census descriptor of every pixel, type
-// ADF_SGBM_COST_CENSUS_DENSE (kernelSize 3, 5, 7) or ADF_SGBM_COST_CENSUS_SPARSE (5, 7, 9, 11); definition, bit order
+// ADF_SGBM_COST_CENSUS_DENSE (kernelSize 3, 5, 7), ADF_SGBM_COST_CENSUS_SPARSE (5, 7, 9, 11), the modified census
+// ADF_SGBM_COST_MCT_DENSE (3, 5, 7) / ADF_SGBM_COST_MCT_SPARSE (5, 7, 9, 11) or the centre-symmetric
+// ADF_SGBM_COST_CENSUS_CS (3, 5, 7, 9); definition, bit order
 // and why it is not bit parity with the in-tree code: adf_census_transform_* in adf_wls.h.  A descriptor has up to 48
 // bits, and cv::Mat has no 64-bit integer depth, so dist is CV_32SC2: one uint64 per pixel in the machine's byte order
 // (channel 0 the low half), read with dist.ptr<uint64_t>(y)[x].
@@ -593,6 +595,7 @@ public:
     // extension (adf_bm_set_cost in adf_wls.h): ADF_BM_COST_SAD, or a census descriptor + Hamming distance, the cost of
     // the reference's own cv::stereo::StereoBinaryBM; preFilterCap and textureThreshold are validated and not used with
     // it (there is no prefiltered image).  The library checks the pair (type, size) when compute() pushes it.
+    // Descriptors: ADF_BM_COST_CENSUS_DENSE / _CENSUS_SPARSE / _MCT_DENSE / _MCT_SPARSE / _CENSUS_CS (sizes: adf_wls.h).
     int getCostType() const { return cost_; }                void setCostType(int v) { cost_ = v; }
     int getCensusSize() const { return census_size_; }       void setCensusSize(int v) { census_size_ = v; }
     // StereoMatcher::compute: CV_8UC1 views -> CV_16SC1 disparity * 16, rejected pixels (minDisparity - 1) * 16
@@ -675,7 +678,8 @@ public:
     int getDisp12MaxDiff() const { return disp12_; }         void setDisp12MaxDiff(int v) { disp12_ = v; }
     int getSpeckleWindowSize() const { return speckle_window_; } void setSpeckleWindowSize(int v) { speckle_window_ = v; }
     // extension (adf_sgbm_set_cost in adf_wls.h): ADF_SGBM_COST_BT, or a census descriptor + Hamming distance, the cost of
-    // cv::stereo::StereoBinarySGBM (its setBinaryKernelType / kernelSize); the pair is checked when compute() pushes it
+    // cv::stereo::StereoBinarySGBM (its setBinaryKernelType / kernelSize); the pair is checked when compute() pushes it.
+    // Descriptors: ADF_SGBM_COST_CENSUS_DENSE / _CENSUS_SPARSE / _MCT_DENSE / _MCT_SPARSE / _CENSUS_CS (sizes: adf_wls.h).
     int getCostType() const { return cost_; }                void setCostType(int v) { cost_ = v; }
     int getCensusSize() const { return census_size_; }       void setCensusSize(int v) { census_size_ = v; }
     // StereoMatcher::compute: CV_8UC1 / CV_8UC3 views -> CV_16SC1 disparity * 16, invalid pixels (minDisparity - 1) * 16

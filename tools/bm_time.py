@@ -1,9 +1,10 @@
 """Times the device block matcher (both views) on synthetic pairs:
-python tools/bm_time.py [--cost {sad,dense,sparse}] [--census-size K] [--against-sad] [--reps R] [W H ndisp wsz n [uniq texture]]
+python tools/bm_time.py [--cost {sad,dense,sparse,mct-dense,mct-sparse,cs}] [--census-size K] [--against-sad | --against COST:K] [--reps R] [W H ndisp wsz n [uniq texture]]
 (uniq / texture: uniquenessRatio and textureThreshold of the LEFT matcher, default 0 as the filter factory sets them;
 --cost: SAD on the x-Sobel prefiltered views (default) or a census descriptor with a Hamming distance, adf_bm_set_cost;
 --against-sad: a second handle runs the SAD cost, the two costs take turns with computeBoth -- the filter's settings, texture
-and uniqueness 0 -- and the median time of each and their ratio are printed)"""
+and uniqueness 0 -- and the median time of each and their ratio are printed; --against COST:K: the same with another
+census cost as the second handle, e.g. the descriptor with the same number of byte planes)"""
 import argparse
 import sys
 
@@ -13,11 +14,13 @@ import torch
 sys.path.insert(0, ".")
 import addingdisparityfiltering_amd as adf
 
-COST = {"sad": adf.BM_COST_SAD, "dense": adf.BM_COST_CENSUS_DENSE, "sparse": adf.BM_COST_CENSUS_SPARSE}
+COST = {"sad": adf.BM_COST_SAD, "dense": adf.BM_COST_CENSUS_DENSE, "sparse": adf.BM_COST_CENSUS_SPARSE,
+        "mct-dense": adf.BM_COST_MCT_DENSE, "mct-sparse": adf.BM_COST_MCT_SPARSE, "cs": adf.BM_COST_CENSUS_CS}
 ap = argparse.ArgumentParser()
 ap.add_argument("--cost", choices=tuple(COST), default="sad")
 ap.add_argument("--census-size", type=int, default=7)
 ap.add_argument("--against-sad", action="store_true")
+ap.add_argument("--against", metavar="COST:K", default=None)
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("shape", nargs="*")
 opt = ap.parse_args()
@@ -32,10 +35,10 @@ e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=Tr
 name = opt.cost if opt.cost == "sad" else "%s %d" % (opt.cost, opt.census_size)
 
 
-def matcher(cost):
+def matcher(cost, size=opt.census_size):
     m = adf.StereoBM.create(nd, wsz)
     m.setTextureThreshold(0); m.setUniquenessRatio(0)
-    m.setCostType(COST[cost]); m.setCensusSize(opt.census_size)
+    m.setCostType(COST[cost]); m.setCensusSize(size)
     return m
 
 
@@ -47,10 +50,15 @@ def timed(fn, reps):
     return e0.elapsed_time(e1) / reps
 
 
-if opt.against_sad:
+if opt.against_sad or opt.against:
     if opt.cost == "sad" or len(opt.shape) > 5:
-        sys.exit("--against-sad compares a census cost with SAD in the filter's configuration")
-    ms = {"sad": matcher("sad"), opt.cost: matcher(opt.cost)}
+        sys.exit("--against-sad / --against compare a census cost with another cost in the filter's configuration")
+    if opt.against:
+        bcost, bsize = opt.against.split(":")
+        base_name, base = "%s %s" % (bcost, bsize), matcher(bcost, int(bsize))
+    else:
+        base_name, base = "sad", matcher("sad")
+    ms = {base_name: base, name: matcher(opt.cost)}
     times = {c: [] for c in ms}
     for c, m in ms.items():                      # warm up: code objects, the view buffers
         for _ in range(2):
@@ -61,9 +69,9 @@ if opt.against_sad:
         for c, m in ms.items():
             times[c].append(timed(lambda: m.computeBoth(left, right, dl, dr), inner))
     med = {c: float(np.median(t)) for c, t in times.items()}
-    print("matcher both views, one launch: %dx%d ndisp %d block %d, %d pairs: sad %.3f ms (min %.3f max %.3f), %s %.3f ms "
-          "(min %.3f max %.3f), ratio %.3f" % (W, H, nd, wsz, n, med["sad"], min(times["sad"]), max(times["sad"]), name, med[opt.cost],
-                                              min(times[opt.cost]), max(times[opt.cost]), med[opt.cost] / med["sad"]))
+    print("matcher both views, one launch: %dx%d ndisp %d block %d, %d pairs: %s %.3f ms (min %.3f max %.3f), %s %.3f ms "
+          "(min %.3f max %.3f), ratio %.3f" % (W, H, nd, wsz, n, base_name, med[base_name], min(times[base_name]), max(times[base_name]), name,
+                                              med[name], min(times[name]), max(times[name]), med[name] / med[base_name]))
     sys.exit(0)
 
 lm = matcher(opt.cost)

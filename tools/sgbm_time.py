@@ -1,5 +1,5 @@
 """Times the device semi-global matcher (left view, then the right-view matcher of createRightMatcher) on synthetic
-pairs: python tools/sgbm_time.py [--cost {bt,dense,sparse}] [--census-size K] [--against-bt] [--reps R] [W H ndisp block n channels mode]
+pairs: python tools/sgbm_time.py [--cost {bt,dense,sparse,mct-dense,mct-sparse,cs}] [--census-size K] [--against-bt] [--reps R] [W H ndisp block n channels mode]
 (mode: 2 = MODE_SGBM_3WAY (default), 0 = MODE_SGBM, 1 = MODE_HH; --cost: the Birchfield-Tomasi block cost (default) or a
 census descriptor with a Hamming distance, adf_sgbm_set_cost; --against-bt: the same two handles also run the
 Birchfield-Tomasi cost, the two costs taking turns, and the ratio of the two whole compute() times is printed)"""
@@ -13,7 +13,7 @@ sys.path.insert(0, ".")
 import addingdisparityfiltering_amd as adf
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--cost", choices=("bt", "dense", "sparse"), default="bt")
+ap.add_argument("--cost", choices=("bt", "dense", "sparse", "mct-dense", "mct-sparse", "cs"), default="bt")
 ap.add_argument("--census-size", type=int, default=7)
 ap.add_argument("--against-bt", action="store_true")
 ap.add_argument("--reps", type=int, default=2)
@@ -30,7 +30,8 @@ lm.setP1(24 * bs * bs); lm.setP2(96 * bs * bs); lm.setPreFilterCap(63); lm.setMo
 lm.setCensusSize(opt.census_size)
 wls = adf.createDisparityWLSFilter(lm)                 # samples/disparity_filtering.cpp:166-172
 rm = adf.createRightMatcher(lm)
-COST = {"bt": adf.SGBM_COST_BT, "dense": adf.SGBM_COST_CENSUS_DENSE, "sparse": adf.SGBM_COST_CENSUS_SPARSE}
+COST = {"bt": adf.SGBM_COST_BT, "dense": adf.SGBM_COST_CENSUS_DENSE, "sparse": adf.SGBM_COST_CENSUS_SPARSE,
+        "mct-dense": adf.SGBM_COST_MCT_DENSE, "mct-sparse": adf.SGBM_COST_MCT_SPARSE, "cs": adf.SGBM_COST_CENSUS_CS}
 costs = ["bt", opt.cost] if opt.against_bt and opt.cost != "bt" else [opt.cost]
 dl = torch.empty((n, H, W), dtype=torch.int16, device="cuda")
 dr = torch.empty_like(dl)
