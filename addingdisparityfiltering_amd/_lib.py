@@ -14,7 +14,7 @@ ADF_OK, ADF_EBADARG, ADF_ESIZE, ADF_EHIP, ADF_ENOMEM, ADF_ENODEV = range(6)
 SOLVER_EXACT, SOLVER_WAVE = 0, 1
 PATH_CONF_BAND, PATH_FUSED_FIRST_PASS, PATH_MERGED_PREP, PATH_SCALED_FUSED, PATH_SCALED_HALF = 1, 2, 4, 8, 16    # adf_wls_get_last_path bits (include/adf_wls.h)
 PATH_ROW_WEIGHTS_GUIDE = 32    # adf_wls_get_last_solver_path bit
-DEPTH_8U, DEPTH_16S, DEPTH_32F = 0, 3, 5
+DEPTH_8U, DEPTH_16S, DEPTH_32S, DEPTH_32F = 0, 3, 4, 5
 SGBM_COST_BT, SGBM_COST_CENSUS_DENSE, SGBM_COST_CENSUS_SPARSE = 0, 1, 2    # adf_sgbm_set_cost (include/adf_wls.h)
 BM_COST_SAD, BM_COST_CENSUS_DENSE, BM_COST_CENSUS_SPARSE = 0, 1, 2    # adf_bm_set_cost (the census values equal SGBM_COST_CENSUS_*)
 # modified census (window mean) on the dense / the sparse grid, centre-symmetric census; 3 and 7 stay unassigned (include/adf_wls.h)
@@ -125,6 +125,9 @@ SYMBOLS = [
     ("adf_bm_compute_device", _i, [_vp, _i, _vp, _pd, _pd, _vp, _pd, _pd, _i, _i, _vp, _pd, _pd, _vp]),
     ("adf_bm_compute_both_device", _i, [_vp, _i, _vp, _pd, _pd, _vp, _pd, _pd, _i, _i, _vp, _pd, _pd, _vp, _pd, _pd, _vp]),
     ("adf_bm_compute_host", _i, [_vp, _i, _vp, _pd, _pd, _vp, _pd, _pd, _i, _i, _vp, _pd, _pd]),
+    ("adf_bm_compute_cost_device", _i, [_vp, _i, _vp, _pd, _pd, _vp, _pd, _pd, _i, _i, _vp, _pd, _pd, _vp, _pd, _pd, _vp]),
+    ("adf_bm_compute_cost_host", _i, [_vp, _i, _vp, _pd, _pd, _vp, _pd, _pd, _i, _i, _vp, _pd, _pd, _vp, _pd, _pd]),
+    ("adf_bm_compute_both_cost_device", _i, [_vp, _i, _vp, _pd, _pd, _vp, _pd, _pd, _i, _i] + [_vp, _pd, _pd] * 4 + [_vp]),
     ("adf_sgbm_create", _i, [C.POINTER(_vp), _i, _i, _i]),
     ("adf_sgbm_destroy", None, [_vp]),
     ("adf_sgbm_get_device", _i, [_vp, C.POINTER(_i)]),
@@ -141,6 +144,8 @@ SYMBOLS = [
     ("adf_filter_speckles_workspace_bytes", _sz, [_i, _i, _i]),
     ("adf_filter_speckles_device", _i, [_i, _vp, _pd, _pd, _i, _i, _i, _i, _i, _vp, _sz, _vp]),
     ("adf_filter_speckles_host", _i, [_i, _vp, _pd, _pd, _i, _i, _i, _i, _i]),
+    ("adf_validate_disparity_device", _i, [_i, _vp, _pd, _pd, _vp, _pd, _pd, _i, _i, _i, _i, _i, _i, _vp]),
+    ("adf_validate_disparity_host", _i, [_i, _vp, _pd, _pd, _vp, _pd, _pd, _i, _i, _i, _i, _i, _i]),
     ("adf_half_size", _i, [_i, C.POINTER(_i)]),
     ("adf_prepare_views_device", _i, [_i, _vp, _pd, _pd, _i, _i, _i, _vp, _pd, _pd, _i, _i, _i, _vp]),
     ("adf_prepare_views_host", _i, [_i, _vp, _pd, _pd, _i, _i, _i, _vp, _pd, _pd, _i, _i, _i]),

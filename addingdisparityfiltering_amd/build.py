@@ -21,6 +21,7 @@ SOURCES = {
     "sgbm_matcher.hip": [],
     "census_kernels.hip": [],
     "speckle_kernels.hip": [],
+    "validate_kernels.hip": [],
     "view_prep_kernels.hip": [],
     "reproject_kernels.hip": [],
     "rectify_kernels.hip": [],

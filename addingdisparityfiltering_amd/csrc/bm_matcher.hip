@@ -23,7 +23,10 @@
 // over the tile's columns, the neighbours' prefix vectors come through a per-wave LDS slot, and the winner is
 // tracked a pair of disparities at a time: the winner pair and the pairs before / after it are captured as whole
 // registers (for the uniqueness test also the smallest pair minimum two or more pairs away), and which half won
-// is decided once at the end.  Nothing but the int16 result is written.
+// is decided once at the end.  Nothing but the int16 result is written -- and, for a caller that passes a cost plane
+// (adf_bm_compute_cost_*), the aggregated cost of the winning integer disparity beside it, truncated to 16 bits; 0 where the
+// map holds the filtered value.  The plane pointer is uniform over the launch: the existing entry points pass null and pay
+// one scalar test per output row.
 // The kernel is bound by integer VALU issue (about 11 instructions per pixel and disparity; EXPERIMENTS.md section 10), not
 // by HBM: the views are read through L1/L2 once per disparity, HBM sees them once.
 //
@@ -118,6 +121,7 @@ __global__ void __launch_bounds__(CENSUS_THREADS) bm_census_pack_kernel(CensusPa
 struct ViewArgs {
     const uint32_t* Lt; const uint32_t* Rt;                  // prefiltered views (census: descriptor planes), t_pair dwords per image
     int16_t* disp; ptrdiff_t dstride, dpair;                 // bytes
+    int16_t* cost; ptrdiff_t cstride, cpair;                 // the winner's cost, CV_16S like calib3d's cost map; null: not wanted
     int mindisp;
     int xs, xe;            // matched columns [xs, xe)
     int texthr, uniq;
@@ -407,6 +411,7 @@ __global__ void __launch_bounds__(256) bm_match_kernel(MatchArgs a)
         const int y = 4 * g + r;
         if (y >= a.H) continue;
         int16_t* drow = reinterpret_cast<int16_t*>(reinterpret_cast<char*>(va.disp) + (ptrdiff_t)pz * va.dpair + (ptrdiff_t)y * va.dstride);
+        int16_t* crow = va.cost ? reinterpret_cast<int16_t*>(reinterpret_cast<char*>(va.cost) + (ptrdiff_t)pz * va.cpair + (ptrdiff_t)y * va.cstride) : nullptr;
 #pragma unroll
         for (int j = 0; j < CPL; j++) {
             const int t = lane * CPL + j;
@@ -433,11 +438,12 @@ __global__ void __launch_bounds__(256) bm_match_kernel(MatchArgs a)
                 if ((int)other <= thresh) out = filtered;
             }
             drow[c + j] = out;
+            if (crow) crow[c + j] = out != filtered ? (int16_t)sb : (int16_t)0;   // sb: the cost at kb, before the sub-pixel fit
         }
     }
 }
 
-// columns without a full search range or window: (minDisparity - 1) * 16
+// columns without a full search range or window: (minDisparity - 1) * 16, and 0 in the cost plane
 __global__ void __launch_bounds__(256) bm_border_kernel(MatchArgs a)
 {
     const int y = blockIdx.y;
@@ -449,6 +455,9 @@ __global__ void __launch_bounds__(256) bm_border_kernel(MatchArgs a)
     const int16_t filtered = (int16_t)((va.mindisp - 1) * 16);
     int16_t* row = reinterpret_cast<int16_t*>(reinterpret_cast<char*>(va.disp) + (ptrdiff_t)pz * va.dpair + (ptrdiff_t)y * va.dstride);
     for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) row[i < nleft ? i : xr + (i - nleft)] = filtered;
+    if (!va.cost) return;
+    int16_t* crow = reinterpret_cast<int16_t*>(reinterpret_cast<char*>(va.cost) + (ptrdiff_t)pz * va.cpair + (ptrdiff_t)y * va.cstride);
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) crow[i < nleft ? i : xr + (i - nleft)] = 0;
 }
 
 template <bool UNIQ, class COST>
@@ -574,14 +583,28 @@ static int bm_check(const adf_bm* h, int n, const void* l, const void* r, const 
     return ADF_OK;
 }
 
+// An optional cost plane of a call (p == NULL: not wanted): rows `stride`, pairs `pair` bytes apart.
+struct CostPlane { int16_t* p; ptrdiff_t stride, pair; };
+static const CostPlane NO_COST{nullptr, 0, 0};
+
+static int bm_cost_check(const CostPlane& c, const char* which, int n_pairs, int W)
+{
+    if (!c.p) return fail(ADF_EBADARG, "%s cost plane is NULL", which);
+    if (c.stride < (ptrdiff_t)W * 2) return fail(ADF_ESIZE, "%s cost plane: row stride smaller than a row", which);
+    if ((c.stride & 1) || (reinterpret_cast<uintptr_t>(c.p) & 1) || (n_pairs > 1 && (c.pair & 1)))
+        return fail(ADF_ESIZE, "%s cost plane must be 2-byte aligned", which);
+    return ADF_OK;
+}
+
 // Shared body: prefilter both images once (census: form their descriptor planes), then one launch for the left view
-// alone (disp_right == NULL) or for both views.
+// alone (disp_right == NULL) or for both views; each view with or without its cost plane.
 static int bm_compute_impl(adf_bm_t* h, int n_pairs,
                            const uint8_t* left, ptrdiff_t left_stride, ptrdiff_t left_pair_stride,
                            const uint8_t* right, ptrdiff_t right_stride, ptrdiff_t right_pair_stride,
                            int W, int H,
                            int16_t* disp_left, ptrdiff_t dl_stride, ptrdiff_t dl_pair_stride,
                            int16_t* disp_right, ptrdiff_t dr_stride, ptrdiff_t dr_pair_stride,
+                           const CostPlane& cost_left, const CostPlane& cost_right,
                            hipStream_t st)
 {
     int rc = bm_check(h, n_pairs, left, right, disp_left, W, H, left_stride, right_stride, dl_stride);
@@ -627,9 +650,10 @@ static int bm_compute_impl(adf_bm_t* h, int n_pairs,
     }
 
     const int w2 = h->block / 2;
-    auto view_args = [&](const uint32_t* ref, const uint32_t* srch, int16_t* d, ptrdiff_t ds_, ptrdiff_t dp, int md, int texthr, int uniq) {
+    auto view_args = [&](const uint32_t* ref, const uint32_t* srch, int16_t* d, ptrdiff_t ds_, ptrdiff_t dp, const CostPlane& cp, int md, int texthr, int uniq) {
         ViewArgs v;
         v.Lt = ref; v.Rt = srch; v.disp = d; v.dstride = ds_; v.dpair = dp;
+        v.cost = cp.p; v.cstride = cp.stride; v.cpair = cp.pair;
         v.mindisp = md;
         const int maxd = md + h->num_disp - 1;
         v.xs = (maxd > 0 ? maxd : 0) + w2;
@@ -641,10 +665,10 @@ static int bm_compute_impl(adf_bm_t* h, int n_pairs,
     a.nviews = nviews; a.t_pair = image; a.planes = planes; a.plane = view;
     a.W = W; a.Wp = Wp; a.H = H; a.HG = HG; a.ndisp = h->num_disp; a.cap = h->cap;
     // (a census cost has no prefiltered image to sum a texture of: textureThreshold is validated and not used)
-    a.v[0] = view_args(Lt, Rt, disp_left, dl_stride, dl_pair_stride, h->min_disp, census ? 0 : h->texthr, h->uniq);
+    a.v[0] = view_args(Lt, Rt, disp_left, dl_stride, dl_pair_stride, cost_left, h->min_disp, census ? 0 : h->texthr, h->uniq);
     // the right-view matcher of createRightMatcher (disparity_filters.cpp:421-431): views swapped,
     // minDisparity = -(min_disp + num_disp) + 1, texture and uniqueness tests off
-    a.v[1] = disp_right ? view_args(Rt, Lt, disp_right, dr_stride, dr_pair_stride, -(h->min_disp + h->num_disp) + 1, 0, 0) : a.v[0];
+    a.v[1] = disp_right ? view_args(Rt, Lt, disp_right, dr_stride, dr_pair_stride, cost_right, -(h->min_disp + h->num_disp) + 1, 0, 0) : a.v[0];
     hipLaunchKernelGGL(bm_border_kernel, dim3(4, H, n_pairs * nviews), dim3(256), 0, st, a);
     if (a.v[0].xe > a.v[0].xs || (nviews == 2 && a.v[1].xe > a.v[1].xs)) {
         hipError_t e = launch_match_for(a, census, h->uniq > 0, w2, n_pairs, st);
@@ -661,7 +685,21 @@ extern "C" int adf_bm_compute_device(adf_bm_t* h, int n_pairs,
                                      void* stream)
 {
     return bm_compute_impl(h, n_pairs, left, left_stride, left_pair_stride, right, right_stride, right_pair_stride, W, H,
-                           disparity, disp_stride, disp_pair_stride, nullptr, 0, 0, (hipStream_t)stream);
+                           disparity, disp_stride, disp_pair_stride, nullptr, 0, 0, NO_COST, NO_COST, (hipStream_t)stream);
+}
+
+extern "C" int adf_bm_compute_cost_device(adf_bm_t* h, int n_pairs,
+                                          const uint8_t* left, ptrdiff_t left_stride, ptrdiff_t left_pair_stride,
+                                          const uint8_t* right, ptrdiff_t right_stride, ptrdiff_t right_pair_stride,
+                                          int W, int H,
+                                          int16_t* disparity, ptrdiff_t disp_stride, ptrdiff_t disp_pair_stride,
+                                          int16_t* cost, ptrdiff_t cost_stride, ptrdiff_t cost_pair_stride,
+                                          void* stream)
+{
+    const CostPlane c{cost, cost_stride, cost_pair_stride};
+    if (int rc = bm_cost_check(c, "the", n_pairs, W)) return rc;
+    return bm_compute_impl(h, n_pairs, left, left_stride, left_pair_stride, right, right_stride, right_pair_stride, W, H,
+                           disparity, disp_stride, disp_pair_stride, nullptr, 0, 0, c, NO_COST, (hipStream_t)stream);
 }
 
 extern "C" int adf_bm_compute_both_device(adf_bm_t* h, int n_pairs,
@@ -675,7 +713,57 @@ extern "C" int adf_bm_compute_both_device(adf_bm_t* h, int n_pairs,
     if (!disp_right) return fail(ADF_EBADARG, "disp_right is NULL");
     return bm_compute_impl(h, n_pairs, left, left_stride, left_pair_stride, right, right_stride, right_pair_stride, W, H,
                            disp_left, disp_left_stride, disp_left_pair_stride,
-                           disp_right, disp_right_stride, disp_right_pair_stride, (hipStream_t)stream);
+                           disp_right, disp_right_stride, disp_right_pair_stride, NO_COST, NO_COST, (hipStream_t)stream);
+}
+
+extern "C" int adf_bm_compute_both_cost_device(adf_bm_t* h, int n_pairs,
+                                               const uint8_t* left, ptrdiff_t left_stride, ptrdiff_t left_pair_stride,
+                                               const uint8_t* right, ptrdiff_t right_stride, ptrdiff_t right_pair_stride,
+                                               int W, int H,
+                                               int16_t* disp_left, ptrdiff_t disp_left_stride, ptrdiff_t disp_left_pair_stride,
+                                               int16_t* disp_right, ptrdiff_t disp_right_stride, ptrdiff_t disp_right_pair_stride,
+                                               int16_t* cost_left, ptrdiff_t cost_left_stride, ptrdiff_t cost_left_pair_stride,
+                                               int16_t* cost_right, ptrdiff_t cost_right_stride, ptrdiff_t cost_right_pair_stride,
+                                               void* stream)
+{
+    if (!disp_right) return fail(ADF_EBADARG, "disp_right is NULL");
+    const CostPlane cl{cost_left, cost_left_stride, cost_left_pair_stride}, cr{cost_right, cost_right_stride, cost_right_pair_stride};
+    if (int rc = bm_cost_check(cl, "the left", n_pairs, W)) return rc;
+    if (int rc = bm_cost_check(cr, "the right", n_pairs, W)) return rc;
+    return bm_compute_impl(h, n_pairs, left, left_stride, left_pair_stride, right, right_stride, right_pair_stride, W, H,
+                           disp_left, disp_left_stride, disp_left_pair_stride,
+                           disp_right, disp_right_stride, disp_right_pair_stride, cl, cr, (hipStream_t)stream);
+}
+
+// The host-pointer entries: views in, map (and cost plane, when wanted) out through one staging block of the handle.
+static int bm_compute_host_impl(adf_bm_t* h, int n_pairs,
+                                const uint8_t* left, ptrdiff_t left_stride, ptrdiff_t left_pair_stride,
+                                const uint8_t* right, ptrdiff_t right_stride, ptrdiff_t right_pair_stride,
+                                int W, int H,
+                                int16_t* disparity, ptrdiff_t disp_stride, ptrdiff_t disp_pair_stride, const CostPlane* cost)
+{
+    int rc = bm_check(h, n_pairs, left, right, disparity, W, H, left_stride, right_stride, disp_stride);
+    if (rc) return rc;
+    if (cost && (rc = bm_cost_check(*cost, "the", n_pairs, W))) return rc;
+    DeviceScope ds(h->device);
+    const size_t vbytes = (size_t)W * H, dbytes = (size_t)W * H * 2;
+    rc = h->stage.reserve((2 * vbytes + (cost ? 2 : 1) * dbytes) * (size_t)n_pairs, nullptr, FILL_NONE);
+    if (rc) return rc;
+    uint8_t* dl = (uint8_t*)h->stage.p;
+    uint8_t* dr = dl + vbytes * n_pairs;
+    int16_t* dd = (int16_t*)(dr + vbytes * n_pairs);
+    int16_t* dc = dd + (size_t)W * H * n_pairs;                       // (used with a cost plane only)
+    if ((rc = copy_images(dl, W, vbytes, left, left_stride, left_pair_stride, W, H, n_pairs, hipMemcpyHostToDevice, nullptr))) return rc;
+    if ((rc = copy_images(dr, W, vbytes, right, right_stride, right_pair_stride, W, H, n_pairs, hipMemcpyHostToDevice, nullptr))) return rc;
+    rc = cost ? adf_bm_compute_cost_device(h, n_pairs, dl, W, (ptrdiff_t)vbytes, dr, W, (ptrdiff_t)vbytes, W, H, dd, (ptrdiff_t)W * 2, (ptrdiff_t)dbytes,
+                                           dc, (ptrdiff_t)W * 2, (ptrdiff_t)dbytes, nullptr)
+              : adf_bm_compute_device(h, n_pairs, dl, W, (ptrdiff_t)vbytes, dr, W, (ptrdiff_t)vbytes, W, H, dd, (ptrdiff_t)W * 2, (ptrdiff_t)dbytes, nullptr);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    if ((rc = copy_images(disparity, disp_stride, disp_pair_stride, dd, (size_t)W * 2, dbytes, (size_t)W * 2, H, n_pairs, hipMemcpyDeviceToHost, nullptr))) return rc;
+    if (cost && (rc = copy_images(cost->p, cost->stride, cost->pair, dc, (size_t)W * 2, dbytes, (size_t)W * 2, H, n_pairs, hipMemcpyDeviceToHost, nullptr))) return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return ADF_OK;
 }
 
 extern "C" int adf_bm_compute_host(adf_bm_t* h, int n_pairs,
@@ -684,21 +772,18 @@ extern "C" int adf_bm_compute_host(adf_bm_t* h, int n_pairs,
                                    int W, int H,
                                    int16_t* disparity, ptrdiff_t disp_stride, ptrdiff_t disp_pair_stride)
 {
-    int rc = bm_check(h, n_pairs, left, right, disparity, W, H, left_stride, right_stride, disp_stride);
-    if (rc) return rc;
-    DeviceScope ds(h->device);
-    const size_t vbytes = (size_t)W * H, dbytes = (size_t)W * H * 2;
-    rc = h->stage.reserve((2 * vbytes + dbytes) * (size_t)n_pairs, nullptr, FILL_NONE);
-    if (rc) return rc;
-    uint8_t* dl = (uint8_t*)h->stage.p;
-    uint8_t* dr = dl + vbytes * n_pairs;
-    int16_t* dd = (int16_t*)(dr + vbytes * n_pairs);
-    if ((rc = copy_images(dl, W, vbytes, left, left_stride, left_pair_stride, W, H, n_pairs, hipMemcpyHostToDevice, nullptr))) return rc;
-    if ((rc = copy_images(dr, W, vbytes, right, right_stride, right_pair_stride, W, H, n_pairs, hipMemcpyHostToDevice, nullptr))) return rc;
-    rc = adf_bm_compute_device(h, n_pairs, dl, W, (ptrdiff_t)vbytes, dr, W, (ptrdiff_t)vbytes, W, H, dd, (ptrdiff_t)W * 2, (ptrdiff_t)dbytes, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    if ((rc = copy_images(disparity, disp_stride, disp_pair_stride, dd, (size_t)W * 2, dbytes, (size_t)W * 2, H, n_pairs, hipMemcpyDeviceToHost, nullptr))) return rc;
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return ADF_OK;
+    return bm_compute_host_impl(h, n_pairs, left, left_stride, left_pair_stride, right, right_stride, right_pair_stride, W, H,
+                                disparity, disp_stride, disp_pair_stride, nullptr);
+}
+
+extern "C" int adf_bm_compute_cost_host(adf_bm_t* h, int n_pairs,
+                                        const uint8_t* left, ptrdiff_t left_stride, ptrdiff_t left_pair_stride,
+                                        const uint8_t* right, ptrdiff_t right_stride, ptrdiff_t right_pair_stride,
+                                        int W, int H,
+                                        int16_t* disparity, ptrdiff_t disp_stride, ptrdiff_t disp_pair_stride,
+                                        int16_t* cost, ptrdiff_t cost_stride, ptrdiff_t cost_pair_stride)
+{
+    const CostPlane c{cost, cost_stride, cost_pair_stride};
+    return bm_compute_host_impl(h, n_pairs, left, left_stride, left_pair_stride, right, right_stride, right_pair_stride, W, H,
+                                disparity, disp_stride, disp_pair_stride, &c);
 }

@@ -12,6 +12,8 @@ edge_filter.hpp (EF.hpp), over the C-ABI in include/adf_wls.h:
     createFastGlobalSmootherFilter(...)             EF.hpp:393
     fastGlobalSmootherFilter(...)                   EF.hpp:413
     filterSpeckles(img, newVal, maxSpeckleSize, maxDiff, buf)   calib3d (outside the reference tree)
+    validateDisparity(disparity, cost, minDisparity, numberOfDisparities, disp12MaxDiff)   calib3d (outside the reference tree)
+    StereoBM.computeWithCost / computeBothWithCost / computeFull, StereoSGBM.computeFull   what calib3d's compute does with the matcher's own settings (extension names)
     censusTransform(image, kernelSize, type)        modules/stereo descriptor.hpp:428 / descriptor.cpp:77-98
     StereoBM.setCostType(BM_COST_CENSUS_*) / setCensusSize(k)   the cost of modules/stereo stereo_binary_bm.cpp:367-408 (extension)
     resize(src, dsize, fx, fy) at half size, cvtColor(src, COLOR_BGR2GRAY)   imgproc (outside the reference tree)
@@ -54,9 +56,9 @@ def _as_rect(roi):
     return Rect(int(x), int(y), int(w), int(h))
 
 
-_ITEMSIZE = {np.int16: 2, np.uint8: 1, np.float32: 4, np.uint64: 8}
+_ITEMSIZE = {np.int16: 2, np.uint8: 1, np.float32: 4, np.uint64: 8, np.int32: 4}
 # (torch has no unsigned 64-bit type that every build can index: a descriptor plane is an int64 tensor carrying the bit pattern)
-_TORCH_DTYPE = {np.int16: torch.int16, np.uint8: torch.uint8, np.float32: torch.float32, np.uint64: torch.int64} if torch is not None else {}
+_TORCH_DTYPE = {np.int16: torch.int16, np.uint8: torch.uint8, np.float32: torch.float32, np.uint64: torch.int64, np.int32: torch.int32} if torch is not None else {}
 _raw_stream = getattr(getattr(torch, "_C", None), "_cuda_getCurrentRawStream", None) if torch is not None else None
 
 
@@ -355,7 +357,7 @@ def _accessors(*names):
     return add
 
 
-@_accessors("minDisparity", "numDisparities", "blockSize", "disp12MaxDiff", "speckleWindowSize", "uniquenessRatio")
+@_accessors("minDisparity", "numDisparities", "blockSize", "disp12MaxDiff", "speckleWindowSize", "speckleRange", "uniquenessRatio")
 class StereoMatcher(_Handle):
     """The parameters every matcher has, and the part of compute() both have in common.  A subclass names its C entry
     point (`_entry`) and the channels a view may have (`_channels`), and supplies `_refuse()` (its own settings it cannot
@@ -365,6 +367,7 @@ class StereoMatcher(_Handle):
     def __init__(self, minDisparity=0, numDisparities=16, blockSize=3):
         self.minDisparity, self.numDisparities, self.blockSize = minDisparity, numDisparities, blockSize
         self.disp12MaxDiff, self.speckleWindowSize, self.uniquenessRatio = -1, 0, 10
+        self.speckleRange = 0       # read by computeFull only: compute() runs no speckle filter
 
     def _views(self, left, right, device_only=None):
         """(L, R, batched): both views described and equal in size; `device_only`: the refusal of host arrays."""
@@ -398,6 +401,10 @@ class StereoMatcher(_Handle):
         if self.speckleWindowSize > 0:
             raise AdfError(_lib.ADF_EBADARG, "speckle filtering is not implemented inside compute(); "
                                              "use filterSpeckles on the result")
+        return self._match(left, right, disparity)
+
+    def _match(self, left, right, disparity):
+        """compute() past its refusals: the match alone, whatever the speckle settings say (computeFull runs them)."""
         L, R, batched = self._views(left, right)
         if L.device != R.device:
             raise AdfError(_lib.ADF_EBADARG, "left and right must live on the same side (host or device)")
@@ -409,8 +416,10 @@ class StereoMatcher(_Handle):
 
 @_accessors("textureThreshold", "preFilterCap", "costType", "censusSize")
 class StereoBM(StereoMatcher):
-    """cv::StereoBM's accessors plus compute() on the device (csrc/bm_matcher.hip): CV_8UC1 views.  The left-right check
-    and the speckle filter of cv::StereoBM are not implemented: the filter factory switches both off (DF.cpp:389-390).
+    """cv::StereoBM's accessors plus compute() on the device (csrc/bm_matcher.hip): CV_8UC1 views.  compute() runs neither
+    the left-right check nor the speckle filter of cv::StereoBM and refuses settings that ask for them: the filter factory
+    switches both off (DF.cpp:389-390).  computeFull() is the whole calib3d chain -- computeWithCost(), validateDisparity(),
+    filterSpeckles() -- with the matcher's own disp12MaxDiff, speckleWindowSize and speckleRange.
 
     Extension: setCostType(BM_COST_CENSUS_DENSE / _SPARSE) + setCensusSize(k) match census descriptors with a Hamming
     distance, the cost of the reference's own cv::stereo::StereoBinaryBM (include/adf_wls.h: adf_bm_set_cost), which
@@ -454,6 +463,62 @@ class StereoBM(StereoMatcher):
         return (self._h, L.n, L.ptr, L.stride, L.pair_stride, R.ptr, R.stride, R.pair_stride, L.w, L.h,
                 D.ptr, D.stride, D.pair_stride)
 
+    def computeWithCost(self, left, right, disparity=None, cost=None):
+        """Extension: compute()'s map AND the CV_16S plane of the winning disparity's aggregated cost, the pair calib3d's
+        StereoBM hands to validateDisparity (include/adf_wls.h: adf_bm_compute_cost_*).  The map is compute()'s byte for
+        byte; the plane holds (int16)cost where the map holds a disparity and 0 where it holds (minDisparity-1)*16.  The
+        match alone: disp12MaxDiff and the speckle settings are not applied here (computeFull does).  Host arrays take the
+        host entry; device tensors run on torch's current stream.  Returns (disparity, cost)."""
+        L, R, batched = self._views(left, right)
+        if L.device != R.device:
+            raise AdfError(_lib.ADF_EBADARG, "left and right must live on the same side (host or device)")
+        (disparity, cost), (D, K) = self._outputs((disparity, cost), ("disparity", "cost"), L, batched,
+                                                  "disparity and cost must match the views")
+        self._prepare((L, R, D, K))
+        _call("adf_bm_compute_cost", L, self._args(L, R, D) + (K.ptr, K.stride, K.pair_stride))
+        return disparity, cost
+
+    def computeBothWithCost(self, left, right, disparity_left=None, disparity_right=None, cost_left=None, cost_right=None):
+        """Extension: computeBoth's two maps and the cost plane of each search, identical to `self.computeWithCost(left,
+        right)` and `createRightMatcher(self).computeWithCost(right, left)`.  Device tensors only; the same fallback to
+        two separate computes as computeBoth when a SAD matcher's preFilterCap is not 31.  Returns (disparity_left,
+        disparity_right, cost_left, cost_right)."""
+        L, R, batched = self._views(left, right, "computeBothWithCost takes device tensors; use two computeWithCost() calls on the host")
+        outs, (DL, DR, KL, KR) = self._outputs(
+            (disparity_left, disparity_right, cost_left, cost_right), ("disparity_left", "disparity_right", "cost_left", "cost_right"),
+            L, batched, "disparity maps and cost planes must match the views")
+        if self.preFilterCap != 31 and self.costType == BM_COST_SAD:
+            self._right_matcher().computeWithCost(right, left, outs[1], outs[3])
+            self.computeWithCost(left, right, outs[0], outs[2])
+            return tuple(outs)
+        self._prepare((L, R, DL, DR, KL, KR))
+        _lib.check(_lib.lib().adf_bm_compute_both_cost_device(
+            *self._args(L, R, DL), DR.ptr, DR.stride, DR.pair_stride, KL.ptr, KL.stride, KL.pair_stride,
+            KR.ptr, KR.stride, KR.pair_stride, _stream_of(L)))
+        return tuple(outs)
+
+    def computeFull(self, left, right, disparity=None):
+        """Extension: what calib3d's StereoBM::compute does with the matcher's own settings, under a new name so that
+        compute() stays what the filter factory expects: the match with its cost; validateDisparity when
+        0 <= disp12MaxDiff; filterSpeckles((minDisparity-1)*16, speckleWindowSize, speckleRange) when speckleWindowSize > 0
+        -- the range unscaled, the call-site convention of modules/stereo/src/stereo_binary_bm.cpp:416-417."""
+        disparity, cost = self.computeWithCost(left, right, disparity)
+        if self.disp12MaxDiff >= 0:      # (past 2^26 no two CV_16S values differ by more: the clamp changes nothing)
+            validateDisparity(disparity, cost, self.minDisparity, self.numDisparities, min(int(self.disp12MaxDiff), 1 << 26))
+        if self.speckleWindowSize > 0:
+            filterSpeckles(disparity, (int(self.minDisparity) - 1) * 16, self.speckleWindowSize, self.speckleRange)
+        return disparity
+
+    def _right_matcher(self):
+        """createRightMatcher(self) on a matcher (and handle) this one keeps for the two-launch fallback."""
+        if getattr(self, "_right", None) is None:
+            self._right = StereoBM(1, 5)
+        rm = createRightMatcher(self)
+        for k in ("minDisparity", "numDisparities", "blockSize", "textureThreshold", "uniquenessRatio",
+                  "preFilterCap", "disp12MaxDiff", "speckleWindowSize", "costType", "censusSize"):
+            setattr(self._right, k, getattr(rm, k))
+        return self._right
+
     def computeBoth(self, left, right, disparity_left=None, disparity_right=None):
         """Extension: this matcher's map AND the map of createRightMatcher(self) (DF.cpp:417-431) from one launch --
         identical to `self.compute(left, right)` and `createRightMatcher(self).compute(right, left)`, with the views
@@ -470,14 +535,9 @@ class StereoBM(StereoMatcher):
         (disparity_left, disparity_right), (DL, DR) = self._outputs(
             (disparity_left, disparity_right), ("disparity_left", "disparity_right"), L, batched, "disparity maps must match the views")
         if self.preFilterCap != 31 and self.costType == BM_COST_SAD:
-            if getattr(self, "_right", None) is None:
-                self._right = StereoBM(1, 5)
-            rm = createRightMatcher(self)
-            for k in ("minDisparity", "numDisparities", "blockSize", "textureThreshold", "uniquenessRatio",
-                      "preFilterCap", "disp12MaxDiff", "speckleWindowSize", "costType", "censusSize"):
-                setattr(self._right, k, getattr(rm, k))
+            right_matcher = self._right_matcher()
             self.compute(left, right, disparity_left)
-            self._right.compute(right, left, disparity_right)
+            right_matcher.compute(right, left, disparity_right)
             return disparity_left, disparity_right
         self._prepare((L, R, DL, DR))
         _lib.check(_lib.lib().adf_bm_compute_both_device(*self._args(L, R, DL), DR.ptr, DR.stride, DR.pair_stride, _stream_of(L)))
@@ -491,7 +551,8 @@ class StereoSGBM(StereoMatcher):
     samples/disparity_filtering.cpp:166-176), five (MODE_SGBM) or eight (MODE_HH), bit-exact against
     oracle/adf_oracle_sgbm.c; parity unpinned at calib3d.  compute() takes CV_8UC1 / CV_8UC3 views (H,W[,3]) or a batch
     (N,H,W[,3]) and runs the matcher's own left-right check (disp12MaxDiff; create's default 0 reads as 1, the filter
-    factory switches it off with 1000000, DF.cpp:389); the speckle filter is not built (DF.cpp:390 sets it to 0).
+    factory switches it off with 1000000, DF.cpp:389); compute() runs no speckle filter (DF.cpp:390 sets it to 0) and
+    refuses speckleWindowSize > 0; computeFull() is compute() followed by filterSpeckles with the matcher's settings.
 
     Extension: setCostType(SGBM_COST_CENSUS_DENSE / _SPARSE) + setCensusSize(k) match on census descriptors with a Hamming
     distance, the cost of the reference's own cv::stereo::StereoBinarySGBM (its setBinaryKernelType / kernelSize;
@@ -514,7 +575,19 @@ class StereoSGBM(StereoMatcher):
                uniquenessRatio=0, speckleWindowSize=0, speckleRange=0, mode=0):
         m = StereoSGBM(minDisparity, numDisparities, blockSize, P1, P2, mode, preFilterCap)
         m.disp12MaxDiff, m.uniquenessRatio, m.speckleWindowSize = disp12MaxDiff, uniquenessRatio, speckleWindowSize
+        m.speckleRange = speckleRange
         return m
+
+    def computeFull(self, left, right, disparity=None):
+        """Extension: what calib3d's StereoSGBM::compute does with the matcher's own settings, under a new name so that
+        compute() stays what the filter factory expects: compute(), whose own left-right check already runs, then
+        filterSpeckles((minDisparity-1)*16, speckleWindowSize, 16*speckleRange) when speckleWindowSize > 0
+        (modules/stereo/src/stereo_binary_sgbm.cpp:716-718)."""
+        self._refuse()
+        disparity = self._match(left, right, disparity)
+        if self.speckleWindowSize > 0:
+            filterSpeckles(disparity, (int(self.minDisparity) - 1) * 16, self.speckleWindowSize, 16 * int(self.speckleRange))
+        return disparity
 
     def _refuse(self):
         if self.mode not in (StereoSGBM.MODE_SGBM, StereoSGBM.MODE_HH, StereoSGBM.MODE_SGBM_3WAY):
@@ -588,6 +661,50 @@ def filterSpeckles(img, newVal, maxSpeckleSize, maxDiff, buf=None):
     with torch.cuda.device(img.device):
         _call("adf_filter_speckles", im, args + (ws, ws_bytes))
     return img, buf
+
+
+def validateDisparity(disparity, cost, minDisparity, numberOfDisparities, disp12MaxDiff=1):
+    """calib3d's validateDisparity(disparity, cost, minDisparity, numberOfDisparities, disp12MaxDiff): the block matcher's
+    own left-right check on its map and on the aggregated cost of each winning disparity (StereoBM.computeWithCost).  Per
+    row every pixel votes, with its cost, for the column it matched in the other view; a pixel is set to
+    (minDisparity-1)*16 when both columns it may have matched hold a winner that differs from it by more than
+    16*disp12MaxDiff (the full statement, the refusals and the deviation for votes outside the row: include/adf_wls.h).
+    `disparity`: CV_16SC1 (H,W) or a batch (N,H,W), modified IN PLACE and returned; `cost`: int16 or int32, same shape and
+    side.  A torch CUDA tensor runs on the device, asynchronously on torch's current stream; a numpy array takes the host
+    entry point.  Parity with calib3d is unpinned."""
+    if disparity is None or cost is None:
+        raise AdfError(_lib.ADF_EBADARG, "disparity and cost must not be empty")
+    nd = len(disparity.shape)
+    if nd not in (2, 3):
+        raise AdfError(_lib.ADF_EBADARG, "disparity must be (H,W) or a batch (N,H,W)")
+    D = _Image(disparity, np.int16, "disparity", nd == 3)
+    cdt = cost.dtype if _is_torch(cost) else np.asarray(cost).dtype
+    if cdt == np.int16 or (torch is not None and cdt == torch.int16):
+        ctype, code = np.int16, _lib.DEPTH_16S
+    elif cdt == np.int32 or (torch is not None and cdt == torch.int32):
+        ctype, code = np.int32, _lib.DEPTH_32S
+    else:
+        raise AdfError(_lib.ADF_EBADARG, "cost must be int16 (CV_16S) or int32 (CV_32S), got %s" % (cdt,))
+    if len(cost.shape) != nd:
+        raise AdfError(_lib.ADF_ESIZE, "cost must have the disparity map's shape")
+    K = _Image(cost, ctype, "cost", nd == 3)
+    if (K.n, K.h, K.w) != (D.n, D.h, D.w) or K.device != D.device:
+        raise AdfError(_lib.ADF_ESIZE, "cost must have the disparity map's shape on its side (host or device)")
+    ints = []
+    for v, what in ((minDisparity, "minDisparity"), (numberOfDisparities, "numberOfDisparities"), (disp12MaxDiff, "disp12MaxDiff")):
+        v = int(v)
+        if not -_INT32_MAX <= v <= _INT32_MAX:
+            raise AdfError(_lib.ADF_EBADARG, "%s does not fit an int" % what)
+        ints.append(v)
+    args = (D.n, D.ptr, D.stride, D.pair_stride, K.ptr, K.stride, K.pair_stride, code, D.w, D.h) + tuple(ints)
+    if not D.device:
+        _call("adf_validate_disparity", D, args)
+        return disparity
+    if cost.device != disparity.device:
+        raise AdfError(_lib.ADF_EBADARG, "cost lives on %s, disparity on %s" % (cost.device, disparity.device))
+    with torch.cuda.device(disparity.device):
+        _call("adf_validate_disparity", D, args)
+    return disparity
 
 
 def censusTransform(image, kernelSize, type, dst=None):

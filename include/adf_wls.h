@@ -63,8 +63,8 @@ enum adf_status {
  * ADF_SOLVER_EXACT when the filtered map has to reproduce the scalar evaluation order bit for bit. */
 enum adf_solver { ADF_SOLVER_EXACT = 0, ADF_SOLVER_WAVE = 1 };
 
-/* cv::Mat depth codes for adf_fgs_filter_* (FGS.cpp:184). */
-enum adf_depth { ADF_8U = 0, ADF_16S = 3, ADF_32F = 5 };
+/* cv::Mat depth codes for adf_fgs_filter_* (FGS.cpp:184); ADF_32S (CV_32S) is a cost plane of adf_validate_disparity_* only. */
+enum adf_depth { ADF_8U = 0, ADF_16S = 3, ADF_32S = 4, ADF_32F = 5 };
 
 typedef struct adf_wls adf_wls_t; /* cv::Ptr<DisparityWLSFilter>        */
 typedef struct adf_fgs adf_fgs_t; /* cv::Ptr<FastGlobalSmootherFilter>  */
@@ -414,6 +414,43 @@ int adf_bm_compute_host(adf_bm_t* h, int n_pairs,
                         const uint8_t* right, ptrdiff_t right_stride, ptrdiff_t right_pair_stride,
                         int W, int H,
                         int16_t* disparity, ptrdiff_t disp_stride, ptrdiff_t disp_pair_stride);
+/* The winning-cost map.  adf_bm_compute_cost_* are adf_bm_compute_* plus a CV_16SC1 cost plane (W x H, rows `cost_stride`,
+ * pairs `cost_pair_stride` bytes apart, 2-byte aligned, non-NULL), what calib3d's StereoBM keeps for its own left-right
+ * check (validateDisparity, below).  The disparity map is byte for byte the one adf_bm_compute_* writes, and
+ *   - where the map holds a disparity other than (minDisparity-1)*16, the plane holds (int16_t)S[kb][x]: the aggregated
+ *     cost (SAD or Hamming, every ADF_BM_COST_*) of the winning INTEGER disparity kb, before the sub-pixel fit;
+ *   - where the map holds (minDisparity-1)*16 -- texture test, uniqueness test, rows and columns without a full window
+ *     or search range -- the plane holds 0 (calib3d leaves those entries unwritten; 0 makes the plane deterministic).
+ * The conversion is a plain truncation to 16 bits, because calib3d's cost map is CV_16S.  It changes a value only where a
+ * cost can exceed 32767: a SAD is at most 2 * preFilterCap * blockSize^2, which passes 32767 only with blockSize 21 and
+ * preFilterCap above 37, blockSize 19 and preFilterCap above 45, or blockSize 17 and preFilterCap above 56 -- never with
+ * blockSize 15 or less; a census cost is at most 48 * 441 = 21168 and never truncates.  Parity with calib3d is UNPINNED
+ * here as for the rest of the matcher (the class is outside the reference tree); the plane is bit-exact against the direct
+ * statement tests/validate_ref.py.
+ * adf_bm_compute_both_cost_device: both maps of adf_bm_compute_both_device and both planes; the right view's plane is the
+ * cost of the createRightMatcher search, equal to what a separate adf_bm_compute_cost_device of that matcher writes. */
+int adf_bm_compute_cost_device(adf_bm_t* h, int n_pairs,
+                               const uint8_t* left, ptrdiff_t left_stride, ptrdiff_t left_pair_stride,
+                               const uint8_t* right, ptrdiff_t right_stride, ptrdiff_t right_pair_stride,
+                               int W, int H,
+                               int16_t* disparity, ptrdiff_t disp_stride, ptrdiff_t disp_pair_stride,
+                               int16_t* cost, ptrdiff_t cost_stride, ptrdiff_t cost_pair_stride,
+                               void* stream);
+int adf_bm_compute_cost_host(adf_bm_t* h, int n_pairs,
+                             const uint8_t* left, ptrdiff_t left_stride, ptrdiff_t left_pair_stride,
+                             const uint8_t* right, ptrdiff_t right_stride, ptrdiff_t right_pair_stride,
+                             int W, int H,
+                             int16_t* disparity, ptrdiff_t disp_stride, ptrdiff_t disp_pair_stride,
+                             int16_t* cost, ptrdiff_t cost_stride, ptrdiff_t cost_pair_stride);
+int adf_bm_compute_both_cost_device(adf_bm_t* h, int n_pairs,
+                                    const uint8_t* left, ptrdiff_t left_stride, ptrdiff_t left_pair_stride,
+                                    const uint8_t* right, ptrdiff_t right_stride, ptrdiff_t right_pair_stride,
+                                    int W, int H,
+                                    int16_t* disp_left, ptrdiff_t disp_left_stride, ptrdiff_t disp_left_pair_stride,
+                                    int16_t* disp_right, ptrdiff_t disp_right_stride, ptrdiff_t disp_right_pair_stride,
+                                    int16_t* cost_left, ptrdiff_t cost_left_stride, ptrdiff_t cost_left_pair_stride,
+                                    int16_t* cost_right, ptrdiff_t cost_right_stride, ptrdiff_t cost_right_pair_stride,
+                                    void* stream);
 
 /* ---------------- semi-global matcher feeding the filter ----------------
  * cv::StereoSGBM as the reference's sample configures it (samples/disparity_filtering.cpp:166-176, 229-235:
@@ -555,6 +592,40 @@ int adf_filter_speckles_device(int n_maps, int16_t* img, ptrdiff_t stride, ptrdi
                                void* workspace, size_t workspace_bytes, void* stream);
 int adf_filter_speckles_host(int n_maps, int16_t* img, ptrdiff_t stride, ptrdiff_t map_stride, int W, int H,
                              int new_val, int max_speckle_size, int max_diff);
+
+/* ---------------- validateDisparity (the block matcher's own left-right check) ----------------
+ * calib3d's validateDisparity(disp, cost, minDisparity, numberOfDisparities, disp12MaxDiff), the step
+ * cv::StereoBM::compute runs on its map and on the aggregated cost of each winning disparity (adf_bm_compute_cost_*)
+ * when 0 <= disp12MaxDiff.  The chain of the canonical stereo sample is three calls:
+ *     adf_bm_compute_cost_device -> adf_validate_disparity_device -> adf_filter_speckles_device.
+ * n_maps equally sized CV_16SC1 maps `map_stride` bytes apart, modified IN PLACE; cost: a plane of cost_type ADF_16S or
+ * ADF_32S (calib3d accepts CV_16S and CV_32S) per map, read only.  Every row of every map is independent, all
+ * arithmetic is int32:
+ *     minD = min_disparity, maxD = minD + num_disparities, INV = (minD-1)*16, X0 = max(maxD, 0), X1 = W + min(minD, 0)
+ *   1. disp2[x2] = INV and cost2[x2] = INT_MAX for every x2 in [0, W);
+ *   2. x ascending in [X0, X1) with d = disp[x] != INV, c = cost[x]: x2 = x - ((d + 8) >> 4); if cost2[x2] > c then
+ *      (cost2, disp2)[x2] = (c, d).  The comparison is strict: among equal costs the smallest x wins, and a CV_32S cost
+ *      of INT_MAX never wins;
+ *   3. x in [X0, X1) with d = disp[x] != INV, d0 = d >> 4, d1 = (d + 15) >> 4: disp[x] = INV only if for d0 AND for d1
+ *      0 <= x-dk < W, disp2[x-dk] > INV and |disp2[x-dk] - d| > 16 * disp12_max_diff.  A candidate outside the row or on
+ *      an empty disp2 keeps the pixel.
+ * Deviation: a pixel whose x2 of step 2 falls outside [0, W) does not vote; calib3d indexes out of bounds there.  Maps of
+ * this library's matcher never produce that case (d lies in [minD*16, (maxD-1)*16]: the sub-pixel term is 0 at both ends
+ * of the search).  calib3d is outside the reference tree, so parity with it is UNPINNED; the device is bit-exact against
+ * the sequential statement tests/validate_ref.py and identical from run to run (csrc/validate_kernels.hip).
+ * Refused: disp12_max_diff < 0 ("off" is the matcher's business, not this function's) or above 2^26, num_disparities <= 0,
+ * INV outside CV_16S, an unknown cost_type, NULL pointers, misaligned images (all ADF_EBADARG); W above
+ * ADF_VALIDATE_MAX_WIDTH -- a row is held on chip -- and strides smaller than a row (ADF_ESIZE).
+ * Stateless: no workspace, no allocation, no synchronisation on the device path, so the call may be captured into a
+ * hipGraph.  _device: device pointers, asynchronous on `stream`, on the current HIP device.  _host: host pointers,
+ * copies, runs and synchronises. */
+#define ADF_VALIDATE_MAX_WIDTH 15360
+int adf_validate_disparity_device(int n_maps, int16_t* disp, ptrdiff_t stride, ptrdiff_t map_stride,
+                                  const void* cost, ptrdiff_t cost_stride, ptrdiff_t cost_map_stride, int cost_type,
+                                  int W, int H, int min_disparity, int num_disparities, int disp12_max_diff, void* stream);
+int adf_validate_disparity_host(int n_maps, int16_t* disp, ptrdiff_t stride, ptrdiff_t map_stride,
+                                const void* cost, ptrdiff_t cost_stride, ptrdiff_t cost_map_stride, int cost_type,
+                                int W, int H, int min_disparity, int num_disparities, int disp12_max_diff);
 
 /* ---------------- the matcher's views (cv::resize to half size, cv::cvtColor BGR2GRAY) ----------------
  * The two imgproc calls the sample's default pipeline makes before matching (samples/disparity_filtering.cpp:130-141):

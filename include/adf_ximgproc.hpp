@@ -104,6 +104,23 @@ inline void filterSpeckles(Mat& img, double newVal, int maxSpeckleSize, double m
                                    (int)nv, maxSpeckleSize, (int)md));
 }
 
+// calib3d's validateDisparity(disparity, cost, minDisparity, numberOfDisparities, disp12MaxDiff) (outside the reference
+// tree; parity unpinned, see adf_validate_disparity_* in adf_wls.h), the block matcher's own left-right check: a CV_16SC1
+// host Mat, in place, and the CV_16SC1 or CV_32SC1 cost of each winning disparity (StereoBM::computeWithCost below),
+// through the library's host entry.  A negative disp12MaxDiff is refused: "off" is the matcher's business.
+inline void validateDisparity(Mat& disparity, const Mat& cost, int minDisparity, int numberOfDisparities, int disp12MaxDiff = 1)
+{
+    if (disparity.empty() || mat_depth(disparity) != D16S || mat_channels(disparity) != 1)
+        throw Exception(ADF_EBADARG, "validateDisparity: disparity must be a non-empty CV_16SC1 image");
+    if (cost.empty() || (mat_depth(cost) != D16S && mat_depth(cost) != D32S) || mat_channels(cost) != 1)
+        throw Exception(ADF_EBADARG, "validateDisparity: cost must be a non-empty CV_16SC1 or CV_32SC1 image");
+    if (cost.rows != disparity.rows || cost.cols != disparity.cols)
+        throw Exception(ADF_ESIZE, "validateDisparity: cost must have the disparity map's size");
+    check(adf_validate_disparity_host(1, reinterpret_cast<int16_t*>(disparity.data), mat_step(disparity), 0, cost.data, mat_step(cost), 0,
+                                      mat_depth(cost) == D16S ? ADF_16S : ADF_32S, disparity.cols, disparity.rows,
+                                      minDisparity, numberOfDisparities, disp12MaxDiff));
+}
+
 // cv::stereo::censusTransform(image, kernelSize, dist, type) (modules/stereo descriptor.hpp:428, descriptor.cpp:77-98) on a
 // CV_8UC1 host Mat, through the library's host entry: the census descriptor of every pixel, type
 // ADF_SGBM_COST_CENSUS_DENSE (kernelSize 3, 5, 7), ADF_SGBM_COST_CENSUS_SPARSE (5, 7, 9, 11), the modified census
@@ -601,20 +618,45 @@ public:
     // StereoMatcher::compute: CV_8UC1 views -> CV_16SC1 disparity * 16, rejected pixels (minDisparity - 1) * 16
     void compute(const Mat& left, const Mat& right, Mat& disparity)
     {
-        if (left.empty() || right.empty() || mat_depth(left) != D8U || mat_depth(right) != D8U ||
-            mat_channels(left) != 1 || mat_channels(right) != 1)
-            throw Exception(ADF_EBADARG, "Both input images must have CV_8UC1");
-        if (left.rows != right.rows || left.cols != right.cols)
-            throw Exception(ADF_ESIZE, "All the images must have the same size");
+        check_views(left, right);
         if ((disp12_ >= 0 && disp12_ < 1000000) || speckle_window_ > 0)          // the filter factory switches both off (DF.cpp:389-390)
             throw Exception(ADF_EBADARG, "the matcher's own left-right check and speckle filter are not implemented");
-        check(adf_bm_set_params(h_, min_disp_, num_disp_, block_, cap_, texture_, uniq_));
-        check(adf_bm_set_cost(h_, cost_, census_size_));
+        push_params();
         Mat out;
         mat_create(out, left.rows, left.cols, D16S, 1);
         check(adf_bm_compute_host(h_, 1, left.data, mat_step(left), 0, right.data, mat_step(right), 0, left.cols, left.rows,
                                   reinterpret_cast<int16_t*>(out.data), mat_step(out), 0));
         disparity = out;
+    }
+    // extension (adf_bm_compute_cost_host in adf_wls.h): compute()'s map and the CV_16SC1 aggregated cost of each winning
+    // disparity (0 where the map holds (minDisparity - 1) * 16), the pair adf::validateDisparity takes.  The match alone:
+    // disp12MaxDiff and speckleWindowSize are not applied, so the caller runs validateDisparity / filterSpeckles itself.
+    void computeWithCost(const Mat& left, const Mat& right, Mat& disparity, Mat& cost)
+    {
+        check_views(left, right);
+        push_params();
+        Mat out, c;
+        mat_create(out, left.rows, left.cols, D16S, 1);
+        mat_create(c, left.rows, left.cols, D16S, 1);
+        check(adf_bm_compute_cost_host(h_, 1, left.data, mat_step(left), 0, right.data, mat_step(right), 0, left.cols, left.rows,
+                                       reinterpret_cast<int16_t*>(out.data), mat_step(out), 0,
+                                       reinterpret_cast<int16_t*>(c.data), mat_step(c), 0));
+        disparity = out;
+        cost = c;
+    }
+private:
+    static void check_views(const Mat& left, const Mat& right)
+    {
+        if (left.empty() || right.empty() || mat_depth(left) != D8U || mat_depth(right) != D8U ||
+            mat_channels(left) != 1 || mat_channels(right) != 1)
+            throw Exception(ADF_EBADARG, "Both input images must have CV_8UC1");
+        if (left.rows != right.rows || left.cols != right.cols)
+            throw Exception(ADF_ESIZE, "All the images must have the same size");
+    }
+    void push_params()
+    {
+        check(adf_bm_set_params(h_, min_disp_, num_disp_, block_, cap_, texture_, uniq_));
+        check(adf_bm_set_cost(h_, cost_, census_size_));
     }
 };
 
