@@ -63,6 +63,8 @@ _REMAP_DEV = [_i, _vp, _pd, _pd, _i, _i, _i, _vp, _pd, _vp, _pd, _vp, _pd, _pd, 
 _RECTIFY_VIEWS_DEV = [_i, _vp, _pd, _pd, _i, _i, _i, C.POINTER(RectifyParams), _vp, _pd, _pd, _i, _i, _i, _i, _vp, _vp]
 _FILTER_SCALED_DEV = [_vp, _i, _vp, _pd, _pd, _i, _i, _vp, _pd, _pd, _i, _i, _i, _vp, _pd, _pd, _vp, _pd, _pd,
                       C.POINTER(Rect), _vp]
+# adf_wls_filter_typed_*: the scaled call with a depth behind the left map's strides and one behind the output's
+_FILTER_TYPED_DEV = _FILTER_SCALED_DEV[:5] + [_i] + _FILTER_SCALED_DEV[5:16] + [_i] + _FILTER_SCALED_DEV[16:]
 SYMBOLS = [
     ("adf_version", _i, []),
     ("adf_last_error", C.c_char_p, []),
@@ -92,6 +94,8 @@ SYMBOLS = [
     ("adf_wls_filter_f32_host", _i, _FILTER_DEV[:-1]),
     ("adf_wls_filter_scaled_f32_device", _i, _FILTER_SCALED_DEV),
     ("adf_wls_filter_scaled_f32_host", _i, _FILTER_SCALED_DEV[:-1]),
+    ("adf_wls_filter_typed_device", _i, _FILTER_TYPED_DEV),
+    ("adf_wls_filter_typed_host", _i, _FILTER_TYPED_DEV[:-1]),
     ("adf_wls_get_confidence_device", _i, [_vp, _i, _vp, _pd, _vp]),
     ("adf_wls_get_confidence_host", _i, [_vp, _i, _vp, _pd]),
     ("adf_wls_get_device", _i, [_vp, C.POINTER(_i)]),

@@ -40,9 +40,9 @@ static Geom make_geom(int W, int H, int rx, int ry, int rw, int rh)
 static Geom plain_conf_layout(Geom g) { g.cx0 = 0; g.cpitch = g.W; g.cframe = g.frame; return g; }
 
 // Per-launch HIP-event timing (adf_wls_profile_*).  Events are pooled and reused.
-enum KClass { K_FILL = 0, K_WEIGHTS, K_DISC, K_LRC, K_PROLOGUE, K_PASS_H_FIRST, K_PASS_H, K_PASS_V, K_PASS_V_LAST, K_RESIZE, K_COUNT };
+enum KClass { K_FILL = 0, K_WEIGHTS, K_DISC, K_LRC, K_PROLOGUE, K_PASS_H_FIRST, K_PASS_H, K_PASS_V, K_PASS_V_LAST, K_RESIZE, K_QUANT, K_COUNT };
 static const char* const kclass_names[K_COUNT] = {"fill_outside", "weights", "discontinuity", "lrc_confidence",
-                                                  "plain_prologue", "pass_h_first", "pass_h", "pass_v", "pass_v_last", "resize"};
+                                                  "plain_prologue", "pass_h_first", "pass_h", "pass_v", "pass_v_last", "resize", "quantise_maps"};
 struct Profiler {
     bool on = false;
     struct Rec { int cls; hipEvent_t a, b; double alg, moved; };
@@ -117,7 +117,7 @@ static int run_passes(bool wave, const Geom& g, const SolvePlanes& p, int n_rhs,
         // + R right-hand sides and writes R -- fused, C + conf + dL read (low-resolution maps: their bytes per view pixel,
         // each row counted once), U0/U1 written; the column pass writes the fused epilogue's output instead of 4R bytes
         // per pixel on the last iteration
-        const double lo_b = (fused && fuse->lo_conf) ? 6.0 * fuse->lo_scale_x * fuse->lo_scale_y : 6.0;
+        const double lo_b = (fused && fuse->lo_conf) ? 6.0 * fuse->lo_scale_x * fuse->lo_scale_y : (fused && fuse->dl_f32) ? 8.0 : 6.0;
         const double wb = gw ? (double)gw->ch : 4.0;
         const double hb = fused ? (wb + lo_b + 8.0) * px : (wb + 8.0 * n_rhs) * px;
         const double out_b = (last ? epilogue_bytes(fo.epilogue) : 4.0 * n_rhs) * px;
@@ -339,12 +339,17 @@ static int ensure_conf_planes(adf_wls* h, const Geom& g, int n_pairs, hipStream_
     return ADF_OK;
 }
 
-static size_t wls_pair_ws_bytes(const Geom& g, bool conf, bool wave, bool disc_maps)
+// Row pitch (elements) of the int16 planes q a call on float maps keeps for its confidence kernels: 16-byte rows.
+static int quant_pitch(int W) { return round_up(W, 8); }
+
+static size_t wls_pair_ws_bytes(const Geom& g, bool conf, bool wave, bool disc_maps, bool quant_planes)
 {
     // exact: ROI planes CH CV D F0 A0 B0 (+ F1 A1 B1 with confidence); wave: CH CV A0 (+ A1), in place
     // full frames: cL cR, the depth-discontinuity maps (not needed when the one-sweep confidence kernel runs)
     size_t planes = wave ? (conf ? 4 : 3) : (conf ? 9 : 6);
-    return planes * g.plane * sizeof(float) + (conf && disc_maps ? 2 * g.frame * sizeof(float) : 0);
+    // float maps (adf_wls_filter_typed_*), confidence mode: the two int16 planes q -- never part of an int16 call's workspace
+    return planes * g.plane * sizeof(float) + (conf && disc_maps ? 2 * g.frame * sizeof(float) : 0) +
+           (quant_planes ? 2 * (size_t)quant_pitch(g.W) * g.H * sizeof(int16_t) : 0);
 }
 
 // DF.cpp:228-233: the caller's ROI, or what the handle's offsets leave of a w x hgt map
@@ -358,10 +363,10 @@ static int resolve_roi(const adf_wls* h, const adf_rect* roi_in, int w, int hgt,
 }
 
 // DF.cpp:262-264: the right map of a confidence-mode call on maps w wide
-static int check_right_map(const int16_t* dispR, ptrdiff_t sR, int w)
+static int check_right_map(const void* dispR, ptrdiff_t sR, int w, size_t esz)
 {
     if (!dispR) return fail(ADF_EBADARG, "disparity_map_right is required with use_confidence");
-    if (sR < (ptrdiff_t)w * 2) return fail(ADF_ESIZE, "right disparity stride smaller than a row");
+    if (sR < (ptrdiff_t)(w * esz)) return fail(ADF_ESIZE, "right disparity stride smaller than a row");
     return ADF_OK;
 }
 
@@ -385,9 +390,10 @@ static WavePassArgs first_pass_probe(const FusedInputs& f, int len)
 
 // Fused first row pass at view resolution: U1 = conf, U0 = conf*float(dL) read from the confidence planes and the left
 // disparity maps of the pairs from `conf` / `dl` on (DF.cpp:288-290).
-static FusedInputs view_fuse(const float* conf, const int16_t* dl, ptrdiff_t sL, ptrdiff_t psL, const Geom& g)
+static FusedInputs view_fuse(const float* conf, const void* dl, ptrdiff_t sL, ptrdiff_t psL, bool f32, const Geom& g)
 {
     FusedInputs f{};
+    f.dl_f32 = f32 ? 1 : 0;
     f.conf_in = conf; f.conf_frame = g.cframe; f.conf_pitch = g.cpitch; f.conf_x0 = g.cx0 + g.rx; f.conf_y0 = g.ry;
     f.dl_in = dl; f.dl_stride = sL; f.dl_pair_stride = psL; f.dl_x0 = g.rx; f.dl_y0 = g.ry;
     return f;
@@ -401,8 +407,9 @@ static FusedInputs view_fuse(const float* conf, const int16_t* dl, ptrdiff_t sL,
 // the low-resolution confidence map before the fork 14.20 / 14.51 (two memory-bound kernels side by side gain nothing),
 // no overlap at all 14.49 / 14.69.
 struct ScaledStage {
-    const int16_t* dispL; ptrdiff_t sL, psL;   // the caller's low-resolution maps
+    const int16_t* dispL; ptrdiff_t sL, psL;   // the caller's low-resolution maps (float maps: their int16 planes q)
     const int16_t* dispR; ptrdiff_t sR, psR;
+    const float* vL; ptrdiff_t svL, psvL;      // float maps: the left map's v plane -- resized in float, no rounding
     float resize_factor, x_ratio;              // DF.cpp:225, 241
     char* dhi; size_t dhi_bytes;               // the resized left maps (not with fuse_lo)
     float *cl, *cr;                            // low-resolution discontinuity maps
@@ -480,9 +487,12 @@ static int scaled_resize(adf_wls_t* h, const ScaledStage& s, hipStream_t st, Pro
     const int W = c.ghi.W, H = c.ghi.H;
     const size_t lo = (size_t)c.dW * c.dH;
     const double Fhi = (double)W * H * c.n_pairs;
+    // float maps: v through the float taps the confidence map goes through, times x_ratio once, nothing rounded
+    const double eb = s.vL ? 4.0 : 2.0;
     ResizeArgs r16{s.dispL, s.sL, s.psL, c.dW, c.dH, s.dhi, (ptrdiff_t)W * 2, (ptrdiff_t)s.dhi_bytes, W, H, (double)c.dW / W, (double)c.dH / H, s.x_ratio, 1};
-    ProfScope ps(prof, K_RESIZE, 2.0 * Fhi + 2.0 * (double)lo * c.n_pairs, 2.0 * Fhi + 2.0 * (double)lo * c.n_pairs, st);
-    HIP_TRY(launch_resize_linear(r16, c.n_pairs, st));
+    ResizeArgs r32{s.vL, s.svL, s.psvL, c.dW, c.dH, s.dhi, (ptrdiff_t)W * 4, (ptrdiff_t)s.dhi_bytes, W, H, (double)c.dW / W, (double)c.dH / H, s.x_ratio, 0};
+    ProfScope ps(prof, K_RESIZE, eb * Fhi + eb * (double)lo * c.n_pairs, eb * Fhi + eb * (double)lo * c.n_pairs, st);
+    HIP_TRY(launch_resize_linear(s.vL ? r32 : r16, c.n_pairs, st));
     return ADF_OK;
 }
 
@@ -541,7 +551,7 @@ static GuideWeights guide_weights(const adf_wls* h, const uint8_t* guide, ptrdif
     return GuideWeights{guide, sG, psG, gch, g.rx, g.ry, h->lut.cur};
 }
 
-static WlsPlan plan_wls(const adf_wls* h, const Geom& g, int n_pairs, const int16_t* dispL, ptrdiff_t sL, ptrdiff_t psL,
+static WlsPlan plan_wls(const adf_wls* h, const Geom& g, int n_pairs, const void* dispL, ptrdiff_t sL, ptrdiff_t psL, bool f32in,
                         const uint8_t* view, ptrdiff_t sG, ptrdiff_t psG, int gch, const ScaledStage* scaled)
 {
     WlsPlan p{};
@@ -555,12 +565,12 @@ static WlsPlan plan_wls(const adf_wls* h, const Geom& g, int n_pairs, const int1
     // strides and the pointers known here, not on the chunk.
     const float* planes = h->conf.p ? (const float*)h->conf.p : UNALLOCATED;
     p.fused_first = stage == CONF_SCALED_LO ||
-                    ((stage == CONF_SCALED || stage == CONF_LEFT) && p.wave &&
-                     wave_hpass_can_fuse(first_pass_probe(view_fuse(planes, dispL, sL, psL, g), g.rw)));
+                    (((stage == CONF_SCALED && !f32in) || stage == CONF_LEFT) && p.wave &&   // (a resized float map is not clamped again: prologue)
+                     wave_hpass_can_fuse(first_pass_probe(view_fuse(planes, dispL, sL, psL, f32in, g), g.rw)));
     // the band kernel writes no right-hand sides: it needs the fused first pass
     p.band = stage == CONF_LEFT && p.fused_first && h->conf_band && conf_band_fits(g, h->disc_radius);
     if (p.band) stage = CONF_BAND;
-    p.per_pair = wls_pair_ws_bytes(g, conf, p.wave, !p.band);
+    p.per_pair = wls_pair_ws_bytes(g, conf, p.wave, !p.band, f32in && conf && !scaled);
     p.chunk = (int)(h->ws_limit / p.per_pair);
     if (p.chunk < 1) p.chunk = 1;
     if (p.chunk > n_pairs) p.chunk = n_pairs;
@@ -598,16 +608,25 @@ struct OutMap {
     size_t esz() const { return f32 ? sizeof(float) : sizeof(int16_t); }
 };
 
-// scaled: the down-scaled path (DF.cpp:274): its stage replaces the confidence kernels, dispR is not used, and dispL is
-// the stage's resized map (with fuse_lo only a stand-in that is never dereferenced).
-static int wls_filter_impl(adf_wls_t* h, int n_pairs,
-                           const int16_t* dispL, ptrdiff_t sL, ptrdiff_t psL,
+// The disparity maps of a call: CV_16SC1 or, with f32, CV_32FC1 in the same units (adf_wls_filter_typed_*); the right
+// map has the left one's depth.
+struct DispMaps {
+    const void* L; ptrdiff_t sL, psL;
+    const void* R; ptrdiff_t sR, psR;
+    bool f32;
+    size_t esz() const { return f32 ? sizeof(float) : sizeof(int16_t); }
+};
+
+// scaled: the down-scaled path (DF.cpp:274): its stage replaces the confidence kernels, dm.R is not used, and dm.L is
+// the stage's resized map (with fuse_lo only a stand-in that is never dereferenced; float: the resized v, taken as it is).
+static int wls_filter_impl(adf_wls_t* h, int n_pairs, const DispMaps& dm,
                            const uint8_t* view, ptrdiff_t sG, ptrdiff_t psG, int gch, int W, int H,
-                           const OutMap& om,
-                           const int16_t* dispR, ptrdiff_t sR, ptrdiff_t psR,
-                           const adf_rect* roi_in, hipStream_t st, const ScaledStage* scaled = nullptr)
+                           const OutMap& om, const adf_rect* roi_in, hipStream_t st, const ScaledStage* scaled = nullptr)
 {
     NEED_HANDLE(h);
+    const void* const dispL = dm.L; const void* const dispR = dm.R;
+    const ptrdiff_t sL = dm.sL, psL = dm.psL, sR = dm.sR, psR = dm.psR;
+    const bool f32in = dm.f32;
     // DF.cpp:221-222
     if (!dispL || W <= 0 || H <= 0) return fail(ADF_EBADARG, "disparity_map_left is empty");
     if (!view || (gch != 1 && gch != 3)) return fail(ADF_EBADARG, "left_view must be CV_8UC1 or CV_8UC3");
@@ -616,13 +635,13 @@ static int wls_filter_impl(adf_wls_t* h, int n_pairs,
     const double ob_px = (double)om.esz();                                 // output bytes per pixel
     if (!out) return fail(ADF_EBADARG, "filtered_disparity_map is NULL");
     if (n_pairs < 1) return fail(ADF_EBADARG, "n_pairs must be >= 1");
-    if (sL < (ptrdiff_t)W * 2 || sO < (ptrdiff_t)(W * om.esz()) || sG < (ptrdiff_t)W * gch)
+    if (sL < (ptrdiff_t)(W * dm.esz()) || sO < (ptrdiff_t)(W * om.esz()) || sG < (ptrdiff_t)W * gch)
         return fail(ADF_ESIZE, "row stride smaller than a row");
     if (om.f32 && ((reinterpret_cast<uintptr_t>(out) | (uintptr_t)sO | (uintptr_t)psO) & 3u))
         return fail(ADF_EBADARG, "a float filtered_disparity_map needs a 4-byte aligned base and strides");
     const bool conf = h->use_confidence;
     int rc;
-    if (conf && !scaled && (rc = check_right_map(dispR, sR, W))) return rc;
+    if (conf && !scaled && (rc = check_right_map(dispR, sR, W, dm.esz()))) return rc;
     if (h->lambda < 0 || h->sigma_color < 0) return fail(ADF_EBADARG, "lambda and sigma_color must be >= 0 (FGS.cpp:143)");
     adf_rect roi;
     if ((rc = resolve_roi(h, roi_in, W, H, roi))) return rc;
@@ -635,13 +654,20 @@ static int wls_filter_impl(adf_wls_t* h, int n_pairs,
     h->last_cpitch = g.cpitch; h->last_cx0 = g.cx0; h->last_path = 0; h->last_solver_path = 0;
 
     if ((rc = h->lut.ensure((float)h->sigma_color, st))) return rc;
-    const WlsPlan plan = plan_wls(h, g, n_pairs, dispL, sL, psL, view, sG, psG, gch, scaled);
+    const WlsPlan plan = plan_wls(h, g, n_pairs, dispL, sL, psL, f32in, view, sG, psG, gch, scaled);
+    // float maps: the confidence kernels read int16 planes q of the chunk's maps, made by one launch (design (a))
+    const bool quant = f32in && conf && !scaled;
+    const int qpitch = quant_pitch(W);
+    const size_t qframe = (size_t)qpitch * H;                              // elements per plane
+    // the right-hand sides' source depth: a resized float map (scaled) is taken as it is
+    const int rhs_depth = !f32in ? ADF_16S : scaled ? ADF_32F : DEPTH_WLS_F32;
+    const double db_px = (double)dm.esz();                                 // map bytes per pixel
     const bool wave = plan.wave;
     h->last_solver = wave ? ADF_SOLVER_WAVE : ADF_SOLVER_EXACT;
     if ((rc = h->ws.reserve(plan.per_pair * (size_t)plan.chunk, st, FILL_ZERO))) return rc;
     if (conf && !scaled && (rc = ensure_conf_planes(h, g, n_pairs, st))) return rc;
     {
-        const long long sig[8] = {W, H, roi.x, roi.y, roi.width, roi.height, (long long)plan.band * 4 + (long long)wave * 2 + conf, plan.chunk};
+        const long long sig[8] = {W, H, roi.x, roi.y, roi.width, roi.height, (long long)quant * 8 + (long long)plan.band * 4 + (long long)wave * 2 + conf, plan.chunk};
         if (memcmp(sig, h->ws_sig, sizeof(sig)) != 0) {
             HIP_TRY(hipMemsetAsync(h->ws.p, 0, h->ws.bytes, st));
             memcpy(h->ws_sig, sig, sizeof(sig));
@@ -657,8 +683,11 @@ static int wls_filter_impl(adf_wls_t* h, int n_pairs,
     if (conf) {
         p.A1 = take(g.plane);                     // wave: directly behind A0 (the pair plane spans both)
         if (!wave) { p.F1 = take(g.plane); p.B1 = take(g.plane); }
-        if (!plan.band) { cL = take(g.frame); cR = take(g.frame); }
     }
+    // (before the full-frame maps: everything in front is a multiple of 256 bytes, so the planes' rows are 16-byte aligned)
+    int16_t* const qL = quant ? (int16_t*)take(qframe) : nullptr;          // 2 * qframe int16 = qframe floats per pair
+    int16_t* const qR = quant ? qL + qframe * (size_t)plan.chunk : nullptr;
+    if (conf && !plan.band) { cL = take(g.frame); cR = take(g.frame); }
     // exact: the horizontal pass wants the row index fastest (T); wave: row-major (N), except that two
     // right-hand sides share one interleaved pair plane (A0 and A1 are adjacent: 2*plane floats per
     // image starting at A0) and Cvert is strip-major -- see fgs_wave_common.h
@@ -674,8 +703,13 @@ static int wls_filter_impl(adf_wls_t* h, int n_pairs,
     for (int first = 0; first < n_pairs; first += plan.chunk) {
         const int n = (n_pairs - first < plan.chunk) ? n_pairs - first : plan.chunk;
         const ChunkPlan& cp = n == plan.chunk ? plan.full : plan.tail;
-        const int16_t* dL = (const int16_t*)((const char*)dispL + (ptrdiff_t)first * psL);
-        const int16_t* dR = dispR ? (const int16_t*)((const char*)dispR + (ptrdiff_t)first * psR) : nullptr;
+        // the caller's maps, and what the confidence kernels read: the same, or the chunk's planes q
+        const void* mL = (const char*)dispL + (ptrdiff_t)first * psL;
+        const void* mR = dispR ? (const char*)dispR + (ptrdiff_t)first * psR : nullptr;
+        const int16_t* dL = quant ? qL : (const int16_t*)mL;
+        const int16_t* dR = quant ? qR : (const int16_t*)mR;
+        const ptrdiff_t sLq = quant ? (ptrdiff_t)qpitch * 2 : sL, psLq = quant ? (ptrdiff_t)qframe * 2 : psL;
+        const ptrdiff_t sRq = quant ? (ptrdiff_t)qpitch * 2 : sR, psRq = quant ? (ptrdiff_t)qframe * 2 : psR;
         const uint8_t* gv = view + (ptrdiff_t)first * psG;
         void* o = (char*)out + (ptrdiff_t)first * psO;
         float* confp = conf ? (float*)h->conf.p + (size_t)first * g.cframe : nullptr;
@@ -688,10 +722,17 @@ static int wls_filter_impl(adf_wls_t* h, int n_pairs,
         WeightArgs wa{gv, sG, psG, gch, h->lut.cur, cp.guide_rows ? nullptr : p.CH, p.CV, orient_h, orient_cv, g,
                       wave ? nullptr : p.B0};   // exact: B0 is free until the first pass writes its output there
         const GuideWeights gw = guide_weights(h, gv, sG, psG, gch, g);
-        ConfBandArgs ba{dL, sL, psL, dR, sR, psR, confp, g, rrx, thresh, h->disc_radius, h->roll_off, 0};
-        DiscArgs da{{dL, dR}, {sL, sR}, {psL, psR}, {roi.x, rrx}, roi.y, roi.width, roi.height, h->disc_radius, h->roll_off,
+        ConfBandArgs ba{dL, sLq, psLq, dR, sRq, psRq, confp, g, rrx, thresh, h->disc_radius, h->roll_off, 0};
+        DiscArgs da{{dL, dR}, {sLq, sRq}, {psLq, psRq}, {roi.x, rrx}, roi.y, roi.width, roi.height, h->disc_radius, h->roll_off,
                     {cL, cR}, W, g.frame, cp.stage == CONF_LEFT ? 1 : -1};
-        const FusedInputs fuse = cp.stage == CONF_SCALED_LO ? lo_fuse(h, *scaled, first, g) : view_fuse(confp, dL, sL, psL, g);
+        const FusedInputs fuse = cp.stage == CONF_SCALED_LO ? lo_fuse(h, *scaled, first, g) : view_fuse(confp, mL, sL, psL, f32in, g);
+        // the right-hand sides from the caller's maps and the confidence plane (DF.cpp:286-290): the down-scaled path's
+        // prologue, and the float maps' wherever the first row pass is not fused
+        auto conf_prologue = [&]() {
+            PlainPrologueArgs pa{mL, sL, psL, rhs_depth, 1, 0, p.A0, g, orient_u2, confp, p.A1};
+            ProfScope ps(prof, K_PROLOGUE, (12.0 + db_px) * P, (12.0 + db_px) * P, st);
+            return launch_plain_prologue(pa, n, st);
+        };
 
         hipStream_t wst = st;
         if (cp.fork_weights) {
@@ -708,11 +749,16 @@ static int wls_filter_impl(adf_wls_t* h, int n_pairs,
             HIP_TRY(launch_weights(wa, n, wst));                           // FGS.cpp:163-172
         }
         if (cp.fork_weights) HIP_TRY(hipEventRecord(h->ev_join, h->side));
+        if (quant) {
+            QuantArgs qa{{mL, mR}, {sL, sR}, {psL, psR}, {qL, qR}, nullptr, W, H, qpitch, qframe, n};
+            ProfScope ps(prof, K_QUANT, 12.0 * F, 12.0 * F, st);         // 2 maps: 4 read + 2 written per pixel
+            HIP_TRY(launch_quantise_maps(qa, st));
+        }
 
         switch (cp.stage) {
         case CONF_NONE: {
-            PlainPrologueArgs pa{dL, sL, psL, ADF_16S, 1, 0, p.A0, g, orient_h};
-            ProfScope ps(prof, K_PROLOGUE, 6.0 * P, 6.0 * P, st);
+            PlainPrologueArgs pa{mL, sL, psL, rhs_depth, 1, 0, p.A0, g, orient_h};
+            ProfScope ps(prof, K_PROLOGUE, (4.0 + db_px) * P, (4.0 + db_px) * P, st);
             HIP_TRY(launch_plain_prologue(pa, n, st));                     // FGS.cpp:203-205
             break;
         }
@@ -720,9 +766,7 @@ static int wls_filter_impl(adf_wls_t* h, int n_pairs,
             if (!cp.outside_on_side) HIP_TRY(fill_outside(st));
             if (first == 0 && ((rc = scaled_conf_map(h, *scaled, st, prof)) || (rc = scaled_resize(h, *scaled, st, prof)))) return rc;
             if (plan.fused_first) break;
-            PlainPrologueArgs pa{dL, sL, psL, ADF_16S, 1, 0, p.A0, g, orient_u2, confp, p.A1};
-            ProfScope ps(prof, K_PROLOGUE, 14.0 * P, 14.0 * P, st);
-            HIP_TRY(launch_plain_prologue(pa, n, st));
+            HIP_TRY(conf_prologue());
             break;
         }
         case CONF_SCALED_LO:  // the first row pass taps the low-resolution maps itself: no resize launch, no view-sized planes
@@ -753,8 +797,9 @@ static int wls_filter_impl(adf_wls_t* h, int n_pairs,
                 ProfScope ps(prof, K_DISC, 2.0 * P, 6.0 * P, st);
                 HIP_TRY(launch_discontinuity(da, n, st));                  // DF.cpp:204 (right view)
             }
-            const bool fused = plan.fused_first;
-            ConfLeftArgs ca{dL, sL, psL, dR, sR, psR, cR, confp, fused ? nullptr : p.A0, fused ? nullptr : p.A1,
+            // (float maps: the kernel sees q, so it writes the confidence map only and the prologue forms conf * v)
+            const bool fused = plan.fused_first || quant;
+            ConfLeftArgs ca{dL, sLq, psLq, dR, sRq, psRq, cR, confp, fused ? nullptr : p.A0, fused ? nullptr : p.A1,
                             g, rrx, thresh, h->disc_radius, h->roll_off};
             {   // alg: conf (4P); moved: dL 2 + dR 2 + cR 4 reads, conf 4 (+8 when U0/U1 are materialised)
                 const double wu = fused ? 0.0 : 8.0;
@@ -762,6 +807,7 @@ static int wls_filter_impl(adf_wls_t* h, int n_pairs,
                 HIP_TRY(launch_conf_left(ca, n, st));                      // DF.cpp:204-209 (+288-290)
             }
             if (!cp.outside_on_side) HIP_TRY(fill_outside(st));            // DF.cpp:284, :187-190
+            if (quant && !plan.fused_first) HIP_TRY(conf_prologue());
             break;
         }
         case CONF_TWO_KERNEL: {
@@ -769,9 +815,11 @@ static int wls_filter_impl(adf_wls_t* h, int n_pairs,
                 ProfScope ps(prof, K_DISC, 4.0 * P, 12.0 * P, st);
                 HIP_TRY(launch_discontinuity(da, n, st));                  // DF.cpp:204
             }
-            LrcArgs la{dL, sL, psL, dR, sR, psR, cL, cR, confp, o, sO, psO, fill, om.f32 ? 1 : 0, p.A0, p.A1, g, rrx, thresh, orient_u2};
+            // float maps: the kernel reads its own pixel from the caller's left map (v, and q on the fly), the gather from qR
+            LrcArgs la{quant ? (const int16_t*)mL : dL, quant ? sL : sLq, quant ? psL : psLq, dR, sRq, psRq, cL, cR, confp, o, sO, psO,
+                       fill, om.f32 ? 1 : 0, p.A0, p.A1, g, rrx, thresh, orient_u2, quant ? 1 : 0};
             // alg: confidence map out (4F) + the two rhs planes (8P); moved adds dL,dR,cL,cR reads
-            ProfScope ps(prof, K_LRC, 4.0 * F + 8.0 * P + ob_px * (F - P), 4.0 * F + 20.0 * P + ob_px * (F - P), st);
+            ProfScope ps(prof, K_LRC, 4.0 * F + 8.0 * P + ob_px * (F - P), 4.0 * F + (18.0 + db_px) * P + ob_px * (F - P), st);
             HIP_TRY(launch_lrc_prologue(la, n, st));                       // DF.cpp:208-209,288-290
             break;
         }
@@ -788,22 +836,48 @@ static int wls_filter_impl(adf_wls_t* h, int n_pairs,
 
 // Down-scaled disparity path (DF.cpp:224-227, 239-247, 268-277): disparity maps of dW x dH, view and
 // output of W x H.  ROI is in disparity-map coordinates, like the reference's.
-static int wls_filter_scaled_device(adf_wls_t* h, int n_pairs,
-                                    const int16_t* dispL, ptrdiff_t sL, ptrdiff_t psL, int dW, int dH,
+// Float maps (include/adf_wls.h): base and strides are multiples of 4 bytes, and the filtered map overlaps neither.
+static int check_float_maps(const DispMaps& dm, int n_pairs, int dW, int dH, const OutMap& om, int W, int H)
+{
+    if (!dm.f32) return ADF_OK;
+    if ((reinterpret_cast<uintptr_t>(dm.L) | (uintptr_t)dm.sL | (uintptr_t)dm.psL) & 3u ||
+        (dm.R && ((reinterpret_cast<uintptr_t>(dm.R) | (uintptr_t)dm.sR | (uintptr_t)dm.psR) & 3u)))
+        return fail(ADF_EBADARG, "a float disparity map needs a 4-byte aligned base and strides");
+    // [first byte, last byte] of n_pairs images of `rows` rows of `row_bytes`, whatever the signs of the strides
+    auto span = [&](const void* p, ptrdiff_t s, ptrdiff_t ps, size_t row_bytes, int rows, uintptr_t& lo, uintptr_t& hi) {
+        const ptrdiff_t a = s * (rows - 1), b = ps * (n_pairs - 1);
+        lo = reinterpret_cast<uintptr_t>(p) + (a < 0 ? a : 0) + (b < 0 ? b : 0);
+        hi = reinterpret_cast<uintptr_t>(p) + (a > 0 ? a : 0) + (b > 0 ? b : 0) + row_bytes;
+    };
+    if (!om.p || dW <= 0 || dH <= 0 || W <= 0 || H <= 0 || n_pairs < 1) return ADF_OK;   // (refused by the call itself)
+    uintptr_t olo, ohi, mlo, mhi;
+    span(om.p, om.stride, om.pair_stride, (size_t)W * om.esz(), H, olo, ohi);
+    const void* maps[2] = {dm.L, dm.R}; const ptrdiff_t ss[2] = {dm.sL, dm.sR}, pss[2] = {dm.psL, dm.psR};
+    for (int m = 0; m < 2; m++) {
+        if (!maps[m]) continue;
+        span(maps[m], ss[m], pss[m], (size_t)dW * 4, dH, mlo, mhi);
+        if (olo < mhi && mlo < ohi) return fail(ADF_EBADARG, "filtered_disparity_map overlaps a float disparity map");
+    }
+    return ADF_OK;
+}
+
+static int wls_filter_scaled_device(adf_wls_t* h, int n_pairs, const DispMaps& dm, int dW, int dH,
                                     const uint8_t* view, ptrdiff_t sG, ptrdiff_t psG, int gch, int W, int H,
-                                    const OutMap& om,
-                                    const int16_t* dispR, ptrdiff_t sR, ptrdiff_t psR,
-                                    const adf_rect* roi_in, hipStream_t st)
+                                    const OutMap& om, const adf_rect* roi_in, hipStream_t st)
 {
     NEED_HANDLE(h);
+    int rc;
+    if ((rc = check_float_maps(dm, n_pairs, dW, dH, om, W, H))) return rc;
     if (dW == W && dH == H)                                                // DF.cpp:224-227: same size, resize_factor 1
-        return wls_filter_impl(h, n_pairs, dispL, sL, psL, view, sG, psG, gch, W, H, om, dispR, sR, psR, roi_in, st);
+        return wls_filter_impl(h, n_pairs, dm, view, sG, psG, gch, W, H, om, roi_in, st);
+    const void* const dispL = dm.L; const void* const dispR = dm.R;
+    const ptrdiff_t sL = dm.sL, psL = dm.psL, sR = dm.sR, psR = dm.psR;
+    const bool f32in = dm.f32;
     if (!dispL || dW <= 0 || dH <= 0 || W <= 0 || H <= 0) return fail(ADF_EBADARG, "disparity_map_left is empty");
     if (n_pairs < 1) return fail(ADF_EBADARG, "n_pairs must be >= 1");
-    if (sL < (ptrdiff_t)dW * 2) return fail(ADF_ESIZE, "row stride smaller than a row");
+    if (sL < (ptrdiff_t)(dW * dm.esz())) return fail(ADF_ESIZE, "row stride smaller than a row");
     const bool conf = h->use_confidence;
-    int rc;
-    if (conf && ((rc = check_right_map(dispR, sR, dW)) || (rc = check_radius(h)))) return rc;
+    if (conf && ((rc = check_right_map(dispR, sR, dW, dm.esz())) || (rc = check_radius(h)))) return rc;
     adf_rect rlo;                                                          // disparity-map coordinates
     if ((rc = resolve_roi(h, roi_in, dW, dH, rlo))) return rc;
     const float resize_factor = dW / (float)W;                             // DF.cpp:225
@@ -816,19 +890,26 @@ static int wls_filter_scaled_device(adf_wls_t* h, int n_pairs,
     h->lazy_conf.pending = false;    // (the previous call's low-resolution maps are about to be overwritten or freed)
     const size_t lo = (size_t)dW * dH, hi = (size_t)W * H;
     const Geom ghi = make_geom(W, H, rhi.x, rhi.y, rhi.width, rhi.height);   // the geometry wls_filter_impl will derive
-    ScaledStage s{dispL, sL, psL, dispR, sR, psR, resize_factor, x_ratio, nullptr, 0, nullptr, nullptr,
-                  ConfResize{UNALLOCATED, dW, dH, rlo, ghi, false, n_pairs}, false, nullptr};
+    // float maps: the low-resolution confidence kernels read the planes q, the resize reads the plane v (set below)
+    const int qpitch = quant_pitch(dW);
+    const size_t qframe = (size_t)qpitch * dH;
+    ScaledStage s{(const int16_t*)dispL, sL, psL, (const int16_t*)dispR, sR, psR, nullptr, 0, 0, resize_factor, x_ratio, nullptr, 0,
+                  nullptr, nullptr, ConfResize{UNALLOCATED, dW, dH, rlo, ghi, false, n_pairs}, false, nullptr};
     s.lo.band_map = conf && h->conf_band &&
                     conf_band_fits(plain_conf_layout(make_geom(dW, dH, rlo.x, rlo.y, rlo.width, rlo.height)), h->disc_radius);
     // Can the first row pass interpolate the maps itself (fgs_wave_h.hip, FUSE_LO)?  Confidence mode on the wave solver,
     // scale factors within the staging buffer's reach.  Then neither the resized disparity map nor -- until
     // getConfidenceMap() asks for it -- the resized confidence map is ever written.
-    s.fuse_lo = conf && h->scaled_fuse && h->solver == ADF_SOLVER_WAVE && wave_fits(ghi) &&
+    // (float maps take the resize kernels: the fused low-resolution prologue has no float form)
+    s.fuse_lo = conf && !f32in && h->scaled_fuse && h->solver == ADF_SOLVER_WAVE && wave_fits(ghi) &&
                 wave_hpass_can_fuse_lo(first_pass_probe(lo_fuse(h, s, 0, ghi), ghi.rw));
     // scratch: resized disparity (int16, view size; not with fuse_lo) + low-resolution cL, cR, conf (float)
-    s.dhi_bytes = s.fuse_lo ? 0 : pad_to(hi * 2, 256);
+    s.dhi_bytes = s.fuse_lo ? 0 : pad_to(hi * dm.esz(), 256);
     const size_t maps_bytes = pad_to((size_t)n_pairs * (s.dhi_bytes + (conf ? 3 * lo * sizeof(float) : 0)), 256);
-    const size_t need = maps_bytes + (s.fuse_lo ? 2 * ((size_t)rhi.width + 4) * sizeof(float) : 0);   // + the columns' taps
+    const size_t taps_bytes = pad_to(s.fuse_lo ? 2 * ((size_t)rhi.width + 4) * sizeof(float) : 0, 256);   // + the columns' taps
+    // + float maps: v (float) and, in confidence mode, the two planes q (int16), per pair
+    const size_t quant_bytes = f32in ? (size_t)n_pairs * qframe * (4 + (conf ? 4 : 0)) : 0;
+    const size_t need = maps_bytes + taps_bytes + quant_bytes;
     if ((rc = h->scaled.reserve(need, st, FILL_ZERO))) return rc;
     s.dhi = (char*)h->scaled.p;
     s.cl = (float*)(s.dhi + (size_t)n_pairs * s.dhi_bytes);
@@ -836,21 +917,33 @@ static int wls_filter_scaled_device(adf_wls_t* h, int n_pairs,
     s.lo.clo = s.cr + (size_t)n_pairs * lo;
     s.taps = s.fuse_lo ? (float*)((char*)h->scaled.p + maps_bytes) : nullptr;
     if (conf && (rc = ensure_conf_planes(h, ghi, n_pairs, st))) return rc;
+    if (f32in) {
+        float* v = (float*)((char*)h->scaled.p + maps_bytes + taps_bytes);
+        int16_t* qL = conf ? (int16_t*)(v + (size_t)n_pairs * qframe) : nullptr;
+        int16_t* qR = conf ? qL + (size_t)n_pairs * qframe : nullptr;
+        QuantArgs qa{{dispL, conf ? dispR : nullptr}, {sL, sR}, {psL, psR}, {qL, qR}, v, dW, dH, qpitch, qframe, n_pairs};
+        const double lo_px = (double)lo * n_pairs;
+        ProfScope ps(&h->prof, K_QUANT, (conf ? 16.0 : 8.0) * lo_px, (conf ? 16.0 : 8.0) * lo_px, st);
+        HIP_TRY(launch_quantise_maps(qa, st));
+        s.dispL = qL; s.dispR = qR; s.sL = s.sR = (ptrdiff_t)qpitch * 2; s.psL = s.psR = (ptrdiff_t)qframe * 2;
+        s.vL = v; s.svL = (ptrdiff_t)qpitch * 4; s.psvL = (ptrdiff_t)qframe * 4;
+    }
     // (fuse_lo: wls_filter_impl never dereferences its dispL -- the caller's low-resolution map stands in, with its own strides)
-    rc = wls_filter_impl(h, n_pairs, s.fuse_lo ? dispL : (const int16_t*)s.dhi, (ptrdiff_t)W * 2, (ptrdiff_t)s.dhi_bytes,
-                         view, sG, psG, gch, W, H, om, nullptr, 0, 0, &rhi, st, &s);
+    const DispMaps dhi{s.fuse_lo ? dispL : (const void*)s.dhi, (ptrdiff_t)(W * dm.esz()), (ptrdiff_t)s.dhi_bytes, nullptr, 0, 0, f32in};
+    rc = wls_filter_impl(h, n_pairs, dhi, view, sG, psG, gch, W, H, om, &rhi, st, &s);
     h->roi = rlo;                                                          // getROI(): valid_disp_ROI (DF.cpp:139)
     return rc;
 }
 
-static int wls_filter_scaled_host(adf_wls_t* h, int n_pairs,
-                                  const int16_t* dispL, ptrdiff_t sL, ptrdiff_t psL, int dW, int dH,
+static int wls_filter_scaled_host(adf_wls_t* h, int n_pairs, const DispMaps& dm, int dW, int dH,
                                   const uint8_t* view, ptrdiff_t sG, ptrdiff_t psG, int gch, int W, int H,
-                                  const OutMap& om,
-                                  const int16_t* dispR, ptrdiff_t sR, ptrdiff_t psR,
-                                  const adf_rect* roi)
+                                  const OutMap& om, const adf_rect* roi)
 {
     NEED_HANDLE(h);
+    const void* const dispL = dm.L; const void* const dispR = dm.R;
+    const ptrdiff_t sL = dm.sL, psL = dm.psL, sR = dm.sR, psR = dm.psR;
+    int rc = check_float_maps(dm, n_pairs, dW, dH, om, W, H);
+    if (rc) return rc;
     if (!dispL || !view || !om.p || W <= 0 || H <= 0 || dW <= 0 || dH <= 0 || n_pairs < 1)
         return fail(ADF_EBADARG, "adf_wls_filter_host: empty input");
     if (gch != 1 && gch != 3) return fail(ADF_EBADARG, "left_view must be CV_8UC1 or CV_8UC3");
@@ -859,22 +952,21 @@ static int wls_filter_scaled_host(adf_wls_t* h, int n_pairs,
     hipStream_t st = nullptr;
     // dense device copies: [dispL | dispR | out | view] per batch
     const size_t orow = (size_t)W * om.esz();
-    const size_t dbytes = (size_t)dW * dH * 2, obytes = orow * H, gbytes = (size_t)W * H * gch;
+    const size_t drow = (size_t)dW * dm.esz();
+    const size_t dbytes = drow * dH, obytes = orow * H, gbytes = (size_t)W * H * gch;
     const size_t dpad = pad_to(dbytes, 256), opad = pad_to(obytes, 256), gpad = pad_to(gbytes, 256);
     const size_t need = (size_t)n_pairs * (2 * dpad + opad + gpad);
-    int rc = h->stage.reserve(need, st, FILL_ZERO);
-    if (rc) return rc;
+    if ((rc = h->stage.reserve(need, st, FILL_ZERO))) return rc;
     char* dLd = (char*)h->stage.p;
     char* dRd = dLd + (size_t)n_pairs * dpad;
     char* od = dRd + (size_t)n_pairs * dpad;
     char* gd = od + (size_t)n_pairs * opad;
-    if ((rc = copy_images(dLd, (size_t)dW * 2, dpad, dispL, sL, psL, (size_t)dW * 2, dH, n_pairs, hipMemcpyHostToDevice, st))) return rc;
-    if (dispR && (rc = copy_images(dRd, (size_t)dW * 2, dpad, dispR, sR, psR, (size_t)dW * 2, dH, n_pairs, hipMemcpyHostToDevice, st))) return rc;
+    if ((rc = copy_images(dLd, drow, dpad, dispL, sL, psL, drow, dH, n_pairs, hipMemcpyHostToDevice, st))) return rc;
+    if (dispR && (rc = copy_images(dRd, drow, dpad, dispR, sR, psR, drow, dH, n_pairs, hipMemcpyHostToDevice, st))) return rc;
     if ((rc = copy_images(gd, (size_t)W * gch, gpad, view, sG, psG, (size_t)W * gch, H, n_pairs, hipMemcpyHostToDevice, st))) return rc;
-    rc = wls_filter_scaled_device(h, n_pairs, (const int16_t*)dLd, (ptrdiff_t)dW * 2, (ptrdiff_t)dpad, dW, dH,
-                                  (const uint8_t*)gd, (ptrdiff_t)W * gch, (ptrdiff_t)gpad, gch, W, H,
-                                  OutMap{od, (ptrdiff_t)orow, (ptrdiff_t)opad, om.f32},
-                                  dispR ? (const int16_t*)dRd : nullptr, (ptrdiff_t)dW * 2, (ptrdiff_t)dpad, roi, st);
+    const DispMaps dd{dLd, (ptrdiff_t)drow, (ptrdiff_t)dpad, dispR ? dRd : nullptr, (ptrdiff_t)drow, (ptrdiff_t)dpad, dm.f32};
+    rc = wls_filter_scaled_device(h, n_pairs, dd, dW, dH, (const uint8_t*)gd, (ptrdiff_t)W * gch, (ptrdiff_t)gpad, gch, W, H,
+                                  OutMap{od, (ptrdiff_t)orow, (ptrdiff_t)opad, om.f32}, roi, st);
     if (rc) return rc;
     if ((rc = copy_images(om.p, om.stride, om.pair_stride, od, orow, opad, orow, H, n_pairs, hipMemcpyDeviceToHost, st))) return rc;
     HIP_TRY(hipStreamSynchronize(st));
@@ -891,30 +983,58 @@ static int wls_filter_scaled_host(adf_wls_t* h, int n_pairs,
     extern "C" int adf_wls_filter##SUFFIX##_device(adf_wls_t* h, int n_pairs, ADF_WLS_SAME_ARGS, T* out, ptrdiff_t sO,        \
                                                    ptrdiff_t psO, ADF_WLS_RIGHT_ARGS, void* stream)                           \
     {                                                                                                                         \
-        return wls_filter_impl(h, n_pairs, dispL, sL, psL, view, sG, psG, gch, W, H, OutMap{out, sO, psO, F32}, dispR, sR,    \
-                               psR, roi, (hipStream_t)stream);                                                                \
+        return wls_filter_impl(h, n_pairs, DispMaps{dispL, sL, psL, dispR, sR, psR, false}, view, sG, psG, gch, W, H,         \
+                               OutMap{out, sO, psO, F32}, roi, (hipStream_t)stream);                                          \
     }                                                                                                                         \
     extern "C" int adf_wls_filter_scaled##SUFFIX##_device(adf_wls_t* h, int n_pairs, ADF_WLS_SCALED_ARGS, T* out,             \
                                                           ptrdiff_t sO, ptrdiff_t psO, ADF_WLS_RIGHT_ARGS, void* stream)      \
     {                                                                                                                         \
-        return wls_filter_scaled_device(h, n_pairs, dispL, sL, psL, dW, dH, view, sG, psG, gch, W, H,                         \
-                                        OutMap{out, sO, psO, F32}, dispR, sR, psR, roi, (hipStream_t)stream);                 \
+        return wls_filter_scaled_device(h, n_pairs, DispMaps{dispL, sL, psL, dispR, sR, psR, false}, dW, dH, view, sG, psG,   \
+                                        gch, W, H, OutMap{out, sO, psO, F32}, roi, (hipStream_t)stream);                      \
     }                                                                                                                         \
     extern "C" int adf_wls_filter_scaled##SUFFIX##_host(adf_wls_t* h, int n_pairs, ADF_WLS_SCALED_ARGS, T* out, ptrdiff_t sO, \
                                                         ptrdiff_t psO, ADF_WLS_RIGHT_ARGS)                                    \
     {                                                                                                                         \
-        return wls_filter_scaled_host(h, n_pairs, dispL, sL, psL, dW, dH, view, sG, psG, gch, W, H,                           \
-                                      OutMap{out, sO, psO, F32}, dispR, sR, psR, roi);                                        \
+        return wls_filter_scaled_host(h, n_pairs, DispMaps{dispL, sL, psL, dispR, sR, psR, false}, dW, dH, view, sG, psG,     \
+                                      gch, W, H, OutMap{out, sO, psO, F32}, roi);                                             \
     }                                                                                                                         \
     extern "C" int adf_wls_filter##SUFFIX##_host(adf_wls_t* h, int n_pairs, ADF_WLS_SAME_ARGS, T* out, ptrdiff_t sO,          \
                                                  ptrdiff_t psO, ADF_WLS_RIGHT_ARGS)                                           \
     {                                                                                                                         \
-        return wls_filter_scaled_host(h, n_pairs, dispL, sL, psL, W, H, view, sG, psG, gch, W, H, OutMap{out, sO, psO, F32},  \
-                                      dispR, sR, psR, roi);                                                                   \
+        return wls_filter_scaled_host(h, n_pairs, DispMaps{dispL, sL, psL, dispR, sR, psR, false}, W, H, view, sG, psG, gch,  \
+                                      W, H, OutMap{out, sO, psO, F32}, roi);                                                  \
     }
 ADF_WLS_ENTRIES(, int16_t, false)
 ADF_WLS_ENTRIES(_f32, float, true)
 #undef ADF_WLS_ENTRIES
+
+// The typed pair: the scaled entries' arguments with the maps' and the filtered map's depth as arguments.
+static int typed_depths(int disp_depth, int out_depth)
+{
+    if (disp_depth != ADF_16S && disp_depth != ADF_32F) return fail(ADF_EBADARG, "disparity maps must be ADF_16S or ADF_32F (got depth %d)", disp_depth);
+    if (out_depth != ADF_16S && out_depth != ADF_32F) return fail(ADF_EBADARG, "filtered_disparity_map must be ADF_16S or ADF_32F (got depth %d)", out_depth);
+    return ADF_OK;
+}
+extern "C" int adf_wls_filter_typed_device(adf_wls_t* h, int n_pairs, const void* dispL, ptrdiff_t sL, ptrdiff_t psL, int disp_depth,
+                                           int dW, int dH, const uint8_t* view, ptrdiff_t sG, ptrdiff_t psG, int gch, int W, int H,
+                                           void* out, ptrdiff_t sO, ptrdiff_t psO, int out_depth,
+                                           const void* dispR, ptrdiff_t sR, ptrdiff_t psR, const adf_rect* roi, void* stream)
+{
+    NEED_HANDLE(h);
+    if (int rc = typed_depths(disp_depth, out_depth)) return rc;
+    return wls_filter_scaled_device(h, n_pairs, DispMaps{dispL, sL, psL, dispR, sR, psR, disp_depth == ADF_32F}, dW, dH, view, sG, psG,
+                                    gch, W, H, OutMap{out, sO, psO, out_depth == ADF_32F}, roi, (hipStream_t)stream);
+}
+extern "C" int adf_wls_filter_typed_host(adf_wls_t* h, int n_pairs, const void* dispL, ptrdiff_t sL, ptrdiff_t psL, int disp_depth,
+                                         int dW, int dH, const uint8_t* view, ptrdiff_t sG, ptrdiff_t psG, int gch, int W, int H,
+                                         void* out, ptrdiff_t sO, ptrdiff_t psO, int out_depth,
+                                         const void* dispR, ptrdiff_t sR, ptrdiff_t psR, const adf_rect* roi)
+{
+    NEED_HANDLE(h);
+    if (int rc = typed_depths(disp_depth, out_depth)) return rc;
+    return wls_filter_scaled_host(h, n_pairs, DispMaps{dispL, sL, psL, dispR, sR, psR, disp_depth == ADF_32F}, dW, dH, view, sG, psG,
+                                  gch, W, H, OutMap{out, sO, psO, out_depth == ADF_32F}, roi);
+}
 #undef ADF_WLS_SAME_ARGS
 #undef ADF_WLS_SCALED_ARGS
 #undef ADF_WLS_RIGHT_ARGS

@@ -103,6 +103,9 @@ struct LrcArgs {
     float* U0; float* U1;             // ROI planes: conf*disp, conf
     Geom g; int rrx;                  // right ROI x (DF.cpp:202)
     int thresh; int orient;           // orientation of U0/U1
+    // float maps (adf_wls_filter_typed_*): dL is the caller's CV_32FC1 left map -- the kernel forms v and q of its own
+    // pixel itself, U0 = conf * v -- while dR stays the int16 plane q of the right map (a gather)
+    int dl_f32 = 0;
 };
 
 // Source plane -> float right-hand side on the ROI: the no-confidence path's float(disp)
@@ -119,7 +122,23 @@ struct PlainPrologueArgs {
     int pair2, c2;
 };
 
-// cv::resize(INTER_LINEAR) of CV_16SC1 (is16, optional saturating post-scale) or CV_32FC1 images.
+// A float disparity map of a WLS filter call as a right-hand side source (adf_wls_filter_typed_*): ADF_32F whose
+// elements go through wls_input_value -- the generic smoother's ADF_32F sources are taken as they are.
+constexpr int DEPTH_WLS_F32 = 0x100 | ADF_32F;
+
+// The float disparity maps of a chunk of pairs (adf_wls_filter_typed_*) -> what the confidence kernels read: per map m
+// (0 = left, 1 = right; src[1] may be null) the plane q[m] of q = (int16_t)rintf(v), v = wls_input_value(element), and,
+// where v is set, the left map's v as a float plane (the down-scaled path resizes it).  Planes are `pitch` elements
+// wide (a multiple of 8: 16-byte rows; columns past W hold 0), images `frame` elements apart.
+struct QuantArgs {
+    const void* src[2]; ptrdiff_t stride[2], pair_stride[2];   // bytes
+    int16_t* q[2]; float* v;
+    int W, H, pitch; size_t frame;
+    int n_pairs;
+};
+
+// cv::resize(INTER_LINEAR) of CV_16SC1 (is16, optional saturating post-scale) or CV_32FC1 images (post-scale: one
+// float multiply, no saturation).
 struct ResizeArgs {
     const void* src; ptrdiff_t sstride, spair; int sw, sh; // bytes
     void* dst; ptrdiff_t dstride, dpair; int dw, dh;
@@ -156,7 +175,8 @@ struct FusedInputs {
     // fused prologue of the first horizontal pass (DF.cpp:288-290): when conf_in is set the right-hand
     // sides are read as U1 = conf, U0 = conf * float(dL) from the confidence plane and the disparity map
     const float* conf_in; size_t conf_frame; int conf_pitch, conf_x0, conf_y0;
-    const int16_t* dl_in; ptrdiff_t dl_stride, dl_pair_stride; int dl_x0, dl_y0;
+    int dl_f32;   // dl_in is a CV_32FC1 map (adf_wls_filter_typed_*): U0 = conf * wls_input_value(dL), one float multiply
+    const void* dl_in; ptrdiff_t dl_stride, dl_pair_stride; int dl_x0, dl_y0;
     // ... or, down-scaled path (DF.cpp:268-277 then 288-290), from the LOW-resolution maps: when lo_conf is set the
     // pass interpolates the confidence map and the left disparity map itself (cv::resize INTER_LINEAR, tap for tap as
     // resize_kernels.hip / the oracle's resize_linear_*; disparity saturated, multiplied by lo_post_scale and
@@ -212,6 +232,7 @@ bool prep_small_fits(const Geom& g, int radius, int channels, int n_pairs);
 hipError_t launch_prep_small(const ConfBandArgs& c, const WeightArgs& w, const OutsideArgs& o, int n_pairs, hipStream_t st);
 int conf_left_max_radius();
 hipError_t launch_plain_prologue(const PlainPrologueArgs& a, int n_pairs, hipStream_t st);
+hipError_t launch_quantise_maps(const QuantArgs& a, hipStream_t st);
 hipError_t launch_weights(const WeightArgs& a, int n_pairs, hipStream_t st);   // a.chor null: Cvert only (streaming kernel)
 bool weights_stream_fits(const WeightArgs& a);                                  // ... which takes these arguments?
 hipError_t launch_resize_linear(const ResizeArgs& a, int n_pairs, hipStream_t st);
@@ -291,6 +312,13 @@ __device__ __forceinline__ void store_fill(void* map, ptrdiff_t row_offset_bytes
 // The float epilogues' form of a value the int16 epilogues saturate to -32768 for being NaN, infinite or outside the
 // int range (sat16 below): -32768.0f, so that sat16(float map) == int16 map and the float map holds no NaN or inf.
 __device__ __forceinline__ float wls_f32_value(float x) { return !(__builtin_fabsf(x) < 2147483648.0f) ? -32768.0f : x; }
+// A float disparity map's element as the solve takes it (include/adf_wls.h, float maps): clamped to the int16 range,
+// -32768 where it is NaN or infinite; always finite.  And as the confidence arithmetic takes it: rounded half to even.
+__device__ __forceinline__ float wls_input_value(float d)
+{
+    return __builtin_fabsf(d) < __builtin_inff() ? fminf(fmaxf(d, -32768.0f), 32767.0f) : -32768.0f;
+}
+__device__ __forceinline__ int16_t wls_input_q(float v) { return (int16_t)(int)rintf(v); }
 // saturate_cast<short>(float): cvRound (round-half-even; NaN / out-of-int-range -> INT_MIN) + clamp.
 __device__ __forceinline__ int16_t sat16(float v)
 {

@@ -26,7 +26,8 @@ constexpr int H_TWO_WAVE_MAX = 60;   // longest chunk whose two-right-hand-side 
 //                resize kernels wrote (6 B/px) and this pass read back (6 B/px) never exist.
 //  FUSE_LO_HALF  FUSE_LO for maps of exactly half the view's width on a ROI that starts on an even column >= 2
 //                (lo_interp4).  Same operands, same arithmetic: bit-identical to FUSE_LO (tests).
-constexpr int FUSE_NONE = 0, FUSE_VIEW = 1, FUSE_LO = 2, FUSE_LO_HALF = 3;
+//  FUSE_VIEW_F32 FUSE_VIEW on a CV_32FC1 left map (fused_f32_conf, fused_f32_map): every bucket and weight source FUSE_VIEW has.
+constexpr int FUSE_NONE = 0, FUSE_VIEW = 1, FUSE_LO = 2, FUSE_LO_HALF = 3, FUSE_VIEW_F32 = 4;
 // Where the row's weights come from (WS):
 //  WS_PLANE            the Chor plane the weight kernel wrote (load_c, transpose_in).
 //  WS_GUIDE1 / _GUIDE3 the guide row itself, one or three channels (guide_fetch, guide_weights): Chor is a pure function
@@ -175,6 +176,69 @@ __device__ __forceinline__ void load_fused_view(const WavePassArgs& a, const Row
             t1[k].w = 0.0f;
         }
         t0[k] = make_float4(t1[k].x * (float)draw[k].x, t1[k].y * (float)draw[k].y, t1[k].z * (float)draw[k].z, t1[k].w * (float)draw[k].w);
+    }
+}
+
+// FUSE_VIEW_F32: FUSE_VIEW on a CV_32FC1 left map (adf_wls_filter_typed_*): t0 = conf * v, v = wls_input_value(dL), ONE
+// float multiply where the int16 form has conf * float(dL).  One 16-byte load per lane and vector at any 4-byte aligned
+// address, landing in t0 itself.  Two steps, each "loads only, then arithmetic": fused_f32_conf issues the confidence
+// (and weight) loads, fused_f32_map the map's loads and then forms the clamp, the partial vector and the products.  The
+// kernel runs them back to back -- every load of the row in flight at once, as in the int16 form -- except in the guide
+// forms of the long buckets (fused_f32_defer), where a map row in flight is 2 registers per vector more than the int16
+// form's and the weights' table look-ups would spill: there the map is loaded once the weights are made.
+// The partial last vector is loaded so that it ends with the row (len >= 4), never past the caller's buffer, and its
+// elements are moved down; what lies past the row becomes 0.0f * 0.0f, the +0 the int16 form leaves there.
+constexpr bool fused_f32_defer(int m, bool guide) { return guide && m >= 56; }
+
+template <int M, bool WITH_C>
+__device__ __forceinline__ void fused_f32_conf(const WavePassArgs& a, const RowPos& p, float4 (&tC)[M / 4], float4 (&t1)[M / 4])
+{
+    constexpr int MQ = M / 4;
+    const float4* sF = reinterpret_cast<const float4*>(a.fuse.conf_in + (size_t)blockIdx.y * a.fuse.conf_frame +
+                                                       (size_t)(a.fuse.conf_y0 + blockIdx.x) * a.fuse.conf_pitch + a.fuse.conf_x0);
+    const int nfused = fused_vecs(a.len);
+#pragma unroll
+    for (int k = 0; k < MQ; k++) {
+        const int idx = p.v0 + 64 * k + p.lane;
+        if constexpr (WITH_C) tC[k] = load_c(a, p, k);
+        t1[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (idx < nfused) t1[k] = load_nt(sF + idx);
+    }
+}
+
+template <int M>
+__device__ __forceinline__ void fused_f32_map(const WavePassArgs& a, const RowPos& p, float4 (&t0)[M / 4], float4 (&t1)[M / 4])
+{
+    constexpr int MQ = M / 4;
+    typedef float v4f_u __attribute__((ext_vector_type(4), aligned(4)));
+    const char* sD = reinterpret_cast<const char*>(a.fuse.dl_in) + (ptrdiff_t)blockIdx.y * a.fuse.dl_pair_stride +
+                     (ptrdiff_t)(a.fuse.dl_y0 + blockIdx.x) * a.fuse.dl_stride + (ptrdiff_t)a.fuse.dl_x0 * 4;
+    const int nfull = a.len >> 2, rem = a.len & 3;
+    const int nfused = fused_vecs(a.len);
+    const unsigned dl_last = (unsigned)a.len * 4u - 16u;     // byte offset of the last whole vector (len >= 4)
+#pragma unroll
+    for (int k = 0; k < MQ; k++) {
+        const int idx = p.v0 + 64 * k + p.lane;
+        t0[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (idx < nfused) {
+            const unsigned doff = min((unsigned)idx * 16u, dl_last);
+            const v4f_u dq = __builtin_nontemporal_load(reinterpret_cast<const v4f_u*>(sD + doff));
+            t0[k] = make_float4(dq.x, dq.y, dq.z, dq.w);
+        }
+    }
+    const int tl = nfull - p.v0;                             // the partial vector, counted from this wave's first
+    const int ktail = (rem && tl >= 0 && tl < 16 * M) ? (tl >> 6) : -1;   // wave-uniform: the one k that holds it
+#pragma unroll
+    for (int k = 0; k < MQ; k++) {
+        if (k == ktail && p.lane == (tl & 63)) {             // the vector holds columns len-4 .. len-1: keep the last `rem`
+            const float4 d = t0[k];
+            t0[k] = rem == 1 ? make_float4(d.w, 0.f, 0.f, 0.f) : rem == 2 ? make_float4(d.z, d.w, 0.f, 0.f) : make_float4(d.y, d.z, d.w, 0.f);
+            if (rem < 2) t1[k].y = 0.0f;
+            if (rem < 3) t1[k].z = 0.0f;
+            t1[k].w = 0.0f;
+        }
+        t0[k] = make_float4(t1[k].x * wls_input_value(t0[k].x), t1[k].y * wls_input_value(t0[k].y),
+                            t1[k].z * wls_input_value(t0[k].z), t1[k].w * wls_input_value(t0[k].w));
     }
 }
 
@@ -737,11 +801,16 @@ __global__ void __launch_bounds__(64 * NW, (M > (NW == 2 ? 40 : H_TWO_WAVE_MAX) 
     if constexpr (GUIDE) guide_fetch<M, WS>(a, lane, tG);
     if constexpr (LO) load_fused_lo<M, FUSED == FUSE_LO_HALF>(a, p, stage, tC, t0, t1);
     else if constexpr (FUSED == FUSE_VIEW) load_fused_view<M, !GUIDE>(a, p, tC, t0, t1);
+    else if constexpr (FUSED == FUSE_VIEW_F32) {
+        fused_f32_conf<M, !GUIDE>(a, p, tC, t1);
+        if constexpr (!fused_f32_defer(M, GUIDE)) fused_f32_map<M>(a, p, t0, t1);
+    }
     else load_planes<M, R, !GUIDE>(a, p, tC, t0, t1);
 
     float c[M], f0[M], f1[M];
     if constexpr (GUIDE) guide_weights<M, WS>(a, stage, lut_head, lane, tG, c);
     else transpose_in<M>(stage, lane, tC, c, a.lambda);
+    if constexpr (FUSED == FUSE_VIEW_F32 && fused_f32_defer(M, GUIDE)) fused_f32_map<M>(a, p, t0, t1);
     if constexpr (PAIR && FUSED == FUSE_NONE) {
         pair_in<M>(stage, lane, t0, 0, f0, f1);
         pair_in<M>(stage, lane, t1, 1, f0, f1);
@@ -812,7 +881,8 @@ hipError_t launch_h_guide(const WavePassArgs& a, int n_rhs, dim3 grid, hipStream
 {
     if (a.fuse.conf_in) {
         if (n_rhs != 2) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_VIEW, 1, WS>), grid, dim3(64), 0, st, a);
+        if (a.fuse.dl_f32) hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_VIEW_F32, 1, WS>), grid, dim3(64), 0, st, a);
+        else hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_VIEW, 1, WS>), grid, dim3(64), 0, st, a);
     } else if (n_rhs == 2) hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_NONE, 1, WS>), grid, dim3(64), 0, st, a);
     else hipLaunchKernelGGL((wave_hpass_kernel<M, 1, FUSE_NONE, 1, WS>), grid, dim3(64), 0, st, a);
     return hipGetLastError();
@@ -842,7 +912,8 @@ hipError_t launch_h(const WavePassArgs& a, int n_rhs, int n_pairs, hipStream_t s
         if (!half) hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_LO, NW>), grid, block, 0, st, a);
     } else if (a.fuse.conf_in) {
         if (n_rhs != 2) return hipErrorInvalidValue;
-        hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_VIEW, NW>), grid, block, 0, st, a);
+        if (a.fuse.dl_f32) hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_VIEW_F32, NW>), grid, block, 0, st, a);
+        else hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_VIEW, NW>), grid, block, 0, st, a);
     } else if (n_rhs == 2) hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_NONE, NW>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((wave_hpass_kernel<M, 1, FUSE_NONE, NW>), grid, block, 0, st, a);
     return hipGetLastError();
@@ -874,7 +945,8 @@ bool wave_hpass_can_fuse(const WavePassArgs& a)
     if (!a.fuse.conf_in || !a.fuse.dl_in) return false;
     if (a.len < 4 || a.fuse.conf_pitch % 4 != 0 || a.fuse.conf_x0 % 4 != 0 || a.fuse.conf_frame % 4 != 0) return false;
     if ((reinterpret_cast<uintptr_t>(a.fuse.conf_in) & 15u) != 0) return false;
-    if (a.fuse.dl_stride % 2 != 0 || a.fuse.dl_pair_stride % 2 != 0 || (reinterpret_cast<uintptr_t>(a.fuse.dl_in) & 1u) != 0) return false;
+    const unsigned em = a.fuse.dl_f32 ? 3u : 1u;              // the map's element alignment: 16-byte loads at any 4-byte address
+    if ((a.fuse.dl_stride & em) != 0 || (a.fuse.dl_pair_stride & em) != 0 || (reinterpret_cast<uintptr_t>(a.fuse.dl_in) & em) != 0) return false;
     return true;
 }
 

@@ -39,10 +39,13 @@ static_assert(RC == 4, "the vector stores below write four columns");
 //   element alignment; a tap picks its element by a per-lane index fixed for the whole tile.  A dword load per tap cost
 //   ~32 cycles of the CU's address path each (40 per thread): the kernels ran at 1.0-1.8 TB/s whatever the loads'
 //   order.
-template <bool IS16, bool UP, bool VEC>
+//   FSCALE (CV_32FC1 only): the result is multiplied once by post_scale, in float, without rounding to an integer or
+//   saturating: the float disparity maps of adf_wls_filter_typed_* (the CV_16S form's x_ratio step, DF.cpp:244,273).
+template <bool IS16, bool UP, bool VEC, bool FSCALE = false>
 __global__ void __launch_bounds__(256) resize_linear_kernel(ResizeArgs a)
 {
     static_assert(!VEC || UP, "the vector path is an upscaling path");
+    static_assert(!FSCALE || !IS16, "the CV_16S form has its own saturating post-scale");
     constexpr int NS = UP ? RR + 1 : 2 * RR;
     const int dx0 = (blockIdx.x * 256 + threadIdx.x) * RC;
     if (dx0 >= a.dw) return;
@@ -191,6 +194,10 @@ __global__ void __launch_bounds__(256) resize_linear_kernel(ResizeArgs a)
                     for (int c = 0; c < RC; c++) if (dx0 + c < a.dw) d[c] = q[c];
                 }
             } else {
+                if constexpr (FSCALE) {
+    #pragma unroll
+                    for (int c = 0; c < RC; c++) v[c] = v[c] * a.post_scale;
+                }
                 float* d = reinterpret_cast<float*>(drow) + dx0;
                 if (full && (reinterpret_cast<uintptr_t>(d) & 15u) == 0) {
                     typedef float v4f __attribute__((ext_vector_type(4)));
@@ -218,6 +225,10 @@ hipError_t launch_resize_linear(const ResizeArgs& a, int n_pairs, hipStream_t st
         if (vec) hipLaunchKernelGGL((resize_linear_kernel<true, true, true>), grid, dim3(256), 0, st, a);
         else if (up) hipLaunchKernelGGL((resize_linear_kernel<true, true, false>), grid, dim3(256), 0, st, a);
         else hipLaunchKernelGGL((resize_linear_kernel<true, false, false>), grid, dim3(256), 0, st, a);
+    } else if (a.post_scale != 1.0f) {
+        if (vec) hipLaunchKernelGGL((resize_linear_kernel<false, true, true, true>), grid, dim3(256), 0, st, a);
+        else if (up) hipLaunchKernelGGL((resize_linear_kernel<false, true, false, true>), grid, dim3(256), 0, st, a);
+        else hipLaunchKernelGGL((resize_linear_kernel<false, false, false, true>), grid, dim3(256), 0, st, a);
     } else {
         if (vec) hipLaunchKernelGGL((resize_linear_kernel<false, true, true>), grid, dim3(256), 0, st, a);
         else if (up) hipLaunchKernelGGL((resize_linear_kernel<false, true, false>), grid, dim3(256), 0, st, a);

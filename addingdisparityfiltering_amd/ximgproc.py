@@ -172,6 +172,18 @@ def _check_device(dev, imgs, what):
                                              "(create one handle per GPU)" % (what, dev, im.keep.device.index))
 
 
+def _map_dtype(m, exactly=None):
+    """np.float32 for a float32 disparity map (numpy or torch), np.int16 for everything else -- which _Image then holds
+    to int16, so that any other dtype is refused with ADF_EBADARG.  With `exactly`: that dtype if the map has it, else None."""
+    dt = getattr(m, "dtype", None)
+    want = np.float32 if exactly is None else exactly
+    if _is_torch(m):
+        has = dt is _TORCH_DTYPE[want]
+    else:
+        has = dt is not None and np.dtype(dt) == np.dtype(want)
+    return want if has else (np.int16 if exactly is None else None)
+
+
 class DisparityFilter:
     """Main interface for all disparity map filters (DF.hpp:52-76)."""
 
@@ -258,6 +270,8 @@ class DisparityWLSFilter(_Handle, DisparityFilter):
     # ---- DisparityFilter::filter (DF.hpp:75) ----
     def filter(self, disparity_map_left, left_view, filtered_disparity_map=None,
                disparity_map_right=None, ROI=None, right_view=None):
+        """disparity maps: int16 (CV_16SC1) or float32 (CV_32FC1, the same units: disparity * 16 -- include/adf_wls.h,
+        adf_wls_filter_typed_*); the left map's dtype selects the depth and the right map must have it too."""
         return self._filter("adf_wls_filter_scaled", np.int16, disparity_map_left, left_view, filtered_disparity_map,
                             disparity_map_right, ROI)
 
@@ -276,14 +290,19 @@ class DisparityWLSFilter(_Handle, DisparityFilter):
         if left_view is None:
             raise AdfError(_lib.ADF_EBADARG, "left_view is empty")
         batched = len(disparity_map_left.shape) == 3
-        dl = _Image(disparity_map_left, np.int16, "disparity_map_left", batched)
+        # the left map's dtype selects the maps' depth: int16, or float32 through the typed entry (refused here, before
+        # the library is asked: float64, float16, and a right map of another dtype)
+        mdt = _map_dtype(disparity_map_left)
+        if mdt is np.float32 and disparity_map_right is not None and _map_dtype(disparity_map_right, np.int16) is np.int16:
+            mdt = np.int16   # a pair has ONE depth: beside an int16 right map the float32 left map is the one refused
+        dl = _Image(disparity_map_left, mdt, "disparity_map_left", batched)
         gv = _Image(left_view, np.uint8, "left_view", batched, allow_channels=(1, 3))
         if gv.n != dl.n:
             raise AdfError(_lib.ADF_ESIZE, "batch sizes of disparity maps and views differ")
         # a disparity map of another resolution is resized to the view (DF.cpp:224-227, 239-247, 268-277)
         dr = None
         if disparity_map_right is not None and getattr(disparity_map_right, "size", 1) != 0:
-            dr = _Image(disparity_map_right, np.int16, "disparity_map_right", batched)
+            dr = _Image(disparity_map_right, mdt, "disparity_map_right", batched)
             if (dr.n, dr.h, dr.w) != (dl.n, dl.h, dl.w):
                 raise AdfError(_lib.ADF_ESIZE, "left and right disparity maps differ in size")  # DF.cpp:263-264
         elif self._use_confidence:
@@ -304,6 +323,9 @@ class DisparityWLSFilter(_Handle, DisparityFilter):
                 out.ptr, out.stride, out.pair_stride,
                 dr.ptr if dr else None, dr.stride if dr else 0, dr.pair_stride if dr else 0,
                 C.byref(roi) if roi is not None else None)
+        if mdt is np.float32:   # (int16 maps stay on their entry, argument for argument)
+            entry = "adf_wls_filter_typed"
+            args = args[:5] + (_lib.DEPTH_32F,) + args[5:16] + (_DEPTH[out_dtype],) + args[16:]
         # (the one fork written out instead of going through _call: this call's host time is counted in microseconds)
         if dl.device:
             _lib.check(getattr(_lib.lib(), entry + "_device")(*args, _stream_of(dl)))

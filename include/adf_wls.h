@@ -136,8 +136,8 @@ int adf_wls_get_last_solver_path(const adf_wls_t* h, int* path_flags);
 
 /* DisparityFilter::filter (DF.hpp:75, DF.cpp:219-298) on a batch of n_pairs
  * independent, equally sized stereo pairs laid out `*_pair_stride` bytes apart
- * (n_pairs = 1 is the reference call).  disparity maps: CV_16SC1 (disparity*16),
- * W x H; left_view: CV_8UC1 / CV_8UC3 (view_channels), same size; out: CV_16SC1,
+ * (n_pairs = 1 is the reference call).  disparity maps: CV_16SC1 (disparity*16; CV_32FC1 maps go through
+ * adf_wls_filter_typed_* below), W x H; left_view: CV_8UC1 / CV_8UC3 (view_channels), same size; out: CV_16SC1,
  * W x H, filled with -16 outside the ROI (DF.cpp:254,284).  disp_right may be
  * NULL only for a filter created with use_confidence = 0.  roi: NULL or zero
  * area = derive from the offsets given at creation (DF.cpp:228-233). */
@@ -230,6 +230,57 @@ int adf_wls_filter_scaled_f32_host(adf_wls_t* h, int n_pairs,
                                    float* out, ptrdiff_t out_stride, ptrdiff_t out_pair_stride,
                                    const int16_t* disp_right, ptrdiff_t disp_right_stride, ptrdiff_t disp_right_pair_stride,
                                    const adf_rect* roi);
+
+/* Extension: float32 (CV_32FC1) disparity MAPS, through one typed pair of entries.  The reference asserts CV_16S maps
+ * (DF.cpp:221,262); upstream OpenCV widened DisparityWLSFilter::filter to CV_32F later, so the definition is this library's
+ * own, as with the float filtered map above.  For callers whose disparities are float already -- a learned matcher or a
+ * cost-volume refinement on the same device, adf_wls_filter_f32_*'s own output -- and who would otherwise round them to
+ * 1/16 pixel, the very information the float filtered map keeps.
+ * adf_wls_filter_typed_*: the arguments of adf_wls_filter_scaled_* with the maps and `out` as void*, `disp_depth` (the
+ * depth of BOTH maps) behind the left map's strides and `out_depth` behind the output's strides, each ADF_16S or ADF_32F
+ * (ADF_EBADARG otherwise).  disp_W == W && disp_H == H is the plain call.  With disp_depth == ADF_16S the call is byte
+ * for byte adf_wls_filter[_scaled][_f32]_*; the eight entries above keep their signatures and behaviour.
+ * Float maps (disp_depth == ADF_32F):
+ *   - Units: those of the int16 map, disparity * 16.  CV_32FC1, base and strides multiples of 4 bytes (ADF_EBADARG
+ *     otherwise); left and right map have the same depth.  `out` must not overlap the maps (ADF_EBADARG).
+ *   - For every element d two values are derived where it is loaded:
+ *       v = isfinite(d) ? min(max(d, -32768.0f), 32767.0f) : -32768.0f     the value the solve uses;
+ *       q = (int16_t)rintf(v), half to even                                the value the confidence map uses.
+ *   - Confidence: the discontinuity maps (DF.cpp:161-210, 349-373), the discontinuity-aware left-right check
+ *     (DF.cpp:306-341, including ridx = j - (q >> 4) and abs(q + qr) < thresh) and the low-resolution confidence of a
+ *     scaled call are computed on q: adf_wls_get_confidence_* after a float call is bit for bit the map of the int16 call
+ *     on the q maps.  (That arithmetic is integer sums and thresholds of 1.5 px; it gains nothing from sub-LSB input.)
+ *   - Data term: u0 = c * v with confidence -- ONE float multiply where the int16 call has c * (float)d (DF.cpp:288-290)
+ *     -- and u0 = v without (DF.cpp:250,257).  Weights, passes, epilogues, fill, ROI, chunking, solver fallback,
+ *     profiling and stream capture are those of the int16 call.
+ *   - Scaled calls (maps smaller than the view): the v map is resized with the float taps the confidence map goes
+ *     through, then multiplied once, in float, by x_ratio = W / (float)disp_W (DF.cpp:241-244, 270-273): no rounding, no
+ *     saturation.  The low-resolution confidence is computed on q with resize_factor, then resized, as for int16 maps.
+ *     Such a call never reports ADF_PATH_SCALED_FUSED (it runs the resize kernels).
+ *   - Relation R1, full-resolution calls: when every element of both maps is an integer in [-32768, 32767], the int16
+ *     output and the float output are bit for bit those of the int16 call on the (int16_t) maps, with either solver, on
+ *     every path, and adf_wls_get_last_path reports the same word.  It does NOT hold for scaled calls: the int16 call
+ *     rounds (and saturates) the interpolated map, the float call does not.
+ *   - Never NaN: for any input bits (NaN, +-inf, 1e30) the guarantees of the float filtered map above carry over -- no NaN
+ *     or inf in the output, -16.0f outside the ROI, saturate_cast<short>(out_f32) == out_i16.
+ *   - Workspace: a confidence-mode call keeps the two maps' q as int16 planes (one extra launch, 12 bytes per pixel of
+ *     traffic, 4 bytes per pixel and pair of adf_wls_workspace_bytes); calls on int16 maps neither run it nor pay for it. */
+int adf_wls_filter_typed_device(adf_wls_t* h, int n_pairs,
+                                const void* disp_left, ptrdiff_t disp_left_stride, ptrdiff_t disp_left_pair_stride, int disp_depth,
+                                int disp_W, int disp_H,
+                                const uint8_t* left_view, ptrdiff_t view_stride, ptrdiff_t view_pair_stride,
+                                int view_channels, int W, int H,
+                                void* out, ptrdiff_t out_stride, ptrdiff_t out_pair_stride, int out_depth,
+                                const void* disp_right, ptrdiff_t disp_right_stride, ptrdiff_t disp_right_pair_stride,
+                                const adf_rect* roi, void* stream);
+int adf_wls_filter_typed_host(adf_wls_t* h, int n_pairs,
+                              const void* disp_left, ptrdiff_t disp_left_stride, ptrdiff_t disp_left_pair_stride, int disp_depth,
+                              int disp_W, int disp_H,
+                              const uint8_t* left_view, ptrdiff_t view_stride, ptrdiff_t view_pair_stride,
+                              int view_channels, int W, int H,
+                              void* out, ptrdiff_t out_stride, ptrdiff_t out_pair_stride, int out_depth,
+                              const void* disp_right, ptrdiff_t disp_right_stride, ptrdiff_t disp_right_pair_stride,
+                              const adf_rect* roi);
 
 /* getConfidenceMap() (DF.hpp:117, DF.cpp:138): CV_32FC1, W x H, values in [0,255],
  * zero outside the ROI, of pair `pair` of the last filter call.  Valid until the

@@ -456,14 +456,18 @@ private:
     // filter() and filterToFloat(): one set of checks, the output's depth and the entry point differ
     void run(const Mat& dl, const Mat& view, Mat& out, const Mat& dr, Rect ROI, bool f32)
     {
-        if (dl.empty() || mat_depth(dl) != D16S || mat_channels(dl) != 1)       // DF.cpp:221
-            throw Exception(ADF_EBADARG, "disparity_map_left must be a non-empty CV_16SC1 image");
+        // CV_16SC1 (DF.cpp:221) or, an extension, CV_32FC1 maps in the same units (adf_wls_filter_typed_* in adf_wls.h:
+        // the solve takes the floats as they are, the confidence map their rounding); the left map's depth is the pair's
+        const bool fin = !dl.empty() && mat_depth(dl) == D32F;
+        if (dl.empty() || (mat_depth(dl) != D16S && !fin) || mat_channels(dl) != 1)
+            throw Exception(ADF_EBADARG, "disparity_map_left must be a non-empty CV_16SC1 or CV_32FC1 image");
         if (view.empty() || mat_depth(view) != D8U || (mat_channels(view) != 1 && mat_channels(view) != 3)) // :222
             throw Exception(ADF_EBADARG, "left_view must be CV_8UC1 or CV_8UC3");
         const bool have_r = !dr.empty();
         if (use_confidence_) {                                                 // DF.cpp:262-264
-            if (!have_r || mat_depth(dr) != D16S || mat_channels(dr) != 1)
-                throw Exception(ADF_EBADARG, "disparity_map_right must be a non-empty CV_16SC1 image");
+            if (!have_r || mat_depth(dr) != mat_depth(dl) || mat_channels(dr) != 1)
+                throw Exception(ADF_EBADARG, fin ? "disparity_map_right must be a non-empty CV_32FC1 image, as the left map is"
+                                                 : "disparity_map_right must be a non-empty CV_16SC1 image");
             if (dr.rows != dl.rows || dr.cols != dl.cols)
                 throw Exception(ADF_ESIZE, "left and right disparity maps differ in size");
         }
@@ -474,7 +478,11 @@ private:
         const ptrdiff_t rs = have_r ? mat_step(dr) : 0;
         const adf_rect* rp = ROI.area() != 0 ? &roi : nullptr;
         // a lower-resolution disparity map is resized to the view inside the call (DF.cpp:239-247,268-277)
-        if (f32)
+        if (fin)
+            check(adf_wls_filter_typed_host(h_, 1, dl.data, mat_step(dl), 0, ADF_32F, dl.cols, dl.rows, view.data, mat_step(view), 0,
+                                            mat_channels(view), view.cols, view.rows, out.data, mat_step(out), 0,
+                                            f32 ? ADF_32F : ADF_16S, (have_r && use_confidence_) ? dr.data : nullptr, rs, 0, rp));   // (no confidence: no use for a right map)
+        else if (f32)
             check(adf_wls_filter_scaled_f32_host(h_, 1, l, mat_step(dl), 0, dl.cols, dl.rows, view.data, mat_step(view), 0,
                                                  mat_channels(view), view.cols, view.rows,
                                                  reinterpret_cast<float*>(out.data), mat_step(out), 0, r, rs, 0, rp));
