@@ -19,6 +19,11 @@ using namespace adf;
 // shared pieces
 // ----------------------------------------------------------------------------------------------
 static inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+// image k of a batch whose images lie `pair_stride` bytes apart (null stays null)
+template <class T> static const T* pairs_on(const T* p, ptrdiff_t pair_stride, int k)
+{
+    return p ? (const T*)((const char*)p + (ptrdiff_t)k * pair_stride) : nullptr;
+}
 
 static Geom make_geom(int W, int H, int rx, int ry, int rw, int rh)
 {
@@ -43,6 +48,33 @@ static Geom plain_conf_layout(Geom g) { g.cx0 = 0; g.cpitch = g.W; g.cframe = g.
 enum KClass { K_FILL = 0, K_WEIGHTS, K_DISC, K_LRC, K_PROLOGUE, K_PASS_H_FIRST, K_PASS_H, K_PASS_V, K_PASS_V_LAST, K_RESIZE, K_QUANT, K_COUNT };
 static const char* const kclass_names[K_COUNT] = {"fill_outside", "weights", "discontinuity", "lrc_confidence",
                                                   "plain_prologue", "pass_h_first", "pass_h", "pass_v", "pass_v_last", "resize", "quantise_maps"};
+// What a launch reports: the bytes the algorithm has to move, and the bytes this kernel moves.  One function
+// per class of the preparation stage (run_passes has the solve passes'); P = ROI pixels, F = frame pixels, outside =
+// F - P, all times the pair count; out_b / map_b = bytes per element of the filtered map / the disparity maps.
+struct Bytes { double alg, moved; };
+static Bytes same_bytes(double b) { return Bytes{b, b}; }
+static Bytes fill_bytes(double outside, bool conf, double out_b) { return same_bytes(((conf ? 4.0 : 0.0) + out_b) * outside); }
+static Bytes weights_bytes(double P, int gch, bool chor) { return same_bytes((gch + (chor ? 8.0 : 4.0)) * P); }
+// reads the int16 ROIs, writes the float maps (the maps themselves are not algorithmic I/O); one view or both
+static Bytes disc_bytes(double P, bool both) { return both ? Bytes{4.0 * P, 12.0 * P} : Bytes{2.0 * P, 6.0 * P}; }
+// lrc_confidence, band kernel: dL 2 + dR 2 read, conf 4 written
+static Bytes band_bytes(double P) { return same_bytes(8.0 * P); }
+// ... merged launch: the band kernel's, the weight kernel's with both planes, the fill's with the confidence plane
+static Bytes merged_bytes(double P, double outside, int gch, double out_b) { return same_bytes((8.0 + gch + 8.0) * P + (4.0 + out_b) * outside); }
+// ... left-view kernel: alg conf (4P); moved dL 2 + dR 2 + cR 4 reads, conf 4 (+8 when U0/U1 are materialised)
+static Bytes conf_left_bytes(double P, bool rhs) { const double wu = rhs ? 8.0 : 0.0; return Bytes{(4.0 + wu) * P, (12.0 + wu) * P}; }
+// ... LRC kernel: alg confidence map out (4F) + the two rhs planes (8P); moved adds dL, dR, cL, cR reads; `fill`: the
+// filtered map outside the ROI where the kernel writes that too
+static Bytes lrc_bytes(double F, double P, bool rhs, double map_b, double fill)
+{
+    return Bytes{4.0 * F + (rhs ? 8.0 * P : 0.0) + fill, 4.0 * F + (rhs ? 18.0 + map_b : 12.0) * P + fill};
+}
+// float(src) (4P written), or conf * float(src) and conf (conf read, 8P written)
+static Bytes prologue_bytes(double P, bool weighted, double map_b) { return same_bytes(((weighted ? 12.0 : 4.0) + map_b) * P); }
+static Bytes resize_bytes(double dst_px, double src_px, double elem_b) { return same_bytes(elem_b * dst_px + elem_b * src_px); }
+// per map 4 read and, for q, 2 written; v: 4 written
+static Bytes quant_bytes(double px, bool q, bool right, bool v) { return same_bytes(((right ? 8.0 : 4.0) + (q ? (right ? 4.0 : 2.0) : 0.0) + (v ? 4.0 : 0.0)) * px); }
+
 struct Profiler {
     bool on = false;
     struct Rec { int cls; hipEvent_t a, b; double alg, moved; };
@@ -67,6 +99,7 @@ struct ProfScope {
         r.cls = cls; r.alg = alg; r.moved = moved; r.a = p->get(); r.b = p->get();
         if (r.a) hipEventRecord(r.a, st);
     }
+    ProfScope(Profiler* prof, int cls, Bytes b, hipStream_t s) : ProfScope(prof, cls, b.alg, b.moved, s) {}
     ~ProfScope()
     {
         if (!p) return;
@@ -362,18 +395,115 @@ static int resolve_roi(const adf_wls* h, const adf_rect* roi_in, int w, int hgt,
     return ADF_OK;
 }
 
-// DF.cpp:262-264: the right map of a confidence-mode call on maps w wide
-static int check_right_map(const void* dispR, ptrdiff_t sR, int w, size_t esz)
+// The filtered map of a call: CV_16SC1 (adf_wls_filter_*) or, with f32, CV_32FC1 holding the float the int16 epilogue
+// rounds (adf_wls_filter_f32_*).  Only the last column pass and the fill outside the ROI know the difference.
+struct OutMap {
+    void* p; ptrdiff_t stride, pair_stride; bool f32;
+    size_t esz() const { return f32 ? sizeof(float) : sizeof(int16_t); }
+};
+
+// The disparity maps of a call: CV_16SC1 or, with f32, CV_32FC1 in the same units (adf_wls_filter_typed_*); the right
+// map has the left one's depth.
+struct DispMaps {
+    const void* L; ptrdiff_t sL, psL;
+    const void* R; ptrdiff_t sR, psR;
+    bool f32;
+    size_t esz() const { return f32 ? sizeof(float) : sizeof(int16_t); }
+    DispMaps from(int k) const { return DispMaps{pairs_on(L, psL, k), sL, psL, pairs_on(R, psR, k), sR, psR, f32}; }
+};
+
+struct View { const uint8_t* p; ptrdiff_t stride, pair_stride; int ch, W, H; };
+
+// One filter call, as check_call has accepted it.  Every entry point -- same size, down-scaled and typed; the host
+// entries with their device copies -- builds one, and nothing behind it looks at the caller's arguments again.
+struct WlsCall {
+    int n_pairs;
+    DispMaps dm; int dW, dH;         // the caller's maps and their own size
+    View view;                       // W x H
+    OutMap om;                       // W x H
+    adf_rect rlo, rhi;               // the ROI in map coordinates (getROI(), DF.cpp:139) and in view coordinates
+    float resize_factor, x_ratio;    // DF.cpp:225, 241
+    bool scaled;                     // the maps are not of the view's size (DF.cpp:224-227, 239-247, 268-277)
+};
+
+static int no_right_map() { return fail(ADF_EBADARG, "disparity_map_right is required with use_confidence"); }
+static int bad_view_channels() { return fail(ADF_EBADARG, "left_view must be CV_8UC1 or CV_8UC3"); }
+
+// Float maps (include/adf_wls.h): base and strides are multiples of 4 bytes, and the filtered map overlaps neither.
+static int check_float_maps(const DispMaps& dm, int n_pairs, int dW, int dH, const OutMap& om, int W, int H)
 {
-    if (!dispR) return fail(ADF_EBADARG, "disparity_map_right is required with use_confidence");
-    if (sR < (ptrdiff_t)(w * esz)) return fail(ADF_ESIZE, "right disparity stride smaller than a row");
+    if (!dm.f32) return ADF_OK;
+    if ((reinterpret_cast<uintptr_t>(dm.L) | (uintptr_t)dm.sL | (uintptr_t)dm.psL) & 3u ||
+        (dm.R && ((reinterpret_cast<uintptr_t>(dm.R) | (uintptr_t)dm.sR | (uintptr_t)dm.psR) & 3u)))
+        return fail(ADF_EBADARG, "a float disparity map needs a 4-byte aligned base and strides");
+    // [first byte, last byte] of n_pairs images of `rows` rows of `row_bytes`, whatever the signs of the strides
+    auto span = [&](const void* p, ptrdiff_t s, ptrdiff_t ps, size_t row_bytes, int rows, uintptr_t& lo, uintptr_t& hi) {
+        const ptrdiff_t a = s * (rows - 1), b = ps * (n_pairs - 1);
+        lo = reinterpret_cast<uintptr_t>(p) + (a < 0 ? a : 0) + (b < 0 ? b : 0);
+        hi = reinterpret_cast<uintptr_t>(p) + (a > 0 ? a : 0) + (b > 0 ? b : 0) + row_bytes;
+    };
+    if (!om.p || dW <= 0 || dH <= 0 || W <= 0 || H <= 0 || n_pairs < 1) return ADF_OK;   // (refused by the rules behind this one)
+    uintptr_t olo, ohi, mlo, mhi;
+    span(om.p, om.stride, om.pair_stride, (size_t)W * om.esz(), H, olo, ohi);
+    const void* maps[2] = {dm.L, dm.R}; const ptrdiff_t ss[2] = {dm.sL, dm.sR}, pss[2] = {dm.psL, dm.psR};
+    for (int m = 0; m < 2; m++) {
+        if (!maps[m]) continue;
+        span(maps[m], ss[m], pss[m], (size_t)dW * 4, dH, mlo, mhi);
+        if (olo < mhi && mlo < ohi) return fail(ADF_EBADARG, "filtered_disparity_map overlaps a float disparity map");
+    }
     return ADF_OK;
 }
 
-static int check_radius(const adf_wls* h)
+// THE argument check of DisparityWLSFilter::filter: every rule once, and the record of the accepted call.  The ROI is in
+// disparity-map coordinates, like the reference's.  The rules run in one of two orders, because which of two faults a
+// call is refused for is part of the interface (tests/test_abi.py and its siblings pin it): a same-size call is checked in
+// the reference's order (DF.cpp:221-233, 262-264); a down-scaled call settles its maps and both ROIs before it looks at
+// the view and the filtered map.
+static int check_call(const adf_wls* h, int n_pairs, const DispMaps& dm, int dW, int dH, const View& view, const OutMap& om,
+                      const adf_rect* roi_in, WlsCall& c)
 {
-    if (h->disc_radius < 0 || h->disc_radius > max_disc_radius())
-        return fail(ADF_EBADARG, "depth discontinuity radius %d outside [0,%d]", h->disc_radius, max_disc_radius());
+    const int W = view.W, H = view.H;
+    const bool conf = h->use_confidence;
+    c = WlsCall{n_pairs, dm, dW, dH, view, om, adf_rect{0, 0, 0, 0}, adf_rect{0, 0, 0, 0}, 1.0f, 1.0f, !(dW == W && dH == H)};
+    const auto short_row = []() -> int { return fail(ADF_ESIZE, "row stride smaller than a row"); };
+    const auto refuse_if = [](bool bad, int code, const char* msg) -> int { return bad ? fail(code, "%s", msg) : ADF_OK; };
+    const auto maps = [&] { return refuse_if(!dm.L || dW <= 0 || dH <= 0 || W <= 0 || H <= 0, ADF_EBADARG, "disparity_map_left is empty"); };   // DF.cpp:221-222
+    const auto guide = [&]() -> int { return !view.p || (view.ch != 1 && view.ch != 3) ? bad_view_channels() : ADF_OK; };
+    const auto filtered = [&] { return refuse_if(!om.p, ADF_EBADARG, "filtered_disparity_map is NULL"); };
+    const auto pairs = [&] { return refuse_if(n_pairs < 1, ADF_EBADARG, "n_pairs must be >= 1"); };
+    const auto map_rows = [&]() -> int { return dm.sL < (ptrdiff_t)(dW * dm.esz()) ? short_row() : ADF_OK; };
+    const auto view_rows = [&]() -> int { return om.stride < (ptrdiff_t)(W * om.esz()) || view.stride < (ptrdiff_t)W * view.ch ? short_row() : ADF_OK; };
+    const auto float_out = [&] {
+        return refuse_if(om.f32 && ((reinterpret_cast<uintptr_t>(om.p) | (uintptr_t)om.stride | (uintptr_t)om.pair_stride) & 3u), ADF_EBADARG,
+                         "a float filtered_disparity_map needs a 4-byte aligned base and strides");
+    };
+    const auto right_map = [&]() -> int {                                  // DF.cpp:262-264
+        if (!conf || !dm.R) return conf ? no_right_map() : ADF_OK;
+        return refuse_if(dm.sR < (ptrdiff_t)(dW * dm.esz()), ADF_ESIZE, "right disparity stride smaller than a row");
+    };
+    const auto radius = [&]() -> int {
+        return conf && (h->disc_radius < 0 || h->disc_radius > max_disc_radius())
+                   ? fail(ADF_EBADARG, "depth discontinuity radius %d outside [0,%d]", h->disc_radius, max_disc_radius()) : ADF_OK;
+    };
+    const auto smoothness = [&] { return refuse_if(h->lambda < 0 || h->sigma_color < 0, ADF_EBADARG, "lambda and sigma_color must be >= 0 (FGS.cpp:143)"); };
+    const auto map_roi = [&] { return resolve_roi(h, roi_in, dW, dH, c.rlo); };
+    const auto view_roi = [&]() -> int {                                   // DF.cpp:225, 241-242, 270-271
+        c.resize_factor = dW / (float)W;
+        const float x_ratio = c.x_ratio = W / (float)dW, y_ratio = H / (float)dH;
+        c.rhi = adf_rect{(int)(c.rlo.x * x_ratio), (int)(c.rlo.y * y_ratio), (int)(c.rlo.width * x_ratio), (int)(c.rlo.height * y_ratio)};
+        if (c.rhi.width > 0 && c.rhi.height > 0 && c.rhi.x + c.rhi.width <= W && c.rhi.y + c.rhi.height <= H) return ADF_OK;
+        return fail(ADF_ESIZE, "scaled ROI (%d,%d,%d,%d) does not fit the %dx%d view", c.rhi.x, c.rhi.y, c.rhi.width, c.rhi.height, W, H);
+    };
+    int rc = check_float_maps(dm, n_pairs, dW, dH, om, W, H);
+    if (rc || (rc = maps())) return rc;
+    if (!c.scaled) {
+        if ((rc = guide()) || (rc = filtered()) || (rc = pairs()) || (rc = map_rows()) || (rc = view_rows()) || (rc = float_out()) ||
+            (rc = right_map()) || (rc = smoothness()) || (rc = map_roi()) || (rc = radius())) return rc;
+        c.rhi = c.rlo;                                                     // DF.cpp:224-227: resize_factor 1
+        return ADF_OK;
+    }
+    if ((rc = pairs()) || (rc = map_rows()) || (rc = right_map()) || (rc = radius()) || (rc = map_roi()) || (rc = view_roi()) ||
+        (rc = guide()) || (rc = filtered()) || (rc = view_rows()) || (rc = float_out()) || (rc = smoothness())) return rc;
     return ADF_OK;
 }
 
@@ -388,50 +518,76 @@ static WavePassArgs first_pass_probe(const FusedInputs& f, int len)
     return a;
 }
 
-// Fused first row pass at view resolution: U1 = conf, U0 = conf*float(dL) read from the confidence planes and the left
-// disparity maps of the pairs from `conf` / `dl` on (DF.cpp:288-290).
-static FusedInputs view_fuse(const float* conf, const void* dl, ptrdiff_t sL, ptrdiff_t psL, bool f32, const Geom& g)
+// What the kernels of a range of pairs read of the disparity maps.  caller_maps() starts one; quantise_maps() and the
+// down-scaled path's buffers re-point it.
+struct MapSource {
+    // the confidence kernels' int16 maps: the caller's, or the planes q of float maps (null: float maps not quantised)
+    const int16_t* L; ptrdiff_t sL, psL;
+    const int16_t* R; ptrdiff_t sR, psR;
+    // what the right-hand sides are formed from: the caller's left maps (a float one: DEPTH_WLS_F32) or the down-scaled
+    // path's resized ones (a float one is taken as it is: ADF_32F); null where the first row pass interpolates the
+    // low-resolution maps itself
+    const void* rhs; ptrdiff_t s_rhs, ps_rhs; int rhs_depth;
+    // down-scaled path, float maps: the left map's v plane -- resized in float, no rounding
+    const float* v; ptrdiff_t sv, psv;
+    bool rhs_f32() const { return rhs_depth != ADF_16S; }
+    MapSource from(int k) const                                            // the same for the pairs from k on
+    {
+        MapSource m = *this;
+        m.L = pairs_on(L, psL, k); m.R = pairs_on(R, psR, k); m.rhs = pairs_on(rhs, ps_rhs, k); m.v = pairs_on(v, psv, k);
+        return m;
+    }
+};
+
+static MapSource caller_maps(const DispMaps& dm)
+{
+    MapSource m{};
+    if (!dm.f32) { m.L = (const int16_t*)dm.L; m.sL = dm.sL; m.psL = dm.psL; m.R = (const int16_t*)dm.R; m.sR = dm.sR; m.psR = dm.psR; }
+    m.rhs = dm.L; m.s_rhs = dm.sL; m.ps_rhs = dm.psL; m.rhs_depth = dm.f32 ? DEPTH_WLS_F32 : ADF_16S;
+    return m;
+}
+
+// Float maps: what the confidence kernels read is made by one launch (design (a)) -- the int16 planes q of the `n` pairs
+// of `dm` at qL / qR (null: none) and the left map's v as a float plane at v (null: none).  `m` reads them from then on.
+static int quantise_maps(Profiler* prof, const DispMaps& dm, int W, int H, int n, int16_t* qL, int16_t* qR, float* v,
+                         hipStream_t st, MapSource& m)
+{
+    const int pitch = quant_pitch(W);
+    const size_t frame = (size_t)pitch * H;                                // elements per plane
+    QuantArgs qa{{dm.L, qR ? dm.R : nullptr}, {dm.sL, dm.sR}, {dm.psL, dm.psR}, {qL, qR}, v, W, H, pitch, frame, n};
+    {
+        ProfScope ps(prof, K_QUANT, quant_bytes((double)W * H * n, qL != nullptr, qR != nullptr, v != nullptr), st);
+        HIP_TRY(launch_quantise_maps(qa, st));
+    }
+    m.L = qL; m.R = qR; m.sL = m.sR = (ptrdiff_t)pitch * 2; m.psL = m.psR = (ptrdiff_t)frame * 2;
+    m.v = v; m.sv = (ptrdiff_t)pitch * 4; m.psv = (ptrdiff_t)frame * 4;
+    return ADF_OK;
+}
+
+// Fused first row pass at view resolution: U1 = conf, U0 = conf*float(dL) read from the confidence planes from `conf`
+// on and the maps the right-hand sides come from (DF.cpp:288-290).
+static FusedInputs view_fuse(const float* conf, const MapSource& m, const Geom& g)
 {
     FusedInputs f{};
-    f.dl_f32 = f32 ? 1 : 0;
+    f.dl_f32 = m.rhs_f32() ? 1 : 0;
     f.conf_in = conf; f.conf_frame = g.cframe; f.conf_pitch = g.cpitch; f.conf_x0 = g.cx0 + g.rx; f.conf_y0 = g.ry;
-    f.dl_in = dl; f.dl_stride = sL; f.dl_pair_stride = psL; f.dl_x0 = g.rx; f.dl_y0 = g.ry;
+    f.dl_in = m.rhs; f.dl_stride = m.s_rhs; f.dl_pair_stride = m.ps_rhs; f.dl_x0 = g.rx; f.dl_y0 = g.ry;
     return f;
 }
 
-// The down-scaled path's own work (DF.cpp:239-247, 268-277) for ALL pairs of a call.  adf_wls_filter_scaled_device
-// decides and allocates it; wls_filter_impl queues it on the caller's stream where a same-size call runs its confidence
-// kernels -- beside the weight kernel, which it has forked to the side stream by then and which needs the view only.
-// Measured at 64 x 4K views / 1080p maps: everything after the fork 13.8-14.1 / 13.8-14.0 ms per call (radius 2 / 5; the
-// band kernel crawls beside the weight kernel's small workgroups, 0.44 -> 0.9-1.7 ms, but the resizes then run alone),
-// the low-resolution confidence map before the fork 14.20 / 14.51 (two memory-bound kernels side by side gain nothing),
-// no overlap at all 14.49 / 14.69.
-struct ScaledStage {
-    const int16_t* dispL; ptrdiff_t sL, psL;   // the caller's low-resolution maps (float maps: their int16 planes q)
-    const int16_t* dispR; ptrdiff_t sR, psR;
-    const float* vL; ptrdiff_t svL, psvL;      // float maps: the left map's v plane -- resized in float, no rounding
-    float resize_factor, x_ratio;              // DF.cpp:225, 241
-    char* dhi; size_t dhi_bytes;               // the resized left maps (not with fuse_lo)
-    float *cl, *cr;                            // low-resolution discontinuity maps
-    ConfResize lo;                             // low-resolution confidence maps, both geometries, pair count
-    bool fuse_lo;                              // the first row pass interpolates the low-resolution maps itself ...
-    float* taps;                               // ... with this scratch for the columns' source coordinates
-};
-
-// Fused first row pass in its low-resolution form, for the pairs from `first` on (DF.cpp:272-274 then 288-290).
-static FusedInputs lo_fuse(const adf_wls* h, const ScaledStage& s, int first, const Geom& g)
+// ... and in its low-resolution form (DF.cpp:272-274 then 288-290): the pass interpolates the low-resolution confidence
+// maps from `clo` on (made by the band kernel: zero outside the ROI) and the int16 maps of `m`; g: the view's geometry.
+static FusedInputs lo_fuse(const adf_wls* h, const WlsCall& c, bool band_map, const float* clo, const MapSource& m, float* taps, const Geom& g)
 {
-    const ConfResize& c = s.lo;
-    const size_t lo = (size_t)c.dW * c.dH;
     FusedInputs f{};
-    f.lo_conf = c.clo + (size_t)first * lo; f.lo_conf_stride = c.dW; f.lo_conf_pair = (ptrdiff_t)lo;
-    f.lo_dl = (const int16_t*)((const char*)s.dispL + (ptrdiff_t)first * s.psL); f.lo_dl_stride = s.sL; f.lo_dl_pair = s.psL;
+    f.lo_conf = clo; f.lo_conf_stride = c.dW; f.lo_conf_pair = (ptrdiff_t)((size_t)c.dW * c.dH);
+    f.lo_dl = m.L; f.lo_dl_stride = m.sL; f.lo_dl_pair = m.psL;
     f.lo_w = c.dW; f.lo_h = c.dH; f.hi_x0 = g.rx; f.hi_y0 = g.ry;
-    f.lo_scale_x = (double)c.dW / c.ghi.W; f.lo_scale_y = (double)c.dH / c.ghi.H; f.lo_post_scale = s.x_ratio;
-    if (c.band_map) {
+    f.lo_scale_x = (double)c.dW / g.W; f.lo_scale_y = (double)c.dH / g.H; f.lo_post_scale = c.x_ratio;
+    if (band_map) {
         f.lo_zero_outside = 1; f.lo_vx0 = c.rlo.x; f.lo_vy0 = c.rlo.y; f.lo_vx1 = c.rlo.x + c.rlo.width; f.lo_vy1 = c.rlo.y + c.rlo.height;
     }
-    f.lo_taps = s.taps; f.lo_half = h->scaled_half ? 1 : 0;
+    f.lo_taps = taps; f.lo_half = h->scaled_half ? 1 : 0;
     return f;
 }
 
@@ -440,73 +596,116 @@ static int resize_conf_planes(adf_wls_t* h, const ConfResize& c, hipStream_t st,
 {
     const size_t lo = (size_t)c.dW * c.dH;
     const Geom& ghi = c.ghi;
-    const double Fhi = (double)ghi.W * ghi.H * c.n_pairs;
     ResizeArgs rc32{c.clo, (ptrdiff_t)c.dW * 4, (ptrdiff_t)(lo * 4), c.dW, c.dH, (float*)h->conf.p + ghi.cx0, (ptrdiff_t)ghi.cpitch * 4,
                     (ptrdiff_t)(ghi.cframe * 4), ghi.W, ghi.H, (double)c.dW / ghi.W, (double)c.dH / ghi.H, 1.0f, 0};
     if (c.band_map) { rc32.zero_outside = 1; rc32.vx0 = c.rlo.x; rc32.vy0 = c.rlo.y; rc32.vx1 = c.rlo.x + c.rlo.width; rc32.vy1 = c.rlo.y + c.rlo.height; }
-    ProfScope ps(prof, K_RESIZE, 4.0 * Fhi + 4.0 * (double)lo * c.n_pairs, 4.0 * Fhi + 4.0 * (double)lo * c.n_pairs, st);
+    ProfScope ps(prof, K_RESIZE, resize_bytes((double)ghi.W * ghi.H * c.n_pairs, (double)lo * c.n_pairs, 4.0), st);
     HIP_TRY(launch_resize_linear(rc32, c.n_pairs, st));
     return ADF_OK;
 }
 
-// The low-resolution confidence maps of all pairs (DF.cpp:197-210 at the maps' resolution, DF.cpp:318, 359).
-static int scaled_conf_map(adf_wls_t* h, const ScaledStage& s, hipStream_t st, Profiler* prof)
+// cv::resize of the low-resolution left maps of all pairs to the view, times x_ratio (DF.cpp:243-244, 272-273), into
+// `dhi`, where lo.rhs reads them: the int16 maps saturated; float maps' v through the float taps the confidence map
+// goes through, nothing rounded.
+static int resize_disparity(Profiler* prof, const WlsCall& c, const MapSource& lo, void* dhi, hipStream_t st)
 {
-    const ConfResize& c = s.lo;
-    const Geom glo = plain_conf_layout(make_geom(c.dW, c.dH, c.rlo.x, c.rlo.y, c.rlo.width, c.rlo.height));
-    const size_t lo = (size_t)c.dW * c.dH;
-    const double Plo = (double)c.rlo.width * c.rlo.height * c.n_pairs;
-    const int rrx = c.dW - (c.rlo.x + c.rlo.width);                       // DF.cpp:202
-    const float roll_off = h->roll_off / (s.resize_factor * s.resize_factor);   // DF.cpp:359
-    const int thresh_lo = (int)(s.resize_factor * h->lrc_thresh);       // DF.cpp:318
-    if (c.band_map) {
-        // the one-sweep kernel at the maps' resolution: ROI pixels from the band kernel, zeros outside (DF.cpp:187-190)
-        ConfBandArgs ba{s.dispL, s.sL, s.psL, s.dispR, s.sR, s.psR, c.clo, glo, rrx, thresh_lo, h->disc_radius, roll_off, 0};
-        ProfScope ps(prof, K_LRC, 8.0 * Plo, 8.0 * Plo, st);
-        HIP_TRY(launch_conf_band(ba, c.n_pairs, st));                    // DF.cpp:197-210
-        return ADF_OK;
-    }
-    DiscArgs da{{s.dispL, s.dispR}, {s.sL, s.sR}, {s.psL, s.psR}, {c.rlo.x, rrx}, c.rlo.y, c.rlo.width, c.rlo.height,
-                h->disc_radius, roll_off, {s.cl, s.cr}, c.dW, lo, -1};
-    {
-        ProfScope ps(prof, K_DISC, 4.0 * Plo, 12.0 * Plo, st);
-        HIP_TRY(launch_discontinuity(da, c.n_pairs, st));                // DF.cpp:204
-    }
-    LrcArgs la{s.dispL, s.sL, s.psL, s.dispR, s.sR, s.psR, s.cl, s.cr, c.clo, nullptr, 0, 0, 0, 0, nullptr, nullptr, glo, rrx, thresh_lo, ORIENT_N};
-    ProfScope ps(prof, K_LRC, 4.0 * (double)lo * c.n_pairs, 4.0 * (double)lo * c.n_pairs + 12.0 * Plo, st);
-    HIP_TRY(launch_lrc_prologue(la, c.n_pairs, st));                     // DF.cpp:208-209
+    const int W = c.view.W, H = c.view.H;
+    const double sx = (double)c.dW / W, sy = (double)c.dH / H;
+    const ResizeArgs ra = lo.v ? ResizeArgs{lo.v, lo.sv, lo.psv, c.dW, c.dH, dhi, lo.s_rhs, lo.ps_rhs, W, H, sx, sy, c.x_ratio, 0}
+                               : ResizeArgs{lo.L, lo.sL, lo.psL, c.dW, c.dH, dhi, lo.s_rhs, lo.ps_rhs, W, H, sx, sy, c.x_ratio, 1};
+    ProfScope ps(prof, K_RESIZE, resize_bytes((double)W * H * c.n_pairs, (double)c.dW * c.dH * c.n_pairs, lo.v ? 4.0 : 2.0), st);
+    HIP_TRY(launch_resize_linear(ra, c.n_pairs, st));
     return ADF_OK;
 }
 
-// The resizes to the view: the confidence maps (DF.cpp:274) and the left disparity maps (DF.cpp:243-244, 272-273).
-static int scaled_resize(adf_wls_t* h, const ScaledStage& s, hipStream_t st, Profiler* prof)
-{
-    const ConfResize& c = s.lo;
-    int rc = h->use_confidence ? resize_conf_planes(h, c, st, prof) : ADF_OK;
-    if (rc) return rc;
-    const int W = c.ghi.W, H = c.ghi.H;
-    const size_t lo = (size_t)c.dW * c.dH;
-    const double Fhi = (double)W * H * c.n_pairs;
-    // float maps: v through the float taps the confidence map goes through, times x_ratio once, nothing rounded
-    const double eb = s.vL ? 4.0 : 2.0;
-    ResizeArgs r16{s.dispL, s.sL, s.psL, c.dW, c.dH, s.dhi, (ptrdiff_t)W * 2, (ptrdiff_t)s.dhi_bytes, W, H, (double)c.dW / W, (double)c.dH / H, s.x_ratio, 1};
-    ResizeArgs r32{s.vL, s.svL, s.psvL, c.dW, c.dH, s.dhi, (ptrdiff_t)W * 4, (ptrdiff_t)s.dhi_bytes, W, H, (double)c.dW / W, (double)c.dH / H, s.x_ratio, 0};
-    ProfScope ps(prof, K_RESIZE, eb * Fhi + eb * (double)lo * c.n_pairs, eb * Fhi + eb * (double)lo * c.n_pairs, st);
-    HIP_TRY(launch_resize_linear(s.vL ? r32 : r16, c.n_pairs, st));
-    return ADF_OK;
-}
-
-// How a WLS filter call makes the two right-hand sides conf*disp and conf (DF.cpp:286-290), or float(disp) without
-// confidence (DF.cpp:257).
+// How a WLS filter call makes its confidence map (DF.cpp:197-210), or none (DF.cpp:257).
 enum ConfStage {
-    CONF_NONE,        // no confidence: the plain prologue
-    CONF_SCALED,      // down-scaled: low-resolution confidence map, both resizes, then the prologue or the fused first pass
+    CONF_NONE,        // no confidence
+    CONF_SCALED,      // down-scaled: low-resolution confidence map, then both resizes
     CONF_SCALED_LO,   // down-scaled: low-resolution confidence map; the first row pass interpolates it and the disparity map
     CONF_MERGED,      // weights + one-sweep confidence map + fill outside the ROI in one launch (small calls)
     CONF_BAND,        // both views' maps, LRC and x255 in one band sweep: the right view's map lives in LDS only
     CONF_LEFT,        // the right view's map, then the left one + LRC + x255 in one sweep (cL never hits memory)
-    CONF_TWO_KERNEL,  // both views' maps, then LRC + x255 + the right-hand sides (and the fill outside the ROI)
+    CONF_TWO_KERNEL,  // both views' maps, then LRC + x255 (+ the right-hand sides and the fill outside the ROI)
 };
+
+// Where the first row pass finds the two right-hand sides conf*disp and conf (DF.cpp:286-290), or float(disp) without
+// confidence (DF.cpp:257).
+enum RhsSource {
+    RHS_PLAIN,          // the plain prologue writes float(disp) (FGS.cpp:203-205)
+    RHS_FUSED_VIEW,     // the pass forms them itself from the view-sized confidence planes and maps (no prologue planes)
+    RHS_FUSED_LO,       // ... from the low-resolution ones, which it interpolates
+    RHS_CONF_PROLOGUE,  // the confidence-weighted prologue: the down-scaled path's, and float maps' behind the left-view kernel
+    RHS_CONF_KERNEL,    // the left-view or the LRC kernel writes them with the confidence map
+};
+
+// The numbers the confidence kernels take besides maps and geometry, for maps `resize_factor` times the view's size.
+struct ConfRule { int rrx, thresh, radius; float roll_off; };
+static ConfRule conf_rule(const adf_wls* h, const WlsCall& c)
+{
+    return ConfRule{c.dW - (c.rlo.x + c.rlo.width),                                        // DF.cpp:202
+                    (int)(c.resize_factor * h->lrc_thresh),                               // DF.cpp:318
+                    h->disc_radius, h->roll_off / (c.resize_factor * c.resize_factor)};   // DF.cpp:359
+}
+
+// What a confidence stage writes.
+struct ConfOut {
+    float* conf;                        // the confidence planes (x255), in the layout of the stage's Geom
+    float* cL; float* cR;               // full-frame discontinuity maps (not the band kernel)
+    float* U0; float* U1; int orient;   // the right-hand sides (null: not this stage's; the band kernel never)
+    const OutsideArgs* fill;            // two-kernel: its LRC kernel also fills the filtered map outside the ROI (DF.cpp:284)
+};
+
+static ConfBandArgs conf_band_args(const MapSource& m, float* conf, const Geom& g, const ConfRule& r)
+{
+    return ConfBandArgs{m.L, m.sL, m.psL, m.R, m.sR, m.psR, conf, g, r.rrx, r.thresh, r.radius, r.roll_off, 0};
+}
+
+static DiscArgs disc_args(const MapSource& m, const ConfOut& o, const Geom& g, const ConfRule& r, int only_view)
+{
+    return DiscArgs{{m.L, m.R}, {m.sL, m.sR}, {m.psL, m.psR}, {g.rx, r.rrx}, g.ry, g.rw, g.rh, r.radius, r.roll_off,
+                    {o.cL, o.cR}, g.W, g.frame, only_view};
+}
+
+static LrcArgs lrc_args(const MapSource& m, const ConfOut& o, const Geom& g, const ConfRule& r)
+{
+    // right-hand sides of float maps: the kernel reads its own pixel from the caller's left map (v, and q on the fly),
+    // the gather from the right map's plane q
+    const bool own_f32 = o.U0 && m.rhs_f32();
+    LrcArgs a = LrcArgs{m.L, m.sL, m.psL, m.R, m.sR, m.psR, o.cL, o.cR, o.conf, nullptr, 0, 0, 0, 0, o.U0, o.U1,
+                        g, r.rrx, r.thresh, o.orient, own_f32 ? 1 : 0};
+    if (own_f32) { a.dL = (const int16_t*)m.rhs; a.sL = m.s_rhs; a.psL = m.ps_rhs; }
+    if (o.fill) { a.out = o.fill->out; a.sO = o.fill->stride; a.psO = o.fill->pair_stride; a.fill = o.fill->fill; a.out_f32 = o.fill->out_f32; }
+    return a;
+}
+
+// Queues the confidence map of `n` pairs from the int16 maps of `m` at geometry `g` (DF.cpp:197-210): the band, the
+// left-view or the two-kernel stage.  The view-resolution chunk and the down-scaled path's low-resolution map both come
+// here.
+static int conf_stage(Profiler* prof, ConfStage kind, const MapSource& m, const Geom& g, const ConfRule& r, const ConfOut& o,
+                      int n, hipStream_t st)
+{
+    const double F = (double)g.frame * n, P = (double)g.rw * g.rh * n;
+    if (kind == CONF_BAND) {
+        ProfScope ps(prof, K_LRC, band_bytes(P), st);
+        HIP_TRY(launch_conf_band(conf_band_args(m, o.conf, g, r), n, st));
+        return ADF_OK;
+    }
+    {
+        ProfScope ps(prof, K_DISC, disc_bytes(P, kind != CONF_LEFT), st);
+        HIP_TRY(launch_discontinuity(disc_args(m, o, g, r, kind == CONF_LEFT ? 1 : -1), n, st));   // DF.cpp:204 (left: the right view)
+    }
+    if (kind == CONF_LEFT) {
+        ConfLeftArgs ca{m.L, m.sL, m.psL, m.R, m.sR, m.psR, o.cR, o.conf, o.U0, o.U1, g, r.rrx, r.thresh, r.radius, r.roll_off};
+        ProfScope ps(prof, K_LRC, conf_left_bytes(P, o.U0 != nullptr), st);
+        HIP_TRY(launch_conf_left(ca, n, st));                              // DF.cpp:204-209 (+288-290)
+        return ADF_OK;
+    }
+    const double fill = o.fill ? fill_bytes(F - P, false, o.fill->out_f32 ? 4.0 : 2.0).alg : 0.0;
+    ProfScope ps(prof, K_LRC, lrc_bytes(F, P, o.U0 != nullptr, m.rhs_f32() ? 4.0 : 2.0, fill), st);
+    HIP_TRY(launch_lrc_prologue(lrc_args(m, o, g, r), n, st));             // DF.cpp:208-209 (+288-290)
+    return ADF_OK;
+}
 
 // What one chunk of pairs queues.
 struct ChunkPlan {
@@ -516,17 +715,23 @@ struct ChunkPlan {
     bool guide_rows;       // the row passes form their weights from the guide: the weight kernel writes Cvert only
 };
 
-// What a WLS filter call queues, decided before its chunk loop.
+// What a WLS filter call queues, decided from its record before anything is allocated or queued.
 struct WlsPlan {
+    Geom g;                   // the view's geometry
     bool wave;                // the wave solver (else the exact one)
-    bool fused_first;         // the first row pass forms its right-hand sides itself (no prologue planes)
+    RhsSource rhs;
     bool band;                // the one-sweep confidence kernel: no full-frame discontinuity maps in the workspace
+    bool quant_planes;        // float maps of the view's size, confidence mode: the workspace holds a chunk's planes q
+    // down-scaled: the maps' geometry (plain confidence layout); the band kernel makes the low-resolution confidence
+    // maps (zero outside the ROI, DF.cpp:187-190); bytes per pair of the resized left maps (none with RHS_FUSED_LO)
+    Geom glo; bool lo_band; size_t dhi_bytes;
     size_t per_pair; int chunk;
     // chunks of `chunk` pairs, and a shorter last one: the merged launch is for small calls, so it depends on the
     // chunk's pair count
     ChunkPlan full, tail;
     int path;                 // ADF_PATH_* bits of the preparation stage
     int solver_path;          // ... of the solve passes
+    bool fused_first() const { return rhs == RHS_FUSED_VIEW || rhs == RHS_FUSED_LO; }
 };
 
 static ChunkPlan plan_chunk(const adf_wls* h, ConfStage stage, bool wave, bool guide_rows)
@@ -546,128 +751,163 @@ static ChunkPlan plan_chunk(const adf_wls* h, ConfStage stage, bool wave, bool g
 }
 
 // The row passes' weights straight from the guide of the pairs from `guide` on (fgs_wave_h.hip, WS_GUIDE*).
-static GuideWeights guide_weights(const adf_wls* h, const uint8_t* guide, ptrdiff_t sG, ptrdiff_t psG, int gch, const Geom& g)
+static GuideWeights guide_weights(const adf_wls* h, const uint8_t* guide, const View& v, const Geom& g)
 {
-    return GuideWeights{guide, sG, psG, gch, g.rx, g.ry, h->lut.cur};
+    return GuideWeights{guide, v.stride, v.pair_stride, v.ch, g.rx, g.ry, h->lut.cur};
 }
 
-static WlsPlan plan_wls(const adf_wls* h, const Geom& g, int n_pairs, const void* dispL, ptrdiff_t sL, ptrdiff_t psL, bool f32in,
-                        const uint8_t* view, ptrdiff_t sG, ptrdiff_t psG, int gch, const ScaledStage* scaled)
+static WlsPlan plan_wls(const adf_wls* h, const WlsCall& c)
 {
     WlsPlan p{};
-    const bool conf = h->use_confidence;
+    const bool conf = h->use_confidence, f32in = c.dm.f32;
+    const View& v = c.view;
+    const Geom g = p.g = make_geom(v.W, v.H, c.rhi.x, c.rhi.y, c.rhi.width, c.rhi.height);
     // sizes outside the register-resident kernels' range fall back to the exact solver
     p.wave = h->solver == ADF_SOLVER_WAVE && wave_fits(g);
+    // what the right-hand sides would be read from: the caller's maps or, down-scaled, the resized ones (not allocated yet)
+    MapSource m = caller_maps(c.dm);
+    bool fuse_lo = false;
+    if (c.scaled) {
+        p.glo = plain_conf_layout(make_geom(c.dW, c.dH, c.rlo.x, c.rlo.y, c.rlo.width, c.rlo.height));
+        p.lo_band = conf && h->conf_band && conf_band_fits(p.glo, h->disc_radius);
+        // Can the first row pass interpolate the maps itself (fgs_wave_h.hip, FUSE_LO)?  Confidence mode on the wave
+        // solver, scale factors within the staging buffer's reach.  Then neither the resized disparity map nor -- until
+        // getConfidenceMap() asks for it -- the resized confidence map is ever written.
+        // (float maps take the resize kernels: the fused low-resolution prologue has no float form)
+        fuse_lo = conf && !f32in && h->scaled_fuse && p.wave &&
+                  wave_hpass_can_fuse_lo(first_pass_probe(lo_fuse(h, c, p.lo_band, UNALLOCATED, m, nullptr, g), g.rw));
+        p.dhi_bytes = fuse_lo ? 0 : pad_to((size_t)v.W * v.H * c.dm.esz(), 256);
+        m.rhs = fuse_lo ? nullptr : UNALLOCATED; m.s_rhs = (ptrdiff_t)(v.W * c.dm.esz()); m.ps_rhs = (ptrdiff_t)p.dhi_bytes;
+        m.rhs_depth = f32in ? ADF_32F : ADF_16S;
+    }
     ConfStage stage = !conf ? CONF_NONE
-                    : scaled ? (scaled->fuse_lo ? CONF_SCALED_LO : CONF_SCALED)
+                    : c.scaled ? (fuse_lo ? CONF_SCALED_LO : CONF_SCALED)
                     : (p.wave && h->disc_radius <= conf_left_max_radius()) ? CONF_LEFT : CONF_TWO_KERNEL;
     // The view-resolution form of the fused first pass has alignment conditions that depend only on the geometry, the
     // strides and the pointers known here, not on the chunk.
     const float* planes = h->conf.p ? (const float*)h->conf.p : UNALLOCATED;
-    p.fused_first = stage == CONF_SCALED_LO ||
-                    (((stage == CONF_SCALED && !f32in) || stage == CONF_LEFT) && p.wave &&   // (a resized float map is not clamped again: prologue)
-                     wave_hpass_can_fuse(first_pass_probe(view_fuse(planes, dispL, sL, psL, f32in, g), g.rw)));
+    const bool fused_view = ((stage == CONF_SCALED && !f32in) || stage == CONF_LEFT) && p.wave &&   // (a resized float map is not clamped again: prologue)
+                            wave_hpass_can_fuse(first_pass_probe(view_fuse(planes, m, g), g.rw));
     // the band kernel writes no right-hand sides: it needs the fused first pass
-    p.band = stage == CONF_LEFT && p.fused_first && h->conf_band && conf_band_fits(g, h->disc_radius);
+    p.band = stage == CONF_LEFT && fused_view && h->conf_band && conf_band_fits(g, h->disc_radius);
     if (p.band) stage = CONF_BAND;
-    p.per_pair = wls_pair_ws_bytes(g, conf, p.wave, !p.band, f32in && conf && !scaled);
+    p.quant_planes = f32in && conf && !c.scaled;
+    p.rhs = stage == CONF_NONE ? RHS_PLAIN : stage == CONF_SCALED_LO ? RHS_FUSED_LO : fused_view ? RHS_FUSED_VIEW
+          : (stage == CONF_SCALED || (stage == CONF_LEFT && p.quant_planes)) ? RHS_CONF_PROLOGUE : RHS_CONF_KERNEL;
+    p.per_pair = wls_pair_ws_bytes(g, conf, p.wave, !p.band, p.quant_planes);
     p.chunk = (int)(h->ws_limit / p.per_pair);
     if (p.chunk < 1) p.chunk = 1;
-    if (p.chunk > n_pairs) p.chunk = n_pairs;
+    if (p.chunk > c.n_pairs) p.chunk = c.n_pairs;
     // The guide is new on every call, so the Chor plane of a full-resolution call on the wave solver is written once and
     // read num_iter times for nothing the guide row does not say in fewer bytes: the row passes take the guide instead
     // where their bucket has that form and the streaming weight kernel (the one with a Cvert-only form) runs.
     bool guide_rows = false;
-    if (p.wave && !scaled && h->row_weights_guide) {
+    if (p.wave && !c.scaled && h->row_weights_guide) {
         WavePassArgs probe{};
-        probe.len = g.rw; probe.gw = guide_weights(h, view, sG, psG, gch, g);
+        probe.len = g.rw; probe.gw = guide_weights(h, v.p, v, g);
         WeightArgs wprobe{};
-        wprobe.stride = sG; wprobe.ch = gch; wprobe.chor_orient = ORIENT_N; wprobe.g = g;
+        wprobe.stride = v.stride; wprobe.ch = v.ch; wprobe.chor_orient = ORIENT_N; wprobe.g = g;
         guide_rows = wave_hpass_guide_fits(probe) && weights_stream_fits(wprobe);
     }
     auto chunk_of = [&](int n) {
-        const bool merged = p.band && h->merge_small && prep_small_fits(g, h->disc_radius, gch, n) && prep_small_guide_fits(g, sG, gch);
+        const bool merged = p.band && h->merge_small && prep_small_fits(g, h->disc_radius, v.ch, n) && prep_small_guide_fits(g, v.stride, v.ch);
         return plan_chunk(h, merged ? CONF_MERGED : stage, p.wave, guide_rows);
     };
     p.full = chunk_of(p.chunk);
-    p.tail = chunk_of(n_pairs % p.chunk ? n_pairs % p.chunk : p.chunk);
-    p.path = ((p.band || (scaled && scaled->lo.band_map)) ? ADF_PATH_CONF_BAND : 0) |
-             (p.fused_first ? ADF_PATH_FUSED_FIRST_PASS : 0) |
+    p.tail = chunk_of(c.n_pairs % p.chunk ? c.n_pairs % p.chunk : p.chunk);
+    p.path = ((p.band || p.lo_band) ? ADF_PATH_CONF_BAND : 0) |
+             (p.fused_first() ? ADF_PATH_FUSED_FIRST_PASS : 0) |
              ((p.full.stage == CONF_MERGED || p.tail.stage == CONF_MERGED) ? ADF_PATH_MERGED_PREP : 0);
     p.solver_path = (p.full.guide_rows || p.tail.guide_rows) ? ADF_PATH_ROW_WEIGHTS_GUIDE : 0;
-    if (stage == CONF_SCALED_LO)
+    if (p.rhs == RHS_FUSED_LO)
         p.path |= ADF_PATH_SCALED_FUSED |
-                  (wave_hpass_lo_half(first_pass_probe(lo_fuse(h, *scaled, 0, g), g.rw)) ? ADF_PATH_SCALED_HALF : 0);
+                  (wave_hpass_lo_half(first_pass_probe(lo_fuse(h, c, p.lo_band, UNALLOCATED, m, nullptr, g), g.rw)) ? ADF_PATH_SCALED_HALF : 0);
     return p;
 }
 
-// The filtered map of a call: CV_16SC1 (adf_wls_filter_*) or, with f32, CV_32FC1 holding the float the int16 epilogue
-// rounds (adf_wls_filter_f32_*).  Only the last column pass and the fill outside the ROI know the difference.
-struct OutMap {
-    void* p; ptrdiff_t stride, pair_stride; bool f32;
-    size_t esz() const { return f32 ? sizeof(float) : sizeof(int16_t); }
-};
+// The down-scaled path's own buffers in h->scaled, for ALL pairs of a call: the resized left maps (none with
+// RHS_FUSED_LO) and, in confidence mode, the low-resolution discontinuity and confidence maps; the scratch for the
+// columns' source coordinates of the fused low-resolution first pass; for float maps v and, in confidence mode, qL qR.
+struct ScaledBufs { char* dhi; float *cl, *cr, *clo; float* taps; };
 
-// The disparity maps of a call: CV_16SC1 or, with f32, CV_32FC1 in the same units (adf_wls_filter_typed_*); the right
-// map has the left one's depth.
-struct DispMaps {
-    const void* L; ptrdiff_t sL, psL;
-    const void* R; ptrdiff_t sR, psR;
-    bool f32;
-    size_t esz() const { return f32 ? sizeof(float) : sizeof(int16_t); }
-};
-
-// scaled: the down-scaled path (DF.cpp:274): its stage replaces the confidence kernels, dm.R is not used, and dm.L is
-// the stage's resized map (with fuse_lo only a stand-in that is never dereferenced; float: the resized v, taken as it is).
-static int wls_filter_impl(adf_wls_t* h, int n_pairs, const DispMaps& dm,
-                           const uint8_t* view, ptrdiff_t sG, ptrdiff_t psG, int gch, int W, int H,
-                           const OutMap& om, const adf_rect* roi_in, hipStream_t st, const ScaledStage* scaled = nullptr)
+// Carves them, sizes the view-sized confidence planes and, for float maps, makes q and v: `lo` is what the kernels
+// read of the maps from then on.
+static int scaled_buffers(adf_wls_t* h, const WlsCall& c, const WlsPlan& plan, hipStream_t st, ScaledBufs& b, MapSource& lo)
 {
-    NEED_HANDLE(h);
-    const void* const dispL = dm.L; const void* const dispR = dm.R;
-    const ptrdiff_t sL = dm.sL, psL = dm.psL, sR = dm.sR, psR = dm.psR;
-    const bool f32in = dm.f32;
-    // DF.cpp:221-222
-    if (!dispL || W <= 0 || H <= 0) return fail(ADF_EBADARG, "disparity_map_left is empty");
-    if (!view || (gch != 1 && gch != 3)) return fail(ADF_EBADARG, "left_view must be CV_8UC1 or CV_8UC3");
-    void* const out = om.p;
-    const ptrdiff_t sO = om.stride, psO = om.pair_stride;
-    const double ob_px = (double)om.esz();                                 // output bytes per pixel
-    if (!out) return fail(ADF_EBADARG, "filtered_disparity_map is NULL");
-    if (n_pairs < 1) return fail(ADF_EBADARG, "n_pairs must be >= 1");
-    if (sL < (ptrdiff_t)(W * dm.esz()) || sO < (ptrdiff_t)(W * om.esz()) || sG < (ptrdiff_t)W * gch)
-        return fail(ADF_ESIZE, "row stride smaller than a row");
-    if (om.f32 && ((reinterpret_cast<uintptr_t>(out) | (uintptr_t)sO | (uintptr_t)psO) & 3u))
-        return fail(ADF_EBADARG, "a float filtered_disparity_map needs a 4-byte aligned base and strides");
-    const bool conf = h->use_confidence;
-    int rc;
-    if (conf && !scaled && (rc = check_right_map(dispR, sR, W, dm.esz()))) return rc;
-    if (h->lambda < 0 || h->sigma_color < 0) return fail(ADF_EBADARG, "lambda and sigma_color must be >= 0 (FGS.cpp:143)");
-    adf_rect roi;
-    if ((rc = resolve_roi(h, roi_in, W, H, roi))) return rc;
-    if (conf && (rc = check_radius(h))) return rc;
+    const bool conf = h->use_confidence, f32in = c.dm.f32, fuse_lo = plan.rhs == RHS_FUSED_LO;
+    const size_t n = (size_t)c.n_pairs, lo_px = (size_t)c.dW * c.dH;
+    const size_t qframe = (size_t)quant_pitch(c.dW) * c.dH;
+    const size_t maps_bytes = pad_to(n * (plan.dhi_bytes + (conf ? 3 * lo_px * sizeof(float) : 0)), 256);
+    const size_t taps_bytes = pad_to(fuse_lo ? 2 * ((size_t)c.rhi.width + 4) * sizeof(float) : 0, 256);
+    const size_t quant_bytes = f32in ? n * qframe * (4 + (conf ? 4 : 0)) : 0;   // v (float) + the two planes q (int16), per pair
+    int rc = h->scaled.reserve(maps_bytes + taps_bytes + quant_bytes, st, FILL_ZERO);
+    if (rc) return rc;
+    b.dhi = (char*)h->scaled.p;
+    b.cl = (float*)(b.dhi + n * plan.dhi_bytes);
+    b.cr = b.cl + n * lo_px;
+    b.clo = b.cr + n * lo_px;
+    b.taps = fuse_lo ? (float*)(b.dhi + maps_bytes) : nullptr;
+    if (conf && (rc = ensure_conf_planes(h, plan.g, c.n_pairs, st))) return rc;
+    lo = caller_maps(c.dm);
+    if (f32in) {
+        float* v = (float*)(b.dhi + maps_bytes + taps_bytes);
+        int16_t* qL = conf ? (int16_t*)(v + n * qframe) : nullptr;
+        int16_t* qR = conf ? qL + n * qframe : nullptr;
+        if ((rc = quantise_maps(&h->prof, c.dm, c.dW, c.dH, c.n_pairs, qL, qR, v, st, lo))) return rc;
+    }
+    lo.rhs = fuse_lo ? nullptr : b.dhi; lo.s_rhs = (ptrdiff_t)(c.view.W * c.dm.esz()); lo.ps_rhs = (ptrdiff_t)plan.dhi_bytes;
+    lo.rhs_depth = f32in ? ADF_32F : ADF_16S;                              // (a resized float map is taken as it is)
+    return ADF_OK;
+}
 
-    DeviceScope ds(h->device);
-    const Geom g = make_geom(W, H, roi.x, roi.y, roi.width, roi.height);
-    h->lazy_conf.pending = false;
+// The down-scaled path's confidence maps of ALL pairs (DF.cpp:268-277): the low-resolution map, then the resizes of it
+// and of the left maps to the view -- or neither where the first row pass interpolates both.  wls_filter_impl queues this
+// on the caller's stream where a same-size call runs its confidence kernels -- beside the weight kernel, which it has
+// forked to the side stream by then and which needs the view only.
+// Measured at 64 x 4K views / 1080p maps: everything after the fork 13.8-14.1 / 13.8-14.0 ms per call (radius 2 / 5; the
+// band kernel crawls beside the weight kernel's small workgroups, 0.44 -> 0.9-1.7 ms, but the resizes then run alone),
+// the low-resolution confidence map before the fork 14.20 / 14.51 (two memory-bound kernels side by side gain nothing),
+// no overlap at all 14.49 / 14.69.
+static int scaled_conf_maps(adf_wls_t* h, const WlsCall& c, const WlsPlan& plan, const ScaledBufs& b, const MapSource& lo,
+                            const ConfRule& rule, hipStream_t st)
+{
+    Profiler* prof = &h->prof;
+    int rc = conf_stage(prof, plan.lo_band ? CONF_BAND : CONF_TWO_KERNEL, lo, plan.glo, rule, ConfOut{b.clo, b.cl, b.cr}, c.n_pairs, st);
+    if (rc) return rc;
+    const ConfResize cr{b.clo, c.dW, c.dH, c.rlo, plan.g, plan.lo_band, c.n_pairs};
+    if (plan.rhs != RHS_FUSED_LO)
+        return (rc = resize_conf_planes(h, cr, st, prof)) ? rc : resize_disparity(prof, c, lo, b.dhi, st);
+    // a call captured into a graph is replayed without this host code: the view-sized confidence maps are made
+    // inside the call (the graph), so getConfidenceMap() stays current after replays; otherwise on demand
+    if (stream_is_capturing(st)) return resize_conf_planes(h, cr, st, prof);
+    h->lazy_conf = adf_wls::LazyConf{true, cr};
+    return ADF_OK;
+}
+
+// One accepted call by its plan: the workspace, then per chunk of pairs a fixed sequence -- fork, outside fill and
+// weights, quantise, confidence stage, right-hand sides, join, passes.
+static int wls_filter_impl(adf_wls_t* h, const WlsCall& c, const WlsPlan& plan, hipStream_t st)
+{
+    const bool conf = h->use_confidence, wave = plan.wave;
+    const Geom& g = plan.g;
+    const View& vw = c.view;
+    const OutMap& om = c.om;
+    const adf_rect& roi = c.rhi;
+    const int n_pairs = c.n_pairs, W = vw.W, H = vw.H, gch = vw.ch;
+    const double ob_px = (double)om.esz(), db_px = (double)c.dm.esz();     // bytes per pixel of the filtered map, of the maps
+    Profiler* prof = &h->prof;
+    int rc;
+    ScaledBufs sb{};
+    MapSource lo{};
+    if (c.scaled && (rc = scaled_buffers(h, c, plan, st, sb, lo))) return rc;
     h->roi = roi; h->last_W = W; h->last_H = H; h->last_pairs = n_pairs;
     h->last_cpitch = g.cpitch; h->last_cx0 = g.cx0; h->last_path = 0; h->last_solver_path = 0;
-
-    if ((rc = h->lut.ensure((float)h->sigma_color, st))) return rc;
-    const WlsPlan plan = plan_wls(h, g, n_pairs, dispL, sL, psL, f32in, view, sG, psG, gch, scaled);
-    // float maps: the confidence kernels read int16 planes q of the chunk's maps, made by one launch (design (a))
-    const bool quant = f32in && conf && !scaled;
-    const int qpitch = quant_pitch(W);
-    const size_t qframe = (size_t)qpitch * H;                              // elements per plane
-    // the right-hand sides' source depth: a resized float map (scaled) is taken as it is
-    const int rhs_depth = !f32in ? ADF_16S : scaled ? ADF_32F : DEPTH_WLS_F32;
-    const double db_px = (double)dm.esz();                                 // map bytes per pixel
-    const bool wave = plan.wave;
     h->last_solver = wave ? ADF_SOLVER_WAVE : ADF_SOLVER_EXACT;
     if ((rc = h->ws.reserve(plan.per_pair * (size_t)plan.chunk, st, FILL_ZERO))) return rc;
-    if (conf && !scaled && (rc = ensure_conf_planes(h, g, n_pairs, st))) return rc;
+    if (conf && !c.scaled && (rc = ensure_conf_planes(h, g, n_pairs, st))) return rc;
     {
-        const long long sig[8] = {W, H, roi.x, roi.y, roi.width, roi.height, (long long)quant * 8 + (long long)plan.band * 4 + (long long)wave * 2 + conf, plan.chunk};
+        const long long sig[8] = {W, H, roi.x, roi.y, roi.width, roi.height,
+                                  (long long)plan.quant_planes * 8 + (long long)plan.band * 4 + (long long)wave * 2 + conf, plan.chunk};
         if (memcmp(sig, h->ws_sig, sizeof(sig)) != 0) {
             HIP_TRY(hipMemsetAsync(h->ws.p, 0, h->ws.bytes, st));
             memcpy(h->ws_sig, sig, sizeof(sig));
@@ -684,9 +924,11 @@ static int wls_filter_impl(adf_wls_t* h, int n_pairs, const DispMaps& dm,
         p.A1 = take(g.plane);                     // wave: directly behind A0 (the pair plane spans both)
         if (!wave) { p.F1 = take(g.plane); p.B1 = take(g.plane); }
     }
-    // (before the full-frame maps: everything in front is a multiple of 256 bytes, so the planes' rows are 16-byte aligned)
-    int16_t* const qL = quant ? (int16_t*)take(qframe) : nullptr;          // 2 * qframe int16 = qframe floats per pair
-    int16_t* const qR = quant ? qL + qframe * (size_t)plan.chunk : nullptr;
+    // float maps: the planes q of a chunk (before the full-frame maps: everything in front is a multiple of 256 bytes, so
+    // the planes' rows are 16-byte aligned); 2 * qframe int16 = qframe floats per pair
+    const size_t qframe = (size_t)quant_pitch(W) * H;
+    int16_t* const qL = plan.quant_planes ? (int16_t*)take(qframe) : nullptr;
+    int16_t* const qR = qL ? qL + qframe * (size_t)plan.chunk : nullptr;
     if (conf && !plan.band) { cL = take(g.frame); cR = take(g.frame); }
     // exact: the horizontal pass wants the row index fastest (T); wave: row-major (N), except that two
     // right-hand sides share one interleaved pair plane (A0 and A1 are adjacent: 2*plane floats per
@@ -695,45 +937,36 @@ static int wls_filter_impl(adf_wls_t* h, int n_pairs, const DispMaps& dm,
     const int orient_u2 = wave ? ORIENT_PAIR : ORIENT_T;     // the two right-hand sides of a confidence-mode call
     const int orient_cv = wave ? ORIENT_STRIP : ORIENT_N;
     const int16_t fill = (int16_t)(16 * (h->min_disp - 1));            // DF.cpp:254,284
-    const int rrx = W - (roi.x + roi.width);                           // DF.cpp:202
-    const int thresh = (int)(1.0f * h->lrc_thresh);                    // DF.cpp:318 (resize_factor 1)
-    Profiler* prof = &h->prof;
+    const ConfRule rule = conf_rule(h, c);
     h->last_path = plan.path; h->last_solver_path = plan.solver_path;
 
     for (int first = 0; first < n_pairs; first += plan.chunk) {
         const int n = (n_pairs - first < plan.chunk) ? n_pairs - first : plan.chunk;
         const ChunkPlan& cp = n == plan.chunk ? plan.full : plan.tail;
-        // the caller's maps, and what the confidence kernels read: the same, or the chunk's planes q
-        const void* mL = (const char*)dispL + (ptrdiff_t)first * psL;
-        const void* mR = dispR ? (const char*)dispR + (ptrdiff_t)first * psR : nullptr;
-        const int16_t* dL = quant ? qL : (const int16_t*)mL;
-        const int16_t* dR = quant ? qR : (const int16_t*)mR;
-        const ptrdiff_t sLq = quant ? (ptrdiff_t)qpitch * 2 : sL, psLq = quant ? (ptrdiff_t)qframe * 2 : psL;
-        const ptrdiff_t sRq = quant ? (ptrdiff_t)qpitch * 2 : sR, psRq = quant ? (ptrdiff_t)qframe * 2 : psR;
-        const uint8_t* gv = view + (ptrdiff_t)first * psG;
-        void* o = (char*)out + (ptrdiff_t)first * psO;
+        const uint8_t* gv = pairs_on(vw.p, vw.pair_stride, first);
+        void* o = (char*)om.p + (ptrdiff_t)first * om.pair_stride;
         float* confp = conf ? (float*)h->conf.p + (size_t)first * g.cframe : nullptr;
         const double F = (double)g.frame * n, P = (double)g.rw * g.rh * n;
+        // what the chunk's kernels read of the maps (float maps of the view's size: q once the chunk is quantised)
+        MapSource m = c.scaled ? lo.from(first) : caller_maps(c.dm).from(first);
         // the output outside the ROI (DF.cpp:284), and the confidence plane there where this call's own kernels make it
-        OutsideArgs oa{o, sO, psO, fill, om.f32 ? 1 : 0, scaled ? nullptr : confp, g};
-        const double ob = ((oa.conf ? 4.0 : 0.0) + ob_px) * (F - P);
-        auto fill_outside = [&](hipStream_t s) { ProfScope ps(prof, K_FILL, ob, ob, s); return launch_outside(oa, n, s); };
+        OutsideArgs oa{o, om.stride, om.pair_stride, fill, om.f32 ? 1 : 0, c.scaled ? nullptr : confp, g};
+        auto fill_outside = [&](hipStream_t s) {
+            ProfScope ps(prof, K_FILL, fill_bytes(F - P, oa.conf != nullptr, ob_px), s);
+            return launch_outside(oa, n, s);
+        };
         // (guide_rows: no Chor -- the plane stays carved and untouched)
-        WeightArgs wa{gv, sG, psG, gch, h->lut.cur, cp.guide_rows ? nullptr : p.CH, p.CV, orient_h, orient_cv, g,
+        WeightArgs wa{gv, vw.stride, vw.pair_stride, gch, h->lut.cur, cp.guide_rows ? nullptr : p.CH, p.CV, orient_h, orient_cv, g,
                       wave ? nullptr : p.B0};   // exact: B0 is free until the first pass writes its output there
-        const GuideWeights gw = guide_weights(h, gv, sG, psG, gch, g);
-        ConfBandArgs ba{dL, sLq, psLq, dR, sRq, psRq, confp, g, rrx, thresh, h->disc_radius, h->roll_off, 0};
-        DiscArgs da{{dL, dR}, {sLq, sRq}, {psLq, psRq}, {roi.x, rrx}, roi.y, roi.width, roi.height, h->disc_radius, h->roll_off,
-                    {cL, cR}, W, g.frame, cp.stage == CONF_LEFT ? 1 : -1};
-        const FusedInputs fuse = cp.stage == CONF_SCALED_LO ? lo_fuse(h, *scaled, first, g) : view_fuse(confp, mL, sL, psL, f32in, g);
-        // the right-hand sides from the caller's maps and the confidence plane (DF.cpp:286-290): the down-scaled path's
-        // prologue, and the float maps' wherever the first row pass is not fused
-        auto conf_prologue = [&]() {
-            PlainPrologueArgs pa{mL, sL, psL, rhs_depth, 1, 0, p.A0, g, orient_u2, confp, p.A1};
-            ProfScope ps(prof, K_PROLOGUE, (12.0 + db_px) * P, (12.0 + db_px) * P, st);
+        const GuideWeights gw = guide_weights(h, gv, vw, g);
+        auto prologue = [&](bool weighted) {                               // FGS.cpp:203-205, or DF.cpp:286-290
+            PlainPrologueArgs pa{m.rhs, m.s_rhs, m.ps_rhs, m.rhs_depth, 1, 0, p.A0, g, weighted ? orient_u2 : orient_h};
+            if (weighted) { pa.conf = confp; pa.U1 = p.A1; }
+            ProfScope ps(prof, K_PROLOGUE, prologue_bytes(P, weighted, db_px), st);
             return launch_plain_prologue(pa, n, st);
         };
 
+        // fork
         hipStream_t wst = st;
         if (cp.fork_weights) {
             if ((rc = h->ensure_side(st))) return rc;
@@ -741,213 +974,89 @@ static int wls_filter_impl(adf_wls_t* h, int n_pairs, const DispMaps& dm,
             HIP_TRY(hipStreamWaitEvent(h->side, h->ev_fork, 0));
             wst = h->side;
         }
+        // outside fill and weights (without confidence a down-scaled call resizes its maps between the two)
         if (cp.stage == CONF_NONE || cp.outside_on_side) HIP_TRY(fill_outside(wst));
-        if (cp.stage == CONF_NONE && scaled && first == 0 && (rc = scaled_resize(h, *scaled, st, prof))) return rc;
+        if (cp.stage == CONF_NONE && c.scaled && first == 0 && (rc = resize_disparity(prof, c, lo, sb.dhi, st))) return rc;
         if (cp.stage != CONF_MERGED) {
-            const double wb = (gch + (cp.guide_rows ? 4.0 : 8.0)) * P;
-            ProfScope ps(prof, K_WEIGHTS, wb, wb, wst);
+            ProfScope ps(prof, K_WEIGHTS, weights_bytes(P, gch, !cp.guide_rows), wst);
             HIP_TRY(launch_weights(wa, n, wst));                           // FGS.cpp:163-172
         }
         if (cp.fork_weights) HIP_TRY(hipEventRecord(h->ev_join, h->side));
-        if (quant) {
-            QuantArgs qa{{mL, mR}, {sL, sR}, {psL, psR}, {qL, qR}, nullptr, W, H, qpitch, qframe, n};
-            ProfScope ps(prof, K_QUANT, 12.0 * F, 12.0 * F, st);         // 2 maps: 4 read + 2 written per pixel
-            HIP_TRY(launch_quantise_maps(qa, st));
-        }
-
+        // quantise
+        if (plan.quant_planes &&
+            (rc = quantise_maps(prof, c.dm.from(first), W, H, n, qL, qR, nullptr, st, m))) return rc;
+        // confidence stage, with the outside fill (DF.cpp:284, :187-190) where it did not go to the side stream
         switch (cp.stage) {
-        case CONF_NONE: {
-            PlainPrologueArgs pa{mL, sL, psL, rhs_depth, 1, 0, p.A0, g, orient_h};
-            ProfScope ps(prof, K_PROLOGUE, (4.0 + db_px) * P, (4.0 + db_px) * P, st);
-            HIP_TRY(launch_plain_prologue(pa, n, st));                     // FGS.cpp:203-205
+        case CONF_NONE:
             break;
-        }
-        case CONF_SCALED: {   // confidence resized to the view (DF.cpp:274): only the prologue remains (DF.cpp:286-290)
+        case CONF_SCALED:
+        case CONF_SCALED_LO:
             if (!cp.outside_on_side) HIP_TRY(fill_outside(st));
-            if (first == 0 && ((rc = scaled_conf_map(h, *scaled, st, prof)) || (rc = scaled_resize(h, *scaled, st, prof)))) return rc;
-            if (plan.fused_first) break;
-            HIP_TRY(conf_prologue());
-            break;
-        }
-        case CONF_SCALED_LO:  // the first row pass taps the low-resolution maps itself: no resize launch, no view-sized planes
-            if (!cp.outside_on_side) HIP_TRY(fill_outside(st));
-            if (first != 0) break;
-            if ((rc = scaled_conf_map(h, *scaled, st, prof))) return rc;
-            // a call captured into a graph is replayed without this host code: the view-sized confidence maps are made
-            // inside the call (the graph), so getConfidenceMap() stays current after replays; otherwise on demand
-            if (!stream_is_capturing(st)) h->lazy_conf = adf_wls::LazyConf{true, scaled->lo};
-            else if ((rc = resize_conf_planes(h, scaled->lo, st, prof))) return rc;
+            if (first == 0 && (rc = scaled_conf_maps(h, c, plan, sb, lo, rule, st))) return rc;
             break;
         case CONF_MERGED: {
-            const double b = (8.0 + gch + 8.0) * P + (4.0 + ob_px) * (F - P);
-            ProfScope ps(prof, K_LRC, b, b, st);
-            HIP_TRY(launch_prep_small(ba, wa, oa, n, st));                 // FGS.cpp:163-172 + DF.cpp:197-210 + :284
+            ProfScope ps(prof, K_LRC, merged_bytes(P, F - P, gch, ob_px), st);
+            HIP_TRY(launch_prep_small(conf_band_args(m, confp, g, rule), wa, oa, n, st));   // FGS.cpp:163-172 + DF.cpp:197-210 + :284
             break;
         }
-        case CONF_BAND: {
-            {
-                ProfScope ps(prof, K_LRC, 8.0 * P, 8.0 * P, st);         // dL 2 + dR 2 read, conf 4 written
-                HIP_TRY(launch_conf_band(ba, n, st));                      // DF.cpp:197-210
-            }
-            if (!cp.outside_on_side) HIP_TRY(fill_outside(st));            // DF.cpp:284, :187-190
-            break;
-        }
-        case CONF_LEFT: {
-            {
-                ProfScope ps(prof, K_DISC, 2.0 * P, 6.0 * P, st);
-                HIP_TRY(launch_discontinuity(da, n, st));                  // DF.cpp:204 (right view)
-            }
-            // (float maps: the kernel sees q, so it writes the confidence map only and the prologue forms conf * v)
-            const bool fused = plan.fused_first || quant;
-            ConfLeftArgs ca{dL, sLq, psLq, dR, sRq, psRq, cR, confp, fused ? nullptr : p.A0, fused ? nullptr : p.A1,
-                            g, rrx, thresh, h->disc_radius, h->roll_off};
-            {   // alg: conf (4P); moved: dL 2 + dR 2 + cR 4 reads, conf 4 (+8 when U0/U1 are materialised)
-                const double wu = fused ? 0.0 : 8.0;
-                ProfScope ps(prof, K_LRC, (4.0 + wu) * P, (12.0 + wu) * P, st);
-                HIP_TRY(launch_conf_left(ca, n, st));                      // DF.cpp:204-209 (+288-290)
-            }
-            if (!cp.outside_on_side) HIP_TRY(fill_outside(st));            // DF.cpp:284, :187-190
-            if (quant && !plan.fused_first) HIP_TRY(conf_prologue());
-            break;
-        }
+        case CONF_BAND:
+        case CONF_LEFT:
         case CONF_TWO_KERNEL: {
-            {   // reads the int16 ROIs, writes the float maps (the maps themselves are not algorithmic I/O)
-                ProfScope ps(prof, K_DISC, 4.0 * P, 12.0 * P, st);
-                HIP_TRY(launch_discontinuity(da, n, st));                  // DF.cpp:204
-            }
-            // float maps: the kernel reads its own pixel from the caller's left map (v, and q on the fly), the gather from qR
-            LrcArgs la{quant ? (const int16_t*)mL : dL, quant ? sL : sLq, quant ? psL : psLq, dR, sRq, psRq, cL, cR, confp, o, sO, psO,
-                       fill, om.f32 ? 1 : 0, p.A0, p.A1, g, rrx, thresh, orient_u2, quant ? 1 : 0};
-            // alg: confidence map out (4F) + the two rhs planes (8P); moved adds dL,dR,cL,cR reads
-            ProfScope ps(prof, K_LRC, 4.0 * F + 8.0 * P + ob_px * (F - P), 4.0 * F + (18.0 + db_px) * P + ob_px * (F - P), st);
-            HIP_TRY(launch_lrc_prologue(la, n, st));                       // DF.cpp:208-209,288-290
+            ConfOut out{confp, cL, cR};
+            if (plan.rhs == RHS_CONF_KERNEL) { out.U0 = p.A0; out.U1 = p.A1; out.orient = orient_u2; }
+            if (cp.stage == CONF_TWO_KERNEL) out.fill = &oa;
+            if ((rc = conf_stage(prof, cp.stage, m, g, rule, out, n, st))) return rc;
+            if (cp.stage != CONF_TWO_KERNEL && !cp.outside_on_side) HIP_TRY(fill_outside(st));
             break;
         }
         }
+        // right-hand sides, where neither the first row pass nor the confidence kernel forms them
+        if (plan.rhs == RHS_PLAIN || plan.rhs == RHS_CONF_PROLOGUE) HIP_TRY(prologue(plan.rhs == RHS_CONF_PROLOGUE));
+        // join
         if (cp.fork_weights) HIP_TRY(hipStreamWaitEvent(st, h->ev_join, 0));
+        // passes
+        const FusedInputs fuse = plan.rhs == RHS_FUSED_LO
+            ? lo_fuse(h, c, plan.lo_band, sb.clo + (size_t)first * c.dW * c.dH, m, sb.taps, g) : view_fuse(confp, m, g);
         const int epi = conf ? (om.f32 ? EPI_WLS_CONF_F32 : EPI_WLS_CONF) : (om.f32 ? EPI_F32 : EPI_I16);
-        FinalOut fo{epi, o, sO, psO, roi.x, roi.y, 1, 0};
+        FinalOut fo{epi, o, om.stride, om.pair_stride, roi.x, roi.y, 1, 0};
         rc = run_passes(wave, g, p, conf ? 2 : 1, (float)h->lambda, (float)h->atten, h->num_iter, fo, n, st, prof,
-                        plan.fused_first ? &fuse : nullptr, cp.guide_rows ? &gw : nullptr);
+                        plan.fused_first() ? &fuse : nullptr, cp.guide_rows ? &gw : nullptr);
         if (rc) return rc;                                                 // DF.cpp:257-258, 292-296
     }
     return ADF_OK;
 }
 
-// Down-scaled disparity path (DF.cpp:224-227, 239-247, 268-277): disparity maps of dW x dH, view and
-// output of W x H.  ROI is in disparity-map coordinates, like the reference's.
-// Float maps (include/adf_wls.h): base and strides are multiples of 4 bytes, and the filtered map overlaps neither.
-static int check_float_maps(const DispMaps& dm, int n_pairs, int dW, int dH, const OutMap& om, int W, int H)
-{
-    if (!dm.f32) return ADF_OK;
-    if ((reinterpret_cast<uintptr_t>(dm.L) | (uintptr_t)dm.sL | (uintptr_t)dm.psL) & 3u ||
-        (dm.R && ((reinterpret_cast<uintptr_t>(dm.R) | (uintptr_t)dm.sR | (uintptr_t)dm.psR) & 3u)))
-        return fail(ADF_EBADARG, "a float disparity map needs a 4-byte aligned base and strides");
-    // [first byte, last byte] of n_pairs images of `rows` rows of `row_bytes`, whatever the signs of the strides
-    auto span = [&](const void* p, ptrdiff_t s, ptrdiff_t ps, size_t row_bytes, int rows, uintptr_t& lo, uintptr_t& hi) {
-        const ptrdiff_t a = s * (rows - 1), b = ps * (n_pairs - 1);
-        lo = reinterpret_cast<uintptr_t>(p) + (a < 0 ? a : 0) + (b < 0 ? b : 0);
-        hi = reinterpret_cast<uintptr_t>(p) + (a > 0 ? a : 0) + (b > 0 ? b : 0) + row_bytes;
-    };
-    if (!om.p || dW <= 0 || dH <= 0 || W <= 0 || H <= 0 || n_pairs < 1) return ADF_OK;   // (refused by the call itself)
-    uintptr_t olo, ohi, mlo, mhi;
-    span(om.p, om.stride, om.pair_stride, (size_t)W * om.esz(), H, olo, ohi);
-    const void* maps[2] = {dm.L, dm.R}; const ptrdiff_t ss[2] = {dm.sL, dm.sR}, pss[2] = {dm.psL, dm.psR};
-    for (int m = 0; m < 2; m++) {
-        if (!maps[m]) continue;
-        span(maps[m], ss[m], pss[m], (size_t)dW * 4, dH, mlo, mhi);
-        if (olo < mhi && mlo < ohi) return fail(ADF_EBADARG, "filtered_disparity_map overlaps a float disparity map");
-    }
-    return ADF_OK;
-}
-
-static int wls_filter_scaled_device(adf_wls_t* h, int n_pairs, const DispMaps& dm, int dW, int dH,
-                                    const uint8_t* view, ptrdiff_t sG, ptrdiff_t psG, int gch, int W, int H,
-                                    const OutMap& om, const adf_rect* roi_in, hipStream_t st)
+// Every device entry: check, plan, run.
+static int wls_filter_device(adf_wls_t* h, int n_pairs, const DispMaps& dm, int dW, int dH, const View& view, const OutMap& om,
+                             const adf_rect* roi, hipStream_t st)
 {
     NEED_HANDLE(h);
-    int rc;
-    if ((rc = check_float_maps(dm, n_pairs, dW, dH, om, W, H))) return rc;
-    if (dW == W && dH == H)                                                // DF.cpp:224-227: same size, resize_factor 1
-        return wls_filter_impl(h, n_pairs, dm, view, sG, psG, gch, W, H, om, roi_in, st);
-    const void* const dispL = dm.L; const void* const dispR = dm.R;
-    const ptrdiff_t sL = dm.sL, psL = dm.psL, sR = dm.sR, psR = dm.psR;
-    const bool f32in = dm.f32;
-    if (!dispL || dW <= 0 || dH <= 0 || W <= 0 || H <= 0) return fail(ADF_EBADARG, "disparity_map_left is empty");
-    if (n_pairs < 1) return fail(ADF_EBADARG, "n_pairs must be >= 1");
-    if (sL < (ptrdiff_t)(dW * dm.esz())) return fail(ADF_ESIZE, "row stride smaller than a row");
-    const bool conf = h->use_confidence;
-    if (conf && ((rc = check_right_map(dispR, sR, dW, dm.esz())) || (rc = check_radius(h)))) return rc;
-    adf_rect rlo;                                                          // disparity-map coordinates
-    if ((rc = resolve_roi(h, roi_in, dW, dH, rlo))) return rc;
-    const float resize_factor = dW / (float)W;                             // DF.cpp:225
-    const float x_ratio = W / (float)dW, y_ratio = H / (float)dH;          // DF.cpp:241-242,270-271
-    adf_rect rhi{(int)(rlo.x * x_ratio), (int)(rlo.y * y_ratio), (int)(rlo.width * x_ratio), (int)(rlo.height * y_ratio)};
-    if (rhi.width <= 0 || rhi.height <= 0 || rhi.x + rhi.width > W || rhi.y + rhi.height > H)
-        return fail(ADF_ESIZE, "scaled ROI (%d,%d,%d,%d) does not fit the %dx%d view", rhi.x, rhi.y, rhi.width, rhi.height, W, H);
-
+    WlsCall c;
+    int rc = check_call(h, n_pairs, dm, dW, dH, view, om, roi, c);
+    if (rc) return rc;
     DeviceScope ds(h->device);
     h->lazy_conf.pending = false;    // (the previous call's low-resolution maps are about to be overwritten or freed)
-    const size_t lo = (size_t)dW * dH, hi = (size_t)W * H;
-    const Geom ghi = make_geom(W, H, rhi.x, rhi.y, rhi.width, rhi.height);   // the geometry wls_filter_impl will derive
-    // float maps: the low-resolution confidence kernels read the planes q, the resize reads the plane v (set below)
-    const int qpitch = quant_pitch(dW);
-    const size_t qframe = (size_t)qpitch * dH;
-    ScaledStage s{(const int16_t*)dispL, sL, psL, (const int16_t*)dispR, sR, psR, nullptr, 0, 0, resize_factor, x_ratio, nullptr, 0,
-                  nullptr, nullptr, ConfResize{UNALLOCATED, dW, dH, rlo, ghi, false, n_pairs}, false, nullptr};
-    s.lo.band_map = conf && h->conf_band &&
-                    conf_band_fits(plain_conf_layout(make_geom(dW, dH, rlo.x, rlo.y, rlo.width, rlo.height)), h->disc_radius);
-    // Can the first row pass interpolate the maps itself (fgs_wave_h.hip, FUSE_LO)?  Confidence mode on the wave solver,
-    // scale factors within the staging buffer's reach.  Then neither the resized disparity map nor -- until
-    // getConfidenceMap() asks for it -- the resized confidence map is ever written.
-    // (float maps take the resize kernels: the fused low-resolution prologue has no float form)
-    s.fuse_lo = conf && !f32in && h->scaled_fuse && h->solver == ADF_SOLVER_WAVE && wave_fits(ghi) &&
-                wave_hpass_can_fuse_lo(first_pass_probe(lo_fuse(h, s, 0, ghi), ghi.rw));
-    // scratch: resized disparity (int16, view size; not with fuse_lo) + low-resolution cL, cR, conf (float)
-    s.dhi_bytes = s.fuse_lo ? 0 : pad_to(hi * dm.esz(), 256);
-    const size_t maps_bytes = pad_to((size_t)n_pairs * (s.dhi_bytes + (conf ? 3 * lo * sizeof(float) : 0)), 256);
-    const size_t taps_bytes = pad_to(s.fuse_lo ? 2 * ((size_t)rhi.width + 4) * sizeof(float) : 0, 256);   // + the columns' taps
-    // + float maps: v (float) and, in confidence mode, the two planes q (int16), per pair
-    const size_t quant_bytes = f32in ? (size_t)n_pairs * qframe * (4 + (conf ? 4 : 0)) : 0;
-    const size_t need = maps_bytes + taps_bytes + quant_bytes;
-    if ((rc = h->scaled.reserve(need, st, FILL_ZERO))) return rc;
-    s.dhi = (char*)h->scaled.p;
-    s.cl = (float*)(s.dhi + (size_t)n_pairs * s.dhi_bytes);
-    s.cr = s.cl + (size_t)n_pairs * lo;
-    s.lo.clo = s.cr + (size_t)n_pairs * lo;
-    s.taps = s.fuse_lo ? (float*)((char*)h->scaled.p + maps_bytes) : nullptr;
-    if (conf && (rc = ensure_conf_planes(h, ghi, n_pairs, st))) return rc;
-    if (f32in) {
-        float* v = (float*)((char*)h->scaled.p + maps_bytes + taps_bytes);
-        int16_t* qL = conf ? (int16_t*)(v + (size_t)n_pairs * qframe) : nullptr;
-        int16_t* qR = conf ? qL + (size_t)n_pairs * qframe : nullptr;
-        QuantArgs qa{{dispL, conf ? dispR : nullptr}, {sL, sR}, {psL, psR}, {qL, qR}, v, dW, dH, qpitch, qframe, n_pairs};
-        const double lo_px = (double)lo * n_pairs;
-        ProfScope ps(&h->prof, K_QUANT, (conf ? 16.0 : 8.0) * lo_px, (conf ? 16.0 : 8.0) * lo_px, st);
-        HIP_TRY(launch_quantise_maps(qa, st));
-        s.dispL = qL; s.dispR = qR; s.sL = s.sR = (ptrdiff_t)qpitch * 2; s.psL = s.psR = (ptrdiff_t)qframe * 2;
-        s.vL = v; s.svL = (ptrdiff_t)qpitch * 4; s.psvL = (ptrdiff_t)qframe * 4;
-    }
-    // (fuse_lo: wls_filter_impl never dereferences its dispL -- the caller's low-resolution map stands in, with its own strides)
-    const DispMaps dhi{s.fuse_lo ? dispL : (const void*)s.dhi, (ptrdiff_t)(W * dm.esz()), (ptrdiff_t)s.dhi_bytes, nullptr, 0, 0, f32in};
-    rc = wls_filter_impl(h, n_pairs, dhi, view, sG, psG, gch, W, H, om, &rhi, st, &s);
-    h->roi = rlo;                                                          // getROI(): valid_disp_ROI (DF.cpp:139)
+    if ((rc = h->lut.ensure((float)h->sigma_color, st))) return rc;
+    rc = wls_filter_impl(h, c, plan_wls(h, c), st);
+    if (c.scaled) h->roi = c.rlo;                                          // getROI(): valid_disp_ROI (DF.cpp:139)
     return rc;
 }
 
-static int wls_filter_scaled_host(adf_wls_t* h, int n_pairs, const DispMaps& dm, int dW, int dH,
-                                  const uint8_t* view, ptrdiff_t sG, ptrdiff_t psG, int gch, int W, int H,
-                                  const OutMap& om, const adf_rect* roi)
+// Every host entry: dense device copies of the images, the device call on them, the filtered map copied back.  Refused
+// here is only what has to be before anything is read through the host pointers -- the float maps' rules, which the
+// copies would satisfy whatever the caller passed, and what the copies' sizes and sources depend on; wls_filter_device
+// refuses the rest.
+static int wls_filter_host(adf_wls_t* h, int n_pairs, const DispMaps& dm, int dW, int dH, const View& view, const OutMap& om,
+                           const adf_rect* roi)
 {
     NEED_HANDLE(h);
-    const void* const dispL = dm.L; const void* const dispR = dm.R;
-    const ptrdiff_t sL = dm.sL, psL = dm.psL, sR = dm.sR, psR = dm.psR;
+    const int W = view.W, H = view.H, gch = view.ch;
     int rc = check_float_maps(dm, n_pairs, dW, dH, om, W, H);
     if (rc) return rc;
-    if (!dispL || !view || !om.p || W <= 0 || H <= 0 || dW <= 0 || dH <= 0 || n_pairs < 1)
+    if (!dm.L || !view.p || !om.p || W <= 0 || H <= 0 || dW <= 0 || dH <= 0 || n_pairs < 1)
         return fail(ADF_EBADARG, "adf_wls_filter_host: empty input");
-    if (gch != 1 && gch != 3) return fail(ADF_EBADARG, "left_view must be CV_8UC1 or CV_8UC3");
-    if (h->use_confidence && !dispR) return fail(ADF_EBADARG, "disparity_map_right is required with use_confidence");
+    if (gch != 1 && gch != 3) return bad_view_channels();
+    if (h->use_confidence && !dm.R) return no_right_map();
     DeviceScope ds(h->device);
     hipStream_t st = nullptr;
     // dense device copies: [dispL | dispR | out | view] per batch
@@ -961,12 +1070,12 @@ static int wls_filter_scaled_host(adf_wls_t* h, int n_pairs, const DispMaps& dm,
     char* dRd = dLd + (size_t)n_pairs * dpad;
     char* od = dRd + (size_t)n_pairs * dpad;
     char* gd = od + (size_t)n_pairs * opad;
-    if ((rc = copy_images(dLd, drow, dpad, dispL, sL, psL, drow, dH, n_pairs, hipMemcpyHostToDevice, st))) return rc;
-    if (dispR && (rc = copy_images(dRd, drow, dpad, dispR, sR, psR, drow, dH, n_pairs, hipMemcpyHostToDevice, st))) return rc;
-    if ((rc = copy_images(gd, (size_t)W * gch, gpad, view, sG, psG, (size_t)W * gch, H, n_pairs, hipMemcpyHostToDevice, st))) return rc;
-    const DispMaps dd{dLd, (ptrdiff_t)drow, (ptrdiff_t)dpad, dispR ? dRd : nullptr, (ptrdiff_t)drow, (ptrdiff_t)dpad, dm.f32};
-    rc = wls_filter_scaled_device(h, n_pairs, dd, dW, dH, (const uint8_t*)gd, (ptrdiff_t)W * gch, (ptrdiff_t)gpad, gch, W, H,
-                                  OutMap{od, (ptrdiff_t)orow, (ptrdiff_t)opad, om.f32}, roi, st);
+    if ((rc = copy_images(dLd, drow, dpad, dm.L, dm.sL, dm.psL, drow, dH, n_pairs, hipMemcpyHostToDevice, st))) return rc;
+    if (dm.R && (rc = copy_images(dRd, drow, dpad, dm.R, dm.sR, dm.psR, drow, dH, n_pairs, hipMemcpyHostToDevice, st))) return rc;
+    if ((rc = copy_images(gd, (size_t)W * gch, gpad, view.p, view.stride, view.pair_stride, (size_t)W * gch, H, n_pairs, hipMemcpyHostToDevice, st))) return rc;
+    const DispMaps dd{dLd, (ptrdiff_t)drow, (ptrdiff_t)dpad, dm.R ? dRd : nullptr, (ptrdiff_t)drow, (ptrdiff_t)dpad, dm.f32};
+    rc = wls_filter_device(h, n_pairs, dd, dW, dH, View{(const uint8_t*)gd, (ptrdiff_t)W * gch, (ptrdiff_t)gpad, gch, W, H},
+                           OutMap{od, (ptrdiff_t)orow, (ptrdiff_t)opad, om.f32}, roi, st);
     if (rc) return rc;
     if ((rc = copy_images(om.p, om.stride, om.pair_stride, od, orow, opad, orow, H, n_pairs, hipMemcpyDeviceToHost, st))) return rc;
     HIP_TRY(hipStreamSynchronize(st));
@@ -979,34 +1088,24 @@ static int wls_filter_scaled_host(adf_wls_t* h, int n_pairs, const DispMaps& dm,
 #define ADF_WLS_SCALED_ARGS const int16_t* dispL, ptrdiff_t sL, ptrdiff_t psL, int dW, int dH, \
                             const uint8_t* view, ptrdiff_t sG, ptrdiff_t psG, int gch, int W, int H
 #define ADF_WLS_RIGHT_ARGS const int16_t* dispR, ptrdiff_t sR, ptrdiff_t psR, const adf_rect* roi
-#define ADF_WLS_ENTRIES(SUFFIX, T, F32)                                                                                       \
-    extern "C" int adf_wls_filter##SUFFIX##_device(adf_wls_t* h, int n_pairs, ADF_WLS_SAME_ARGS, T* out, ptrdiff_t sO,        \
-                                                   ptrdiff_t psO, ADF_WLS_RIGHT_ARGS, void* stream)                           \
+// (an entry's images as wls_filter_device / wls_filter_host take them; a same-size entry's maps have the view's size)
+#define ADF_WLS_IMAGES(DW, DH, F32IN, F32OUT) DispMaps{dispL, sL, psL, dispR, sR, psR, F32IN}, DW, DH, \
+                                              View{view, sG, psG, gch, W, H}, OutMap{out, sO, psO, F32OUT}, roi
+#define ADF_WLS_ENTRY_PAIR(NAME, MAP_ARGS, DW, DH, T, F32)                                                                     \
+    extern "C" int NAME##_device(adf_wls_t* h, int n_pairs, MAP_ARGS, T* out, ptrdiff_t sO, ptrdiff_t psO, ADF_WLS_RIGHT_ARGS, \
+                                 void* stream)                                                                                \
     {                                                                                                                         \
-        return wls_filter_impl(h, n_pairs, DispMaps{dispL, sL, psL, dispR, sR, psR, false}, view, sG, psG, gch, W, H,         \
-                               OutMap{out, sO, psO, F32}, roi, (hipStream_t)stream);                                          \
+        return wls_filter_device(h, n_pairs, ADF_WLS_IMAGES(DW, DH, false, F32), (hipStream_t)stream);                        \
     }                                                                                                                         \
-    extern "C" int adf_wls_filter_scaled##SUFFIX##_device(adf_wls_t* h, int n_pairs, ADF_WLS_SCALED_ARGS, T* out,             \
-                                                          ptrdiff_t sO, ptrdiff_t psO, ADF_WLS_RIGHT_ARGS, void* stream)      \
+    extern "C" int NAME##_host(adf_wls_t* h, int n_pairs, MAP_ARGS, T* out, ptrdiff_t sO, ptrdiff_t psO, ADF_WLS_RIGHT_ARGS)   \
     {                                                                                                                         \
-        return wls_filter_scaled_device(h, n_pairs, DispMaps{dispL, sL, psL, dispR, sR, psR, false}, dW, dH, view, sG, psG,   \
-                                        gch, W, H, OutMap{out, sO, psO, F32}, roi, (hipStream_t)stream);                      \
-    }                                                                                                                         \
-    extern "C" int adf_wls_filter_scaled##SUFFIX##_host(adf_wls_t* h, int n_pairs, ADF_WLS_SCALED_ARGS, T* out, ptrdiff_t sO, \
-                                                        ptrdiff_t psO, ADF_WLS_RIGHT_ARGS)                                    \
-    {                                                                                                                         \
-        return wls_filter_scaled_host(h, n_pairs, DispMaps{dispL, sL, psL, dispR, sR, psR, false}, dW, dH, view, sG, psG,     \
-                                      gch, W, H, OutMap{out, sO, psO, F32}, roi);                                             \
-    }                                                                                                                         \
-    extern "C" int adf_wls_filter##SUFFIX##_host(adf_wls_t* h, int n_pairs, ADF_WLS_SAME_ARGS, T* out, ptrdiff_t sO,          \
-                                                 ptrdiff_t psO, ADF_WLS_RIGHT_ARGS)                                           \
-    {                                                                                                                         \
-        return wls_filter_scaled_host(h, n_pairs, DispMaps{dispL, sL, psL, dispR, sR, psR, false}, W, H, view, sG, psG, gch,  \
-                                      W, H, OutMap{out, sO, psO, F32}, roi);                                                  \
+        return wls_filter_host(h, n_pairs, ADF_WLS_IMAGES(DW, DH, false, F32));                                               \
     }
-ADF_WLS_ENTRIES(, int16_t, false)
-ADF_WLS_ENTRIES(_f32, float, true)
-#undef ADF_WLS_ENTRIES
+ADF_WLS_ENTRY_PAIR(adf_wls_filter, ADF_WLS_SAME_ARGS, W, H, int16_t, false)
+ADF_WLS_ENTRY_PAIR(adf_wls_filter_f32, ADF_WLS_SAME_ARGS, W, H, float, true)
+ADF_WLS_ENTRY_PAIR(adf_wls_filter_scaled, ADF_WLS_SCALED_ARGS, dW, dH, int16_t, false)
+ADF_WLS_ENTRY_PAIR(adf_wls_filter_scaled_f32, ADF_WLS_SCALED_ARGS, dW, dH, float, true)
+#undef ADF_WLS_ENTRY_PAIR
 
 // The typed pair: the scaled entries' arguments with the maps' and the filtered map's depth as arguments.
 static int typed_depths(int disp_depth, int out_depth)
@@ -1022,8 +1121,7 @@ extern "C" int adf_wls_filter_typed_device(adf_wls_t* h, int n_pairs, const void
 {
     NEED_HANDLE(h);
     if (int rc = typed_depths(disp_depth, out_depth)) return rc;
-    return wls_filter_scaled_device(h, n_pairs, DispMaps{dispL, sL, psL, dispR, sR, psR, disp_depth == ADF_32F}, dW, dH, view, sG, psG,
-                                    gch, W, H, OutMap{out, sO, psO, out_depth == ADF_32F}, roi, (hipStream_t)stream);
+    return wls_filter_device(h, n_pairs, ADF_WLS_IMAGES(dW, dH, disp_depth == ADF_32F, out_depth == ADF_32F), (hipStream_t)stream);
 }
 extern "C" int adf_wls_filter_typed_host(adf_wls_t* h, int n_pairs, const void* dispL, ptrdiff_t sL, ptrdiff_t psL, int disp_depth,
                                          int dW, int dH, const uint8_t* view, ptrdiff_t sG, ptrdiff_t psG, int gch, int W, int H,
@@ -1032,9 +1130,9 @@ extern "C" int adf_wls_filter_typed_host(adf_wls_t* h, int n_pairs, const void* 
 {
     NEED_HANDLE(h);
     if (int rc = typed_depths(disp_depth, out_depth)) return rc;
-    return wls_filter_scaled_host(h, n_pairs, DispMaps{dispL, sL, psL, dispR, sR, psR, disp_depth == ADF_32F}, dW, dH, view, sG, psG,
-                                  gch, W, H, OutMap{out, sO, psO, out_depth == ADF_32F}, roi);
+    return wls_filter_host(h, n_pairs, ADF_WLS_IMAGES(dW, dH, disp_depth == ADF_32F, out_depth == ADF_32F));
 }
+#undef ADF_WLS_IMAGES
 #undef ADF_WLS_SAME_ARGS
 #undef ADF_WLS_SCALED_ARGS
 #undef ADF_WLS_RIGHT_ARGS
