@@ -565,13 +565,28 @@ extern "C" int adf_bm_get_params(const adf_bm_t* h, int* min_disparity, int* num
     return ADF_OK;
 }
 
-static int bm_check(const adf_bm* h, int n, const void* l, const void* r, const void* d, int W, int H,
-                    ptrdiff_t ls, ptrdiff_t rs, ptrdiff_t dstr)
+// One compute call as its entry received it: planes with rows `stride`, pairs `pair` bytes apart.  disp / cost [0]: the
+// left view's, [1]: the right view's (nviews == 2: a both-views entry); with_cost: a cost entry, which takes the cost
+// plane of every view it matches.  device: device pointers that the kernels index (a host entry's are copied by bytes).
+template <class T> struct Plane { T* p; ptrdiff_t stride, pair; };
+struct BmCall {
+    adf_bm* h; int n_pairs; Plane<const uint8_t> left, right; int W, H;
+    int nviews; bool with_cost; Plane<int16_t> disp[2], cost[2]; bool device;
+};
+
+// a CV_16S plane that does not start every row (with `pairs`: and every pair) on an even address
+static bool odd(const Plane<int16_t>& m, bool pairs) { return (m.stride & 1) || (reinterpret_cast<uintptr_t>(m.p) & 1) || (pairs && (m.pair & 1)); }
+
+// The rules of every compute call, then those of maps that a kernel indexes and of the right view's map.
+static int bm_check(const BmCall& c)
 {
+    const adf_bm* h = c.h;
+    const int W = c.W, H = c.H;
+    const Plane<int16_t>& d = c.disp[0];
     if (!h) return fail(ADF_EBADARG, "handle is NULL");
-    if (n <= 0 || !l || !r || !d) return fail(ADF_EBADARG, "views and disparity must be non-NULL, n_pairs positive");
-    if (W <= 0 || H <= 0 || ls < W || rs < W || dstr < (ptrdiff_t)W * 2) return fail(ADF_ESIZE, "bad size or stride");
-    if ((dstr & 1) || (reinterpret_cast<uintptr_t>(d) & 1)) return fail(ADF_ESIZE, "disparity rows must be 2-byte aligned");
+    if (c.n_pairs <= 0 || !c.left.p || !c.right.p || !d.p) return fail(ADF_EBADARG, "views and disparity must be non-NULL, n_pairs positive");
+    if (W <= 0 || H <= 0 || c.left.stride < W || c.right.stride < W || d.stride < (ptrdiff_t)W * 2) return fail(ADF_ESIZE, "bad size or stride");
+    if (odd(d, false)) return fail(ADF_ESIZE, "disparity rows must be 2-byte aligned");
     // the checks cv::StereoBM::compute makes on its parameters; the window is limited to 21 so that a
     // window sum fits 16 bits
     if (h->num_disp <= 0 || h->num_disp % 16) return fail(ADF_EBADARG, "numDisparities must be positive and divisible by 16");
@@ -580,101 +595,142 @@ static int bm_check(const adf_bm* h, int n, const void* l, const void* r, const 
     if (h->cap < 1 || h->cap > 63) return fail(ADF_EBADARG, "preFilterCap must be within 1..63");
     if (h->texthr < 0 || h->uniq < 0) return fail(ADF_EBADARG, "textureThreshold and uniquenessRatio must be non-negative");
     if (h->min_disp < -32768 || h->min_disp + h->num_disp > 2047) return fail(ADF_EBADARG, "disparity range does not fit CV_16S with 4 fractional bits");
+    if (c.device && odd(d, c.n_pairs > 1)) return fail(ADF_ESIZE, "disparity maps must be 2-byte aligned");
+    if (c.nviews == 2 && (c.disp[1].stride < (ptrdiff_t)W * 2 || odd(c.disp[1], c.n_pairs > 1)))
+        return fail(ADF_ESIZE, "bad stride or alignment of the right disparity map");
     return ADF_OK;
 }
 
-// An optional cost plane of a call (p == NULL: not wanted): rows `stride`, pairs `pair` bytes apart.
-struct CostPlane { int16_t* p; ptrdiff_t stride, pair; };
-static const CostPlane NO_COST{nullptr, 0, 0};
-
-static int bm_cost_check(const CostPlane& c, const char* which, int n_pairs, int W)
+// The planes that a both-views or a cost entry adds to compute's.  A function of its own because the entries differ in
+// WHEN they report them: the device entries before bm_check, adf_bm_compute_cost_host after it (tests/matcher_refusals.json).
+static int bm_check_added(const BmCall& c)
 {
-    if (!c.p) return fail(ADF_EBADARG, "%s cost plane is NULL", which);
-    if (c.stride < (ptrdiff_t)W * 2) return fail(ADF_ESIZE, "%s cost plane: row stride smaller than a row", which);
-    if ((c.stride & 1) || (reinterpret_cast<uintptr_t>(c.p) & 1) || (n_pairs > 1 && (c.pair & 1)))
-        return fail(ADF_ESIZE, "%s cost plane must be 2-byte aligned", which);
+    if (c.nviews == 2 && !c.disp[1].p) return fail(ADF_EBADARG, "disp_right is NULL");
+    static const char* const names[2][2] = {{"the", ""}, {"the left", "the right"}};
+    for (int v = 0; c.with_cost && v < c.nviews; v++) {
+        const Plane<int16_t>& k = c.cost[v];
+        const char* which = names[c.nviews - 1][v];
+        if (!k.p) return fail(ADF_EBADARG, "%s cost plane is NULL", which);
+        if (k.stride < (ptrdiff_t)c.W * 2) return fail(ADF_ESIZE, "%s cost plane: row stride smaller than a row", which);
+        if (odd(k, c.n_pairs > 1)) return fail(ADF_ESIZE, "%s cost plane must be 2-byte aligned", which);
+    }
     return ADF_OK;
 }
 
-// Shared body: prefilter both images once (census: form their descriptor planes), then one launch for the left view
-// alone (disp_right == NULL) or for both views; each view with or without its cost plane.
-static int bm_compute_impl(adf_bm_t* h, int n_pairs,
-                           const uint8_t* left, ptrdiff_t left_stride, ptrdiff_t left_pair_stride,
-                           const uint8_t* right, ptrdiff_t right_stride, ptrdiff_t right_pair_stride,
-                           int W, int H,
-                           int16_t* disp_left, ptrdiff_t dl_stride, ptrdiff_t dl_pair_stride,
-                           int16_t* disp_right, ptrdiff_t dr_stride, ptrdiff_t dr_pair_stride,
-                           const CostPlane& cost_left, const CostPlane& cost_right,
-                           hipStream_t st)
+// The geometry of a checked call: a pure function of the handle's settings and the call's sizes.
+struct BmSearch { int mindisp, xs, xe, texthr, uniq; };   // matched columns [xs, xe)
+struct BmPlan {
+    int HG, HGP, Wp;             // row groups of the image, with the padding groups; dwords per padded row (lanes past the image read, and discard, it)
+    bool census; int planes, w2;
+    size_t plane, image;         // dwords per prefiltered view or descriptor plane / per image: sized from the handle's cost of THIS call
+    size_t views_bytes;          // h->views: the left images of the batch, then the right ones
+    BmSearch v[2];               // the left view's search, and the right view's in the left image
+};
+
+static BmPlan bm_plan(const BmCall& c)
 {
-    int rc = bm_check(h, n_pairs, left, right, disp_left, W, H, left_stride, right_stride, dl_stride);
-    if (rc) return rc;
-    if (n_pairs > 1 && (dl_pair_stride & 1)) return fail(ADF_ESIZE, "disparity maps must be 2-byte aligned");
-    const int nviews = disp_right ? 2 : 1;
-    if (disp_right) {
-        if (dr_stride < (ptrdiff_t)W * 2 || (dr_stride & 1) || (reinterpret_cast<uintptr_t>(disp_right) & 1) ||
-            (n_pairs > 1 && (dr_pair_stride & 1)))
-            return fail(ADF_ESIZE, "bad stride or alignment of the right disparity map");
-        if (h->min_disp + h->num_disp - 1 > 32767 || -(h->min_disp + h->num_disp) + 1 < -32768)
-            return fail(ADF_EBADARG, "disparity range of the right-view matcher does not fit");
-    }
-    DeviceScope ds(h->device);
-    const int HG = (H + 3) / 4, HGP = HG + 2 * PG;
-    const int Wp = (W + XPAD + 3) / 4 * 4;                     // padded row: lanes past the image read (and discard) it
-    const size_t view = (size_t)HGP * Wp;                      // dwords per prefiltered view / per descriptor plane
-    const bool census = h->cost != ADF_BM_COST_SAD;
-    const int planes = census ? census_planes(h->cost, h->census_size) : 1;
-    const size_t image = view * (size_t)planes;                // dwords per image: sized from the handle's cost of THIS call
-    rc = h->views.reserve(2 * image * (size_t)n_pairs * sizeof(uint32_t), st, FILL_NONE);
-    if (rc) return rc;
-    uint32_t* Lt = (uint32_t*)h->views.p;
-    uint32_t* Rt = Lt + image * (size_t)n_pairs;
-
-    if (census) {
-        CensusPackArgs p;
-        p.src[0] = left; p.stride[0] = left_stride; p.pair_stride[0] = left_pair_stride;
-        p.src[1] = right; p.stride[1] = right_stride; p.pair_stride[1] = right_pair_stride;
-        p.dst = Lt; p.dst_view = image * (size_t)n_pairs; p.dst_pair = image; p.dst_plane = view;
-        p.W = W; p.Wp = Wp; p.H = H; p.HGP = HGP;
-        const dim3 grid((W + CENSUS_TILE_W - 1) / CENSUS_TILE_W, (HGP * 4 + CENSUS_TILE_H - 1) / CENSUS_TILE_H, 2 * n_pairs);
-        const bool known = census_dispatch(h->cost, h->census_size, [&](auto s) { hipLaunchKernelGGL((bm_census_pack_kernel<decltype(s)>), grid, dim3(CENSUS_THREADS), 0, st, p); });
-        if (!known) return fail(ADF_EBADARG, "census size %d is not supported", h->census_size);
-    } else {
-        PrefilterArgs p;
-        p.W = W; p.Wp = Wp; p.H = H; p.HGP = HGP; p.cap = h->cap; p.dst_pair = view;
-        dim3 pgrid((W + 255) / 256, HGP, n_pairs);
-        p.src = left; p.stride = left_stride; p.pair_stride = left_pair_stride; p.dst = Lt;
-        hipLaunchKernelGGL(bm_prefilter_kernel, pgrid, dim3(256), 0, st, p);
-        p.src = right; p.stride = right_stride; p.pair_stride = right_pair_stride; p.dst = Rt;
-        hipLaunchKernelGGL(bm_prefilter_kernel, pgrid, dim3(256), 0, st, p);
-    }
-
-    const int w2 = h->block / 2;
-    auto view_args = [&](const uint32_t* ref, const uint32_t* srch, int16_t* d, ptrdiff_t ds_, ptrdiff_t dp, const CostPlane& cp, int md, int texthr, int uniq) {
-        ViewArgs v;
-        v.Lt = ref; v.Rt = srch; v.disp = d; v.dstride = ds_; v.dpair = dp;
-        v.cost = cp.p; v.cstride = cp.stride; v.cpair = cp.pair;
-        v.mindisp = md;
+    const adf_bm* h = c.h;
+    BmPlan p;
+    p.HG = (c.H + 3) / 4; p.HGP = p.HG + 2 * PG; p.Wp = (c.W + XPAD + 3) / 4 * 4;
+    p.census = h->cost != ADF_BM_COST_SAD; p.planes = p.census ? census_planes(h->cost, h->census_size) : 1; p.w2 = h->block / 2;
+    p.plane = (size_t)p.HGP * p.Wp; p.image = p.plane * (size_t)p.planes;
+    p.views_bytes = 2 * p.image * (size_t)c.n_pairs * sizeof(uint32_t);
+    auto search = [&](int md, int texthr, int uniq) {
         const int maxd = md + h->num_disp - 1;
-        v.xs = (maxd > 0 ? maxd : 0) + w2;
-        v.xe = W - (md < 0 ? -md : 0) - w2;
-        v.texthr = texthr; v.uniq = uniq;
-        return v;
+        return BmSearch{md, (maxd > 0 ? maxd : 0) + p.w2, c.W - (md < 0 ? -md : 0) - p.w2, texthr, uniq};
     };
-    MatchArgs a;
-    a.nviews = nviews; a.t_pair = image; a.planes = planes; a.plane = view;
-    a.W = W; a.Wp = Wp; a.H = H; a.HG = HG; a.ndisp = h->num_disp; a.cap = h->cap;
     // (a census cost has no prefiltered image to sum a texture of: textureThreshold is validated and not used)
-    a.v[0] = view_args(Lt, Rt, disp_left, dl_stride, dl_pair_stride, cost_left, h->min_disp, census ? 0 : h->texthr, h->uniq);
+    p.v[0] = search(h->min_disp, p.census ? 0 : h->texthr, h->uniq);
     // the right-view matcher of createRightMatcher (disparity_filters.cpp:421-431): views swapped,
     // minDisparity = -(min_disp + num_disp) + 1, texture and uniqueness tests off
-    a.v[1] = disp_right ? view_args(Rt, Lt, disp_right, dr_stride, dr_pair_stride, cost_right, -(h->min_disp + h->num_disp) + 1, 0, 0) : a.v[0];
-    hipLaunchKernelGGL(bm_border_kernel, dim3(4, H, n_pairs * nviews), dim3(256), 0, st, a);
-    if (a.v[0].xe > a.v[0].xs || (nviews == 2 && a.v[1].xe > a.v[1].xs)) {
-        hipError_t e = launch_match_for(a, census, h->uniq > 0, w2, n_pairs, st);
+    p.v[1] = search(-(h->min_disp + h->num_disp) + 1, 0, 0);
+    return p;
+}
+
+// A checked call on device pointers: prefilter both images once (census: form their descriptor planes), then one launch
+// for the left view alone or for both views; each view with or without its cost plane.
+static int bm_run(const BmCall& c, const BmPlan& p, hipStream_t st)
+{
+    adf_bm* h = c.h;
+    const int W = c.W, H = c.H, n = c.n_pairs;
+    DeviceScope ds(h->device);
+    if (int rc = h->views.reserve(p.views_bytes, st, FILL_NONE)) return rc;
+    uint32_t* const T[2] = {(uint32_t*)h->views.p, (uint32_t*)h->views.p + p.image * (size_t)n};
+
+    if (p.census) {
+        CensusPackArgs a;
+        a.src[0] = c.left.p; a.stride[0] = c.left.stride; a.pair_stride[0] = c.left.pair;
+        a.src[1] = c.right.p; a.stride[1] = c.right.stride; a.pair_stride[1] = c.right.pair;
+        a.dst = T[0]; a.dst_view = p.image * (size_t)n; a.dst_pair = p.image; a.dst_plane = p.plane;
+        a.W = W; a.Wp = p.Wp; a.H = H; a.HGP = p.HGP;
+        const dim3 grid((W + CENSUS_TILE_W - 1) / CENSUS_TILE_W, (p.HGP * 4 + CENSUS_TILE_H - 1) / CENSUS_TILE_H, 2 * n);
+        // (adf_bm_set_cost keeps every pair that census_dispatch does not list out of the handle)
+        census_dispatch(h->cost, h->census_size, [&](auto s) { hipLaunchKernelGGL((bm_census_pack_kernel<decltype(s)>), grid, dim3(CENSUS_THREADS), 0, st, a); });
+    } else {
+        PrefilterArgs a;
+        a.W = W; a.Wp = p.Wp; a.H = H; a.HGP = p.HGP; a.cap = h->cap; a.dst_pair = p.plane;
+        const dim3 grid((W + 255) / 256, p.HGP, n);
+        a.src = c.left.p; a.stride = c.left.stride; a.pair_stride = c.left.pair; a.dst = T[0];
+        hipLaunchKernelGGL(bm_prefilter_kernel, grid, dim3(256), 0, st, a);
+        a.src = c.right.p; a.stride = c.right.stride; a.pair_stride = c.right.pair; a.dst = T[1];
+        hipLaunchKernelGGL(bm_prefilter_kernel, grid, dim3(256), 0, st, a);
+    }
+
+    MatchArgs a;
+    a.nviews = c.nviews; a.t_pair = p.image; a.planes = p.planes; a.plane = p.plane;
+    a.W = W; a.Wp = p.Wp; a.H = H; a.HG = p.HG; a.ndisp = h->num_disp; a.cap = h->cap;
+    for (int i = 0; i < 2; i++) {
+        const int v = i < c.nviews ? i : 0;                    // (one view: the second slot repeats the first)
+        const BmSearch& s = p.v[v];
+        ViewArgs& va = a.v[i];
+        va.Lt = T[v]; va.Rt = T[1 - v];                        // reference and searched image
+        va.disp = c.disp[v].p; va.dstride = c.disp[v].stride; va.dpair = c.disp[v].pair;
+        va.cost = c.cost[v].p; va.cstride = c.cost[v].stride; va.cpair = c.cost[v].pair;
+        va.mindisp = s.mindisp; va.xs = s.xs; va.xe = s.xe; va.texthr = s.texthr; va.uniq = s.uniq;
+    }
+    hipLaunchKernelGGL(bm_border_kernel, dim3(4, H, n * c.nviews), dim3(256), 0, st, a);
+    if (a.v[0].xe > a.v[0].xs || (c.nviews == 2 && a.v[1].xe > a.v[1].xs)) {
+        hipError_t e = launch_match_for(a, p.census, h->uniq > 0, p.w2, n, st);
         if (e != hipSuccess) return fail(ADF_EHIP, "%s", hipGetErrorString(e));
     }
     return launched();
+}
+
+// A checked call on host pointers: views in, map (and cost plane, when wanted) out through one staging block of the
+// handle, in which the same call runs on dense copies.
+static int bm_run_host(const BmCall& c, const BmPlan& p)
+{
+    adf_bm* h = c.h;
+    const int n = c.n_pairs;
+    DeviceScope ds(h->device);
+    const ptrdiff_t vrow = c.W, vbytes = vrow * c.H, drow = vrow * 2, dbytes = drow * c.H;
+    int rc = h->stage.reserve((size_t)(2 * vbytes + (c.with_cost ? 2 : 1) * dbytes) * n, nullptr, FILL_NONE);
+    if (rc) return rc;
+    uint8_t* dl = (uint8_t*)h->stage.p;
+    uint8_t* dr = dl + vbytes * n;
+    int16_t* dd = (int16_t*)(dr + vbytes * n);
+    int16_t* dc = dd + (size_t)c.W * c.H * n;                         // (used with a cost plane only)
+    BmCall d = c;                                                     // the call on its staged copies
+    d.device = true;
+    d.left = {dl, vrow, vbytes}; d.right = {dr, vrow, vbytes}; d.disp[0] = {dd, drow, dbytes};
+    if (c.with_cost) d.cost[0] = {dc, drow, dbytes};
+    if ((rc = copy_images(dl, vrow, vbytes, c.left.p, c.left.stride, c.left.pair, vrow, c.H, n, hipMemcpyHostToDevice, nullptr))) return rc;
+    if ((rc = copy_images(dr, vrow, vbytes, c.right.p, c.right.stride, c.right.pair, vrow, c.H, n, hipMemcpyHostToDevice, nullptr))) return rc;
+    if ((rc = bm_run(d, p, nullptr))) return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    if ((rc = copy_images(c.disp[0].p, c.disp[0].stride, c.disp[0].pair, dd, drow, dbytes, drow, c.H, n, hipMemcpyDeviceToHost, nullptr))) return rc;
+    if (c.with_cost && (rc = copy_images(c.cost[0].p, c.cost[0].stride, c.cost[0].pair, dc, drow, dbytes, drow, c.H, n, hipMemcpyDeviceToHost, nullptr))) return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return ADF_OK;
+}
+
+// Every compute entry: its record through the checks, the plan and the run.  A device entry reports an added plane's
+// fault before the call's, adf_bm_compute_cost_host after it (tests/matcher_refusals.json).
+static int bm_compute(const BmCall& c, void* stream)
+{
+    if (int rc = c.device ? bm_check_added(c) : bm_check(c)) return rc;
+    if (int rc = c.device ? bm_check(c) : bm_check_added(c)) return rc;
+    return c.device ? bm_run(c, bm_plan(c), (hipStream_t)stream) : bm_run_host(c, bm_plan(c));
 }
 
 extern "C" int adf_bm_compute_device(adf_bm_t* h, int n_pairs,
@@ -684,8 +740,9 @@ extern "C" int adf_bm_compute_device(adf_bm_t* h, int n_pairs,
                                      int16_t* disparity, ptrdiff_t disp_stride, ptrdiff_t disp_pair_stride,
                                      void* stream)
 {
-    return bm_compute_impl(h, n_pairs, left, left_stride, left_pair_stride, right, right_stride, right_pair_stride, W, H,
-                           disparity, disp_stride, disp_pair_stride, nullptr, 0, 0, NO_COST, NO_COST, (hipStream_t)stream);
+    const BmCall c{h, n_pairs, {left, left_stride, left_pair_stride}, {right, right_stride, right_pair_stride}, W, H, 1, false,
+                   {{disparity, disp_stride, disp_pair_stride}, {}}, {}, true};
+    return bm_compute(c, stream);
 }
 
 extern "C" int adf_bm_compute_cost_device(adf_bm_t* h, int n_pairs,
@@ -696,10 +753,9 @@ extern "C" int adf_bm_compute_cost_device(adf_bm_t* h, int n_pairs,
                                           int16_t* cost, ptrdiff_t cost_stride, ptrdiff_t cost_pair_stride,
                                           void* stream)
 {
-    const CostPlane c{cost, cost_stride, cost_pair_stride};
-    if (int rc = bm_cost_check(c, "the", n_pairs, W)) return rc;
-    return bm_compute_impl(h, n_pairs, left, left_stride, left_pair_stride, right, right_stride, right_pair_stride, W, H,
-                           disparity, disp_stride, disp_pair_stride, nullptr, 0, 0, c, NO_COST, (hipStream_t)stream);
+    const BmCall c{h, n_pairs, {left, left_stride, left_pair_stride}, {right, right_stride, right_pair_stride}, W, H, 1, true,
+                   {{disparity, disp_stride, disp_pair_stride}, {}}, {{cost, cost_stride, cost_pair_stride}, {}}, true};
+    return bm_compute(c, stream);
 }
 
 extern "C" int adf_bm_compute_both_device(adf_bm_t* h, int n_pairs,
@@ -710,10 +766,9 @@ extern "C" int adf_bm_compute_both_device(adf_bm_t* h, int n_pairs,
                                           int16_t* disp_right, ptrdiff_t disp_right_stride, ptrdiff_t disp_right_pair_stride,
                                           void* stream)
 {
-    if (!disp_right) return fail(ADF_EBADARG, "disp_right is NULL");
-    return bm_compute_impl(h, n_pairs, left, left_stride, left_pair_stride, right, right_stride, right_pair_stride, W, H,
-                           disp_left, disp_left_stride, disp_left_pair_stride,
-                           disp_right, disp_right_stride, disp_right_pair_stride, NO_COST, NO_COST, (hipStream_t)stream);
+    const BmCall c{h, n_pairs, {left, left_stride, left_pair_stride}, {right, right_stride, right_pair_stride}, W, H, 2, false,
+                   {{disp_left, disp_left_stride, disp_left_pair_stride}, {disp_right, disp_right_stride, disp_right_pair_stride}}, {}, true};
+    return bm_compute(c, stream);
 }
 
 extern "C" int adf_bm_compute_both_cost_device(adf_bm_t* h, int n_pairs,
@@ -726,44 +781,10 @@ extern "C" int adf_bm_compute_both_cost_device(adf_bm_t* h, int n_pairs,
                                                int16_t* cost_right, ptrdiff_t cost_right_stride, ptrdiff_t cost_right_pair_stride,
                                                void* stream)
 {
-    if (!disp_right) return fail(ADF_EBADARG, "disp_right is NULL");
-    const CostPlane cl{cost_left, cost_left_stride, cost_left_pair_stride}, cr{cost_right, cost_right_stride, cost_right_pair_stride};
-    if (int rc = bm_cost_check(cl, "the left", n_pairs, W)) return rc;
-    if (int rc = bm_cost_check(cr, "the right", n_pairs, W)) return rc;
-    return bm_compute_impl(h, n_pairs, left, left_stride, left_pair_stride, right, right_stride, right_pair_stride, W, H,
-                           disp_left, disp_left_stride, disp_left_pair_stride,
-                           disp_right, disp_right_stride, disp_right_pair_stride, cl, cr, (hipStream_t)stream);
-}
-
-// The host-pointer entries: views in, map (and cost plane, when wanted) out through one staging block of the handle.
-static int bm_compute_host_impl(adf_bm_t* h, int n_pairs,
-                                const uint8_t* left, ptrdiff_t left_stride, ptrdiff_t left_pair_stride,
-                                const uint8_t* right, ptrdiff_t right_stride, ptrdiff_t right_pair_stride,
-                                int W, int H,
-                                int16_t* disparity, ptrdiff_t disp_stride, ptrdiff_t disp_pair_stride, const CostPlane* cost)
-{
-    int rc = bm_check(h, n_pairs, left, right, disparity, W, H, left_stride, right_stride, disp_stride);
-    if (rc) return rc;
-    if (cost && (rc = bm_cost_check(*cost, "the", n_pairs, W))) return rc;
-    DeviceScope ds(h->device);
-    const size_t vbytes = (size_t)W * H, dbytes = (size_t)W * H * 2;
-    rc = h->stage.reserve((2 * vbytes + (cost ? 2 : 1) * dbytes) * (size_t)n_pairs, nullptr, FILL_NONE);
-    if (rc) return rc;
-    uint8_t* dl = (uint8_t*)h->stage.p;
-    uint8_t* dr = dl + vbytes * n_pairs;
-    int16_t* dd = (int16_t*)(dr + vbytes * n_pairs);
-    int16_t* dc = dd + (size_t)W * H * n_pairs;                       // (used with a cost plane only)
-    if ((rc = copy_images(dl, W, vbytes, left, left_stride, left_pair_stride, W, H, n_pairs, hipMemcpyHostToDevice, nullptr))) return rc;
-    if ((rc = copy_images(dr, W, vbytes, right, right_stride, right_pair_stride, W, H, n_pairs, hipMemcpyHostToDevice, nullptr))) return rc;
-    rc = cost ? adf_bm_compute_cost_device(h, n_pairs, dl, W, (ptrdiff_t)vbytes, dr, W, (ptrdiff_t)vbytes, W, H, dd, (ptrdiff_t)W * 2, (ptrdiff_t)dbytes,
-                                           dc, (ptrdiff_t)W * 2, (ptrdiff_t)dbytes, nullptr)
-              : adf_bm_compute_device(h, n_pairs, dl, W, (ptrdiff_t)vbytes, dr, W, (ptrdiff_t)vbytes, W, H, dd, (ptrdiff_t)W * 2, (ptrdiff_t)dbytes, nullptr);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    if ((rc = copy_images(disparity, disp_stride, disp_pair_stride, dd, (size_t)W * 2, dbytes, (size_t)W * 2, H, n_pairs, hipMemcpyDeviceToHost, nullptr))) return rc;
-    if (cost && (rc = copy_images(cost->p, cost->stride, cost->pair, dc, (size_t)W * 2, dbytes, (size_t)W * 2, H, n_pairs, hipMemcpyDeviceToHost, nullptr))) return rc;
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return ADF_OK;
+    const BmCall c{h, n_pairs, {left, left_stride, left_pair_stride}, {right, right_stride, right_pair_stride}, W, H, 2, true,
+                   {{disp_left, disp_left_stride, disp_left_pair_stride}, {disp_right, disp_right_stride, disp_right_pair_stride}},
+                   {{cost_left, cost_left_stride, cost_left_pair_stride}, {cost_right, cost_right_stride, cost_right_pair_stride}}, true};
+    return bm_compute(c, stream);
 }
 
 extern "C" int adf_bm_compute_host(adf_bm_t* h, int n_pairs,
@@ -772,8 +793,9 @@ extern "C" int adf_bm_compute_host(adf_bm_t* h, int n_pairs,
                                    int W, int H,
                                    int16_t* disparity, ptrdiff_t disp_stride, ptrdiff_t disp_pair_stride)
 {
-    return bm_compute_host_impl(h, n_pairs, left, left_stride, left_pair_stride, right, right_stride, right_pair_stride, W, H,
-                                disparity, disp_stride, disp_pair_stride, nullptr);
+    const BmCall c{h, n_pairs, {left, left_stride, left_pair_stride}, {right, right_stride, right_pair_stride}, W, H, 1, false,
+                   {{disparity, disp_stride, disp_pair_stride}, {}}, {}, false};
+    return bm_compute(c, nullptr);
 }
 
 extern "C" int adf_bm_compute_cost_host(adf_bm_t* h, int n_pairs,
@@ -783,7 +805,7 @@ extern "C" int adf_bm_compute_cost_host(adf_bm_t* h, int n_pairs,
                                         int16_t* disparity, ptrdiff_t disp_stride, ptrdiff_t disp_pair_stride,
                                         int16_t* cost, ptrdiff_t cost_stride, ptrdiff_t cost_pair_stride)
 {
-    const CostPlane c{cost, cost_stride, cost_pair_stride};
-    return bm_compute_host_impl(h, n_pairs, left, left_stride, left_pair_stride, right, right_stride, right_pair_stride, W, H,
-                                disparity, disp_stride, disp_pair_stride, &c);
+    const BmCall c{h, n_pairs, {left, left_stride, left_pair_stride}, {right, right_stride, right_pair_stride}, W, H, 1, true,
+                   {{disparity, disp_stride, disp_pair_stride}, {}}, {{cost, cost_stride, cost_pair_stride}, {}}, false};
+    return bm_compute(c, nullptr);
 }

@@ -571,8 +571,11 @@ hipError_t launch_cost(const CostArgs& a, int bs, int n_images, hipStream_t st)
     return hipGetLastError();
 }
 
+constexpr size_t WINNER_LDS_LIMIT = 150 * 1024;              // what the winner pass may take of a CU's 160 KiB
+
+// lds_out: the winner pass's dynamic LDS (SgbmPlan::lds_out)
 template <int DPL>
-hipError_t launch_paths(const PathArgs& a0, int mode, int n, hipStream_t st)
+hipError_t launch_paths(const PathArgs& a0, int mode, int n, size_t lds_out, hipStream_t st)
 {
     PathArgs a = a0;
     hipLaunchKernelGGL((sgbm_path_kernel<DPL, DIR_TOP>), dim3((a.w1 + 3) / 4, n), dim3(256), 0, st, a);      // from above
@@ -587,8 +590,7 @@ hipError_t launch_paths(const PathArgs& a0, int mode, int n, hipStream_t st)
         if (k == nadd - 1) hipLaunchKernelGGL((sgbm_path_kernel<DPL, DIR_ADD_OUT>), dim3((nlines + 3) / 4, n), dim3(256), 0, st, a);
         else hipLaunchKernelGGL((sgbm_path_kernel<DPL, DIR_ADD>), dim3((nlines + 3) / 4, n), dim3(256), 0, st, a);
     }
-    const size_t lds_out = ((size_t)a.w1 + (a.disp12 < 100000 ? 2 * (size_t)a.W : 0)) * 4 * sizeof(int16_t);
-    if (lds_out > 150 * 1024) return hipErrorInvalidValue;
+    if (lds_out > WINNER_LDS_LIMIT) return hipErrorInvalidValue;
     if (lds_out > 48 * 1024) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(sgbm_path_kernel<DPL, DIR_RIGHT>),
                                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_out);
@@ -699,26 +701,126 @@ extern "C" int adf_sgbm_get_device(const adf_sgbm_t* h, int* device)
     return ADF_OK;
 }
 
-static int sgbm_check(const adf_sgbm* h, int n, const void* l, const void* r, const void* d, int cn, int W, int H,
-                      ptrdiff_t ls, ptrdiff_t rs, ptrdiff_t dstr)
+// One compute call as its entry received it: planes with rows `stride`, pairs `pair` bytes apart; device: device pointers
+// that the kernels index (the host entry's are copied by bytes into a dense staging block).
+template <class T> struct Plane { T* p; ptrdiff_t stride, pair; };
+struct SgbmCall { adf_sgbm* h; int n_pairs; Plane<const uint8_t> left, right; int cn, W, H; Plane<int16_t> disp; bool device; };
+
+static int sgbm_block(const adf_sgbm* h) { return h->block > 0 ? h->block : 5; }
+// dynamic LDS of the winner pass: per wave a row of `cols` results and, with the matcher's own left-right check, two rows of the image's width
+static size_t sgbm_winner_lds(const adf_sgbm* h, int cols, int W) { return ((size_t)cols + (h->disp12 < 100000 ? 2 * (size_t)W : 0)) * 4 * sizeof(int16_t); }
+
+static int sgbm_check(const SgbmCall& c)
 {
+    const adf_sgbm* h = c.h;
+    const int cn = c.cn, W = c.W, H = c.H;
     if (!h) return fail(ADF_EBADARG, "handle is NULL");
-    if (n <= 0 || !l || !r || !d) return fail(ADF_EBADARG, "views and disparity must be non-NULL, n_pairs positive");
+    if (c.n_pairs <= 0 || !c.left.p || !c.right.p || !c.disp.p) return fail(ADF_EBADARG, "views and disparity must be non-NULL, n_pairs positive");
     if (cn != 1 && cn != 3) return fail(ADF_EBADARG, "views must be CV_8UC1 or CV_8UC3");
     if (h->cost != ADF_SGBM_COST_BT && cn != 1) return fail(ADF_EBADARG, "a census cost takes CV_8UC1 views (descriptor.cpp:58)");
-    if (W <= 0 || H <= 0 || ls < (ptrdiff_t)W * cn || rs < (ptrdiff_t)W * cn || dstr < (ptrdiff_t)W * 2) return fail(ADF_ESIZE, "bad size or stride");
-    if ((dstr & 1) || (reinterpret_cast<uintptr_t>(d) & 1)) return fail(ADF_ESIZE, "disparity rows must be 2-byte aligned");
+    if (W <= 0 || H <= 0 || c.left.stride < (ptrdiff_t)W * cn || c.right.stride < (ptrdiff_t)W * cn || c.disp.stride < (ptrdiff_t)W * 2)
+        return fail(ADF_ESIZE, "bad size or stride");
+    if ((c.disp.stride & 1) || (reinterpret_cast<uintptr_t>(c.disp.p) & 1)) return fail(ADF_ESIZE, "disparity rows must be 2-byte aligned");
     if (h->mode != ADF_SGBM_MODE_3WAY && h->mode != ADF_SGBM_MODE_SGBM && h->mode != ADF_SGBM_MODE_HH)
         return fail(ADF_EBADARG, "mode must be StereoSGBM::MODE_SGBM, MODE_HH or MODE_SGBM_3WAY");
     if (h->num_disp <= 0 || h->num_disp % 16) return fail(ADF_EBADARG, "numDisparities must be positive and divisible by 16");
     if (h->num_disp > 512) return fail(ADF_EBADARG, "numDisparities above 512 is not supported");
-    const int bs = h->block > 0 ? h->block : 5;
-    if (bs % 2 == 0 || bs > 11) return fail(ADF_EBADARG, "blockSize must be odd and at most 11");
+    if (sgbm_block(h) % 2 == 0 || sgbm_block(h) > 11) return fail(ADF_EBADARG, "blockSize must be odd and at most 11");
     if (h->min_disp < -2047 || h->min_disp + h->num_disp > 2047) return fail(ADF_EBADARG, "disparity range does not fit CV_16S with 4 fractional bits");
     if (h->P1 < 0 || h->P2 < 0 || h->P1 > 8000 || h->P2 > 16000) return fail(ADF_EBADARG, "P1 / P2 out of range");
-    if (h->disp12 < 100000 && (size_t)(W + 2 * (size_t)W) * 8 > 150 * 1024)
+    // (whatever the disparity range leaves of a row: the limit is stated for the whole width)
+    if (h->disp12 < 100000 && sgbm_winner_lds(h, W, W) > WINNER_LDS_LIMIT)
         return fail(ADF_ESIZE, "the matcher's own left-right check (disp12MaxDiff) supports images up to 6400 columns");
+    if (c.device && c.n_pairs > 1 && (c.disp.pair & 1)) return fail(ADF_ESIZE, "disparity maps must be 2-byte aligned");
     return ADF_OK;
+}
+
+// What a checked call runs with: a pure function of the handle's settings and the call's sizes.
+struct SgbmPlan {
+    int D, minD, bs, P1, P2, ur, ftzero, minX1, w1; int16_t invalid; bool census;   // the effective parameters; matched columns [minX1, minX1 + w1)
+    // per image in flight, 256-byte aligned: a signal plane (12 * cn bytes per pixel; census: a descriptor plane, 8), a cost volume, the raw map
+    size_t rec_bytes, vol_bytes, raw_bytes;
+    int chunk;                                  // images in flight: what ws_limit holds of the call's pairs
+    size_t rec1, rec2, C, S, L, raw, ws_bytes;  // h->ws: byte offsets of its regions, `chunk` parts each (L: the last accumulating path's own volume)
+    int dpl; size_t lds_out;                    // disparities per lane of the path kernels; the winner pass's dynamic LDS
+};
+
+static SgbmPlan sgbm_plan(const SgbmCall& c)
+{
+    const adf_sgbm* h = c.h;
+    const size_t px = (size_t)c.W * c.H;
+    SgbmPlan p;
+    p.D = h->num_disp; p.minD = h->min_disp; p.bs = sgbm_block(h);
+    p.P1 = h->P1 > 0 ? h->P1 : 2; p.P2 = std::max(h->P2 > 0 ? h->P2 : 5, p.P1 + 1);
+    p.ur = h->uniq >= 0 ? h->uniq : 10; p.ftzero = std::max(h->cap, 15) | 1;
+    p.minX1 = std::max(p.minD + p.D, 0); p.w1 = (c.W + std::min(p.minD, 0)) - p.minX1;
+    p.invalid = (int16_t)((p.minD - 1) * SG_DISP_SCALE);
+    p.census = h->cost != ADF_SGBM_COST_BT;
+    p.rec_bytes = pad_to(px * (p.census ? 8 : c.cn * 3 * 4), 256);
+    p.vol_bytes = pad_to(p.w1 > 0 ? (size_t)c.H * p.w1 * p.D * 2 : 0, 256);
+    p.raw_bytes = pad_to(px * 2, 256);
+    p.chunk = (int)std::min<size_t>(std::max<size_t>(h->ws_limit / (2 * p.rec_bytes + 3 * p.vol_bytes + p.raw_bytes), 1), c.n_pairs);
+    p.ws_bytes = 0;
+    auto region = [&](size_t part) { const size_t at = p.ws_bytes; p.ws_bytes += part * p.chunk; return at; };
+    p.rec1 = region(p.rec_bytes); p.rec2 = region(p.rec_bytes); p.C = region(p.vol_bytes); p.S = region(p.vol_bytes);
+    p.L = region(p.vol_bytes); p.raw = region(p.raw_bytes);
+    p.dpl = p.D <= 64 ? 1 : p.D <= 128 ? 2 : p.D <= 256 ? 4 : 8;
+    p.lds_out = sgbm_winner_lds(h, p.w1, c.W);
+    return p;
+}
+
+// Images [first, first + n) of a checked call on device pointers, n <= p.chunk, through the workspace's regions.
+static int sgbm_run_chunk(const SgbmCall& c, const SgbmPlan& p, int first, int n, hipStream_t st)
+{
+    const adf_sgbm* h = c.h;
+    const int W = c.W, H = c.H;
+    char* ws = (char*)h->ws.p;
+    uint32_t* rec1 = (uint32_t*)(ws + p.rec1); uint32_t* rec2 = (uint32_t*)(ws + p.rec2); int16_t* raw = (int16_t*)(ws + p.raw);
+    const size_t rec_pair = p.rec_bytes / 4, volp = p.vol_bytes / 2, raw_el = p.raw_bytes / 2;   // dwords, int16 elements
+    const uint8_t* L = c.left.p + (ptrdiff_t)first * c.left.pair;
+    const uint8_t* R = c.right.p + (ptrdiff_t)first * c.right.pair;
+    int16_t* out = (int16_t*)((char*)c.disp.p + (ptrdiff_t)first * c.disp.pair);
+    const dim3 per_row((W + 255) / 256, H, n);
+    FillArgs fa{raw, W, (ptrdiff_t)raw_el, W, H, p.invalid};
+    hipLaunchKernelGGL(sgbm_fill_kernel, per_row, dim3(256), 0, st, fa);
+    if (p.w1 > 0) {
+        if (p.census) {                                    // preFilterCap plays no part in this cost
+            int rc;
+            if ((rc = census_run(n, L, c.left.stride, c.left.pair, W, H, h->cost, h->census_size, (uint64_t*)rec1, (ptrdiff_t)W * 8, (ptrdiff_t)p.rec_bytes, st))) return rc;
+            if ((rc = census_run(n, R, c.right.stride, c.right.pair, W, H, h->cost, h->census_size, (uint64_t*)rec2, (ptrdiff_t)W * 8, (ptrdiff_t)p.rec_bytes, st))) return rc;
+        } else {
+            SignalArgs sa{L, c.left.stride, c.left.pair, c.cn, W, H, p.ftzero, rec1, rec_pair};
+            hipLaunchKernelGGL(sgbm_signals_kernel, per_row, dim3(256), 0, st, sa);
+            sa.img = R; sa.stride = c.right.stride; sa.pair_stride = c.right.pair; sa.rec = rec2;
+            hipLaunchKernelGGL(sgbm_signals_kernel, per_row, dim3(256), 0, st, sa);
+        }
+        // bands: the bs-1 warm-up rows are paid per band; enough workgroups to fill the chip when the chunk's images are small
+        int rpb = 128;
+        while (rpb > 16 && (size_t)((H + rpb - 1) / rpb) * ((p.w1 + 61) / 62) * ((p.D + 63) / 64) * n < 2048) rpb >>= 1;
+        CostArgs ca{rec1, rec2, rec_pair, (int16_t*)(ws + p.C), volp, W, H, p.D, p.minD, p.minX1, p.w1, rpb};
+        if ((size_t)((H + rpb - 1) / rpb) * n > 65535) return fail(ADF_ESIZE, "too many images per call for the cost kernel's grid");
+        hipError_t e = p.census ? launch_cost<CensusCost>(ca, p.bs, n, st)
+                     : c.cn == 1 ? launch_cost<BtCost<1>>(ca, p.bs, n, st) : launch_cost<BtCost<3>>(ca, p.bs, n, st);
+        if (e != hipSuccess) return fail(ADF_EHIP, "%s", hipGetErrorString(e));
+        PathArgs pa{ca.C, (int16_t*)(ws + p.S), (int16_t*)(ws + p.L), volp, W, H, p.D, p.minD, p.minX1, p.w1, p.P1, p.P2, p.ur,
+                    raw, (ptrdiff_t)W, (ptrdiff_t)raw_el, 0, 0, h->disp12};
+        e = p.dpl == 1 ? launch_paths<1>(pa, h->mode, n, p.lds_out, st) : p.dpl == 2 ? launch_paths<2>(pa, h->mode, n, p.lds_out, st)
+          : p.dpl == 4 ? launch_paths<4>(pa, h->mode, n, p.lds_out, st) : launch_paths<8>(pa, h->mode, n, p.lds_out, st);
+        if (e != hipSuccess) return fail(ADF_EHIP, "%s", hipGetErrorString(e));
+    }
+    MedianArgs ma{raw, (ptrdiff_t)W, (ptrdiff_t)raw_el, out, c.disp.stride / 2, c.disp.pair / 2, W, H};
+    hipLaunchKernelGGL(sgbm_median_kernel, per_row, dim3(256), 0, st, ma);
+    return ADF_OK;
+}
+
+// A checked call on device pointers: the workspace, then chunk after chunk.
+static int sgbm_run(const SgbmCall& c, const SgbmPlan& p, hipStream_t st)
+{
+    DeviceScope ds(c.h->device);
+    if (int rc = c.h->ws.reserve(p.ws_bytes, st, FILL_NONE)) return rc;
+    for (int first = 0; first < c.n_pairs; first += p.chunk)
+        if (int rc = sgbm_run_chunk(c, p, first, std::min(p.chunk, c.n_pairs - first), st)) return rc;
+    return launched();
 }
 
 extern "C" int adf_sgbm_compute_device(adf_sgbm_t* h, int n_pairs,
@@ -728,101 +830,35 @@ extern "C" int adf_sgbm_compute_device(adf_sgbm_t* h, int n_pairs,
                                        int16_t* disparity, ptrdiff_t disp_stride, ptrdiff_t disp_pair_stride,
                                        void* stream)
 {
-    int rc = sgbm_check(h, n_pairs, left, right, disparity, channels, W, H, left_stride, right_stride, disp_stride);
-    if (rc) return rc;
-    if (n_pairs > 1 && (disp_pair_stride & 1)) return fail(ADF_ESIZE, "disparity maps must be 2-byte aligned");
-    hipStream_t st = (hipStream_t)stream;
-    DeviceScope ds(h->device);
-    const int cn = channels, D = h->num_disp, minD = h->min_disp, maxD = minD + D;
-    const int bs = h->block > 0 ? h->block : 5;
-    const int P1 = h->P1 > 0 ? h->P1 : 2, P2 = std::max(h->P2 > 0 ? h->P2 : 5, P1 + 1);
-    const int ur = h->uniq >= 0 ? h->uniq : 10;
-    const int ftzero = std::max(h->cap, 15) | 1;
-    const int minX1 = std::max(maxD, 0), w1 = (W + std::min(minD, 0)) - minX1;
-    const int16_t invalid = (int16_t)((minD - 1) * SG_DISP_SCALE);
-
-    // workspace per image in flight: two signal planes (12 * cn bytes per pixel) or, with a census cost, two descriptor
-    // planes (8), the C and S volumes, the raw map (every part 256-byte aligned)
-    const bool census = h->cost != ADF_SGBM_COST_BT;
-    const size_t rec_bytes = pad_to((size_t)W * H * (census ? 8 : cn * 3 * 4), 256);
-    const size_t rec_pair = rec_bytes / 4;                                            // dwords
-    const size_t vol_bytes = pad_to(w1 > 0 ? (size_t)H * w1 * D * 2 : 0, 256);
-    const size_t volp = vol_bytes / 2;                                                // int16 elements
-    const size_t raw_bytes = pad_to((size_t)W * H * 2, 256);
-    const size_t raw_el = raw_bytes / 2;
-    const size_t per_img = 2 * rec_bytes + 3 * vol_bytes + raw_bytes;     // C, S and the last accumulating path's own volume
-    int chunk = (int)(h->ws_limit / per_img);
-    if (chunk < 1) chunk = 1;
-    if (chunk > n_pairs) chunk = n_pairs;
-    rc = h->ws.reserve(per_img * (size_t)chunk, st, FILL_NONE);
-    if (rc) return rc;
-    char* wsb = (char*)h->ws.p;
-    uint32_t* rec1 = (uint32_t*)wsb;
-    uint32_t* rec2 = (uint32_t*)(wsb + rec_bytes * chunk);
-    int16_t* Cv = (int16_t*)(wsb + 2 * rec_bytes * chunk);
-    int16_t* Sv = (int16_t*)(wsb + 2 * rec_bytes * chunk + vol_bytes * chunk);
-    int16_t* Lv = (int16_t*)(wsb + 2 * rec_bytes * chunk + 2 * vol_bytes * chunk);
-    int16_t* raw = (int16_t*)(wsb + 2 * rec_bytes * chunk + 3 * vol_bytes * chunk);
-
-    for (int first = 0; first < n_pairs; first += chunk) {
-        const int n = std::min(chunk, n_pairs - first);
-        const uint8_t* L = left + (ptrdiff_t)first * left_pair_stride;
-        const uint8_t* R = right + (ptrdiff_t)first * right_pair_stride;
-        int16_t* out = (int16_t*)((char*)disparity + (ptrdiff_t)first * disp_pair_stride);
-        FillArgs fa{raw, W, (ptrdiff_t)raw_el, W, H, invalid};
-        hipLaunchKernelGGL(sgbm_fill_kernel, dim3((W + 255) / 256, H, n), dim3(256), 0, st, fa);
-        if (w1 > 0) {
-            if (census) {                                      // preFilterCap plays no part in this cost
-                if ((rc = census_run(n, L, left_stride, left_pair_stride, W, H, h->cost, h->census_size, (uint64_t*)rec1, (ptrdiff_t)W * 8, (ptrdiff_t)rec_bytes, st))) return rc;
-                if ((rc = census_run(n, R, right_stride, right_pair_stride, W, H, h->cost, h->census_size, (uint64_t*)rec2, (ptrdiff_t)W * 8, (ptrdiff_t)rec_bytes, st))) return rc;
-            } else {
-                SignalArgs sa{L, left_stride, left_pair_stride, cn, W, H, ftzero, rec1, rec_pair};
-                hipLaunchKernelGGL(sgbm_signals_kernel, dim3((W + 255) / 256, H, n), dim3(256), 0, st, sa);
-                sa.img = R; sa.stride = right_stride; sa.pair_stride = right_pair_stride; sa.rec = rec2;
-                hipLaunchKernelGGL(sgbm_signals_kernel, dim3((W + 255) / 256, H, n), dim3(256), 0, st, sa);
-            }
-            CostArgs ca{rec1, rec2, rec_pair, Cv, volp, W, H, D, minD, minX1, w1, 0};
-            // bands: the bs-1 warm-up rows are paid per band; enough workgroups to fill the chip when the image is small
-            int rpb = 128;
-            while (rpb > 16 && (size_t)((H + rpb - 1) / rpb) * ((w1 + 61) / 62) * ((D + 63) / 64) * n < 2048) rpb >>= 1;
-            ca.rows_per_band = rpb;
-            if ((size_t)((H + rpb - 1) / rpb) * n > 65535) return fail(ADF_ESIZE, "too many images per call for the cost kernel's grid");
-            hipError_t e = census ? launch_cost<CensusCost>(ca, bs, n, st)
-                         : cn == 1 ? launch_cost<BtCost<1>>(ca, bs, n, st) : launch_cost<BtCost<3>>(ca, bs, n, st);
-            if (e != hipSuccess) return fail(ADF_EHIP, "%s", hipGetErrorString(e));
-            PathArgs pa{Cv, Sv, Lv, volp, W, H, D, minD, minX1, w1, P1, P2, ur, raw, (ptrdiff_t)W, (ptrdiff_t)raw_el, 0, 0, h->disp12};
-            e = D <= 64 ? launch_paths<1>(pa, h->mode, n, st) : D <= 128 ? launch_paths<2>(pa, h->mode, n, st)
-              : D <= 256 ? launch_paths<4>(pa, h->mode, n, st) : launch_paths<8>(pa, h->mode, n, st);
-            if (e != hipSuccess) return fail(ADF_EHIP, "%s", hipGetErrorString(e));
-        }
-        MedianArgs ma{raw, (ptrdiff_t)W, (ptrdiff_t)raw_el, out, disp_stride / 2, disp_pair_stride / 2, W, H};
-        hipLaunchKernelGGL(sgbm_median_kernel, dim3((W + 255) / 256, H, n), dim3(256), 0, st, ma);
-    }
-    return launched();
+    const SgbmCall c{h, n_pairs, {left, left_stride, left_pair_stride}, {right, right_stride, right_pair_stride}, channels, W, H,
+                     {disparity, disp_stride, disp_pair_stride}, true};
+    if (int rc = sgbm_check(c)) return rc;
+    return sgbm_run(c, sgbm_plan(c), (hipStream_t)stream);
 }
 
+// The host entry: views in, map out through one staging block of the handle, in which the same call runs on dense copies.
 extern "C" int adf_sgbm_compute_host(adf_sgbm_t* h, int n_pairs,
                                      const uint8_t* left, ptrdiff_t left_stride, ptrdiff_t left_pair_stride,
                                      const uint8_t* right, ptrdiff_t right_stride, ptrdiff_t right_pair_stride,
                                      int channels, int W, int H,
                                      int16_t* disparity, ptrdiff_t disp_stride, ptrdiff_t disp_pair_stride)
 {
-    int rc = sgbm_check(h, n_pairs, left, right, disparity, channels, W, H, left_stride, right_stride, disp_stride);
+    const SgbmCall c{h, n_pairs, {left, left_stride, left_pair_stride}, {right, right_stride, right_pair_stride}, channels, W, H,
+                     {disparity, disp_stride, disp_pair_stride}, false};
+    int rc = sgbm_check(c);
     if (rc) return rc;
     DeviceScope ds(h->device);
-    const size_t vrow = (size_t)W * channels, vbytes = vrow * H, dbytes = (size_t)W * H * 2;
-    rc = h->stage.reserve((2 * vbytes + dbytes) * (size_t)n_pairs + 512, nullptr, FILL_NONE);
-    if (rc) return rc;
+    const ptrdiff_t vrow = (ptrdiff_t)W * channels, vbytes = vrow * H, drow = (ptrdiff_t)W * 2, dbytes = drow * H;
+    if ((rc = h->stage.reserve((size_t)(2 * vbytes + dbytes) * n_pairs + 512, nullptr, FILL_NONE))) return rc;
     uint8_t* dl = (uint8_t*)h->stage.p;
     uint8_t* dr = dl + vbytes * n_pairs;
     int16_t* dd = (int16_t*)pad_to((uintptr_t)(dr + vbytes * n_pairs), 256);
+    const SgbmCall d{h, n_pairs, {dl, vrow, vbytes}, {dr, vrow, vbytes}, channels, W, H, {dd, drow, dbytes}, true};   // the call, staged
     if ((rc = copy_images(dl, vrow, vbytes, left, left_stride, left_pair_stride, vrow, H, n_pairs, hipMemcpyHostToDevice, nullptr))) return rc;
     if ((rc = copy_images(dr, vrow, vbytes, right, right_stride, right_pair_stride, vrow, H, n_pairs, hipMemcpyHostToDevice, nullptr))) return rc;
-    rc = adf_sgbm_compute_device(h, n_pairs, dl, (ptrdiff_t)vrow, (ptrdiff_t)vbytes, dr, (ptrdiff_t)vrow, (ptrdiff_t)vbytes, channels, W, H,
-                                 dd, (ptrdiff_t)W * 2, (ptrdiff_t)dbytes, nullptr);
-    if (rc) return rc;
+    if ((rc = sgbm_run(d, sgbm_plan(d), nullptr))) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
-    if ((rc = copy_images(disparity, disp_stride, disp_pair_stride, dd, (size_t)W * 2, dbytes, (size_t)W * 2, H, n_pairs, hipMemcpyDeviceToHost, nullptr))) return rc;
+    if ((rc = copy_images(disparity, disp_stride, disp_pair_stride, dd, drow, dbytes, drow, H, n_pairs, hipMemcpyDeviceToHost, nullptr))) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
     return ADF_OK;
 }

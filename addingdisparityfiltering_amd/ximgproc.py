@@ -139,12 +139,15 @@ _entries = {}   # base name -> (host function, device function), resolved on fir
 def _call(name, img, args):
     """THE host/device fork: `name`_device(*args, stream) for an image held by a CUDA tensor (torch's current stream on
     its device), `name`_host(*args) otherwise.  Pointers go as plain integers (None = null): the prototypes in _lib.py
-    say void*, so no ctypes object is built per argument."""
+    say void*, so no ctypes object is built per argument.  A device-only entry has no host function: host arrays are
+    refused (its caller words the refusal first)."""
     pair = _entries.get(name)
     if pair is None:
-        pair = _entries[name] = (getattr(_lib.lib(), name + "_host"), getattr(_lib.lib(), name + "_device"))
+        pair = _entries[name] = (getattr(_lib.lib(), name + "_host", None), getattr(_lib.lib(), name + "_device"))
     if img.device:
         _lib.check(pair[1](*args, _stream_of(img)))
+    elif pair[0] is None:
+        raise AdfError(_lib.ADF_EBADARG, "%s takes device tensors only" % name)
     else:
         _lib.check(pair[0](*args))
 
@@ -379,6 +382,11 @@ def _accessors(*names):
     return add
 
 
+def _triple(X):
+    """A plane's three arguments of a C entry: pointer, row stride, pair stride."""
+    return X.ptr, X.stride, X.pair_stride
+
+
 @_accessors("minDisparity", "numDisparities", "blockSize", "disp12MaxDiff", "speckleWindowSize", "speckleRange", "uniquenessRatio")
 class StereoMatcher(_Handle):
     """The parameters every matcher has, and the part of compute() both have in common.  A subclass names its C entry
@@ -391,29 +399,6 @@ class StereoMatcher(_Handle):
         self.disp12MaxDiff, self.speckleWindowSize, self.uniquenessRatio = -1, 0, 10
         self.speckleRange = 0       # read by computeFull only: compute() runs no speckle filter
 
-    def _views(self, left, right, device_only=None):
-        """(L, R, batched): both views described and equal in size; `device_only`: the refusal of host arrays."""
-        nd = len(left.shape)
-        color = 3 in self._channels and nd in (3, 4) and left.shape[-1] == 3   # (H,W,3) / (N,H,W,3); a batch of 3-pixel-wide gray images is not a case
-        batched = nd == (4 if color else 3)
-        L = _Image(left, np.uint8, "left", batched, self._channels)
-        R = _Image(right, np.uint8, "right", batched, self._channels)
-        if device_only and not (L.device and R.device):
-            raise AdfError(_lib.ADF_EBADARG, device_only)
-        if (L.n, L.h, L.w, L.c) != (R.n, R.h, R.w, R.c):
-            raise AdfError(_lib.ADF_ESIZE, "All the images must have the same size")
-        return L, R, batched
-
-    @staticmethod
-    def _outputs(maps, names, L, batched, mismatch):
-        """(maps, their descriptors): the caller's maps, new ones where None, of the views' size and on their side."""
-        maps = [_out_like(L, batched, np.int16) if m is None else m for m in maps]
-        descs = [_Image(m, np.int16, what, batched) for m, what in zip(maps, names)]
-        for D in descs:
-            if (D.n, D.h, D.w) != (L.n, L.h, L.w) or D.device != L.device:
-                raise AdfError(_lib.ADF_ESIZE, mismatch)
-        return maps, descs
-
     def compute(self, left, right, disparity=None):
         """StereoMatcher::compute: 8-bit views (H,W) or a batch (N,H,W) -> CV_16SC1 disparity*16, rejected pixels
         (minDisparity-1)*16.  torch CUDA tensors are matched where they are, asynchronously on torch's current stream;
@@ -425,15 +410,44 @@ class StereoMatcher(_Handle):
                                              "use filterSpeckles on the result")
         return self._match(left, right, disparity)
 
-    def _match(self, left, right, disparity):
-        """compute() past its refusals: the match alone, whatever the speckle settings say (computeFull runs them)."""
-        L, R, batched = self._views(left, right)
+    def _views(self, left, right, device_only=None):
+        """(L, R, batched): both views described, equal in size and on the same side; `device_only`: the refusal of host arrays."""
+        nd = len(left.shape)
+        color = 3 in self._channels and nd in (3, 4) and left.shape[-1] == 3   # (H,W,3) / (N,H,W,3); a batch of 3-pixel-wide gray images is not a case
+        batched = nd == (4 if color else 3)
+        L = _Image(left, np.uint8, "left", batched, self._channels)
+        R = _Image(right, np.uint8, "right", batched, self._channels)
+        if device_only and not (L.device and R.device):
+            raise AdfError(_lib.ADF_EBADARG, device_only)
+        if (L.n, L.h, L.w, L.c) != (R.n, R.h, R.w, R.c):
+            raise AdfError(_lib.ADF_ESIZE, "All the images must have the same size")
         if L.device != R.device:
             raise AdfError(_lib.ADF_EBADARG, "left and right must live on the same side (host or device)")
-        (disparity,), (D,) = self._outputs((disparity,), ("disparity",), L, batched, "disparity must match the views")
-        self._prepare((L, R, D))
-        _call(self._entry, L, self._args(L, R, D))
-        return disparity
+        return L, R, batched
+
+    def _run(self, entry, views, planes, mismatch, instead=None):
+        """A compute call past its views (_views): the output planes {name: the caller's or None for a new one} of the
+        views' size and on their side, the handle prepared, `entry` through _call -- or, where the matcher cannot use
+        `entry`, `instead(*planes)`.  Returns the planes."""
+        L, R, batched = views
+        maps = [_out_like(L, batched, np.int16) if m is None else m for m in planes.values()]
+        descs = [_Image(m, np.int16, what, batched) for m, what in zip(maps, planes)]
+        for D in descs:
+            if (D.n, D.h, D.w) != (L.n, L.h, L.w) or D.device != L.device:
+                raise AdfError(_lib.ADF_ESIZE, mismatch)
+        if instead is not None:
+            instead(*maps)
+            return tuple(maps)
+        self._prepare((L, R, *descs))
+        args = self._args(L, R, descs[0])
+        for D in descs[1:]:
+            args += _triple(D)
+        _call(entry, L, args)
+        return tuple(maps)
+
+    def _match(self, left, right, disparity):
+        """compute() past its refusals: the match alone, whatever the speckle settings say (computeFull runs them)."""
+        return self._run(self._entry, self._views(left, right), {"disparity": disparity}, "disparity must match the views")[0]
 
 
 @_accessors("textureThreshold", "preFilterCap", "costType", "censusSize")
@@ -483,7 +497,7 @@ class StereoBM(StereoMatcher):
 
     def _args(self, L, R, D):
         return (self._h, L.n, L.ptr, L.stride, L.pair_stride, R.ptr, R.stride, R.pair_stride, L.w, L.h,
-                D.ptr, D.stride, D.pair_stride)
+                D.ptr, D.stride, D.pair_stride)     # (spelled out: this runs once per call)
 
     def computeWithCost(self, left, right, disparity=None, cost=None):
         """Extension: compute()'s map AND the CV_16S plane of the winning disparity's aggregated cost, the pair calib3d's
@@ -491,33 +505,20 @@ class StereoBM(StereoMatcher):
         byte; the plane holds (int16)cost where the map holds a disparity and 0 where it holds (minDisparity-1)*16.  The
         match alone: disp12MaxDiff and the speckle settings are not applied here (computeFull does).  Host arrays take the
         host entry; device tensors run on torch's current stream.  Returns (disparity, cost)."""
-        L, R, batched = self._views(left, right)
-        if L.device != R.device:
-            raise AdfError(_lib.ADF_EBADARG, "left and right must live on the same side (host or device)")
-        (disparity, cost), (D, K) = self._outputs((disparity, cost), ("disparity", "cost"), L, batched,
-                                                  "disparity and cost must match the views")
-        self._prepare((L, R, D, K))
-        _call("adf_bm_compute_cost", L, self._args(L, R, D) + (K.ptr, K.stride, K.pair_stride))
-        return disparity, cost
+        return self._run("adf_bm_compute_cost", self._views(left, right), {"disparity": disparity, "cost": cost},
+                         "disparity and cost must match the views")
 
     def computeBothWithCost(self, left, right, disparity_left=None, disparity_right=None, cost_left=None, cost_right=None):
         """Extension: computeBoth's two maps and the cost plane of each search, identical to `self.computeWithCost(left,
         right)` and `createRightMatcher(self).computeWithCost(right, left)`.  Device tensors only; the same fallback to
         two separate computes as computeBoth when a SAD matcher's preFilterCap is not 31.  Returns (disparity_left,
         disparity_right, cost_left, cost_right)."""
-        L, R, batched = self._views(left, right, "computeBothWithCost takes device tensors; use two computeWithCost() calls on the host")
-        outs, (DL, DR, KL, KR) = self._outputs(
-            (disparity_left, disparity_right, cost_left, cost_right), ("disparity_left", "disparity_right", "cost_left", "cost_right"),
-            L, batched, "disparity maps and cost planes must match the views")
-        if self.preFilterCap != 31 and self.costType == BM_COST_SAD:
-            self._right_matcher().computeWithCost(right, left, outs[1], outs[3])
-            self.computeWithCost(left, right, outs[0], outs[2])
-            return tuple(outs)
-        self._prepare((L, R, DL, DR, KL, KR))
-        _lib.check(_lib.lib().adf_bm_compute_both_cost_device(
-            *self._args(L, R, DL), DR.ptr, DR.stride, DR.pair_stride, KL.ptr, KL.stride, KL.pair_stride,
-            KR.ptr, KR.stride, KR.pair_stride, _stream_of(L)))
-        return tuple(outs)
+        views = self._views(left, right, "computeBothWithCost takes device tensors; use two computeWithCost() calls on the host")
+        rm = self._unshared_right_matcher()
+        return self._run("adf_bm_compute_both_cost", views,
+                         {"disparity_left": disparity_left, "disparity_right": disparity_right, "cost_left": cost_left, "cost_right": cost_right},
+                         "disparity maps and cost planes must match the views",
+                         rm and (lambda dl, dr, kl, kr: (rm.computeWithCost(right, left, dr, kr), self.computeWithCost(left, right, dl, kl))))
 
     def computeFull(self, left, right, disparity=None):
         """Extension: what calib3d's StereoBM::compute does with the matcher's own settings, under a new name so that
@@ -531,8 +532,11 @@ class StereoBM(StereoMatcher):
             filterSpeckles(disparity, (int(self.minDisparity) - 1) * 16, self.speckleWindowSize, self.speckleRange)
         return disparity
 
-    def _right_matcher(self):
-        """createRightMatcher(self) on a matcher (and handle) this one keeps for the two-launch fallback."""
+    def _unshared_right_matcher(self):
+        """None where one launch serves both views (computeBoth's docstring); for a SAD matcher whose preFilterCap is not
+        31, createRightMatcher(self) on a matcher (and handle) this one keeps for the two-launch fallback."""
+        if self.preFilterCap == 31 or self.costType != BM_COST_SAD:
+            return None
         if getattr(self, "_right", None) is None:
             self._right = StereoBM(1, 5)
         rm = createRightMatcher(self)
@@ -551,19 +555,13 @@ class StereoBM(StereoMatcher):
         too; with any other cap the two maps are produced by the two separate computes (same results, two launches).
         With a census cost there is no prefilter: the views share their descriptor planes whatever the cap is, and the
         single launch is always taken."""
-        L, R, batched = self._views(left, right, "computeBoth takes device tensors; use two compute() calls on the host")
+        views = self._views(left, right, "computeBoth takes device tensors; use two compute() calls on the host")
         if self._left_right_check_on() or self.speckleWindowSize > 0:
             raise AdfError(_lib.ADF_EBADARG, "the matcher's own left-right check and speckle filter are not implemented")
-        (disparity_left, disparity_right), (DL, DR) = self._outputs(
-            (disparity_left, disparity_right), ("disparity_left", "disparity_right"), L, batched, "disparity maps must match the views")
-        if self.preFilterCap != 31 and self.costType == BM_COST_SAD:
-            right_matcher = self._right_matcher()
-            self.compute(left, right, disparity_left)
-            right_matcher.compute(right, left, disparity_right)
-            return disparity_left, disparity_right
-        self._prepare((L, R, DL, DR))
-        _lib.check(_lib.lib().adf_bm_compute_both_device(*self._args(L, R, DL), DR.ptr, DR.stride, DR.pair_stride, _stream_of(L)))
-        return disparity_left, disparity_right
+        rm = self._unshared_right_matcher()
+        return self._run("adf_bm_compute_both", views, {"disparity_left": disparity_left, "disparity_right": disparity_right},
+                         "disparity maps must match the views",
+                         rm and (lambda dl, dr: (self.compute(left, right, dl), rm.compute(right, left, dr))))
 
 
 @_accessors("P1", "P2", "mode", "preFilterCap", "costType", "censusSize")
@@ -630,7 +628,7 @@ class StereoSGBM(StereoMatcher):
 
     def _args(self, L, R, D):
         return (self._h, L.n, L.ptr, L.stride, L.pair_stride, R.ptr, R.stride, R.pair_stride, L.c, L.w, L.h,
-                D.ptr, D.stride, D.pair_stride)
+                D.ptr, D.stride, D.pair_stride)     # (spelled out: this runs once per call)
 
 
 _INT32_MAX = 2 ** 31 - 1

@@ -629,12 +629,7 @@ public:
         check_views(left, right);
         if ((disp12_ >= 0 && disp12_ < 1000000) || speckle_window_ > 0)          // the filter factory switches both off (DF.cpp:389-390)
             throw Exception(ADF_EBADARG, "the matcher's own left-right check and speckle filter are not implemented");
-        push_params();
-        Mat out;
-        mat_create(out, left.rows, left.cols, D16S, 1);
-        check(adf_bm_compute_host(h_, 1, left.data, mat_step(left), 0, right.data, mat_step(right), 0, left.cols, left.rows,
-                                  reinterpret_cast<int16_t*>(out.data), mat_step(out), 0));
-        disparity = out;
+        match(left, right, disparity, nullptr);
     }
     // extension (adf_bm_compute_cost_host in adf_wls.h): compute()'s map and the CV_16SC1 aggregated cost of each winning
     // disparity (0 where the map holds (minDisparity - 1) * 16), the pair adf::validateDisparity takes.  The match alone:
@@ -642,17 +637,26 @@ public:
     void computeWithCost(const Mat& left, const Mat& right, Mat& disparity, Mat& cost)
     {
         check_views(left, right);
+        match(left, right, disparity, &cost);
+    }
+private:
+    // checked views -> the map and, with `cost`, the winners' cost plane, through the host entry that returns them
+    void match(const Mat& left, const Mat& right, Mat& disparity, Mat* cost)
+    {
         push_params();
         Mat out, c;
         mat_create(out, left.rows, left.cols, D16S, 1);
-        mat_create(c, left.rows, left.cols, D16S, 1);
-        check(adf_bm_compute_cost_host(h_, 1, left.data, mat_step(left), 0, right.data, mat_step(right), 0, left.cols, left.rows,
-                                       reinterpret_cast<int16_t*>(out.data), mat_step(out), 0,
-                                       reinterpret_cast<int16_t*>(c.data), mat_step(c), 0));
+        int16_t* const d = reinterpret_cast<int16_t*>(out.data);
+        if (cost) {
+            mat_create(c, left.rows, left.cols, D16S, 1);
+            check(adf_bm_compute_cost_host(h_, 1, left.data, mat_step(left), 0, right.data, mat_step(right), 0, left.cols, left.rows,
+                                           d, mat_step(out), 0, reinterpret_cast<int16_t*>(c.data), mat_step(c), 0));
+            *cost = c;
+        } else
+            check(adf_bm_compute_host(h_, 1, left.data, mat_step(left), 0, right.data, mat_step(right), 0, left.cols, left.rows,
+                                      d, mat_step(out), 0));
         disparity = out;
-        cost = c;
     }
-private:
     static void check_views(const Mat& left, const Mat& right)
     {
         if (left.empty() || right.empty() || mat_depth(left) != D8U || mat_depth(right) != D8U ||
