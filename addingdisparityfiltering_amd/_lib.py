@@ -20,6 +20,7 @@ BM_COST_SAD, BM_COST_CENSUS_DENSE, BM_COST_CENSUS_SPARSE = 0, 1, 2    # adf_bm_s
 # modified census (window mean) on the dense / the sparse grid, centre-symmetric census; 3 and 7 stay unassigned (include/adf_wls.h)
 SGBM_COST_MCT_DENSE, SGBM_COST_MCT_SPARSE, SGBM_COST_CENSUS_CS = 4, 5, 6
 BM_COST_MCT_DENSE, BM_COST_MCT_SPARSE, BM_COST_CENSUS_CS = 4, 5, 6
+SGBM_RIGHT_MATCHER, SGBM_RIGHT_FROM_VOLUME = 0, 1    # adf_sgbm_compute_both_*'s right_source (include/adf_wls.h)
 MISSING_NONE, MISSING_MIN, MISSING_VALUE = 0, 1, 2    # adf_reproject_params.missing_mode (include/adf_wls.h)
 
 
@@ -143,6 +144,8 @@ SYMBOLS = [
     ("adf_sgbm_get_cost", _i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
     ("adf_sgbm_compute_device", _i, [_vp, _i, _vp, _pd, _pd, _vp, _pd, _pd, _i, _i, _i, _vp, _pd, _pd, _vp]),
     ("adf_sgbm_compute_host", _i, [_vp, _i, _vp, _pd, _pd, _vp, _pd, _pd, _i, _i, _i, _vp, _pd, _pd]),
+    ("adf_sgbm_compute_both_device", _i, [_vp, _i, _vp, _pd, _pd, _vp, _pd, _pd, _i, _i, _i, _vp, _pd, _pd, _vp, _pd, _pd, _i, _vp]),
+    ("adf_sgbm_compute_both_host", _i, [_vp, _i, _vp, _pd, _pd, _vp, _pd, _pd, _i, _i, _i, _vp, _pd, _pd, _vp, _pd, _pd, _i]),
     ("adf_census_transform_device", _i, [_i, _vp, _pd, _pd, _i, _i, _i, _i, _vp, _pd, _pd, _vp]),
     ("adf_census_transform_host", _i, [_i, _vp, _pd, _pd, _i, _i, _i, _i, _vp, _pd, _pd]),
     ("adf_filter_speckles_workspace_bytes", _sz, [_i, _i, _i]),

@@ -286,7 +286,9 @@ __global__ void __launch_bounds__(256) sgbm_cost_kernel(CostArgs a)
 // S -- it no longer reads S (8 bytes per pixel and disparity moved instead of 12) -- and DIR_RIGHT, which is bound by
 // vector issue and has bandwidth to spare, reads both and adds them in the accumulation's own order:
 // sat(sat(S + L_last) + L_right).
-enum { DIR_TOP = 0, DIR_ADD = 1, DIR_RIGHT = 2, DIR_ADD_OUT = 3 };
+// DIR_RIGHT_BOTH: DIR_RIGHT that also takes the RIGHT view's raw map from the same registers (include/adf_wls.h,
+// ADF_SGBM_RIGHT_FROM_VOLUME): the final S(x, d) of the left view is a cost of (right column x - d, d).
+enum { DIR_TOP = 0, DIR_ADD = 1, DIR_RIGHT = 2, DIR_ADD_OUT = 3, DIR_RIGHT_BOTH = 4 };
 
 struct PathArgs {
     const int16_t* C; int16_t* S; int16_t* L2; size_t vol;
@@ -294,6 +296,8 @@ struct PathArgs {
     int16_t* out; ptrdiff_t out_stride, out_pair;   // raw disparity map (elements)
     int dx, dy;                                     // DIR_ADD: direction of travel
     int disp12;                                     // DIR_RIGHT: the matcher's own left-right check (>= 100000: off)
+    int16_t* out_r; ptrdiff_t out_r_stride, out_r_pair;   // DIR_RIGHT_BOTH: the right view's raw map (elements)
+    int ring;                                       // DIR_RIGHT_BOTH: slots of a wave's ring of live right columns (sgbm_ring)
 };
 
 __device__ __forceinline__ int wave_min_i32(int v)
@@ -353,12 +357,13 @@ __global__ void __launch_bounds__(256) sgbm_path_kernel(PathArgs a)
     extern __shared__ int16_t sOut[];                         // DIR_RIGHT: [4][w1] the scanline's results (written out coalesced),
                                                               // then [4][W] disp2 and [4][W] its cost (left-right check)
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    constexpr bool WIN = DIR == DIR_RIGHT || DIR == DIR_RIGHT_BOTH, BOTH = DIR == DIR_RIGHT_BOTH;
     const int line = blockIdx.x * 4 + wv;                     // scanline: a column (TOP), a row (RIGHT), any straight line (ADD)
     // scanline -> first pixel (x0, y0), direction (dx, dy), length.  Diagonals: one line per pixel of the row the
     // path enters through, then one per remaining pixel of the column it enters through.
     int dx, dy, x0, y0, nlines, nsteps;
     if (DIR == DIR_TOP) { dx = 0; dy = 1; nlines = a.w1; x0 = line; y0 = 0; nsteps = a.H; }
-    else if (DIR == DIR_RIGHT) { dx = -1; dy = 0; nlines = a.H; x0 = a.w1 - 1; y0 = line; nsteps = a.w1; }
+    else if (WIN) { dx = -1; dy = 0; nlines = a.H; x0 = a.w1 - 1; y0 = line; nsteps = a.w1; }
     else {
         dx = a.dx; dy = a.dy;
         const int ys = dy > 0 ? 0 : a.H - 1, xs = dx > 0 ? 0 : a.w1 - 1;
@@ -380,7 +385,7 @@ __global__ void __launch_bounds__(256) sgbm_path_kernel(PathArgs a)
     const int16_t* C = a.C + vol0 + (active ? d0 : 0);
     int16_t* S = a.S + vol0 + (active ? d0 : 0);
     int16_t* L2 = a.L2 + vol0 + (active ? d0 : 0);
-    constexpr bool READS_S = DIR == DIR_ADD || DIR == DIR_RIGHT;
+    constexpr bool READS_S = DIR == DIR_ADD || WIN;
     // element offset of step t
     auto offs = [&](int t) -> size_t {
         return ((size_t)(y0 + t * dy) * a.w1 + (size_t)(x0 + t * dx)) * a.D;
@@ -393,17 +398,82 @@ __global__ void __launch_bounds__(256) sgbm_path_kernel(PathArgs a)
     int16_t* myOut = sOut + wv * a.w1;
     // the matcher's own left-right check (stereo_binary_sgbm.cpp:548-556, 598-613): disp2 = per column of image 2 the
     // disparity of the cheapest winner pointing at it, kept in LDS for the row
-    const bool lrc = DIR == DIR_RIGHT && a.disp12 < 100000;
+    const bool lrc = WIN && a.disp12 < 100000;
     int16_t* d2p = sOut + 4 * a.w1 + wv * a.W;
     int16_t* d2c = sOut + 4 * a.w1 + 4 * a.W + wv * a.W;
     if (lrc)
         for (int x = lane; x < a.W; x += 64) { d2p[x] = invalid; d2c[x] = (int16_t)SG_MAX_COST; }   // :449-453
 
+    // DIR_RIGHT_BOTH: the right view's map from the same S (include/adf_wls.h, ADF_SGBM_RIGHT_FROM_VOLUME).  S(x1, d) is the
+    // cost of candidate d of the right column xr = x1 + cR - d.  The row is walked from the right, so the candidates of one
+    // xr arrive one per step in DESCENDING d: a strict `<` keeps the largest d of the smallest cost, and xr is finished by
+    // the step that brings its d = 0.  The fit of candidate (xc, d) reads S(xc+1, d+1) and S(xc-1, d-1): h1 / h2 keep the
+    // previous two steps' st, and the candidates of column xc are entered one step late, when column xc-1 is known.
+    //   ringR  per wave, a ring of a.ring >= D live right columns, 8 bytes each: x = cost << 16 | fit << 15 | d,
+    //          y = S(d+1) | S(d-1) << 16; an empty slot holds cost SHRT_MAX, which no candidate beats
+    //   rOut   per wave, the row's W raw values, written out coalesced after the loop
+    // Within a step the lanes' xr are distinct, and a wave's LDS operations stay in order across steps: no atomics.
+    typedef uint32_t us2x __attribute__((ext_vector_type(2)));
+    constexpr uint32_t RING_EMPTY = (uint32_t)SG_MAX_COST << 16;
+    const int base_r = 4 * a.w1 + (lrc ? 8 * a.W : 0);        // int16 elements of sOut before this variant's part
+    int16_t* rOut = sOut + base_r + wv * a.W;
+    us2x* ringR = reinterpret_cast<us2x*>(sOut + base_r + 4 * a.W) + wv * a.ring;
+    const int cR = a.minX1 - a.minD;
+    const int invalid_r = -(a.minD + a.D) * SG_DISP_SCALE;
+    int h1[BOTH ? DPL : 1], h2[BOTH ? DPL : 1];
+    if constexpr (BOTH) {
+#pragma unroll
+        for (int k = 0; k < DPL; k++) h1[k] = h2[k] = SG_MAX_COST;
+        for (int x = lane; x < a.W; x += 64) rOut[x] = (int16_t)invalid_r;
+        for (int i = lane; i < a.ring; i += 64) ringR[i] = us2x{RING_EMPTY, 0};
+    }
+    // a finished slot -> the raw value, in the right matcher's own index d' = D-1-d (stereo_binary_sgbm.cpp:584-596 there)
+    auto right_value = [&](uint32_t e0, uint32_t e1) -> int {
+        const int m = (int)e0 >> 16, d = (int)(e0 & 1023);
+        int v = (a.D - 1 - d) * SG_DISP_SCALE;
+        if (e0 & 0x8000u) {
+            const int sp = (int)(short)(e1 & 0xffffu), sm = (int)e1 >> 16;        // S(d+1) = S'(d'-1), S(d-1) = S'(d'+1)
+            const int denom2 = max(sp + sm - 2 * m, 1);
+            v += div_trunc_small((sp - sm) * SG_DISP_SCALE + denom2, denom2 * 2);
+        }
+        return m >= SG_MAX_COST ? invalid_r : v + (1 - a.minD - a.D) * SG_DISP_SCALE;
+    };
+    // the candidates of column xc (costs h1) once `cur` = column xc-1 is known (below_ok) or known not to exist
+    auto right_candidates = [&](int xc, const int (&cur)[BOTH ? DPL : 1], bool below_ok) {
+        if constexpr (!BOTH) return;
+        else {
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");          // (compiler only: the previous step's slots are written)
+        const int up = __builtin_amdgcn_update_dpp(SG_MAX_COST, h2[0], 0x130, 0xf, 0xf, false);               // wave_shl:1: S(xc+1, d0+DPL)
+        const int dn = __builtin_amdgcn_update_dpp(SG_MAX_COST, cur[DPL - 1], 0x138, 0xf, 0xf, false);   // wave_shr:1: S(xc-1, d0-1)
+        const bool sides_ok = below_ok && xc + 1 < a.w1;
+        const int xr0 = xc + cR - d0;
+#pragma unroll
+        for (int k = 0; k < DPL; k++) {
+            const int d = d0 + k;
+            const int sp = k == DPL - 1 ? up : h2[k + 1 < DPL ? k + 1 : k], sm = k == 0 ? dn : cur[k > 0 ? k - 1 : 0];
+            const bool fit = sides_ok && d > 0 && d < a.D - 1;
+            const us2x mine = {((uint32_t)h1[k] << 16) | (fit ? 0x8000u : 0u) | (uint32_t)d, ((uint32_t)sp & 0xffffu) | ((uint32_t)sm << 16)};
+            us2x* slot = ringR + ((xr0 - k) & (a.ring - 1));
+            if (k == 0) {                                      // lane 0's is d = 0: the last candidate of its column
+                const us2x old = *slot;
+                const bool win = active && h1[0] < ((int)old.x >> 16);
+                if (lane == 0) {
+                    const us2x f = win ? mine : old;
+                    rOut[xr0] = (int16_t)right_value(f.x, f.y);
+                    *slot = us2x{RING_EMPTY, 0};
+                } else if (win)
+                    *slot = mine;
+            } else if (active && h1[k] < ((int)slot->x >> 16))
+                *slot = mine;
+        }
+        }
+    };
+
     // one step of formula 13 at scanline position t with the operands c (block cost) and s (S so far)
     auto step = [&](int t, const int (&c)[DPL], const int (&s_in)[DPL], const int (&l2)[DPL]) {
         int s[DPL];
 #pragma unroll
-        for (int k = 0; k < DPL; k++) s[k] = DIR == DIR_RIGHT ? sat16i(s_in[k] + l2[k]) : s_in[k];   // the last accumulating path's costs
+        for (int k = 0; k < DPL; k++) s[k] = WIN ? sat16i(s_in[k] + l2[k]) : s_in[k];   // the last accumulating path's costs
         const size_t o = offs(t);
         // stereo_binary_sgbm.cpp:419-446: neighbours d-1 / d+1, guards SHRT_MAX outside [0, D)
         const int lm = __builtin_amdgcn_update_dpp(SG_MAX_COST, L[DPL - 1], 0x138, 0xf, 0xf, false);   // wave_shr:1
@@ -464,6 +534,11 @@ __global__ void __launch_bounds__(256) sgbm_path_kernel(PathArgs a)
                     res = d + a.minD * SG_DISP_SCALE;           // :596
                 }
                 if (lane == 0) myOut[a.w1 - 1 - t] = (int16_t)res;
+                if constexpr (BOTH) {
+                    if (t > 0) right_candidates(a.w1 - t, st, true);       // (uniform; LDS only)
+#pragma unroll
+                    for (int k = 0; k < DPL; k++) { h2[k] = h1[k]; h1[k] = st[k]; }
+                }
             }
         }
     };
@@ -472,7 +547,7 @@ __global__ void __launch_bounds__(256) sgbm_path_kernel(PathArgs a)
     // latency).  The pipelined loop has NO branch around a vector-memory operation: with one, the compiler can only
     // wait for every outstanding load at each use, which serialises the ring.
     constexpr int PF = DPL >= 8 ? 4 : 8;
-    int cq[PF][DPL], sq[PF][DPL], lq[DIR == DIR_RIGHT ? PF : 1][DPL];
+    int cq[PF][DPL], sq[PF][DPL], lq[WIN ? PF : 1][DPL];
 #pragma unroll
     for (int k = 0; k < DPL; k++) lq[0][k] = 0;
 #pragma unroll
@@ -484,7 +559,7 @@ __global__ void __launch_bounds__(256) sgbm_path_kernel(PathArgs a)
 #pragma unroll
             for (int k = 0; k < DPL; k++) sq[p][k] = 0;
         }
-        if (DIR == DIR_RIGHT) load_costs<DPL>(L2 + offs(tt), lq[p]);
+        if (WIN) load_costs<DPL>(L2 + offs(tt), lq[p]);
     }
     int t0 = 0;
     for (; t0 + PF <= nsteps; t0 += PF) {
@@ -493,19 +568,30 @@ __global__ void __launch_bounds__(256) sgbm_path_kernel(PathArgs a)
             const int t = t0 + p;
             int c[DPL], s[DPL], l2[DPL];
 #pragma unroll
-            for (int k = 0; k < DPL; k++) { c[k] = cq[p][k]; s[k] = sq[p][k]; l2[k] = lq[DIR == DIR_RIGHT ? p : 0][k]; }
+            for (int k = 0; k < DPL; k++) { c[k] = cq[p][k]; s[k] = sq[p][k]; l2[k] = lq[WIN ? p : 0][k]; }
             const int tt = t + PF < nsteps ? t + PF : nsteps - 1;
             load_costs<DPL>(C + offs(tt), cq[p]);
             if (READS_S) load_costs<DPL>(S + offs(tt), sq[p]);
-            if (DIR == DIR_RIGHT) load_costs<DPL>(L2 + offs(tt), lq[p]);
+            if (WIN) load_costs<DPL>(L2 + offs(tt), lq[p]);
             step(t, c, s, l2);
         }
     }
 #pragma unroll
     for (int p = 0; p < PF; p++)                              // the last nsteps % PF steps: operands already in the ring
-        if (t0 + p < nsteps) step(t0 + p, cq[p], sq[p], lq[DIR == DIR_RIGHT ? p : 0]);
+        if (t0 + p < nsteps) step(t0 + p, cq[p], sq[p], lq[WIN ? p : 0]);
 
-    if (DIR == DIR_RIGHT) {                                   // the scanline's results, coalesced
+    if constexpr (BOTH) {
+        right_candidates(0, h1, false);                       // the candidates of column 0: nothing lies below them
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        for (int j = lane + 1; j < a.D; j += 64) {            // the columns that never see d = 0 (partial ranges count)
+            const us2x e = ringR[(cR - j) & (a.ring - 1)];
+            rOut[cR - j] = (int16_t)right_value(e.x, e.y);
+        }
+        __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+        int16_t* out_r = a.out_r + (ptrdiff_t)blockIdx.y * a.out_r_pair + (ptrdiff_t)line * a.out_r_stride;
+        for (int x = lane; x < a.W; x += 64) out_r[x] = rOut[x];
+    }
+    if (WIN) {                                   // the scanline's results, coalesced
         int16_t* out = a.out + (ptrdiff_t)blockIdx.y * a.out_pair + (ptrdiff_t)line * a.out_stride + a.minX1;
         const int maxdiff = a.disp12 > 0 ? a.disp12 : 1;      // :141
         for (int x1 = lane; x1 < a.w1; x1 += 64) {
@@ -572,10 +658,29 @@ hipError_t launch_cost(const CostArgs& a, int bs, int n_images, hipStream_t st)
 }
 
 constexpr size_t WINNER_LDS_LIMIT = 150 * 1024;              // what the winner pass may take of a CU's 160 KiB
+// The both-views call's own refusals (sgbm_check), and the widths its LDS limit comes to: 16 W + 16 KiB, with the matcher's
+// own left-right check 32 W + 16 KiB, within WINNER_LDS_LIMIT.  tests/test_gpu_sgbm_both.py pins their words (the recorded
+// fixture tests/matcher_refusals.json pins those of the entries it was recorded from).
+constexpr int SGBM_BOTH_MAX_W = 8576, SGBM_BOTH_MAX_W_LRC = 4288;
+constexpr const char* MSG_RIGHT_SOURCE = "right_source must be ADF_SGBM_RIGHT_MATCHER or ADF_SGBM_RIGHT_FROM_VOLUME";
+constexpr const char* MSG_MAPS_OVERLAP = "the two disparity maps must not overlap";
+constexpr const char* MSG_BOTH_WIDTH = "ADF_SGBM_RIGHT_FROM_VOLUME supports images up to %d columns (%d with the matcher's own left-right check, disp12MaxDiff)";
 
-// lds_out: the winner pass's dynamic LDS (SgbmPlan::lds_out)
+template <int DPL, int DIR>
+hipError_t launch_winner(const PathArgs& a, int n, size_t lds_out, hipStream_t st)
+{
+    if (lds_out > 48 * 1024) {
+        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(sgbm_path_kernel<DPL, DIR>),
+                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_out);
+        if (e != hipSuccess) return e;
+    }
+    hipLaunchKernelGGL((sgbm_path_kernel<DPL, DIR>), dim3((a.H + 3) / 4, n), dim3(256), lds_out, st, a);   // from the right + winner
+    return hipGetLastError();
+}
+
+// lds_out: the winner pass's dynamic LDS (SgbmPlan::lds_out); both: the winner pass also writes the right view's raw map
 template <int DPL>
-hipError_t launch_paths(const PathArgs& a0, int mode, int n, size_t lds_out, hipStream_t st)
+hipError_t launch_paths(const PathArgs& a0, int mode, int n, size_t lds_out, bool both, hipStream_t st)
 {
     PathArgs a = a0;
     hipLaunchKernelGGL((sgbm_path_kernel<DPL, DIR_TOP>), dim3((a.w1 + 3) / 4, n), dim3(256), 0, st, a);      // from above
@@ -591,13 +696,7 @@ hipError_t launch_paths(const PathArgs& a0, int mode, int n, size_t lds_out, hip
         else hipLaunchKernelGGL((sgbm_path_kernel<DPL, DIR_ADD>), dim3((nlines + 3) / 4, n), dim3(256), 0, st, a);
     }
     if (lds_out > WINNER_LDS_LIMIT) return hipErrorInvalidValue;
-    if (lds_out > 48 * 1024) {
-        hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(sgbm_path_kernel<DPL, DIR_RIGHT>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_out);
-        if (e != hipSuccess) return e;
-    }
-    hipLaunchKernelGGL((sgbm_path_kernel<DPL, DIR_RIGHT>), dim3((a.H + 3) / 4, n), dim3(256), lds_out, st, a);   // from the right + winner
-    return hipGetLastError();
+    return both ? launch_winner<DPL, DIR_RIGHT_BOTH>(a, n, lds_out, st) : launch_winner<DPL, DIR_RIGHT>(a, n, lds_out, st);
 }
 
 } // namespace
@@ -703,12 +802,32 @@ extern "C" int adf_sgbm_get_device(const adf_sgbm_t* h, int* device)
 
 // One compute call as its entry received it: planes with rows `stride`, pairs `pair` bytes apart; device: device pointers
 // that the kernels index (the host entry's are copied by bytes into a dense staging block).
+// A both-views call (adf_sgbm_compute_both_*) carries the right view's map too, disp_r, and names its source.
 template <class T> struct Plane { T* p; ptrdiff_t stride, pair; };
-struct SgbmCall { adf_sgbm* h; int n_pairs; Plane<const uint8_t> left, right; int cn, W, H; Plane<int16_t> disp; bool device; };
+struct SgbmCall {
+    adf_sgbm* h; int n_pairs; Plane<const uint8_t> left, right; int cn, W, H; Plane<int16_t> disp; bool device;
+    bool both = false; Plane<int16_t> disp_r = {nullptr, 0, 0}; int right_source = ADF_SGBM_RIGHT_MATCHER;
+    bool from_volume() const { return both && right_source == ADF_SGBM_RIGHT_FROM_VOLUME; }
+};
 
 static int sgbm_block(const adf_sgbm* h) { return h->block > 0 ? h->block : 5; }
-// dynamic LDS of the winner pass: per wave a row of `cols` results and, with the matcher's own left-right check, two rows of the image's width
-static size_t sgbm_winner_lds(const adf_sgbm* h, int cols, int W) { return ((size_t)cols + (h->disp12 < 100000 ? 2 * (size_t)W : 0)) * 4 * sizeof(int16_t); }
+// slots of a wave's ring of live right columns (ADF_SGBM_RIGHT_FROM_VOLUME): a power of two that holds D
+static int sgbm_ring(int D) { int r = 16; while (r < D) r <<= 1; return r; }
+constexpr int SGBM_RING_MAX = 512;                           // = sgbm_ring(the largest numDisparities)
+// dynamic LDS of the winner pass: per wave a row of `cols` results and, with the matcher's own left-right check, two rows of
+// the image's width; a call that takes the right view's map from the volume adds a row of the image's width and `ring` slots of 8 bytes
+static size_t sgbm_winner_lds(const adf_sgbm* h, int cols, int W, int ring = 0)
+{
+    return ((size_t)cols + (h->disp12 < 100000 ? 2 * (size_t)W : 0) + (ring ? (size_t)W : 0)) * 4 * sizeof(int16_t) + (size_t)ring * 4 * 8;
+}
+
+// bytes [lo, hi) that n maps of H rows of W int16 touch
+static void map_extent(const Plane<int16_t>& m, int n, int W, int H, uintptr_t& lo, uintptr_t& hi)
+{
+    const ptrdiff_t span = (ptrdiff_t)(n - 1) * m.pair;
+    lo = reinterpret_cast<uintptr_t>(m.p) + std::min<ptrdiff_t>(span, 0);
+    hi = reinterpret_cast<uintptr_t>(m.p) + std::max<ptrdiff_t>(span, 0) + (ptrdiff_t)(H - 1) * m.stride + (ptrdiff_t)W * 2;
+}
 
 static int sgbm_check(const SgbmCall& c)
 {
@@ -732,6 +851,20 @@ static int sgbm_check(const SgbmCall& c)
     if (h->disp12 < 100000 && sgbm_winner_lds(h, W, W) > WINNER_LDS_LIMIT)
         return fail(ADF_ESIZE, "the matcher's own left-right check (disp12MaxDiff) supports images up to 6400 columns");
     if (c.device && c.n_pairs > 1 && (c.disp.pair & 1)) return fail(ADF_ESIZE, "disparity maps must be 2-byte aligned");
+    if (!c.both) return ADF_OK;
+    if (c.right_source != ADF_SGBM_RIGHT_MATCHER && c.right_source != ADF_SGBM_RIGHT_FROM_VOLUME)
+        return fail(ADF_EBADARG, "%s", MSG_RIGHT_SOURCE);
+    if (!c.disp_r.p) return fail(ADF_EBADARG, "views and disparity must be non-NULL, n_pairs positive");
+    if (c.disp_r.stride < (ptrdiff_t)W * 2) return fail(ADF_ESIZE, "bad size or stride");
+    if ((c.disp_r.stride & 1) || (reinterpret_cast<uintptr_t>(c.disp_r.p) & 1)) return fail(ADF_ESIZE, "disparity rows must be 2-byte aligned");
+    if (c.device && c.n_pairs > 1 && (c.disp_r.pair & 1)) return fail(ADF_ESIZE, "disparity maps must be 2-byte aligned");
+    uintptr_t l0, l1, r0, r1;
+    map_extent(c.disp, c.n_pairs, W, H, l0, l1);
+    map_extent(c.disp_r, c.n_pairs, W, H, r0, r1);
+    if (l0 < r1 && r0 < l1) return fail(ADF_EBADARG, "%s", MSG_MAPS_OVERLAP);
+    // (as above: stated for the whole width, and for the largest ring)
+    if (c.from_volume() && sgbm_winner_lds(h, W, W, SGBM_RING_MAX) > WINNER_LDS_LIMIT)
+        return fail(ADF_ESIZE, MSG_BOTH_WIDTH, SGBM_BOTH_MAX_W, SGBM_BOTH_MAX_W_LRC);
     return ADF_OK;
 }
 
@@ -739,10 +872,12 @@ static int sgbm_check(const SgbmCall& c)
 struct SgbmPlan {
     int D, minD, bs, P1, P2, ur, ftzero, minX1, w1; int16_t invalid; bool census;   // the effective parameters; matched columns [minX1, minX1 + w1)
     // per image in flight, 256-byte aligned: a signal plane (12 * cn bytes per pixel; census: a descriptor plane, 8), a cost volume, the raw map
-    size_t rec_bytes, vol_bytes, raw_bytes;
+    // (raw2_bytes: the right view's raw map of ADF_SGBM_RIGHT_FROM_VOLUME, else 0)
+    size_t rec_bytes, vol_bytes, raw_bytes, raw2_bytes;
     int chunk;                                  // images in flight: what ws_limit holds of the call's pairs
-    size_t rec1, rec2, C, S, L, raw, ws_bytes;  // h->ws: byte offsets of its regions, `chunk` parts each (L: the last accumulating path's own volume)
+    size_t rec1, rec2, C, S, L, raw, raw2, ws_bytes;  // h->ws: byte offsets of its regions, `chunk` parts each (L: the last accumulating path's own volume)
     int dpl; size_t lds_out;                    // disparities per lane of the path kernels; the winner pass's dynamic LDS
+    int ring; int16_t invalid_r;                // ADF_SGBM_RIGHT_FROM_VOLUME: the ring's slots (else 0) and the right map's invalid value
 };
 
 static SgbmPlan sgbm_plan(const SgbmCall& c)
@@ -759,13 +894,16 @@ static SgbmPlan sgbm_plan(const SgbmCall& c)
     p.rec_bytes = pad_to(px * (p.census ? 8 : c.cn * 3 * 4), 256);
     p.vol_bytes = pad_to(p.w1 > 0 ? (size_t)c.H * p.w1 * p.D * 2 : 0, 256);
     p.raw_bytes = pad_to(px * 2, 256);
-    p.chunk = (int)std::min<size_t>(std::max<size_t>(h->ws_limit / (2 * p.rec_bytes + 3 * p.vol_bytes + p.raw_bytes), 1), c.n_pairs);
+    p.raw2_bytes = c.from_volume() ? p.raw_bytes : 0;
+    p.chunk = (int)std::min<size_t>(std::max<size_t>(h->ws_limit / (2 * p.rec_bytes + 3 * p.vol_bytes + p.raw_bytes + p.raw2_bytes), 1), c.n_pairs);
     p.ws_bytes = 0;
     auto region = [&](size_t part) { const size_t at = p.ws_bytes; p.ws_bytes += part * p.chunk; return at; };
     p.rec1 = region(p.rec_bytes); p.rec2 = region(p.rec_bytes); p.C = region(p.vol_bytes); p.S = region(p.vol_bytes);
-    p.L = region(p.vol_bytes); p.raw = region(p.raw_bytes);
+    p.L = region(p.vol_bytes); p.raw = region(p.raw_bytes); p.raw2 = region(p.raw2_bytes);
     p.dpl = p.D <= 64 ? 1 : p.D <= 128 ? 2 : p.D <= 256 ? 4 : 8;
-    p.lds_out = sgbm_winner_lds(h, p.w1, c.W);
+    p.ring = c.from_volume() ? sgbm_ring(p.D) : 0;
+    p.invalid_r = (int16_t)(-(p.minD + p.D) * SG_DISP_SCALE);
+    p.lds_out = sgbm_winner_lds(h, p.w1, c.W, p.ring);
     return p;
 }
 
@@ -781,8 +919,13 @@ static int sgbm_run_chunk(const SgbmCall& c, const SgbmPlan& p, int first, int n
     const uint8_t* R = c.right.p + (ptrdiff_t)first * c.right.pair;
     int16_t* out = (int16_t*)((char*)c.disp.p + (ptrdiff_t)first * c.disp.pair);
     const dim3 per_row((W + 255) / 256, H, n);
+    int16_t* raw2 = (int16_t*)(ws + p.raw2);                  // (the right view's raw map: ADF_SGBM_RIGHT_FROM_VOLUME only)
     FillArgs fa{raw, W, (ptrdiff_t)raw_el, W, H, p.invalid};
     hipLaunchKernelGGL(sgbm_fill_kernel, per_row, dim3(256), 0, st, fa);
+    if (p.ring) {
+        fa.p = raw2; fa.v = p.invalid_r;
+        hipLaunchKernelGGL(sgbm_fill_kernel, per_row, dim3(256), 0, st, fa);
+    }
     if (p.w1 > 0) {
         if (p.census) {                                    // preFilterCap plays no part in this cost
             int rc;
@@ -803,13 +946,19 @@ static int sgbm_run_chunk(const SgbmCall& c, const SgbmPlan& p, int first, int n
                      : c.cn == 1 ? launch_cost<BtCost<1>>(ca, p.bs, n, st) : launch_cost<BtCost<3>>(ca, p.bs, n, st);
         if (e != hipSuccess) return fail(ADF_EHIP, "%s", hipGetErrorString(e));
         PathArgs pa{ca.C, (int16_t*)(ws + p.S), (int16_t*)(ws + p.L), volp, W, H, p.D, p.minD, p.minX1, p.w1, p.P1, p.P2, p.ur,
-                    raw, (ptrdiff_t)W, (ptrdiff_t)raw_el, 0, 0, h->disp12};
-        e = p.dpl == 1 ? launch_paths<1>(pa, h->mode, n, p.lds_out, st) : p.dpl == 2 ? launch_paths<2>(pa, h->mode, n, p.lds_out, st)
-          : p.dpl == 4 ? launch_paths<4>(pa, h->mode, n, p.lds_out, st) : launch_paths<8>(pa, h->mode, n, p.lds_out, st);
+                    raw, (ptrdiff_t)W, (ptrdiff_t)raw_el, 0, 0, h->disp12, raw2, (ptrdiff_t)W, (ptrdiff_t)raw_el, p.ring};
+        const bool both = p.ring != 0;
+        e = p.dpl == 1 ? launch_paths<1>(pa, h->mode, n, p.lds_out, both, st) : p.dpl == 2 ? launch_paths<2>(pa, h->mode, n, p.lds_out, both, st)
+          : p.dpl == 4 ? launch_paths<4>(pa, h->mode, n, p.lds_out, both, st) : launch_paths<8>(pa, h->mode, n, p.lds_out, both, st);
         if (e != hipSuccess) return fail(ADF_EHIP, "%s", hipGetErrorString(e));
     }
     MedianArgs ma{raw, (ptrdiff_t)W, (ptrdiff_t)raw_el, out, c.disp.stride / 2, c.disp.pair / 2, W, H};
     hipLaunchKernelGGL(sgbm_median_kernel, per_row, dim3(256), 0, st, ma);
+    if (p.ring) {
+        int16_t* out_r = (int16_t*)((char*)c.disp_r.p + (ptrdiff_t)first * c.disp_r.pair);
+        MedianArgs mr{raw2, (ptrdiff_t)W, (ptrdiff_t)raw_el, out_r, c.disp_r.stride / 2, c.disp_r.pair / 2, W, H};
+        hipLaunchKernelGGL(sgbm_median_kernel, per_row, dim3(256), 0, st, mr);
+    }
     return ADF_OK;
 }
 
@@ -821,6 +970,43 @@ static int sgbm_run(const SgbmCall& c, const SgbmPlan& p, hipStream_t st)
     for (int first = 0; first < c.n_pairs; first += p.chunk)
         if (int rc = sgbm_run_chunk(c, p, first, std::min(p.chunk, c.n_pairs - first), st)) return rc;
     return launched();
+}
+
+// The handle as createRightMatcher's matcher (disparity_filters.cpp:432-445) for the length of a scope: minDisparity
+// 1 - minDisparity - numDisparities, uniqueness test and left-right check off; P1, P2, mode, cap and cost are the handle's.
+struct RightMatcherScope {
+    adf_sgbm* h; int md, uniq, disp12;
+    explicit RightMatcherScope(adf_sgbm* h_) : h(h_), md(h_->min_disp), uniq(h_->uniq), disp12(h_->disp12)
+    {
+        h->min_disp = 1 - md - h->num_disp; h->uniq = 0; h->disp12 = 1000000;
+    }
+    ~RightMatcherScope() { h->min_disp = md; h->uniq = uniq; h->disp12 = disp12; }
+    RightMatcherScope(const RightMatcherScope&) = delete;
+    RightMatcherScope& operator=(const RightMatcherScope&) = delete;
+};
+
+// ADF_SGBM_RIGHT_MATCHER: the right matcher's call of a both-views call -- views swapped, the map is disp_r
+static SgbmCall sgbm_right_call(const SgbmCall& c)
+{
+    return SgbmCall{c.h, c.n_pairs, c.right, c.left, c.cn, c.W, c.H, c.disp_r, c.device};
+}
+
+// A both-views call on device pointers, checked here: one run that writes both maps (ADF_SGBM_RIGHT_FROM_VOLUME), or the
+// left matcher's run and then the right matcher's through the same workspace (ADF_SGBM_RIGHT_MATCHER).
+static int sgbm_run_both(const SgbmCall& c, hipStream_t st)
+{
+    if (int rc = sgbm_check(c)) return rc;
+    if (c.from_volume()) return sgbm_run(c, sgbm_plan(c), st);
+    const SgbmCall r = sgbm_right_call(c);
+    {
+        RightMatcherScope as_right(c.h);
+        if (int rc = sgbm_check(r)) return rc;               // (nothing is launched unless both calls can run)
+    }
+    SgbmCall l = c;
+    l.both = false;
+    if (int rc = sgbm_run(l, sgbm_plan(l), st)) return rc;
+    RightMatcherScope as_right(c.h);
+    return sgbm_run(r, sgbm_plan(r), st);
 }
 
 extern "C" int adf_sgbm_compute_device(adf_sgbm_t* h, int n_pairs,
@@ -859,6 +1045,53 @@ extern "C" int adf_sgbm_compute_host(adf_sgbm_t* h, int n_pairs,
     if ((rc = sgbm_run(d, sgbm_plan(d), nullptr))) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
     if ((rc = copy_images(disparity, disp_stride, disp_pair_stride, dd, drow, dbytes, drow, H, n_pairs, hipMemcpyDeviceToHost, nullptr))) return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return ADF_OK;
+}
+
+extern "C" int adf_sgbm_compute_both_device(adf_sgbm_t* h, int n_pairs,
+                                            const uint8_t* left, ptrdiff_t left_stride, ptrdiff_t left_pair_stride,
+                                            const uint8_t* right, ptrdiff_t right_stride, ptrdiff_t right_pair_stride,
+                                            int channels, int W, int H,
+                                            int16_t* disp_left, ptrdiff_t disp_left_stride, ptrdiff_t disp_left_pair_stride,
+                                            int16_t* disp_right, ptrdiff_t disp_right_stride, ptrdiff_t disp_right_pair_stride,
+                                            int right_source, void* stream)
+{
+    const SgbmCall c{h, n_pairs, {left, left_stride, left_pair_stride}, {right, right_stride, right_pair_stride}, channels, W, H,
+                     {disp_left, disp_left_stride, disp_left_pair_stride}, true,
+                     true, {disp_right, disp_right_stride, disp_right_pair_stride}, right_source};
+    return sgbm_run_both(c, (hipStream_t)stream);
+}
+
+// As adf_sgbm_compute_host: the same call on dense copies in the handle's staging block, which holds both maps here.
+extern "C" int adf_sgbm_compute_both_host(adf_sgbm_t* h, int n_pairs,
+                                          const uint8_t* left, ptrdiff_t left_stride, ptrdiff_t left_pair_stride,
+                                          const uint8_t* right, ptrdiff_t right_stride, ptrdiff_t right_pair_stride,
+                                          int channels, int W, int H,
+                                          int16_t* disp_left, ptrdiff_t disp_left_stride, ptrdiff_t disp_left_pair_stride,
+                                          int16_t* disp_right, ptrdiff_t disp_right_stride, ptrdiff_t disp_right_pair_stride,
+                                          int right_source)
+{
+    const SgbmCall c{h, n_pairs, {left, left_stride, left_pair_stride}, {right, right_stride, right_pair_stride}, channels, W, H,
+                     {disp_left, disp_left_stride, disp_left_pair_stride}, false,
+                     true, {disp_right, disp_right_stride, disp_right_pair_stride}, right_source};
+    int rc = sgbm_check(c);
+    if (rc) return rc;
+    DeviceScope ds(h->device);
+    const ptrdiff_t vrow = (ptrdiff_t)W * channels, vbytes = vrow * H, drow = (ptrdiff_t)W * 2, dbytes = pad_to((size_t)drow * H, 256);
+    if ((rc = h->stage.reserve((size_t)(2 * vbytes + 2 * dbytes) * n_pairs + 512, nullptr, FILL_NONE))) return rc;
+    uint8_t* dl = (uint8_t*)h->stage.p;
+    uint8_t* dr = dl + vbytes * n_pairs;
+    int16_t* ddl = (int16_t*)pad_to((uintptr_t)(dr + vbytes * n_pairs), 256);
+    int16_t* ddr = (int16_t*)((char*)ddl + dbytes * n_pairs);
+    const SgbmCall d{h, n_pairs, {dl, vrow, vbytes}, {dr, vrow, vbytes}, channels, W, H, {ddl, drow, dbytes}, true,
+                     true, {ddr, drow, dbytes}, right_source};                                                        // the call, staged
+    if ((rc = copy_images(dl, vrow, vbytes, left, left_stride, left_pair_stride, vrow, H, n_pairs, hipMemcpyHostToDevice, nullptr))) return rc;
+    if ((rc = copy_images(dr, vrow, vbytes, right, right_stride, right_pair_stride, vrow, H, n_pairs, hipMemcpyHostToDevice, nullptr))) return rc;
+    if ((rc = sgbm_run_both(d, nullptr))) return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    if ((rc = copy_images(disp_left, disp_left_stride, disp_left_pair_stride, ddl, drow, dbytes, drow, H, n_pairs, hipMemcpyDeviceToHost, nullptr))) return rc;
+    if ((rc = copy_images(disp_right, disp_right_stride, disp_right_pair_stride, ddr, drow, dbytes, drow, H, n_pairs, hipMemcpyDeviceToHost, nullptr))) return rc;
     HIP_TRY(hipStreamSynchronize(nullptr));
     return ADF_OK;
 }

@@ -14,6 +14,7 @@ edge_filter.hpp (EF.hpp), over the C-ABI in include/adf_wls.h:
     filterSpeckles(img, newVal, maxSpeckleSize, maxDiff, buf)   calib3d (outside the reference tree)
     validateDisparity(disparity, cost, minDisparity, numberOfDisparities, disp12MaxDiff)   calib3d (outside the reference tree)
     StereoBM.computeWithCost / computeBothWithCost / computeFull, StereoSGBM.computeFull   what calib3d's compute does with the matcher's own settings (extension names)
+    StereoSGBM.computeBoth(left, right, ..., rightSource)   both views' maps from one call (extension; include/adf_wls.h: adf_sgbm_compute_both_*)
     censusTransform(image, kernelSize, type)        modules/stereo descriptor.hpp:428 / descriptor.cpp:77-98
     StereoBM.setCostType(BM_COST_CENSUS_*) / setCensusSize(k)   the cost of modules/stereo stereo_binary_bm.cpp:367-408 (extension)
     resize(src, dsize, fx, fy) at half size, cvtColor(src, COLOR_BGR2GRAY)   imgproc (outside the reference tree)
@@ -35,6 +36,7 @@ from ._lib import SGBM_COST_BT, SGBM_COST_CENSUS_DENSE, SGBM_COST_CENSUS_SPARSE 
 from ._lib import BM_COST_SAD, BM_COST_CENSUS_DENSE, BM_COST_CENSUS_SPARSE  # noqa: F401  (re-exported)
 from ._lib import SGBM_COST_MCT_DENSE, SGBM_COST_MCT_SPARSE, SGBM_COST_CENSUS_CS  # noqa: F401  (re-exported)
 from ._lib import BM_COST_MCT_DENSE, BM_COST_MCT_SPARSE, BM_COST_CENSUS_CS  # noqa: F401  (re-exported)
+from ._lib import SGBM_RIGHT_MATCHER, SGBM_RIGHT_FROM_VOLUME  # noqa: F401  (re-exported)
 from ._lib import AdfError, PATH_CONF_BAND, PATH_FUSED_FIRST_PASS, PATH_MERGED_PREP, PATH_ROW_WEIGHTS_GUIDE, PATH_SCALED_FUSED, PATH_SCALED_HALF, Rect, SOLVER_EXACT, SOLVER_WAVE  # noqa: F401  (re-exported)
 
 try:  # torch is optional plumbing: device memory and streams only
@@ -425,10 +427,10 @@ class StereoMatcher(_Handle):
             raise AdfError(_lib.ADF_EBADARG, "left and right must live on the same side (host or device)")
         return L, R, batched
 
-    def _run(self, entry, views, planes, mismatch, instead=None):
+    def _run(self, entry, views, planes, mismatch, instead=None, tail=()):
         """A compute call past its views (_views): the output planes {name: the caller's or None for a new one} of the
         views' size and on their side, the handle prepared, `entry` through _call -- or, where the matcher cannot use
-        `entry`, `instead(*planes)`.  Returns the planes."""
+        `entry`, `instead(*planes)`.  `tail`: the entry's arguments past its planes.  Returns the planes."""
         L, R, batched = views
         maps = [_out_like(L, batched, np.int16) if m is None else m for m in planes.values()]
         descs = [_Image(m, np.int16, what, batched) for m, what in zip(maps, planes)]
@@ -442,7 +444,7 @@ class StereoMatcher(_Handle):
         args = self._args(L, R, descs[0])
         for D in descs[1:]:
             args += _triple(D)
-        _call(entry, L, args)
+        _call(entry, L, args + tail)
         return tuple(maps)
 
     def _match(self, left, right, disparity):
@@ -629,6 +631,29 @@ class StereoSGBM(StereoMatcher):
     def _args(self, L, R, D):
         return (self._h, L.n, L.ptr, L.stride, L.pair_stride, R.ptr, R.stride, R.pair_stride, L.c, L.w, L.h,
                 D.ptr, D.stride, D.pair_stride)     # (spelled out: this runs once per call)
+
+    def computeBoth(self, left, right, disparity_left=None, disparity_right=None, rightSource=SGBM_RIGHT_MATCHER):
+        """Extension: this matcher's map AND a right-view map from one call, the pair DisparityWLSFilter.filter takes
+        (include/adf_wls.h: adf_sgbm_compute_both_*).  The left map is compute()'s byte for byte.  Host arrays take the
+        host entry; device tensors run on torch's current stream.  compute()'s refusals apply (speckleWindowSize > 0
+        included).  Returns (disparity_left, disparity_right).
+
+        rightSource=SGBM_RIGHT_MATCHER (default): the map of createRightMatcher(self).compute(right, left), as a second
+        run inside the call -- identical to the two separate computes, and as expensive.
+        rightSource=SGBM_RIGHT_FROM_VOLUME: a speed-for-fidelity option.  The right map is read from this view's
+        aggregated volume along its diagonals inside the winner pass (no second cost volume, no second set of path
+        passes).  It is NOT the right matcher's map -- the paths ran along the left image -- and has its own definition
+        in include/adf_wls.h, bit-exact against tests/sgbm_both_ref.py; on the Tsukuba fixture (a CPU measurement) 93-96 %
+        of its columns lie within 1 px of the right matcher's, and the filter improves the raw map a little less with it."""
+        self._refuse()
+        if self.speckleWindowSize > 0:
+            raise AdfError(_lib.ADF_EBADARG, "speckle filtering is not implemented inside computeBoth(); "
+                                             "use filterSpeckles on the result")
+        if rightSource not in (SGBM_RIGHT_MATCHER, SGBM_RIGHT_FROM_VOLUME):
+            raise AdfError(_lib.ADF_EBADARG, "rightSource must be SGBM_RIGHT_MATCHER or SGBM_RIGHT_FROM_VOLUME")
+        return self._run("adf_sgbm_compute_both", self._views(left, right),
+                         {"disparity_left": disparity_left, "disparity_right": disparity_right}, "disparity maps must match the views",
+                         tail=(int(rightSource),))
 
 
 _INT32_MAX = 2 ** 31 - 1

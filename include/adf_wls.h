@@ -575,6 +575,63 @@ int adf_sgbm_compute_host(adf_sgbm_t* h, int n_pairs,
                           const uint8_t* right, ptrdiff_t right_stride, ptrdiff_t right_pair_stride,
                           int channels, int W, int H,
                           int16_t* disparity, ptrdiff_t disp_stride, ptrdiff_t disp_pair_stride);
+/* Extension (not a cv:: call): both views' maps from one call, what DisparityWLSFilter::filter(dispL, view, out, dispR)
+ * takes.  disp_left is adf_sgbm_compute_*'s map with the handle's settings, byte for byte (uniquenessRatio and the
+ * matcher's own left-right check included).  disp_right (CV_16SC1, W x H, non-NULL, 2-byte aligned, not overlapping
+ * disp_left) comes from `right_source`; any other value is ADF_EBADARG:
+ *
+ * ADF_SGBM_RIGHT_MATCHER (0): the map of createRightMatcher's matcher (disparity_filters.cpp:432-445) -- views swapped,
+ *   minDisparity = 1 - minDisparity - numDisparities, uniquenessRatio 0, disp12MaxDiff 1000000; P1, P2, mode,
+ *   preFilterCap, cost type and census size are the handle's -- as a second run through the same workspace inside the
+ *   call.  Identical to the two separate computes, and as expensive.
+ *
+ * ADF_SGBM_RIGHT_FROM_VOLUME (1): a speed-for-fidelity option.  The right view's map is read from the LEFT view's
+ *   aggregated volume along its diagonals (Hirschmueller 2008 derives the match image's map "from the same costs, by
+ *   traversing the epipolar line"), inside the winner pass: no second cost volume, no second set of path passes.  It is
+ *   NOT the right matcher's map, because the paths were aggregated along the left image.  The definition, with
+ *   md = minDisparity, nd = numDisparities, matched left columns [minX1, maxX1) = [max(md+nd, 0), W + min(md, 0)),
+ *   w1 = maxX1 - minX1, and S[y][x1][k] (x1 in [0, w1), k in [0, nd)) the final summed path cost, the very value the left
+ *   winner reads, bit for bit.  For row y and right-view column xr in [0, W):
+ *     1. Candidates K = { k in [0, nd) : minX1 <= xr + md + k < maxX1 }, s(k) = S[y][xr + md + k - minX1][k].  Partial
+ *        ranges count: every xr with at least one candidate gets a winner (md = 0: columns 1 ... W-1).
+ *     2. invalid_R = -(md + nd) * 16, the (minDisparity_R - 1) * 16 of the right matcher.  If K is empty, or
+ *        m = min s(k) >= SHRT_MAX, the raw value is invalid_R.
+ *     3. The winner k* is the LARGEST k with s(k) = m: the right matcher's own "first minimum" in its own index
+ *        d' = nd - 1 - k.
+ *     4. Sub-pixel fit only if 0 < k* < nd-1 and both k*-1 and k*+1 are in K: den = max(s(k*+1) + s(k*-1) - 2m, 1),
+ *        d'16 = d' * 16 + trunc(((s(k*+1) - s(k*-1)) * 16 + den) / (2 * den)), C truncation toward zero
+ *        (stereo_binary_sgbm.cpp:584-591 in the right matcher's index); otherwise d'16 = d' * 16.
+ *     5. Raw value d'16 + (1 - md - nd) * 16: k* = 0 gives -md * 16, every value is <= -md * 16, as the right matcher's.
+ *     6. No uniqueness test and no left-right check on this map; then the 3x3 median of every map of this matcher, over
+ *        a raw plane pre-filled with invalid_R.
+ *   When w1 <= 0 both maps are entirely invalid.  Bit-exact against the direct statement tests/sgbm_both_ref.py.
+ *   Agreement with the right matcher's map, MEASURED ON THE CPU with that statement on ONE fixture (Tsukuba, 384 x 288,
+ *   16 disparities; share of columns 1 ... W-nd-1 within 1 px): Birchfield-Tomasi, block 3 or 5, 3-way, the sample's
+ *   P1 / P2, cap 63: 95.8 %; census dense 5, block 3, 3-way, P1 72 / P2 288: 92.6 %; census dense 7, block 5, MODE_SGBM,
+ *   P1 200 / P2 800: 92.8 %.  The filtered map against ground truth (oracle.wls_filter; block 3: MSE 1.451, bad 5.20 %
+ *   with this map; 1.392, 4.94 % with the right matcher's; 1.597, 6.15 % unfiltered; block 5: 1.598, 5.28 % / 1.551,
+ *   4.91 % / 1.709, 6.51 %): the filter still improves the raw map, by a little less than with the genuine right map.
+ *   Limits: the winner pass keeps a row of each map and a ring of numDisparities live right columns in LDS (16 W bytes
+ *   + at most 16 KiB; 32 W with the matcher's own left-right check) within 150 KiB: images up to 8576 columns, 4288 with
+ *   disp12MaxDiff below 100000 -- wider calls are ADF_ESIZE and launch nothing.  Workspace per image in flight:
+ *   adf_sgbm_compute_*'s (two signal or descriptor planes, three H x w1 x nd int16 volumes, one W x H int16 raw map)
+ *   plus a second W x H int16 raw map; ADF_SGBM_RIGHT_MATCHER takes exactly adf_sgbm_compute_*'s. */
+#define ADF_SGBM_RIGHT_MATCHER 0
+#define ADF_SGBM_RIGHT_FROM_VOLUME 1
+int adf_sgbm_compute_both_device(adf_sgbm_t* h, int n_pairs,
+                                 const uint8_t* left, ptrdiff_t left_stride, ptrdiff_t left_pair_stride,
+                                 const uint8_t* right, ptrdiff_t right_stride, ptrdiff_t right_pair_stride,
+                                 int channels, int W, int H,
+                                 int16_t* disp_left, ptrdiff_t disp_left_stride, ptrdiff_t disp_left_pair_stride,
+                                 int16_t* disp_right, ptrdiff_t disp_right_stride, ptrdiff_t disp_right_pair_stride,
+                                 int right_source, void* stream);
+int adf_sgbm_compute_both_host(adf_sgbm_t* h, int n_pairs,
+                               const uint8_t* left, ptrdiff_t left_stride, ptrdiff_t left_pair_stride,
+                               const uint8_t* right, ptrdiff_t right_stride, ptrdiff_t right_pair_stride,
+                               int channels, int W, int H,
+                               int16_t* disp_left, ptrdiff_t disp_left_stride, ptrdiff_t disp_left_pair_stride,
+                               int16_t* disp_right, ptrdiff_t disp_right_stride, ptrdiff_t disp_right_pair_stride,
+                               int right_source);
 
 /* ---------------- census transform (cv::stereo::censusTransform) ----------------
  * cv::stereo::censusTransform(image, kernelSize, dist, type) (descriptor.hpp:428, descriptor.cpp:77-98) on n_images

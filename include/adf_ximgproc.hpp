@@ -739,6 +739,34 @@ public:
     // StereoMatcher::compute: CV_8UC1 / CV_8UC3 views -> CV_16SC1 disparity * 16, invalid pixels (minDisparity - 1) * 16
     void compute(const Mat& left, const Mat& right, Mat& disparity)
     {
+        prepare(left, right);
+        Mat out;
+        mat_create(out, left.rows, left.cols, D16S, 1);
+        check(adf_sgbm_compute_host(h_, 1, left.data, mat_step(left), 0, right.data, mat_step(right), 0, mat_channels(left),
+                                    left.cols, left.rows, reinterpret_cast<int16_t*>(out.data), mat_step(out), 0));
+        disparity = out;
+    }
+    // extension (adf_sgbm_compute_both_host in adf_wls.h): compute()'s map and a right-view map from one call, the pair
+    // DisparityWLSFilter::filter takes.  ADF_SGBM_RIGHT_MATCHER (default): the map of createRightMatcher(this)->compute(right,
+    // left), identical to the two separate computes and as expensive.  ADF_SGBM_RIGHT_FROM_VOLUME: a speed-for-fidelity
+    // option -- the right map is read from this view's aggregated volume inside the winner pass; it is NOT the right matcher's
+    // map and has its own definition in adf_wls.h.
+    void computeBoth(const Mat& left, const Mat& right, Mat& disparity_left, Mat& disparity_right, int rightSource = ADF_SGBM_RIGHT_MATCHER)
+    {
+        prepare(left, right);
+        Mat outl, outr;
+        mat_create(outl, left.rows, left.cols, D16S, 1);
+        mat_create(outr, left.rows, left.cols, D16S, 1);
+        check(adf_sgbm_compute_both_host(h_, 1, left.data, mat_step(left), 0, right.data, mat_step(right), 0, mat_channels(left),
+                                         left.cols, left.rows, reinterpret_cast<int16_t*>(outl.data), mat_step(outl), 0,
+                                         reinterpret_cast<int16_t*>(outr.data), mat_step(outr), 0, rightSource));
+        disparity_left = outl;
+        disparity_right = outr;
+    }
+private:
+    // the views checked, the speckle setting refused, the parameters pushed
+    void prepare(const Mat& left, const Mat& right)
+    {
         if (left.empty() || right.empty() || mat_depth(left) != D8U || mat_depth(right) != D8U ||
             (mat_channels(left) != 1 && mat_channels(left) != 3) || mat_channels(left) != mat_channels(right))
             throw Exception(ADF_EBADARG, "Both input images must have CV_8UC1 or CV_8UC3");
@@ -749,11 +777,6 @@ public:
         check(adf_sgbm_set_params(h_, min_disp_, num_disp_, block_, P1_, P2_, cap_, uniq_, mode_));
         check(adf_sgbm_set_disp12_max_diff(h_, disp12_));
         check(adf_sgbm_set_cost(h_, cost_, census_size_));
-        Mat out;
-        mat_create(out, left.rows, left.cols, D16S, 1);
-        check(adf_sgbm_compute_host(h_, 1, left.data, mat_step(left), 0, right.data, mat_step(right), 0, mat_channels(left),
-                                    left.cols, left.rows, reinterpret_cast<int16_t*>(out.data), mat_step(out), 0));
-        disparity = out;
     }
 };
 
