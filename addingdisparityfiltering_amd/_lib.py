@@ -22,6 +22,8 @@ SGBM_COST_MCT_DENSE, SGBM_COST_MCT_SPARSE, SGBM_COST_CENSUS_CS = 4, 5, 6
 BM_COST_MCT_DENSE, BM_COST_MCT_SPARSE, BM_COST_CENSUS_CS = 4, 5, 6
 SGBM_RIGHT_MATCHER, SGBM_RIGHT_FROM_VOLUME = 0, 1    # adf_sgbm_compute_both_*'s right_source (include/adf_wls.h)
 MISSING_NONE, MISSING_MIN, MISSING_VALUE = 0, 1, 2    # adf_reproject_params.missing_mode (include/adf_wls.h)
+WMF_EXP, WMF_IV1, WMF_IV2, WMF_COS, WMF_JAC, WMF_OFF = range(6)    # cv::ximgproc::WMFWeightType; EXP and OFF are built (ADF_WMF_*)
+WMF_WEIGHT_ONE, WMF_TABLE_LEVELS, WMF_MAX_RADIUS = 65536, 3 * 256 * 256, 31
 
 
 class AdfError(RuntimeError):
@@ -62,6 +64,7 @@ _POINT_CLOUD_DEV = [_i, _vp, _i, _pd, _pd, _i, _i, C.POINTER(ReprojectParams), C
 _RECTIFY_MAP_DEV = [C.POINTER(RectifyParams), _i, _i, _vp, _pd, _vp, _pd, _vp]
 _REMAP_DEV = [_i, _vp, _pd, _pd, _i, _i, _i, _vp, _pd, _vp, _pd, _vp, _pd, _pd, _i, _i, _i, _i, _vp, _vp]
 _RECTIFY_VIEWS_DEV = [_i, _vp, _pd, _pd, _i, _i, _i, C.POINTER(RectifyParams), _vp, _pd, _pd, _i, _i, _i, _i, _vp, _vp]
+_WMF_DEV = [_i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _i, _i, _d, _i, _vp, _pd, _pd, _i, _d, _vp]
 _FILTER_SCALED_DEV = [_vp, _i, _vp, _pd, _pd, _i, _i, _vp, _pd, _pd, _i, _i, _i, _vp, _pd, _pd, _vp, _pd, _pd,
                       C.POINTER(Rect), _vp]
 # adf_wls_filter_typed_*: the scaled call with a depth behind the left map's strides and one behind the output's
@@ -169,6 +172,9 @@ SYMBOLS = [
     ("adf_remap_host", _i, _REMAP_DEV[:-1]),
     ("adf_rectify_views_device", _i, _RECTIFY_VIEWS_DEV),
     ("adf_rectify_views_host", _i, _RECTIFY_VIEWS_DEV[:-1]),
+    ("adf_wmf_weight_table_host", _i, [_d, _i, _vp, _i]),
+    ("adf_weighted_median_filter_device", _i, _WMF_DEV),
+    ("adf_weighted_median_filter_host", _i, _WMF_DEV[:-1]),
 ]
 
 _lib = None

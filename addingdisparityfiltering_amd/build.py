@@ -25,6 +25,7 @@ SOURCES = {
     "view_prep_kernels.hip": [],
     "reproject_kernels.hip": [],
     "rectify_kernels.hip": [],
+    "wmf_kernels.hip": [],
 }
 OUT = os.path.join(_HERE, "libadf_wls.so")
 # -ffp-contract=off: the exact solver and the confidence map reproduce the reference's separate

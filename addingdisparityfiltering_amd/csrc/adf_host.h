@@ -107,6 +107,14 @@ struct Lut {
     void release() { tables.clear(); cur = nullptr; }
 };
 
+// The weighted median filter's weight table (include/adf_wls.h: T, ADF_WMF_TABLE_LEVELS uint32 entries): an immutable
+// device table per (device, sigma, weight type), shared by every call of the process (adf_host.hip: WmfStore, 16 of them).
+struct WmfTable;
+ADF_LOCAL int wmf_weights_check(const char* who, double sigma, int weight_type);   // the refusals both entry kinds share
+// The table of the current device: a look-up when the key was seen before (no device work, capturable), else built on
+// the host and uploaded with one synchronous copy.  The caller holds `out` until its launches are queued.
+ADF_LOCAL int wmf_table_device(double sigma, int weight_type, std::shared_ptr<WmfTable>& out, const uint32_t** dev);
+
 // The host-pointer entry points' copies: `n` images of `rows` rows of `row_bytes`, image k at `k * image_stride` bytes
 // with rows `pitch` bytes apart on either side, asynchronously on `st` (a host destination is complete once `st` has
 // been synchronised).  The layout of a staging block stays with the caller.

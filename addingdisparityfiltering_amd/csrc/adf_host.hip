@@ -90,31 +90,34 @@ struct adf::LutTable {
     ~LutTable() { if (dev) { DeviceScope ds(device); hipFree(dev); } }
 };
 
-struct LutStore {
+// The process-wide store of one kind of immutable device table (the filters' LutTable, the weighted median's WmfTable):
+// up to CAP of them, least recently used dropped first.
+template <class TABLE> struct TableStore {
     static constexpr size_t CAP = 16;
     std::mutex m;
-    std::vector<std::shared_ptr<LutTable>> tables;               // most recently used last
-    static LutStore& get() { static LutStore* s = new LutStore; return *s; }   // (never destroyed: no HIP calls at exit)
-    std::shared_ptr<LutTable> find(int device, float sigma)
+    std::vector<std::shared_ptr<TABLE>> tables;                  // most recently used last
+    static TableStore& get() { static TableStore* s = new TableStore; return *s; }   // (never destroyed: no HIP calls at exit)
+    template <class SAME> std::shared_ptr<TABLE> find(SAME&& same)
     {
         std::lock_guard<std::mutex> lk(m);
         for (size_t k = 0; k < tables.size(); k++)
-            if (tables[k]->device == device && tables[k]->sigma == sigma) {
+            if (same(*tables[k])) {
                 auto t = tables[k];
                 tables.erase(tables.begin() + (ptrdiff_t)k); tables.push_back(t);
                 return t;
             }
         return nullptr;
     }
-    void add(const std::shared_ptr<LutTable>& t)
+    void add(const std::shared_ptr<TABLE>& t)
     {
         std::lock_guard<std::mutex> lk(m);
-        // (a table dropped here lives on while a handle still refers to it; with no handle left nothing can be reading it)
+        // (a table dropped here lives on while a handle or a call still refers to it; with none left nothing can be reading it)
         if (tables.size() >= CAP) tables.erase(tables.begin());
         tables.push_back(t);
     }
     void clear() { std::lock_guard<std::mutex> lk(m); tables.clear(); }
 };
+using LutStore = TableStore<LutTable>;
 
 static void lut_build_host(float s, float* host)
 {
@@ -163,7 +166,7 @@ int adf::Lut::ensure(float s, hipStream_t st)
     }
     int device = 0;
     HIP_TRY(hipGetDevice(&device));
-    std::shared_ptr<LutTable> t = LutStore::get().find(device, s);
+    std::shared_ptr<LutTable> t = LutStore::get().find([&](const LutTable& q) { return q.device == device && q.sigma == s; });
     if (!t) {
         std::vector<float> host(ADF_LUT_LEVELS);
         lut_build_host(s, host.data());
@@ -177,6 +180,69 @@ int adf::Lut::ensure(float s, hipStream_t st)
     }
     tables.push_back(Entry{t, ++tick});
     cur = t->dev;
+    return ADF_OK;
+}
+
+// The weighted median filter's table (include/adf_wls.h: T), built on the host with libm like the table above and kept
+// the same way: one immutable device table per (device, sigma, weight type), a look-up after its first use.  hipFree of
+// a dropped table waits for the device, so a kernel queued with it has finished reading.
+struct adf::WmfTable {
+    int device = 0, type = 0; double sigma = 0; uint32_t* dev = nullptr;
+    WmfTable() = default;
+    WmfTable(const WmfTable&) = delete;
+    WmfTable& operator=(const WmfTable&) = delete;
+    ~WmfTable() { if (dev) { DeviceScope ds(device); hipFree(dev); } }
+};
+using WmfStore = TableStore<WmfTable>;
+
+static void wmf_build_host(double sigma, int weight_type, uint32_t* host)
+{
+    if (weight_type == ADF_WMF_OFF) { std::fill(host, host + ADF_WMF_TABLE_LEVELS, (uint32_t)ADF_WMF_WEIGHT_ONE); return; }
+    // Below a quarter of the last place every later entry rounds to 0 (the argument only falls, and libm's error is far
+    // below the factor of two that is left): those entries are stored, not computed.
+    int i = 0;
+    for (; i < ADF_WMF_TABLE_LEVELS; i++) {
+        const double e = exp(-(double)i / (2.0 * sigma * sigma)) * 65536.0;
+        if (e < 0.25) break;
+        host[i] = (uint32_t)lrint(e);
+    }
+    std::fill(host + i, host + ADF_WMF_TABLE_LEVELS, 0u);
+}
+
+int adf::wmf_weights_check(const char* who, double sigma, int weight_type)
+{
+    if (weight_type != ADF_WMF_EXP && weight_type != ADF_WMF_OFF)
+        return fail(ADF_EBADARG, "%s: weight_type must be ADF_WMF_EXP (0) or ADF_WMF_OFF (5); WMF_IV1, WMF_IV2, WMF_COS and WMF_JAC are not built", who);
+    if (!std::isfinite(sigma) || !(sigma > 0.0)) return fail(ADF_EBADARG, "%s: sigma must be finite and > 0", who);
+    return ADF_OK;
+}
+
+int adf::wmf_table_device(double sigma, int weight_type, std::shared_ptr<WmfTable>& out, const uint32_t** dev)
+{
+    if (weight_type == ADF_WMF_OFF) sigma = 1.0;                  // (one table whatever the sigma)
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) return fail(ADF_ENODEV, "no HIP device");
+    out = WmfStore::get().find([&](const WmfTable& q) { return q.device == device && q.sigma == sigma && q.type == weight_type; });
+    if (!out) {
+        std::vector<uint32_t> host(ADF_WMF_TABLE_LEVELS);
+        wmf_build_host(sigma, weight_type, host.data());
+        uint32_t* d = nullptr;
+        HIP_TRY(device_malloc(reinterpret_cast<void**>(&d), sizeof(uint32_t) * ADF_WMF_TABLE_LEVELS));
+        hipError_t e = hipMemcpy(d, host.data(), sizeof(uint32_t) * ADF_WMF_TABLE_LEVELS, hipMemcpyHostToDevice);
+        if (e != hipSuccess) { hipFree(d); return fail(ADF_EHIP, "weighted median table upload failed: %s", hipGetErrorString(e)); }
+        out = std::make_shared<WmfTable>();
+        out->device = device; out->type = weight_type; out->sigma = sigma; out->dev = d;
+        WmfStore::get().add(out);
+    }
+    *dev = out->dev;
+    return ADF_OK;
+}
+
+extern "C" int adf_wmf_weight_table_host(double sigma, int weight_type, uint32_t* table, int levels)
+{
+    if (!table || levels != ADF_WMF_TABLE_LEVELS) return fail(ADF_EBADARG, "adf_wmf_weight_table_host: table must hold %d entries", ADF_WMF_TABLE_LEVELS);
+    if (int rc = wmf_weights_check("adf_wmf_weight_table_host", sigma, weight_type)) return rc;
+    wmf_build_host(sigma, weight_type, table);
     return ADF_OK;
 }
 
@@ -321,4 +387,5 @@ extern "C" void adf_release_cached_memory(void)
 {
     BlockCache::get().clear();
     LutStore::get().clear();
+    WmfStore::get().clear();
 }

@@ -20,6 +20,7 @@ edge_filter.hpp (EF.hpp), over the C-ABI in include/adf_wls.h:
     resize(src, dsize, fx, fy) at half size, cvtColor(src, COLOR_BGR2GRAY)   imgproc (outside the reference tree)
     reprojectImageTo3D(disparity, Q, handleMissingValues, ddepth), pointCloud(...)   calib3d (outside the reference tree)
     initUndistortRectifyMap(K, dist, R, P, size), remap(src, map1, map2), rectifyViews(...)   calib3d / imgproc (outside the reference tree)
+    weightedMedianFilter(joint, src, r, sigma, weightType, mask, ignoreValue)   weighted_median_filter.hpp:64-90 (the library's own integer definition)
 
 Images are numpy arrays (host path: copied to the GPU and back) or torch CUDA
 tensors (device path: zero-copy, asynchronous on torch's current stream).  A
@@ -37,6 +38,7 @@ from ._lib import BM_COST_SAD, BM_COST_CENSUS_DENSE, BM_COST_CENSUS_SPARSE  # no
 from ._lib import SGBM_COST_MCT_DENSE, SGBM_COST_MCT_SPARSE, SGBM_COST_CENSUS_CS  # noqa: F401  (re-exported)
 from ._lib import BM_COST_MCT_DENSE, BM_COST_MCT_SPARSE, BM_COST_CENSUS_CS  # noqa: F401  (re-exported)
 from ._lib import SGBM_RIGHT_MATCHER, SGBM_RIGHT_FROM_VOLUME  # noqa: F401  (re-exported)
+from ._lib import WMF_EXP, WMF_IV1, WMF_IV2, WMF_COS, WMF_JAC, WMF_OFF  # noqa: F401  (cv's WMFWeightType; EXP and OFF are built)
 from ._lib import AdfError, PATH_CONF_BAND, PATH_FUSED_FIRST_PASS, PATH_MERGED_PREP, PATH_ROW_WEIGHTS_GUIDE, PATH_SCALED_FUSED, PATH_SCALED_HALF, Rect, SOLVER_EXACT, SOLVER_WAVE  # noqa: F401  (re-exported)
 
 try:  # torch is optional plumbing: device memory and streams only
@@ -1216,6 +1218,84 @@ def rectifyViews(src, cameraMatrix, distCoeffs, R, newCameraMatrix, size=None, b
         raise AdfError(_lib.ADF_EBADARG, "%s: the size is empty" % _RV)
     prm = rectifyParams(cameraMatrix, distCoeffs, R, newCameraMatrix, _RV)
     return _sample(_RV, src, None, prm, W, H, borderValue, dst)
+
+
+# ---------------------------------------------------------------------------------------------
+# Weighted median filter: cv::ximgproc::weightedMedianFilter (weighted_median_filter.hpp:64-90) in the library's own
+# integer definition (include/adf_wls.h; csrc/wmf_kernels.hip; the direct statement is tests/wmf_ref.py).
+# ---------------------------------------------------------------------------------------------
+_WMF = "weightedMedianFilter"
+_WMF_NOT_BUILT = {WMF_IV1: "WMF_IV1", WMF_IV2: "WMF_IV2", WMF_COS: "WMF_COS", WMF_JAC: "WMF_JAC"}
+
+
+def _wmf_weight_type(who, weightType):
+    try:
+        wt = int(weightType)
+    except (TypeError, ValueError):
+        raise AdfError(_lib.ADF_EBADARG, "%s: weightType must be WMF_EXP or WMF_OFF" % who)
+    if wt in _WMF_NOT_BUILT:
+        raise AdfError(_lib.ADF_EBADARG, "%s: %s is not built; WMF_EXP and WMF_OFF are" % (who, _WMF_NOT_BUILT[wt]))
+    if wt not in (WMF_EXP, WMF_OFF):
+        raise AdfError(_lib.ADF_EBADARG, "%s: weightType must be WMF_EXP or WMF_OFF" % who)
+    return wt
+
+
+def wmfWeightTable(sigma, weightType=WMF_EXP):
+    """The weight table T of weightedMedianFilter exactly as its calls build it (adf_wmf_weight_table_host): 3*256*256
+    uint32 entries indexed by the squared joint distance, lrint(exp(-i / (2 sigma^2)) * 65536) for WMF_EXP, all 65536 for
+    WMF_OFF.  Host only: no device is touched."""
+    wt = _wmf_weight_type("wmfWeightTable", weightType)
+    table = np.empty(_lib.WMF_TABLE_LEVELS, np.uint32)
+    _lib.check(_lib.lib().adf_wmf_weight_table_host(float(sigma), wt, table.ctypes.data, table.size))
+    return table
+
+
+def weightedMedianFilter(joint, src, r, sigma=25.5, weightType=WMF_EXP, mask=None, ignoreValue=None, dst=None):
+    """cv::ximgproc::weightedMedianFilter(joint, src, dst, r, sigma, weightType, mask) in the library's own integer
+    definition (include/adf_wls.h): per pixel the weighted median of the used pixels of the (2r+1)^2 window clipped at the
+    border, with weights T[squared joint distance] -- the smallest window value v whose weight at or below it reaches half
+    the total.  `src`: uint8, int16 or float32, (H,W) or a batch (N,H,W), one channel; `joint`: uint8 of that size with 1
+    or 3 channels; `mask`: uint8, 0 = ignored.  Extension: `ignoreValue` -- pixels holding it are ignored too, and get a
+    value from their neighbours: (minDisparity-1)*16 fills the holes validateDisparity and filterSpeckles leave.  A pixel
+    whose window has no used pixel of positive weight keeps its value.  1 <= r <= 31; weightType WMF_EXP or WMF_OFF (the
+    plain median); WMF_IV1, WMF_IV2, WMF_COS, WMF_JAC and multi-channel sources are not built.  Torch CUDA tensors run on
+    the device, asynchronously on torch's current stream (the first call with a new sigma uploads its table
+    synchronously and cannot be captured into a graph; later ones can); numpy arrays take the host entry point.
+    Returns dst, which must not overlap the inputs."""
+    if joint is None or src is None:
+        raise AdfError(_lib.ADF_EBADARG, "%s: joint and src must not be empty" % _WMF)
+    wt = _wmf_weight_type(_WMF, weightType)
+    nd = len(src.shape)
+    if nd not in (2, 3):
+        raise AdfError(_lib.ADF_EBADARG, "%s: src must be (H,W) or a batch (N,H,W) of one-channel maps" % _WMF)
+    batched = nd == 3
+    for dt in (np.uint8, np.int16, np.float32):
+        if _map_dtype(src, dt) is not None:
+            break
+    else:
+        raise AdfError(_lib.ADF_EBADARG, "%s: src must be uint8 (CV_8U), int16 (CV_16S) or float32 (CV_32F)" % _WMF)
+    S = _Image(src, dt, "src", batched)
+    J = _Image(joint, np.uint8, "joint", batched, allow_channels=(1, 3))
+    M = None if mask is None else _Image(mask, np.uint8, "mask", batched)
+    if dst is None:
+        dst = _out_like(S, batched, dt)
+    D = _Image(dst, dt, "dst", batched)
+    for im, what in ((J, "joint"), (M, "mask"), (D, "dst")):
+        if im is None:
+            continue
+        if (im.n, im.h, im.w) != (S.n, S.h, S.w) or im.device != S.device:
+            raise AdfError(_lib.ADF_ESIZE, "%s: %s must have src's size on its side (host or device)" % (_WMF, what))
+        if S.device and im.keep.device != S.keep.device:
+            raise AdfError(_lib.ADF_EBADARG, "%s: %s lives on %s, src on %s" % (_WMF, what, im.keep.device, S.keep.device))
+    args = (S.n, J.ptr, J.stride, J.pair_stride, J.c, S.ptr, S.stride, S.pair_stride, _DEPTH[dt], D.ptr, D.stride, D.pair_stride,
+            S.w, S.h, int(r), float(sigma), wt, M.ptr if M else None, M.stride if M else 0, M.pair_stride if M else 0,
+            0 if ignoreValue is None else 1, 0.0 if ignoreValue is None else float(ignoreValue))
+    if not S.device:
+        _call("adf_weighted_median_filter", S, args)
+        return dst
+    with torch.cuda.device(S.keep.device):
+        _call("adf_weighted_median_filter", S, args)
+    return dst
 
 
 def createDisparityWLSFilter(matcher_left):

@@ -335,7 +335,8 @@ void adf_fgs_destroy(adf_fgs_t* h);
  * reference's own perf test (perf/perf_fgs_filter.cpp:70-76) -- would pay hipMalloc + hipFree (which waits for the whole
  * device) and 3*256*256 libm calls for the weight table on every call.  The library therefore keeps a destroyed
  * filter's device block (at most 8 blocks / 3 GB per process, handed to the next filter behind the event of its last
- * user: no host synchronisation) and the weight tables by (device, sigma) (16 of them).  This returns all of it to the
+ * user: no host synchronisation) and the weight tables by (device, sigma) (16 of them; the weighted median filter's
+ * tables by (device, sigma, weight type), 16 more).  This returns all of it to the
  * driver; it waits for the blocks' last users.  (The library does the same on its own whenever one of its device
  * allocations -- a filter's workspace, a matcher's -- is refused for want of memory, and tries again; allocations the
  * CALLER makes in the same process do not see the cache: call this before a large one.) */
@@ -938,6 +939,80 @@ int adf_rectify_views_host(int n_images, const uint8_t* src, ptrdiff_t src_strid
                            int srcH, int channels, const adf_rectify_params* prm, uint8_t* dst, ptrdiff_t dst_stride,
                            ptrdiff_t dst_image_stride, int W, int H, int interpolation, int border_mode,
                            const uint8_t* border_value /* 3 */);
+
+/* ---------------- weighted median filter (cv::ximgproc::weightedMedianFilter) ----------------
+ * cv::ximgproc::weightedMedianFilter(joint, src, dst, r, sigma, weightType, mask) (weighted_median_filter.hpp:64-90,
+ * weighted_median_filter.cpp; Zhang et al., "100+ Times Faster Weighted Median Filter"): the operator that fills and
+ * de-noises a disparity map from the map's own values -- edge-aware through a joint image, blind to masked pixels (which
+ * is what fills holes), and returning only values that occur in the window, so it never blends foreground and background.
+ * In the chain: matcher -> adf_validate_disparity_* / adf_filter_speckles_* -> this, with ignore_value =
+ * (minDisparity-1)*16 -> adf_reproject_*; or in front of the WLS filter.
+ *
+ * This is the library's OWN definition: the reference cannot be matched bit for bit (below).  The rule it converges to
+ * (weighted_median_filter.cpp:493-543: the smallest cut with non-negative balance) is kept.
+ *
+ * Inputs.  n_maps equally sized maps of W x H, `*_map_stride` bytes apart, rows `*_stride` bytes apart.
+ *   - src, dst: ONE channel, depth ADF_8U, ADF_16S or ADF_32F, dst of the same depth.  Multi-channel sources are not
+ *     built: callers split them.
+ *   - joint: 8-bit, joint_channels 1 or 3 (interleaved), the size of src.
+ *   - mask (optional): an 8-bit plane of that size, 0 = ignored; NULL = no mask.
+ *   - use_ignore != 0 with ignore_value (optional; ignore_value is not looked at otherwise).
+ * Whether a tap is used.  Pixel q is used when mask(q) != 0 and, with use_ignore, src(q) != ignore_value (compared as
+ * doubles).  In a float map a NaN is never used; +-inf are ordinary ordered values; float values are ordered as IEEE
+ * totals, -0.0 below +0.0, and the output is the BITS of a tap.  For ADF_8U and ADF_16S ignore_value must be an integer
+ * inside the depth's range (ADF_EBADARG otherwise).
+ * Window.  For pixel p every q with |qx - px| <= r and |qy - py| <= r inside the image: clipped at the border, nothing is
+ * replicated (as weighted_median_filter.cpp:437-441, 549-550).
+ * Weights, all integers.  w(p, q) = T[ sum_c (joint_c(p) - joint_c(q))^2 ], the index 0 .. 3*255^2:
+ *   - ADF_WMF_EXP: T[i] = (uint32_t)lrint(exp(-(double)i / (2.0 * sigma * sigma)) * 65536.0), built on the host with libm
+ *     like the filters' table (adf_weight_table_host).  For a 1-channel joint this is weighted_median_filter.cpp:252-263
+ *     in fixed point; for 3 channels it is the EXACT colour distance where the reference has its cluster centres;
+ *   - ADF_WMF_OFF: T[i] = 65536, the plain median of the used pixels;
+ *   - cv's WMF_IV1, WMF_IV2, WMF_COS and WMF_JAC are not built: every other weight_type is ADF_EBADARG.
+ * Result.  Tot = sum of w over the used taps, L(v) = sum of w over the used taps with src(q) <= v: dst(p) is the smallest
+ * tap value v with 2 * L(v) >= Tot.  Tot == 0 -- no tap used, or every used tap of weight 0 -- gives dst(p) = src(p)
+ * unchanged.  A pixel that is itself unused still gets its result from its neighbours: that is the hole filling.
+ * Radius.  1 <= r <= ADF_WMF_MAX_RADIUS = 31; the bound is arithmetic: 63^2 * 65536 < 2^28, so Tot and 2 * L fit unsigned
+ * 32-bit.  Every sum is an integer sum: the result does not depend on summation order, is bit-exact against the direct
+ * NumPy statement tests/wmf_ref.py and identical from run to run (csrc/wmf_kernels.hip).
+ * Deviations from the reference, all deliberate:
+ *   - fixed-point integer weights where it accumulates floats in a history-dependent order (:55-131, 277-347, 475-543);
+ *   - the exact colour distance of a 3-channel joint where it k-means-clusters the joint to 256 indices;
+ *   - ADF_16S and ADF_32F sources are NOT quantised to 256 levels: the result is one of the source's own values;
+ *   - four weight types (IV1, IV2, COS, JAC) and multi-channel sources are not built.
+ * Refused: sigma not finite or not > 0, r outside [1, 31], an unknown depth, weight_type or joint_channels, NULL joint /
+ * src / dst, bases or strides not aligned to the depth (2 bytes for ADF_16S, 4 for ADF_32F), dst overlapping (by the byte
+ * ranges they span) src, joint or mask (all ADF_EBADARG); W*H at or above 2^31, strides smaller than a row, destination
+ * maps of a batch that overlap each other (ADF_ESIZE).  All of this is checked before a device is touched.
+ *
+ * adf_wmf_weight_table_host: T exactly as the calls build it, ADF_WMF_TABLE_LEVELS entries.  Host only -- no device is
+ * touched.
+ * (the device copy of T lives in a process-wide cache by (device, sigma, weight type), 16 of them, which
+ * adf_release_cached_memory frees: coming back to a sigma is free and capturable; a NEW value builds its table on the
+ * host inside the call and uploads it with one synchronous copy -- use each sigma once BEFORE capturing calls with it into
+ * a hipGraph.  Every later call with that sigma allocates nothing and never synchronises.)
+ * _device: device pointers on the current HIP device, asynchronous on `stream`.  _host: host pointers; copies, runs and
+ * synchronises. */
+#define ADF_WMF_EXP 0 /* cv::ximgproc::WMF_EXP */
+#define ADF_WMF_OFF 5 /* cv::ximgproc::WMF_OFF */
+#define ADF_WMF_WEIGHT_ONE 65536
+#define ADF_WMF_TABLE_LEVELS (3 * 256 * 256)
+#define ADF_WMF_MAX_RADIUS 31
+int adf_wmf_weight_table_host(double sigma, int weight_type, uint32_t* table, int levels);
+int adf_weighted_median_filter_device(int n_maps,
+                                      const uint8_t* joint, ptrdiff_t joint_stride, ptrdiff_t joint_map_stride, int joint_channels,
+                                      const void* src, ptrdiff_t src_stride, ptrdiff_t src_map_stride, int depth,
+                                      void* dst, ptrdiff_t dst_stride, ptrdiff_t dst_map_stride,
+                                      int W, int H, int r, double sigma, int weight_type,
+                                      const uint8_t* mask, ptrdiff_t mask_stride, ptrdiff_t mask_map_stride,
+                                      int use_ignore, double ignore_value, void* stream);
+int adf_weighted_median_filter_host(int n_maps,
+                                    const uint8_t* joint, ptrdiff_t joint_stride, ptrdiff_t joint_map_stride, int joint_channels,
+                                    const void* src, ptrdiff_t src_stride, ptrdiff_t src_map_stride, int depth,
+                                    void* dst, ptrdiff_t dst_stride, ptrdiff_t dst_map_stride,
+                                    int W, int H, int r, double sigma, int weight_type,
+                                    const uint8_t* mask, ptrdiff_t mask_stride, ptrdiff_t mask_map_stride,
+                                    int use_ignore, double ignore_value);
 
 #ifdef __cplusplus
 }

@@ -121,6 +121,45 @@ inline void validateDisparity(Mat& disparity, const Mat& cost, int minDisparity,
                                       minDisparity, numberOfDisparities, disp12MaxDiff));
 }
 
+// cv::ximgproc::weightedMedianFilter(joint, src, dst, r, sigma, weightType, mask) (weighted_median_filter.hpp:64-90) on host
+// Mats through the library's host entry, in the library's own integer definition (adf_weighted_median_filter_* in
+// adf_wls.h: fixed-point weights, the exact colour distance of a 3-channel joint, no quantisation of CV_16S / CV_32F
+// sources).  joint: CV_8UC1 or CV_8UC3; src: CV_8UC1, CV_16SC1 or CV_32FC1 of its size (multi-channel sources are not built:
+// split them); mask: empty or CV_8UC1, 0 = ignored.  WMF_EXP and WMF_OFF are built; WMF_IV1, WMF_IV2, WMF_COS and WMF_JAC
+// are refused.  The overload with ignoreValue (extension) also ignores -- and so fills from their neighbours -- the pixels
+// that hold it: (minDisparity - 1) * 16 for a matcher's map after validateDisparity / filterSpeckles.
+enum WMFWeightType { WMF_EXP, WMF_IV1, WMF_IV2, WMF_COS, WMF_JAC, WMF_OFF }; // cv's values
+inline void weighted_median(const Mat& joint, const Mat& src, Mat& dst, int r, double sigma, int weightType, const Mat& mask,
+                            const double* ignoreValue)
+{
+    if (src.empty() || mat_channels(src) != 1 || (mat_depth(src) != D8U && mat_depth(src) != D16S && mat_depth(src) != D32F))
+        throw Exception(ADF_EBADARG, "weightedMedianFilter: src must be a non-empty CV_8UC1, CV_16SC1 or CV_32FC1 image");
+    if (joint.empty() || mat_depth(joint) != D8U)
+        throw Exception(ADF_EBADARG, "weightedMedianFilter: joint must be a non-empty CV_8UC1 or CV_8UC3 image");
+    if (joint.rows != src.rows || joint.cols != src.cols) throw Exception(ADF_ESIZE, "weightedMedianFilter: joint must have src's size");
+    if (!mask.empty() && (mat_depth(mask) != D8U || mat_channels(mask) != 1))
+        throw Exception(ADF_EBADARG, "weightedMedianFilter: mask must be empty or a CV_8UC1 image");
+    if (!mask.empty() && (mask.rows != src.rows || mask.cols != src.cols)) throw Exception(ADF_ESIZE, "weightedMedianFilter: mask must have src's size");
+    Mat out;                                                             // (dst may be src: the result lands in a new Mat)
+    mat_create(out, src.rows, src.cols, mat_depth(src), 1);
+    const int depth = mat_depth(src) == D8U ? ADF_8U : mat_depth(src) == D16S ? ADF_16S : ADF_32F;
+    check(adf_weighted_median_filter_host(1, joint.data, mat_step(joint), 0, mat_channels(joint), src.data, mat_step(src), 0, depth,
+                                          out.data, mat_step(out), 0, src.cols, src.rows, r, sigma, weightType,
+                                          mask.empty() ? nullptr : mask.data, mask.empty() ? 0 : mat_step(mask), 0,
+                                          ignoreValue ? 1 : 0, ignoreValue ? *ignoreValue : 0.0));
+    dst = out;
+}
+inline void weightedMedianFilter(const Mat& joint, const Mat& src, Mat& dst, int r, double sigma = 25.5, int weightType = WMF_EXP,
+                                 const Mat& mask = Mat())
+{
+    weighted_median(joint, src, dst, r, sigma, weightType, mask, nullptr);
+}
+inline void weightedMedianFilter(const Mat& joint, const Mat& src, Mat& dst, int r, double sigma, int weightType, const Mat& mask,
+                                 double ignoreValue)
+{
+    weighted_median(joint, src, dst, r, sigma, weightType, mask, &ignoreValue);
+}
+
 // cv::stereo::censusTransform(image, kernelSize, dist, type) (modules/stereo descriptor.hpp:428, descriptor.cpp:77-98) on a
 // CV_8UC1 host Mat, through the library's host entry: the census descriptor of every pixel, type
 // ADF_SGBM_COST_CENSUS_DENSE (kernelSize 3, 5, 7), ADF_SGBM_COST_CENSUS_SPARSE (5, 7, 9, 11), the modified census
