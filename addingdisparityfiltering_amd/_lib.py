@@ -24,6 +24,7 @@ SGBM_RIGHT_MATCHER, SGBM_RIGHT_FROM_VOLUME = 0, 1    # adf_sgbm_compute_both_*'s
 MISSING_NONE, MISSING_MIN, MISSING_VALUE = 0, 1, 2    # adf_reproject_params.missing_mode (include/adf_wls.h)
 WMF_EXP, WMF_IV1, WMF_IV2, WMF_COS, WMF_JAC, WMF_OFF = range(6)    # cv::ximgproc::WMFWeightType; EXP and OFF are built (ADF_WMF_*)
 WMF_WEIGHT_ONE, WMF_TABLE_LEVELS, WMF_MAX_RADIUS = 65536, 3 * 256 * 256, 31
+GF_MAX_RADIUS = 31    # ADF_GF_MAX_RADIUS
 
 
 class AdfError(RuntimeError):
@@ -65,6 +66,7 @@ _RECTIFY_MAP_DEV = [C.POINTER(RectifyParams), _i, _i, _vp, _pd, _vp, _pd, _vp]
 _REMAP_DEV = [_i, _vp, _pd, _pd, _i, _i, _i, _vp, _pd, _vp, _pd, _vp, _pd, _pd, _i, _i, _i, _i, _vp, _vp]
 _RECTIFY_VIEWS_DEV = [_i, _vp, _pd, _pd, _i, _i, _i, C.POINTER(RectifyParams), _vp, _pd, _pd, _i, _i, _i, _i, _vp, _vp]
 _WMF_DEV = [_i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _i, _i, _d, _i, _vp, _pd, _pd, _i, _d, _vp]
+_GF_DEV = [_i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _i, _i, _i, _d, _vp, _sz, _vp]
 _FILTER_SCALED_DEV = [_vp, _i, _vp, _pd, _pd, _i, _i, _vp, _pd, _pd, _i, _i, _i, _vp, _pd, _pd, _vp, _pd, _pd,
                       C.POINTER(Rect), _vp]
 # adf_wls_filter_typed_*: the scaled call with a depth behind the left map's strides and one behind the output's
@@ -175,6 +177,9 @@ SYMBOLS = [
     ("adf_wmf_weight_table_host", _i, [_d, _i, _vp, _i]),
     ("adf_weighted_median_filter_device", _i, _WMF_DEV),
     ("adf_weighted_median_filter_host", _i, _WMF_DEV[:-1]),
+    ("adf_guided_filter_workspace_bytes", _sz, [_i, _i, _i, _i]),
+    ("adf_guided_filter_device", _i, _GF_DEV),
+    ("adf_guided_filter_host", _i, _GF_DEV[:-3]),
 ]
 
 _lib = None

@@ -21,6 +21,8 @@ edge_filter.hpp (EF.hpp), over the C-ABI in include/adf_wls.h:
     reprojectImageTo3D(disparity, Q, handleMissingValues, ddepth), pointCloud(...)   calib3d (outside the reference tree)
     initUndistortRectifyMap(K, dist, R, P, size), remap(src, map1, map2), rectifyViews(...)   calib3d / imgproc (outside the reference tree)
     weightedMedianFilter(joint, src, r, sigma, weightType, mask, ignoreValue)   weighted_median_filter.hpp:64-90 (the library's own integer definition)
+    guidedFilter(guide, src, radius, eps, dDepth)   EF.hpp:180  / guided_filter.cpp (the library's own exact definition)
+    createGuidedFilter(guide, radius, eps) -> GuidedFilter.filter(src, dst, dDepth)   EF.hpp:158, 143
 
 Images are numpy arrays (host path: copied to the GPU and back) or torch CUDA
 tensors (device path: zero-copy, asynchronous on torch's current stream).  A
@@ -39,6 +41,7 @@ from ._lib import SGBM_COST_MCT_DENSE, SGBM_COST_MCT_SPARSE, SGBM_COST_CENSUS_CS
 from ._lib import BM_COST_MCT_DENSE, BM_COST_MCT_SPARSE, BM_COST_CENSUS_CS  # noqa: F401  (re-exported)
 from ._lib import SGBM_RIGHT_MATCHER, SGBM_RIGHT_FROM_VOLUME  # noqa: F401  (re-exported)
 from ._lib import WMF_EXP, WMF_IV1, WMF_IV2, WMF_COS, WMF_JAC, WMF_OFF  # noqa: F401  (cv's WMFWeightType; EXP and OFF are built)
+from ._lib import GF_MAX_RADIUS  # noqa: F401  (re-exported)
 from ._lib import AdfError, PATH_CONF_BAND, PATH_FUSED_FIRST_PASS, PATH_MERGED_PREP, PATH_ROW_WEIGHTS_GUIDE, PATH_SCALED_FUSED, PATH_SCALED_HALF, Rect, SOLVER_EXACT, SOLVER_WAVE  # noqa: F401  (re-exported)
 
 try:  # torch is optional plumbing: device memory and streams only
@@ -1296,6 +1299,104 @@ def weightedMedianFilter(joint, src, r, sigma=25.5, weightType=WMF_EXP, mask=Non
     with torch.cuda.device(S.keep.device):
         _call("adf_weighted_median_filter", S, args)
     return dst
+
+# ---------------------------------------------------------------------------------------------
+# cv::ximgproc::guidedFilter / createGuidedFilter / GuidedFilter (EF.hpp:143-180, guided_filter.cpp) in the library's own
+# exact definition (include/adf_wls.h; csrc/guided_filter_kernels.hip; the direct statement is tests/gf_ref.py).
+# ---------------------------------------------------------------------------------------------
+_GF = "guidedFilter"
+CV_8U, CV_16S = 0, 3    # cv's depth codes (CV_32F is above): what dDepth takes
+_GF_DTYPE = {CV_8U: np.uint8, CV_16S: np.int16, CV_32F: np.float32}
+
+
+def guidedFilterWorkspaceBytes(n, H, W, channels):
+    """Bytes of device workspace guidedFilter needs for n maps of H x W under a guide of `channels` channels
+    (adf_guided_filter_workspace_bytes): the channels + 1 float coefficient planes between its two launches."""
+    return int(_lib.lib().adf_guided_filter_workspace_bytes(int(n), int(W), int(H), int(channels)))
+
+
+def guidedFilter(guide, src, radius, eps, dDepth=-1, dst=None, workspace=None):
+    """cv::ximgproc::guidedFilter(guide, src, dst, radius, eps, dDepth) in the library's own definition (include/adf_wls.h):
+    per (2 radius + 1)^2 window, BORDER_REFLECT, the linear model q = a . guide + b of the source with regulariser eps (in
+    squared grey levels of the 0..255 guide), the models covering a pixel averaged -- exact integer statistics, one stated
+    operation order, bit-exact against tests/gf_ref.py.
+
+        guide    uint8, (H,W) or (H,W,3); with a batch (N,H,W) or (N,H,W,3)
+        src      uint8, int16 or float32, (H,W) or a batch (N,H,W), one channel
+        radius   0 .. 31 (GF_MAX_RADIUS)
+        eps      finite, > 0
+        dDepth   -1 = src's depth, or CV_8U, CV_16S, CV_32F: integer outputs are rounded half to even and saturated
+        dst      None, or an array / tensor of that depth and src's shape that overlaps neither input
+
+    The filter is not blind to a matcher's invalid value (minDisparity-1)*16: fill the holes first (weightedMedianFilter
+    with ignoreValue).  Multi-channel sources are not built: split them.  Torch CUDA tensors run on the device,
+    asynchronously on torch's current stream; `workspace` (device path only): a CUDA tensor of at least
+    guidedFilterWorkspaceBytes(...) bytes -- the call then allocates nothing and may be captured into a CUDA graph; None =
+    the library's cached scratch.  Numpy arrays take the host entry point.  Returns dst."""
+    if guide is None or src is None:
+        raise AdfError(_lib.ADF_EBADARG, "%s: guide and src must not be empty" % _GF)
+    nd = len(src.shape)
+    if nd not in (2, 3):
+        raise AdfError(_lib.ADF_EBADARG, "%s: src must be (H,W) or a batch (N,H,W) of one-channel maps" % _GF)
+    batched = nd == 3
+    for dt in (np.uint8, np.int16, np.float32):
+        if _map_dtype(src, dt) is not None:
+            break
+    else:
+        raise AdfError(_lib.ADF_EBADARG, "%s: src must be uint8 (CV_8U), int16 (CV_16S) or float32 (CV_32F)" % _GF)
+    if dDepth != -1 and dDepth not in _GF_DTYPE:
+        raise AdfError(_lib.ADF_EBADARG, "%s: dDepth must be -1, CV_8U, CV_16S or CV_32F" % _GF)
+    ddt = dt if dDepth == -1 else _GF_DTYPE[dDepth]
+    S = _Image(src, dt, "src", batched)
+    G = _Image(guide, np.uint8, "guide", batched, allow_channels=(1, 3))
+    if dst is None:
+        dst = _out_like(S, batched, ddt)
+    D = _Image(dst, ddt, "dst", batched)
+    for im, what in ((G, "guide"), (D, "dst")):
+        if (im.n, im.h, im.w) != (S.n, S.h, S.w) or im.device != S.device:
+            raise AdfError(_lib.ADF_ESIZE, "%s: %s must have src's size on its side (host or device)" % (_GF, what))
+        if S.device and im.keep.device != S.keep.device:
+            raise AdfError(_lib.ADF_EBADARG, "%s: %s lives on %s, src on %s" % (_GF, what, im.keep.device, S.keep.device))
+    args = (S.n, G.ptr, G.stride, G.pair_stride, G.c, S.ptr, S.stride, S.pair_stride, _DEPTH[dt], D.ptr, D.stride, D.pair_stride,
+            _DEPTH[ddt], S.w, S.h, int(radius), float(eps))
+    if not S.device:
+        if workspace is not None:
+            raise AdfError(_lib.ADF_EBADARG, "%s: a workspace goes with CUDA tensors only" % _GF)
+        _call("adf_guided_filter", S, args)
+        return dst
+    ws, ws_bytes = None, 0
+    if workspace is not None:
+        if not (_is_torch(workspace) and workspace.is_cuda and workspace.is_contiguous()):
+            raise AdfError(_lib.ADF_EBADARG, "%s: workspace must be a contiguous CUDA tensor (or None)" % _GF)
+        if workspace.device != S.keep.device:
+            raise AdfError(_lib.ADF_EBADARG, "%s: workspace lives on %s, src on %s" % (_GF, workspace.device, S.keep.device))
+        ws, ws_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    with torch.cuda.device(S.keep.device):
+        _call("adf_guided_filter", S, args + (ws, ws_bytes))
+    return dst
+
+
+class GuidedFilter:
+    """cv::ximgproc::GuidedFilter (EF.hpp:130-144): holds the guide, radius and eps; filter(src) is
+    guidedFilter(guide, src, radius, eps).  The guide's statistics are recomputed per call (they ride along in the
+    coefficient kernel), so the object saves no work: it is the reference's interface."""
+
+    def __init__(self, guide, radius, eps):
+        if guide is None:
+            raise AdfError(_lib.ADF_EBADARG, "%s: guide must not be empty" % _GF)
+        if not (0 <= int(radius) <= GF_MAX_RADIUS):
+            raise AdfError(_lib.ADF_EBADARG, "%s: radius must lie in [0, %d]" % (_GF, GF_MAX_RADIUS))
+        if not (math.isfinite(float(eps)) and float(eps) > 0):
+            raise AdfError(_lib.ADF_EBADARG, "%s: eps must be finite and > 0" % _GF)
+        self._guide, self._radius, self._eps = guide, int(radius), float(eps)
+
+    def filter(self, src, dst=None, dDepth=-1, workspace=None):
+        return guidedFilter(self._guide, src, self._radius, self._eps, dDepth, dst, workspace)
+
+
+def createGuidedFilter(guide, radius, eps):
+    """EF.hpp:158: a GuidedFilter on `guide` (held by reference, not copied)."""
+    return GuidedFilter(guide, radius, eps)
 
 
 def createDisparityWLSFilter(matcher_left):

@@ -1014,6 +1014,88 @@ int adf_weighted_median_filter_host(int n_maps,
                                     const uint8_t* mask, ptrdiff_t mask_stride, ptrdiff_t mask_map_stride,
                                     int use_ignore, double ignore_value);
 
+/* ---------------- guided filter (cv::ximgproc::guidedFilter / GuidedFilter) ----------------
+ * createGuidedFilter(guide, radius, eps) (EF.hpp:158), GuidedFilter::filter(src, dst, dDepth) (EF.hpp:143) and
+ * guidedFilter(guide, src, dst, radius, eps, dDepth) (EF.hpp:180; modules/ximgproc/src/guided_filter.cpp = GF.cpp; He et
+ * al., "Guided Image Filtering"): per window a linear model q = a . I + b of the source in the guide, the models of all
+ * windows that cover a pixel averaged.  No recursion along a scanline: two streaming launches per call.  In the chain:
+ * matcher -> adf_validate_disparity_* / adf_filter_speckles_* -> adf_weighted_median_filter_* (which fills the holes: this
+ * filter is NOT blind to (minDisparity-1)*16, it blends it in) -> this -> adf_reproject_*; or on the float map of a
+ * learned matcher.
+ *
+ * This is the library's OWN definition.  It keeps GF.cpp's window, border, meaning of eps and linear model; it has exact
+ * integer statistics and one stated operation order, so the result is bit-exact against the direct NumPy statement
+ * tests/gf_ref.py and identical from run to run.
+ *
+ * Inputs.  n_maps equally sized maps of W x H, `*_map_stride` bytes apart, rows `*_stride` bytes apart.
+ *   - guide: 8-bit, guide_channels 1 or 3 (interleaved), the size of src.
+ *   - src: ONE channel, depth ADF_8U, ADF_16S or ADF_32F.
+ *   - dst: one channel, depth dst_depth, any of the three, independent of src's (cv's dDepth).
+ *   - 0 <= r <= ADF_GF_MAX_RADIUS = 31.
+ *   - eps finite and > 0, in squared grey levels of the 0..255 guide (GF.cpp:333, 354: the guide is not scaled to [0, 1]).
+ * Window and border.  The (2r+1)^2 square, N = (2r+1)^2, at every depth with BORDER_REFLECT (GF.cpp:160-163): index i of
+ * an axis of length n reads m = i mod 2n (non-negative), then m < n ? m : 2n-1-m.  The radius may exceed the image
+ * (numpy.pad(mode="symmetric")).
+ * Stage 1, the coefficients of every pixel's window (I_c the guide's channels, p the source):
+ *   - integer sources: S_c = sum I_c, S_cd = sum I_c I_d, S_p = sum p, S_cp = sum I_c p are integers;
+ *     V_cd = N S_cd - S_c S_d and n_c = N S_cp - S_c S_p in int64 (every term is below 3969^2 * 255 * 32768 < 2^53, so their
+ *     conversion to double is exact);
+ *   - E = eps * (double)N * (double)N, evaluated left to right;
+ *   - ADF_32F sources: S_p and S_cp are double sums of (double)p and (double)I_c * (double)p in the fixed order of stage 2
+ *     (column first, then row); n_c = (double)N * S_cp - (double)S_c * S_p.  Integer-valued float maps therefore give the
+ *     int16 call's bits; non-finite source values give what IEEE arithmetic gives in that order;
+ *   - 1 channel: a_0 = (float)(n_0 / (V_00 + E));
+ *   - 3 channels, in double, no contraction, exactly these expressions:
+ *       s00 = V_00 + E, s11 = V_11 + E, s22 = V_22 + E, s01 = V_01, s02 = V_02, s12 = V_12;
+ *       c00 = s11*s22 - s12*s12, c01 = s02*s12 - s01*s22, c02 = s01*s12 - s02*s11;
+ *       c11 = s00*s22 - s02*s02, c12 = s01*s02 - s00*s12, c22 = s00*s11 - s01*s01;
+ *       det = (s00*c00 + s01*c01) + s02*c02;
+ *       a_0 = (float)(((c00*n_0 + c01*n_1) + c02*n_2) / det);
+ *       a_1 = (float)(((c01*n_0 + c11*n_1) + c12*n_2) / det);
+ *       a_2 = (float)(((c02*n_0 + c12*n_1) + c22*n_2) / det);
+ *     det not finite or not > 0: every a_c is 0;
+ *   - b = (float)((((double)S_p - (double)a_0 * S_0) - (double)a_1 * S_1 - (double)a_2 * S_2) / (double)N), the
+ *     subtractions left to right.
+ * Stage 2, the output.  SA_c and SB are the float32 window sums of a_c and b in ONE fixed order:
+ *   - the column sum C(y, x) = ((v(y-r, x) + v(y-r+1, x)) + ...) + v(y+r, x), top to bottom, reflected indices, every
+ *     partial sum rounded to float32;
+ *   - then the row sum S(y, x) = ((C(y, x-r) + C(y, x-r+1)) + ...) + C(y, x+r), left to right;
+ *   - q = (((double)SB + (double)SA_0 * I_0) + (double)SA_1 * I_1 + (double)SA_2 * I_2) / (double)N, left to right;
+ *   - dst = (float)q for ADF_32F; rint(q) (half to even, cv's saturate_cast) saturated to the depth for ADF_8U / ADF_16S
+ *     (a NaN gives the depth's minimum, as cv's saturate_cast does).
+ * Deviations from the reference, all deliberate:
+ *   - exact covariances where it forms mean(I p) - mean(I) mean(p) in float32 (GF.cpp:487-510, 330-358): on CV_16S
+ *     disparities mean(I p) reaches 10^6..10^7, where a float32 ulp is 0.5..1, so its covariance is wrong by about its own
+ *     size wherever the guide is flat;
+ *   - CV_16S sources (it takes CV_8U and CV_32F only, GF.cpp:707);
+ *   - one-channel sources only (callers split them, as with the weighted median);
+ *   - guides of 1 or 3 channels of 8 bits;
+ *   - the guide's statistics are recomputed per call: there is no init stage (they ride along in the same kernel);
+ *   - its box means are cv::boxFilter(..., BORDER_REFLECT) of un-vendored OpenCV: bit parity is unpinnable.
+ * Refused: eps not finite or not > 0, r outside [0, 31], an unknown depth or guide_channels, NULL guide / src / dst, bases
+ * or strides not aligned to the depth (2 bytes for ADF_16S, 4 for ADF_32F), dst overlapping (by the byte ranges they span)
+ * guide or src (all ADF_EBADARG); W*H at or above 2^31, strides smaller than a row, destination maps of a batch that
+ * overlap each other (ADF_ESIZE).  All of this is checked before a device is touched.
+ * Workspace: the coefficient planes between the two launches, (guide_channels + 1) float planes per map --
+ * adf_guided_filter_workspace_bytes(n_maps, W, H, guide_channels) bytes of 4-byte aligned device memory (0 for arguments
+ * the calls refuse).  workspace == NULL takes library scratch from the process-wide cache (no allocation once it is
+ * warm); a caller-supplied workspace makes the call capturable into a hipGraph.
+ * _device: device pointers on the current HIP device, asynchronous on `stream`.  _host: host pointers; copies, runs and
+ * synchronises. */
+#define ADF_GF_MAX_RADIUS 31
+size_t adf_guided_filter_workspace_bytes(int n_maps, int W, int H, int guide_channels);
+int adf_guided_filter_device(int n_maps,
+                             const uint8_t* guide, ptrdiff_t guide_stride, ptrdiff_t guide_map_stride, int guide_channels,
+                             const void* src, ptrdiff_t src_stride, ptrdiff_t src_map_stride, int src_depth,
+                             void* dst, ptrdiff_t dst_stride, ptrdiff_t dst_map_stride, int dst_depth,
+                             int W, int H, int r, double eps,
+                             void* workspace, size_t workspace_bytes, void* stream);
+int adf_guided_filter_host(int n_maps,
+                           const uint8_t* guide, ptrdiff_t guide_stride, ptrdiff_t guide_map_stride, int guide_channels,
+                           const void* src, ptrdiff_t src_stride, ptrdiff_t src_map_stride, int src_depth,
+                           void* dst, ptrdiff_t dst_stride, ptrdiff_t dst_map_stride, int dst_depth,
+                           int W, int H, int r, double eps);
+
 #ifdef __cplusplus
 }
 #endif

@@ -160,6 +160,62 @@ inline void weightedMedianFilter(const Mat& joint, const Mat& src, Mat& dst, int
     weighted_median(joint, src, dst, r, sigma, weightType, mask, &ignoreValue);
 }
 
+// cv::ximgproc::guidedFilter(guide, src, dst, radius, eps, dDepth) (EF.hpp:180), createGuidedFilter(guide, radius, eps)
+// (EF.hpp:158) and GuidedFilter::filter(src, dst, dDepth) (EF.hpp:143) on host Mats through the library's host entry, in
+// the library's own definition (adf_guided_filter_* in adf_wls.h: exact integer statistics, one stated operation order,
+// BORDER_REFLECT).  guide: CV_8UC1 or CV_8UC3; src: CV_8UC1, CV_16SC1 or CV_32FC1 of its size (multi-channel sources are
+// not built: split them); dDepth: -1 (src's depth), CV_8U, CV_16S or CV_32F; 0 <= radius <= ADF_GF_MAX_RADIUS; eps > 0 in
+// squared grey levels of the 0..255 guide.  dst may be src.  The filter is not blind to a matcher's invalid value: run
+// weightedMedianFilter with ignoreValue first.
+inline void guidedFilter(const Mat& guide, const Mat& src, Mat& dst, int radius, double eps, int dDepth = -1)
+{
+    if (src.empty() || mat_channels(src) != 1 || (mat_depth(src) != D8U && mat_depth(src) != D16S && mat_depth(src) != D32F))
+        throw Exception(ADF_EBADARG, "guidedFilter: src must be a non-empty CV_8UC1, CV_16SC1 or CV_32FC1 image");
+    if (guide.empty() || mat_depth(guide) != D8U)
+        throw Exception(ADF_EBADARG, "guidedFilter: guide must be a non-empty CV_8UC1 or CV_8UC3 image");
+    if (guide.rows != src.rows || guide.cols != src.cols) throw Exception(ADF_ESIZE, "guidedFilter: guide must have src's size");
+    const int ddepth = dDepth == -1 ? mat_depth(src) : dDepth;
+    if (ddepth != D8U && ddepth != D16S && ddepth != D32F)
+        throw Exception(ADF_EBADARG, "guidedFilter: dDepth must be -1, CV_8U, CV_16S or CV_32F");
+    auto code = [](int depth) { return depth == D8U ? ADF_8U : depth == D16S ? ADF_16S : ADF_32F; };
+    Mat out;                                                             // (dst may be src: the result lands in a new Mat)
+    mat_create(out, src.rows, src.cols, ddepth, 1);
+    check(adf_guided_filter_host(1, guide.data, mat_step(guide), 0, mat_channels(guide), src.data, mat_step(src), 0, code(mat_depth(src)),
+                                 out.data, mat_step(out), 0, code(ddepth), src.cols, src.rows, radius, eps));
+    dst = out;
+}
+
+class GuidedFilter {
+public:
+    virtual ~GuidedFilter() {}
+    virtual void filter(const Mat& src, Mat& dst, int dDepth = -1) = 0;
+};
+
+// Holds its own copy of the guide (the caller's Mat may change or go away, as with cv's) and the parameters; the guide's
+// statistics are recomputed per call -- they ride along in the coefficient kernel -- so the object saves no work.
+class GuidedFilterImpl : public GuidedFilter {
+    Mat guide_;
+    int radius_;
+    double eps_;
+public:
+    GuidedFilterImpl(const Mat& guide, int radius, double eps) : radius_(radius), eps_(eps)
+    {
+        if (guide.empty() || mat_depth(guide) != D8U || (mat_channels(guide) != 1 && mat_channels(guide) != 3))
+            throw Exception(ADF_EBADARG, "createGuidedFilter: guide must be a non-empty CV_8UC1 or CV_8UC3 image");
+        if (radius < 0 || radius > ADF_GF_MAX_RADIUS) throw Exception(ADF_EBADARG, "createGuidedFilter: radius must lie in [0, 31]");
+        if (!std::isfinite(eps) || !(eps > 0.0)) throw Exception(ADF_EBADARG, "createGuidedFilter: eps must be finite and > 0");
+        mat_create(guide_, guide.rows, guide.cols, D8U, mat_channels(guide));
+        for (int y = 0; y < guide.rows; y++)
+            std::memcpy(guide_.data + (size_t)mat_step(guide_) * y, guide.data + (size_t)mat_step(guide) * y, (size_t)guide.cols * mat_channels(guide));
+    }
+    void filter(const Mat& src, Mat& dst, int dDepth = -1) override { guidedFilter(guide_, src, dst, radius_, eps_, dDepth); }
+};
+
+inline Ptr<GuidedFilter> createGuidedFilter(const Mat& guide, int radius, double eps)
+{
+    return Ptr<GuidedFilter>(new GuidedFilterImpl(guide, radius, eps));
+}
+
 // cv::stereo::censusTransform(image, kernelSize, dist, type) (modules/stereo descriptor.hpp:428, descriptor.cpp:77-98) on a
 // CV_8UC1 host Mat, through the library's host entry: the census descriptor of every pixel, type
 // ADF_SGBM_COST_CENSUS_DENSE (kernelSize 3, 5, 7), ADF_SGBM_COST_CENSUS_SPARSE (5, 7, 9, 11), the modified census
