@@ -25,6 +25,7 @@ MISSING_NONE, MISSING_MIN, MISSING_VALUE = 0, 1, 2    # adf_reproject_params.mis
 WMF_EXP, WMF_IV1, WMF_IV2, WMF_COS, WMF_JAC, WMF_OFF = range(6)    # cv::ximgproc::WMFWeightType; EXP and OFF are built (ADF_WMF_*)
 WMF_WEIGHT_ONE, WMF_TABLE_LEVELS, WMF_MAX_RADIUS = 65536, 3 * 256 * 256, 31
 GF_MAX_RADIUS = 31    # ADF_GF_MAX_RADIUS
+DTF_NC, DTF_IC, DTF_RF, DT_MAX_ITERS = 0, 1, 2, 8    # ADF_DTF_*, ADF_DT_MAX_ITERS
 
 
 class AdfError(RuntimeError):
@@ -67,6 +68,7 @@ _REMAP_DEV = [_i, _vp, _pd, _pd, _i, _i, _i, _vp, _pd, _vp, _pd, _vp, _pd, _pd, 
 _RECTIFY_VIEWS_DEV = [_i, _vp, _pd, _pd, _i, _i, _i, C.POINTER(RectifyParams), _vp, _pd, _pd, _i, _i, _i, _i, _vp, _vp]
 _WMF_DEV = [_i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _i, _i, _d, _i, _vp, _pd, _pd, _i, _d, _vp]
 _GF_DEV = [_i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _i, _i, _i, _d, _vp, _sz, _vp]
+_DT_DEV = [_i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _i, _i, _d, _d, _i, _i, _vp, _sz, _vp]
 _FILTER_SCALED_DEV = [_vp, _i, _vp, _pd, _pd, _i, _i, _vp, _pd, _pd, _i, _i, _i, _vp, _pd, _pd, _vp, _pd, _pd,
                       C.POINTER(Rect), _vp]
 # adf_wls_filter_typed_*: the scaled call with a depth behind the left map's strides and one behind the output's
@@ -180,6 +182,10 @@ SYMBOLS = [
     ("adf_guided_filter_workspace_bytes", _sz, [_i, _i, _i, _i]),
     ("adf_guided_filter_device", _i, _GF_DEV),
     ("adf_guided_filter_host", _i, _GF_DEV[:-3]),
+    ("adf_dt_filter_workspace_bytes", _sz, [_i, _i, _i]),
+    ("adf_dt_rf_table_host", _i, [_d, _d, _i, _i, _vp]),
+    ("adf_dt_filter_device", _i, _DT_DEV),
+    ("adf_dt_filter_host", _i, _DT_DEV[:-3]),
 ]
 
 _lib = None

@@ -23,6 +23,8 @@ edge_filter.hpp (EF.hpp), over the C-ABI in include/adf_wls.h:
     weightedMedianFilter(joint, src, r, sigma, weightType, mask, ignoreValue)   weighted_median_filter.hpp:64-90 (the library's own integer definition)
     guidedFilter(guide, src, radius, eps, dDepth)   EF.hpp:180  / guided_filter.cpp (the library's own exact definition)
     createGuidedFilter(guide, radius, eps) -> GuidedFilter.filter(src, dst, dDepth)   EF.hpp:158, 143
+    dtFilter(guide, src, sigmaSpatial, sigmaColor, mode, numIters)   EF.hpp:120  / dtfilter_cpu.hpp (DTF_RF only; the library's own exact definition)
+    createDTFilter(guide, sigmaSpatial, sigmaColor, mode, numIters) -> DTFilter.filter(src, dst, dDepth)   EF.hpp:100, 80
 
 Images are numpy arrays (host path: copied to the GPU and back) or torch CUDA
 tensors (device path: zero-copy, asynchronous on torch's current stream).  A
@@ -42,6 +44,7 @@ from ._lib import BM_COST_MCT_DENSE, BM_COST_MCT_SPARSE, BM_COST_CENSUS_CS  # no
 from ._lib import SGBM_RIGHT_MATCHER, SGBM_RIGHT_FROM_VOLUME  # noqa: F401  (re-exported)
 from ._lib import WMF_EXP, WMF_IV1, WMF_IV2, WMF_COS, WMF_JAC, WMF_OFF  # noqa: F401  (cv's WMFWeightType; EXP and OFF are built)
 from ._lib import GF_MAX_RADIUS  # noqa: F401  (re-exported)
+from ._lib import DTF_NC, DTF_IC, DTF_RF, DT_MAX_ITERS  # noqa: F401  (cv's EdgeAwareFiltersList; DTF_RF is built)
 from ._lib import AdfError, PATH_CONF_BAND, PATH_FUSED_FIRST_PASS, PATH_MERGED_PREP, PATH_ROW_WEIGHTS_GUIDE, PATH_SCALED_FUSED, PATH_SCALED_HALF, Rect, SOLVER_EXACT, SOLVER_WAVE  # noqa: F401  (re-exported)
 
 try:  # torch is optional plumbing: device memory and streams only
@@ -1397,6 +1400,134 @@ class GuidedFilter:
 def createGuidedFilter(guide, radius, eps):
     """EF.hpp:158: a GuidedFilter on `guide` (held by reference, not copied)."""
     return GuidedFilter(guide, radius, eps)
+
+
+# ---------------------------------------------------------------------------------------------
+# cv::ximgproc::dtFilter / createDTFilter / DTFilter (EF.hpp:66-121, dtfilter_cpu.hpp) in mode DTF_RF, in the library's own
+# exact definition (include/adf_wls.h; csrc/dt_filter_kernels.hip; the direct statement is tests/dt_ref.py).
+# ---------------------------------------------------------------------------------------------
+_DT = "dtFilter"
+_DT_NOT_BUILT = {DTF_NC: "DTF_NC", DTF_IC: "DTF_IC"}
+
+
+def _dt_mode(who, mode):
+    try:
+        m = int(mode)
+    except (TypeError, ValueError):
+        raise AdfError(_lib.ADF_EBADARG, "%s: mode must be DTF_RF" % who)
+    if m in _DT_NOT_BUILT:
+        raise AdfError(_lib.ADF_EBADARG, "%s: %s is not built; DTF_RF is" % (who, _DT_NOT_BUILT[m]))
+    if m != DTF_RF:
+        raise AdfError(_lib.ADF_EBADARG, "%s: mode must be DTF_RF" % who)
+    return m
+
+
+def dtRfTable(sigmaSpatial, sigmaColor, numIters=3, channels=1):
+    """The feedback table of dtFilter's DTF_RF mode exactly as its calls build it (adf_dt_rf_table_host): float32,
+    (max(1, numIters), 255 * channels + 1); row i - 1 holds A_i[L] for the L1 guide difference L.  Host only: no device is
+    touched."""
+    n = max(1, int(numIters))
+    if n > DT_MAX_ITERS or int(channels) not in (1, 3):     # (the library refuses them too; the array is sized first)
+        raise AdfError(_lib.ADF_EBADARG, "dtRfTable: numIters must not exceed %d, channels must be 1 or 3" % DT_MAX_ITERS)
+    table = np.empty((n, 255 * int(channels) + 1), np.float32)
+    _lib.check(_lib.lib().adf_dt_rf_table_host(float(sigmaSpatial), float(sigmaColor), int(numIters), int(channels), table.ctypes.data))
+    return table
+
+
+def dtFilterWorkspaceBytes(n, H, W):
+    """Bytes of device workspace dtFilter needs for n maps of H x W (adf_dt_filter_workspace_bytes): one float plane per
+    map, which holds the map between the passes."""
+    return int(_lib.lib().adf_dt_filter_workspace_bytes(int(n), int(W), int(H)))
+
+
+def dtFilter(guide, src, sigmaSpatial, sigmaColor, mode=DTF_RF, numIters=3, dDepth=-1, dst=None, workspace=None):
+    """cv::ximgproc::dtFilter(guide, src, dst, sigmaSpatial, sigmaColor, mode, numIters) in mode DTF_RF, in the library's
+    own definition (include/adf_wls.h): numIters times, a recursive sweep along every row there and back, then along every
+    column, x[j] += A[L] (x[j-1] - x[j]) with the feedback A falling with the guide's L1 difference L between the two
+    pixels -- one stated operation order, bit-exact against tests/dt_ref.py fed with dtRfTable.
+
+        guide         uint8, (H,W) or (H,W,3); with a batch (N,H,W) or (N,H,W,3)
+        src           uint8, int16 or float32, (H,W) or a batch (N,H,W), one channel
+        sigmaSpatial  clamped to >= 1;  sigmaColor  clamped to >= 0.01 (in grey levels of the 0..255 guide); both finite
+        mode          DTF_RF.  The reference's default is DTF_NC, which this build refuses, as it does DTF_IC: the default
+                      HERE is DTF_RF
+        numIters      clamped to >= 1, at most 8 (DT_MAX_ITERS)
+        dDepth        -1 = src's depth, or CV_8U, CV_16S, CV_32F: integer outputs are rounded half to even and saturated
+        dst           None, or an array / tensor of that depth and src's shape that overlaps neither input
+
+    The filter is not blind to a matcher's invalid value (minDisparity-1)*16: fill the holes first (weightedMedianFilter
+    with ignoreValue).  Multi-channel sources are not built: split them.  Torch CUDA tensors run on the device,
+    asynchronously on torch's current stream; `workspace` (device path only): a CUDA tensor of at least
+    dtFilterWorkspaceBytes(...) bytes -- the call then allocates nothing and may be captured into a CUDA graph; None =
+    the library's cached scratch.  Numpy arrays take the host entry point.  Returns dst."""
+    if guide is None or src is None:
+        raise AdfError(_lib.ADF_EBADARG, "%s: guide and src must not be empty" % _DT)
+    m = _dt_mode(_DT, mode)
+    nd = len(src.shape)
+    if nd not in (2, 3):
+        raise AdfError(_lib.ADF_EBADARG, "%s: src must be (H,W) or a batch (N,H,W) of one-channel maps" % _DT)
+    batched = nd == 3
+    for dt in (np.uint8, np.int16, np.float32):
+        if _map_dtype(src, dt) is not None:
+            break
+    else:
+        raise AdfError(_lib.ADF_EBADARG, "%s: src must be uint8 (CV_8U), int16 (CV_16S) or float32 (CV_32F)" % _DT)
+    if dDepth != -1 and dDepth not in _GF_DTYPE:
+        raise AdfError(_lib.ADF_EBADARG, "%s: dDepth must be -1, CV_8U, CV_16S or CV_32F" % _DT)
+    ddt = dt if dDepth == -1 else _GF_DTYPE[dDepth]
+    S = _Image(src, dt, "src", batched)
+    G = _Image(guide, np.uint8, "guide", batched, allow_channels=(1, 3))
+    if dst is None:
+        dst = _out_like(S, batched, ddt)
+    D = _Image(dst, ddt, "dst", batched)
+    for im, what in ((G, "guide"), (D, "dst")):
+        if (im.n, im.h, im.w) != (S.n, S.h, S.w) or im.device != S.device:
+            raise AdfError(_lib.ADF_ESIZE, "%s: %s must have src's size on its side (host or device)" % (_DT, what))
+        if S.device and im.keep.device != S.keep.device:
+            raise AdfError(_lib.ADF_EBADARG, "%s: %s lives on %s, src on %s" % (_DT, what, im.keep.device, S.keep.device))
+    args = (S.n, G.ptr, G.stride, G.pair_stride, G.c, S.ptr, S.stride, S.pair_stride, _DEPTH[dt], D.ptr, D.stride, D.pair_stride,
+            _DEPTH[ddt], S.w, S.h, float(sigmaSpatial), float(sigmaColor), m, int(numIters))
+    if not S.device:
+        if workspace is not None:
+            raise AdfError(_lib.ADF_EBADARG, "%s: a workspace goes with CUDA tensors only" % _DT)
+        _call("adf_dt_filter", S, args)
+        return dst
+    ws, ws_bytes = None, 0
+    if workspace is not None:
+        if not (_is_torch(workspace) and workspace.is_cuda and workspace.is_contiguous()):
+            raise AdfError(_lib.ADF_EBADARG, "%s: workspace must be a contiguous CUDA tensor (or None)" % _DT)
+        if workspace.device != S.keep.device:
+            raise AdfError(_lib.ADF_EBADARG, "%s: workspace lives on %s, src on %s" % (_DT, workspace.device, S.keep.device))
+        ws, ws_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    with torch.cuda.device(S.keep.device):
+        _call("adf_dt_filter", S, args + (ws, ws_bytes))
+    return dst
+
+
+class DTFilter:
+    """cv::ximgproc::DTFilter (EF.hpp:66-84): holds the guide and the parameters; filter(src) is dtFilter(guide, src, ...).
+    There is no init stage -- the weights are one table read per step, recomputed from the guide in every sweep -- so the
+    object saves no work: it is the reference's interface.  As with dtFilter, the default mode is DTF_RF (the reference's
+    DTF_NC is not built)."""
+
+    def __init__(self, guide, sigmaSpatial, sigmaColor, mode=DTF_RF, numIters=3):
+        if guide is None:
+            raise AdfError(_lib.ADF_EBADARG, "%s: guide must not be empty" % _DT)
+        m = _dt_mode(_DT, mode)
+        if not (math.isfinite(float(sigmaSpatial)) and math.isfinite(float(sigmaColor))):
+            raise AdfError(_lib.ADF_EBADARG, "%s: sigmaSpatial and sigmaColor must be finite" % _DT)
+        if int(numIters) > DT_MAX_ITERS:
+            raise AdfError(_lib.ADF_EBADARG, "%s: numIters must not exceed %d" % (_DT, DT_MAX_ITERS))
+        self._guide, self._ss, self._sr, self._mode, self._iters = guide, float(sigmaSpatial), float(sigmaColor), m, int(numIters)
+
+    def filter(self, src, dst=None, dDepth=-1, workspace=None):
+        return dtFilter(self._guide, src, self._ss, self._sr, self._mode, self._iters, dDepth, dst, workspace)
+
+
+def createDTFilter(guide, sigmaSpatial, sigmaColor, mode=DTF_RF, numIters=3):
+    """EF.hpp:100: a DTFilter on `guide` (held by reference, not copied).  The default mode is DTF_RF, not the reference's
+    DTF_NC, which is not built."""
+    return DTFilter(guide, sigmaSpatial, sigmaColor, mode, numIters)
 
 
 def createDisparityWLSFilter(matcher_left):

@@ -1096,6 +1096,80 @@ int adf_guided_filter_host(int n_maps,
                            void* dst, ptrdiff_t dst_stride, ptrdiff_t dst_map_stride, int dst_depth,
                            int W, int H, int r, double eps);
 
+/* ---------------- domain transform filter (cv::ximgproc::dtFilter / DTFilter), recursive mode ----------------
+ * createDTFilter(guide, sigmaSpatial, sigmaColor, mode, numIters) (EF.hpp:100), DTFilter::filter(src, dst, dDepth)
+ * (EF.hpp:80) and dtFilter(guide, src, dst, sigmaSpatial, sigmaColor, mode, numIters) (EF.hpp:120;
+ * modules/ximgproc/src/dtfilter_cpu.hpp = DT.hpp, dtfilter_cpu.inl.hpp = DT.inl; Gastal and Oliveira, "Domain Transform
+ * for Edge-Aware Image and Video Processing"): in mode DTF_RF one iteration is four first-order recursive sweeps over the
+ * map -- along every row there and back, then along every column -- whose feedback falls with the guide's difference
+ * between the two pixels of a step.  No window and no tridiagonal solve: the cheapest edge-aware refinement of a
+ * disparity map.  In the chain it stands where the guided filter does.
+ *
+ * This is the library's OWN definition.  It keeps DT's distance, its sigma schedule and its recurrence in DT's order of
+ * evaluation, which IS the definition; it builds the feedback table with one rounding per entry.  The result is bit-exact
+ * against the direct NumPy statement tests/dt_ref.py fed with adf_dt_rf_table_host, and identical from run to run.
+ *
+ * Inputs.  n_maps equally sized maps of W x H, `*_map_stride` bytes apart, rows `*_stride` bytes apart.
+ *   - guide: 8-bit, guide_channels 1 or 3 (interleaved), the size of src.
+ *   - src: ONE channel, depth ADF_8U, ADF_16S or ADF_32F.
+ *   - dst: one channel, depth dst_depth, any of the three, independent of src's (cv's dDepth).
+ *   - mode: ADF_DTF_RF.  ADF_DTF_NC and ADF_DTF_IC (windows of variable width in the transformed domain) are NOT built.
+ * Parameters, as DT.inl:79-83 clamps them: ss = max(1.0f, (float)sigmaSpatial), sr = max(0.01f, (float)sigmaColor),
+ * N = max(1, numIters).
+ * Distance (DT.hpp:115-118).  k = ss / sr in float32.  For the L1 difference L of two guide pixels (the sum over the
+ * channels of |difference|: 0..255 for 1 channel, 0..765 for 3) d_L = 1.0f + k * (float)L, the product and the sum each
+ * rounded to float32.
+ * Feedback table, one row per iteration i = 1..N, 255 * guide_channels + 1 entries each:
+ *   - sigmaH_i = ss * 2^(N-i) / sqrt(4^N - 1) in double, left to right (DT.hpp:120-123);
+ *   - A_i[L] = (float)exp((-sqrt(2/3) / sigmaH_i) * (double)d_L), in double, libm's exp on the host.
+ *   adf_dt_rf_table_host writes the N rows, row i - 1 first, exactly as the calls build them.  Host only -- no device is
+ *   touched.  (The calls hand a row to their kernels with the launch: there is no device table to build or cache.)
+ * Recurrence (DT.inl:407-415, 438-466), on x = (float)src, for i = 1..N:
+ *   - every row, left to right, j = 1..W-1:   x[j] = x[j] + A_i[L(j-1, j)] * (x[j-1] - x[j]);
+ *   - then right to left, j = W-2..0:         x[j] = x[j] + A_i[L(j, j+1)] * (x[j+1] - x[j]);
+ *   - then the same down (1..H-1) and up (H-2..0) every column, L between the two rows.
+ *   Subtraction, product and sum are each rounded to float32 (no FMA).  W == 1 leaves the rows as they are, H == 1 the
+ *   columns.  Every step is a convex combination of two values of the map: a constant map comes back exactly.
+ * Output.  dst = x for ADF_32F; rint(x) (half to even, cv's saturate_cast) saturated to the depth for ADF_8U / ADF_16S
+ * (a NaN gives the depth's minimum).
+ * Deviations from the reference, all deliberate:
+ *   - DT rounds alpha = exp(-sqrt(2/3) / sigmaH_1) and log(alpha) to float, runs cv::exp once over a float plane of
+ *     d * log(alpha), and squares that plane in place for each later iteration (DT.inl:401-405, 539-561): its weights
+ *     of iteration i carry 2^(i-1) accumulated roundings.  Ours carry one; the cost is measured in tests/test_dt_ref.py;
+ *   - the weights are not a plane: they are one table read per step, recomputed from the guide in every sweep, so there
+ *     is no init stage (DTFilter keeps the guide and the parameters);
+ *   - one-channel sources only (callers split them); guides of 1 or 3 channels of 8 bits;
+ *   - DTF_NC and DTF_IC are refused.
+ * Refused: mode ADF_DTF_NC or ADF_DTF_IC (not built) and any other mode but ADF_DTF_RF, sigmas that are not finite (as
+ * double or as float32), numIters above ADF_DT_MAX_ITERS = 8, an unknown depth or guide_channels, NULL guide / src / dst,
+ * n_maps, W or H below 1, bases or strides not aligned to the depth (2 bytes for ADF_16S, 4 for ADF_32F), dst
+ * overlapping (by the byte ranges they span) guide or src (all ADF_EBADARG); W*H at or above 2^31, strides smaller than
+ * a row, destination maps of a batch that overlap each other, a workspace that is too small (ADF_ESIZE).  All of this is
+ * checked before a device is touched.
+ * Workspace: the map between the passes, one float plane per map -- adf_dt_filter_workspace_bytes(n_maps, W, H) bytes of
+ * 4-byte aligned device memory (0 for arguments the calls refuse).  workspace == NULL takes library scratch from the
+ * process-wide cache (no allocation once it is warm); a caller-supplied workspace makes the call capturable into a
+ * hipGraph.
+ * _device: device pointers on the current HIP device, asynchronous on `stream`.  _host: host pointers; copies, runs and
+ * synchronises. */
+#define ADF_DTF_NC 0 /* cv::ximgproc::DTF_NC: not built */
+#define ADF_DTF_IC 1 /* cv::ximgproc::DTF_IC: not built */
+#define ADF_DTF_RF 2 /* cv::ximgproc::DTF_RF */
+#define ADF_DT_MAX_ITERS 8
+size_t adf_dt_filter_workspace_bytes(int n_maps, int W, int H);
+int adf_dt_rf_table_host(double sigma_spatial, double sigma_color, int num_iters, int guide_channels, float* table);
+int adf_dt_filter_device(int n_maps,
+                         const uint8_t* guide, ptrdiff_t guide_stride, ptrdiff_t guide_map_stride, int guide_channels,
+                         const void* src, ptrdiff_t src_stride, ptrdiff_t src_map_stride, int src_depth,
+                         void* dst, ptrdiff_t dst_stride, ptrdiff_t dst_map_stride, int dst_depth,
+                         int W, int H, double sigma_spatial, double sigma_color, int mode, int num_iters,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int adf_dt_filter_host(int n_maps,
+                       const uint8_t* guide, ptrdiff_t guide_stride, ptrdiff_t guide_map_stride, int guide_channels,
+                       const void* src, ptrdiff_t src_stride, ptrdiff_t src_map_stride, int src_depth,
+                       void* dst, ptrdiff_t dst_stride, ptrdiff_t dst_map_stride, int dst_depth,
+                       int W, int H, double sigma_spatial, double sigma_color, int mode, int num_iters);
+
 #ifdef __cplusplus
 }
 #endif

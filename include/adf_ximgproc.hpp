@@ -216,6 +216,73 @@ inline Ptr<GuidedFilter> createGuidedFilter(const Mat& guide, int radius, double
     return Ptr<GuidedFilter>(new GuidedFilterImpl(guide, radius, eps));
 }
 
+// cv::ximgproc::dtFilter(guide, src, dst, sigmaSpatial, sigmaColor, mode, numIters) (EF.hpp:121), createDTFilter(guide,
+// sigmaSpatial, sigmaColor, mode, numIters) (EF.hpp:102) and DTFilter::filter(src, dst, dDepth) (EF.hpp:79) on host Mats
+// through the library's host entry, in mode DTF_RF and the library's own definition (adf_dt_filter_* in adf_wls.h: the
+// recurrence in the reference's order, a feedback table with one rounding per entry).  guide: CV_8UC1 or CV_8UC3; src:
+// CV_8UC1, CV_16SC1 or CV_32FC1 of its size (multi-channel sources are not built: split them); dDepth: -1 (src's depth),
+// CV_8U, CV_16S or CV_32F.  DTF_NC and DTF_IC are not built and refused -- so the default mode HERE is DTF_RF, not the
+// reference's DTF_NC.  dst may be src.  The filter is not blind to a matcher's invalid value: run weightedMedianFilter
+// with ignoreValue first.
+enum EdgeAwareFiltersList { DTF_NC, DTF_IC, DTF_RF }; // cv's values
+inline void dt_filter(const Mat& guide, const Mat& src, Mat& dst, double sigmaSpatial, double sigmaColor, int mode, int numIters, int dDepth)
+{
+    if (src.empty() || mat_channels(src) != 1 || (mat_depth(src) != D8U && mat_depth(src) != D16S && mat_depth(src) != D32F))
+        throw Exception(ADF_EBADARG, "dtFilter: src must be a non-empty CV_8UC1, CV_16SC1 or CV_32FC1 image");
+    if (guide.empty() || mat_depth(guide) != D8U)
+        throw Exception(ADF_EBADARG, "dtFilter: guide must be a non-empty CV_8UC1 or CV_8UC3 image");
+    if (guide.rows != src.rows || guide.cols != src.cols) throw Exception(ADF_ESIZE, "dtFilter: guide must have src's size");
+    const int ddepth = dDepth == -1 ? mat_depth(src) : dDepth;
+    if (ddepth != D8U && ddepth != D16S && ddepth != D32F)
+        throw Exception(ADF_EBADARG, "dtFilter: dDepth must be -1, CV_8U, CV_16S or CV_32F");
+    auto code = [](int depth) { return depth == D8U ? ADF_8U : depth == D16S ? ADF_16S : ADF_32F; };
+    Mat out;                                                             // (dst may be src: the result lands in a new Mat)
+    mat_create(out, src.rows, src.cols, ddepth, 1);
+    check(adf_dt_filter_host(1, guide.data, mat_step(guide), 0, mat_channels(guide), src.data, mat_step(src), 0, code(mat_depth(src)),
+                             out.data, mat_step(out), 0, code(ddepth), src.cols, src.rows, sigmaSpatial, sigmaColor, mode, numIters));
+    dst = out;
+}
+inline void dtFilter(const Mat& guide, const Mat& src, Mat& dst, double sigmaSpatial, double sigmaColor, int mode = DTF_RF, int numIters = 3)
+{
+    dt_filter(guide, src, dst, sigmaSpatial, sigmaColor, mode, numIters, -1);
+}
+
+class DTFilter {
+public:
+    virtual ~DTFilter() {}
+    virtual void filter(const Mat& src, Mat& dst, int dDepth = -1) = 0;
+};
+
+// Holds its own copy of the guide (the caller's Mat may change or go away, as with cv's) and the parameters.  There is no
+// init stage: the weights are one table read per step, recomputed from the guide in every sweep.
+class DTFilterImpl : public DTFilter {
+    Mat guide_;
+    double sigmaSpatial_, sigmaColor_;
+    int mode_, numIters_;
+public:
+    DTFilterImpl(const Mat& guide, double sigmaSpatial, double sigmaColor, int mode, int numIters)
+        : sigmaSpatial_(sigmaSpatial), sigmaColor_(sigmaColor), mode_(mode), numIters_(numIters)
+    {
+        if (guide.empty() || mat_depth(guide) != D8U || (mat_channels(guide) != 1 && mat_channels(guide) != 3))
+            throw Exception(ADF_EBADARG, "createDTFilter: guide must be a non-empty CV_8UC1 or CV_8UC3 image");
+        if (mode != DTF_RF) throw Exception(ADF_EBADARG, "createDTFilter: mode must be DTF_RF (DTF_NC and DTF_IC are not built)");
+        if (!std::isfinite(sigmaSpatial) || !std::isfinite(sigmaColor)) throw Exception(ADF_EBADARG, "createDTFilter: the sigmas must be finite");
+        if (numIters > ADF_DT_MAX_ITERS) throw Exception(ADF_EBADARG, "createDTFilter: numIters must not exceed 8");
+        mat_create(guide_, guide.rows, guide.cols, D8U, mat_channels(guide));
+        for (int y = 0; y < guide.rows; y++)
+            std::memcpy(guide_.data + (size_t)mat_step(guide_) * y, guide.data + (size_t)mat_step(guide) * y, (size_t)guide.cols * mat_channels(guide));
+    }
+    void filter(const Mat& src, Mat& dst, int dDepth = -1) override
+    {
+        dt_filter(guide_, src, dst, sigmaSpatial_, sigmaColor_, mode_, numIters_, dDepth);
+    }
+};
+
+inline Ptr<DTFilter> createDTFilter(const Mat& guide, double sigmaSpatial, double sigmaColor, int mode = DTF_RF, int numIters = 3)
+{
+    return Ptr<DTFilter>(new DTFilterImpl(guide, sigmaSpatial, sigmaColor, mode, numIters));
+}
+
 // cv::stereo::censusTransform(image, kernelSize, dist, type) (modules/stereo descriptor.hpp:428, descriptor.cpp:77-98) on a
 // CV_8UC1 host Mat, through the library's host entry: the census descriptor of every pixel, type
 // ADF_SGBM_COST_CENSUS_DENSE (kernelSize 3, 5, 7), ADF_SGBM_COST_CENSUS_SPARSE (5, 7, 9, 11), the modified census
