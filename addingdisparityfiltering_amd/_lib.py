@@ -26,6 +26,8 @@ WMF_EXP, WMF_IV1, WMF_IV2, WMF_COS, WMF_JAC, WMF_OFF = range(6)    # cv::ximgpro
 WMF_WEIGHT_ONE, WMF_TABLE_LEVELS, WMF_MAX_RADIUS = 65536, 3 * 256 * 256, 31
 GF_MAX_RADIUS = 31    # ADF_GF_MAX_RADIUS
 DTF_NC, DTF_IC, DTF_RF, DT_MAX_ITERS = 0, 1, 2, 8    # ADF_DTF_*, ADF_DT_MAX_ITERS
+JBF_MAX_RADIUS = 31    # ADF_JBF_MAX_RADIUS
+BORDER_REPLICATE, BORDER_REFLECT, BORDER_WRAP, BORDER_REFLECT_101 = 1, 2, 3, 4    # cv::BorderTypes; 1, 2 and 4 are built (ADF_BORDER_*)
 
 
 class AdfError(RuntimeError):
@@ -69,6 +71,7 @@ _RECTIFY_VIEWS_DEV = [_i, _vp, _pd, _pd, _i, _i, _i, C.POINTER(RectifyParams), _
 _WMF_DEV = [_i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _i, _i, _d, _i, _vp, _pd, _pd, _i, _d, _vp]
 _GF_DEV = [_i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _i, _i, _i, _d, _vp, _sz, _vp]
 _DT_DEV = [_i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _i, _i, _d, _d, _i, _i, _vp, _sz, _vp]
+_JBF_DEV = [_i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _i, _i, _i, _d, _d, _i, _vp]
 _FILTER_SCALED_DEV = [_vp, _i, _vp, _pd, _pd, _i, _i, _vp, _pd, _pd, _i, _i, _i, _vp, _pd, _pd, _vp, _pd, _pd,
                       C.POINTER(Rect), _vp]
 # adf_wls_filter_typed_*: the scaled call with a depth behind the left map's strides and one behind the output's
@@ -186,6 +189,9 @@ SYMBOLS = [
     ("adf_dt_rf_table_host", _i, [_d, _d, _i, _i, _vp]),
     ("adf_dt_filter_device", _i, _DT_DEV),
     ("adf_dt_filter_host", _i, _DT_DEV[:-3]),
+    ("adf_jbf_tables_host", _i, [_i, _d, _d, _i, _vp, _vp, C.POINTER(_i)]),
+    ("adf_joint_bilateral_filter_device", _i, _JBF_DEV),
+    ("adf_joint_bilateral_filter_host", _i, _JBF_DEV[:-1]),
 ]
 
 _lib = None

@@ -28,6 +28,7 @@ SOURCES = {
     "wmf_kernels.hip": [],
     "guided_filter_kernels.hip": [],
     "dt_filter_kernels.hip": [],
+    "joint_bilateral_kernels.hip": [],
 }
 OUT = os.path.join(_HERE, "libadf_wls.so")
 # -ffp-contract=off: the exact solver and the confidence map reproduce the reference's separate

@@ -115,6 +115,19 @@ ADF_LOCAL int wmf_weights_check(const char* who, double sigma, int weight_type);
 // the host and uploaded with one synchronous copy.  The caller holds `out` until its launches are queued.
 ADF_LOCAL int wmf_table_device(double sigma, int weight_type, std::shared_ptr<WmfTable>& out, const uint32_t** dev);
 
+// The joint bilateral filter's tables (include/adf_wls.h: C, then S, in one block of floats): an immutable device table
+// per (device, sigma_color, sigma_space, r, joint channels), shared by every call of the process (adf_host.hip: JbfStore).
+struct JbfTable;
+// The refusals both entry kinds and adf_jbf_tables_host share; on ADF_OK the clamped sigmas and the radius.
+ADF_LOCAL int jbf_params_check(const char* who, int d, double sigma_color, double sigma_space, int joint_channels,
+                               double* sc, double* ss, int* r);
+constexpr size_t jbf_colour_entries(int channels) { return (size_t)255 * channels + 1; }
+constexpr size_t jbf_space_entries(int r) { return (size_t)r * r + 1; }
+// The tables of the current device, as wmf_table_device: a look-up when the key was seen before (capturable), else built
+// on the host and uploaded with one synchronous copy.  The caller holds `out` until its launches are queued.
+ADF_LOCAL int jbf_table_device(double sc, double ss, int r, int channels, std::shared_ptr<JbfTable>& out,
+                               const float** colour, const float** space);
+
 // The host-pointer entry points' copies: `n` images of `rows` rows of `row_bytes`, image k at `k * image_stride` bytes
 // with rows `pitch` bytes apart on either side, asynchronously on `st` (a host destination is complete once `st` has
 // been synchronised).  The layout of a staging block stays with the caller.

@@ -90,8 +90,8 @@ struct adf::LutTable {
     ~LutTable() { if (dev) { DeviceScope ds(device); hipFree(dev); } }
 };
 
-// The process-wide store of one kind of immutable device table (the filters' LutTable, the weighted median's WmfTable):
-// up to CAP of them, least recently used dropped first.
+// The process-wide store of one kind of immutable device table (the filters' LutTable, the weighted median's WmfTable,
+// the joint bilateral filter's JbfTable): up to CAP of them, least recently used dropped first.
 template <class TABLE> struct TableStore {
     static constexpr size_t CAP = 16;
     std::mutex m;
@@ -246,6 +246,74 @@ extern "C" int adf_wmf_weight_table_host(double sigma, int weight_type, uint32_t
     return ADF_OK;
 }
 
+// The joint bilateral filter's tables (include/adf_wls.h: C and S), built on the host with libm like the tables above and
+// kept the same way: one block of floats, C then S, per (device, sigma_color, sigma_space, r, channels).
+struct adf::JbfTable {
+    int device = 0, r = 0, channels = 0; double sc = 0, ss = 0; float* dev = nullptr;
+    JbfTable() = default;
+    JbfTable(const JbfTable&) = delete;
+    JbfTable& operator=(const JbfTable&) = delete;
+    ~JbfTable() { if (dev) { DeviceScope ds(device); hipFree(dev); } }
+};
+using JbfStore = TableStore<JbfTable>;
+
+static void jbf_build_host(double sc, double ss, int r, int channels, float* colour, float* space)
+{
+    const double cc = -0.5 / (sc * sc), cs = -0.5 / (ss * ss);
+    colour[0] = space[0] = 1.0f;
+    for (int a = 1; a < (int)jbf_colour_entries(channels); a++) colour[a] = (float)exp((double)(a * a) * cc);
+    for (int q = 1; q < (int)jbf_space_entries(r); q++) space[q] = (float)exp((double)q * cs);
+}
+
+int adf::jbf_params_check(const char* who, int d, double sigma_color, double sigma_space, int joint_channels,
+                          double* sc, double* ss, int* r)
+{
+    if (joint_channels != 1 && joint_channels != 3) return fail(ADF_EBADARG, "%s: joint must have 1 or 3 channels", who);
+    if (!std::isfinite(sigma_color) || !std::isfinite(sigma_space) || !std::isfinite((float)sigma_color) || !std::isfinite((float)sigma_space))
+        return fail(ADF_EBADARG, "%s: sigmaColor and sigmaSpace must be finite (as float32 too)", who);
+    *sc = sigma_color <= 0 ? 1.0 : sigma_color;
+    *ss = sigma_space <= 0 ? 1.0 : sigma_space;
+    const double rr = std::max(1.0, d <= 0 ? std::nearbyint(*ss * 1.5) : (double)(d / 2));   // (nearbyint: half to even, cvRound)
+    if (!(rr <= (double)ADF_JBF_MAX_RADIUS))
+        return fail(ADF_EBADARG, "%s: the radius (d / 2, or cvRound(1.5 sigmaSpace) for d <= 0) must not exceed %d", who, ADF_JBF_MAX_RADIUS);
+    *r = (int)rr;
+    return ADF_OK;
+}
+
+int adf::jbf_table_device(double sc, double ss, int r, int channels, std::shared_ptr<JbfTable>& out, const float** colour, const float** space)
+{
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) return fail(ADF_ENODEV, "no HIP device");
+    out = JbfStore::get().find([&](const JbfTable& q) { return q.device == device && q.sc == sc && q.ss == ss && q.r == r && q.channels == channels; });
+    if (!out) {
+        const size_t nc = jbf_colour_entries(channels), ns = jbf_space_entries(r);
+        std::vector<float> host(nc + ns);
+        jbf_build_host(sc, ss, r, channels, host.data(), host.data() + nc);
+        float* d = nullptr;
+        HIP_TRY(device_malloc(reinterpret_cast<void**>(&d), sizeof(float) * host.size()));
+        hipError_t e = hipMemcpy(d, host.data(), sizeof(float) * host.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { hipFree(d); return fail(ADF_EHIP, "joint bilateral table upload failed: %s", hipGetErrorString(e)); }
+        out = std::make_shared<JbfTable>();
+        out->device = device; out->r = r; out->channels = channels; out->sc = sc; out->ss = ss; out->dev = d;
+        JbfStore::get().add(out);
+    }
+    *colour = out->dev;
+    *space = out->dev + jbf_colour_entries(channels);
+    return ADF_OK;
+}
+
+extern "C" int adf_jbf_tables_host(int d, double sigma_color, double sigma_space, int joint_channels, float* colour, float* space, int* radius)
+{
+    double sc, ss;
+    int r;
+    if (int rc = jbf_params_check("adf_jbf_tables_host", d, sigma_color, sigma_space, joint_channels, &sc, &ss, &r)) return rc;
+    if (radius) *radius = r;
+    if (!colour && !space) return ADF_OK;                         // the radius alone: what sizes the space table
+    if (!colour || !space) return fail(ADF_EBADARG, "adf_jbf_tables_host: colour and space must both be given (or neither: the radius alone)");
+    jbf_build_host(sc, ss, r, joint_channels, colour, space);
+    return ADF_OK;
+}
+
 // Device blocks of short-lived handles (adf_fgs: the planes and the staged image of ONE image), kept for the next
 // handle instead of going back to the driver: hipMalloc + hipFree of a 4K handle's 300 MB cost more than its filter
 // call, and hipFree waits for the whole device.  A block comes back with the event behind its last user; whoever takes
@@ -388,4 +456,5 @@ extern "C" void adf_release_cached_memory(void)
     BlockCache::get().clear();
     LutStore::get().clear();
     WmfStore::get().clear();
+    JbfStore::get().clear();
 }

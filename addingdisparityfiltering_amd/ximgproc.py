@@ -25,6 +25,7 @@ edge_filter.hpp (EF.hpp), over the C-ABI in include/adf_wls.h:
     createGuidedFilter(guide, radius, eps) -> GuidedFilter.filter(src, dst, dDepth)   EF.hpp:158, 143
     dtFilter(guide, src, sigmaSpatial, sigmaColor, mode, numIters)   EF.hpp:120  / dtfilter_cpu.hpp (DTF_RF only; the library's own exact definition)
     createDTFilter(guide, sigmaSpatial, sigmaColor, mode, numIters) -> DTFilter.filter(src, dst, dDepth)   EF.hpp:100, 80
+    jointBilateralFilter(joint, src, d, sigmaColor, sigmaSpace, borderType, dDepth)   EF.hpp:317 / joint_bilateral_filter.cpp (8-bit joints; the library's own exact definition)
 
 Images are numpy arrays (host path: copied to the GPU and back) or torch CUDA
 tensors (device path: zero-copy, asynchronous on torch's current stream).  A
@@ -45,6 +46,7 @@ from ._lib import SGBM_RIGHT_MATCHER, SGBM_RIGHT_FROM_VOLUME  # noqa: F401  (re-
 from ._lib import WMF_EXP, WMF_IV1, WMF_IV2, WMF_COS, WMF_JAC, WMF_OFF  # noqa: F401  (cv's WMFWeightType; EXP and OFF are built)
 from ._lib import GF_MAX_RADIUS  # noqa: F401  (re-exported)
 from ._lib import DTF_NC, DTF_IC, DTF_RF, DT_MAX_ITERS  # noqa: F401  (cv's EdgeAwareFiltersList; DTF_RF is built)
+from ._lib import JBF_MAX_RADIUS, BORDER_REPLICATE, BORDER_REFLECT, BORDER_WRAP, BORDER_REFLECT_101  # noqa: F401  (cv's BorderTypes; 1, 2 and 4 are built)
 from ._lib import AdfError, PATH_CONF_BAND, PATH_FUSED_FIRST_PASS, PATH_MERGED_PREP, PATH_ROW_WEIGHTS_GUIDE, PATH_SCALED_FUSED, PATH_SCALED_HALF, Rect, SOLVER_EXACT, SOLVER_WAVE  # noqa: F401  (re-exported)
 
 try:  # torch is optional plumbing: device memory and streams only
@@ -1528,6 +1530,100 @@ def createDTFilter(guide, sigmaSpatial, sigmaColor, mode=DTF_RF, numIters=3):
     """EF.hpp:100: a DTFilter on `guide` (held by reference, not copied).  The default mode is DTF_RF, not the reference's
     DTF_NC, which is not built."""
     return DTFilter(guide, sigmaSpatial, sigmaColor, mode, numIters)
+
+
+# ---------------------------------------------------------------------------------------------
+# cv::ximgproc::jointBilateralFilter (EF.hpp:317, joint_bilateral_filter.cpp) in the library's own exact definition
+# (include/adf_wls.h; csrc/joint_bilateral_kernels.hip; the direct statement is tests/jbf_ref.py).
+# ---------------------------------------------------------------------------------------------
+_JBF = "jointBilateralFilter"
+BORDER_DEFAULT = BORDER_REFLECT_101     # cv::BORDER_DEFAULT
+_JBF_NOT_BUILT = {BORDER_CONSTANT: "BORDER_CONSTANT", BORDER_WRAP: "BORDER_WRAP"}
+
+
+def _jbf_border(who, borderType):
+    try:
+        b = int(borderType)
+    except (TypeError, ValueError):
+        raise AdfError(_lib.ADF_EBADARG, "%s: borderType must be BORDER_REPLICATE, BORDER_REFLECT or BORDER_REFLECT_101" % who)
+    if b in _JBF_NOT_BUILT:
+        raise AdfError(_lib.ADF_EBADARG, "%s: %s is not built; BORDER_REPLICATE, BORDER_REFLECT and BORDER_REFLECT_101 are"
+                       % (who, _JBF_NOT_BUILT[b]))
+    if b not in (BORDER_REPLICATE, BORDER_REFLECT, BORDER_REFLECT_101):
+        raise AdfError(_lib.ADF_EBADARG, "%s: borderType %d is not built; BORDER_REPLICATE, BORDER_REFLECT and BORDER_REFLECT_101 are" % (who, b))
+    return b
+
+
+def jbfTables(d, sigmaColor, sigmaSpace, channels=1):
+    """The tables of jointBilateralFilter exactly as its calls use them (adf_jbf_tables_host): (C, S, r) with C float32 of
+    255 * channels + 1 entries indexed by the joint's L1 difference, S float32 of r * r + 1 entries indexed by the squared
+    distance, and the radius r the clamps give.  Host only: no device is touched."""
+    r = C.c_int(0)
+    fn = _lib.lib().adf_jbf_tables_host
+    _lib.check(fn(int(d), float(sigmaColor), float(sigmaSpace), int(channels), None, None, C.byref(r)))   # (sizes S)
+    colour, space = np.empty(255 * int(channels) + 1, np.float32), np.empty(r.value * r.value + 1, np.float32)
+    _lib.check(fn(int(d), float(sigmaColor), float(sigmaSpace), int(channels), colour.ctypes.data, space.ctypes.data, C.byref(r)))
+    return colour, space, r.value
+
+
+def jointBilateralFilter(joint, src, d, sigmaColor, sigmaSpace, borderType=BORDER_REFLECT_101, dDepth=-1, dst=None):
+    """cv::ximgproc::jointBilateralFilter(joint, src, dst, d, sigmaColor, sigmaSpace, borderType) in the library's own
+    definition (include/adf_wls.h): the mean of the source over the disc of radius r, a tap weighted by
+    S[squared distance] * C[L1 difference of the joint's pixels], float32 sums in one stated order -- bit-exact against
+    tests/jbf_ref.py fed with jbfTables.
+
+        joint       uint8, (H,W) or (H,W,3); with a batch (N,H,W) or (N,H,W,3); not src itself
+        src         uint8, int16 or float32, (H,W) or a batch (N,H,W), one channel
+        d           the diameter: r = d // 2; d <= 0: r = round-half-even(1.5 sigmaSpace); r is raised to 1 and must not
+                    exceed 31 (JBF_MAX_RADIUS)
+        sigmaColor  in grey levels of the 0..255 joint; sigmaSpace in pixels; both finite, <= 0 means 1
+        borderType  BORDER_REPLICATE, BORDER_REFLECT or BORDER_REFLECT_101 (cv's default, the default here);
+                    BORDER_CONSTANT and BORDER_WRAP are not built
+        dDepth      -1 = src's depth, or CV_8U, CV_16S, CV_32F: integer outputs are rounded half to even and saturated
+        dst         None, or an array / tensor of that depth and src's shape that overlaps neither input
+
+    The filter is not blind to a matcher's invalid value (minDisparity-1)*16: fill the holes first (weightedMedianFilter
+    with ignoreValue).  Float (CV_32F) joints, multi-channel sources and the fall-back to cv::bilateralFilter for an empty
+    joint or joint is src are not built.  Torch CUDA tensors run on the device, asynchronously on torch's current stream:
+    one launch, no workspace, and once a (sigmaColor, sigmaSpace, r, channels) has been used the call allocates nothing
+    and may be captured into a CUDA graph.  Numpy arrays take the host entry point.  Returns dst."""
+    if joint is None or src is None:
+        raise AdfError(_lib.ADF_EBADARG, "%s: joint and src must not be empty (an empty joint is cv::bilateralFilter, which is not built)" % _JBF)
+    if joint is src:
+        raise AdfError(_lib.ADF_EBADARG, "%s: joint is src is cv::bilateralFilter, which is not built" % _JBF)
+    b = _jbf_border(_JBF, borderType)
+    nd = len(src.shape)
+    if nd not in (2, 3):
+        raise AdfError(_lib.ADF_EBADARG, "%s: src must be (H,W) or a batch (N,H,W) of one-channel maps; multi-channel sources are not built" % _JBF)
+    batched = nd == 3
+    for dt in (np.uint8, np.int16, np.float32):
+        if _map_dtype(src, dt) is not None:
+            break
+    else:
+        raise AdfError(_lib.ADF_EBADARG, "%s: src must be uint8 (CV_8U), int16 (CV_16S) or float32 (CV_32F)" % _JBF)
+    if _map_dtype(joint, np.float32) is not None:
+        raise AdfError(_lib.ADF_EBADARG, "%s: a float32 (CV_32F) joint is not built; the joint must be uint8" % _JBF)
+    if dDepth != -1 and dDepth not in _GF_DTYPE:
+        raise AdfError(_lib.ADF_EBADARG, "%s: dDepth must be -1, CV_8U, CV_16S or CV_32F" % _JBF)
+    ddt = dt if dDepth == -1 else _GF_DTYPE[dDepth]
+    S = _Image(src, dt, "src", batched)
+    J = _Image(joint, np.uint8, "joint", batched, allow_channels=(1, 3))
+    if dst is None:
+        dst = _out_like(S, batched, ddt)
+    D = _Image(dst, ddt, "dst", batched)
+    for im, what in ((J, "joint"), (D, "dst")):
+        if (im.n, im.h, im.w) != (S.n, S.h, S.w) or im.device != S.device:
+            raise AdfError(_lib.ADF_ESIZE, "%s: %s must have src's size on its side (host or device)" % (_JBF, what))
+        if S.device and im.keep.device != S.keep.device:
+            raise AdfError(_lib.ADF_EBADARG, "%s: %s lives on %s, src on %s" % (_JBF, what, im.keep.device, S.keep.device))
+    args = (S.n, J.ptr, J.stride, J.pair_stride, J.c, S.ptr, S.stride, S.pair_stride, _DEPTH[dt], D.ptr, D.stride, D.pair_stride,
+            _DEPTH[ddt], S.w, S.h, int(d), float(sigmaColor), float(sigmaSpace), b)
+    if not S.device:
+        _call("adf_joint_bilateral_filter", S, args)
+        return dst
+    with torch.cuda.device(S.keep.device):
+        _call("adf_joint_bilateral_filter", S, args)
+    return dst
 
 
 def createDisparityWLSFilter(matcher_left):

@@ -1170,6 +1170,87 @@ int adf_dt_filter_host(int n_maps,
                        void* dst, ptrdiff_t dst_stride, ptrdiff_t dst_map_stride, int dst_depth,
                        int W, int H, double sigma_spatial, double sigma_color, int mode, int num_iters);
 
+/* ---------------- joint bilateral filter (cv::ximgproc::jointBilateralFilter) ----------------
+ * jointBilateralFilter(joint, src, dst, d, sigmaColor, sigmaSpace, borderType) (EF.hpp:317;
+ * modules/ximgproc/src/joint_bilateral_filter.cpp = JBF.cpp): every pixel becomes the weighted mean of the source over a
+ * disc around it, a tap's weight falling with its distance and with the difference between the JOINT image's pixels
+ * there and at the centre -- the textbook refinement of a disparity map through the colour view, and the building block
+ * of rollingGuidanceFilter.  One streaming launch per call.  In the chain it stands where the guided filter does:
+ * matcher -> adf_validate_disparity_* / adf_filter_speckles_* -> adf_weighted_median_filter_* (which fills the holes: this
+ * filter is NOT blind to (minDisparity-1)*16, it blends it in) -> this -> adf_reproject_*.
+ *
+ * This is the library's OWN definition.  It keeps JBF.cpp's `_8u` path (JBF.cpp:231-337) operation for operation and
+ * widens the source depths.  The result is bit-exact against the direct NumPy statement tests/jbf_ref.py fed with
+ * adf_jbf_tables_host, and identical from run to run.
+ *
+ * Inputs.  n_maps equally sized maps of W x H, `*_map_stride` bytes apart, rows `*_stride` bytes apart.
+ *   - joint: 8-bit, joint_channels 1 or 3 (interleaved), the size of src.
+ *   - src: ONE channel, depth ADF_8U, ADF_16S or ADF_32F (the reference demands src.depth() == joint.depth(); a 16-bit
+ *     or float disparity map through an 8-bit view is the case this library exists for).
+ *   - dst: one channel, depth dst_depth, any of the three, independent of src's (cv's dDepth; the reference's is
+ *     src.type()).
+ * Parameters, as JBF.cpp:361-371 clamps them: sigma_color <= 0 -> 1, sigma_space <= 0 -> 1;
+ * r = d <= 0 ? cvRound(sigma_space * 1.5) : d / 2, then max(r, 1); cvRound rounds half to even (1.5 -> 2, 4.5 -> 4).
+ * r above ADF_JBF_MAX_RADIUS = 31 is refused.
+ * Tables, built on the host in double with libm's exp, one rounding per entry:
+ *   - colour: C[a] = (float)exp((double)(a * a) * (-0.5 / (sigma_color * sigma_color))), a = 1 .. 255 * joint_channels;
+ *   - space:  S[q] = (float)exp((double)q * (-0.5 / (sigma_space * sigma_space))), q = 1 .. r * r, indexed by the squared
+ *     distance q = i*i + j*j (JBF.cpp:307's value for every tap at that distance);
+ *   - C[0] = S[0] = 1.0f.
+ *   adf_jbf_tables_host writes C (255 * joint_channels + 1 entries), S (r * r + 1 entries, r the returned radius) and r
+ *   exactly as the calls use them; colour and space may both be NULL, which gives the radius alone (what sizes S).  Host
+ *   only -- no device is touched.
+ * Window.  The taps (i, j), -r <= i, j <= r, with i*i + j*j <= r*r, in row-major order: i (rows) outer, j inner.  This
+ * order IS the definition.  A tap outside the image is taken, for joint and src alike (the reference's copyMakeBorder of
+ * both), from the coordinate cv::borderInterpolate gives on each axis of length n:
+ *   - ADF_BORDER_REPLICATE (1):   min(max(p, 0), n - 1);
+ *   - ADF_BORDER_REFLECT (2):     m = p mod 2n (non-negative), then m < n ? m : 2n - 1 - m;
+ *   - ADF_BORDER_REFLECT_101 (4, cv's BORDER_DEFAULT): n == 1 ? 0 : m = p mod (2n - 2), then m < n ? m : 2n - 2 - m.
+ *   Reflection so repeats until the coordinate is inside, and an axis of length 1 gives 0: a 3 x 2 image takes r = 31.
+ *   BORDER_CONSTANT (0), BORDER_WRAP (3) and anything else are NOT built.
+ * Per pixel p, with x = (float)src, sum = 0.0f, wsum = 0.0f, for the taps q in order:
+ *   L = the L1 difference of joint(p) and joint(q) over the channels (0 .. 255 * joint_channels);
+ *   w = S[i*i + j*j] * C[L];  sum = sum + w * x(q);  wsum = wsum + w;
+ * every product and sum rounded to float32, no FMA.  Then y = sum / wsum, the correctly rounded IEEE quotient.  The centre
+ * tap has weight exactly 1, so wsum >= 1: there is no zero divide and no special case.  Denormal table entries and
+ * products stay denormal (nothing is flushed).  Non-finite float sources propagate as the arithmetic gives; the payload
+ * bits of a resulting NaN are not specified.
+ * Output.  dst = y for ADF_32F; rint(y) (half to even, cv's saturate_cast) saturated to the depth for ADF_8U / ADF_16S
+ * (a NaN gives the depth's minimum).
+ * Deviations from the reference, all deliberate:
+ *   - 8-bit joints only: the `_32f` path with its interpolated 4096-bin table is not built;
+ *   - one-channel sources only (callers split them); CV_16S sources; any output depth;
+ *   - an empty joint or joint == src (the reference falls back to cv::bilateralFilter) is refused;
+ *   - the uniform-joint Gaussian shortcut exists only in the `_32f` path and is not taken;
+ *   - no ignore value: run adf_weighted_median_filter_* first, as the sections above say.
+ *   For an 8-bit source and the three border types this is the reference's `_8u` arithmetic itself.
+ * Refused: sigmas that are not finite (as double or as float32), a radius above ADF_JBF_MAX_RADIUS, a border type that is
+ * not built, an unknown depth or joint_channels, NULL joint / src / dst, n_maps, W or H below 1, bases or strides not
+ * aligned to the depth (2 bytes for ADF_16S, 4 for ADF_32F), dst overlapping (by the byte ranges they span) joint or src
+ * (all ADF_EBADARG); W*H at or above 2^31, strides smaller than a row, destination maps of a batch that overlap each
+ * other (ADF_ESIZE).  All of this is checked before a device is touched.
+ * Workspace: none.  The two tables are one immutable device table per (device, sigma_color, sigma_space, r,
+ * joint_channels) in the process-wide store (adf_release_cached_memory drops them); after its first use a key is a
+ * look-up, the call launches one kernel and allocates nothing, and is capturable into a hipGraph.
+ * _device: device pointers on the current HIP device, asynchronous on `stream`.  _host: host pointers; copies, runs and
+ * synchronises. */
+#define ADF_JBF_MAX_RADIUS 31
+#define ADF_BORDER_REPLICATE 1   /* cv::BORDER_REPLICATE */
+#define ADF_BORDER_REFLECT 2     /* cv::BORDER_REFLECT */
+#define ADF_BORDER_REFLECT_101 4 /* cv::BORDER_REFLECT_101 = cv::BORDER_DEFAULT */
+int adf_jbf_tables_host(int d, double sigma_color, double sigma_space, int joint_channels, float* colour, float* space, int* radius);
+int adf_joint_bilateral_filter_device(int n_maps,
+                                      const uint8_t* joint, ptrdiff_t joint_stride, ptrdiff_t joint_map_stride, int joint_channels,
+                                      const void* src, ptrdiff_t src_stride, ptrdiff_t src_map_stride, int src_depth,
+                                      void* dst, ptrdiff_t dst_stride, ptrdiff_t dst_map_stride, int dst_depth,
+                                      int W, int H, int d, double sigma_color, double sigma_space, int border_type,
+                                      void* stream);
+int adf_joint_bilateral_filter_host(int n_maps,
+                                    const uint8_t* joint, ptrdiff_t joint_stride, ptrdiff_t joint_map_stride, int joint_channels,
+                                    const void* src, ptrdiff_t src_stride, ptrdiff_t src_map_stride, int src_depth,
+                                    void* dst, ptrdiff_t dst_stride, ptrdiff_t dst_map_stride, int dst_depth,
+                                    int W, int H, int d, double sigma_color, double sigma_space, int border_type);
+
 #ifdef __cplusplus
 }
 #endif

@@ -283,6 +283,34 @@ inline Ptr<DTFilter> createDTFilter(const Mat& guide, double sigmaSpatial, doubl
     return Ptr<DTFilter>(new DTFilterImpl(guide, sigmaSpatial, sigmaColor, mode, numIters));
 }
 
+// cv::ximgproc::jointBilateralFilter(joint, src, dst, d, sigmaColor, sigmaSpace, borderType) (EF.hpp:317) on host Mats
+// through the library's host entry, in the library's own definition (adf_joint_bilateral_filter_* in adf_wls.h: the
+// reference's `_8u` arithmetic in its order of evaluation, widened to CV_16S and CV_32F sources).  joint: CV_8UC1 or
+// CV_8UC3 (CV_32F joints are not built); src: CV_8UC1, CV_16SC1 or CV_32FC1 of its size (multi-channel sources are not
+// built: split them); dst gets src's depth and may be src.  d > 0: radius d / 2; d <= 0: cvRound(1.5 sigmaSpace); at most
+// ADF_JBF_MAX_RADIUS.  borderType: BORDER_REPLICATE, BORDER_REFLECT or BORDER_REFLECT_101 (= BORDER_DEFAULT, cv's and the
+// default here); BORDER_CONSTANT and BORDER_WRAP are not built and refused.  An empty joint or joint == src, which the
+// reference hands to cv::bilateralFilter, is refused.  The filter is not blind to a matcher's invalid value: run
+// weightedMedianFilter with ignoreValue first.  (BORDER_CONSTANT is declared with remap below.)
+enum BorderTypes { BORDER_REPLICATE = 1, BORDER_REFLECT = 2, BORDER_WRAP = 3, BORDER_REFLECT_101 = 4, BORDER_DEFAULT = 4 }; // cv's values
+inline void jointBilateralFilter(const Mat& joint, const Mat& src, Mat& dst, int d, double sigmaColor, double sigmaSpace,
+                                 int borderType = BORDER_DEFAULT)
+{
+    if (src.empty() || mat_channels(src) != 1 || (mat_depth(src) != D8U && mat_depth(src) != D16S && mat_depth(src) != D32F))
+        throw Exception(ADF_EBADARG, "jointBilateralFilter: src must be a non-empty CV_8UC1, CV_16SC1 or CV_32FC1 image");
+    if (joint.empty() || mat_depth(joint) != D8U)
+        throw Exception(ADF_EBADARG, "jointBilateralFilter: joint must be a non-empty CV_8UC1 or CV_8UC3 image (an empty or CV_32F joint is not built)");
+    if (joint.data == src.data)
+        throw Exception(ADF_EBADARG, "jointBilateralFilter: joint == src is cv::bilateralFilter, which is not built");
+    if (joint.rows != src.rows || joint.cols != src.cols) throw Exception(ADF_ESIZE, "jointBilateralFilter: joint must have src's size");
+    const int depth = mat_depth(src) == D8U ? ADF_8U : mat_depth(src) == D16S ? ADF_16S : ADF_32F;
+    Mat out;                                                             // (dst may be src or joint: the result lands in a new Mat)
+    mat_create(out, src.rows, src.cols, mat_depth(src), 1);
+    check(adf_joint_bilateral_filter_host(1, joint.data, mat_step(joint), 0, mat_channels(joint), src.data, mat_step(src), 0, depth,
+                                          out.data, mat_step(out), 0, depth, src.cols, src.rows, d, sigmaColor, sigmaSpace, borderType));
+    dst = out;
+}
+
 // cv::stereo::censusTransform(image, kernelSize, dist, type) (modules/stereo descriptor.hpp:428, descriptor.cpp:77-98) on a
 // CV_8UC1 host Mat, through the library's host entry: the census descriptor of every pixel, type
 // ADF_SGBM_COST_CENSUS_DENSE (kernelSize 3, 5, 7), ADF_SGBM_COST_CENSUS_SPARSE (5, 7, 9, 11), the modified census
