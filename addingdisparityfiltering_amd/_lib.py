@@ -28,6 +28,7 @@ GF_MAX_RADIUS = 31    # ADF_GF_MAX_RADIUS
 DTF_NC, DTF_IC, DTF_RF, DT_MAX_ITERS = 0, 1, 2, 8    # ADF_DTF_*, ADF_DT_MAX_ITERS
 JBF_MAX_RADIUS = 31    # ADF_JBF_MAX_RADIUS
 BORDER_REPLICATE, BORDER_REFLECT, BORDER_WRAP, BORDER_REFLECT_101 = 1, 2, 3, 4    # cv::BorderTypes; 1, 2 and 4 are built (ADF_BORDER_*)
+RGF_MAX_ITERS = 16    # ADF_RGF_MAX_ITERS
 
 
 class AdfError(RuntimeError):
@@ -72,6 +73,7 @@ _WMF_DEV = [_i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _i, _i,
 _GF_DEV = [_i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _i, _i, _i, _d, _vp, _sz, _vp]
 _DT_DEV = [_i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _i, _i, _d, _d, _i, _i, _vp, _sz, _vp]
 _JBF_DEV = [_i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _i, _i, _i, _d, _d, _i, _vp]
+_RGF_DEV = [_i, _vp, _pd, _pd, _vp, _pd, _pd, _i, _i, _i, _i, _d, _d, _i, _i, _vp, _sz, _vp]
 _FILTER_SCALED_DEV = [_vp, _i, _vp, _pd, _pd, _i, _i, _vp, _pd, _pd, _i, _i, _i, _vp, _pd, _pd, _vp, _pd, _pd,
                       C.POINTER(Rect), _vp]
 # adf_wls_filter_typed_*: the scaled call with a depth behind the left map's strides and one behind the output's
@@ -192,6 +194,10 @@ SYMBOLS = [
     ("adf_jbf_tables_host", _i, [_i, _d, _d, _i, _vp, _vp, C.POINTER(_i)]),
     ("adf_joint_bilateral_filter_device", _i, _JBF_DEV),
     ("adf_joint_bilateral_filter_host", _i, _JBF_DEV[:-1]),
+    ("adf_rolling_guidance_workspace_bytes", _sz, [_i, _i, _i, _i, _i]),
+    ("adf_rgf_tables_host", _i, [_i, _i, _d, _d, _vp, _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_float)]),
+    ("adf_rolling_guidance_filter_device", _i, _RGF_DEV),
+    ("adf_rolling_guidance_filter_host", _i, _RGF_DEV[:-3]),
 ]
 
 _lib = None

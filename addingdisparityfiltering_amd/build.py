@@ -29,6 +29,7 @@ SOURCES = {
     "guided_filter_kernels.hip": [],
     "dt_filter_kernels.hip": [],
     "joint_bilateral_kernels.hip": [],
+    "rolling_guidance_kernels.hip": [],
 }
 OUT = os.path.join(_HERE, "libadf_wls.so")
 # -ffp-contract=off: the exact solver and the confidence map reproduce the reference's separate

@@ -128,6 +128,21 @@ constexpr size_t jbf_space_entries(int r) { return (size_t)r * r + 1; }
 ADF_LOCAL int jbf_table_device(double sc, double ss, int r, int channels, std::shared_ptr<JbfTable>& out,
                                const float** colour, const float** space);
 
+// The rolling guidance filter's tables (include/adf_wls.h: the range table C of T entries, or G of RGF_GRID_ENTRIES
+// for ADF_32F, then S, in one block of floats): an immutable device table per (device, depth, sigma_color, sigma_space,
+// r), kept like the joint bilateral filter's (adf_host.hip: RgfStore).
+struct RgfTable;
+constexpr size_t RGF_GRID_ENTRIES = 4098;  // G[0 .. 4097]
+// The refusals the entry points and adf_rgf_tables_host share (jbf_params_check's, an unknown depth, a `scale` that is
+// not finite); on ADF_OK the clamped sigmas, the radius and scale (1.0f for the integer depths).
+ADF_LOCAL int rgf_params_check(const char* who, int depth, int d, double sigma_color, double sigma_space,
+                               double* sc, double* ss, int* r, float* scale);
+// T for an integer depth (the entries up to and including the first that rounds to 0.0f), 4098 for ADF_32F.
+ADF_LOCAL size_t rgf_colour_entries(int depth, double sc);
+// As jbf_table_device; *entries = what rgf_colour_entries gives.
+ADF_LOCAL int rgf_table_device(int depth, double sc, double ss, int r, std::shared_ptr<RgfTable>& out,
+                               const float** colour, const float** space, int* entries);
+
 // The host-pointer entry points' copies: `n` images of `rows` rows of `row_bytes`, image k at `k * image_stride` bytes
 // with rows `pitch` bytes apart on either side, asynchronously on `st` (a host destination is complete once `st` has
 // been synchronised).  The layout of a staging block stays with the caller.

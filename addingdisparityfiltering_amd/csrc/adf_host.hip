@@ -91,7 +91,8 @@ struct adf::LutTable {
 };
 
 // The process-wide store of one kind of immutable device table (the filters' LutTable, the weighted median's WmfTable,
-// the joint bilateral filter's JbfTable): up to CAP of them, least recently used dropped first.
+// the joint bilateral filter's JbfTable, the rolling guidance filter's RgfTable): up to CAP of them, least recently used
+// dropped first.
 template <class TABLE> struct TableStore {
     static constexpr size_t CAP = 16;
     std::mutex m;
@@ -257,12 +258,19 @@ struct adf::JbfTable {
 };
 using JbfStore = TableStore<JbfTable>;
 
+static void jbf_build_space(double ss, int r, float* space)       // S: the rolling guidance filter's too
+{
+    const double cs = -0.5 / (ss * ss);
+    space[0] = 1.0f;
+    for (int q = 1; q < (int)jbf_space_entries(r); q++) space[q] = (float)exp((double)q * cs);
+}
+
 static void jbf_build_host(double sc, double ss, int r, int channels, float* colour, float* space)
 {
-    const double cc = -0.5 / (sc * sc), cs = -0.5 / (ss * ss);
-    colour[0] = space[0] = 1.0f;
+    const double cc = -0.5 / (sc * sc);
+    colour[0] = 1.0f;
     for (int a = 1; a < (int)jbf_colour_entries(channels); a++) colour[a] = (float)exp((double)(a * a) * cc);
-    for (int q = 1; q < (int)jbf_space_entries(r); q++) space[q] = (float)exp((double)q * cs);
+    jbf_build_space(ss, r, space);
 }
 
 int adf::jbf_params_check(const char* who, int d, double sigma_color, double sigma_space, int joint_channels,
@@ -311,6 +319,95 @@ extern "C" int adf_jbf_tables_host(int d, double sigma_color, double sigma_space
     if (!colour && !space) return ADF_OK;                         // the radius alone: what sizes the space table
     if (!colour || !space) return fail(ADF_EBADARG, "adf_jbf_tables_host: colour and space must both be given (or neither: the radius alone)");
     jbf_build_host(sc, ss, r, joint_channels, colour, space);
+    return ADF_OK;
+}
+
+// The rolling guidance filter's tables (include/adf_wls.h: "rolling guidance filter"), built and kept like the joint
+// bilateral filter's: one block of floats, the range table then S, per (device, depth, sigma_color, sigma_space, r).
+// The range table of an integer depth is C cut after its first zero entry (T entries, up to 65536: the square is formed
+// in double); ADF_32F's is the constant grid G, and sigma_color reaches the kernel as `scale`.
+struct adf::RgfTable {
+    int device = 0, depth = 0, r = 0, entries = 0; double sc = 0, ss = 0; float* dev = nullptr;
+    RgfTable() = default;
+    RgfTable(const RgfTable&) = delete;
+    RgfTable& operator=(const RgfTable&) = delete;
+    ~RgfTable() { if (dev) { DeviceScope ds(device); hipFree(dev); } }
+};
+using RgfStore = TableStore<RgfTable>;
+
+// C[L] for L = 0 .. the first entry that is 0.0f (or the depth's last level); `colour` may be null: the count alone.
+static size_t rgf_build_colour(int depth, double sc, float* colour)
+{
+    if (depth == ADF_32F) {
+        if (colour)
+            for (size_t i = 0; i < RGF_GRID_ENTRIES; i++) colour[i] = (float)exp(-0.5 * ((double)i / 256.0) * ((double)i / 256.0));
+        return RGF_GRID_ENTRIES;
+    }
+    const size_t levels = depth == ADF_8U ? 256 : 65536;
+    const double cc = -0.5 / (sc * sc);
+    if (colour) colour[0] = 1.0f;
+    for (size_t L = 1; L < levels; L++) {
+        const float c = (float)exp((double)L * (double)L * cc);
+        if (colour) colour[L] = c;
+        if (c == 0.0f) return L + 1;
+    }
+    return levels;
+}
+
+size_t adf::rgf_colour_entries(int depth, double sc) { return rgf_build_colour(depth, sc, nullptr); }
+
+int adf::rgf_params_check(const char* who, int depth, int d, double sigma_color, double sigma_space,
+                          double* sc, double* ss, int* r, float* scale)
+{
+    if (depth != ADF_8U && depth != ADF_16S && depth != ADF_32F)
+        return fail(ADF_EBADARG, "%s: src must be CV_8U (ADF_8U), CV_16S (ADF_16S) or CV_32F (ADF_32F), one channel", who);
+    if (int rc = jbf_params_check(who, d, sigma_color, sigma_space, 1, sc, ss, r)) return rc;
+    *scale = depth == ADF_32F ? (float)(256.0 / *sc) : 1.0f;
+    if (!std::isfinite(*scale))
+        return fail(ADF_EBADARG, "%s: sigmaColor %g is too small for a float32 source: 256 / sigmaColor is not a finite float32", who, *sc);
+    return ADF_OK;
+}
+
+int adf::rgf_table_device(int depth, double sc, double ss, int r, std::shared_ptr<RgfTable>& out,
+                          const float** colour, const float** space, int* entries)
+{
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) return fail(ADF_ENODEV, "no HIP device");
+    if (depth == ADF_32F) sc = 1.0;                               // (G does not depend on it)
+    out = RgfStore::get().find([&](const RgfTable& q) { return q.device == device && q.depth == depth && q.sc == sc && q.ss == ss && q.r == r; });
+    if (!out) {
+        const size_t nc = rgf_colour_entries(depth, sc), ns = jbf_space_entries(r);
+        std::vector<float> host(nc + ns);
+        rgf_build_colour(depth, sc, host.data());
+        jbf_build_space(ss, r, host.data() + nc);
+        float* d = nullptr;
+        HIP_TRY(device_malloc(reinterpret_cast<void**>(&d), sizeof(float) * host.size()));
+        hipError_t e = hipMemcpy(d, host.data(), sizeof(float) * host.size(), hipMemcpyHostToDevice);
+        if (e != hipSuccess) { hipFree(d); return fail(ADF_EHIP, "rolling guidance table upload failed: %s", hipGetErrorString(e)); }
+        out = std::make_shared<RgfTable>();
+        out->device = device; out->depth = depth; out->r = r; out->entries = (int)nc; out->sc = sc; out->ss = ss; out->dev = d;
+        RgfStore::get().add(out);
+    }
+    *colour = out->dev;
+    *space = out->dev + out->entries;
+    *entries = out->entries;
+    return ADF_OK;
+}
+
+extern "C" int adf_rgf_tables_host(int depth, int d, double sigma_color, double sigma_space, float* colour, float* space,
+                                   int* radius, int* colour_entries, float* scale)
+{
+    double sc, ss;
+    int r;
+    float k;
+    if (int rc = rgf_params_check("adf_rgf_tables_host", depth, d, sigma_color, sigma_space, &sc, &ss, &r, &k)) return rc;
+    if (radius) *radius = r;
+    if (scale) *scale = k;
+    if (colour_entries) *colour_entries = (int)rgf_colour_entries(depth, sc);
+    if (!colour && !space) return ADF_OK;                         // the sizes alone
+    if (!colour || !space) return fail(ADF_EBADARG, "adf_rgf_tables_host: colour and space must both be given (or neither: the sizes alone)");
+    rgf_build_colour(depth, sc, colour);
+    jbf_build_space(ss, r, space);
     return ADF_OK;
 }
 
@@ -457,4 +554,5 @@ extern "C" void adf_release_cached_memory(void)
     LutStore::get().clear();
     WmfStore::get().clear();
     JbfStore::get().clear();
+    RgfStore::get().clear();
 }

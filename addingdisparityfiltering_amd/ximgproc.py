@@ -26,6 +26,7 @@ edge_filter.hpp (EF.hpp), over the C-ABI in include/adf_wls.h:
     dtFilter(guide, src, sigmaSpatial, sigmaColor, mode, numIters)   EF.hpp:120  / dtfilter_cpu.hpp (DTF_RF only; the library's own exact definition)
     createDTFilter(guide, sigmaSpatial, sigmaColor, mode, numIters) -> DTFilter.filter(src, dst, dDepth)   EF.hpp:100, 80
     jointBilateralFilter(joint, src, d, sigmaColor, sigmaSpace, borderType, dDepth)   EF.hpp:317 / joint_bilateral_filter.cpp (8-bit joints; the library's own exact definition)
+    rollingGuidanceFilter(src, d, sigmaColor, sigmaSpace, numOfIter, borderType)   EF.hpp:350 / rolling_guidance_filter.cpp (one channel; the library's own exact definition)
 
 Images are numpy arrays (host path: copied to the GPU and back) or torch CUDA
 tensors (device path: zero-copy, asynchronous on torch's current stream).  A
@@ -46,6 +47,7 @@ from ._lib import SGBM_RIGHT_MATCHER, SGBM_RIGHT_FROM_VOLUME  # noqa: F401  (re-
 from ._lib import WMF_EXP, WMF_IV1, WMF_IV2, WMF_COS, WMF_JAC, WMF_OFF  # noqa: F401  (cv's WMFWeightType; EXP and OFF are built)
 from ._lib import GF_MAX_RADIUS  # noqa: F401  (re-exported)
 from ._lib import DTF_NC, DTF_IC, DTF_RF, DT_MAX_ITERS  # noqa: F401  (cv's EdgeAwareFiltersList; DTF_RF is built)
+from ._lib import RGF_MAX_ITERS  # noqa: F401  (re-exported)
 from ._lib import JBF_MAX_RADIUS, BORDER_REPLICATE, BORDER_REFLECT, BORDER_WRAP, BORDER_REFLECT_101  # noqa: F401  (cv's BorderTypes; 1, 2 and 4 are built)
 from ._lib import AdfError, PATH_CONF_BAND, PATH_FUSED_FIRST_PASS, PATH_MERGED_PREP, PATH_ROW_WEIGHTS_GUIDE, PATH_SCALED_FUSED, PATH_SCALED_HALF, Rect, SOLVER_EXACT, SOLVER_WAVE  # noqa: F401  (re-exported)
 
@@ -1623,6 +1625,115 @@ def jointBilateralFilter(joint, src, d, sigmaColor, sigmaSpace, borderType=BORDE
         return dst
     with torch.cuda.device(S.keep.device):
         _call("adf_joint_bilateral_filter", S, args)
+    return dst
+
+
+# ---------------------------------------------------------------------------------------------
+# cv::ximgproc::rollingGuidanceFilter (EF.hpp:350, rolling_guidance_filter.cpp) in the library's own exact definition
+# (include/adf_wls.h; csrc/rolling_guidance_kernels.hip; the direct statement is tests/rgf_ref.py).
+# ---------------------------------------------------------------------------------------------
+_RGF = "rollingGuidanceFilter"
+
+
+def _rgf_depth(who, depth_or_dtype):
+    """The ADF depth code of a depth code (CV_8U, CV_16S, CV_32F) or of a numpy / torch dtype; anything else is refused."""
+    if isinstance(depth_or_dtype, int) and depth_or_dtype in _GF_DTYPE:
+        return _DEPTH[_GF_DTYPE[depth_or_dtype]]
+    for dt in (np.uint8, np.int16, np.float32):
+        if torch is not None and isinstance(depth_or_dtype, torch.dtype):
+            if depth_or_dtype is _TORCH_DTYPE[dt]:
+                return _DEPTH[dt]
+            continue
+        try:
+            if np.dtype(depth_or_dtype) == np.dtype(dt):
+                return _DEPTH[dt]
+        except TypeError:
+            break
+    raise AdfError(_lib.ADF_EBADARG, "%s: the depth must be uint8 (CV_8U), int16 (CV_16S) or float32 (CV_32F)" % who)
+
+
+def rgfTables(depth_or_dtype, d, sigmaColor, sigmaSpace):
+    """The tables of rollingGuidanceFilter exactly as its calls use them (adf_rgf_tables_host): (colour, space, r, scale).
+    For uint8 / int16 `colour` is C, float32 of T entries indexed by min(|J(p) - J(q)|, T - 1) -- the range table cut after
+    its first zero entry, T <= 256 or 65536 -- and scale is 1.0; for float32 it is the constant grid G of 4098 entries that
+    |J(p) - J(q)| * scale is interpolated in, scale = float32(256 / sigmaColor).  `space` is S, float32 of r * r + 1
+    entries indexed by the squared distance, and r the radius the clamps give.  Host only: no device is touched."""
+    depth = _rgf_depth("rgfTables", depth_or_dtype)
+    r, n, k = C.c_int(0), C.c_int(0), C.c_float(0)
+    fn = _lib.lib().adf_rgf_tables_host
+    args = (depth, int(d), float(sigmaColor), float(sigmaSpace))
+    _lib.check(fn(*args, None, None, C.byref(r), C.byref(n), C.byref(k)))   # (the sizes)
+    colour, space = np.empty(n.value, np.float32), np.empty(r.value * r.value + 1, np.float32)
+    _lib.check(fn(*args, colour.ctypes.data, space.ctypes.data, C.byref(r), C.byref(n), C.byref(k)))
+    return colour, space, r.value, np.float32(k.value)
+
+
+def rollingGuidanceWorkspaceBytes(n, H, W, dtype, numOfIter):
+    """Bytes of device workspace rollingGuidanceFilter needs for n maps of H x W of `dtype` (or depth code) and numOfIter
+    iterations (adf_rolling_guidance_workspace_bytes): one plane of that depth per map, which takes every other
+    iteration's result; 0 for numOfIter <= 1."""
+    return int(_lib.lib().adf_rolling_guidance_workspace_bytes(int(n), int(W), int(H), _rgf_depth("rollingGuidanceWorkspaceBytes", dtype), int(numOfIter)))
+
+
+def rollingGuidanceFilter(src, d=-1, sigmaColor=25, sigmaSpace=3, numOfIter=4, borderType=BORDER_DEFAULT, dst=None, workspace=None):
+    """cv::ximgproc::rollingGuidanceFilter(src, dst, d, sigmaColor, sigmaSpace, numOfIter, borderType) in the library's own
+    definition (include/adf_wls.h): J_0 = src; numOfIter times J_{k+1} = the joint bilateral filter of src with the joint
+    J_k, stored in src's depth; dst = the last J.  Structures below the spatial scale vanish in the first iteration, the
+    later ones restore the large edges -- with no colour view.  Bit-exact against tests/rgf_ref.py fed with rgfTables.
+
+        src         uint8, int16 or float32, (H,W) or a batch (N,H,W), one channel
+        d           the diameter: r = d // 2; d <= 0: r = round-half-even(1.5 sigmaSpace); r is raised to 1 and must not
+                    exceed 31 (JBF_MAX_RADIUS)
+        sigmaColor  in the map's own units (1/16 pixel for a matcher's int16 map); sigmaSpace in pixels; finite, <= 0 means 1
+        numOfIter   0 .. 16 (RGF_MAX_ITERS); 0 copies src
+        borderType  BORDER_REPLICATE, BORDER_REFLECT or BORDER_REFLECT_101 (cv's default, the default here)
+        dst         None, or an array / tensor of src's dtype and shape that does not overlap it (no in-place call)
+
+    The range weight of uint8 / int16 maps is a host-built table of the integer difference; float32 maps interpolate a
+    constant 4096-bin grid laid over 16 sigmaColor (not, as the reference, over the joint's min-max range), and a uniform
+    map takes no Gaussian shortcut.  The filter is not blind to a matcher's invalid value: fill the holes first
+    (weightedMedianFilter with ignoreValue).  Torch CUDA tensors run on the device, asynchronously on torch's current
+    stream; `workspace` (device path only): a CUDA tensor of at least rollingGuidanceWorkspaceBytes(...) bytes -- once a
+    (dtype, sigmaColor, sigmaSpace, r) has been used the call then allocates nothing and may be captured into a CUDA
+    graph; None = the library's cached scratch.  Numpy arrays take the host entry point.  Returns dst."""
+    if src is None:
+        raise AdfError(_lib.ADF_EBADARG, "%s: src must not be empty" % _RGF)
+    b = _jbf_border(_RGF, borderType)
+    nd = len(src.shape)
+    if nd not in (2, 3):
+        raise AdfError(_lib.ADF_EBADARG, "%s: src must be (H,W) or a batch (N,H,W) of one-channel maps; multi-channel sources are not built" % _RGF)
+    batched = nd == 3
+    for dt in (np.uint8, np.int16, np.float32):
+        if _map_dtype(src, dt) is not None:
+            break
+    else:
+        raise AdfError(_lib.ADF_EBADARG, "%s: src must be uint8 (CV_8U), int16 (CV_16S) or float32 (CV_32F)" % _RGF)
+    S = _Image(src, dt, "src", batched)
+    if dst is src:
+        raise AdfError(_lib.ADF_EBADARG, "%s: dst is src: there is no in-place call" % _RGF)
+    if dst is None:
+        dst = _out_like(S, batched, dt)
+    D = _Image(dst, dt, "dst", batched)
+    if (D.n, D.h, D.w) != (S.n, S.h, S.w) or D.device != S.device:
+        raise AdfError(_lib.ADF_ESIZE, "%s: dst must have src's size on its side (host or device)" % _RGF)
+    if S.device and D.keep.device != S.keep.device:
+        raise AdfError(_lib.ADF_EBADARG, "%s: dst lives on %s, src on %s" % (_RGF, D.keep.device, S.keep.device))
+    args = (S.n, S.ptr, S.stride, S.pair_stride, D.ptr, D.stride, D.pair_stride, _DEPTH[dt], S.w, S.h, int(d), float(sigmaColor),
+            float(sigmaSpace), int(numOfIter), b)
+    if not S.device:
+        if workspace is not None:
+            raise AdfError(_lib.ADF_EBADARG, "%s: a workspace goes with CUDA tensors only" % _RGF)
+        _call("adf_rolling_guidance_filter", S, args)
+        return dst
+    ws, ws_bytes = None, 0
+    if workspace is not None:
+        if not (_is_torch(workspace) and workspace.is_cuda and workspace.is_contiguous()):
+            raise AdfError(_lib.ADF_EBADARG, "%s: workspace must be a contiguous CUDA tensor (or None)" % _RGF)
+        if workspace.device != S.keep.device:
+            raise AdfError(_lib.ADF_EBADARG, "%s: workspace lives on %s, src on %s" % (_RGF, workspace.device, S.keep.device))
+        ws, ws_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+    with torch.cuda.device(S.keep.device):
+        _call("adf_rolling_guidance_filter", S, args + (ws, ws_bytes))
     return dst
 
 

@@ -1251,6 +1251,94 @@ int adf_joint_bilateral_filter_host(int n_maps,
                                     void* dst, ptrdiff_t dst_stride, ptrdiff_t dst_map_stride, int dst_depth,
                                     int W, int H, int d, double sigma_color, double sigma_space, int border_type);
 
+/* ---------------- rolling guidance filter (cv::ximgproc::rollingGuidanceFilter) ----------------
+ * rollingGuidanceFilter(src, dst, d, sigmaColor, sigmaSpace, numOfIter, borderType) (EF.hpp:350;
+ * modules/ximgproc/src/rolling_guidance_filter.cpp = RGF.cpp:45-82): guidance = src; numOfIter times
+ * jointBilateralFilter(guidance, src, guidance, ...); dst = guidance.  The scale-aware smoother of the family: structures
+ * smaller than the spatial scale (matcher noise, speckle remnants) vanish in the first iteration, the later ones put the
+ * large depth edges back where they were -- and it needs no colour view at all.  num_iter launches per call.  In the
+ * chain it stands where the joint bilateral filter does, after the holes are filled (adf_weighted_median_filter_*).
+ *
+ * This is the library's OWN definition, bit-exact against the direct NumPy statement tests/rgf_ref.py fed with
+ * adf_rgf_tables_host, and identical from run to run.
+ *
+ * Inputs.  n_maps equally sized maps of W x H, `*_map_stride` bytes apart, rows `*_stride` bytes apart.
+ *   - src: ONE channel, depth ADF_8U, ADF_16S or ADF_32F.
+ *   - dst: one channel, THE SOURCE'S depth (the reference's dst has src.type(); there is no dDepth here).  dst overlaps
+ *     neither src nor, across a batch, another map's dst.
+ * Parameters.  sigma_color <= 0 -> 1, sigma_space <= 0 -> 1 (RGF.cpp:56-59); the radius as the joint bilateral filter's:
+ * r = d <= 0 ? cvRound(sigma_space * 1.5) : d / 2, then max(r, 1); r above ADF_JBF_MAX_RADIUS is refused.  border_type:
+ * ADF_BORDER_REPLICATE, ADF_BORDER_REFLECT or ADF_BORDER_REFLECT_101 (cv's default), cv::borderInterpolate on each axis
+ * exactly as the joint bilateral section states it.  num_iter: 0 copies src to dst (the reference's `while (numOfIter--)`
+ * does the same); negative (the reference would loop until the counter wraps) and above ADF_RGF_MAX_ITERS = 16 (a
+ * decision, not a measurement: the filter has converged long before) are refused.
+ * Iteration.  J_0 = src.  For k = 0 .. num_iter - 1, J_{k+1} is the joint bilateral filter of src with joint J_k, STORED
+ * IN THE SOURCE'S DEPTH: rint (half to even), saturated, for the integer depths (a NaN gives the depth's minimum); as it
+ * is for ADF_32F.  dst = J_num_iter.  The border rule applies to src and to J_k alike.
+ * Per pixel p.  The taps q = p + (i, j) with i*i + j*j <= r*r, rows outer, columns inner: this order IS the definition.
+ * With x = (float)src, sum = 0.0f, wsum = 0.0f, per tap:
+ *   w = S[i*i + j*j] * Wc(p, q);  sum = sum + w * x(q);  wsum = wsum + w;
+ * every product and sum rounded to float32, no FMA; y = sum / wsum is the correctly rounded IEEE quotient.  S is the joint
+ * bilateral filter's space table, unchanged (S[0] = 1).
+ * Range weight Wc, integer depths.  L = |J_k(p) - J_k(q)| as an integer (0 .. 255 or 0 .. 65535); Wc = C[min(L, T - 1)].
+ *   C[0] = 1.0f, C[L] = (float)exp((double)L * (double)L * (-0.5 / (sigma_color * sigma_color))), built on the host in
+ *   double with libm's exp, one rounding per entry (the square is formed in double: L * L in int overflows from 46341
+ *   on).  T is the number of entries up to and including the first that rounds to 0.0f, at most 256 or 65536 (16 at
+ *   sigma_color 1, 362 at 25, 14422 at 1000, all 65536 from 4545 up).  C falls monotonically, so the clamp returns exactly
+ *   what the full table would.  For ADF_8U this is the joint bilateral filter's C for one channel and the arithmetic is
+ *   the reference's `_8u` path operation for operation: one iteration equals adf_joint_bilateral_filter_* with a
+ *   one-channel 8-bit joint and dst_depth = ADF_8U, bit for bit.
+ * Range weight Wc, ADF_32F.  The reference's `_32f` path (JBF.cpp:98-108) interpolates a 4096-bin table laid over the
+ *   joint's min-max range, which it finds anew with minMaxLoc on every call, and switches to a square-window GaussianBlur
+ *   when the joint is uniform.  Ours keeps the interpolation and puts the grid on sigma_color instead: no reduction, no
+ *   data-dependent table, no second algorithm.
+ *     G[i] = (float)exp(-0.5 * (i / 256.0) * (i / 256.0)), i = 0 .. 4097: a constant table, independent of every
+ *            parameter, zero from i = 3692 on -- a difference beyond 16 sigma weighs exactly 0;
+ *     scale = (float)(256.0 / sigma_color); a call whose scale is not finite is refused;
+ *     L = fabsf(J(p) - J(q));  a = L * scale;  if (!(a < 4096.0f)) a = 4096.0f   (NaN and infinity go to the zero end);
+ *     idx = (int)a;  f = a - (float)idx;  Wc = G[idx] + f * (G[idx + 1] - G[idx]), each operation rounded separately.
+ *   The centre tap has L = 0 and weight exactly 1 for finite data, so wsum >= 1.  Non-finite sources propagate as this
+ *   arithmetic gives; the payload bits of a NaN are not specified.
+ * adf_rgf_tables_host writes the range table (`colour`: C, T entries, or G, 4098 entries) and S (`space`, r * r + 1
+ * entries) exactly as the calls use them, and returns the radius, the range table's entry count and scale (1.0f for the
+ * integer depths) through the pointers that are not NULL; colour == space == NULL gives the sizes alone.  Host only.
+ * Deviations from the reference, all deliberate:
+ *   - CV_16S sources;
+ *   - the float grid as above, and no Gaussian shortcut for a uniform joint;
+ *   - one-channel sources only (callers split them);
+ *   - no in-place call (dst must not overlap src);
+ *   - no ignore value: the matcher's invalid value is blended in, as with the joint bilateral filter.  The range weight
+ *     on the map itself makes it a weak tap, not an absent one; hole filling still comes first
+ *     (adf_weighted_median_filter_*).
+ * Refused, all before a device is touched: what the joint bilateral section lists (sigmas that are not finite, the
+ * radius, the border type, an unknown depth, NULL src / dst, n_maps, W or H below 1, alignment, dst overlapping src: all
+ * ADF_EBADARG; W*H at or above 2^31, strides smaller than a row, overlapping destination maps: ADF_ESIZE), num_iter
+ * outside 0 .. ADF_RGF_MAX_ITERS, a scale that is not finite, a workspace that overlaps src or dst (ADF_EBADARG), a
+ * workspace that is too small (ADF_ESIZE).
+ * Workspace.  The iterations write alternately into one dense plane of the source's depth per map and into dst, arranged
+ * so that the last one writes dst; src is read by every iteration and never written.  Hence
+ * adf_rolling_guidance_workspace_bytes = n_maps * W * H * the depth's size for num_iter >= 2, and 0 for num_iter <= 1 and
+ * for arguments the calls refuse.  The rules are adf_dt_filter_*'s: NULL takes library scratch from the process-wide
+ * cache; with a caller's workspace the call allocates nothing and is capturable into a hipGraph once the tables are
+ * warm.  The device tables (the range table, then S) are one immutable table per (device, depth, sigma_color,
+ * sigma_space, r) in the process-wide store next to the joint bilateral filter's, dropped by adf_release_cached_memory.
+ * _device: device pointers on the current HIP device, asynchronous on `stream`.  _host: host pointers; copies, runs and
+ * synchronises. */
+#define ADF_RGF_MAX_ITERS 16
+size_t adf_rolling_guidance_workspace_bytes(int n_maps, int W, int H, int depth, int num_iter);
+int adf_rgf_tables_host(int depth, int d, double sigma_color, double sigma_space, float* colour, float* space,
+                        int* radius, int* colour_entries, float* scale);
+int adf_rolling_guidance_filter_device(int n_maps,
+                                       const void* src, ptrdiff_t src_stride, ptrdiff_t src_map_stride,
+                                       void* dst, ptrdiff_t dst_stride, ptrdiff_t dst_map_stride,
+                                       int depth, int W, int H, int d, double sigma_color, double sigma_space, int num_iter,
+                                       int border_type, void* workspace, size_t workspace_bytes, void* stream);
+int adf_rolling_guidance_filter_host(int n_maps,
+                                     const void* src, ptrdiff_t src_stride, ptrdiff_t src_map_stride,
+                                     void* dst, ptrdiff_t dst_stride, ptrdiff_t dst_map_stride,
+                                     int depth, int W, int H, int d, double sigma_color, double sigma_space, int num_iter,
+                                     int border_type);
+
 #ifdef __cplusplus
 }
 #endif

@@ -311,6 +311,27 @@ inline void jointBilateralFilter(const Mat& joint, const Mat& src, Mat& dst, int
     dst = out;
 }
 
+// cv::ximgproc::rollingGuidanceFilter(src, dst, d, sigmaColor, sigmaSpace, numOfIter, borderType) (EF.hpp:350) on host Mats
+// through the library's host entry, in the library's own definition (adf_rolling_guidance_filter_* in adf_wls.h): numOfIter
+// joint bilateral filters of src, each with the previous result -- kept in src's depth -- as the joint, the first with src
+// itself.  src: CV_8UC1, CV_16SC1 or CV_32FC1 (multi-channel sources are not built: split them); dst gets src's type and
+// may be src (the result lands in a new Mat).  d, sigmaSpace and borderType as for jointBilateralFilter above; sigmaColor
+// is in the map's own units; numOfIter 0 .. ADF_RGF_MAX_ITERS, 0 copies src.  CV_32F maps interpolate a constant grid laid
+// over 16 sigmaColor, not over the joint's min-max range as the reference does, and take no Gaussian shortcut when
+// uniform.  The filter is not blind to a matcher's invalid value: run weightedMedianFilter with ignoreValue first.
+inline void rollingGuidanceFilter(const Mat& src, Mat& dst, int d = -1, double sigmaColor = 25, double sigmaSpace = 3, int numOfIter = 4,
+                                  int borderType = BORDER_DEFAULT)
+{
+    if (src.empty() || mat_channels(src) != 1 || (mat_depth(src) != D8U && mat_depth(src) != D16S && mat_depth(src) != D32F))
+        throw Exception(ADF_EBADARG, "rollingGuidanceFilter: src must be a non-empty CV_8UC1, CV_16SC1 or CV_32FC1 image");
+    const int depth = mat_depth(src) == D8U ? ADF_8U : mat_depth(src) == D16S ? ADF_16S : ADF_32F;
+    Mat out;                                                             // (dst may be src: the result lands in a new Mat)
+    mat_create(out, src.rows, src.cols, mat_depth(src), 1);
+    check(adf_rolling_guidance_filter_host(1, src.data, mat_step(src), 0, out.data, mat_step(out), 0, depth, src.cols, src.rows, d,
+                                           sigmaColor, sigmaSpace, numOfIter, borderType));
+    dst = out;
+}
+
 // cv::stereo::censusTransform(image, kernelSize, dist, type) (modules/stereo descriptor.hpp:428, descriptor.cpp:77-98) on a
 // CV_8UC1 host Mat, through the library's host entry: the census descriptor of every pixel, type
 // ADF_SGBM_COST_CENSUS_DENSE (kernelSize 3, 5, 7), ADF_SGBM_COST_CENSUS_SPARSE (5, 7, 9, 11), the modified census
