@@ -1,8 +1,10 @@
 // adf_host.h -- the host toolkit every C-ABI source shares (adf_host.hip): error returns, the device scope, device
 // memory (growable buffers, the process-wide block cache, scratch taken from it), the weight tables, the image copies
 // of the host-pointer entry points, and what the stateless operators' launches share: the launch check, rounding up,
-// THE batch loop over the grid limit, the rule for destination images that must not overlap, and the choice between a
-// caller's workspace and library scratch.  Host code only; what kernels and host code share is adf_internal.h.
+// THE batch loop over the grid limit, THE launch of a tile kernel over every tile of every image, the rule for
+// destination images that must not overlap, the choice between a caller's workspace and library scratch, and the
+// checks the edge-aware filters' entry points make alike: the depths, alignment, the bytes a batch spans, the borders
+// that are built.  Host code only; what kernels and host code share is adf_internal.h.
 #pragma once
 
 #include "adf_internal.h"
@@ -52,9 +54,51 @@ template <class F> int for_batches(int n, int per_launch, F&& f)
     return ADF_OK;
 }
 
+// THE launch of a tile kernel -- one workgroup of tile_w x tile_h threads per tile of as many output pixels, the images
+// along the grid's y -- over every tile of n images of W x H.  ARGS has tiles_x (tiles per row of tiles, set here) and
+// tile0 (the first tile of a launch); a launch holds up to GRID_LIMIT images and PER_LAUNCH tiles.  point(a, m0)
+// re-points the args at image m0.  A kernel whose dynamic LDS comes near the default limit has the limit raised first.
+template <class ARGS, class POINT>
+ADF_LOCAL int launch_tiles(void (*kernel)(ARGS), size_t lds, int W, int H, int tile_w, int tile_h, int n, ARGS a, hipStream_t st, POINT&& point)
+{
+    if (lds > 48 * 1024 - 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    const unsigned tiles_y = (unsigned)((H + tile_h - 1) / tile_h);
+    a.tiles_x = (unsigned)((W + tile_w - 1) / tile_w);
+    const uint64_t tiles = (uint64_t)a.tiles_x * tiles_y;               // W*H is below 2^31 and a tile has 256 pixels: 32 bits
+    constexpr uint64_t PER_LAUNCH = 1u << 22;                            // (a grid's threads stay below 2^31)
+    return for_batches(n, GRID_LIMIT, [&](int m0, unsigned nm) {
+        point(a, m0);
+        for (uint64_t t0 = 0; t0 < tiles; t0 += PER_LAUNCH) {
+            a.tile0 = (unsigned)t0;
+            hipLaunchKernelGGL(kernel, dim3((unsigned)std::min(tiles - t0, PER_LAUNCH), nm), dim3((unsigned)(tile_w * tile_h)), lds, st, a);
+        }
+        return launched();
+    });
+}
+
 // n images of `rows` rows of `row_bytes` (rows `stride`, images `image_stride` bytes apart) stay clear of one another:
 // they follow one another or, where the operator allows it, interleave row by row.
 ADF_LOCAL bool images_disjoint(int n, ptrdiff_t row_bytes, int rows, ptrdiff_t stride, ptrdiff_t image_stride, bool may_interleave);
+
+// What the edge-aware filters' checks share.  An image depth (ADF_8U, ADF_16S, ADF_32F) and its bytes per pixel:
+constexpr bool known_depth(int depth) { return depth == ADF_8U || depth == ADF_16S || depth == ADF_32F; }
+constexpr size_t depth_size(int depth) { return depth == ADF_8U ? 1 : depth == ADF_16S ? 2 : 4; }
+// A pointer and its strides are multiples of the element size `es` (a power of two).
+inline bool aligned(const void* p, ptrdiff_t stride, ptrdiff_t map_stride, ptrdiff_t es)
+{
+    return !(((uintptr_t)p & (es - 1)) || (stride & (es - 1)) || (map_stride & (es - 1)));
+}
+// The bytes n images span, [lo, hi): what "overlap" is tested on.
+struct Span { uintptr_t lo, hi; };
+inline Span span_of(const void* p, int n, ptrdiff_t row_bytes, int rows, ptrdiff_t stride, ptrdiff_t map_stride)
+{
+    const uintptr_t b = reinterpret_cast<uintptr_t>(p);
+    return Span{b, b + (uintptr_t)((ptrdiff_t)(n - 1) * map_stride + (ptrdiff_t)(rows - 1) * stride + row_bytes)};
+}
+inline bool overlap(Span a, Span b) { return a.lo < b.hi && b.lo < a.hi; }
+// The borders the bilateral filters build are BORDER_REPLICATE, BORDER_REFLECT and BORDER_REFLECT_101: BORDER_CONSTANT
+// and BORDER_WRAP are refused by name, any other value by number.
+ADF_LOCAL int border_check(const char* who, int border);
 
 // Growable device buffer (never shrinks; freed with the handle).  Growing drains `st` before the old block is freed.
 // FILL_ZERO clears a newly allocated block on `st` (the filters: the sweeps read, and discard, pitch padding);

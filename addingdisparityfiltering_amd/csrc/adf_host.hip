@@ -59,6 +59,15 @@ bool adf::images_disjoint(int n, ptrdiff_t row_bytes, int rows, ptrdiff_t stride
     return may_interleave && image_stride >= row_bytes && image_stride * (n - 1) + row_bytes <= stride;
 }
 
+int adf::border_check(const char* who, int border)
+{
+    if (border == 0 || border == 3)
+        return fail(ADF_EBADARG, "%s: %s is not built; BORDER_REPLICATE, BORDER_REFLECT and BORDER_REFLECT_101 are", who, border == 0 ? "BORDER_CONSTANT" : "BORDER_WRAP");
+    if (border != ADF_BORDER_REPLICATE && border != ADF_BORDER_REFLECT && border != ADF_BORDER_REFLECT_101)
+        return fail(ADF_EBADARG, "%s: borderType %d is not built; BORDER_REPLICATE (1), BORDER_REFLECT (2) and BORDER_REFLECT_101 (4) are", who, border);
+    return ADF_OK;
+}
+
 int adf::DevBuf::reserve(size_t need, hipStream_t st, Fill fill)
 {
     if (need <= bytes) return ADF_OK;
@@ -82,17 +91,23 @@ int adf::DevBuf::reserve(size_t need, hipStream_t st, Fill fill)
 // per call, and 3*256*256 libm calls cost ~1 ms on one core -- ten times the 720p filter call itself.  A table seen
 // before is a look-up; a new one is built by a few threads (each entry is the same scalar libm expression as before:
 // same bits).
-struct adf::LutTable {
-    int device = 0; float sigma = 0; float* dev = nullptr;
-    LutTable() = default;
-    LutTable(const LutTable&) = delete;
-    LutTable& operator=(const LutTable&) = delete;
-    ~LutTable() { if (dev) { DeviceScope ds(device); hipFree(dev); } }
+//
+// What every kind of immutable device table is: `count` elements of T at `dev` on `device`, found by `key`; hipFree of a
+// dropped table waits for the device, so a kernel queued with it has finished reading.
+template <class T, class KEY> struct ADF_LOCAL DeviceTable {
+    using Elem = T;
+    using Key = KEY;
+    int device = 0; KEY key{}; size_t count = 0; T* dev = nullptr;
+    DeviceTable() = default;
+    DeviceTable(const DeviceTable&) = delete;
+    DeviceTable& operator=(const DeviceTable&) = delete;
+    ~DeviceTable() { if (dev) { DeviceScope ds(device); hipFree(dev); } }
 };
+struct adf::LutTable : DeviceTable<float, float> {};               // key: sigma
 
 // The process-wide store of one kind of immutable device table (the filters' LutTable, the weighted median's WmfTable,
 // the joint bilateral filter's JbfTable, the rolling guidance filter's RgfTable): up to CAP of them, least recently used
-// dropped first.
+// dropped first.  THE way to a table is table_device: a look-up, else the one upload.
 template <class TABLE> struct TableStore {
     static constexpr size_t CAP = 16;
     std::mutex m;
@@ -119,6 +134,29 @@ template <class TABLE> struct TableStore {
     void clear() { std::lock_guard<std::mutex> lk(m); tables.clear(); }
 };
 using LutStore = TableStore<LutTable>;
+
+// The table of `key` on the current device: a look-up when the key was seen before (no device work, capturable), else
+// count(), a call made only then, gives its size, build(host) fills that many elements on the host, and one synchronous
+// copy uploads them (`what` names the table where that fails).  The caller holds `out` until its launches are queued.
+template <class TABLE, class COUNT, class BUILD>
+static int table_device(const char* what, const typename TABLE::Key& key, COUNT&& count, BUILD&& build, std::shared_ptr<TABLE>& out)
+{
+    using Elem = typename TABLE::Elem;
+    int device = 0;
+    if (hipGetDevice(&device) != hipSuccess) return fail(ADF_ENODEV, "no HIP device");
+    out = TableStore<TABLE>::get().find([&](const TABLE& q) { return q.device == device && q.key == key; });
+    if (out) return ADF_OK;
+    std::vector<Elem> host(count());
+    build(host.data());
+    Elem* d = nullptr;
+    HIP_TRY(device_malloc(reinterpret_cast<void**>(&d), sizeof(Elem) * host.size()));
+    hipError_t e = hipMemcpy(d, host.data(), sizeof(Elem) * host.size(), hipMemcpyHostToDevice);
+    if (e != hipSuccess) { hipFree(d); return fail(ADF_EHIP, "%s table upload failed: %s", what, hipGetErrorString(e)); }
+    out = std::make_shared<TABLE>();
+    out->device = device; out->key = key; out->count = host.size(); out->dev = d;
+    TableStore<TABLE>::get().add(out);
+    return ADF_OK;
+}
 
 static void lut_build_host(float s, float* host)
 {
@@ -158,7 +196,7 @@ static void lut_build_host(float s, float* host)
 int adf::Lut::ensure(float s, hipStream_t st)
 {
     for (auto& e : tables)
-        if (e.t->sigma == s) { e.used = ++tick; cur = e.t->dev; return ADF_OK; }
+        if (e.t->key == s) { e.used = ++tick; cur = e.t->dev; return ADF_OK; }
     if ((int)tables.size() >= LUT_CACHE) {                 // drop the least recently used table: kernels of
         size_t lru = 0;                                    // earlier calls on `st` may still read it
         for (size_t k = 1; k < tables.size(); k++) if (tables[k].used < tables[lru].used) lru = k;
@@ -167,7 +205,7 @@ int adf::Lut::ensure(float s, hipStream_t st)
     }
     int device = 0;
     HIP_TRY(hipGetDevice(&device));
-    std::shared_ptr<LutTable> t = LutStore::get().find([&](const LutTable& q) { return q.device == device && q.sigma == s; });
+    std::shared_ptr<LutTable> t = LutStore::get().find([&](const LutTable& q) { return q.device == device && q.key == s; });
     if (!t) {
         std::vector<float> host(ADF_LUT_LEVELS);
         lut_build_host(s, host.data());
@@ -176,7 +214,7 @@ int adf::Lut::ensure(float s, hipStream_t st)
         hipError_t e = hipMemcpy(d, host.data(), sizeof(float) * ADF_LUT_LEVELS, hipMemcpyHostToDevice);
         if (e != hipSuccess) { hipFree(d); return fail(ADF_EHIP, "LUT upload failed: %s", hipGetErrorString(e)); }
         t = std::make_shared<LutTable>();
-        t->device = device; t->sigma = s; t->dev = d;
+        t->device = device; t->key = s; t->count = ADF_LUT_LEVELS; t->dev = d;
         LutStore::get().add(t);
     }
     tables.push_back(Entry{t, ++tick});
@@ -185,15 +223,12 @@ int adf::Lut::ensure(float s, hipStream_t st)
 }
 
 // The weighted median filter's table (include/adf_wls.h: T), built on the host with libm like the table above and kept
-// the same way: one immutable device table per (device, sigma, weight type), a look-up after its first use.  hipFree of
-// a dropped table waits for the device, so a kernel queued with it has finished reading.
-struct adf::WmfTable {
-    int device = 0, type = 0; double sigma = 0; uint32_t* dev = nullptr;
-    WmfTable() = default;
-    WmfTable(const WmfTable&) = delete;
-    WmfTable& operator=(const WmfTable&) = delete;
-    ~WmfTable() { if (dev) { DeviceScope ds(device); hipFree(dev); } }
+// the same way: one immutable device table per (device, sigma, weight type), a look-up after its first use.
+struct WmfKey {
+    double sigma; int type;
+    bool operator==(const WmfKey& o) const { return sigma == o.sigma && type == o.type; }
 };
+struct adf::WmfTable : DeviceTable<uint32_t, WmfKey> {};
 using WmfStore = TableStore<WmfTable>;
 
 static void wmf_build_host(double sigma, int weight_type, uint32_t* host)
@@ -221,20 +256,9 @@ int adf::wmf_weights_check(const char* who, double sigma, int weight_type)
 int adf::wmf_table_device(double sigma, int weight_type, std::shared_ptr<WmfTable>& out, const uint32_t** dev)
 {
     if (weight_type == ADF_WMF_OFF) sigma = 1.0;                  // (one table whatever the sigma)
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess) return fail(ADF_ENODEV, "no HIP device");
-    out = WmfStore::get().find([&](const WmfTable& q) { return q.device == device && q.sigma == sigma && q.type == weight_type; });
-    if (!out) {
-        std::vector<uint32_t> host(ADF_WMF_TABLE_LEVELS);
-        wmf_build_host(sigma, weight_type, host.data());
-        uint32_t* d = nullptr;
-        HIP_TRY(device_malloc(reinterpret_cast<void**>(&d), sizeof(uint32_t) * ADF_WMF_TABLE_LEVELS));
-        hipError_t e = hipMemcpy(d, host.data(), sizeof(uint32_t) * ADF_WMF_TABLE_LEVELS, hipMemcpyHostToDevice);
-        if (e != hipSuccess) { hipFree(d); return fail(ADF_EHIP, "weighted median table upload failed: %s", hipGetErrorString(e)); }
-        out = std::make_shared<WmfTable>();
-        out->device = device; out->type = weight_type; out->sigma = sigma; out->dev = d;
-        WmfStore::get().add(out);
-    }
+    if (int rc = table_device("weighted median", WmfKey{sigma, weight_type}, [] { return (size_t)ADF_WMF_TABLE_LEVELS; },
+                              [&](uint32_t* host) { wmf_build_host(sigma, weight_type, host); }, out))
+        return rc;
     *dev = out->dev;
     return ADF_OK;
 }
@@ -249,13 +273,11 @@ extern "C" int adf_wmf_weight_table_host(double sigma, int weight_type, uint32_t
 
 // The joint bilateral filter's tables (include/adf_wls.h: C and S), built on the host with libm like the tables above and
 // kept the same way: one block of floats, C then S, per (device, sigma_color, sigma_space, r, channels).
-struct adf::JbfTable {
-    int device = 0, r = 0, channels = 0; double sc = 0, ss = 0; float* dev = nullptr;
-    JbfTable() = default;
-    JbfTable(const JbfTable&) = delete;
-    JbfTable& operator=(const JbfTable&) = delete;
-    ~JbfTable() { if (dev) { DeviceScope ds(device); hipFree(dev); } }
+struct JbfKey {
+    double sc, ss; int r, channels;
+    bool operator==(const JbfKey& o) const { return sc == o.sc && ss == o.ss && r == o.r && channels == o.channels; }
 };
+struct adf::JbfTable : DeviceTable<float, JbfKey> {};
 using JbfStore = TableStore<JbfTable>;
 
 static void jbf_build_space(double ss, int r, float* space)       // S: the rolling guidance filter's too
@@ -290,23 +312,12 @@ int adf::jbf_params_check(const char* who, int d, double sigma_color, double sig
 
 int adf::jbf_table_device(double sc, double ss, int r, int channels, std::shared_ptr<JbfTable>& out, const float** colour, const float** space)
 {
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess) return fail(ADF_ENODEV, "no HIP device");
-    out = JbfStore::get().find([&](const JbfTable& q) { return q.device == device && q.sc == sc && q.ss == ss && q.r == r && q.channels == channels; });
-    if (!out) {
-        const size_t nc = jbf_colour_entries(channels), ns = jbf_space_entries(r);
-        std::vector<float> host(nc + ns);
-        jbf_build_host(sc, ss, r, channels, host.data(), host.data() + nc);
-        float* d = nullptr;
-        HIP_TRY(device_malloc(reinterpret_cast<void**>(&d), sizeof(float) * host.size()));
-        hipError_t e = hipMemcpy(d, host.data(), sizeof(float) * host.size(), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { hipFree(d); return fail(ADF_EHIP, "joint bilateral table upload failed: %s", hipGetErrorString(e)); }
-        out = std::make_shared<JbfTable>();
-        out->device = device; out->r = r; out->channels = channels; out->sc = sc; out->ss = ss; out->dev = d;
-        JbfStore::get().add(out);
-    }
+    const size_t nc = jbf_colour_entries(channels);
+    if (int rc = table_device("joint bilateral", JbfKey{sc, ss, r, channels}, [&] { return nc + jbf_space_entries(r); },
+                              [&](float* host) { jbf_build_host(sc, ss, r, channels, host, host + nc); }, out))
+        return rc;
     *colour = out->dev;
-    *space = out->dev + jbf_colour_entries(channels);
+    *space = out->dev + nc;
     return ADF_OK;
 }
 
@@ -326,13 +337,11 @@ extern "C" int adf_jbf_tables_host(int d, double sigma_color, double sigma_space
 // bilateral filter's: one block of floats, the range table then S, per (device, depth, sigma_color, sigma_space, r).
 // The range table of an integer depth is C cut after its first zero entry (T entries, up to 65536: the square is formed
 // in double); ADF_32F's is the constant grid G, and sigma_color reaches the kernel as `scale`.
-struct adf::RgfTable {
-    int device = 0, depth = 0, r = 0, entries = 0; double sc = 0, ss = 0; float* dev = nullptr;
-    RgfTable() = default;
-    RgfTable(const RgfTable&) = delete;
-    RgfTable& operator=(const RgfTable&) = delete;
-    ~RgfTable() { if (dev) { DeviceScope ds(device); hipFree(dev); } }
+struct RgfKey {
+    int depth; double sc, ss; int r;
+    bool operator==(const RgfKey& o) const { return depth == o.depth && sc == o.sc && ss == o.ss && r == o.r; }
 };
+struct adf::RgfTable : DeviceTable<float, RgfKey> {};
 using RgfStore = TableStore<RgfTable>;
 
 // C[L] for L = 0 .. the first entry that is 0.0f (or the depth's last level); `colour` may be null: the count alone.
@@ -371,26 +380,14 @@ int adf::rgf_params_check(const char* who, int depth, int d, double sigma_color,
 int adf::rgf_table_device(int depth, double sc, double ss, int r, std::shared_ptr<RgfTable>& out,
                           const float** colour, const float** space, int* entries)
 {
-    int device = 0;
-    if (hipGetDevice(&device) != hipSuccess) return fail(ADF_ENODEV, "no HIP device");
     if (depth == ADF_32F) sc = 1.0;                               // (G does not depend on it)
-    out = RgfStore::get().find([&](const RgfTable& q) { return q.device == device && q.depth == depth && q.sc == sc && q.ss == ss && q.r == r; });
-    if (!out) {
-        const size_t nc = rgf_colour_entries(depth, sc), ns = jbf_space_entries(r);
-        std::vector<float> host(nc + ns);
-        rgf_build_colour(depth, sc, host.data());
-        jbf_build_space(ss, r, host.data() + nc);
-        float* d = nullptr;
-        HIP_TRY(device_malloc(reinterpret_cast<void**>(&d), sizeof(float) * host.size()));
-        hipError_t e = hipMemcpy(d, host.data(), sizeof(float) * host.size(), hipMemcpyHostToDevice);
-        if (e != hipSuccess) { hipFree(d); return fail(ADF_EHIP, "rolling guidance table upload failed: %s", hipGetErrorString(e)); }
-        out = std::make_shared<RgfTable>();
-        out->device = device; out->depth = depth; out->r = r; out->entries = (int)nc; out->sc = sc; out->ss = ss; out->dev = d;
-        RgfStore::get().add(out);
-    }
+    const size_t ns = jbf_space_entries(r);
+    if (int rc = table_device("rolling guidance", RgfKey{depth, sc, ss, r}, [&] { return rgf_colour_entries(depth, sc) + ns; },
+                              [&](float* host) { jbf_build_space(ss, r, host + rgf_build_colour(depth, sc, host)); }, out))
+        return rc;
+    *entries = (int)(out->count - ns);                            // the range table, then S
     *colour = out->dev;
-    *space = out->dev + out->entries;
-    *entries = out->entries;
+    *space = out->dev + *entries;
     return ADF_OK;
 }
 

@@ -289,23 +289,6 @@ struct DtCall {                        // one call as its C entry point received
 
 constexpr const char* WHO = "dtFilter";
 
-bool known_depth(int depth) { return depth == ADF_8U || depth == ADF_16S || depth == ADF_32F; }
-size_t depth_size(int depth) { return depth == ADF_8U ? 1 : depth == ADF_16S ? 2 : 4; }
-
-// The bytes n images span, [lo, hi): what "overlap" is tested on.
-struct Span { uintptr_t lo, hi; };
-Span span_of(const void* p, int n, ptrdiff_t row_bytes, int rows, ptrdiff_t stride, ptrdiff_t map_stride)
-{
-    const uintptr_t b = reinterpret_cast<uintptr_t>(p);
-    return Span{b, b + (uintptr_t)((ptrdiff_t)(n - 1) * map_stride + (ptrdiff_t)(rows - 1) * stride + row_bytes)};
-}
-bool overlap(Span a, Span b) { return a.lo < b.hi && b.lo < a.hi; }
-
-bool aligned(const void* p, ptrdiff_t stride, ptrdiff_t map_stride, ptrdiff_t es)
-{
-    return !(((uintptr_t)p & (es - 1)) || (stride & (es - 1)) || (map_stride & (es - 1)));
-}
-
 // The parameters as DT.inl:79-83 clamps them.
 struct DtParams { float ss, sr; int N; };
 DtParams clamped(double sigma_spatial, double sigma_color, int num_iters)

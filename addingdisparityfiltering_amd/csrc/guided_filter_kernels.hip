@@ -225,23 +225,6 @@ struct GfCall {                        // one call as its C entry point received
 
 constexpr const char* WHO = "guidedFilter";
 
-bool known_depth(int depth) { return depth == ADF_8U || depth == ADF_16S || depth == ADF_32F; }
-size_t depth_size(int depth) { return depth == ADF_8U ? 1 : depth == ADF_16S ? 2 : 4; }
-
-// The bytes n images span, [lo, hi): what "overlap" is tested on.
-struct Span { uintptr_t lo, hi; };
-Span span_of(const void* p, int n, ptrdiff_t row_bytes, int rows, ptrdiff_t stride, ptrdiff_t map_stride)
-{
-    const uintptr_t b = reinterpret_cast<uintptr_t>(p);
-    return Span{b, b + (uintptr_t)((ptrdiff_t)(n - 1) * map_stride + (ptrdiff_t)(rows - 1) * stride + row_bytes)};
-}
-bool overlap(Span a, Span b) { return a.lo < b.hi && b.lo < a.hi; }
-
-bool aligned(const void* p, ptrdiff_t stride, ptrdiff_t map_stride, ptrdiff_t es)
-{
-    return !(((uintptr_t)p & (es - 1)) || (stride & (es - 1)) || (map_stride & (es - 1)));
-}
-
 int gf_check(const GfCall& c)
 {
     if (!c.guide || !c.src || !c.dst) return fail(ADF_EBADARG, "%s: guide, src and dst must be non-NULL", WHO);
@@ -270,26 +253,14 @@ int gf_check(const GfCall& c)
 }
 
 // The launches of one stage: `kernel` over every tile of every map.
-template <class K>
-int gf_launch(const GfCall& c, GfArgs a, K kernel, size_t lds, hipStream_t st)
+int gf_launch(const GfCall& c, const GfArgs& a, void (*kernel)(GfArgs), size_t lds, hipStream_t st)
 {
-    if (lds > 48 * 1024 - 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const unsigned tiles_y = (unsigned)((c.H + TH - 1) / TH);
-    a.tiles_x = (unsigned)((c.W + TW - 1) / TW);
-    const uint64_t tiles = (uint64_t)a.tiles_x * tiles_y;               // below 2^31 / 256 + W / 32 + H / 8 + 1: 32 bits
-    constexpr uint64_t PER_LAUNCH = 1u << 22;                            // (a grid's threads stay below 2^31)
     const size_t planes_per_map = (size_t)(c.guide_channels + 1) * c.W * c.H;
-    float* const planes = a.planes;
-    return for_batches(c.n, GRID_LIMIT, [&](int m0, unsigned nm) {
-        a.guide = c.guide + (ptrdiff_t)m0 * c.guide_map_stride;
-        a.src = static_cast<const char*>(c.src) + (ptrdiff_t)m0 * c.src_map_stride;
-        a.dst = static_cast<char*>(c.dst) + (ptrdiff_t)m0 * c.dst_map_stride;
-        a.planes = planes + planes_per_map * m0;
-        for (uint64_t t0 = 0; t0 < tiles; t0 += PER_LAUNCH) {
-            a.tile0 = (unsigned)t0;
-            hipLaunchKernelGGL(kernel, dim3((unsigned)std::min(tiles - t0, PER_LAUNCH), nm), dim3(NT), lds, st, a);
-        }
-        return launched();
+    return launch_tiles(kernel, lds, c.W, c.H, TW, TH, c.n, a, st, [&](GfArgs& t, int m0) {
+        t.guide = c.guide + (ptrdiff_t)m0 * c.guide_map_stride;
+        t.src = static_cast<const char*>(c.src) + (ptrdiff_t)m0 * c.src_map_stride;
+        t.dst = static_cast<char*>(c.dst) + (ptrdiff_t)m0 * c.dst_map_stride;
+        t.planes = a.planes + planes_per_map * m0;
     });
 }
 

@@ -200,22 +200,11 @@ struct WmfCall {                       // one call as its C entry point received
 
 constexpr const char* WHO = "weightedMedianFilter";
 
-size_t depth_size(int depth) { return depth == ADF_8U ? 1 : depth == ADF_16S ? 2 : 4; }
-
-// The bytes n images span, [lo, hi): what "overlap" is tested on.
-struct Span { uintptr_t lo, hi; };
-Span span_of(const void* p, int n, ptrdiff_t row_bytes, int rows, ptrdiff_t stride, ptrdiff_t map_stride)
-{
-    const uintptr_t b = reinterpret_cast<uintptr_t>(p);
-    return Span{b, b + (uintptr_t)((ptrdiff_t)(n - 1) * map_stride + (ptrdiff_t)(rows - 1) * stride + row_bytes)};
-}
-bool overlap(Span a, Span b) { return a.lo < b.hi && b.lo < a.hi; }
-
 int wmf_check(const WmfCall& c)
 {
     if (!c.joint || !c.src || !c.dst) return fail(ADF_EBADARG, "%s: joint, src and dst must be non-NULL", WHO);
     if (c.n < 1 || c.W < 1 || c.H < 1) return fail(ADF_EBADARG, "%s: the map is empty", WHO);
-    if (c.depth != ADF_8U && c.depth != ADF_16S && c.depth != ADF_32F)
+    if (!known_depth(c.depth))
         return fail(ADF_EBADARG, "%s: src must be CV_8U (ADF_8U), CV_16S (ADF_16S) or CV_32F (ADF_32F), one channel", WHO);
     if (c.joint_channels != 1 && c.joint_channels != 3) return fail(ADF_EBADARG, "%s: joint must have 1 or 3 channels", WHO);
     if (int rc = wmf_weights_check(WHO, c.sigma, c.weight_type)) return rc;
@@ -226,8 +215,7 @@ int wmf_check(const WmfCall& c)
             return fail(ADF_EBADARG, "%s: ignore_value must be an integer inside the range of src's depth", WHO);
     }
     const ptrdiff_t es = (ptrdiff_t)depth_size(c.depth);
-    if (((uintptr_t)c.src & (es - 1)) || (c.src_stride & (es - 1)) || (c.src_map_stride & (es - 1)) ||
-        ((uintptr_t)c.dst & (es - 1)) || (c.dst_stride & (es - 1)) || (c.dst_map_stride & (es - 1)))
+    if (!aligned(c.src, c.src_stride, c.src_map_stride, es) || !aligned(c.dst, c.dst_stride, c.dst_map_stride, es))
         return fail(ADF_EBADARG, "%s: src and dst and their strides must be aligned to the depth", WHO);
     if ((int64_t)c.W * c.H >= ((int64_t)1 << 31)) return fail(ADF_ESIZE, "%s: W*H must be below 2^31", WHO);
     const ptrdiff_t row = (ptrdiff_t)c.W * es, jrow = (ptrdiff_t)c.W * c.joint_channels;
@@ -246,24 +234,13 @@ int wmf_check(const WmfCall& c)
 }
 
 template <class T, int CH>
-int wmf_launch(const WmfCall& c, WmfArgs a, hipStream_t st)
+int wmf_launch(const WmfCall& c, const WmfArgs& a, hipStream_t st)
 {
-    const size_t lds = tile_entries(c.r) * sizeof(uint2);
-    if (lds > 48 * 1024 - 1024) HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void*>(wmf_kernel<T, CH>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    const unsigned tiles_y = (unsigned)((c.H + TH - 1) / TH);
-    a.tiles_x = (unsigned)((c.W + TW - 1) / TW);
-    const uint64_t tiles = (uint64_t)a.tiles_x * tiles_y;               // below 2^31 / 256 + W / 32 + H / 8 + 1: 32 bits
-    constexpr uint64_t PER_LAUNCH = 1u << 22;                            // (a grid's threads stay below 2^31)
-    return for_batches(c.n, GRID_LIMIT, [&](int m0, unsigned nm) {
-        a.joint = c.joint + (ptrdiff_t)m0 * c.joint_map_stride;
-        a.src = static_cast<const char*>(c.src) + (ptrdiff_t)m0 * c.src_map_stride;
-        a.dst = static_cast<char*>(c.dst) + (ptrdiff_t)m0 * c.dst_map_stride;
-        a.mask = c.mask ? c.mask + (ptrdiff_t)m0 * c.mask_map_stride : nullptr;
-        for (uint64_t t0 = 0; t0 < tiles; t0 += PER_LAUNCH) {
-            a.tile0 = (unsigned)t0;
-            hipLaunchKernelGGL((wmf_kernel<T, CH>), dim3((unsigned)std::min(tiles - t0, PER_LAUNCH), nm), dim3(NT), lds, st, a);
-        }
-        return launched();
+    return launch_tiles(wmf_kernel<T, CH>, tile_entries(c.r) * sizeof(uint2), c.W, c.H, TW, TH, c.n, a, st, [&](WmfArgs& t, int m0) {
+        t.joint = c.joint + (ptrdiff_t)m0 * c.joint_map_stride;
+        t.src = static_cast<const char*>(c.src) + (ptrdiff_t)m0 * c.src_map_stride;
+        t.dst = static_cast<char*>(c.dst) + (ptrdiff_t)m0 * c.dst_map_stride;
+        t.mask = c.mask ? c.mask + (ptrdiff_t)m0 * c.mask_map_stride : nullptr;
     });
 }
 
