@@ -2,9 +2,11 @@
 // memory (growable buffers, the process-wide block cache, scratch taken from it), the weight tables, the image copies
 // of the host-pointer entry points, and what the stateless operators' launches share: the launch check, rounding up,
 // THE batch loop over the grid limit, THE launch of a tile kernel over every tile of every image, the rule for
-// destination images that must not overlap, the choice between a caller's workspace and library scratch, and the
-// checks the edge-aware filters' entry points make alike: the depths, alignment, the bytes a batch spans, the borders
-// that are built.  Host code only; what kernels and host code share is adf_internal.h.
+// destination images that must not overlap, the choice between a caller's workspace and library scratch, and what the
+// five edge-aware filters' entry points share: the depths, alignment, the bytes a batch spans, the borders that are
+// built, THE record of a call's images (FilterImages), THE tail of their checks from alignment to overlap
+// (filter_geometry_check) and THE host-pointer call on staged images (staged_call).  Host code only; what kernels and
+// host code share is adf_internal.h.
 #pragma once
 
 #include "adf_internal.h"
@@ -100,6 +102,26 @@ inline bool overlap(Span a, Span b) { return a.lo < b.hi && b.lo < a.hi; }
 // and BORDER_WRAP are refused by name, any other value by number.
 ADF_LOCAL int border_check(const char* who, int border);
 
+// THE images of one edge-aware filter call (weighted median, guided, domain transform, joint bilateral, rolling
+// guidance): n maps of W x H each.  A filter's call record holds one next to its own parameters.
+struct FilterImage {
+    void* p; ptrdiff_t stride, map_stride;     // bytes between rows and between maps; p null: the call has no such image
+    uint8_t* map(int m0) const { return static_cast<uint8_t*>(p) + (ptrdiff_t)m0 * map_stride; }   // map m0: what a launch is pointed at
+};
+struct FilterImages {
+    int n, W, H;
+    FilterImage guide; int guide_channels;     // 8-bit guide or joint (read only); none: rolling guidance
+    FilterImage src; int src_depth;            // (read only)
+    FilterImage dst; int dst_depth;
+    FilterImage mask;                          // 8-bit (read only); none: every filter but the weighted median, and there optional
+};
+inline FilterImage image_of(const void* p, ptrdiff_t stride, ptrdiff_t map_stride) { return FilterImage{const_cast<void*>(p), stride, map_stride}; }
+// The tail of the five filters' checks, after each one's own head (NULL, empty, depths, parameters), in this order:
+// alignment to the depths, W*H below 2^31, row strides, negative map strides, destination maps that overlap one
+// another, a destination that overlaps an input.  `depths` ("their depths", "the depth") and `inputs` (the names after
+// "dst must not overlap") are the two phrases in which the filters' texts differ.
+ADF_LOCAL int filter_geometry_check(const char* who, const FilterImages& im, const char* depths, const char* inputs);
+
 // Growable device buffer (never shrinks; freed with the handle).  Growing drains `st` before the old block is freed.
 // FILL_ZERO clears a newly allocated block on `st` (the filters: the sweeps read, and discard, pitch padding);
 // FILL_NONE leaves it as the driver gave it (the matchers' workspaces: gigabytes that are written before they are read).
@@ -192,5 +214,40 @@ ADF_LOCAL int rgf_table_device(int depth, double sc, double ss, int r, std::shar
 // been synchronised).  The layout of a staging block stays with the caller.
 int copy_images(void* dst, size_t dst_pitch, ptrdiff_t dst_image_stride, const void* src, size_t src_pitch,
                 ptrdiff_t src_image_stride, size_t row_bytes, size_t rows, int n, hipMemcpyKind kind, hipStream_t st);
+
+// THE host-pointer entry of an edge-aware filter, after its check: one scratch block holds the guides, dense, then the
+// sources, the masks, the results and `ws_bytes` of workspace, each part padded to 256 bytes (an image the call does not
+// have takes none); the inputs are copied in, run(the same images on the device, the workspace, the null stream) queues
+// the filter, and the results are copied out and waited for.
+template <class RUN> int staged_call(const FilterImages& host, size_t ws_bytes, RUN&& run)
+{
+    FilterImages dev = host;
+    const FilterImage* from[4] = {&host.guide, &host.src, &host.mask, &host.dst};
+    FilterImage* to[4] = {&dev.guide, &dev.src, &dev.mask, &dev.dst};
+    const size_t pixel[4] = {(size_t)host.guide_channels, depth_size(host.src_depth), 1, depth_size(host.dst_depth)};
+    size_t row[4], at[5] = {0};
+    for (int k = 0; k < 4; k++) {
+        row[k] = from[k]->p ? pixel[k] * (size_t)host.W : 0;
+        at[k + 1] = at[k] + pad_to(row[k] * (size_t)host.H * (size_t)host.n, 256);
+    }
+    Scratch blk;
+    if (int rc = blk.take(at[4] + ws_bytes, nullptr)) return rc;
+    char* base = static_cast<char*>(blk.p);
+    for (int k = 0; k < 4; k++) {
+        if (!row[k]) continue;
+        *to[k] = FilterImage{base + at[k], (ptrdiff_t)row[k], (ptrdiff_t)(row[k] * (size_t)host.H)};
+        if (k == 3) break;                                               // the results: nothing to copy in
+        if (int rc = copy_images(to[k]->p, row[k], to[k]->map_stride, from[k]->p, (size_t)from[k]->stride, from[k]->map_stride, row[k],
+                                 (size_t)host.H, host.n, hipMemcpyHostToDevice, nullptr))
+            return rc;
+    }
+    if (int rc = run(dev, static_cast<void*>(base + at[4]), (hipStream_t)nullptr)) return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    if (int rc = copy_images(host.dst.p, (size_t)host.dst.stride, host.dst.map_stride, dev.dst.p, row[3], dev.dst.map_stride, row[3],
+                             (size_t)host.H, host.n, hipMemcpyDeviceToHost, nullptr))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(nullptr));
+    return ADF_OK;
+}
 
 } // namespace adf

@@ -68,6 +68,28 @@ int adf::border_check(const char* who, int border)
     return ADF_OK;
 }
 
+int adf::filter_geometry_check(const char* who, const FilterImages& im, const char* depths, const char* inputs)
+{
+    const FilterImage &g = im.guide, &s = im.src, &d = im.dst, &m = im.mask;
+    const ptrdiff_t ss = (ptrdiff_t)depth_size(im.src_depth), ds = (ptrdiff_t)depth_size(im.dst_depth);
+    if (!aligned(s.p, s.stride, s.map_stride, ss) || !aligned(d.p, d.stride, d.map_stride, ds))
+        return fail(ADF_EBADARG, "%s: src and dst and their strides must be aligned to %s", who, depths);
+    if ((int64_t)im.W * im.H >= ((int64_t)1 << 31)) return fail(ADF_ESIZE, "%s: W*H must be below 2^31", who);
+    const ptrdiff_t srow = (ptrdiff_t)im.W * ss, drow = (ptrdiff_t)im.W * ds, grow = (ptrdiff_t)im.W * im.guide_channels, mrow = im.W;
+    if (s.stride < srow || d.stride < drow || (g.p && g.stride < grow) || (m.p && m.stride < mrow))
+        return fail(ADF_ESIZE, "%s: row stride smaller than a row", who);
+    if (im.n > 1 && (s.map_stride < 0 || (g.p && g.map_stride < 0) || (m.p && m.map_stride < 0)))
+        return fail(ADF_ESIZE, "%s: map strides must not be negative", who);
+    if (!images_disjoint(im.n, drow, im.H, d.stride, d.map_stride, false))
+        return fail(ADF_ESIZE, "%s: destination maps of the batch overlap (map stride smaller than a map)", who);
+    const Span out = span_of(d.p, im.n, drow, im.H, d.stride, d.map_stride);
+    if (overlap(out, span_of(s.p, im.n, srow, im.H, s.stride, s.map_stride)) ||
+        (g.p && overlap(out, span_of(g.p, im.n, grow, im.H, g.stride, g.map_stride))) ||
+        (m.p && overlap(out, span_of(m.p, im.n, mrow, im.H, m.stride, m.map_stride))))
+        return fail(ADF_EBADARG, "%s: dst must not overlap %s", who, inputs);
+    return ADF_OK;
+}
+
 int adf::DevBuf::reserve(size_t need, hipStream_t st, Fill fill)
 {
     if (need <= bytes) return ADF_OK;

@@ -280,11 +280,8 @@ __global__ void __launch_bounds__(64) dt_col_kernel(DtArgs a, DtRow<CH> row)
 }
 
 struct DtCall {                        // one call as its C entry point received it
-    int n;
-    const uint8_t* guide; ptrdiff_t guide_stride, guide_map_stride; int guide_channels;
-    const void* src; ptrdiff_t src_stride, src_map_stride; int src_depth;
-    void* dst; ptrdiff_t dst_stride, dst_map_stride; int dst_depth;
-    int W, H; double sigma_spatial, sigma_color; int mode, num_iters;
+    FilterImages im;
+    double sigma_spatial, sigma_color; int mode, num_iters;
 };
 
 constexpr const char* WHO = "dtFilter";
@@ -340,27 +337,13 @@ int dt_check(const DtCall& c)
     if (c.mode == ADF_DTF_NC || c.mode == ADF_DTF_IC)
         return fail(ADF_EBADARG, "%s: DTF_NC and DTF_IC are not built; use ADF_DTF_RF", WHO);
     if (c.mode != ADF_DTF_RF) return fail(ADF_EBADARG, "%s: unknown mode %d", WHO, c.mode);
-    if (!c.guide || !c.src || !c.dst) return fail(ADF_EBADARG, "%s: guide, src and dst must be non-NULL", WHO);
-    if (c.n < 1 || c.W < 1 || c.H < 1) return fail(ADF_EBADARG, "%s: the map is empty", WHO);
-    if (!known_depth(c.src_depth) || !known_depth(c.dst_depth))
+    const FilterImages& im = c.im;
+    if (!im.guide.p || !im.src.p || !im.dst.p) return fail(ADF_EBADARG, "%s: guide, src and dst must be non-NULL", WHO);
+    if (im.n < 1 || im.W < 1 || im.H < 1) return fail(ADF_EBADARG, "%s: the map is empty", WHO);
+    if (!known_depth(im.src_depth) || !known_depth(im.dst_depth))
         return fail(ADF_EBADARG, "%s: src and dst must be CV_8U (ADF_8U), CV_16S (ADF_16S) or CV_32F (ADF_32F), one channel", WHO);
-    if (int rc = params_check(WHO, c.sigma_spatial, c.sigma_color, c.num_iters, c.guide_channels)) return rc;
-    const ptrdiff_t ss = (ptrdiff_t)depth_size(c.src_depth), ds = (ptrdiff_t)depth_size(c.dst_depth);
-    if (!aligned(c.src, c.src_stride, c.src_map_stride, ss) || !aligned(c.dst, c.dst_stride, c.dst_map_stride, ds))
-        return fail(ADF_EBADARG, "%s: src and dst and their strides must be aligned to their depths", WHO);
-    if ((int64_t)c.W * c.H >= ((int64_t)1 << 31)) return fail(ADF_ESIZE, "%s: W*H must be below 2^31", WHO);
-    const ptrdiff_t srow = (ptrdiff_t)c.W * ss, drow = (ptrdiff_t)c.W * ds, grow = (ptrdiff_t)c.W * c.guide_channels;
-    if (c.src_stride < srow || c.dst_stride < drow || c.guide_stride < grow)
-        return fail(ADF_ESIZE, "%s: row stride smaller than a row", WHO);
-    if (c.n > 1 && (c.src_map_stride < 0 || c.guide_map_stride < 0))
-        return fail(ADF_ESIZE, "%s: map strides must not be negative", WHO);
-    if (!images_disjoint(c.n, drow, c.H, c.dst_stride, c.dst_map_stride, false))
-        return fail(ADF_ESIZE, "%s: destination maps of the batch overlap (map stride smaller than a map)", WHO);
-    const Span d = span_of(c.dst, c.n, drow, c.H, c.dst_stride, c.dst_map_stride);
-    if (overlap(d, span_of(c.src, c.n, srow, c.H, c.src_stride, c.src_map_stride)) ||
-        overlap(d, span_of(c.guide, c.n, grow, c.H, c.guide_stride, c.guide_map_stride)))
-        return fail(ADF_EBADARG, "%s: dst must not overlap src or guide", WHO);
-    return ADF_OK;
+    if (int rc = params_check(WHO, c.sigma_spatial, c.sigma_color, c.num_iters, im.guide_channels)) return rc;
+    return filter_geometry_check(WHO, im, "their depths", "src or guide");
 }
 
 // One pass of every map: `kernel` over grid_x groups of 64 scanlines, with the iteration's table row.
@@ -370,11 +353,11 @@ int dt_launch(const DtCall& c, DtArgs a, K kernel, unsigned grid_x, unsigned thr
     DtRow<CH> row;
     std::copy(table_row, table_row + levels_of(CH), row.a);
     const DtArgs a0 = a;
-    return for_batches(c.n, GRID_LIMIT, [&](int m0, unsigned nm) {
+    return for_batches(c.im.n, GRID_LIMIT, [&](int m0, unsigned nm) {
         a.guide = a0.guide + (ptrdiff_t)m0 * a0.guide_map_stride;
         a.src = static_cast<const char*>(a0.src) + (ptrdiff_t)m0 * a0.src_map_stride;
         a.dst = static_cast<char*>(a0.dst) + (ptrdiff_t)m0 * a0.dst_map_stride;
-        a.plane = a0.plane + (size_t)m0 * c.W * c.H;
+        a.plane = a0.plane + (size_t)m0 * c.im.W * c.im.H;
         hipLaunchKernelGGL(kernel, dim3(grid_x, nm), dim3(threads), 0, st, a, row);
         return launched();
     });
@@ -385,25 +368,25 @@ int dt_passes(const DtCall& c, const DtArgs& user, hipStream_t st)
 {
     const DtParams p = clamped(c.sigma_spatial, c.sigma_color, c.num_iters);
     const float* table = table_of(p, CH);
-    const unsigned rows_x = (unsigned)((c.H + 63) / 64), cols_x = (unsigned)((c.W + 63) / 64);
-    const ptrdiff_t prow = (ptrdiff_t)c.W * 4, pmap = prow * c.H;
+    const unsigned rows_x = (unsigned)((c.im.H + 63) / 64), cols_x = (unsigned)((c.im.W + 63) / 64);
+    const ptrdiff_t prow = (ptrdiff_t)c.im.W * 4, pmap = prow * c.im.H;
     for (int i = 0; i < p.N; i++) {
         const float* row = table + (size_t)i * levels_of(CH);
         DtArgs a = user;
         int rc;
         if (i == 0) {                                                    // the first row pass reads src in its depth
-            rc = c.src_depth == ADF_8U    ? dt_launch<CH>(c, a, dt_row_kernel<uint8_t, CH>, rows_x, RT, row, st)
-                 : c.src_depth == ADF_16S ? dt_launch<CH>(c, a, dt_row_kernel<int16_t, CH>, rows_x, RT, row, st)
-                                          : dt_launch<CH>(c, a, dt_row_kernel<float, CH>, rows_x, RT, row, st);
+            rc = c.im.src_depth == ADF_8U    ? dt_launch<CH>(c, a, dt_row_kernel<uint8_t, CH>, rows_x, RT, row, st)
+                 : c.im.src_depth == ADF_16S ? dt_launch<CH>(c, a, dt_row_kernel<int16_t, CH>, rows_x, RT, row, st)
+                                             : dt_launch<CH>(c, a, dt_row_kernel<float, CH>, rows_x, RT, row, st);
         } else {
             a.src = a.plane; a.src_stride = prow; a.src_map_stride = pmap;
             rc = dt_launch<CH>(c, a, dt_row_kernel<float, CH>, rows_x, RT, row, st);
         }
         if (rc) return rc;
         if (i == p.N - 1) {                                              // the last column pass writes dst in its depth
-            rc = c.dst_depth == ADF_8U    ? dt_launch<CH>(c, a, dt_col_kernel<uint8_t, CH>, cols_x, 64, row, st)
-                 : c.dst_depth == ADF_16S ? dt_launch<CH>(c, a, dt_col_kernel<int16_t, CH>, cols_x, 64, row, st)
-                                          : dt_launch<CH>(c, a, dt_col_kernel<float, CH>, cols_x, 64, row, st);
+            rc = c.im.dst_depth == ADF_8U    ? dt_launch<CH>(c, a, dt_col_kernel<uint8_t, CH>, cols_x, 64, row, st)
+                 : c.im.dst_depth == ADF_16S ? dt_launch<CH>(c, a, dt_col_kernel<int16_t, CH>, cols_x, 64, row, st)
+                                             : dt_launch<CH>(c, a, dt_col_kernel<float, CH>, cols_x, 64, row, st);
         } else {
             a.dst = a.plane; a.dst_stride = prow; a.dst_map_stride = pmap;
             rc = dt_launch<CH>(c, a, dt_col_kernel<float, CH>, cols_x, 64, row, st);
@@ -416,13 +399,23 @@ int dt_passes(const DtCall& c, const DtArgs& user, hipStream_t st)
 // ws: adf_dt_filter_workspace_bytes of device memory, one float plane per map
 int dt_run(const DtCall& c, void* ws, hipStream_t st)
 {
+    const FilterImages& im = c.im;
     DtArgs a{};
-    a.guide = c.guide; a.guide_stride = c.guide_stride; a.guide_map_stride = c.guide_map_stride;
-    a.src = c.src; a.src_stride = c.src_stride; a.src_map_stride = c.src_map_stride;
-    a.dst = c.dst; a.dst_stride = c.dst_stride; a.dst_map_stride = c.dst_map_stride;
+    a.guide = static_cast<const uint8_t*>(im.guide.p); a.guide_stride = im.guide.stride; a.guide_map_stride = im.guide.map_stride;
+    a.src = im.src.p; a.src_stride = im.src.stride; a.src_map_stride = im.src.map_stride;
+    a.dst = im.dst.p; a.dst_stride = im.dst.stride; a.dst_map_stride = im.dst.map_stride;
     a.plane = static_cast<float*>(ws);
-    a.W = c.W; a.H = c.H;
-    return c.guide_channels == 3 ? dt_passes<3>(c, a, st) : dt_passes<1>(c, a, st);
+    a.W = im.W; a.H = im.H;
+    return im.guide_channels == 3 ? dt_passes<3>(c, a, st) : dt_passes<1>(c, a, st);
+}
+
+DtCall call_of(int n_maps, const uint8_t* guide, ptrdiff_t guide_stride, ptrdiff_t guide_map_stride, int guide_channels,
+               const void* src, ptrdiff_t src_stride, ptrdiff_t src_map_stride, int src_depth,
+               void* dst, ptrdiff_t dst_stride, ptrdiff_t dst_map_stride, int dst_depth,
+               int W, int H, double sigma_spatial, double sigma_color, int mode, int num_iters)
+{
+    return DtCall{{n_maps, W, H, image_of(guide, guide_stride, guide_map_stride), guide_channels, image_of(src, src_stride, src_map_stride), src_depth,
+                   image_of(dst, dst_stride, dst_map_stride), dst_depth, {}}, sigma_spatial, sigma_color, mode, num_iters};
 }
 
 } // namespace
@@ -448,8 +441,8 @@ extern "C" int adf_dt_filter_device(int n_maps,
                                     int W, int H, double sigma_spatial, double sigma_color, int mode, int num_iters,
                                     void* workspace, size_t workspace_bytes, void* stream)
 {
-    const DtCall c{n_maps, guide, guide_stride, guide_map_stride, guide_channels, src, src_stride, src_map_stride, src_depth,
-                   dst, dst_stride, dst_map_stride, dst_depth, W, H, sigma_spatial, sigma_color, mode, num_iters};
+    const DtCall c = call_of(n_maps, guide, guide_stride, guide_map_stride, guide_channels, src, src_stride, src_map_stride, src_depth,
+                             dst, dst_stride, dst_map_stride, dst_depth, W, H, sigma_spatial, sigma_color, mode, num_iters);
     int rc = dt_check(c);
     if (rc) return rc;
     Scratch blk;
@@ -465,26 +458,12 @@ extern "C" int adf_dt_filter_host(int n_maps,
                                   void* dst, ptrdiff_t dst_stride, ptrdiff_t dst_map_stride, int dst_depth,
                                   int W, int H, double sigma_spatial, double sigma_color, int mode, int num_iters)
 {
-    const DtCall c{n_maps, guide, guide_stride, guide_map_stride, guide_channels, src, src_stride, src_map_stride, src_depth,
-                   dst, dst_stride, dst_map_stride, dst_depth, W, H, sigma_spatial, sigma_color, mode, num_iters};
+    const DtCall c = call_of(n_maps, guide, guide_stride, guide_map_stride, guide_channels, src, src_stride, src_map_stride, src_depth,
+                             dst, dst_stride, dst_map_stride, dst_depth, W, H, sigma_spatial, sigma_color, mode, num_iters);
     int rc = dt_check(c);
     if (rc) return rc;
-    // one block: the guides, dense, then the sources, the results and the float planes
-    const size_t grow = (size_t)W * guide_channels, gmap = (size_t)H * grow, guides = pad_to(gmap * n_maps, 256);
-    const size_t srow = (size_t)W * depth_size(src_depth), smap = (size_t)H * srow, srcs = pad_to(smap * n_maps, 256);
-    const size_t drow = (size_t)W * depth_size(dst_depth), dmap = (size_t)H * drow, dsts = pad_to(dmap * n_maps, 256);
-    Scratch blk;
-    if ((rc = blk.take(guides + srcs + dsts + adf_dt_filter_workspace_bytes(n_maps, W, H), nullptr))) return rc;
-    char* base = static_cast<char*>(blk.p);
-    DtCall d = c;                                                        // the same call on the staged images
-    d.guide = reinterpret_cast<uint8_t*>(base); d.guide_stride = (ptrdiff_t)grow; d.guide_map_stride = (ptrdiff_t)gmap;
-    d.src = base + guides; d.src_stride = (ptrdiff_t)srow; d.src_map_stride = (ptrdiff_t)smap;
-    d.dst = base + guides + srcs; d.dst_stride = (ptrdiff_t)drow; d.dst_map_stride = (ptrdiff_t)dmap;
-    if ((rc = copy_images(base, grow, gmap, guide, guide_stride, guide_map_stride, grow, H, n_maps, hipMemcpyHostToDevice, nullptr))) return rc;
-    if ((rc = copy_images(base + guides, srow, smap, src, src_stride, src_map_stride, srow, H, n_maps, hipMemcpyHostToDevice, nullptr))) return rc;
-    if ((rc = dt_run(d, base + guides + srcs + dsts, nullptr))) return rc;
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    if ((rc = copy_images(dst, dst_stride, dst_map_stride, base + guides + srcs, drow, dmap, drow, H, n_maps, hipMemcpyDeviceToHost, nullptr))) return rc;
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return ADF_OK;
+    // the workspace: the float planes
+    return staged_call(c.im, adf_dt_filter_workspace_bytes(n_maps, W, H), [&](const FilterImages& staged, void* ws, hipStream_t st) {
+        return dt_run(DtCall{staged, c.sigma_spatial, c.sigma_color, c.mode, c.num_iters}, ws, st);   // the same call on the staged images
+    });
 }

@@ -216,50 +216,32 @@ __global__ void __launch_bounds__(NT) gf_apply_kernel(GfArgs a)
 }
 
 struct GfCall {                        // one call as its C entry point received it
-    int n;
-    const uint8_t* guide; ptrdiff_t guide_stride, guide_map_stride; int guide_channels;
-    const void* src; ptrdiff_t src_stride, src_map_stride; int src_depth;
-    void* dst; ptrdiff_t dst_stride, dst_map_stride; int dst_depth;
-    int W, H, r; double eps;
+    FilterImages im;
+    int r; double eps;
 };
 
 constexpr const char* WHO = "guidedFilter";
 
 int gf_check(const GfCall& c)
 {
-    if (!c.guide || !c.src || !c.dst) return fail(ADF_EBADARG, "%s: guide, src and dst must be non-NULL", WHO);
-    if (c.n < 1 || c.W < 1 || c.H < 1) return fail(ADF_EBADARG, "%s: the map is empty", WHO);
-    if (!known_depth(c.src_depth) || !known_depth(c.dst_depth))
+    const FilterImages& im = c.im;
+    if (!im.guide.p || !im.src.p || !im.dst.p) return fail(ADF_EBADARG, "%s: guide, src and dst must be non-NULL", WHO);
+    if (im.n < 1 || im.W < 1 || im.H < 1) return fail(ADF_EBADARG, "%s: the map is empty", WHO);
+    if (!known_depth(im.src_depth) || !known_depth(im.dst_depth))
         return fail(ADF_EBADARG, "%s: src and dst must be CV_8U (ADF_8U), CV_16S (ADF_16S) or CV_32F (ADF_32F), one channel", WHO);
-    if (c.guide_channels != 1 && c.guide_channels != 3) return fail(ADF_EBADARG, "%s: guide must have 1 or 3 channels", WHO);
+    if (im.guide_channels != 1 && im.guide_channels != 3) return fail(ADF_EBADARG, "%s: guide must have 1 or 3 channels", WHO);
     if (c.r < 0 || c.r > ADF_GF_MAX_RADIUS) return fail(ADF_EBADARG, "%s: r must lie in [0, %d]", WHO, ADF_GF_MAX_RADIUS);
     if (!std::isfinite(c.eps) || !(c.eps > 0.0)) return fail(ADF_EBADARG, "%s: eps must be finite and > 0", WHO);
-    const ptrdiff_t ss = (ptrdiff_t)depth_size(c.src_depth), ds = (ptrdiff_t)depth_size(c.dst_depth);
-    if (!aligned(c.src, c.src_stride, c.src_map_stride, ss) || !aligned(c.dst, c.dst_stride, c.dst_map_stride, ds))
-        return fail(ADF_EBADARG, "%s: src and dst and their strides must be aligned to their depths", WHO);
-    if ((int64_t)c.W * c.H >= ((int64_t)1 << 31)) return fail(ADF_ESIZE, "%s: W*H must be below 2^31", WHO);
-    const ptrdiff_t srow = (ptrdiff_t)c.W * ss, drow = (ptrdiff_t)c.W * ds, grow = (ptrdiff_t)c.W * c.guide_channels;
-    if (c.src_stride < srow || c.dst_stride < drow || c.guide_stride < grow)
-        return fail(ADF_ESIZE, "%s: row stride smaller than a row", WHO);
-    if (c.n > 1 && (c.src_map_stride < 0 || c.guide_map_stride < 0))
-        return fail(ADF_ESIZE, "%s: map strides must not be negative", WHO);
-    if (!images_disjoint(c.n, drow, c.H, c.dst_stride, c.dst_map_stride, false))
-        return fail(ADF_ESIZE, "%s: destination maps of the batch overlap (map stride smaller than a map)", WHO);
-    const Span d = span_of(c.dst, c.n, drow, c.H, c.dst_stride, c.dst_map_stride);
-    if (overlap(d, span_of(c.src, c.n, srow, c.H, c.src_stride, c.src_map_stride)) ||
-        overlap(d, span_of(c.guide, c.n, grow, c.H, c.guide_stride, c.guide_map_stride)))
-        return fail(ADF_EBADARG, "%s: dst must not overlap src or guide", WHO);
-    return ADF_OK;
+    return filter_geometry_check(WHO, im, "their depths", "src or guide");
 }
 
 // The launches of one stage: `kernel` over every tile of every map.
 int gf_launch(const GfCall& c, const GfArgs& a, void (*kernel)(GfArgs), size_t lds, hipStream_t st)
 {
-    const size_t planes_per_map = (size_t)(c.guide_channels + 1) * c.W * c.H;
-    return launch_tiles(kernel, lds, c.W, c.H, TW, TH, c.n, a, st, [&](GfArgs& t, int m0) {
-        t.guide = c.guide + (ptrdiff_t)m0 * c.guide_map_stride;
-        t.src = static_cast<const char*>(c.src) + (ptrdiff_t)m0 * c.src_map_stride;
-        t.dst = static_cast<char*>(c.dst) + (ptrdiff_t)m0 * c.dst_map_stride;
+    const FilterImages& im = c.im;
+    const size_t planes_per_map = (size_t)(im.guide_channels + 1) * im.W * im.H;
+    return launch_tiles(kernel, lds, im.W, im.H, TW, TH, im.n, a, st, [&](GfArgs& t, int m0) {
+        t.guide = im.guide.map(m0); t.src = im.src.map(m0); t.dst = im.dst.map(m0);
         t.planes = a.planes + planes_per_map * m0;
     });
 }
@@ -268,25 +250,34 @@ template <int CH>
 int gf_stages(const GfCall& c, const GfArgs& a, hipStream_t st)
 {
     const size_t l1 = coef_lds(c.r, CH), l2 = apply_lds(c.r);
-    int rc = c.src_depth == ADF_8U    ? gf_launch(c, a, gf_coef_kernel<uint8_t, CH>, l1, st)
-             : c.src_depth == ADF_16S ? gf_launch(c, a, gf_coef_kernel<int16_t, CH>, l1, st)
-                                      : gf_launch(c, a, gf_coef_kernel<float, CH>, l1, st);
+    int rc = c.im.src_depth == ADF_8U    ? gf_launch(c, a, gf_coef_kernel<uint8_t, CH>, l1, st)
+             : c.im.src_depth == ADF_16S ? gf_launch(c, a, gf_coef_kernel<int16_t, CH>, l1, st)
+                                         : gf_launch(c, a, gf_coef_kernel<float, CH>, l1, st);
     if (rc) return rc;
-    return c.dst_depth == ADF_8U    ? gf_launch(c, a, gf_apply_kernel<uint8_t, CH>, l2, st)
-           : c.dst_depth == ADF_16S ? gf_launch(c, a, gf_apply_kernel<int16_t, CH>, l2, st)
-                                    : gf_launch(c, a, gf_apply_kernel<float, CH>, l2, st);
+    return c.im.dst_depth == ADF_8U    ? gf_launch(c, a, gf_apply_kernel<uint8_t, CH>, l2, st)
+           : c.im.dst_depth == ADF_16S ? gf_launch(c, a, gf_apply_kernel<int16_t, CH>, l2, st)
+                                       : gf_launch(c, a, gf_apply_kernel<float, CH>, l2, st);
 }
 
 // ws: adf_guided_filter_workspace_bytes of device memory, the coefficient planes of every map
 int gf_run(const GfCall& c, void* ws, hipStream_t st)
 {
+    const FilterImages& im = c.im;
     GfArgs a{};
-    a.guide_stride = c.guide_stride; a.guide_map_stride = c.guide_map_stride;
-    a.src_stride = c.src_stride; a.src_map_stride = c.src_map_stride;
-    a.dst_stride = c.dst_stride; a.dst_map_stride = c.dst_map_stride;
+    a.guide_stride = im.guide.stride; a.guide_map_stride = im.guide.map_stride;
+    a.src_stride = im.src.stride; a.src_map_stride = im.src.map_stride;
+    a.dst_stride = im.dst.stride; a.dst_map_stride = im.dst.map_stride;
     a.planes = static_cast<float*>(ws);
-    a.W = c.W; a.H = c.H; a.r = c.r; a.eps = c.eps;
-    return c.guide_channels == 3 ? gf_stages<3>(c, a, st) : gf_stages<1>(c, a, st);
+    a.W = im.W; a.H = im.H; a.r = c.r; a.eps = c.eps;
+    return im.guide_channels == 3 ? gf_stages<3>(c, a, st) : gf_stages<1>(c, a, st);
+}
+
+GfCall call_of(int n_maps, const uint8_t* guide, ptrdiff_t guide_stride, ptrdiff_t guide_map_stride, int guide_channels,
+               const void* src, ptrdiff_t src_stride, ptrdiff_t src_map_stride, int src_depth,
+               void* dst, ptrdiff_t dst_stride, ptrdiff_t dst_map_stride, int dst_depth, int W, int H, int r, double eps)
+{
+    return GfCall{{n_maps, W, H, image_of(guide, guide_stride, guide_map_stride), guide_channels, image_of(src, src_stride, src_map_stride), src_depth,
+                   image_of(dst, dst_stride, dst_map_stride), dst_depth, {}}, r, eps};
 }
 
 } // namespace
@@ -304,8 +295,8 @@ extern "C" int adf_guided_filter_device(int n_maps,
                                         int W, int H, int r, double eps,
                                         void* workspace, size_t workspace_bytes, void* stream)
 {
-    const GfCall c{n_maps, guide, guide_stride, guide_map_stride, guide_channels, src, src_stride, src_map_stride, src_depth,
-                   dst, dst_stride, dst_map_stride, dst_depth, W, H, r, eps};
+    const GfCall c = call_of(n_maps, guide, guide_stride, guide_map_stride, guide_channels, src, src_stride, src_map_stride, src_depth,
+                             dst, dst_stride, dst_map_stride, dst_depth, W, H, r, eps);
     int rc = gf_check(c);
     if (rc) return rc;
     Scratch blk;
@@ -321,26 +312,12 @@ extern "C" int adf_guided_filter_host(int n_maps,
                                       void* dst, ptrdiff_t dst_stride, ptrdiff_t dst_map_stride, int dst_depth,
                                       int W, int H, int r, double eps)
 {
-    const GfCall c{n_maps, guide, guide_stride, guide_map_stride, guide_channels, src, src_stride, src_map_stride, src_depth,
-                   dst, dst_stride, dst_map_stride, dst_depth, W, H, r, eps};
+    const GfCall c = call_of(n_maps, guide, guide_stride, guide_map_stride, guide_channels, src, src_stride, src_map_stride, src_depth,
+                             dst, dst_stride, dst_map_stride, dst_depth, W, H, r, eps);
     int rc = gf_check(c);
     if (rc) return rc;
-    // one block: the guides, dense, then the sources, the results and the coefficient planes
-    const size_t grow = (size_t)W * guide_channels, gmap = (size_t)H * grow, guides = pad_to(gmap * n_maps, 256);
-    const size_t srow = (size_t)W * depth_size(src_depth), smap = (size_t)H * srow, srcs = pad_to(smap * n_maps, 256);
-    const size_t drow = (size_t)W * depth_size(dst_depth), dmap = (size_t)H * drow, dsts = pad_to(dmap * n_maps, 256);
-    Scratch blk;
-    if ((rc = blk.take(guides + srcs + dsts + adf_guided_filter_workspace_bytes(n_maps, W, H, guide_channels), nullptr))) return rc;
-    char* base = static_cast<char*>(blk.p);
-    GfCall d = c;                                                        // the same call on the staged images
-    d.guide = reinterpret_cast<uint8_t*>(base); d.guide_stride = (ptrdiff_t)grow; d.guide_map_stride = (ptrdiff_t)gmap;
-    d.src = base + guides; d.src_stride = (ptrdiff_t)srow; d.src_map_stride = (ptrdiff_t)smap;
-    d.dst = base + guides + srcs; d.dst_stride = (ptrdiff_t)drow; d.dst_map_stride = (ptrdiff_t)dmap;
-    if ((rc = copy_images(base, grow, gmap, guide, guide_stride, guide_map_stride, grow, H, n_maps, hipMemcpyHostToDevice, nullptr))) return rc;
-    if ((rc = copy_images(base + guides, srow, smap, src, src_stride, src_map_stride, srow, H, n_maps, hipMemcpyHostToDevice, nullptr))) return rc;
-    if ((rc = gf_run(d, base + guides + srcs + dsts, nullptr))) return rc;
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    if ((rc = copy_images(dst, dst_stride, dst_map_stride, base + guides + srcs, drow, dmap, drow, H, n_maps, hipMemcpyDeviceToHost, nullptr))) return rc;
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return ADF_OK;
+    // the workspace: the coefficient planes
+    return staged_call(c.im, adf_guided_filter_workspace_bytes(n_maps, W, H, guide_channels), [&](const FilterImages& staged, void* ws, hipStream_t st) {
+        return gf_run(GfCall{staged, c.r, c.eps}, ws, st);               // the same call on the staged images
+    });
 }

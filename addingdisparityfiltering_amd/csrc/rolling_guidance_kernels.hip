@@ -102,10 +102,8 @@ template <int KIND> struct Rgf {
 };
 
 struct RgfCall {                       // one call as its C entry point received it
-    int n;
-    const void* src; ptrdiff_t src_stride, src_map_stride;
-    void* dst; ptrdiff_t dst_stride, dst_map_stride;
-    int depth, W, H, d; double sigma_color, sigma_space; int num_iter, border;
+    FilterImages im;                   // no guide; one depth for src and dst
+    int d; double sigma_color, sigma_space; int num_iter, border;
     double sc, ss; int r; float scale; // the clamped sigmas, the radius and the float grid's scale (rgf_check)
 };
 
@@ -113,24 +111,14 @@ constexpr const char* WHO = "rollingGuidanceFilter";
 
 int rgf_check(RgfCall& c)
 {
-    if (!c.src || !c.dst) return fail(ADF_EBADARG, "%s: src and dst must be non-NULL", WHO);
-    if (c.n < 1 || c.W < 1 || c.H < 1) return fail(ADF_EBADARG, "%s: the map is empty", WHO);
-    if (int rc = rgf_params_check(WHO, c.depth, c.d, c.sigma_color, c.sigma_space, &c.sc, &c.ss, &c.r, &c.scale)) return rc;
+    const FilterImages& im = c.im;
+    if (!im.src.p || !im.dst.p) return fail(ADF_EBADARG, "%s: src and dst must be non-NULL", WHO);
+    if (im.n < 1 || im.W < 1 || im.H < 1) return fail(ADF_EBADARG, "%s: the map is empty", WHO);
+    if (int rc = rgf_params_check(WHO, im.src_depth, c.d, c.sigma_color, c.sigma_space, &c.sc, &c.ss, &c.r, &c.scale)) return rc;
     if (c.num_iter < 0 || c.num_iter > ADF_RGF_MAX_ITERS)
         return fail(ADF_EBADARG, "%s: numOfIter must lie in [0, %d] (got %d)", WHO, ADF_RGF_MAX_ITERS, c.num_iter);
     if (int rc = border_check(WHO, c.border)) return rc;
-    const ptrdiff_t es = (ptrdiff_t)depth_size(c.depth);
-    if (!aligned(c.src, c.src_stride, c.src_map_stride, es) || !aligned(c.dst, c.dst_stride, c.dst_map_stride, es))
-        return fail(ADF_EBADARG, "%s: src and dst and their strides must be aligned to the depth", WHO);
-    if ((int64_t)c.W * c.H >= ((int64_t)1 << 31)) return fail(ADF_ESIZE, "%s: W*H must be below 2^31", WHO);
-    const ptrdiff_t row = (ptrdiff_t)c.W * es;
-    if (c.src_stride < row || c.dst_stride < row) return fail(ADF_ESIZE, "%s: row stride smaller than a row", WHO);
-    if (c.n > 1 && c.src_map_stride < 0) return fail(ADF_ESIZE, "%s: map strides must not be negative", WHO);
-    if (!images_disjoint(c.n, row, c.H, c.dst_stride, c.dst_map_stride, false))
-        return fail(ADF_ESIZE, "%s: destination maps of the batch overlap (map stride smaller than a map)", WHO);
-    if (overlap(span_of(c.dst, c.n, row, c.H, c.dst_stride, c.dst_map_stride), span_of(c.src, c.n, row, c.H, c.src_stride, c.src_map_stride)))
-        return fail(ADF_EBADARG, "%s: dst must not overlap src (there is no in-place call)", WHO);
-    return ADF_OK;
+    return filter_geometry_check(WHO, im, "the depth", "src (there is no in-place call)");
 }
 
 // ws: adf_rolling_guidance_workspace_bytes of device memory, one dense plane of the source's depth per map (unused, and
@@ -138,26 +126,28 @@ int rgf_check(RgfCall& c)
 // the last one writes dst.
 int rgf_run(const RgfCall& c, void* ws, hipStream_t st)
 {
-    const ptrdiff_t row = (ptrdiff_t)c.W * (ptrdiff_t)depth_size(c.depth), map = row * c.H;
+    const FilterImages& im = c.im;
+    const int depth = im.src_depth;
+    const ptrdiff_t row = (ptrdiff_t)im.W * (ptrdiff_t)depth_size(depth), map = row * im.H;
     if (c.num_iter == 0)
-        return copy_images(c.dst, (size_t)c.dst_stride, c.dst_map_stride, c.src, (size_t)c.src_stride, c.src_map_stride, (size_t)row, (size_t)c.H, c.n,
-                           hipMemcpyDeviceToDevice, st);
+        return copy_images(im.dst.p, (size_t)im.dst.stride, im.dst.map_stride, im.src.p, (size_t)im.src.stride, im.src.map_stride, (size_t)row,
+                           (size_t)im.H, im.n, hipMemcpyDeviceToDevice, st);
     std::shared_ptr<RgfTable> table;                                     // held until the launches are queued
     TileArgs a{};
     int entries = 0;
-    if (int rc = rgf_table_device(c.depth, c.sc, c.ss, c.r, table, &a.colour, &a.space, &entries)) return rc;
-    const Kind kind = c.depth == ADF_32F ? FLOAT : entries > LDS_ENTRIES ? INT_FAR : INT_NEAR;
+    if (int rc = rgf_table_device(depth, c.sc, c.ss, c.r, table, &a.colour, &a.space, &entries)) return rc;
+    const Kind kind = depth == ADF_32F ? FLOAT : entries > LDS_ENTRIES ? INT_FAR : INT_NEAR;
     a.lds_entries = kind == FLOAT ? entries : std::min(entries, LDS_ENTRIES);
     a.last_offset = 4u * (unsigned)(entries - 1);
     a.scale = c.scale;
-    a.src = c.src; a.src_stride = c.src_stride; a.src_map_stride = c.src_map_stride;
-    a.W = c.W; a.H = c.H; a.r = c.r; a.border = c.border; a.src_depth = a.dst_depth = c.depth;
+    a.src = im.src.p; a.src_stride = im.src.stride; a.src_map_stride = im.src.map_stride;
+    a.W = im.W; a.H = im.H; a.r = c.r; a.border = c.border; a.src_depth = a.dst_depth = depth;
     a.entry_bytes = 8;
     const auto kernel = kind == FLOAT ? bilateral_tile_kernel<Rgf<FLOAT>> : kind == INT_FAR ? bilateral_tile_kernel<Rgf<INT_FAR>> : bilateral_tile_kernel<Rgf<INT_NEAR>>;
     for (int k = 0; k < c.num_iter; k++) {
-        if ((c.num_iter - 1 - k) % 2 == 0) { a.dst = c.dst; a.dst_stride = c.dst_stride; a.dst_map_stride = c.dst_map_stride; }
+        if ((c.num_iter - 1 - k) % 2 == 0) { a.dst = im.dst.p; a.dst_stride = im.dst.stride; a.dst_map_stride = im.dst.map_stride; }
         else { a.dst = ws; a.dst_stride = row; a.dst_map_stride = map; }
-        const int rc = launch_tiles(kernel, lds_bytes(c.r, (size_t)a.lds_entries), c.W, c.H, TW, TH, c.n, a, st, [&](TileArgs& t, int m0) {
+        const int rc = launch_tiles(kernel, lds_bytes(c.r, (size_t)a.lds_entries), im.W, im.H, TW, TH, im.n, a, st, [&](TileArgs& t, int m0) {
             t.src = static_cast<const char*>(a.src) + (ptrdiff_t)m0 * a.src_map_stride;
             t.joint = a.joint ? static_cast<const char*>(a.joint) + (ptrdiff_t)m0 * a.joint_map_stride : nullptr;
             t.dst = static_cast<char*>(a.dst) + (ptrdiff_t)m0 * a.dst_map_stride;
@@ -171,8 +161,8 @@ int rgf_run(const RgfCall& c, void* ws, hipStream_t st)
 RgfCall call_of(int n_maps, const void* src, ptrdiff_t src_stride, ptrdiff_t src_map_stride, void* dst, ptrdiff_t dst_stride,
                 ptrdiff_t dst_map_stride, int depth, int W, int H, int d, double sigma_color, double sigma_space, int num_iter, int border_type)
 {
-    return RgfCall{n_maps, src, src_stride, src_map_stride, dst, dst_stride, dst_map_stride, depth, W, H, d, sigma_color, sigma_space,
-                   num_iter, border_type, 0.0, 0.0, 0, 1.0f};
+    return RgfCall{{n_maps, W, H, {}, 0, image_of(src, src_stride, src_map_stride), depth, image_of(dst, dst_stride, dst_map_stride), depth, {}},
+                   d, sigma_color, sigma_space, num_iter, border_type, 0.0, 0.0, 0, 1.0f};
 }
 
 } // namespace
@@ -219,18 +209,10 @@ extern "C" int adf_rolling_guidance_filter_host(int n_maps,
                         num_iter, border_type);
     int rc = rgf_check(c);
     if (rc) return rc;
-    // one block: the sources, dense, then the results and the planes between the iterations
-    const size_t row = (size_t)W * depth_size(depth), map = (size_t)H * row, maps = pad_to(map * n_maps, 256);
-    Scratch blk;
-    if ((rc = blk.take(2 * maps + adf_rolling_guidance_workspace_bytes(n_maps, W, H, depth, num_iter), nullptr))) return rc;
-    char* base = static_cast<char*>(blk.p);
-    RgfCall s = c;                                                       // the same call on the staged images
-    s.src = base; s.src_stride = (ptrdiff_t)row; s.src_map_stride = (ptrdiff_t)map;
-    s.dst = base + maps; s.dst_stride = (ptrdiff_t)row; s.dst_map_stride = (ptrdiff_t)map;
-    if ((rc = copy_images(base, row, map, src, src_stride, src_map_stride, row, H, n_maps, hipMemcpyHostToDevice, nullptr))) return rc;
-    if ((rc = rgf_run(s, base + 2 * maps, nullptr))) return rc;
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    if ((rc = copy_images(dst, dst_stride, dst_map_stride, base + maps, row, map, row, H, n_maps, hipMemcpyDeviceToHost, nullptr))) return rc;
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return ADF_OK;
+    // the workspace: the planes between the iterations (none for num_iter <= 1)
+    return staged_call(c.im, adf_rolling_guidance_workspace_bytes(n_maps, W, H, depth, num_iter), [&](const FilterImages& staged, void* ws, hipStream_t st) {
+        RgfCall s = c;                                                   // the same call on the staged images
+        s.im = staged;
+        return rgf_run(s, ws, st);
+    });
 }

@@ -189,12 +189,8 @@ __global__ void __launch_bounds__(NT) wmf_kernel(WmfArgs a)
 }
 
 struct WmfCall {                       // one call as its C entry point received it
-    int n;
-    const uint8_t* joint; ptrdiff_t joint_stride, joint_map_stride; int joint_channels;
-    const void* src; ptrdiff_t src_stride, src_map_stride; int depth;
-    void* dst; ptrdiff_t dst_stride, dst_map_stride;
-    int W, H, r; double sigma; int weight_type;
-    const uint8_t* mask; ptrdiff_t mask_stride, mask_map_stride;
+    FilterImages im;                   // guide = the joint; one depth for src and dst
+    int r; double sigma; int weight_type;
     int use_ignore; double ignore_value;
 };
 
@@ -202,60 +198,44 @@ constexpr const char* WHO = "weightedMedianFilter";
 
 int wmf_check(const WmfCall& c)
 {
-    if (!c.joint || !c.src || !c.dst) return fail(ADF_EBADARG, "%s: joint, src and dst must be non-NULL", WHO);
-    if (c.n < 1 || c.W < 1 || c.H < 1) return fail(ADF_EBADARG, "%s: the map is empty", WHO);
-    if (!known_depth(c.depth))
+    const FilterImages& im = c.im;
+    if (!im.guide.p || !im.src.p || !im.dst.p) return fail(ADF_EBADARG, "%s: joint, src and dst must be non-NULL", WHO);
+    if (im.n < 1 || im.W < 1 || im.H < 1) return fail(ADF_EBADARG, "%s: the map is empty", WHO);
+    if (!known_depth(im.src_depth))
         return fail(ADF_EBADARG, "%s: src must be CV_8U (ADF_8U), CV_16S (ADF_16S) or CV_32F (ADF_32F), one channel", WHO);
-    if (c.joint_channels != 1 && c.joint_channels != 3) return fail(ADF_EBADARG, "%s: joint must have 1 or 3 channels", WHO);
+    if (im.guide_channels != 1 && im.guide_channels != 3) return fail(ADF_EBADARG, "%s: joint must have 1 or 3 channels", WHO);
     if (int rc = wmf_weights_check(WHO, c.sigma, c.weight_type)) return rc;
     if (c.r < 1 || c.r > ADF_WMF_MAX_RADIUS) return fail(ADF_EBADARG, "%s: r must lie in [1, %d]", WHO, ADF_WMF_MAX_RADIUS);
-    if (c.use_ignore && c.depth != ADF_32F) {
-        const double lim_lo = c.depth == ADF_8U ? 0.0 : -32768.0, lim_hi = c.depth == ADF_8U ? 255.0 : 32767.0;
+    if (c.use_ignore && im.src_depth != ADF_32F) {
+        const double lim_lo = im.src_depth == ADF_8U ? 0.0 : -32768.0, lim_hi = im.src_depth == ADF_8U ? 255.0 : 32767.0;
         if (!(c.ignore_value >= lim_lo && c.ignore_value <= lim_hi) || c.ignore_value != std::nearbyint(c.ignore_value))
             return fail(ADF_EBADARG, "%s: ignore_value must be an integer inside the range of src's depth", WHO);
     }
-    const ptrdiff_t es = (ptrdiff_t)depth_size(c.depth);
-    if (!aligned(c.src, c.src_stride, c.src_map_stride, es) || !aligned(c.dst, c.dst_stride, c.dst_map_stride, es))
-        return fail(ADF_EBADARG, "%s: src and dst and their strides must be aligned to the depth", WHO);
-    if ((int64_t)c.W * c.H >= ((int64_t)1 << 31)) return fail(ADF_ESIZE, "%s: W*H must be below 2^31", WHO);
-    const ptrdiff_t row = (ptrdiff_t)c.W * es, jrow = (ptrdiff_t)c.W * c.joint_channels;
-    if (c.src_stride < row || c.dst_stride < row || c.joint_stride < jrow || (c.mask && c.mask_stride < c.W))
-        return fail(ADF_ESIZE, "%s: row stride smaller than a row", WHO);
-    if (c.n > 1 && (c.src_map_stride < 0 || c.joint_map_stride < 0 || (c.mask && c.mask_map_stride < 0)))
-        return fail(ADF_ESIZE, "%s: map strides must not be negative", WHO);
-    if (!images_disjoint(c.n, row, c.H, c.dst_stride, c.dst_map_stride, false))
-        return fail(ADF_ESIZE, "%s: destination maps of the batch overlap (map stride smaller than a map)", WHO);
-    const Span d = span_of(c.dst, c.n, row, c.H, c.dst_stride, c.dst_map_stride);
-    if (overlap(d, span_of(c.src, c.n, row, c.H, c.src_stride, c.src_map_stride)) ||
-        overlap(d, span_of(c.joint, c.n, jrow, c.H, c.joint_stride, c.joint_map_stride)) ||
-        (c.mask && overlap(d, span_of(c.mask, c.n, c.W, c.H, c.mask_stride, c.mask_map_stride))))
-        return fail(ADF_EBADARG, "%s: dst must not overlap src, joint or mask", WHO);
-    return ADF_OK;
+    return filter_geometry_check(WHO, im, "the depth", "src, joint or mask");
 }
 
 template <class T, int CH>
 int wmf_launch(const WmfCall& c, const WmfArgs& a, hipStream_t st)
 {
-    return launch_tiles(wmf_kernel<T, CH>, tile_entries(c.r) * sizeof(uint2), c.W, c.H, TW, TH, c.n, a, st, [&](WmfArgs& t, int m0) {
-        t.joint = c.joint + (ptrdiff_t)m0 * c.joint_map_stride;
-        t.src = static_cast<const char*>(c.src) + (ptrdiff_t)m0 * c.src_map_stride;
-        t.dst = static_cast<char*>(c.dst) + (ptrdiff_t)m0 * c.dst_map_stride;
-        t.mask = c.mask ? c.mask + (ptrdiff_t)m0 * c.mask_map_stride : nullptr;
+    return launch_tiles(wmf_kernel<T, CH>, tile_entries(c.r) * sizeof(uint2), c.im.W, c.im.H, TW, TH, c.im.n, a, st, [&](WmfArgs& t, int m0) {
+        t.joint = c.im.guide.map(m0); t.src = c.im.src.map(m0); t.dst = c.im.dst.map(m0);
+        t.mask = c.im.mask.p ? c.im.mask.map(m0) : nullptr;
     });
 }
 
 int wmf_run(const WmfCall& c, hipStream_t st)
 {
+    const FilterImages& im = c.im;
     std::shared_ptr<WmfTable> table;                                     // held until the launches are queued
     WmfArgs a{};
     if (int rc = wmf_table_device(c.sigma, c.weight_type, table, &a.table)) return rc;
-    a.joint_stride = c.joint_stride; a.joint_map_stride = c.joint_map_stride;
-    a.src_stride = c.src_stride; a.src_map_stride = c.src_map_stride;
-    a.dst_stride = c.dst_stride; a.dst_map_stride = c.dst_map_stride;
-    a.mask_stride = c.mask_stride; a.mask_map_stride = c.mask_map_stride;
-    a.W = c.W; a.H = c.H; a.r = c.r;
+    a.joint_stride = im.guide.stride; a.joint_map_stride = im.guide.map_stride;
+    a.src_stride = im.src.stride; a.src_map_stride = im.src.map_stride;
+    a.dst_stride = im.dst.stride; a.dst_map_stride = im.dst.map_stride;
+    a.mask_stride = im.mask.stride; a.mask_map_stride = im.mask.map_stride;
+    a.W = im.W; a.H = im.H; a.r = c.r;
     a.use_ignore = c.use_ignore != 0;
-    if (c.depth == ADF_32F) {
+    if (im.src_depth == ADF_32F) {
         // src is compared with ignore_value as doubles: a value no float has (NaN included) ignores nothing
         const float f = (float)c.ignore_value;
         if (a.use_ignore && !((double)f == c.ignore_value)) a.use_ignore = 0;
@@ -263,12 +243,22 @@ int wmf_run(const WmfCall& c, hipStream_t st)
     } else {
         a.ignore = a.use_ignore ? (uint32_t)(int)c.ignore_value : 0u;
     }
-    const bool ch3 = c.joint_channels == 3;
-    switch (c.depth) {
+    const bool ch3 = im.guide_channels == 3;
+    switch (im.src_depth) {
     case ADF_8U: return ch3 ? wmf_launch<uint8_t, 3>(c, a, st) : wmf_launch<uint8_t, 1>(c, a, st);
     case ADF_16S: return ch3 ? wmf_launch<int16_t, 3>(c, a, st) : wmf_launch<int16_t, 1>(c, a, st);
     default: return ch3 ? wmf_launch<float, 3>(c, a, st) : wmf_launch<float, 1>(c, a, st);
     }
+}
+
+WmfCall call_of(int n_maps, const uint8_t* joint, ptrdiff_t joint_stride, ptrdiff_t joint_map_stride, int joint_channels,
+                const void* src, ptrdiff_t src_stride, ptrdiff_t src_map_stride, int depth, void* dst, ptrdiff_t dst_stride, ptrdiff_t dst_map_stride,
+                int W, int H, int r, double sigma, int weight_type, const uint8_t* mask, ptrdiff_t mask_stride, ptrdiff_t mask_map_stride,
+                int use_ignore, double ignore_value)
+{
+    return WmfCall{{n_maps, W, H, image_of(joint, joint_stride, joint_map_stride), joint_channels, image_of(src, src_stride, src_map_stride), depth,
+                    image_of(dst, dst_stride, dst_map_stride), depth, image_of(mask, mask_stride, mask_map_stride)},
+                   r, sigma, weight_type, use_ignore, ignore_value};
 }
 
 } // namespace
@@ -281,9 +271,9 @@ extern "C" int adf_weighted_median_filter_device(int n_maps,
                                                  const uint8_t* mask, ptrdiff_t mask_stride, ptrdiff_t mask_map_stride,
                                                  int use_ignore, double ignore_value, void* stream)
 {
-    const WmfCall c{n_maps, joint, joint_stride, joint_map_stride, joint_channels, src, src_stride, src_map_stride, depth,
-                    dst, dst_stride, dst_map_stride, W, H, r, sigma, weight_type, mask, mask_stride, mask_map_stride,
-                    use_ignore, ignore_value};
+    const WmfCall c = call_of(n_maps, joint, joint_stride, joint_map_stride, joint_channels, src, src_stride, src_map_stride, depth,
+                              dst, dst_stride, dst_map_stride, W, H, r, sigma, weight_type, mask, mask_stride, mask_map_stride,
+                              use_ignore, ignore_value);
     int rc = wmf_check(c);
     return rc ? rc : wmf_run(c, (hipStream_t)stream);
 }
@@ -296,29 +286,13 @@ extern "C" int adf_weighted_median_filter_host(int n_maps,
                                                const uint8_t* mask, ptrdiff_t mask_stride, ptrdiff_t mask_map_stride,
                                                int use_ignore, double ignore_value)
 {
-    const WmfCall c{n_maps, joint, joint_stride, joint_map_stride, joint_channels, src, src_stride, src_map_stride, depth,
-                    dst, dst_stride, dst_map_stride, W, H, r, sigma, weight_type, mask, mask_stride, mask_map_stride,
-                    use_ignore, ignore_value};
+    const WmfCall c = call_of(n_maps, joint, joint_stride, joint_map_stride, joint_channels, src, src_stride, src_map_stride, depth,
+                              dst, dst_stride, dst_map_stride, W, H, r, sigma, weight_type, mask, mask_stride, mask_map_stride,
+                              use_ignore, ignore_value);
     int rc = wmf_check(c);
-    if (rc) return rc;
-    // one block: the joint images, dense, then the sources, the masks and the results
-    const size_t jrow = (size_t)W * joint_channels, jmap = (size_t)H * jrow, joints = pad_to(jmap * n_maps, 256);
-    const size_t srow = (size_t)W * depth_size(depth), smap = (size_t)H * srow, srcs = pad_to(smap * n_maps, 256);
-    const size_t mrow = (size_t)W, mmap = (size_t)H * mrow, masks = mask ? pad_to(mmap * n_maps, 256) : 0;
-    Scratch blk;
-    if ((rc = blk.take(joints + 2 * srcs + masks, nullptr))) return rc;
-    char* base = static_cast<char*>(blk.p);
-    WmfCall d = c;                                                       // the same call on the staged images
-    d.joint = reinterpret_cast<uint8_t*>(base); d.joint_stride = (ptrdiff_t)jrow; d.joint_map_stride = (ptrdiff_t)jmap;
-    d.src = base + joints; d.src_stride = (ptrdiff_t)srow; d.src_map_stride = (ptrdiff_t)smap;
-    d.dst = base + joints + srcs; d.dst_stride = (ptrdiff_t)srow; d.dst_map_stride = (ptrdiff_t)smap;
-    if (mask) { d.mask = reinterpret_cast<uint8_t*>(base + joints + 2 * srcs); d.mask_stride = (ptrdiff_t)mrow; d.mask_map_stride = (ptrdiff_t)mmap; }
-    if ((rc = copy_images(base, jrow, jmap, joint, joint_stride, joint_map_stride, jrow, H, n_maps, hipMemcpyHostToDevice, nullptr))) return rc;
-    if ((rc = copy_images(base + joints, srow, smap, src, src_stride, src_map_stride, srow, H, n_maps, hipMemcpyHostToDevice, nullptr))) return rc;
-    if (mask && (rc = copy_images(base + joints + 2 * srcs, mrow, mmap, mask, mask_stride, mask_map_stride, mrow, H, n_maps, hipMemcpyHostToDevice, nullptr))) return rc;
-    if ((rc = wmf_run(d, nullptr))) return rc;
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    if ((rc = copy_images(dst, dst_stride, dst_map_stride, base + joints + srcs, srow, smap, srow, H, n_maps, hipMemcpyDeviceToHost, nullptr))) return rc;
-    HIP_TRY(hipStreamSynchronize(nullptr));
-    return ADF_OK;
+    return rc ? rc : staged_call(c.im, 0, [&](const FilterImages& staged, void*, hipStream_t st) {
+        WmfCall d = c;                                                   // the same call on the staged images
+        d.im = staged;
+        return wmf_run(d, st);
+    });
 }

@@ -34,6 +34,7 @@ leading batch dimension filters N independent, equally sized pairs in one call.
 All compute runs in the HIP library; there is no CPU fallback.
 """
 import ctypes as C
+import functools
 import math
 
 import numpy as np
@@ -1238,16 +1239,88 @@ _WMF = "weightedMedianFilter"
 _WMF_NOT_BUILT = {WMF_IV1: "WMF_IV1", WMF_IV2: "WMF_IV2", WMF_COS: "WMF_COS", WMF_JAC: "WMF_JAC"}
 
 
-def _wmf_weight_type(who, weightType):
+def _choice(who, value, accepted, not_built, must, are, unknown=None):
+    """int(value) when it is one of `accepted`.  A value of cv's that this build leaves out is refused by its name in
+    `not_built` -- any other integer too, worded by `unknown`, where the filter has such a text -- with what IS built
+    (`are`); everything else with what the parameter must be (`must`)."""
     try:
-        wt = int(weightType)
+        v = int(value)
     except (TypeError, ValueError):
-        raise AdfError(_lib.ADF_EBADARG, "%s: weightType must be WMF_EXP or WMF_OFF" % who)
-    if wt in _WMF_NOT_BUILT:
-        raise AdfError(_lib.ADF_EBADARG, "%s: %s is not built; WMF_EXP and WMF_OFF are" % (who, _WMF_NOT_BUILT[wt]))
-    if wt not in (WMF_EXP, WMF_OFF):
-        raise AdfError(_lib.ADF_EBADARG, "%s: weightType must be WMF_EXP or WMF_OFF" % who)
-    return wt
+        raise AdfError(_lib.ADF_EBADARG, "%s: %s" % (who, must))
+    if v in accepted:
+        return v
+    name = not_built.get(v) or (unknown and unknown % v)
+    if name:
+        raise AdfError(_lib.ADF_EBADARG, "%s: %s is not built; %s" % (who, name, are))
+    raise AdfError(_lib.ADF_EBADARG, "%s: %s" % (who, must))
+
+
+_wmf_weight_type = functools.partial(_choice, accepted=(WMF_EXP, WMF_OFF), not_built=_WMF_NOT_BUILT,   # (who, weightType)
+                                     must="weightType must be WMF_EXP or WMF_OFF", are="WMF_EXP and WMF_OFF are")
+
+
+CV_8U, CV_16S = 0, 3    # cv's depth codes (CV_32F is above): what dDepth takes
+_GF_DTYPE = {CV_8U: np.uint8, CV_16S: np.int16, CV_32F: np.float32}
+
+
+def _filter_images(who, src, dst, dDepth=-1, guide=None, role="guide", mask=None, suffix="", float_guide=None, in_place=None):
+    """What the five edge-aware filters ask of their images, in the one order they all report it -> (S, G, M, D, dst,
+    dt, ddt): the _Images of src, of the guide or joint (`role` names it; None: the filter has none), of the mask (None:
+    none) and of dst -- made here, of dtype ddt, when None --, src's dtype and dst's.  A filter without a dDepth leaves
+    it at -1: dst has src's dtype.  `suffix` ends the refusal of a src that is no map or batch; `float_guide` and
+    `in_place` word one filter's own refusal (a float32 joint; dst is src) at its place in that order."""
+    nd = len(src.shape)
+    if nd not in (2, 3):
+        raise AdfError(_lib.ADF_EBADARG, "%s: src must be (H,W) or a batch (N,H,W) of one-channel maps%s" % (who, suffix))
+    batched = nd == 3
+    for dt in (np.uint8, np.int16, np.float32):
+        if _map_dtype(src, dt) is not None:
+            break
+    else:
+        raise AdfError(_lib.ADF_EBADARG, "%s: src must be uint8 (CV_8U), int16 (CV_16S) or float32 (CV_32F)" % who)
+    if float_guide and _map_dtype(guide, np.float32) is not None:
+        raise AdfError(_lib.ADF_EBADARG, "%s: %s" % (who, float_guide))
+    if dDepth != -1 and dDepth not in _GF_DTYPE:
+        raise AdfError(_lib.ADF_EBADARG, "%s: dDepth must be -1, CV_8U, CV_16S or CV_32F" % who)
+    ddt = dt if dDepth == -1 else _GF_DTYPE[dDepth]
+    S = _Image(src, dt, "src", batched)
+    G = None if guide is None else _Image(guide, np.uint8, role, batched, allow_channels=(1, 3))
+    M = None if mask is None else _Image(mask, np.uint8, "mask", batched)
+    if in_place and dst is src:
+        raise AdfError(_lib.ADF_EBADARG, "%s: %s" % (who, in_place))
+    if dst is None:
+        dst = _out_like(S, batched, ddt)
+    D = _Image(dst, ddt, "dst", batched)
+    for im, what in ((G, role), (M, "mask"), (D, "dst")):
+        if im is None:
+            continue
+        if (im.n, im.h, im.w) != (S.n, S.h, S.w) or im.device != S.device:
+            raise AdfError(_lib.ADF_ESIZE, "%s: %s must have src's size on its side (host or device)" % (who, what))
+        if S.device and im.keep.device != S.keep.device:
+            raise AdfError(_lib.ADF_EBADARG, "%s: %s lives on %s, src on %s" % (who, what, im.keep.device, S.keep.device))
+    return S, G, M, D, dst, dt, ddt
+
+
+def _workspace(who, S, workspace):
+    """(pointer, bytes) of a caller's workspace for a call on S's device: a contiguous CUDA tensor there; (None, 0) for None."""
+    if workspace is None:
+        return None, 0
+    if not S.device:
+        raise AdfError(_lib.ADF_EBADARG, "%s: a workspace goes with CUDA tensors only" % who)
+    if not (_is_torch(workspace) and workspace.is_cuda and workspace.is_contiguous()):
+        raise AdfError(_lib.ADF_EBADARG, "%s: workspace must be a contiguous CUDA tensor (or None)" % who)
+    if workspace.device != S.keep.device:
+        raise AdfError(_lib.ADF_EBADARG, "%s: workspace lives on %s, src on %s" % (who, workspace.device, S.keep.device))
+    return workspace.data_ptr(), workspace.numel() * workspace.element_size()
+
+
+def _filter_call(name, S, args, ws=None):
+    """The entry `name` on S's side, on S's device when it has one; `ws` (the device entry alone takes one) follows args."""
+    if not S.device:
+        _call(name, S, args)
+        return
+    with torch.cuda.device(S.keep.device):     # (spelled out, not _on_device: this runs once per filter call)
+        _call(name, S, args + ws if ws else args)
 
 
 def wmfWeightTable(sigma, weightType=WMF_EXP):
@@ -1275,36 +1348,11 @@ def weightedMedianFilter(joint, src, r, sigma=25.5, weightType=WMF_EXP, mask=Non
     if joint is None or src is None:
         raise AdfError(_lib.ADF_EBADARG, "%s: joint and src must not be empty" % _WMF)
     wt = _wmf_weight_type(_WMF, weightType)
-    nd = len(src.shape)
-    if nd not in (2, 3):
-        raise AdfError(_lib.ADF_EBADARG, "%s: src must be (H,W) or a batch (N,H,W) of one-channel maps" % _WMF)
-    batched = nd == 3
-    for dt in (np.uint8, np.int16, np.float32):
-        if _map_dtype(src, dt) is not None:
-            break
-    else:
-        raise AdfError(_lib.ADF_EBADARG, "%s: src must be uint8 (CV_8U), int16 (CV_16S) or float32 (CV_32F)" % _WMF)
-    S = _Image(src, dt, "src", batched)
-    J = _Image(joint, np.uint8, "joint", batched, allow_channels=(1, 3))
-    M = None if mask is None else _Image(mask, np.uint8, "mask", batched)
-    if dst is None:
-        dst = _out_like(S, batched, dt)
-    D = _Image(dst, dt, "dst", batched)
-    for im, what in ((J, "joint"), (M, "mask"), (D, "dst")):
-        if im is None:
-            continue
-        if (im.n, im.h, im.w) != (S.n, S.h, S.w) or im.device != S.device:
-            raise AdfError(_lib.ADF_ESIZE, "%s: %s must have src's size on its side (host or device)" % (_WMF, what))
-        if S.device and im.keep.device != S.keep.device:
-            raise AdfError(_lib.ADF_EBADARG, "%s: %s lives on %s, src on %s" % (_WMF, what, im.keep.device, S.keep.device))
+    S, J, M, D, dst, dt, _ = _filter_images(_WMF, src, dst, -1, joint, "joint", mask)
     args = (S.n, J.ptr, J.stride, J.pair_stride, J.c, S.ptr, S.stride, S.pair_stride, _DEPTH[dt], D.ptr, D.stride, D.pair_stride,
             S.w, S.h, int(r), float(sigma), wt, M.ptr if M else None, M.stride if M else 0, M.pair_stride if M else 0,
             0 if ignoreValue is None else 1, 0.0 if ignoreValue is None else float(ignoreValue))
-    if not S.device:
-        _call("adf_weighted_median_filter", S, args)
-        return dst
-    with torch.cuda.device(S.keep.device):
-        _call("adf_weighted_median_filter", S, args)
+    _filter_call("adf_weighted_median_filter", S, args)
     return dst
 
 # ---------------------------------------------------------------------------------------------
@@ -1312,8 +1360,6 @@ def weightedMedianFilter(joint, src, r, sigma=25.5, weightType=WMF_EXP, mask=Non
 # exact definition (include/adf_wls.h; csrc/guided_filter_kernels.hip; the direct statement is tests/gf_ref.py).
 # ---------------------------------------------------------------------------------------------
 _GF = "guidedFilter"
-CV_8U, CV_16S = 0, 3    # cv's depth codes (CV_32F is above): what dDepth takes
-_GF_DTYPE = {CV_8U: np.uint8, CV_16S: np.int16, CV_32F: np.float32}
 
 
 def guidedFilterWorkspaceBytes(n, H, W, channels):
@@ -1342,44 +1388,10 @@ def guidedFilter(guide, src, radius, eps, dDepth=-1, dst=None, workspace=None):
     the library's cached scratch.  Numpy arrays take the host entry point.  Returns dst."""
     if guide is None or src is None:
         raise AdfError(_lib.ADF_EBADARG, "%s: guide and src must not be empty" % _GF)
-    nd = len(src.shape)
-    if nd not in (2, 3):
-        raise AdfError(_lib.ADF_EBADARG, "%s: src must be (H,W) or a batch (N,H,W) of one-channel maps" % _GF)
-    batched = nd == 3
-    for dt in (np.uint8, np.int16, np.float32):
-        if _map_dtype(src, dt) is not None:
-            break
-    else:
-        raise AdfError(_lib.ADF_EBADARG, "%s: src must be uint8 (CV_8U), int16 (CV_16S) or float32 (CV_32F)" % _GF)
-    if dDepth != -1 and dDepth not in _GF_DTYPE:
-        raise AdfError(_lib.ADF_EBADARG, "%s: dDepth must be -1, CV_8U, CV_16S or CV_32F" % _GF)
-    ddt = dt if dDepth == -1 else _GF_DTYPE[dDepth]
-    S = _Image(src, dt, "src", batched)
-    G = _Image(guide, np.uint8, "guide", batched, allow_channels=(1, 3))
-    if dst is None:
-        dst = _out_like(S, batched, ddt)
-    D = _Image(dst, ddt, "dst", batched)
-    for im, what in ((G, "guide"), (D, "dst")):
-        if (im.n, im.h, im.w) != (S.n, S.h, S.w) or im.device != S.device:
-            raise AdfError(_lib.ADF_ESIZE, "%s: %s must have src's size on its side (host or device)" % (_GF, what))
-        if S.device and im.keep.device != S.keep.device:
-            raise AdfError(_lib.ADF_EBADARG, "%s: %s lives on %s, src on %s" % (_GF, what, im.keep.device, S.keep.device))
+    S, G, _, D, dst, dt, ddt = _filter_images(_GF, src, dst, dDepth, guide)
     args = (S.n, G.ptr, G.stride, G.pair_stride, G.c, S.ptr, S.stride, S.pair_stride, _DEPTH[dt], D.ptr, D.stride, D.pair_stride,
             _DEPTH[ddt], S.w, S.h, int(radius), float(eps))
-    if not S.device:
-        if workspace is not None:
-            raise AdfError(_lib.ADF_EBADARG, "%s: a workspace goes with CUDA tensors only" % _GF)
-        _call("adf_guided_filter", S, args)
-        return dst
-    ws, ws_bytes = None, 0
-    if workspace is not None:
-        if not (_is_torch(workspace) and workspace.is_cuda and workspace.is_contiguous()):
-            raise AdfError(_lib.ADF_EBADARG, "%s: workspace must be a contiguous CUDA tensor (or None)" % _GF)
-        if workspace.device != S.keep.device:
-            raise AdfError(_lib.ADF_EBADARG, "%s: workspace lives on %s, src on %s" % (_GF, workspace.device, S.keep.device))
-        ws, ws_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
-    with torch.cuda.device(S.keep.device):
-        _call("adf_guided_filter", S, args + (ws, ws_bytes))
+    _filter_call("adf_guided_filter", S, args, _workspace(_GF, S, workspace))
     return dst
 
 
@@ -1414,16 +1426,7 @@ _DT = "dtFilter"
 _DT_NOT_BUILT = {DTF_NC: "DTF_NC", DTF_IC: "DTF_IC"}
 
 
-def _dt_mode(who, mode):
-    try:
-        m = int(mode)
-    except (TypeError, ValueError):
-        raise AdfError(_lib.ADF_EBADARG, "%s: mode must be DTF_RF" % who)
-    if m in _DT_NOT_BUILT:
-        raise AdfError(_lib.ADF_EBADARG, "%s: %s is not built; DTF_RF is" % (who, _DT_NOT_BUILT[m]))
-    if m != DTF_RF:
-        raise AdfError(_lib.ADF_EBADARG, "%s: mode must be DTF_RF" % who)
-    return m
+_dt_mode = functools.partial(_choice, accepted=(DTF_RF,), not_built=_DT_NOT_BUILT, must="mode must be DTF_RF", are="DTF_RF is")   # (who, mode)
 
 
 def dtRfTable(sigmaSpatial, sigmaColor, numIters=3, channels=1):
@@ -1467,44 +1470,10 @@ def dtFilter(guide, src, sigmaSpatial, sigmaColor, mode=DTF_RF, numIters=3, dDep
     if guide is None or src is None:
         raise AdfError(_lib.ADF_EBADARG, "%s: guide and src must not be empty" % _DT)
     m = _dt_mode(_DT, mode)
-    nd = len(src.shape)
-    if nd not in (2, 3):
-        raise AdfError(_lib.ADF_EBADARG, "%s: src must be (H,W) or a batch (N,H,W) of one-channel maps" % _DT)
-    batched = nd == 3
-    for dt in (np.uint8, np.int16, np.float32):
-        if _map_dtype(src, dt) is not None:
-            break
-    else:
-        raise AdfError(_lib.ADF_EBADARG, "%s: src must be uint8 (CV_8U), int16 (CV_16S) or float32 (CV_32F)" % _DT)
-    if dDepth != -1 and dDepth not in _GF_DTYPE:
-        raise AdfError(_lib.ADF_EBADARG, "%s: dDepth must be -1, CV_8U, CV_16S or CV_32F" % _DT)
-    ddt = dt if dDepth == -1 else _GF_DTYPE[dDepth]
-    S = _Image(src, dt, "src", batched)
-    G = _Image(guide, np.uint8, "guide", batched, allow_channels=(1, 3))
-    if dst is None:
-        dst = _out_like(S, batched, ddt)
-    D = _Image(dst, ddt, "dst", batched)
-    for im, what in ((G, "guide"), (D, "dst")):
-        if (im.n, im.h, im.w) != (S.n, S.h, S.w) or im.device != S.device:
-            raise AdfError(_lib.ADF_ESIZE, "%s: %s must have src's size on its side (host or device)" % (_DT, what))
-        if S.device and im.keep.device != S.keep.device:
-            raise AdfError(_lib.ADF_EBADARG, "%s: %s lives on %s, src on %s" % (_DT, what, im.keep.device, S.keep.device))
+    S, G, _, D, dst, dt, ddt = _filter_images(_DT, src, dst, dDepth, guide)
     args = (S.n, G.ptr, G.stride, G.pair_stride, G.c, S.ptr, S.stride, S.pair_stride, _DEPTH[dt], D.ptr, D.stride, D.pair_stride,
             _DEPTH[ddt], S.w, S.h, float(sigmaSpatial), float(sigmaColor), m, int(numIters))
-    if not S.device:
-        if workspace is not None:
-            raise AdfError(_lib.ADF_EBADARG, "%s: a workspace goes with CUDA tensors only" % _DT)
-        _call("adf_dt_filter", S, args)
-        return dst
-    ws, ws_bytes = None, 0
-    if workspace is not None:
-        if not (_is_torch(workspace) and workspace.is_cuda and workspace.is_contiguous()):
-            raise AdfError(_lib.ADF_EBADARG, "%s: workspace must be a contiguous CUDA tensor (or None)" % _DT)
-        if workspace.device != S.keep.device:
-            raise AdfError(_lib.ADF_EBADARG, "%s: workspace lives on %s, src on %s" % (_DT, workspace.device, S.keep.device))
-        ws, ws_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
-    with torch.cuda.device(S.keep.device):
-        _call("adf_dt_filter", S, args + (ws, ws_bytes))
+    _filter_call("adf_dt_filter", S, args, _workspace(_DT, S, workspace))
     return dst
 
 
@@ -1543,17 +1512,9 @@ BORDER_DEFAULT = BORDER_REFLECT_101     # cv::BORDER_DEFAULT
 _JBF_NOT_BUILT = {BORDER_CONSTANT: "BORDER_CONSTANT", BORDER_WRAP: "BORDER_WRAP"}
 
 
-def _jbf_border(who, borderType):
-    try:
-        b = int(borderType)
-    except (TypeError, ValueError):
-        raise AdfError(_lib.ADF_EBADARG, "%s: borderType must be BORDER_REPLICATE, BORDER_REFLECT or BORDER_REFLECT_101" % who)
-    if b in _JBF_NOT_BUILT:
-        raise AdfError(_lib.ADF_EBADARG, "%s: %s is not built; BORDER_REPLICATE, BORDER_REFLECT and BORDER_REFLECT_101 are"
-                       % (who, _JBF_NOT_BUILT[b]))
-    if b not in (BORDER_REPLICATE, BORDER_REFLECT, BORDER_REFLECT_101):
-        raise AdfError(_lib.ADF_EBADARG, "%s: borderType %d is not built; BORDER_REPLICATE, BORDER_REFLECT and BORDER_REFLECT_101 are" % (who, b))
-    return b
+_jbf_border = functools.partial(_choice, accepted=(BORDER_REPLICATE, BORDER_REFLECT, BORDER_REFLECT_101), not_built=_JBF_NOT_BUILT,   # (who, borderType)
+                                must="borderType must be BORDER_REPLICATE, BORDER_REFLECT or BORDER_REFLECT_101",
+                                are="BORDER_REPLICATE, BORDER_REFLECT and BORDER_REFLECT_101 are", unknown="borderType %d")
 
 
 def jbfTables(d, sigmaColor, sigmaSpace, channels=1):
@@ -1594,37 +1555,11 @@ def jointBilateralFilter(joint, src, d, sigmaColor, sigmaSpace, borderType=BORDE
     if joint is src:
         raise AdfError(_lib.ADF_EBADARG, "%s: joint is src is cv::bilateralFilter, which is not built" % _JBF)
     b = _jbf_border(_JBF, borderType)
-    nd = len(src.shape)
-    if nd not in (2, 3):
-        raise AdfError(_lib.ADF_EBADARG, "%s: src must be (H,W) or a batch (N,H,W) of one-channel maps; multi-channel sources are not built" % _JBF)
-    batched = nd == 3
-    for dt in (np.uint8, np.int16, np.float32):
-        if _map_dtype(src, dt) is not None:
-            break
-    else:
-        raise AdfError(_lib.ADF_EBADARG, "%s: src must be uint8 (CV_8U), int16 (CV_16S) or float32 (CV_32F)" % _JBF)
-    if _map_dtype(joint, np.float32) is not None:
-        raise AdfError(_lib.ADF_EBADARG, "%s: a float32 (CV_32F) joint is not built; the joint must be uint8" % _JBF)
-    if dDepth != -1 and dDepth not in _GF_DTYPE:
-        raise AdfError(_lib.ADF_EBADARG, "%s: dDepth must be -1, CV_8U, CV_16S or CV_32F" % _JBF)
-    ddt = dt if dDepth == -1 else _GF_DTYPE[dDepth]
-    S = _Image(src, dt, "src", batched)
-    J = _Image(joint, np.uint8, "joint", batched, allow_channels=(1, 3))
-    if dst is None:
-        dst = _out_like(S, batched, ddt)
-    D = _Image(dst, ddt, "dst", batched)
-    for im, what in ((J, "joint"), (D, "dst")):
-        if (im.n, im.h, im.w) != (S.n, S.h, S.w) or im.device != S.device:
-            raise AdfError(_lib.ADF_ESIZE, "%s: %s must have src's size on its side (host or device)" % (_JBF, what))
-        if S.device and im.keep.device != S.keep.device:
-            raise AdfError(_lib.ADF_EBADARG, "%s: %s lives on %s, src on %s" % (_JBF, what, im.keep.device, S.keep.device))
+    S, J, _, D, dst, dt, ddt = _filter_images(_JBF, src, dst, dDepth, joint, "joint", suffix="; multi-channel sources are not built",
+                                              float_guide="a float32 (CV_32F) joint is not built; the joint must be uint8")
     args = (S.n, J.ptr, J.stride, J.pair_stride, J.c, S.ptr, S.stride, S.pair_stride, _DEPTH[dt], D.ptr, D.stride, D.pair_stride,
             _DEPTH[ddt], S.w, S.h, int(d), float(sigmaColor), float(sigmaSpace), b)
-    if not S.device:
-        _call("adf_joint_bilateral_filter", S, args)
-        return dst
-    with torch.cuda.device(S.keep.device):
-        _call("adf_joint_bilateral_filter", S, args)
+    _filter_call("adf_joint_bilateral_filter", S, args)
     return dst
 
 
@@ -1699,41 +1634,11 @@ def rollingGuidanceFilter(src, d=-1, sigmaColor=25, sigmaSpace=3, numOfIter=4, b
     if src is None:
         raise AdfError(_lib.ADF_EBADARG, "%s: src must not be empty" % _RGF)
     b = _jbf_border(_RGF, borderType)
-    nd = len(src.shape)
-    if nd not in (2, 3):
-        raise AdfError(_lib.ADF_EBADARG, "%s: src must be (H,W) or a batch (N,H,W) of one-channel maps; multi-channel sources are not built" % _RGF)
-    batched = nd == 3
-    for dt in (np.uint8, np.int16, np.float32):
-        if _map_dtype(src, dt) is not None:
-            break
-    else:
-        raise AdfError(_lib.ADF_EBADARG, "%s: src must be uint8 (CV_8U), int16 (CV_16S) or float32 (CV_32F)" % _RGF)
-    S = _Image(src, dt, "src", batched)
-    if dst is src:
-        raise AdfError(_lib.ADF_EBADARG, "%s: dst is src: there is no in-place call" % _RGF)
-    if dst is None:
-        dst = _out_like(S, batched, dt)
-    D = _Image(dst, dt, "dst", batched)
-    if (D.n, D.h, D.w) != (S.n, S.h, S.w) or D.device != S.device:
-        raise AdfError(_lib.ADF_ESIZE, "%s: dst must have src's size on its side (host or device)" % _RGF)
-    if S.device and D.keep.device != S.keep.device:
-        raise AdfError(_lib.ADF_EBADARG, "%s: dst lives on %s, src on %s" % (_RGF, D.keep.device, S.keep.device))
+    S, _, _, D, dst, dt, _ = _filter_images(_RGF, src, dst, suffix="; multi-channel sources are not built",
+                                            in_place="dst is src: there is no in-place call")
     args = (S.n, S.ptr, S.stride, S.pair_stride, D.ptr, D.stride, D.pair_stride, _DEPTH[dt], S.w, S.h, int(d), float(sigmaColor),
             float(sigmaSpace), int(numOfIter), b)
-    if not S.device:
-        if workspace is not None:
-            raise AdfError(_lib.ADF_EBADARG, "%s: a workspace goes with CUDA tensors only" % _RGF)
-        _call("adf_rolling_guidance_filter", S, args)
-        return dst
-    ws, ws_bytes = None, 0
-    if workspace is not None:
-        if not (_is_torch(workspace) and workspace.is_cuda and workspace.is_contiguous()):
-            raise AdfError(_lib.ADF_EBADARG, "%s: workspace must be a contiguous CUDA tensor (or None)" % _RGF)
-        if workspace.device != S.keep.device:
-            raise AdfError(_lib.ADF_EBADARG, "%s: workspace lives on %s, src on %s" % (_RGF, workspace.device, S.keep.device))
-        ws, ws_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
-    with torch.cuda.device(S.keep.device):
-        _call("adf_rolling_guidance_filter", S, args + (ws, ws_bytes))
+    _filter_call("adf_rolling_guidance_filter", S, args, _workspace(_RGF, S, workspace))
     return dst
 
 

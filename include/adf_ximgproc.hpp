@@ -129,21 +129,46 @@ inline void validateDisparity(Mat& disparity, const Mat& cost, int minDisparity,
 // are refused.  The overload with ignoreValue (extension) also ignores -- and so fills from their neighbours -- the pixels
 // that hold it: (minDisparity - 1) * 16 for a matcher's map after validateDisparity / filterSpeckles.
 enum WMFWeightType { WMF_EXP, WMF_IV1, WMF_IV2, WMF_COS, WMF_JAC, WMF_OFF }; // cv's values
+// What the five edge-aware filters below ask of their Mats, said once; `who` is the function's name in the texts.
+inline void filter_src(const std::string& who, const Mat& src)
+{
+    if (src.empty() || mat_channels(src) != 1 || (mat_depth(src) != D8U && mat_depth(src) != D16S && mat_depth(src) != D32F))
+        throw Exception(ADF_EBADARG, who + ": src must be a non-empty CV_8UC1, CV_16SC1 or CV_32FC1 image");
+}
+inline void filter_guide(const std::string& who, const std::string& role, const Mat& guide, const Mat& src)   // role: "guide" or "joint"
+{
+    if (guide.empty() || mat_depth(guide) != D8U) throw Exception(ADF_EBADARG, who + ": " + role + " must be a non-empty CV_8UC1 or CV_8UC3 image");
+    if (guide.rows != src.rows || guide.cols != src.cols) throw Exception(ADF_ESIZE, who + ": " + role + " must have src's size");
+}
+inline int filter_ddepth(const std::string& who, const Mat& src, int dDepth)   // the depth dDepth asks for: -1 is src's
+{
+    const int ddepth = dDepth == -1 ? mat_depth(src) : dDepth;
+    if (ddepth != D8U && ddepth != D16S && ddepth != D32F) throw Exception(ADF_EBADARG, who + ": dDepth must be -1, CV_8U, CV_16S or CV_32F");
+    return ddepth;
+}
+inline int depth_code(int depth) { return depth == D8U ? ADF_8U : depth == D16S ? ADF_16S : ADF_32F; }   // cv's depth as the C-ABI's
+inline Mat filter_out(const Mat& src, int depth) { Mat out; mat_create(out, src.rows, src.cols, depth, 1); return out; }   // a new Mat: dst may be src
+inline Mat guide_copy(const std::string& who, const Mat& guide)   // a filter object's own dense copy of the guide it accepts
+{
+    if (guide.empty() || mat_depth(guide) != D8U || (mat_channels(guide) != 1 && mat_channels(guide) != 3))
+        throw Exception(ADF_EBADARG, who + ": guide must be a non-empty CV_8UC1 or CV_8UC3 image");
+    Mat own;
+    mat_create(own, guide.rows, guide.cols, D8U, mat_channels(guide));
+    for (int y = 0; y < guide.rows; y++)
+        std::memcpy(own.data + (size_t)mat_step(own) * y, guide.data + (size_t)mat_step(guide) * y, (size_t)guide.cols * mat_channels(guide));
+    return own;
+}
+
 inline void weighted_median(const Mat& joint, const Mat& src, Mat& dst, int r, double sigma, int weightType, const Mat& mask,
                             const double* ignoreValue)
 {
-    if (src.empty() || mat_channels(src) != 1 || (mat_depth(src) != D8U && mat_depth(src) != D16S && mat_depth(src) != D32F))
-        throw Exception(ADF_EBADARG, "weightedMedianFilter: src must be a non-empty CV_8UC1, CV_16SC1 or CV_32FC1 image");
-    if (joint.empty() || mat_depth(joint) != D8U)
-        throw Exception(ADF_EBADARG, "weightedMedianFilter: joint must be a non-empty CV_8UC1 or CV_8UC3 image");
-    if (joint.rows != src.rows || joint.cols != src.cols) throw Exception(ADF_ESIZE, "weightedMedianFilter: joint must have src's size");
+    filter_src("weightedMedianFilter", src);
+    filter_guide("weightedMedianFilter", "joint", joint, src);
     if (!mask.empty() && (mat_depth(mask) != D8U || mat_channels(mask) != 1))
         throw Exception(ADF_EBADARG, "weightedMedianFilter: mask must be empty or a CV_8UC1 image");
     if (!mask.empty() && (mask.rows != src.rows || mask.cols != src.cols)) throw Exception(ADF_ESIZE, "weightedMedianFilter: mask must have src's size");
-    Mat out;                                                             // (dst may be src: the result lands in a new Mat)
-    mat_create(out, src.rows, src.cols, mat_depth(src), 1);
-    const int depth = mat_depth(src) == D8U ? ADF_8U : mat_depth(src) == D16S ? ADF_16S : ADF_32F;
-    check(adf_weighted_median_filter_host(1, joint.data, mat_step(joint), 0, mat_channels(joint), src.data, mat_step(src), 0, depth,
+    Mat out = filter_out(src, mat_depth(src));
+    check(adf_weighted_median_filter_host(1, joint.data, mat_step(joint), 0, mat_channels(joint), src.data, mat_step(src), 0, depth_code(mat_depth(src)),
                                           out.data, mat_step(out), 0, src.cols, src.rows, r, sigma, weightType,
                                           mask.empty() ? nullptr : mask.data, mask.empty() ? 0 : mat_step(mask), 0,
                                           ignoreValue ? 1 : 0, ignoreValue ? *ignoreValue : 0.0));
@@ -169,19 +194,12 @@ inline void weightedMedianFilter(const Mat& joint, const Mat& src, Mat& dst, int
 // weightedMedianFilter with ignoreValue first.
 inline void guidedFilter(const Mat& guide, const Mat& src, Mat& dst, int radius, double eps, int dDepth = -1)
 {
-    if (src.empty() || mat_channels(src) != 1 || (mat_depth(src) != D8U && mat_depth(src) != D16S && mat_depth(src) != D32F))
-        throw Exception(ADF_EBADARG, "guidedFilter: src must be a non-empty CV_8UC1, CV_16SC1 or CV_32FC1 image");
-    if (guide.empty() || mat_depth(guide) != D8U)
-        throw Exception(ADF_EBADARG, "guidedFilter: guide must be a non-empty CV_8UC1 or CV_8UC3 image");
-    if (guide.rows != src.rows || guide.cols != src.cols) throw Exception(ADF_ESIZE, "guidedFilter: guide must have src's size");
-    const int ddepth = dDepth == -1 ? mat_depth(src) : dDepth;
-    if (ddepth != D8U && ddepth != D16S && ddepth != D32F)
-        throw Exception(ADF_EBADARG, "guidedFilter: dDepth must be -1, CV_8U, CV_16S or CV_32F");
-    auto code = [](int depth) { return depth == D8U ? ADF_8U : depth == D16S ? ADF_16S : ADF_32F; };
-    Mat out;                                                             // (dst may be src: the result lands in a new Mat)
-    mat_create(out, src.rows, src.cols, ddepth, 1);
-    check(adf_guided_filter_host(1, guide.data, mat_step(guide), 0, mat_channels(guide), src.data, mat_step(src), 0, code(mat_depth(src)),
-                                 out.data, mat_step(out), 0, code(ddepth), src.cols, src.rows, radius, eps));
+    filter_src("guidedFilter", src);
+    filter_guide("guidedFilter", "guide", guide, src);
+    const int ddepth = filter_ddepth("guidedFilter", src, dDepth);
+    Mat out = filter_out(src, ddepth);
+    check(adf_guided_filter_host(1, guide.data, mat_step(guide), 0, mat_channels(guide), src.data, mat_step(src), 0, depth_code(mat_depth(src)),
+                                 out.data, mat_step(out), 0, depth_code(ddepth), src.cols, src.rows, radius, eps));
     dst = out;
 }
 
@@ -191,22 +209,17 @@ public:
     virtual void filter(const Mat& src, Mat& dst, int dDepth = -1) = 0;
 };
 
-// Holds its own copy of the guide (the caller's Mat may change or go away, as with cv's) and the parameters; the guide's
+// Holds its own copy of the guide (made first: the caller's Mat may change or go away, as with cv's) and the parameters; the guide's
 // statistics are recomputed per call -- they ride along in the coefficient kernel -- so the object saves no work.
 class GuidedFilterImpl : public GuidedFilter {
     Mat guide_;
     int radius_;
     double eps_;
 public:
-    GuidedFilterImpl(const Mat& guide, int radius, double eps) : radius_(radius), eps_(eps)
+    GuidedFilterImpl(const Mat& guide, int radius, double eps) : guide_(guide_copy("createGuidedFilter", guide)), radius_(radius), eps_(eps)
     {
-        if (guide.empty() || mat_depth(guide) != D8U || (mat_channels(guide) != 1 && mat_channels(guide) != 3))
-            throw Exception(ADF_EBADARG, "createGuidedFilter: guide must be a non-empty CV_8UC1 or CV_8UC3 image");
         if (radius < 0 || radius > ADF_GF_MAX_RADIUS) throw Exception(ADF_EBADARG, "createGuidedFilter: radius must lie in [0, 31]");
         if (!std::isfinite(eps) || !(eps > 0.0)) throw Exception(ADF_EBADARG, "createGuidedFilter: eps must be finite and > 0");
-        mat_create(guide_, guide.rows, guide.cols, D8U, mat_channels(guide));
-        for (int y = 0; y < guide.rows; y++)
-            std::memcpy(guide_.data + (size_t)mat_step(guide_) * y, guide.data + (size_t)mat_step(guide) * y, (size_t)guide.cols * mat_channels(guide));
     }
     void filter(const Mat& src, Mat& dst, int dDepth = -1) override { guidedFilter(guide_, src, dst, radius_, eps_, dDepth); }
 };
@@ -227,19 +240,12 @@ inline Ptr<GuidedFilter> createGuidedFilter(const Mat& guide, int radius, double
 enum EdgeAwareFiltersList { DTF_NC, DTF_IC, DTF_RF }; // cv's values
 inline void dt_filter(const Mat& guide, const Mat& src, Mat& dst, double sigmaSpatial, double sigmaColor, int mode, int numIters, int dDepth)
 {
-    if (src.empty() || mat_channels(src) != 1 || (mat_depth(src) != D8U && mat_depth(src) != D16S && mat_depth(src) != D32F))
-        throw Exception(ADF_EBADARG, "dtFilter: src must be a non-empty CV_8UC1, CV_16SC1 or CV_32FC1 image");
-    if (guide.empty() || mat_depth(guide) != D8U)
-        throw Exception(ADF_EBADARG, "dtFilter: guide must be a non-empty CV_8UC1 or CV_8UC3 image");
-    if (guide.rows != src.rows || guide.cols != src.cols) throw Exception(ADF_ESIZE, "dtFilter: guide must have src's size");
-    const int ddepth = dDepth == -1 ? mat_depth(src) : dDepth;
-    if (ddepth != D8U && ddepth != D16S && ddepth != D32F)
-        throw Exception(ADF_EBADARG, "dtFilter: dDepth must be -1, CV_8U, CV_16S or CV_32F");
-    auto code = [](int depth) { return depth == D8U ? ADF_8U : depth == D16S ? ADF_16S : ADF_32F; };
-    Mat out;                                                             // (dst may be src: the result lands in a new Mat)
-    mat_create(out, src.rows, src.cols, ddepth, 1);
-    check(adf_dt_filter_host(1, guide.data, mat_step(guide), 0, mat_channels(guide), src.data, mat_step(src), 0, code(mat_depth(src)),
-                             out.data, mat_step(out), 0, code(ddepth), src.cols, src.rows, sigmaSpatial, sigmaColor, mode, numIters));
+    filter_src("dtFilter", src);
+    filter_guide("dtFilter", "guide", guide, src);
+    const int ddepth = filter_ddepth("dtFilter", src, dDepth);
+    Mat out = filter_out(src, ddepth);
+    check(adf_dt_filter_host(1, guide.data, mat_step(guide), 0, mat_channels(guide), src.data, mat_step(src), 0, depth_code(mat_depth(src)),
+                             out.data, mat_step(out), 0, depth_code(ddepth), src.cols, src.rows, sigmaSpatial, sigmaColor, mode, numIters));
     dst = out;
 }
 inline void dtFilter(const Mat& guide, const Mat& src, Mat& dst, double sigmaSpatial, double sigmaColor, int mode = DTF_RF, int numIters = 3)
@@ -261,16 +267,11 @@ class DTFilterImpl : public DTFilter {
     int mode_, numIters_;
 public:
     DTFilterImpl(const Mat& guide, double sigmaSpatial, double sigmaColor, int mode, int numIters)
-        : sigmaSpatial_(sigmaSpatial), sigmaColor_(sigmaColor), mode_(mode), numIters_(numIters)
+        : guide_(guide_copy("createDTFilter", guide)), sigmaSpatial_(sigmaSpatial), sigmaColor_(sigmaColor), mode_(mode), numIters_(numIters)
     {
-        if (guide.empty() || mat_depth(guide) != D8U || (mat_channels(guide) != 1 && mat_channels(guide) != 3))
-            throw Exception(ADF_EBADARG, "createDTFilter: guide must be a non-empty CV_8UC1 or CV_8UC3 image");
         if (mode != DTF_RF) throw Exception(ADF_EBADARG, "createDTFilter: mode must be DTF_RF (DTF_NC and DTF_IC are not built)");
         if (!std::isfinite(sigmaSpatial) || !std::isfinite(sigmaColor)) throw Exception(ADF_EBADARG, "createDTFilter: the sigmas must be finite");
         if (numIters > ADF_DT_MAX_ITERS) throw Exception(ADF_EBADARG, "createDTFilter: numIters must not exceed 8");
-        mat_create(guide_, guide.rows, guide.cols, D8U, mat_channels(guide));
-        for (int y = 0; y < guide.rows; y++)
-            std::memcpy(guide_.data + (size_t)mat_step(guide_) * y, guide.data + (size_t)mat_step(guide) * y, (size_t)guide.cols * mat_channels(guide));
     }
     void filter(const Mat& src, Mat& dst, int dDepth = -1) override
     {
@@ -296,16 +297,14 @@ enum BorderTypes { BORDER_REPLICATE = 1, BORDER_REFLECT = 2, BORDER_WRAP = 3, BO
 inline void jointBilateralFilter(const Mat& joint, const Mat& src, Mat& dst, int d, double sigmaColor, double sigmaSpace,
                                  int borderType = BORDER_DEFAULT)
 {
-    if (src.empty() || mat_channels(src) != 1 || (mat_depth(src) != D8U && mat_depth(src) != D16S && mat_depth(src) != D32F))
-        throw Exception(ADF_EBADARG, "jointBilateralFilter: src must be a non-empty CV_8UC1, CV_16SC1 or CV_32FC1 image");
-    if (joint.empty() || mat_depth(joint) != D8U)
+    filter_src("jointBilateralFilter", src);
+    if (joint.empty() || mat_depth(joint) != D8U)              // (its own: joint == src is said between the two of filter_guide)
         throw Exception(ADF_EBADARG, "jointBilateralFilter: joint must be a non-empty CV_8UC1 or CV_8UC3 image (an empty or CV_32F joint is not built)");
     if (joint.data == src.data)
         throw Exception(ADF_EBADARG, "jointBilateralFilter: joint == src is cv::bilateralFilter, which is not built");
     if (joint.rows != src.rows || joint.cols != src.cols) throw Exception(ADF_ESIZE, "jointBilateralFilter: joint must have src's size");
-    const int depth = mat_depth(src) == D8U ? ADF_8U : mat_depth(src) == D16S ? ADF_16S : ADF_32F;
-    Mat out;                                                             // (dst may be src or joint: the result lands in a new Mat)
-    mat_create(out, src.rows, src.cols, mat_depth(src), 1);
+    const int depth = depth_code(mat_depth(src));
+    Mat out = filter_out(src, mat_depth(src));                           // (dst may be joint too)
     check(adf_joint_bilateral_filter_host(1, joint.data, mat_step(joint), 0, mat_channels(joint), src.data, mat_step(src), 0, depth,
                                           out.data, mat_step(out), 0, depth, src.cols, src.rows, d, sigmaColor, sigmaSpace, borderType));
     dst = out;
@@ -322,12 +321,9 @@ inline void jointBilateralFilter(const Mat& joint, const Mat& src, Mat& dst, int
 inline void rollingGuidanceFilter(const Mat& src, Mat& dst, int d = -1, double sigmaColor = 25, double sigmaSpace = 3, int numOfIter = 4,
                                   int borderType = BORDER_DEFAULT)
 {
-    if (src.empty() || mat_channels(src) != 1 || (mat_depth(src) != D8U && mat_depth(src) != D16S && mat_depth(src) != D32F))
-        throw Exception(ADF_EBADARG, "rollingGuidanceFilter: src must be a non-empty CV_8UC1, CV_16SC1 or CV_32FC1 image");
-    const int depth = mat_depth(src) == D8U ? ADF_8U : mat_depth(src) == D16S ? ADF_16S : ADF_32F;
-    Mat out;                                                             // (dst may be src: the result lands in a new Mat)
-    mat_create(out, src.rows, src.cols, mat_depth(src), 1);
-    check(adf_rolling_guidance_filter_host(1, src.data, mat_step(src), 0, out.data, mat_step(out), 0, depth, src.cols, src.rows, d,
+    filter_src("rollingGuidanceFilter", src);
+    Mat out = filter_out(src, mat_depth(src));
+    check(adf_rolling_guidance_filter_host(1, src.data, mat_step(src), 0, out.data, mat_step(out), 0, depth_code(mat_depth(src)), src.cols, src.rows, d,
                                            sigmaColor, sigmaSpace, numOfIter, borderType));
     dst = out;
 }
