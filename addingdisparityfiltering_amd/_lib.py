@@ -26,6 +26,7 @@ WMF_EXP, WMF_IV1, WMF_IV2, WMF_COS, WMF_JAC, WMF_OFF = range(6)    # cv::ximgpro
 WMF_WEIGHT_ONE, WMF_TABLE_LEVELS, WMF_MAX_RADIUS = 65536, 3 * 256 * 256, 31
 GF_MAX_RADIUS = 31    # ADF_GF_MAX_RADIUS
 DTF_NC, DTF_IC, DTF_RF, DT_MAX_ITERS = 0, 1, 2, 8    # ADF_DTF_*, ADF_DT_MAX_ITERS
+DT_NC_MAX_RADIUS = 127    # ADF_DT_NC_MAX_RADIUS
 JBF_MAX_RADIUS = 31    # ADF_JBF_MAX_RADIUS
 BORDER_REPLICATE, BORDER_REFLECT, BORDER_WRAP, BORDER_REFLECT_101 = 1, 2, 3, 4    # cv::BorderTypes; 1, 2 and 4 are built (ADF_BORDER_*)
 RGF_MAX_ITERS = 16    # ADF_RGF_MAX_ITERS
@@ -191,6 +192,10 @@ SYMBOLS = [
     ("adf_dt_rf_table_host", _i, [_d, _d, _i, _i, _vp]),
     ("adf_dt_filter_device", _i, _DT_DEV),
     ("adf_dt_filter_host", _i, _DT_DEV[:-3]),
+    ("adf_dt_window_filter_workspace_bytes", _sz, [_i, _i, _i]),
+    ("adf_dt_nc_radii_host", _i, [_d, _i, _vp]),
+    ("adf_dt_window_filter_device", _i, _DT_DEV),
+    ("adf_dt_window_filter_host", _i, _DT_DEV[:-3]),
     ("adf_jbf_tables_host", _i, [_i, _d, _d, _i, _vp, _vp, C.POINTER(_i)]),
     ("adf_joint_bilateral_filter_device", _i, _JBF_DEV),
     ("adf_joint_bilateral_filter_host", _i, _JBF_DEV[:-1]),

@@ -28,6 +28,7 @@ SOURCES = {
     "wmf_kernels.hip": [],
     "guided_filter_kernels.hip": [],
     "dt_filter_kernels.hip": [],
+    "dt_window_kernels.hip": [],
     "joint_bilateral_kernels.hip": [],
     "rolling_guidance_kernels.hip": [],
 }

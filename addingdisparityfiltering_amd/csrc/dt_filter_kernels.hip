@@ -28,10 +28,7 @@
 // The first row pass reads src in its depth, the last column pass's upward sweep writes dst in its depth; in between
 // the map is one float plane per map in the workspace.  LDS per workgroup: 24.5 KiB of tiles + the table row (row pass),
 // the table row (column pass).  Times and what bounds them: DESIGN.md, section 22.
-#include "adf_host.h"
-
-#include <cmath>
-#include <type_traits>
+#include "dt_common.h"
 
 #pragma clang fp contract(off)
 
@@ -56,20 +53,6 @@ struct DtArgs {
     float* plane;                                                        // [map][H][W]
     int W, H;
 };
-
-// A guide pixel as one word, and the L1 difference of two of them.
-template <int CH> __device__ __forceinline__ unsigned pixel(const uint8_t* g)
-{
-    unsigned v = g[0];
-    if constexpr (CH == 3) v |= (unsigned)g[1] << 8 | (unsigned)g[2] << 16;
-    return v;
-}
-template <int CH> __device__ __forceinline__ int l1(unsigned p, unsigned q)
-{
-    int s = abs((int)(p & 255) - (int)(q & 255));
-    if constexpr (CH == 3) s += abs((int)(p >> 8 & 255) - (int)(q >> 8 & 255)) + abs((int)(p >> 16 & 255) - (int)(q >> 16 & 255));
-    return s;
-}
 
 // The wave's index in its workgroup, as the scalar it is: what is addressed by it gets a scalar base.
 __device__ __forceinline__ int wave_of_group() { return __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)); }
@@ -201,18 +184,6 @@ __global__ void __launch_bounds__(RT) dt_row_kernel(DtArgs a, DtRow<CH> row)
     }
 }
 
-// dst = x in the output's depth: x, or rint (half to even) saturated; a NaN gives the depth's minimum.
-template <class T> __device__ __forceinline__ T convert(float x)
-{
-    if constexpr (std::is_same<T, float>::value) {
-        return x;
-    } else {
-        const float lo = std::is_same<T, uint8_t>::value ? 0.0f : -32768.0f, hi = std::is_same<T, uint8_t>::value ? 255.0f : 32767.0f;
-        const float v = rintf(x);
-        return !(v >= lo) ? (T)lo : v > hi ? (T)hi : (T)v;
-    }
-}
-
 // `count` steps of one column's sweep, step t at row first + dir * t: x = x + A[L(row, the row before it)] (carry - x),
 // handed to store(row, x).  Loads run PF rows ahead of the chain.  carry / gcarry: the value and guide pixel of the row
 // the sweep comes from, updated.
@@ -286,13 +257,6 @@ struct DtCall {                        // one call as its C entry point received
 
 constexpr const char* WHO = "dtFilter";
 
-// The parameters as DT.inl:79-83 clamps them.
-struct DtParams { float ss, sr; int N; };
-DtParams clamped(double sigma_spatial, double sigma_color, int num_iters)
-{
-    return DtParams{std::max(1.0f, (float)sigma_spatial), std::max(0.01f, (float)sigma_color), std::max(1, num_iters)};
-}
-
 // What the table depends on, refused alike by the calls and by adf_dt_rf_table_host.
 int params_check(const char* who, double sigma_spatial, double sigma_color, int num_iters, int guide_channels)
 {
@@ -309,8 +273,7 @@ void build_table(const DtParams& p, int ch, float* table)
     const int levels = levels_of(ch);
     const float k = p.ss / p.sr;
     for (int i = 1; i <= p.N; i++) {
-        const double sigma_h = (double)p.ss * std::pow(2.0, (double)(p.N - i)) / std::sqrt(std::pow(4.0, (double)p.N) - 1.0);
-        const double a = -std::sqrt(2.0 / 3.0) / sigma_h;
+        const double a = -std::sqrt(2.0 / 3.0) / sigma_h(p, i);
         for (int L = 0; L < levels; L++) {
             const float kl = k * (float)L;
             const float d = 1.0f + kl;

@@ -25,6 +25,8 @@ edge_filter.hpp (EF.hpp), over the C-ABI in include/adf_wls.h:
     createGuidedFilter(guide, radius, eps) -> GuidedFilter.filter(src, dst, dDepth)   EF.hpp:158, 143
     dtFilter(guide, src, sigmaSpatial, sigmaColor, mode, numIters)   EF.hpp:120  / dtfilter_cpu.hpp (DTF_RF only; the library's own exact definition)
     createDTFilter(guide, sigmaSpatial, sigmaColor, mode, numIters) -> DTFilter.filter(src, dst, dDepth)   EF.hpp:100, 80
+    dtWindowFilter(guide, src, sigmaSpatial, sigmaColor, mode, numIters)   the same call in mode DTF_NC, the reference's default (the library's own exact definition)
+    createDTWindowFilter(guide, sigmaSpatial, sigmaColor, mode, numIters) -> DTWindowFilter.filter(src, dst, dDepth)
     jointBilateralFilter(joint, src, d, sigmaColor, sigmaSpace, borderType, dDepth)   EF.hpp:317 / joint_bilateral_filter.cpp (8-bit joints; the library's own exact definition)
     rollingGuidanceFilter(src, d, sigmaColor, sigmaSpace, numOfIter, borderType)   EF.hpp:350 / rolling_guidance_filter.cpp (one channel; the library's own exact definition)
 
@@ -47,7 +49,7 @@ from ._lib import BM_COST_MCT_DENSE, BM_COST_MCT_SPARSE, BM_COST_CENSUS_CS  # no
 from ._lib import SGBM_RIGHT_MATCHER, SGBM_RIGHT_FROM_VOLUME  # noqa: F401  (re-exported)
 from ._lib import WMF_EXP, WMF_IV1, WMF_IV2, WMF_COS, WMF_JAC, WMF_OFF  # noqa: F401  (cv's WMFWeightType; EXP and OFF are built)
 from ._lib import GF_MAX_RADIUS  # noqa: F401  (re-exported)
-from ._lib import DTF_NC, DTF_IC, DTF_RF, DT_MAX_ITERS  # noqa: F401  (cv's EdgeAwareFiltersList; DTF_RF is built)
+from ._lib import DTF_NC, DTF_IC, DTF_RF, DT_MAX_ITERS, DT_NC_MAX_RADIUS  # noqa: F401  (cv's EdgeAwareFiltersList; DTF_RF and, under dtWindowFilter, DTF_NC are built)
 from ._lib import RGF_MAX_ITERS  # noqa: F401  (re-exported)
 from ._lib import JBF_MAX_RADIUS, BORDER_REPLICATE, BORDER_REFLECT, BORDER_WRAP, BORDER_REFLECT_101  # noqa: F401  (cv's BorderTypes; 1, 2 and 4 are built)
 from ._lib import AdfError, PATH_CONF_BAND, PATH_FUSED_FIRST_PASS, PATH_MERGED_PREP, PATH_ROW_WEIGHTS_GUIDE, PATH_SCALED_FUSED, PATH_SCALED_HALF, Rect, SOLVER_EXACT, SOLVER_WAVE  # noqa: F401  (re-exported)
@@ -1456,8 +1458,8 @@ def dtFilter(guide, src, sigmaSpatial, sigmaColor, mode=DTF_RF, numIters=3, dDep
         guide         uint8, (H,W) or (H,W,3); with a batch (N,H,W) or (N,H,W,3)
         src           uint8, int16 or float32, (H,W) or a batch (N,H,W), one channel
         sigmaSpatial  clamped to >= 1;  sigmaColor  clamped to >= 0.01 (in grey levels of the 0..255 guide); both finite
-        mode          DTF_RF.  The reference's default is DTF_NC, which this build refuses, as it does DTF_IC: the default
-                      HERE is DTF_RF
+        mode          DTF_RF.  The reference's default is DTF_NC, which this call refuses, as it does DTF_IC: the default
+                      HERE is DTF_RF.  DTF_NC is dtWindowFilter
         numIters      clamped to >= 1, at most 8 (DT_MAX_ITERS)
         dDepth        -1 = src's depth, or CV_8U, CV_16S, CV_32F: integer outputs are rounded half to even and saturated
         dst           None, or an array / tensor of that depth and src's shape that overlaps neither input
@@ -1501,6 +1503,89 @@ def createDTFilter(guide, sigmaSpatial, sigmaColor, mode=DTF_RF, numIters=3):
     """EF.hpp:100: a DTFilter on `guide` (held by reference, not copied).  The default mode is DTF_RF, not the reference's
     DTF_NC, which is not built."""
     return DTFilter(guide, sigmaSpatial, sigmaColor, mode, numIters)
+
+
+# ---------------------------------------------------------------------------------------------
+# cv::ximgproc::dtFilter / createDTFilter / DTFilter in mode DTF_NC, the reference's default, under names of their own
+# (dtFilter above is pinned to refuse DTF_NC), in the library's own exact definition (include/adf_wls.h;
+# csrc/dt_window_kernels.hip; the direct statement is tests/dt_window_ref.py).
+# ---------------------------------------------------------------------------------------------
+_DTW = "dtWindowFilter"
+
+
+def _dtw_mode(who, mode):
+    """DTF_NC; DTF_RF is sent to dtFilter, DTF_IC refused as not built."""
+    if isinstance(mode, int) and mode == DTF_RF:
+        raise AdfError(_lib.ADF_EBADARG, "%s: DTF_RF is dtFilter's mode; mode must be DTF_NC" % who)
+    return _choice(who, mode, accepted=(DTF_NC,), not_built={DTF_IC: "DTF_IC"}, must="mode must be DTF_NC", are="DTF_NC is")
+
+
+def dtNcRadii(sigmaSpatial, numIters=3):
+    """The radii r_1 .. r_N of dtWindowFilter's iterations exactly as its calls form them (adf_dt_nc_radii_host):
+    float32, (max(1, numIters),); iteration i averages over the pixels within r_i of each pixel in the transformed domain,
+    at most floor(r_i) to either side.  Host only: no device is touched."""
+    n = max(1, int(numIters))
+    if n > DT_MAX_ITERS:     # (the library refuses it too; the array is sized first)
+        raise AdfError(_lib.ADF_EBADARG, "dtNcRadii: numIters must not exceed %d" % DT_MAX_ITERS)
+    radii = np.empty(n, np.float32)
+    _lib.check(_lib.lib().adf_dt_nc_radii_host(float(sigmaSpatial), int(numIters), radii.ctypes.data))
+    return radii
+
+
+def dtWindowFilterWorkspaceBytes(n, H, W):
+    """Bytes of device workspace dtWindowFilter needs for n maps of H x W (adf_dt_window_filter_workspace_bytes): two
+    float planes per map, between which the passes carry the map."""
+    return int(_lib.lib().adf_dt_window_filter_workspace_bytes(int(n), int(W), int(H)))
+
+
+def dtWindowFilter(guide, src, sigmaSpatial, sigmaColor, mode=DTF_NC, numIters=3, dDepth=-1, dst=None, workspace=None):
+    """cv::ximgproc::dtFilter(guide, src, dst, sigmaSpatial, sigmaColor, mode, numIters) in mode DTF_NC -- the
+    reference's default --, in the library's own definition (include/adf_wls.h): numIters times, every pixel becomes the
+    mean of the map over a window along its row, then along its column; the window holds the pixels whose distance in the
+    transformed domain -- pixel steps plus sigmaSpatial / sigmaColor times the guide's L1 differences walked over -- stays
+    within the iteration's radius (dtNcRadii).  Bit-exact against tests/dt_window_ref.py fed with dtNcRadii.
+
+        guide, src, sigmaColor, numIters, dDepth, dst   as dtFilter's
+        sigmaSpatial  clamped to >= 1, finite, and small enough for the first radius to stay within 127 pixels
+                      (DT_NC_MAX_RADIUS): up to 84 at numIters 3
+        mode          DTF_NC.  DTF_RF is dtFilter's; DTF_IC is not built
+
+    Everything else -- invalid values, multi-channel sources, tensors and streams, `workspace` (here at least
+    dtWindowFilterWorkspaceBytes(...) bytes), host arrays -- is as with dtFilter.  Returns dst."""
+    if guide is None or src is None:
+        raise AdfError(_lib.ADF_EBADARG, "%s: guide and src must not be empty" % _DTW)
+    m = _dtw_mode(_DTW, mode)
+    S, G, _, D, dst, dt, ddt = _filter_images(_DTW, src, dst, dDepth, guide)
+    args = (S.n, G.ptr, G.stride, G.pair_stride, G.c, S.ptr, S.stride, S.pair_stride, _DEPTH[dt], D.ptr, D.stride, D.pair_stride,
+            _DEPTH[ddt], S.w, S.h, float(sigmaSpatial), float(sigmaColor), m, int(numIters))
+    _filter_call("adf_dt_window_filter", S, args, _workspace(_DTW, S, workspace))
+    return dst
+
+
+class DTWindowFilter:
+    """cv::ximgproc::DTFilter (EF.hpp:66-84) in mode DTF_NC: holds the guide and the parameters; filter(src) is
+    dtWindowFilter(guide, src, ...).  There is no init stage -- the distances are summed from the guide in every pass -- so
+    the object saves no work: it is the reference's interface, with the reference's default mode."""
+
+    def __init__(self, guide, sigmaSpatial, sigmaColor, mode=DTF_NC, numIters=3):
+        if guide is None:
+            raise AdfError(_lib.ADF_EBADARG, "%s: guide must not be empty" % _DTW)
+        m = _dtw_mode(_DTW, mode)
+        if not (math.isfinite(float(sigmaSpatial)) and math.isfinite(float(sigmaColor))):
+            raise AdfError(_lib.ADF_EBADARG, "%s: sigmaSpatial and sigmaColor must be finite" % _DTW)
+        if int(numIters) > DT_MAX_ITERS:
+            raise AdfError(_lib.ADF_EBADARG, "%s: numIters must not exceed %d" % (_DTW, DT_MAX_ITERS))
+        if not dtNcRadii(sigmaSpatial, numIters)[0] < DT_NC_MAX_RADIUS + 1:
+            raise AdfError(_lib.ADF_EBADARG, "%s: the first iteration's radius exceeds %d pixels" % (_DTW, DT_NC_MAX_RADIUS))
+        self._guide, self._ss, self._sr, self._mode, self._iters = guide, float(sigmaSpatial), float(sigmaColor), m, int(numIters)
+
+    def filter(self, src, dst=None, dDepth=-1, workspace=None):
+        return dtWindowFilter(self._guide, src, self._ss, self._sr, self._mode, self._iters, dDepth, dst, workspace)
+
+
+def createDTWindowFilter(guide, sigmaSpatial, sigmaColor, mode=DTF_NC, numIters=3):
+    """EF.hpp:100 with the reference's default mode: a DTWindowFilter on `guide` (held by reference, not copied)."""
+    return DTWindowFilter(guide, sigmaSpatial, sigmaColor, mode, numIters)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -1113,7 +1113,9 @@ int adf_guided_filter_host(int n_maps,
  *   - guide: 8-bit, guide_channels 1 or 3 (interleaved), the size of src.
  *   - src: ONE channel, depth ADF_8U, ADF_16S or ADF_32F.
  *   - dst: one channel, depth dst_depth, any of the three, independent of src's (cv's dDepth).
- *   - mode: ADF_DTF_RF.  ADF_DTF_NC and ADF_DTF_IC (windows of variable width in the transformed domain) are NOT built.
+ *   - mode: ADF_DTF_RF.  These entry points refuse ADF_DTF_NC and ADF_DTF_IC (windows of variable width in the transformed
+ *     domain) as not built: ADF_DTF_NC lives under its own names, adf_dt_window_filter_* (the next section); ADF_DTF_IC is
+ *     NOT built.
  * Parameters, as DT.inl:79-83 clamps them: ss = max(1.0f, (float)sigmaSpatial), sr = max(0.01f, (float)sigmaColor),
  * N = max(1, numIters).
  * Distance (DT.hpp:115-118).  k = ss / sr in float32.  For the L1 difference L of two guide pixels (the sum over the
@@ -1139,7 +1141,7 @@ int adf_guided_filter_host(int n_maps,
  *   - the weights are not a plane: they are one table read per step, recomputed from the guide in every sweep, so there
  *     is no init stage (DTFilter keeps the guide and the parameters);
  *   - one-channel sources only (callers split them); guides of 1 or 3 channels of 8 bits;
- *   - DTF_NC and DTF_IC are refused.
+ *   - DTF_NC and DTF_IC are refused here (DTF_NC is adf_dt_window_filter_*).
  * Refused: mode ADF_DTF_NC or ADF_DTF_IC (not built) and any other mode but ADF_DTF_RF, sigmas that are not finite (as
  * double or as float32), numIters above ADF_DT_MAX_ITERS = 8, an unknown depth or guide_channels, NULL guide / src / dst,
  * n_maps, W or H below 1, bases or strides not aligned to the depth (2 bytes for ADF_16S, 4 for ADF_32F), dst
@@ -1152,7 +1154,7 @@ int adf_guided_filter_host(int n_maps,
  * hipGraph.
  * _device: device pointers on the current HIP device, asynchronous on `stream`.  _host: host pointers; copies, runs and
  * synchronises. */
-#define ADF_DTF_NC 0 /* cv::ximgproc::DTF_NC: not built */
+#define ADF_DTF_NC 0 /* cv::ximgproc::DTF_NC: adf_dt_window_filter_* (adf_dt_filter_* refuses it as not built) */
 #define ADF_DTF_IC 1 /* cv::ximgproc::DTF_IC: not built */
 #define ADF_DTF_RF 2 /* cv::ximgproc::DTF_RF */
 #define ADF_DT_MAX_ITERS 8
@@ -1169,6 +1171,77 @@ int adf_dt_filter_host(int n_maps,
                        const void* src, ptrdiff_t src_stride, ptrdiff_t src_map_stride, int src_depth,
                        void* dst, ptrdiff_t dst_stride, ptrdiff_t dst_map_stride, int dst_depth,
                        int W, int H, double sigma_spatial, double sigma_color, int mode, int num_iters);
+
+/* ---------------- domain transform filter, normalized convolution (cv::ximgproc::dtFilter, mode DTF_NC) ----------------
+ * The reference's DEFAULT mode (dtFilter(..., int mode = DTF_NC, ...), createDTFilter likewise; EF.hpp:100-120, DT.hpp,
+ * DT.inl): per iteration every pixel becomes the plain mean of the map over a window along its row, then along its
+ * column, the window being the pixels within a radius of it in the transformed domain -- the pixel distance plus the
+ * guide's differences walked over.  No sequential chain along a scanline: every pixel finds its own window.  It arrives
+ * under names of its own because adf_dt_filter_* is pinned to refuse ADF_DTF_NC; a binding of the reference routes
+ * mode == DTF_NC to adf_dt_window_filter_* and mode == DTF_RF to adf_dt_filter_* (INTEGRATION.md, section 2.13).
+ *
+ * This is the library's OWN definition.  The result is bit-exact against the direct NumPy statement
+ * tests/dt_window_ref.py fed with adf_dt_nc_radii_host, and identical from run to run.
+ *
+ * Inputs: those of adf_dt_filter_* -- n_maps maps of W x H; guide 8-bit with 1 or 3 interleaved channels; src ONE channel
+ * of depth ADF_8U, ADF_16S or ADF_32F; dst one channel of depth dst_depth, independent of src's.  mode: ADF_DTF_NC.
+ * Parameters, clamped as DT.inl:79-83 does and as adf_dt_filter_* does: ss = max(1.0f, (float)sigmaSpatial),
+ * sr = max(0.01f, (float)sigmaColor), N = max(1, numIters), N <= ADF_DT_MAX_ITERS.  k = ss / sr in float32.
+ * Radii (DT.hpp:120-128).  sigmaH_i = ss * 2^(N-i) / sqrt(4^N - 1) in double, r_i = (float)(3.0 * sigmaH_i), i = 1..N;
+ *   R_i = floor(r_i).  adf_dt_nc_radii_host writes r_1 .. r_N exactly as the calls form them.  Host only -- no device is
+ *   touched.
+ * Distance, local and with one rounding.  For pixels a <= b of one scanline S(a, b) is the exact integer sum of the
+ *   guide's L1 differences (the sum over the channels of |difference|: 0..255 per step for 1 channel, 0..765 for 3) over the
+ *   steps between them, and D(a, b) = (float)(b - a) + k * (float)S(a, b): the two conversions, the product and the sum
+ *   each rounded to float32 (no FMA).  D is non-decreasing in b - a, and D >= b - a.
+ * Window of pixel j in a scanline of n pixels (the asymmetry is the reference's: getLeftBound uses >=, getRightBound <,
+ *   DT.hpp:248-260):
+ *   - lb is the smallest a in [0, j] with D(a, j) <= r_i;
+ *   - rb is the largest b in [j, n-1] with b == j or D(j, b) < r_i.
+ *   The window is contiguous, has at most 2 R_i + 1 pixels and is clipped by the ends of the scanline.
+ * Pass.  y[j] = (x[lb] + x[lb+1] + ... + x[rb]) / (float)(rb - lb + 1): the sum runs left to right in float32, starting
+ *   from x[lb], and is followed by one IEEE float32 division.  A pass reads one plane and writes another.
+ * Call.  x = (float)src; for i = 1..N: every row with r_i, then every column with r_i (DT.inl:157-163).
+ * Output, as in DTF_RF.  dst = x for ADF_32F; rint(x) (half to even) saturated to the depth for ADF_8U / ADF_16S (a NaN
+ *   gives the depth's minimum).
+ * Limit.  R_1 <= ADF_DT_NC_MAX_RADIUS = 127, else ADF_EBADARG.  It admits the reference's own perf configuration
+ *   (sigmaSpatial = 80 at 3 iterations: r_1 = 120.9), bounds the halo a tile carries, and keeps every partial sum of the
+ *   first pass over an ADF_16S map an integer below 2^24: that pass is exact, and an integer-valued constant map comes
+ *   back exactly.
+ * Deviations from the reference, all deliberate:
+ *   - the reference compares float32 running sums of the distance along the whole scanline (idist[], DT.inl:484-491),
+ *     which carry up to W accumulated roundings; ours is local, has one rounding and is translation-invariant;
+ *   - the reference differences a float32 running integral of the row (integrateRow, DT.inl:211-221), which on a 4K row
+ *     of 16-bit disparities passes 2^24 and loses integer bits; ours sums the window directly;
+ *   - one-channel sources only (callers split them); guides of 1 or 3 channels of 8 bits;
+ *   - DTF_IC stays unbuilt.
+ *   Measured against the reference's arithmetic restated in NumPy (tests/test_dt_window_ref.py): DESIGN.md, section 26.
+ * Refused: mode ADF_DTF_IC (not built), ADF_DTF_RF (it is adf_dt_filter_*'s) and any other mode but ADF_DTF_NC; R_1 above
+ * ADF_DT_NC_MAX_RADIUS; and everything adf_dt_filter_* refuses, with the same status -- sigmas that are not finite (as
+ * double or as float32), numIters above ADF_DT_MAX_ITERS, an unknown depth or guide_channels, NULL guide / src / dst,
+ * n_maps, W or H below 1, bases or strides not aligned to the depth, dst overlapping guide or src (all ADF_EBADARG); W*H at
+ * or above 2^31, strides smaller than a row, destination maps of a batch that overlap each other, a workspace that is too
+ * small (ADF_ESIZE).  All of this is checked before a device is touched.
+ * Workspace: the map between the passes, TWO float planes per map -- adf_dt_window_filter_workspace_bytes(n_maps, W, H)
+ * bytes of 4-byte aligned device memory (0 for arguments the calls refuse).  The rules are adf_dt_filter_*'s: NULL takes
+ * library scratch from the process-wide cache; a caller-supplied workspace makes the call capturable into a hipGraph (2 N
+ * launches in one chain, no device table).
+ * _device: device pointers on the current HIP device, asynchronous on `stream`.  _host: host pointers; copies, runs and
+ * synchronises. */
+#define ADF_DT_NC_MAX_RADIUS 127
+size_t adf_dt_window_filter_workspace_bytes(int n_maps, int W, int H);
+int adf_dt_nc_radii_host(double sigma_spatial, int num_iters, float* radii);
+int adf_dt_window_filter_device(int n_maps,
+                                const uint8_t* guide, ptrdiff_t guide_stride, ptrdiff_t guide_map_stride, int guide_channels,
+                                const void* src, ptrdiff_t src_stride, ptrdiff_t src_map_stride, int src_depth,
+                                void* dst, ptrdiff_t dst_stride, ptrdiff_t dst_map_stride, int dst_depth,
+                                int W, int H, double sigma_spatial, double sigma_color, int mode, int num_iters,
+                                void* workspace, size_t workspace_bytes, void* stream);
+int adf_dt_window_filter_host(int n_maps,
+                              const uint8_t* guide, ptrdiff_t guide_stride, ptrdiff_t guide_map_stride, int guide_channels,
+                              const void* src, ptrdiff_t src_stride, ptrdiff_t src_map_stride, int src_depth,
+                              void* dst, ptrdiff_t dst_stride, ptrdiff_t dst_map_stride, int dst_depth,
+                              int W, int H, double sigma_spatial, double sigma_color, int mode, int num_iters);
 
 /* ---------------- joint bilateral filter (cv::ximgproc::jointBilateralFilter) ----------------
  * jointBilateralFilter(joint, src, dst, d, sigmaColor, sigmaSpace, borderType) (EF.hpp:317;

@@ -234,8 +234,8 @@ inline Ptr<GuidedFilter> createGuidedFilter(const Mat& guide, int radius, double
 // through the library's host entry, in mode DTF_RF and the library's own definition (adf_dt_filter_* in adf_wls.h: the
 // recurrence in the reference's order, a feedback table with one rounding per entry).  guide: CV_8UC1 or CV_8UC3; src:
 // CV_8UC1, CV_16SC1 or CV_32FC1 of its size (multi-channel sources are not built: split them); dDepth: -1 (src's depth),
-// CV_8U, CV_16S or CV_32F.  DTF_NC and DTF_IC are not built and refused -- so the default mode HERE is DTF_RF, not the
-// reference's DTF_NC.  dst may be src.  The filter is not blind to a matcher's invalid value: run weightedMedianFilter
+// CV_8U, CV_16S or CV_32F.  DTF_NC and DTF_IC are refused here as not built -- so the default mode HERE is DTF_RF, not the
+// reference's DTF_NC, which is dtWindowFilter / createDTWindowFilter below.  dst may be src.  The filter is not blind to a matcher's invalid value: run weightedMedianFilter
 // with ignoreValue first.
 enum EdgeAwareFiltersList { DTF_NC, DTF_IC, DTF_RF }; // cv's values
 inline void dt_filter(const Mat& guide, const Mat& src, Mat& dst, double sigmaSpatial, double sigmaColor, int mode, int numIters, int dDepth)
@@ -282,6 +282,61 @@ public:
 inline Ptr<DTFilter> createDTFilter(const Mat& guide, double sigmaSpatial, double sigmaColor, int mode = DTF_RF, int numIters = 3)
 {
     return Ptr<DTFilter>(new DTFilterImpl(guide, sigmaSpatial, sigmaColor, mode, numIters));
+}
+
+// cv::ximgproc::dtFilter / createDTFilter / DTFilter::filter in mode DTF_NC -- the reference's default -- on host Mats
+// through the library's host entry, under names of their own (dtFilter above keeps refusing DTF_NC), in the library's own
+// definition (adf_dt_window_filter_* in adf_wls.h: a local distance with one rounding, every window summed directly).
+// guide, src, dDepth and dst are dtFilter's.  The default mode is DTF_NC, as the reference's; DTF_RF is dtFilter's and
+// DTF_IC is not built: both are refused, and so is a sigmaSpatial whose first radius exceeds ADF_DT_NC_MAX_RADIUS pixels
+// (84 at 3 iterations still passes).  A binding of the reference routes mode == DTF_NC here and mode == DTF_RF to dtFilter.
+inline void dt_window_filter(const Mat& guide, const Mat& src, Mat& dst, double sigmaSpatial, double sigmaColor, int mode, int numIters, int dDepth)
+{
+    filter_src("dtWindowFilter", src);
+    filter_guide("dtWindowFilter", "guide", guide, src);
+    const int ddepth = filter_ddepth("dtWindowFilter", src, dDepth);
+    Mat out = filter_out(src, ddepth);
+    check(adf_dt_window_filter_host(1, guide.data, mat_step(guide), 0, mat_channels(guide), src.data, mat_step(src), 0, depth_code(mat_depth(src)),
+                                    out.data, mat_step(out), 0, depth_code(ddepth), src.cols, src.rows, sigmaSpatial, sigmaColor, mode, numIters));
+    dst = out;
+}
+inline void dtWindowFilter(const Mat& guide, const Mat& src, Mat& dst, double sigmaSpatial, double sigmaColor, int mode = DTF_NC, int numIters = 3)
+{
+    dt_window_filter(guide, src, dst, sigmaSpatial, sigmaColor, mode, numIters, -1);
+}
+
+class DTWindowFilter {
+public:
+    virtual ~DTWindowFilter() {}
+    virtual void filter(const Mat& src, Mat& dst, int dDepth = -1) = 0;
+};
+
+// Holds its own copy of the guide (the caller's Mat may change or go away, as with cv's) and the parameters.  There is no
+// init stage: the distances are summed from the guide in every pass.
+class DTWindowFilterImpl : public DTWindowFilter {
+    Mat guide_;
+    double sigmaSpatial_, sigmaColor_;
+    int mode_, numIters_;
+public:
+    DTWindowFilterImpl(const Mat& guide, double sigmaSpatial, double sigmaColor, int mode, int numIters)
+        : guide_(guide_copy("createDTWindowFilter", guide)), sigmaSpatial_(sigmaSpatial), sigmaColor_(sigmaColor), mode_(mode), numIters_(numIters)
+    {
+        if (mode != DTF_NC) throw Exception(ADF_EBADARG, "createDTWindowFilter: mode must be DTF_NC (DTF_RF is createDTFilter's, DTF_IC is not built)");
+        if (!std::isfinite(sigmaSpatial) || !std::isfinite(sigmaColor)) throw Exception(ADF_EBADARG, "createDTWindowFilter: the sigmas must be finite");
+        if (numIters > ADF_DT_MAX_ITERS) throw Exception(ADF_EBADARG, "createDTWindowFilter: numIters must not exceed 8");
+        float radii[ADF_DT_MAX_ITERS];
+        check(adf_dt_nc_radii_host(sigmaSpatial, numIters, radii));
+        if (!(radii[0] < (float)(ADF_DT_NC_MAX_RADIUS + 1))) throw Exception(ADF_EBADARG, "createDTWindowFilter: the first iteration's radius exceeds 127 pixels");
+    }
+    void filter(const Mat& src, Mat& dst, int dDepth = -1) override
+    {
+        dt_window_filter(guide_, src, dst, sigmaSpatial_, sigmaColor_, mode_, numIters_, dDepth);
+    }
+};
+
+inline Ptr<DTWindowFilter> createDTWindowFilter(const Mat& guide, double sigmaSpatial, double sigmaColor, int mode = DTF_NC, int numIters = 3)
+{
+    return Ptr<DTWindowFilter>(new DTWindowFilterImpl(guide, sigmaSpatial, sigmaColor, mode, numIters));
 }
 
 // cv::ximgproc::jointBilateralFilter(joint, src, dst, d, sigmaColor, sigmaSpace, borderType) (EF.hpp:317) on host Mats
