@@ -14,6 +14,7 @@ ADF_OK, ADF_EBADARG, ADF_ESIZE, ADF_EHIP, ADF_ENOMEM, ADF_ENODEV = range(6)
 SOLVER_EXACT, SOLVER_WAVE = 0, 1
 PATH_CONF_BAND, PATH_FUSED_FIRST_PASS, PATH_MERGED_PREP, PATH_SCALED_FUSED, PATH_SCALED_HALF = 1, 2, 4, 8, 16    # adf_wls_get_last_path bits (include/adf_wls.h)
 PATH_ROW_WEIGHTS_GUIDE = 32    # adf_wls_get_last_solver_path bit
+HANDOFF_PAIR_PLANE, HANDOFF_IMAGE, HANDOFF_IMAGE_PAIR_TAIL = 0, 1, 2   # adf_wls_get_last_handoff
 DEPTH_8U, DEPTH_16S, DEPTH_32S, DEPTH_32F = 0, 3, 4, 5
 SGBM_COST_BT, SGBM_COST_CENSUS_DENSE, SGBM_COST_CENSUS_SPARSE = 0, 1, 2    # adf_sgbm_set_cost (include/adf_wls.h)
 BM_COST_SAD, BM_COST_CENSUS_DENSE, BM_COST_CENSUS_SPARSE = 0, 1, 2    # adf_bm_set_cost (the census values equal SGBM_COST_CENSUS_*)
@@ -100,6 +101,7 @@ SYMBOLS = [
     ("adf_wls_get_last_solver", _i, [_vp, C.POINTER(_i)]),
     ("adf_wls_get_last_path", _i, [_vp, C.POINTER(_i)]),
     ("adf_wls_get_last_solver_path", _i, [_vp, C.POINTER(_i)]),
+    ("adf_wls_get_last_handoff", _i, [_vp, C.POINTER(_i)]),
     ("adf_wls_filter_device", _i, _FILTER_DEV),
     ("adf_wls_filter_host", _i, _FILTER_DEV[:-1]),
     ("adf_wls_filter_scaled_device", _i, _FILTER_SCALED_DEV),

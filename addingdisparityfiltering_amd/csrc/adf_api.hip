@@ -139,7 +139,7 @@ static void set_final_out(Args& a, const FinalOut& fo)
 // first row pass forms its right-hand sides from.
 static int run_passes(bool wave, const Geom& g, const SolvePlanes& p, int n_rhs, float lambda, float atten, int num_iter,
                       const FinalOut& fo, int n_pairs, hipStream_t st, Profiler* prof = nullptr,
-                      const FusedInputs* fuse = nullptr, const GuideWeights* gw = nullptr)
+                      const FusedInputs* fuse = nullptr, const GuideWeights* gw = nullptr, float* image = nullptr, int image_m = 0)
 {
     const double px = (double)g.rw * g.rh * n_pairs;
     float lam = lambda;
@@ -164,6 +164,12 @@ static int run_passes(bool wave, const Geom& g, const SolvePlanes& p, int n_rhs,
             v.C = p.CV; v.U0 = p.A0; v.U1 = p.A1;
             v.nscan = g.rw; v.len = g.rh; v.pitch = g.pw; v.plane = g.plane; v.lambda = lam;
             if (last) set_final_out(v, fo);
+            // the last hand-off: nobody but the last column pass reads what the last row pass writes, so that pass stores
+            // the column pass's register image instead of the pair plane (same bytes: 8 written, 8 read per pixel)
+            if (image && last && it > 0) {
+                h.image = v.image = image; h.image_m = v.image_m = image_m;
+                h.image_plane = v.image_plane = wave_image_floats(g.pw, image_m);
+            }
             {
                 ProfScope ps(prof, fused ? K_PASS_H_FIRST : K_PASS_H, hb, hb, st);
                 HIP_TRY(launch_wave_hpass(h, n_rhs, n_pairs, st));             // FGS.cpp:209
@@ -205,6 +211,14 @@ struct ConfResize {
     bool band_map;                        // the band kernel made them: zero outside the ROI (DF.cpp:187-190)
     int n_pairs;
 };
+
+// The smallest chunk of a call, in ROI pixels, whose last hand-off takes the register image.  Measured on batches of
+// 1 ... 64 pairs of 3840 x 2160 (ROI 3584 x 2160), both forms alternating in one process (tools/last_handoff_time.py,
+// profiles/last_handoff_ab.txt, "chunk size series"): up to 8 pairs the row pass's scattered lines cost what the column
+// pass's loads gain (the two passes' sum within +-1 %, the call 0.3-1.6 % slower with the image); 12 pairs is the
+// smallest batch at which the sum is lower outside both forms' spread and the call is not slower.  Other geometries are
+// taken by their pixel count: estimated, not measured.
+constexpr long long HANDOFF_IMAGE_MIN_PX = 12LL * 3584 * 2160;
 
 struct adf_wls {
     int device = 0;
@@ -250,6 +264,10 @@ struct adf_wls {
     bool conf_band = true;   // ADF_CONF_BAND=0: the two-kernel confidence stage (A/B measurements)
     bool merge_small = true; // ADF_MERGE_SMALL=0: never the merged preparation launch (A/B measurements)
     bool row_weights_guide = true; // ADF_ROW_WEIGHTS_GUIDE=0: the row passes always read the Chor plane (A/B measurements, tests)
+    bool handoff_image = true;     // ADF_LAST_HANDOFF_IMAGE=0: the last row pass always writes the pair plane (A/B measurements, the tests' reference)
+    // ... and the smallest chunk, in ROI pixels, whose last hand-off takes the image (ADF_LAST_HANDOFF_MIN_PX: tests only)
+    long long handoff_min_px = HANDOFF_IMAGE_MIN_PX;
+    int last_handoff = ADF_HANDOFF_PAIR_PLANE;   // the form the last call's last hand-off took (adf_wls_get_last_handoff)
     // HIP maps the streams of ONE priority level onto a small pool of hardware queues (4 by default) and two streams that
     // share a queue run one after the other: a side stream of the caller's priority lost the overlap for about one caller
     // stream in four (tools/batch_cpp.cpp: 13.5-13.6 ms per 64 x 4K call instead of 12.8-13.2).  Each priority level has a pool
@@ -295,6 +313,8 @@ extern "C" int adf_wls_create(adf_wls_t** out, int use_confidence, int l, int r,
     if (const char* e = getenv("ADF_SCALED_FUSE")) h->scaled_fuse = atoi(e) != 0;  // measurement knob
     if (const char* e = getenv("ADF_ROW_WEIGHTS_GUIDE")) h->row_weights_guide = atoi(e) != 0;   // measurement knob
     if (const char* e = getenv("ADF_LO_HALF")) h->scaled_half = atoi(e) != 0;
+    if (const char* e = getenv("ADF_LAST_HANDOFF_IMAGE")) h->handoff_image = atoi(e) != 0;   // measurement knob
+    if (const char* e = getenv("ADF_LAST_HANDOFF_MIN_PX")) h->handoff_min_px = atoll(e);      // test knob
     if (const char* e = getenv("ADF_MERGE_SMALL")) h->merge_small = atoi(e) != 0;   // measurement knob
     *out = h;
     return ADF_OK;
@@ -341,6 +361,7 @@ extern "C" int adf_wls_get_solver(const adf_wls_t* h, int* v) { NEED_HANDLE(h); 
 extern "C" int adf_wls_get_last_solver(const adf_wls_t* h, int* v) { NEED_HANDLE(h); if (v) *v = h->last_solver; return ADF_OK; }
 extern "C" int adf_wls_get_last_path(const adf_wls_t* h, int* v) { NEED_HANDLE(h); if (v) *v = h->last_path; return ADF_OK; }
 extern "C" int adf_wls_get_last_solver_path(const adf_wls_t* h, int* v) { NEED_HANDLE(h); if (v) *v = h->last_solver_path; return ADF_OK; }
+extern "C" int adf_wls_get_last_handoff(const adf_wls_t* h, int* v) { NEED_HANDLE(h); if (v) *v = h->last_handoff; return ADF_OK; }
 
 extern "C" int adf_wls_get_device(const adf_wls_t* h, int* device) { NEED_HANDLE(h); if (device) *device = h->device; return ADF_OK; }
 extern "C" int adf_wls_get_roi(const adf_wls_t* h, adf_rect* roi) { NEED_HANDLE(h); if (roi) *roi = h->roi; return ADF_OK; }
@@ -375,13 +396,16 @@ static int ensure_conf_planes(adf_wls* h, const Geom& g, int n_pairs, hipStream_
 // Row pitch (elements) of the int16 planes q a call on float maps keeps for its confidence kernels: 16-byte rows.
 static int quant_pitch(int W) { return round_up(W, 8); }
 
-static size_t wls_pair_ws_bytes(const Geom& g, bool conf, bool wave, bool disc_maps, bool quant_planes)
+static size_t wls_pair_ws_bytes(const Geom& g, bool conf, bool wave, bool disc_maps, bool quant_planes, int image_m = 0, bool image_in_chor = false)
 {
     // exact: ROI planes CH CV D F0 A0 B0 (+ F1 A1 B1 with confidence); wave: CH CV A0 (+ A1), in place
     // full frames: cL cR, the depth-discontinuity maps (not needed when the one-sweep confidence kernel runs)
     size_t planes = wave ? (conf ? 4 : 3) : (conf ? 9 : 6);
     // float maps (adf_wls_filter_typed_*), confidence mode: the two int16 planes q -- never part of an int16 call's workspace
+    // image_m: the register image of the last hand-off (wave_image_floats >= 2 planes): a plane of its own, or Chor's
+    // plane and the rest behind it
     return planes * g.plane * sizeof(float) + (conf && disc_maps ? 2 * g.frame * sizeof(float) : 0) +
+           (image_m ? (wave_image_floats(g.pw, image_m) - (image_in_chor ? g.plane : 0)) * sizeof(float) : 0) +
            (quant_planes ? 2 * (size_t)quant_pitch(g.W) * g.H * sizeof(int16_t) : 0);
 }
 
@@ -713,6 +737,7 @@ struct ChunkPlan {
     bool fork_weights;     // the weight kernel runs on the side stream, beside the confidence kernels
     bool outside_on_side;  // ... behind the fill outside the ROI
     bool guide_rows;       // the row passes form their weights from the guide: the weight kernel writes Cvert only
+    bool image;            // the last row pass hands the last column pass its register image instead of the pair plane
 };
 
 // What a WLS filter call queues, decided from its record before anything is allocated or queued.
@@ -726,6 +751,8 @@ struct WlsPlan {
     // maps (zero outside the ROI, DF.cpp:187-190); bytes per pair of the resized left maps (none with RHS_FUSED_LO)
     Geom glo; bool lo_band; size_t dhi_bytes;
     size_t per_pair; int chunk;
+    int image_m;              // the workspace holds a register image for the last hand-off, laid out for this chunk length (0: none)
+    bool image_in_chor;       // ... whose first g.plane floats per pair are Chor's plane, which no kernel of the call touches
     // chunks of `chunk` pairs, and a shorter last one: the merged launch is for small calls, so it depends on the
     // chunk's pair count
     ChunkPlan full, tail;
@@ -734,7 +761,7 @@ struct WlsPlan {
     bool fused_first() const { return rhs == RHS_FUSED_VIEW || rhs == RHS_FUSED_LO; }
 };
 
-static ChunkPlan plan_chunk(const adf_wls* h, ConfStage stage, bool wave, bool guide_rows)
+static ChunkPlan plan_chunk(const adf_wls* h, ConfStage stage, bool wave, bool guide_rows, bool image)
 {
     // confidence mode: the weights depend on the guide only and the confidence kernels on the disparity maps only -- one
     // is bound by memory latency, the others lean on the vector ALUs -- so the weight kernel is forked onto the side
@@ -747,7 +774,7 @@ static ChunkPlan plan_chunk(const adf_wls* h, ConfStage stage, bool wave, bool g
     // it starts when the confidence kernel's workgroups hold nearly every register of every CU and crawls through 0.8 ms
     // as the call's tail (round 3).  The two-kernel stage fills in its LRC kernel.
     // (the merged launch for small calls writes both weight planes: those are bound by latency, not bytes)
-    return ChunkPlan{stage, fork, fork && wave && stage != CONF_TWO_KERNEL, guide_rows && stage != CONF_MERGED};
+    return ChunkPlan{stage, fork, fork && wave && stage != CONF_TWO_KERNEL, guide_rows && stage != CONF_MERGED, image};
 }
 
 // The row passes' weights straight from the guide of the pairs from `guide` on (fgs_wave_h.hip, WS_GUIDE*).
@@ -794,10 +821,6 @@ static WlsPlan plan_wls(const adf_wls* h, const WlsCall& c)
     p.quant_planes = f32in && conf && !c.scaled;
     p.rhs = stage == CONF_NONE ? RHS_PLAIN : stage == CONF_SCALED_LO ? RHS_FUSED_LO : fused_view ? RHS_FUSED_VIEW
           : (stage == CONF_SCALED || (stage == CONF_LEFT && p.quant_planes)) ? RHS_CONF_PROLOGUE : RHS_CONF_KERNEL;
-    p.per_pair = wls_pair_ws_bytes(g, conf, p.wave, !p.band, p.quant_planes);
-    p.chunk = (int)(h->ws_limit / p.per_pair);
-    if (p.chunk < 1) p.chunk = 1;
-    if (p.chunk > c.n_pairs) p.chunk = c.n_pairs;
     // The guide is new on every call, so the Chor plane of a full-resolution call on the wave solver is written once and
     // read num_iter times for nothing the guide row does not say in fewer bytes: the row passes take the guide instead
     // where their bucket has that form and the streaming weight kernel (the one with a Cvert-only form) runs.
@@ -809,9 +832,28 @@ static WlsPlan plan_wls(const adf_wls* h, const WlsCall& c)
         wprobe.stride = v.stride; wprobe.ch = v.ch; wprobe.chor_orient = ORIENT_N; wprobe.g = g;
         guide_rows = wave_hpass_guide_fits(probe) && weights_stream_fits(wprobe);
     }
+    // The last hand-off as the last column pass's register image: two right-hand sides on the wave solver, a row pass
+    // that is not the fused first one (num_iter >= 2), one-wave rows, whole-strip columns -- and a chunk of at least
+    // handoff_min_px ROI pixels, counted with the image's plane in the workspace.  Where no chunk of the call can write
+    // Chor -- the row passes take the guide and not even a one-pair chunk is small enough for the merged launch, which
+    // writes both weight planes -- Chor's carved-but-untouched plane is the image's first part (image_in_chor) and the
+    // workspace grows by the rest only.
+    const int image_m = (conf && p.wave && h->handoff_image && h->num_iter >= 2 && wave_hpass_image_fits(g.rw)) ? wave_vpass_image_m(g.rh) : 0;
+    const long long roi_px = (long long)g.rw * g.rh;
+    const bool may_merge = p.band && h->merge_small && prep_small_fits(g, h->disc_radius, v.ch, 1) && prep_small_guide_fits(g, v.stride, v.ch);
+    auto chunk_for = [&](int im) {
+        p.image_m = im;
+        p.image_in_chor = im && guide_rows && !may_merge;
+        p.per_pair = wls_pair_ws_bytes(g, conf, p.wave, !p.band, p.quant_planes, im, p.image_in_chor);
+        p.chunk = (int)(h->ws_limit / p.per_pair);
+        if (p.chunk < 1) p.chunk = 1;
+        if (p.chunk > c.n_pairs) p.chunk = c.n_pairs;
+    };
+    chunk_for(image_m);
+    if (image_m && roi_px * p.chunk < h->handoff_min_px) chunk_for(0);
     auto chunk_of = [&](int n) {
         const bool merged = p.band && h->merge_small && prep_small_fits(g, h->disc_radius, v.ch, n) && prep_small_guide_fits(g, v.stride, v.ch);
-        return plan_chunk(h, merged ? CONF_MERGED : stage, p.wave, guide_rows);
+        return plan_chunk(h, merged ? CONF_MERGED : stage, p.wave, guide_rows, p.image_m && roi_px * n >= h->handoff_min_px);
     };
     p.full = chunk_of(p.chunk);
     p.tail = chunk_of(c.n_pairs % p.chunk ? c.n_pairs % p.chunk : p.chunk);
@@ -903,11 +945,12 @@ static int wls_filter_impl(adf_wls_t* h, const WlsCall& c, const WlsPlan& plan, 
     h->roi = roi; h->last_W = W; h->last_H = H; h->last_pairs = n_pairs;
     h->last_cpitch = g.cpitch; h->last_cx0 = g.cx0; h->last_path = 0; h->last_solver_path = 0;
     h->last_solver = wave ? ADF_SOLVER_WAVE : ADF_SOLVER_EXACT;
+    h->last_handoff = ADF_HANDOFF_PAIR_PLANE;
     if ((rc = h->ws.reserve(plan.per_pair * (size_t)plan.chunk, st, FILL_ZERO))) return rc;
     if (conf && !c.scaled && (rc = ensure_conf_planes(h, g, n_pairs, st))) return rc;
     {
         const long long sig[8] = {W, H, roi.x, roi.y, roi.width, roi.height,
-                                  (long long)plan.quant_planes * 8 + (long long)plan.band * 4 + (long long)wave * 2 + conf, plan.chunk};
+                                  (long long)plan.image_in_chor * 1024 + (long long)plan.image_m * 16 + (long long)plan.quant_planes * 8 + (long long)plan.band * 4 + (long long)wave * 2 + conf, plan.chunk};
         if (memcmp(sig, h->ws_sig, sizeof(sig)) != 0) {
             HIP_TRY(hipMemsetAsync(h->ws.p, 0, h->ws.bytes, st));
             memcpy(h->ws_sig, sig, sizeof(sig));
@@ -917,13 +960,20 @@ static int wls_filter_impl(adf_wls_t* h, const WlsCall& c, const WlsPlan& plan, 
     float* base = (float*)h->ws.p;
     auto take = [&](size_t elems) { float* p = base; base += elems * (size_t)plan.chunk; return p; };
     SolvePlanes p{};
-    p.CH = take(g.plane); p.CV = take(g.plane); p.A0 = take(g.plane);
+    p.CH = take(g.plane);
+    // the last hand-off's register image in Chor's plane (all pairs' planes, contiguous) and what it needs beyond it
+    float* const image_rest = plan.image_in_chor ? take(wave_image_floats(g.pw, plan.image_m) - g.plane) : nullptr;
+    (void)image_rest;
+    p.CV = take(g.plane); p.A0 = take(g.plane);
     if (!wave) { p.D = take(g.plane); p.F0 = take(g.plane); p.B0 = take(g.plane); }
     float *cL = nullptr, *cR = nullptr;
     if (conf) {
         p.A1 = take(g.plane);                     // wave: directly behind A0 (the pair plane spans both)
         if (!wave) { p.F1 = take(g.plane); p.B1 = take(g.plane); }
     }
+    // the last hand-off's register image: rows past the ROI's last one are never written and must read as zeros (finite
+    // is what the column pass needs), which the zero fill on a signature change above gives
+    float* const image = !plan.image_m ? nullptr : plan.image_in_chor ? p.CH : take(wave_image_floats(g.pw, plan.image_m));
     // float maps: the planes q of a chunk (before the full-frame maps: everything in front is a multiple of 256 bytes, so
     // the planes' rows are 16-byte aligned); 2 * qframe int16 = qframe floats per pair
     const size_t qframe = (size_t)quant_pitch(W) * H;
@@ -939,6 +989,7 @@ static int wls_filter_impl(adf_wls_t* h, const WlsCall& c, const WlsPlan& plan, 
     const int16_t fill = (int16_t)(16 * (h->min_disp - 1));            // DF.cpp:254,284
     const ConfRule rule = conf_rule(h, c);
     h->last_path = plan.path; h->last_solver_path = plan.solver_path;
+    h->last_handoff = (plan.full.image && plan.tail.image) ? ADF_HANDOFF_IMAGE : plan.full.image ? ADF_HANDOFF_IMAGE_PAIR_TAIL : ADF_HANDOFF_PAIR_PLANE;
 
     for (int first = 0; first < n_pairs; first += plan.chunk) {
         const int n = (n_pairs - first < plan.chunk) ? n_pairs - first : plan.chunk;
@@ -1020,7 +1071,7 @@ static int wls_filter_impl(adf_wls_t* h, const WlsCall& c, const WlsPlan& plan, 
         const int epi = conf ? (om.f32 ? EPI_WLS_CONF_F32 : EPI_WLS_CONF) : (om.f32 ? EPI_F32 : EPI_I16);
         FinalOut fo{epi, o, om.stride, om.pair_stride, roi.x, roi.y, 1, 0};
         rc = run_passes(wave, g, p, conf ? 2 : 1, (float)h->lambda, (float)h->atten, h->num_iter, fo, n, st, prof,
-                        plan.fused_first() ? &fuse : nullptr, cp.guide_rows ? &gw : nullptr);
+                        plan.fused_first() ? &fuse : nullptr, cp.guide_rows ? &gw : nullptr, cp.image ? image : nullptr, plan.image_m);
         if (rc) return rc;                                                 // DF.cpp:257-258, 292-296
     }
     return ADF_OK;
@@ -1037,7 +1088,15 @@ static int wls_filter_device(adf_wls_t* h, int n_pairs, const DispMaps& dm, int 
     DeviceScope ds(h->device);
     h->lazy_conf.pending = false;    // (the previous call's low-resolution maps are about to be overwritten or freed)
     if ((rc = h->lut.ensure((float)h->sigma_color, st))) return rc;
-    rc = wls_filter_impl(h, c, plan_wls(h, c), st);
+    const WlsPlan plan = plan_wls(h, c);
+    rc = wls_filter_impl(h, c, plan, st);
+    if (rc == ADF_ENOMEM && plan.image_m) {
+        // the image makes the workspace larger than the pair-plane hand-off's: a call that does not fit with it runs without
+        const bool keep = h->handoff_image;
+        h->handoff_image = false;
+        rc = wls_filter_impl(h, c, plan_wls(h, c), st);
+        h->handoff_image = keep;
+    }
     if (c.scaled) h->roi = c.rlo;                                          // getROI(): valid_disp_ROI (DF.cpp:139)
     return rc;
 }

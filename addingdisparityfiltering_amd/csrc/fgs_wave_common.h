@@ -36,6 +36,14 @@
 //                   reads an image row as 128-byte pieces at a 256-byte stride (the other row of the pair
 //                   fills the gaps) and de-interleaves in its LDS staging buffer.  Measured against plain
 //                   row-major pair rows: column pass -6 %, row pass +3.5 %.  U1 pointers are ignored.
+//   the last hand-off (WavePassArgs::image; two right-hand sides, one-wave rows, whole-strip columns)   what the last
+//                   row pass writes only the last column pass reads, so it may be that pass's REGISTER IMAGE:
+//                   [pw/16 strips][8 waves][Mc rows of a chunk][64 lanes = (chunk % 8) * 8 + column pair][U0 c, U0 c+1,
+//                   U1 c, U1 c+1], Mc the column bucket's chunk length, 64 * Mc rows per strip (those past the
+//                   column's end stay zero), pw * 64 * Mc * 2 floats per image.  A thread's two columns of both
+//                   right-hand sides of a row are one 16-byte element, a wave instruction of the column pass one
+//                   contiguous KiB, a strip one contiguous stream; the row pass stores a strip's 16 columns of a row as
+//                   one whole 128-byte line.  Measured: profiles/last_handoff_floor.txt, last_handoff_ab.txt.
 #pragma once
 #include "adf_internal.h"
 

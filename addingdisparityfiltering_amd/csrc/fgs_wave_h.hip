@@ -771,6 +771,42 @@ __device__ __forceinline__ void store_pair(const WavePassArgs& a, const RowPos& 
     }
 }
 
+// The last hand-off (IMAGE): the row pass nobody but the last column pass reads after stores its solutions as that
+// pass's register image (fgs_wave_common.h) instead of the pair plane.  Same staging buffer, same values, half a row
+// at a time; the staged order is the image's -- a strip's 16 columns as eight float4s [U0 c, U0 c+1, U1 c, U1 c+1] --
+// so the eight lanes that store a strip of this row write one whole 128-byte line: row i of chunk ch of strip s lies at
+// float4 s*(512*Mc) + (ch/8)*(64*Mc) + i*64 + (ch%8)*8 of the pair's image, Mc = a.image_m the column bucket's chunk.
+__device__ __forceinline__ constexpr int image_slot(int j) { return ((j >> 4) << 3) + ((j & 15) >> 1); }
+
+template <int M>
+__device__ __forceinline__ void store_image(const WavePassArgs& a, const RowPos& p, float4* stage, int lane, const float (&f0)[M], const float (&f1)[M])
+{
+    constexpr int MQ = M / 4;
+    const unsigned mc = (unsigned)a.image_m, ch = (unsigned)blockIdx.x / mc, i = (unsigned)blockIdx.x - ch * mc;   // wave-uniform
+    float4* d4 = reinterpret_cast<float4*>(a.image + (size_t)blockIdx.y * a.image_plane) + ((ch >> 3) * (64u * mc) + i * 64u + (ch & 7u) * 8u);
+    const unsigned strip_step = 512u * mc;
+#pragma unroll
+    for (int half = 0; half < 2; half++) {
+        if ((p.lane >> 5) == half) {
+#pragma unroll
+            for (int k = 0; k < MQ; k++) {
+                // (8-byte writes of register pairs as the solve left them: a float4 gathered from f0 and f1 would be
+                // four copies per slot, and at M = 56 / 60 those spill)
+                v2f* s2 = reinterpret_cast<v2f*>(stage + image_slot((p.lane & 31) * M + 4 * k));
+                s2[0] = (v2f){f0[4 * k], f0[4 * k + 1]}; s2[1] = (v2f){f1[4 * k], f1[4 * k + 1]};
+                s2[2] = (v2f){f0[4 * k + 2], f0[4 * k + 3]}; s2[3] = (v2f){f1[4 * k + 2], f1[4 * k + 3]};
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < MQ; k++) {
+            const int idx = 64 * (k + half * MQ) + lane;      // float4 of the interleaved row: strip idx / 8, piece idx % 8
+            if (idx < p.nvecU) store_nt(stage[64 * k + lane], d4 + ((unsigned)(idx >> 3) * strip_step + (unsigned)(idx & 7)));
+        }
+        __syncthreads();
+    }
+}
+
 // NW = 2: rows longer than 64 chunks of 64 elements (ROIs wider than 4096 columns: 8K frames) are solved by TWO
 // wavefronts of one workgroup, wave w owning columns [w*64*M, (w+1)*64*M) -- its own staging buffer, its own loads and
 // stores, the chunk sweeps unchanged -- and meeting the other three times through LDS: the weight in front of chunk 64,
@@ -778,11 +814,12 @@ __device__ __forceinline__ void store_pair(const WavePassArgs& a, const RowPos& 
 // solves (fgs_wave_common.h, reduced128).
 // (the longest chunk with two right-hand sides does not fit two waves per SIMD without spilling: the
 // pair staging keeps both right-hand sides and two of the three load batches alive at once)
-template <int M, int R, int FUSED, int NW = 1, int WS = WS_PLANE>
+template <int M, int R, int FUSED, int NW = 1, int WS = WS_PLANE, bool IMAGE = false>
 __global__ void __launch_bounds__(64 * NW, (M > (NW == 2 ? 40 : H_TWO_WAVE_MAX) && R > 1) ? 1 : 2) wave_hpass_kernel(WavePassArgs a)
 {
     static_assert(M % 4 == 0 && M >= 4, "chunk length must be a multiple of 4");
     static_assert(NW == 1 || NW == 2, "one or two wavefronts per row");
+    static_assert(!IMAGE || (R == 2 && FUSED == FUSE_NONE && NW == 1), "the last hand-off's image: a plain one-wave pass of two right-hand sides");
     constexpr bool LO = FUSED == FUSE_LO || FUSED == FUSE_LO_HALF;
     constexpr bool PAIR = R > 1;
     constexpr bool GUIDE = WS != WS_PLANE;
@@ -864,7 +901,8 @@ __global__ void __launch_bounds__(64 * NW, (M > (NW == 2 ? 40 : H_TWO_WAVE_MAX) 
     // the lane index makes it recompute them here instead.
     int lane_s = lane;
     asm volatile("" : "+v"(lane_s));
-    if constexpr (PAIR) store_pair<M>(a, p, stage, lane_s, f0, f1);
+    if constexpr (IMAGE) store_image<M>(a, p, stage, lane_s, f0, f1);
+    else if constexpr (PAIR) store_pair<M>(a, p, stage, lane_s, f0, f1);
     else store_plain<M>(a, p, stage, lane_s, f0);
 }
 
@@ -883,7 +921,8 @@ hipError_t launch_h_guide(const WavePassArgs& a, int n_rhs, dim3 grid, hipStream
         if (n_rhs != 2) return hipErrorInvalidValue;
         if (a.fuse.dl_f32) hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_VIEW_F32, 1, WS>), grid, dim3(64), 0, st, a);
         else hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_VIEW, 1, WS>), grid, dim3(64), 0, st, a);
-    } else if (n_rhs == 2) hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_NONE, 1, WS>), grid, dim3(64), 0, st, a);
+    } else if (n_rhs == 2 && a.image) hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_NONE, 1, WS, true>), grid, dim3(64), 0, st, a);
+    else if (n_rhs == 2) hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_NONE, 1, WS>), grid, dim3(64), 0, st, a);
     else hipLaunchKernelGGL((wave_hpass_kernel<M, 1, FUSE_NONE, 1, WS>), grid, dim3(64), 0, st, a);
     return hipGetLastError();
 }
@@ -914,6 +953,9 @@ hipError_t launch_h(const WavePassArgs& a, int n_rhs, int n_pairs, hipStream_t s
         if (n_rhs != 2) return hipErrorInvalidValue;
         if (a.fuse.dl_f32) hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_VIEW_F32, NW>), grid, block, 0, st, a);
         else hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_VIEW, NW>), grid, block, 0, st, a);
+    } else if (n_rhs == 2 && a.image) {
+        if constexpr (NW == 1) hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_NONE, 1, WS_PLANE, true>), grid, block, 0, st, a);
+        else return hipErrorInvalidValue;                     // two-wave rows have no image form
     } else if (n_rhs == 2) hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_NONE, NW>), grid, block, 0, st, a);
     else hipLaunchKernelGGL((wave_hpass_kernel<M, 1, FUSE_NONE, NW>), grid, block, 0, st, a);
     return hipGetLastError();
@@ -962,6 +1004,14 @@ bool wave_hpass_guide_fits(const WavePassArgs& a)
     return guide_bucket(nw);
 }
 
+bool wave_hpass_image_fits(int row_len)
+{
+    if (row_len < 2 || row_len > wave_max_row_len()) return false;
+    int m, nw;
+    pick_row_bucket(row_len, m, nw);
+    return nw == 1;
+}
+
 bool wave_hpass_lo_half(const WavePassArgs& a)
 {
     if (!(a.fuse.lo_conf && a.fuse.lo_half && a.fuse.lo_scale_x == 0.5 && (a.fuse.hi_x0 & 1) == 0 && a.fuse.hi_x0 >= 2)) return false;
@@ -1001,6 +1051,10 @@ hipError_t launch_wave_hpass(const WavePassArgs& a, int n_rhs, int n_pairs, hipS
     if (a.fuse.lo_conf && !wave_hpass_can_fuse_lo(a)) return hipErrorInvalidValue;
     if (!a.fuse.lo_conf && a.fuse.conf_in && !wave_hpass_can_fuse(a)) return hipErrorInvalidValue;
     if (a.gw.guide && !wave_hpass_guide_fits(a)) return hipErrorInvalidValue;
+    // the image of the last hand-off: a plain pass of two right-hand sides on one-wave rows, every row inside the image
+    if (a.image && (n_rhs != 2 || a.fuse.conf_in || a.fuse.lo_conf || !wave_hpass_image_fits(a.len) || a.image_m < 1 ||
+                    a.nscan > 64 * a.image_m || a.image_plane < wave_image_floats(a.pitch, a.image_m)))
+        return hipErrorInvalidValue;
     return dispatch_index<N_ROW_BUCKETS>(bucket_index(ROW_BUCKETS, a.len), [&](auto I) {
         constexpr Bucket b = ROW_BUCKETS[decltype(I)::value];
         return launch_h<b.m, b.chunks / 64>(a, n_rhs, n_pairs, st);

@@ -15,6 +15,7 @@ using namespace wave;
 // ---------------------------------------------------------------------------------------------
 constexpr int VT = 512;  // threads per strip
 constexpr int VC = 16;   // columns per strip (the layouts' strip: fgs_wave_common.h)
+typedef float v4f __attribute__((ext_vector_type(4)));
 // Round 3: columns longer than 64 chunks of 34 rows (ROIs taller than 2176 rows: 8K frames) run HALF strips of 128 chunks
 // -- VCW = 8 columns, NCH = 128, still 512 threads and the same rows and registers per thread, i.e. the same 415 KB of a
 // CU's register file per workgroup -- with a 128-row reduced system per column (fgs_wave_common.h, reduced128).  Half
@@ -124,10 +125,15 @@ __device__ __forceinline__ unsigned vstep(int r0, int i, int pitch)
     return (unsigned)pitch * 4u;
 }
 
-template <int M, int R, int EPI, int VCW = VC, int NCH = 64>
+// IMG (the last pass of a call whose last row pass stored the hand-off's register image, a.image): f0[i], f1[i] come
+// from the image instead of the pair plane -- [strip][wave][row in chunk i][lane][U0 c, U0 c+1, U1 c, U1 c+1], the
+// thread's two columns of both right-hand sides of a row as ONE 16-byte element, a wave instruction one contiguous
+// KiB, 1 KiB from row to row, the strip one contiguous stream like its weights.  Whole strips only.
+template <int M, int R, int EPI, int VCW = VC, int NCH = 64, bool IMG = false>
 __global__ void __launch_bounds__(VT) wave_vpass_kernel(WavePassArgs a)
 {
     static_assert((VCW == 16 && NCH == 64) || (VCW == 8 && NCH == 128), "whole strips of 64 chunks or half strips of 128");
+    static_assert(!IMG || (R == 2 && VCW == VC && (EPI == EPI_WLS_CONF || EPI == EPI_WLS_CONF_F32)), "the image: whole strips, both right-hand sides, the filter's epilogues");
     static_assert((VCW / 2) * NCH == VT, "one thread per (chunk, column pair)");
     constexpr int XPN = VCW / 2;         // column pairs per workgroup
     __shared__ float nb[4][NCH][VCW];   // next-chunk exchange: GS0, GS1, PS, QS
@@ -187,17 +193,28 @@ __global__ void __launch_bounds__(VT) wave_vpass_kernel(WavePassArgs a)
     // (FGS.cpp:658-660), so whatever finite, diagonally dominant system those rows form is decoupled
     // from the real one by exact zeros (0 * finite), and the stores below skip them.  Untouched
     // loaded pairs stay where the load put them -- a select here would copy every pair.
+    // IMG: the image holds all 64 * M rows of every strip, and the rows past the column's end are its padding -- zero
+    // since the workspace was last laid out, which no kernel writes -- so they are loaded where they lie.
     {
         unsigned voff = voff0, coff = coff0;
         const v2f lam = vsplat(a.lambda);
+        const char* bI = IMG ? reinterpret_cast<const char*>(a.image + (size_t)blockIdx.y * a.image_plane) : nullptr;
+        unsigned ioff = (((unsigned)strip * (NCH / 8) + ((unsigned)tid >> 6)) * (unsigned)M) * 1024u + ((unsigned)tid & 63u) * 16u;
 #pragma unroll
         for (int i = 0; i < M; i++) {
             const bool ok = r0 + i < h;
-            const unsigned vo = ok ? voff : safe;
             c[i] = *reinterpret_cast<const v2f*>(bC + (ok ? coff : csafe));
-            f0[i] = *reinterpret_cast<const v2f*>(b0 + vo);
-            f1[i] = (R > 1) ? *reinterpret_cast<const v2f*>(b1 + vo) : vsplat(0.0f);
-            voff += vstep<R>(r0, i, a.pitch); coff += pitch_c;
+            if constexpr (IMG) {
+                const v4f q = *reinterpret_cast<const v4f*>(bI + ioff);
+                f0[i] = (v2f){q.x, q.y}; f1[i] = (v2f){q.z, q.w};
+                ioff += 1024u;
+            } else {
+                const unsigned vo = ok ? voff : safe;
+                f0[i] = *reinterpret_cast<const v2f*>(b0 + vo);
+                f1[i] = (R > 1) ? *reinterpret_cast<const v2f*>(b1 + vo) : vsplat(0.0f);
+                voff += vstep<R>(r0, i, a.pitch);
+            }
+            coff += pitch_c;
             ADF_STEP_FENCE();   // one row's addresses at a time: hoisting all of them costs 2 registers per row
         }
 #pragma unroll
@@ -335,6 +352,13 @@ hipError_t launch_v(const WavePassArgs& a, int n_rhs, int epi, int n_pairs, hipS
         // (two right-hand sides with a generic epilogue: channel pairs of a generic FGS source)
         if constexpr (R == 1 && (EPI == EPI_WLS_CONF || EPI == EPI_WLS_CONF_F32)) return hipErrorInvalidValue;   // the ratio needs both right-hand sides
         else {
+            if (a.image) {   // the last hand-off's image: whole strips, the filter's epilogues, the image laid out for this bucket
+                if constexpr (R == 2 && VCW == VC && (EPI == EPI_WLS_CONF || EPI == EPI_WLS_CONF_F32)) {
+                    if (a.image_m != M || a.image_plane < wave_image_floats(a.pitch, M)) return hipErrorInvalidValue;
+                    hipLaunchKernelGGL((wave_vpass_kernel<M, R, EPI, VCW, NCH, true>), grid, block, 0, st, a);
+                    return hipGetLastError();
+                } else return hipErrorInvalidValue;
+            }
             hipLaunchKernelGGL((wave_vpass_kernel<M, R, EPI, VCW, NCH>), grid, block, 0, st, a);
             return hipGetLastError();
         }
@@ -348,6 +372,13 @@ constexpr int N_COL_BUCKETS = sizeof(COL_BUCKETS) / sizeof(COL_BUCKETS[0]);
 } // namespace
 
 int wave_max_col_len() { return COL_BUCKETS[N_COL_BUCKETS - 1].m * COL_BUCKETS[N_COL_BUCKETS - 1].chunks; }
+
+int wave_vpass_image_m(int col_len)
+{
+    if (col_len < 2 || col_len > wave_max_col_len()) return 0;
+    const Bucket& b = COL_BUCKETS[bucket_index(COL_BUCKETS, col_len)];
+    return b.chunks == 64 ? b.m : 0;
+}
 
 hipError_t launch_wave_vpass(const WavePassArgs& a, int n_rhs, int epilogue, int n_pairs, hipStream_t st)
 {

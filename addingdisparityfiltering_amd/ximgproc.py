@@ -52,7 +52,7 @@ from ._lib import GF_MAX_RADIUS  # noqa: F401  (re-exported)
 from ._lib import DTF_NC, DTF_IC, DTF_RF, DT_MAX_ITERS, DT_NC_MAX_RADIUS  # noqa: F401  (cv's EdgeAwareFiltersList; DTF_RF and, under dtWindowFilter, DTF_NC are built)
 from ._lib import RGF_MAX_ITERS  # noqa: F401  (re-exported)
 from ._lib import JBF_MAX_RADIUS, BORDER_REPLICATE, BORDER_REFLECT, BORDER_WRAP, BORDER_REFLECT_101  # noqa: F401  (cv's BorderTypes; 1, 2 and 4 are built)
-from ._lib import AdfError, PATH_CONF_BAND, PATH_FUSED_FIRST_PASS, PATH_MERGED_PREP, PATH_ROW_WEIGHTS_GUIDE, PATH_SCALED_FUSED, PATH_SCALED_HALF, Rect, SOLVER_EXACT, SOLVER_WAVE  # noqa: F401  (re-exported)
+from ._lib import AdfError, HANDOFF_IMAGE, HANDOFF_IMAGE_PAIR_TAIL, HANDOFF_PAIR_PLANE, PATH_CONF_BAND, PATH_FUSED_FIRST_PASS, PATH_MERGED_PREP, PATH_ROW_WEIGHTS_GUIDE, PATH_SCALED_FUSED, PATH_SCALED_HALF, Rect, SOLVER_EXACT, SOLVER_WAVE  # noqa: F401  (re-exported)
 
 try:  # torch is optional plumbing: device memory and streams only
     import torch
@@ -270,6 +270,10 @@ class DisparityWLSFilter(_Handle, DisparityFilter):
     def getLastSolverPath(self):
         """... and which its solve passes took (PATH_ROW_WEIGHTS_GUIDE): a word of its own."""
         return _read(_lib.lib().adf_wls_get_last_solver_path, C.c_int, self._h)
+
+    def getLastHandoff(self):
+        """HANDOFF_IMAGE where the last row pass of the last call stored the last column pass's register image."""
+        return _read(_lib.lib().adf_wls_get_last_handoff, C.c_int, self._h)
 
     def enableProfiling(self, on=True):
         """Bracket every kernel launch with HIP events on the caller's stream (measurement hook)."""

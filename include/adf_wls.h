@@ -133,6 +133,14 @@ int adf_wls_get_last_path(const adf_wls_t* h, int* path_flags);
                                         guide rows themselves (FGS.cpp:607-614 inside the pass); the weight kernel wrote the
                                         vertical weights only and the horizontal plane was neither written nor read */
 int adf_wls_get_last_solver_path(const adf_wls_t* h, int* path_flags);
+/* ... and how the last row pass of the last filter call handed its solutions to the last column pass (a getter of its
+ * own; the results do not depend on it): through the pair plane every other pass uses, or as the column pass's
+ * register image -- wave solver, confidence mode, at least two iterations, ROIs of up to 4096 columns and 2176 rows,
+ * chunks of at least twelve 4K pairs' worth of ROI pixels (92.9 Mpx).  ADF_LAST_HANDOFF_IMAGE=0 at handle creation forces the pair plane. */
+#define ADF_HANDOFF_PAIR_PLANE 0
+#define ADF_HANDOFF_IMAGE 1
+#define ADF_HANDOFF_IMAGE_PAIR_TAIL 2 /* the full chunks the image, the shorter last chunk (below the size threshold) the pair plane */
+int adf_wls_get_last_handoff(const adf_wls_t* h, int* form);
 
 /* DisparityFilter::filter (DF.hpp:75, DF.cpp:219-298) on a batch of n_pairs
  * independent, equally sized stereo pairs laid out `*_pair_stride` bytes apart

@@ -33,7 +33,7 @@ constexpr int CPW = 64 / LPR;                            // chunks per wave inst
 typedef float v2f __attribute__((ext_vector_type(2)));
 typedef float v4f __attribute__((ext_vector_type(4)));
 
-struct Args { float* C; float* U; int pitch, h; size_t plane; int delay; short* out; int out_w, out_x0; };
+struct Args { float* C; float* U; int pitch, h; size_t plane; int delay; short* out; int out_w, out_x0; float* I; size_t image; };   // I: the last hand-off's register image, `image` floats per pair
 
 template <int N> __device__ __forceinline__ void wait_vm() { asm volatile("s_waitcnt vmcnt(%0)" :: "n"(N) : "memory"); }
 __device__ __forceinline__ void wait_lds() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
@@ -49,7 +49,9 @@ __device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst)
 enum { F_GLDS = 1, F_LSTORE = 2, F_NOLOAD = 4, F_NOSTORE = 8, F_WINDOW = 16, F_PERSIST = 32,
        F_S16 = 64,      // stores as the LAST pass makes them: int16 row-major, 4 bytes per thread and row = a 32-byte piece per strip row
        F_S16T = 128,    // int16 into a tiled scratch [4-row tile][strip][4 rows][16 columns]: a strip's 4 rows are one whole 128-byte line
-       F_REMAP = 256 }; // strips b, b+8, b+16, b+24 (same XCD) on four adjacent strips, as the kernel's last pass   // F_WINDOW: L0 in groups of 8 rows, a wait per group
+       F_REMAP = 256,   // strips b, b+8, b+16, b+24 (same XCD) on four adjacent strips, as the kernel's last pass   // F_WINDOW: L0 in groups of 8 rows, a wait per group
+       F_IMG = 512 };   // right-hand sides from the last hand-off's register image [strip][wave][row in chunk][lane][U0 c0, U0 c1, U1 c0, U1 c1]:
+                        // one 16-byte load per row, 1 KiB per wave instruction, 1 KiB from row to row (L0 form, whole strips)
 
 struct Ctx {
     const char* bC; char* b0; unsigned tile_b, strip, h, rbase; int wv, lane, j, p, xp, cidx, r0;
@@ -146,13 +148,22 @@ __global__ void __launch_bounds__(VT, 2) vpat(Args a)
             unsigned vo = line_off(c, (unsigned)c.r0, pitch) + c.xp * 8u, co = ((c.strip * c.h + (unsigned)c.r0) * VC + 2u * c.xp) * 4u;
             const unsigned vsafe = line_off(c, c.rbase, pitch) + c.xp * 8u, csafe = ((c.strip * c.h + c.rbase) * VC + 2u * c.xp) * 4u;
             const unsigned tile_b = 2u * TR * pitch * 4u;
+            // (F_IMG: whole strips of 64 chunks only; rows past the column's end come from the image's own padding)
+            const char* bI = reinterpret_cast<const char*>(a.I + (size_t)blockIdx.y * a.image);
+            unsigned io = ((c.strip * (unsigned)(CH / 8) + (unsigned)c.wv) * (unsigned)M) * 1024u + (unsigned)c.lane * 16u;
 #pragma unroll
             for (int i = 0; i < M; i++) {
                 const bool ok = (unsigned)c.r0 + i < c.h;
                 const unsigned v = ok ? vo : vsafe;
                 cc[i] = *reinterpret_cast<const v2f*>(c.bC + (ok ? co : csafe));
+                if constexpr ((MODE & F_IMG) != 0) {
+                    const v4f q = *reinterpret_cast<const v4f*>(bI + io);
+                    f0[i] = (v2f){q.x, q.y}; f1[i] = (v2f){q.z, q.w};
+                    io += 1024u;
+                } else {
                 f0[i] = *reinterpret_cast<const v2f*>(c.b0 + v);
                 f1[i] = *reinterpret_cast<const v2f*>(c.b0 + v + 4u * VC);
+                }
                 vo += ((((unsigned)c.r0 + i + 1u) & (TR - 1u)) == 0u) ? tile_b - (TR - 1u) * (8u * VC) : 8u * VC;
                 co += 4u * VC;
                 __builtin_amdgcn_sched_barrier(0);
@@ -352,6 +363,87 @@ float run(const Args& a, int pairs, int reps, size_t lds)
     return ms / reps;
 }
 
+// ---- the third row pass's side of the last hand-off ----
+// One wavefront per image row of the 3584-column ROI (the M = 56 row bucket, 18 KiB of LDS per workgroup as the guide
+// forms have: two waves per SIMD): the row's 28 float4s per lane are loaded from the pair plane exactly as the row pass
+// loads them (128-byte pieces at a 256-byte stride) and stored
+//   H_PAIR   back where they came from (the pair plane: eight 128-byte pieces at a 256-byte stride per instruction)
+//   H_IMAGE  as whole 128-byte lines at the register image's addresses (eight lines per instruction, one per strip,
+//            8 * M KiB apart; the lines of consecutive rows of a chunk are 1 KiB apart)
+// H_NOLOAD / H_NOSTORE: one leg alone.
+enum { H_PAIR = 0, H_IMAGE = 1, H_NOLOAD = 2, H_NOSTORE = 4 };
+template <int HM>
+__global__ void __launch_bounds__(64) hpat(Args a)
+{
+    constexpr int NV = 28;                                   // float4s per lane of a pair row of 3584 columns
+    const unsigned lane = threadIdx.x, y = blockIdx.x, pitch = (unsigned)a.pitch, nvec = 2u * pitch / 4u;
+    v4f* s = reinterpret_cast<v4f*>(a.U + 2 * (size_t)blockIdx.y * a.plane + (size_t)(y / TR) * (2u * TR * pitch) + (y % TR) * 32u);
+    const unsigned chunk = y / (unsigned)M, i = y % (unsigned)M;
+    v4f* d = reinterpret_cast<v4f*>(a.I + (size_t)blockIdx.y * a.image) + (chunk / 8u) * (unsigned)(M * 64) + i * 64u + (chunk % 8u) * 8u;
+    v4f t[NV];
+#pragma unroll
+    for (int k = 0; k < NV; k++) {
+        const unsigned q = 64u * k + lane;
+        t[k] = (v4f){(float)k, 1.f, 2.f, (float)lane};
+        if (!(HM & H_NOLOAD) && q < nvec) t[k] = __builtin_nontemporal_load(s + (q >> 3) * (8u * TR) + (q & 7u));
+    }
+#pragma unroll
+    for (int k = 0; k < NV; k++) asm volatile("" : "+v"(t[k]));
+    if (HM & H_NOSTORE) {
+        float acc = 0.f;
+#pragma unroll
+        for (int k = 0; k < NV; k++) acc += t[k].x + t[k].y + t[k].z + t[k].w;
+        if (acc == 123456.789f) a.U[0] = acc;
+        return;
+    }
+    unsigned lane_s = lane;
+    asm volatile("" : "+v"(lane_s));                         // (the store addresses are formed after the loads, as in the row pass)
+#pragma unroll
+    for (int k = 0; k < NV; k++) {
+        const unsigned q = 64u * k + lane_s;
+        if (q < nvec) {
+            if (HM & H_IMAGE) __builtin_nontemporal_store(t[k], d + (size_t)(q >> 3) * (unsigned)(512 * M) + (q & 7u));
+            else __builtin_nontemporal_store(t[k], s + (q >> 3) * (8u * TR) + (q & 7u));
+        }
+    }
+}
+
+template <int HM>
+float run_h(const Args& a, int pairs, int reps)
+{
+    const size_t lds = 18 * 1024;
+    dim3 grid(a.h, pairs), block(64);
+    hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));
+    for (int w = 0; w < 2; w++) hipLaunchKernelGGL(hpat<HM>, grid, block, lds, 0, a);
+    CK(hipEventRecord(e0));
+    for (int r = 0; r < reps; r++) hipLaunchKernelGGL(hpat<HM>, grid, block, lds, 0, a);
+    CK(hipEventRecord(e1)); CK(hipEventSynchronize(e1)); CK(hipGetLastError());
+    float ms = 0; CK(hipEventElapsedTime(&ms, e0, e1));
+    return ms / reps;
+}
+
+// The last hand-off, both sides, pair plane against register image; `rounds` repetitions of the whole series so that
+// the pair plane's own spread in this run is on the page.
+static void handoff(Args a, int pairs, int rounds, size_t lds)
+{
+    printf("last hand-off, %d pairs of 3584 x 2160 (x64/pairs in ms): third row pass's pattern and last column pass's pattern\n", pairs);
+    const double sc = 64.0 / pairs;
+    for (int r = 0; r < rounds; r++) {
+        const float hp = run_h<H_PAIR>(a, pairs, 10), hi = run_h<H_IMAGE>(a, pairs, 10);
+        const float hl = run_h<H_NOSTORE>(a, pairs, 10), sp = run_h<H_PAIR | H_NOLOAD>(a, pairs, 10), si = run_h<H_IMAGE | H_NOLOAD>(a, pairs, 10);
+        a.delay = 0;
+        const float vp0 = run<F_S16 | F_REMAP>(a, pairs, 10, lds), vi0 = run<F_S16 | F_REMAP | F_IMG>(a, pairs, 10, lds);
+        const float lp = run<F_NOSTORE | F_REMAP>(a, pairs, 10, lds), li = run<F_NOSTORE | F_REMAP | F_IMG>(a, pairs, 10, lds);
+        a.delay = 2;
+        const float vp2 = run<F_S16 | F_REMAP>(a, pairs, 10, lds), vi2 = run<F_S16 | F_REMAP | F_IMG>(a, pairs, 10, lds);
+        a.delay = 0;
+        printf("  round %d  row: load+store pair %.3f image %.3f | loads only %.3f | stores only pair %.3f image %.3f\n", r, hp * sc, hi * sc, hl * sc, sp * sc, si * sc);
+        printf("  round %d  col: loads+int16 rows, no solve pair %.3f image %.3f | 7 us solve pair %.3f image %.3f | loads only pair %.3f image %.3f\n",
+               r, vp0 * sc, vi0 * sc, vp2 * sc, vi2 * sc, lp * sc, li * sc);
+        printf("  round %d  sum (row + col with 7 us solve): pair %.3f image %.3f  difference %+.3f\n", r, (hp + vp2) * sc, (hi + vi2) * sc, (hi + vi2 - hp - vp2) * sc);
+    }
+}
+
 __global__ void fill_kernel(float* p, size_t n, unsigned seed)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -361,7 +453,7 @@ __global__ void fill_kernel(float* p, size_t n, unsigned seed)
 // L1+S1 and every mix must produce exactly what L0+S0 produces on the same data
 static bool verify()
 {
-    Args a; a.pitch = 3584; a.h = 2160; a.plane = (size_t)a.pitch * a.h; a.delay = 0; a.out = nullptr; a.out_w = 3840; a.out_x0 = 256;
+    Args a; a.pitch = 3584; a.h = 2160; a.plane = (size_t)a.pitch * a.h; a.delay = 0; a.out = nullptr; a.out_w = 3840; a.out_x0 = 256; a.I = nullptr; a.image = 0;
     float* U[4];
     CK(hipMalloc(&a.C, a.plane * 4));
     hipLaunchKernelGGL(fill_kernel, dim3((unsigned)((a.plane + 255) / 256)), dim3(256), 0, 0, a.C, a.plane, 7u);
@@ -399,8 +491,15 @@ int main(int argc, char** argv)
     CK(hipMalloc(&a.C, a.plane * 4 * pairs)); CK(hipMalloc(&a.U, a.plane * 8 * pairs));
     a.out_w = 3840; a.out_x0 = 256; CK(hipMalloc(&a.out, (size_t)a.out_w * a.h * 2 * pairs));
     CK(hipMemset(a.C, 0, a.plane * 4 * pairs)); CK(hipMemset(a.U, 0, a.plane * 8 * pairs));
+    a.image = (size_t)a.pitch * (CH * M) * 2;                 // every strip holds CH * M rows, the column's padding included
+    CK(hipMalloc(&a.I, a.image * 4 * pairs)); CK(hipMemset(a.I, 0, a.image * 4 * pairs));
     const double px = (double)a.plane * pairs;
     const size_t lds = (VT / 64) * NS * 1024 + 44 * 1024 * VC / 16;   // the real kernel's exchange buffers ride along
+    if (argc > 2 && VC == 16 && VT == 512) {                  // vpattern <pairs> <rounds>: the last hand-off's series only
+        CK(hipFuncSetAttribute(reinterpret_cast<const void*>(vpat<F_S16 | F_REMAP | F_IMG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        handoff(a, pairs, atoi(argv[2]), lds);
+        return 0;
+    }
     struct { const char* name; float ms; double bytes; } r[] = {
         {"L0+S0 (as the kernel)", run<0>(a, pairs, 10, lds), 20 * px},
         {"L1+S0 (LDS-DMA whole lines)", run<F_GLDS>(a, pairs, 10, lds), 20 * px},
