@@ -102,6 +102,7 @@ SYMBOLS = [
     ("adf_wls_get_last_path", _i, [_vp, C.POINTER(_i)]),
     ("adf_wls_get_last_solver_path", _i, [_vp, C.POINTER(_i)]),
     ("adf_wls_get_last_handoff", _i, [_vp, C.POINTER(_i)]),
+    ("adf_wls_get_inner_handoffs", _i, [_vp, C.POINTER(_i), C.POINTER(_i)]),
     ("adf_wls_filter_device", _i, _FILTER_DEV),
     ("adf_wls_filter_host", _i, _FILTER_DEV[:-1]),
     ("adf_wls_filter_scaled_device", _i, _FILTER_SCALED_DEV),

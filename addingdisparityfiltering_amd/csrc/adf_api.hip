@@ -134,12 +134,30 @@ static void set_final_out(Args& a, const FinalOut& fo)
     a.out_x0 = fo.x0; a.out_y0 = fo.y0; a.out_cn = fo.cn; a.out_c = fo.c;
 }
 
+// Which row -> column hand-offs of a chunk's passes go through the column pass's register image (fgs_wave_common.h)
+// instead of the pair plane: the last one (`image` set), the inner ones behind the first (`inner`), the first one
+// (`first`: the fused first pass has the image form).  A one-iteration call's only hand-off keeps the pair plane.
+struct HandoffImage {
+    float* image = nullptr; int m = 0; bool inner = false, first = false;
+    bool at(int it, int num_iter) const
+    {
+        if (!image || num_iter < 2) return false;
+        return it == num_iter - 1 ? true : it > 0 ? inner : first;
+    }
+    int inner_count(int num_iter) const
+    {
+        int n = 0;
+        for (int it = 0; it + 1 < num_iter; it++) n += at(it, num_iter);
+        return n;
+    }
+};
+
 // The passes on either solver.  exact: the planes ping-pong between A and B, the horizontal pass reads the row index
 // fastest; wave: the on-chip partitioned solver, row-major planes solved in place.  `fuse` (wave only): the inputs the
 // first row pass forms its right-hand sides from.
 static int run_passes(bool wave, const Geom& g, const SolvePlanes& p, int n_rhs, float lambda, float atten, int num_iter,
                       const FinalOut& fo, int n_pairs, hipStream_t st, Profiler* prof = nullptr,
-                      const FusedInputs* fuse = nullptr, const GuideWeights* gw = nullptr, float* image = nullptr, int image_m = 0)
+                      const FusedInputs* fuse = nullptr, const GuideWeights* gw = nullptr, const HandoffImage& ho = HandoffImage{})
 {
     const double px = (double)g.rw * g.rh * n_pairs;
     float lam = lambda;
@@ -164,11 +182,15 @@ static int run_passes(bool wave, const Geom& g, const SolvePlanes& p, int n_rhs,
             v.C = p.CV; v.U0 = p.A0; v.U1 = p.A1;
             v.nscan = g.rw; v.len = g.rh; v.pitch = g.pw; v.plane = g.plane; v.lambda = lam;
             if (last) set_final_out(v, fo);
-            // the last hand-off: nobody but the last column pass reads what the last row pass writes, so that pass stores
-            // the column pass's register image instead of the pair plane (same bytes: 8 written, 8 read per pixel)
-            if (image && last && it > 0) {
-                h.image = v.image = image; h.image_m = v.image_m = image_m;
-                h.image_plane = v.image_plane = wave_image_floats(g.pw, image_m);
+            // The row -> column hand-offs: nobody but the column pass of the same iteration reads what a row pass writes, so
+            // the row pass stores that pass's register image instead of the pair plane (same bytes: 8 written, 8 read per
+            // pixel).  Ordering: within an iteration the row pass writes the image and the column pass reads it; the column
+            // pass writes the pair plane and the next iteration's row pass reads that.  Nothing is read and written in
+            // the same launch except the column pass's own strip of the pair plane, and the column pass holds its whole
+            // strip in registers before its first store.
+            if (ho.at(it, num_iter)) {
+                h.image = v.image = ho.image; h.image_m = v.image_m = ho.m;
+                h.image_plane = v.image_plane = wave_image_floats(g.pw, ho.m);
             }
             {
                 ProfScope ps(prof, fused ? K_PASS_H_FIRST : K_PASS_H, hb, hb, st);
@@ -218,6 +240,10 @@ struct ConfResize {
 // pass's loads gain (the two passes' sum within +-1 %, the call 0.3-1.6 % slower with the image); 12 pairs is the
 // smallest batch at which the sum is lower outside both forms' spread and the call is not slower.  Other geometries are
 // taken by their pixel count: estimated, not measured.
+// The inner hand-offs take the image under the same threshold: in the same series with three handles (all hand-offs /
+// the last only / none; profiles/inner_handoff_ab.txt, "chunk size series") they do not need a larger chunk than the
+// last one -- level with "last only" within both spreads up to 4 pairs, lower from 8 pairs on, and at 12 pairs lower
+// outside both spreads (2.54-2.61 against 2.60-2.68 ms per call).
 constexpr long long HANDOFF_IMAGE_MIN_PX = 12LL * 3584 * 2160;
 
 struct adf_wls {
@@ -264,10 +290,12 @@ struct adf_wls {
     bool conf_band = true;   // ADF_CONF_BAND=0: the two-kernel confidence stage (A/B measurements)
     bool merge_small = true; // ADF_MERGE_SMALL=0: never the merged preparation launch (A/B measurements)
     bool row_weights_guide = true; // ADF_ROW_WEIGHTS_GUIDE=0: the row passes always read the Chor plane (A/B measurements, tests)
-    bool handoff_image = true;     // ADF_LAST_HANDOFF_IMAGE=0: the last row pass always writes the pair plane (A/B measurements, the tests' reference)
+    bool handoff_image = true;     // ADF_LAST_HANDOFF_IMAGE=0: every row pass writes the pair plane (A/B measurements, the tests' reference)
+    bool handoff_inner = true;     // ADF_INNER_HANDOFF_IMAGE=0: all but the last row pass write the pair plane (A/B measurements)
     // ... and the smallest chunk, in ROI pixels, whose last hand-off takes the image (ADF_LAST_HANDOFF_MIN_PX: tests only)
     long long handoff_min_px = HANDOFF_IMAGE_MIN_PX;
     int last_handoff = ADF_HANDOFF_PAIR_PLANE;   // the form the last call's last hand-off took (adf_wls_get_last_handoff)
+    int last_inner[2] = {0, 0};    // inner hand-offs of the last call's full / tail chunk that took the image (adf_wls_get_inner_handoffs)
     // HIP maps the streams of ONE priority level onto a small pool of hardware queues (4 by default) and two streams that
     // share a queue run one after the other: a side stream of the caller's priority lost the overlap for about one caller
     // stream in four (tools/batch_cpp.cpp: 13.5-13.6 ms per 64 x 4K call instead of 12.8-13.2).  Each priority level has a pool
@@ -314,6 +342,7 @@ extern "C" int adf_wls_create(adf_wls_t** out, int use_confidence, int l, int r,
     if (const char* e = getenv("ADF_ROW_WEIGHTS_GUIDE")) h->row_weights_guide = atoi(e) != 0;   // measurement knob
     if (const char* e = getenv("ADF_LO_HALF")) h->scaled_half = atoi(e) != 0;
     if (const char* e = getenv("ADF_LAST_HANDOFF_IMAGE")) h->handoff_image = atoi(e) != 0;   // measurement knob
+    if (const char* e = getenv("ADF_INNER_HANDOFF_IMAGE")) h->handoff_inner = atoi(e) != 0;  // measurement knob
     if (const char* e = getenv("ADF_LAST_HANDOFF_MIN_PX")) h->handoff_min_px = atoll(e);      // test knob
     if (const char* e = getenv("ADF_MERGE_SMALL")) h->merge_small = atoi(e) != 0;   // measurement knob
     *out = h;
@@ -362,6 +391,14 @@ extern "C" int adf_wls_get_last_solver(const adf_wls_t* h, int* v) { NEED_HANDLE
 extern "C" int adf_wls_get_last_path(const adf_wls_t* h, int* v) { NEED_HANDLE(h); if (v) *v = h->last_path; return ADF_OK; }
 extern "C" int adf_wls_get_last_solver_path(const adf_wls_t* h, int* v) { NEED_HANDLE(h); if (v) *v = h->last_solver_path; return ADF_OK; }
 extern "C" int adf_wls_get_last_handoff(const adf_wls_t* h, int* v) { NEED_HANDLE(h); if (v) *v = h->last_handoff; return ADF_OK; }
+
+extern "C" int adf_wls_get_inner_handoffs(const adf_wls_t* h, int* full, int* tail)
+{
+    NEED_HANDLE(h);
+    if (full) *full = h->last_inner[0];
+    if (tail) *tail = h->last_inner[1];
+    return ADF_OK;
+}
 
 extern "C" int adf_wls_get_device(const adf_wls_t* h, int* device) { NEED_HANDLE(h); if (device) *device = h->device; return ADF_OK; }
 extern "C" int adf_wls_get_roi(const adf_wls_t* h, adf_rect* roi) { NEED_HANDLE(h); if (roi) *roi = h->roi; return ADF_OK; }
@@ -738,6 +775,7 @@ struct ChunkPlan {
     bool outside_on_side;  // ... behind the fill outside the ROI
     bool guide_rows;       // the row passes form their weights from the guide: the weight kernel writes Cvert only
     bool image;            // the last row pass hands the last column pass its register image instead of the pair plane
+    bool inner_image;      // ... and so do the row passes before it, each to the column pass of its iteration
 };
 
 // What a WLS filter call queues, decided from its record before anything is allocated or queued.
@@ -753,6 +791,7 @@ struct WlsPlan {
     size_t per_pair; int chunk;
     int image_m;              // the workspace holds a register image for the last hand-off, laid out for this chunk length (0: none)
     bool image_in_chor;       // ... whose first g.plane floats per pair are Chor's plane, which no kernel of the call touches
+    bool first_image;         // the fused first row pass has the image form (a FUSE_VIEW pass on an int16 map)
     // chunks of `chunk` pairs, and a shorter last one: the merged launch is for small calls, so it depends on the
     // chunk's pair count
     ChunkPlan full, tail;
@@ -761,7 +800,7 @@ struct WlsPlan {
     bool fused_first() const { return rhs == RHS_FUSED_VIEW || rhs == RHS_FUSED_LO; }
 };
 
-static ChunkPlan plan_chunk(const adf_wls* h, ConfStage stage, bool wave, bool guide_rows, bool image)
+static ChunkPlan plan_chunk(const adf_wls* h, ConfStage stage, bool wave, bool guide_rows, bool image, bool inner_image)
 {
     // confidence mode: the weights depend on the guide only and the confidence kernels on the disparity maps only -- one
     // is bound by memory latency, the others lean on the vector ALUs -- so the weight kernel is forked onto the side
@@ -774,7 +813,7 @@ static ChunkPlan plan_chunk(const adf_wls* h, ConfStage stage, bool wave, bool g
     // it starts when the confidence kernel's workgroups hold nearly every register of every CU and crawls through 0.8 ms
     // as the call's tail (round 3).  The two-kernel stage fills in its LRC kernel.
     // (the merged launch for small calls writes both weight planes: those are bound by latency, not bytes)
-    return ChunkPlan{stage, fork, fork && wave && stage != CONF_TWO_KERNEL, guide_rows && stage != CONF_MERGED, image};
+    return ChunkPlan{stage, fork, fork && wave && stage != CONF_TWO_KERNEL, guide_rows && stage != CONF_MERGED, image, image && inner_image};
 }
 
 // The row passes' weights straight from the guide of the pairs from `guide` on (fgs_wave_h.hip, WS_GUIDE*).
@@ -853,8 +892,10 @@ static WlsPlan plan_wls(const adf_wls* h, const WlsCall& c)
     if (image_m && roi_px * p.chunk < h->handoff_min_px) chunk_for(0);
     auto chunk_of = [&](int n) {
         const bool merged = p.band && h->merge_small && prep_small_fits(g, h->disc_radius, v.ch, n) && prep_small_guide_fits(g, v.stride, v.ch);
-        return plan_chunk(h, merged ? CONF_MERGED : stage, p.wave, guide_rows, p.image_m && roi_px * n >= h->handoff_min_px);
+        // (the inner hand-offs under the last one's conditions: the batch-size series of profiles/inner_handoff_ab.txt)
+        return plan_chunk(h, merged ? CONF_MERGED : stage, p.wave, guide_rows, p.image_m && roi_px * n >= h->handoff_min_px, h->handoff_inner);
     };
+    p.first_image = p.rhs == RHS_FUSED_VIEW && wave_hpass_first_image(view_fuse(planes, m, g));
     p.full = chunk_of(p.chunk);
     p.tail = chunk_of(c.n_pairs % p.chunk ? c.n_pairs % p.chunk : p.chunk);
     p.path = ((p.band || p.lo_band) ? ADF_PATH_CONF_BAND : 0) |
@@ -945,7 +986,7 @@ static int wls_filter_impl(adf_wls_t* h, const WlsCall& c, const WlsPlan& plan, 
     h->roi = roi; h->last_W = W; h->last_H = H; h->last_pairs = n_pairs;
     h->last_cpitch = g.cpitch; h->last_cx0 = g.cx0; h->last_path = 0; h->last_solver_path = 0;
     h->last_solver = wave ? ADF_SOLVER_WAVE : ADF_SOLVER_EXACT;
-    h->last_handoff = ADF_HANDOFF_PAIR_PLANE;
+    h->last_handoff = ADF_HANDOFF_PAIR_PLANE; h->last_inner[0] = h->last_inner[1] = 0;
     if ((rc = h->ws.reserve(plan.per_pair * (size_t)plan.chunk, st, FILL_ZERO))) return rc;
     if (conf && !c.scaled && (rc = ensure_conf_planes(h, g, n_pairs, st))) return rc;
     {
@@ -989,6 +1030,8 @@ static int wls_filter_impl(adf_wls_t* h, const WlsCall& c, const WlsPlan& plan, 
     const int16_t fill = (int16_t)(16 * (h->min_disp - 1));            // DF.cpp:254,284
     const ConfRule rule = conf_rule(h, c);
     h->last_path = plan.path; h->last_solver_path = plan.solver_path;
+    auto handoff_of = [&](const ChunkPlan& cp) { return HandoffImage{cp.image ? image : nullptr, plan.image_m, cp.inner_image, cp.inner_image && plan.first_image}; };
+    if (wave) { h->last_inner[0] = handoff_of(plan.full).inner_count(h->num_iter); h->last_inner[1] = handoff_of(plan.tail).inner_count(h->num_iter); }
     h->last_handoff = (plan.full.image && plan.tail.image) ? ADF_HANDOFF_IMAGE : plan.full.image ? ADF_HANDOFF_IMAGE_PAIR_TAIL : ADF_HANDOFF_PAIR_PLANE;
 
     for (int first = 0; first < n_pairs; first += plan.chunk) {
@@ -1071,7 +1114,7 @@ static int wls_filter_impl(adf_wls_t* h, const WlsCall& c, const WlsPlan& plan, 
         const int epi = conf ? (om.f32 ? EPI_WLS_CONF_F32 : EPI_WLS_CONF) : (om.f32 ? EPI_F32 : EPI_I16);
         FinalOut fo{epi, o, om.stride, om.pair_stride, roi.x, roi.y, 1, 0};
         rc = run_passes(wave, g, p, conf ? 2 : 1, (float)h->lambda, (float)h->atten, h->num_iter, fo, n, st, prof,
-                        plan.fused_first() ? &fuse : nullptr, cp.guide_rows ? &gw : nullptr, cp.image ? image : nullptr, plan.image_m);
+                        plan.fused_first() ? &fuse : nullptr, cp.guide_rows ? &gw : nullptr, handoff_of(cp));
         if (rc) return rc;                                                 // DF.cpp:257-258, 292-296
     }
     return ADF_OK;

@@ -213,9 +213,9 @@ struct WavePassArgs {
     size_t plane;
     float lambda;
     GuideWeights gw;   // row passes only
-    // The last hand-off's register image (fgs_wave_common.h): where the last row pass of a call with two right-hand
-    // sides stores its solutions INSTEAD of the pair plane and the last column pass loads them from; null = the pair
-    // plane.  image_m is the column bucket's chunk length, image_plane the image's floats per pair.
+    // A row -> column hand-off's register image (fgs_wave_common.h): where a row pass of a call with two right-hand
+    // sides stores its solutions INSTEAD of the pair plane and the column pass that follows loads them from; null = the
+    // pair plane.  image_m is the column bucket's chunk length, image_plane the image's floats per pair.
     float* image; size_t image_plane; int image_m;
 };
 // the kernels' argument layout (the guide of the row passes' weights and the hand-off image are appended: no other member moved)
@@ -249,10 +249,12 @@ bool wave_hpass_can_fuse_lo(const WavePassArgs& a);   // the low-resolution form
 bool wave_hpass_lo_half(const WavePassArgs& a);      // ... in its half-width form (fgs_wave_h.hip, FUSE_LO_HALF)?
 bool wave_hpass_guide_fits(const WavePassArgs& a);   // can the row pass form its weights from a.gw (a.len, a.gw, a.fuse)?
 int wave_max_col_len();
-// The last hand-off's register image (WavePassArgs::image): does the row pass of rows of `row_len` elements have the
-// store form (one-wave rows); the chunk length of the column bucket of `col_len` rows, 0 where the column pass lacks the
-// load form (half strips); floats per pair of the image.
+// A hand-off's register image (WavePassArgs::image): does the row pass of rows of `row_len` elements have the
+// store form (one-wave rows); does the fused first pass on the inputs `f` have it (the view-resolution prologue on an
+// int16 map); the chunk length of the column bucket of `col_len` rows, 0 where the column pass lacks the load form
+// (half strips); floats per pair of the image.
 bool wave_hpass_image_fits(int row_len);
+bool wave_hpass_first_image(const FusedInputs& f);
 int wave_vpass_image_m(int col_len);
 inline size_t wave_image_floats(int pitch, int m) { return (size_t)pitch * (size_t)(64 * m) * 2; }
 // largest depth-discontinuity radius the tile kernel supports (LDS bound)

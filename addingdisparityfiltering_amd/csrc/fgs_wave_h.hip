@@ -771,8 +771,11 @@ __device__ __forceinline__ void store_pair(const WavePassArgs& a, const RowPos& 
     }
 }
 
-// The last hand-off (IMAGE): the row pass nobody but the last column pass reads after stores its solutions as that
-// pass's register image (fgs_wave_common.h) instead of the pair plane.  Same staging buffer, same values, half a row
+// A row -> column hand-off (IMAGE): what a row pass writes is read by nobody but the column pass that follows it, so
+// the row pass stores its solutions as that pass's register image (fgs_wave_common.h) instead of the pair plane.  (The
+// column -> row hand-off stays on the pair plane: the row pass needs its contiguous rows.)  The plain pass and the
+// FUSE_VIEW first pass have the form; FUSE_VIEW_F32 and the low-resolution prologues keep the pair plane for the first
+// hand-off.  Same staging buffer, same values, half a row
 // at a time; the staged order is the image's -- a strip's 16 columns as eight float4s [U0 c, U0 c+1, U1 c, U1 c+1] --
 // so the eight lanes that store a strip of this row write one whole 128-byte line: row i of chunk ch of strip s lies at
 // float4 s*(512*Mc) + (ch/8)*(64*Mc) + i*64 + (ch%8)*8 of the pair's image, Mc = a.image_m the column bucket's chunk.
@@ -819,7 +822,8 @@ __global__ void __launch_bounds__(64 * NW, (M > (NW == 2 ? 40 : H_TWO_WAVE_MAX) 
 {
     static_assert(M % 4 == 0 && M >= 4, "chunk length must be a multiple of 4");
     static_assert(NW == 1 || NW == 2, "one or two wavefronts per row");
-    static_assert(!IMAGE || (R == 2 && FUSED == FUSE_NONE && NW == 1), "the last hand-off's image: a plain one-wave pass of two right-hand sides");
+    static_assert(!IMAGE || (R == 2 && (FUSED == FUSE_NONE || FUSED == FUSE_VIEW) && NW == 1),
+                  "a hand-off's image: a one-wave pass of two right-hand sides, plain or with the view-resolution int16 prologue");
     constexpr bool LO = FUSED == FUSE_LO || FUSED == FUSE_LO_HALF;
     constexpr bool PAIR = R > 1;
     constexpr bool GUIDE = WS != WS_PLANE;
@@ -910,6 +914,10 @@ __global__ void __launch_bounds__(64 * NW, (M > (NW == 2 ? 40 : H_TWO_WAVE_MAX) 
 // single-occupancy kernels, whose half-width form needs five registers more than a lane has (it takes the general form).
 constexpr bool lo_half_bucket(int m, int nw) { return !(m == 60 && nw == 1); }
 
+// Is the image form of the FUSE_VIEW first pass built?  Every one-wave bucket and weight source has it: none spills and
+// each keeps its pair-plane form's occupancy (profiles/inner_handoff_isa.txt).
+constexpr bool FIRST_IMAGE = true;
+
 // the guide forms of a bucket: every one-wave bucket has them
 constexpr bool guide_bucket(int nw) { return nw == 1; }
 
@@ -920,7 +928,10 @@ hipError_t launch_h_guide(const WavePassArgs& a, int n_rhs, dim3 grid, hipStream
     if (a.fuse.conf_in) {
         if (n_rhs != 2) return hipErrorInvalidValue;
         if (a.fuse.dl_f32) hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_VIEW_F32, 1, WS>), grid, dim3(64), 0, st, a);
-        else hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_VIEW, 1, WS>), grid, dim3(64), 0, st, a);
+        else if (a.image) {
+            if constexpr (FIRST_IMAGE) hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_VIEW, 1, WS, true>), grid, dim3(64), 0, st, a);
+            else return hipErrorInvalidValue;
+        } else hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_VIEW, 1, WS>), grid, dim3(64), 0, st, a);
     } else if (n_rhs == 2 && a.image) hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_NONE, 1, WS, true>), grid, dim3(64), 0, st, a);
     else if (n_rhs == 2) hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_NONE, 1, WS>), grid, dim3(64), 0, st, a);
     else hipLaunchKernelGGL((wave_hpass_kernel<M, 1, FUSE_NONE, 1, WS>), grid, dim3(64), 0, st, a);
@@ -952,7 +963,10 @@ hipError_t launch_h(const WavePassArgs& a, int n_rhs, int n_pairs, hipStream_t s
     } else if (a.fuse.conf_in) {
         if (n_rhs != 2) return hipErrorInvalidValue;
         if (a.fuse.dl_f32) hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_VIEW_F32, NW>), grid, block, 0, st, a);
-        else hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_VIEW, NW>), grid, block, 0, st, a);
+        else if (a.image) {
+            if constexpr (FIRST_IMAGE && NW == 1) hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_VIEW, 1, WS_PLANE, true>), grid, block, 0, st, a);
+            else return hipErrorInvalidValue;                     // two-wave rows have no image form
+        } else hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_VIEW, NW>), grid, block, 0, st, a);
     } else if (n_rhs == 2 && a.image) {
         if constexpr (NW == 1) hipLaunchKernelGGL((wave_hpass_kernel<M, 2, FUSE_NONE, 1, WS_PLANE, true>), grid, block, 0, st, a);
         else return hipErrorInvalidValue;                     // two-wave rows have no image form
@@ -1012,6 +1026,8 @@ bool wave_hpass_image_fits(int row_len)
     return nw == 1;
 }
 
+bool wave_hpass_first_image(const FusedInputs& f) { return FIRST_IMAGE && f.conf_in && !f.lo_conf && !f.dl_f32; }
+
 bool wave_hpass_lo_half(const WavePassArgs& a)
 {
     if (!(a.fuse.lo_conf && a.fuse.lo_half && a.fuse.lo_scale_x == 0.5 && (a.fuse.hi_x0 & 1) == 0 && a.fuse.hi_x0 >= 2)) return false;
@@ -1051,8 +1067,9 @@ hipError_t launch_wave_hpass(const WavePassArgs& a, int n_rhs, int n_pairs, hipS
     if (a.fuse.lo_conf && !wave_hpass_can_fuse_lo(a)) return hipErrorInvalidValue;
     if (!a.fuse.lo_conf && a.fuse.conf_in && !wave_hpass_can_fuse(a)) return hipErrorInvalidValue;
     if (a.gw.guide && !wave_hpass_guide_fits(a)) return hipErrorInvalidValue;
-    // the image of the last hand-off: a plain pass of two right-hand sides on one-wave rows, every row inside the image
-    if (a.image && (n_rhs != 2 || a.fuse.conf_in || a.fuse.lo_conf || !wave_hpass_image_fits(a.len) || a.image_m < 1 ||
+    // a hand-off's image: a pass of two right-hand sides on one-wave rows -- plain or, where that form is built, with the
+    // view-resolution prologue on an int16 map -- every row inside the image
+    if (a.image && (n_rhs != 2 || a.fuse.lo_conf || (a.fuse.conf_in && (a.fuse.dl_f32 || !FIRST_IMAGE)) || !wave_hpass_image_fits(a.len) || a.image_m < 1 ||
                     a.nscan > 64 * a.image_m || a.image_plane < wave_image_floats(a.pitch, a.image_m)))
         return hipErrorInvalidValue;
     return dispatch_index<N_ROW_BUCKETS>(bucket_index(ROW_BUCKETS, a.len), [&](auto I) {

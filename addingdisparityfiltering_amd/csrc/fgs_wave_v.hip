@@ -125,15 +125,16 @@ __device__ __forceinline__ unsigned vstep(int r0, int i, int pitch)
     return (unsigned)pitch * 4u;
 }
 
-// IMG (the last pass of a call whose last row pass stored the hand-off's register image, a.image): f0[i], f1[i] come
+// IMG (a pass of two right-hand sides whose row pass stored the hand-off's register image, a.image): f0[i], f1[i] come
 // from the image instead of the pair plane -- [strip][wave][row in chunk i][lane][U0 c, U0 c+1, U1 c, U1 c+1], the
 // thread's two columns of both right-hand sides of a row as ONE 16-byte element, a wave instruction one contiguous
-// KiB, 1 KiB from row to row, the strip one contiguous stream like its weights.  Whole strips only.
+// KiB, 1 KiB from row to row, the strip one contiguous stream like its weights.  Whole strips only.  The plain pass
+// (EPI_PLANES) stores to the pair plane as ever: the next row pass needs its contiguous rows.
 template <int M, int R, int EPI, int VCW = VC, int NCH = 64, bool IMG = false>
 __global__ void __launch_bounds__(VT) wave_vpass_kernel(WavePassArgs a)
 {
     static_assert((VCW == 16 && NCH == 64) || (VCW == 8 && NCH == 128), "whole strips of 64 chunks or half strips of 128");
-    static_assert(!IMG || (R == 2 && VCW == VC && (EPI == EPI_WLS_CONF || EPI == EPI_WLS_CONF_F32)), "the image: whole strips, both right-hand sides, the filter's epilogues");
+    static_assert(!IMG || (R == 2 && VCW == VC && (EPI == EPI_PLANES || EPI == EPI_WLS_CONF || EPI == EPI_WLS_CONF_F32)), "the image: whole strips, both right-hand sides, the plain pass or the filter's epilogues");
     static_assert((VCW / 2) * NCH == VT, "one thread per (chunk, column pair)");
     constexpr int XPN = VCW / 2;         // column pairs per workgroup
     __shared__ float nb[4][NCH][VCW];   // next-chunk exchange: GS0, GS1, PS, QS
@@ -352,8 +353,8 @@ hipError_t launch_v(const WavePassArgs& a, int n_rhs, int epi, int n_pairs, hipS
         // (two right-hand sides with a generic epilogue: channel pairs of a generic FGS source)
         if constexpr (R == 1 && (EPI == EPI_WLS_CONF || EPI == EPI_WLS_CONF_F32)) return hipErrorInvalidValue;   // the ratio needs both right-hand sides
         else {
-            if (a.image) {   // the last hand-off's image: whole strips, the filter's epilogues, the image laid out for this bucket
-                if constexpr (R == 2 && VCW == VC && (EPI == EPI_WLS_CONF || EPI == EPI_WLS_CONF_F32)) {
+            if (a.image) {   // a hand-off's image: whole strips, the plain pass or the filter's epilogues, the image laid out for this bucket
+                if constexpr (R == 2 && VCW == VC && (EPI == EPI_PLANES || EPI == EPI_WLS_CONF || EPI == EPI_WLS_CONF_F32)) {
                     if (a.image_m != M || a.image_plane < wave_image_floats(a.pitch, M)) return hipErrorInvalidValue;
                     hipLaunchKernelGGL((wave_vpass_kernel<M, R, EPI, VCW, NCH, true>), grid, block, 0, st, a);
                     return hipGetLastError();

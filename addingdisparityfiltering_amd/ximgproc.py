@@ -275,6 +275,13 @@ class DisparityWLSFilter(_Handle, DisparityFilter):
         """HANDOFF_IMAGE where the last row pass of the last call stored the last column pass's register image."""
         return _read(_lib.lib().adf_wls_get_last_handoff, C.c_int, self._h)
 
+    def getInnerHandoffs(self):
+        """(full, tail): how many hand-offs before the last one took the register image in the last call's full chunks
+        and in its shorter last chunk."""
+        full, tail = C.c_int(0), C.c_int(0)
+        _lib.check(_lib.lib().adf_wls_get_inner_handoffs(self._h, C.byref(full), C.byref(tail)))
+        return full.value, tail.value
+
     def enableProfiling(self, on=True):
         """Bracket every kernel launch with HIP events on the caller's stream (measurement hook)."""
         _lib.check(_lib.lib().adf_wls_profile_enable(self._h, int(bool(on))))

@@ -141,6 +141,14 @@ int adf_wls_get_last_solver_path(const adf_wls_t* h, int* path_flags);
 #define ADF_HANDOFF_IMAGE 1
 #define ADF_HANDOFF_IMAGE_PAIR_TAIL 2 /* the full chunks the image, the shorter last chunk (below the size threshold) the pair plane */
 int adf_wls_get_last_handoff(const adf_wls_t* h, int* form);
+/* ... and how many of the INNER row -> column hand-offs (those of iterations before the last: num_iter - 1 of them)
+ * took the register image in the last call's full chunks and in its shorter last chunk (equal to `full` where the call
+ * has none).  An inner hand-off takes the image under the last one's conditions; the first one only where the first row
+ * pass forms its right-hand sides from view-resolution int16 maps (float maps and the down-scaled path's interpolating
+ * first pass keep the pair plane there).  A one-iteration call has no inner hand-off.  ADF_INNER_HANDOFF_IMAGE=0 at
+ * handle creation keeps the inner hand-offs on the pair plane and leaves the last one alone; ADF_LAST_HANDOFF_IMAGE=0
+ * keeps every hand-off there.  The results do not depend on either. */
+int adf_wls_get_inner_handoffs(const adf_wls_t* h, int* full, int* tail);
 
 /* DisparityFilter::filter (DF.hpp:75, DF.cpp:219-298) on a batch of n_pairs
  * independent, equally sized stereo pairs laid out `*_pair_stride` bytes apart

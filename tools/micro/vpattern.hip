@@ -444,6 +444,30 @@ static void handoff(Args a, int pairs, int rounds, size_t lds)
     }
 }
 
+// An INNER hand-off's column side: the plain column pass (consecutive blocks on consecutive strips, 8-byte stores of
+// both right-hand sides to the pair plane, the Cvert stream as it is) with its right-hand sides loaded from the pair
+// plane as today against one 16-byte load per row from the register image.  `rounds` repetitions so that the pair
+// plane's own spread in this run is on the page; the last line is the gate of the change that built the kernels.
+static void inner_handoff(Args a, int pairs, int rounds, size_t lds)
+{
+    printf("inner hand-off, %d pairs of 3584 x 2160 (x64/pairs in ms): plain column pass's pattern, loads from pair plane | register image, stores to the pair plane\n", pairs);
+    const double sc = 64.0 / pairs;
+    float pmin = 1e30f, pmax = 0.f, imin = 1e30f, imax = 0.f;
+    for (int r = 0; r < rounds; r++) {
+        a.delay = 0;
+        const float vp0 = run<0>(a, pairs, 10, lds), vi0 = run<F_IMG>(a, pairs, 10, lds);
+        const float lp = run<F_NOSTORE>(a, pairs, 10, lds), li = run<F_NOSTORE | F_IMG>(a, pairs, 10, lds);
+        a.delay = 2;
+        const float vp2 = run<0>(a, pairs, 10, lds), vi2 = run<F_IMG>(a, pairs, 10, lds);
+        a.delay = 0;
+        pmin = vp2 < pmin ? vp2 : pmin; pmax = vp2 > pmax ? vp2 : pmax; imin = vi2 < imin ? vi2 : imin; imax = vi2 > imax ? vi2 : imax;
+        printf("  round %d  col: loads+pair-plane stores, no solve pair %.3f image %.3f | 7 us solve pair %.3f image %.3f (%+.3f) | loads only pair %.3f image %.3f\n",
+               r, vp0 * sc, vi0 * sc, vp2 * sc, vi2 * sc, (vi2 - vp2) * sc, lp * sc, li * sc);
+    }
+    printf("  with the 7 us solve: pair %.3f-%.3f (spread %.3f)  image %.3f-%.3f  smallest gap (pair min - image max) %+.3f  = %.1f x the pair plane's spread\n",
+           pmin * sc, pmax * sc, (pmax - pmin) * sc, imin * sc, imax * sc, (pmin - imax) * sc, (pmin - imax) / (pmax - pmin > 0.f ? pmax - pmin : 1e-6f));
+}
+
 __global__ void fill_kernel(float* p, size_t n, unsigned seed)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -497,7 +521,8 @@ int main(int argc, char** argv)
     const size_t lds = (VT / 64) * NS * 1024 + 44 * 1024 * VC / 16;   // the real kernel's exchange buffers ride along
     if (argc > 2 && VC == 16 && VT == 512) {                  // vpattern <pairs> <rounds>: the last hand-off's series only
         CK(hipFuncSetAttribute(reinterpret_cast<const void*>(vpat<F_S16 | F_REMAP | F_IMG>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        handoff(a, pairs, atoi(argv[2]), lds);
+        if (argc > 3 && argv[3][0] == 'i') inner_handoff(a, pairs, atoi(argv[2]), lds);   // vpattern <pairs> <rounds> inner
+        else handoff(a, pairs, atoi(argv[2]), lds);
         return 0;
     }
     struct { const char* name; float ms; double bytes; } r[] = {
