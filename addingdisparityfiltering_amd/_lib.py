@@ -31,6 +31,7 @@ DT_NC_MAX_RADIUS = 127    # ADF_DT_NC_MAX_RADIUS
 JBF_MAX_RADIUS = 31    # ADF_JBF_MAX_RADIUS
 BORDER_REPLICATE, BORDER_REFLECT, BORDER_WRAP, BORDER_REFLECT_101 = 1, 2, 3, 4    # cv::BorderTypes; 1, 2 and 4 are built (ADF_BORDER_*)
 RGF_MAX_ITERS = 16    # ADF_RGF_MAX_ITERS
+AM_MAX_TREE_HEIGHT = 8    # ADF_AM_MAX_TREE_HEIGHT
 
 
 class AdfError(RuntimeError):
@@ -61,6 +62,12 @@ class RectifyParams(C.Structure):
                 ("dist", C.c_double * 8), ("ir", C.c_double * 9)]
 
 
+class AmPlan(C.Structure):
+    """adf_am_plan: what amFilter's host side derives from (sigma_s, sigma_r, tree_height, W, H)."""
+    _fields_ = [(k, C.c_int) for k in ("df", "height", "sh", "sw", "manifolds")] + \
+               [(k, C.c_float) for k in ("a_root", "a_child", "sr2", "arg_w", "ss", "ratio", "ln_a", "arg_out")]
+
+
 # every symbol include/adf_wls.h declares: (name, restype, argtypes)
 _vp, _i, _d, _pd, _sz = C.c_void_p, C.c_int, C.c_double, C.c_ssize_t, C.c_size_t
 _FILTER_DEV = [_vp, _i, _vp, _pd, _pd, _vp, _pd, _pd, _i, _i, _i, _vp, _pd, _pd, _vp, _pd, _pd,
@@ -75,6 +82,7 @@ _WMF_DEV = [_i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _i, _i,
 _GF_DEV = [_i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _i, _i, _i, _d, _vp, _sz, _vp]
 _DT_DEV = [_i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _i, _i, _d, _d, _i, _i, _vp, _sz, _vp]
 _JBF_DEV = [_i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _i, _i, _i, _d, _d, _i, _vp]
+_AM_DEV = [_i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _vp, _pd, _pd, _i, _i, _i, _d, _d, _i, _i, _vp, _sz, _vp]
 _RGF_DEV = [_i, _vp, _pd, _pd, _vp, _pd, _pd, _i, _i, _i, _i, _d, _d, _i, _i, _vp, _sz, _vp]
 _FILTER_SCALED_DEV = [_vp, _i, _vp, _pd, _pd, _i, _i, _vp, _pd, _pd, _i, _i, _i, _vp, _pd, _pd, _vp, _pd, _pd,
                       C.POINTER(Rect), _vp]
@@ -206,6 +214,11 @@ SYMBOLS = [
     ("adf_rgf_tables_host", _i, [_i, _i, _d, _d, _vp, _vp, C.POINTER(_i), C.POINTER(_i), C.POINTER(C.c_float)]),
     ("adf_rolling_guidance_filter_device", _i, _RGF_DEV),
     ("adf_rolling_guidance_filter_host", _i, _RGF_DEV[:-3]),
+    ("adf_am_plan_host", _i, [_d, _d, _i, _i, _i, C.POINTER(AmPlan), _vp]),
+    ("adf_am_exp_host", _i, [_vp, _vp, _sz]),
+    ("adf_am_filter_workspace_bytes", _sz, [_i, _i, _i, _i, _d, _d, _i]),
+    ("adf_am_filter_device", _i, _AM_DEV),
+    ("adf_am_filter_host", _i, _AM_DEV[:-3]),
 ]
 
 _lib = None

@@ -31,6 +31,7 @@ SOURCES = {
     "dt_window_kernels.hip": [],
     "joint_bilateral_kernels.hip": [],
     "rolling_guidance_kernels.hip": [],
+    "am_filter_kernels.hip": [],
 }
 OUT = os.path.join(_HERE, "libadf_wls.so")
 # -ffp-contract=off: the exact solver and the confidence map reproduce the reference's separate

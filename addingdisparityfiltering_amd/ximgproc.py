@@ -50,7 +50,7 @@ from ._lib import SGBM_RIGHT_MATCHER, SGBM_RIGHT_FROM_VOLUME  # noqa: F401  (re-
 from ._lib import WMF_EXP, WMF_IV1, WMF_IV2, WMF_COS, WMF_JAC, WMF_OFF  # noqa: F401  (cv's WMFWeightType; EXP and OFF are built)
 from ._lib import GF_MAX_RADIUS  # noqa: F401  (re-exported)
 from ._lib import DTF_NC, DTF_IC, DTF_RF, DT_MAX_ITERS, DT_NC_MAX_RADIUS  # noqa: F401  (cv's EdgeAwareFiltersList; DTF_RF and, under dtWindowFilter, DTF_NC are built)
-from ._lib import RGF_MAX_ITERS  # noqa: F401  (re-exported)
+from ._lib import RGF_MAX_ITERS, AM_MAX_TREE_HEIGHT  # noqa: F401  (re-exported)
 from ._lib import JBF_MAX_RADIUS, BORDER_REPLICATE, BORDER_REFLECT, BORDER_WRAP, BORDER_REFLECT_101  # noqa: F401  (cv's BorderTypes; 1, 2 and 4 are built)
 from ._lib import AdfError, HANDOFF_IMAGE, HANDOFF_IMAGE_PAIR_TAIL, HANDOFF_PAIR_PLANE, PATH_CONF_BAND, PATH_FUSED_FIRST_PASS, PATH_MERGED_PREP, PATH_ROW_WEIGHTS_GUIDE, PATH_SCALED_FUSED, PATH_SCALED_HALF, Rect, SOLVER_EXACT, SOLVER_WAVE  # noqa: F401  (re-exported)
 
@@ -1736,6 +1736,125 @@ def rollingGuidanceFilter(src, d=-1, sigmaColor=25, sigmaSpace=3, numOfIter=4, b
             float(sigmaSpace), int(numOfIter), b)
     _filter_call("adf_rolling_guidance_filter", S, args, _workspace(_RGF, S, workspace))
     return dst
+
+
+# ---------------------------------------------------------------------------------------------
+# cv::ximgproc::amFilter / createAMFilter / AdaptiveManifoldFilter (EF.hpp:203-280, adaptive_manifold_filter_n.cpp) in
+# the library's own exact definition (include/adf_wls.h; csrc/am_filter_kernels.hip; the direct statement is
+# tests/am_ref.py).
+# ---------------------------------------------------------------------------------------------
+_AM = "amFilter"
+
+
+def amPlan(sigma_s, sigma_r, tree_height=-1, W=1, H=1):
+    """What amFilter's host side derives from its parameters and the map's size, exactly as its calls form it
+    (adf_am_plan_host): a dict with df, height, sh, sw, manifolds (ints), the float32 scalars a_root, a_child, sr2, argW,
+    ss, ratio, lnA, argOut, and jtab, the 256 float32 levels of the joint.  Host only: no device is touched."""
+    p = _lib.AmPlan()
+    jtab = np.empty(256, np.float32)
+    _lib.check(_lib.lib().adf_am_plan_host(float(sigma_s), float(sigma_r), int(tree_height), int(W), int(H), C.byref(p), jtab.ctypes.data))
+    out = {k: int(getattr(p, k)) for k in ("df", "height", "sh", "sw", "manifolds")}
+    out.update({k: np.float32(getattr(p, f)) for k, f in (("a_root", "a_root"), ("a_child", "a_child"), ("sr2", "sr2"), ("argW", "arg_w"),
+                                                          ("ss", "ss"), ("ratio", "ratio"), ("lnA", "ln_a"), ("argOut", "arg_out"))})
+    out["jtab"] = jtab
+    return out
+
+
+def amFilterWorkspaceBytes(n, H, W, channels, sigma_s, sigma_r, tree_height=-1):
+    """Bytes of device workspace amFilter needs for n maps of H x W with a joint of `channels` channels
+    (adf_am_filter_workspace_bytes); 0 for arguments the calls refuse."""
+    return int(_lib.lib().adf_am_filter_workspace_bytes(int(n), int(W), int(H), int(channels), float(sigma_s), float(sigma_r), int(tree_height)))
+
+
+def _am_filter(joint, src, sigma_s, sigma_r, tree_height, adjust_outliers, dst, dDepth, workspace):
+    if joint is None:
+        raise AdfError(_lib.ADF_EBADARG, "%s: joint must not be empty (filtering src by itself is not built)" % _AM)
+    if src is None:
+        raise AdfError(_lib.ADF_EBADARG, "%s: src must not be empty" % _AM)
+    S, G, _, D, dst, dt, ddt = _filter_images(_AM, src, dst, dDepth, joint, role="joint")
+    args = (S.n, G.ptr, G.stride, G.pair_stride, G.c, S.ptr, S.stride, S.pair_stride, _DEPTH[dt], D.ptr, D.stride, D.pair_stride,
+            _DEPTH[ddt], S.w, S.h, float(sigma_s), float(sigma_r), int(tree_height), int(bool(adjust_outliers)))
+    _filter_call("adf_am_filter", S, args, _workspace(_AM, S, workspace))
+    return dst
+
+
+def amFilter(joint, src, sigma_s, sigma_r, adjust_outliers=False, dst=None, dDepth=-1, workspace=None):
+    """cv::ximgproc::amFilter(joint, src, dst, sigma_s, sigma_r, adjust_outliers): the adaptive manifold filter, a
+    high-dimensional bilateral filter of a map through a gray or BGR view for large kernels, in the library's own
+    definition (include/adf_wls.h).  Bit-exact against tests/am_ref.py fed with amPlan.
+
+        joint    (H,W) or (H,W,3) uint8, or a batch (N,H,W[,3]); must not be None
+        src      (H,W) or (N,H,W) uint8, int16 or float32, one channel
+        sigma_s  >= 1: the spatial scale in pixels; the small plane is 1/df of the map, df = amPlan(...)["df"]
+        sigma_r  in (0, 1]: the range scale, the joint taken as 0 .. 1
+        adjust_outliers  pull pixels far from every manifold back to src
+        dDepth   -1 (src's depth, as the reference), CV_8U, CV_16S or CV_32F
+        dst      must not overlap src or joint
+
+    The tree height is automatic (AdaptiveManifoldFilter sets it).  Tensors, streams, `workspace` (at least
+    amFilterWorkspaceBytes(...) bytes) and host arrays are as with dtFilter.  Returns dst."""
+    return _am_filter(joint, src, sigma_s, sigma_r, -1, adjust_outliers, dst, dDepth, workspace)
+
+
+class AdaptiveManifoldFilter:
+    """cv::ximgproc::AdaptiveManifoldFilter (EF.hpp:203-245): the parameters as properties, filter(src, dst, joint).
+    UseRNG is False and cannot be switched on (the reference's random start vector is not built; its default is True);
+    PCAIterations is stored, clamped to >= 1, and does not change the result (include/adf_wls.h)."""
+
+    def __init__(self, sigma_s=16.0, sigma_r=0.2, adjust_outliers=False):
+        self._sigma_s, self._sigma_r, self._tree_height, self._pca, self._adjust = float(sigma_s), float(sigma_r), -1, 1, bool(adjust_outliers)
+
+    @staticmethod
+    def create():
+        return AdaptiveManifoldFilter()
+
+    def getSigmaS(self):
+        return self._sigma_s
+
+    def setSigmaS(self, val):
+        self._sigma_s = float(val)
+
+    def getSigmaR(self):
+        return self._sigma_r
+
+    def setSigmaR(self, val):
+        self._sigma_r = float(val)
+
+    def getTreeHeight(self):
+        return self._tree_height
+
+    def setTreeHeight(self, val):
+        self._tree_height = int(val)
+
+    def getPCAIterations(self):
+        return self._pca
+
+    def setPCAIterations(self, val):
+        self._pca = max(1, int(val))
+
+    def getAdjustOutliers(self):
+        return self._adjust
+
+    def setAdjustOutliers(self, val):
+        self._adjust = bool(val)
+
+    def getUseRNG(self):
+        return False
+
+    def setUseRNG(self, val):
+        if val:
+            raise AdfError(_lib.ADF_EBADARG, "%s: UseRNG is not built; the start vector is (0.5, -0.5, 0.5)" % _AM)
+
+    def filter(self, src, dst=None, joint=None, dDepth=-1, workspace=None):
+        return _am_filter(joint, src, self._sigma_s, self._sigma_r, self._tree_height, self._adjust, dst, dDepth, workspace)
+
+    def collectGarbage(self):
+        """Nothing to collect: the object holds no device memory."""
+
+
+def createAMFilter(sigma_s, sigma_r, adjust_outliers=False):
+    """EF.hpp:259: an AdaptiveManifoldFilter with these parameters."""
+    return AdaptiveManifoldFilter(sigma_s, sigma_r, adjust_outliers)
 
 
 def createDisparityWLSFilter(matcher_left):

@@ -1428,6 +1428,96 @@ int adf_rolling_guidance_filter_host(int n_maps,
                                      int depth, int W, int H, int d, double sigma_color, double sigma_space, int num_iter,
                                      int border_type);
 
+/* ---------------- adaptive manifold filter (cv::ximgproc::amFilter / AdaptiveManifoldFilter) ----------------
+ * amFilter(joint, src, dst, sigma_s, sigma_r, adjust_outliers) (EF.hpp:203-280;
+ * modules/ximgproc/src/adaptive_manifold_filter_n.cpp = AMF.cpp): Gastal & Oliveira's adaptive manifolds, an approximation
+ * of a high-dimensional bilateral filter of a map through a gray or BGR view with large kernels (sigma_s 16 .. 64, where
+ * the joint bilateral filter stops at radius 31).  A complete binary tree of 2^height - 1 manifolds; every manifold
+ * weighs the pixels by their distance to it, blurs the weighted map at 1/df of its size and hands its share back.
+ *
+ * This is the library's OWN definition.  The result is bit-exact against the direct NumPy statement tests/am_ref.py fed
+ * with adf_am_plan_host, and identical from run to run.
+ *
+ * Images: n_maps maps of W x H; joint 8-bit with 1 or 3 interleaved channels; src ONE channel of depth ADF_8U, ADF_16S
+ * or ADF_32F; dst one channel of depth dst_depth, independent of src's (the reference gives src's).  dst must not
+ * overlap src or joint.
+ * Plan (host, double arithmetic; AMF.cpp:70-75, 172-184).  df = max(1, 2^floor(log2(min(sigma_s / 4, 256 sigma_r))));
+ *   height = tree_height > 0 ? tree_height : max(2, ceil((floor(log2 sigma_s) - 1) (1 - sigma_r))); the small size
+ *   (sh, sw) = (cvRound(H (1 / df)), cvRound(W (1 / df))), ties to even.  The tree is always complete: nothing on the
+ *   host depends on the data.  Float32 scalars, each rounded once: a(sigma) = (float)exp(-sqrt(2) / sigma) for
+ *   sigma = sigma_s (a_root) and sigma_s / df (a_child); sr2 = (float)(sigma_r / sqrt(2)); arg_w = -0.5f / (sr2 * sr2);
+ *   ss = (float)(sigma_s / df); ratio = (ss / sr2)^2 in float32; ln_a = (float)(-sqrt(2) / ss);
+ *   arg_out = (float)(-0.5 / sigma_r^2); Jtab[v] = (float)(v / 255.0).  adf_am_plan_host returns all of them (jtab: 256
+ *   floats, may be NULL).  Host only -- no device is touched.
+ * Arithmetic.  Every + - * / sqrt is one IEEE float32 operation, rounded once, never contracted; quotient and root are
+ *   correctly rounded; denormals are kept; x / 0 = 0 everywhere (cv::divide's rule).
+ * am_exp(x), x <= 0, from float32 operations alone: t = x * (float)log2(e), n = floor(t + 0.5f), f = t - n, p the Horner
+ *   form of degree 7 in f with c_k = (float)(ln2^k / k!) (multiply, then add), the result p * 2^n with 2^n built from
+ *   bits; 0 where n < -126 (or x is a NaN); am_exp(0) == 1.  At most 1.6 ulp on [-1, 0], relative error 3.9e-6 at
+ *   x = -86 (the argument's rounding).  adf_am_exp_host(x, y, n) evaluates it on the host.
+ * down(P), full -> small: cv::resize INTER_LINEAR by the tap rule of the WLS filter's down-scaled path
+ *   (fx = (float)((dx + 0.5) scale - 0.5), sx = floor(fx), fx -= sx; along a row a tap that would leave it has the
+ *   weights (1, 0); along a column the rows are clamped and the weights stay; row blend S[sx] (1 - fx) + S[sx+1] fx
+ *   first, then the column blend) with scale = df on both axes: for df >= 2 the 2 x 2 pixels at the centre of each cell.
+ *   up(P), small -> full: the same rule with scale_x = sw / W, scale_y = sh / H in double.
+ * sweep(P, ah, av), in place: every row left to right x[j] = x[j] + ah[j-1] (x[j-1] - x[j]), then right to left
+ *   x[j] = x[j] + ah[j] (x[j+1] - x[j]); then every column down and up with av (AMF.cpp's RF pass, one iteration).
+ *   h_filter(P, sigma) = sweep with the constant a(sigma).
+ * Tree.  Root: eta_c = h_filter(J_c, sigma_s) at full size, J_c = Jtab[joint channel c], cluster = every pixel.  Nodes
+ *   in pre-order, the minus child before the plus child; each adds to num and den in that order.  A node at level l:
+ *   1. etaF = eta and eta = down(eta) at the root; etaF = up(eta) below it.
+ *   2. d2 = sum over c, in order, of (etaF_c - J_c)^2; w = am_exp(d2 * arg_w); with adjust_outliers mind = d2 at l = 1,
+ *      else min(mind, d2).
+ *   3. psi = down(f * w), psi0 = down(w), f = (float)src.
+ *   4. ah = am_exp(sqrt((sum over c of (eta_c[j] - eta_c[j+1])^2) * ratio + 1) * ln_a), av likewise between rows;
+ *      sweep(psi, ah, av), sweep(psi0, ah, av).
+ *   5. num = num + up(psi) * w, den = den + up(psi0) * w.
+ *   6. If l < height: X_c = J_c - etaF_c.  One joint channel: o = X_0.  Three: m = 0.5 X_0 + (-0.5) X_1 + 0.5 X_2 in
+ *      that order (the reference's start vector without its random generator), 0 outside the cluster;
+ *      s_c = sum over the pixels of rint((m * X_c) * 2^30) as 64-bit integers (exact, so any order gives it), times
+ *      2^-30 in double; vec = (float)(s / sqrt(s_0^2 + s_1^2 + s_2^2)) in double, 0 if the norm is 0;
+ *      o = vec_0 X_0 + vec_1 X_1 + vec_2 X_2 in that order.  minus = cluster and o < 0, plus = cluster and o >= 0.  Per
+ *      child: tm = 1 - w inside its cluster, 0 outside; tb = h_filter(down(tm), ss);
+ *      eta_c = h_filter(down(tm * J_c), ss) / tb.
+ *   g = num / den; with adjust_outliers alpha = am_exp(mind * arg_out), g = alpha * (g - f) + f.  dst = g for ADF_32F;
+ *   rint(g) (half to even) saturated to the depth for ADF_8U / ADF_16S.
+ * Deviations from the reference, all deliberate: cv::exp is replaced by am_exp; the joint is normalised through Jtab;
+ *   useRNG is false (the reference seeds cv::RNG from the centre pixel; that generator is not part of this library, so
+ *   setUseRNG(true) is refused as not built -- the reference's default is true); num_pca_iterations does not change the
+ *   result (AMF.cpp:759-800 multiplies with the START vector in every iteration, so n iterations give n times one pass
+ *   before normalisation): this definition takes one pass; one-channel sources only; a NULL joint (the reference then
+ *   filters src by itself) is not built.
+ * Refused (ADF_EBADARG, before a device is touched): sigma_s below 1 or not finite; sigma_r outside (0, 1] or not finite
+ *   (the reference's own assert); tree_height 0, below -1 or above ADF_AM_MAX_TREE_HEIGHT, and an automatic height above
+ *   it; sh or sw below 1; a NULL joint, src or dst; joint_channels other than 1 or 3; unknown depths; n_maps, W or H below
+ *   1; and what the other edge-aware filters' shared check refuses, with the same status (alignment, overlap: ADF_EBADARG;
+ *   W*H at or above 2^31, strides, overlapping destination maps, a workspace that is too small: ADF_ESIZE).
+ * Workspace: adf_am_filter_workspace_bytes(n_maps, W, H, joint_channels, sigma_s, sigma_r, tree_height) bytes of 4-byte
+ *   aligned device memory (0 for arguments the calls refuse): per map num, den, mind and the root manifold at full size,
+ *   a byte of cluster bits per pixel, and 4 + 2 height (1 + channels) small planes.  NULL takes library scratch; a
+ *   caller-supplied workspace makes the call capturable into a hipGraph (one chain of launches and at most one memset).
+ * _device: device pointers on the current HIP device, asynchronous on `stream`.  _host: host pointers; copies, runs and
+ * synchronises. */
+#define ADF_AM_MAX_TREE_HEIGHT 8 /* 255 manifolds */
+typedef struct adf_am_plan {
+    int df, height, sh, sw, manifolds;
+    float a_root, a_child, sr2, arg_w, ss, ratio, ln_a, arg_out;
+} adf_am_plan;
+int adf_am_plan_host(double sigma_s, double sigma_r, int tree_height, int W, int H, adf_am_plan* plan, float* jtab);
+int adf_am_exp_host(const float* x, float* y, size_t n);
+size_t adf_am_filter_workspace_bytes(int n_maps, int W, int H, int joint_channels, double sigma_s, double sigma_r, int tree_height);
+int adf_am_filter_device(int n_maps,
+                         const uint8_t* joint, ptrdiff_t joint_stride, ptrdiff_t joint_map_stride, int joint_channels,
+                         const void* src, ptrdiff_t src_stride, ptrdiff_t src_map_stride, int src_depth,
+                         void* dst, ptrdiff_t dst_stride, ptrdiff_t dst_map_stride, int dst_depth,
+                         int W, int H, double sigma_s, double sigma_r, int tree_height, int adjust_outliers,
+                         void* workspace, size_t workspace_bytes, void* stream);
+int adf_am_filter_host(int n_maps,
+                       const uint8_t* joint, ptrdiff_t joint_stride, ptrdiff_t joint_map_stride, int joint_channels,
+                       const void* src, ptrdiff_t src_stride, ptrdiff_t src_map_stride, int src_depth,
+                       void* dst, ptrdiff_t dst_stride, ptrdiff_t dst_map_stride, int dst_depth,
+                       int W, int H, double sigma_s, double sigma_r, int tree_height, int adjust_outliers);
+
 #ifdef __cplusplus
 }
 #endif

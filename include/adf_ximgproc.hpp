@@ -339,6 +339,88 @@ inline Ptr<DTWindowFilter> createDTWindowFilter(const Mat& guide, double sigmaSp
     return Ptr<DTWindowFilter>(new DTWindowFilterImpl(guide, sigmaSpatial, sigmaColor, mode, numIters));
 }
 
+// cv::ximgproc::amFilter(joint, src, dst, sigma_s, sigma_r, adjust_outliers) (EF.hpp:280), createAMFilter(sigma_s, sigma_r,
+// adjust_outliers) (EF.hpp:259) and AdaptiveManifoldFilter (EF.hpp:203-245) on host Mats through the library's host entry,
+// in the library's own definition (adf_am_filter_* in adf_wls.h: a complete tree of manifolds, its own exp, every operation
+// in a stated order).  joint: CV_8UC1 or CV_8UC3, never empty (the reference then filters src by itself: not built); src:
+// CV_8UC1, CV_16SC1 or CV_32FC1 of its size; dst gets src's depth and may be src.  sigma_s >= 1; 0 < sigma_r <= 1, the
+// joint taken as 0 .. 1.  Where this departs from the reference: UseRNG is false and setUseRNG(true) is refused (the
+// reference's default is true); PCAIterations is stored, clamped to >= 1, and does not change the result.
+inline void am_filter(const Mat& joint, const Mat& src, Mat& dst, double sigma_s, double sigma_r, int tree_height, bool adjust_outliers)
+{
+    filter_src("amFilter", src);
+    if (joint.empty()) throw Exception(ADF_EBADARG, "amFilter: joint must not be empty (filtering src by itself is not built)");
+    filter_guide("amFilter", "joint", joint, src);
+    Mat out = filter_out(src, mat_depth(src));
+    check(adf_am_filter_host(1, joint.data, mat_step(joint), 0, mat_channels(joint), src.data, mat_step(src), 0, depth_code(mat_depth(src)),
+                             out.data, mat_step(out), 0, depth_code(mat_depth(src)), src.cols, src.rows, sigma_s, sigma_r, tree_height,
+                             adjust_outliers ? 1 : 0));
+    dst = out;
+}
+inline void amFilter(const Mat& joint, const Mat& src, Mat& dst, double sigma_s, double sigma_r, bool adjust_outliers = false)
+{
+    am_filter(joint, src, dst, sigma_s, sigma_r, -1, adjust_outliers);
+}
+
+class AdaptiveManifoldFilter {
+public:
+    virtual ~AdaptiveManifoldFilter() {}
+    virtual void filter(const Mat& src, Mat& dst, const Mat& joint = Mat()) = 0;
+    virtual void collectGarbage() = 0;
+    static Ptr<AdaptiveManifoldFilter> create();
+    virtual double getSigmaS() const = 0;
+    virtual void setSigmaS(double val) = 0;
+    virtual double getSigmaR() const = 0;
+    virtual void setSigmaR(double val) = 0;
+    virtual int getTreeHeight() const = 0;
+    virtual void setTreeHeight(int val) = 0;
+    virtual int getPCAIterations() const = 0;
+    virtual void setPCAIterations(int val) = 0;
+    virtual bool getAdjustOutliers() const = 0;
+    virtual void setAdjustOutliers(bool val) = 0;
+    virtual bool getUseRNG() const = 0;
+    virtual void setUseRNG(bool val) = 0;
+};
+
+// Holds the parameters alone: the tree is rebuilt from the joint in every call.
+class AdaptiveManifoldFilterImpl : public AdaptiveManifoldFilter {
+    double sigma_s_ = 16.0, sigma_r_ = 0.2;
+    int tree_height_ = -1, pca_iterations_ = 1;
+    bool adjust_outliers_ = false;
+public:
+    void filter(const Mat& src, Mat& dst, const Mat& joint = Mat()) override
+    {
+        am_filter(joint, src, dst, sigma_s_, sigma_r_, tree_height_, adjust_outliers_);
+    }
+    void collectGarbage() override {}
+    double getSigmaS() const override { return sigma_s_; }
+    void setSigmaS(double val) override { sigma_s_ = val; }
+    double getSigmaR() const override { return sigma_r_; }
+    void setSigmaR(double val) override { sigma_r_ = val; }
+    int getTreeHeight() const override { return tree_height_; }
+    void setTreeHeight(int val) override { tree_height_ = val; }
+    int getPCAIterations() const override { return pca_iterations_; }
+    void setPCAIterations(int val) override { pca_iterations_ = val < 1 ? 1 : val; }
+    bool getAdjustOutliers() const override { return adjust_outliers_; }
+    void setAdjustOutliers(bool val) override { adjust_outliers_ = val; }
+    bool getUseRNG() const override { return false; }
+    void setUseRNG(bool val) override
+    {
+        if (val) throw Exception(ADF_EBADARG, "amFilter: UseRNG is not built; the start vector is (0.5, -0.5, 0.5)");
+    }
+};
+
+inline Ptr<AdaptiveManifoldFilter> AdaptiveManifoldFilter::create() { return Ptr<AdaptiveManifoldFilter>(new AdaptiveManifoldFilterImpl()); }
+
+inline Ptr<AdaptiveManifoldFilter> createAMFilter(double sigma_s, double sigma_r, bool adjust_outliers = false)
+{
+    Ptr<AdaptiveManifoldFilter> f = AdaptiveManifoldFilter::create();
+    f->setSigmaS(sigma_s);
+    f->setSigmaR(sigma_r);
+    f->setAdjustOutliers(adjust_outliers);
+    return f;
+}
+
 // cv::ximgproc::jointBilateralFilter(joint, src, dst, d, sigmaColor, sigmaSpace, borderType) (EF.hpp:317) on host Mats
 // through the library's host entry, in the library's own definition (adf_joint_bilateral_filter_* in adf_wls.h: the
 // reference's `_8u` arithmetic in its order of evaluation, widened to CV_16S and CV_32F sources).  joint: CV_8UC1 or
